@@ -10,7 +10,7 @@ compute.c:443) — with no host copies inside the timed region.
 Workloads (BASELINE.json configs):
   N = 1 : configs[2]  4096x4096 Y-only, Q=10, -i 500, weight 0.3, pweight 0.001
           (the configuration the metric "Mpixel-iterations/sec on 4K Y-plane" is quoted on).
-          `other_configs` carries configs[0], configs[1], a configs[4] slice and the 16384x2048 band that is
+          With --full, `other_configs` carries configs[0], configs[1], a configs[4] slice and the 16384x2048 band that is
           the N = 1 point of the N > 1 workload below.
   N > 1 : configs[3]  16384-wide Y-only plane, Q=10, -i 100, row-tiled: 2048 rows per GPU
           (N = 8 is exactly the 16384x16384 config); weak scaling (fixed rows per GPU).  Every engine is
@@ -28,9 +28,9 @@ Workloads (BASELINE.json configs):
                      exchange north_star names), librccl dlopen()ed by the C library;
             rccl   : one process per GPU, the Python harness over torch.distributed / librccl (jpeg2png_amd/tiled.py).
           `value` is the fastest leg whose plane has the same hash as the SAME canvas solved whole on ONE GPU
-          (`other_configs` carries that solve — the strong-scaling denominator — and every other leg, each with
-          `bits_equal_to_the_whole_canvas_solve`), and configs[4] — 256 x 1080p 4:2:0 Q50 -i 100 through the C
-          batch engine over all N GPUs.
+          (`other_configs` carries every other leg, each with `bits_equal_to_the_whole_canvas_solve`, and with
+          --full that solve — the strong-scaling denominator — and configs[4] — 256 x 1080p 4:2:0 Q50 -i 100
+          through the C batch engine over all N GPUs).
   --config batch : configs[4] slice — B x 1080p 4:2:0 Q=50 -i 100 through the C batch API
           (host buffers in, RGB out: PCIe inclusive), images/s and Mpx-it/s.
 
@@ -41,12 +41,20 @@ The JSON also carries
                  8 TB/s HBM peak, i.e. launch gaps and everything else included; `kernel` names the
                  phase kernel with the LOWER per-kernel fraction and `per_kernel` lists both, from
                  HIP events recorded on the solver's stream during the timed region;
-  cpu_baseline : the UNMODIFIED reference (oracle/_ref, built from /root/reference by
-                 oracle/Makefile) — or our C port if that .so is absent — timed on this
+  parity       : the plane the last timed step left behind against the reference's, by digest;
+and, with --full only (everything that takes runs of its own beside the headline):
+  host_to_host, other_configs (N = 1), the batch of configs[4] (N > 1);
+  cpu_baseline : the UNMODIFIED reference (oracle/_ref, built by oracle/Makefile from the
+                 reference sources) — or our C port if that .so is absent — timed on this
                  box's host cores on a bounded sample of the same workload, 1 thread;
   cpu_baseline_all_cores : the same library called from one host thread per core on independent
                  planes — the reference's file-level OpenMP parallelism (jpeg2png.c:330; its
                  in-solver OpenMP gains nothing for a single plane).
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32): the
+solved plane (the whole plane where it fits DUMP_LIMIT_BYTES, else a sample at positions drawn with a fixed
+seed), or the last RGB image of a --config batch step.  The inputs are synthesised from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -60,7 +68,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0            # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0            # MI355X HBM3E peak (AMD's MI355X specification)
 BYTES_GRADIENT = 16              # per canvas pixel per launch (phase A)
 BYTES_PROJECT = 22               # phase B
 BYTES_ITERATION = BYTES_GRADIENT + BYTES_PROJECT
@@ -68,6 +76,7 @@ WEIGHT, PWEIGHT = 0.3, 0.001     # jpeg2png.c:22-23 defaults
 EVENT_PAIR_US = None             # what a bracket of two HIP event records costs by itself (calibrated by the solver)
 RCCL_LEG_TIMEOUT_S = 180         # watchdog of the Python RCCL harness leg of an N > 1 run
 C_LEG_TIMEOUT_S = 120            # ... and of each child process that runs one leg of the C row tiling
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # what --dump-outputs writes at most, all files together
 
 
 def parse():
@@ -75,6 +84,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: host_to_host, other_configs, the batch of an N > 1 run, "
+                         "cpu_baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--config", choices=["headline", "batch"], default="headline")
     ap.add_argument("--size", type=int, default=0, help="override plane width (debug)")
     ap.add_argument("--height", type=int, default=0, help="override plane height (debug, single GPU)")
@@ -93,7 +107,28 @@ def parse():
     ap.add_argument("--nt", type=int, default=-1, help="A/B: non-temporal level 0..3 of the phase kernels (J2P_OPT_NT_GRADIENT); default: the library's policy")
     ap.add_argument("--narrow", type=int, default=-1, help="A/B: 0 = the projection reads int16 coefficients although one byte each would do (J2P_OPT_NARROW_COEFFICIENTS)")
     ap.add_argument("--norm-in-project", type=int, default=-1, help="A/B: final norm tree inside k_project (needs --norm-fold 1)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def output_sample(array, limit):
+    """`array` as float32 if it has at most `limit` elements, else `limit` of its elements (flattened) at positions drawn
+    with a fixed seed and kept in ascending order: the same positions for every run of the same workload"""
+    out = np.ascontiguousarray(array, dtype=np.float32)
+    if out.size <= limit:
+        return out
+    pos = np.sort(np.random.default_rng(0).choice(out.size, limit, replace=False))
+    return out.reshape(-1)[pos]
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: array} as directory/<name>.npy, float32, DUMP_LIMIT_BYTES in all (shared evenly)"""
+    os.makedirs(directory, exist_ok=True)
+    limit = (DUMP_LIMIT_BYTES // len(arrays) - 4096) // 4          # (4096: room for the .npy header)
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), output_sample(array, limit))
 
 
 def _flush_c_stdio():
@@ -399,6 +434,8 @@ def bench_batch(a, j, synth):
         for _ in range(a.steps):
             step()
         dt = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"rgb": ring[(a.batch - 1) % len(ring)]})      # the last image of the last step
     W, H = 1920, 1088
     print(json.dumps({
         "metric": "Mpixel-iterations/sec, batch of 1080p 4:2:0 images (host buffers in, RGB out)",
@@ -612,7 +649,11 @@ def single_gpu(a, j, synth, local_rank):
     px = W * H
     value = px * its * a.steps / elapsed / 1e6
     # the plane the LAST timed step left behind (every step is a whole solve from iteration 0), against the reference's
-    parity = parity_object(plane_digest(solver.download(0)), W, H, its, seed)
+    plane = solver.download(0)
+    parity = parity_object(plane_digest(plane), W, H, its, seed)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"y_plane": plane})
+    del plane
     per_kernel = per_kernel_roofline(px, px, g_ms, p_ms)
     traffic, traffic_src = pmc_traffic(W, H)          # (a shape without committed counters: null)
     roof = roofline_object(value, 1, its, elapsed, a.steps, px, per_kernel, samples, a.timing_every, traffic, traffic_src)
@@ -639,16 +680,16 @@ def single_gpu(a, j, synth, local_rank):
         out["unverified_value"] = out["value"]
         out["value"] = None
     solver.close()
-    if not a.no_host_to_host and not a.size:
+    if a.full and not a.no_host_to_host and not a.size:
         try:
             planes = synth.make_planes(W, H, "444", 10, seed=seed, y_only=True)
             out["host_to_host"] = host_to_host(j, planes, its, elapsed / a.steps * 1e3, device=local_rank)
             del planes
         except Exception as e:          # noqa: BLE001
             out["host_to_host"] = {"error": f"{type(e).__name__}: {e}"}
-    if not a.no_other_configs and not a.size:
+    if a.full and not a.no_other_configs and not a.size:
         out["other_configs"] = other_configs(j, synth)
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"], out["cpu_baseline_all_cores"] = cpu_baseline(W, seed)
     _flush_c_stdio()
     print(json.dumps(out), flush=True)
@@ -725,7 +766,8 @@ def tiled(a, j, synth, rank, world, local_rank, one_device):
         if rank == 0:
             devices = list(range(n_gpus)) if n_gpus > 1 and not one_device else [local_rank] * nband
             spec = {"plane": plane_file, "W": W, "H": H, "quant": [int(q) for q in np.asarray(whole_plane.quant_table).reshape(-1)],
-                    "its": its, "devices": devices, "warmup": a.warmup, "steps": a.steps, "timing_every": a.timing_every}
+                    "its": its, "devices": devices, "warmup": a.warmup, "steps": a.steps, "timing_every": a.timing_every,
+                    "dump": f"{tag}_{name}_out" if a.dump_outputs else None}
             env = dict(os.environ)
             env.pop("J2P_TILED_EXCHANGE", None)
             env.pop("J2P_TILED_WAIT", None)
@@ -765,7 +807,7 @@ def tiled(a, j, synth, rank, world, local_rank, one_device):
                 picker = [ln.strip() for ln in r.stderr.splitlines() if ln.startswith("jpeg2png_amd: row tiling")]
                 legs[name] = {"elapsed": res["elapsed"], "g_ms": res["g_ms"], "p_ms": res["p_ms"], "samples": res["samples"], "split": False,
                               "host_cpu_s": res["host_cpu_s"], "digest": res["digest"], "exchange": how,
-                              "create_s": res.get("create_s"), "picker_log": picker, "rccl": res.get("rccl"),
+                              "create_s": res.get("create_s"), "picker_log": picker, "rccl": res.get("rccl"), "dump": spec["dump"],
                               "parallelism": (f"row-tiled x{nband}: C engine (j2p_tiled), one process drives all GPUs, one host thread per "
                                               f"band; exchange '{how}': {what}")}
             except subprocess.TimeoutExpired:
@@ -936,9 +978,22 @@ def tiled(a, j, synth, rank, world, local_rank, one_device):
         ranks.barrier()                 # a rank that failed alone leaves the others in a collective: the watchdog ends that
         watchdog.cancel()
     finish()
+    if rank == 0 and a.dump_outputs:
+        # the plane of the leg that became `value`, as its child process wrote it; the others' are dropped
+        import shutil
+        src = legs.get(state["out"]["config"]["engine"], {}).get("dump")
+        if src and os.path.exists(os.path.join(src, "y_plane.npy")):
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            shutil.move(os.path.join(src, "y_plane.npy"), os.path.join(a.dump_outputs, "y_plane.npy"))
+        else:
+            print(f"bench: --dump-outputs: leg {state['out']['config']['engine']} leaves no plane on rank 0; nothing written",
+                  file=sys.stderr, flush=True)
+        import glob
+        for d in glob.glob(f"{tag}_*_out"):
+            shutil.rmtree(d, ignore_errors=True)
 
     # ---- the same canvas on ONE GPU, configs[4] over all GPUs, the CPU baseline (rank 0) ----
-    if rank == 0 and state["out"] is not None and not a.no_other_configs:
+    if rank == 0 and state["out"] is not None and a.full and not a.no_other_configs:
         extra = []
         if whole is not None and "error" not in whole:
             r = {k: v for k, v in whole.items() if k != "digest"}
@@ -958,7 +1013,7 @@ def tiled(a, j, synth, rank, world, local_rank, one_device):
         except Exception as e:          # noqa: BLE001
             extra.append({"config": "configs[4] batch", "error": f"{type(e).__name__}: {e}"})
         state["out"]["other_configs"] += extra
-    if rank == 0 and state["out"] is not None and not a.no_cpu_baseline:
+    if rank == 0 and state["out"] is not None and a.full and not a.no_cpu_baseline:
         state["out"]["cpu_baseline"], state["out"]["cpu_baseline_all_cores"] = cpu_baseline(W, seed)
     ranks.barrier()
     if rank == 0:
@@ -993,8 +1048,12 @@ def leg_child(spec_json):
             elapsed = time.perf_counter() - t0
             g_ms, p_ms, samples = eng.kernel_times()
             eng.enable_timing(0)
+            plane_out = t.download(0)
             out = {"elapsed": elapsed, "g_ms": g_ms, "p_ms": p_ms, "samples": samples, "host_cpu_s": round(t.host_cpu_seconds(), 3),
-                   "exchange": t.exchange(), "digest": plane_digest(t.download(0)), "create_s": round(create_s, 3)}
+                   "exchange": t.exchange(), "digest": plane_digest(plane_out), "create_s": round(create_s, 3)}
+            if spec.get("dump"):
+                dump_outputs(spec["dump"], {"y_plane": plane_out})
+            del plane_out
             if out["exchange"] == "rccl":
                 out["rccl"] = {"ncclGetVersion": j.rccl_version(), "nranks_of_ncclCommInitAll": len(spec["devices"]),
                                "devices": spec["devices"]}

@@ -23,6 +23,8 @@ def build(ref=True):
         subprocess.run(["make", "-s", "-C", _HERE, "ref-cli"], check=False)
         # ... and the same program with compute.o replaced by libjpeg2png_amd.so (the drop-in proof)
         subprocess.run(["make", "-s", "-C", _HERE, "ref-dropin"], check=False)
+        # the struct layouts of the reference's headers, alone and under ours (tests/test_capi.py)
+        subprocess.run(["make", "-s", "-C", _HERE, "ref-layout"], check=False)
 
 
 class _OPlane(ctypes.Structure):

@@ -105,3 +105,39 @@ def test_roofline_object_says_which_fraction_is_which():
     assert abs(r["frac"] - 38 * 143000.0e6 / 8e12) < 1e-3 and r["traffic"] == 676000000 and r["traffic_source"] == "profiles/x.json"
     prof, src = bench.rocprof_kernel_us()
     assert prof and src and os.path.exists(os.path.join(ROOT, src)) and 30 < prof["k_gradient"] < 80 and 40 < prof["k_project"] < 80
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the plain line and --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------
+def test_plain_run_measures_only_the_headline_and_steps_are_honoured(monkeypatch):
+    import bench
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dumped_outputs_are_float32_bounded_and_the_same_positions_every_run(tmp_path):
+    import numpy as np
+    import bench
+    small = np.arange(48 * 64, dtype=np.float32).reshape(48, 64)
+    plane = np.random.default_rng(5).standard_normal((4096, 4096), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "y_plane": plane})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "y_plane": plane})
+    total = 0
+    for name in ("small", "y_plane"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)          # what fits is written whole
+    sample = np.load(tmp_path / "a" / "y_plane.npy")
+    assert sample.ndim == 1 and 0.9 * bench.DUMP_LIMIT_BYTES / 2 / 4 < sample.size < plane.size
+    assert np.isin(sample, plane).all()

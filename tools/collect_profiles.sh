@@ -24,7 +24,7 @@ python $R/tools/pmc_summary.py --about "rocprofv3 on MI355X, $TAG: separate --ke
         "$OUT/${TAG}_pmc_fetch" "$OUT/${TAG}_pmc_write" "$OUT/${TAG}_pmc_sq" > "$OUT/${TAG}_pmc_summary.json"
 find "$OUT" -name '*.csv' -size +2M -delete
 find "$OUT" -name '*_agent_info.csv' -delete
-python $R/bench.py --steps 3 --warmup 1 > "$OUT/${TAG}_bench_n1.log" 2>&1
+python $R/bench.py --steps 3 --warmup 1 --full > "$OUT/${TAG}_bench_n1.log" 2>&1
 grep '^{' "$OUT/${TAG}_bench_n1.log" | tail -1 > "$OUT/${TAG}_bench_n1.json"
 cat "$OUT/${TAG}_bench_kernel_stats.csv" | head -8
 cat "$OUT/${TAG}_bench_n1.json"

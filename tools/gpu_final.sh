@@ -14,9 +14,9 @@ bash tools/collect_profiles.sh $TAG 2>&1 | tail -6
 import json; d=json.load(open('gpurun_out/${TAG}_bench_driver_shape.json')); r=d['roofline']; h=d.get('host_to_host',{})
 print('driver shape:', d['value'], d['ms_per_step'], r['frac'], d['parity']['bit_identical'], h.get('ms_per_call'), h.get('ms_per_call_in_call_order'), [o.get('Mpx_it_per_s') for o in d.get('other_configs',[])])"
 # two ranks on this box's one GPU (gloo): the driver's --gpus N launch shape, rank 0 driving two bands, both C schedules
-( J2P_BENCH_ONE_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --size 4096 ) > $O/bench_2ranks.log 2>&1; echo "2-rank bench rc=$?"; grep '^{' $O/bench_2ranks.log | tail -1 > gpurun_out/${TAG}_bench_2ranks_1gpu_gloo.json; cut -c1-400 gpurun_out/${TAG}_bench_2ranks_1gpu_gloo.json
+( J2P_BENCH_ONE_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --size 4096 --full ) > $O/bench_2ranks.log 2>&1; echo "2-rank bench rc=$?"; grep '^{' $O/bench_2ranks.log | tail -1 > $O/../${TAG}_bench_2ranks_1gpu_gloo.json; cut -c1-400 $O/../${TAG}_bench_2ranks_1gpu_gloo.json
 # 8 bands of 16384x2048 on one GPU (C engine, both schedules; strong-scaling denominator; 256-image batch)
-( timeout 600 python bench.py --force-tiled --bands 8 --steps 2 --warmup 1 --no-cpu-baseline ) 2>&1 | grep '^{' | tail -1 > gpurun_out/${TAG}_bench_tiled_8bands_1gpu.json; cut -c1-300 gpurun_out/${TAG}_bench_tiled_8bands_1gpu.json
+( timeout 600 python bench.py --force-tiled --bands 8 --steps 2 --warmup 1 --no-cpu-baseline --full ) 2>&1 | grep '^{' | tail -1 > $O/../${TAG}_bench_tiled_8bands_1gpu.json; cut -c1-300 $O/../${TAG}_bench_tiled_8bands_1gpu.json
 # the RCCL exchange of the C engine with one band as its own neighbour (ncclCommInitAll, ncclAllGather, grouped
 # ncclSend / ncclRecv on real hardware), against the same rows solved whole
 ( J2P_LIBRARY=jpeg2png_amd/libjpeg2png_amd_exp.so J2P_TILED_EXCHANGE=rccl J2P_TILED_SELF_NEIGHBOURS=1 timeout 300 python - <<PY

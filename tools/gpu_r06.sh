@@ -162,7 +162,7 @@ PY
   ( cd /tmp; rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/r06_batch_trace -- python $GRAFT_REPO_ROOT/bench.py --config batch --steps 1 --warmup 1 --batch 32 > $GRAFT_REPO_ROOT/$O/r06_batch_trace.log 2>&1 )
   F=$(find $O/r06_batch_trace -name '*kernel_trace.csv' | head -1); python tools/batch_occupancy.py $F 64 | tee $O/r06_batch_occupancy.json; rm -rf $O/r06_batch_trace
   grep '^{' $O/r06_batch_trace.log | tail -1 | cut -c1-300
-  ( J2P_BENCH_ONE_DEVICE=0 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --size 4096 ) > $O/r06_bench_2ranks.log 2>&1; echo "2-rank bench rc=$?"; grep '^{' $O/r06_bench_2ranks.log | tail -1 > $O/r06_bench_2ranks_1gpu_gloo.json; cut -c1-1500 $O/r06_bench_2ranks_1gpu_gloo.json; grep "^bench:" $O/r06_bench_2ranks.log | head -5
+  ( J2P_BENCH_ONE_DEVICE=0 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --size 4096 --full ) > $O/r06_bench_2ranks.log 2>&1; echo "2-rank bench rc=$?"; grep '^{' $O/r06_bench_2ranks.log | tail -1 > $O/r06_bench_2ranks_1gpu_gloo.json; cut -c1-1500 $O/r06_bench_2ranks_1gpu_gloo.json; grep "^bench:" $O/r06_bench_2ranks.log | head -5
   ;;
 l)
   # double items at the start of the launch: parity, then shares by size (timing)

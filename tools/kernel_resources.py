@@ -5,16 +5,19 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from jpeg2png_amd.buildlib import HIP_FLAGS, INCLUDE, CSRC  # noqa: E402
 
-out = "/tmp/j2p_res.s"
+tmp = tempfile.TemporaryDirectory()                 # (a private directory: runs side by side, or by other users, do not collide)
+out = os.path.join(tmp.name, "j2p_res.s")
 cmd = ["/opt/rocm/bin/hipcc", *[f for f in HIP_FLAGS if f != "-Wall"], *sys.argv[1:], "-I", INCLUDE, "-I", CSRC,
        "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, "j2p_solver.hip")]
 subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 md = open(out).read()
+tmp.cleanup()
 md = md[md.index("amdhsa.kernels"):]
 for b in md.split("  - .agpr_count")[1:]:
     f = {k: re.search(r"\.%s:\s+(\S+)" % k, b).group(1) for k in
