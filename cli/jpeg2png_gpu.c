@@ -120,7 +120,8 @@ static void jpeg_message(j_common_ptr info)
         pthread_mutex_unlock(&ui_lock);
 }
 
-static void read_coefficients(FILE *in, struct jpeg_in *jp)
+/* zoom: the integer zoom factor (-z) the sampling factors are multiplied by later on, for the memory guard */
+static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom)
 {
         struct jpeg_decompress_struct d;
         struct jpeg_error_mgr err;
@@ -152,7 +153,7 @@ static void read_coefficients(FILE *in, struct jpeg_in *jp)
                 k->h_samp = d.max_v_samp_factor / ci->v_samp_factor;
                 if(k->h / 8 != (jp->h / k->h_samp + 7) / 8) { die("jpeg invalid coef h size"); }
                 if(k->w / 8 != (jp->w / k->w_samp + 7) / 8) { die("jpeg invalid coef w size"); }
-                if(SIZE_MAX / k->h / k->w / k->h_samp / k->w_samp < 6) { die("jpeg is too big to fit in memory"); }
+                if(SIZE_MAX / k->h / k->w / (k->h_samp * zoom) / (k->w_samp * zoom) < 6) { die("jpeg is too big to fit in memory"); }
                 k->data = malloc(sizeof(int16_t) * (size_t)k->w * k->h);
                 if(!k->data) { die("could not allocate memory for coefs"); }
                 int16_t *dst = k->data;
@@ -200,6 +201,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         bool joint, quiet;
+        unsigned zoom;          /* -z: integer zoom factor 1..4 (every sampling factor times zoom, output zoom times the size) */
         bool tile;              /* fewer files than GPUs: every image row-tiled over its share of them */
         unsigned nfiles;
         FILE *csv;
@@ -260,8 +262,24 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         FILE *in = fopen(infile, "rb");
         if(!in) { die_perror("could not open input file `%s`", infile); }
         struct jpeg_in jp;
-        read_coefficients(in, &jp);
+        read_coefficients(in, &jp, o->zoom);
         fclose(in);
+        /* zooming by z = the same solve with every component's sampling factors times z (compute.c:407-416): the
+         * canvas, and the image written, are z times as wide and as high.  The library's canvas height limit is
+         * 65536 rows; refused here, before any GPU work */
+        const unsigned zoom = o->zoom;
+        {
+                unsigned long long cw = 0, chh = 0;
+                for(int c = 0; c < 3; c++) {
+                        const unsigned long long w = (unsigned long long)jp.c[c].w * jp.c[c].w_samp * zoom;
+                        const unsigned long long h = (unsigned long long)jp.c[c].h * jp.c[c].h_samp * zoom;
+                        if(w > cw) { cw = w; }
+                        if(h > chh) { chh = h; }
+                }
+                if(cw > 65536 || chh > 65536) {
+                        die("zoomed canvas of `%s` is %llux%llu pixels: at most 65536 per side", infile, cw, chh);
+                }
+        }
 
         struct job_ctx ctx = {o, infile};
         j2p_job job;
@@ -270,8 +288,8 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         for(int c = 0; c < 3; c++) {
                 job.planes[c].w = jp.c[c].w;
                 job.planes[c].h = jp.c[c].h;
-                job.planes[c].w_samp = jp.c[c].w_samp;
-                job.planes[c].h_samp = jp.c[c].h_samp;
+                job.planes[c].w_samp = jp.c[c].w_samp * zoom;
+                job.planes[c].h_samp = jp.c[c].h_samp * zoom;
                 job.planes[c].data = jp.c[c].data;
                 job.planes[c].fdata = NULL;                             /* decoded on the device */
                 job.planes[c].quant_table = jp.c[c].quant;
@@ -295,9 +313,9 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 job.tile_count = (index + 1) * (unsigned)o->ndev / o->nfiles - job.tile_first;
         }
         job.out_bits = o->png_bits;
-        job.out_w = jp.w;
-        job.out_h = jp.h;
-        size_t bytes = (size_t)jp.w * jp.h * 3 * (o->png_bits / 8);
+        job.out_w = jp.w * zoom;
+        job.out_h = jp.h * zoom;
+        size_t bytes = (size_t)job.out_w * job.out_h * 3 * (o->png_bits / 8);
         uint8_t *pixels = malloc(bytes);
         if(!pixels) { die("could not allocate image data"); }
         job.out_rgb = pixels;
@@ -312,7 +330,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         for(int c = 0; c < 3; c++) { free(jp.c[c].data); }
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
-        write_rgb_png(out, jp.w, jp.h, o->png_bits, pixels);
+        write_rgb_png(out, job.out_w, job.out_h, o->png_bits, pixels);
         fclose(out);
         free(pixels);
 }
@@ -354,6 +372,7 @@ static void usage(void)
                "  -s, --separate-components    optimise Y, Cb, Cr independently (three GPU streams)\n"
                "  -t, --threads N              input files processed concurrently (default: online cores)\n"
                "  -1, --16-bits-png            16-bit PNG\n"
+               "  -z, --zoom N                 upscale N times (1..4) while removing the artifacts (default 1)\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -370,15 +389,15 @@ int main(int argc, char **argv)
                 {"threads", required_argument, NULL, 't'}, {"quiet", no_argument, NULL, 'q'},
                 {"separate-components", no_argument, NULL, 's'}, {"16-bits-png", no_argument, NULL, '1'},
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
-                {"second-order-weight", required_argument, NULL, 'w'}, {NULL, 0, NULL, 0}};
+                {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .joint = true, .quiet = false, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
-        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL;
+                            .png_bits = 8, .joint = true, .quiet = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -391,6 +410,7 @@ int main(int argc, char **argv)
                 case 'i': i_arg = optarg; break;
                 case 'p': p_arg = optarg; break;
                 case 'w': w_arg = optarg; break;
+                case 'z': z_arg = optarg; break;
                 default: help = true; break;
                 }
         }
@@ -417,6 +437,12 @@ int main(int argc, char **argv)
                 if(n == 3) { if(o.joint) { die("different iteration counts are only possible when using separated components"); } }
                 else if(n == 1) { o.iterations[1] = o.iterations[2] = o.iterations[0]; }
                 else { die("invalid number of iterations"); }
+        }
+        if(z_arg) {
+                char *end = NULL;
+                const unsigned long z = strtoul(z_arg, &end, 10);
+                if(end == z_arg || *end != '\0' || z_arg[0] == '-' || z < 1 || z > 4) { die("invalid zoom factor"); }
+                o.zoom = (unsigned)z;
         }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);

@@ -56,6 +56,14 @@ typedef struct j2p_plane {
         const uint16_t *quant_table;/* 64 entries, natural order, all non-zero (jpeg.c:41-46) */
 } j2p_plane;
 
+/* Zooming (upscaling while deblocking) by an integer s: multiply w_samp and h_samp of EVERY plane by s, and (j2p_job)
+ * set out_w / out_h to s times the image size.  The canvas is then s times as wide and as high (compute.c:407-416), x_0
+ * the replicated planes (compute.c:295-309), and the result the smoothest image whose means over each coefficient's
+ * s*w_samp x s*h_samp footprint re-encode to the given coefficients (compute.c:334-404) — the reference's compute() on
+ * the same factors, bit for bit.  Limits: s in 1..4 (what the command-line driver and the Python binding accept; the
+ * wide-footprint projection path covers footprints 3, 4, 6 and 8 columns wide, others take the generic one), and the
+ * canvas height at most 65536 rows, as for any input. */
+
 /* Row band of the canvas this solver owns, in canvas rows.  {0,0} = whole canvas.
  * row_begin/row_end must be multiples of lcm(8*h_samp) over channels and of
  * J2P_TILE_ROWS so that no DCT block and no gradient tile straddles two GPUs. */
@@ -117,9 +125,16 @@ void j2p_pool_trim(void);
 #define J2P_OPT_NARROW_COEFFICIENTS 7 /* 1 (default): a channel whose quantised coefficients all lie in [-127, 127] (found at create)
                                      keeps them resident as one byte each and the projection reads those: 21 instead of
                                      22 bytes per pixel; 0: the int16 form (jpeg2png.h:14) for every channel — same floats, same bits */
+#define J2P_OPT_WIDE_FOOTPRINT 8  /* 1 (default): a channel whose footprint is 3, 4, 6 or 8 canvas columns wide (any rows: zoomed
+                                     channels, see "Zooming" at j2p_plane) is projected by the wide-footprint path wherever its strip
+                                     lies inside canvas and coverage — except in the one-launch projection of small canvases with
+                                     several samplings (J2P_OPT_MIXED_PROJECT); 0: the generic path for those channels — same bits */
 int j2p_solver_debug_option(j2p_solver *s, int option, int value);
 /* bytes per quantised coefficient the projection kernel reads for channel c: 1 or 2 (J2P_OPT_NARROW_COEFFICIENTS) */
 int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *bytes);
+/* *on = 1 when the interior strips of channel c take the wide-footprint projection path in an unlogged run (J2P_OPT_WIDE_FOOTPRINT,
+ * J2P_OPT_MIXED_PROJECT), else 0 */
+int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on);
 
 /* The checked build (the analogue of the reference's DEBUG=1, whose pixel indexer p() asserts every access,
  * utils.h:68-81): compiled with -DJ2P_DEBUG, every global load and store of the two phase kernels is compared

@@ -84,10 +84,12 @@ C_ABI_SYMBOLS = [
     "j2p_batch_create", "j2p_batch_destroy", "j2p_batch_submit", "j2p_batch_wait",
     "compute", "j2p_compute", "j2p_compute_tiled", "j2p_compute_timing", "j2p_debug_fail_run_after", "j2p_solver_launches_per_iteration", "j2p_solver_timing_overhead",
     "j2p_debug_build", "j2p_debug_grad_items", "j2p_experiments_build", "j2p_solver_debug_violations", "j2p_solver_trace", "j2p_division_exhaustive",
-    "j2p_solver_coefficient_bytes",
+    "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint",
 ]
 J2P_OPT_NORM_FOLD, J2P_OPT_JOINT_INWAVE, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 2, 4, 5, 6
 J2P_OPT_NARROW_COEFFICIENTS = 7
+J2P_OPT_WIDE_FOOTPRINT = 8
+ZOOM_MAX = 4
 
 _lib = None
 
@@ -420,6 +422,12 @@ class Solver:
         _check(self._lib.j2p_solver_coefficient_bytes(self._h, int(c), ctypes.byref(n)))
         return n.value
 
+    def wide_footprint(self, c=0):
+        """True when the interior strips of channel c take the wide-footprint projection path (J2P_OPT_WIDE_FOOTPRINT)"""
+        n = ctypes.c_uint()
+        _check(self._lib.j2p_solver_wide_footprint(self._h, int(c), ctypes.byref(n)))
+        return bool(n.value)
+
     def debug_option(self, option, value):
         """schedule switches (J2P_OPT_*): speed only, never results"""
         _check(self._lib.j2p_solver_debug_option(self._h, int(option), int(value)))
@@ -717,6 +725,22 @@ def compute_c(planes, weight, pweight, iterations, device=0, repeat=1, splits=No
                 libc.free(coefs[c].fdata)              # free_simd, jpeg2png.c:169
                 libc.free(coefs[c].data)
     return outs, seconds
+
+
+def zoomed(planes, s):
+    """The planes of an image zoomed by the integer factor s (1..4): copies whose sampling factors are s times the
+    given ones.  The solve of those is the smoothest image s times as wide and as high whose block means re-encode to
+    the same coefficients (compute.c:295-309, 334-404 with every footprint s times larger).  Solver, TiledSolver,
+    compute() and Batch.submit(..., width=s*w, height=s*h) take them as they are."""
+    import copy
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 1 <= int(s) <= ZOOM_MAX:
+        raise J2PError(f"zoom factor must be an integer in 1..{ZOOM_MAX}, not {s!r}")
+    out = []
+    for p in planes:
+        q = copy.copy(p)
+        q.w_samp, q.h_samp = p.w_samp * int(s), p.h_samp * int(s)
+        out.append(q)
+    return out
 
 
 def compute(planes, weight, pweight, iterations, log=False, device=0):

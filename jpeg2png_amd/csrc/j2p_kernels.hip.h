@@ -2176,8 +2176,157 @@ __device__ __forceinline__ void sub_store_residual(const ChanDev &k, size_t base
         }
 }
 
+// Phase B front/back end for a subsampled channel with a WIDE footprint — WS = 3, 4, 6 or 8 canvas columns per
+// coefficient, any number hs of canvas rows (run time): what zooming makes of every channel (x2 of 4:2:0 chroma is 4 x 4,
+// x3 is 3 x 3 and 6 x 6, x4 is 4 x 4 and 8 x 8).  The strip lies wholly inside canvas and coverage, as for SubTile.
+// A lane owns WS contiguous floats of each of its 8 hs rows, loaded and stored as one or two dwordx4 (WS 4, 8), dwordx2
+// (6) or dwords (3).  8 hs x WS stepped pixels do not fit in registers (4 x 4: 128), so the front end keeps only the
+// eight means and leaves the stepped pixels in x_{k+1}'s own place (k.xprev, whose x_{k-1} value each lane has just
+// read); the back end reads them back — 20 bytes per pixel over the two passes instead of 28 for stepping every pixel
+// twice (-DJ2P_WIDE_RESTEP=1, the other candidate: DESIGN.md section 11).  Rows: a loop at run time; columns and the
+// eight block rows: compile time (no register array indexed at run time).
+#ifndef J2P_WIDE_RESTEP
+#define J2P_WIDE_RESTEP 0
+#endif
+template <int WS>
+__device__ __forceinline__ void wide_load(const float *p, float (&v)[WS])
+{
+        if constexpr(WS % 4 == 0) {
+#pragma unroll
+                for(int i = 0; i < WS; i += 4) {
+                        const float4 t = *reinterpret_cast<const float4 *>(p + i);
+                        v[i] = t.x;
+                        v[i + 1] = t.y;
+                        v[i + 2] = t.z;
+                        v[i + 3] = t.w;
+                }
+        } else if constexpr(WS % 2 == 0) {
+#pragma unroll
+                for(int i = 0; i < WS; i += 2) {
+                        const float2 t = *reinterpret_cast<const float2 *>(p + i);
+                        v[i] = t.x;
+                        v[i + 1] = t.y;
+                }
+        } else {
+#pragma unroll
+                for(int i = 0; i < WS; i++) { v[i] = p[i]; }
+        }
+}
+template <int WS>
+__device__ __forceinline__ void wide_store(float *p, const float (&v)[WS])
+{
+        if constexpr(WS % 4 == 0) {
+#pragma unroll
+                for(int i = 0; i < WS; i += 4) { *reinterpret_cast<float4 *>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]); }
+        } else if constexpr(WS % 2 == 0) {
+#pragma unroll
+                for(int i = 0; i < WS; i += 2) { *reinterpret_cast<float2 *>(p + i) = make_float2(v[i], v[i + 1]); }
+        } else {
+#pragma unroll
+                for(int i = 0; i < WS; i++) { p[i] = v[i]; }
+        }
+}
+
+// the WS pixels of one canvas row at `off`, stepped as stepped() steps each (compute.c:435, 213); the short division
+// where the wavefront's numerators pass the screen (same bits as `/`)
+template <int WS>
+__device__ __forceinline__ void wide_step_row(const ChanDev &k, size_t off, float factor, float step, float norm, bool fast, float rn,
+                                              float (&y)[WS])
+{
+        float gv[WS], xc[WS], xp[WS];
+        J2P_CHK(k, grad, k.grad + off, 4 * WS, 215);
+        J2P_CHK(k, x_own[0], k.xcur + off, 4 * WS, 216);
+        J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 217);
+        wide_load<WS>(k.grad + off, gv);
+        wide_load<WS>(k.xcur + off, xc);
+        wide_load<WS>(k.xprev + off, xp);
+#pragma unroll
+        for(int j = 0; j < WS; j++) { y[j] = xc[j] + factor * (xc[j] - xp[j]); }         // compute.c:435
+        if(norm == 0.f) { return; }                                                       // compute.c:212
+        NumScreen scr;
+#pragma unroll
+        for(int j = 0; j < WS; j += 2) { scr.add(v2f{gv[j], gv[j + 1 < WS ? j + 1 : j]}); }
+        if(fast && __builtin_amdgcn_ballot_w64(scr.suspect()) == 0) {
+                const v2f nn = v2f{norm, norm}, rr = v2f{rn, rn};
+#pragma unroll
+                for(int j = 0; j < WS; j += 2) {
+                        const v2f q = div_exact_recip(v2f{gv[j], gv[j + 1 < WS ? j + 1 : j]}, nn, rr);
+                        y[j] = y[j] - step * q.x;                                        // compute.c:213
+                        if(j + 1 < WS) { y[j + 1] = y[j + 1] - step * q.y; }
+                }
+        } else {
+#pragma unroll
+                for(int j = 0; j < WS; j++) { y[j] = y[j] - step * (gv[j] / norm); }
+        }
+}
+
+// front end: the eight block means of the lane's coefficient column (compute.c:348-358: sy outer, sx inner, from 0.f)
+template <int WS>
+__device__ __forceinline__ void wide_load_step_mean(const ChanDev &k, size_t base, unsigned W, unsigned hs, float factor, float step,
+                                                    float norm, float (&mean)[8])
+{
+        const bool fast = den_ok(norm);
+        const float rn = fast ? 1.f / norm : 0.f;                             // correctly rounded: what div_exact_recip needs
+        const float cnt = (float)(WS * hs);
+#pragma unroll
+        for(int r = 0; r < 8; r++) {
+                float m = 0.f;
+                for(unsigned sy = 0; sy < hs; sy++) {
+                        const size_t off = base + (size_t)(r * hs + sy) * W;
+                        float y[WS];
+                        wide_step_row<WS>(k, off, factor, step, norm, fast, rn, y);
+#pragma unroll
+                        for(int sx = 0; sx < WS; sx++) { m += y[sx]; }
+#if !J2P_WIDE_RESTEP
+                        J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 218);
+                        wide_store<WS>(k.xprev + off, y);                     // staged for the back end
+#endif
+                }
+                mean[r] = m / cnt;                                            // compute.c:359
+        }
+}
+
+// back end: (stepped - old mean) + new mean (compute.c:365, 398), band-edge rows also into the neighbours' halo rows
+template <int WS>
+__device__ __forceinline__ void wide_store_residual(const ChanDev &k, size_t base, unsigned W, unsigned hs, float factor, float step,
+                                                    float norm, const float (&mean_old)[8], const float (&mean_new)[8],
+                                                    float *halo_up, float *halo_down)
+{
+#if J2P_WIDE_RESTEP
+        const bool fast = den_ok(norm);
+        const float rn = fast ? 1.f / norm : 0.f;
+#else
+        (void)factor; (void)step; (void)norm;
+#endif
+#pragma unroll
+        for(int r = 0; r < 8; r++) {
+                for(unsigned sy = 0; sy < hs; sy++) {
+                        const unsigned row = r * hs + sy;
+                        const size_t off = base + (size_t)row * W;
+                        float y[WS], o[WS];
+#if J2P_WIDE_RESTEP
+                        wide_step_row<WS>(k, off, factor, step, norm, fast, rn, y);
+#else
+                        J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 219);
+                        wide_load<WS>(k.xprev + off, y);
+#endif
+#pragma unroll
+                        for(int sx = 0; sx < WS; sx++) {
+                                const float res = y[sx] - mean_old[r];                   // compute.c:365
+                                o[sx] = res + mean_new[r];                               // compute.c:398
+                        }
+                        J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 220);
+                        wide_store<WS>(k.xprev + off, o);
+                        // (the strip covers whole block rows of the band: its rows 0, 1 / 8 hs - 2, 8 hs - 1 are the band's)
+                        if(row < (unsigned)kHalo && halo_up) { peer_store_ws<WS>(halo_up + (size_t)row * W, o); }
+                        if(row + kHalo >= 8 * hs && halo_down) { peer_store_ws<WS>(halo_down + (size_t)(row + kHalo - 8 * hs) * W, o); }
+                }
+        }
+}
+
 // WS, HS: the subsampling this instantiation has a register-resident fast path for
-// (1,1 = full-resolution channel; 0,0 = any other sampling, generic path only).  Strips that
+// (1,1 = full-resolution channel; WS,0 = WS in 3, 4, 6, 8 columns by any rows, the wide-footprint path;
+// 0,0 = any other sampling, generic path only).  Strips that
 // stick out of the canvas or of the channel's coverage always take the generic path.
 struct __attribute__((aligned(16))) ProjShared {
         float tp[4 * kTpWave];
@@ -2335,11 +2484,17 @@ __device__ __forceinline__ void project_strip(const ProjArgs &a, ProjShared &sh)
                              (sx * 64 + 64) * ws <= W && cy0 + 8 <= k.ch && ly0 + 8 * hs <= a.geo.rows;
         const size_t sub_base = (size_t)ly0 * W + (size_t)cx * ws;
         SubTile<(kSub ? WS : 1), (kSub ? HS : 1)> tile;
+        // wide footprint (zoomed channels): the same strips, the stepped pixels staged in memory
+        constexpr bool kWide = WS >= 3 && HS == 0;
+        const bool fullwide = kWide && ws == (unsigned)WS && sx * 64 + 64 <= k.cw && (sx * 64 + 64) * ws <= W && cy0 + 8 <= k.ch &&
+                              ly0 + 8 * hs <= a.geo.rows;
 
         float v[8];
         float st1[8];                                                   // stepped pixels of a `full && resample1` strip
         if(fullsub) {
                 sub_load_step_mean<(kSub ? WS : 1), (kSub ? HS : 1)>(k, sub_base, W, a.factor, a.step, norm, tile, v);
+        } else if(fullwide) {
+                if constexpr(kWide) { wide_load_step_mean<WS>(k, sub_base, W, hs, a.factor, a.step, norm, v); }
         } else if(full) {
                 v2f y2[4], g2[4];
                 NumScreen scr;
@@ -2555,6 +2710,12 @@ __device__ __forceinline__ void project_strip(const ProjArgs &a, ProjShared &sh)
                         sub_store_residual<(kSub ? WS : 1), (kSub ? HS : 1)>(k, sub_base, W, tile, mean_old, v,
                                                                              push_up ? push_up + (size_t)cx * ws : nullptr,
                                                                              push_down ? push_down + (size_t)cx * ws : nullptr);
+                } else if(fullwide) {
+                        if constexpr(kWide) {
+                                wide_store_residual<WS>(k, sub_base, W, hs, a.factor, a.step, norm, mean_old, v,
+                                                        push_up ? push_up + (size_t)cx * ws : nullptr,
+                                                        push_down ? push_down + (size_t)cx * ws : nullptr);
+                        }
                 } else if(full) {
                         // full && resample1: residual (x - mean) + new mean, lane = column again
                         const size_t base = (size_t)ly0 * W + cx;
@@ -2644,7 +2805,9 @@ __global__ __launch_bounds__(256, (J2P_PROJECT_WAVES && WS == 1 && HS == 1 && !L
 // Small canvases are bound by the number of dependent launches per iteration, not by bytes: there ALL channels
 // of an image go into one launch whatever their sampling (blockIdx.z = channel; 1x1 and 2x2 keep their
 // register-resident paths, everything else takes the generic one).  Not for large images: the kernel needs the
-// registers of its hungriest path for every wavefront.
+// registers of its hungriest path for every wavefront.  The wide-footprint path of zoomed channels is NOT taken here:
+// canvases this small are bound by launches, not bytes, and with its four forms inlined besides the others the
+// checked build of this kernel needed 896 bytes of scratch (which the row tiling cannot have, tests/test_capi.py).
 template <bool LOG, bool NIP>
 __global__ __launch_bounds__(256) void k_project_mixed(ProjArgs a)
 {

@@ -67,6 +67,7 @@ struct ChanHost {
         uint8_t *d8 = nullptr;               // d + 128 in bytes (k_narrow_coefficients); read by k_project instead of d when `narrow`
         bool narrow_fits = false;            // every |d| of the channel's rows held here is <= 127
         bool narrow = false;                 // ... and the projection reads the bytes (J2P_OPT_NARROW_COEFFICIENTS, default on)
+        bool wide = false;                   // ws is 3, 4, 6 or 8 and the projection takes the wide-footprint path (J2P_OPT_WIDE_FOOTPRINT)
         float *q = nullptr;
         float *decoded = nullptr;            // frows * cw floats
         float *scratch_f = nullptr;          // decode scratch of bands too short to lend their x buffers (create only)
@@ -110,6 +111,7 @@ struct j2p_solver {
         size_t live_ws = 0, live_g = 0, live_planes = 0, live_d = 0;
         bool phase_log = false;         // the gradient phase of the running iteration was issued with logging
         bool mixed_project = true;      // small canvases: all samplings in one projection launch (J2P_OPT_MIXED_PROJECT)
+        bool wide_footprint = true;     // footprints 3, 4, 6, 8 columns wide take the wide-footprint path (J2P_OPT_WIDE_FOOTPRINT)
         unsigned *d_maxabs = nullptr;                 // [channel] largest |d| (k_narrow_coefficients, create only)
         unsigned long long *dbg_counters = nullptr;   // J2P_DEBUG builds: [0] address violations, [1] first site, [2] first offset
         unsigned long long *trace = nullptr;          // J2P_TRACE builds: wave records (tools/wave_trace.py)
@@ -370,6 +372,15 @@ void account_coefficient_bytes(j2p_solver *s)
         s->live_d = d_bytes;
         if(s->live_registered) { live_add(s->device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, +1); }
         if(!s->nt_forced) { s->nt = nt_policy(s); }
+}
+
+// which channels the projection sends down the wide-footprint path (project_strip: WS = ws in 3, 4, 6, 8, rows at run time)
+void set_wide_footprint(j2p_solver *s)
+{
+        for(unsigned c = 0; c < s->nch; c++) {
+                const unsigned ws = s->ch[c].ws;
+                s->ch[c].wide = s->wide_footprint && (ws == 3 || ws == 4 || ws == 6 || ws == 8);
+        }
 }
 
 ChanDev chan_dev(const j2p_solver *s, unsigned c)
@@ -706,14 +717,27 @@ void launch_project_unit(int nt, int nip, bool ptr, dim3 grid, hipStream_t st, c
         }
 }
 // every other case by sampling class: logging, subsampled channels, the per-wavefront tree of small canvases
+// (wide: the class's footprint takes the wide-footprint path, ChanHost::wide; any number of rows)
 template <bool LOG, int NIP>
-void launch_project_sampled(unsigned ws, unsigned hs, dim3 grid, hipStream_t st, const ProjArgs &a)
+void launch_project_sampled(unsigned ws, unsigned hs, bool wide, dim3 grid, hipStream_t st, const ProjArgs &a)
 {
         if(ws == 1 && hs == 1) { hipLaunchKernelGGL((k_project<LOG, 1, 1, 0, NIP>), grid, dim3(256), 0, st, a); }
         else if(ws == 2 && hs == 2) { hipLaunchKernelGGL((k_project<LOG, 2, 2, 0, NIP>), grid, dim3(256), 0, st, a); }
         else if(ws == 2 && hs == 1) { hipLaunchKernelGGL((k_project<LOG, 2, 1, 0, NIP>), grid, dim3(256), 0, st, a); }
         else if(ws == 1 && hs == 2) { hipLaunchKernelGGL((k_project<LOG, 1, 2, 0, NIP>), grid, dim3(256), 0, st, a); }
+        else if(wide && ws == 4) { hipLaunchKernelGGL((k_project<LOG, 4, 0, 0, NIP>), grid, dim3(256), 0, st, a); }
+        else if(wide && ws == 8) { hipLaunchKernelGGL((k_project<LOG, 8, 0, 0, NIP>), grid, dim3(256), 0, st, a); }
+        else if(wide && ws == 3) { hipLaunchKernelGGL((k_project<LOG, 3, 0, 0, NIP>), grid, dim3(256), 0, st, a); }
+        else if(wide && ws == 6) { hipLaunchKernelGGL((k_project<LOG, 6, 0, 0, NIP>), grid, dim3(256), 0, st, a); }
         else { hipLaunchKernelGGL((k_project<LOG, 0, 0, 0, NIP>), grid, dim3(256), 0, st, a); }
+}
+
+// whether the projection phase is ONE k_project_mixed launch (small canvases with several samplings); nip as below
+bool projects_mixed(const j2p_solver *s, int nip)
+{
+        bool mixed = false;
+        for(unsigned c = 1; c < s->nch; c++) { mixed = mixed || s->ch[c].ws != s->ch[0].ws || s->ch[c].hs != s->ch[0].hs; }
+        return mixed && s->mixed_project && nip != 2 && (size_t)s->W * s->rows <= kMixedProjectPixels;
 }
 
 // part: 0 = whole phase; J2P_PROJECT_BOUNDARY (1) = norm + the band's first and last block row of every
@@ -787,9 +811,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                 else { a.by_offset[z] = 1; a.by_mul[z] = 1; a.nby[z] = brows > 2 ? brows - 2 : 0; }
                 return a.nby[z];
         };
-        bool mixed = false;
-        for(unsigned c = 1; c < s->nch; c++) { mixed = mixed || s->ch[c].ws != s->ch[0].ws || s->ch[c].hs != s->ch[0].hs; }
-        if(mixed && s->mixed_project && nip != 2 && (size_t)s->W * s->rows <= kMixedProjectPixels) {
+        if(projects_mixed(s, nip)) {
                 // (k_project_mixed has the per-wavefront tree only; canvases this small take that form anyway)
                 // small canvas, several samplings: one launch for all channels (k_project_mixed)
                 unsigned max_strips = 0;
@@ -824,6 +846,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                 }
                 if(a.nby[0] == 0) { continue; }
                 const unsigned strips = ((s->W + 64 * ws - 1) / (64 * ws)) * a.nby[0];
+                const bool wide = s->ch[c0].wide;
                 dim3 grid((strips + 3) / 4, 1, nz);
                 if(ws == 1 && hs == 1 && !log && nip != 1) {
                         // the 1x1 instantiations: g is read non-temporally exactly when the gradient launch wrote it that
@@ -833,11 +856,11 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                         const int nt = inwave_nt_off ? 0 : s->nt;
                         launch_project_unit(nt, nip, far_rows, grid, st, a);
                 }
-                else if(log && nip == 2) { launch_project_sampled<true, 2>(ws, hs, grid, st, a); }
-                else if(log) { launch_project_sampled<true, 0>(ws, hs, grid, st, a); }
-                else if(nip == 2) { launch_project_sampled<false, 2>(ws, hs, grid, st, a); }
-                else if(nip == 1) { launch_project_sampled<false, 1>(ws, hs, grid, st, a); }
-                else { launch_project_sampled<false, 0>(ws, hs, grid, st, a); }
+                else if(log && nip == 2) { launch_project_sampled<true, 2>(ws, hs, wide, grid, st, a); }
+                else if(log) { launch_project_sampled<true, 0>(ws, hs, wide, grid, st, a); }
+                else if(nip == 2) { launch_project_sampled<false, 2>(ws, hs, wide, grid, st, a); }
+                else if(nip == 1) { launch_project_sampled<false, 1>(ws, hs, wide, grid, st, a); }
+                else { launch_project_sampled<false, 0>(ws, hs, wide, grid, st, a); }
 #ifdef J2P_TRACE
                 if(s->trace_on) {
                         s->trace_used += grid.x * grid.z * 4;
@@ -1300,6 +1323,12 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                 }
                 account_coefficient_bytes(s);
         }
+        {
+                // the wide-footprint projection path for the footprints it has (J2P_OPT_WIDE_FOOTPRINT)
+                const char *env = j2p_exp_env("J2P_WIDE_FOOTPRINT");
+                s->wide_footprint = !(env && atoi(env) == 0);
+                set_wide_footprint(s);
+        }
 #undef CREATE_TRY
         rc = launch_init(s);
         if(rc != J2P_OK) { j2p_solver_destroy(s); return rc; }
@@ -1344,6 +1373,10 @@ int j2p_solver_debug_option(j2p_solver *s, int option, int value)
                 for(unsigned c = 0; c < s->nch; c++) { s->ch[c].narrow = value != 0 && s->ch[c].narrow_fits; }
                 account_coefficient_bytes(s);
                 break;
+        case J2P_OPT_WIDE_FOOTPRINT:
+                s->wide_footprint = value != 0;
+                set_wide_footprint(s);
+                break;
         default: return fail(J2P_EINVAL, "unknown option %d", option);
         }
         return J2P_OK;
@@ -1353,6 +1386,15 @@ int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *byte
 {
         if(!s || !bytes || c >= s->nch) { return fail(J2P_EINVAL, "j2p_solver_coefficient_bytes: bad argument"); }
         *bytes = s->ch[c].narrow ? 1u : 2u;
+        return J2P_OK;
+}
+
+int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on)
+{
+        if(!s || !on || c >= s->nch) { return fail(J2P_EINVAL, "j2p_solver_wide_footprint: bad argument"); }
+        // (k_project_mixed has no wide-footprint path; bands of whole phases reduce ||g|| in k_project, NIP 2)
+        const int nip = !s->whole && s->band_nip && s->ntr_global <= kWaveTreeMax ? 2 : 0;
+        *on = s->ch[c].wide && !projects_mixed(s, nip) ? 1u : 0u;
         return J2P_OK;
 }
 
