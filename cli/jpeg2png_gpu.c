@@ -16,6 +16,8 @@
  *                  fewer files than GPUs the GPUs are shared out among the files and every image is row-tiled
  *                  over its share (one band per GPU; the library uses fewer bands, or one GPU, for images too
  *                  small to pay for the cross-band schedule: at least 2 Mpixel per band) — same pixels either way
+ *   -g, --greyscale = a greyscale PNG: the reference's compute(1, ...) on component 0 alone, as `-s` solves it
+ *                  (jpeg2png.c:147-152), written with Cb = Cr = 0 (png.c:37-45); one- and three-component JPEGs
  * Messages and exit codes follow the reference ("jpeg2png: <message>", EXIT_FAILURE).
  */
 #define _POSIX_C_SOURCE 200809L
@@ -103,6 +105,7 @@ struct component {
 
 struct jpeg_in {
         unsigned w, h;
+        unsigned n;             /* components read: 3, or 1 with -g (component 0 only) */
         struct component c[3];
 };
 
@@ -120,8 +123,9 @@ static void jpeg_message(j_common_ptr info)
         pthread_mutex_unlock(&ui_lock);
 }
 
-/* zoom: the integer zoom factor (-z) the sampling factors are multiplied by later on, for the memory guard */
-static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom)
+/* zoom: the integer zoom factor (-z) the sampling factors are multiplied by later on, for the memory guard;
+ * grey (-g): one- and three-component files are accepted and only component 0 is read */
+static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom, bool grey)
 {
         struct jpeg_decompress_struct d;
         struct jpeg_error_mgr err;
@@ -132,8 +136,10 @@ static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom)
         jpeg_read_header(&d, TRUE);
         jp->w = d.image_width;
         jp->h = d.image_height;
-        if(d.num_components != 3) { die("only 3 component jpegs are supported"); }
-        for(int c = 0; c < 3; c++) {
+        if(!grey && d.num_components != 3) { die("only 3 component jpegs are supported"); }
+        if(grey && d.num_components != 1 && d.num_components != 3) { die("only 1 and 3 component jpegs are supported with -g"); }
+        jp->n = grey ? 1 : 3;
+        for(unsigned c = 0; c < jp->n; c++) {
                 int t = d.comp_info[c].quant_tbl_no;
                 if(t < 0 || t >= NUM_QUANT_TBLS) { die("weird jpeg: invalid quant_tbl_no"); }
                 JQUANT_TBL *tbl = d.quant_tbl_ptrs[t];
@@ -144,7 +150,7 @@ static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom)
                 }
         }
         jvirt_barray_ptr *arrays = jpeg_read_coefficients(&d);
-        for(int c = 0; c < 3; c++) {
+        for(unsigned c = 0; c < jp->n; c++) {
                 jpeg_component_info *ci = &d.comp_info[c];
                 struct component *k = &jp->c[c];
                 k->w = ci->width_in_blocks * 8;
@@ -174,19 +180,20 @@ static void png_fatal(png_structp png, png_const_charp msg)
         die("%s", msg);
 }
 
-static void write_rgb_png(FILE *out, unsigned w, unsigned h, unsigned bits, uint8_t *pixels)
+/* channels: 3 (RGB) or 1 (greyscale, -g) */
+static void write_png(FILE *out, unsigned w, unsigned h, unsigned bits, unsigned channels, uint8_t *pixels)
 {
         png_structp png = png_create_write_struct(PNG_LIBPNG_VER_STRING, NULL, png_fatal, NULL);
         if(!png) { die("could not initialize PNG write struct"); }
         png_infop info = png_create_info_struct(png);
         if(!info) { die("could not initialize PNG info struct"); }
         png_init_io(png, out);
-        png_set_IHDR(png, info, w, h, (int)bits, PNG_COLOR_TYPE_RGB, PNG_INTERLACE_NONE, PNG_COMPRESSION_TYPE_BASE,
-                     PNG_FILTER_TYPE_BASE);
+        png_set_IHDR(png, info, w, h, (int)bits, channels == 1 ? PNG_COLOR_TYPE_GRAY : PNG_COLOR_TYPE_RGB, PNG_INTERLACE_NONE,
+                     PNG_COMPRESSION_TYPE_BASE, PNG_FILTER_TYPE_BASE);
         png_write_info(png, info);
         png_bytep *rows = malloc(sizeof(*rows) * h);
         if(!rows) { die("allocation failure"); }
-        size_t stride = (size_t)w * 3 * (bits / 8);
+        size_t stride = (size_t)w * channels * (bits / 8);
         for(unsigned y = 0; y < h; y++) { rows[y] = pixels + y * stride; }
         png_write_image(png, rows);
         free(rows);
@@ -201,6 +208,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         bool joint, quiet;
+        bool grey;              /* -g: component 0 alone, one-channel job, greyscale PNG */
         unsigned zoom;          /* -z: integer zoom factor 1..4 (every sampling factor times zoom, output zoom times the size) */
         bool tile;              /* fewer files than GPUs: every image row-tiled over its share of them */
         unsigned nfiles;
@@ -262,7 +270,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         FILE *in = fopen(infile, "rb");
         if(!in) { die_perror("could not open input file `%s`", infile); }
         struct jpeg_in jp;
-        read_coefficients(in, &jp, o->zoom);
+        read_coefficients(in, &jp, o->zoom, o->grey);
         fclose(in);
         /* zooming by z = the same solve with every component's sampling factors times z (compute.c:407-416): the
          * canvas, and the image written, are z times as wide and as high.  The library's canvas height limit is
@@ -270,7 +278,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         const unsigned zoom = o->zoom;
         {
                 unsigned long long cw = 0, chh = 0;
-                for(int c = 0; c < 3; c++) {
+                for(unsigned c = 0; c < jp.n; c++) {
                         const unsigned long long w = (unsigned long long)jp.c[c].w * jp.c[c].w_samp * zoom;
                         const unsigned long long h = (unsigned long long)jp.c[c].h * jp.c[c].h_samp * zoom;
                         if(w > cw) { cw = w; }
@@ -284,8 +292,10 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         struct job_ctx ctx = {o, infile};
         j2p_job job;
         memset(&job, 0, sizeof(job));
-        job.nchannel = 3;
-        for(int c = 0; c < 3; c++) {
+        /* -g: component 0 as one compute(1, ...) with entry 0 of the lists, as the first call of `-s` makes it
+         * (jpeg2png.c:147-152); separate, so that its CSV rows are channel 0's, as that run writes them */
+        job.nchannel = jp.n;
+        for(unsigned c = 0; c < jp.n; c++) {
                 job.planes[c].w = jp.c[c].w;
                 job.planes[c].h = jp.c[c].h;
                 job.planes[c].w_samp = jp.c[c].w_samp * zoom;
@@ -297,7 +307,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 job.pweight[c] = o->pweights[c];
                 job.iterations[c] = o->iterations[c];
         }
-        job.separate = !o->joint;
+        job.separate = o->grey || !o->joint;
         job.tile = o->tile;
         {
                 /* (tests row-tile small images: the pixel gate of the library can be lowered from outside the program) */
@@ -315,7 +325,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         job.out_bits = o->png_bits;
         job.out_w = jp.w * zoom;
         job.out_h = jp.h * zoom;
-        size_t bytes = (size_t)job.out_w * job.out_h * 3 * (o->png_bits / 8);
+        size_t bytes = (size_t)job.out_w * job.out_h * jp.n * (o->png_bits / 8);
         uint8_t *pixels = malloc(bytes);
         if(!pixels) { die("could not allocate image data"); }
         job.out_rgb = pixels;
@@ -327,10 +337,10 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         if(batch_rc != J2P_OK) { die("%s", batch_err); }
         gpu_check(j2p_batch_submit(batch, &job, &ticket));
         gpu_check(j2p_batch_wait(batch, ticket));
-        for(int c = 0; c < 3; c++) { free(jp.c[c].data); }
+        for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
-        write_rgb_png(out, job.out_w, job.out_h, o->png_bits, pixels);
+        write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels);
         fclose(out);
         free(pixels);
 }
@@ -373,6 +383,9 @@ static void usage(void)
                "  -t, --threads N              input files processed concurrently (default: online cores)\n"
                "  -1, --16-bits-png            16-bit PNG\n"
                "  -z, --zoom N                 upscale N times (1..4) while removing the artifacts (default 1)\n"
+               "  -g, --greyscale              greyscale PNG; also reads 1-component JPEGs.  The grey is component 0\n"
+               "                               (Y) solved alone, as -s solves it, with the first -w/-p/-i value; not\n"
+               "                               the luma of the default joint solve\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -389,15 +402,16 @@ int main(int argc, char **argv)
                 {"threads", required_argument, NULL, 't'}, {"quiet", no_argument, NULL, 'q'},
                 {"separate-components", no_argument, NULL, 's'}, {"16-bits-png", no_argument, NULL, '1'},
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
-                {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'}, {NULL, 0, NULL, 0}};
+                {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
+                {"greyscale", no_argument, NULL, 'g'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .joint = true, .quiet = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+                            .png_bits = 8, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:g", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -411,6 +425,7 @@ int main(int argc, char **argv)
                 case 'p': p_arg = optarg; break;
                 case 'w': w_arg = optarg; break;
                 case 'z': z_arg = optarg; break;
+                case 'g': o.grey = true; break;
                 default: help = true; break;
                 }
         }
@@ -498,7 +513,7 @@ int main(int argc, char **argv)
 
         if(!o.quiet) {
                 pthread_mutex_lock(&ui_lock);
-                bar_max = o.joint ? nin * o.iterations[0] : nin * (o.iterations[0] + o.iterations[1] + o.iterations[2]);
+                bar_max = o.joint || o.grey ? nin * o.iterations[0] : nin * (o.iterations[0] + o.iterations[1] + o.iterations[2]);
                 if(bar_max == 0) { bar_max = 1; }
                 bar_cur = 0;
                 bar_on = true;

@@ -378,6 +378,15 @@ int j2p_planes_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned h, uns
  * (row_end - row_begin) * w * 3 (or 6) bytes */
 int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
                            uint8_t *out_host);
+/* Greyscale: the same writer on ONE (solver, channel) pair with Cb = Cr = 0, i.e. R = G = B of png.c:37-45 after the
+ * luma +128 fix-up — one sample per pixel.  out_host receives h*w bytes (bits == 8) or h*w*2 bytes, big-endian samples
+ * (bits == 16, at most 65280).  The plane is the reference's compute(1, ...) on one component: the only component of a
+ * greyscale JPEG, or component 0 (Y) of a colour one, solved alone as `-s` solves it (jpeg2png.c:147-152) — not the luma
+ * of a joint compute(3, ...), whose total variation couples the channels.  Same argument checks and whole / band rules
+ * as j2p_planes_to_rgb / j2p_planes_rows_to_rgb. */
+int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsigned bits, uint8_t *out_host);
+int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
+                            uint8_t *out_host);
 
 /* Image batches (BASELINE configs[4]; the file loop jpeg2png.c:330-337): a batch owns slots_per_device worker
  * threads per GPU, each driving one image at a time on streams of its own, so that the uploads, solves and
@@ -393,9 +402,10 @@ typedef struct j2p_job {
         float pweight[J2P_MAX_CHANNELS];
         unsigned iterations[J2P_MAX_CHANNELS];
         /* output: out_bits 8 / 16 = RGB samples (png.c:37-62 incl. the luma +128 of jpeg2png.c:156-159), cropped to
-         * out_w x out_h, into out_rgb (h*w*3 or h*w*6 bytes); out_bits 0 = the float canvas planes into
-         * out_planes[c] (NULL entries are skipped): W*H floats of the joint canvas, or — separate — of component
-         * c's own canvas, w*w_samp x h*h_samp (compute.c:410-416 per call) */
+         * out_w x out_h, into out_rgb (h*w*3 or h*w*6 bytes); with nchannel == 1 the samples are greyscale
+         * (j2p_planes_to_grey: h*w or h*w*2 bytes into out_rgb); nchannel == 2 has no sample output.  out_bits 0 = the
+         * float canvas planes into out_planes[c] (NULL entries are skipped): W*H floats of the joint canvas, or
+         * — separate — of component c's own canvas, w*w_samp x h*h_samp (compute.c:410-416 per call) */
         /* (hand over output memory that is already MAPPED — arrays reused between jobs: mapping or first-touching host memory
          * while other jobs' kernels run stalls a launch of theirs each time; 229 against 196-201 images/s at 1080p on one GPU,
          * profiles/r05_batch_prealloc.jsonl) */

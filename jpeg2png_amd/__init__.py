@@ -76,6 +76,7 @@ C_ABI_SYMBOLS = [
     "j2p_solver_download_gradient", "j2p_solver_set_logging", "j2p_log_rows_from_sums",
     "j2p_solver_plane_ptr", "j2p_solver_sync", "j2p_solver_kernel_times", "j2p_solver_enable_timing",
     "j2p_decode_plane", "j2p_dct8x8_blocks", "j2p_math_selftest", "j2p_planes_to_rgb", "j2p_planes_rows_to_rgb", "j2p_sqrt_exhaustive",
+    "j2p_planes_to_grey", "j2p_planes_rows_to_grey",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -565,8 +566,9 @@ class TiledSolver:
 
 class Batch:
     """Images in flight over slots_per_device worker threads per GPU (include/jpeg2png_amd.h: j2p_batch_*).
-    submit() returns a ticket; wait(ticket) returns the job's output: RGB samples [h, w, 3] (bits 8 / 16) or the
-    list of float canvas planes (bits 0)."""
+    submit() returns a ticket; wait(ticket) returns the job's output: RGB samples [h, w, 3] (bits 8 / 16), greyscale
+    samples [h, w] for a one-plane job (bits 8 / 16: the plane's compute(1, ...) written as png.c writes it with
+    Cb = Cr = 0), or the list of float canvas planes (bits 0)."""
 
     def __init__(self, devices=(0,), slots_per_device=3):
         lib = load_library()
@@ -611,11 +613,15 @@ class Batch:
             # half-written array, so it is an error here, not an assert that -O strips)
             if bits not in (8, 16):
                 raise J2PError("job: out_bits must be 0, 8 or 16")
+            if n == 2:
+                raise J2PError("job: sample output needs three planes (RGB) or one (greyscale)")
+            # one plane: greyscale, one sample per pixel
+            shape = (height, width) if n == 1 else (height, width, 3)
             if out is None:
-                out = np.empty((height, width, 3), dtype=np.uint8 if bits == 8 else ">u2")
-            if not (isinstance(out, np.ndarray) and out.shape == (height, width, 3) and out.flags["C_CONTIGUOUS"]
+                out = np.empty(shape, dtype=np.uint8 if bits == 8 else ">u2")
+            if not (isinstance(out, np.ndarray) and out.shape == shape and out.flags["C_CONTIGUOUS"]
                     and out.flags["WRITEABLE"] and out.dtype.itemsize == bits // 8 and out.dtype.kind in "ui"):
-                raise J2PError(f"out must be a writeable C-contiguous ({height}, {width}, 3) array of "
+                raise J2PError(f"out must be a writeable C-contiguous {shape} array of "
                                            f"{bits // 8}-byte integers for bits = {bits}")
             job.out_bits, job.out_w, job.out_h = bits, width, height
             job.out_rgb = out.ctypes.data

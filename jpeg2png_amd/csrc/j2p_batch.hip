@@ -3,12 +3,12 @@
 //
 // A j2p_batch owns `slots_per_device` worker threads per GPU.  A job is one image — what decode_file() does
 // between read_jpeg() and write_png(): one joint compute(3, ...) or three separate compute(1, ...) calls, then the
-// planes handed back as floats or, converted on the device (png.c:37-62), as RGB samples.  Every worker drives its
-// jobs on streams of its own, so while one slot's image is being solved the next slot's coefficients go up and a
-// third one's pixels come down: H2D / solve / D2H overlap without any of them knowing about the others.  Device
-// memory comes from the library's pool (one arena per solver, recycled between jobs): after the first few images
-// a job performs no hipMalloc / hipFree — the device-wide synchronisation inside hipFree is what used to
-// serialise concurrent compute() calls.
+// planes handed back as floats or, converted on the device (png.c:37-62), as RGB samples (greyscale ones for a
+// one-channel job).  Every worker drives its jobs on streams of its own, so while one slot's image is being solved
+// the next slot's coefficients go up and a third one's pixels come down: H2D / solve / D2H overlap without any of
+// them knowing about the others.  Device memory comes from the library's pool (one arena per solver, recycled
+// between jobs): after the first few images a job performs no hipMalloc / hipFree — the device-wide synchronisation
+// inside hipFree is what used to serialise concurrent compute() calls.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <condition_variable>
@@ -84,7 +84,9 @@ int validate_job(const j2p_job &d)
 {
         if(d.nchannel == 0 || d.nchannel > J2P_MAX_CHANNELS) { return j2p_fail(J2P_EINVAL, "job: nchannel must be 1..3"); }
         if(d.out_bits != 0 && d.out_bits != 8 && d.out_bits != 16) { return j2p_fail(J2P_EINVAL, "job: out_bits must be 0, 8 or 16"); }
-        if(d.out_bits && (!d.out_rgb || d.nchannel != 3)) { return j2p_fail(J2P_EINVAL, "job: RGB output needs three channels and out_rgb"); }
+        if(d.out_bits && (!d.out_rgb || d.nchannel == 2)) {
+                return j2p_fail(J2P_EINVAL, "job: sample output needs out_rgb and three channels (RGB) or one (greyscale)");
+        }
         return J2P_OK;
 }
 
@@ -184,20 +186,21 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 }
         }
         if(d.out_bits) {
-                const size_t row_bytes = (size_t)d.out_w * (d.out_bits == 8 ? 3 : 6);
+                const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
                 for(unsigned b = 0; b < nband; b++) {
                         const unsigned y0 = cuts[b];
                         unsigned y1 = b + 1 < nband ? cuts[b + 1] : d.out_h;
                         if(y1 > d.out_h) { y1 = d.out_h; }
                         if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
                         j2p_plane_ref ref[3];
-                        for(unsigned c = 0; c < 3; c++) {
+                        for(unsigned c = 0; c < d.nchannel; c++) {
                                 j2p_solver *bs = nullptr;
                                 JOB_TRY(j2p_tiled_band(d.separate ? t[c] : t[0], b, nullptr, nullptr, nullptr, &bs));
                                 ref[c].solver = bs;
                                 ref[c].channel = d.separate ? 0 : c;
                         }
-                        JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes));
+                        if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes)); }
+                        else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes)); }
                 }
         } else {
                 for(unsigned c = 0; c < d.nchannel; c++) {
@@ -262,11 +265,12 @@ int run_job(const j2p_job &d, int device)
         }
         if(d.out_bits) {
                 j2p_plane_ref ref[3];
-                for(unsigned c = 0; c < 3; c++) {
+                for(unsigned c = 0; c < d.nchannel; c++) {
                         ref[c].solver = d.separate ? s[c] : s[0];
                         ref[c].channel = d.separate ? 0 : c;
                 }
-                JOB_TRY(j2p_planes_to_rgb(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb));
+                if(d.nchannel == 1) { JOB_TRY(j2p_planes_to_grey(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }   // greyscale: one sample per pixel
+                else { JOB_TRY(j2p_planes_to_rgb(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }
         } else {
                 for(unsigned c = 0; c < d.nchannel; c++) {
                         if(!d.out_planes[c]) { continue; }

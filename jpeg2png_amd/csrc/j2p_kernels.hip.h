@@ -2967,6 +2967,25 @@ __global__ __launch_bounds__(256) void k_to_rgb(const float *yp, unsigned ys, co
         }
 }
 
+// Greyscale: one plane through the same writer with Cb = Cr = 0, where R = G = B = to_sample(yi) exactly (yi + 0.0 and
+// yi - 0.0 - 0.0 in double are yi).  out: 1 byte per pixel (bits == 8) or 2 bytes, a big-endian sample (bits == 16).
+__global__ __launch_bounds__(256) void k_to_grey(const float *yp, unsigned ys, unsigned w, unsigned h, unsigned bits, uint8_t *out)
+{
+        const size_t n = (size_t)w * h;
+        const float bitfactor = (float)((double)(1 << bits) / 256.);
+        for(size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+                const unsigned x = (unsigned)(i % w), y = (unsigned)(i / w);
+                const float yi = (float)((double)yp[(size_t)y * ys + x] + 128.);   // jpeg2png.c:158
+                const unsigned v = to_sample((double)yi, bitfactor);
+                if(bits == 8) {
+                        out[i] = (uint8_t)(v & 0xff);
+                } else {
+                        uint8_t *o = out + i * 2;
+                        o[0] = (uint8_t)((v >> 8) & 0xff); o[1] = (uint8_t)(v & 0xff);
+                }
+        }
+}
+
 // ---------------------------------------------------------------------------
 // Self-test of the fast division / square root against the compiler's IEEE forms
 // on n pseudo-random operand pairs inside the screened range (tests/ only).

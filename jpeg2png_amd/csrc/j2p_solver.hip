@@ -2076,12 +2076,15 @@ int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
         return rc;
 }
 
-// rows [y0, y1) of the image from three (solver, channel) pairs on one device that all hold those canvas rows
-static int rgb_rows(const j2p_plane_ref planes[3], unsigned w, unsigned y0, unsigned y1, unsigned bits, uint8_t *out_host)
+// rows [y0, y1) of the image from nplane (solver, channel) pairs on one device that all hold those canvas rows:
+// three -> RGB (k_to_rgb), one -> greyscale (k_to_grey)
+static int convert_rows(const j2p_plane_ref *planes, int nplane, unsigned w, unsigned y0, unsigned y1, unsigned bits,
+                        uint8_t *out_host)
 {
+        const char *what = nplane == 3 ? "to_rgb" : "to_grey";
         const float *ptr[3];
         unsigned stride[3];
-        for(int i = 0; i < 3; i++) {
+        for(int i = 0; i < nplane; i++) {
                 j2p_solver *s = planes[i].solver;
                 if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %d: bad solver/channel", i); }
                 if(s->device != planes[0].solver->device) { return fail(J2P_EINVAL, "planes live on different devices"); }
@@ -2089,26 +2092,30 @@ static int rgb_rows(const j2p_plane_ref planes[3], unsigned w, unsigned y0, unsi
                         return fail(J2P_EINVAL, "plane %d: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
                                     s->row0, s->row0 + s->rows, s->W);
                 }
-                if(s->grad_done) { return fail(J2P_ESTATE, "to_rgb between the two phases of an iteration"); }
+                if(s->grad_done) { return fail(J2P_ESTATE, "%s between the two phases of an iteration", what); }
                 ptr[i] = s->ch[planes[i].channel].xbuf[s->cur] + (size_t)(kHalo + (y0 - s->row0)) * s->W;
                 stride[i] = s->W;
         }
         const unsigned h = y1 - y0;
         j2p_solver *s0 = planes[0].solver;
         DeviceGuard guard(s0->device);
-        for(int i = 1; i < 3; i++) {
+        for(int i = 1; i < nplane; i++) {
                 if(planes[i].solver != s0) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
         }
-        const size_t bytes = (size_t)w * h * (bits == 8 ? 3 : 6);
+        const size_t bytes = (size_t)w * h * (size_t)nplane * (bits / 8);
         void *dout = nullptr;
         size_t dout_bytes = 0;
         HIP_TRY(pool_take(s0->device, bytes, &dout, &dout_bytes));       // pooled like the solvers' arenas: no hipFree per image
-        hipLaunchKernelGGL(k_to_rgb, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2],
-                           w, h, bits, static_cast<uint8_t *>(dout));
+        if(nplane == 3) {
+                hipLaunchKernelGGL(k_to_rgb, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2],
+                                   w, h, bits, static_cast<uint8_t *>(dout));
+        } else {
+                hipLaunchKernelGGL(k_to_grey, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0], w, h, bits, static_cast<uint8_t *>(dout));
+        }
         hipError_t e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s0->stream);
         if(e == hipSuccess) { e = hipStreamSynchronize(s0->stream); }
         pool_give(s0->device, dout, dout_bytes);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_rgb: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_%s: %s", what, hipGetErrorString(e)); }
         return J2P_OK;
 }
 
@@ -2120,7 +2127,7 @@ int j2p_planes_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned h, uns
         for(int i = 0; i < 3; i++) {
                 if(planes[i].solver && !planes[i].solver->whole) { return fail(J2P_ESTATE, "to_rgb needs whole-canvas solvers (bands: j2p_planes_rows_to_rgb)"); }
         }
-        return rgb_rows(planes, w, 0, h, bits, out_host);
+        return convert_rows(planes, 3, w, 0, h, bits, out_host);
 }
 
 int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
@@ -2129,7 +2136,25 @@ int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned r
         if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
         if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
         if(w == 0 || row_begin >= row_end) { return fail(J2P_EINVAL, "empty row range"); }
-        return rgb_rows(planes, w, row_begin, row_end, bits, out_host);
+        return convert_rows(planes, 3, w, row_begin, row_end, bits, out_host);
+}
+
+int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
+{
+        if(!plane || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
+        if(w == 0 || h == 0) { return fail(J2P_EINVAL, "empty image"); }
+        if(plane->solver && !plane->solver->whole) { return fail(J2P_ESTATE, "to_grey needs a whole-canvas solver (bands: j2p_planes_rows_to_grey)"); }
+        return convert_rows(plane, 1, w, 0, h, bits, out_host);
+}
+
+int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
+                            uint8_t *out_host)
+{
+        if(!plane || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
+        if(w == 0 || row_begin >= row_end) { return fail(J2P_EINVAL, "empty row range"); }
+        return convert_rows(plane, 1, w, row_begin, row_end, bits, out_host);
 }
 
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,
