@@ -112,8 +112,7 @@ void j2p_pool_trim(void);
 #define J2P_OPT_NORM_FOLD     1   /* 1 (default for band solvers and for whole canvases up to 2.5 Mpixel): level 1 of the
                                      ||g|| reduction runs inside the gradient kernel (its last-arriving wavefronts);
                                      0: separate reduction kernel — same bits */
-#define J2P_OPT_JOINT_INWAVE  2   /* 1: all channels of a joint image in one wavefront; 0 (default): one wavefront
-                                     per channel.  Environment J2P_JOINT_INWAVE sets the default at create time */
+/* (2 is not an option any more: the all-channels-in-one-wavefront gradient kernel it selected is deleted) */
 #define J2P_OPT_NORM_IN_PROJECT 4 /* 1 (needs NORM_FOLD): the gradient kernel leaves per-tile-row sums and every wavefront of
                                      the projection kernel runs the final tree itself: no reduction launch in between */
 #define J2P_OPT_NT_GRADIENT 5     /* 0..3: which streams are accessed non-temporally (1: the gradient plane, 2: + the prob

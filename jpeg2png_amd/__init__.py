@@ -87,7 +87,7 @@ C_ABI_SYMBOLS = [
     "j2p_debug_build", "j2p_debug_grad_items", "j2p_experiments_build", "j2p_solver_debug_violations", "j2p_solver_trace", "j2p_division_exhaustive",
     "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint",
 ]
-J2P_OPT_NORM_FOLD, J2P_OPT_JOINT_INWAVE, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 2, 4, 5, 6
+J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 4, 5, 6
 J2P_OPT_NARROW_COEFFICIENTS = 7
 J2P_OPT_WIDE_FOOTPRINT = 8
 ZOOM_MAX = 4
@@ -145,7 +145,7 @@ def load_library():
 
 class library:
     """context manager: another build of the library for the objects created inside the block — the experiments build
-    (-DJ2P_EXPERIMENTS: schedules and environment knobs the release build does not carry, buildlib.build_experiments)
+    (-DJ2P_EXPERIMENTS: the release kernels plus environment knobs and split phases the release build does not carry, buildlib.build_experiments)
     in the schedule-equivalence tests.  Solvers remember the library they were created from; both copies share the
     process's HIP runtime."""
 
@@ -250,8 +250,8 @@ def rccl_version():
 
 
 def experiments_build():
-    """True when the loaded library is the experiments build (-DJ2P_EXPERIMENTS): the schedules that lost their
-    measurements — split phases among them — answer only there"""
+    """True when the loaded library is the experiments build (-DJ2P_EXPERIMENTS): the environment knobs that move choices
+    among the release kernels, and the split phases, answer only there"""
     return bool(load_library().j2p_experiments_build())
 
 

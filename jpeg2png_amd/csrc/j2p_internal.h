@@ -4,11 +4,11 @@
 #include "jpeg2png_amd.h"
 
 // Environment knobs of the EXPERIMENTS build (-DJ2P_EXPERIMENTS: jpeg2png_amd/libjpeg2png_amd_exp.so, built by
-// buildlib.build_experiments() for the schedule-equivalence tests and the timing tools): schedules that measured slower
-// everywhere (one column per lane, all channels of a joint image in one wavefront, the reduction as the gradient
-// launch's last workgroup, split phases) and the switches that select them.  The release library carries neither the
-// kernels nor the switches and reads only J2P_DEVICE, J2P_DEVICES, J2P_TILED_EXCHANGE, J2P_TILED_WAIT,
-// J2P_TILED_VERIFY, J2P_RCCL_LIBRARY, J2P_POOL_MIB and J2P_COMPUTE_TIMING.
+// buildlib.build_experiments() for the schedule-equivalence tests and the timing tools): the switches that move choices
+// AMONG the release kernels (rows per strip, item shares, launch direction, where the norm is finished, ...) and the
+// split phases.  Its device code is the release build's.  The release library carries neither the switches nor the split
+// phases and reads only J2P_DEVICE, J2P_DEVICES, J2P_TILED_EXCHANGE, J2P_TILED_WAIT, J2P_TILED_VERIFY, J2P_RCCL_LIBRARY,
+// J2P_POOL_MIB and J2P_COMPUTE_TIMING.
 static inline const char *j2p_exp_env(const char *name)
 {
 #ifdef J2P_EXPERIMENTS

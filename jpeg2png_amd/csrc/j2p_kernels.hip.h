@@ -28,7 +28,6 @@
 // a time — are gone from this file; their measurements are profiles/r03_decomposition.jsonl and r05_decomposition.jsonl.)
 // -DJ2P_TRACE -DJ2P_TRACE_CLOCK: the trace record's middle stamp becomes the wavefront's life in CORE-clock ticks (s_memtime)
 // next to its life on the constant 100 MHz clock: the shader clock the kernels actually run at (tools/core_clock.py)
-// (and one that stays correct: J2P_PROJECT_MAXWAVES=N caps k_project's wavefronts per SIMD through its LDS footprint)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -407,11 +406,6 @@ __device__ __forceinline__ v2f buf_load2(__amdgpu_buffer_rsrc_t r, unsigned lane
         return __builtin_bit_cast(v2f, raw);
 }
 template <bool NT>
-__device__ __forceinline__ void buf_store(float v, __amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned row_off)
-{
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)lane_off, (int)row_off, NT ? 2 : 0);
-}
-template <bool NT>
 __device__ __forceinline__ void buf_store(v2f v, __amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned row_off)
 {
         typedef unsigned v2u __attribute__((ext_vector_type(2)));
@@ -425,24 +419,11 @@ __device__ __forceinline__ void buf_store4(float a, float b, float c, float d, _
                             __builtin_bit_cast(unsigned, d)};
         __builtin_amdgcn_raw_buffer_store_b128(raw, r, (int)lane_off, (int)row_off, NT ? 2 : 0);
 }
-template <bool NT, class V>
-__device__ __forceinline__ V buf_load(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned row_off)
-{
-        if constexpr(sizeof(V) == 8) { return buf_load2<NT>(r, lane_off, row_off); }
-        else { return buf_load1<NT>(r, lane_off, row_off); }
-}
 
-// Everything below is written once for a lane's PIXEL VECTOR V: v2f = two neighbouring columns per lane, the arithmetic
-// issuing as packed operations (128-column strips: what canvases that fill the chip use), or float = one column per
-// lane (64-column strips: twice the wavefronts with half the work each, for canvases whose launches would otherwise
-// leave most wavefront slots empty — packed f32 operations cost two plain ones on gfx950, so nothing is lost per pixel
-// but the halo columns).  The few places that care which of the two they are dealing with are these overloads.
-template <class V>
-__device__ __forceinline__ V splat(float s);
-template <>
-__device__ __forceinline__ float splat<float>(float s) { return s; }
-template <>
-__device__ __forceinline__ v2f splat<v2f>(float s) { return v2f{s, s}; }
+// A lane's PIXEL VECTOR is v2f: two neighbouring columns per lane, so that the arithmetic issues as packed operations
+// (128-column strips).  (One column per lane — the same text instantiated on float, 64-column strips — was measured and
+// lost everywhere: DESIGN.md section 10.)
+__device__ __forceinline__ v2f splat(float s) { return v2f{s, s}; }
 
 // wave_shr:1 / wave_shl:1 with bound_ctrl: the lane without a source reads 0, and because no "old" value
 // has to be supplied the compiler does not spend a v_mov on initialising the destination
@@ -457,8 +438,6 @@ __device__ __forceinline__ float lane_from_right(float v)   // value held by lan
 // columns x-1 / x+1 of a lane's pixel vector
 __device__ __forceinline__ v2f left_of(v2f a) { return v2f{lane_from_left(a.y), a.x}; }
 __device__ __forceinline__ v2f right_of(v2f a) { return v2f{a.y, lane_from_right(a.x)}; }
-__device__ __forceinline__ float left_of(float a) { return lane_from_left(a); }
-__device__ __forceinline__ float right_of(float a) { return lane_from_right(a); }
 
 // The lane shifts feed one addition or subtraction each.  Written per element, the shifted operand can go into the
 // instruction itself (v_add_f32_dpp / v_subrev_f32_dpp) with one plain v_add_f32 as its partner
@@ -466,44 +445,30 @@ __device__ __forceinline__ v2f add_left_of(v2f g, v2f t) { return v2f{g.x + lane
 __device__ __forceinline__ v2f add_right_of(v2f g, v2f t) { return v2f{g.x + t.y, g.y + lane_from_right(t.x)}; }  // g + right_of(t)
 __device__ __forceinline__ v2f minus_left_of(v2f a) { return v2f{a.x - lane_from_left(a.y), a.y - a.x}; }         // a - left_of(a)
 __device__ __forceinline__ v2f right_of_minus(v2f a) { return v2f{a.y - a.x, lane_from_right(a.x) - a.y}; }       // right_of(a) - a
-__device__ __forceinline__ float add_left_of(float g, float t) { return g + lane_from_left(t); }
-__device__ __forceinline__ float add_right_of(float g, float t) { return g + lane_from_right(t); }
-__device__ __forceinline__ float minus_left_of(float a) { return a - lane_from_left(a); }
-__device__ __forceinline__ float right_of_minus(float a) { return lane_from_right(a) - a; }
 
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ float pk_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // hardware approximations (1 ulp) and the IEEE forms, per element
 __device__ __forceinline__ v2f hw_rcp(v2f d) { return v2f{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)}; }
-__device__ __forceinline__ float hw_rcp(float d) { return __builtin_amdgcn_rcpf(d); }
 __device__ __forceinline__ v2f hw_rsq(v2f x) { return v2f{__builtin_amdgcn_rsqf(x.x), __builtin_amdgcn_rsqf(x.y)}; }
-__device__ __forceinline__ float hw_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 __device__ __forceinline__ v2f ieee_sqrt(v2f x) { return v2f{sqrtf(x.x), sqrtf(x.y)}; }
-__device__ __forceinline__ float ieee_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ v2f ieee_div(v2f x, v2f d) { return v2f{x.x / d.x, x.y / d.y}; }
-__device__ __forceinline__ float ieee_div(float x, float d) { return x / d; }
 // a where n != 0, 0 where n == 0 (compute.c:97,158); n where n != 0, 1 where n == 0; max(n, m)
 __device__ __forceinline__ v2f weight_unless_zero(v2f n, float a) { return v2f{n.x == 0.f ? 0.f : a, n.y == 0.f ? 0.f : a}; }
-__device__ __forceinline__ float weight_unless_zero(float n, float a) { return n == 0.f ? 0.f : a; }
 __device__ __forceinline__ v2f one_if_zero(v2f n) { return v2f{n.x == 0.f ? 1.f : n.x, n.y == 0.f ? 1.f : n.y}; }
-__device__ __forceinline__ float one_if_zero(float n) { return n == 0.f ? 1.f : n; }
 __device__ __forceinline__ v2f at_least(v2f n, float m) { return v2f{fmaxf(n.x, m), fmaxf(n.y, m)}; }
-__device__ __forceinline__ float at_least(float n, float m) { return fmaxf(n, m); }
 // acc += (double)(a * n) element by element, in column order (the log sums, compute.c:92,156)
 __device__ __forceinline__ void add_scaled(double &acc, float a, v2f n)
 {
         acc += (double)(a * n.x);
         acc += (double)(a * n.y);
 }
-__device__ __forceinline__ void add_scaled(double &acc, float a, float n) { acc += (double)(a * n); }
 // acc += (double)v element by element (compute.c:203)
 __device__ __forceinline__ void add_elements(double &acc, v2f v)
 {
         acc += (double)v.x;
         acc += (double)v.y;
 }
-__device__ __forceinline__ void add_elements(double &acc, float v) { acc += (double)v; }
 // The operand screen of the short division / sqrt sequences, on bit patterns and for a whole row at once (make_y in
 // k_gradient): a loaded pixel is outside the range for which the short paths are exact when 0 < |y| < 2^-20, |y| >= 2^41
 // or it is a NaN.  Flat regions whose pixels are rounding noise around 0 (1e-17 in the chroma of a grey area) do occur
@@ -518,27 +483,19 @@ __device__ __forceinline__ void screen_update(unsigned &hi, unsigned &lo, v2f y)
         hi = max(hi, max(u.x, u.y));
         lo = min(lo, min(um.x, um.y));
 }
-__device__ __forceinline__ void screen_update(unsigned &hi, unsigned &lo, float y)
-{
-        const unsigned u = __builtin_bit_cast(unsigned, y) & 0x7fffffffu;
-        hi = max(hi, u);
-        lo = min(lo, u - 1u);
-}
 
 // shared part of the division: reciprocal refined by one Newton step
-template <class V>
-__device__ __forceinline__ V div_prepare(V d)
+__device__ __forceinline__ v2f div_prepare(v2f d)
 {
-        const V r = hw_rcp(d);
-        const V e = pk_fma(-d, r, splat<V>(1.f));
+        const v2f r = hw_rcp(d);
+        const v2f e = pk_fma(-d, r, splat(1.f));
         return pk_fma(e, r, r);
 }
 // x / d given r = div_prepare(d)
-template <class V>
-__device__ __forceinline__ V div_shared(V x, V d, V r)
+__device__ __forceinline__ v2f div_shared(v2f x, v2f d, v2f r)
 {
-        const V q0 = x * r;
-        const V q1 = pk_fma(pk_fma(-d, q0, x), r, q0);
+        const v2f q0 = x * r;
+        const v2f q1 = pk_fma(pk_fma(-d, q0, x), r, q0);
         return pk_fma(pk_fma(-d, q1, x), r, q1);
 }
 // ---- the SHORT division ----
@@ -546,26 +503,24 @@ __device__ __forceinline__ V div_shared(V x, V d, V r)
 // e = x - d q0 (exact, one fma), q = RN(q0 + e r) is RN(x / d).  Three operations per quotient instead of five.
 // Not taken on trust: j2p_division_exhaustive enumerates EVERY denominator mantissa against EVERY numerator mantissa
 // (2^46 quotients, GPU test) with r = 1.f / d; operand ranges as for div_shared (no intermediate can be subnormal).
-template <class V>
-__device__ __forceinline__ V recip_exact(V d, V seed)
+__device__ __forceinline__ v2f recip_exact(v2f d, v2f seed)
 {
-        const V one = splat<V>(1.f);
-        const V r1 = pk_fma(pk_fma(-d, seed, one), seed, seed);
+        const v2f one = splat(1.f);
+        const v2f r1 = pk_fma(pk_fma(-d, seed, one), seed, seed);
         return pk_fma(pk_fma(-d, r1, one), r1, r1);
 }
-template <class V>
-__device__ __forceinline__ V div_exact_recip(V x, V d, V r)
+__device__ __forceinline__ v2f div_exact_recip(v2f x, v2f d, v2f r)
 {
-        const V q0 = x * r;
+        const v2f q0 = x * r;
         return pk_fma(pk_fma(-d, q0, x), r, q0);
 }
 
 // the same for N numerators over one denominator, written breadth-first so that the N
 // independent fma chains are interleaved instead of issued back to back
-template <int N, class V>
-__device__ __forceinline__ void div_shared_n(const V (&x)[N], V d, V r, V (&q)[N])
+template <int N>
+__device__ __forceinline__ void div_shared_n(const v2f (&x)[N], v2f d, v2f r, v2f (&q)[N])
 {
-        V q0[N], e0[N], q1[N], e1[N];
+        v2f q0[N], e0[N], q1[N], e1[N];
 #pragma unroll
         for(int i = 0; i < N; i++) { q0[i] = x[i] * r; }
 #pragma unroll
@@ -594,24 +549,11 @@ __device__ __forceinline__ v2f sqrt_fast(v2f x)
         r = v2f{vs.x > 0.f ? up.x : r.x, vs.y > 0.f ? up.y : r.y};
         return r;
 }
-__device__ __forceinline__ float sqrt_fast(float x)
-{
-        const float s = __builtin_amdgcn_sqrtf(x);
-        const int si = __builtin_bit_cast(int, s);
-        const float dn = __builtin_bit_cast(float, si - 1), up = __builtin_bit_cast(float, si + 1);
-        const float vp = pk_fma(-dn, s, x), vs = pk_fma(-up, s, x);
-        float r = vp <= 0.f ? dn : s;
-        r = vs > 0.f ? up : r;
-        return r;
-}
 
-constexpr int kStripCols = 124;   // output columns per wavefront strip with two columns per lane (one: 60)
-#ifndef J2P_RING
-#define J2P_RING 4
-#endif
-constexpr int kRing = J2P_RING;   // row slots = hand-unroll factor of the marching loop (1 channel; 3 otherwise: registers);
-                                  // rows are fetched (slots - 1) trips ahead (3 slots: 12 % slower; 2 or 5 ring turns per
-                                  // loop iteration: slower too)
+constexpr int kStripCols = 124;   // output columns per wavefront strip: 128 loaded, two halo columns on each side
+constexpr int kRing = 4;          // row slots = hand-unroll factor of the marching loop; rows are fetched (slots - 1) trips
+                                  // ahead (3 slots: 12 % slower; 2 or 5 ring turns per loop iteration: slower too; 3 slots at
+                                  // five wavefronts per SIMD, see kGradWaves: a percent either way)
 
 // compile-time description of a strip for k_gradient's march: `value` = it touches no image / band / coverage
 // edge (clamps and masks are the identity), `unit` = additionally every channel of the wavefront is sampled 1x1
@@ -622,10 +564,10 @@ struct MarchTag {
         static constexpr bool unit = UNIT;
 };
 
-template <int NCH, bool TGV, class V = v2f>
+// what a pixel's neighbours need from it, for the wavefront's channel (see march_rows)
 struct SourceTerms {
-        V tvx[NCH], tvo[NCH], tvy[NCH];                           // TV: to (x+1) (shifted at its use), own, to the row below
-        V A[NCH], O[NCH], B[NCH], C[NCH];                         // TGV2 (A and C are shifted left / right at their uses)
+        v2f tvx, tvo, tvy;                                          // TV: to (x+1) (shifted at its use), own, to the row below
+        v2f A, O, B, C;                                             // TGV2 (A and C are shifted left / right at their uses)
 };
 
 // sqrtf for 2^-100 <= x < 2^127 through the reciprocal square root: the compiler's own expansion
@@ -633,22 +575,20 @@ struct SourceTerms {
 // and a final residual correction).  Correctly rounded on that whole range — checked
 // EXHAUSTIVELY against sqrtf() by j2p_sqrt_exhaustive (every float, GPU test).  Not valid for 0.
 // `r` receives the v_rsq_f32 values the root was made of.
-template <class V>
-__device__ __forceinline__ V sqrt_rsq(V x, V &r)
+__device__ __forceinline__ v2f sqrt_rsq(v2f x, v2f &r)
 {
         r = hw_rsq(x);
-        V s = x * r;
-        V h = r * 0.5f;
-        const V e = pk_fma(-h, s, splat<V>(0.5f));
+        v2f s = x * r;
+        v2f h = r * 0.5f;
+        const v2f e = pk_fma(-h, s, splat(0.5f));
         h = pk_fma(h, e, h);
         s = pk_fma(s, e, s);
-        const V d = pk_fma(-s, s, x);
+        const v2f d = pk_fma(-s, s, x);
         return pk_fma(d, h, s);
 }
-template <class V>
-__device__ __forceinline__ V sqrt_rsq(V x)
+__device__ __forceinline__ v2f sqrt_rsq(v2f x)
 {
-        V r;
+        v2f r;
         return sqrt_rsq(x, r);
 }
 
@@ -657,16 +597,16 @@ __device__ __forceinline__ V sqrt_rsq(V x)
 // screened path x is 0 or >= 2^-88, so x + 2^-120 is x itself unless x == 0, where the root comes
 // out as exactly 2^-60 (checked by j2p_math_selftest) — one add instead of clamping both
 // the radicand and the root.
-template <bool FAST, bool EXACT_ZERO, class V>
-__device__ __forceinline__ V sqrt_pair(V x)
+template <bool FAST, bool EXACT_ZERO>
+__device__ __forceinline__ v2f sqrt_pair(v2f x)
 {
         if(!FAST) { return ieee_sqrt(x); }
         if(EXACT_ZERO) { return sqrt_fast(x); }
-        return sqrt_rsq(x + splat<V>(0x1p-120f));
+        return sqrt_rsq(x + splat(0x1p-120f));
 }
 // divisor for the quotients of a pixel whose norm is n (see sqrt_pair)
-template <bool FAST, bool EXACT_ZERO, class V>
-__device__ __forceinline__ V divisor_of(V n)
+template <bool FAST, bool EXACT_ZERO>
+__device__ __forceinline__ v2f divisor_of(v2f n)
 {
         if(!FAST) { return one_if_zero(n); }                                       // divide by 1, scale by 0
         if(EXACT_ZERO) { return at_least(n, 0x1p-60f); }
@@ -680,12 +620,12 @@ __device__ __forceinline__ V divisor_of(V n)
 // radicand x every numerator enumerated, clean except at those norms).  The march sends rows that may hold such a
 // norm down the unscreened path (allones_candidate).  Per pixel pair 4 + 7 x 3 packed operations instead of
 // 2 + 2 transcendental + 7 x 5.
-template <bool FAST, bool EXACT_ZERO, class V>
-__device__ __forceinline__ void norm_and_reciprocal(V x, V &n, V &d, V &r)
+template <bool FAST, bool EXACT_ZERO>
+__device__ __forceinline__ void norm_and_reciprocal(v2f x, v2f &n, v2f &d, v2f &r)
 {
         if constexpr(FAST && !EXACT_ZERO) {
-                V seed;
-                n = sqrt_rsq(x + splat<V>(0x1p-120f), seed);
+                v2f seed;
+                n = sqrt_rsq(x + splat(0x1p-120f), seed);
                 d = n;
                 r = recip_exact(d, seed);
         } else {
@@ -695,8 +635,8 @@ __device__ __forceinline__ void norm_and_reciprocal(V x, V &n, V &d, V &r)
                 else { r = d; }
         }
 }
-template <bool FAST, bool EXACT_ZERO, int N, class V>
-__device__ __forceinline__ void div_n(const V (&x)[N], V d, V r, V (&q)[N])
+template <bool FAST, bool EXACT_ZERO, int N>
+__device__ __forceinline__ void div_n(const v2f (&x)[N], v2f d, v2f r, v2f (&q)[N])
 {
         if constexpr(FAST && !EXACT_ZERO) {
 #pragma unroll
@@ -721,12 +661,6 @@ __device__ __forceinline__ bool allones_candidate(v2f r1, v2f r2)
                                                 __builtin_elementwise_max(__builtin_bit_cast(v2h, b.x), __builtin_bit_cast(v2h, b.y)));
         return m.x >= (unsigned short)0xfffe;
 }
-__device__ __forceinline__ bool allones_candidate(float r1, float r2)
-{
-        typedef unsigned short v2h __attribute__((ext_vector_type(2)));
-        const v2h m = __builtin_elementwise_max(__builtin_bit_cast(v2h, r1), __builtin_bit_cast(v2h, r2));
-        return m.x >= (unsigned short)0xfffe;
-}
 
 // The four TGV2 numerators of a pixel (compute.c:165-182): s + gxx, gyy + s, s (its sign goes onto the quotient)
 // and the own term 2 gxx + 2 s + 2 gyy.  On the screened path every operand is a multiple of 2^-44 below 2^43, so
@@ -734,8 +668,8 @@ __device__ __forceinline__ bool allones_candidate(float r1, float r2)
 // first numerator (float addition commutes) — and the factor 2 moves through the division and onto the weight:
 // a2 * -((2 m) / n) == (2 a2) * -(m / n), all of it exact scaling.  Three multiplications and one addition less
 // per pixel; the unscreened path (subnormal operands possible) keeps the reference's expression.
-template <bool FAST, class V>
-__device__ __forceinline__ void tgv_numerators(V xx, V sy, V yy, V (&num)[4])
+template <bool FAST>
+__device__ __forceinline__ void tgv_numerators(v2f xx, v2f sy, v2f yy, v2f (&num)[4])
 {
         num[0] = sy + xx;
         num[1] = yy + sy;
@@ -743,8 +677,8 @@ __device__ __forceinline__ void tgv_numerators(V xx, V sy, V yy, V (&num)[4])
         if(FAST) { num[3] = num[0] + yy; }
         else { num[3] = 2.f * xx + 2.f * sy + 2.f * yy; }
 }
-template <bool FAST, class V>
-__device__ __forceinline__ V own_term(V a2, V q3)
+template <bool FAST>
+__device__ __forceinline__ v2f own_term(v2f a2, v2f q3)
 {
         if(FAST) { return (2.f * a2) * -q3; }       // 2 a2: exact and wave-uniform (hoisted out of the march)
         return a2 * -q3;
@@ -757,65 +691,48 @@ __device__ __forceinline__ V own_term(V a2, V q3)
 //                    path) — from which the march decides which path the row takes
 //   source_finish  : norms, quotients, weights.  FAST: the screened path (short sequences, see norm_and_reciprocal);
 //                    otherwise plain `/` and sqrtf().  tv / tv2 receive the log sums when `log_row`.
-template <int NCH, bool TGV, class V = v2f>
 struct SourcePrep {
-        V n1r, n2r;                                // gx^2 + gy^2 summed over the channels; the TGV2 counterpart
-        V xx[NCH], sy[NCH], yy[NCH];
+        v2f n1r, n2r;                                // gx^2 + gy^2 summed over the image's channels; the TGV2 counterpart
+        v2f xx, sy, yy;                              // the second differences of the wavefront's own channel
 };
 
-template <int NCH, bool TGV, bool MASKED, class V>
-__device__ __forceinline__ void source_prepare(const V (&gx)[NCH], const V (&gy)[NCH], const V (&gxp)[NCH],
-                                               const V (&gyp)[NCH], V m_hx, V m_hy, SourcePrep<NCH, TGV, V> &p)
+// (one-channel images; the channels of a joint image meet in source_prepare_joint)
+template <bool TGV, bool MASKED>
+__device__ __forceinline__ void source_prepare(v2f gx, v2f gy, v2f gxp, v2f gyp, v2f m_hx, v2f m_hy, SourcePrep &p)
 {
         // ---- TV (compute.c:84-89) ----
         // (the reference starts the sum at 0.f; a square is never -0, so 0.f + gx * gx is gx * gx bit for bit)
-        V n1 = gx[0] * gx[0];
-        n1 += gy[0] * gy[0];
-#pragma unroll
-        for(int c = 1; c < NCH; c++) {
-                n1 += gx[c] * gx[c];
-                n1 += gy[c] * gy[c];
-        }
+        v2f n1 = gx * gx;
+        n1 += gy * gy;
         p.n1r = n1;
-        p.n2r = splat<V>(0.f);
+        p.n2r = splat(0.f);
         // ---- TGV2 (compute.c:136-152) ----
         if(TGV) {
-                V n2 = splat<V>(0.f);
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        // MASKED == false: the caller knows every mask is 1 here (v * 1.f is v, so dropping
-                        // the products changes no bit)
-                        p.xx[c] = MASKED ? minus_left_of(gx[c]) * m_hx : minus_left_of(gx[c]);
-                        const V gyx = MASKED ? minus_left_of(gy[c]) * m_hx : minus_left_of(gy[c]);
-                        const V gxy = MASKED ? (gx[c] - gxp[c]) * m_hy : gx[c] - gxp[c];
-                        p.yy[c] = MASKED ? (gy[c] - gyp[c]) * m_hy : gy[c] - gyp[c];
-                        p.sy[c] = (gxy + gyx) * 0.5f;                     // (g_xy + g_yx) / 2.
-                        const V term = p.xx[c] * p.xx[c] + 2.f * (p.sy[c] * p.sy[c]) + p.yy[c] * p.yy[c];
-                        if(c == 0) { n2 = term; }                       // 0.f + term is term: never -0
-                        else { n2 += term; }
-                }
-                p.n2r = n2;
+                // MASKED == false: the caller knows every mask is 1 here (v * 1.f is v, so dropping
+                // the products changes no bit)
+                p.xx = MASKED ? minus_left_of(gx) * m_hx : minus_left_of(gx);
+                const v2f gyx = MASKED ? minus_left_of(gy) * m_hx : minus_left_of(gy);
+                const v2f gxy = MASKED ? (gx - gxp) * m_hy : gx - gxp;
+                p.yy = MASKED ? (gy - gyp) * m_hy : gy - gyp;
+                p.sy = (gxy + gyx) * 0.5f;                     // (g_xy + g_yx) / 2.
+                p.n2r = p.xx * p.xx + 2.f * (p.sy * p.sy) + p.yy * p.yy;   // 0.f + term is term: never -0
         }
 }
 
 // source_finish on the screened path without log sums (the hot one), LEVEL BY LEVEL.  The arithmetic is that of
 // norm_and_reciprocal<true, false> + div_exact_recip, operation for operation — sqrt_rsq and recip_exact for the two norms,
 // then one residual correction per quotient — but written breadth-first: the two norm chains side by side, the 7 quotient
-// chains of a channel side by side, with a scheduling barrier for vector instructions between the levels.  Why: on gfx950 a
+// chains side by side, with a scheduling barrier for vector instructions between the levels.  Why: on gfx950 a
 // packed f32 operation needs a wait state before an instruction that reads its result, and left to itself the compiler
 // emits each chain depth-first — 30 of the hot march's 250 instructions per row trip were `s_nop 0` between a v_pk_fma and
 // the v_pk_fma that consumes it (tools/isa_count.py), each one an issue slot of the wavefront.  Same bits, fewer slots.
-#ifndef J2P_LEVELS
-#define J2P_LEVELS 1
-#endif
 #define J2P_LEVEL_END() __builtin_amdgcn_sched_barrier(0x0094)      /* SALU, VMEM and DS may cross; vector ALU work may not */
-template <int NCH, bool TGV, class V>
-__device__ __forceinline__ void source_finish_levels(const V (&gx)[NCH], const V (&gy)[NCH], const SourcePrep<NCH, TGV, V> &p, float a_tv,
-                                                     float a_tgv, SourceTerms<NCH, TGV, V> &s)
+template <bool TGV>
+__device__ __forceinline__ void source_finish_levels(v2f gx, v2f gy, const SourcePrep &p, float a_tv, float a_tgv, SourceTerms &s)
 {
         constexpr int K = TGV ? 2 : 1;                         // norms: TV, TGV2
-        const V one = splat<V>(1.f), half = splat<V>(0.5f), tiny = splat<V>(0x1p-120f);
-        V x[K], r[K], sq[K], h[K], e[K], n[K], rc[K];
+        const v2f one = splat(1.f), half = splat(0.5f), tiny = splat(0x1p-120f);
+        v2f x[K], r[K], sq[K], h[K], e[K], n[K], rc[K];
         x[0] = p.n1r + tiny;
         if(TGV) { x[K - 1] = p.n2r + tiny; }
         // ---- sqrt_rsq ----
@@ -829,27 +746,22 @@ __device__ __forceinline__ void source_finish_levels(const V (&gx)[NCH], const V
 #pragma unroll
         for(int k = 0; k < K; k++) { e[k] = pk_fma(-h[k], sq[k], half); }
         // (numerators have nothing to do with the norms: they fill the slots between the levels of the two chains)
-        V num[NCH][TGV ? 7 : 3];
-        const V a1 = splat<V>(a_tv), a2 = splat<V>(a_tgv);
-#pragma unroll
-        for(int c = 0; c < NCH; c++) {
-                num[c][0] = a1 * gx[c];
-                num[c][1] = a1 * gy[c];
-                num[c][2] = a1 * -(gx[c] + gy[c]);
-        }
+        constexpr int Q = TGV ? 7 : 3;
+        v2f num[Q];
+        const v2f a1 = splat(a_tv), a2 = splat(a_tgv);
+        num[0] = a1 * gx;
+        num[1] = a1 * gy;
+        num[2] = a1 * -(gx + gy);
         J2P_LEVEL_END();
 #pragma unroll
         for(int k = 0; k < K; k++) { h[k] = pk_fma(h[k], e[k], h[k]); }
 #pragma unroll
         for(int k = 0; k < K; k++) { sq[k] = pk_fma(sq[k], e[k], sq[k]); }
         if(TGV) {
+                v2f t4[4];
+                tgv_numerators<true>(p.xx, p.sy, p.yy, t4);
 #pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        V t4[4];
-                        tgv_numerators<true>(p.xx[c], p.sy[c], p.yy[c], t4);
-#pragma unroll
-                        for(int i = 0; i < 4; i++) { num[c][(TGV ? 3 : 0) + i] = t4[i]; }
-                }
+                for(int i = 0; i < 4; i++) { num[(TGV ? 3 : 0) + i] = t4[i]; }
         }
         J2P_LEVEL_END();
 #pragma unroll
@@ -872,89 +784,68 @@ __device__ __forceinline__ void source_finish_levels(const V (&gx)[NCH], const V
         for(int k = 0; k < K; k++) { rc[k] = pk_fma(e[k], h[k], h[k]); }
         J2P_LEVEL_END();
         // ---- the quotients: q0 = RN(x r), q = RN(q0 + (x - d q0) r)  (div_exact_recip) ----
-        constexpr int Q = TGV ? 7 : 3;
-        V q0[NCH][Q], er[NCH][Q];
+        v2f q0[Q], er[Q];
 #pragma unroll
-        for(int c = 0; c < NCH; c++) {
-#pragma unroll
-                for(int i = 0; i < Q; i++) { q0[c][i] = num[c][i] * rc[i < 3 ? 0 : K - 1]; }
-        }
+        for(int i = 0; i < Q; i++) { q0[i] = num[i] * rc[i < 3 ? 0 : K - 1]; }
         J2P_LEVEL_END();
 #pragma unroll
-        for(int c = 0; c < NCH; c++) {
-#pragma unroll
-                for(int i = 0; i < Q; i++) { er[c][i] = pk_fma(-n[i < 3 ? 0 : K - 1], q0[c][i], num[c][i]); }
-        }
+        for(int i = 0; i < Q; i++) { er[i] = pk_fma(-n[i < 3 ? 0 : K - 1], q0[i], num[i]); }
         J2P_LEVEL_END();
 #pragma unroll
-        for(int c = 0; c < NCH; c++) {
-#pragma unroll
-                for(int i = 0; i < Q; i++) { q0[c][i] = pk_fma(er[c][i], rc[i < 3 ? 0 : K - 1], q0[c][i]); }
-        }
+        for(int i = 0; i < Q; i++) { q0[i] = pk_fma(er[i], rc[i < 3 ? 0 : K - 1], q0[i]); }
         J2P_LEVEL_END();
-#pragma unroll
-        for(int c = 0; c < NCH; c++) {
-                s.tvx[c] = q0[c][0];
-                s.tvy[c] = q0[c][1];
-                s.tvo[c] = q0[c][2];
-                if(TGV) {
-                        s.A[c] = a2 * q0[c][Q - 4];                                     // to (x-1,y), (x+1,y)
-                        s.B[c] = a2 * q0[c][Q - 3];                                     // to (x,y-1), (x,y+1)
-                        s.C[c] = a2 * -q0[c][Q - 2];                                    // to (x+1,y-1), (x-1,y+1)
-                        s.O[c] = own_term<true>(a2, q0[c][Q - 1]);                      // own
-                }
+        s.tvx = q0[0];
+        s.tvy = q0[1];
+        s.tvo = q0[2];
+        if(TGV) {
+                s.A = a2 * q0[Q - 4];                                     // to (x-1,y), (x+1,y)
+                s.B = a2 * q0[Q - 3];                                     // to (x,y-1), (x,y+1)
+                s.C = a2 * -q0[Q - 2];                                    // to (x+1,y-1), (x-1,y+1)
+                s.O = own_term<true>(a2, q0[Q - 1]);                      // own
         }
 }
 
-template <int NCH, bool TGV, bool LOG, bool FAST, class V>
-__device__ __forceinline__ void source_finish(const V (&gx)[NCH], const V (&gy)[NCH], const SourcePrep<NCH, TGV, V> &p, float a_tv,
-                                              float a_tgv, bool log_row, double &tv, double &tv2, SourceTerms<NCH, TGV, V> &s)
+template <bool TGV, bool LOG, bool FAST>
+__device__ __forceinline__ void source_finish(v2f gx, v2f gy, const SourcePrep &p, float a_tv, float a_tgv, bool log_row, double &tv,
+                                              double &tv2, SourceTerms &s)
 {
-#if J2P_LEVELS
-        if constexpr(FAST && !LOG && NCH == 1) {
+        if constexpr(FAST && !LOG) {
                 (void)log_row; (void)tv; (void)tv2;
-                source_finish_levels<NCH, TGV, V>(gx, gy, p, a_tv, a_tgv, s);
+                source_finish_levels<TGV>(gx, gy, p, a_tv, a_tgv, s);
                 return;
         }
-#endif
         // ---- TV (compute.c:90-104) ----
-        V n1, d1, r1;
+        v2f n1, d1, r1;
         norm_and_reciprocal<FAST, LOG>(p.n1r, n1, d1, r1);
         if(LOG && log_row) { add_scaled(tv, a_tv, n1); }
         // A pixel with zero norm contributes nothing (compute.c:97).  Screened path: n == 0 implies
         // every numerator is exactly 0 (no square can underflow), so any positive divisor gives 0.
         // Unscreened path: divide by 1, scale by 0.
-        const V a1 = FAST ? splat<V>(a_tv) : weight_unless_zero(n1, a_tv);
-#pragma unroll
-        for(int c = 0; c < NCH; c++) {
-                if(NCH > 1) { __builtin_amdgcn_sched_barrier(0); }   // one channel at a time: bounds the live ranges
-                const V num[3] = {a1 * gx[c], a1 * gy[c], a1 * -(gx[c] + gy[c])};
-                V q[3];
+        const v2f a1 = FAST ? splat(a_tv) : weight_unless_zero(n1, a_tv);
+        {
+                const v2f num[3] = {a1 * gx, a1 * gy, a1 * -(gx + gy)};
+                v2f q[3];
                 div_n<FAST, LOG, 3>(num, d1, r1, q);
-                s.tvx[c] = q[0];
-                s.tvy[c] = q[1];
-                s.tvo[c] = q[2];
+                s.tvx = q[0];
+                s.tvy = q[1];
+                s.tvo = q[2];
         }
         // ---- TGV2 (compute.c:153-183) ----
         if(TGV) {
-                V n2, d2, r2;
+                v2f n2, d2, r2;
                 norm_and_reciprocal<FAST, LOG>(p.n2r, n2, d2, r2);
                 if(LOG && log_row) { add_scaled(tv2, a_tgv, n2); }
-                const V a2 = FAST ? splat<V>(a_tgv) : weight_unless_zero(n2, a_tgv);   // compute.c:158
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        if(NCH > 1) { __builtin_amdgcn_sched_barrier(0); }
-                        // a2 * (expr / n2): division first (compute.c:165-182)
-                        // the two negative numerators are divided as positives and the sign goes onto the quotient:
-                        // (-v) / n == -(v / n) bit for bit, in the IEEE and in the short sequences alike
-                        V num[4], q[4];
-                        tgv_numerators<FAST>(p.xx[c], p.sy[c], p.yy[c], num);
-                        div_n<FAST, LOG, 4>(num, d2, r2, q);
-                        s.A[c] = a2 * q[0];                                             // to (x-1,y), (x+1,y)
-                        s.B[c] = a2 * q[1];                                             // to (x,y-1), (x,y+1)
-                        s.C[c] = a2 * -q[2];                                            // to (x+1,y-1), (x-1,y+1)
-                        s.O[c] = own_term<FAST>(a2, q[3]);                              // own
-                }
+                const v2f a2 = FAST ? splat(a_tgv) : weight_unless_zero(n2, a_tgv);   // compute.c:158
+                // a2 * (expr / n2): division first (compute.c:165-182)
+                // the two negative numerators are divided as positives and the sign goes onto the quotient:
+                // (-v) / n == -(v / n) bit for bit, in the IEEE and in the short sequences alike
+                v2f num[4], q[4];
+                tgv_numerators<FAST>(p.xx, p.sy, p.yy, num);
+                div_n<FAST, LOG, 4>(num, d2, r2, q);
+                s.A = a2 * q[0];                                             // to (x-1,y), (x+1,y)
+                s.B = a2 * q[1];                                             // to (x,y-1), (x,y+1)
+                s.C = a2 * -q[2];                                            // to (x+1,y-1), (x-1,y+1)
+                s.O = own_term<FAST>(a2, q[3]);                              // own
         }
 }
 
@@ -963,36 +854,36 @@ __device__ __forceinline__ void source_finish(const V (&gx)[NCH], const V (&gy)[
 // the channels (compute.c:84-89, 148-152): every wavefront publishes the squares of its own
 // differences, and after one barrier every wavefront adds them up in the reference's order
 // ((((0 + gx0^2) + gy0^2) + gx1^2) + ... ; per-channel Hessian terms likewise), so all of them
-// hold bit-identical sums — and take the same path — and the rest of the work (source_finish<1, ...>)
+// hold bit-identical sums — and take the same path — and the rest of the work (source_finish)
 // stays private to the channel.  `xchg` is a double-buffered LDS area: [2][J][64 lanes][3] pixel vectors.
-template <int J, bool TGV, bool MASKED, class V>
-__device__ __forceinline__ void source_prepare_joint(int cidx, int lane, int parity, V *xchg, V gx, V gy, V gxp, V gyp,
-                                                     V m_hx, V m_hy, SourcePrep<1, TGV, V> &p)
+template <int J, bool TGV, bool MASKED>
+__device__ __forceinline__ void source_prepare_joint(int cidx, int lane, int parity, v2f *xchg, v2f gx, v2f gy, v2f gxp, v2f gyp,
+                                                     v2f m_hx, v2f m_hy, SourcePrep &p)
 {
-        V xx = splat<V>(0.f), sy = xx, yy = xx, tq = xx;
+        v2f xx = splat(0.f), sy = xx, yy = xx, tq = xx;
         if(TGV) {
                 xx = MASKED ? minus_left_of(gx) * m_hx : minus_left_of(gx);
-                const V gyx = MASKED ? minus_left_of(gy) * m_hx : minus_left_of(gy);
-                const V gxy = MASKED ? (gx - gxp) * m_hy : gx - gxp;
+                const v2f gyx = MASKED ? minus_left_of(gy) * m_hx : minus_left_of(gy);
+                const v2f gxy = MASKED ? (gx - gxp) * m_hy : gx - gxp;
                 yy = MASKED ? (gy - gyp) * m_hy : gy - gyp;
                 sy = (gxy + gyx) * 0.5f;
                 tq = xx * xx + 2.f * (sy * sy) + yy * yy;
         }
-        p.xx[0] = xx;
-        p.sy[0] = sy;
-        p.yy[0] = yy;
-        V *mine = xchg + ((size_t)(parity * J + cidx) * 64 + lane) * 3;
+        p.xx = xx;
+        p.sy = sy;
+        p.yy = yy;
+        v2f *mine = xchg + ((size_t)(parity * J + cidx) * 64 + lane) * 3;
         mine[0] = gx * gx;
         mine[1] = gy * gy;
         mine[2] = tq;
         __syncthreads();
         // (sums start with channel 0's terms: 0.f + a square is the square, see source_prepare)
-        const V *o0 = xchg + ((size_t)(parity * J) * 64 + lane) * 3;
-        V n1 = o0[0], n2 = o0[2];
+        const v2f *o0 = xchg + ((size_t)(parity * J) * 64 + lane) * 3;
+        v2f n1 = o0[0], n2 = o0[2];
         n1 += o0[1];
 #pragma unroll
         for(int c = 1; c < J; c++) {
-                const V *o = xchg + ((size_t)(parity * J + c) * 64 + lane) * 3;
+                const v2f *o = xchg + ((size_t)(parity * J + c) * 64 + lane) * 3;
                 n1 += o[0];
                 n1 += o[1];
                 n2 += o[2];
@@ -1134,34 +1025,15 @@ __device__ __forceinline__ void fold_arrive(const GradArgs &a, unsigned tr, unsi
         if(lane == 0) { __hip_atomic_store(a.done_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 
-#ifndef J2P_GRAD_WAVES
-#define J2P_GRAD_WAVES 4
-#endif
-constexpr int kGradWaves1 = J2P_GRAD_WAVES;    // waves per SIMD the 1-channel gradient kernel is register-limited to (5 needs <= 96 VGPRs: spills)
-// ... except the hot instantiation — one channel per workgroup wavefront, no logging (Y-only planes, the components of `-s`):
-// with a ring of three row slots it fits 96 registers without a spill, i.e. five wavefronts per SIMD (round 5; the same
-// ring at four wavefronts and either ring in the joint / logging kernels do not: 20-56 bytes of scratch)
-#ifndef J2P_HOT_WAVES
-#define J2P_HOT_WAVES 4
-#endif
-#ifndef J2P_HOT_RING
-#define J2P_HOT_RING 4
-#endif
-constexpr int kHotWaves = J2P_HOT_WAVES, kHotRing = J2P_HOT_RING;
-// ... separately for the planes whose working set exceeds the Infinity Cache (NT >= 1: from ~15 Mpixel; no instantiation
-// more).  Measured with 5 / 3 there (profiles/r05_ab_five_wavefronts.jsonl): 4096^2 -0.2 %, 8192x4096 and 16384x2048
-// -1.0 %, 8192^2 +1.2 % — a percent either way again; stays 4 / 4
-#ifndef J2P_BIG_WAVES
-#define J2P_BIG_WAVES 4
-#endif
-#ifndef J2P_BIG_RING
-#define J2P_BIG_RING 4
-#endif
-constexpr int kBigWaves = J2P_BIG_WAVES, kBigRing = J2P_BIG_RING;
-constexpr int kGradWaves3 = 2;    // ... the three-channels-in-one-wavefront schedule
-// NCH channels are handled inside one wavefront (J == 1, workgroup = 4 strips), or — for a
-// jointly optimised image — J wavefronts of a workgroup take one channel each of the same strip
-// and only exchange their norm contributions through LDS (J > 1, NCH == 1).
+// wavefronts per SIMD every gradient kernel is built for (128 VGPRs).  5 needs <= 96 VGPRs: with the ring of four row slots
+// it spills; with a ring of THREE the hot instantiation (one channel per workgroup wavefront, no logging) fits without a
+// spill, the same ring at four wavefronts and either ring in the joint / logging kernels do not (20-56 bytes of scratch).
+// Measured with 5 / 3 (round 5; profiles/r05_ab_five_wavefronts.jsonl for the planes beyond the Infinity Cache): 4096^2
+// -0.2 %, 8192x4096 and 16384x2048 -1.0 %, 8192^2 +1.2 % — a percent either way; stays 4 wavefronts, 4 slots (kRing)
+constexpr int kGradWaves = 4;
+// One wavefront = one channel of one strip.  A one-channel image: the four wavefronts of a workgroup take four strips
+// (J == 1).  A jointly optimised image of J = 2 or 3 channels: the J wavefronts of a workgroup take one channel each of
+// the same strip and only exchange their norm contributions through LDS (source_prepare_joint).
 // NT (0..3): which streams bypass the caches' retention (non-temporal loads / stores), chosen by the solver from the
 // size of its working set against the 256 MiB Infinity Cache (nt_policy in j2p_solver_create).  x_k and x_{k-1} are
 // each touched two or three times per iteration and never get the hint; g (written by this kernel, read once by
@@ -1169,7 +1041,6 @@ constexpr int kGradWaves3 = 2;    // ... the three-channels-in-one-wavefront sch
 // d (read once per iteration by k_project) at 3.  What is left without the hint is what should stay cache-resident:
 // 4096^2 Y (288 MiB): level 1, 137 -> 127 us per iteration; 16384x2048 (576 MiB, the planes x_k, x_{k-1} are exactly
 // 256 MiB): level 3, 292 -> 240 us; when everything fits the hint costs 1-2 %.
-// PX: columns per lane (2: packed arithmetic, 128-column strips; 1: 64-column strips, see the pixel-vector overloads above)
 // What one wavefront of a gradient launch works on (wave-uniform; grad_item): strip `wcol`, band-local target rows
 // [t0, t0 + nrows) of tile row `tr` — the whole tile row (kind 0), one of its halves (kind 1) or quarters (kind 2; `sub`
 // says which), or tile rows tr AND tr + 1 (kind 3).  Half and quarter items exist so that the LAST workgroups of a launch
@@ -1185,23 +1056,23 @@ struct StripItem {
                                 // still takes part in its workgroup's hand-over
 };
 
-// The march of one wavefront over its item's rows: FISTA point, gradient, g stored; the sums of g^2 come back per lane in
-// the tile row's canonical order — lo = a0 + a1, hi = a2 + a3 with a_i the running sum over the tile row's i-th group of
-// FOUR rows (an item that covers only part of the tile row leaves the others 0) — so that the partial of a tile row,
-// (a0 + a1) + (a2 + a3) summed over the lanes, has the same bits whether one, two or four wavefronts marched it — or one
-// wavefront marched it together with the tile row below (second index of the sums: which of the item's tile rows).
-// xchg = the workgroup's LDS (joint images).
-template <int NCH, int J>
-constexpr int kItemTiles = NCH == 1 && J == 1 ? 2 : 1;       // tile rows an item can cover (double items: one channel per wavefront)
-template <int NCH, bool TGV, bool LOG, int J, int NT, int PX, class V>
-__device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const StripItem &it, double (&g2_lo)[NCH][kItemTiles<NCH, J>],
-                                           double (&g2_hi)[NCH][kItemTiles<NCH, J>], double &tv_acc, double &tv2_acc, unsigned long long &tr_data)
+// The march of one wavefront over its item's rows, for its one channel (a.ch[0], or a.ch[wave] of a joint image): FISTA
+// point, gradient, g stored; the sums of g^2 come back per lane in the tile row's canonical order — lo = a0 + a1,
+// hi = a2 + a3 with a_i the running sum over the tile row's i-th group of FOUR rows (an item that covers only part of the
+// tile row leaves the others 0) — so that the partial of a tile row, (a0 + a1) + (a2 + a3) summed over the lanes, has the
+// same bits whether one, two or four wavefronts marched it — or one wavefront marched it together with the tile row below
+// (the index of the sums: which of the item's tile rows).  xchg = the workgroup's LDS (joint images).
+template <int J>
+constexpr int kItemTiles = J == 1 ? 2 : 1;       // tile rows an item can cover (double items: one-channel images only)
+template <bool TGV, bool LOG, int J, int NT>
+__device__ __forceinline__ void march_rows(const GradArgs &a, v2f *xchg, const StripItem &it, double (&g2_lo)[kItemTiles<J>],
+                                           double (&g2_hi)[kItemTiles<J>], double &tv_acc, double &tv2_acc, unsigned long long &tr_data)
 {
-        constexpr int kCols = 64 * PX - 4;                      // output columns per strip: 2 halo columns on each side
+        constexpr int kCols = kStripCols;
         const int lane = (int)threadIdx.x & 63;
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // uniform: keeps row/strip arithmetic scalar
         const int wcol = it.wcol;
-        const int cbase = J == 1 ? 0 : wave;                    // first channel of this wavefront
+        const int chan = J == 1 ? 0 : wave;                     // the channel of this wavefront
         const int W = (int)a.geo.W, H = (int)a.geo.H;
         const int rows = (int)a.geo.rows, row0 = (int)a.geo.row0;
         const int t0 = it.t0;                                   // band-local target rows [t0, t1)
@@ -1209,24 +1080,18 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
         const int tile0 = it.tile0;
         // (the three scalars by value: read through `a` inside the lambdas they ended up in an LDS-promoted alloca)
         const float fista_factor = a.factor, w_tv = a.a_tv, w_tgv = a.a_tgv;
-        // Strip i loads columns [kCols i, kCols i + 64 PX); its two outermost columns on each side are halo — except
+        // Strip i loads columns [kCols i, kCols i + 128); its two outermost columns on each side are halo — except
         // at the image's left and right edges, where the neighbour beyond the edge contributes nothing anyway, so the
         // first strip also owns its left halo lanes and the last strip its right ones: n strips cover kCols n + 4
-        // columns (two columns per lane: 124 n + 4, 33 strips for W = 4096).
-        const int xl = wcol * kCols + lane * PX;               // canvas column of the lane's first pixel (W is a multiple of 8)
+        // columns (124 n + 4, 33 strips for W = 4096).
+        const int xl = wcol * kCols + lane * 2;                // canvas column of the lane's first pixel (W is a multiple of 8)
 
         const bool pair_in = xl >= 0 && xl < W;                // the lane's columns are in the image (both, or neither)
-        const bool pair_own = pair_in && (lane * PX >= 2 || wcol == 0) && (lane * PX + PX <= 64 * PX - 2 || wcol * kCols + 64 * PX >= W);
+        const bool pair_own = pair_in && (lane * 2 >= 2 || wcol == 0) && (lane * 2 + 2 <= 128 - 2 || wcol * kCols + 128 >= W);
         // per-lane constant masks (1.f / 0.f), multiplied instead of selected: v*1 is exact, v*0 = +-0
         const float in_f = pair_in ? 1.f : 0.f;
-        V m_gx, m_hx;
-        if constexpr(PX == 2) {
-                m_gx = v2f{in_f, xl + 1 >= W - 1 ? 0.f : in_f};     // gx = 0 on the last column (compute.c:79)
-                m_hx = v2f{xl == 0 ? 0.f : in_f, in_f};             // gxx, gyx = 0 on the first column
-        } else {
-                m_gx = xl >= W - 1 ? 0.f : in_f;
-                m_hx = xl == 0 ? 0.f : in_f;
-        }
+        const v2f m_gx = v2f{in_f, xl + 1 >= W - 1 ? 0.f : in_f};     // gx = 0 on the last column (compute.c:79)
+        const v2f m_hx = v2f{xl == 0 ? 0.f : in_f, in_f};             // gxx, gyx = 0 on the first column
 
         // Rows are fetched kRing-1 loop trips before they are needed: `fetch_row` only issues the
         // loads of x_k / x_{k-1} (raw values stay in the ring), `make_y` turns them into the FISTA
@@ -1234,25 +1099,24 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
         // lanes left/right of the image and rows above/below it read a clamped, valid address and
         // are zeroed by a mask afterwards — so the loop body is straight-line code and the compiler
         // can keep the younger loads in flight (counted s_waitcnt) instead of draining them.
-        const int xl_c = xl < 0 ? 0 : (xl > W - PX ? W - PX : xl);
+        const int xl_c = xl < 0 ? 0 : (xl > W - 2 ? W - 2 : xl);
         const unsigned xoff = (unsigned)xl_c * 4u;             // byte offset of the lane's pixel vector within a row
         // (rows t0 - 2 ... t1 + 1 are what the segment touches; the x buffers have 2 halo rows above the band's row 0)
         const int seg_base = t0 - 2, grad_base = t0;
-        __amdgpu_buffer_rsrc_t res_cur[NCH], res_prev[NCH], res_grad[NCH], res_pg[NCH];
-#pragma unroll
-        for(int c = 0; c < NCH; c++) {
-                const ChanDev &k = a.ch[cbase + c];
-                res_cur[c] = rows_from(k.xcur + (ptrdiff_t)seg_base * W);
-                res_prev[c] = rows_from(k.xprev + (ptrdiff_t)seg_base * W);
-                res_grad[c] = rows_from(k.grad + (ptrdiff_t)grad_base * W);
+        __amdgpu_buffer_rsrc_t res_cur, res_prev, res_grad, res_pg;
+        {
+                const ChanDev &k = a.ch[chan];
+                res_cur = rows_from(k.xcur + (ptrdiff_t)seg_base * W);
+                res_prev = rows_from(k.xprev + (ptrdiff_t)seg_base * W);
+                res_grad = rows_from(k.grad + (ptrdiff_t)grad_base * W);
                 // (the prob state of a unit-sampled channel, see load_p: coefficient row = canvas row)
-                res_pg[c] = rows_from(k.pg + (size_t)((unsigned)(row0 + grad_base) - k.crow0) * k.cw);
+                res_pg = rows_from(k.pg + (size_t)((unsigned)(row0 + grad_base) - k.crow0) * k.cw);
         }
         const int lr_lo = -(row0 < (int)kHalo ? row0 : (int)kHalo);                      // first readable band-local row
         const int lr_hi = rows - 1 + (H - row0 - rows < (int)kHalo ? H - row0 - rows : (int)kHalo);
         // FREE (a std::bool_constant, see `march` below): the strip is known to lie inside the image and the
         // band with room to spare, so the row clamps and every 0/1 mask are the identity and are left out
-        auto fetch_row = [&](auto free_tag, int lr, V (&rc)[NCH], V (&rp)[NCH]) {
+        auto fetch_row = [&](auto free_tag, int lr, v2f &rc, v2f &rp) {
                 constexpr bool FREE = decltype(free_tag)::value;
                 // rows past the strip's last needed row (t1+1) re-read that row: a cache hit, not HBM traffic
                 int lm = lr > t1 + 1 ? t1 + 1 : lr;
@@ -1262,15 +1126,12 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
                 const ptrdiff_t roff = (ptrdiff_t)lc * W;              // (the pointer form: what J2P_DEBUG checks)
                 (void)roff;
                 const unsigned row_off = (unsigned)(lc - seg_base) * (unsigned)W * 4u;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        J2P_CHK(a.ch[cbase + c], x_read[0], reinterpret_cast<const char *>(a.ch[cbase + c].xcur + roff) + xoff, 4 * PX, 101);
-                        J2P_CHK(a.ch[cbase + c], x_read[1], reinterpret_cast<const char *>(a.ch[cbase + c].xprev + roff) + xoff, 4 * PX, 102);
-                        rc[c] = buf_load<false, V>(res_cur[c], xoff, row_off);
-                        rp[c] = buf_load<false, V>(res_prev[c], xoff, row_off);
-                }
+                J2P_CHK(a.ch[chan], x_read[0], reinterpret_cast<const char *>(a.ch[chan].xcur + roff) + xoff, 8, 101);
+                J2P_CHK(a.ch[chan], x_read[1], reinterpret_cast<const char *>(a.ch[chan].xprev + roff) + xoff, 8, 102);
+                rc = buf_load2<false>(res_cur, xoff, row_off);
+                rp = buf_load2<false>(res_prev, xoff, row_off);
         };
-        auto make_y = [&](auto free_tag, int lr, const V (&rc)[NCH], const V (&rp)[NCH], V (&y)[NCH], unsigned &suspect) {
+        auto make_y = [&](auto free_tag, int lr, v2f rc, v2f rp, v2f &y, unsigned &suspect) {
                 constexpr bool FREE = decltype(free_tag)::value;
                 const int gr = row0 + lr;
                 const float m = gr >= 0 && gr < H ? in_f : 0.f;   // 0 outside the image
@@ -1279,121 +1140,103 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
                 // wraps to the top, so zeros drop out of the minimum).  Two compares per row, each feeding a
                 // ballot directly, so the flag is born in scalar registers.
                 unsigned hi = 0u, lo = ~0u;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        const V yy = rc[c] + fista_factor * (rc[c] - rp[c]);     // compute.c:435
-                        y[c] = FREE ? yy : yy * m;
-                        screen_update(hi, lo, y[c]);
-                }
+                const v2f yy = rc + fista_factor * (rc - rp);     // compute.c:435
+                y = FREE ? yy : yy * m;
+                screen_update(hi, lo, y);
                 constexpr unsigned kLo = 0x35800000u, kHi = 0x54000000u;      // bits of 2^-20 and 2^41
                 const unsigned long long out_of_range = __builtin_amdgcn_ballot_w64(hi >= kHi) | __builtin_amdgcn_ballot_w64(lo < kLo - 1u);
                 suspect = (unsigned)out_of_range | (unsigned)(out_of_range >> 32);   // wave-uniform, non-zero = suspect
         };
         // forward differences of row gr given rows gr and gr+1 (compute.c:79,81)
-        auto diffs = [&](auto free_tag, int gr, const V (&yc)[NCH], const V (&yn)[NCH], V (&gx)[NCH], V (&gy)[NCH]) {
+        auto diffs = [&](auto free_tag, int gr, v2f yc, v2f yn, v2f &gx, v2f &gy) {
                 constexpr bool FREE = decltype(free_tag)::value;
                 const float m_gy = gr >= 0 && gr < H - 1 ? 1.f : 0.f;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        gx[c] = FREE ? right_of_minus(yc[c]) : right_of_minus(yc[c]) * m_gx;
-                        gy[c] = FREE ? yn[c] - yc[c] : (yn[c] - yc[c]) * m_gy;
-                }
+                gx = FREE ? right_of_minus(yc) : right_of_minus(yc) * m_gx;
+                gy = FREE ? yn - yc : (yn - yc) * m_gy;
         };
 
         // prob-gradient state of one target row (compute.c:53-66: replicated over the sample's
         // footprint).  Loaded unconditionally from a clamped address; `pmask` (per lane) and the row
         // test at the point of use decide whether it contributes.  A channel with pweight == 0 has an
         // all-zero state buffer, so it needs no special case.
-        V p_scale[NCH];
-        int p_col[NCH][PX];
-#pragma unroll
-        for(int c = 0; c < NCH; c++) {
-                const ChanDev &k = a.ch[cbase + c];
+        v2f p_scale;
+        int p_col[2];
+        {
+                const ChanDev &k = a.ch[chan];
                 const bool on = k.prob_on && pair_own && (unsigned)xl < k.cw * k.ws;
-                p_scale[c] = splat<V>(on ? k.p_alpha : 0.f);
+                p_scale = splat(on ? k.p_alpha : 0.f);
                 const unsigned cmax = k.cw - 1;
 #pragma unroll
-                for(int e = 0; e < PX; e++) {
+                for(int e = 0; e < 2; e++) {
                         const unsigned ce = (unsigned)(xl_c + e) / k.ws;
-                        p_col[c][e] = (int)(ce > cmax ? cmax : ce) * 4;   // byte offsets within a coefficient row
+                        p_col[e] = (int)(ce > cmax ? cmax : ce) * 4;   // byte offsets within a coefficient row
                 }
         }
-        auto load_p = [&](auto free_tag, int lt, V (&pv)[NCH]) {
+        auto load_p = [&](auto free_tag, int lt, v2f &pv) {
                 constexpr bool FREE = decltype(free_tag)::value;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        const ChanDev &k = a.ch[cbase + c];
-                        // coefficient row of canvas row lt, clamped into the rows this band holds
-                        const int ltc = lt > t1 - 1 ? t1 - 1 : lt;                     // past the strip: re-read its last row
-                        const int gt = row0 + (FREE ? ltc : (ltc < 0 ? 0 : ltc));
-                        if constexpr(decltype(free_tag)::unit) {
-                                const float *prow = k.pg + (size_t)((unsigned)gt - k.crow0) * k.cw;
-                                J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + xoff, 4 * PX, 103);
-                                (void)prow;
-                                pv[c] = buf_load<(NT >= 2), V>(res_pg[c], xoff, (unsigned)(gt - row0 - grad_base) * k.cw * 4u);
-                                continue;
-                        }
-                        unsigned cr;
-                        if(k.hs == 1) { cr = (unsigned)gt; }                            // (uniform branch: skips the scalar division)
-                        else { cr = (unsigned)gt / k.hs; }
-                        if(!FREE) {
-                                const unsigned cr_hi = k.crow0 + (k.crows ? k.crows - 1 : 0);
-                                cr = cr < k.crow0 ? k.crow0 : (cr > cr_hi ? cr_hi : cr);
-                        }
-                        const float *prow = k.pg + (size_t)(cr - k.crow0) * k.cw;
-                        J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + (unsigned)p_col[c][0], 4, 104);
-                        if constexpr(PX == 2) {
-                                J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + (unsigned)p_col[c][1], 4, 105);
-                                pv[c] = v2f{*reinterpret_cast<const float *>(reinterpret_cast<const char *>(prow) + (unsigned)p_col[c][0]),
-                                            *reinterpret_cast<const float *>(reinterpret_cast<const char *>(prow) + (unsigned)p_col[c][1])};   // two dword loads whatever the sampling: no branch
-                        } else {
-                                pv[c] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(prow) + (unsigned)p_col[c][0]);
-                        }
+                const ChanDev &k = a.ch[chan];
+                // coefficient row of canvas row lt, clamped into the rows this band holds
+                const int ltc = lt > t1 - 1 ? t1 - 1 : lt;                     // past the strip: re-read its last row
+                const int gt = row0 + (FREE ? ltc : (ltc < 0 ? 0 : ltc));
+                if constexpr(decltype(free_tag)::unit) {
+                        const float *prow = k.pg + (size_t)((unsigned)gt - k.crow0) * k.cw;
+                        J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + xoff, 8, 103);
+                        (void)prow;
+                        pv = buf_load2<(NT >= 2)>(res_pg, xoff, (unsigned)(gt - row0 - grad_base) * k.cw * 4u);
+                        return;
                 }
+                unsigned cr;
+                if(k.hs == 1) { cr = (unsigned)gt; }                            // (uniform branch: skips the scalar division)
+                else { cr = (unsigned)gt / k.hs; }
+                if(!FREE) {
+                        const unsigned cr_hi = k.crow0 + (k.crows ? k.crows - 1 : 0);
+                        cr = cr < k.crow0 ? k.crow0 : (cr > cr_hi ? cr_hi : cr);
+                }
+                const float *prow = k.pg + (size_t)(cr - k.crow0) * k.cw;
+                J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + (unsigned)p_col[0], 4, 104);
+                J2P_CHK(k, pg, reinterpret_cast<const char *>(prow) + (unsigned)p_col[1], 4, 105);
+                pv = v2f{*reinterpret_cast<const float *>(reinterpret_cast<const char *>(prow) + (unsigned)p_col[0]),
+                         *reinterpret_cast<const float *>(reinterpret_cast<const char *>(prow) + (unsigned)p_col[1])};   // two dword loads whatever the sampling: no branch
         };
 
-        double g2[NCH];                                  // sum of g*g over the running group of four rows
-#pragma unroll
-        for(int c = 0; c < NCH; c++) { g2[c] = 0.; }
+        double g2 = 0.;                                  // sum of g*g over the running group of four rows
         // a group of four rows is complete (target row t was its last): into the tile row's lower or upper pair sum
         const int tile_rows = (int)a.geo.rpw;
         auto close_group = [&](int t) {
                 int rel = t - tile0;                             // (everything here is wave-uniform)
-                const bool second = kItemTiles<NCH, J> == 2 && rel >= tile_rows;
+                const bool second = kItemTiles<J> == 2 && rel >= tile_rows;
                 if(second) { rel -= tile_rows; }
                 const bool upper = (rel & 8) != 0;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        if constexpr(kItemTiles<NCH, J> == 2) {
-                                if(second) {
-                                        if(upper) { g2_hi[c][1] += g2[c]; }
-                                        else { g2_lo[c][1] += g2[c]; }
-                                } else {
-                                        if(upper) { g2_hi[c][0] += g2[c]; }
-                                        else { g2_lo[c][0] += g2[c]; }
-                                }
+                if constexpr(kItemTiles<J> == 2) {
+                        if(second) {
+                                if(upper) { g2_hi[1] += g2; }
+                                else { g2_lo[1] += g2; }
                         } else {
-                                if(upper) { g2_hi[c][0] += g2[c]; }
-                                else { g2_lo[c][0] += g2[c]; }
+                                if(upper) { g2_hi[0] += g2; }
+                                else { g2_lo[0] += g2; }
                         }
-                        g2[c] = 0.;
+                } else {
+                        if(upper) { g2_hi[0] += g2; }
+                        else { g2_lo[0] += g2; }
                 }
+                g2 = 0.;
         };
-        constexpr int R = NCH == 1 ? (J == 1 && !LOG && PX == 2 ? (NT >= 1 ? kBigRing : kHotRing) : kRing) : 3;
+        constexpr int R = kRing;
 
-        // The march over the strip's rows, compiled twice: once general, once for strips that touch neither an
-        // image edge, a band edge nor a channel's coverage limit (all but the outermost strips and segments).
-        // In the second form the clamps, compares and multiplications by 1.f disappear — about a seventh of the
-        // instructions of a trip, most of them scalar — and nothing else changes, so the bits are the same.
+        // The march over the strip's rows, compiled three times: general; for strips that touch neither an image edge,
+        // a band edge nor the channel's coverage limit (all but the outermost strips and segments); and for such strips
+        // of a channel sampled 1x1 (MarchTag).  In the second form the clamps, compares and multiplications by 1.f
+        // disappear — about a seventh of the instructions of a trip, most of them scalar — in the third the prob state
+        // is one load; nothing else changes, so the bits are the same.
         auto march = [&](auto free_tag) {
                 constexpr bool FREE = decltype(free_tag)::value;
                 // rings of kRing row slots, slot = (row - (t0-1)) mod kRing = phase of the trip that owns the row
-                V RC[R][NCH], RP[R][NCH], Y[R][NCH], GX[R][NCH], GY[R][NCH], PV[R][NCH];
+                v2f RC[R], RP[R], Y[R], GX[R], GY[R], PV[R];
                 unsigned bad1, bad2;   // screen results (non-zero = suspect) of the last two rows made; plain scalars
-                SourceTerms<NCH, TGV, V> S[R];
+                SourceTerms S[R];
                 {
                         // rows t0-2, t0-1, t0 are needed at once; rows up to t0+R-2 are put in flight
-                        V mc[NCH], mp[NCH], ym[NCH];
+                        v2f mc, mp, ym;
                         unsigned bm;
                         fetch_row(free_tag, t0 - 2, mc, mp);
                         fetch_row(free_tag, t0 - 1, RC[0], RP[0]);
@@ -1425,65 +1268,58 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
                         const unsigned badmask = bad2 | bad1 | bnew;        // rows r-1, r, r+1
                         bad2 = bad1;
                         bad1 = bnew;
-                        SourceTerms<NCH, TGV, V> &s = S[P];
+                        SourceTerms &s = S[P];
                         diffs(free_tag, gr, Y[P], Y[P1], GX[P], GY[P]);
                         {
                                 // A row above or below the image needs no special case: its y is 0, m_gy zeroes
                                 // its gy, and hy = 0 zeroes its gxy/gyy, so every term comes out 0.
-                                const bool log_row = LOG && pair_own && r >= t0 && r < t1 && cbase == 0;
+                                const bool log_row = LOG && pair_own && r >= t0 && r < t1 && chan == 0;
                                 const float hy = gr <= 0 || gr >= H ? 0.f : in_f;  // gxy, gyy = 0 on the first row (compute.c:141-143)
-                                const V m_hy = splat<V>(hy);
+                                const v2f m_hy = splat(hy);
                                 // second differences and the sums under the two norms (the same on every path), then the
                                 // path: screened unless the rows involved hold a value outside the screen's range or one
                                 // of the norms may have an all-ones mantissa (see norm_and_reciprocal)
-                                SourcePrep<NCH, TGV, V> prep;
+                                SourcePrep prep;
                                 if constexpr(J > 1) {
                                         const int parity = (r - t0 + 1) & 1;
-                                        source_prepare_joint<J, TGV, !FREE>(cbase, lane, parity, xchg, GX[P][0], GY[P][0], GX[PM1][0], GY[PM1][0],
-                                                                            m_hx, m_hy, prep);
+                                        source_prepare_joint<J, TGV, !FREE>(chan, lane, parity, xchg, GX[P], GY[P], GX[PM1], GY[PM1], m_hx, m_hy, prep);
                                 } else {
-                                        source_prepare<NCH, TGV, !FREE>(GX[P], GY[P], GX[PM1], GY[PM1], m_hx, m_hy, prep);
+                                        source_prepare<TGV, !FREE>(GX[P], GY[P], GX[PM1], GY[PM1], m_hx, m_hy, prep);
                                 }
                                 bool slow = badmask != 0;
                                 if constexpr(!LOG) { slow = slow || __builtin_amdgcn_ballot_w64(allones_candidate(prep.n1r, prep.n2r)) != 0; }
-                                if(!slow) { source_finish<NCH, TGV, LOG, true>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
-                                else { source_finish<NCH, TGV, LOG, false>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
+                                if(!slow) { source_finish<TGV, LOG, true>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
+                                else { source_finish<TGV, LOG, false>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
                         }
                         // ---- target row t = r-1: rows t-1, t, t+1 live in slots PM2, PM1, P ----
                         const int t = r - 1;
                         if(t >= t0) {
-                                const SourceTerms<NCH, TGV, V> &up = S[PM2], &mid = S[PM1];
+                                const SourceTerms &up = S[PM2], &mid = S[PM1];
                                 const int gt = row0 + t;
-        #pragma unroll
-                                for(int c = 0; c < NCH; c++) {
-                                        const ChanDev &k = a.ch[cbase + c];
-                                        V g = splat<V>(0.f);
-                                        if(FREE || (unsigned)gt < k.ch * k.hs) { g += p_scale[c] * PV[PM1][c]; }   // row t, fetched R-1 trips ago
-                                        g += up.tvy[c];                  // TV from (x, t-1)
-                                        g = add_left_of(g, mid.tvx[c]);  // TV from (x-1, t)
-                                        g += mid.tvo[c];                 // TV own
-                                        if(TGV) {
-                                                g += up.B[c];                    // (x,   t-1)
-                                                g = add_right_of(g, up.C[c]);    // (x+1, t-1)
-                                                g = add_left_of(g, mid.A[c]);    // (x-1, t)
-                                                g += mid.O[c];                   // own
-                                                g = add_right_of(g, mid.A[c]);   // (x+1, t)
-                                                g = add_left_of(g, s.C[c]);      // (x-1, t+1)
-                                                g += s.B[c];                     // (x,   t+1)
-                                        }
-                                        if(pair_own) {
-                                                J2P_CHK(k, grad, reinterpret_cast<char *>(k.grad + (size_t)t * W) + (unsigned)xl * 4u, 4 * PX, 106);
-                                                buf_store<(NT >= 1)>(g, res_grad[c], (unsigned)xl * 4u, (unsigned)(t - grad_base) * (unsigned)W * 4u);
-                                                add_elements(g2[c], g * g);      // compute.c:203
-                                        }
+                                const ChanDev &k = a.ch[chan];
+                                v2f g = splat(0.f);
+                                if(FREE || (unsigned)gt < k.ch * k.hs) { g += p_scale * PV[PM1]; }   // row t, fetched R-1 trips ago
+                                g += up.tvy;                  // TV from (x, t-1)
+                                g = add_left_of(g, mid.tvx);  // TV from (x-1, t)
+                                g += mid.tvo;                 // TV own
+                                if(TGV) {
+                                        g += up.B;                    // (x,   t-1)
+                                        g = add_right_of(g, up.C);    // (x+1, t-1)
+                                        g = add_left_of(g, mid.A);    // (x-1, t)
+                                        g += mid.O;                   // own
+                                        g = add_right_of(g, mid.A);   // (x+1, t)
+                                        g = add_left_of(g, s.C);      // (x-1, t+1)
+                                        g += s.B;                     // (x,   t+1)
+                                }
+                                if(pair_own) {
+                                        J2P_CHK(k, grad, reinterpret_cast<char *>(k.grad + (size_t)t * W) + (unsigned)xl * 4u, 8, 106);
+                                        buf_store<(NT >= 1)>(g, res_grad, (unsigned)xl * 4u, (unsigned)(t - grad_base) * (unsigned)W * 4u);
+                                        add_elements(g2, g * g);      // compute.c:203
                                 }
                                 // t0 is a multiple of 4 and the trip of phase 1 handles t = t0 - 1 + 4 i: with a ring of four
                                 // the place where groups end is known at compile time
-                                if constexpr(R == 4) {
-                                        if constexpr(P == 1) { close_group(t); }
-                                } else {
-                                        if(((t - t0) & 3) == 3) { close_group(t); }
-                                }
+                                static_assert(R == 4, "close_group is placed for a ring of four row slots");
+                                if constexpr(P == 1) { close_group(t); }
                         }
                 };
 
@@ -1494,14 +1330,8 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
                         trip(std::integral_constant<int, 1>{}, r + 1);
                         if(r + 2 > t1) { return false; }
                         trip(std::integral_constant<int, 2>{}, r + 2);
-                        if(R > 3) {
-                                if(r + 3 > t1) { return false; }
-                                trip(std::integral_constant<int, 3 % R>{}, r + 3);
-                        }
-                        if(R > 4) {
-                                if(r + 4 > t1) { return false; }
-                                trip(std::integral_constant<int, 4 % R>{}, r + 4);
-                        }
+                        if(r + 3 > t1) { return false; }
+                        trip(std::integral_constant<int, 3>{}, r + 3);
                         return r + R <= t1;
                 };
                 for(int r = t0 - 1; r <= t1; r += R) {
@@ -1509,20 +1339,12 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
                 }
         };
         {
-                bool seg_free = wcol > 0 && wcol * kCols + 64 * PX <= W - 1 &&           // no lane on the first / last column
-                                row0 + t0 - 2 >= 0 && row0 + t1 + 1 < H &&                // rows t0-2 .. t1+1 inside the image
-                                t0 - 2 >= lr_lo && t1 + 1 <= lr_hi;                       // ... and readable in this band
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        const ChanDev &k = a.ch[cbase + c];
-                        seg_free = seg_free && (unsigned)(row0 + t1) <= k.ch * k.hs;      // every target row is covered by the channel
-                }
-                bool unit = seg_free;
-#pragma unroll
-                for(int c = 0; c < NCH; c++) {
-                        const ChanDev &k = a.ch[cbase + c];
-                        unit = unit && k.ws == 1 && k.hs == 1 && (unsigned)(wcol * kCols + 64 * PX) <= k.cw;
-                }
+                const ChanDev &k = a.ch[chan];
+                const bool covered = (unsigned)(row0 + t1) <= k.ch * k.hs;                      // every target row is covered by the channel
+                const bool seg_free = wcol > 0 && wcol * kCols + 128 <= W - 1 &&               // no lane on the first / last column
+                                      row0 + t0 - 2 >= 0 && row0 + t1 + 1 < H &&                // rows t0-2 .. t1+1 inside the image
+                                      t0 - 2 >= lr_lo && t1 + 1 <= lr_hi && covered;            // ... and readable in this band
+                const bool unit = seg_free && k.ws == 1 && k.hs == 1 && (unsigned)(wcol * kCols + 128) <= k.cw;
                 if(__builtin_amdgcn_readfirstlane(unit ? 1 : 0)) { march(MarchTag<true, true>{}); }
                 else if(__builtin_amdgcn_readfirstlane(seg_free ? 1 : 0)) { march(MarchTag<true, false>{}); }
                 else { march(MarchTag<false, false>{}); }
@@ -1537,13 +1359,12 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, V *xchg, const Str
 // GPU-count invariant norm reduction — and report in (fold_arrive); the last strip of a tile row / of the launch to do so
 // finishes the reduction.  The wavefronts of a half / quarter item hand their sums to the workgroup's wavefront that
 // marched the tile row's first rows, through LDS (fold_buf).
-template <int NCH, bool TGV, bool LOG, int J, int NT, int PX, class V>
-__device__ __forceinline__ void gradient_strip(const GradArgs &a, V *xchg, double *fold_buf, const StripItem &it)
+template <bool TGV, bool LOG, int J, int NT>
+__device__ __forceinline__ void gradient_strip(const GradArgs &a, v2f *xchg, double *fold_buf, const StripItem &it)
 {
-        static_assert(NCH == 1 || J == 1, "one channel per wavefront when a workgroup holds several");
         const int lane = (int)threadIdx.x & 63;
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-        const int cbase = J == 1 ? 0 : wave;
+        const int chan = J == 1 ? 0 : wave;
 #ifdef J2P_TRACE
         const unsigned long long tr_start = trace_now();
 #ifdef J2P_TRACE_CLOCK
@@ -1551,14 +1372,11 @@ __device__ __forceinline__ void gradient_strip(const GradArgs &a, V *xchg, doubl
 #endif
 #endif
         unsigned long long tr_data = 0;
-        constexpr int kTiles = kItemTiles<NCH, J>;
-        double lo[NCH][kTiles], hi[NCH][kTiles], tv_acc = 0., tv2_acc = 0.;
+        constexpr int kTiles = kItemTiles<J>;
+        double lo[kTiles], hi[kTiles], tv_acc = 0., tv2_acc = 0.;
 #pragma unroll
-        for(int c = 0; c < NCH; c++) {
-#pragma unroll
-                for(int k = 0; k < kTiles; k++) { lo[c][k] = hi[c][k] = 0.; }
-        }
-        if(it.active) { march_rows<NCH, TGV, LOG, J, NT, PX, V>(a, xchg, it, lo, hi, tv_acc, tv2_acc, tr_data); }
+        for(int k = 0; k < kTiles; k++) { lo[k] = hi[k] = 0.; }
+        if(it.active) { march_rows<TGV, LOG, J, NT>(a, xchg, it, lo, hi, tv_acc, tv2_acc, tr_data); }
         if(LOG) {
 #pragma unroll
                 for(int off = 32; off > 0; off >>= 1) {
@@ -1567,23 +1385,23 @@ __device__ __forceinline__ void gradient_strip(const GradArgs &a, V *xchg, doubl
                 }
         }
         bool publisher = it.active;
-        if constexpr(NCH == 1 && J == 1) {
+        if constexpr(J == 1) {
                 if(it.kind == kKindHalf || it.kind == kKindQuarter) {
                         // half items: wavefronts (0, 1) and (2, 3) of the workgroup share a strip; quarter items: all four do
                         const int first = it.kind == kKindHalf ? (wave & ~1) : 0;
                         if(wave != first) {
-                                fold_buf[wave * 64 + lane] = lo[0][0] + hi[0][0];        // (one of the two is 0)
+                                fold_buf[wave * 64 + lane] = lo[0] + hi[0];        // (one of the two is 0)
                                 if(LOG && lane == 0) { fold_buf[256 + 2 * wave] = tv_acc; fold_buf[257 + 2 * wave] = tv2_acc; }
                         }
                         __syncthreads();
                         publisher = wave == first && it.active;
                         if(publisher) {
                                 if(it.kind == kKindHalf) {
-                                        hi[0][0] = fold_buf[(wave + 1) * 64 + lane];
+                                        hi[0] = fold_buf[(wave + 1) * 64 + lane];
                                         if(LOG) { tv_acc += fold_buf[256 + 2 * (wave + 1)]; tv2_acc += fold_buf[257 + 2 * (wave + 1)]; }
                                 } else {
-                                        lo[0][0] = lo[0][0] + fold_buf[64 + lane];
-                                        hi[0][0] = fold_buf[128 + lane] + fold_buf[192 + lane];
+                                        lo[0] = lo[0] + fold_buf[64 + lane];
+                                        hi[0] = fold_buf[128 + lane] + fold_buf[192 + lane];
                                         if(LOG) {
 #pragma unroll
                                                 for(int w = 1; w < 4; w++) { tv_acc += fold_buf[256 + 2 * w]; tv2_acc += fold_buf[257 + 2 * w]; }
@@ -1599,26 +1417,23 @@ __device__ __forceinline__ void gradient_strip(const GradArgs &a, V *xchg, doubl
                 const int ntile = kTiles == 2 && it.kind == kKindDouble && it.tile0 + (int)a.geo.rpw < (int)a.geo.rows ? 2 : 1;
                 for(int k = 0; k < ntile; k++) {
                         const unsigned tr = it.tr + (unsigned)k;
+                        double v = kTiles == 2 && k == 1 ? lo[kTiles - 1] + hi[kTiles - 1] : lo[0] + hi[0];
 #pragma unroll
-                        for(int c = 0; c < NCH; c++) {
-                                double v = kTiles == 2 && k == 1 ? lo[c][kTiles - 1] + hi[c][kTiles - 1] : lo[c][0] + hi[c][0];
-#pragma unroll
-                                for(int off = 32; off > 0; off >>= 1) { v += __shfl_down(v, off, 64); }
-                                // (a folding launch marks its partials with the iteration's parity, see fold_tile_row: the sign bit is
-                                // SET to it, whatever it was — a sum of squares is >= +0, and a NaN must not make the reader wait for ever)
-                                if(a.row_ticket) {
-                                        const unsigned long long bits = (__builtin_bit_cast(unsigned long long, v) & ~(1ull << 63)) | ((unsigned long long)a.fold_phase << 63);
-                                        v = __builtin_bit_cast(double, bits);
-                                }
-                                if(lane == 0) { publish_double(&a.part_g2[(cbase + c) * nparts + (size_t)tr * ntiles_row + it.wcol], v); }
+                        for(int off = 32; off > 0; off >>= 1) { v += __shfl_down(v, off, 64); }
+                        // (a folding launch marks its partials with the iteration's parity, see fold_tile_row: the sign bit is
+                        // SET to it, whatever it was — a sum of squares is >= +0, and a NaN must not make the reader wait for ever)
+                        if(a.row_ticket) {
+                                const unsigned long long bits = (__builtin_bit_cast(unsigned long long, v) & ~(1ull << 63)) | ((unsigned long long)a.fold_phase << 63);
+                                v = __builtin_bit_cast(double, bits);
                         }
-                        if(LOG && lane == 0 && cbase == 0) {
+                        if(lane == 0) { publish_double(&a.part_g2[chan * nparts + (size_t)tr * ntiles_row + it.wcol], v); }
+                        if(LOG && lane == 0 && chan == 0) {
                                 // (the CSV sums of a double item sit with its first tile row; the second one's slot holds 0)
                                 const size_t w = (size_t)tr * ntiles_row + it.wcol;
                                 a.part_tv[2 * w] = k == 0 ? tv_acc : 0.;
                                 a.part_tv[2 * w + 1] = k == 0 ? tv2_acc : 0.;
                         }
-                        if(a.row_ticket) { fold_arrive(a, tr, (unsigned)NCH, nparts, fold_buf, lane); }
+                        if(a.row_ticket) { fold_arrive(a, tr, 1u, nparts, fold_buf, lane); }
                 }
         }
 #ifdef J2P_TRACE
@@ -1726,19 +1541,19 @@ constexpr int kDebugWaveCap = 2;
 constexpr int kDebugWaveCap = 64;
 #endif
 constexpr int grad_waves(int want) { return want < kDebugWaveCap ? want : kDebugWaveCap; }
-template <int NCH, bool TGV, bool LOG, int J = 1, int NT = 0, int PX = 2>
-__global__ __launch_bounds__((J == 1 ? 256 : 64 * J), grad_waves(PX == 1 ? (J == 1 && !LOG ? 6 : 2) : NCH == 1 ? (J == 1 && !LOG ? (NT >= 1 ? kBigWaves : kHotWaves) : kGradWaves1) : NCH == 2 ? 3 : kGradWaves3))
+// The gradient kernel: TGV = the TGV2 term is on (weight != 0), LOG = the CSV sums are wanted, J = 1 ... 3 channel wavefronts
+// per workgroup (march_rows), NT = the non-temporal level.  A workgroup is four strips of a one-channel image (256 threads)
+// or the J channels of one strip of a joint image (64 J threads).
+template <bool TGV, bool LOG, int J = 1, int NT = 0>
+__global__ __launch_bounds__((J == 1 ? 256 : 64 * J), grad_waves(kGradWaves))
 void k_gradient(GradArgs a)
 {
-        static_assert(J == 1 || NCH == 1, "channel-per-wavefront mode keeps one channel per wavefront");
-        static_assert(PX == 2 || NCH == 1, "one column per lane: one channel per wavefront");
-        typedef typename std::conditional<PX == 2, v2f, float>::type V;
-        __shared__ __attribute__((aligned(16))) V xchg[J == 1 ? 1 : 2 * J * 64 * 3];
+        __shared__ __attribute__((aligned(16))) v2f xchg[J == 1 ? 1 : 2 * J * 64 * 3];
         __shared__ double fold_buf[kFoldMaxRows];               // the norm tree of the launch's last wavefront; sub-item hand-over
         StripItem it;
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
         if(!grad_item<J>(a.geo, blockIdx.x, wave, it)) { return; }
-        gradient_strip<NCH, TGV, LOG, J, NT, PX, V>(a, xchg, fold_buf, it);
+        gradient_strip<TGV, LOG, J, NT>(a, xchg, fold_buf, it);
 }
 
 // ---------------------------------------------------------------------------
@@ -2183,11 +1998,8 @@ __device__ __forceinline__ void sub_store_residual(const ChanDev &k, size_t base
 // (6) or dwords (3).  8 hs x WS stepped pixels do not fit in registers (4 x 4: 128), so the front end keeps only the
 // eight means and leaves the stepped pixels in x_{k+1}'s own place (k.xprev, whose x_{k-1} value each lane has just
 // read); the back end reads them back — 20 bytes per pixel over the two passes instead of 28 for stepping every pixel
-// twice (-DJ2P_WIDE_RESTEP=1, the other candidate: DESIGN.md section 11).  Rows: a loop at run time; columns and the
+// twice (the other candidate, measured: DESIGN.md section 11).  Rows: a loop at run time; columns and the
 // eight block rows: compile time (no register array indexed at run time).
-#ifndef J2P_WIDE_RESTEP
-#define J2P_WIDE_RESTEP 0
-#endif
 template <int WS>
 __device__ __forceinline__ void wide_load(const float *p, float (&v)[WS])
 {
@@ -2277,10 +2089,8 @@ __device__ __forceinline__ void wide_load_step_mean(const ChanDev &k, size_t bas
                         wide_step_row<WS>(k, off, factor, step, norm, fast, rn, y);
 #pragma unroll
                         for(int sx = 0; sx < WS; sx++) { m += y[sx]; }
-#if !J2P_WIDE_RESTEP
                         J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 218);
                         wide_store<WS>(k.xprev + off, y);                     // staged for the back end
-#endif
                 }
                 mean[r] = m / cnt;                                            // compute.c:359
         }
@@ -2292,24 +2102,15 @@ __device__ __forceinline__ void wide_store_residual(const ChanDev &k, size_t bas
                                                     float norm, const float (&mean_old)[8], const float (&mean_new)[8],
                                                     float *halo_up, float *halo_down)
 {
-#if J2P_WIDE_RESTEP
-        const bool fast = den_ok(norm);
-        const float rn = fast ? 1.f / norm : 0.f;
-#else
         (void)factor; (void)step; (void)norm;
-#endif
 #pragma unroll
         for(int r = 0; r < 8; r++) {
                 for(unsigned sy = 0; sy < hs; sy++) {
                         const unsigned row = r * hs + sy;
                         const size_t off = base + (size_t)row * W;
                         float y[WS], o[WS];
-#if J2P_WIDE_RESTEP
-                        wide_step_row<WS>(k, off, factor, step, norm, fast, rn, y);
-#else
                         J2P_CHK(k, x_own[1], k.xprev + off, 4 * WS, 219);
                         wide_load<WS>(k.xprev + off, y);
-#endif
 #pragma unroll
                         for(int sx = 0; sx < WS; sx++) {
                                 const float res = y[sx] - mean_old[r];                   // compute.c:365
@@ -2783,22 +2584,11 @@ __device__ __forceinline__ void project_strip(const ProjArgs &a, ProjShared &sh)
 
 // NIP: the norm comes from norm_tree_wave (ProjArgs::norm_rowsums) instead of ProjArgs::norm
 // (70 registers for the 1x1 form with buffer addressing = seven wavefronts per SIMD, 78 = six in the pointer form; capping
-// seven back to six — J2P_PROJECT_MAXWAVES=6 — changes nothing, forcing eight spills)
-#ifndef J2P_PROJECT_WAVES
-#define J2P_PROJECT_WAVES 0
-#endif
+// seven back to six through the LDS footprint changed nothing, forcing eight through the launch bounds spills)
 template <bool LOG, int WS, int HS, int NT = 0, int NIP = 0, bool PTR = false>
-__global__ __launch_bounds__(256, (J2P_PROJECT_WAVES && WS == 1 && HS == 1 && !LOG && !NIP ? J2P_PROJECT_WAVES : 1)) void k_project(ProjArgs a)
+__global__ __launch_bounds__(256, 1) void k_project(ProjArgs a)
 {
         __shared__ ProjShared sh;
-#ifdef J2P_PROJECT_MAXWAVES     // (experiment: cap the wavefronts per SIMD by the workgroup's LDS footprint instead of raising them)
-        __shared__ float occupancy_pad[(160 * 1024 / (J2P_PROJECT_MAXWAVES + 1) - sizeof(ProjShared)) / 4 + 64];
-        if(a.geo.W == 0xffffffffu) {            // (never: keeps the allocation alive)
-                occupancy_pad[threadIdx.x] = (float)a.geo.H;
-                __syncthreads();
-                if(occupancy_pad[threadIdx.x ^ 1] == 3.f) { __builtin_trap(); }
-        }
-#endif
         project_strip<LOG, WS, HS, NT, NIP, PTR>(a, sh);
 }
 

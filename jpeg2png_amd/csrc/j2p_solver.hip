@@ -102,7 +102,6 @@ struct j2p_solver {
         bool fold = false;       // norm reduction folded into k_gradient (J2P_OPT_NORM_FOLD); default: band solvers only
         unsigned zone_d = 0, zone_b = 0, zone_c = 0;   // shares (1/256) of a gradient launch dealt as double / half / quarter tile rows (grad_item)
         bool grad_reverse = false;         // the gradient launch walks the canvas bottom-up (Geo::reverse)
-        bool joint_inwave = false;   // J2P_OPT_JOINT_INWAVE
         bool norm_in_project = false;   // J2P_OPT_NORM_IN_PROJECT (with fold): level 2 of the norm inside k_project
         int nip_form = 1;               // ... by every wavefront (1: small canvases) or by the workgroup's first (2), see project_strip
         int nt = 0;                     // 0..3: streams with the non-temporal hint (nt_policy; J2P_OPT_NT_GRADIENT)
@@ -121,7 +120,6 @@ struct j2p_solver {
         bool norm_by_project = false;   // ... or left level-1 row sums that k_project reduces itself
         unsigned *tickets = nullptr;     // device: [ntr_local] per-tile-row arrival counters + [1] finished-rows counter
         unsigned rpw = 16;
-        unsigned px = 2;                // columns per lane of the gradient strips (2: 128-column strips, 1: 64-column strips)
         bool interior_done = false;
         bool rowsums_pending = false;
         unsigned ntx = 0, nseg = 0, ntr_local = 0, ntr_global = 0, first_tr = 0;   // strips per row, row segments
@@ -312,11 +310,6 @@ constexpr size_t kMixedProjectPixels = (size_t)1 << 20;  // canvases up to this 
 // iteration, 8192^2 521.6 -> 511.3; at 4096^2 the launch (4.7 us) is the cheaper one, 117.6 vs 119.4
 // (profiles/r04_fold_without_ack_waits.jsonl)
 constexpr size_t kFoldWholePixels = (size_t)1 << 25;
-// fewer gradient wavefronts than this (128-column, 16-row strips) -> 64-column strips.  0 = never: measured on canvases from
-// 0.26 to 16.8 Mpixel (profiles/r03_px_rpw_sweep.jsonl) the one-column-per-lane form is nowhere faster than the packed one
-// with the same rows per strip (512x512 4:2:0 29.2 vs 27.5 us per iteration, 1080p Y 31.1 vs 28.7, 2048^2 45.5 vs 44.4):
-// twice the wavefronts do not shorten the launch, because each still walks as many rows, one row trip at a time
-constexpr unsigned long long kPx1Waves = 0;
 // rows per gradient strip: 16; 8, then 4, while the strips make fewer wavefronts than half the chip's 4096 slots (the
 // launch is then one generation whose length is the busiest SIMD's: shorter strips balance it, at 25 / 50 instead of 12.5 %
 // redundant rows).  A limit of 4096 for the first step was measured too (profiles/r03_px_rpw_sweep.jsonl,
@@ -462,36 +455,33 @@ double *rowsums_of(const j2p_solver *s, unsigned iter)
 unsigned grad_units(const j2p_solver *s, unsigned ntr)
 {
         const unsigned positions = s->ntx * ((ntr + 1) / 2);
-        return s->nch == 1 || s->joint_inwave ? (positions + 3) / 4 : positions;
+        return s->nch == 1 ? (positions + 3) / 4 : positions;
 }
 ZoneShares zone_shares(const Geo &g) { return ZoneShares{g.zone_d, g.zone_b, g.zone_c}; }
 
-template <int NCH, int J, int PX = 2>
-void launch_gradient_n(const GradArgs &a, hipStream_t st, bool tgv, bool log, int nt)
+template <int J>
+void launch_gradient(const GradArgs &a, hipStream_t st, bool tgv, bool log, int nt)
 {
         // J == 1: 4 strips per 256-thread workgroup; J > 1: one strip per workgroup of J wavefronts
         const dim3 grid(grad_grid(a.geo.units, zone_shares(a.geo)));
         const dim3 block = J == 1 ? dim3(256) : dim3(64 * J);
-        if constexpr(NCH == 1 && PX == 2) {
-                // non-temporal g / prob state (see nt_policy): the one-channel-per-wavefront kernels without logging
-                if(nt >= 1 && !log) {
-                        if(nt >= 2) {
-                                if(tgv) { hipLaunchKernelGGL((k_gradient<NCH, true, false, J, 2>), grid, block, 0, st, a); }
-                                else { hipLaunchKernelGGL((k_gradient<NCH, false, false, J, 2>), grid, block, 0, st, a); }
-                        } else {
-                                if(tgv) { hipLaunchKernelGGL((k_gradient<NCH, true, false, J, 1>), grid, block, 0, st, a); }
-                                else { hipLaunchKernelGGL((k_gradient<NCH, false, false, J, 1>), grid, block, 0, st, a); }
-                        }
-                        return;
+        // non-temporal g / prob state (see nt_policy): the kernels without logging
+        if(nt >= 1 && !log) {
+                if(nt >= 2) {
+                        if(tgv) { hipLaunchKernelGGL((k_gradient<true, false, J, 2>), grid, block, 0, st, a); }
+                        else { hipLaunchKernelGGL((k_gradient<false, false, J, 2>), grid, block, 0, st, a); }
+                } else {
+                        if(tgv) { hipLaunchKernelGGL((k_gradient<true, false, J, 1>), grid, block, 0, st, a); }
+                        else { hipLaunchKernelGGL((k_gradient<false, false, J, 1>), grid, block, 0, st, a); }
                 }
+                return;
         }
-        // (one column per lane is for canvases that leave wavefront slots empty: they fit the caches, no hint)
         if(tgv) {
-                if(log) { hipLaunchKernelGGL((k_gradient<NCH, true, true, J, 0, PX>), grid, block, 0, st, a); }
-                else { hipLaunchKernelGGL((k_gradient<NCH, true, false, J, 0, PX>), grid, block, 0, st, a); }
+                if(log) { hipLaunchKernelGGL((k_gradient<true, true, J>), grid, block, 0, st, a); }
+                else { hipLaunchKernelGGL((k_gradient<true, false, J>), grid, block, 0, st, a); }
         } else {
-                if(log) { hipLaunchKernelGGL((k_gradient<NCH, false, true, J, 0, PX>), grid, block, 0, st, a); }
-                else { hipLaunchKernelGGL((k_gradient<NCH, false, false, J, 0, PX>), grid, block, 0, st, a); }
+                if(log) { hipLaunchKernelGGL((k_gradient<false, true, J>), grid, block, 0, st, a); }
+                else { hipLaunchKernelGGL((k_gradient<false, false, J>), grid, block, 0, st, a); }
         }
 }
 
@@ -585,7 +575,7 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.geo.units = grad_units(s, nseg_launch);
         a.geo.ntr_launch = nseg_launch;
         // (half / quarter items: whole phases of one channel per workgroup wavefront, see the policy in j2p_solver_create)
-        if(part == 0 && s->nch == 1 && !s->joint_inwave) { a.geo.zone_d = s->zone_d; a.geo.zone_b = s->zone_b; a.geo.zone_c = s->zone_c; }
+        if(part == 0 && s->nch == 1) { a.geo.zone_d = s->zone_d; a.geo.zone_b = s->zone_b; a.geo.zone_c = s->zone_c; }
         a.geo.reverse = part == 0 && s->grad_reverse ? 1u : 0u;
         a.factor = s->factor;
         a.a_tv = (float)(1. / (double)sqrtf((float)s->nch));                    // compute.c:90
@@ -612,42 +602,18 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.ntr_global = s->ntr_global;
         const bool tgv = s->weight != 0.f;
         if(part != 2) { mark(s); }     // event timing covers the main launch only (the edge part runs on another stream)
-        // joint images: one wavefront per channel, the norms exchanged through LDS (three times the
-        // wavefronts at 4 per SIMD), beats all channels in one wavefront (248 VGPRs, 2 per SIMD) at every
-        // size measured: 198 vs 293 us at 12 Mpixel 4:2:0, 494 vs 717 us at 36 Mpixel.  J2P_JOINT_INWAVE=1
-        // selects the in-wavefront kernel (kept: it is the same arithmetic in another schedule, and tested).
-#ifdef J2P_EXPERIMENTS
-        const bool inwave = s->joint_inwave;
+        // one wavefront per channel; the channels of a joint image share a workgroup and exchange their norm
+        // contributions through LDS (the schedules that lost to this one: DESIGN.md section 10)
         switch(s->nch) {
-        case 1:
-                if(s->px == 1) { launch_gradient_n<1, 1, 1>(a, st, tgv, log, 0); }
-                else { launch_gradient_n<1, 1>(a, st, tgv, log, s->nt); }
-                break;
-        case 2:
-                if(inwave) { launch_gradient_n<2, 1>(a, st, tgv, log, 0); }
-                else if(s->px == 1) { launch_gradient_n<1, 2, 1>(a, st, tgv, log, 0); }
-                else { launch_gradient_n<1, 2>(a, st, tgv, log, s->nt); }
-                break;
-        default:
-                if(inwave) { launch_gradient_n<3, 1>(a, st, tgv, log, 0); }
-                else if(s->px == 1) { launch_gradient_n<1, 3, 1>(a, st, tgv, log, 0); }
-                else { launch_gradient_n<1, 3>(a, st, tgv, log, s->nt); }
-                break;
+        case 1: launch_gradient<1>(a, st, tgv, log, s->nt); break;
+        case 2: launch_gradient<2>(a, st, tgv, log, s->nt); break;
+        default: launch_gradient<3>(a, st, tgv, log, s->nt); break;
         }
-#else
-        // (release build: one wavefront per channel, two columns per lane — the schedules that won everywhere)
-        switch(s->nch) {
-        case 1: launch_gradient_n<1, 1>(a, st, tgv, log, s->nt); break;
-        case 2: launch_gradient_n<1, 2>(a, st, tgv, log, s->nt); break;
-        default: launch_gradient_n<1, 3>(a, st, tgv, log, s->nt); break;
-        }
-#endif
         if(part != 2) { mark(s); }
         HIP_TRY(hipGetLastError());
 #ifdef J2P_TRACE
         if(s->trace_on) {       // one record per wavefront of the launch (J == 1: 4 strips per workgroup; joint: one strip)
-                const bool per_channel = s->nch > 1 && !s->joint_inwave;
-                s->trace_used += grad_grid(a.geo.units, zone_shares(a.geo)) * (per_channel ? s->nch : 4u);
+                s->trace_used += grad_grid(a.geo.units, zone_shares(a.geo)) * (s->nch > 1 ? s->nch : 4u);
         }
 #endif
         if(part == 1) {
@@ -803,7 +769,6 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                 }
         }
         if(part != 1) { mark(s); }
-        const bool inwave_nt_off = s->nch > 1 && s->joint_inwave;      // those gradient kernels have no non-temporal form
         auto block_rows = [&](unsigned hs, unsigned z) -> unsigned {
                 const unsigned brows = (s->rows + 8 * hs - 1) / (8 * hs);
                 if(part == 0) { a.by_offset[z] = 0; a.by_mul[z] = 1; a.nby[z] = brows; }
@@ -853,8 +818,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                         // way (nt levels, nt_policy); rows >= 64 KiB apart take the pointer form of the 24 loads (see
                         // project_strip); bands reduce ||g|| themselves (NIP 2)
                         const bool far_rows = (size_t)s->W * sizeof(float) >= 65536;
-                        const int nt = inwave_nt_off ? 0 : s->nt;
-                        launch_project_unit(nt, nip, far_rows, grid, st, a);
+                        launch_project_unit(s->nt, nip, far_rows, grid, st, a);
                 }
                 else if(log && nip == 2) { launch_project_sampled<true, 2>(ws, hs, wide, grid, st, a); }
                 else if(log) { launch_project_sampled<true, 0>(ws, hs, wide, grid, st, a); }
@@ -1036,12 +1000,9 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         s->weight = weight;
         s->iterations = iterations;
         {
-                // the one schedule switch tests reach through the environment (read once, here): all channels of a
-                // joint image inside one wavefront instead of one wavefront per channel — same bits, slower
-                const char *env = j2p_exp_env("J2P_JOINT_INWAVE");
-                s->joint_inwave = env && atoi(env) != 0;
-                // ... and: one projection launch per sampling class also on small canvases (J2P_OPT_MIXED_PROJECT)
-                env = j2p_exp_env("J2P_MIXED_PROJECT");
+                // schedule switches tests reach through the environment (read once, here): one projection launch per
+                // sampling class also on small canvases (J2P_OPT_MIXED_PROJECT)
+                const char *env = j2p_exp_env("J2P_MIXED_PROJECT");
                 if(env) { s->mixed_project = atoi(env) != 0; }
                 // ... and (A/B timing): band solvers finish ||g|| with a k_norm_finish launch instead of inside k_project
                 env = j2p_exp_env("J2P_BAND_NIP");
@@ -1097,35 +1058,28 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                 }
         }
         // reductions: tile rows are counted on the canvas, the band owns a contiguous range
-        // Gradient strips: columns per lane (px) and rows per strip = rows per norm partial ("tile row", rpw).
-        // A canvas that fills the chip: 128-column strips (two columns per lane, packed arithmetic) of 16 rows (32 / 48 / 64
-        // measured no faster).  A smaller canvas leaves wavefront slots empty and is bound by how long ONE
-        // wavefront takes to walk its rows (wave timelines, profiles/r03_wave_trace.jsonl: ~0.9 us per row trip whatever
-        // the SIMD's load), so it gets shorter strips (8 or 4 rows: fewer trips per wavefront).  64-column strips (one
-        // column per lane: the same kernel instantiated on float instead of float2) exist behind J2P_PX=1 and do not
-        // pay (kPx1Waves).  Functions of the CANVAS only (never of the band), so that every band of a tiled run — and
-        // the whole-canvas solver — reduce ||g|| over the same partials in the same order.
+        // Gradient strips: 128 columns (two per lane, packed arithmetic) by rpw rows = rows per norm partial ("tile row").
+        // A canvas that fills the chip: 16 rows (32 / 48 / 64 measured no faster).  A smaller canvas leaves
+        // wavefront slots empty and is bound by how long ONE wavefront takes to walk its rows (wave timelines,
+        // profiles/r03_wave_trace.jsonl: ~0.9 us per row trip whatever the SIMD's load), so it gets shorter strips (8 or 4
+        // rows: fewer trips per wavefront; narrower strips do not pay).  Functions of the CANVAS only (never
+        // of the band), so that every band of a tiled run — and the whole-canvas solver — reduce ||g|| over the same
+        // partials in the same order.
         {
-                auto strips = [&](unsigned px) { return W <= 4 ? 1u : (W - 4 + (64 * px - 4) - 1) / (64 * px - 4); };
-                auto waves = [&](unsigned px, unsigned g) { return (unsigned long long)strips(px) * nchannel * ((H + g - 1) / g); };
-                unsigned px = 2, g = kTY;
+                const unsigned strips = W <= 4 ? 1u : (W - 4 + kStripCols - 1) / kStripCols;
+                auto waves = [&](unsigned g) { return (unsigned long long)strips * nchannel * ((H + g - 1) / g); };
+                unsigned g = kTY;
                 // (limits measured, profiles/r03_px_rpw_sweep.jsonl)
-                if(waves(2, kTY) < kPx1Waves && !s->joint_inwave) { px = 1; }
-                if(waves(px, g) < kHalfStripWaves) { g = 8; }
-                if(g == 8 && waves(px, g) < kShortStripWaves) { g = 4; }
-                // (timing experiments: J2P_PX = 1 / 2, J2P_RPW = 2 ... 64 for every solver of the process; band solvers take
+                if(waves(g) < kHalfStripWaves) { g = 8; }
+                if(g == 8 && waves(g) < kShortStripWaves) { g = 4; }
+                // (timing experiments: J2P_RPW = 2 ... 64 for every solver of the process; band solvers take
                 // only the divisors of the band alignment, 16 — tools/rpw_fine.py sweeps the rest on whole canvases)
-                if(const char *env = j2p_exp_env("J2P_PX")) {
-                        const int v = atoi(env);
-                        if((v == 1 && !s->joint_inwave) || v == 2) { px = (unsigned)v; }
-                }
                 if(const char *env = j2p_exp_env("J2P_RPW")) {
                         const int v = atoi(env);
                         if(v >= 2 && v <= 64 && (s->whole || kTY % v == 0)) { g = (unsigned)v; }
                 }
-                s->px = px;
                 s->rpw = g;
-                s->ntx = strips(px);
+                s->ntx = strips;
                 // The LAST wavefronts of a gradient launch march half and quarter tile rows (grad_item): a launch ends with
                 // its last wavefront, and a whole 16-row item dispatched last keeps a few SIMDs busy for a wavefront life
                 // (17 us of 53 at 4096^2, profiles/r06_wave_trace.jsonl) while the rest of the chip drains.  Shares in
@@ -1134,7 +1088,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                 // r06_zones_by_size.jsonl; us per iteration without / with) 1080p 30.1 / 28.7, 2048^2 45.5 / 42.2,
                 // 4096x2048 70.9 / 67.8, 4096x3072 94.2 / 92.0, 4096^2 120.0 / 118.7; nothing from three wavefront
                 // generations on (8192x4096 235.3 / 235.9, 16384x2048 230.8 / 231.1, 8192^2 515.7 / 515.8).
-                const unsigned long long launch_waves = (unsigned long long)strips(px) * ((s->rows + g - 1) / g);
+                const unsigned long long launch_waves = (unsigned long long)strips * ((s->rows + g - 1) / g);
                 if(nchannel == 1 && g >= 8 && launch_waves < kZoneMaxWaves) {
                         s->zone_b = kZoneB;
                         s->zone_c = g >= 16 ? kZoneC : 0;
@@ -1351,13 +1305,6 @@ int j2p_solver_debug_option(j2p_solver *s, int option, int value)
                 // 0: reduction launch between the phases; 1: folded into k_gradient by tickets
                 if(value != 0 && value != 1) { return fail(J2P_EINVAL, "J2P_OPT_NORM_FOLD is 0 or 1"); }
                 s->fold = value == 1;
-                break;
-        case J2P_OPT_JOINT_INWAVE:
-#ifndef J2P_EXPERIMENTS
-                if(value) { return fail(J2P_ESTATE, "J2P_OPT_JOINT_INWAVE 1 (all channels in one wavefront) exists in the experiments build only"); }
-#endif
-                if(value && s->px == 1) { return fail(J2P_ESTATE, "the in-wavefront joint kernel has no one-column-per-lane form (set J2P_JOINT_INWAVE=1 before the solver is created)"); }
-                s->joint_inwave = value != 0;
                 break;
         case J2P_OPT_NORM_IN_PROJECT:
                 // 0: off; 1: the per-wavefront tree; 2: the per-workgroup tree; (needs NORM_FOLD)

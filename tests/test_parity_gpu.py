@@ -553,11 +553,11 @@ def test_out_of_range_operands_take_the_ieee_path(lib, oracle):
         np.testing.assert_allclose(got_log, want_log, rtol=1e-9, atol=1e-9)
 
 
-def test_noise_around_zero_takes_the_ieee_path(exp_lib, oracle, monkeypatch):
+def test_noise_around_zero_takes_the_ieee_path(exp_lib, oracle):
     """all-zero coefficient blocks (a flat grey area: chroma 0) leave rounding noise of 1e-17 and
     below around 0 for the first iterations — far under the 2^-20 the short division / sqrt
     sequences are screened for, down to values whose squares are subnormal.  Such rows must take
-    the IEEE path, in both schedules of the joint gradient kernel and in the 1-channel kernel."""
+    the IEEE path, in the joint gradient kernel and in the 1-channel kernel."""
     import jpeg2png_amd as j
     from oracle import bindings
     planes = make_case(264, 136, "420", 10, seed=99)
@@ -574,16 +574,13 @@ def test_noise_around_zero_takes_the_ieee_path(exp_lib, oracle, monkeypatch):
         if its == 3:
             tiny = sum(int(((np.abs(w) < 2.0 ** -43) & (w != 0)).sum()) for w in want)
             assert tiny > 1000, "the case no longer produces noise around 0"
-        for mode in ("0", "1"):
-            monkeypatch.setenv("J2P_JOINT_INWAVE", mode)
-            for log in (False, True):
-                got = copy.deepcopy(planes)
-                got_log = j.compute(got, 0.3, pws, its, log=log)
-                for c in range(3):
-                    assert bit_equal(got[c].fdata, want[c]), f"its {its} mode {mode} log {log} channel {c}"
-                if log:
-                    np.testing.assert_allclose(got_log, want_log, rtol=1e-9, atol=1e-9)
-        monkeypatch.delenv("J2P_JOINT_INWAVE")
+        for log in (False, True):
+            got = copy.deepcopy(planes)
+            got_log = j.compute(got, 0.3, pws, its, log=log)
+            for c in range(3):
+                assert bit_equal(got[c].fdata, want[c]), f"its {its} log {log} channel {c}"
+            if log:
+                np.testing.assert_allclose(got_log, want_log, rtol=1e-9, atol=1e-9)
         for c in (0, 1):
             want1, _ = oracle.oracle_compute(planes[c:c + 1], 0.3, [0.001], its)
             got = copy.deepcopy(planes[c:c + 1])
@@ -591,25 +588,22 @@ def test_noise_around_zero_takes_the_ieee_path(exp_lib, oracle, monkeypatch):
             assert bit_equal(got[0].fdata, want1[0]), f"its {its} separate channel {c}"
 
 
-def test_both_joint_modes_agree(exp_lib, oracle, monkeypatch):
-    """channels-in-one-wavefront and one-wavefront-per-channel gradient kernels are two schedules of
-    the same arithmetic"""
+def test_joint_kernel_agrees_with_the_oracle(exp_lib, oracle):
+    """the joint gradient kernel (one wavefront per channel, norms exchanged through LDS) against the oracle's bits"""
     import jpeg2png_amd as j
     planes = make_case(264, 88, "420", 10, seed=88)
     want, _ = oracle.oracle_compute(planes, 0.3, [0.001] * 3, 7)
-    for mode in ("0", "1"):
-        monkeypatch.setenv("J2P_JOINT_INWAVE", mode)
-        got = copy.deepcopy(planes)
-        j.compute(got, 0.3, [0.001] * 3, 7)
-        for c in range(3):
-            assert bit_equal(got[c].fdata, want[c]), f"mode {mode} channel {c}"
+    got = copy.deepcopy(planes)
+    j.compute(got, 0.3, [0.001] * 3, 7)
+    for c in range(3):
+        assert bit_equal(got[c].fdata, want[c]), f"channel {c}"
 
 
 @pytest.mark.parametrize("shape", [(520, 136, "420", False), (1000, 96, "444", True), (264, 200, "422", False)])
 def test_every_schedule_switch_leaves_the_bits_alone(exp_lib, oracle, shape, monkeypatch):
     """the J2P_OPT_* switches select schedules of the same arithmetic (where the norm is reduced, whether g is
-    streamed non-temporally, one projection launch or one per sampling class), J2P_PX / J2P_RPW the geometry of the
-    gradient strips (one or two columns per lane, rows per strip): every combination the solver can pick by itself —
+    streamed non-temporally, one projection launch or one per sampling class), J2P_RPW the geometry of the
+    gradient strips (rows per strip): every combination the solver can pick by itself —
     the choice depends on the canvas size — must give the bits of the reference on ONE canvas"""
     import jpeg2png_amd as j
     w, h, sub, yonly = shape
@@ -630,41 +624,30 @@ def test_every_schedule_switch_leaves_the_bits_alone(exp_lib, oracle, shape, mon
         {j.J2P_OPT_NT_GRADIENT: 3},
         {j.J2P_OPT_NT_GRADIENT: 3, j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0},
         {j.J2P_OPT_MIXED_PROJECT: 0},                                               # what a > 1 Mpixel canvas gets
-        {j.J2P_OPT_MIXED_PROJECT: 0, j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0, "J2P_JOINT_INWAVE": "1"},
+        {j.J2P_OPT_MIXED_PROJECT: 0, j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0},
     ]
-    for px in ("2", "1"):
-        monkeypatch.setenv("J2P_PX", px)
-        for opts in settings:
-            if "J2P_JOINT_INWAVE" in opts:
-                if px == "1":
-                    continue                    # the in-wavefront joint kernel exists with two columns per lane only
-                monkeypatch.setenv("J2P_JOINT_INWAVE", "1")
-            with j.Solver(planes, 0.3, [0.001] * n, its) as s:
-                for k, v in opts.items():
-                    if not isinstance(k, str):
-                        s.debug_option(k, v)
-                s.run(its)
-                for c in range(n):
-                    assert bit_equal(s.download(c), want[c]), f"px {px} options {opts} channel {c}"
-            monkeypatch.delenv("J2P_JOINT_INWAVE", raising=False)
-    # rows per strip (what canvases of other sizes get) with both strip widths, whole canvas and bands
-    for px in ("2", "1"):
-        for rpw in ("4", "8", "16"):
-            monkeypatch.setenv("J2P_PX", px)
-            monkeypatch.setenv("J2P_RPW", rpw)
-            got = copy.deepcopy(planes)
-            rows = j.compute(got, 0.3, [0.001] * n, its, log=True)
+    for opts in settings:
+        with j.Solver(planes, 0.3, [0.001] * n, its) as s:
+            for k, v in opts.items():
+                s.debug_option(k, v)
+            s.run(its)
             for c in range(n):
-                assert bit_equal(got[c].fdata, want[c]), f"px {px} rpw {rpw} channel {c}"
-            assert np.isfinite(rows).all()
-            if h >= 128:
-                with j.TiledSolver(planes, 0.3, [0.001] * n, its, devices=band_devices(2)) as t:
-                    t.run(its)
-                    for c in range(n):
-                        assert bit_equal(t.download(c), want[c]), f"px {px} rpw {rpw}, two bands: channel {c}"
+                assert bit_equal(s.download(c), want[c]), f"options {opts} channel {c}"
+    # rows per strip (what canvases of other sizes get), whole canvas and bands
+    for rpw in ("4", "8", "16"):
+        monkeypatch.setenv("J2P_RPW", rpw)
+        got = copy.deepcopy(planes)
+        rows = j.compute(got, 0.3, [0.001] * n, its, log=True)
+        for c in range(n):
+            assert bit_equal(got[c].fdata, want[c]), f"rpw {rpw} channel {c}"
+        assert np.isfinite(rows).all()
+        if h >= 128:
+            with j.TiledSolver(planes, 0.3, [0.001] * n, its, devices=band_devices(2)) as t:
+                t.run(its)
+                for c in range(n):
+                    assert bit_equal(t.download(c), want[c]), f"rpw {rpw}, two bands: channel {c}"
     # strip heights that do not divide the band alignment (what tools/rpw_fine.py sweeps): whole canvases take them,
     # band solvers keep their own choice — the bits are the reference's either way
-    monkeypatch.setenv("J2P_PX", "2")
     for rpw in ("2", "6", "12", "24"):
         monkeypatch.setenv("J2P_RPW", rpw)
         got = copy.deepcopy(planes)
@@ -690,7 +673,6 @@ def test_half_and_quarter_items_leave_the_bits_alone(exp_lib, oracle, shape, mon
     planes = make_case(w, h, "444", 10, seed=97, y_only=True)
     its = 9
     want, want_rows = oracle.oracle_compute(planes, weight, [0.001], its, log=True)
-    monkeypatch.setenv("J2P_PX", "2")
     monkeypatch.setenv("J2P_RPW", "16")
     for zd, zb, zc, rev in ((0, 0, 0, 0), (0, 256, 0, 0), (0, 0, 256, 1), (0, 100, 100, 0), (0, 64, 32, 1), (0, 26, 10, 0), (0, 1, 255, 0), (0, 0, 0, 1),
                             (256, 0, 0, 0), (256, 0, 0, 1), (128, 64, 32, 0), (100, 0, 100, 1), (160, 32, 10, 0)):
@@ -878,18 +860,13 @@ def test_wide_randomised_sweep_against_the_compiled_reference(lib, oracle):
             assert bit_equal(got[c].fdata, want[c]), f"wide sweep case {cs.describe()} channel {c}"
 
 
-@pytest.mark.parametrize("inwave", ["0", "1"])
-def test_two_channel_joint_against_the_compiled_reference(lib, oracle, inwave):
+def test_two_channel_joint_against_the_compiled_reference(lib, oracle):
     """nchannel == 2 (compute.c:118 allows 1..3; the CLI only uses 1 and 3): every pair of components of the
-    sweep stream's colour cases, both schedules of the joint gradient kernel"""
+    sweep stream's colour cases through the joint gradient kernel"""
     if not oracle.have_ref():
         pytest.skip("oracle/_ref not built (needs /root/reference)")
     import subprocess
     import sys
-    env = dict(os.environ, J2P_JOINT_INWAVE=inwave)
-    if inwave == "1":               # that schedule lives in the experiments build
-        from jpeg2png_amd.buildlib import build_experiments
-        env["J2P_LIBRARY"] = build_experiments()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "two_channel.py")], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "two_channel.py")], cwd=ROOT, env=dict(os.environ),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
