@@ -6,7 +6,8 @@
  * libjpeg (the contract of jpeg.c:22-80), writing the PNG with libpng (png.c:20-78).
  * What moves to the GPU: decode_coefficients + unbox (jpeg.c:83-92, box.c:5), the whole
  * solver, the luma fix-up and the YCbCr->RGB conversion (jpeg2png.c:156-159, png.c:37-62),
- * so that only int16 coefficients go up and only RGB bytes come down.
+ * so that only int16 coefficients go up and only RGB bytes come down (with -j: only int16 coefficients, which
+ * libjpeg Huffman-codes into a JPEG file).
  *
  * Differences from the reference, on purpose:
  *   -t threads   = number of input files in flight (host threads reading / writing files; each file's GPU work
@@ -18,6 +19,9 @@
  *                  small to pay for the cross-band schedule: at least 2 Mpixel per band) — same pixels either way
  *   -g, --greyscale = a greyscale PNG: the reference's compute(1, ...) on component 0 alone, as `-s` solves it
  *                  (jpeg2png.c:147-152), written with Cb = Cr = 0 (png.c:37-45); one- and three-component JPEGs
+ *   -j, --jpeg Q = a baseline JFIF file of libjpeg quality Q (1..100) instead of a PNG, 4:4:4 (one component with -g):
+ *                  the GPU turns the solved float planes straight into quantised coefficients (j2p_planes_to_coefficients)
+ *                  and the host only entropy-codes them (jpeg_write_coefficients) — no RGB, no 8-bit samples in between
  * Messages and exit codes follow the reference ("jpeg2png: <message>", EXIT_FAILURE).
  */
 #define _POSIX_C_SOURCE 200809L
@@ -201,12 +205,83 @@ static void write_png(FILE *out, unsigned w, unsigned h, unsigned bits, unsigned
         png_destroy_write_struct(&png, &info);
 }
 
+/* ---- JPEG out (-j): the quantised coefficients arrive from the GPU; libjpeg only entropy-codes them ---- */
+
+/* libjpeg's own tables for `quality` (jpeg_set_defaults, jpeg_set_colorspace, jpeg_set_quality(Q, TRUE)), natural order:
+ * table 0 for component 0, table 1 for the chroma components */
+static void setup_jpeg_out(struct jpeg_compress_struct *c, unsigned w, unsigned h, unsigned ncomp, int quality)
+{
+        c->image_width = w;
+        c->image_height = h;
+        c->input_components = (int)ncomp;
+        c->in_color_space = ncomp == 1 ? JCS_GRAYSCALE : JCS_YCbCr;
+        jpeg_set_defaults(c);
+        jpeg_set_colorspace(c, ncomp == 1 ? JCS_GRAYSCALE : JCS_YCbCr);
+        jpeg_set_quality(c, quality, TRUE);
+        for(unsigned i = 0; i < ncomp; i++) {
+                c->comp_info[i].h_samp_factor = 1;                      /* 4:4:4 */
+                c->comp_info[i].v_samp_factor = 1;
+        }
+}
+
+static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
+{
+        struct jpeg_compress_struct c;
+        struct jpeg_error_mgr err;
+        c.err = jpeg_std_error(&err);
+        err.output_message = jpeg_message;
+        jpeg_create_compress(&c);
+        setup_jpeg_out(&c, 8, 8, ncomp, quality);
+        for(unsigned i = 0; i < ncomp; i++) {
+                JQUANT_TBL *tbl = c.quant_tbl_ptrs[c.comp_info[i].quant_tbl_no];
+                if(!tbl) { die("libjpeg gave no quantization table"); }
+                for(int j = 0; j < 64; j++) { quant[i][j] = tbl->quantval[j]; }
+        }
+        jpeg_destroy_compress(&c);
+}
+
+/* coef[i]: bh * bw blocks of 64 int16, block-major, natural order (JBLOCK rows) */
+static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, int16_t *const coef[3])
+{
+        struct jpeg_compress_struct c;
+        struct jpeg_error_mgr err;
+        c.err = jpeg_std_error(&err);
+        err.output_message = jpeg_message;
+        jpeg_create_compress(&c);
+        jpeg_stdio_dest(&c, out);
+        setup_jpeg_out(&c, w, h, ncomp, quality);
+        const unsigned bw = (w + 7) / 8, bh = (h + 7) / 8;
+#if JPEG_LIB_VERSION >= 70
+        /* IJG 7+: jpeg_write_coefficients expects what jpeg_calc_jpeg_dimensions / initial_setup would have left */
+        c.min_DCT_h_scaled_size = 8;
+        c.min_DCT_v_scaled_size = 8;
+        c.jpeg_width = w;
+        c.jpeg_height = h;
+#endif
+        jvirt_barray_ptr arrays[3] = {NULL, NULL, NULL};
+        for(unsigned i = 0; i < ncomp; i++) {
+                c.comp_info[i].width_in_blocks = bw;
+                c.comp_info[i].height_in_blocks = bh;
+                arrays[i] = c.mem->request_virt_barray((j_common_ptr)&c, JPOOL_IMAGE, FALSE, bw, bh, 1);
+        }
+        jpeg_write_coefficients(&c, arrays);
+        for(unsigned i = 0; i < ncomp; i++) {
+                for(unsigned by = 0; by < bh; by++) {
+                        JBLOCKARRAY row = c.mem->access_virt_barray((j_common_ptr)&c, arrays[i], by, 1, TRUE);
+                        memcpy(row[0][0], coef[i] + (size_t)by * bw * 64, sizeof(int16_t) * 64 * bw);
+                }
+        }
+        jpeg_finish_compress(&c);
+        jpeg_destroy_compress(&c);
+}
+
 /* ---- one file: decode_file (jpeg2png.c:120-172) ---- */
 
 struct options {
         unsigned iterations[3];
         float weights[3], pweights[3];
         unsigned png_bits;
+        int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
         bool joint, quiet;
         bool grey;              /* -g: component 0 alone, one-channel job, greyscale PNG */
         unsigned zoom;          /* -z: integer zoom factor 1..4 (every sampling factor times zoom, output zoom times the size) */
@@ -322,13 +397,29 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 job.tile_first = index * (unsigned)o->ndev / o->nfiles;
                 job.tile_count = (index + 1) * (unsigned)o->ndev / o->nfiles - job.tile_first;
         }
-        job.out_bits = o->png_bits;
         job.out_w = jp.w * zoom;
         job.out_h = jp.h * zoom;
-        size_t bytes = (size_t)job.out_w * job.out_h * jp.n * (o->png_bits / 8);
-        uint8_t *pixels = malloc(bytes);
-        if(!pixels) { die("could not allocate image data"); }
-        job.out_rgb = pixels;
+        uint8_t *pixels = NULL;
+        uint16_t out_quant[3][64];
+        int16_t *out_coef[3] = {NULL, NULL, NULL};
+        if(o->jpeg_quality) {
+                /* -j: int16 coefficients of a 4:4:4 (or one-component) JPEG come down instead of samples */
+                jpeg_out_tables(jp.n, o->jpeg_quality, out_quant);
+                job.out_blocks_w = (job.out_w + 7) / 8;
+                job.out_blocks_h = (job.out_h + 7) / 8;
+                for(unsigned c = 0; c < jp.n; c++) {
+                        out_coef[c] = malloc(sizeof(int16_t) * 64 * (size_t)job.out_blocks_w * job.out_blocks_h);
+                        if(!out_coef[c]) { die("could not allocate image data"); }
+                        job.out_quant[c] = out_quant[c];
+                        job.out_coef[c] = out_coef[c];
+                }
+        } else {
+                job.out_bits = o->png_bits;
+                size_t bytes = (size_t)job.out_w * job.out_h * jp.n * (o->png_bits / 8);
+                pixels = malloc(bytes);
+                if(!pixels) { die("could not allocate image data"); }
+                job.out_rgb = pixels;
+        }
         job.on_rows = o->csv ? job_rows : NULL;
         job.on_progress = o->quiet ? NULL : job_progress;
         job.user = &ctx;
@@ -340,9 +431,11 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
-        write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels);
+        if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, out_coef); }
+        else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
+        for(unsigned c = 0; c < 3; c++) { free(out_coef[c]); }
 }
 
 /* ---- file-level parallelism (jpeg2png.c:330: omp parallel for over files) ---- */
@@ -386,6 +479,8 @@ static void usage(void)
                "  -g, --greyscale              greyscale PNG; also reads 1-component JPEGs.  The grey is component 0\n"
                "                               (Y) solved alone, as -s solves it, with the first -w/-p/-i value; not\n"
                "                               the luma of the default joint solve\n"
+               "  -j, --jpeg Q                 write a baseline JPEG of quality Q (1..100, 4:4:4; one component with -g)\n"
+               "                               straight from the solved planes instead of a PNG; needs -o for every input\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -403,15 +498,15 @@ int main(int argc, char **argv)
                 {"separate-components", no_argument, NULL, 's'}, {"16-bits-png", no_argument, NULL, '1'},
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
-                {"greyscale", no_argument, NULL, 'g'}, {NULL, 0, NULL, 0}};
+                {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
-        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL;
+                            .png_bits = 8, .jpeg_quality = 0, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:g", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -426,6 +521,7 @@ int main(int argc, char **argv)
                 case 'w': w_arg = optarg; break;
                 case 'z': z_arg = optarg; break;
                 case 'g': o.grey = true; break;
+                case 'j': j_arg = optarg; break;
                 default: help = true; break;
                 }
         }
@@ -458,6 +554,15 @@ int main(int argc, char **argv)
                 const unsigned long z = strtoul(z_arg, &end, 10);
                 if(end == z_arg || *end != '\0' || z_arg[0] == '-' || z < 1 || z > 4) { die("invalid zoom factor"); }
                 o.zoom = (unsigned)z;
+        }
+        if(j_arg) {
+                char *end = NULL;
+                const unsigned long q = strtoul(j_arg, &end, 10);
+                if(end == j_arg || *end != '\0' || j_arg[0] == '-' || q < 1 || q > 100) { die("invalid jpeg quality"); }
+                o.jpeg_quality = (int)q;
+                if(o.png_bits == 16) { die("16-bit output is only possible for PNG"); }
+                /* the default name would replace .jpg by .jpg: the input itself */
+                if(nout == 0) { die("-j needs an output file name (-o) for every input"); }
         }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);

@@ -387,6 +387,24 @@ int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsig
 int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
                             uint8_t *out_host);
 
+/* JPEG output: ONE (solver, channel) pair's current iterate as quantised DCT coefficients, ready for libjpeg's
+ * jpeg_write_coefficients — no RGB conversion and no 8-bit samples in between.  For each 8x8 block of the canvas plane:
+ * dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes), every coefficient divided by quant_table[j] as
+ * the correctly rounded f32 quotient, rounded to nearest (ties to even), clamped to [-1023, 1023] (what libjpeg's Huffman
+ * coder accepts).  No +128 anywhere: the planes are level-shifted already (luma is centred on 0 until the PNG writer adds
+ * 128, jpeg2png.c:156-159), which is what JPEG stores.  out_host receives blocks_h * blocks_w blocks of 64 int16,
+ * block-major, natural order (the layout of j2p_plane.data and of libjpeg's JBLOCK rows) — blocks_w x blocks_h from the
+ * canvas's top left corner, i.e. ceil(width / 8) x ceil(height / 8) for an image cropped from it.  quant_table: 64
+ * entries, natural order, all non-zero (J2P_EINVAL otherwise, as for blocks_w * 8 / blocks_h * 8 beyond the canvas).
+ * Whole / band rules and argument checks as j2p_planes_to_grey / j2p_planes_rows_to_grey; the rows form takes BLOCK rows
+ * [block_row_begin, block_row_end), which must lie inside the solver's band (band cuts are multiples of 16 rows: no block
+ * straddles two bands), and writes (block_row_end - block_row_begin) * blocks_w blocks. */
+int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h,
+                               const uint16_t quant_table[64], int16_t *out_host);
+int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w,
+                                    unsigned block_row_begin, unsigned block_row_end,
+                                    const uint16_t quant_table[64], int16_t *out_host);
+
 /* Image batches (BASELINE configs[4]; the file loop jpeg2png.c:330-337): a batch owns slots_per_device worker
  * threads per GPU, each driving one image at a time on streams of its own, so that the uploads, solves and
  * downloads of different images overlap; device memory is recycled between images (no hipMalloc / hipFree per
@@ -429,6 +447,13 @@ typedef struct j2p_job {
         int tile;
         unsigned tile_first, tile_count;
         size_t tile_min_band_pixels;           /* 0 = the library's gate (2 Mpixel) */
+        /* JPEG output (j2p_planes_to_coefficients): out_coef[0] != NULL selects it; out_bits must then be 0 and every one of the
+         * nchannel entries of out_quant (64 non-zero steps, natural order) and out_coef (out_blocks_h * out_blocks_w * 64
+         * int16) must be set.  Component c comes from the joint canvas or — separate — its own solver's; a tiled job converts
+         * every band's block rows on the band's GPU.  out_planes is still honoured.  All zero: no coefficient output */
+        const uint16_t *out_quant[J2P_MAX_CHANNELS];
+        int16_t *out_coef[J2P_MAX_CHANNELS];
+        unsigned out_blocks_w, out_blocks_h;
 } j2p_job;
 int j2p_batch_create(j2p_batch **out, unsigned ndev, const int devices[], unsigned slots_per_device);
 void j2p_batch_destroy(j2p_batch *b);                       /* finishes queued jobs first */

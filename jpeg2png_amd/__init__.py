@@ -54,7 +54,13 @@ class _CJob(ctypes.Structure):
                 ("out_bits", ctypes.c_uint), ("out_w", ctypes.c_uint), ("out_h", ctypes.c_uint),
                 ("out_rgb", ctypes.c_void_p), ("out_planes", ctypes.c_void_p * 3),
                 ("on_rows", _ROWS_CB), ("on_progress", _PROGRESS_CB), ("user", ctypes.c_void_p), ("tile", ctypes.c_int),
-                ("tile_first", ctypes.c_uint), ("tile_count", ctypes.c_uint), ("tile_min_band_pixels", ctypes.c_size_t)]
+                ("tile_first", ctypes.c_uint), ("tile_count", ctypes.c_uint), ("tile_min_band_pixels", ctypes.c_size_t),
+                ("out_quant", ctypes.c_void_p * 3), ("out_coef", ctypes.c_void_p * 3),
+                ("out_blocks_w", ctypes.c_uint), ("out_blocks_h", ctypes.c_uint)]
+
+
+class _CPlaneRef(ctypes.Structure):
+    _fields_ = [("solver", ctypes.c_void_p), ("channel", ctypes.c_uint)]
 
 
 class _CExchange(ctypes.Structure):
@@ -76,7 +82,7 @@ C_ABI_SYMBOLS = [
     "j2p_solver_download_gradient", "j2p_solver_set_logging", "j2p_log_rows_from_sums",
     "j2p_solver_plane_ptr", "j2p_solver_sync", "j2p_solver_kernel_times", "j2p_solver_enable_timing",
     "j2p_decode_plane", "j2p_dct8x8_blocks", "j2p_math_selftest", "j2p_planes_to_rgb", "j2p_planes_rows_to_rgb", "j2p_sqrt_exhaustive",
-    "j2p_planes_to_grey", "j2p_planes_rows_to_grey",
+    "j2p_planes_to_grey", "j2p_planes_rows_to_grey", "j2p_planes_to_coefficients", "j2p_planes_rows_to_coefficients",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -224,6 +230,9 @@ def _bind(path):
     lib.j2p_tiled_reset.argtypes = [ctypes.c_void_p]
     lib.j2p_tiled_download.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
     lib.j2p_tiled_host_cpu_seconds.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    lib.j2p_planes_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_planes_rows_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                    ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.c_uint]
     lib.j2p_batch_destroy.argtypes = [ctypes.c_void_p]
     lib.j2p_batch_destroy.restype = None
@@ -398,6 +407,28 @@ class Solver:
     def download(self, c):
         out = np.empty((self.row_end - self.row_begin, self.W), dtype=np.float32)
         _check(self._lib.j2p_solver_download(self._h, c, out.ctypes.data))
+        return out
+
+    def coefficients(self, c, quant_table, blocks_w=None, blocks_h=None):
+        """channel c's current iterate as quantised DCT coefficients for a JPEG writer (j2p_planes_to_coefficients):
+        dct8x8s of every 8x8 block, divided by quant_table (64 non-zero steps, natural order), rounded to nearest even,
+        clamped to +-1023 -> int16 [blocks_h, blocks_w, 64], natural order.  Default: the whole canvas; a band solver
+        gives its own block rows."""
+        q = np.ascontiguousarray(quant_table, dtype=np.uint16).reshape(-1)
+        if q.size != 64:
+            raise J2PError("quant_table must have 64 entries")
+        r0, r1 = self.row_begin // 8, self.row_end // 8
+        bw = self.W // 8 if blocks_w is None else int(blocks_w)
+        whole = self.row_begin == 0 and self.row_end == self.H
+        bh = (r1 - r0) if blocks_h is None else int(blocks_h)
+        if bw < 0 or bh < 0:
+            raise J2PError("blocks_w / blocks_h must not be negative")
+        out = np.empty((bh, bw, 64), dtype=np.int16)
+        ref = _CPlaneRef(self._h, int(c))
+        if whole:
+            _check(self._lib.j2p_planes_to_coefficients(ctypes.byref(ref), bw, bh, q.ctypes.data, out.ctypes.data))
+        else:
+            _check(self._lib.j2p_planes_rows_to_coefficients(ctypes.byref(ref), bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
     def download_gradient(self, c):
@@ -581,8 +612,11 @@ class Batch:
         self._pending = {}
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
-               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None):
-        """tile=True: the image is row-tiled over the batch's devices instead of solved on one of them;
+               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None):
+        """quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
+        quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
+        writer entropy-codes — instead of the float planes;
+        tile=True: the image is row-tiled over the batch's devices instead of solved on one of them;
         tile_devices=(first, count): over that slice of the batch's device list only; on_progress(n): called from the worker
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
         n = len(planes)
@@ -606,7 +640,29 @@ class Batch:
         W = max(p.w * p.w_samp for p in planes)
         H = max(p.h * p.h_samp for p in planes)
         shapes = [(p.h * p.h_samp, p.w * p.w_samp) if separate else (H, W) for p in planes]
-        if bits:
+        if quant_tables is not None:
+            if bits:
+                raise J2PError("job: coefficient output (quant_tables) needs bits = 0")
+            if len(quant_tables) != n:
+                raise J2PError("job: one quantisation table per plane")
+            if width is None or height is None or int(width) < 1 or int(height) < 1:
+                raise J2PError("job: coefficient output needs width and height")
+            bw, bh = (int(width) + 7) // 8, (int(height) + 7) // 8
+            tables = [np.ascontiguousarray(q, dtype=np.uint16).reshape(-1) for q in quant_tables]
+            if any(q.size != 64 for q in tables):
+                raise J2PError("job: a quantisation table has 64 entries")
+            if out is None:
+                out = [np.empty((bh, bw, 64), dtype=np.int16) for _ in range(n)]
+            if not (isinstance(out, (list, tuple)) and len(out) == n and all(
+                    isinstance(a, np.ndarray) and a.shape == (bh, bw, 64) and a.dtype == np.int16 and a.flags["C_CONTIGUOUS"]
+                    and a.flags["WRITEABLE"] for a in out)):
+                raise J2PError(f"out must be a list of {n} writeable C-contiguous int16 arrays of shape {(bh, bw, 64)}")
+            for c in range(n):
+                job.out_quant[c] = tables[c].ctypes.data
+                job.out_coef[c] = out[c].ctypes.data
+            job.out_blocks_w, job.out_blocks_h = bw, bh
+            keep = (keep, tables)
+        elif bits:
             # (out: a caller's own RGB array, reused between jobs — nothing is then mapped or faulted in while other jobs'
             # kernels run, which costs those a stalled launch each time)
             # (the C side writes height * width * 3 samples of bits / 8 bytes: anything else is a heap overflow or a

@@ -87,6 +87,17 @@ int validate_job(const j2p_job &d)
         if(d.out_bits && (!d.out_rgb || d.nchannel == 2)) {
                 return j2p_fail(J2P_EINVAL, "job: sample output needs out_rgb and three channels (RGB) or one (greyscale)");
         }
+        if(d.out_coef[0]) {
+                // coefficient output (JPEG): instead of samples, for every channel
+                if(d.out_bits) { return j2p_fail(J2P_EINVAL, "job: coefficient output (out_coef) needs out_bits 0"); }
+                if(d.out_blocks_w == 0 || d.out_blocks_h == 0) { return j2p_fail(J2P_EINVAL, "job: coefficient output needs out_blocks_w and out_blocks_h"); }
+                for(unsigned c = 0; c < d.nchannel; c++) {
+                        if(!d.out_coef[c] || !d.out_quant[c]) { return j2p_fail(J2P_EINVAL, "job: coefficient output needs out_coef and out_quant for channel %u", c); }
+                        for(int j = 0; j < 64; j++) {
+                                if(d.out_quant[c][j] == 0) { return j2p_fail(J2P_EINVAL, "job: channel %u: output quantisation table entry %d is zero", c, j); }
+                        }
+                }
+        }
         return J2P_OK;
 }
 
@@ -203,6 +214,26 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                         else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes)); }
                 }
         } else {
+                if(d.out_coef[0]) {
+                        // every band quantises its own block rows on its own GPU (cuts are multiples of 16 rows)
+                        for(unsigned c = 0; c < d.nchannel; c++) {
+                                const unsigned k = d.separate ? c : 0;
+                                if(d.out_blocks_h * 8ull > H[k]) {
+                                        rc = j2p_fail(J2P_EINVAL, "job: %u block rows are not inside channel %u's canvas of %u rows", d.out_blocks_h, c, H[k]);
+                                        goto out;
+                                }
+                                for(unsigned b = 0; b < nband; b++) {
+                                        const unsigned r0 = cuts[b] / 8;
+                                        unsigned r1 = (b + 1 < nband ? cuts[b + 1] : H[k]) / 8;
+                                        if(r1 > d.out_blocks_h) { r1 = d.out_blocks_h; }
+                                        if(r0 >= r1) { continue; }               // band below the image (canvas padding only)
+                                        j2p_plane_ref ref = {nullptr, d.separate ? 0 : c};
+                                        JOB_TRY(j2p_tiled_band(t[k], b, nullptr, nullptr, nullptr, &ref.solver));
+                                        JOB_TRY(j2p_planes_rows_to_coefficients(&ref, d.out_blocks_w, r0, r1, d.out_quant[c],
+                                                                                d.out_coef[c] + (size_t)r0 * d.out_blocks_w * 64));
+                                }
+                        }
+                }
                 for(unsigned c = 0; c < d.nchannel; c++) {
                         if(!d.out_planes[c]) { continue; }
                         JOB_TRY(j2p_tiled_download(d.separate ? t[c] : t[0], d.separate ? 0 : c, d.out_planes[c]));
@@ -272,6 +303,12 @@ int run_job(const j2p_job &d, int device)
                 if(d.nchannel == 1) { JOB_TRY(j2p_planes_to_grey(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }   // greyscale: one sample per pixel
                 else { JOB_TRY(j2p_planes_to_rgb(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }
         } else {
+                if(d.out_coef[0]) {
+                        for(unsigned c = 0; c < d.nchannel; c++) {
+                                const j2p_plane_ref ref = {d.separate ? s[c] : s[0], d.separate ? 0 : c};
+                                JOB_TRY(j2p_planes_to_coefficients(&ref, d.out_blocks_w, d.out_blocks_h, d.out_quant[c], d.out_coef[c]));
+                        }
+                }
                 for(unsigned c = 0; c < d.nchannel; c++) {
                         if(!d.out_planes[c]) { continue; }
                         JOB_TRY(j2p_solver_download(d.separate ? s[c] : s[0], d.separate ? 0 : c, d.out_planes[c]));

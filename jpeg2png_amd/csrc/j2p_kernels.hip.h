@@ -2777,6 +2777,69 @@ __global__ __launch_bounds__(256) void k_to_grey(const float *yp, unsigned ys, u
 }
 
 // ---------------------------------------------------------------------------
+// JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,
+// each coefficient divided by its output quantisation step (IEEE f32 quotient: `/` under
+// -fhip-fp32-correctly-rounded-divide-sqrt, never a reciprocal multiply), rounded to nearest even, clamped to
+// [-1023, 1023] (what libjpeg's Huffman coder takes: AC magnitudes of at most 10 bits, DC differences of at most 11).
+// No +128: JPEG's level shift and the luma fix-up of jpeg2png.c:156-159 cancel.
+// plane: raster floats, first row = row 0 of block row r0; blocks [r0, r1) x [0, blocks_w).
+// out: block-major int16 [(r1 - r0) * blocks_w][64], natural order — the JBLOCK rows of libjpeg.
+// Mapping of k_dct_blocks: one wavefront = 8 horizontally adjacent blocks, lane >> 3 the block, lane & 7 the row; a
+// lane loads its row of 8 floats as two float4 (8 lanes: 256 contiguous bytes of one plane row) and stores its 8
+// coefficients as one 16-byte vector (the wavefront: 1 KB contiguous).
+// ---------------------------------------------------------------------------
+struct QuantSteps {
+        float q[64];        // natural order
+};
+
+__global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, unsigned stride, unsigned blocks_w, unsigned r0, unsigned r1,
+                                                         QuantSteps steps, int16_t *out)
+{
+        __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
+        __shared__ float qs[64];
+        if(threadIdx.x < 64) { qs[threadIdx.x] = steps.q[threadIdx.x]; }
+        __syncthreads();
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned groups_x = (blocks_w + 7) / 8;
+        const unsigned grp = blockIdx.x * 4 + wave;
+        if(grp >= groups_x * (r1 - r0)) { return; }                     // whole wavefronts only: no barrier follows
+        const unsigned by = grp / groups_x, bx = (grp % groups_x) * 8 + (unsigned)(lane >> 3);
+        const int rr = lane & 7;
+        const bool ok = bx < blocks_w;
+        float v[8];
+        if(ok) {
+                const float4 *src = reinterpret_cast<const float4 *>(plane + (size_t)(by * 8 + (unsigned)rr) * stride + bx * 8);
+                const float4 a = src[0], b = src[1];
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+                v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        } else {
+#pragma unroll
+                for(int u = 0; u < 8; u++) { v[u] = 0.f; }
+        }
+        float *scratch = tp + wave * kTpWave;
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        unsigned packed[4];
+#pragma unroll
+        for(int u = 0; u < 8; u += 2) {
+                unsigned half[2];
+#pragma unroll
+                for(int k = 0; k < 2; k++) {
+                        float t = rintf(v[u + k] / qs[rr * 8 + u + k]);
+                        t = t > 1023.f ? 1023.f : (t < -1023.f ? -1023.f : t);
+                        half[k] = (unsigned)(int)t & 0xffffu;
+                }
+                packed[u / 2] = half[0] | (half[1] << 16);
+        }
+        if(ok) {
+                uint4 *dst = reinterpret_cast<uint4 *>(out + ((size_t)by * blocks_w + bx) * 64 + rr * 8);
+                *dst = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+        }
+}
+
+// ---------------------------------------------------------------------------
 // Self-test of the fast division / square root against the compiler's IEEE forms
 // on n pseudo-random operand pairs inside the screened range (tests/ only).
 // ---------------------------------------------------------------------------

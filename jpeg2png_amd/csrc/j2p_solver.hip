@@ -2104,6 +2104,58 @@ int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row
         return convert_rows(plane, 1, w, row_begin, row_end, bits, out_host);
 }
 
+// block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients (k_quantise_blocks)
+static int quantise_rows(const j2p_plane_ref *plane, unsigned blocks_w, unsigned r0, unsigned r1, const uint16_t quant_table[64],
+                         int16_t *out_host)
+{
+        j2p_solver *s = plane->solver;
+        if(!s || plane->channel >= s->nch) { return fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
+        QuantSteps steps;
+        for(int j = 0; j < 64; j++) {
+                if(quant_table[j] == 0) { return fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
+                steps.q[j] = (float)quant_table[j];
+        }
+        if((unsigned long long)blocks_w * 8 > s->W || r0 * 8ull < s->row0 || r1 * 8ull > (unsigned long long)s->row0 + s->rows) {
+                return fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks are not inside the solver's rows [%u,%u) x %u columns",
+                            r0, r1, blocks_w, s->row0, s->row0 + s->rows, s->W);
+        }
+        if(s->grad_done) { return fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
+        const float *src = s->ch[plane->channel].xbuf[s->cur] + (size_t)(kHalo + (r0 * 8 - s->row0)) * s->W;
+        DeviceGuard guard(s->device);
+        const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
+        void *dout = nullptr;
+        size_t dout_bytes = 0;
+        HIP_TRY(pool_take(s->device, bytes, &dout, &dout_bytes));
+        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
+        hipLaunchKernelGGL(k_quantise_blocks, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s->stream, src, s->W, blocks_w, r0, r1, steps,
+                           static_cast<int16_t *>(dout));
+        hipError_t e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s->stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(s->stream); }
+        pool_give(s->device, dout, dout_bytes);
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h, const uint16_t quant_table[64],
+                               int16_t *out_host)
+{
+        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || blocks_h == 0) { return fail(J2P_EINVAL, "empty image"); }
+        if(plane->solver && !plane->solver->whole) {
+                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: j2p_planes_rows_to_coefficients)");
+        }
+        return quantise_rows(plane, blocks_w, 0, blocks_h, quant_table, out_host);
+}
+
+int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned block_row_begin, unsigned block_row_end,
+                                    const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || block_row_begin >= block_row_end) { return fail(J2P_EINVAL, "empty row range"); }
+        return quantise_rows(plane, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+}
+
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,
                       unsigned long long *sqrt_mismatches)
 {
