@@ -19,9 +19,12 @@
  *                  small to pay for the cross-band schedule: at least 2 Mpixel per band) — same pixels either way
  *   -g, --greyscale = a greyscale PNG: the reference's compute(1, ...) on component 0 alone, as `-s` solves it
  *                  (jpeg2png.c:147-152), written with Cb = Cr = 0 (png.c:37-45); one- and three-component JPEGs
- *   -j, --jpeg Q = a baseline JFIF file of libjpeg quality Q (1..100) instead of a PNG, 4:4:4 (one component with -g):
+ *   -j, --jpeg Q = a baseline JFIF file of libjpeg quality Q (1..100) instead of a PNG, 4:4:4 unless -S (one component with -g):
  *                  the GPU turns the solved float planes straight into quantised coefficients (j2p_planes_to_coefficients)
  *                  and the host only entropy-codes them (jpeg_write_coefficients) — no RGB, no 8-bit samples in between
+ *   -S, --chroma-subsampling 444|422|420|440 = with -j: the chroma components of the file at half the resolution across, across
+ *                  and down, or down; every chroma sample is the mean of the solved values it covers (the mean the solver's
+ *                  projection constrains, compute.c:351-359), taken in float on the GPU (j2p_planes_to_coefficients_sub)
  * Messages and exit codes follow the reference ("jpeg2png: <message>", EXIT_FAILURE).
  */
 #define _POSIX_C_SOURCE 200809L
@@ -209,7 +212,7 @@ static void write_png(FILE *out, unsigned w, unsigned h, unsigned bits, unsigned
 
 /* libjpeg's own tables for `quality` (jpeg_set_defaults, jpeg_set_colorspace, jpeg_set_quality(Q, TRUE)), natural order:
  * table 0 for component 0, table 1 for the chroma components */
-static void setup_jpeg_out(struct jpeg_compress_struct *c, unsigned w, unsigned h, unsigned ncomp, int quality)
+static void setup_jpeg_out(struct jpeg_compress_struct *c, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h)
 {
         c->image_width = w;
         c->image_height = h;
@@ -218,9 +221,10 @@ static void setup_jpeg_out(struct jpeg_compress_struct *c, unsigned w, unsigned 
         jpeg_set_defaults(c);
         jpeg_set_colorspace(c, ncomp == 1 ? JCS_GRAYSCALE : JCS_YCbCr);
         jpeg_set_quality(c, quality, TRUE);
+        /* chroma at 1 / sub_w x 1 / sub_h: component 0 carries the factors, the others 1 (4:4:4: all 1) */
         for(unsigned i = 0; i < ncomp; i++) {
-                c->comp_info[i].h_samp_factor = 1;                      /* 4:4:4 */
-                c->comp_info[i].v_samp_factor = 1;
+                c->comp_info[i].h_samp_factor = i == 0 ? (int)sub_w : 1;
+                c->comp_info[i].v_samp_factor = i == 0 ? (int)sub_h : 1;
         }
 }
 
@@ -231,7 +235,7 @@ static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
         c.err = jpeg_std_error(&err);
         err.output_message = jpeg_message;
         jpeg_create_compress(&c);
-        setup_jpeg_out(&c, 8, 8, ncomp, quality);
+        setup_jpeg_out(&c, 8, 8, ncomp, quality, 1, 1);
         for(unsigned i = 0; i < ncomp; i++) {
                 JQUANT_TBL *tbl = c.quant_tbl_ptrs[c.comp_info[i].quant_tbl_no];
                 if(!tbl) { die("libjpeg gave no quantization table"); }
@@ -240,8 +244,11 @@ static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
         jpeg_destroy_compress(&c);
 }
 
-/* coef[i]: bh * bw blocks of 64 int16, block-major, natural order (JBLOCK rows) */
-static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, int16_t *const coef[3])
+/* coef[i]: component i's bh * bw blocks of 64 int16, block-major, natural order (JBLOCK rows); component 0 has
+ * ceil(w / 8) x ceil(h / 8) blocks, the chroma components ceil(that / sub_w) x ceil(that / sub_h).  Only these real blocks are
+ * filled: the dummy blocks that complete a partial MCU are libjpeg's own (jctrans.c), but it reaches them through arrays
+ * whose sizes are rounded up to the component's sampling factors and that can hold v_samp_factor rows at a time */
+static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h, int16_t *const coef[3])
 {
         struct jpeg_compress_struct c;
         struct jpeg_error_mgr err;
@@ -249,7 +256,8 @@ static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int qu
         err.output_message = jpeg_message;
         jpeg_create_compress(&c);
         jpeg_stdio_dest(&c, out);
-        setup_jpeg_out(&c, w, h, ncomp, quality);
+        if(ncomp == 1) { sub_w = sub_h = 1; }
+        setup_jpeg_out(&c, w, h, ncomp, quality, sub_w, sub_h);
         const unsigned bw = (w + 7) / 8, bh = (h + 7) / 8;
 #if JPEG_LIB_VERSION >= 70
         /* IJG 7+: jpeg_write_coefficients expects what jpeg_calc_jpeg_dimensions / initial_setup would have left */
@@ -259,16 +267,22 @@ static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int qu
         c.jpeg_height = h;
 #endif
         jvirt_barray_ptr arrays[3] = {NULL, NULL, NULL};
+        unsigned cbw[3], cbh[3];
         for(unsigned i = 0; i < ncomp; i++) {
-                c.comp_info[i].width_in_blocks = bw;
-                c.comp_info[i].height_in_blocks = bh;
-                arrays[i] = c.mem->request_virt_barray((j_common_ptr)&c, JPOOL_IMAGE, FALSE, bw, bh, 1);
+                const unsigned hs = (unsigned)c.comp_info[i].h_samp_factor, vs = (unsigned)c.comp_info[i].v_samp_factor;
+                cbw[i] = i == 0 ? bw : (bw + sub_w - 1) / sub_w;
+                cbh[i] = i == 0 ? bh : (bh + sub_h - 1) / sub_h;
+                c.comp_info[i].width_in_blocks = cbw[i];
+                c.comp_info[i].height_in_blocks = cbh[i];
+                /* (pre-zeroed: the transcoder reads the padding row of an odd block-row count, which nothing here writes) */
+                arrays[i] = c.mem->request_virt_barray((j_common_ptr)&c, JPOOL_IMAGE, TRUE, (cbw[i] + hs - 1) / hs * hs,
+                                                       (cbh[i] + vs - 1) / vs * vs, (JDIMENSION)vs);
         }
         jpeg_write_coefficients(&c, arrays);
         for(unsigned i = 0; i < ncomp; i++) {
-                for(unsigned by = 0; by < bh; by++) {
+                for(unsigned by = 0; by < cbh[i]; by++) {
                         JBLOCKARRAY row = c.mem->access_virt_barray((j_common_ptr)&c, arrays[i], by, 1, TRUE);
-                        memcpy(row[0][0], coef[i] + (size_t)by * bw * 64, sizeof(int16_t) * 64 * bw);
+                        memcpy(row[0][0], coef[i] + (size_t)by * cbw[i] * 64, sizeof(int16_t) * 64 * cbw[i]);
                 }
         }
         jpeg_finish_compress(&c);
@@ -282,6 +296,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
+        unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
         bool grey;              /* -g: component 0 alone, one-channel job, greyscale PNG */
         unsigned zoom;          /* -z: integer zoom factor 1..4 (every sampling factor times zoom, output zoom times the size) */
@@ -403,12 +418,16 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         uint16_t out_quant[3][64];
         int16_t *out_coef[3] = {NULL, NULL, NULL};
         if(o->jpeg_quality) {
-                /* -j: int16 coefficients of a 4:4:4 (or one-component) JPEG come down instead of samples */
+                /* -j: int16 coefficients of a JPEG come down instead of samples (-S: fewer for the chroma components) */
                 jpeg_out_tables(jp.n, o->jpeg_quality, out_quant);
                 job.out_blocks_w = (job.out_w + 7) / 8;
                 job.out_blocks_h = (job.out_h + 7) / 8;
                 for(unsigned c = 0; c < jp.n; c++) {
-                        out_coef[c] = malloc(sizeof(int16_t) * 64 * (size_t)job.out_blocks_w * job.out_blocks_h);
+                        job.out_sub_w[c] = c == 0 ? 1 : o->sub_w;
+                        job.out_sub_h[c] = c == 0 ? 1 : o->sub_h;
+                        const size_t bw = (job.out_blocks_w + job.out_sub_w[c] - 1) / job.out_sub_w[c];
+                        const size_t bh = (job.out_blocks_h + job.out_sub_h[c] - 1) / job.out_sub_h[c];
+                        out_coef[c] = malloc(sizeof(int16_t) * 64 * bw * bh);
                         if(!out_coef[c]) { die("could not allocate image data"); }
                         job.out_quant[c] = out_quant[c];
                         job.out_coef[c] = out_coef[c];
@@ -431,7 +450,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
-        if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, out_coef); }
+        if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, out_coef); }
         else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
@@ -479,8 +498,11 @@ static void usage(void)
                "  -g, --greyscale              greyscale PNG; also reads 1-component JPEGs.  The grey is component 0\n"
                "                               (Y) solved alone, as -s solves it, with the first -w/-p/-i value; not\n"
                "                               the luma of the default joint solve\n"
-               "  -j, --jpeg Q                 write a baseline JPEG of quality Q (1..100, 4:4:4; one component with -g)\n"
+               "  -j, --jpeg Q                 write a baseline JPEG of quality Q (1..100; 4:4:4 unless -S, one component with -g)\n"
                "                               straight from the solved planes instead of a PNG; needs -o for every input\n"
+               "  -S, --chroma-subsampling 444|422|420|440\n"
+               "                               with -j: chroma at half the resolution across (422), across and down (420)\n"
+               "                               or down (440), every sample the mean of the solved values it covers\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -498,15 +520,16 @@ int main(int argc, char **argv)
                 {"separate-components", no_argument, NULL, 's'}, {"16-bits-png", no_argument, NULL, '1'},
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
-                {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'}, {NULL, 0, NULL, 0}};
+                {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
+                {"chroma-subsampling", required_argument, NULL, 'S'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .jpeg_quality = 0, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
-        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL;
+                            .png_bits = 8, .jpeg_quality = 0, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -522,6 +545,7 @@ int main(int argc, char **argv)
                 case 'z': z_arg = optarg; break;
                 case 'g': o.grey = true; break;
                 case 'j': j_arg = optarg; break;
+                case 'S': S_arg = optarg; break;
                 default: help = true; break;
                 }
         }
@@ -563,6 +587,16 @@ int main(int argc, char **argv)
                 if(o.png_bits == 16) { die("16-bit output is only possible for PNG"); }
                 /* the default name would replace .jpg by .jpg: the input itself */
                 if(nout == 0) { die("-j needs an output file name (-o) for every input"); }
+        }
+        if(S_arg) {
+                static const struct { const char *name; unsigned w, h; } subs[] = {{"444", 1, 1}, {"422", 2, 1}, {"420", 2, 2}, {"440", 1, 2}};
+                unsigned k = 0;
+                while(k < 4 && strcmp(S_arg, subs[k].name) != 0) { k++; }
+                if(k == 4) { die("invalid chroma subsampling"); }
+                if(!j_arg) { die("-S needs JPEG output (-j)"); }
+                if(o.grey && k != 0) { die("chroma subsampling needs a colour output"); }
+                o.sub_w = subs[k].w;
+                o.sub_h = subs[k].h;
         }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);

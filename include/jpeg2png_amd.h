@@ -405,6 +405,26 @@ int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_
                                     unsigned block_row_begin, unsigned block_row_end,
                                     const uint16_t quant_table[64], int16_t *out_host);
 
+/* Subsampled JPEG output (4:2:2, 4:2:0, 4:4:0): the same, of a plane at 1 / sub_w x 1 / sub_h of the canvas's resolution; sub_w and
+ * sub_h are 1 or 2 (J2P_EINVAL otherwise).  Output sample (X, Y), 0 <= X < 8 * blocks_w, 0 <= Y < 8 * blocks_h, is the mean the
+ * projection constrains (compute.c:351-359): a float accumulator that starts at 0.f takes the sub_h * sub_w canvas values at rows
+ * Y * sub_h + j, columns X * sub_w + i in raster order (j outer, i inner), one float addition each, and is divided by
+ * (float)(sub_w * sub_h).  A row index beyond the canvas's last row reads the last row, a column index beyond the last column the
+ * last column; every block must START inside the canvas (8 * sub_w * (blocks_w - 1) < width, 8 * sub_h * (blocks_h - 1) < height:
+ * J2P_EINVAL otherwise), so only the last block row / column of a grid that overhangs the canvas replicates — e.g. the 3 chroma
+ * blocks (48 columns) of a 4:2:0 file made from a 40-column canvas.  The 8x8 blocks of those samples are then transformed,
+ * divided, rounded and clamped exactly as above.  With sub_w = sub_h = 1 these ARE the functions above, their stricter "inside the
+ * canvas" check included.  A component of sampling (sub_w, sub_h) in an image of blocks_w x blocks_h full-resolution blocks has
+ * ceil(blocks_w / sub_w) x ceil(blocks_h / sub_h) blocks (libjpeg's ceil(ceil(width / sub_w) / 8)).
+ * Rows form: output block row r covers canvas rows [8 * sub_h * r, 8 * sub_h * (r + 1)); its first row must lie in the solver's
+ * band, and rows beyond the band are replicated only where the band ends with the canvas (band cuts are multiples of 16 rows, so
+ * no 4:2:0 block row straddles two bands). */
+int j2p_planes_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned blocks_h,
+                                   const uint16_t quant_table[64], int16_t *out_host);
+int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w,
+                                        unsigned block_row_begin, unsigned block_row_end,
+                                        const uint16_t quant_table[64], int16_t *out_host);
+
 /* Image batches (BASELINE configs[4]; the file loop jpeg2png.c:330-337): a batch owns slots_per_device worker
  * threads per GPU, each driving one image at a time on streams of its own, so that the uploads, solves and
  * downloads of different images overlap; device memory is recycled between images (no hipMalloc / hipFree per
@@ -454,6 +474,10 @@ typedef struct j2p_job {
         const uint16_t *out_quant[J2P_MAX_CHANNELS];
         int16_t *out_coef[J2P_MAX_CHANNELS];
         unsigned out_blocks_w, out_blocks_h;
+        /* subsampled coefficient output (j2p_planes_to_coefficients_sub): channel c at 1 / out_sub_w[c] x 1 / out_sub_h[c] of the
+         * resolution (1 or 2; 0 means 1).  out_blocks_w x out_blocks_h stays the grid of a full-resolution component; channel c gets,
+         * and out_coef[c] holds, ceil(out_blocks_w / out_sub_w[c]) x ceil(out_blocks_h / out_sub_h[c]) blocks */
+        unsigned out_sub_w[J2P_MAX_CHANNELS], out_sub_h[J2P_MAX_CHANNELS];
 } j2p_job;
 int j2p_batch_create(j2p_batch **out, unsigned ndev, const int devices[], unsigned slots_per_device);
 void j2p_batch_destroy(j2p_batch *b);                       /* finishes queued jobs first */

@@ -56,7 +56,8 @@ class _CJob(ctypes.Structure):
                 ("on_rows", _ROWS_CB), ("on_progress", _PROGRESS_CB), ("user", ctypes.c_void_p), ("tile", ctypes.c_int),
                 ("tile_first", ctypes.c_uint), ("tile_count", ctypes.c_uint), ("tile_min_band_pixels", ctypes.c_size_t),
                 ("out_quant", ctypes.c_void_p * 3), ("out_coef", ctypes.c_void_p * 3),
-                ("out_blocks_w", ctypes.c_uint), ("out_blocks_h", ctypes.c_uint)]
+                ("out_blocks_w", ctypes.c_uint), ("out_blocks_h", ctypes.c_uint),
+                ("out_sub_w", ctypes.c_uint * 3), ("out_sub_h", ctypes.c_uint * 3)]
 
 
 class _CPlaneRef(ctypes.Structure):
@@ -83,6 +84,7 @@ C_ABI_SYMBOLS = [
     "j2p_solver_plane_ptr", "j2p_solver_sync", "j2p_solver_kernel_times", "j2p_solver_enable_timing",
     "j2p_decode_plane", "j2p_dct8x8_blocks", "j2p_math_selftest", "j2p_planes_to_rgb", "j2p_planes_rows_to_rgb", "j2p_sqrt_exhaustive",
     "j2p_planes_to_grey", "j2p_planes_rows_to_grey", "j2p_planes_to_coefficients", "j2p_planes_rows_to_coefficients",
+    "j2p_planes_to_coefficients_sub", "j2p_planes_rows_to_coefficients_sub",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -233,6 +235,10 @@ def _bind(path):
     lib.j2p_planes_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_planes_rows_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                                     ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_planes_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                   ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_planes_rows_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                        ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.c_uint]
     lib.j2p_batch_destroy.argtypes = [ctypes.c_void_p]
     lib.j2p_batch_destroy.restype = None
@@ -311,6 +317,17 @@ def division_exhaustive(which, first=0, count=0, device=0):
     rep = (ctypes.c_ulonglong * 9)()
     _check(lib.j2p_division_exhaustive(device, which, first, count, rep))
     return rep[0], [hex(v) for v in rep[1:] if v]
+
+
+def _sampling(subsampling):
+    """(sx, sy) of a coefficient output: 1 or 2 each"""
+    try:
+        sx, sy = (int(v) for v in subsampling)
+    except (TypeError, ValueError):
+        raise J2PError("subsampling must be a pair (sx, sy)") from None
+    if sx not in (1, 2) or sy not in (1, 2):
+        raise J2PError(f"sampling factors {sx}x{sy} (1 and 2 are supported)")
+    return sx, sy
 
 
 class Solver:
@@ -409,23 +426,38 @@ class Solver:
         _check(self._lib.j2p_solver_download(self._h, c, out.ctypes.data))
         return out
 
-    def coefficients(self, c, quant_table, blocks_w=None, blocks_h=None):
+    def coefficients(self, c, quant_table, blocks_w=None, blocks_h=None, subsampling=(1, 1)):
         """channel c's current iterate as quantised DCT coefficients for a JPEG writer (j2p_planes_to_coefficients):
         dct8x8s of every 8x8 block, divided by quant_table (64 non-zero steps, natural order), rounded to nearest even,
         clamped to +-1023 -> int16 [blocks_h, blocks_w, 64], natural order.  Default: the whole canvas; a band solver
-        gives its own block rows."""
+        gives its own block rows.
+        subsampling=(sx, sy), each 1 or 2 (j2p_planes_to_coefficients_sub): of the plane at 1/sx x 1/sy of the resolution,
+        every sample the mean of its sy x sx canvas values; a grid that overhangs the canvas replicates the canvas's last
+        column / row (every block must start inside).  Default grid: ceil(canvas blocks / (sx, sy))."""
         q = np.ascontiguousarray(quant_table, dtype=np.uint16).reshape(-1)
         if q.size != 64:
             raise J2PError("quant_table must have 64 entries")
-        r0, r1 = self.row_begin // 8, self.row_end // 8
-        bw = self.W // 8 if blocks_w is None else int(blocks_w)
+        sx, sy = _sampling(subsampling)
         whole = self.row_begin == 0 and self.row_end == self.H
+        if (sx, sy) == (1, 1):
+            r0, r1 = self.row_begin // 8, self.row_end // 8
+            bw = self.W // 8 if blocks_w is None else int(blocks_w)
+        else:
+            # a band's block rows: those that start in it (cuts are multiples of 16 rows)
+            r0, r1 = -(-self.row_begin // (8 * sy)), -(-self.row_end // (8 * sy))
+            bw = -(-self.W // (8 * sx)) if blocks_w is None else int(blocks_w)
         bh = (r1 - r0) if blocks_h is None else int(blocks_h)
         if bw < 0 or bh < 0:
             raise J2PError("blocks_w / blocks_h must not be negative")
         out = np.empty((bh, bw, 64), dtype=np.int16)
         ref = _CPlaneRef(self._h, int(c))
-        if whole:
+        if (sx, sy) != (1, 1):
+            if whole:
+                _check(self._lib.j2p_planes_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, bh, q.ctypes.data, out.ctypes.data))
+            else:
+                _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data,
+                                                                     out.ctypes.data))
+        elif whole:
             _check(self._lib.j2p_planes_to_coefficients(ctypes.byref(ref), bw, bh, q.ctypes.data, out.ctypes.data))
         else:
             _check(self._lib.j2p_planes_rows_to_coefficients(ctypes.byref(ref), bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
@@ -612,10 +644,12 @@ class Batch:
         self._pending = {}
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
-               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None):
+               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None):
         """quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
         quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
         writer entropy-codes — instead of the float planes;
+        subsampling=[(sx, sy) per plane] (with quant_tables; 1 or 2 each): plane c at 1/sx x 1/sy of the resolution, int16
+        [ceil(ceil(height / 8) / sy), ceil(ceil(width / 8) / sx), 64] — the component of a 4:2:0 / 4:2:2 / 4:4:0 JPEG;
         tile=True: the image is row-tiled over the batch's devices instead of solved on one of them;
         tile_devices=(first, count): over that slice of the batch's device list only; on_progress(n): called from the worker
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
@@ -648,20 +682,27 @@ class Batch:
             if width is None or height is None or int(width) < 1 or int(height) < 1:
                 raise J2PError("job: coefficient output needs width and height")
             bw, bh = (int(width) + 7) // 8, (int(height) + 7) // 8
+            subs = [(1, 1)] * n if subsampling is None else [_sampling(v) for v in subsampling]
+            if len(subs) != n:
+                raise J2PError("job: one (sx, sy) pair per plane")
+            grids = [(-(-bh // sy), -(-bw // sx), 64) for sx, sy in subs]
             tables = [np.ascontiguousarray(q, dtype=np.uint16).reshape(-1) for q in quant_tables]
             if any(q.size != 64 for q in tables):
                 raise J2PError("job: a quantisation table has 64 entries")
             if out is None:
-                out = [np.empty((bh, bw, 64), dtype=np.int16) for _ in range(n)]
+                out = [np.empty(g, dtype=np.int16) for g in grids]
             if not (isinstance(out, (list, tuple)) and len(out) == n and all(
-                    isinstance(a, np.ndarray) and a.shape == (bh, bw, 64) and a.dtype == np.int16 and a.flags["C_CONTIGUOUS"]
-                    and a.flags["WRITEABLE"] for a in out)):
-                raise J2PError(f"out must be a list of {n} writeable C-contiguous int16 arrays of shape {(bh, bw, 64)}")
+                    isinstance(a, np.ndarray) and a.shape == g and a.dtype == np.int16 and a.flags["C_CONTIGUOUS"]
+                    and a.flags["WRITEABLE"] for a, g in zip(out, grids))):
+                raise J2PError(f"out must be a list of {n} writeable C-contiguous int16 arrays of shapes {grids}")
             for c in range(n):
                 job.out_quant[c] = tables[c].ctypes.data
                 job.out_coef[c] = out[c].ctypes.data
+                job.out_sub_w[c], job.out_sub_h[c] = subs[c]
             job.out_blocks_w, job.out_blocks_h = bw, bh
             keep = (keep, tables)
+        elif subsampling is not None:
+            raise J2PError("job: subsampling needs coefficient output (quant_tables)")
         elif bits:
             # (out: a caller's own RGB array, reused between jobs — nothing is then mapped or faulted in while other jobs'
             # kernels run, which costs those a stalled launch each time)

@@ -79,6 +79,9 @@ unsigned next_chunk(unsigned done, unsigned left, std::chrono::steady_clock::tim
 
 unsigned gcd_u(unsigned a, unsigned b) { return b ? gcd_u(b, a % b) : a; }
 
+// j2p_job::out_sub_w / out_sub_h: 0 means 1, so that zero-initialised jobs are 4:4:4
+unsigned out_sub(unsigned v) { return v ? v : 1u; }
+
 // what both paths of a job check before they touch anything
 int validate_job(const j2p_job &d)
 {
@@ -95,6 +98,9 @@ int validate_job(const j2p_job &d)
                         if(!d.out_coef[c] || !d.out_quant[c]) { return j2p_fail(J2P_EINVAL, "job: coefficient output needs out_coef and out_quant for channel %u", c); }
                         for(int j = 0; j < 64; j++) {
                                 if(d.out_quant[c][j] == 0) { return j2p_fail(J2P_EINVAL, "job: channel %u: output quantisation table entry %d is zero", c, j); }
+                        }
+                        if(d.out_sub_w[c] > 2 || d.out_sub_h[c] > 2) {
+                                return j2p_fail(J2P_EINVAL, "job: channel %u: output sampling factors %ux%u (1 and 2 are supported)", c, d.out_sub_w[c], d.out_sub_h[c]);
                         }
                 }
         }
@@ -215,22 +221,25 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 }
         } else {
                 if(d.out_coef[0]) {
-                        // every band quantises its own block rows on its own GPU (cuts are multiples of 16 rows)
+                        // every band quantises its own block rows on its own GPU (cuts are multiples of 16 rows: of a block row of
+                        // either sampling); the last band also takes the block row that overhangs the canvas
                         for(unsigned c = 0; c < d.nchannel; c++) {
                                 const unsigned k = d.separate ? c : 0;
-                                if(d.out_blocks_h * 8ull > H[k]) {
+                                const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
+                                const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
+                                if(sx * sy == 1 ? d.out_blocks_h * 8ull > H[k] : 8ull * sy * (bh - 1) >= H[k]) {
                                         rc = j2p_fail(J2P_EINVAL, "job: %u block rows are not inside channel %u's canvas of %u rows", d.out_blocks_h, c, H[k]);
                                         goto out;
                                 }
                                 for(unsigned b = 0; b < nband; b++) {
-                                        const unsigned r0 = cuts[b] / 8;
-                                        unsigned r1 = (b + 1 < nband ? cuts[b + 1] : H[k]) / 8;
-                                        if(r1 > d.out_blocks_h) { r1 = d.out_blocks_h; }
+                                        const unsigned r0 = cuts[b] / (8 * sy);
+                                        unsigned r1 = b + 1 < nband ? cuts[b + 1] / (8 * sy) : (H[k] + 8 * sy - 1) / (8 * sy);
+                                        if(r1 > bh) { r1 = bh; }
                                         if(r0 >= r1) { continue; }               // band below the image (canvas padding only)
                                         j2p_plane_ref ref = {nullptr, d.separate ? 0 : c};
                                         JOB_TRY(j2p_tiled_band(t[k], b, nullptr, nullptr, nullptr, &ref.solver));
-                                        JOB_TRY(j2p_planes_rows_to_coefficients(&ref, d.out_blocks_w, r0, r1, d.out_quant[c],
-                                                                                d.out_coef[c] + (size_t)r0 * d.out_blocks_w * 64));
+                                        JOB_TRY(j2p_planes_rows_to_coefficients_sub(&ref, sx, sy, bw, r0, r1, d.out_quant[c],
+                                                                                    d.out_coef[c] + (size_t)r0 * bw * 64));
                                 }
                         }
                 }
@@ -306,7 +315,9 @@ int run_job(const j2p_job &d, int device)
                 if(d.out_coef[0]) {
                         for(unsigned c = 0; c < d.nchannel; c++) {
                                 const j2p_plane_ref ref = {d.separate ? s[c] : s[0], d.separate ? 0 : c};
-                                JOB_TRY(j2p_planes_to_coefficients(&ref, d.out_blocks_w, d.out_blocks_h, d.out_quant[c], d.out_coef[c]));
+                                const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
+                                JOB_TRY(j2p_planes_to_coefficients_sub(&ref, sx, sy, (d.out_blocks_w + sx - 1) / sx, (d.out_blocks_h + sy - 1) / sy,
+                                                                       d.out_quant[c], d.out_coef[c]));
                         }
                 }
                 for(unsigned c = 0; c < d.nchannel; c++) {

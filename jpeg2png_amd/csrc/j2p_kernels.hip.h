@@ -2792,6 +2792,30 @@ struct QuantSteps {
         float q[64];        // natural order
 };
 
+// the tail both forms share: a lane holds row `lane & 7` of block `lane >> 3` of its wavefront's 8 blocks in v[];
+// dct8x8s, quotient, rounding, clamp, and the row's 8 coefficients as one 16-byte store into `block` (ok lanes only)
+__device__ __forceinline__ void quantise_store(float (&v)[8], float *scratch, const float *qs, int lane, bool ok, int16_t *block)
+{
+        const int rr = lane & 7;
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        unsigned packed[4];
+#pragma unroll
+        for(int u = 0; u < 8; u += 2) {
+                unsigned half[2];
+#pragma unroll
+                for(int k = 0; k < 2; k++) {
+                        float t = rintf(v[u + k] / qs[rr * 8 + u + k]);
+                        t = t > 1023.f ? 1023.f : (t < -1023.f ? -1023.f : t);
+                        half[k] = (unsigned)(int)t & 0xffffu;
+                }
+                packed[u / 2] = half[0] | (half[1] << 16);
+        }
+        if(ok) { *reinterpret_cast<uint4 *>(block + rr * 8) = make_uint4(packed[0], packed[1], packed[2], packed[3]); }
+}
+
 __global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, unsigned stride, unsigned blocks_w, unsigned r0, unsigned r1,
                                                          QuantSteps steps, int16_t *out)
 {
@@ -2816,27 +2840,76 @@ __global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, uns
 #pragma unroll
                 for(int u = 0; u < 8; u++) { v[u] = 0.f; }
         }
-        float *scratch = tp + wave * kTpWave;
-        transpose8(v, scratch, lane);
-        fdct8(v);
-        transpose8(v, scratch, lane);
-        fdct8(v);
-        unsigned packed[4];
+        quantise_store(v, tp + wave * kTpWave, qs, lane, ok, out + ((size_t)by * blocks_w + bx) * 64);
+}
+
+// ---------------------------------------------------------------------------
+// The subsampling form (4:2:2, 4:2:0, 4:4:0 output): output sample (X, Y) of the block grid is the mean the projection
+// constrains (compute.c:351-359) — a float accumulator that starts at 0.f takes the SY * SX canvas values at rows
+// Y * SY + j, columns X * SX + i in raster order (j outer, i inner), one addition each, and is divided by
+// (float)(SX * SY) — and the 8x8 blocks of those samples go through the same transform, quotient, rounding and clamp.
+// plane: first row = the first canvas row of the block_rows output block rows; stride x rows: what the canvas holds from
+// there on.  A row index beyond the canvas's last row reads the last row, a column beyond the last column the last
+// column: only the last block row / column of a grid that overhangs the canvas (every block STARTS inside it, which the
+// host checks).  Same mapping: a lane loads SY rows of 8 * SX consecutive floats as float4 (a block starts at a
+// multiple of 8 * SX floats and the stride is a multiple of 8: aligned), 8 lanes 256 * SX contiguous bytes of a canvas
+// row; only lanes whose footprint crosses the canvas's edge take the clamped scalar loads.
+// ---------------------------------------------------------------------------
+template <int SX, int SY>
+__global__ __launch_bounds__(256) void k_quantise_blocks_sub(const float *plane, unsigned stride, unsigned rows, unsigned blocks_w,
+                                                             unsigned block_rows, QuantSteps steps, int16_t *out)
+{
+        static_assert((SX == 1 || SX == 2) && (SY == 1 || SY == 2), "sampling factors 1 and 2");
+        __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
+        __shared__ float qs[64];
+        if(threadIdx.x < 64) { qs[threadIdx.x] = steps.q[threadIdx.x]; }
+        __syncthreads();
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned groups_x = (blocks_w + 7) / 8;
+        const unsigned grp = blockIdx.x * 4 + wave;
+        if(grp >= groups_x * block_rows) { return; }                    // whole wavefronts only: no barrier follows
+        const unsigned by = grp / groups_x, bx = (grp % groups_x) * 8 + (unsigned)(lane >> 3);
+        const int rr = lane & 7;
+        const bool ok = bx < blocks_w;
+        const unsigned x0 = bx * (8 * SX), y0 = (by * 8 + (unsigned)rr) * SY;
+        float v[8];
 #pragma unroll
-        for(int u = 0; u < 8; u += 2) {
-                unsigned half[2];
+        for(int u = 0; u < 8; u++) { v[u] = 0.f; }
+        if(ok && x0 + 8 * SX <= stride && y0 + SY <= rows) {
 #pragma unroll
-                for(int k = 0; k < 2; k++) {
-                        float t = rintf(v[u + k] / qs[rr * 8 + u + k]);
-                        t = t > 1023.f ? 1023.f : (t < -1023.f ? -1023.f : t);
-                        half[k] = (unsigned)(int)t & 0xffffu;
+                for(int j = 0; j < SY; j++) {
+                        const float4 *src = reinterpret_cast<const float4 *>(plane + (size_t)(y0 + j) * stride + x0);
+                        float f[8 * SX];
+#pragma unroll
+                        for(int k = 0; k < 2 * SX; k++) {
+                                const float4 a = src[k];
+                                f[4 * k] = a.x; f[4 * k + 1] = a.y; f[4 * k + 2] = a.z; f[4 * k + 3] = a.w;
+                        }
+#pragma unroll
+                        for(int u = 0; u < 8; u++) {
+#pragma unroll
+                                for(int i = 0; i < SX; i++) { v[u] = v[u] + f[u * SX + i]; }
+                        }
                 }
-                packed[u / 2] = half[0] | (half[1] << 16);
+        } else if(ok) {
+                // the footprint crosses the canvas's last column or row: replicate them
+#pragma unroll
+                for(int j = 0; j < SY; j++) {
+                        const unsigned y = y0 + j < rows ? y0 + j : rows - 1;
+                        const float *src = plane + (size_t)y * stride;
+#pragma unroll
+                        for(int u = 0; u < 8; u++) {
+#pragma unroll
+                                for(int i = 0; i < SX; i++) {
+                                        const unsigned x = x0 + u * SX + i;
+                                        v[u] = v[u] + src[x < stride ? x : stride - 1];
+                                }
+                        }
+                }
         }
-        if(ok) {
-                uint4 *dst = reinterpret_cast<uint4 *>(out + ((size_t)by * blocks_w + bx) * 64 + rr * 8);
-                *dst = make_uint4(packed[0], packed[1], packed[2], packed[3]);
-        }
+#pragma unroll
+        for(int u = 0; u < 8; u++) { v[u] = v[u] / (float)(SX * SY); }
+        quantise_store(v, tp + wave * kTpWave, qs, lane, ok, out + ((size_t)by * blocks_w + bx) * 64);
 }
 
 // ---------------------------------------------------------------------------

@@ -2156,6 +2156,72 @@ int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_
         return quantise_rows(plane, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
 }
 
+// the subsampling form (k_quantise_blocks_sub): output block row r covers canvas rows [8 * sub_h * r, 8 * sub_h * (r + 1)); every
+// block starts inside the canvas and the solver's rows, and what a block reaches beyond them are the canvas's last rows / columns
+static int quantise_rows_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0, unsigned r1,
+                             const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(sub_w < 1 || sub_w > 2 || sub_h < 1 || sub_h > 2) {
+                return fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
+        }
+        if(sub_w == 1 && sub_h == 1) { return quantise_rows(plane, blocks_w, r0, r1, quant_table, out_host); }
+        j2p_solver *s = plane->solver;
+        if(!s || plane->channel >= s->nch) { return fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
+        QuantSteps steps;
+        for(int j = 0; j < 64; j++) {
+                if(quant_table[j] == 0) { return fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
+                steps.q[j] = (float)quant_table[j];
+        }
+        const unsigned long long row_end = (unsigned long long)s->row0 + s->rows, step_y = 8ull * sub_h;
+        // (rows beyond the solver's own may only be the canvas's: a band that is not the last ends on a multiple of 16)
+        if(8ull * sub_w * (blocks_w - 1) >= s->W || step_y * r0 < s->row0 || step_y * (r1 - 1) >= row_end ||
+           (step_y * r1 > row_end && row_end != s->H)) {
+                return fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks of %ux%u-pixel samples are not inside the solver's rows "
+                            "[%u,%u) x %u columns (every block must start there; only the canvas's last rows and columns are replicated)",
+                            r0, r1, blocks_w, sub_w, sub_h, s->row0, s->row0 + s->rows, s->W);
+        }
+        if(s->grad_done) { return fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
+        const unsigned first = (unsigned)(step_y * r0);
+        const float *src = s->ch[plane->channel].xbuf[s->cur] + (size_t)(kHalo + (first - s->row0)) * s->W;
+        DeviceGuard guard(s->device);
+        const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
+        void *dout = nullptr;
+        size_t dout_bytes = 0;
+        HIP_TRY(pool_take(s->device, bytes, &dout, &dout_bytes));
+        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
+        const dim3 grid((unsigned)((groups + 3) / 4)), block(256);
+        const unsigned rows = (unsigned)(row_end - first);
+        int16_t *o = static_cast<int16_t *>(dout);
+        if(sub_w == 2 && sub_h == 2) { hipLaunchKernelGGL((k_quantise_blocks_sub<2, 2>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
+        else if(sub_w == 2) { hipLaunchKernelGGL((k_quantise_blocks_sub<2, 1>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
+        else { hipLaunchKernelGGL((k_quantise_blocks_sub<1, 2>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
+        hipError_t e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s->stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(s->stream); }
+        pool_give(s->device, dout, dout_bytes);
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients_sub: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_planes_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned blocks_h,
+                                   const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || blocks_h == 0) { return fail(J2P_EINVAL, "empty image"); }
+        if(plane->solver && !plane->solver->whole) {
+                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: j2p_planes_rows_to_coefficients_sub)");
+        }
+        return quantise_rows_sub(plane, sub_w, sub_h, blocks_w, 0, blocks_h, quant_table, out_host);
+}
+
+int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w,
+                                        unsigned block_row_begin, unsigned block_row_end, const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || block_row_begin >= block_row_end) { return fail(J2P_EINVAL, "empty row range"); }
+        return quantise_rows_sub(plane, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+}
+
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,
                       unsigned long long *sqrt_mismatches)
 {
