@@ -232,11 +232,6 @@ def _bind(path):
     lib.j2p_tiled_reset.argtypes = [ctypes.c_void_p]
     lib.j2p_tiled_download.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
     lib.j2p_tiled_host_cpu_seconds.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-    lib.j2p_planes_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
-    lib.j2p_planes_rows_to_coefficients.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
-                                                    ctypes.c_void_p, ctypes.c_void_p]
-    lib.j2p_planes_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
-                                                   ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_planes_rows_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                                         ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.c_uint]
@@ -427,40 +422,26 @@ class Solver:
         return out
 
     def coefficients(self, c, quant_table, blocks_w=None, blocks_h=None, subsampling=(1, 1)):
-        """channel c's current iterate as quantised DCT coefficients for a JPEG writer (j2p_planes_to_coefficients):
+        """channel c's current iterate as quantised DCT coefficients for a JPEG writer (j2p_planes_rows_to_coefficients_sub):
         dct8x8s of every 8x8 block, divided by quant_table (64 non-zero steps, natural order), rounded to nearest even,
         clamped to +-1023 -> int16 [blocks_h, blocks_w, 64], natural order.  Default: the whole canvas; a band solver
         gives its own block rows.
-        subsampling=(sx, sy), each 1 or 2 (j2p_planes_to_coefficients_sub): of the plane at 1/sx x 1/sy of the resolution,
+        subsampling=(sx, sy), each 1 or 2: of the plane at 1/sx x 1/sy of the resolution,
         every sample the mean of its sy x sx canvas values; a grid that overhangs the canvas replicates the canvas's last
         column / row (every block must start inside).  Default grid: ceil(canvas blocks / (sx, sy))."""
         q = np.ascontiguousarray(quant_table, dtype=np.uint16).reshape(-1)
         if q.size != 64:
             raise J2PError("quant_table must have 64 entries")
         sx, sy = _sampling(subsampling)
-        whole = self.row_begin == 0 and self.row_end == self.H
-        if (sx, sy) == (1, 1):
-            r0, r1 = self.row_begin // 8, self.row_end // 8
-            bw = self.W // 8 if blocks_w is None else int(blocks_w)
-        else:
-            # a band's block rows: those that start in it (cuts are multiples of 16 rows)
-            r0, r1 = -(-self.row_begin // (8 * sy)), -(-self.row_end // (8 * sy))
-            bw = -(-self.W // (8 * sx)) if blocks_w is None else int(blocks_w)
+        # a band's block rows: those that start in it (cuts are multiples of 16 rows)
+        r0, r1 = -(-self.row_begin // (8 * sy)), -(-self.row_end // (8 * sy))
+        bw = -(-self.W // (8 * sx)) if blocks_w is None else int(blocks_w)
         bh = (r1 - r0) if blocks_h is None else int(blocks_h)
         if bw < 0 or bh < 0:
             raise J2PError("blocks_w / blocks_h must not be negative")
         out = np.empty((bh, bw, 64), dtype=np.int16)
         ref = _CPlaneRef(self._h, int(c))
-        if (sx, sy) != (1, 1):
-            if whole:
-                _check(self._lib.j2p_planes_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, bh, q.ctypes.data, out.ctypes.data))
-            else:
-                _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data,
-                                                                     out.ctypes.data))
-        elif whole:
-            _check(self._lib.j2p_planes_to_coefficients(ctypes.byref(ref), bw, bh, q.ctypes.data, out.ctypes.data))
-        else:
-            _check(self._lib.j2p_planes_rows_to_coefficients(ctypes.byref(ref), bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
+        _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
     def download_gradient(self, c):

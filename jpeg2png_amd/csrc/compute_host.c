@@ -16,15 +16,7 @@
 
 #include "jpeg2png_amd.h"
 #include "jpeg2png_amd_compute.h"
-
-/* Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar or a CSV log: compute.c:428,449-452 tick
- * once per iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a
- * fixed chunk moves the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first,
- * then a sixth of the iterations done so far (every chunk ~1/6 of the time elapsed: the bar of `-i 50` moves ~24
- * times, 4096^2 `-i 500` syncs ~36 times = under 1 % of its 60 ms), never more than ~50 ms worth or J2P_CHUNK_MAX
- * (the row buffer).  With neither a bar nor a log the whole loop goes to the device queue at once. */
-#define J2P_CHUNK_MAX 256u
-#define J2P_CHUNK_MS 50.0
+#include "j2p_internal.h"              /* the chunk rule (j2p_next_chunk), j2p_set_last_error, j2p_tiled_exchange_forced */
 
 /* stands in for `omp critical(progressbar)` (compute.c:450): compute() may be entered from
  * several host threads at once (jpeg2png.c:147,330) and they share one progress bar */
@@ -43,10 +35,6 @@ extern void die_message_start(void) __attribute__((weak));
  * preparing the output planes and freeing the inputs on a helper thread BESIDE the loop, wait = until the last iteration
  * has finished, download, destroy.  Kept per calling thread for j2p_compute_timing() — the host-to-host figure of
  * bench.py taken apart; J2P_COMPUTE_TIMING=1 also prints one line per call on stderr. */
-/* (internal, j2p_solver.hip) the calling thread's j2p_last_error() text */
-extern void j2p_set_last_error(const char *msg);
-extern int j2p_tiled_exchange_forced(void);          /* (internal, j2p_tiled.hip) */
-
 static double now_ms(void)
 {
         struct timespec ts;
@@ -204,19 +192,8 @@ static int compute_on(unsigned nband, const int devices[], unsigned nchannel, st
         unsigned done = 0;
         const double t_loop = now_ms();
         while(done < iterations) {
-                unsigned n = iterations - done;
                 /* nothing to report between chunks: the whole loop goes to the device queue at once */
-                if(want_log || pb) {
-                        unsigned chunk = done / 6;
-                        if(done) {
-                                const double per_it = (now_ms() - t_loop) / (double)done;
-                                const double most = per_it > 0. ? J2P_CHUNK_MS / per_it : (double)J2P_CHUNK_MAX;
-                                if((double)chunk > most) { chunk = (unsigned)most; }
-                        }
-                        if(chunk > J2P_CHUNK_MAX) { chunk = J2P_CHUNK_MAX; }
-                        if(chunk < 1) { chunk = 1; }
-                        if(n > chunk) { n = chunk; }
-                }
+                const unsigned n = want_log || pb ? j2p_next_chunk(done, iterations - done, now_ms() - t_loop) : iterations - done;
                 rc = t ? j2p_tiled_run(t, n, want_log ? rows : NULL) : j2p_solver_run(s, n, want_log ? rows : NULL);
                 if(rc == J2P_OK && !want_log && pb) { rc = t ? j2p_tiled_sync(t) : j2p_solver_sync(s); }
                 if(rc != J2P_OK) { break; }

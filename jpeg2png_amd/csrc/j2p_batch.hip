@@ -25,8 +25,6 @@
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
 
-extern "C" int j2p_tiled_exchange_forced(void);     // j2p_tiled.hip
-
 namespace {
 
 struct Job {
@@ -53,28 +51,10 @@ struct j2p_batch {
 
 namespace {
 
-// iterations per round trip when a job wants progress or log rows: as compute() does it (compute_host.c) — one iteration
-// each at first, then a sixth of the iterations done so far, never more than ~50 ms worth or kChunkMax (the row buffer):
-// the bar of the default `-i 50` moves two dozen times, not twice (compute.c:449-452 ticks once per iteration)
-constexpr unsigned kChunkMax = 256;
-constexpr double kChunkMs = 50.;
-unsigned next_chunk(unsigned done, unsigned left, std::chrono::steady_clock::time_point t_loop)
-{
-        unsigned chunk = done / 6;
-        if(done) {
-                const double per_it = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count() / done;
-                const double most = per_it > 0. ? kChunkMs / per_it : (double)kChunkMax;
-                if((double)chunk > most) { chunk = (unsigned)most; }
-        }
-        if(chunk > kChunkMax) { chunk = kChunkMax; }
-        if(chunk < 1) { chunk = 1; }
-        return left < chunk ? left : chunk;
-}
-
 #define JOB_TRY(expr)                                                                              \
         do {                                                                                       \
-                rc = (expr);                                                                       \
-                if(rc != J2P_OK) { goto out; }                                                     \
+                const int rc_ = (expr);                                                            \
+                if(rc_ != J2P_OK) { return rc_; }                                                  \
         } while(0)
 
 unsigned gcd_u(unsigned a, unsigned b) { return b ? gcd_u(b, a % b) : a; }
@@ -90,6 +70,7 @@ int validate_job(const j2p_job &d)
         if(d.out_bits && (!d.out_rgb || d.nchannel == 2)) {
                 return j2p_fail(J2P_EINVAL, "job: sample output needs out_rgb and three channels (RGB) or one (greyscale)");
         }
+        if(d.out_bits && (d.out_w == 0 || d.out_h == 0)) { return j2p_fail(J2P_EINVAL, "job: sample output of an empty image"); }
         if(d.out_coef[0]) {
                 // coefficient output (JPEG): instead of samples, for every channel
                 if(d.out_bits) { return j2p_fail(J2P_EINVAL, "job: coefficient output (out_coef) needs out_bits 0"); }
@@ -115,6 +96,122 @@ size_t tile_min_band_pixels(const j2p_job &d)
         return d.tile_min_band_pixels ? (d.tile_min_band_pixels == (size_t)-1 ? 0 : d.tile_min_band_pixels) : (size_t)2 << 20;
 }
 
+// Output channel c of a job is channel 0 of its own solve (`-s`, jpeg2png.c:147-152: one compute(1, ...) per component,
+// each with its own weight and iteration count) or channel c of the one joint solve (jpeg2png.c:144: compute(3, ...) with
+// the first weight and iteration count).  The only place that knows.
+struct Where {
+        unsigned solve, channel;
+};
+Where where(const j2p_job &d, unsigned c) { return d.separate ? Where{c, 0} : Where{0, c}; }
+unsigned solves(const j2p_job &d) { return d.separate ? d.nchannel : 1; }
+
+// The k-th solve of a job: one j2p_solver that holds the canvas on one GPU (a single band), or one j2p_tiled with a band
+// per GPU.  Never a one-band j2p_tiled: a whole-canvas solver and a band solver pick different norm paths.
+struct Engine {
+        j2p_solver *s = nullptr;
+        j2p_tiled *t = nullptr;
+        int run(unsigned n, j2p_log_row *rows) const { return t ? j2p_tiled_run(t, n, rows) : j2p_solver_run(s, n, rows); }
+        int sync() const { return t ? j2p_tiled_sync(t) : j2p_solver_sync(s); }
+        int download(unsigned c, float *out) const { return t ? j2p_tiled_download(t, c, out) : j2p_solver_download(s, c, out); }
+        unsigned nband() const
+        {
+                unsigned n = 1;
+                if(t) { (void)j2p_tiled_canvas(t, nullptr, nullptr, &n); }
+                return n;
+        }
+        // band b's solver and the canvas rows it holds
+        int band(unsigned b, j2p_solver **bs, unsigned *row_begin, unsigned *row_end) const
+        {
+                if(t) { return j2p_tiled_band(t, b, nullptr, row_begin, row_end, bs); }
+                *bs = s;
+                return j2p_solver_band(s, row_begin, row_end);
+        }
+};
+
+// the engines of one job, destroyed with it
+struct Engines {
+        Engine e[J2P_MAX_CHANNELS];
+        ~Engines()
+        {
+                for(Engine &k : e) {
+                        if(k.t) { j2p_tiled_destroy(k.t); }
+                        if(k.s) { j2p_solver_destroy(k.s); }
+                }
+        }
+};
+
+// What a job does once its engines exist: the iterations (compute.c:427-453), then the samples, coefficients or planes.
+// Chunked when the caller watches (j2p_next_chunk), so that its bar and CSV keep moving.  `overlap`: the chunk of every
+// solve is issued before any of them is settled (sync, progress, done) — how the three solves of `-s` overlap on one GPU,
+// unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
+int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap)
+{
+        const unsigned nsolve = solves(d);
+        if(!d.on_rows && !d.on_progress) {
+                for(unsigned k = 0; k < nsolve; k++) { JOB_TRY(e[k].run(d.iterations[k], nullptr)); }
+        } else {
+                j2p_log_row rows[J2P_CHUNK_MAX];
+                unsigned done[J2P_MAX_CHANNELS] = {0, 0, 0};
+                const auto t_loop = std::chrono::steady_clock::now();
+                for(;;) {
+                        unsigned step[J2P_MAX_CHANNELS] = {0, 0, 0};
+                        const auto settle = [&](unsigned k) {
+                                if(!d.on_rows) { JOB_TRY(e[k].sync()); }
+                                if(d.on_progress) { d.on_progress(d.user, step[k]); }
+                                done[k] += step[k];
+                                return (int)J2P_OK;
+                        };
+                        bool any = false;
+                        for(unsigned k = 0; k < nsolve; k++) {
+                                const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
+                                step[k] = j2p_next_chunk(done[k], d.iterations[k] - done[k], ms);
+                                if(!step[k]) { continue; }
+                                any = true;
+                                JOB_TRY(e[k].run(step[k], d.on_rows ? rows : nullptr));
+                                if(d.on_rows) { d.on_rows(d.user, d.separate ? k : 3u, done[k], step[k], rows); }   // channel 3 = joint, jpeg2png.c:143
+                                if(!overlap) { JOB_TRY(settle(k)); }
+                        }
+                        if(!any) { break; }
+                        for(unsigned k = 0; overlap && k < nsolve; k++) {
+                                if(step[k]) { JOB_TRY(settle(k)); }
+                        }
+                }
+        }
+        // Every band delivers its own rows from its own GPU.  The solves of a job share their cuts (multiples of 16 rows: of a
+        // block row of either sampling) and differ only in where the last band ends; the last band takes all that the output
+        // has left — the block row that overhangs the canvas too — and the rows forms refuse what is not there.
+        const unsigned nband = e[0].nband();
+        for(unsigned b = 0; b < nband; b++) {
+                j2p_plane_ref ref[J2P_MAX_CHANNELS];
+                unsigned row0[J2P_MAX_CHANNELS], row1[J2P_MAX_CHANNELS];
+                for(unsigned c = 0; c < d.nchannel; c++) {
+                        const Where at = where(d, c);
+                        ref[c].channel = at.channel;
+                        JOB_TRY(e[at.solve].band(b, &ref[c].solver, &row0[c], &row1[c]));
+                }
+                if(d.out_bits) {
+                        const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
+                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;
+                        if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
+                        uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
+                        if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, out)); }   // greyscale: one sample per pixel
+                        else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
+                        continue;
+                }
+                for(unsigned c = 0; d.out_coef[0] && c < d.nchannel; c++) {
+                        const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
+                        const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
+                        const unsigned r0 = row0[c] / (8 * sy), r1 = b + 1 < nband && row1[c] / (8 * sy) < bh ? row1[c] / (8 * sy) : bh;
+                        if(r0 >= r1) { continue; }                       // band below the image (canvas padding only)
+                        JOB_TRY(j2p_planes_rows_to_coefficients_sub(&ref[c], sx, sy, bw, r0, r1, d.out_quant[c], d.out_coef[c] + (size_t)r0 * bw * 64));
+                }
+        }
+        for(unsigned c = 0; !d.out_bits && c < d.nchannel; c++) {
+                if(d.out_planes[c]) { JOB_TRY(e[where(d, c).solve].download(where(d, c).channel, d.out_planes[c])); }
+        }
+        return J2P_OK;
+}
+
 // One image over several of the batch's devices (j2p_job::tile): every solve of the job becomes a j2p_tiled with band
 // b on devices[b]; the solves of `-s` share their cuts so that band b of the three components meets on one GPU for
 // the colour conversion.  Returns J2P_OK with *handled = false when the image should be solved on one GPU after all:
@@ -124,13 +221,13 @@ size_t tile_min_band_pixels(const j2p_job &d)
 int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handled)
 {
         *handled = false;
-        const unsigned nsolve = d.separate ? d.nchannel : 1;
+        const unsigned nsolve = solves(d);
         unsigned H[J2P_MAX_CHANNELS] = {0, 0, 0}, Wc[J2P_MAX_CHANNELS] = {0, 0, 0}, align = J2P_TILE_ROWS, hmin = ~0u;
         for(unsigned c = 0; c < d.nchannel; c++) {
                 const j2p_plane &p = d.planes[c];
                 if(p.h_samp == 0 || p.h == 0 || p.w_samp == 0 || p.w == 0) { return j2p_fail(J2P_EINVAL, "job: channel %u: empty plane", c); }
                 align = align / gcd_u(align, 8 * p.h_samp) * (8 * p.h_samp);
-                const unsigned k = d.separate ? c : 0;
+                const unsigned k = where(d, c).solve;
                 if(p.h * p.h_samp > H[k]) { H[k] = p.h * p.h_samp; }
                 if(p.w * p.w_samp > Wc[k]) { Wc[k] = p.w * p.w_samp; }
         }
@@ -157,179 +254,34 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                         start += units / nband + (b < units % nband ? 1 : 0);
                 }
         }
-        j2p_tiled *t[J2P_MAX_CHANNELS] = {nullptr, nullptr, nullptr};
-        unsigned its[J2P_MAX_CHANNELS] = {0, 0, 0}, done[J2P_MAX_CHANNELS] = {0, 0, 0};
-        int rc = J2P_OK;
-        const bool chunked = d.on_rows || d.on_progress;
+        Engines eng;
         for(unsigned k = 0; k < nsolve; k++) {
                 cuts[nband] = H[k];
-                its[k] = d.iterations[k];
-                if(d.separate) {
-                        rc = j2p_tiled_create(&t[k], nband, devices.data(), cuts, 1, &d.planes[k], d.weight[k], &d.pweight[k], its[k]);
-                } else {
-                        rc = j2p_tiled_create(&t[k], nband, devices.data(), cuts, d.nchannel, d.planes, d.weight[0], d.pweight, its[k]);
-                }
+                const int rc = j2p_tiled_create(&eng.e[k].t, nband, devices.data(), cuts, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k],
+                                                &d.pweight[k], d.iterations[k]);
                 if((rc == J2P_EDEVICE || rc == J2P_ENOMEM) && !j2p_tiled_exchange_forced()) {
                         // these GPUs cannot be tiled over (no peer access and no RCCL, no exchange that verifies on them, or
                         // no room for the band arenas): the image is solved on one of them, as it would have been without
                         // `tile`.  Nothing has run yet.  (An exchange NAMED through J2P_TILED_EXCHANGE / J2P_TILED_WAIT that
                         // cannot be had is an error: the caller asked for that one.)
                         fprintf(stderr, "jpeg2png_amd: not row-tiling this image over %u GPUs (%s); solving it on one\n", nband, j2p_last_error());
-                        rc = J2P_OK;
-                        goto out;
+                        return J2P_OK;
                 }
-                if(rc != J2P_OK) { goto out; }
+                if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        if(!chunked) {
-                for(unsigned k = 0; k < nsolve; k++) { JOB_TRY(j2p_tiled_run(t[k], its[k], nullptr)); }
-        } else {
-                j2p_log_row rows[kChunkMax];
-                const auto t_loop = std::chrono::steady_clock::now();
-                for(;;) {
-                        bool any = false;
-                        for(unsigned k = 0; k < nsolve; k++) {
-                                const unsigned left = its[k] - done[k];
-                                const unsigned step = next_chunk(done[k], left, t_loop);
-                                if(!step) { continue; }
-                                any = true;
-                                JOB_TRY(j2p_tiled_run(t[k], step, d.on_rows ? rows : nullptr));
-                                if(d.on_rows) { d.on_rows(d.user, d.separate ? k : 3u, done[k], step, rows); }
-                                else { JOB_TRY(j2p_tiled_sync(t[k])); }
-                                if(d.on_progress) { d.on_progress(d.user, step); }
-                                done[k] += step;
-                        }
-                        if(!any) { break; }
-                }
-        }
-        if(d.out_bits) {
-                const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
-                for(unsigned b = 0; b < nband; b++) {
-                        const unsigned y0 = cuts[b];
-                        unsigned y1 = b + 1 < nband ? cuts[b + 1] : d.out_h;
-                        if(y1 > d.out_h) { y1 = d.out_h; }
-                        if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
-                        j2p_plane_ref ref[3];
-                        for(unsigned c = 0; c < d.nchannel; c++) {
-                                j2p_solver *bs = nullptr;
-                                JOB_TRY(j2p_tiled_band(d.separate ? t[c] : t[0], b, nullptr, nullptr, nullptr, &bs));
-                                ref[c].solver = bs;
-                                ref[c].channel = d.separate ? 0 : c;
-                        }
-                        if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes)); }
-                        else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, d.out_rgb + (size_t)y0 * row_bytes)); }
-                }
-        } else {
-                if(d.out_coef[0]) {
-                        // every band quantises its own block rows on its own GPU (cuts are multiples of 16 rows: of a block row of
-                        // either sampling); the last band also takes the block row that overhangs the canvas
-                        for(unsigned c = 0; c < d.nchannel; c++) {
-                                const unsigned k = d.separate ? c : 0;
-                                const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
-                                const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
-                                if(sx * sy == 1 ? d.out_blocks_h * 8ull > H[k] : 8ull * sy * (bh - 1) >= H[k]) {
-                                        rc = j2p_fail(J2P_EINVAL, "job: %u block rows are not inside channel %u's canvas of %u rows", d.out_blocks_h, c, H[k]);
-                                        goto out;
-                                }
-                                for(unsigned b = 0; b < nband; b++) {
-                                        const unsigned r0 = cuts[b] / (8 * sy);
-                                        unsigned r1 = b + 1 < nband ? cuts[b + 1] / (8 * sy) : (H[k] + 8 * sy - 1) / (8 * sy);
-                                        if(r1 > bh) { r1 = bh; }
-                                        if(r0 >= r1) { continue; }               // band below the image (canvas padding only)
-                                        j2p_plane_ref ref = {nullptr, d.separate ? 0 : c};
-                                        JOB_TRY(j2p_tiled_band(t[k], b, nullptr, nullptr, nullptr, &ref.solver));
-                                        JOB_TRY(j2p_planes_rows_to_coefficients_sub(&ref, sx, sy, bw, r0, r1, d.out_quant[c],
-                                                                                    d.out_coef[c] + (size_t)r0 * bw * 64));
-                                }
-                        }
-                }
-                for(unsigned c = 0; c < d.nchannel; c++) {
-                        if(!d.out_planes[c]) { continue; }
-                        JOB_TRY(j2p_tiled_download(d.separate ? t[c] : t[0], d.separate ? 0 : c, d.out_planes[c]));
-                }
-        }
-out:
-        for(unsigned k = 0; k < J2P_MAX_CHANNELS; k++) {
-                if(t[k]) { j2p_tiled_destroy(t[k]); }
-        }
-        return rc;
+        return solve_and_deliver(d, eng.e, false);
 }
 
 int run_job(const j2p_job &d, int device)
 {
-        j2p_solver *s[J2P_MAX_CHANNELS] = {nullptr, nullptr, nullptr};
-        unsigned nsolver = 0;
-        unsigned its[J2P_MAX_CHANNELS] = {0, 0, 0}, done[J2P_MAX_CHANNELS] = {0, 0, 0};
-        int rc = J2P_OK;
         const j2p_band whole = {0, 0};
-        const bool chunked = d.on_rows || d.on_progress;
-        if(d.separate) {
-                // jpeg2png.c:147-152: one compute(1, ...) per component, each with its own weight and iteration count
-                nsolver = d.nchannel;
-                for(unsigned c = 0; c < nsolver; c++) {
-                        its[c] = d.iterations[c];
-                        JOB_TRY(j2p_solver_create(&s[c], device, nullptr, 1, &d.planes[c], d.weight[c], &d.pweight[c], its[c], whole, 0));
-                }
-        } else {
-                // jpeg2png.c:144: compute(3, ...) with the first weight and iteration count
-                nsolver = 1;
-                its[0] = d.iterations[0];
-                JOB_TRY(j2p_solver_create(&s[0], device, nullptr, d.nchannel, d.planes, d.weight[0], d.pweight, its[0], whole, 0));
+        Engines eng;
+        for(unsigned k = 0; k < solves(d); k++) {
+                JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k], &d.pweight[k],
+                                          d.iterations[k], whole, 0));
         }
-        if(!chunked) {
-                for(unsigned c = 0; c < nsolver; c++) { JOB_TRY(j2p_solver_run(s[c], its[c], nullptr)); }
-        } else {
-                // compute.c:427-453 in chunks so that the caller's bar and CSV keep moving; without log rows the
-                // chunks of the (up to three) solvers are issued back to back and overlap on the GPU
-                j2p_log_row rows[kChunkMax];
-                const auto t_loop = std::chrono::steady_clock::now();
-                for(;;) {
-                        unsigned step[J2P_MAX_CHANNELS] = {0, 0, 0};
-                        bool any = false;
-                        for(unsigned c = 0; c < nsolver; c++) {
-                                const unsigned left = its[c] - done[c];
-                                step[c] = next_chunk(done[c], left, t_loop);
-                                if(!step[c]) { continue; }
-                                any = true;
-                                JOB_TRY(j2p_solver_run(s[c], step[c], d.on_rows ? rows : nullptr));
-                                if(d.on_rows) { d.on_rows(d.user, d.separate ? c : 3u, done[c], step[c], rows); }   // channel 3 = joint, jpeg2png.c:143
-                        }
-                        if(!any) { break; }
-                        for(unsigned c = 0; c < nsolver; c++) {
-                                if(!step[c]) { continue; }
-                                if(!d.on_rows) { JOB_TRY(j2p_solver_sync(s[c])); }
-                                if(d.on_progress) { d.on_progress(d.user, step[c]); }
-                                done[c] += step[c];
-                        }
-                }
-        }
-        if(d.out_bits) {
-                j2p_plane_ref ref[3];
-                for(unsigned c = 0; c < d.nchannel; c++) {
-                        ref[c].solver = d.separate ? s[c] : s[0];
-                        ref[c].channel = d.separate ? 0 : c;
-                }
-                if(d.nchannel == 1) { JOB_TRY(j2p_planes_to_grey(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }   // greyscale: one sample per pixel
-                else { JOB_TRY(j2p_planes_to_rgb(ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)); }
-        } else {
-                if(d.out_coef[0]) {
-                        for(unsigned c = 0; c < d.nchannel; c++) {
-                                const j2p_plane_ref ref = {d.separate ? s[c] : s[0], d.separate ? 0 : c};
-                                const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
-                                JOB_TRY(j2p_planes_to_coefficients_sub(&ref, sx, sy, (d.out_blocks_w + sx - 1) / sx, (d.out_blocks_h + sy - 1) / sy,
-                                                                       d.out_quant[c], d.out_coef[c]));
-                        }
-                }
-                for(unsigned c = 0; c < d.nchannel; c++) {
-                        if(!d.out_planes[c]) { continue; }
-                        JOB_TRY(j2p_solver_download(d.separate ? s[c] : s[0], d.separate ? 0 : c, d.out_planes[c]));
-                }
-        }
-out:
-        for(unsigned c = 0; c < J2P_MAX_CHANNELS; c++) {
-                if(s[c]) { j2p_solver_destroy(s[c]); }
-        }
-        return rc;
+        return solve_and_deliver(d, eng.e, true);
 }
 
 void worker_main(j2p_batch *b, int device)

@@ -3,6 +3,41 @@
 #include <stdlib.h>
 #include "jpeg2png_amd.h"
 
+// ---- the part compute_host.c (C11) shares with the HIP translation units ----
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// sets the calling thread's j2p_last_error() text (j2p_solver.hip)
+void j2p_set_last_error(const char *msg);
+// true when J2P_TILED_EXCHANGE / J2P_TILED_WAIT name an exchange: one that cannot be had is then an error, not a reason to
+// solve on one GPU (j2p_tiled.hip)
+int j2p_tiled_exchange_forced(void);
+
+// Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
+// iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
+// the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the
+// iterations done so far (every chunk ~1/6 of the time elapsed: the bar of `-i 50` moves ~24 times, 4096^2 `-i 500` syncs
+// ~36 times = under 1 % of its 60 ms), never more than ~J2P_CHUNK_MS worth or J2P_CHUNK_MAX (the callers' row buffers),
+// never more than are left.  elapsed_ms: since the loop began, for the `done` iterations so far.
+#define J2P_CHUNK_MAX 256u
+#define J2P_CHUNK_MS 50.0
+static inline unsigned j2p_next_chunk(unsigned done, unsigned left, double elapsed_ms)
+{
+        unsigned chunk = done / 6;
+        if(done) {
+                const double per_it = elapsed_ms / (double)done;
+                const double most = per_it > 0. ? J2P_CHUNK_MS / per_it : (double)J2P_CHUNK_MAX;
+                if((double)chunk > most) { chunk = (unsigned)most; }
+        }
+        if(chunk > J2P_CHUNK_MAX) { chunk = J2P_CHUNK_MAX; }
+        if(chunk < 1) { chunk = 1; }
+        return left < chunk ? left : chunk;
+}
+
+#ifdef __cplusplus
+}  // extern "C"
+
 // Environment knobs of the EXPERIMENTS build (-DJ2P_EXPERIMENTS: jpeg2png_amd/libjpeg2png_amd_exp.so, built by
 // buildlib.build_experiments() for the schedule-equivalence tests and the timing tools): the switches that move choices
 // AMONG the release kernels (rows per strip, item shares, launch direction, where the norm is finished, ...) and the
@@ -34,3 +69,4 @@ void j2p_rows_from_sums_carry(unsigned nch, float weight, const float *pweight, 
 bool j2p_injected_failure();
 // ... (negative argument) true when the LAST band of this threaded run has to fail halfway through its iterations
 bool j2p_injected_band_failure();
+#endif  // __cplusplus

@@ -2722,7 +2722,7 @@ __global__ __launch_bounds__(256) void k_dct_blocks(float *blocks, size_t nblock
 // jpeg2png.c:156-159, cropped to the image size.  The reference evaluates the
 // colour matrix in double, narrows to float for the clamp, scales by
 // (1 << bits) / 256 in float and truncates to unsigned; the same here.
-// out: 3 bytes per pixel (bits == 8) or 6 bytes, big-endian samples (bits == 16).
+// out: one byte per sample (bits == 8) or two, big-endian (bits == 16).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ unsigned to_sample(double v, float bitfactor)
 {
@@ -2731,50 +2731,50 @@ __device__ __forceinline__ unsigned to_sample(double v, float bitfactor)
         return (unsigned)(x * bitfactor);
 }
 
-__global__ __launch_bounds__(256) void k_to_rgb(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
-                                                unsigned crs, unsigned w, unsigned h, unsigned bits, uint8_t *out)
+// the sample(s) of one pixel as big-endian bytes: one byte each (bits == 8) or two (bits == 16)
+template <int N>
+__device__ __forceinline__ void store_samples(uint8_t *out, size_t i, const unsigned (&v)[N], unsigned bits)
 {
-        const size_t n = (size_t)w * h;
-        const float bitfactor = (float)((double)(1 << bits) / 256.);
-        for(size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-                const unsigned x = (unsigned)(i % w), y = (unsigned)(i / w);
-                const float yi = (float)((double)yp[(size_t)y * ys + x] + 128.);   // jpeg2png.c:158
-                const float cbi = cbp[(size_t)y * cbs + x], cri = crp[(size_t)y * crs + x];
-                const unsigned r = to_sample((double)yi + 1.402 * (double)cri, bitfactor);
-                const unsigned g = to_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri, bitfactor);
-                const unsigned b = to_sample((double)yi + 1.772 * (double)cbi, bitfactor);
-                if(bits == 8) {
-                        uint8_t *o = out + i * 3;
-                        o[0] = (uint8_t)(r & 0xff);
-                        o[1] = (uint8_t)(g & 0xff);
-                        o[2] = (uint8_t)(b & 0xff);
-                } else {
-                        uint8_t *o = out + i * 6;
-                        o[0] = (uint8_t)((r >> 8) & 0xff); o[1] = (uint8_t)(r & 0xff);
-                        o[2] = (uint8_t)((g >> 8) & 0xff); o[3] = (uint8_t)(g & 0xff);
-                        o[4] = (uint8_t)((b >> 8) & 0xff); o[5] = (uint8_t)(b & 0xff);
-                }
+        if(bits == 8) {
+                uint8_t *o = out + i * N;
+#pragma unroll
+                for(int k = 0; k < N; k++) { o[k] = (uint8_t)(v[k] & 0xff); }
+        } else {
+                uint8_t *o = out + i * (2 * N);
+#pragma unroll
+                for(int k = 0; k < N; k++) { o[2 * k] = (uint8_t)((v[k] >> 8) & 0xff); o[2 * k + 1] = (uint8_t)(v[k] & 0xff); }
         }
 }
 
-// Greyscale: one plane through the same writer with Cb = Cr = 0, where R = G = B = to_sample(yi) exactly (yi + 0.0 and
-// yi - 0.0 - 0.0 in double are yi).  out: 1 byte per pixel (bits == 8) or 2 bytes, a big-endian sample (bits == 16).
-__global__ __launch_bounds__(256) void k_to_grey(const float *yp, unsigned ys, unsigned w, unsigned h, unsigned bits, uint8_t *out)
+// NPLANE 3: RGB.  NPLANE 1: greyscale — the same writer with Cb = Cr = 0, where R = G = B = to_sample(yi) exactly
+// (yi + 0.0 and yi - 0.0 - 0.0 in double are yi), so the colour matrix is not evaluated and cbp / crp are not read.
+// out: NPLANE samples per pixel.
+template <int NPLANE>
+__global__ __launch_bounds__(256) void k_to_samples(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
+                                                    unsigned crs, unsigned w, unsigned h, unsigned bits, uint8_t *out)
 {
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
         const size_t n = (size_t)w * h;
         const float bitfactor = (float)((double)(1 << bits) / 256.);
         for(size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
                 const unsigned x = (unsigned)(i % w), y = (unsigned)(i / w);
                 const float yi = (float)((double)yp[(size_t)y * ys + x] + 128.);   // jpeg2png.c:158
-                const unsigned v = to_sample((double)yi, bitfactor);
-                if(bits == 8) {
-                        out[i] = (uint8_t)(v & 0xff);
+                unsigned v[NPLANE];
+                if constexpr(NPLANE == 3) {
+                        const float cbi = cbp[(size_t)y * cbs + x], cri = crp[(size_t)y * crs + x];
+                        v[0] = to_sample((double)yi + 1.402 * (double)cri, bitfactor);
+                        v[1] = to_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri, bitfactor);
+                        v[2] = to_sample((double)yi + 1.772 * (double)cbi, bitfactor);
                 } else {
-                        uint8_t *o = out + i * 2;
-                        o[0] = (uint8_t)((v >> 8) & 0xff); o[1] = (uint8_t)(v & 0xff);
+                        v[0] = to_sample((double)yi, bitfactor);
                 }
+                store_samples(out, i, v, bits);
         }
 }
+// Instantiated explicitly: an implicit instantiation is emitted at the end of the code object, where the same instructions
+// measured 2 us (5 %) slower per 4096x3072 image than k_to_rgb did from here (profiles/README.md: output_stage_refactor)
+template __global__ void k_to_samples<3>(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, unsigned, uint8_t *);
+template __global__ void k_to_samples<1>(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, unsigned, uint8_t *);
 
 // ---------------------------------------------------------------------------
 // JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,
@@ -2782,17 +2782,15 @@ __global__ __launch_bounds__(256) void k_to_grey(const float *yp, unsigned ys, u
 // -fhip-fp32-correctly-rounded-divide-sqrt, never a reciprocal multiply), rounded to nearest even, clamped to
 // [-1023, 1023] (what libjpeg's Huffman coder takes: AC magnitudes of at most 10 bits, DC differences of at most 11).
 // No +128: JPEG's level shift and the luma fix-up of jpeg2png.c:156-159 cancel.
-// plane: raster floats, first row = row 0 of block row r0; blocks [r0, r1) x [0, blocks_w).
-// out: block-major int16 [(r1 - r0) * blocks_w][64], natural order — the JBLOCK rows of libjpeg.
+// out: block-major int16 [blocks][64], natural order — the JBLOCK rows of libjpeg.
 // Mapping of k_dct_blocks: one wavefront = 8 horizontally adjacent blocks, lane >> 3 the block, lane & 7 the row; a
-// lane loads its row of 8 floats as two float4 (8 lanes: 256 contiguous bytes of one plane row) and stores its 8
-// coefficients as one 16-byte vector (the wavefront: 1 KB contiguous).
+// lane stores its 8 coefficients as one 16-byte vector (the wavefront: 1 KB contiguous).
 // ---------------------------------------------------------------------------
 struct QuantSteps {
         float q[64];        // natural order
 };
 
-// the tail both forms share: a lane holds row `lane & 7` of block `lane >> 3` of its wavefront's 8 blocks in v[];
+// the tail: a lane holds row `lane & 7` of block `lane >> 3` of its wavefront's 8 blocks in v[];
 // dct8x8s, quotient, rounding, clamp, and the row's 8 coefficients as one 16-byte store into `block` (ok lanes only)
 __device__ __forceinline__ void quantise_store(float (&v)[8], float *scratch, const float *qs, int lane, bool ok, int16_t *block)
 {
@@ -2816,48 +2814,25 @@ __device__ __forceinline__ void quantise_store(float (&v)[8], float *scratch, co
         if(ok) { *reinterpret_cast<uint4 *>(block + rr * 8) = make_uint4(packed[0], packed[1], packed[2], packed[3]); }
 }
 
-__global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, unsigned stride, unsigned blocks_w, unsigned r0, unsigned r1,
-                                                         QuantSteps steps, int16_t *out)
-{
-        __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
-        __shared__ float qs[64];
-        if(threadIdx.x < 64) { qs[threadIdx.x] = steps.q[threadIdx.x]; }
-        __syncthreads();
-        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-        const unsigned groups_x = (blocks_w + 7) / 8;
-        const unsigned grp = blockIdx.x * 4 + wave;
-        if(grp >= groups_x * (r1 - r0)) { return; }                     // whole wavefronts only: no barrier follows
-        const unsigned by = grp / groups_x, bx = (grp % groups_x) * 8 + (unsigned)(lane >> 3);
-        const int rr = lane & 7;
-        const bool ok = bx < blocks_w;
-        float v[8];
-        if(ok) {
-                const float4 *src = reinterpret_cast<const float4 *>(plane + (size_t)(by * 8 + (unsigned)rr) * stride + bx * 8);
-                const float4 a = src[0], b = src[1];
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-                v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
-#pragma unroll
-                for(int u = 0; u < 8; u++) { v[u] = 0.f; }
-        }
-        quantise_store(v, tp + wave * kTpWave, qs, lane, ok, out + ((size_t)by * blocks_w + bx) * 64);
-}
-
 // ---------------------------------------------------------------------------
-// The subsampling form (4:2:2, 4:2:0, 4:4:0 output): output sample (X, Y) of the block grid is the mean the projection
-// constrains (compute.c:351-359) — a float accumulator that starts at 0.f takes the SY * SX canvas values at rows
-// Y * SY + j, columns X * SX + i in raster order (j outer, i inner), one addition each, and is divided by
-// (float)(SX * SY) — and the 8x8 blocks of those samples go through the same transform, quotient, rounding and clamp.
+// One kernel for every output sampling (4:4:4, 4:2:2, 4:2:0, 4:4:0): output sample (X, Y) of the block grid is the mean
+// the projection constrains (compute.c:351-359) — a float accumulator that starts at 0.f takes the SY * SX canvas values
+// at rows Y * SY + j, columns X * SX + i in raster order (j outer, i inner), one addition each, and is divided by
+// (float)(SX * SY) — and the 8x8 blocks of those samples go through the transform, quotient, rounding and clamp above.
+// <1, 1> gives the coefficients of the plane itself: (0.f + x) / 1.f differs from x only for x = -0.f, which becomes
+// +0.f; another sign on a zero input can only change the sign of a zero somewhere in the two fdct8 passes, and every
+// such zero ends as the integer 0 after rintf and the conversion to int.
 // plane: first row = the first canvas row of the block_rows output block rows; stride x rows: what the canvas holds from
-// there on.  A row index beyond the canvas's last row reads the last row, a column beyond the last column the last
-// column: only the last block row / column of a grid that overhangs the canvas (every block STARTS inside it, which the
-// host checks).  Same mapping: a lane loads SY rows of 8 * SX consecutive floats as float4 (a block starts at a
-// multiple of 8 * SX floats and the stride is a multiple of 8: aligned), 8 lanes 256 * SX contiguous bytes of a canvas
+// there on.  out: block-major int16 [block_rows * blocks_w][64].  A row index beyond the canvas's last row reads the
+// last row, a column beyond the last column the last column: only the last block row / column of a grid that overhangs
+// the canvas (every block STARTS inside it, which the host checks; never for <1, 1>, where canvas, band cuts and
+// blocks_w * 8 are all multiples of 8).  A lane loads SY rows of 8 * SX consecutive floats as float4 (a block starts at
+// a multiple of 8 * SX floats and the stride is a multiple of 8: aligned), 8 lanes 256 * SX contiguous bytes of a canvas
 // row; only lanes whose footprint crosses the canvas's edge take the clamped scalar loads.
 // ---------------------------------------------------------------------------
 template <int SX, int SY>
-__global__ __launch_bounds__(256) void k_quantise_blocks_sub(const float *plane, unsigned stride, unsigned rows, unsigned blocks_w,
-                                                             unsigned block_rows, QuantSteps steps, int16_t *out)
+__global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, unsigned stride, unsigned rows, unsigned blocks_w,
+                                                         unsigned block_rows, QuantSteps steps, int16_t *out)
 {
         static_assert((SX == 1 || SX == 2) && (SY == 1 || SY == 2), "sampling factors 1 and 2");
         __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
@@ -2875,7 +2850,8 @@ __global__ __launch_bounds__(256) void k_quantise_blocks_sub(const float *plane,
         float v[8];
 #pragma unroll
         for(int u = 0; u < 8; u++) { v[u] = 0.f; }
-        if(ok && x0 + 8 * SX <= stride && y0 + SY <= rows) {
+        const bool inside = SX * SY == 1 || (x0 + 8 * SX <= stride && y0 + SY <= rows);         // (<1, 1>: nothing can overhang)
+        if(ok && inside) {
 #pragma unroll
                 for(int j = 0; j < SY; j++) {
                         const float4 *src = reinterpret_cast<const float4 *>(plane + (size_t)(y0 + j) * stride + x0);
@@ -2911,6 +2887,11 @@ __global__ __launch_bounds__(256) void k_quantise_blocks_sub(const float *plane,
         for(int u = 0; u < 8; u++) { v[u] = v[u] / (float)(SX * SY); }
         quantise_store(v, tp + wave * kTpWave, qs, lane, ok, out + ((size_t)by * blocks_w + bx) * 64);
 }
+// (explicit instantiations, as for k_to_samples)
+template __global__ void k_quantise_blocks<1, 1>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
+template __global__ void k_quantise_blocks<2, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
+template __global__ void k_quantise_blocks<2, 1>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
+template __global__ void k_quantise_blocks<1, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
 
 // ---------------------------------------------------------------------------
 // Self-test of the fast division / square root against the compiler's IEEE forms

@@ -2023,14 +2023,22 @@ int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
         return rc;
 }
 
-// rows [y0, y1) of the image from nplane (solver, channel) pairs on one device that all hold those canvas rows:
-// three -> RGB (k_to_rgb), one -> greyscale (k_to_grey)
-static int convert_rows(const j2p_plane_ref *planes, int nplane, unsigned w, unsigned y0, unsigned y1, unsigned bits,
+// rows [y0, y1) of the image from nplane (solver, channel) pairs on one device that all hold those canvas rows, through
+// k_to_samples: three -> RGB, one -> greyscale.  `whole`: called as a whole-canvas form, which band solvers refuse.
+static int convert_rows(const j2p_plane_ref *planes, int nplane, bool whole, unsigned w, unsigned y0, unsigned y1, unsigned bits,
                         uint8_t *out_host)
 {
         const char *what = nplane == 3 ? "to_rgb" : "to_grey";
-        const float *ptr[3];
-        unsigned stride[3];
+        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
+        if(w == 0 || y0 >= y1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
+        for(int i = 0; whole && i < nplane; i++) {
+                if(planes[i].solver && !planes[i].solver->whole) {
+                        return fail(J2P_ESTATE, "%s needs whole-canvas solvers (bands: j2p_planes_rows_%s)", what, what);
+                }
+        }
+        const float *ptr[3] = {nullptr, nullptr, nullptr};
+        unsigned stride[3] = {0, 0, 0};
         for(int i = 0; i < nplane; i++) {
                 j2p_solver *s = planes[i].solver;
                 if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %d: bad solver/channel", i); }
@@ -2053,12 +2061,8 @@ static int convert_rows(const j2p_plane_ref *planes, int nplane, unsigned w, uns
         void *dout = nullptr;
         size_t dout_bytes = 0;
         HIP_TRY(pool_take(s0->device, bytes, &dout, &dout_bytes));       // pooled like the solvers' arenas: no hipFree per image
-        if(nplane == 3) {
-                hipLaunchKernelGGL(k_to_rgb, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2],
-                                   w, h, bits, static_cast<uint8_t *>(dout));
-        } else {
-                hipLaunchKernelGGL(k_to_grey, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0], w, h, bits, static_cast<uint8_t *>(dout));
-        }
+        hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0],
+                           ptr[1], stride[1], ptr[2], stride[2], w, h, bits, static_cast<uint8_t *>(dout));
         hipError_t e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s0->stream);
         if(e == hipSuccess) { e = hipStreamSynchronize(s0->stream); }
         pool_give(s0->device, dout, dout_bytes);
@@ -2068,112 +2072,52 @@ static int convert_rows(const j2p_plane_ref *planes, int nplane, unsigned w, uns
 
 int j2p_planes_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
 {
-        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
-        if(w == 0 || h == 0) { return fail(J2P_EINVAL, "empty image"); }
-        for(int i = 0; i < 3; i++) {
-                if(planes[i].solver && !planes[i].solver->whole) { return fail(J2P_ESTATE, "to_rgb needs whole-canvas solvers (bands: j2p_planes_rows_to_rgb)"); }
-        }
-        return convert_rows(planes, 3, w, 0, h, bits, out_host);
+        return convert_rows(planes, 3, true, w, 0, h, bits, out_host);
 }
 
 int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
                            uint8_t *out_host)
 {
-        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
-        if(w == 0 || row_begin >= row_end) { return fail(J2P_EINVAL, "empty row range"); }
-        return convert_rows(planes, 3, w, row_begin, row_end, bits, out_host);
+        return convert_rows(planes, 3, false, w, row_begin, row_end, bits, out_host);
 }
 
 int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
 {
-        if(!plane || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
-        if(w == 0 || h == 0) { return fail(J2P_EINVAL, "empty image"); }
-        if(plane->solver && !plane->solver->whole) { return fail(J2P_ESTATE, "to_grey needs a whole-canvas solver (bands: j2p_planes_rows_to_grey)"); }
-        return convert_rows(plane, 1, w, 0, h, bits, out_host);
+        return convert_rows(plane, 1, true, w, 0, h, bits, out_host);
 }
 
 int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
                             uint8_t *out_host)
 {
-        if(!plane || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
-        if(w == 0 || row_begin >= row_end) { return fail(J2P_EINVAL, "empty row range"); }
-        return convert_rows(plane, 1, w, row_begin, row_end, bits, out_host);
+        return convert_rows(plane, 1, false, w, row_begin, row_end, bits, out_host);
 }
 
-// block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients (k_quantise_blocks)
-static int quantise_rows(const j2p_plane_ref *plane, unsigned blocks_w, unsigned r0, unsigned r1, const uint16_t quant_table[64],
-                         int16_t *out_host)
+// block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
+// 1/sub_w x 1/sub_h of its resolution (k_quantise_blocks<sub_w, sub_h>): output block row r covers canvas rows
+// [8 * sub_h * r, 8 * sub_h * (r + 1)).  `whole`: called as a whole-canvas form, which band solvers refuse.
+static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
+                         unsigned r1, const uint16_t quant_table[64], int16_t *out_host)
 {
+        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || r0 >= r1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
         j2p_solver *s = plane->solver;
-        if(!s || plane->channel >= s->nch) { return fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
-        QuantSteps steps;
-        for(int j = 0; j < 64; j++) {
-                if(quant_table[j] == 0) { return fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
-                steps.q[j] = (float)quant_table[j];
+        if(whole && s && !s->whole) {
+                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: the j2p_planes_rows_to_coefficients forms)");
         }
-        if((unsigned long long)blocks_w * 8 > s->W || r0 * 8ull < s->row0 || r1 * 8ull > (unsigned long long)s->row0 + s->rows) {
-                return fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks are not inside the solver's rows [%u,%u) x %u columns",
-                            r0, r1, blocks_w, s->row0, s->row0 + s->rows, s->W);
-        }
-        if(s->grad_done) { return fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
-        const float *src = s->ch[plane->channel].xbuf[s->cur] + (size_t)(kHalo + (r0 * 8 - s->row0)) * s->W;
-        DeviceGuard guard(s->device);
-        const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
-        void *dout = nullptr;
-        size_t dout_bytes = 0;
-        HIP_TRY(pool_take(s->device, bytes, &dout, &dout_bytes));
-        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
-        hipLaunchKernelGGL(k_quantise_blocks, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s->stream, src, s->W, blocks_w, r0, r1, steps,
-                           static_cast<int16_t *>(dout));
-        hipError_t e = hipGetLastError();
-        if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s->stream); }
-        if(e == hipSuccess) { e = hipStreamSynchronize(s->stream); }
-        pool_give(s->device, dout, dout_bytes);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients: %s", hipGetErrorString(e)); }
-        return J2P_OK;
-}
-
-int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h, const uint16_t quant_table[64],
-                               int16_t *out_host)
-{
-        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(blocks_w == 0 || blocks_h == 0) { return fail(J2P_EINVAL, "empty image"); }
-        if(plane->solver && !plane->solver->whole) {
-                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: j2p_planes_rows_to_coefficients)");
-        }
-        return quantise_rows(plane, blocks_w, 0, blocks_h, quant_table, out_host);
-}
-
-int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned block_row_begin, unsigned block_row_end,
-                                    const uint16_t quant_table[64], int16_t *out_host)
-{
-        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(blocks_w == 0 || block_row_begin >= block_row_end) { return fail(J2P_EINVAL, "empty row range"); }
-        return quantise_rows(plane, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
-}
-
-// the subsampling form (k_quantise_blocks_sub): output block row r covers canvas rows [8 * sub_h * r, 8 * sub_h * (r + 1)); every
-// block starts inside the canvas and the solver's rows, and what a block reaches beyond them are the canvas's last rows / columns
-static int quantise_rows_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0, unsigned r1,
-                             const uint16_t quant_table[64], int16_t *out_host)
-{
         if(sub_w < 1 || sub_w > 2 || sub_h < 1 || sub_h > 2) {
                 return fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
         }
-        if(sub_w == 1 && sub_h == 1) { return quantise_rows(plane, blocks_w, r0, r1, quant_table, out_host); }
-        j2p_solver *s = plane->solver;
         if(!s || plane->channel >= s->nch) { return fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
         QuantSteps steps;
         for(int j = 0; j < 64; j++) {
                 if(quant_table[j] == 0) { return fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
                 steps.q[j] = (float)quant_table[j];
         }
+        // One rule for every sampling: every block starts inside the solver's rows and columns, and rows beyond the band are
+        // replicated only where the band ends with the canvas (a band that is not the last ends on a multiple of 16).  For 1x1
+        // that is "the whole grid inside": W, the band's rows and every block's start are multiples of 8, so a block that starts
+        // inside ends inside.
         const unsigned long long row_end = (unsigned long long)s->row0 + s->rows, step_y = 8ull * sub_h;
-        // (rows beyond the solver's own may only be the canvas's: a band that is not the last ends on a multiple of 16)
         if(8ull * sub_w * (blocks_w - 1) >= s->W || step_y * r0 < s->row0 || step_y * (r1 - 1) >= row_end ||
            (step_y * r1 > row_end && row_end != s->H)) {
                 return fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks of %ux%u-pixel samples are not inside the solver's rows "
@@ -2189,37 +2133,40 @@ static int quantise_rows_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigne
         size_t dout_bytes = 0;
         HIP_TRY(pool_take(s->device, bytes, &dout, &dout_bytes));
         const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
-        const dim3 grid((unsigned)((groups + 3) / 4)), block(256);
-        const unsigned rows = (unsigned)(row_end - first);
-        int16_t *o = static_cast<int16_t *>(dout);
-        if(sub_w == 2 && sub_h == 2) { hipLaunchKernelGGL((k_quantise_blocks_sub<2, 2>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
-        else if(sub_w == 2) { hipLaunchKernelGGL((k_quantise_blocks_sub<2, 1>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
-        else { hipLaunchKernelGGL((k_quantise_blocks_sub<1, 2>), grid, block, 0, s->stream, src, s->W, rows, blocks_w, r1 - r0, steps, o); }
+        const auto kernel = sub_w == 2 ? (sub_h == 2 ? k_quantise_blocks<2, 2> : k_quantise_blocks<2, 1>)
+                                       : (sub_h == 2 ? k_quantise_blocks<1, 2> : k_quantise_blocks<1, 1>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s->stream, src, s->W, (unsigned)(row_end - first),
+                           blocks_w, r1 - r0, steps, static_cast<int16_t *>(dout));
         hipError_t e = hipGetLastError();
         if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s->stream); }
         if(e == hipSuccess) { e = hipStreamSynchronize(s->stream); }
         pool_give(s->device, dout, dout_bytes);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients_sub: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients: %s", hipGetErrorString(e)); }
         return J2P_OK;
+}
+
+int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h, const uint16_t quant_table[64],
+                               int16_t *out_host)
+{
+        return quantise_rows(plane, true, 1, 1, blocks_w, 0, blocks_h, quant_table, out_host);
+}
+
+int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned block_row_begin, unsigned block_row_end,
+                                    const uint16_t quant_table[64], int16_t *out_host)
+{
+        return quantise_rows(plane, false, 1, 1, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
 }
 
 int j2p_planes_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned blocks_h,
                                    const uint16_t quant_table[64], int16_t *out_host)
 {
-        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(blocks_w == 0 || blocks_h == 0) { return fail(J2P_EINVAL, "empty image"); }
-        if(plane->solver && !plane->solver->whole) {
-                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: j2p_planes_rows_to_coefficients_sub)");
-        }
-        return quantise_rows_sub(plane, sub_w, sub_h, blocks_w, 0, blocks_h, quant_table, out_host);
+        return quantise_rows(plane, true, sub_w, sub_h, blocks_w, 0, blocks_h, quant_table, out_host);
 }
 
 int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w,
                                         unsigned block_row_begin, unsigned block_row_end, const uint16_t quant_table[64], int16_t *out_host)
 {
-        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(blocks_w == 0 || block_row_begin >= block_row_end) { return fail(J2P_EINVAL, "empty row range"); }
-        return quantise_rows_sub(plane, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+        return quantise_rows(plane, false, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
 }
 
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,

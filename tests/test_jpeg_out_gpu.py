@@ -1,4 +1,4 @@
-"""JPEG output from the solved planes (k_quantise_blocks, j2p_planes_to_coefficients / j2p_planes_rows_to_coefficients,
+"""JPEG output from the solved planes (k_quantise_blocks<1, 1>, j2p_planes_to_coefficients / j2p_planes_rows_to_coefficients,
 Solver.coefficients, Batch.submit(quant_tables=...)): the int16 coefficients are, array for array, the compiled
 reference's dct8x8s (ooura/dct.c:98-130) of every 8x8 block of the downloaded plane, divided by the output table in
 float32, rounded to nearest even and clamped to +-1023 — for one block, for more blocks per row than a wavefront owns,

@@ -1,4 +1,4 @@
-"""Subsampled JPEG output from the solved planes (k_quantise_blocks_sub, j2p_planes_to_coefficients_sub /
+"""Subsampled JPEG output from the solved planes (k_quantise_blocks<SX, SY>, j2p_planes_to_coefficients_sub /
 j2p_planes_rows_to_coefficients_sub, Solver.coefficients(subsampling=), Batch.submit(subsampling=)): the int16
 coefficients are, array for array, the definition computed here in numpy — every output sample the float32 mean of its
 sy x sx canvas values (accumulator from 0, raster order, one addition each, divided by float32(sx * sy); indices beyond

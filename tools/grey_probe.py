@@ -55,7 +55,7 @@ with j.Batch(devices=(0,), slots_per_device=1) as b:
         for kind in jobs:
             emit({"what": "batch", "image": f"{w}x{h} 4:2:0", "job": kind, "iterations": its, "rounds": rounds,
                   "ms_per_image_median": round(statistics.median(samples[kind]), 2),
-                  "ms_per_image_best": round(min(samples[kind]), 2), "output_bytes": jobs[kind][1].nbytes})
+                  "ms_per_image_best": round(min(samples[kind]), 2), "ms_per_image_worst": round(max(samples[kind]), 2), "output_bytes": jobs[kind][1].nbytes})
         rg = statistics.median(samples["grey (-g)"]) / statistics.median(samples["joint RGB"])
         emit({"what": "batch", "image": f"{w}x{h} 4:2:0", "summary": True, "grey_over_joint_rgb": round(rg, 3)})
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Subsampled JPEG output (-j Q -S 420) against 4:4:4 JPEG output and RGB8 on one 4096x3072 4:2:0 image, default 50
 iterations, alternated runs, medians (the sibling of tools/jpeg_probe.py):
-  kernels  k_quantise_blocks_sub<2, 2> per chroma plane next to k_quantise_blocks on the same two planes, from one
+  kernels  k_quantise_blocks<2, 2> per chroma plane next to k_quantise_blocks<1, 1> on the same two planes, from one
            `rocprofv3 --kernel-trace --stats` run of this script's --kernels mode (a child process of its own) in which
            every round holds one 4:4:4 and one 4:2:0 coefficient job: launches in time order are Y, Cb, Cr of the first
            and Y, Cb, Cr of the second;
@@ -87,15 +87,16 @@ if os.path.exists(rocprof):
                 for row in csv.DictReader(f):
                     if "k_quantise_blocks" in row["Kernel_Name"]:
                         start, end = int(row["Start_Timestamp"]), int(row["End_Timestamp"])
-                        launches.append((start, "sub" if "k_quantise_blocks_sub" in row["Kernel_Name"] else "full", (end - start) / 1e3))
+                        full = "k_quantise_blocks<1,1>" in row["Kernel_Name"].replace(" ", "")
+                        launches.append((start, "full" if full else "sub", (end - start) / 1e3))
     launches.sort()
     # every round: full Y, full Cb, full Cr | full Y, sub Cb, sub Cr
     kinds = [k for _, k, _ in launches]
     if len(launches) % 6 or kinds != ["full", "full", "full", "full", "sub", "sub"] * (len(launches) // 6):
         sys.exit(f"unexpected launch order in the kernel trace: {kinds[:12]}")
-    groups = {"k_quantise_blocks, chroma planes of the 4:4:4 job": [d for i, (_, _, d) in enumerate(launches) if i % 6 in (1, 2)],
-              f"k_quantise_blocks_sub<{subs[1][0]}, {subs[1][1]}>, chroma planes of the {sampling} job": [d for _, k, d in launches if k == "sub"],
-              "k_quantise_blocks, luma planes of both jobs": [d for i, (_, _, d) in enumerate(launches) if i % 6 in (0, 3)]}
+    groups = {"k_quantise_blocks<1, 1>, chroma planes of the 4:4:4 job": [d for i, (_, _, d) in enumerate(launches) if i % 6 in (1, 2)],
+              f"k_quantise_blocks<{subs[1][0]}, {subs[1][1]}>, chroma planes of the {sampling} job": [d for _, k, d in launches if k == "sub"],
+              "k_quantise_blocks<1, 1>, luma planes of both jobs": [d for i, (_, _, d) in enumerate(launches) if i % 6 in (0, 3)]}
     for name, d in groups.items():
         emit({"what": "kernel", "kernel": name, "image": f"{W}x{H}", "launches": len(d), "us_median": round(statistics.median(d), 2),
               "us_min": round(min(d), 2), "us_max": round(max(d), 2), "per": "plane"})
@@ -129,7 +130,7 @@ with j.Batch(devices=(0,), slots_per_device=1) as b:
         nbytes = {"RGB8": rgb.nbytes, "coefficients 444": sum(c.nbytes for c in full), f"coefficients {sampling}": sum(c.nbytes for c in sub)}
         for kind in kinds:
             emit({"what": "batch", "image": f"{W}x{H} 4:2:0", "output": kind, "iterations": n_it, "rounds": rounds,
-                  "ms_per_image_median": round(statistics.median(samples[kind]), 2), "ms_per_image_best": round(min(samples[kind]), 2),
+                  "ms_per_image_median": round(statistics.median(samples[kind]), 2), "ms_per_image_best": round(min(samples[kind]), 2), "ms_per_image_worst": round(max(samples[kind]), 2),
                   "download_bytes": nbytes[kind], "download_bytes_per_pixel": round(nbytes[kind] / (W * H), 2)})
 
 # ---- the driver end to end: a process per run, as a user runs it ----
