@@ -109,9 +109,9 @@ void j2p_pool_trim(void);
 
 /* diagnostics: schedule switches that change speed, never results (A/B timing and the parity tests of both
  * schedules).  Only between iterations. */
-#define J2P_OPT_NORM_FOLD     1   /* 1 (default for band solvers and for whole canvases up to 2.5 Mpixel): level 1 of the
-                                     ||g|| reduction runs inside the gradient kernel (its last-arriving wavefronts);
-                                     0: separate reduction kernel — same bits */
+#define J2P_OPT_NORM_FOLD     1   /* 1 (default for band solvers, for whole canvases up to 2.5 Mpixel and for whole canvases from
+                                     32 Mpixel on): level 1 of the ||g|| reduction runs inside the gradient kernel (its
+                                     last-arriving wavefronts); 0: separate reduction kernel — same bits */
 /* (2 is not an option any more: the all-channels-in-one-wavefront gradient kernel it selected is deleted) */
 #define J2P_OPT_NORM_IN_PROJECT 4 /* 1 (needs NORM_FOLD): the gradient kernel leaves per-tile-row sums and every wavefront of
                                      the projection kernel runs the final tree itself: no reduction launch in between */
@@ -149,6 +149,27 @@ int j2p_debug_build(void);
  * rows, tile row, kind (0 whole, 1 half, 2 quarter, 3 double)}; *n_items: how many the launch has; *workgroups: its grid. */
 int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
                          unsigned zone_c, int reverse, unsigned *items, unsigned max_items, unsigned *n_items, unsigned *workgroups);
+/* Test hook (no device needed): the solver's norm plan — who reduces ||g|| between the two phase kernels of ONE iteration
+ * (DESIGN.md section 4 has the table) — for a whole-canvas (whole 1) or band (0) solver with J2P_OPT_NORM_FOLD `fold`,
+ * J2P_OPT_NORM_IN_PROJECT `norm_in_project` (0, 1, 2), bands finishing ||g|| inside k_project (`band_nip`, the default) or
+ * not, `tile_rows` tile rows in the canvas, the phase the reduction would ride on issued in parts (`split`: the gradient
+ * phase of a whole canvas, the projection phase of a band) and the CSV sums wanted (`log`).
+ * *level1, who forms the per-tile-row sums: */
+#define J2P_NORM_L1_NONE 0      /* nobody: k_norm_whole reads the strips' partials itself */
+#define J2P_NORM_L1_TICKETS 1   /* the gradient launch: the last wavefront to arrive at a tile row sums it */
+#define J2P_NORM_L1_ROWSUMS 2   /* a k_rowsums launch behind the gradient phase */
+/* *level2, who runs the tree over them and writes ||g||: */
+#define J2P_NORM_L2_GRADIENT 0       /* the gradient launch: its last wavefront */
+#define J2P_NORM_L2_NORM_WHOLE 1     /* a k_norm_whole launch */
+#define J2P_NORM_L2_NORM_FINISH 2    /* a k_norm_finish launch */
+#define J2P_NORM_L2_PROJECT_WAVES 3  /* every wavefront of k_project (NIP 1) */
+#define J2P_NORM_L2_PROJECT_FIRST 4  /* the first wavefront of every workgroup of k_project (NIP 2) */
+#define J2P_NORM_L2_EXTERNAL 5       /* the caller, between the phases (j2p_solver_norm_from_bands / _norm_external): never
+                                        planned, only what those calls turn a plan into */
+/* *launches: kernel launches of such an iteration, 2 + the reduction launches of the plan (k_rowsums, k_norm_whole,
+ * k_norm_finish). */
+int j2p_debug_norm_plan(int whole, int fold, int norm_in_project, int band_nip, unsigned tile_rows, int split, int log,
+                        int *level1, int *level2, unsigned *launches);
 int j2p_solver_debug_violations(j2p_solver *s, unsigned long long *count, unsigned *site, unsigned long long *offset);
 
 /* Timing tool (builds with -DJ2P_TRACE only, tools/wave_trace.py; J2P_ESTATE otherwise): while on, every wavefront
@@ -160,8 +181,11 @@ int j2p_solver_trace(j2p_solver *s, int on, unsigned long long *host_out, unsign
 int j2p_solver_canvas(const j2p_solver *s, unsigned *W, unsigned *H);
 int j2p_solver_band(const j2p_solver *s, unsigned *row_begin, unsigned *row_end);
 
-/* kernel launches per iteration of an unlogged j2p_solver_run(): 2 = gradient and projection with ||g|| reduced inside
- * them, 3 = with a reduction launch in between */
+/* kernel launches per iteration of an unlogged run of whole phases: 2 = gradient and projection with ||g|| reduced inside
+ * them, + the reduction launches the solver's norm plan issues in between (k_rowsums, k_norm_whole, k_norm_finish; see
+ * j2p_debug_norm_plan).  Read from the plan, so also right where the tile-row limit bites: a whole canvas or a band of a
+ * canvas with more than 1024 tile rows takes k_norm_finish (3; reported as 2 before), and a band with folding off takes
+ * k_rowsums as well (3 or 4; k_rowsums went uncounted before). */
 int j2p_solver_launches_per_iteration(const j2p_solver *s, unsigned *n);
 
 /* back to iteration 0 from the inputs that are already resident in HBM */

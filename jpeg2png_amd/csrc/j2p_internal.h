@@ -35,6 +35,12 @@ static inline unsigned j2p_next_chunk(unsigned done, unsigned left, double elaps
         return left < chunk ? left : chunk;
 }
 
+// The most tile rows whose sums ONE in-kernel tree turns into ||g||: the tree at the end of a folding k_gradient launch and
+// the one k_project's wavefronts run (j2p_kernels.hip.h size their arrays by it), hence also where the solver's norm plan
+// (j2p_solver.hip: norm_plan) and the row tiling's exchange picker (j2p_tiled.hip) fall back to a k_norm_finish launch or
+// to the copy exchange.  Canvas height <= 16384 at 16-row tile rows.
+#define J2P_NORM_TREE_ROWS 1024u
+
 #ifdef __cplusplus
 }  // extern "C"
 

@@ -33,6 +33,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "j2p_internal.h"          // J2P_NORM_TREE_ROWS
+
 namespace j2p {
 
 constexpr int kMaxCh = 3;
@@ -898,7 +900,7 @@ __device__ __forceinline__ void source_prepare_joint(int cidx, int lane, int par
 // evaluates it — so the norm is bit-identical to the stand-alone kernels' and independent of the order in
 // which wavefronts arrive.  Cross-workgroup hand-over: see fold_arrive.
 // ---------------------------------------------------------------------------
-constexpr unsigned kFoldMaxRows = 1024;      // tile rows the in-kernel tree handles (canvas height <= 16384)
+constexpr unsigned kFoldMaxRows = J2P_NORM_TREE_ROWS;      // tile rows the in-kernel tree handles (canvas height <= 16384)
 
 // lanes 8c..8c+7 of the calling wavefront: the eight interleaved running sums of strip_sum for channel c
 __device__ __forceinline__ void fold_tile_row(const GradArgs &a, unsigned tr, size_t nparts, int lane)
@@ -1685,7 +1687,8 @@ __global__ __launch_bounds__(256) void k_norm_whole(const double *part, unsigned
 // s = P/2 ... 1, P = the power of two >= n) — lane l holds elements l, l + 64, l + 128, ...; the levels with s >= 64
 // add registers of one lane, the levels below move partner values between lanes.  Identical additions, hence the
 // identical double, as tree_sum_lds.  n <= 1024.  (Padding P up to 64 only adds exact zeros to sums that are >= 0.)
-constexpr unsigned kWaveTreeMax = 1024;
+constexpr unsigned kWaveTreeMax = J2P_NORM_TREE_ROWS;
+static_assert(kWaveTreeMax >= 128 && (kWaveTreeMax & (kWaveTreeMax - 1)) == 0, "norm_tree_reduce halves kWaveTreeMax / 64 registers per lane down to one");
 // in two steps, so that the caller can put its own loads in flight between them: the row sums are requested first,
 // the planes' rows right behind them, and the tree runs while those are still on their way (one memory round trip
 // in front of the projection's arithmetic instead of two: 512x512 4:2:0 k_project 2.96 -> see profiles/ us to first data)

@@ -75,6 +75,32 @@ struct ChanHost {
         float pweight = 0.f;
 };
 
+// The norm plan: who reduces ||g|| between the two phase kernels of ONE iteration ("the norm between
+// the phases": the table, the measurements).  Level 1 turns the strips' partials into per-tile-row sums (J2P_NORM_L1_*),
+// level 2 runs the fixed tree over those and writes the float norm (J2P_NORM_L2_*).  Every form computes the same bits.
+struct NormPlan {
+        int level1 = J2P_NORM_L1_NONE, level2 = J2P_NORM_L2_NORM_WHOLE;
+        // k_project's NIP template argument (0 = ||g|| is read from memory); launches between the two phase kernels
+        int nip() const { return level2 == J2P_NORM_L2_PROJECT_WAVES ? 1 : (level2 == J2P_NORM_L2_PROJECT_FIRST ? 2 : 0); }
+        unsigned launches() const { return (level1 == J2P_NORM_L1_ROWSUMS) + (level2 == J2P_NORM_L2_NORM_WHOLE || level2 == J2P_NORM_L2_NORM_FINISH); }
+};
+// The one place the choice is made: pure, a few compares.  `nip_form`: whole canvases that fold run level 2 inside k_project
+// (0 no, 1 every wavefront, 2 each workgroup's first); `band_nip`: bands do (NIP 2); `split`: the phase level 2 would ride on
+// comes in parts (the gradient phase of a whole canvas, the projection phase of a band) and cannot carry a reduction over
+// all rows; `log`: the run wants the CSV sums, whose projection kernels have no per-wavefront tree.
+NormPlan norm_plan(bool whole, bool fold, int nip_form, bool band_nip, unsigned tile_rows, bool split, bool log)
+{
+        const bool tree = !split && tile_rows <= J2P_NORM_TREE_ROWS;           // one in-kernel tree can take every row
+        NormPlan p;
+        p.level1 = fold ? J2P_NORM_L1_TICKETS : (whole ? J2P_NORM_L1_NONE : J2P_NORM_L1_ROWSUMS);
+        if(!whole) { p.level2 = tree && band_nip ? J2P_NORM_L2_PROJECT_FIRST : J2P_NORM_L2_NORM_FINISH; }
+        else if(!fold) { p.level2 = J2P_NORM_L2_NORM_WHOLE; }
+        else if(!tree) { p.level2 = J2P_NORM_L2_NORM_FINISH; }
+        else if(nip_form && !log) { p.level2 = nip_form == 2 ? J2P_NORM_L2_PROJECT_FIRST : J2P_NORM_L2_PROJECT_WAVES; }
+        else { p.level2 = J2P_NORM_L2_GRADIENT; }
+        return p;
+}
+
 }  // namespace
 
 struct j2p_solver {
@@ -99,11 +125,11 @@ struct j2p_solver {
         void *arena = nullptr;   // the one device allocation everything below is carved from (pooled, see pool_take)
         size_t arena_bytes = 0;
         // reductions
-        bool fold = false;       // norm reduction folded into k_gradient (J2P_OPT_NORM_FOLD); default: band solvers only
+        bool fold = false;       // level 1 of the norm reduction inside k_gradient (J2P_OPT_NORM_FOLD; default: norm_defaults)
         unsigned zone_d = 0, zone_b = 0, zone_c = 0;   // shares (1/256) of a gradient launch dealt as double / half / quarter tile rows (grad_item)
         bool grad_reverse = false;         // the gradient launch walks the canvas bottom-up (Geo::reverse)
-        bool norm_in_project = false;   // J2P_OPT_NORM_IN_PROJECT (with fold): level 2 of the norm inside k_project
-        int nip_form = 1;               // ... by every wavefront (1: small canvases) or by the workgroup's first (2), see project_strip
+        int nip_form = 0;               // J2P_OPT_NORM_IN_PROJECT (with fold): level 2 inside k_project, by every wavefront (1) or the workgroup's first (2)
+        NormPlan plan;                  // the running iteration's (do_phase_gradient); between iterations: nobody reads it
         int nt = 0;                     // 0..3: streams with the non-temporal hint (nt_policy; J2P_OPT_NT_GRADIENT)
         bool nt_forced = false;         // set through J2P_OPT_NT_GRADIENT: the policy no longer touches it
         bool live_registered = false;   // this solver's bytes are part of the device's live total (nt_policy)
@@ -116,12 +142,10 @@ struct j2p_solver {
         unsigned long long *trace = nullptr;          // J2P_TRACE builds: wave records (tools/wave_trace.py)
         unsigned trace_cap = 0, trace_used = 0;      // records reserved by the launches so far
         bool trace_on = false;
-        bool norm_ready = false; // the gradient launch of this iteration also produced norm[]
-        bool norm_by_project = false;   // ... or left level-1 row sums that k_project reduces itself
         unsigned *tickets = nullptr;     // device: [ntr_local] per-tile-row arrival counters + [1] finished-rows counter
         unsigned rpw = 16;
         bool interior_done = false;
-        bool rowsums_pending = false;
+        bool finish_pending = false;     // split gradient phase: j2p_solver_phase_rowsums has still to run (k_rowsums if planned, the band's log sums)
         unsigned ntx = 0, nseg = 0, ntr_local = 0, ntr_global = 0, first_tr = 0;   // strips per row, row segments
         double *part_g2 = nullptr;       // [c][ntr_local][ntx]
         double *rowsum_odd = nullptr;    // band solvers: second level-1 buffer, used by odd iterations once rowsum_alternate is on
@@ -143,7 +167,6 @@ struct j2p_solver {
         double carried_prob[kMaxCh] = {0., 0., 0.};
         bool carried_valid = true;
         bool log_phases = false;         // the phase calls run the logging kernels and fill log_band
-        bool bandlog_pending = false;    // split gradient phase: band sums still to be launched (phase_rowsums)
         double *log_band = nullptr;      // [2 + kMaxCh]: tv, tv2 of the last gradient phase, prob per channel of the last projection
         // timing
         unsigned timing = 0;     // 0 = off, k = time every k-th iteration
@@ -302,14 +325,22 @@ struct Carver {
 };
 
 constexpr size_t kNtWorkingSet = (size_t)260 << 20;      // see nt_policy in j2p_solver_create
-constexpr size_t kNormInProjectPixels = (size_t)5 << 19; // whole canvases up to this size (2.5 Mpixel) reduce ||g|| without a launch of its own
 constexpr size_t kMixedProjectPixels = (size_t)1 << 20;  // canvases up to this size project all channels in one launch
 
-// whole canvases from this size on (and at most kFoldMaxRows tile rows) reduce ||g|| entirely inside k_gradient: on wide
-// planes the k_norm_whole launch stages 17 K partials through one CU (9 us at W = 16384) — 16384x2048 232.1 -> 229.4 us per
-// iteration, 8192^2 521.6 -> 511.3; at 4096^2 the launch (4.7 us) is the cheaper one, 117.6 vs 119.4
-// (profiles/r04_fold_without_ack_waits.jsonl)
+// The default norm configuration, which norm_plan works from (J2P_OPT_NORM_FOLD / _NORM_IN_PROJECT override it; measured:
+// DESIGN.md section 4).  Bands fold: the in-kernel reduction replaces a launch AND lets the row sums alternate between two
+// buffers.  On whole canvases its serial tail costs what the k_norm_whole launch did (4096^2 140.0 us per iteration either
+// way, 512^2 4:2:0 42.0 vs 40.3 us), so they fold only up to kNormInProjectPixels (2.5 Mpixel: bound by the number of
+// dependent launches, every wavefront of k_project runs the tree, NIP 1) and — where one tree takes the tile rows — from
+// kFoldWholePixels (32 Mpixel) on, where k_norm_whole would stage 17 K partials through one CU (both levels in k_gradient)
+constexpr size_t kNormInProjectPixels = (size_t)5 << 19;
 constexpr size_t kFoldWholePixels = (size_t)1 << 25;
+void norm_defaults(j2p_solver *s)
+{
+        const size_t pixels = (size_t)s->W * s->H;
+        s->nip_form = s->whole && pixels <= kNormInProjectPixels ? 1 : 0;
+        s->fold = !s->whole || s->nip_form || (pixels >= kFoldWholePixels && s->ntr_global <= J2P_NORM_TREE_ROWS);
+}
 // rows per gradient strip: 16; 8, then 4, while the strips make fewer wavefronts than half the chip's 4096 slots (the
 // launch is then one generation whose length is the busiest SIMD's: shorter strips balance it, at 25 / 50 instead of 12.5 %
 // redundant rows).  A limit of 4096 for the first step was measured too (profiles/r03_px_rpw_sweep.jsonl,
@@ -450,6 +481,9 @@ double *rowsums_of(const j2p_solver *s, unsigned iter)
         return (s->rowsum_alternate && (iter & 1)) ? s->rowsum_odd : s->rowsum_local;
 }
 
+NormPlan plan_of(const j2p_solver *s, bool split, bool log) { return norm_plan(s->whole, s->fold, s->nip_form, s->band_nip, s->ntr_global, split, log); }
+bool rowsums_owed(const j2p_solver *s) { return s->finish_pending && s->plan.level1 == J2P_NORM_L1_ROWSUMS; }
+
 // units of a gradient launch over `ntr` tile rows (grad_item): pairs of tile rows x 4 strips (256-thread workgroups), or —
 // joint images, one wavefront per channel — x one strip
 unsigned grad_units(const j2p_solver *s, unsigned ntr)
@@ -548,6 +582,18 @@ static void launch_rowsums(j2p_solver *s)
                            (const double *)s->part_g2, s->rowsum_local, s->ntx, s->ntr_local, s->nch, per_block);
 }
 
+// the end of a gradient phase — of a split one: on the solver's stream, which the caller has made wait for the boundary part
+int do_rowsums(j2p_solver *s)
+{
+        if(!s->grad_done) { return fail(J2P_ESTATE, "rowsums without a finished gradient phase"); }
+        if(!s->finish_pending) { return J2P_OK; }      // (a whole phase has finished itself)
+        if(s->plan.level1 == J2P_NORM_L1_ROWSUMS) { launch_rowsums(s); }
+        if(s->phase_log && s->log_phases) { launch_band_log(s, 0); }
+        s->finish_pending = false;
+        HIP_TRY(hipGetLastError());
+        return J2P_OK;
+}
+
 int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nullptr)
 {
         if(s->grad_done) { return fail(J2P_ESTATE, "phase_gradient called twice without phase_project"); }
@@ -556,6 +602,8 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         if(part != 0 && s->nseg < 3) { return fail(J2P_ESTATE, "band too short to split the gradient phase"); }
         if(!st) { st = s->stream; }
         if(part != 2) {
+                // the iteration's norm plan, decided here once; a band learns only in do_phase_project whether ITS phase is split
+                s->plan = plan_of(s, s->whole && part != 0, log);
                 s->phase_log = log;
                 // FISTA scalars in float, as compute.c:431-432,440
                 const float tnext = (1 + sqrtf(1 + 4 * (s->t * s->t))) / 2;
@@ -583,11 +631,8 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.a_tgv = (float)((double)alpha * 1. / (double)sqrtf((float)s->nch));   // compute.c:154
         a.part_g2 = s->part_g2;
         a.part_tv = s->part_tv;
-        // the norm reduction rides on this launch: level 1 (row sums) always, level 2 (tree -> norm) when the
-        // launch covers the whole canvas
-        const bool nip = s->norm_in_project && s->fold && s->whole && part == 0 && s->ntr_global <= kWaveTreeMax && !log;
-        const bool fold_norm = !nip && s->fold && s->whole && part == 0 && s->ntr_global <= kFoldMaxRows;
-        a.row_ticket = s->fold ? s->tickets : nullptr;
+        // what of the norm reduction rides on this launch (the plan): level 1 by tickets, level 2 behind it
+        a.row_ticket = s->plan.level1 == J2P_NORM_L1_TICKETS ? s->tickets : nullptr;
         a.done_ticket = s->tickets + s->ntr_local;
         a.rowsum = rowsums_of(s, s->iter);
         a.push = nullptr;
@@ -595,7 +640,7 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
                 if(part != 0) { return fail(J2P_ESTATE, "linked bands run whole phases (there is no exchange to hide)"); }
                 a.push = s->push_dev + (s->iter & 1);
         }
-        a.norm_out = fold_norm ? s->norm : nullptr;
+        a.norm_out = s->plan.level2 == J2P_NORM_L2_GRADIENT ? s->norm : nullptr;
         a.nch_total = s->nch;
         a.fold_phase = s->iter & 1;
         a.fold_rows = s->ntr_local;
@@ -621,38 +666,10 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
                 return J2P_OK;
         }
         s->interior_done = false;
-        s->norm_ready = fold_norm;
-        s->norm_by_project = nip;
-        if(part == 0 && !s->whole && !s->fold) {
-                launch_rowsums(s);
-                HIP_TRY(hipGetLastError());
-        }
         s->grad_done = true;
-        s->rowsums_pending = part == 2 && !s->whole && !s->fold;
-        // band sums for the CSV row: behind the last launch of the phase (for a split phase that is
-        // j2p_solver_phase_rowsums(), once the solver's stream has joined the edge part)
-        s->bandlog_pending = false;
-        if(log && s->log_phases) {
-                if(part == 0) { launch_band_log(s, 0); }
-                else { s->bandlog_pending = true; }
-        }
-        return J2P_OK;
-}
-
-// after a split gradient phase: per-tile-row sums on the solver's stream (the caller has made that
-// stream wait for the boundary part)
-int do_rowsums(j2p_solver *s)
-{
-        if(!s->grad_done) { return fail(J2P_ESTATE, "rowsums without a finished gradient phase"); }
-        if(s->bandlog_pending) {
-                launch_band_log(s, 0);
-                s->bandlog_pending = false;
-        }
-        if(!s->rowsums_pending) { return J2P_OK; }     // whole-canvas solver: folded into the norm kernel
-        launch_rowsums(s);
-        HIP_TRY(hipGetLastError());
-        s->rowsums_pending = false;
-        return J2P_OK;
+        // k_rowsums and the band's CSV sums go behind the phase's last launch: now, or in j2p_solver_phase_rowsums()
+        s->finish_pending = true;
+        return part == 0 ? do_rowsums(s) : J2P_OK;
 }
 
 // the instantiations of k_project by what the launch needs: NT = non-temporal level (nt_policy), NIP = who reduces
@@ -712,7 +729,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
 {
         const hipStream_t st = s->stream;
         if(!s->grad_done) { return fail(J2P_ESTATE, "phase_project called before phase_gradient"); }
-        if(s->rowsums_pending) { return fail(J2P_ESTATE, "phase_project before j2p_solver_phase_rowsums"); }
+        if(rowsums_owed(s)) { return fail(J2P_ESTATE, "phase_project before j2p_solver_phase_rowsums"); }
         // the two phases of an iteration must agree on logging: where the norm is reduced depends on it
         if(log != s->phase_log) { return fail(J2P_ESTATE, "phase_project: logging differs from this iteration's gradient phase"); }
         if(part == 2 && !s->proj_boundary_done) { return fail(J2P_ESTATE, "interior part of phase_project before the boundary part"); }
@@ -722,17 +739,16 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         // the global [tile row][channel] sums a band solver finishes ||g|| from: gathered by the caller, or — linked
         // bands — stored there by every band's gradient launch, even and odd iterations in two arrays
         const double *global_rows = s->whole ? rowsums_of(s, s->iter) : ((s->linked && (s->iter & 1)) ? s->rowsum_all_odd : s->rowsum_all);
-        bool nip2 = false;
-        if(part == 2 || s->norm_ready || s->norm_by_project) {
-                // the norm is already there, or every wavefront of k_project reduces the row sums itself
-        } else if(!s->whole && s->band_nip && part == 0 && s->ntr_global <= kWaveTreeMax) {
-                // band solvers: the first wavefront of every workgroup of k_project runs the tree (NIP 2) — no launch
-                nip2 = true;
-        } else if(s->fold) {
-                // level 1 came with the gradient launch (band solvers: the caller has gathered all bands' row sums)
+        // (the one circumstance the gradient phase could not know: a band's projection phase in parts takes the split plan)
+        if(part == 1 && !s->whole && s->plan.level2 == J2P_NORM_L2_PROJECT_FIRST) { s->plan = plan_of(s, true, log); }
+        // the reduction launch in front of k_project, if the plan has one (an interior part finds ||g|| written, as if by the caller)
+        switch(part == 2 ? J2P_NORM_L2_EXTERNAL : s->plan.level2) {
+        case J2P_NORM_L2_NORM_FINISH:
+                // level 1 came with the gradient phase (band solvers: the caller has gathered all bands' row sums)
                 hipLaunchKernelGGL(k_norm_finish, dim3(s->nch), dim3(256), P * sizeof(double), st,
                                    global_rows, s->ntr_global, s->nch, s->norm);
-        } else if(s->whole) {
+                break;
+        case J2P_NORM_L2_NORM_WHOLE: {
                 // stage as many of the partials at once as the CU's LDS holds (P <= 4096)
                 unsigned stage = 0;                                  // narrow canvases: direct form (4.6 vs 5.4 us at 4096^2)
                 if(s->ntx > 48) {
@@ -741,9 +757,9 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
                 }
                 hipLaunchKernelGGL(k_norm_whole, dim3(s->nch), dim3(256), (P + stage) * sizeof(double), st,
                                    (const double *)s->part_g2, s->ntx, s->ntr_local, s->nch, s->norm, stage);
-        } else {
-                hipLaunchKernelGGL(k_norm_finish, dim3(s->nch), dim3(256), P * sizeof(double), st,
-                                   global_rows, s->ntr_global, s->nch, s->norm);
+                break;
+        }
+        default: break;         // the gradient launch or the caller has written ||g||, or k_project runs the tree itself
         }
         ProjArgs a;
         for(unsigned c = 0; c < s->nch; c++) { a.ch[c] = chan_dev(s, c); }
@@ -754,15 +770,15 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         a.norm = s->norm;
         a.part_prob = s->part_prob;
         a.strips_per_chan = s->strips_stride;
-        a.norm_rowsums = nip2 ? global_rows : (s->norm_by_project ? rowsums_of(s, s->iter) : nullptr);
+        const int nip = s->plan.nip();
+        a.norm_rowsums = nip ? global_rows : nullptr;
         a.norm_rows = s->ntr_global;
         a.norm_nch = s->nch;
-        const int nip = nip2 ? 2 : (s->norm_by_project ? s->nip_form : 0);
         for(unsigned c = 0; c < kMaxCh; c++) { a.halo_up[c] = a.halo_down[c] = nullptr; }
         if(s->linked) {
                 // the band's edge rows of x_{k+1} also go into the neighbours' halo rows of the buffer being written
                 // (only the NIP 2 instantiations store them: a linked band always takes those)
-                if(!nip2) { return fail(J2P_ESTATE, "linked bands: ||g|| must be reduced inside k_project (whole phases, at most %u tile rows, J2P_BAND_NIP not 0)", kWaveTreeMax); }
+                if(nip != 2) { return fail(J2P_ESTATE, "linked bands: ||g|| must be reduced inside k_project (whole phases, at most %u tile rows, J2P_BAND_NIP not 0)", J2P_NORM_TREE_ROWS); }
                 for(unsigned c = 0; c < s->nch; c++) {
                         a.halo_up[c] = s->links.up_halo[s->cur ^ 1][c];
                         a.halo_down[c] = s->links.down_halo[s->cur ^ 1][c];
@@ -875,11 +891,9 @@ int launch_init(j2p_solver *s)
         s->cur = 0;
         s->grad_done = false;
         s->interior_done = false;
-        s->rowsums_pending = false;
-        s->norm_ready = false;
-        s->norm_by_project = false;
+        s->finish_pending = false;
+        s->plan = NormPlan();
         s->proj_boundary_done = false;
-        s->bandlog_pending = false;
         for(unsigned c = 0; c < kMaxCh; c++) { s->carried_prob[c] = 0.; }
         s->carried_valid = true;
         return J2P_OK;
@@ -982,20 +996,6 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         s->row0 = row0;
         s->rows = row1 - row0;
         s->whole = whole;
-        // the in-kernel reduction is worth its serial tail only for band solvers, where it replaces a launch AND lets
-        // the row sums alternate between two buffers (measured on whole canvases: 4096^2 140.0 us per iteration either
-        // way, 512^2 4:2:0 42.0 vs 40.3 us — the tail costs what the k_norm_whole launch did)
-        s->fold = !whole;
-        // ... except on whole canvases small enough to be bound by the number of dependent launches: there the
-        // gradient kernel leaves the per-tile-row sums and every wavefront of k_project runs the final tree itself
-        // (512x512 4:2:0: 27.7 -> 27.2 us per iteration, 1024^2 Y: 22.1 -> 21.7, 1080p and 1536^2 Y: equal;
-        // 2048^2: 48.9 -> 50.8, 4096^2: 130 -> 134, hence the limit)
-        if(whole && (size_t)W * H <= kNormInProjectPixels) {
-                s->fold = true;
-                s->norm_in_project = true;
-        }
-        // ... and on whole canvases large enough for the reduction launch to cost more than the fold (kFoldWholePixels)
-        if(whole && (size_t)W * H >= kFoldWholePixels && (H + kTY - 1) / kTY <= kFoldMaxRows) { s->fold = true; }
         s->band_local = !whole && (band_local_arrays & J2P_BAND_LOCAL_ARRAYS) != 0;
         s->weight = weight;
         s->iterations = iterations;
@@ -1113,6 +1113,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         s->ntr_local = s->nseg;
         s->ntr_global = (H + s->rpw - 1) / s->rpw;
         s->first_tr = row0 / s->rpw;
+        norm_defaults(s);
         const size_t ntiles = (size_t)s->ntx * s->ntr_local;
         unsigned max_strips = 0;
         for(unsigned c = 0; c < nchannel; c++) {
@@ -1308,8 +1309,7 @@ int j2p_solver_debug_option(j2p_solver *s, int option, int value)
                 break;
         case J2P_OPT_NORM_IN_PROJECT:
                 // 0: off; 1: the per-wavefront tree; 2: the per-workgroup tree; (needs NORM_FOLD)
-                s->norm_in_project = value != 0;
-                s->nip_form = value == 2 ? 2 : 1;
+                s->nip_form = value == 0 ? 0 : (value == 2 ? 2 : 1);
                 break;
         case J2P_OPT_NT_GRADIENT:
                 s->nt_forced = value >= 0;                 // negative: back to the policy
@@ -1339,9 +1339,8 @@ int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *byte
 int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on)
 {
         if(!s || !on || c >= s->nch) { return fail(J2P_EINVAL, "j2p_solver_wide_footprint: bad argument"); }
-        // (k_project_mixed has no wide-footprint path; bands of whole phases reduce ||g|| in k_project, NIP 2)
-        const int nip = !s->whole && s->band_nip && s->ntr_global <= kWaveTreeMax ? 2 : 0;
-        *on = s->ch[c].wide && !projects_mixed(s, nip) ? 1u : 0u;
+        // (k_project_mixed has no wide-footprint path; NIP 2 — bands of whole phases — never takes the mixed launch)
+        *on = s->ch[c].wide && !projects_mixed(s, plan_of(s, false, false).nip()) ? 1u : 0u;
         return J2P_OK;
 }
 
@@ -1422,6 +1421,17 @@ int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsi
         return J2P_OK;
 }
 
+int j2p_debug_norm_plan(int whole, int fold, int norm_in_project, int band_nip, unsigned tile_rows, int split, int log,
+                        int *level1, int *level2, unsigned *launches)
+{
+        if(!level1 || !level2 || !launches || norm_in_project < 0 || norm_in_project > 2 || tile_rows == 0) { return fail(J2P_EINVAL, "bad argument"); }
+        const NormPlan p = norm_plan(whole != 0, fold != 0, norm_in_project, band_nip != 0, tile_rows, split != 0, log != 0);
+        *level1 = p.level1;
+        *level2 = p.level2;
+        *launches = 2 + p.launches();
+        return J2P_OK;
+}
+
 int j2p_debug_build(void)
 {
 #ifdef J2P_DEBUG
@@ -1469,9 +1479,8 @@ int j2p_solver_band(const j2p_solver *s, unsigned *row_begin, unsigned *row_end)
 int j2p_solver_launches_per_iteration(const j2p_solver *s, unsigned *n)
 {
         if(!s || !n) { return fail(J2P_EINVAL, "NULL argument"); }
-        // (unlogged runs of a whole-canvas solver; logging adds the log kernels and takes the two-launch form)
-        if(!s->whole) { *n = 2 + (s->band_nip ? 0u : 1u); }
-        else { *n = s->fold ? 2 : 3; }
+        // (unlogged runs of whole phases; logging adds the log kernels and moves level 2 out of k_project)
+        *n = 2 + plan_of(s, false, false).launches();
         return J2P_OK;
 }
 
@@ -1784,7 +1793,7 @@ int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *cons
         if(!s || !rowsums || !first_tile_row || !tile_rows) { return fail(J2P_EINVAL, "NULL argument"); }
         if(nband == 0 || nband > (unsigned)kMaxBands) { return fail(J2P_EINVAL, "1..%d bands", kMaxBands); }
         if(nout > (unsigned)kMaxBands || (nout && !norm_out)) { return fail(J2P_EINVAL, "norm_from_bands: bad output list"); }
-        if(!s->grad_done || s->rowsums_pending) { return fail(J2P_ESTATE, "norm_from_bands needs a finished gradient phase"); }
+        if(!s->grad_done || rowsums_owed(s)) { return fail(J2P_ESTATE, "norm_from_bands needs a finished gradient phase"); }
         // a whole-canvas solver above kNormInProjectPixels reduces its partials in one kernel and never forms the
         // level-1 row sums this call reads
         if(s->whole && !s->fold) { return fail(J2P_ESTATE, "norm_from_bands: this solver leaves no per-tile-row sums (whole canvas, norm folding off)"); }
@@ -1818,7 +1827,8 @@ int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *cons
         while(P < s->ntr_global) { P <<= 1; }
         hipLaunchKernelGGL(k_norm_bands, dim3(s->nch), dim3(256), P * sizeof(double), s->stream, t, s->ntr_global, s->nch);
         HIP_TRY(hipGetLastError());
-        s->norm_ready = true;
+        // (a whole canvas whose k_project runs the tree keeps doing so: the words written here are the other bands')
+        if(!(s->whole && s->plan.nip())) { s->plan.level2 = J2P_NORM_L2_EXTERNAL; }
         return J2P_OK;
 }
 
@@ -1832,9 +1842,9 @@ int j2p_solver_norm_ptr(j2p_solver *s, float **norm)
 int j2p_solver_norm_external(j2p_solver *s)
 {
         if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(!s->grad_done || s->rowsums_pending) { return fail(J2P_ESTATE, "norm_external needs a finished gradient phase"); }
-        if(s->norm_by_project) { return fail(J2P_ESTATE, "norm_external: this solver reduces the norm inside its projection kernel"); }
-        s->norm_ready = true;
+        if(!s->grad_done || rowsums_owed(s)) { return fail(J2P_ESTATE, "norm_external needs a finished gradient phase"); }
+        if(s->whole && s->plan.nip()) { return fail(J2P_ESTATE, "norm_external: this solver reduces the norm inside its projection kernel"); }
+        s->plan.level2 = J2P_NORM_L2_EXTERNAL;
         return J2P_OK;
 }
 

@@ -53,7 +53,7 @@
 namespace {
 
 constexpr unsigned kLogCols = 2 + J2P_MAX_CHANNELS;
-constexpr unsigned kTreeRowsInProject = 1024;   // tile rows k_project's in-kernel tree handles (kWaveTreeMax)
+constexpr unsigned kTreeRowsInProject = J2P_NORM_TREE_ROWS;   // tile rows k_project's in-kernel tree handles
 
 enum Exchange { kDirect = 0, kCopy = 1, kRccl = 2 };
 const char *const kExchangeName[3] = {"direct", "copy", "rccl"};

@@ -661,6 +661,51 @@ def test_every_schedule_switch_leaves_the_bits_alone(exp_lib, oracle, shape, mon
                     assert bit_equal(t.download(c), want[c]), f"rpw {rpw} (ignored by band solvers), two bands: channel {c}"
 
 
+def test_more_tile_rows_than_one_tree_takes_against_the_reference(lib, oracle):
+    """a whole canvas of more than 1024 tile rows — 64x4128 gets 4-row tile rows, 1032 of them — folds level 1 of the norm
+    into k_gradient but can run level 2 in neither kernel: tickets, then a k_norm_finish launch (the norm plan's fallback,
+    reached by default on ordinary tall images).  The smallest shape that gets there, against the reference's bits"""
+    import jpeg2png_amd as j
+    planes = make_case(64, 4128, "444", 10, seed=93, y_only=True)
+    its = 5
+    want, _ = oracle.oracle_compute(planes, 0.3, [0.001], its)
+    with j.Solver(planes, 0.3, [0.001], its) as s:
+        assert s.launches_per_iteration() == 3
+        s.run(its)
+        assert bit_equal(s.download(0), want[0])
+    with j.Solver(planes, 0.3, [0.001], its) as s:
+        rows = s.run(its, log=True)
+        assert bit_equal(s.download(0), want[0]), "with the CSV sums"
+        assert np.isfinite(rows).all()
+
+
+def test_reported_launches_follow_the_norm_options(lib):
+    """launches_per_iteration() is read from the norm plan: the six norm settings of
+    test_every_schedule_switch_leaves_the_bits_alone on its 4:2:2 canvas (13 tile rows: no limit bites) — the stand-alone
+    k_norm_whole launch is the only reduction launch among them — and none of them moves a channel between the
+    projection paths that wide_footprint() reports"""
+    import jpeg2png_amd as j
+    planes = make_case(264, 200, "422", 10, seed=91)
+    settings = [
+        ({j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0}, 3),
+        ({j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 1}, 2),
+        ({j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NT_GRADIENT: 2, j.J2P_OPT_MIXED_PROJECT: 0}, 2),
+        ({j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 1}, 2),
+        ({j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 2, j.J2P_OPT_MIXED_PROJECT: 0}, 2),
+        ({j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 2, j.J2P_OPT_MIXED_PROJECT: 0, j.J2P_OPT_NT_GRADIENT: 3}, 2),
+    ]
+    with j.Solver(planes, 0.3, [0.001] * 3, 1) as s:
+        assert s.launches_per_iteration() == 2                 # (the solver's own choice at this size: NIP 1)
+        default_paths = [s.wide_footprint(c) for c in range(3)]
+    for opts, launches in settings:
+        with j.Solver(planes, 0.3, [0.001] * 3, 1) as s:
+            for k, v in opts.items():
+                s.debug_option(k, v)
+            assert s.launches_per_iteration() == launches, f"options {opts}"
+            if j.J2P_OPT_MIXED_PROJECT not in opts:
+                assert [s.wide_footprint(c) for c in range(3)] == default_paths, f"options {opts}"
+
+
 @pytest.mark.parametrize("shape", [(700, 328, 0.3), (1000, 96, 0.3), (264, 200, 0.0), (4096, 48, 0.3)])
 def test_half_and_quarter_items_leave_the_bits_alone(exp_lib, oracle, shape, monkeypatch):
     """the first workgroups of a gradient launch march two tile rows at once, the last ones half and quarter tile rows
