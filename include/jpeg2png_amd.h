@@ -411,6 +411,51 @@ int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsig
 int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
                             uint8_t *out_host);
 
+/* Tensor output: the same conversion up to the clamp, left ON THE DEVICE as the elements of a strided tensor — for consumers
+ * that run on the GPU themselves (a model that is fed deblocked images): no 8-bit truncation, no download, no host
+ * synchronisation.  For image pixel (x, y) with the planes' values Y, Cb, Cr at canvas (x, y), exactly as above (png.c:37-47,
+ * jpeg2png.c:156-159):
+ *     yi = (float)((double)Y + 128.)
+ *     v0 = clampf((float)((double)yi + 1.402 * (double)Cr))
+ *     v1 = clampf((float)((double)yi - 0.34414 * (double)Cb - 0.71414 * (double)Cr))
+ *     v2 = clampf((float)((double)yi + 1.772 * (double)Cb))
+ * with clampf = CLAMP(x, 0., 255.) on the narrowed float; one plane: v0 = clampf(yi), Cb / Cr are not read.  Channel k's
+ * element is then
+ *     u8               : (uint8_t)(unsigned)v_k — the 8-bit samples of j2p_planes_to_rgb / _grey, byte for byte;
+ *     f32 / f16 / bf16 : t = v_k * scale[k] rounded to f32, then t = t + bias[k] rounded to f32 (two operations, never a
+ *                        fused one, and applied also for scale 1 / bias 0: -0.f becomes +0.f); f32 stores t, f16 and bf16
+ *                        store t rounded to nearest, ties to even.
+ * Element (k, y, x) goes to data + k * stride_c + (y - row_begin) * stride_y + x * stride_x, strides in ELEMENTS: CHW is
+ * stride_x == 1, HWC is stride_c == 1 and stride_x == nplane, and anything else is served too — a slot of an N x C x H x W
+ * batch, a padded canvas, a transposed view.  Bytes that are not elements of the image are never written.  (Contiguous
+ * CHW / HWC destinations whose rows are aligned to 4 elements are written with 16 / 8 / 4-byte stores; any other view one
+ * element at a time: as correct, only slower.)
+ * nplane is 3 or 1.  Argument checks, state checks and whole / band rules of j2p_planes_to_rgb / j2p_planes_rows_to_rgb;
+ * J2P_EINVAL also for an unknown dtype, a stride below 1, data NULL, not aligned to its element size, or not plain device
+ * memory of the solvers' device (managed and host memory are refused), a scale or bias that is not finite, and u8 with
+ * scale != 1 or bias != 0.
+ * ASYNCHRONOUS: the calls enqueue on planes[0].solver's stream and return; nothing is staged, copied or waited for on that
+ * stream.  The caller orders its consumers behind j2p_solver_stream() (an event, or hipStreamSynchronize). */
+#define J2P_DTYPE_U8 0
+#define J2P_DTYPE_F16 1
+#define J2P_DTYPE_BF16 2
+#define J2P_DTYPE_F32 3
+typedef struct j2p_tensor {
+        void *data;                      /* DEVICE memory on the solvers' device */
+        int dtype;
+        ptrdiff_t stride_c, stride_y, stride_x;   /* in elements, all >= 1 */
+        float scale[3], bias[3];         /* float dtypes; u8 requires 1 and 0 */
+} j2p_tensor;
+int j2p_planes_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_tensor *out);
+int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w,
+                              unsigned row_begin, unsigned row_end, const j2p_tensor *out);
+/* Test hook (no device needed): which of k_to_tensor's destination paths the full-width rows of a w-column image of nplane
+ * (3 or 1) planes take for a destination at data_address with these strides: 0 generic (one element per store), 1 planar,
+ * 2 interleaved (4 elements per store; they need the address aligned to such a store and stride_y — planar with three planes
+ * also stride_c — a multiple of 4 elements).  Images narrower than 4 columns are generic. */
+int j2p_debug_tensor_path(unsigned w, unsigned nplane, int dtype, ptrdiff_t stride_c, ptrdiff_t stride_y, ptrdiff_t stride_x,
+                          uintptr_t data_address, int *path);
+
 /* JPEG output: ONE (solver, channel) pair's current iterate as quantised DCT coefficients, ready for libjpeg's
  * jpeg_write_coefficients — no RGB conversion and no 8-bit samples in between.  For each 8x8 block of the canvas plane:
  * dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes), every coefficient divided by quant_table[j] as
@@ -502,7 +547,17 @@ typedef struct j2p_job {
          * resolution (1 or 2; 0 means 1).  out_blocks_w x out_blocks_h stays the grid of a full-resolution component; channel c gets,
          * and out_coef[c] holds, ceil(out_blocks_w / out_sub_w[c]) x ceil(out_blocks_h / out_sub_h[c]) blocks */
         unsigned out_sub_w[J2P_MAX_CHANNELS], out_sub_h[J2P_MAX_CHANNELS];
+        /* tensor output (j2p_planes_rows_to_tensor): out_tensor.data != NULL selects it — the image, cropped to out_w x out_h, as
+         * the elements of a tensor in DEVICE memory of one of the batch's GPUs; out_bits must then be 0, out_coef[0] NULL and
+         * nchannel 1 or 3.  The job runs on a worker of the tensor's device (another device: J2P_EINVAL at submit), and after
+         * j2p_batch_wait the tensor is complete for any stream.  Not with `tile` (J2P_EINVAL, "not supported"): bands on other
+         * GPUs would have to store into the tensor's device through peer access, which no machine at hand can test.
+         * out_planes is still honoured.  Appended last: the fields above keep their offsets (j2p_debug_job_layout) */
+        j2p_tensor out_tensor;
 } j2p_job;
+/* test hook: sizeof(j2p_job) and offsetof(j2p_job, out_tensor) as this library was compiled — what a binding's own mirror of
+ * the struct is compared with */
+void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset);
 int j2p_batch_create(j2p_batch **out, unsigned ndev, const int devices[], unsigned slots_per_device);
 void j2p_batch_destroy(j2p_batch *b);                       /* finishes queued jobs first */
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket);

@@ -48,6 +48,13 @@ _ROWS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint,
 _PROGRESS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint)
 
 
+class _CTensor(ctypes.Structure):
+    """j2p_tensor: a strided destination in device memory (strides in elements)"""
+    _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int),
+                ("stride_c", ctypes.c_ssize_t), ("stride_y", ctypes.c_ssize_t), ("stride_x", ctypes.c_ssize_t),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -57,7 +64,8 @@ class _CJob(ctypes.Structure):
                 ("tile_first", ctypes.c_uint), ("tile_count", ctypes.c_uint), ("tile_min_band_pixels", ctypes.c_size_t),
                 ("out_quant", ctypes.c_void_p * 3), ("out_coef", ctypes.c_void_p * 3),
                 ("out_blocks_w", ctypes.c_uint), ("out_blocks_h", ctypes.c_uint),
-                ("out_sub_w", ctypes.c_uint * 3), ("out_sub_h", ctypes.c_uint * 3)]
+                ("out_sub_w", ctypes.c_uint * 3), ("out_sub_h", ctypes.c_uint * 3),
+                ("out_tensor", _CTensor)]
 
 
 class _CPlaneRef(ctypes.Structure):
@@ -85,6 +93,7 @@ C_ABI_SYMBOLS = [
     "j2p_decode_plane", "j2p_dct8x8_blocks", "j2p_math_selftest", "j2p_planes_to_rgb", "j2p_planes_rows_to_rgb", "j2p_sqrt_exhaustive",
     "j2p_planes_to_grey", "j2p_planes_rows_to_grey", "j2p_planes_to_coefficients", "j2p_planes_rows_to_coefficients",
     "j2p_planes_to_coefficients_sub", "j2p_planes_rows_to_coefficients_sub",
+    "j2p_planes_to_tensor", "j2p_planes_rows_to_tensor", "j2p_debug_tensor_path", "j2p_debug_job_layout",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -99,6 +108,8 @@ J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_P
 J2P_OPT_NARROW_COEFFICIENTS = 7
 J2P_OPT_WIDE_FOOTPRINT = 8
 ZOOM_MAX = 4
+J2P_DTYPE_U8, J2P_DTYPE_F16, J2P_DTYPE_BF16, J2P_DTYPE_F32 = 0, 1, 2, 3
+TENSOR_PATHS = ("generic", "planar", "interleaved")     # what j2p_debug_tensor_path reports: 0, 1, 2
 
 _lib = None
 
@@ -234,6 +245,14 @@ def _bind(path):
     lib.j2p_tiled_host_cpu_seconds.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
     lib.j2p_planes_rows_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                                         ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_planes_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CTensor)]
+    lib.j2p_planes_rows_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                              ctypes.POINTER(_CTensor)]
+    lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
+                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+    lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    lib.j2p_debug_job_layout.restype = None
+    lib.j2p_solver_stream.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
     lib.j2p_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.c_uint]
     lib.j2p_batch_destroy.argtypes = [ctypes.c_void_p]
     lib.j2p_batch_destroy.restype = None
@@ -314,6 +333,76 @@ def division_exhaustive(which, first=0, count=0, device=0):
     return rep[0], [hex(v) for v in rep[1:] if v]
 
 
+def tensor_path(w, nplane, dtype, stride_c, stride_y, stride_x, address):
+    """which destination path the tensor kernel takes for the full-width rows of such an image: "generic", "planar" or
+    "interleaved" (j2p_debug_tensor_path; no device needed).  dtype: a J2P_DTYPE_* code; strides in elements"""
+    path = ctypes.c_int(-1)
+    _check(load_library().j2p_debug_tensor_path(int(w), int(nplane), int(dtype), int(stride_c), int(stride_y), int(stride_x), int(address),
+                                                ctypes.byref(path)))
+    return TENSOR_PATHS[path.value]
+
+
+def job_layout():
+    """(sizeof(j2p_job), offsetof(j2p_job, out_tensor)) as the loaded library was compiled"""
+    size, off = ctypes.c_size_t(), ctypes.c_size_t()
+    load_library().j2p_debug_job_layout(ctypes.byref(size), ctypes.byref(off))
+    return size.value, off.value
+
+
+def _torch():
+    """torch, imported on first use: only tensor output needs it"""
+    try:
+        import torch
+    except ImportError:
+        raise J2PError("tensor output needs PyTorch (torch is not installed)") from None
+    return torch
+
+
+def _tensor_dtype(torch, dtype):
+    codes = {torch.uint8: J2P_DTYPE_U8, torch.float16: J2P_DTYPE_F16, torch.bfloat16: J2P_DTYPE_BF16, torch.float32: J2P_DTYPE_F32}
+    if dtype not in codes:
+        raise J2PError(f"tensor output: dtype must be torch.uint8, float16, bfloat16 or float32, not {dtype!r}")
+    return codes[dtype]
+
+
+def _c_tensor(t, nplane, width, height, layout, scale, bias, device=None):
+    """the j2p_tensor of the CUDA tensor t — (nplane, height, width) for layout "chw", (height, width, nplane) for "hwc", any
+    view: the strides are the tensor's — with per-channel scale and bias (None: 1 and 0).  J2PError for anything else."""
+    torch = _torch()
+    if layout not in ("chw", "hwc"):
+        raise J2PError(f"tensor output: layout must be 'chw' or 'hwc', not {layout!r}")
+    if nplane not in (1, 3):
+        raise J2PError("tensor output needs three planes (RGB) or one (greyscale)")
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("tensor output needs width and height")
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise J2PError("tensor output needs a torch.Tensor on a GPU")
+    if device is not None and t.device.index != device:
+        raise J2PError(f"tensor output: the tensor is on {t.device}, the solver on device {device}")
+    shape = (nplane, int(height), int(width)) if layout == "chw" else (int(height), int(width), nplane)
+    if tuple(t.shape) != shape:
+        raise J2PError(f"tensor output: shape {tuple(t.shape)}, expected {shape} for layout {layout!r}")
+    code = _tensor_dtype(torch, t.dtype)
+    sc, sy, sx = t.stride() if layout == "chw" else (t.stride(2), t.stride(0), t.stride(1))
+    if nplane == 1:
+        sc = max(sc, 1)             # (a dimension of size 1 is never stepped over; torch may report any stride for it)
+    if min(sc, sy, sx) < 1:
+        raise J2PError(f"tensor output: strides (c, y, x) = ({sc}, {sy}, {sx}) must all be at least 1 (no expanded views)")
+
+    def three(v, default, what):
+        if v is None:
+            return [default] * 3
+        v = [float(x) for x in (v if isinstance(v, (list, tuple, np.ndarray)) else [v] * nplane)]
+        if len(v) != nplane:
+            raise J2PError(f"tensor output: {what} must have one value per plane")
+        return v + [default] * (3 - nplane)
+
+    scale, bias = three(scale, 1.0, "scale"), three(bias, 0.0, "bias")
+    if code == J2P_DTYPE_U8 and (scale != [1.0] * 3 or bias != [0.0] * 3):
+        raise J2PError("tensor output: uint8 elements are the 8-bit samples; scale and bias apply to float dtypes only")
+    return _CTensor(t.data_ptr(), code, sc, sy, sx, (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias))
+
+
 def _sampling(subsampling):
     """(sx, sy) of a coefficient output: 1 or 2 each"""
     try:
@@ -349,6 +438,7 @@ class Solver:
         _check(lib.j2p_solver_create(ctypes.byref(h), device, stream, self.nch, cpl, float(weight), pw,
                                      int(iterations), b, 1 if band_local_arrays else 0))
         self._h = h
+        self.device = int(device)
         del keep
         W, H = ctypes.c_uint(), ctypes.c_uint()
         _check(lib.j2p_solver_canvas(h, ctypes.byref(W), ctypes.byref(H)))
@@ -442,6 +532,49 @@ class Solver:
         out = np.empty((bh, bw, 64), dtype=np.int16)
         ref = _CPlaneRef(self._h, int(c))
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
+        return out
+
+    def stream(self):
+        """the hipStream_t the solver launches on (an integer address)"""
+        p = ctypes.c_void_p()
+        _check(self._lib.j2p_solver_stream(self._h, ctypes.byref(p)))
+        return p.value or 0
+
+    def to_tensor(self, width, height, dtype=None, layout="chw", scale=None, bias=None, out=None):
+        """The solved image, cropped to width x height, as an RGB (three-channel solver) or greyscale (one-channel solver)
+        torch.Tensor on the solver's GPU — (3|1, height, width) for layout "chw", (height, width, 3|1) for "hwc" — without
+        leaving the device (j2p_planes_rows_to_tensor): png.c's colour conversion and clamp to [0, 255], then per channel
+        `* scale[k] + bias[k]` in float32 (two rounded operations), stored as dtype: torch.float32 (default), float16,
+        bfloat16 (rounded to nearest even) or uint8 (the 8-bit samples; no scale / bias).  out: a tensor to write into, any
+        view of that shape and dtype (a slot of a batch tensor, ...).  A band solver writes its own rows: height is then
+        the band's row count and the rows are [row_begin, row_begin + height).
+        Nothing waits on the host: the kernel is queued on the solver's stream and torch's current stream is made to wait
+        for it, so torch operations issued afterwards see the finished tensor."""
+        torch = _torch()
+        if self.nch not in (1, 3):
+            raise J2PError("tensor output needs a solver of three channels (RGB) or one (greyscale)")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            dtype = torch.float32 if dtype is None else dtype
+            _tensor_dtype(torch, dtype)
+            if width is None or height is None or int(width) < 1 or int(height) < 1:
+                raise J2PError("tensor output needs width and height")
+            shape = (self.nch, int(height), int(width)) if layout == "chw" else (int(height), int(width), self.nch)
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
+            raise J2PError(f"tensor output: out is {out.dtype}, dtype says {dtype}")
+        ct = _c_tensor(out, self.nch, width, height, layout, scale, bias, device=self.device)
+        refs = (_CPlaneRef * self.nch)(*[_CPlaneRef(self._h, c) for c in range(self.nch)])
+        ours = torch.cuda.ExternalStream(self.stream(), device=dev)
+        theirs = torch.cuda.current_stream(dev)
+        ours.wait_stream(theirs)            # whatever torch still does with `out` (its allocation, a fill) comes first
+        _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
+        theirs.wait_stream(ours)
+        # `out` is now in use on torch's current stream, behind the kernel: an allocator that owns it for another stream must
+        # not hand it out again before that.  (Recorded for THEIR stream, never for ours: the allocator records an event on
+        # every recorded stream when the tensor is freed, and the solver's stream is destroyed with the solver — which a
+        # tensor may well outlive.)
+        out.record_stream(theirs)
         return out
 
     def download_gradient(self, c):
@@ -582,10 +715,11 @@ class TiledSolver:
 
     def band_solver(self, b):
         """borrowed handle of band b's j2p_solver (kernel timing in bench.py); owned by the TiledSolver"""
-        h = ctypes.c_void_p()
-        _check(self._lib.j2p_tiled_band(self._h, b, None, None, None, ctypes.byref(h)))
+        h, d, r0, r1 = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_uint(), ctypes.c_uint()
+        _check(self._lib.j2p_tiled_band(self._h, b, ctypes.byref(d), ctypes.byref(r0), ctypes.byref(r1), ctypes.byref(h)))
         s = Solver.__new__(Solver)
         s._lib, s._h, s._borrowed = self._lib, h, True
+        s.nch, s.device, s.W, s.H, s.row_begin, s.row_end = self.nch, d.value, self.W, self.H, r0.value, r1.value
         return s
 
     def download(self, c):
@@ -625,8 +759,14 @@ class Batch:
         self._pending = {}
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
-               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None):
-        """quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
+               tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
+               tensor=None, layout="chw", scale=None, bias=None):
+        """tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
+        GPU as that tensor's elements — shape (3|1, height, width) for layout "chw" or (height, width, 3|1) for "hwc", dtype
+        uint8 / float16 / bfloat16 / float32, any view, with per-channel scale and bias as in Solver.to_tensor — by a worker
+        of the tensor's GPU; wait() returns the tensor, complete for any stream.  What torch has queued for the tensor on its
+        current stream is waited for before the job is queued;
+        quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
         quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
         writer entropy-codes — instead of the float planes;
         subsampling=[(sx, sy) per plane] (with quant_tables; 1 or 2 each): plane c at 1/sx x 1/sy of the resolution, int16
@@ -655,7 +795,22 @@ class Batch:
         W = max(p.w * p.w_samp for p in planes)
         H = max(p.h * p.h_samp for p in planes)
         shapes = [(p.h * p.h_samp, p.w * p.w_samp) if separate else (H, W) for p in planes]
-        if quant_tables is not None:
+        if tensor is not None:
+            if quant_tables is not None or subsampling is not None:
+                raise J2PError("job: tensor output and coefficient output (quant_tables) exclude each other")
+            if bits:
+                raise J2PError("job: tensor output needs bits = 0")
+            if out is not None:
+                raise J2PError("job: tensor output is written into `tensor`; out is for host arrays")
+            job.out_tensor = _c_tensor(tensor, n, width, height, layout, scale, bias)
+            job.out_w, job.out_h = int(width), int(height)
+            # the workers' streams know nothing of torch's: what it has queued for this memory (a fill, the work of the
+            # memory's previous owner) has to be over before a worker writes
+            _torch().cuda.current_stream(tensor.device).synchronize()
+            out = tensor
+        elif layout != "chw" or scale is not None or bias is not None:
+            raise J2PError("job: layout, scale and bias belong to tensor output (tensor=)")
+        elif quant_tables is not None:
             if bits:
                 raise J2PError("job: coefficient output (quant_tables) needs bits = 0")
             if len(quant_tables) != n:

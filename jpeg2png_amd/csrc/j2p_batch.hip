@@ -4,7 +4,8 @@
 // A j2p_batch owns `slots_per_device` worker threads per GPU.  A job is one image — what decode_file() does
 // between read_jpeg() and write_png(): one joint compute(3, ...) or three separate compute(1, ...) calls, then the
 // planes handed back as floats or, converted on the device (png.c:37-62), as RGB samples (greyscale ones for a
-// one-channel job).  Every worker drives its jobs on streams of its own, so while one slot's image is being solved
+// one-channel job), as quantised coefficients, or left on the device as a tensor (a job that only workers of the tensor's
+// GPU take).  Every worker drives its jobs on streams of its own, so while one slot's image is being solved
 // the next slot's coefficients go up and a third one's pixels come down: H2D / solve / D2H overlap without any of
 // them knowing about the others.  Device memory comes from the library's pool (one arena per solver, recycled
 // between jobs): after the first few images a job performs no hipMalloc / hipFree — the device-wide synchronisation
@@ -30,6 +31,7 @@ namespace {
 struct Job {
         j2p_job desc;
         int ticket = 0;
+        int device = -1;                    // tensor output: the tensor's device, the only one whose workers may take the job
         int rc = J2P_OK;
         bool finished = false;
         char err[256] = "";
@@ -84,6 +86,13 @@ int validate_job(const j2p_job &d)
                                 return j2p_fail(J2P_EINVAL, "job: channel %u: output sampling factors %ux%u (1 and 2 are supported)", c, d.out_sub_w[c], d.out_sub_h[c]);
                         }
                 }
+        }
+        if(d.out_tensor.data) {
+                // tensor output: the image left in device memory, instead of samples and coefficients
+                if(d.out_bits || d.out_coef[0]) { return j2p_fail(J2P_EINVAL, "job: tensor output (out_tensor) needs out_bits 0 and no out_coef"); }
+                if(d.nchannel == 2) { return j2p_fail(J2P_EINVAL, "job: tensor output needs three channels (RGB) or one (greyscale)"); }
+                if(d.out_w == 0 || d.out_h == 0) { return j2p_fail(J2P_EINVAL, "job: tensor output needs out_w and out_h"); }
+                if(d.tile) { return j2p_fail(J2P_EINVAL, "job: tensor output of a row-tiled job is not supported"); }
         }
         return J2P_OK;
 }
@@ -198,6 +207,16 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap)
                         else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
                         continue;
                 }
+                if(d.out_tensor.data) {
+                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;
+                        if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
+                        j2p_tensor rows = d.out_tensor;                  // the band's first row of it
+                        const size_t bytes = d.out_tensor.dtype == J2P_DTYPE_U8 ? 1 : (d.out_tensor.dtype == J2P_DTYPE_F32 ? 4 : 2);
+                        rows.data = static_cast<char *>(d.out_tensor.data) + (size_t)y0 * (size_t)(d.out_tensor.stride_y > 0 ? d.out_tensor.stride_y : 0) * bytes;
+                        JOB_TRY(j2p_planes_rows_to_tensor(ref, d.nchannel, d.out_w, y0, y1, &rows));
+                        JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: complete, for any stream
+                        continue;
+                }
                 for(unsigned c = 0; d.out_coef[0] && c < d.nchannel; c++) {
                         const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
                         const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
@@ -291,10 +310,17 @@ void worker_main(j2p_batch *b, int device)
                 Job *job = nullptr;
                 {
                         std::unique_lock<std::mutex> g(b->lock);
-                        b->work.wait(g, [&] { return b->quit || !b->queue.empty(); });
-                        if(b->queue.empty()) { return; }          // quit, and nothing left to do
-                        job = b->queue.front();
-                        b->queue.pop_front();
+                        // the first queued job this worker may run: any job, except that one with a tensor is pinned to its GPU
+                        const auto mine = [&] {
+                                auto it = b->queue.begin();
+                                while(it != b->queue.end() && (*it)->device >= 0 && (*it)->device != device) { ++it; }
+                                return it;
+                        };
+                        b->work.wait(g, [&] { return b->quit || mine() != b->queue.end(); });
+                        const auto it = mine();
+                        if(it == b->queue.end()) { return; }      // quit, and nothing left for this worker to do
+                        job = *it;
+                        b->queue.erase(it);
                 }
                 int rc = validate_job(job->desc);
                 bool tiled = false;
@@ -375,6 +401,18 @@ int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
         Job *j = new(std::nothrow) Job();
         if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
         j->desc = *job;
+        if(job->out_tensor.data) {
+                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor
+                int rc = validate_job(j->desc);
+                if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
+                        rc = j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
+                }
+                bool owned = false;
+                for(int dev : b->devices) { owned = owned || dev == j->device; }
+                if(rc == J2P_OK && !owned) { rc = j2p_fail(J2P_EINVAL, "job: the tensor lives on device %d, which this batch does not drive", j->device); }
+                if(rc != J2P_OK) { delete j; return rc; }
+        }
+        const bool pinned = j->device >= 0;
         {
                 std::lock_guard<std::mutex> g(b->lock);
                 if(b->quit) { delete j; return j2p_fail(J2P_ESTATE, "batch is shutting down"); }
@@ -383,8 +421,15 @@ int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
                 b->queue.push_back(j);
                 *ticket = j->ticket;
         }
-        b->work.notify_one();
+        // (a pinned job may not be for the worker notify_one would wake)
+        if(pinned) { b->work.notify_all(); } else { b->work.notify_one(); }
         return J2P_OK;
+}
+
+void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)
+{
+        if(size) { *size = sizeof(j2p_job); }
+        if(out_tensor_offset) { *out_tensor_offset = offsetof(j2p_job, out_tensor); }
 }
 
 int j2p_batch_wait(j2p_batch *b, int ticket)

@@ -13,6 +13,9 @@ void j2p_set_last_error(const char *msg);
 // true when J2P_TILED_EXCHANGE / J2P_TILED_WAIT name an exchange: one that cannot be had is then an error, not a reason to
 // solve on one GPU (j2p_tiled.hip)
 int j2p_tiled_exchange_forced(void);
+// the device whose plain device memory p points into (hipPointerGetAttributes); J2P_EINVAL without an error text for host,
+// managed and unknown memory (j2p_solver.hip) — what tensor output checks its destination with
+int j2p_device_of_pointer(const void *p, int *device);
 
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves

@@ -2780,6 +2780,166 @@ template __global__ void k_to_samples<3>(const float *, unsigned, const float *,
 template __global__ void k_to_samples<1>(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, unsigned, uint8_t *);
 
 // ---------------------------------------------------------------------------
+// Tensor output: the same conversion up to the clamp (png.c:37-47 with the luma +128 of jpeg2png.c:156-159), left in DEVICE
+// memory as elements of a strided tensor — element (k, y, x) at data + k * stride_c + y * stride_y + x * stride_x, strides
+// in elements.  Per channel k with the clamped float v_k:
+//   u8                : (uint8_t)(unsigned)v_k — the 8-bit samples of k_to_samples;
+//   f32 / f16 / bf16  : t = v_k * scale[k], then t = t + bias[k] — two separately rounded f32 operations (this file is
+//                       compiled with -ffp-contract=off; never an fma, and no shortcut for scale 1 / bias 0: -0.f + 0.f is
+//                       +0.f) — stored as it is (f32) or rounded to nearest even by the cast (f16, bf16: which instruction
+//                       that is, is the compiler's choice).
+// Indexed in 2-D, no division anywhere: blockIdx.x and the lane give the column, the wavefront of the workgroup and
+// blockIdx.y the row, grid-stride over rows.  A lane converts 4 consecutive pixels of one row from ONE 16-byte load per
+// plane: its first column is a multiple of 4, crops start at canvas column 0, every canvas row starts at a multiple of W
+// floats with W a multiple of 8, and the planes themselves (xbuf) are carved from the solver's arena at multiples of 256
+// bytes (Carver::take) — so every such load is aligned and, W being a multiple of 4, inside the canvas row even where the
+// image ends inside the group.  A wavefront reads 1 KB of every plane's row.
+// LAYOUT (chosen by the host, tensor_path in j2p_solver.hip, the only place that knows the rule):
+//   planar      (stride_x == 1): a lane's 4 elements of a channel go out as one 16 / 8 / 4-byte store (f32 / 16-bit / u8);
+//   interleaved (stride_c == 1, stride_x == NPLANE): its 4 * NPLANE contiguous elements as NPLANE such stores;
+//   generic     : one element per store, any strides.
+// The first two are only launched where every such store is aligned to its width; the w % 4 pixels at the end of a row take
+// the element stores in every layout.  Nothing but elements of the image is ever written.
+// ---------------------------------------------------------------------------
+constexpr int kDtypeU8 = 0, kDtypeF16 = 1, kDtypeBF16 = 2, kDtypeF32 = 3;                // J2P_DTYPE_* (checked in j2p_solver.hip)
+constexpr int kTensorGeneric = 0, kTensorPlanar = 1, kTensorInterleaved = 2;           // what j2p_debug_tensor_path reports
+
+struct TensorOut {
+        void *data;                                     // element (0, first row, 0)
+        long long stride_c, stride_y, stride_x;         // in elements
+        float scale[3], bias[3];
+};
+
+template <int DTYPE>
+struct TensorElement {
+        static_assert(DTYPE == kDtypeU8 || DTYPE == kDtypeF16 || DTYPE == kDtypeBF16 || DTYPE == kDtypeF32, "u8, f16, bf16 or f32");
+        static constexpr int kBytes = DTYPE == kDtypeU8 ? 1 : (DTYPE == kDtypeF32 ? 4 : 2);
+        using Raw = std::conditional_t<kBytes == 1, uint8_t, std::conditional_t<kBytes == 2, uint16_t, uint32_t>>;
+        // the element's bits from the clamped float
+        static __device__ __forceinline__ unsigned make(float v, float scale, float bias)
+        {
+                if constexpr(DTYPE == kDtypeU8) {
+                        return (unsigned)(uint8_t)(unsigned)v;
+                } else {
+                        float t = v * scale;
+                        t = t + bias;
+                        if constexpr(DTYPE == kDtypeF32) { return __float_as_uint(t); }
+                        else if constexpr(DTYPE == kDtypeF16) { return (unsigned)__builtin_bit_cast(uint16_t, (_Float16)t); }
+                        else { return (unsigned)__builtin_bit_cast(uint16_t, (__bf16)t); }
+                }
+        }
+};
+
+// WORDS 32-bit words as one store: 16, 8 or 4 bytes
+template <int WORDS>
+__device__ __forceinline__ void store_words(void *p, const unsigned *v)
+{
+        static_assert(WORDS == 1 || WORDS == 2 || WORDS == 4, "4, 8 or 16 bytes");
+        if constexpr(WORDS == 4) { *reinterpret_cast<uint4 *>(p) = make_uint4(v[0], v[1], v[2], v[3]); }
+        else if constexpr(WORDS == 2) { *reinterpret_cast<uint2 *>(p) = make_uint2(v[0], v[1]); }
+        else { *reinterpret_cast<unsigned *>(p) = v[0]; }
+}
+
+__device__ __forceinline__ float clamp_sample(double v)
+{
+        const float x = (float)v;
+        return (double)x > 255. ? 255.f : ((double)x < 0. ? 0.f : x);           // CLAMP(x, 0., 255.), png.c:15-17: to_sample's
+}
+
+// the rows of one lane: columns [x0, x0 + npix).  FULL: npix is 4 — a loop of its own, so that the compiler sees all four loaded
+// values used and keeps the 16-byte loads whole (with npix a run-time value in one loop it loads three floats and one)
+template <int NPLANE, int DTYPE, int LAYOUT, bool FULL>
+__device__ __forceinline__ void tensor_lane_rows(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp, unsigned crs,
+                                                 unsigned x0, unsigned npix, unsigned h, const TensorOut &o)
+{
+        using E = TensorElement<DTYPE>;
+        using Raw = typename E::Raw;
+        constexpr int kPerWord = 4 / E::kBytes;         // elements per 32-bit word
+        constexpr int kWords = E::kBytes;               // words of one store of 4 elements: 16 / 8 / 4 bytes
+        Raw *const data = static_cast<Raw *>(o.data);
+        for(unsigned y = blockIdx.y * 4 + (threadIdx.x >> 6); y < h; y += gridDim.y * 4) {
+                const float4 y4 = *reinterpret_cast<const float4 *>(yp + (size_t)y * ys + x0);
+                const float yin[4] = {y4.x, y4.y, y4.z, y4.w};
+                float v[NPLANE][4];
+                if constexpr(NPLANE == 3) {
+                        const float4 cb4 = *reinterpret_cast<const float4 *>(cbp + (size_t)y * cbs + x0);
+                        const float4 cr4 = *reinterpret_cast<const float4 *>(crp + (size_t)y * crs + x0);
+                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+#pragma unroll
+                        for(int p = 0; p < 4; p++) {
+                                const float yi = (float)((double)yin[p] + 128.);        // jpeg2png.c:158
+                                const float cbi = cbin[p], cri = crin[p];
+                                v[0][p] = clamp_sample((double)yi + 1.402 * (double)cri);
+                                v[1][p] = clamp_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri);
+                                v[2][p] = clamp_sample((double)yi + 1.772 * (double)cbi);
+                        }
+                } else {
+#pragma unroll
+                        for(int p = 0; p < 4; p++) { v[0][p] = clamp_sample((double)(float)((double)yin[p] + 128.)); }
+                }
+                unsigned e[NPLANE][4];
+#pragma unroll
+                for(int k = 0; k < NPLANE; k++) {
+#pragma unroll
+                        for(int p = 0; p < 4; p++) { e[k][p] = E::make(v[k][p], o.scale[k], o.bias[k]); }
+                }
+                const long long row = (long long)y * o.stride_y;
+                if constexpr(LAYOUT != kTensorGeneric && FULL) {
+                        // the lane's elements in memory order, packed into words: NPLANE stores of kWords words
+                        unsigned words[NPLANE * kWords];
+#pragma unroll
+                        for(int i = 0; i < NPLANE * kWords; i++) { words[i] = 0; }
+#pragma unroll
+                        for(int i = 0; i < NPLANE * 4; i++) {
+                                const unsigned bits = LAYOUT == kTensorPlanar ? e[i / 4][i % 4] : e[i % NPLANE][i / NPLANE];
+                                words[i / kPerWord] |= bits << (8 * E::kBytes * (i % kPerWord));
+                        }
+#pragma unroll
+                        for(int j = 0; j < NPLANE; j++) {
+                                Raw *dst = LAYOUT == kTensorPlanar ? data + (long long)j * o.stride_c + row + x0
+                                                                   : data + row + (long long)x0 * NPLANE + j * 4;
+                                store_words<kWords>(dst, words + j * kWords);
+                        }
+                } else {
+#pragma unroll
+                        for(int p = 0; p < 4; p++) {
+                                if(FULL || (unsigned)p < npix) {
+#pragma unroll
+                                        for(int k = 0; k < NPLANE; k++) {
+                                                data[(long long)k * o.stride_c + row + (long long)(x0 + p) * o.stride_x] = (Raw)e[k][p];
+                                        }
+                                }
+                        }
+                }
+        }
+}
+
+template <int NPLANE, int DTYPE, int LAYOUT>
+__global__ __launch_bounds__(256) void k_to_tensor(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
+                                                   unsigned crs, unsigned w, unsigned h, TensorOut o)
+{
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
+        static_assert(LAYOUT == kTensorGeneric || LAYOUT == kTensorPlanar || (LAYOUT == kTensorInterleaved && NPLANE == 3), "layout");
+        const unsigned x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+        if(x0 >= w) { return; }                                                 // (no barrier in this kernel)
+        if(w - x0 >= 4) { tensor_lane_rows<NPLANE, DTYPE, LAYOUT, true>(yp, ys, cbp, cbs, crp, crs, x0, 4, h, o); }
+        else { tensor_lane_rows<NPLANE, DTYPE, kTensorGeneric, false>(yp, ys, cbp, cbs, crp, crs, x0, w - x0, h, o); }   // the row's last w % 4 pixels
+}
+// (explicit instantiations, as for k_to_samples; one plane has no interleaved layout: stride_x == 1 there, which is planar)
+#define J2P_TENSOR_KERNEL(NPLANE, DTYPE, LAYOUT)                                                                                   \
+        template __global__ void k_to_tensor<NPLANE, DTYPE, LAYOUT>(const float *, unsigned, const float *, unsigned, const float *, \
+                                                                    unsigned, unsigned, unsigned, TensorOut);
+#define J2P_TENSOR_KERNELS(DTYPE)                                                                                                  \
+        J2P_TENSOR_KERNEL(3, DTYPE, kTensorGeneric) J2P_TENSOR_KERNEL(3, DTYPE, kTensorPlanar) J2P_TENSOR_KERNEL(3, DTYPE, kTensorInterleaved) \
+        J2P_TENSOR_KERNEL(1, DTYPE, kTensorGeneric) J2P_TENSOR_KERNEL(1, DTYPE, kTensorPlanar)
+J2P_TENSOR_KERNELS(kDtypeU8)
+J2P_TENSOR_KERNELS(kDtypeF16)
+J2P_TENSOR_KERNELS(kDtypeBF16)
+J2P_TENSOR_KERNELS(kDtypeF32)
+#undef J2P_TENSOR_KERNELS
+#undef J2P_TENSOR_KERNEL
+
+// ---------------------------------------------------------------------------
 // JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,
 // each coefficient divided by its output quantisation step (IEEE f32 quotient: `/` under
 // -fhip-fp32-correctly-rounded-divide-sqrt, never a reciprocal multiply), rounded to nearest even, clamped to

@@ -2102,6 +2102,155 @@ int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row
         return convert_rows(plane, 1, false, w, row_begin, row_end, bits, out_host);
 }
 
+// ---- tensor output: k_to_tensor ----
+static_assert(J2P_DTYPE_U8 == kDtypeU8 && J2P_DTYPE_F16 == kDtypeF16 && J2P_DTYPE_BF16 == kDtypeBF16 && J2P_DTYPE_F32 == kDtypeF32,
+              "the kernels' dtype codes are the header's");
+
+static unsigned tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ? 1 : (dtype == J2P_DTYPE_F32 ? 4 : 2); }
+
+// Which destination path the full groups of 4 pixels of a w-column image take — the only place that knows the rule.  A
+// vector path stores 4 elements at once, 16 / 8 / 4 bytes for f32 / 16-bit / u8, and needs every such store aligned to its
+// width: the first row's address, and (in elements) the row stride and — planar, three planes — the channel stride multiples
+// of 4; a lane's first column is a multiple of 4 already.  Everything else, and every image narrower than one group, is
+// generic: correct for any strides, one element per store.  Decided per image, not per row: rows [a, b) of an image start
+// at a multiple of stride_y from its first row, so the bands of one image agree.
+static int tensor_path(unsigned w, unsigned nplane, int dtype, long long stride_c, long long stride_y, long long stride_x, uintptr_t address)
+{
+        const unsigned store_bytes = 4 * tensor_element_bytes(dtype);
+        if(w < 4 || address % store_bytes != 0 || stride_y % 4 != 0) { return kTensorGeneric; }
+        if(stride_x == 1 && (nplane == 1 || stride_c % 4 == 0)) { return kTensorPlanar; }
+        if(nplane == 3 && stride_c == 1 && stride_x == 3) { return kTensorInterleaved; }
+        return kTensorGeneric;
+}
+
+int j2p_debug_tensor_path(unsigned w, unsigned nplane, int dtype, ptrdiff_t stride_c, ptrdiff_t stride_y, ptrdiff_t stride_x,
+                          uintptr_t data_address, int *path)
+{
+        if(!path || (nplane != 1 && nplane != 3) || dtype < J2P_DTYPE_U8 || dtype > J2P_DTYPE_F32 || w == 0 || stride_c < 1 || stride_y < 1 ||
+           stride_x < 1) {
+                return fail(J2P_EINVAL, "bad argument");
+        }
+        *path = tensor_path(w, nplane, dtype, stride_c, stride_y, stride_x, data_address);
+        return J2P_OK;
+}
+
+using TensorKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, TensorOut);
+
+// [three planes / one][dtype][path]; one plane has no interleaved layout (tensor_path never chooses it there)
+#define J2P_TENSOR_ROW(NPLANE, DTYPE, THIRD) {k_to_tensor<NPLANE, DTYPE, kTensorGeneric>, k_to_tensor<NPLANE, DTYPE, kTensorPlanar>, THIRD}
+#define J2P_TENSOR_ROWS(NPLANE, THIRD)                                                                                                     \
+        {J2P_TENSOR_ROW(NPLANE, kDtypeU8, THIRD(kDtypeU8)), J2P_TENSOR_ROW(NPLANE, kDtypeF16, THIRD(kDtypeF16)),                               \
+         J2P_TENSOR_ROW(NPLANE, kDtypeBF16, THIRD(kDtypeBF16)), J2P_TENSOR_ROW(NPLANE, kDtypeF32, THIRD(kDtypeF32))}
+#define J2P_TENSOR_INTERLEAVED(DTYPE) k_to_tensor<3, DTYPE, kTensorInterleaved>
+#define J2P_TENSOR_NONE(DTYPE) nullptr
+static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENSOR_INTERLEAVED), J2P_TENSOR_ROWS(1, J2P_TENSOR_NONE)};
+#undef J2P_TENSOR_NONE
+#undef J2P_TENSOR_INTERLEAVED
+#undef J2P_TENSOR_ROWS
+#undef J2P_TENSOR_ROW
+
+// rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
+// memory, through k_to_tensor; out->data is the element of row y0.  Argument and state checks of convert_rows, then the
+// tensor's own.  Asynchronous: the kernel is queued on planes[0].solver's stream and nothing waits for it.
+static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
+{
+        if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(nplane != 1 && nplane != 3) { return fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
+        if(w == 0 || y0 >= y1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
+        for(unsigned i = 0; whole && i < nplane; i++) {
+                if(planes[i].solver && !planes[i].solver->whole) {
+                        return fail(J2P_ESTATE, "to_tensor needs whole-canvas solvers (bands: j2p_planes_rows_to_tensor)");
+                }
+        }
+        const float *ptr[3] = {nullptr, nullptr, nullptr};
+        unsigned stride[3] = {0, 0, 0};
+        for(unsigned i = 0; i < nplane; i++) {
+                j2p_solver *s = planes[i].solver;
+                if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
+                if(s->device != planes[0].solver->device) { return fail(J2P_EINVAL, "planes live on different devices"); }
+                if(s->W < w || y0 < s->row0 || y1 > s->row0 + s->rows) {
+                        return fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
+                                    s->row0, s->row0 + s->rows, s->W);
+                }
+                if(s->grad_done) { return fail(J2P_ESTATE, "to_tensor between the two phases of an iteration"); }
+                ptr[i] = s->ch[planes[i].channel].xbuf[s->cur] + (size_t)(kHalo + (y0 - s->row0)) * s->W;
+                stride[i] = s->W;
+                // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
+                if(s->W % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
+        }
+        if(out->dtype != J2P_DTYPE_U8 && out->dtype != J2P_DTYPE_F16 && out->dtype != J2P_DTYPE_BF16 && out->dtype != J2P_DTYPE_F32) {
+                return fail(J2P_EINVAL, "to_tensor: unknown dtype %d", out->dtype);
+        }
+        if(out->stride_c < 1 || out->stride_y < 1 || out->stride_x < 1) {
+                return fail(J2P_EINVAL, "to_tensor: strides (%td, %td, %td) must all be at least 1 element", out->stride_c, out->stride_y, out->stride_x);
+        }
+        if(!out->data) { return fail(J2P_EINVAL, "to_tensor: data is NULL"); }
+        if(reinterpret_cast<uintptr_t>(out->data) % tensor_element_bytes(out->dtype) != 0) {
+                return fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", tensor_element_bytes(out->dtype));
+        }
+        TensorOut o;
+        o.data = out->data;
+        o.stride_c = out->stride_c;
+        o.stride_y = out->stride_y;
+        o.stride_x = out->stride_x;
+        for(unsigned k = 0; k < 3; k++) {
+                // (one plane: only entry 0 is used, the others are not looked at)
+                const float sc = k < nplane ? out->scale[k] : 1.f, bi = k < nplane ? out->bias[k] : 0.f;
+                if(!__builtin_isfinite(sc) || !__builtin_isfinite(bi)) { return fail(J2P_EINVAL, "to_tensor: scale / bias of channel %u is not finite", k); }
+                if(out->dtype == J2P_DTYPE_U8 && (sc != 1.f || bi != 0.f)) {
+                        return fail(J2P_EINVAL, "to_tensor: u8 elements are the 8-bit samples: scale must be 1 and bias 0 (channel %u)", k);
+                }
+                o.scale[k] = sc;
+                o.bias[k] = bi;
+        }
+        j2p_solver *s0 = planes[0].solver;
+        DeviceGuard guard(s0->device);
+        {
+                int device = -1;
+                if(j2p_device_of_pointer(out->data, &device) != J2P_OK || device != s0->device) {
+                        return fail(J2P_EINVAL, "to_tensor: data is not device memory of the solvers' device %d (managed and host memory are refused)", s0->device);
+                }
+        }
+        for(unsigned i = 1; i < nplane; i++) {
+                if(planes[i].solver != s0) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
+        }
+        const unsigned h = y1 - y0;
+        const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));
+        const TensorKernel kernel = kTensorKernels[nplane == 3 ? 0 : 1][out->dtype][path];
+        // a workgroup: 4 rows of 256 columns; grid-stride over rows from a grid of about 2048 workgroups, as k_to_samples'
+        const unsigned gx = (w + 255) / 256, row_groups = (h + 3) / 4;
+        const unsigned gy_cap = gx >= 2048 ? 1 : 2048 / gx;
+        const unsigned gy = row_groups < gy_cap ? row_groups : gy_cap;
+        hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2], w, h, o);
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_tensor: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_device_of_pointer(const void *p, int *device)
+{
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        if(hipPointerGetAttributes(&attr, p) != hipSuccess) {
+                (void)hipGetLastError();                 // (plain host memory is an error to some runtimes, "unregistered" to others)
+                return J2P_EINVAL;
+        }
+        if(attr.type != hipMemoryTypeDevice || attr.isManaged) { return J2P_EINVAL; }
+        *device = attr.device;
+        return J2P_OK;
+}
+
+int j2p_planes_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_tensor *out)
+{
+        return tensor_rows(planes, nplane, true, w, 0, h, out);
+}
+
+int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned row_begin, unsigned row_end,
+                              const j2p_tensor *out)
+{
+        return tensor_rows(planes, nplane, false, w, row_begin, row_end, out);
+}
+
 // block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
 // 1/sub_w x 1/sub_h of its resolution (k_quantise_blocks<sub_w, sub_h>): output block row r covers canvas rows
 // [8 * sub_h * r, 8 * sub_h * (r + 1)).  `whole`: called as a whole-canvas form, which band solvers refuse.
