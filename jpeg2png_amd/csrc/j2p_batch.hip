@@ -198,21 +198,19 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap)
                         ref[c].channel = at.channel;
                         JOB_TRY(e[at.solve].band(b, &ref[c].solver, &row0[c], &row1[c]));
                 }
-                if(d.out_bits) {
-                        const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
-                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;
+                if(d.out_bits || d.out_tensor.data) {
+                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;   // the band's image rows
                         if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
-                        uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
-                        if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, out)); }   // greyscale: one sample per pixel
-                        else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
-                        continue;
-                }
-                if(d.out_tensor.data) {
-                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;
-                        if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
+                        if(d.out_bits) {
+                                const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
+                                uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
+                                if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, out)); }   // greyscale: one sample per pixel
+                                else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
+                                continue;
+                        }
                         j2p_tensor rows = d.out_tensor;                  // the band's first row of it
-                        const size_t bytes = d.out_tensor.dtype == J2P_DTYPE_U8 ? 1 : (d.out_tensor.dtype == J2P_DTYPE_F32 ? 4 : 2);
-                        rows.data = static_cast<char *>(d.out_tensor.data) + (size_t)y0 * (size_t)(d.out_tensor.stride_y > 0 ? d.out_tensor.stride_y : 0) * bytes;
+                        const size_t row_bytes = (size_t)(d.out_tensor.stride_y > 0 ? d.out_tensor.stride_y : 0) * j2p_tensor_element_bytes(d.out_tensor.dtype);
+                        rows.data = static_cast<char *>(d.out_tensor.data) + (size_t)y0 * row_bytes;
                         JOB_TRY(j2p_planes_rows_to_tensor(ref, d.nchannel, d.out_w, y0, y1, &rows));
                         JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: complete, for any stream
                         continue;

@@ -17,6 +17,9 @@ int j2p_tiled_exchange_forced(void);
 // managed and unknown memory (j2p_solver.hip) — what tensor output checks its destination with
 int j2p_device_of_pointer(const void *p, int *device);
 
+// bytes of one tensor element of a J2P_DTYPE_* code (u8 1, f32 4, the 16-bit kinds 2)
+static inline unsigned j2p_tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ? 1 : (dtype == J2P_DTYPE_F32 ? 4 : 2); }
+
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
 // the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the

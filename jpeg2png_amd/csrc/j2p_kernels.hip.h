@@ -2727,11 +2727,27 @@ __global__ __launch_bounds__(256) void k_dct_blocks(float *blocks, size_t nblock
 // (1 << bits) / 256 in float and truncates to unsigned; the same here.
 // out: one byte per sample (bits == 8) or two, big-endian (bits == 16).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned to_sample(double v, float bitfactor)
+__device__ __forceinline__ float clamp_sample(double v)
 {
-        float x = (float)v;
-        x = (double)x > 255. ? 255.f : ((double)x < 0. ? 0.f : x);      // CLAMP(x, 0., 255.), png.c:15-17
-        return (unsigned)(x * bitfactor);
+        const float x = (float)v;
+        return (double)x > 255. ? 255.f : ((double)x < 0. ? 0.f : x);           // CLAMP(x, 0., 255.), png.c:15-17
+}
+
+// One pixel up to the clamp, for k_to_samples and k_to_tensor alike: put(k, x) gets the clamped float x of output channel k,
+// from the solved Y, Cb, Cr.  NPLANE 3: RGB.  NPLANE 1: greyscale — the same writer with Cb = Cr = 0, where R = G = B exactly
+// (yi + 0.0 and yi - 0.0 - 0.0 in double are yi), so the colour matrix is not evaluated and cbi / cri are not looked at.
+template <int NPLANE, typename Put>
+__device__ __forceinline__ void clamped_pixel(float y, float cbi, float cri, Put put)
+{
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
+        const float yi = (float)((double)y + 128.);                             // jpeg2png.c:158
+        if constexpr(NPLANE == 3) {
+                put(0, clamp_sample((double)yi + 1.402 * (double)cri));
+                put(1, clamp_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri));
+                put(2, clamp_sample((double)yi + 1.772 * (double)cbi));
+        } else {
+                put(0, clamp_sample((double)yi));
+        }
 }
 
 // the sample(s) of one pixel as big-endian bytes: one byte each (bits == 8) or two (bits == 16)
@@ -2749,28 +2765,20 @@ __device__ __forceinline__ void store_samples(uint8_t *out, size_t i, const unsi
         }
 }
 
-// NPLANE 3: RGB.  NPLANE 1: greyscale — the same writer with Cb = Cr = 0, where R = G = B = to_sample(yi) exactly
-// (yi + 0.0 and yi - 0.0 - 0.0 in double are yi), so the colour matrix is not evaluated and cbp / crp are not read.
-// out: NPLANE samples per pixel.
+// NPLANE 3: RGB.  NPLANE 1: greyscale, where cbp / crp are not read.  out: NPLANE samples per pixel.
 template <int NPLANE>
 __global__ __launch_bounds__(256) void k_to_samples(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
                                                     unsigned crs, unsigned w, unsigned h, unsigned bits, uint8_t *out)
 {
-        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
         const size_t n = (size_t)w * h;
         const float bitfactor = (float)((double)(1 << bits) / 256.);
         for(size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
                 const unsigned x = (unsigned)(i % w), y = (unsigned)(i / w);
-                const float yi = (float)((double)yp[(size_t)y * ys + x] + 128.);   // jpeg2png.c:158
+                const float yin = yp[(size_t)y * ys + x];
+                float cbi = 0.f, cri = 0.f;                                      // (one plane: not looked at)
+                if constexpr(NPLANE == 3) { cbi = cbp[(size_t)y * cbs + x]; cri = crp[(size_t)y * crs + x]; }
                 unsigned v[NPLANE];
-                if constexpr(NPLANE == 3) {
-                        const float cbi = cbp[(size_t)y * cbs + x], cri = crp[(size_t)y * crs + x];
-                        v[0] = to_sample((double)yi + 1.402 * (double)cri, bitfactor);
-                        v[1] = to_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri, bitfactor);
-                        v[2] = to_sample((double)yi + 1.772 * (double)cbi, bitfactor);
-                } else {
-                        v[0] = to_sample((double)yi, bitfactor);
-                }
+                clamped_pixel<NPLANE>(yin, cbi, cri, [&](int k, float x) { v[k] = (unsigned)(x * bitfactor); });
                 store_samples(out, i, v, bits);
         }
 }
@@ -2840,12 +2848,6 @@ __device__ __forceinline__ void store_words(void *p, const unsigned *v)
         else { *reinterpret_cast<unsigned *>(p) = v[0]; }
 }
 
-__device__ __forceinline__ float clamp_sample(double v)
-{
-        const float x = (float)v;
-        return (double)x > 255. ? 255.f : ((double)x < 0. ? 0.f : x);           // CLAMP(x, 0., 255.), png.c:15-17: to_sample's
-}
-
 // the rows of one lane: columns [x0, x0 + npix).  FULL: npix is 4 — a loop of its own, so that the compiler sees all four loaded
 // values used and keeps the 16-byte loads whole (with npix a run-time value in one loop it loads three floats and one)
 template <int NPLANE, int DTYPE, int LAYOUT, bool FULL>
@@ -2860,23 +2862,15 @@ __device__ __forceinline__ void tensor_lane_rows(const float *yp, unsigned ys, c
         for(unsigned y = blockIdx.y * 4 + (threadIdx.x >> 6); y < h; y += gridDim.y * 4) {
                 const float4 y4 = *reinterpret_cast<const float4 *>(yp + (size_t)y * ys + x0);
                 const float yin[4] = {y4.x, y4.y, y4.z, y4.w};
-                float v[NPLANE][4];
+                float4 cb4 = make_float4(0.f, 0.f, 0.f, 0.f), cr4 = cb4;                  // (one plane: not looked at)
                 if constexpr(NPLANE == 3) {
-                        const float4 cb4 = *reinterpret_cast<const float4 *>(cbp + (size_t)y * cbs + x0);
-                        const float4 cr4 = *reinterpret_cast<const float4 *>(crp + (size_t)y * crs + x0);
-                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
-#pragma unroll
-                        for(int p = 0; p < 4; p++) {
-                                const float yi = (float)((double)yin[p] + 128.);        // jpeg2png.c:158
-                                const float cbi = cbin[p], cri = crin[p];
-                                v[0][p] = clamp_sample((double)yi + 1.402 * (double)cri);
-                                v[1][p] = clamp_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri);
-                                v[2][p] = clamp_sample((double)yi + 1.772 * (double)cbi);
-                        }
-                } else {
-#pragma unroll
-                        for(int p = 0; p < 4; p++) { v[0][p] = clamp_sample((double)(float)((double)yin[p] + 128.)); }
+                        cb4 = *reinterpret_cast<const float4 *>(cbp + (size_t)y * cbs + x0);
+                        cr4 = *reinterpret_cast<const float4 *>(crp + (size_t)y * crs + x0);
                 }
+                const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+                float v[NPLANE][4];
+#pragma unroll
+                for(int p = 0; p < 4; p++) { clamped_pixel<NPLANE>(yin[p], cbin[p], crin[p], [&](int k, float x) { v[k][p] = x; }); }
                 unsigned e[NPLANE][4];
 #pragma unroll
                 for(int k = 0; k < NPLANE; k++) {

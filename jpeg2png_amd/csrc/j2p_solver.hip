@@ -2033,40 +2033,53 @@ int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
         return rc;
 }
 
-// rows [y0, y1) of the image from nplane (solver, channel) pairs on one device that all hold those canvas rows, through
-// k_to_samples: three -> RGB, one -> greyscale.  `whole`: called as a whole-canvas form, which band solvers refuse.
-static int convert_rows(const j2p_plane_ref *planes, int nplane, bool whole, unsigned w, unsigned y0, unsigned y1, unsigned bits,
-                        uint8_t *out_host)
+// What the conversions of solved planes start from: rows [y0, y1) x w columns of the image from nplane (3 or 1) (solver,
+// channel) pairs on one device that all hold those canvas rows.  Checks arguments and state, gives per plane the first of
+// those rows in xbuf[cur] and its stride in floats, and waits for the streams of the solvers other than planes[0].solver,
+// on whose stream the caller launches.  `whole`: called as a whole-canvas form, which band solvers refuse.  what: "to_rgb",
+// "to_grey" or "to_tensor", for the messages.
+static int resolve_rows(const char *what, const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1,
+                        const float *ptr[3], unsigned stride[3])
 {
-        const char *what = nplane == 3 ? "to_rgb" : "to_grey";
-        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
         if(w == 0 || y0 >= y1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
-        for(int i = 0; whole && i < nplane; i++) {
+        for(unsigned i = 0; whole && i < nplane; i++) {
                 if(planes[i].solver && !planes[i].solver->whole) {
                         return fail(J2P_ESTATE, "%s needs whole-canvas solvers (bands: j2p_planes_rows_%s)", what, what);
                 }
         }
-        const float *ptr[3] = {nullptr, nullptr, nullptr};
-        unsigned stride[3] = {0, 0, 0};
-        for(int i = 0; i < nplane; i++) {
+        for(unsigned i = 0; i < 3; i++) { ptr[i] = nullptr; stride[i] = 0; }
+        for(unsigned i = 0; i < nplane; i++) {
                 j2p_solver *s = planes[i].solver;
-                if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %d: bad solver/channel", i); }
+                if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
                 if(s->device != planes[0].solver->device) { return fail(J2P_EINVAL, "planes live on different devices"); }
                 if(s->W < w || y0 < s->row0 || y1 > s->row0 + s->rows) {
-                        return fail(J2P_EINVAL, "plane %d: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
+                        return fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
                                     s->row0, s->row0 + s->rows, s->W);
                 }
                 if(s->grad_done) { return fail(J2P_ESTATE, "%s between the two phases of an iteration", what); }
                 ptr[i] = s->ch[planes[i].channel].xbuf[s->cur] + (size_t)(kHalo + (y0 - s->row0)) * s->W;
                 stride[i] = s->W;
         }
+        DeviceGuard guard(planes[0].solver->device);
+        for(unsigned i = 1; i < nplane; i++) {
+                if(planes[i].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
+        }
+        return J2P_OK;
+}
+
+// rows [y0, y1) of the image as samples on the host, through k_to_samples: three planes -> RGB, one -> greyscale
+static int convert_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, unsigned bits,
+                        uint8_t *out_host)
+{
+        const char *what = nplane == 3 ? "to_rgb" : "to_grey";
+        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
+        const float *ptr[3];
+        unsigned stride[3];
+        if(const int rc = resolve_rows(what, planes, nplane, whole, w, y0, y1, ptr, stride); rc != J2P_OK) { return rc; }
         const unsigned h = y1 - y0;
         j2p_solver *s0 = planes[0].solver;
         DeviceGuard guard(s0->device);
-        for(int i = 1; i < nplane; i++) {
-                if(planes[i].solver != s0) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
-        }
         const size_t bytes = (size_t)w * h * (size_t)nplane * (bits / 8);
         void *dout = nullptr;
         size_t dout_bytes = 0;
@@ -2106,8 +2119,6 @@ int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row
 static_assert(J2P_DTYPE_U8 == kDtypeU8 && J2P_DTYPE_F16 == kDtypeF16 && J2P_DTYPE_BF16 == kDtypeBF16 && J2P_DTYPE_F32 == kDtypeF32,
               "the kernels' dtype codes are the header's");
 
-static unsigned tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ? 1 : (dtype == J2P_DTYPE_F32 ? 4 : 2); }
-
 // Which destination path the full groups of 4 pixels of a w-column image take — the only place that knows the rule.  A
 // vector path stores 4 elements at once, 16 / 8 / 4 bytes for f32 / 16-bit / u8, and needs every such store aligned to its
 // width: the first row's address, and (in elements) the row stride and — planar, three planes — the channel stride multiples
@@ -2116,7 +2127,7 @@ static unsigned tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ?
 // at a multiple of stride_y from its first row, so the bands of one image agree.
 static int tensor_path(unsigned w, unsigned nplane, int dtype, long long stride_c, long long stride_y, long long stride_x, uintptr_t address)
 {
-        const unsigned store_bytes = 4 * tensor_element_bytes(dtype);
+        const unsigned store_bytes = 4 * j2p_tensor_element_bytes(dtype);
         if(w < 4 || address % store_bytes != 0 || stride_y % 4 != 0) { return kTensorGeneric; }
         if(stride_x == 1 && (nplane == 1 || stride_c % 4 == 0)) { return kTensorPlanar; }
         if(nplane == 3 && stride_c == 1 && stride_x == 3) { return kTensorInterleaved; }
@@ -2150,33 +2161,18 @@ static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENS
 #undef J2P_TENSOR_ROW
 
 // rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
-// memory, through k_to_tensor; out->data is the element of row y0.  Argument and state checks of convert_rows, then the
-// tensor's own.  Asynchronous: the kernel is queued on planes[0].solver's stream and nothing waits for it.
+// memory, through k_to_tensor; out->data is the element of row y0.  Asynchronous: the kernel is queued on planes[0].solver's
+// stream and nothing waits for it.
 static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
 {
         if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
         if(nplane != 1 && nplane != 3) { return fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
-        if(w == 0 || y0 >= y1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
-        for(unsigned i = 0; whole && i < nplane; i++) {
-                if(planes[i].solver && !planes[i].solver->whole) {
-                        return fail(J2P_ESTATE, "to_tensor needs whole-canvas solvers (bands: j2p_planes_rows_to_tensor)");
-                }
-        }
-        const float *ptr[3] = {nullptr, nullptr, nullptr};
-        unsigned stride[3] = {0, 0, 0};
+        const float *ptr[3];
+        unsigned stride[3];
+        if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride); rc != J2P_OK) { return rc; }
         for(unsigned i = 0; i < nplane; i++) {
-                j2p_solver *s = planes[i].solver;
-                if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
-                if(s->device != planes[0].solver->device) { return fail(J2P_EINVAL, "planes live on different devices"); }
-                if(s->W < w || y0 < s->row0 || y1 > s->row0 + s->rows) {
-                        return fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
-                                    s->row0, s->row0 + s->rows, s->W);
-                }
-                if(s->grad_done) { return fail(J2P_ESTATE, "to_tensor between the two phases of an iteration"); }
-                ptr[i] = s->ch[planes[i].channel].xbuf[s->cur] + (size_t)(kHalo + (y0 - s->row0)) * s->W;
-                stride[i] = s->W;
                 // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
-                if(s->W % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
+                if(stride[i] % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
         }
         if(out->dtype != J2P_DTYPE_U8 && out->dtype != J2P_DTYPE_F16 && out->dtype != J2P_DTYPE_BF16 && out->dtype != J2P_DTYPE_F32) {
                 return fail(J2P_EINVAL, "to_tensor: unknown dtype %d", out->dtype);
@@ -2185,8 +2181,8 @@ static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole,
                 return fail(J2P_EINVAL, "to_tensor: strides (%td, %td, %td) must all be at least 1 element", out->stride_c, out->stride_y, out->stride_x);
         }
         if(!out->data) { return fail(J2P_EINVAL, "to_tensor: data is NULL"); }
-        if(reinterpret_cast<uintptr_t>(out->data) % tensor_element_bytes(out->dtype) != 0) {
-                return fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", tensor_element_bytes(out->dtype));
+        if(reinterpret_cast<uintptr_t>(out->data) % j2p_tensor_element_bytes(out->dtype) != 0) {
+                return fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", j2p_tensor_element_bytes(out->dtype));
         }
         TensorOut o;
         o.data = out->data;
@@ -2210,9 +2206,6 @@ static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole,
                 if(j2p_device_of_pointer(out->data, &device) != J2P_OK || device != s0->device) {
                         return fail(J2P_EINVAL, "to_tensor: data is not device memory of the solvers' device %d (managed and host memory are refused)", s0->device);
                 }
-        }
-        for(unsigned i = 1; i < nplane; i++) {
-                if(planes[i].solver != s0) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
         }
         const unsigned h = y1 - y0;
         const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));

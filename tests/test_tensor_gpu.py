@@ -37,11 +37,16 @@ def bf16_bits(t):
     return ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint16)
 
 
+def clamped(planes, w, h):
+    """the float32 values after the clamp (png.c:15-17), one array per output channel"""
+    return [np.where(v.astype(np.float64) > 255., np.float32(255), np.where(v.astype(np.float64) < 0., np.float32(0), v)).astype(np.float32)
+            for v in unclamped(planes, w, h)]
+
+
 def expected(planes, w, h, dtype, layout, scale=None, bias=None):
     """the tensor's bit patterns (uint8 / uint16 / uint32) from the downloaded planes: the header's definition, restated"""
     out = []
-    for k, v in enumerate(unclamped(planes, w, h)):
-        v = np.where(v.astype(np.float64) > 255., np.float32(255), np.where(v.astype(np.float64) < 0., np.float32(0), v)).astype(np.float32)
+    for k, v in enumerate(clamped(planes, w, h)):
         if dtype == "u8":
             out.append(v.astype(np.uint32).astype(np.uint8))
             continue
@@ -164,6 +169,45 @@ def test_u8_and_f32_tensors_are_the_8_and_16_bit_samples(torch_cuda, joint_420, 
     # and both agree with the restatement
     assert np.array_equal(bits(t8), expected(c.planes, W, H, "u8", "hwc"))
     assert np.array_equal(bits(t32), expected(c.planes, W, H, "f32", "hwc"))
+
+
+def expected_sample_bytes(planes, w, h, bits_):
+    """the sample forms' bytes from the downloaded planes (png.c:44-62): interleaved, one byte per sample or two, big-endian.
+    The float32 multiply by 256 is exact (a power of two, nothing near overflow)"""
+    if bits_ == 8:
+        return expected(planes, w, h, "u8", "hwc").tobytes()
+    return np.stack([(v * np.float32(256)).astype(np.float32).astype(np.uint32) for v in clamped(planes, w, h)], axis=2).astype(">u2").tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bits_", [8, 16])
+@pytest.mark.parametrize("which", ["rgb", "grey"])
+def test_sample_bytes_are_the_restatement(clamping_444, grey, which, bits_):
+    """The sample forms against numpy, so that the anchor above has an anchor of its own in this file: RGB with the clamp at
+    work and greyscale, 8 and 16 bits, widths with and without a w % 4 tail and narrower than 4, one row and more, and a
+    rows form that does not start at row 0.  64 sentinel bytes behind every output stay as they were."""
+    c = clamping_444 if which == "rgb" else grey
+    u, p, ref = ctypes.c_uint, ctypes.c_void_p, ctypes.POINTER(c.j._CPlaneRef)
+    name = "j2p_planes_to_rgb" if c.n == 3 else "j2p_planes_to_grey"
+    whole_form, rows_form = getattr(c.lib, name), getattr(c.lib, name.replace("planes_", "planes_rows_"))
+    whole_form.argtypes, rows_form.argtypes = [ref, u, u, u, p], [ref, u, u, u, u, p]
+
+    def check(w, y0, y1, call):
+        n = (y1 - y0) * w * c.n * (bits_ // 8)
+        out = np.full(n + 64, 0xa5, np.uint8)
+        assert call(out.ctypes.data) == 0, (w, y0, y1)
+        want = expected_sample_bytes(c.planes, w, y1, bits_)
+        assert out[:n].tobytes() == want[len(want) - n:], (w, y0, y1)
+        assert (out[n:] == 0xa5).all(), (w, y0, y1)
+
+    for w in (1, 3, 4, 5, 47, 48):
+        for h in (1, 31, 32):
+            check(w, 0, h, lambda data: whole_form(c.refs, w, h, bits_, data))
+    for w in (47, 48):
+        check(w, 16, 31, lambda data: rows_form(c.refs, w, 16, 31, bits_, data))
+    if which == "rgb" and bits_ == 8:
+        v = np.frombuffer(expected_sample_bytes(c.planes, W, H, 8), np.uint8)
+        assert (v == 0).any() and (v == 255).any() and len(np.unique(v)) > 16        # the clamp is at work in what was compared
 
 
 # ---- 2. the definition, with the clamp at work ----

@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Tensor output against sample output on one 4096x3072 4:2:0 image solved jointly:
-  kernels  k_to_tensor<3, dtype, layout> for u8 / f16 / bf16 / f32 in chw (planar stores) and hwc (interleaved stores), and
-           k_to_samples<3> at 8 bits, all from ONE `rocprofv3 --kernel-trace` run of this script's --kernels mode (a child
-           process of its own): median device time per launch, and the fraction of the 6.2 TB/s this part delivers that the
-           algorithmic bytes — 12 read + 3 x element size written per pixel — in that time are;
+  kernels  k_to_tensor<3, dtype, layout> for u8 / f16 / bf16 / f32 in chw (planar stores) and hwc (interleaved stores), the
+           u8 hwc tensor at width 4095 (row stride 12285: the generic stores), and the kernel behind the SAMPLE calls —
+           j2p_planes_to_rgb at 8 bits (widths 4096 and 4095) and 16 bits, j2p_planes_to_grey of a one-plane solver at 8 bits.
+           Two `rocprofv3 --kernel-trace` runs of this script, child processes of their own: --kernels (the tensor calls,
+           found by kernel name) and --samples (the sample calls and no other conversion, found by CALL: they are the last
+           launches of that process, in the order made — whatever the kernel behind them is called).  Median device time
+           per launch, and the fraction of the 6.2 TB/s this part delivers that the algorithmic bytes — 4 read per plane +
+           element size written per sample — in that time are;
   batch    images per second through Batch (three slots, outputs reused), f16 chw tensor jobs that stay on the GPU against
            bits=8 jobs that come down to the host, alternated in one process.
-Appends one JSON line per measurement to OUT (default profiles/tensor_probe.jsonl) and prints them.
-    python tools/tensor_probe.py [ITERATIONS] [ROUNDS] [OUT]"""
+Public API only, so the same file runs against any build that has tensor output.  Appends one JSON line per measurement to
+OUT (default profiles/tensor_probe.jsonl) and prints them; COMMIT, when given, goes into every line as "commit".
+    python tools/tensor_probe.py [ITERATIONS] [ROUNDS] [OUT] [COMMIT]"""
 import csv
 import ctypes
 import glob
@@ -34,11 +39,15 @@ DTYPES = {"u8": (0, 1), "f16": (1, 2), "bf16": (2, 2), "f32": (3, 4)}      # nam
 LAYOUTS = {"chw": 1, "hwc": 2}                                             # name -> k_to_tensor's LAYOUT (planar, interleaved)
 
 
+# the sample calls of --samples, in the order made: (name, planes, width, bits)
+SAMPLE_CALLS = [("j2p_planes_to_rgb", 3, W, 8), ("j2p_planes_to_rgb", 3, W - 1, 8), ("j2p_planes_to_rgb", 3, W, 16),
+                ("j2p_planes_to_grey", 1, W, 8)]
+
+
 def kernels_mode(launches):
-    """what the profiler wraps: every tensor kernel and the sample kernel, `launches` + 1 times each, from one solver"""
+    """what the profiler wraps: every tensor kernel, `launches` + 1 times each, from one solver"""
     import torch
     planes = synth.make_planes(W, H, "420", 50, seed=1240)
-    rgb = np.empty((H, W, 3), np.uint8)
     with j.Solver(planes, WEIGHT, [PWEIGHT] * 3, 1) as s:
         s.run(1)
         for name in DTYPES:
@@ -48,63 +57,110 @@ def kernels_mode(launches):
                 for _ in range(launches + 1):
                     s.to_tensor(W, H, layout=layout, out=t)
                     torch.cuda.synchronize()
-        refs = (j._CPlaneRef * 3)(*[j._CPlaneRef(s._h, c) for c in range(3)])
-        s._lib.j2p_planes_to_rgb.argtypes = [ctypes.POINTER(j._CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p]
+        t = torch.empty((H, W - 1, 3), dtype=torch.uint8, device="cuda:0")
         for _ in range(launches + 1):
-            if s._lib.j2p_planes_to_rgb(refs, W, H, 8, rgb.ctypes.data) != 0:
-                sys.exit("j2p_planes_to_rgb failed")
+            s.to_tensor(W - 1, H, layout="hwc", out=t)
+            torch.cuda.synchronize()
 
 
-if "--kernels" in sys.argv:
-    kernels_mode(int(sys.argv[2]))
-    sys.exit(0)
+def samples_mode(launches):
+    """what the profiler wraps: SAMPLE_CALLS, `launches` + 1 times each, after both solvers have run"""
+    planes = synth.make_planes(W, H, "420", 50, seed=1240)
+    lib = j.load_library()
+    for name in ("j2p_planes_to_rgb", "j2p_planes_to_grey"):
+        getattr(lib, name).argtypes = [ctypes.POINTER(j._CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p]
+    with j.Solver(planes, WEIGHT, [PWEIGHT] * 3, 1) as s, j.Solver(planes[:1], WEIGHT, [PWEIGHT], 1) as g:
+        s.run(1)
+        g.run(1)
+        s.sync()
+        g.sync()
+        for name, nplane, w, bits in SAMPLE_CALLS:
+            solver = s if nplane == 3 else g
+            refs = (j._CPlaneRef * nplane)(*[j._CPlaneRef(solver._h, c) for c in range(nplane)])
+            out = np.empty((H, w, nplane * bits // 8), np.uint8)
+            for _ in range(launches + 1):
+                if getattr(lib, name)(refs, w, H, bits, out.ctypes.data) != 0:
+                    sys.exit(f"{name} failed")
+
+
+for flag, mode in (("--kernels", kernels_mode), ("--samples", samples_mode)):
+    if flag in sys.argv:
+        mode(int(sys.argv[2]))
+        sys.exit(0)
 
 args = sys.argv[1:]
 its = int(args[0]) if args else 50
 rounds = int(args[1]) if len(args) > 1 else 3
 out_path = args[2] if len(args) > 2 else os.path.join(ROOT, "profiles", "tensor_probe.jsonl")
+commit = {"commit": args[3]} if len(args) > 3 else {}
 lines = []
 
 
 def emit(rec):
+    rec = {**commit, **rec}
     lines.append(rec)
     print(json.dumps(rec), flush=True)
 
 
-# ---- kernels: a profiled child process ----
+# ---- kernels: two profiled child processes ----
 rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
 if os.path.exists(rocprof):
     launches = 10
-    with tempfile.TemporaryDirectory() as tmp:
-        res = subprocess.run([rocprof, "--kernel-trace", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-                              os.path.abspath(__file__), "--kernels", str(launches)], capture_output=True, text=True, timeout=900, cwd=tmp)
-        if res.returncode != 0:
-            sys.exit("profiled run failed:\n" + res.stdout[-2000:] + res.stderr[-2000:])
-        durations = {}
-        for path in glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True):
-            with open(path, newline="") as f:
-                for row in csv.DictReader(f):
-                    name = row["Kernel_Name"].split("(")[0].replace(" ", "")
-                    durations.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
 
-    def kernel(name, element_bytes, **what):
-        d = [x for k, vs in durations.items() if k.endswith(name.replace(" ", "")) for x in vs][1:]        # (the first launch loads the code)
-        if not d:
-            sys.exit(f"no launch of {name} in the kernel trace")
-        us, nbytes = statistics.median(d), (12 + 3 * element_bytes) * W * H
-        emit({"what": "kernel", "kernel": name, **what, "image": f"{W}x{H}", "launches": len(d), "us_median": round(us, 2),
-              "us_min": round(min(d), 2), "us_max": round(max(d), 2), "bytes_per_pixel": 12 + 3 * element_bytes,
+    def trace(flag):
+        """(name, microseconds) of every kernel launch of the child process, in the order they started; the runtime's own
+        kernels (copies and fills) left out"""
+        with tempfile.TemporaryDirectory() as tmp:
+            res = subprocess.run([rocprof, "--kernel-trace", "--output-format", "csv", "-d", tmp, "--", sys.executable,
+                                  os.path.abspath(__file__), flag, str(launches)], capture_output=True, text=True, timeout=900, cwd=tmp)
+            if res.returncode != 0:
+                sys.exit("profiled run failed:\n" + res.stdout[-2000:] + res.stderr[-2000:])
+            rows = []
+            for path in glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True):
+                with open(path, newline="") as f:
+                    for row in csv.DictReader(f):
+                        name = row["Kernel_Name"].split("(")[0].replace(" ", "")
+                        if not name.startswith("__amd_rocclr"):
+                            rows.append((int(row["Start_Timestamp"]), name, (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3))
+        return [(name, us) for _, name, us in sorted(rows)]
+
+    def kernel(name, d, nplane, w, element_bytes, **what):
+        us, per_pixel = statistics.median(d), nplane * (4 + element_bytes)
+        nbytes = per_pixel * w * H
+        emit({"what": "kernel", "kernel": name, **what, "image": f"{w}x{H}", "launches": len(d), "us_median": round(us, 2),
+              "us_min": round(min(d), 2), "us_max": round(max(d), 2), "bytes_per_pixel": per_pixel,
               "TB_per_s": round(nbytes / us / 1e6, 3), "fraction_of_6.2_TB_per_s": round(nbytes / us / 1e6 / HBM_TBS, 3)})
         return us
 
+    tensor_launches = trace("--kernels")
+
+    def tensor_kernel(name, w, element_bytes, **what):
+        d = [us for k, us in tensor_launches if k.endswith(name.replace(" ", ""))][1:]     # (the first launch loads the code)
+        if not d:
+            sys.exit(f"no launch of {name} in the kernel trace")
+        return kernel(name, d, 3, w, element_bytes, **what)
+
+    tensor_us = {}
     for dtype, (code, nbytes) in DTYPES.items():
         for layout, path in LAYOUTS.items():
-            us = kernel(f"k_to_tensor<3, {code}, {path}>", nbytes, dtype=dtype, layout=layout)
-            if (dtype, layout) == ("u8", "hwc"):
-                u8_hwc = us
-    samples_us = kernel("k_to_samples<3>", 1, dtype="u8", layout="hwc (8-bit samples, then downloaded)")
-    emit({"what": "same bytes", "k_to_tensor<3, 0, 2>_us": round(u8_hwc, 2), "k_to_samples<3>_us": round(samples_us, 2),
-          "tensor_kernel_is_at_least_as_fast": bool(u8_hwc <= samples_us)})
+            tensor_us[dtype, layout, W] = tensor_kernel(f"k_to_tensor<3, {code}, {path}>", W, nbytes, dtype=dtype, layout=layout)
+    tensor_us["u8", "hwc", W - 1] = tensor_kernel("k_to_tensor<3, 0, 0>", W - 1, 1, dtype="u8", layout="hwc (generic stores)")
+
+    sample_launches = trace("--samples")[-len(SAMPLE_CALLS) * (launches + 1):]
+    if len(sample_launches) != len(SAMPLE_CALLS) * (launches + 1):
+        sys.exit("fewer kernel launches in the sample trace than sample calls")
+    sample_us = {}
+    for i, (call, nplane, w, bits) in enumerate(SAMPLE_CALLS):
+        group = sample_launches[i * (launches + 1):(i + 1) * (launches + 1)]
+        names = sorted({k for k, _ in group})
+        if len(names) != 1:
+            sys.exit(f"{call}: its launches are not of one kernel: {names}")
+        sample_us[nplane, w, bits] = kernel(names[0], [us for _, us in group][1:], nplane, w, bits // 8, call=f"{call}(w={w}, bits={bits})",
+                                            then="downloaded")
+    for w in (W, W - 1):
+        t, s = tensor_us["u8", "hwc", w], sample_us[3, w, 8]
+        emit({"what": "same bytes", "image": f"{w}x{H}", "u8_hwc_tensor_us": round(t, 2), "rgb8_samples_us": round(s, 2),
+              "tensor_kernel_is_at_least_as_fast": bool(t <= s)})
 else:
     emit({"what": "kernel", "unmeasured": "rocprofv3 not found"})
 
