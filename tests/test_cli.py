@@ -29,6 +29,21 @@ def make_jpeg(path, w, h, quality, subsampling, seed):
     Image.fromarray(rgb, "RGB").save(path, "JPEG", quality=quality, subsampling=subsampling)
 
 
+def make_flat_jpeg(path, w, h, quality, subsampling, content, seed):
+    """content "solid": one colour everywhere (DC-only blocks in all three components); "grey": a photograph with
+    R = G = B — synth_rgb's luma in all three channels — so Cb = Cr = 128 and every chroma coefficient is 0"""
+    from PIL import Image
+    from jpeg2png_amd import synth
+    if content == "solid":
+        rgb = np.empty((h, w, 3), np.uint8)
+        rgb[:] = (200, 60, 30)
+    else:
+        c = synth.synth_rgb(w, h, seed).astype(np.float64)
+        y = np.clip(np.rint(0.299 * c[:, :, 0] + 0.587 * c[:, :, 1] + 0.114 * c[:, :, 2]), 0, 255).astype(np.uint8)
+        rgb = np.repeat(y[:, :, None], 3, axis=2)
+    Image.fromarray(rgb, "RGB").save(path, "JPEG", quality=quality, subsampling=subsampling)
+
+
 def run(exe, *args):
     return subprocess.run([exe, *args], capture_output=True, text=True)
 
@@ -81,6 +96,11 @@ CASES = [
     ("420_separate", 160, 120, 10, 2, ["-s", "-i", "10,6,4", "-w", "0.3,0.1,0"]),
     ("422_tv_only", 120, 72, 50, 1, ["-i", "6", "-w", "0", "-p", "0.002"]),
     ("odd_size_420", 101, 67, 10, 2, ["-i", "7"]),
+    # flat and uniformly coloured images (make_flat_jpeg): a channel's gradient norm is 0 or tiny (tests/degenerate_cases.py)
+    ("solid_colour_joint", 101, 67, 30, 2, ["-i", "6"], "solid"),
+    ("solid_colour_separate", 160, 120, 30, 2, ["-s", "-i", "6"], "solid"),
+    ("grey_as_colour_joint_16bit", 160, 120, 10, 2, ["-i", "8", "-1"], "grey"),
+    ("grey_as_colour_separate", 101, 67, 10, 2, ["-s", "-i", "9,5,3"], "grey"),
 ]
 
 
@@ -89,9 +109,12 @@ CASES = [
 def test_png_identical_to_reference_program(cli, tmp_path, case):
     if not os.path.exists(REF_CLI):
         pytest.skip("oracle/_ref/jpeg2png_ref not built (needs /root/reference)")
-    name, w, h, q, sub, flags = case
+    name, w, h, q, sub, flags, *content = case
     jpg = tmp_path / "in.jpg"
-    make_jpeg(jpg, w, h, q, sub, seed=len(name))
+    if content:
+        make_flat_jpeg(jpg, w, h, q, sub, content[0], seed=len(name))
+    else:
+        make_jpeg(jpg, w, h, q, sub, seed=len(name))
     ref_png, gpu_png = tmp_path / "ref.png", tmp_path / "gpu.png"
     ref_csv, gpu_csv = tmp_path / "ref.csv", tmp_path / "gpu.csv"
     r = run(REF_CLI, str(jpg), "-o", str(ref_png), "-q", "-c", str(ref_csv), "-t", "1", *flags)

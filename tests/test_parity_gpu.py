@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import band_devices, bit_equal, make_case, psnr
+from jpeg2png_amd import J2P_OPT_MIXED_PROJECT, J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT
 
 pytestmark = pytest.mark.gpu
 
@@ -599,6 +600,25 @@ def test_joint_kernel_agrees_with_the_oracle(exp_lib, oracle):
         assert bit_equal(got[c].fdata, want[c]), f"channel {c}"
 
 
+# the schedule settings of test_every_schedule_switch_leaves_the_bits_alone (tests/test_degenerate_gpu.py runs its flat and
+# uniformly coloured planes through the same list)
+SCHEDULE_SETTINGS = [
+    {},                                                                             # the solver's own choice
+    {J2P_OPT_NORM_IN_PROJECT: 0, J2P_OPT_NORM_FOLD: 0},                             # stand-alone norm kernel
+    {J2P_OPT_NORM_IN_PROJECT: 0, J2P_OPT_NORM_FOLD: 1},                             # both levels inside k_gradient
+    {J2P_OPT_NORM_IN_PROJECT: 0, J2P_OPT_NORM_FOLD: 1, J2P_OPT_NT_GRADIENT: 2, J2P_OPT_MIXED_PROJECT: 0},
+    {J2P_OPT_NORM_FOLD: 1, J2P_OPT_NORM_IN_PROJECT: 1},                             # level 2 inside k_project, every wavefront
+    {J2P_OPT_NORM_FOLD: 1, J2P_OPT_NORM_IN_PROJECT: 2, J2P_OPT_MIXED_PROJECT: 0},   # ... the workgroup's first wavefront
+    {J2P_OPT_NORM_FOLD: 1, J2P_OPT_NORM_IN_PROJECT: 2, J2P_OPT_MIXED_PROJECT: 0, J2P_OPT_NT_GRADIENT: 3},
+    {J2P_OPT_NT_GRADIENT: 1},                                                       # what working sets beyond the Infinity Cache get:
+    {J2P_OPT_NT_GRADIENT: 2},                                                       # g / + prob state / + coefficients non-temporal
+    {J2P_OPT_NT_GRADIENT: 3},
+    {J2P_OPT_NT_GRADIENT: 3, J2P_OPT_NORM_IN_PROJECT: 0, J2P_OPT_NORM_FOLD: 0},
+    {J2P_OPT_MIXED_PROJECT: 0},                                                     # what a > 1 Mpixel canvas gets
+    {J2P_OPT_MIXED_PROJECT: 0, J2P_OPT_NORM_IN_PROJECT: 0, J2P_OPT_NORM_FOLD: 0},
+]
+
+
 @pytest.mark.parametrize("shape", [(520, 136, "420", False), (1000, 96, "444", True), (264, 200, "422", False)])
 def test_every_schedule_switch_leaves_the_bits_alone(exp_lib, oracle, shape, monkeypatch):
     """the J2P_OPT_* switches select schedules of the same arithmetic (where the norm is reduced, whether g is
@@ -611,22 +631,7 @@ def test_every_schedule_switch_leaves_the_bits_alone(exp_lib, oracle, shape, mon
     n = len(planes)
     its = 9
     want, _ = oracle.oracle_compute(planes, 0.3, [0.001] * n, its)
-    settings = [
-        {},                                                                         # the solver's own choice
-        {j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0},                     # stand-alone norm kernel
-        {j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 1},                     # both levels inside k_gradient
-        {j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NT_GRADIENT: 2, j.J2P_OPT_MIXED_PROJECT: 0},
-        {j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 1},                     # level 2 inside k_project, every wavefront
-        {j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 2, j.J2P_OPT_MIXED_PROJECT: 0},   # ... the workgroup's first wavefront
-        {j.J2P_OPT_NORM_FOLD: 1, j.J2P_OPT_NORM_IN_PROJECT: 2, j.J2P_OPT_MIXED_PROJECT: 0, j.J2P_OPT_NT_GRADIENT: 3},
-        {j.J2P_OPT_NT_GRADIENT: 1},                                                 # what working sets beyond the Infinity Cache get:
-        {j.J2P_OPT_NT_GRADIENT: 2},                                                 # g / + prob state / + coefficients non-temporal
-        {j.J2P_OPT_NT_GRADIENT: 3},
-        {j.J2P_OPT_NT_GRADIENT: 3, j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0},
-        {j.J2P_OPT_MIXED_PROJECT: 0},                                               # what a > 1 Mpixel canvas gets
-        {j.J2P_OPT_MIXED_PROJECT: 0, j.J2P_OPT_NORM_IN_PROJECT: 0, j.J2P_OPT_NORM_FOLD: 0},
-    ]
-    for opts in settings:
+    for opts in SCHEDULE_SETTINGS:
         with j.Solver(planes, 0.3, [0.001] * n, its) as s:
             for k, v in opts.items():
                 s.debug_option(k, v)
