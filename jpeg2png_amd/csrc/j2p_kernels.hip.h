@@ -653,15 +653,17 @@ __device__ __forceinline__ void div_n(const v2f (&x)[N], v2f d, v2f r, v2f (&q)[
 // true when one of the radicands of a lane's pixels MAY give a norm with an all-ones mantissa: such a norm is the root
 // of a radicand whose own mantissa ends in 0x7ffffe or 0x7fffff, so "the low 16 bits are >= 0xfffe" is necessary — one
 // row in ~120 trips of a wavefront, which then takes the unscreened (IEEE) path for that row; a few 16-bit maxima and
-// one compare per lane
+// one compare per lane.
+// Each pixel pair is cast to four 16-bit lanes AS A WHOLE (elements 0 and 2 are the low halves of .x and .y).  Written
+// element-wise — bit_cast(v2h, a.x) next to bit_cast(v2h, a.y) — hipcc 7.2 reuses .x for .y, as in sqrt_fast: the
+// compiled screen was max(low16(r1.x), low16(r2.x)) and never looked at the odd column of a lane's pair, so an
+// all-ones norm there stayed on the short division (found by the directed sites of tests/test_screens_gpu.py).
 __device__ __forceinline__ bool allones_candidate(v2f r1, v2f r2)
 {
-        typedef unsigned short v2h __attribute__((ext_vector_type(2)));
-        typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        const v2u a = __builtin_bit_cast(v2u, r1), b = __builtin_bit_cast(v2u, r2);
-        const v2h m = __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(v2h, a.x), __builtin_bit_cast(v2h, a.y)),
-                                                __builtin_elementwise_max(__builtin_bit_cast(v2h, b.x), __builtin_bit_cast(v2h, b.y)));
-        return m.x >= (unsigned short)0xfffe;
+        typedef unsigned short v4h __attribute__((ext_vector_type(4)));
+        const v4h m = __builtin_elementwise_max(__builtin_bit_cast(v4h, r1), __builtin_bit_cast(v4h, r2));
+        const unsigned short lo = m[0] > m[2] ? m[0] : m[2];
+        return lo >= (unsigned short)0xfffe;
 }
 
 // The four TGV2 numerators of a pixel (compute.c:165-182): s + gxx, gyy + s, s (its sign goes onto the quotient)
@@ -1289,7 +1291,9 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, v2f *xchg, const S
                                         source_prepare<TGV, !FREE>(GX[P], GY[P], GX[PM1], GY[PM1], m_hx, m_hy, prep);
                                 }
                                 bool slow = badmask != 0;
+#ifndef J2P_EXP_NO_ALLONES_SCREEN   // (fault injection, tests/test_screens_gpu.py: rows holding an all-ones norm stay on the short division and get WRONG BITS there — which the directed operands of tests/screen_cases.py must then notice)
                                 if constexpr(!LOG) { slow = slow || __builtin_amdgcn_ballot_w64(allones_candidate(prep.n1r, prep.n2r)) != 0; }
+#endif
                                 if(!slow) { source_finish<TGV, LOG, true>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
                                 else { source_finish<TGV, LOG, false>(GX[P], GY[P], prep, w_tv, w_tgv, log_row, tv_acc, tv2_acc, s); }
                         }
@@ -3065,6 +3069,16 @@ __device__ __forceinline__ float rnd_float(unsigned h, unsigned elo, unsigned eh
         const unsigned e = elo + (h >> 9) % (ehi - elo + 1);
         return __builtin_bit_cast(float, (h << 31) | (e << 23) | (mix32(h) & 0x7fffffu));
 }
+// which elements of two pixel pairs differ in their bits.  The pairs are cast AS WHOLES: written element-wise —
+// bit_cast(unsigned, a.x) != bit_cast(unsigned, b.x) next to the same for .y — hipcc 7.2 reuses .x for .y (see
+// allones_candidate), and the checks below compared only the even element of every pair, counting it twice.
+struct PairDiffers { bool x, y; };
+__device__ __forceinline__ PairDiffers bits_differ(v2f a, v2f b)
+{
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        const v2u d = __builtin_bit_cast(v2u, a) ^ __builtin_bit_cast(v2u, b);
+        return PairDiffers{d[0] != 0u, d[1] != 0u};
+}
 __global__ __launch_bounds__(256) void k_math_selftest(size_t n, unsigned seed, unsigned long long *mism /* [2] */)
 {
         unsigned long long bad_div = 0, bad_sqrt = 0;
@@ -3078,16 +3092,17 @@ __global__ __launch_bounds__(256) void k_math_selftest(size_t n, unsigned seed, 
                 if((h2 & 0xff) == 1) { x.y = d.y; }
                 const v2f q = div_shared(x, d, div_prepare(d));
                 const v2f qi = v2f{x.x / d.x, x.y / d.y};
-                bad_div += __builtin_bit_cast(unsigned, q.x) != __builtin_bit_cast(unsigned, qi.x) && !(q.x == 0.f && qi.x == 0.f);
-                bad_div += __builtin_bit_cast(unsigned, q.y) != __builtin_bit_cast(unsigned, qi.y) && !(q.y == 0.f && qi.y == 0.f);
+                const PairDiffers dq = bits_differ(q, qi);
+                bad_div += dq.x && !(q.x == 0.f && qi.x == 0.f);
+                bad_div += dq.y && !(q.y == 0.f && qi.y == 0.f);
                 // square roots: sums of squares in [2^-90, 2^90], or exactly 0, or perfect squares
                 v2f sx = v2f{fabsf(rnd_float(h1 ^ h2, 37, 217)), fabsf(rnd_float(h0 ^ h3, 37, 217))};
                 if((h0 & 0xff) == 0) { sx.x = 0.f; }
                 if((h1 & 0xff) == 1) { sx.y = d.y * d.y; }
                 const v2f sf = sqrt_fast(sx);
                 const v2f si = v2f{sqrtf(sx.x), sqrtf(sx.y)};
-                bad_sqrt += __builtin_bit_cast(unsigned, sf.x) != __builtin_bit_cast(unsigned, si.x);
-                bad_sqrt += __builtin_bit_cast(unsigned, sf.y) != __builtin_bit_cast(unsigned, si.y);
+                const PairDiffers ds = bits_differ(sf, si);
+                bad_sqrt += (int)ds.x + (int)ds.y;
                 // phase B's short division over its whole operand range: denominators in [2^-20, 2^26] with their IEEE
                 // reciprocal, numerators 0 or in [2^-100, 2^61)
                 {
@@ -3097,8 +3112,9 @@ __global__ __launch_bounds__(256) void k_math_selftest(size_t n, unsigned seed, 
                         if((h2 & 0xff) == 11) { nn.y = dd.y; }
                         const v2f qm = div_exact_recip(nn, dd, v2f{1.f / dd.x, 1.f / dd.y});
                         const v2f qi2 = v2f{nn.x / dd.x, nn.y / dd.y};
-                        bad_div += __builtin_bit_cast(unsigned, qm.x) != __builtin_bit_cast(unsigned, qi2.x) && !(qm.x == 0.f && qi2.x == 0.f);
-                        bad_div += __builtin_bit_cast(unsigned, qm.y) != __builtin_bit_cast(unsigned, qi2.y) && !(qm.y == 0.f && qi2.y == 0.f);
+                        const PairDiffers dm = bits_differ(qm, qi2);
+                        bad_div += dm.x && !(qm.x == 0.f && qi2.x == 0.f);
+                        bad_div += dm.y && !(qm.y == 0.f && qi2.y == 0.f);
                 }
                 // the norm -> reciprocal -> quotient chain of source_finish: root through v_rsq_f32, the reciprocal refined
                 // twice from that same v_rsq_f32 value (recip_exact), one-correction quotients against `/` by the IEEE root.
@@ -3109,8 +3125,8 @@ __global__ __launch_bounds__(256) void k_math_selftest(size_t n, unsigned seed, 
                         v2f nn, dd, rr;
                         norm_and_reciprocal<true, false>(rx, nn, dd, rr);
                         const v2f ni = v2f{rx.x == 0.f ? 0x1p-60f : sqrtf(rx.x), rx.y == 0.f ? 0x1p-60f : sqrtf(rx.y)};
-                        bad_sqrt += __builtin_bit_cast(unsigned, nn.x) != __builtin_bit_cast(unsigned, ni.x);
-                        bad_sqrt += __builtin_bit_cast(unsigned, nn.y) != __builtin_bit_cast(unsigned, ni.y);
+                        const PairDiffers dn = bits_differ(nn, ni);
+                        bad_sqrt += (int)dn.x + (int)dn.y;
                         // numerator = norm * a random factor in [2^-40, 2^2) (differences never exceed their norm by much)
                         v2f num = v2f{ni.x * rnd_float(h1 ^ h3, 87, 128), ni.y * rnd_float(h0 ^ h2, 87, 128)};
                         if((h1 & 0x7f) == 3) { num.x = 0.f; }
@@ -3119,8 +3135,9 @@ __global__ __launch_bounds__(256) void k_math_selftest(size_t n, unsigned seed, 
                         const bool skip = allones_candidate(rx + v2f{0x1p-120f, 0x1p-120f}, v2f{1.f, 1.f});
                         const v2f qs = div_exact_recip(num, dd, rr);
                         const v2f qd = v2f{num.x / ni.x, num.y / ni.y};
-                        bad_div += !skip && __builtin_bit_cast(unsigned, qs.x) != __builtin_bit_cast(unsigned, qd.x) && !(qs.x == 0.f && qd.x == 0.f);
-                        bad_div += !skip && __builtin_bit_cast(unsigned, qs.y) != __builtin_bit_cast(unsigned, qd.y) && !(qs.y == 0.f && qd.y == 0.f);
+                        const PairDiffers dd2 = bits_differ(qs, qd);
+                        bad_div += !skip && dd2.x && !(qs.x == 0.f && qd.x == 0.f);
+                        bad_div += !skip && dd2.y && !(qs.y == 0.f && qd.y == 0.f);
                 }
         }
         if(blockIdx.x == 0 && threadIdx.x == 0) {
@@ -3143,10 +3160,9 @@ __global__ __launch_bounds__(256) void k_sqrt_exhaustive(unsigned long long *mis
                 const v2f x = v2f{__builtin_bit_cast(float, (unsigned)(lo + 2 * i)), __builtin_bit_cast(float, (unsigned)(lo + 2 * i + 1))};
                 const v2f want = v2f{sqrtf(x.x), sqrtf(x.y)};
                 const v2f a = sqrt_rsq(x), b = sqrt_fast(x);
-                bad_rsq += (__builtin_bit_cast(unsigned, a.x) != __builtin_bit_cast(unsigned, want.x)) +
-                           (__builtin_bit_cast(unsigned, a.y) != __builtin_bit_cast(unsigned, want.y));
-                bad_fast += (__builtin_bit_cast(unsigned, b.x) != __builtin_bit_cast(unsigned, want.x)) +
-                            (__builtin_bit_cast(unsigned, b.y) != __builtin_bit_cast(unsigned, want.y));
+                const PairDiffers da = bits_differ(a, want), db = bits_differ(b, want);
+                bad_rsq += (int)da.x + (int)da.y;
+                bad_fast += (int)db.x + (int)db.y;
         }
         if(bad_rsq) { atomicAdd(&mism[0], bad_rsq); }
         if(bad_fast) { atomicAdd(&mism[1], bad_fast); }
@@ -3173,11 +3189,11 @@ __global__ __launch_bounds__(256) void k_recip_exhaustive(unsigned long long *mi
                 const v2f n = sqrt_rsq(x, seed);
                 const v2f r = recip_exact(n, seed);
                 const v2f want = v2f{1.f / n.x, 1.f / n.y};
-                const bool bx = __builtin_bit_cast(unsigned, r.x) != __builtin_bit_cast(unsigned, want.x);
-                const bool by = __builtin_bit_cast(unsigned, r.y) != __builtin_bit_cast(unsigned, want.y);
+                const PairDiffers dr = bits_differ(r, want);
+                const bool bx = dr.x, by = dr.y;
                 if(bx || by) {
                         const unsigned long long k = atomicAdd(&mism[0], (unsigned long long)bx + by);
-                        if(k < 8) { mism[1 + k] = __builtin_bit_cast(unsigned, bx ? x.x : x.y); }
+                        if(k < 8) { mism[1 + k] = (unsigned)(lo + 2 * i) + (bx ? 0u : 1u); }
                 }
                 bad += 0;
         }
@@ -3208,8 +3224,8 @@ __global__ __launch_bounds__(256) void k_div_exhaustive(unsigned first, unsigned
                 const v2f a = v2f{__builtin_bit_cast(float, 0x3f800000u + m), __builtin_bit_cast(float, 0x3f800000u + m + 1)};
                 const v2f q = div_exact_recip(a, n, r);
                 const v2f want = v2f{a.x / n.x, a.y / n.y};
-                const bool bx = __builtin_bit_cast(unsigned, q.x) != __builtin_bit_cast(unsigned, want.x);
-                const bool by = __builtin_bit_cast(unsigned, q.y) != __builtin_bit_cast(unsigned, want.y);
+                const PairDiffers dq = bits_differ(q, want);
+                const bool bx = dq.x, by = dq.y;
                 if(bx || by) {
                         bad += (unsigned long long)bx + by;
                         const unsigned long long k = atomicAdd(&mism[9], 1ull);
