@@ -456,6 +456,31 @@ int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, uns
 int j2p_debug_tensor_path(unsigned w, unsigned nplane, int dtype, ptrdiff_t stride_c, ptrdiff_t stride_y, ptrdiff_t stride_x,
                           uintptr_t data_address, int *path);
 
+/* Resized tensor output: the same elements, of a source rectangle (the box) of the w x h image, AREA-resampled to out_w x
+ * out_h — what a consumer's crop and downscale (Resize, CenterCrop, RandomResizedCrop) would compute from the full-size
+ * tensor, written straight into a slot of its batch.  Every bit is defined.  v_k(x, y) is the clamped float of channel k at
+ * image pixel (x, y), exactly as above.  Taps of output column X, in integers: lo = X * box_w, hi = (X + 1) * box_w; the source
+ * columns i = lo / out_w ... (hi - 1) / out_w of the box, with weights a_i = min(hi, (i + 1) * out_w) - max(lo, i * out_w)
+ * (1 <= a_i <= out_w, and they sum to box_w); rows likewise, with box_h, out_h and weights b_j.  An axis that is not resized
+ * (out_w == box_w) has one tap of weight 1 and no division.  In f32, every operation rounded on its own (never a fused
+ * multiply-add, never a reciprocal):
+ *     r_j = 0.f;  r_j = r_j + (float)a_i * v_k(box_x + i, box_y + j)      for i ascending
+ *     acc = 0.f;  acc = acc + (float)b_j * r_j                             for j ascending
+ *     m = acc;  x resized: m = m / (float)box_w;  y resized: m = m / (float)box_h;  m = min(m, 255.f)
+ * and channel k's element is made of m as above (u8 truncates; the float dtypes scale, add the bias and round).  A pure crop
+ * (out == box on both axes) therefore copies v_k, except that -0.f becomes +0.f.  Element (k, Y, X) goes to
+ * data + k * stride_c + Y * stride_y + X * stride_x, 0 <= X < out_w, 0 <= Y < out_h; nothing else is written, and canvas values
+ * outside the box are never used.  Only downscaling: enlarging is what zooming is for.
+ * Whole-canvas solvers only (a band solver: J2P_ESTATE).  The checks of j2p_planes_to_tensor, and J2P_EINVAL for r NULL, an
+ * empty box, a box that leaves the image, and out_w / out_h zero or larger than the box.  ASYNCHRONOUS on planes[0].solver's
+ * stream, as j2p_planes_to_tensor. */
+typedef struct j2p_resize {
+        unsigned box_x, box_y, box_w, box_h;   /* source rectangle, image pixels */
+        unsigned out_w, out_h;                  /* 1 <= out <= box on each axis */
+} j2p_resize;
+int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h,
+                                 const j2p_resize *r, const j2p_tensor *out);
+
 /* JPEG output: ONE (solver, channel) pair's current iterate as quantised DCT coefficients, ready for libjpeg's
  * jpeg_write_coefficients — no RGB conversion and no 8-bit samples in between.  For each 8x8 block of the canvas plane:
  * dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes), every coefficient divided by quant_table[j] as
@@ -561,6 +586,10 @@ void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset);
 int j2p_batch_create(j2p_batch **out, unsigned ndev, const int devices[], unsigned slots_per_device);
 void j2p_batch_destroy(j2p_batch *b);                       /* finishes queued jobs first */
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket);
+/* a tensor job whose tensor receives the image resized (j2p_planes_to_tensor_resized): *r is copied; job->out_tensor.data is
+ * required (J2P_EINVAL without), job->out_w x out_h stays the image's crop, which the box must lie inside, and the tensor has
+ * r->out_w x r->out_h elements per channel.  Not with `tile`, as every tensor job.  r == NULL: j2p_batch_submit. */
+int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket);
 int j2p_batch_wait(j2p_batch *b, int ticket);               /* the job's status; its error text in j2p_last_error() */
 
 /* test hook: n > 0: the n-th j2p_solver_run() / j2p_tiled_run() call from now on (any thread) fails with J2P_EDEVICE

@@ -55,6 +55,12 @@ class _CTensor(ctypes.Structure):
                 ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
 
 
+class _CResize(ctypes.Structure):
+    """j2p_resize: a source rectangle of the image and the size it is area-resampled to"""
+    _fields_ = [("box_x", ctypes.c_uint), ("box_y", ctypes.c_uint), ("box_w", ctypes.c_uint), ("box_h", ctypes.c_uint),
+                ("out_w", ctypes.c_uint), ("out_h", ctypes.c_uint)]
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -94,6 +100,7 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_grey", "j2p_planes_rows_to_grey", "j2p_planes_to_coefficients", "j2p_planes_rows_to_coefficients",
     "j2p_planes_to_coefficients_sub", "j2p_planes_rows_to_coefficients_sub",
     "j2p_planes_to_tensor", "j2p_planes_rows_to_tensor", "j2p_debug_tensor_path", "j2p_debug_job_layout",
+    "j2p_planes_to_tensor_resized", "j2p_batch_submit_resized",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -248,6 +255,9 @@ def _bind(path):
     lib.j2p_planes_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CTensor)]
     lib.j2p_planes_rows_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                               ctypes.POINTER(_CTensor)]
+    lib.j2p_planes_to_tensor_resized.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResize),
+                                                 ctypes.POINTER(_CTensor)]
+    lib.j2p_batch_submit_resized.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CResize), ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -403,6 +413,28 @@ def _c_tensor(t, nplane, width, height, layout, scale, bias, device=None):
     return _CTensor(t.data_ptr(), code, sc, sy, sx, (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias))
 
 
+def _c_resize(width, height, out_width, out_height, box):
+    """the j2p_resize of the keywords out_width / out_height / box of Solver.to_tensor and Batch.submit for a width x height
+    image: box (x, y, w, h) defaults to the whole image, a missing output size to the box's (a pure crop).  Refuses what the
+    library refuses (j2p_resize_error), before anything is allocated."""
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("tensor output needs width and height")
+    try:
+        bx, by, bw, bh = (0, 0, int(width), int(height)) if box is None else (int(v) for v in box)
+    except (TypeError, ValueError):
+        raise J2PError("resize: box must be (x, y, width, height)") from None
+    if bw < 1 or bh < 1:
+        raise J2PError("resize: empty box")
+    if bx < 0 or by < 0 or bx + bw > int(width) or by + bh > int(height):
+        raise J2PError(f"resize: the box {(bx, by, bw, bh)} leaves the {int(width)} x {int(height)} image")
+    ow, oh = bw if out_width is None else int(out_width), bh if out_height is None else int(out_height)
+    if ow < 1 or oh < 1:
+        raise J2PError("resize: empty output")
+    if ow > bw or oh > bh:
+        raise J2PError(f"resize: the output {ow} x {oh} is larger than the box {bw} x {bh} (enlarging is what zooming is for)")
+    return _CResize(bx, by, bw, bh, ow, oh)
+
+
 def _sampling(subsampling):
     """(sx, sy) of a coefficient output: 1 or 2 each"""
     try:
@@ -540,7 +572,8 @@ class Solver:
         _check(self._lib.j2p_solver_stream(self._h, ctypes.byref(p)))
         return p.value or 0
 
-    def to_tensor(self, width, height, dtype=None, layout="chw", scale=None, bias=None, out=None):
+    def to_tensor(self, width, height, dtype=None, layout="chw", scale=None, bias=None, out=None, out_width=None, out_height=None,
+                  box=None):
         """The solved image, cropped to width x height, as an RGB (three-channel solver) or greyscale (one-channel solver)
         torch.Tensor on the solver's GPU — (3|1, height, width) for layout "chw", (height, width, 3|1) for "hwc" — without
         leaving the device (j2p_planes_rows_to_tensor): png.c's colour conversion and clamp to [0, 255], then per channel
@@ -548,12 +581,22 @@ class Solver:
         bfloat16 (rounded to nearest even) or uint8 (the 8-bit samples; no scale / bias).  out: a tensor to write into, any
         view of that shape and dtype (a slot of a batch tensor, ...).  A band solver writes its own rows: height is then
         the band's row count and the rows are [row_begin, row_begin + height).
+        out_width, out_height, box=(x, y, w, h): the rectangle `box` of the width x height image (default: all of it),
+        area-resampled to out_width x out_height (default: the box's size, a pure crop; never larger than the box), is what
+        the tensor receives (j2p_planes_to_tensor_resized) — its shape is then (3|1, out_height, out_width) or the "hwc"
+        form.  Whole-canvas solvers only.  Without any of the three the call is what it was.
         Nothing waits on the host: the kernel is queued on the solver's stream and torch's current stream is made to wait
         for it, so torch operations issued afterwards see the finished tensor."""
+        resize = None
+        if out_width is not None or out_height is not None or box is not None:
+            resize = _c_resize(width, height, out_width, out_height, box)
         torch = _torch()
         if self.nch not in (1, 3):
             raise J2PError("tensor output needs a solver of three channels (RGB) or one (greyscale)")
         dev = torch.device("cuda", self.device)
+        image_width, image_height = width, height
+        if resize is not None:
+            width, height = resize.out_w, resize.out_h        # the tensor's
         if out is None:
             dtype = torch.float32 if dtype is None else dtype
             _tensor_dtype(torch, dtype)
@@ -568,7 +611,10 @@ class Solver:
         ours = torch.cuda.ExternalStream(self.stream(), device=dev)
         theirs = torch.cuda.current_stream(dev)
         ours.wait_stream(theirs)            # whatever torch still does with `out` (its allocation, a fill) comes first
-        _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
+        if resize is not None:
+            _check(self._lib.j2p_planes_to_tensor_resized(refs, self.nch, int(image_width), int(image_height), ctypes.byref(resize), ctypes.byref(ct)))
+        else:
+            _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
         theirs.wait_stream(ours)
         # `out` is now in use on torch's current stream, behind the kernel: an allocator that owns it for another stream must
         # not hand it out again before that.  (Recorded for THEIR stream, never for ours: the allocator records an event on
@@ -760,12 +806,15 @@ class Batch:
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
-               tensor=None, layout="chw", scale=None, bias=None):
+               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None):
         """tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
         GPU as that tensor's elements — shape (3|1, height, width) for layout "chw" or (height, width, 3|1) for "hwc", dtype
         uint8 / float16 / bfloat16 / float32, any view, with per-channel scale and bias as in Solver.to_tensor — by a worker
         of the tensor's GPU; wait() returns the tensor, complete for any stream.  What torch has queued for the tensor on its
         current stream is waited for before the job is queued;
+        out_width, out_height, box=(x, y, w, h) (with tensor= only): the tensor receives the rectangle `box` of the width x height
+        image (default: all of it) area-resampled to out_width x out_height (default: the box's size), as in Solver.to_tensor;
+        its shape is (3|1, out_height, out_width) or the "hwc" form, while width and height stay the image's;
         quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
         quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
         writer entropy-codes — instead of the float planes;
@@ -775,6 +824,11 @@ class Batch:
         tile_devices=(first, count): over that slice of the batch's device list only; on_progress(n): called from the worker
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
         n = len(planes)
+        resize = None
+        if out_width is not None or out_height is not None or box is not None:
+            if tensor is None:
+                raise J2PError("job: out_width, out_height and box belong to tensor output (tensor=)")
+            resize = _c_resize(width, height, out_width, out_height, box)
         job = _CJob()
         job.nchannel = n
         job.tile = 1 if tile else 0
@@ -802,7 +856,10 @@ class Batch:
                 raise J2PError("job: tensor output needs bits = 0")
             if out is not None:
                 raise J2PError("job: tensor output is written into `tensor`; out is for host arrays")
-            job.out_tensor = _c_tensor(tensor, n, width, height, layout, scale, bias)
+            if resize is not None:
+                job.out_tensor = _c_tensor(tensor, n, resize.out_w, resize.out_h, layout, scale, bias)
+            else:
+                job.out_tensor = _c_tensor(tensor, n, width, height, layout, scale, bias)
             job.out_w, job.out_h = int(width), int(height)
             # the workers' streams know nothing of torch's: what it has queued for this memory (a fill, the work of the
             # memory's previous owner) has to be over before a worker writes
@@ -867,7 +924,10 @@ class Batch:
             job.on_progress = cb
             keep = (keep, cb)                       # the trampoline lives as long as the job
         t = ctypes.c_int()
-        _check(self._lib.j2p_batch_submit(self._h, ctypes.byref(job), ctypes.byref(t)))
+        if resize is not None:
+            _check(self._lib.j2p_batch_submit_resized(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
+        else:
+            _check(self._lib.j2p_batch_submit(self._h, ctypes.byref(job), ctypes.byref(t)))
         self._pending[t.value] = (out, keep)
         return t.value
 

@@ -30,6 +30,8 @@ namespace {
 
 struct Job {
         j2p_job desc;
+        j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
+        bool resized = false;
         int ticket = 0;
         int device = -1;                    // tensor output: the tensor's device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -153,7 +155,8 @@ struct Engines {
 // Chunked when the caller watches (j2p_next_chunk), so that its bar and CSV keep moving.  `overlap`: the chunk of every
 // solve is issued before any of them is settled (sync, progress, done) — how the three solves of `-s` overlap on one GPU,
 // unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
-int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap)
+// resize (tensor jobs on one GPU only): the tensor receives the image resized.
+int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize)
 {
         const unsigned nsolve = solves(d);
         if(!d.on_rows && !d.on_progress) {
@@ -206,6 +209,12 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap)
                                 uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
                                 if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, out)); }   // greyscale: one sample per pixel
                                 else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
+                                continue;
+                        }
+                        if(resize) {
+                                // (never row-tiled: this one band is the whole canvas)
+                                JOB_TRY(j2p_planes_to_tensor_resized(ref, d.nchannel, d.out_w, d.out_h, resize, &d.out_tensor));
+                                JOB_TRY(j2p_solver_sync(ref[0].solver));
                                 continue;
                         }
                         j2p_tensor rows = d.out_tensor;                  // the band's first row of it
@@ -287,10 +296,10 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        return solve_and_deliver(d, eng.e, false);
+        return solve_and_deliver(d, eng.e, false, nullptr);
 }
 
-int run_job(const j2p_job &d, int device)
+int run_job(const j2p_job &d, int device, const j2p_resize *resize)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
@@ -298,7 +307,7 @@ int run_job(const j2p_job &d, int device)
                 JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k], &d.pweight[k],
                                           d.iterations[k], whole, 0));
         }
-        return solve_and_deliver(d, eng.e, true);
+        return solve_and_deliver(d, eng.e, true, resize);
 }
 
 void worker_main(j2p_batch *b, int device)
@@ -336,7 +345,7 @@ void worker_main(j2p_batch *b, int device)
                 }
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
-                        rc = run_job(job->desc, single);
+                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -347,6 +356,46 @@ void worker_main(j2p_batch *b, int device)
                 }
                 b->finished.notify_all();
         }
+}
+
+// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized
+int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
+{
+        if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(r) {
+                if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resized job needs tensor output (out_tensor)"); }
+                if(const char *why = j2p_resize_error(r, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+        }
+        Job *j = new(std::nothrow) Job();
+        if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
+        j->desc = *job;
+        if(r) {
+                j->resize = *r;
+                j->resized = true;
+        }
+        if(job->out_tensor.data) {
+                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor
+                int rc = validate_job(j->desc);
+                if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
+                        rc = j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
+                }
+                bool owned = false;
+                for(int dev : b->devices) { owned = owned || dev == j->device; }
+                if(rc == J2P_OK && !owned) { rc = j2p_fail(J2P_EINVAL, "job: the tensor lives on device %d, which this batch does not drive", j->device); }
+                if(rc != J2P_OK) { delete j; return rc; }
+        }
+        const bool pinned = j->device >= 0;
+        {
+                std::lock_guard<std::mutex> g(b->lock);
+                if(b->quit) { delete j; return j2p_fail(J2P_ESTATE, "batch is shutting down"); }
+                j->ticket = b->next_ticket++;
+                b->jobs[j->ticket] = j;
+                b->queue.push_back(j);
+                *ticket = j->ticket;
+        }
+        // (a pinned job may not be for the worker notify_one would wake)
+        if(pinned) { b->work.notify_all(); } else { b->work.notify_one(); }
+        return J2P_OK;
 }
 
 }  // namespace
@@ -395,33 +444,12 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        Job *j = new(std::nothrow) Job();
-        if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
-        j->desc = *job;
-        if(job->out_tensor.data) {
-                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor
-                int rc = validate_job(j->desc);
-                if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
-                        rc = j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
-                }
-                bool owned = false;
-                for(int dev : b->devices) { owned = owned || dev == j->device; }
-                if(rc == J2P_OK && !owned) { rc = j2p_fail(J2P_EINVAL, "job: the tensor lives on device %d, which this batch does not drive", j->device); }
-                if(rc != J2P_OK) { delete j; return rc; }
-        }
-        const bool pinned = j->device >= 0;
-        {
-                std::lock_guard<std::mutex> g(b->lock);
-                if(b->quit) { delete j; return j2p_fail(J2P_ESTATE, "batch is shutting down"); }
-                j->ticket = b->next_ticket++;
-                b->jobs[j->ticket] = j;
-                b->queue.push_back(j);
-                *ticket = j->ticket;
-        }
-        // (a pinned job may not be for the worker notify_one would wake)
-        if(pinned) { b->work.notify_all(); } else { b->work.notify_one(); }
-        return J2P_OK;
+        return submit(b, job, nullptr, ticket);
+}
+
+int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
+{
+        return submit(b, job, r, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

@@ -20,6 +20,18 @@ int j2p_device_of_pointer(const void *p, int *device);
 // bytes of one tensor element of a J2P_DTYPE_* code (u8 1, f32 4, the 16-bit kinds 2)
 static inline unsigned j2p_tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ? 1 : (dtype == J2P_DTYPE_F32 ? 4 : 2); }
 
+// what is wrong with a j2p_resize for a w x h image, or NULL: what j2p_planes_to_tensor_resized and j2p_batch_submit_resized
+// both refuse with J2P_EINVAL
+static inline const char *j2p_resize_error(const j2p_resize *r, unsigned w, unsigned h)
+{
+        if(!r) { return "resize is NULL"; }
+        if(r->box_w == 0 || r->box_h == 0) { return "resize: empty box"; }
+        if(r->box_x >= w || r->box_w > w - r->box_x || r->box_y >= h || r->box_h > h - r->box_y) { return "resize: the box leaves the image"; }
+        if(r->out_w == 0 || r->out_h == 0) { return "resize: empty output"; }
+        if(r->out_w > r->box_w || r->out_h > r->box_h) { return "resize: the output is larger than the box (enlarging is what zooming is for)"; }
+        return NULL;
+}
+
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
 // the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the

@@ -2938,6 +2938,262 @@ J2P_TENSOR_KERNELS(kDtypeF32)
 #undef J2P_TENSOR_KERNEL
 
 // ---------------------------------------------------------------------------
+// Resized tensor output: the clamped floats v_k of a source rectangle (the box) of the image, area-resampled to out_w x
+// out_h <= the box, as elements of the same strided tensor.  Every bit is defined (include/jpeg2png_amd.h):
+//   taps of output column X, in integers: lo = X * box_w, hi = lo + box_w; source columns i = lo / out_w .. (hi - 1) / out_w
+//   of the box with weights a_i = min(hi, (i + 1) * out_w) - max(lo, i * out_w); rows likewise with box_h, out_h, b_j.  An
+//   axis that is not resized has one tap of weight 1: the host passes its taps in the units (1, 1) and no divisor;
+//   r_j = 0.f; r_j = r_j + (float)a_i * v_k(box_x + i, box_y + j), i ascending;  acc = 0.f; acc = acc + (float)b_j * r_j,
+//   j ascending;  m = acc [/ (float)box_w] [/ (float)box_h] (the IEEE quotients), m = min(m, 255.f), and TensorElement of m.
+// Every operation rounded on its own (-ffp-contract=off, correctly rounded division, never a reciprocal).  The products
+// X * box_w are formed in 64 bits (a zoomed canvas is wider than 65535); what the tap walk carries is the tap's offset
+// i * out_w - lo, which lies in (-out_w, box_w) and fits an int.
+// MAPPING: a wavefront owns `rows` consecutive output rows of a tile of lanes x slots output columns, column X0 + p * lanes +
+// lane in slot p of its lane (neighbouring lanes: neighbouring columns, for the stores and for the LDS banks).  For every
+// source row of those output rows' footprint, in order, it goes left to right through the row segment its tile covers in chunks of
+// kResizeChunk columns: the lanes load the chunk with 16-byte loads (aligned DOWN to 4 floats: up to 3 columns left of the
+// box and what is right of the segment in its last group are converted and never looked at; the group lies inside the canvas
+// row as k_to_tensor's does), convert every pixel ONCE and stage the clamped channels in wave-private LDS; then every lane
+// walks those taps of its columns that lie in the chunk.  Chunks ascend, so every r_j is summed in the order above
+// whatever the tile and the chunk size are.  The LDS index is padded by one float per 32 (resize_lds_index): lanes read at a
+// stride of box_w / out_w floats, and with the pad the strides 2, 4, 8, 16 touch 32 distinct banks per 32-lane half, as the
+// four dword stores of the staging do (a lane's 4 floats are then no longer 16-byte aligned, but 4 conflict-free dword
+// stores cost the LDS the cycles of one 16-byte store).  No workgroup barrier: the 4 wavefronts of a workgroup (one above
+// the other in one tile, so that the source row two of them share is in L1 / L2 for the second) do not talk to each other.
+// Where two consecutive output rows of a wavefront share a source row, the second starts from the same r_j (acc = 0.f + b *
+// r_j): the row is read and converted once.  The loads of the next chunk are issued before the taps of this one are walked.
+// The tile is the host's choice (resize_tile in j2p_solver.hip): 256 columns and 8 rows where the output is large, down to
+// 32 columns and one row where it is small, so that a small output of a large image still gives every SIMD a wavefront or
+// two.
+// Element stores and generic strides only: the output is small next to the source that is read.
+// ---------------------------------------------------------------------------
+constexpr int kResizeChunk = 512;                                // source columns staged at a time (a multiple of 256)
+constexpr int kResizeSlots = 4;                                  // output columns per lane, at most
+constexpr int kResizeLds = kResizeChunk + kResizeChunk / 32;     // floats per staged channel
+
+struct ResizeGeom {
+        unsigned box_x, box_y;
+        unsigned tap_bw, tap_ow;        // the units of the x taps: (box_w, out_w), or (1, 1) where the axis is not resized
+        unsigned tap_bh, tap_oh;
+        unsigned qx, rx, qy, ry;        // tap_bw = qx * tap_ow + rx, tap_bh = qy * tap_oh + ry
+        unsigned qlanes, rlanes;        // lanes * tap_bw = qlanes * tap_ow + rlanes
+        unsigned out_w, out_h;
+        float div_x, div_y;             // (float)box_w, (float)box_h; 0.f: axis not resized, no division
+        unsigned lanes, slots;          // the tile: lanes (a power of two, 32 or 64) x slots (1..kResizeSlots) columns
+        unsigned rows;                  // consecutive output rows per wavefront
+};
+
+__device__ __forceinline__ int resize_lds_index(int i) { return i + (i >> 5); }
+
+// the taps of an output index of an axis: source indices [first, last] of the box, and rem with lo = first * ow + rem,
+// 0 <= rem < ow — the first tap's offset first * ow - lo is -rem
+struct ResizeTaps {
+        int first, last, rem;
+};
+// last = (lo + bw - 1) / ow without a division: with bw = q * ow + r that is first + q + floor((rem + r - 1) / ow), and
+// rem + r - 1 lies in [-1, 2 * ow - 2]
+__device__ __forceinline__ ResizeTaps resize_taps_from(int first, int rem, unsigned q, unsigned r, unsigned ow)
+{
+        const int t = rem + (int)r - 1;
+        ResizeTaps out;
+        out.first = first;
+        out.last = first + (int)q + (t >= (int)ow ? 1 : (t < 0 ? -1 : 0));
+        out.rem = rem;
+        return out;
+}
+// of index X, by a 64-bit division: once per wavefront and axis
+__device__ __forceinline__ ResizeTaps resize_taps(unsigned X, unsigned bw, unsigned ow, unsigned q, unsigned r)
+{
+        const unsigned long long lo = (unsigned long long)X * bw, first = lo / ow;
+        return resize_taps_from((int)first, (int)(lo - first * ow), q, r, ow);
+}
+// of the index `step` further on, where step * bw = qs * ow + rs
+__device__ __forceinline__ ResizeTaps resize_taps_step(const ResizeTaps &t, unsigned qs, unsigned rs, unsigned q, unsigned r, unsigned ow)
+{
+        int first = t.first + (int)qs, rem = t.rem + (int)rs;           // (rem < 2 * ow)
+        if(rem >= (int)ow) { rem -= (int)ow; first++; }
+        return resize_taps_from(first, rem, q, r, ow);
+}
+// the weight of the tap at offset off = i * ow - lo: min(hi, (i + 1) * ow) - max(lo, i * ow), both taken relative to lo
+__device__ __forceinline__ float resize_weight(int off, unsigned bw, unsigned ow)
+{
+        const int end = off + (int)ow;
+        return (float)((end < (int)bw ? end : (int)bw) - (off > 0 ? off : 0));
+}
+
+template <int NPLANE, int DTYPE>
+__global__ __launch_bounds__(256) void k_to_tensor_resized(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
+                                                           unsigned crs, ResizeGeom g, TensorOut o)
+{
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
+        static_assert(kResizeChunk % 256 == 0, "whole rounds of 64 lanes x 4 floats");
+        constexpr int kRounds = kResizeChunk / 256;
+        using E = TensorElement<DTYPE>;
+        using Raw = typename E::Raw;
+        __shared__ float stage[4][NPLANE][kResizeLds];
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned Yb = (blockIdx.y * 4 + (unsigned)wave) * g.rows;   // this wavefront's output rows: [Yb, Ye)
+        if(Yb >= g.out_h) { return; }                                    // (no workgroup barrier in this kernel)
+        const unsigned Ye = g.out_h - Yb < g.rows ? g.out_h : Yb + g.rows;
+        float (*const lds)[kResizeLds] = stage[wave];
+        const unsigned tile = g.lanes * g.slots;
+        const unsigned X0 = blockIdx.x * tile;                           // (the grid has no tile beyond out_w)
+        const unsigned ncol = g.out_w - X0 < tile ? g.out_w - X0 : tile;
+        // the taps of the lane's columns X0 + p * lanes + lane: from the tile's first column by steps, no division per column
+        // but one of 32 bits (lane * tap_bw < 64 * 2^18)
+        const ResizeTaps t0 = resize_taps(X0, g.tap_bw, g.tap_ow, g.qx, g.rx);
+        ResizeTaps tx[kResizeSlots];
+        bool has[kResizeSlots];
+        {
+                const unsigned lb = (unsigned)lane * g.tap_bw, ql = lb / g.tap_ow;
+                tx[0] = resize_taps_step(t0, ql, lb - ql * g.tap_ow, g.qx, g.rx, g.tap_ow);
+        }
+#pragma unroll
+        for(int p = 0; p < kResizeSlots; p++) {
+                if(p > 0) { tx[p] = resize_taps_step(tx[p - 1], g.qlanes, g.rlanes, g.qx, g.rx, g.tap_ow); }
+                has[p] = (unsigned)p < g.slots && (unsigned)lane < g.lanes && (unsigned)p * g.lanes + (unsigned)lane < ncol;
+        }
+        // the tile's segment of a source row, in canvas columns: [c_begin, c_last], c_begin a multiple of 4
+        const int c_last = (int)g.box_x + resize_taps(X0 + ncol - 1, g.tap_bw, g.tap_ow, g.qx, g.rx).last;
+        const int c_begin = ((int)g.box_x + t0.first) & ~3;
+        ResizeTaps ty = resize_taps(Yb, g.tap_bh, g.tap_oh, g.qy, g.ry);
+        const int j_end = resize_taps(Ye - 1, g.tap_bh, g.tap_oh, g.qy, g.ry).last;        // the last source row of these output rows
+        Raw *const data = static_cast<Raw *>(o.data);
+
+        // the 16-byte loads of chunk c0 of source row j, into registers: issued one chunk ahead of their use
+        float4 ld[kRounds][NPLANE];
+#pragma unroll
+        for(int u = 0; u < kRounds; u++) {
+#pragma unroll
+                for(int k = 0; k < NPLANE; k++) { ld[u][k] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        }
+        const auto issue = [&](int j, int c0) {
+                const size_t row = (size_t)g.box_y + (size_t)j;
+#pragma unroll
+                for(int u = 0; u < kRounds; u++) {
+                        const int c = c0 + u * 256 + lane * 4;
+                        if(c <= c_last) {
+                                ld[u][0] = *reinterpret_cast<const float4 *>(yp + row * ys + c);
+                                if constexpr(NPLANE == 3) {
+                                        ld[u][1] = *reinterpret_cast<const float4 *>(cbp + row * cbs + c);
+                                        ld[u][2] = *reinterpret_cast<const float4 *>(crp + row * crs + c);
+                                }
+                        }
+                }
+        };
+
+        unsigned Y = Yb;
+        float acc[kResizeSlots][NPLANE];
+#pragma unroll
+        for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                for(int k = 0; k < NPLANE; k++) { acc[p][k] = 0.f; }
+        }
+        int offy = -ty.rem;                                              // source row j's offset j * tap_oh - lo of output row Y
+        issue(ty.first, c_begin);
+        for(int j = ty.first;; j++) {
+                // r_j of every column of the lane: the row's chunks, left to right
+                float r[kResizeSlots][NPLANE];
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) { r[p][k] = 0.f; }
+                }
+                for(int c0 = c_begin; c0 <= c_last; c0 += kResizeChunk) {
+#pragma unroll
+                        for(int u = 0; u < kRounds; u++) {
+                                const int at = u * 256 + lane * 4;
+                                if(c0 + at <= c_last) {
+                                        const float yin[4] = {ld[u][0].x, ld[u][0].y, ld[u][0].z, ld[u][0].w};
+                                        const float4 cb4 = ld[u][NPLANE == 3 ? 1 : 0], cr4 = ld[u][NPLANE == 3 ? 2 : 0];   // (one plane: not looked at)
+                                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+#pragma unroll
+                                        for(int q = 0; q < 4; q++) {
+                                                const int idx = resize_lds_index(at + q);
+                                                clamped_pixel<NPLANE>(yin[q], cbin[q], crin[q], [&](int k, float x) { lds[k][idx] = x; });
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        // the next chunk's loads fly while this one's taps are walked
+                        if(c0 + kResizeChunk <= c_last) { issue(j, c0 + kResizeChunk); }
+                        else if(j < j_end) { issue(j + 1, c_begin); }
+                        const int rel0 = c0 - (int)g.box_x;              // the chunk's first column relative to the box (>= -3)
+#pragma unroll
+                        for(int p = 0; p < kResizeSlots; p++) {
+                                if(!has[p]) { continue; }
+                                const int i0 = tx[p].first > rel0 ? tx[p].first : rel0;
+                                const int i1 = tx[p].last < rel0 + kResizeChunk - 1 ? tx[p].last : rel0 + kResizeChunk - 1;
+                                if(i0 > i1) { continue; }                // none of this column's taps in this chunk
+                                int off = (i0 - tx[p].first) * (int)g.tap_ow - tx[p].rem;         // (< box_w + out_w)
+                                for(int i = i0; i <= i1; i++, off += (int)g.tap_ow) {
+                                        const float a = resize_weight(off, g.tap_bw, g.tap_ow);
+                                        const int idx = resize_lds_index(i - rel0);
+#pragma unroll
+                                        for(int k = 0; k < NPLANE; k++) {
+                                                const float t = a * lds[k][idx];
+                                                r[p][k] = r[p][k] + t;
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();                 // the next chunk is staged over this one
+                }
+                // output row Y takes the row with its weight; where the row is Y's last, Y is finished, and the next output
+                // row, if the row is its first (the one source row two output rows share), starts from the same r_j
+                const float b = resize_weight(offy, g.tap_bh, g.tap_oh);
+                offy += (int)g.tap_oh;
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) {
+                                const float t = b * r[p][k];
+                                acc[p][k] = acc[p][k] + t;
+                        }
+                }
+                if(j < ty.last) { continue; }
+                const long long rowo = (long long)Y * o.stride_y;
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+                        if(!has[p]) { continue; }
+                        const long long X = (long long)(X0 + (unsigned)p * g.lanes + (unsigned)lane);
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) {
+                                float m = acc[p][k];
+                                if(g.div_x != 0.f) { m = m / g.div_x; }
+                                if(g.div_y != 0.f) { m = m / g.div_y; }
+                                m = m < 255.f ? m : 255.f;
+                                data[(long long)k * o.stride_c + rowo + X * o.stride_x] = (Raw)E::make(m, o.scale[k], o.bias[k]);
+                        }
+                }
+                if(++Y == Ye) { break; }
+                ty = resize_taps_step(ty, g.qy, g.ry, g.qy, g.ry, g.tap_oh);
+                offy = -ty.rem;
+                const bool shared = ty.first == j;                      // (a resized axis has at least two taps: never also Y's last)
+                const float b2 = shared ? resize_weight(offy, g.tap_bh, g.tap_oh) : 0.f;
+                if(shared) { offy += (int)g.tap_oh; }
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) {
+                                const float t = b2 * r[p][k];
+                                acc[p][k] = 0.f + t;                      // (not shared: 0.f + 0.f * r_j, which is +0.f: r_j is finite and not negative)
+                        }
+                }
+        }
+}
+#define J2P_RESIZED_KERNELS(NPLANE)                                                                                                          \
+        template __global__ void k_to_tensor_resized<NPLANE, kDtypeU8>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);   \
+        template __global__ void k_to_tensor_resized<NPLANE, kDtypeF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);  \
+        template __global__ void k_to_tensor_resized<NPLANE, kDtypeBF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut); \
+        template __global__ void k_to_tensor_resized<NPLANE, kDtypeF32>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);
+J2P_RESIZED_KERNELS(3)
+J2P_RESIZED_KERNELS(1)
+#undef J2P_RESIZED_KERNELS
+
+// ---------------------------------------------------------------------------
 // JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,
 // each coefficient divided by its output quantisation step (IEEE f32 quotient: `/` under
 // -fhip-fp32-correctly-rounded-divide-sqrt, never a reciprocal multiply), rounded to nearest even, clamped to

@@ -2160,15 +2160,14 @@ static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENS
 #undef J2P_TENSOR_ROWS
 #undef J2P_TENSOR_ROW
 
-// rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
-// memory, through k_to_tensor; out->data is the element of row y0.  Asynchronous: the kernel is queued on planes[0].solver's
-// stream and nothing waits for it.
-static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
+// What both tensor outputs check before they launch, in this order: the arguments, the solvers' state and rows (resolve_rows),
+// the 16-byte alignment of the canvas rows, and the destination's dtype, strides, address, scale / bias and device.  Gives the
+// planes' first rows and strides and the kernels' view of the destination.
+static int tensor_resolve(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out,
+                          const float *ptr[3], unsigned stride[3], TensorOut &o)
 {
         if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
         if(nplane != 1 && nplane != 3) { return fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
-        const float *ptr[3];
-        unsigned stride[3];
         if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride); rc != J2P_OK) { return rc; }
         for(unsigned i = 0; i < nplane; i++) {
                 // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
@@ -2184,7 +2183,6 @@ static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole,
         if(reinterpret_cast<uintptr_t>(out->data) % j2p_tensor_element_bytes(out->dtype) != 0) {
                 return fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", j2p_tensor_element_bytes(out->dtype));
         }
-        TensorOut o;
         o.data = out->data;
         o.stride_c = out->stride_c;
         o.stride_y = out->stride_y;
@@ -2207,6 +2205,20 @@ static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole,
                         return fail(J2P_EINVAL, "to_tensor: data is not device memory of the solvers' device %d (managed and host memory are refused)", s0->device);
                 }
         }
+        return J2P_OK;
+}
+
+// rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
+// memory, through k_to_tensor; out->data is the element of row y0.  Asynchronous: the kernel is queued on planes[0].solver's
+// stream and nothing waits for it.
+static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
+{
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o;
+        if(const int rc = tensor_resolve(planes, nplane, whole, w, y0, y1, out, ptr, stride, o); rc != J2P_OK) { return rc; }
+        j2p_solver *s0 = planes[0].solver;
+        DeviceGuard guard(s0->device);
         const unsigned h = y1 - y0;
         const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));
         const TensorKernel kernel = kTensorKernels[nplane == 3 ? 0 : 1][out->dtype][path];
@@ -2242,6 +2254,74 @@ int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, uns
                               const j2p_tensor *out)
 {
         return tensor_rows(planes, nplane, false, w, row_begin, row_end, out);
+}
+
+// ---- resized tensor output: k_to_tensor_resized ----
+using ResizedKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);
+#define J2P_RESIZED_ROW(NPLANE) \
+        {k_to_tensor_resized<NPLANE, kDtypeU8>, k_to_tensor_resized<NPLANE, kDtypeF16>, k_to_tensor_resized<NPLANE, kDtypeBF16>, k_to_tensor_resized<NPLANE, kDtypeF32>}
+static const ResizedKernel kResizedKernels[2][4] = {J2P_RESIZED_ROW(3), J2P_RESIZED_ROW(1)};            // [three planes / one][dtype]
+#undef J2P_RESIZED_ROW
+
+// The tile of k_to_tensor_resized — output columns and consecutive output rows per wavefront — the only place that knows the
+// rule.  256 columns (64 lanes x 4) make a wavefront's source segment at least as long as k_to_tensor's 256 pixels at any
+// ratio; but a small output of a large image has few such tiles and every one of them a long footprint, so the tile is
+// halved while the chip (256 CUs x 4 SIMDs) would get fewer than two wavefronts per SIMD — not below 32 columns: the lanes
+// beyond the tile's columns only load and convert, they walk no taps.  Rows: a wavefront that owns several consecutive
+// output rows reads and converts the source row that two of them share once instead of twice (at ratios just above 1
+// that is every row) and spreads its set-up over them; up to 8, as long as about four wavefronts per SIMD remain.
+// Same bits for every tile: a column's sums do not depend on which lane or wavefront forms them.
+static void resize_tile(unsigned out_w, unsigned out_h, unsigned *lanes, unsigned *slots, unsigned *rows)
+{
+        unsigned tile = 64 * kResizeSlots;
+        while(tile > 32 && (unsigned long long)((out_w + tile - 1) / tile) * out_h < 2048) { tile /= 2; }
+        *lanes = tile < 64 ? tile : 64;
+        *slots = tile / *lanes;
+        const unsigned long long tiles = (out_w + tile - 1) / tile;
+        unsigned r = 8;
+        while(r > 1 && tiles * ((out_h + r - 1) / r) < 4096) { r /= 2; }
+        while(((out_h + r - 1) / r + 3) / 4 > 65535) { r *= 2; }                // (what a grid's y dimension may be)
+        *rows = r;
+}
+
+int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_resize *r,
+                                 const j2p_tensor *out)
+{
+        if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_resize_error(r, w, h)) { return fail(J2P_EINVAL, "to_tensor: %s", why); }
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o;
+        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o); rc != J2P_OK) { return rc; }
+        j2p_solver *s0 = planes[0].solver;
+        DeviceGuard guard(s0->device);
+        ResizeGeom g;
+        g.box_x = r->box_x;
+        g.box_y = r->box_y;
+        const bool rx = r->out_w != r->box_w, ry = r->out_h != r->box_h;        // an axis that is not resized: one tap of weight 1
+        g.tap_bw = rx ? r->box_w : 1;
+        g.tap_ow = rx ? r->out_w : 1;
+        g.tap_bh = ry ? r->box_h : 1;
+        g.tap_oh = ry ? r->out_h : 1;
+        g.out_w = r->out_w;
+        g.out_h = r->out_h;
+        g.div_x = rx ? (float)r->box_w : 0.f;
+        g.div_y = ry ? (float)r->box_h : 0.f;
+        resize_tile(r->out_w, r->out_h, &g.lanes, &g.slots, &g.rows);
+        // what lets the kernel step from one column's taps to the next without dividing
+        g.qx = g.tap_bw / g.tap_ow;
+        g.rx = g.tap_bw % g.tap_ow;
+        g.qy = g.tap_bh / g.tap_oh;
+        g.ry = g.tap_bh % g.tap_oh;
+        g.qlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw / g.tap_ow);
+        g.rlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw % g.tap_ow);
+        // a workgroup: 4 wavefronts, one above the other, of one tile
+        const unsigned tile = g.lanes * g.slots, gx = (r->out_w + tile - 1) / tile, gy = ((r->out_h + g.rows - 1) / g.rows + 3) / 4;
+        hipLaunchKernelGGL(kResizedKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(gx, gy), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1],
+                           stride[1], ptr[2], stride[2], g, o);
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_tensor_resized: %s", hipGetErrorString(e)); }
+        return J2P_OK;
 }
 
 // block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
