@@ -37,8 +37,25 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-HIP_UNITS = ("j2p_solver.hip", "j2p_tiled.hip", "j2p_batch.hip")
-HEADERS = ("j2p_kernels.hip.h", "j2p_internal.h")
+# every translation unit with the project headers it includes, directly or through another: what an edit rebuilds
+UNIT_HEADERS = {
+    "j2p_solver.hip": ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
+    "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
+    "j2p_tiled.hip": ("j2p_internal.h",),
+    "j2p_batch.hip": ("j2p_internal.h",),
+    "compute_host.c": ("j2p_internal.h",),
+}
+HIP_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".hip"))
+# the units that hold device code (the others are host code).  Only the solver's knows -DJ2P_DEBUG, -DJ2P_TRACE and
+# -DJ2P_EXP_*: the checked build and the A/B variants compile it alone and take every other object from the release build
+DEVICE_UNITS = ("j2p_solver.hip", "j2p_output.hip")
+PUBLIC_HEADERS = ("jpeg2png_amd.h", "jpeg2png_amd_compute.h")
+
+
+def _deps(unit):
+    """the files whose change rebuilds a unit's object"""
+    return ([os.path.join(CSRC, unit)] + [os.path.join(CSRC, h) for h in UNIT_HEADERS[unit]] +
+            [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS] + [os.path.abspath(__file__)])
 
 
 def _run(cmd, verbose):
@@ -53,25 +70,19 @@ def _run(cmd, verbose):
 
 
 def build(force=False, verbose=False):
-    units = [u for u in HIP_UNITS if os.path.exists(os.path.join(CSRC, u))]
-    common = [os.path.join(CSRC, f) for f in HEADERS]
-    common += [os.path.join(INCLUDE, f) for f in ("jpeg2png_amd.h", "jpeg2png_amd_compute.h")]
-    common.append(os.path.abspath(__file__))
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     gcc = shutil.which("gcc") or "gcc"
     objs = []
     extra = os.environ.get("J2P_CXXFLAGS", "").split()
     jobs = []
-    for u in units:
+    for u in HIP_UNITS:
         src, obj = os.path.join(CSRC, u), os.path.join(CSRC, u.replace(".hip", ".o"))
         objs.append(obj)
-        # only j2p_solver.hip holds device code (it includes the kernels header); the others are host code
-        deps = [src] + (common if u == "j2p_solver.hip" else common[1:])
-        if force or _newer(obj, deps):
+        if force or _newer(obj, _deps(u)):
             jobs.append([hipcc, *HIP_FLAGS, *extra, "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj])
     csrc, cobj = os.path.join(CSRC, "compute_host.c"), os.path.join(CSRC, "compute_host.o")
     objs.append(cobj)
-    if force or _newer(cobj, [csrc] + common[1:]):
+    if force or _newer(cobj, _deps("compute_host.c")):
         jobs.append([gcc, "-std=c11", "-O2", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-I", INCLUDE, "-c", csrc, "-o", cobj])
     if not jobs and not _newer(LIB, objs):
         return LIB
@@ -90,14 +101,13 @@ DEBUG_LIB = os.path.join(HERE, "libjpeg2png_amd_debug.so")
 def build_debug(force=False, verbose=False):
     """The checked build (-DJ2P_DEBUG): every global access of the two phase kernels is compared with the range
     it is meant to stay in, the counterpart of the reference's DEBUG=1 build with its asserting pixel indexer
-    (utils.h:68-81).  Same sources; only the device translation unit is compiled a second time.  Loaded with
+    (utils.h:68-81).  Same sources; only the solver's translation unit is compiled a second time.  Loaded with
     J2P_LIBRARY=<this file> (tests/test_debug_build_gpu.py, tools/debug_sweep.py)."""
     build(force=False, verbose=verbose)             # the host-only objects are shared with the release build
     src = os.path.join(CSRC, "j2p_solver.hip")
     obj = os.path.join(CSRC, "j2p_solver_debug.o")
-    deps = [src] + [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(INCLUDE, "jpeg2png_amd.h"), os.path.abspath(__file__)]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if force or _newer(obj, deps):
+    if force or _newer(obj, _deps("j2p_solver.hip")):
         _run([hipcc, *HIP_FLAGS, "-DJ2P_DEBUG", "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj], verbose)
     objs = [obj] + [os.path.join(CSRC, u.replace(".hip", ".o")) for u in HIP_UNITS if u != "j2p_solver.hip"]
     objs.append(os.path.join(CSRC, "compute_host.o"))
@@ -115,19 +125,20 @@ def build_experiments(force=False, verbose=False):
     direction, where the norm is finished, ... (j2p_internal.h: j2p_exp_env) — and the split phases.  Same device code as
     the release build.  What the schedule-equivalence tests load (conftest.exp_lib)
     and the timing tools run on (J2P_LIBRARY=<this file>); never what a user of the library gets."""
-    build(force=False, verbose=verbose)             # compute_host.o is shared
+    build(force=False, verbose=verbose)             # compute_host.o and j2p_output.o, which have no knobs, are shared
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    common = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(INCLUDE, "jpeg2png_amd.h"), os.path.abspath(__file__)]
     # (the objects do not travel with a gpurun lease, the library does: up to date against the SOURCES is enough)
-    sources = [os.path.join(CSRC, u) for u in HIP_UNITS] + common + [os.path.join(CSRC, "compute_host.c")]
+    sources = {f for u in UNIT_HEADERS for f in _deps(u)}
     if not force and os.path.exists(EXP_LIB) and not _newer(EXP_LIB, sources):
         return EXP_LIB
     jobs, objs = [], []
     for u in HIP_UNITS:
+        if u == "j2p_output.hip":
+            objs.append(os.path.join(CSRC, "j2p_output.o"))
+            continue
         src, obj = os.path.join(CSRC, u), os.path.join(CSRC, u.replace(".hip", "_exp.o"))
         objs.append(obj)
-        deps = [src] + (common if u == "j2p_solver.hip" else common[1:])
-        if force or _newer(obj, deps):
+        if force or _newer(obj, _deps(u)):
             jobs.append([hipcc, *HIP_FLAGS, "-DJ2P_EXPERIMENTS", "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj])
     objs.append(os.path.join(CSRC, "compute_host.o"))
     if jobs or _newer(EXP_LIB, objs):

@@ -14,7 +14,7 @@ void j2p_set_last_error(const char *msg);
 // solve on one GPU (j2p_tiled.hip)
 int j2p_tiled_exchange_forced(void);
 // the device whose plain device memory p points into (hipPointerGetAttributes); J2P_EINVAL without an error text for host,
-// managed and unknown memory (j2p_solver.hip) — what tensor output checks its destination with
+// managed and unknown memory (j2p_output.hip) — what tensor output checks its destination with
 int j2p_device_of_pointer(const void *p, int *device);
 
 // bytes of one tensor element of a J2P_DTYPE_* code (u8 1, f32 4, the 16-bit kinds 2)
@@ -62,6 +62,8 @@ static inline unsigned j2p_next_chunk(unsigned done, unsigned left, double elaps
 #ifdef __cplusplus
 }  // extern "C"
 
+#include <hip/hip_runtime_api.h>     // hipStream_t, hipError_t: every C++ unit of the library is a HIP unit
+
 // Environment knobs of the EXPERIMENTS build (-DJ2P_EXPERIMENTS: jpeg2png_amd/libjpeg2png_amd_exp.so, built by
 // buildlib.build_experiments() for the schedule-equivalence tests and the timing tools): the switches that move choices
 // AMONG the release kernels (rows per strip, item shares, launch direction, where the norm is finished, ...) and the
@@ -80,6 +82,26 @@ static inline const char *j2p_exp_env(const char *name)
 
 // error text of the calling thread (what j2p_last_error() returns); returns `code`
 int j2p_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// ---- what the output stage (j2p_output.hip) sees of a solver; defined in j2p_solver.hip ----
+// The solver's place and state as far as converting its planes needs them.  A copy: valid until the solver is next used.
+struct j2p_solver_view {
+        int device;
+        hipStream_t stream;
+        unsigned nch;
+        unsigned W, H;                  // the canvas
+        unsigned row0, rows;            // the canvas rows this solver holds: [row0, row0 + rows)
+        bool whole;                     // ... which are all of them (not a band)
+        bool mid_iteration;             // between the two phases of an iteration: the planes are not an iterate
+};
+j2p_solver_view j2p_solver_view_of(const j2p_solver *s);         // s is not NULL
+// the device address of canvas row y (one of the solver's own) of channel c in the current iterate; the rows after it follow
+// at a stride of W floats.  Hides the halo as j2p_solver_plane_ptr does.
+int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **row);
+// the device-memory pool of j2p_solver.hip, for buffers that live as long as one call: at least `bytes` bytes on `device`,
+// *got the size to give back with
+hipError_t j2p_pool_take(int device, size_t bytes, void **out, size_t *got);
+void j2p_pool_give(int device, void *ptr, size_t bytes);
 
 // log rows from per-iteration sums like j2p_log_rows_from_sums(), but continuing a run: carried[] holds the prob
 // distance per channel of the state entering the first of the n iterations and is updated (all 0 at iteration 0);

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "j2p_internal.h"          // J2P_NORM_TREE_ROWS
+#include "j2p_dct.hip.h"           // fdct8, idct8, transpose8: shared with j2p_output_kernels.hip.h
 
 namespace j2p {
 
@@ -109,108 +110,6 @@ __device__ __forceinline__ void trace_put(unsigned long long *buf, unsigned cap,
         r->id = ((unsigned long long)tag << 56) | ((unsigned long long)(seq & 0xffffffu) << 32) | trace_hwid();
 }
 #endif
-
-// ---------------------------------------------------------------------------
-// 8-point orthonormal DCT-II / DCT-III, one lane owns the whole 8-vector.
-// ---------------------------------------------------------------------------
-// sqrt(2/8)*cos(k*pi/16), sqrt(2/8)*sin(k*pi/16), and cos(pi/4) — the values of
-// ooura/dct.c:24-31, kept as double so that products promote like the reference.
-constexpr double K1c = 0.49039264020161522456, K1s = 0.09754516100806413392;
-constexpr double K2c = 0.46193976625564337806, K2s = 0.19134171618254488586;
-constexpr double K3c = 0.41573480615127261854, K3s = 0.27778511650980111237;
-constexpr double K4 = 0.35355339059327376220, KH = 0.70710678118654752440;
-
-__device__ __forceinline__ float mix_add(double ka, float a, double kb, float b)
-{
-        return (float)(ka * (double)a + kb * (double)b);
-}
-__device__ __forceinline__ float mix_sub(double ka, float a, double kb, float b)
-{
-        return (float)(ka * (double)a - kb * (double)b);
-}
-__device__ __forceinline__ float scale(double k, float a) { return (float)(k * (double)a); }
-
-// one pass of dct8x8s (ooura/dct.c:103-130)
-__device__ __forceinline__ void fdct8(float (&v)[8])
-{
-        float e0 = v[0] + v[7], o0 = v[0] - v[7];
-        float e1 = v[2] + v[5], o1 = v[2] - v[5];
-        float e2 = v[4] + v[3], o2 = v[4] - v[3];
-        float e3 = v[6] + v[1], o3 = v[6] - v[1];
-        float p = e0 + e2, q = e1 + e3;
-        v[0] = scale(K4, p + q);
-        v[4] = scale(K4, p - q);
-        p = e0 - e2;
-        q = e1 - e3;
-        v[2] = mix_sub(K2c, p, K2s, q);
-        v[6] = mix_add(K2c, q, K2s, p);
-        float r = scale(KH, o1 - o3);
-        float t = scale(KH, o1 + o3);
-        float u3 = t - o2;
-        float u1 = t + o2;
-        float w3 = o0 - r;
-        float w1 = o0 + r;
-        v[1] = mix_sub(K1c, w1, K1s, u1);
-        v[7] = mix_add(K1c, u1, K1s, w1);
-        v[3] = mix_sub(K3c, w3, K3s, u3);
-        v[5] = mix_add(K3c, u3, K3s, w3);
-}
-
-// one pass of idct8x8s (ooura/dct.c:39-66)
-__device__ __forceinline__ void idct8(float (&v)[8])
-{
-        float a1 = mix_add(K1c, v[1], K1s, v[7]);
-        float b1 = mix_sub(K1c, v[7], K1s, v[1]);
-        float a3 = mix_add(K3c, v[3], K3s, v[5]);
-        float b3 = mix_sub(K3c, v[5], K3s, v[3]);
-        float dr = a1 - a3;
-        float di = b1 + b3;
-        a1 = a1 + a3;
-        b3 = b3 - b1;
-        b1 = scale(KH, dr + di);
-        a3 = scale(KH, dr - di);
-        float cr = mix_add(K2c, v[2], K2s, v[6]);
-        float ci = mix_sub(K2c, v[6], K2s, v[2]);
-        float s0 = scale(K4, v[0] + v[4]);
-        float d0 = scale(K4, v[0] - v[4]);
-        float m2r = s0 - cr;
-        float m2i = d0 - ci;
-        s0 = s0 + cr;
-        d0 = d0 + ci;
-        v[0] = s0 + a1;
-        v[7] = s0 - a1;
-        v[2] = d0 + b1;
-        v[5] = d0 - b1;
-        v[4] = m2r - b3;
-        v[3] = m2r + b3;
-        v[6] = m2i - a3;
-        v[1] = m2i + a3;
-}
-
-// ---------------------------------------------------------------------------
-// 8x8 transpose inside each group of 8 lanes through wave-private LDS.
-// Lane (b = lane>>3, j = lane&7) owns 8 values v[0..7] of line j of block b and
-// receives element j of every line: out[i] = v_of_lane(b,i)[j].
-// Layout b*104 + line*12 + elem: the two 16-byte stores of a lane group hit 32
-// distinct banks (12*j mod 32 covers all 4-bank slots), and the dword reads of a
-// 32-lane half hit 32 distinct banks (104 mod 32 = 8).
-// ---------------------------------------------------------------------------
-constexpr int kTpLine = 12, kTpBlock = 104, kTpWave = 8 * kTpBlock;  // floats
-
-__device__ __forceinline__ void transpose8(float (&v)[8], float *scratch, int lane)
-{
-        const int b = lane >> 3, j = lane & 7;
-        float4 *dst = reinterpret_cast<float4 *>(scratch + b * kTpBlock + j * kTpLine);
-        dst[0] = make_float4(v[0], v[1], v[2], v[3]);
-        dst[1] = make_float4(v[4], v[5], v[6], v[7]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const float *src = scratch + b * kTpBlock + j;
-#pragma unroll
-        for(int i = 0; i < 8; i++) { v[i] = src[i * kTpLine]; }
-        __builtin_amdgcn_wave_barrier();
-}
 
 // ---------------------------------------------------------------------------
 // Kernel arguments
@@ -2723,592 +2622,6 @@ __global__ __launch_bounds__(256) void k_dct_blocks(float *blocks, size_t nblock
                 for(int u = 0; u < 8; u++) { blocks[blk * 64 + rr * 8 + u] = v[u]; }
         }
 }
-
-// ---------------------------------------------------------------------------
-// YCbCr -> RGB of the PNG writer (png.c:37-62) with the luma +128 fix-up of
-// jpeg2png.c:156-159, cropped to the image size.  The reference evaluates the
-// colour matrix in double, narrows to float for the clamp, scales by
-// (1 << bits) / 256 in float and truncates to unsigned; the same here.
-// out: one byte per sample (bits == 8) or two, big-endian (bits == 16).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float clamp_sample(double v)
-{
-        const float x = (float)v;
-        return (double)x > 255. ? 255.f : ((double)x < 0. ? 0.f : x);           // CLAMP(x, 0., 255.), png.c:15-17
-}
-
-// One pixel up to the clamp, for k_to_samples and k_to_tensor alike: put(k, x) gets the clamped float x of output channel k,
-// from the solved Y, Cb, Cr.  NPLANE 3: RGB.  NPLANE 1: greyscale — the same writer with Cb = Cr = 0, where R = G = B exactly
-// (yi + 0.0 and yi - 0.0 - 0.0 in double are yi), so the colour matrix is not evaluated and cbi / cri are not looked at.
-template <int NPLANE, typename Put>
-__device__ __forceinline__ void clamped_pixel(float y, float cbi, float cri, Put put)
-{
-        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
-        const float yi = (float)((double)y + 128.);                             // jpeg2png.c:158
-        if constexpr(NPLANE == 3) {
-                put(0, clamp_sample((double)yi + 1.402 * (double)cri));
-                put(1, clamp_sample((double)yi - 0.34414 * (double)cbi - 0.71414 * (double)cri));
-                put(2, clamp_sample((double)yi + 1.772 * (double)cbi));
-        } else {
-                put(0, clamp_sample((double)yi));
-        }
-}
-
-// the sample(s) of one pixel as big-endian bytes: one byte each (bits == 8) or two (bits == 16)
-template <int N>
-__device__ __forceinline__ void store_samples(uint8_t *out, size_t i, const unsigned (&v)[N], unsigned bits)
-{
-        if(bits == 8) {
-                uint8_t *o = out + i * N;
-#pragma unroll
-                for(int k = 0; k < N; k++) { o[k] = (uint8_t)(v[k] & 0xff); }
-        } else {
-                uint8_t *o = out + i * (2 * N);
-#pragma unroll
-                for(int k = 0; k < N; k++) { o[2 * k] = (uint8_t)((v[k] >> 8) & 0xff); o[2 * k + 1] = (uint8_t)(v[k] & 0xff); }
-        }
-}
-
-// NPLANE 3: RGB.  NPLANE 1: greyscale, where cbp / crp are not read.  out: NPLANE samples per pixel.
-template <int NPLANE>
-__global__ __launch_bounds__(256) void k_to_samples(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
-                                                    unsigned crs, unsigned w, unsigned h, unsigned bits, uint8_t *out)
-{
-        const size_t n = (size_t)w * h;
-        const float bitfactor = (float)((double)(1 << bits) / 256.);
-        for(size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-                const unsigned x = (unsigned)(i % w), y = (unsigned)(i / w);
-                const float yin = yp[(size_t)y * ys + x];
-                float cbi = 0.f, cri = 0.f;                                      // (one plane: not looked at)
-                if constexpr(NPLANE == 3) { cbi = cbp[(size_t)y * cbs + x]; cri = crp[(size_t)y * crs + x]; }
-                unsigned v[NPLANE];
-                clamped_pixel<NPLANE>(yin, cbi, cri, [&](int k, float x) { v[k] = (unsigned)(x * bitfactor); });
-                store_samples(out, i, v, bits);
-        }
-}
-// Instantiated explicitly: an implicit instantiation is emitted at the end of the code object, where the same instructions
-// measured 2 us (5 %) slower per 4096x3072 image than k_to_rgb did from here (profiles/README.md: output_stage_refactor)
-template __global__ void k_to_samples<3>(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, unsigned, uint8_t *);
-template __global__ void k_to_samples<1>(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, unsigned, uint8_t *);
-
-// ---------------------------------------------------------------------------
-// Tensor output: the same conversion up to the clamp (png.c:37-47 with the luma +128 of jpeg2png.c:156-159), left in DEVICE
-// memory as elements of a strided tensor — element (k, y, x) at data + k * stride_c + y * stride_y + x * stride_x, strides
-// in elements.  Per channel k with the clamped float v_k:
-//   u8                : (uint8_t)(unsigned)v_k — the 8-bit samples of k_to_samples;
-//   f32 / f16 / bf16  : t = v_k * scale[k], then t = t + bias[k] — two separately rounded f32 operations (this file is
-//                       compiled with -ffp-contract=off; never an fma, and no shortcut for scale 1 / bias 0: -0.f + 0.f is
-//                       +0.f) — stored as it is (f32) or rounded to nearest even by the cast (f16, bf16: which instruction
-//                       that is, is the compiler's choice).
-// Indexed in 2-D, no division anywhere: blockIdx.x and the lane give the column, the wavefront of the workgroup and
-// blockIdx.y the row, grid-stride over rows.  A lane converts 4 consecutive pixels of one row from ONE 16-byte load per
-// plane: its first column is a multiple of 4, crops start at canvas column 0, every canvas row starts at a multiple of W
-// floats with W a multiple of 8, and the planes themselves (xbuf) are carved from the solver's arena at multiples of 256
-// bytes (Carver::take) — so every such load is aligned and, W being a multiple of 4, inside the canvas row even where the
-// image ends inside the group.  A wavefront reads 1 KB of every plane's row.
-// LAYOUT (chosen by the host, tensor_path in j2p_solver.hip, the only place that knows the rule):
-//   planar      (stride_x == 1): a lane's 4 elements of a channel go out as one 16 / 8 / 4-byte store (f32 / 16-bit / u8);
-//   interleaved (stride_c == 1, stride_x == NPLANE): its 4 * NPLANE contiguous elements as NPLANE such stores;
-//   generic     : one element per store, any strides.
-// The first two are only launched where every such store is aligned to its width; the w % 4 pixels at the end of a row take
-// the element stores in every layout.  Nothing but elements of the image is ever written.
-// ---------------------------------------------------------------------------
-constexpr int kDtypeU8 = 0, kDtypeF16 = 1, kDtypeBF16 = 2, kDtypeF32 = 3;                // J2P_DTYPE_* (checked in j2p_solver.hip)
-constexpr int kTensorGeneric = 0, kTensorPlanar = 1, kTensorInterleaved = 2;           // what j2p_debug_tensor_path reports
-
-struct TensorOut {
-        void *data;                                     // element (0, first row, 0)
-        long long stride_c, stride_y, stride_x;         // in elements
-        float scale[3], bias[3];
-};
-
-template <int DTYPE>
-struct TensorElement {
-        static_assert(DTYPE == kDtypeU8 || DTYPE == kDtypeF16 || DTYPE == kDtypeBF16 || DTYPE == kDtypeF32, "u8, f16, bf16 or f32");
-        static constexpr int kBytes = DTYPE == kDtypeU8 ? 1 : (DTYPE == kDtypeF32 ? 4 : 2);
-        using Raw = std::conditional_t<kBytes == 1, uint8_t, std::conditional_t<kBytes == 2, uint16_t, uint32_t>>;
-        // the element's bits from the clamped float
-        static __device__ __forceinline__ unsigned make(float v, float scale, float bias)
-        {
-                if constexpr(DTYPE == kDtypeU8) {
-                        return (unsigned)(uint8_t)(unsigned)v;
-                } else {
-                        float t = v * scale;
-                        t = t + bias;
-                        if constexpr(DTYPE == kDtypeF32) { return __float_as_uint(t); }
-                        else if constexpr(DTYPE == kDtypeF16) { return (unsigned)__builtin_bit_cast(uint16_t, (_Float16)t); }
-                        else { return (unsigned)__builtin_bit_cast(uint16_t, (__bf16)t); }
-                }
-        }
-};
-
-// WORDS 32-bit words as one store: 16, 8 or 4 bytes
-template <int WORDS>
-__device__ __forceinline__ void store_words(void *p, const unsigned *v)
-{
-        static_assert(WORDS == 1 || WORDS == 2 || WORDS == 4, "4, 8 or 16 bytes");
-        if constexpr(WORDS == 4) { *reinterpret_cast<uint4 *>(p) = make_uint4(v[0], v[1], v[2], v[3]); }
-        else if constexpr(WORDS == 2) { *reinterpret_cast<uint2 *>(p) = make_uint2(v[0], v[1]); }
-        else { *reinterpret_cast<unsigned *>(p) = v[0]; }
-}
-
-// the rows of one lane: columns [x0, x0 + npix).  FULL: npix is 4 — a loop of its own, so that the compiler sees all four loaded
-// values used and keeps the 16-byte loads whole (with npix a run-time value in one loop it loads three floats and one)
-template <int NPLANE, int DTYPE, int LAYOUT, bool FULL>
-__device__ __forceinline__ void tensor_lane_rows(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp, unsigned crs,
-                                                 unsigned x0, unsigned npix, unsigned h, const TensorOut &o)
-{
-        using E = TensorElement<DTYPE>;
-        using Raw = typename E::Raw;
-        constexpr int kPerWord = 4 / E::kBytes;         // elements per 32-bit word
-        constexpr int kWords = E::kBytes;               // words of one store of 4 elements: 16 / 8 / 4 bytes
-        Raw *const data = static_cast<Raw *>(o.data);
-        for(unsigned y = blockIdx.y * 4 + (threadIdx.x >> 6); y < h; y += gridDim.y * 4) {
-                const float4 y4 = *reinterpret_cast<const float4 *>(yp + (size_t)y * ys + x0);
-                const float yin[4] = {y4.x, y4.y, y4.z, y4.w};
-                float4 cb4 = make_float4(0.f, 0.f, 0.f, 0.f), cr4 = cb4;                  // (one plane: not looked at)
-                if constexpr(NPLANE == 3) {
-                        cb4 = *reinterpret_cast<const float4 *>(cbp + (size_t)y * cbs + x0);
-                        cr4 = *reinterpret_cast<const float4 *>(crp + (size_t)y * crs + x0);
-                }
-                const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
-                float v[NPLANE][4];
-#pragma unroll
-                for(int p = 0; p < 4; p++) { clamped_pixel<NPLANE>(yin[p], cbin[p], crin[p], [&](int k, float x) { v[k][p] = x; }); }
-                unsigned e[NPLANE][4];
-#pragma unroll
-                for(int k = 0; k < NPLANE; k++) {
-#pragma unroll
-                        for(int p = 0; p < 4; p++) { e[k][p] = E::make(v[k][p], o.scale[k], o.bias[k]); }
-                }
-                const long long row = (long long)y * o.stride_y;
-                if constexpr(LAYOUT != kTensorGeneric && FULL) {
-                        // the lane's elements in memory order, packed into words: NPLANE stores of kWords words
-                        unsigned words[NPLANE * kWords];
-#pragma unroll
-                        for(int i = 0; i < NPLANE * kWords; i++) { words[i] = 0; }
-#pragma unroll
-                        for(int i = 0; i < NPLANE * 4; i++) {
-                                const unsigned bits = LAYOUT == kTensorPlanar ? e[i / 4][i % 4] : e[i % NPLANE][i / NPLANE];
-                                words[i / kPerWord] |= bits << (8 * E::kBytes * (i % kPerWord));
-                        }
-#pragma unroll
-                        for(int j = 0; j < NPLANE; j++) {
-                                Raw *dst = LAYOUT == kTensorPlanar ? data + (long long)j * o.stride_c + row + x0
-                                                                   : data + row + (long long)x0 * NPLANE + j * 4;
-                                store_words<kWords>(dst, words + j * kWords);
-                        }
-                } else {
-#pragma unroll
-                        for(int p = 0; p < 4; p++) {
-                                if(FULL || (unsigned)p < npix) {
-#pragma unroll
-                                        for(int k = 0; k < NPLANE; k++) {
-                                                data[(long long)k * o.stride_c + row + (long long)(x0 + p) * o.stride_x] = (Raw)e[k][p];
-                                        }
-                                }
-                        }
-                }
-        }
-}
-
-template <int NPLANE, int DTYPE, int LAYOUT>
-__global__ __launch_bounds__(256) void k_to_tensor(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
-                                                   unsigned crs, unsigned w, unsigned h, TensorOut o)
-{
-        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
-        static_assert(LAYOUT == kTensorGeneric || LAYOUT == kTensorPlanar || (LAYOUT == kTensorInterleaved && NPLANE == 3), "layout");
-        const unsigned x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
-        if(x0 >= w) { return; }                                                 // (no barrier in this kernel)
-        if(w - x0 >= 4) { tensor_lane_rows<NPLANE, DTYPE, LAYOUT, true>(yp, ys, cbp, cbs, crp, crs, x0, 4, h, o); }
-        else { tensor_lane_rows<NPLANE, DTYPE, kTensorGeneric, false>(yp, ys, cbp, cbs, crp, crs, x0, w - x0, h, o); }   // the row's last w % 4 pixels
-}
-// (explicit instantiations, as for k_to_samples; one plane has no interleaved layout: stride_x == 1 there, which is planar)
-#define J2P_TENSOR_KERNEL(NPLANE, DTYPE, LAYOUT)                                                                                   \
-        template __global__ void k_to_tensor<NPLANE, DTYPE, LAYOUT>(const float *, unsigned, const float *, unsigned, const float *, \
-                                                                    unsigned, unsigned, unsigned, TensorOut);
-#define J2P_TENSOR_KERNELS(DTYPE)                                                                                                  \
-        J2P_TENSOR_KERNEL(3, DTYPE, kTensorGeneric) J2P_TENSOR_KERNEL(3, DTYPE, kTensorPlanar) J2P_TENSOR_KERNEL(3, DTYPE, kTensorInterleaved) \
-        J2P_TENSOR_KERNEL(1, DTYPE, kTensorGeneric) J2P_TENSOR_KERNEL(1, DTYPE, kTensorPlanar)
-J2P_TENSOR_KERNELS(kDtypeU8)
-J2P_TENSOR_KERNELS(kDtypeF16)
-J2P_TENSOR_KERNELS(kDtypeBF16)
-J2P_TENSOR_KERNELS(kDtypeF32)
-#undef J2P_TENSOR_KERNELS
-#undef J2P_TENSOR_KERNEL
-
-// ---------------------------------------------------------------------------
-// Resized tensor output: the clamped floats v_k of a source rectangle (the box) of the image, area-resampled to out_w x
-// out_h <= the box, as elements of the same strided tensor.  Every bit is defined (include/jpeg2png_amd.h):
-//   taps of output column X, in integers: lo = X * box_w, hi = lo + box_w; source columns i = lo / out_w .. (hi - 1) / out_w
-//   of the box with weights a_i = min(hi, (i + 1) * out_w) - max(lo, i * out_w); rows likewise with box_h, out_h, b_j.  An
-//   axis that is not resized has one tap of weight 1: the host passes its taps in the units (1, 1) and no divisor;
-//   r_j = 0.f; r_j = r_j + (float)a_i * v_k(box_x + i, box_y + j), i ascending;  acc = 0.f; acc = acc + (float)b_j * r_j,
-//   j ascending;  m = acc [/ (float)box_w] [/ (float)box_h] (the IEEE quotients), m = min(m, 255.f), and TensorElement of m.
-// Every operation rounded on its own (-ffp-contract=off, correctly rounded division, never a reciprocal).  The products
-// X * box_w are formed in 64 bits (a zoomed canvas is wider than 65535); what the tap walk carries is the tap's offset
-// i * out_w - lo, which lies in (-out_w, box_w) and fits an int.
-// MAPPING: a wavefront owns `rows` consecutive output rows of a tile of lanes x slots output columns, column X0 + p * lanes +
-// lane in slot p of its lane (neighbouring lanes: neighbouring columns, for the stores and for the LDS banks).  For every
-// source row of those output rows' footprint, in order, it goes left to right through the row segment its tile covers in chunks of
-// kResizeChunk columns: the lanes load the chunk with 16-byte loads (aligned DOWN to 4 floats: up to 3 columns left of the
-// box and what is right of the segment in its last group are converted and never looked at; the group lies inside the canvas
-// row as k_to_tensor's does), convert every pixel ONCE and stage the clamped channels in wave-private LDS; then every lane
-// walks those taps of its columns that lie in the chunk.  Chunks ascend, so every r_j is summed in the order above
-// whatever the tile and the chunk size are.  The LDS index is padded by one float per 32 (resize_lds_index): lanes read at a
-// stride of box_w / out_w floats, and with the pad the strides 2, 4, 8, 16 touch 32 distinct banks per 32-lane half, as the
-// four dword stores of the staging do (a lane's 4 floats are then no longer 16-byte aligned, but 4 conflict-free dword
-// stores cost the LDS the cycles of one 16-byte store).  No workgroup barrier: the 4 wavefronts of a workgroup (one above
-// the other in one tile, so that the source row two of them share is in L1 / L2 for the second) do not talk to each other.
-// Where two consecutive output rows of a wavefront share a source row, the second starts from the same r_j (acc = 0.f + b *
-// r_j): the row is read and converted once.  The loads of the next chunk are issued before the taps of this one are walked.
-// The tile is the host's choice (resize_tile in j2p_solver.hip): 256 columns and 8 rows where the output is large, down to
-// 32 columns and one row where it is small, so that a small output of a large image still gives every SIMD a wavefront or
-// two.
-// Element stores and generic strides only: the output is small next to the source that is read.
-// ---------------------------------------------------------------------------
-constexpr int kResizeChunk = 512;                                // source columns staged at a time (a multiple of 256)
-constexpr int kResizeSlots = 4;                                  // output columns per lane, at most
-constexpr int kResizeLds = kResizeChunk + kResizeChunk / 32;     // floats per staged channel
-
-struct ResizeGeom {
-        unsigned box_x, box_y;
-        unsigned tap_bw, tap_ow;        // the units of the x taps: (box_w, out_w), or (1, 1) where the axis is not resized
-        unsigned tap_bh, tap_oh;
-        unsigned qx, rx, qy, ry;        // tap_bw = qx * tap_ow + rx, tap_bh = qy * tap_oh + ry
-        unsigned qlanes, rlanes;        // lanes * tap_bw = qlanes * tap_ow + rlanes
-        unsigned out_w, out_h;
-        float div_x, div_y;             // (float)box_w, (float)box_h; 0.f: axis not resized, no division
-        unsigned lanes, slots;          // the tile: lanes (a power of two, 32 or 64) x slots (1..kResizeSlots) columns
-        unsigned rows;                  // consecutive output rows per wavefront
-};
-
-__device__ __forceinline__ int resize_lds_index(int i) { return i + (i >> 5); }
-
-// the taps of an output index of an axis: source indices [first, last] of the box, and rem with lo = first * ow + rem,
-// 0 <= rem < ow — the first tap's offset first * ow - lo is -rem
-struct ResizeTaps {
-        int first, last, rem;
-};
-// last = (lo + bw - 1) / ow without a division: with bw = q * ow + r that is first + q + floor((rem + r - 1) / ow), and
-// rem + r - 1 lies in [-1, 2 * ow - 2]
-__device__ __forceinline__ ResizeTaps resize_taps_from(int first, int rem, unsigned q, unsigned r, unsigned ow)
-{
-        const int t = rem + (int)r - 1;
-        ResizeTaps out;
-        out.first = first;
-        out.last = first + (int)q + (t >= (int)ow ? 1 : (t < 0 ? -1 : 0));
-        out.rem = rem;
-        return out;
-}
-// of index X, by a 64-bit division: once per wavefront and axis
-__device__ __forceinline__ ResizeTaps resize_taps(unsigned X, unsigned bw, unsigned ow, unsigned q, unsigned r)
-{
-        const unsigned long long lo = (unsigned long long)X * bw, first = lo / ow;
-        return resize_taps_from((int)first, (int)(lo - first * ow), q, r, ow);
-}
-// of the index `step` further on, where step * bw = qs * ow + rs
-__device__ __forceinline__ ResizeTaps resize_taps_step(const ResizeTaps &t, unsigned qs, unsigned rs, unsigned q, unsigned r, unsigned ow)
-{
-        int first = t.first + (int)qs, rem = t.rem + (int)rs;           // (rem < 2 * ow)
-        if(rem >= (int)ow) { rem -= (int)ow; first++; }
-        return resize_taps_from(first, rem, q, r, ow);
-}
-// the weight of the tap at offset off = i * ow - lo: min(hi, (i + 1) * ow) - max(lo, i * ow), both taken relative to lo
-__device__ __forceinline__ float resize_weight(int off, unsigned bw, unsigned ow)
-{
-        const int end = off + (int)ow;
-        return (float)((end < (int)bw ? end : (int)bw) - (off > 0 ? off : 0));
-}
-
-template <int NPLANE, int DTYPE>
-__global__ __launch_bounds__(256) void k_to_tensor_resized(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
-                                                           unsigned crs, ResizeGeom g, TensorOut o)
-{
-        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
-        static_assert(kResizeChunk % 256 == 0, "whole rounds of 64 lanes x 4 floats");
-        constexpr int kRounds = kResizeChunk / 256;
-        using E = TensorElement<DTYPE>;
-        using Raw = typename E::Raw;
-        __shared__ float stage[4][NPLANE][kResizeLds];
-        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-        const unsigned Yb = (blockIdx.y * 4 + (unsigned)wave) * g.rows;   // this wavefront's output rows: [Yb, Ye)
-        if(Yb >= g.out_h) { return; }                                    // (no workgroup barrier in this kernel)
-        const unsigned Ye = g.out_h - Yb < g.rows ? g.out_h : Yb + g.rows;
-        float (*const lds)[kResizeLds] = stage[wave];
-        const unsigned tile = g.lanes * g.slots;
-        const unsigned X0 = blockIdx.x * tile;                           // (the grid has no tile beyond out_w)
-        const unsigned ncol = g.out_w - X0 < tile ? g.out_w - X0 : tile;
-        // the taps of the lane's columns X0 + p * lanes + lane: from the tile's first column by steps, no division per column
-        // but one of 32 bits (lane * tap_bw < 64 * 2^18)
-        const ResizeTaps t0 = resize_taps(X0, g.tap_bw, g.tap_ow, g.qx, g.rx);
-        ResizeTaps tx[kResizeSlots];
-        bool has[kResizeSlots];
-        {
-                const unsigned lb = (unsigned)lane * g.tap_bw, ql = lb / g.tap_ow;
-                tx[0] = resize_taps_step(t0, ql, lb - ql * g.tap_ow, g.qx, g.rx, g.tap_ow);
-        }
-#pragma unroll
-        for(int p = 0; p < kResizeSlots; p++) {
-                if(p > 0) { tx[p] = resize_taps_step(tx[p - 1], g.qlanes, g.rlanes, g.qx, g.rx, g.tap_ow); }
-                has[p] = (unsigned)p < g.slots && (unsigned)lane < g.lanes && (unsigned)p * g.lanes + (unsigned)lane < ncol;
-        }
-        // the tile's segment of a source row, in canvas columns: [c_begin, c_last], c_begin a multiple of 4
-        const int c_last = (int)g.box_x + resize_taps(X0 + ncol - 1, g.tap_bw, g.tap_ow, g.qx, g.rx).last;
-        const int c_begin = ((int)g.box_x + t0.first) & ~3;
-        ResizeTaps ty = resize_taps(Yb, g.tap_bh, g.tap_oh, g.qy, g.ry);
-        const int j_end = resize_taps(Ye - 1, g.tap_bh, g.tap_oh, g.qy, g.ry).last;        // the last source row of these output rows
-        Raw *const data = static_cast<Raw *>(o.data);
-
-        // the 16-byte loads of chunk c0 of source row j, into registers: issued one chunk ahead of their use
-        float4 ld[kRounds][NPLANE];
-#pragma unroll
-        for(int u = 0; u < kRounds; u++) {
-#pragma unroll
-                for(int k = 0; k < NPLANE; k++) { ld[u][k] = make_float4(0.f, 0.f, 0.f, 0.f); }
-        }
-        const auto issue = [&](int j, int c0) {
-                const size_t row = (size_t)g.box_y + (size_t)j;
-#pragma unroll
-                for(int u = 0; u < kRounds; u++) {
-                        const int c = c0 + u * 256 + lane * 4;
-                        if(c <= c_last) {
-                                ld[u][0] = *reinterpret_cast<const float4 *>(yp + row * ys + c);
-                                if constexpr(NPLANE == 3) {
-                                        ld[u][1] = *reinterpret_cast<const float4 *>(cbp + row * cbs + c);
-                                        ld[u][2] = *reinterpret_cast<const float4 *>(crp + row * crs + c);
-                                }
-                        }
-                }
-        };
-
-        unsigned Y = Yb;
-        float acc[kResizeSlots][NPLANE];
-#pragma unroll
-        for(int p = 0; p < kResizeSlots; p++) {
-#pragma unroll
-                for(int k = 0; k < NPLANE; k++) { acc[p][k] = 0.f; }
-        }
-        int offy = -ty.rem;                                              // source row j's offset j * tap_oh - lo of output row Y
-        issue(ty.first, c_begin);
-        for(int j = ty.first;; j++) {
-                // r_j of every column of the lane: the row's chunks, left to right
-                float r[kResizeSlots][NPLANE];
-#pragma unroll
-                for(int p = 0; p < kResizeSlots; p++) {
-#pragma unroll
-                        for(int k = 0; k < NPLANE; k++) { r[p][k] = 0.f; }
-                }
-                for(int c0 = c_begin; c0 <= c_last; c0 += kResizeChunk) {
-#pragma unroll
-                        for(int u = 0; u < kRounds; u++) {
-                                const int at = u * 256 + lane * 4;
-                                if(c0 + at <= c_last) {
-                                        const float yin[4] = {ld[u][0].x, ld[u][0].y, ld[u][0].z, ld[u][0].w};
-                                        const float4 cb4 = ld[u][NPLANE == 3 ? 1 : 0], cr4 = ld[u][NPLANE == 3 ? 2 : 0];   // (one plane: not looked at)
-                                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
-#pragma unroll
-                                        for(int q = 0; q < 4; q++) {
-                                                const int idx = resize_lds_index(at + q);
-                                                clamped_pixel<NPLANE>(yin[q], cbin[q], crin[q], [&](int k, float x) { lds[k][idx] = x; });
-                                        }
-                                }
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        // the next chunk's loads fly while this one's taps are walked
-                        if(c0 + kResizeChunk <= c_last) { issue(j, c0 + kResizeChunk); }
-                        else if(j < j_end) { issue(j + 1, c_begin); }
-                        const int rel0 = c0 - (int)g.box_x;              // the chunk's first column relative to the box (>= -3)
-#pragma unroll
-                        for(int p = 0; p < kResizeSlots; p++) {
-                                if(!has[p]) { continue; }
-                                const int i0 = tx[p].first > rel0 ? tx[p].first : rel0;
-                                const int i1 = tx[p].last < rel0 + kResizeChunk - 1 ? tx[p].last : rel0 + kResizeChunk - 1;
-                                if(i0 > i1) { continue; }                // none of this column's taps in this chunk
-                                int off = (i0 - tx[p].first) * (int)g.tap_ow - tx[p].rem;         // (< box_w + out_w)
-                                for(int i = i0; i <= i1; i++, off += (int)g.tap_ow) {
-                                        const float a = resize_weight(off, g.tap_bw, g.tap_ow);
-                                        const int idx = resize_lds_index(i - rel0);
-#pragma unroll
-                                        for(int k = 0; k < NPLANE; k++) {
-                                                const float t = a * lds[k][idx];
-                                                r[p][k] = r[p][k] + t;
-                                        }
-                                }
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();                 // the next chunk is staged over this one
-                }
-                // output row Y takes the row with its weight; where the row is Y's last, Y is finished, and the next output
-                // row, if the row is its first (the one source row two output rows share), starts from the same r_j
-                const float b = resize_weight(offy, g.tap_bh, g.tap_oh);
-                offy += (int)g.tap_oh;
-#pragma unroll
-                for(int p = 0; p < kResizeSlots; p++) {
-#pragma unroll
-                        for(int k = 0; k < NPLANE; k++) {
-                                const float t = b * r[p][k];
-                                acc[p][k] = acc[p][k] + t;
-                        }
-                }
-                if(j < ty.last) { continue; }
-                const long long rowo = (long long)Y * o.stride_y;
-#pragma unroll
-                for(int p = 0; p < kResizeSlots; p++) {
-                        if(!has[p]) { continue; }
-                        const long long X = (long long)(X0 + (unsigned)p * g.lanes + (unsigned)lane);
-#pragma unroll
-                        for(int k = 0; k < NPLANE; k++) {
-                                float m = acc[p][k];
-                                if(g.div_x != 0.f) { m = m / g.div_x; }
-                                if(g.div_y != 0.f) { m = m / g.div_y; }
-                                m = m < 255.f ? m : 255.f;
-                                data[(long long)k * o.stride_c + rowo + X * o.stride_x] = (Raw)E::make(m, o.scale[k], o.bias[k]);
-                        }
-                }
-                if(++Y == Ye) { break; }
-                ty = resize_taps_step(ty, g.qy, g.ry, g.qy, g.ry, g.tap_oh);
-                offy = -ty.rem;
-                const bool shared = ty.first == j;                      // (a resized axis has at least two taps: never also Y's last)
-                const float b2 = shared ? resize_weight(offy, g.tap_bh, g.tap_oh) : 0.f;
-                if(shared) { offy += (int)g.tap_oh; }
-#pragma unroll
-                for(int p = 0; p < kResizeSlots; p++) {
-#pragma unroll
-                        for(int k = 0; k < NPLANE; k++) {
-                                const float t = b2 * r[p][k];
-                                acc[p][k] = 0.f + t;                      // (not shared: 0.f + 0.f * r_j, which is +0.f: r_j is finite and not negative)
-                        }
-                }
-        }
-}
-#define J2P_RESIZED_KERNELS(NPLANE)                                                                                                          \
-        template __global__ void k_to_tensor_resized<NPLANE, kDtypeU8>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);   \
-        template __global__ void k_to_tensor_resized<NPLANE, kDtypeF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);  \
-        template __global__ void k_to_tensor_resized<NPLANE, kDtypeBF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut); \
-        template __global__ void k_to_tensor_resized<NPLANE, kDtypeF32>(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);
-J2P_RESIZED_KERNELS(3)
-J2P_RESIZED_KERNELS(1)
-#undef J2P_RESIZED_KERNELS
-
-// ---------------------------------------------------------------------------
-// JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,
-// each coefficient divided by its output quantisation step (IEEE f32 quotient: `/` under
-// -fhip-fp32-correctly-rounded-divide-sqrt, never a reciprocal multiply), rounded to nearest even, clamped to
-// [-1023, 1023] (what libjpeg's Huffman coder takes: AC magnitudes of at most 10 bits, DC differences of at most 11).
-// No +128: JPEG's level shift and the luma fix-up of jpeg2png.c:156-159 cancel.
-// out: block-major int16 [blocks][64], natural order — the JBLOCK rows of libjpeg.
-// Mapping of k_dct_blocks: one wavefront = 8 horizontally adjacent blocks, lane >> 3 the block, lane & 7 the row; a
-// lane stores its 8 coefficients as one 16-byte vector (the wavefront: 1 KB contiguous).
-// ---------------------------------------------------------------------------
-struct QuantSteps {
-        float q[64];        // natural order
-};
-
-// the tail: a lane holds row `lane & 7` of block `lane >> 3` of its wavefront's 8 blocks in v[];
-// dct8x8s, quotient, rounding, clamp, and the row's 8 coefficients as one 16-byte store into `block` (ok lanes only)
-__device__ __forceinline__ void quantise_store(float (&v)[8], float *scratch, const float *qs, int lane, bool ok, int16_t *block)
-{
-        const int rr = lane & 7;
-        transpose8(v, scratch, lane);
-        fdct8(v);
-        transpose8(v, scratch, lane);
-        fdct8(v);
-        unsigned packed[4];
-#pragma unroll
-        for(int u = 0; u < 8; u += 2) {
-                unsigned half[2];
-#pragma unroll
-                for(int k = 0; k < 2; k++) {
-                        float t = rintf(v[u + k] / qs[rr * 8 + u + k]);
-                        t = t > 1023.f ? 1023.f : (t < -1023.f ? -1023.f : t);
-                        half[k] = (unsigned)(int)t & 0xffffu;
-                }
-                packed[u / 2] = half[0] | (half[1] << 16);
-        }
-        if(ok) { *reinterpret_cast<uint4 *>(block + rr * 8) = make_uint4(packed[0], packed[1], packed[2], packed[3]); }
-}
-
-// ---------------------------------------------------------------------------
-// One kernel for every output sampling (4:4:4, 4:2:2, 4:2:0, 4:4:0): output sample (X, Y) of the block grid is the mean
-// the projection constrains (compute.c:351-359) — a float accumulator that starts at 0.f takes the SY * SX canvas values
-// at rows Y * SY + j, columns X * SX + i in raster order (j outer, i inner), one addition each, and is divided by
-// (float)(SX * SY) — and the 8x8 blocks of those samples go through the transform, quotient, rounding and clamp above.
-// <1, 1> gives the coefficients of the plane itself: (0.f + x) / 1.f differs from x only for x = -0.f, which becomes
-// +0.f; another sign on a zero input can only change the sign of a zero somewhere in the two fdct8 passes, and every
-// such zero ends as the integer 0 after rintf and the conversion to int.
-// plane: first row = the first canvas row of the block_rows output block rows; stride x rows: what the canvas holds from
-// there on.  out: block-major int16 [block_rows * blocks_w][64].  A row index beyond the canvas's last row reads the
-// last row, a column beyond the last column the last column: only the last block row / column of a grid that overhangs
-// the canvas (every block STARTS inside it, which the host checks; never for <1, 1>, where canvas, band cuts and
-// blocks_w * 8 are all multiples of 8).  A lane loads SY rows of 8 * SX consecutive floats as float4 (a block starts at
-// a multiple of 8 * SX floats and the stride is a multiple of 8: aligned), 8 lanes 256 * SX contiguous bytes of a canvas
-// row; only lanes whose footprint crosses the canvas's edge take the clamped scalar loads.
-// ---------------------------------------------------------------------------
-template <int SX, int SY>
-__global__ __launch_bounds__(256) void k_quantise_blocks(const float *plane, unsigned stride, unsigned rows, unsigned blocks_w,
-                                                         unsigned block_rows, QuantSteps steps, int16_t *out)
-{
-        static_assert((SX == 1 || SX == 2) && (SY == 1 || SY == 2), "sampling factors 1 and 2");
-        __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
-        __shared__ float qs[64];
-        if(threadIdx.x < 64) { qs[threadIdx.x] = steps.q[threadIdx.x]; }
-        __syncthreads();
-        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-        const unsigned groups_x = (blocks_w + 7) / 8;
-        const unsigned grp = blockIdx.x * 4 + wave;
-        if(grp >= groups_x * block_rows) { return; }                    // whole wavefronts only: no barrier follows
-        const unsigned by = grp / groups_x, bx = (grp % groups_x) * 8 + (unsigned)(lane >> 3);
-        const int rr = lane & 7;
-        const bool ok = bx < blocks_w;
-        const unsigned x0 = bx * (8 * SX), y0 = (by * 8 + (unsigned)rr) * SY;
-        float v[8];
-#pragma unroll
-        for(int u = 0; u < 8; u++) { v[u] = 0.f; }
-        const bool inside = SX * SY == 1 || (x0 + 8 * SX <= stride && y0 + SY <= rows);         // (<1, 1>: nothing can overhang)
-        if(ok && inside) {
-#pragma unroll
-                for(int j = 0; j < SY; j++) {
-                        const float4 *src = reinterpret_cast<const float4 *>(plane + (size_t)(y0 + j) * stride + x0);
-                        float f[8 * SX];
-#pragma unroll
-                        for(int k = 0; k < 2 * SX; k++) {
-                                const float4 a = src[k];
-                                f[4 * k] = a.x; f[4 * k + 1] = a.y; f[4 * k + 2] = a.z; f[4 * k + 3] = a.w;
-                        }
-#pragma unroll
-                        for(int u = 0; u < 8; u++) {
-#pragma unroll
-                                for(int i = 0; i < SX; i++) { v[u] = v[u] + f[u * SX + i]; }
-                        }
-                }
-        } else if(ok) {
-                // the footprint crosses the canvas's last column or row: replicate them
-#pragma unroll
-                for(int j = 0; j < SY; j++) {
-                        const unsigned y = y0 + j < rows ? y0 + j : rows - 1;
-                        const float *src = plane + (size_t)y * stride;
-#pragma unroll
-                        for(int u = 0; u < 8; u++) {
-#pragma unroll
-                                for(int i = 0; i < SX; i++) {
-                                        const unsigned x = x0 + u * SX + i;
-                                        v[u] = v[u] + src[x < stride ? x : stride - 1];
-                                }
-                        }
-                }
-        }
-#pragma unroll
-        for(int u = 0; u < 8; u++) { v[u] = v[u] / (float)(SX * SY); }
-        quantise_store(v, tp + wave * kTpWave, qs, lane, ok, out + ((size_t)by * blocks_w + bx) * 64);
-}
-// (explicit instantiations, as for k_to_samples)
-template __global__ void k_quantise_blocks<1, 1>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
-template __global__ void k_quantise_blocks<2, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
-template __global__ void k_quantise_blocks<2, 1>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
-template __global__ void k_quantise_blocks<1, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
 
 // ---------------------------------------------------------------------------
 // Self-test of the fast division / square root against the compiler's IEEE forms

@@ -1,0 +1,389 @@
+// jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
+// or cropped and area-resized, and to quantised JPEG coefficients (include/jpeg2png_amd.h: the j2p_planes_* functions).
+//
+// A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
+// and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
+// (j2p_internal.h), never the solver's struct, its halo or its arena.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "jpeg2png_amd.h"
+#include "j2p_internal.h"
+#include "j2p_hip_host.h"
+#include "j2p_output_kernels.hip.h"
+
+using namespace j2p;
+
+extern "C" {
+
+// What the conversions of solved planes start from: rows [y0, y1) x w columns of the image from nplane (3 or 1) (solver,
+// channel) pairs on one device that all hold those canvas rows.  Checks arguments and state, gives per plane the first of
+// those rows in the current iterate and its stride in floats and the view of planes[0].solver, and waits for the streams of
+// the other solvers: the caller launches on planes[0].solver's.  `whole`: called as a whole-canvas form, which band solvers
+// refuse.  what: "to_rgb", "to_grey" or "to_tensor", for the messages.
+static int resolve_rows(const char *what, const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1,
+                        const float *ptr[3], unsigned stride[3], j2p_solver_view &first)
+{
+        if(w == 0 || y0 >= y1) { return j2p_fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
+        for(unsigned i = 0; whole && i < nplane; i++) {
+                if(planes[i].solver && !j2p_solver_view_of(planes[i].solver).whole) {
+                        return j2p_fail(J2P_ESTATE, "%s needs whole-canvas solvers (bands: j2p_planes_rows_%s)", what, what);
+                }
+        }
+        for(unsigned i = 0; i < 3; i++) { ptr[i] = nullptr; stride[i] = 0; }
+        for(unsigned i = 0; i < nplane; i++) {
+                const j2p_solver_view s = planes[i].solver ? j2p_solver_view_of(planes[i].solver) : j2p_solver_view{};
+                if(!planes[i].solver || planes[i].channel >= s.nch) { return j2p_fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
+                if(i == 0) { first = s; }
+                if(s.device != first.device) { return j2p_fail(J2P_EINVAL, "planes live on different devices"); }
+                if(s.W < w || y0 < s.row0 || y1 > s.row0 + s.rows) {
+                        return j2p_fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
+                                    s.row0, s.row0 + s.rows, s.W);
+                }
+                if(s.mid_iteration) { return j2p_fail(J2P_ESTATE, "%s between the two phases of an iteration", what); }
+                if(const int rc = j2p_solver_row(planes[i].solver, planes[i].channel, y0, &ptr[i]); rc != J2P_OK) { return rc; }
+                stride[i] = s.W;
+        }
+        DeviceGuard guard(first.device);
+        for(unsigned i = 1; i < nplane; i++) {
+                if(planes[i].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(j2p_solver_view_of(planes[i].solver).stream)); }
+        }
+        return J2P_OK;
+}
+
+// rows [y0, y1) of the image as samples on the host, through k_to_samples: three planes -> RGB, one -> greyscale
+static int convert_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, unsigned bits,
+                        uint8_t *out_host)
+{
+        const char *what = nplane == 3 ? "to_rgb" : "to_grey";
+        if(!planes || !out_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(bits != 8 && bits != 16) { return j2p_fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
+        const float *ptr[3];
+        unsigned stride[3];
+        j2p_solver_view s0;
+        if(const int rc = resolve_rows(what, planes, nplane, whole, w, y0, y1, ptr, stride, s0); rc != J2P_OK) { return rc; }
+        const unsigned h = y1 - y0;
+        DeviceGuard guard(s0.device);
+        const size_t bytes = (size_t)w * h * (size_t)nplane * (bits / 8);
+        void *dout = nullptr;
+        size_t dout_bytes = 0;
+        HIP_TRY(j2p_pool_take(s0.device, bytes, &dout, &dout_bytes));       // pooled like the solvers' arenas: no hipFree per image
+        hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, s0.stream, ptr[0], stride[0],
+                           ptr[1], stride[1], ptr[2], stride[2], w, h, bits, static_cast<uint8_t *>(dout));
+        hipError_t e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s0.stream);
+        if(e == hipSuccess) { e = hipStreamSynchronize(s0.stream); }
+        j2p_pool_give(s0.device, dout, dout_bytes);
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_%s: %s", what, hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_planes_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
+{
+        return convert_rows(planes, 3, true, w, 0, h, bits, out_host);
+}
+
+int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
+                           uint8_t *out_host)
+{
+        return convert_rows(planes, 3, false, w, row_begin, row_end, bits, out_host);
+}
+
+int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
+{
+        return convert_rows(plane, 1, true, w, 0, h, bits, out_host);
+}
+
+int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
+                            uint8_t *out_host)
+{
+        return convert_rows(plane, 1, false, w, row_begin, row_end, bits, out_host);
+}
+
+// ---- tensor output: k_to_tensor ----
+static_assert(J2P_DTYPE_U8 == kDtypeU8 && J2P_DTYPE_F16 == kDtypeF16 && J2P_DTYPE_BF16 == kDtypeBF16 && J2P_DTYPE_F32 == kDtypeF32,
+              "the kernels' dtype codes are the header's");
+
+// Which destination path the full groups of 4 pixels of a w-column image take — the only place that knows the rule.  A
+// vector path stores 4 elements at once, 16 / 8 / 4 bytes for f32 / 16-bit / u8, and needs every such store aligned to its
+// width: the first row's address, and (in elements) the row stride and — planar, three planes — the channel stride multiples
+// of 4; a lane's first column is a multiple of 4 already.  Everything else, and every image narrower than one group, is
+// generic: correct for any strides, one element per store.  Decided per image, not per row: rows [a, b) of an image start
+// at a multiple of stride_y from its first row, so the bands of one image agree.
+static int tensor_path(unsigned w, unsigned nplane, int dtype, long long stride_c, long long stride_y, long long stride_x, uintptr_t address)
+{
+        const unsigned store_bytes = 4 * j2p_tensor_element_bytes(dtype);
+        if(w < 4 || address % store_bytes != 0 || stride_y % 4 != 0) { return kTensorGeneric; }
+        if(stride_x == 1 && (nplane == 1 || stride_c % 4 == 0)) { return kTensorPlanar; }
+        if(nplane == 3 && stride_c == 1 && stride_x == 3) { return kTensorInterleaved; }
+        return kTensorGeneric;
+}
+
+int j2p_debug_tensor_path(unsigned w, unsigned nplane, int dtype, ptrdiff_t stride_c, ptrdiff_t stride_y, ptrdiff_t stride_x,
+                          uintptr_t data_address, int *path)
+{
+        if(!path || (nplane != 1 && nplane != 3) || dtype < J2P_DTYPE_U8 || dtype > J2P_DTYPE_F32 || w == 0 || stride_c < 1 || stride_y < 1 ||
+           stride_x < 1) {
+                return j2p_fail(J2P_EINVAL, "bad argument");
+        }
+        *path = tensor_path(w, nplane, dtype, stride_c, stride_y, stride_x, data_address);
+        return J2P_OK;
+}
+
+using TensorKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, TensorOut);
+
+// [three planes / one][dtype][path]; one plane has no interleaved layout (tensor_path never chooses it there)
+#define J2P_TENSOR_ROW(NPLANE, DTYPE, THIRD) {k_to_tensor<NPLANE, DTYPE, kTensorGeneric>, k_to_tensor<NPLANE, DTYPE, kTensorPlanar>, THIRD}
+#define J2P_TENSOR_ROWS(NPLANE, THIRD)                                                                                                     \
+        {J2P_TENSOR_ROW(NPLANE, kDtypeU8, THIRD(kDtypeU8)), J2P_TENSOR_ROW(NPLANE, kDtypeF16, THIRD(kDtypeF16)),                               \
+         J2P_TENSOR_ROW(NPLANE, kDtypeBF16, THIRD(kDtypeBF16)), J2P_TENSOR_ROW(NPLANE, kDtypeF32, THIRD(kDtypeF32))}
+#define J2P_TENSOR_INTERLEAVED(DTYPE) k_to_tensor<3, DTYPE, kTensorInterleaved>
+#define J2P_TENSOR_NONE(DTYPE) nullptr
+static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENSOR_INTERLEAVED), J2P_TENSOR_ROWS(1, J2P_TENSOR_NONE)};
+#undef J2P_TENSOR_NONE
+#undef J2P_TENSOR_INTERLEAVED
+#undef J2P_TENSOR_ROWS
+#undef J2P_TENSOR_ROW
+
+// What both tensor outputs check before they launch, in this order: the arguments, the solvers' state and rows (resolve_rows),
+// the 16-byte alignment of the canvas rows, and the destination's dtype, strides, address, scale / bias and device.  Gives the
+// planes' first rows and strides, the kernels' view of the destination and the view of planes[0].solver.
+static int tensor_resolve(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out,
+                          const float *ptr[3], unsigned stride[3], TensorOut &o, j2p_solver_view &s0)
+{
+        if(!planes || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(nplane != 1 && nplane != 3) { return j2p_fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
+        if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride, s0); rc != J2P_OK) { return rc; }
+        for(unsigned i = 0; i < nplane; i++) {
+                // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
+                if(stride[i] % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return j2p_fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
+        }
+        if(out->dtype != J2P_DTYPE_U8 && out->dtype != J2P_DTYPE_F16 && out->dtype != J2P_DTYPE_BF16 && out->dtype != J2P_DTYPE_F32) {
+                return j2p_fail(J2P_EINVAL, "to_tensor: unknown dtype %d", out->dtype);
+        }
+        if(out->stride_c < 1 || out->stride_y < 1 || out->stride_x < 1) {
+                return j2p_fail(J2P_EINVAL, "to_tensor: strides (%td, %td, %td) must all be at least 1 element", out->stride_c, out->stride_y, out->stride_x);
+        }
+        if(!out->data) { return j2p_fail(J2P_EINVAL, "to_tensor: data is NULL"); }
+        if(reinterpret_cast<uintptr_t>(out->data) % j2p_tensor_element_bytes(out->dtype) != 0) {
+                return j2p_fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", j2p_tensor_element_bytes(out->dtype));
+        }
+        o.data = out->data;
+        o.stride_c = out->stride_c;
+        o.stride_y = out->stride_y;
+        o.stride_x = out->stride_x;
+        for(unsigned k = 0; k < 3; k++) {
+                // (one plane: only entry 0 is used, the others are not looked at)
+                const float sc = k < nplane ? out->scale[k] : 1.f, bi = k < nplane ? out->bias[k] : 0.f;
+                if(!__builtin_isfinite(sc) || !__builtin_isfinite(bi)) { return j2p_fail(J2P_EINVAL, "to_tensor: scale / bias of channel %u is not finite", k); }
+                if(out->dtype == J2P_DTYPE_U8 && (sc != 1.f || bi != 0.f)) {
+                        return j2p_fail(J2P_EINVAL, "to_tensor: u8 elements are the 8-bit samples: scale must be 1 and bias 0 (channel %u)", k);
+                }
+                o.scale[k] = sc;
+                o.bias[k] = bi;
+        }
+        DeviceGuard guard(s0.device);
+        {
+                int device = -1;
+                if(j2p_device_of_pointer(out->data, &device) != J2P_OK || device != s0.device) {
+                        return j2p_fail(J2P_EINVAL, "to_tensor: data is not device memory of the solvers' device %d (managed and host memory are refused)", s0.device);
+                }
+        }
+        return J2P_OK;
+}
+
+// rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
+// memory, through k_to_tensor; out->data is the element of row y0.  Asynchronous: the kernel is queued on planes[0].solver's
+// stream and nothing waits for it.
+static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
+{
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o;
+        j2p_solver_view s0;
+        if(const int rc = tensor_resolve(planes, nplane, whole, w, y0, y1, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(s0.device);
+        const unsigned h = y1 - y0;
+        const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));
+        const TensorKernel kernel = kTensorKernels[nplane == 3 ? 0 : 1][out->dtype][path];
+        // a workgroup: 4 rows of 256 columns; grid-stride over rows from a grid of about 2048 workgroups, as k_to_samples'
+        const unsigned gx = (w + 255) / 256, row_groups = (h + 3) / 4;
+        const unsigned gy_cap = gx >= 2048 ? 1 : 2048 / gx;
+        const unsigned gy = row_groups < gy_cap ? row_groups : gy_cap;
+        hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(256), 0, s0.stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2], w, h, o);
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensor: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_device_of_pointer(const void *p, int *device)
+{
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        if(hipPointerGetAttributes(&attr, p) != hipSuccess) {
+                (void)hipGetLastError();                 // (plain host memory is an error to some runtimes, "unregistered" to others)
+                return J2P_EINVAL;
+        }
+        if(attr.type != hipMemoryTypeDevice || attr.isManaged) { return J2P_EINVAL; }
+        *device = attr.device;
+        return J2P_OK;
+}
+
+int j2p_planes_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_tensor *out)
+{
+        return tensor_rows(planes, nplane, true, w, 0, h, out);
+}
+
+int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned row_begin, unsigned row_end,
+                              const j2p_tensor *out)
+{
+        return tensor_rows(planes, nplane, false, w, row_begin, row_end, out);
+}
+
+// ---- resized tensor output: k_to_tensor_resized ----
+using ResizedKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);
+#define J2P_RESIZED_ROW(NPLANE) \
+        {k_to_tensor_resized<NPLANE, kDtypeU8>, k_to_tensor_resized<NPLANE, kDtypeF16>, k_to_tensor_resized<NPLANE, kDtypeBF16>, k_to_tensor_resized<NPLANE, kDtypeF32>}
+static const ResizedKernel kResizedKernels[2][4] = {J2P_RESIZED_ROW(3), J2P_RESIZED_ROW(1)};            // [three planes / one][dtype]
+#undef J2P_RESIZED_ROW
+
+// The tile of k_to_tensor_resized — output columns and consecutive output rows per wavefront — the only place that knows the
+// rule.  256 columns (64 lanes x 4) make a wavefront's source segment at least as long as k_to_tensor's 256 pixels at any
+// ratio; but a small output of a large image has few such tiles and every one of them a long footprint, so the tile is
+// halved while the chip (256 CUs x 4 SIMDs) would get fewer than two wavefronts per SIMD — not below 32 columns: the lanes
+// beyond the tile's columns only load and convert, they walk no taps.  Rows: a wavefront that owns several consecutive
+// output rows reads and converts the source row that two of them share once instead of twice (at ratios just above 1
+// that is every row) and spreads its set-up over them; up to 8, as long as about four wavefronts per SIMD remain.
+// Same bits for every tile: a column's sums do not depend on which lane or wavefront forms them.
+static void resize_tile(unsigned out_w, unsigned out_h, unsigned *lanes, unsigned *slots, unsigned *rows)
+{
+        unsigned tile = 64 * kResizeSlots;
+        while(tile > 32 && (unsigned long long)((out_w + tile - 1) / tile) * out_h < 2048) { tile /= 2; }
+        *lanes = tile < 64 ? tile : 64;
+        *slots = tile / *lanes;
+        const unsigned long long tiles = (out_w + tile - 1) / tile;
+        unsigned r = 8;
+        while(r > 1 && tiles * ((out_h + r - 1) / r) < 4096) { r /= 2; }
+        while(((out_h + r - 1) / r + 3) / 4 > 65535) { r *= 2; }                // (what a grid's y dimension may be)
+        *rows = r;
+}
+
+int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_resize *r,
+                                 const j2p_tensor *out)
+{
+        if(!planes || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_resize_error(r, w, h)) { return j2p_fail(J2P_EINVAL, "to_tensor: %s", why); }
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o;
+        j2p_solver_view s0;
+        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(s0.device);
+        ResizeGeom g;
+        g.box_x = r->box_x;
+        g.box_y = r->box_y;
+        const bool rx = r->out_w != r->box_w, ry = r->out_h != r->box_h;        // an axis that is not resized: one tap of weight 1
+        g.tap_bw = rx ? r->box_w : 1;
+        g.tap_ow = rx ? r->out_w : 1;
+        g.tap_bh = ry ? r->box_h : 1;
+        g.tap_oh = ry ? r->out_h : 1;
+        g.out_w = r->out_w;
+        g.out_h = r->out_h;
+        g.div_x = rx ? (float)r->box_w : 0.f;
+        g.div_y = ry ? (float)r->box_h : 0.f;
+        resize_tile(r->out_w, r->out_h, &g.lanes, &g.slots, &g.rows);
+        // what lets the kernel step from one column's taps to the next without dividing
+        g.qx = g.tap_bw / g.tap_ow;
+        g.rx = g.tap_bw % g.tap_ow;
+        g.qy = g.tap_bh / g.tap_oh;
+        g.ry = g.tap_bh % g.tap_oh;
+        g.qlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw / g.tap_ow);
+        g.rlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw % g.tap_ow);
+        // a workgroup: 4 wavefronts, one above the other, of one tile
+        const unsigned tile = g.lanes * g.slots, gx = (r->out_w + tile - 1) / tile, gy = ((r->out_h + g.rows - 1) / g.rows + 3) / 4;
+        hipLaunchKernelGGL(kResizedKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(gx, gy), dim3(256), 0, s0.stream, ptr[0], stride[0], ptr[1],
+                           stride[1], ptr[2], stride[2], g, o);
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensor_resized: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+// block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
+// 1/sub_w x 1/sub_h of its resolution (k_quantise_blocks<sub_w, sub_h>): output block row r covers canvas rows
+// [8 * sub_h * r, 8 * sub_h * (r + 1)).  `whole`: called as a whole-canvas form, which band solvers refuse.
+static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
+                         unsigned r1, const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(!plane || !quant_table || !out_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(blocks_w == 0 || r0 >= r1) { return j2p_fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
+        const j2p_solver_view s = plane->solver ? j2p_solver_view_of(plane->solver) : j2p_solver_view{};
+        if(whole && plane->solver && !s.whole) {
+                return j2p_fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: the j2p_planes_rows_to_coefficients forms)");
+        }
+        if(sub_w < 1 || sub_w > 2 || sub_h < 1 || sub_h > 2) {
+                return j2p_fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
+        }
+        if(!plane->solver || plane->channel >= s.nch) { return j2p_fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
+        QuantSteps steps;
+        for(int j = 0; j < 64; j++) {
+                if(quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
+                steps.q[j] = (float)quant_table[j];
+        }
+        // One rule for every sampling: every block starts inside the solver's rows and columns, and rows beyond the band are
+        // replicated only where the band ends with the canvas (a band that is not the last ends on a multiple of 16).  For 1x1
+        // that is "the whole grid inside": W, the band's rows and every block's start are multiples of 8, so a block that starts
+        // inside ends inside.
+        const unsigned long long row_end = (unsigned long long)s.row0 + s.rows, step_y = 8ull * sub_h;
+        if(8ull * sub_w * (blocks_w - 1) >= s.W || step_y * r0 < s.row0 || step_y * (r1 - 1) >= row_end ||
+           (step_y * r1 > row_end && row_end != s.H)) {
+                return j2p_fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks of %ux%u-pixel samples are not inside the solver's rows "
+                            "[%u,%u) x %u columns (every block must start there; only the canvas's last rows and columns are replicated)",
+                            r0, r1, blocks_w, sub_w, sub_h, s.row0, s.row0 + s.rows, s.W);
+        }
+        if(s.mid_iteration) { return j2p_fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
+        const unsigned first = (unsigned)(step_y * r0);
+        const float *src = nullptr;
+        if(const int rc = j2p_solver_row(plane->solver, plane->channel, first, &src); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(s.device);
+        const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
+        void *dout = nullptr;
+        size_t dout_bytes = 0;
+        HIP_TRY(j2p_pool_take(s.device, bytes, &dout, &dout_bytes));
+        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
+        const auto kernel = sub_w == 2 ? (sub_h == 2 ? k_quantise_blocks<2, 2> : k_quantise_blocks<2, 1>)
+                                       : (sub_h == 2 ? k_quantise_blocks<1, 2> : k_quantise_blocks<1, 1>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s.stream, src, s.W, (unsigned)(row_end - first),
+                           blocks_w, r1 - r0, steps, static_cast<int16_t *>(dout));
+        hipError_t e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s.stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(s.stream); }
+        j2p_pool_give(s.device, dout, dout_bytes);
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_coefficients: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h, const uint16_t quant_table[64],
+                               int16_t *out_host)
+{
+        return quantise_rows(plane, true, 1, 1, blocks_w, 0, blocks_h, quant_table, out_host);
+}
+
+int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned block_row_begin, unsigned block_row_end,
+                                    const uint16_t quant_table[64], int16_t *out_host)
+{
+        return quantise_rows(plane, false, 1, 1, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+}
+
+int j2p_planes_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned blocks_h,
+                                   const uint16_t quant_table[64], int16_t *out_host)
+{
+        return quantise_rows(plane, true, sub_w, sub_h, blocks_w, 0, blocks_h, quant_table, out_host);
+}
+
+int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w,
+                                        unsigned block_row_begin, unsigned block_row_end, const uint16_t quant_table[64], int16_t *out_host)
+{
+        return quantise_rows(plane, false, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+}
+
+}  // extern "C"

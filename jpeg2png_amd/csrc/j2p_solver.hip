@@ -17,6 +17,7 @@
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
+#include "j2p_hip_host.h"
 #include "j2p_kernels.hip.h"
 
 using namespace j2p;
@@ -24,15 +25,6 @@ using namespace j2p;
 namespace {
 
 thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-        va_list l;
-        va_start(l, fmt);
-        vsnprintf(g_err, sizeof(g_err), fmt, l);
-        va_end(l);
-        return code;
-}
 
 }  // namespace
 
@@ -46,15 +38,6 @@ int j2p_fail(int code, const char *fmt, ...)
 }
 
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-        do {                                                                                       \
-                hipError_t e_ = (expr);                                                            \
-                if(e_ != hipSuccess) {                                                             \
-                        return fail(e_ == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE,          \
-                                    "%s failed: %s", #expr, hipGetErrorString(e_));                \
-                }                                                                                  \
-        } while(0)
 
 struct ChanHost {
         unsigned cw = 0, ch = 0, ws = 1, hs = 1;
@@ -122,7 +105,7 @@ struct j2p_solver {
         int cur = 0;             // xbuf[cur] is x_k
         bool grad_done = false;
         bool proj_boundary_done = false;   // between the two parts of a split projection phase
-        void *arena = nullptr;   // the one device allocation everything below is carved from (pooled, see pool_take)
+        void *arena = nullptr;   // the one device allocation everything below is carved from (pooled, see j2p_pool_take)
         size_t arena_bytes = 0;
         // reductions
         bool fold = false;       // level 1 of the norm reduction inside k_gradient (J2P_OPT_NORM_FOLD; default: norm_defaults)
@@ -179,20 +162,6 @@ struct j2p_solver {
 
 namespace {
 
-struct DeviceGuard {
-        int prev = -1;
-        bool ok = true;
-        explicit DeviceGuard(int dev)
-        {
-                if(hipGetDevice(&prev) != hipSuccess) { prev = -1; }
-                if(prev != dev) { ok = hipSetDevice(dev) == hipSuccess; }
-        }
-        ~DeviceGuard()
-        {
-                if(prev >= 0) { (void)hipSetDevice(prev); }
-        }
-};
-
 // ---------------------------------------------------------------------------
 // Device-memory pool.  hipMalloc / hipFree cost milliseconds and hipFree synchronises the whole device, which
 // serialises the concurrent compute() calls of a multi-threaded host (jpeg2png.c:147,330) far more than the
@@ -246,7 +215,10 @@ hipError_t dev_malloc(void **out, size_t bytes)
         return e;
 }
 
-hipError_t pool_take(int device, size_t bytes, void **out, size_t *got)
+}  // namespace
+
+// (j2p_internal.h: the output stage's device buffers come from the pool too)
+hipError_t j2p_pool_take(int device, size_t bytes, void **out, size_t *got)
 {
         {
                 std::lock_guard<std::mutex> g(g_pool_lock);
@@ -268,7 +240,7 @@ hipError_t pool_take(int device, size_t bytes, void **out, size_t *got)
         return dev_malloc(out, bytes);
 }
 
-void pool_give(int device, void *ptr, size_t bytes)
+void j2p_pool_give(int device, void *ptr, size_t bytes)
 {
         if(!ptr) { return; }
         {
@@ -284,6 +256,8 @@ void pool_give(int device, void *ptr, size_t bytes)
         }
         (void)hipFree(ptr);
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // What is live on each device, for the non-temporal policy (nt_policy): the Infinity Cache is shared by every
@@ -585,7 +559,7 @@ static void launch_rowsums(j2p_solver *s)
 // the end of a gradient phase — of a split one: on the solver's stream, which the caller has made wait for the boundary part
 int do_rowsums(j2p_solver *s)
 {
-        if(!s->grad_done) { return fail(J2P_ESTATE, "rowsums without a finished gradient phase"); }
+        if(!s->grad_done) { return j2p_fail(J2P_ESTATE, "rowsums without a finished gradient phase"); }
         if(!s->finish_pending) { return J2P_OK; }      // (a whole phase has finished itself)
         if(s->plan.level1 == J2P_NORM_L1_ROWSUMS) { launch_rowsums(s); }
         if(s->phase_log && s->log_phases) { launch_band_log(s, 0); }
@@ -596,10 +570,10 @@ int do_rowsums(j2p_solver *s)
 
 int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nullptr)
 {
-        if(s->grad_done) { return fail(J2P_ESTATE, "phase_gradient called twice without phase_project"); }
-        if(part == 2 && !s->interior_done) { return fail(J2P_ESTATE, "gradient boundary part before the interior part"); }
-        if(part != 2 && s->interior_done) { return fail(J2P_ESTATE, "gradient interior part issued twice"); }
-        if(part != 0 && s->nseg < 3) { return fail(J2P_ESTATE, "band too short to split the gradient phase"); }
+        if(s->grad_done) { return j2p_fail(J2P_ESTATE, "phase_gradient called twice without phase_project"); }
+        if(part == 2 && !s->interior_done) { return j2p_fail(J2P_ESTATE, "gradient boundary part before the interior part"); }
+        if(part != 2 && s->interior_done) { return j2p_fail(J2P_ESTATE, "gradient interior part issued twice"); }
+        if(part != 0 && s->nseg < 3) { return j2p_fail(J2P_ESTATE, "band too short to split the gradient phase"); }
         if(!st) { st = s->stream; }
         if(part != 2) {
                 // the iteration's norm plan, decided here once; a band learns only in do_phase_project whether ITS phase is split
@@ -637,7 +611,7 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.rowsum = rowsums_of(s, s->iter);
         a.push = nullptr;
         if(s->linked) {
-                if(part != 0) { return fail(J2P_ESTATE, "linked bands run whole phases (there is no exchange to hide)"); }
+                if(part != 0) { return j2p_fail(J2P_ESTATE, "linked bands run whole phases (there is no exchange to hide)"); }
                 a.push = s->push_dev + (s->iter & 1);
         }
         a.norm_out = s->plan.level2 == J2P_NORM_L2_GRADIENT ? s->norm : nullptr;
@@ -728,12 +702,12 @@ bool projects_mixed(const j2p_solver *s, int nip)
 int do_phase_project(j2p_solver *s, bool log, int part = 0)
 {
         const hipStream_t st = s->stream;
-        if(!s->grad_done) { return fail(J2P_ESTATE, "phase_project called before phase_gradient"); }
-        if(rowsums_owed(s)) { return fail(J2P_ESTATE, "phase_project before j2p_solver_phase_rowsums"); }
+        if(!s->grad_done) { return j2p_fail(J2P_ESTATE, "phase_project called before phase_gradient"); }
+        if(rowsums_owed(s)) { return j2p_fail(J2P_ESTATE, "phase_project before j2p_solver_phase_rowsums"); }
         // the two phases of an iteration must agree on logging: where the norm is reduced depends on it
-        if(log != s->phase_log) { return fail(J2P_ESTATE, "phase_project: logging differs from this iteration's gradient phase"); }
-        if(part == 2 && !s->proj_boundary_done) { return fail(J2P_ESTATE, "interior part of phase_project before the boundary part"); }
-        if(part != 2 && s->proj_boundary_done) { return fail(J2P_ESTATE, "boundary part of phase_project issued twice"); }
+        if(log != s->phase_log) { return j2p_fail(J2P_ESTATE, "phase_project: logging differs from this iteration's gradient phase"); }
+        if(part == 2 && !s->proj_boundary_done) { return j2p_fail(J2P_ESTATE, "interior part of phase_project before the boundary part"); }
+        if(part != 2 && s->proj_boundary_done) { return j2p_fail(J2P_ESTATE, "boundary part of phase_project issued twice"); }
         unsigned P = 1;
         while(P < s->ntr_global) { P <<= 1; }
         // the global [tile row][channel] sums a band solver finishes ||g|| from: gathered by the caller, or — linked
@@ -778,7 +752,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         if(s->linked) {
                 // the band's edge rows of x_{k+1} also go into the neighbours' halo rows of the buffer being written
                 // (only the NIP 2 instantiations store them: a linked band always takes those)
-                if(nip != 2) { return fail(J2P_ESTATE, "linked bands: ||g|| must be reduced inside k_project (whole phases, at most %u tile rows, J2P_BAND_NIP not 0)", J2P_NORM_TREE_ROWS); }
+                if(nip != 2) { return j2p_fail(J2P_ESTATE, "linked bands: ||g|| must be reduced inside k_project (whole phases, at most %u tile rows, J2P_BAND_NIP not 0)", J2P_NORM_TREE_ROWS); }
                 for(unsigned c = 0; c < s->nch; c++) {
                         a.halo_up[c] = s->links.up_halo[s->cur ^ 1][c];
                         a.halo_down[c] = s->links.down_halo[s->cur ^ 1][c];
@@ -918,7 +892,7 @@ void j2p_debug_fail_run_after(int n)
 
 int j2p_device_count(int *count)
 {
-        if(!count) { return fail(J2P_EINVAL, "count is NULL"); }
+        if(!count) { return j2p_fail(J2P_EINVAL, "count is NULL"); }
         int n = 0;
         if(hipGetDeviceCount(&n) != hipSuccess) { n = 0; }
         *count = n;
@@ -931,7 +905,7 @@ void j2p_solver_destroy(j2p_solver *s)
         DeviceGuard guard(s->device);
         if(s->stream) { (void)hipStreamSynchronize(s->stream); }
         if(s->live_registered) { live_add(s->device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, -1); }
-        pool_give(s->device, s->arena, s->arena_bytes);
+        j2p_pool_give(s->device, s->arena, s->arena_bytes);
         (void)hipFree(s->logsums);
         (void)hipFree(s->log_band);
         (void)hipFree(s->trace);
@@ -945,50 +919,50 @@ void j2p_pool_trim(void) { pool_drop_all(); }
 int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
                       float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
 {
-        if(!out || !planes || !pweight) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!out || !planes || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *out = nullptr;
-        if(nchannel == 0 || nchannel > kMaxCh) { return fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
+        if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
         unsigned W = 0, H = 0, align = (unsigned)J2P_TILE_ROWS;
         for(unsigned c = 0; c < nchannel; c++) {
                 const j2p_plane &p = planes[c];
                 if(p.w == 0 || p.h == 0 || (p.w & 7) || (p.h & 7)) {
-                        return fail(J2P_EINVAL, "channel %u: coefficient plane %ux%u is not a positive multiple of 8 (box.c:6-7)", c, p.w, p.h);
+                        return j2p_fail(J2P_EINVAL, "channel %u: coefficient plane %ux%u is not a positive multiple of 8 (box.c:6-7)", c, p.w, p.h);
                 }
-                if(p.w_samp == 0 || p.h_samp == 0) { return fail(J2P_EINVAL, "channel %u: zero sampling factor", c); }
-                if(!p.data || !p.quant_table) { return fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
+                if(p.w_samp == 0 || p.h_samp == 0) { return j2p_fail(J2P_EINVAL, "channel %u: zero sampling factor", c); }
+                if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
                 for(int j = 0; j < 64; j++) {
-                        if(p.quant_table[j] == 0) { return fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
+                        if(p.quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
                 }
                 if(p.w * p.w_samp > W) { W = p.w * p.w_samp; }     // compute.c:410-416
                 if(p.h * p.h_samp > H) { H = p.h * p.h_samp; }
                 align = lcm_u(align, 8 * p.h_samp);
         }
-        if(H > (unsigned)kMaxTileRows * kTY) { return fail(J2P_EINVAL, "canvas height %u exceeds %u", H, kMaxTileRows * kTY); }   // (shorter tile rows: only far below)
+        if(H > (unsigned)kMaxTileRows * kTY) { return j2p_fail(J2P_EINVAL, "canvas height %u exceeds %u", H, kMaxTileRows * kTY); }   // (shorter tile rows: only far below)
         bool whole = band.row_begin == 0 && (band.row_end == 0 || band.row_end >= H);
         if(whole && (band_local_arrays & J2P_BAND_EVEN_IF_WHOLE) && band.row_end >= H) { whole = false; band.row_end = H; }
         unsigned row0 = whole ? 0 : band.row_begin, row1 = whole ? H : band.row_end;
         if(!whole) {
-                if(row0 >= row1 || row1 > H) { return fail(J2P_EINVAL, "bad band [%u,%u) for canvas height %u", row0, row1, H); }
+                if(row0 >= row1 || row1 > H) { return j2p_fail(J2P_EINVAL, "bad band [%u,%u) for canvas height %u", row0, row1, H); }
                 if(row0 % align || (row1 % align && row1 != H)) {
-                        return fail(J2P_EINVAL, "band [%u,%u) must be aligned to %u rows", row0, row1, align);
+                        return j2p_fail(J2P_EINVAL, "band [%u,%u) must be aligned to %u rows", row0, row1, align);
                 }
         }
         int ndev = 0;
         if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-                return fail(J2P_EDEVICE, "no HIP device available: the jpeg2png_amd solver has no CPU fallback");
+                return j2p_fail(J2P_EDEVICE, "no HIP device available: the jpeg2png_amd solver has no CPU fallback");
         }
-        if(device < 0 || device >= ndev) { return fail(J2P_EINVAL, "device %d out of range (0..%d)", device, ndev - 1); }
+        if(device < 0 || device >= ndev) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, ndev - 1); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
 
         // k_norm_whole (only the A/B baseline of the folded reduction, J2P_OPT_NORM_FOLD = 0) stages the norm
         // partials in up to 156 KiB of dynamic LDS (per device: idempotent)
         if(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_norm_whole), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)kNormLdsBytes) != hipSuccess) {
-                return fail(J2P_EDEVICE, "hipFuncSetAttribute(k_norm_whole, %u bytes of LDS) failed", kNormLdsBytes);
+                return j2p_fail(J2P_EDEVICE, "hipFuncSetAttribute(k_norm_whole, %u bytes of LDS) failed", kNormLdsBytes);
         }
         j2p_solver *s = new(std::nothrow) j2p_solver();
-        if(!s) { return fail(J2P_ENOMEM, "host allocation failed"); }
+        if(!s) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
         s->device = device;
         s->nch = nchannel;
         s->W = W;
@@ -1013,7 +987,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         do {                                                                                       \
                 hipError_t e_ = (expr);                                                            \
                 if(e_ != hipSuccess) {                                                             \
-                        rc = fail(e_ == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE,            \
+                        rc = j2p_fail(e_ == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE,            \
                                   "%s failed: %s", #expr, hipGetErrorString(e_));                  \
                         j2p_solver_destroy(s);                                                     \
                         return rc;                                                                 \
@@ -1040,7 +1014,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                 // rows of the decoded input the init kernel touches (own rows + halo, clamped like compute.c:298)
                 if(s->band_local) {
                         if(h.ch * h.hs < H) {
-                                rc = fail(J2P_EINVAL, "band-local arrays need every channel to cover the canvas height");
+                                rc = j2p_fail(J2P_EINVAL, "band-local arrays need every channel to cover the canvas height");
                                 j2p_solver_destroy(s);
                                 return rc;
                         }
@@ -1128,7 +1102,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         Carver carve;
         for(int pass = 0; pass < 2; pass++) {
                 if(pass == 1) {
-                        CREATE_TRY(pool_take(device, carve.used + 256, &s->arena, &s->arena_bytes));
+                        CREATE_TRY(j2p_pool_take(device, carve.used + 256, &s->arena, &s->arena_bytes));
                         carve.base = static_cast<char *>(s->arena);
                         carve.used = 0;
                 }
@@ -1234,7 +1208,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                         } else {
                                 // scratch: the first x buffer holds (rows + 4) * W floats >= the window's int16 data
                                 if(!h.scratch_d && (size_t)nb_rows * 8 * h.cw * sizeof(int16_t) > plane_floats * sizeof(float)) {
-                                        rc = fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
+                                        rc = j2p_fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
                                         j2p_solver_destroy(s);
                                         return rc;
                                 }
@@ -1249,7 +1223,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                         } else {
                                 // window not block aligned (halo rows of a band): decode into the second x buffer, copy the rows
                                 if(!h.scratch_f && (size_t)nb_rows * 8 * h.cw > plane_floats) {
-                                        rc = fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
+                                        rc = j2p_fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
                                         j2p_solver_destroy(s);
                                         return rc;
                                 }
@@ -1293,18 +1267,18 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
 
 int j2p_solver_debug_option(j2p_solver *s, int option, int value)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(s->grad_done || s->interior_done) { return fail(J2P_ESTATE, "options change between iterations only"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(s->grad_done || s->interior_done) { return j2p_fail(J2P_ESTATE, "options change between iterations only"); }
         switch(option) {
         case J2P_OPT_NORM_FOLD:
-                if((s->rowsum_alternate || s->linked) && !value) { return fail(J2P_ESTATE, "alternating / pushed row sums need the folded norm reduction"); }
+                if((s->rowsum_alternate || s->linked) && !value) { return j2p_fail(J2P_ESTATE, "alternating / pushed row sums need the folded norm reduction"); }
                 if(value && !s->fold) {
                         // (the slots must not carry the coming iteration's parity yet, see launch_init)
                         DeviceGuard guard(s->device);
                         HIP_TRY(hipMemsetAsync(s->part_g2, (s->iter & 1) ? 0x00 : 0xff, (size_t)s->ntx * s->ntr_local * s->nch * sizeof(double), s->stream));
                 }
                 // 0: reduction launch between the phases; 1: folded into k_gradient by tickets
-                if(value != 0 && value != 1) { return fail(J2P_EINVAL, "J2P_OPT_NORM_FOLD is 0 or 1"); }
+                if(value != 0 && value != 1) { return j2p_fail(J2P_EINVAL, "J2P_OPT_NORM_FOLD is 0 or 1"); }
                 s->fold = value == 1;
                 break;
         case J2P_OPT_NORM_IN_PROJECT:
@@ -1324,21 +1298,21 @@ int j2p_solver_debug_option(j2p_solver *s, int option, int value)
                 s->wide_footprint = value != 0;
                 set_wide_footprint(s);
                 break;
-        default: return fail(J2P_EINVAL, "unknown option %d", option);
+        default: return j2p_fail(J2P_EINVAL, "unknown option %d", option);
         }
         return J2P_OK;
 }
 
 int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *bytes)
 {
-        if(!s || !bytes || c >= s->nch) { return fail(J2P_EINVAL, "j2p_solver_coefficient_bytes: bad argument"); }
+        if(!s || !bytes || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_coefficient_bytes: bad argument"); }
         *bytes = s->ch[c].narrow ? 1u : 2u;
         return J2P_OK;
 }
 
 int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on)
 {
-        if(!s || !on || c >= s->nch) { return fail(J2P_EINVAL, "j2p_solver_wide_footprint: bad argument"); }
+        if(!s || !on || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_wide_footprint: bad argument"); }
         // (k_project_mixed has no wide-footprint path; NIP 2 — bands of whole phases — never takes the mixed launch)
         *on = s->ch[c].wide && !projects_mixed(s, plan_of(s, false, false).nip()) ? 1u : 0u;
         return J2P_OK;
@@ -1346,7 +1320,7 @@ int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on)
 
 int j2p_solver_trace(j2p_solver *s, int on, unsigned long long *host_out, unsigned max_records, unsigned *n)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
 #ifdef J2P_TRACE
         DeviceGuard guard(s->device);
         constexpr unsigned kCap = 1u << 19;                     // records (16 MiB)
@@ -1369,7 +1343,7 @@ int j2p_solver_trace(j2p_solver *s, int on, unsigned long long *host_out, unsign
         return J2P_OK;
 #else
         (void)on; (void)host_out; (void)max_records; (void)n;
-        return fail(J2P_ESTATE, "not a J2P_TRACE build");
+        return j2p_fail(J2P_ESTATE, "not a J2P_TRACE build");
 #endif
 }
 
@@ -1388,7 +1362,7 @@ int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsi
 {
         // the map of k_gradient's launch (grad_item) evaluated on the HOST, wavefront by wavefront: no device needed
         if(!items || !n_items || !workgroups || W < 8 || rows == 0 || rows_per_tile == 0 || channel_wavefronts < 1 || channel_wavefronts > 3) {
-                return fail(J2P_EINVAL, "bad argument");
+                return j2p_fail(J2P_EINVAL, "bad argument");
         }
         Geo g;
         memset(&g, 0, sizeof(g));
@@ -1424,7 +1398,7 @@ int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsi
 int j2p_debug_norm_plan(int whole, int fold, int norm_in_project, int band_nip, unsigned tile_rows, int split, int log,
                         int *level1, int *level2, unsigned *launches)
 {
-        if(!level1 || !level2 || !launches || norm_in_project < 0 || norm_in_project > 2 || tile_rows == 0) { return fail(J2P_EINVAL, "bad argument"); }
+        if(!level1 || !level2 || !launches || norm_in_project < 0 || norm_in_project > 2 || tile_rows == 0) { return j2p_fail(J2P_EINVAL, "bad argument"); }
         const NormPlan p = norm_plan(whole != 0, fold != 0, norm_in_project, band_nip != 0, tile_rows, split != 0, log != 0);
         *level1 = p.level1;
         *level2 = p.level2;
@@ -1443,7 +1417,7 @@ int j2p_debug_build(void)
 
 int j2p_solver_debug_violations(j2p_solver *s, unsigned long long *count, unsigned *site, unsigned long long *offset)
 {
-        if(!s || !count) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !count) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
 #ifdef J2P_DEBUG
         unsigned long long h[3] = {0, 0, 0};
         DeviceGuard guard(s->device);
@@ -1456,13 +1430,13 @@ int j2p_solver_debug_violations(j2p_solver *s, unsigned long long *count, unsign
 #else
         (void)site;
         (void)offset;
-        return fail(J2P_ESTATE, "not a J2P_DEBUG build: the address checks are compiled out");
+        return j2p_fail(J2P_ESTATE, "not a J2P_DEBUG build: the address checks are compiled out");
 #endif
 }
 
 int j2p_solver_canvas(const j2p_solver *s, unsigned *W, unsigned *H)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         if(W) { *W = s->W; }
         if(H) { *H = s->H; }
         return J2P_OK;
@@ -1470,7 +1444,7 @@ int j2p_solver_canvas(const j2p_solver *s, unsigned *W, unsigned *H)
 
 int j2p_solver_band(const j2p_solver *s, unsigned *row_begin, unsigned *row_end)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         if(row_begin) { *row_begin = s->row0; }
         if(row_end) { *row_end = s->row0 + s->rows; }
         return J2P_OK;
@@ -1478,7 +1452,7 @@ int j2p_solver_band(const j2p_solver *s, unsigned *row_begin, unsigned *row_end)
 
 int j2p_solver_launches_per_iteration(const j2p_solver *s, unsigned *n)
 {
-        if(!s || !n) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !n) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         // (unlogged runs of whole phases; logging adds the log kernels and moves level 2 out of k_project)
         *n = 2 + plan_of(s, false, false).launches();
         return J2P_OK;
@@ -1486,7 +1460,7 @@ int j2p_solver_launches_per_iteration(const j2p_solver *s, unsigned *n)
 
 int j2p_solver_reset(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         int rc = flush_timing(s);
         if(rc != J2P_OK) { return rc; }
@@ -1496,48 +1470,48 @@ int j2p_solver_reset(j2p_solver *s)
 
 int j2p_solver_phase_gradient(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         return do_phase_gradient(s, s->log_phases);
 }
 
 int j2p_solver_phase_gradient_part(j2p_solver *s, int part, void *stream)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         (void)stream;
 #ifndef J2P_EXPERIMENTS
         // (measured slower than whole phases wherever tried, DESIGN.md section 10: the release build keeps the entry points, not the schedule)
         (void)part;
-        return fail(J2P_ESTATE, "split phases exist in the experiments build only (buildlib.build_experiments)");
+        return j2p_fail(J2P_ESTATE, "split phases exist in the experiments build only (buildlib.build_experiments)");
 #endif
-        if(part != J2P_GRADIENT_INTERIOR && part != J2P_GRADIENT_EDGES) { return fail(J2P_EINVAL, "part must be J2P_GRADIENT_INTERIOR or J2P_GRADIENT_EDGES"); }
+        if(part != J2P_GRADIENT_INTERIOR && part != J2P_GRADIENT_EDGES) { return j2p_fail(J2P_EINVAL, "part must be J2P_GRADIENT_INTERIOR or J2P_GRADIENT_EDGES"); }
         DeviceGuard guard(s->device);
         return do_phase_gradient(s, s->log_phases, part, (hipStream_t)stream);
 }
 
 int j2p_solver_phase_rowsums(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         return do_rowsums(s);
 }
 
 int j2p_solver_phase_project(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         return do_phase_project(s, s->log_phases);
 }
 
 int j2p_solver_phase_project_part(j2p_solver *s, int part)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
 #ifndef J2P_EXPERIMENTS
         // (measured slower than whole phases wherever tried, DESIGN.md section 10: the release build keeps the entry points, not the schedule)
         (void)part;
-        return fail(J2P_ESTATE, "split phases exist in the experiments build only (buildlib.build_experiments)");
+        return j2p_fail(J2P_ESTATE, "split phases exist in the experiments build only (buildlib.build_experiments)");
 #endif
-        if(part != J2P_PROJECT_BOUNDARY && part != J2P_PROJECT_INTERIOR) { return fail(J2P_EINVAL, "part must be J2P_PROJECT_BOUNDARY or J2P_PROJECT_INTERIOR"); }
+        if(part != J2P_PROJECT_BOUNDARY && part != J2P_PROJECT_INTERIOR) { return j2p_fail(J2P_EINVAL, "part must be J2P_PROJECT_BOUNDARY or J2P_PROJECT_INTERIOR"); }
         DeviceGuard guard(s->device);
         return do_phase_project(s, s->log_phases, part);
 }
@@ -1595,8 +1569,8 @@ extern "C" {
 int j2p_log_rows_from_sums(unsigned nchannel, float weight, const float pweight[], unsigned n, const double *sums,
                            j2p_log_row *rows)
 {
-        if(!pweight || !sums || !rows) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(nchannel == 0 || nchannel > kMaxCh) { return fail(J2P_EINVAL, "nchannel must be 1..3"); }
+        if(!pweight || !sums || !rows) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3"); }
         double carried[kMaxCh] = {0., 0., 0.};
         rows_from_sums(nchannel, weight, pweight, n, sums, carried, true, rows);
         return J2P_OK;
@@ -1604,11 +1578,11 @@ int j2p_log_rows_from_sums(unsigned nchannel, float weight, const float pweight[
 
 int j2p_solver_set_logging(j2p_solver *s, int on)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         // like the schedule switches: the two phases of an iteration have to agree on it (where the norm is reduced
         // depends on it)
-        if(s->grad_done || s->interior_done) { return fail(J2P_ESTATE, "logging changes between iterations only"); }
+        if(s->grad_done || s->interior_done) { return j2p_fail(J2P_ESTATE, "logging changes between iterations only"); }
         if(on && !s->log_band) {
                 HIP_TRY(dev_malloc((void **)&s->log_band, (2 + kMaxCh) * sizeof(double)));
                 HIP_TRY(hipMemsetAsync(s->log_band, 0, (2 + kMaxCh) * sizeof(double), s->stream));
@@ -1619,9 +1593,9 @@ int j2p_solver_set_logging(j2p_solver *s, int on)
 
 int j2p_solver_run(j2p_solver *s, unsigned n, j2p_log_row *rows)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(!s->whole) { return fail(J2P_ESTATE, "j2p_solver_run needs a whole-canvas solver; drive bands with the phase calls"); }
-        if(j2p_injected_failure()) { return fail(J2P_EDEVICE, "injected failure (j2p_debug_fail_run_after)"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s->whole) { return j2p_fail(J2P_ESTATE, "j2p_solver_run needs a whole-canvas solver; drive bands with the phase calls"); }
+        if(j2p_injected_failure()) { return j2p_fail(J2P_EDEVICE, "injected failure (j2p_debug_fail_run_after)"); }
         DeviceGuard guard(s->device);
         const bool log = rows != nullptr;
         constexpr unsigned kRow = 2 + kMaxCh;
@@ -1669,7 +1643,7 @@ int j2p_solver_run(j2p_solver *s, unsigned n, j2p_log_row *rows)
 
 int j2p_solver_exchange_info(j2p_solver *s, j2p_exchange *info)
 {
-        if(!s || !info) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !info) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         memset(info, 0, sizeof(*info));
         info->partials_local = s->rowsum_local;
         info->local_tile_rows = s->ntr_local;
@@ -1692,14 +1666,14 @@ int j2p_solver_exchange_info(j2p_solver *s, j2p_exchange *info)
 
 int j2p_solver_stream(j2p_solver *s, void **stream)
 {
-        if(!s || !stream) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !stream) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *stream = (void *)s->stream;
         return J2P_OK;
 }
 
 int j2p_solver_halo_rows(j2p_solver *s, int buffer, j2p_exchange *info)
 {
-        if(!s || !info || (buffer != 0 && buffer != 1)) { return fail(J2P_EINVAL, "bad argument"); }
+        if(!s || !info || (buffer != 0 && buffer != 1)) { return j2p_fail(J2P_EINVAL, "bad argument"); }
         memset(info, 0, sizeof(*info));
         info->halo_floats = (size_t)kHalo * s->W;
         for(unsigned c = 0; c < s->nch; c++) {
@@ -1714,10 +1688,10 @@ int j2p_solver_halo_rows(j2p_solver *s, int buffer, j2p_exchange *info)
 
 int j2p_solver_alternate_rowsums(j2p_solver *s, const double *buffers[2])
 {
-        if(!s || !buffers) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(s->whole || !s->rowsum_odd) { return fail(J2P_ESTATE, "alternating row sums are for band solvers"); }
-        if(!s->fold) { return fail(J2P_ESTATE, "alternating row sums need the folded norm reduction"); }
-        if(s->linked) { return fail(J2P_ESTATE, "alternating row sums: this solver's bands are linked (its sums go to the global arrays)"); }
+        if(!s || !buffers) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(s->whole || !s->rowsum_odd) { return j2p_fail(J2P_ESTATE, "alternating row sums are for band solvers"); }
+        if(!s->fold) { return j2p_fail(J2P_ESTATE, "alternating row sums need the folded norm reduction"); }
+        if(s->linked) { return j2p_fail(J2P_ESTATE, "alternating row sums: this solver's bands are linked (its sums go to the global arrays)"); }
         s->rowsum_alternate = true;
         buffers[0] = s->rowsum_local;
         buffers[1] = s->rowsum_odd;
@@ -1726,8 +1700,8 @@ int j2p_solver_alternate_rowsums(j2p_solver *s, const double *buffers[2])
 
 int j2p_solver_global_rowsums(j2p_solver *s, double *arrays[2])
 {
-        if(!s || !arrays) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(s->whole || !s->rowsum_all_odd) { return fail(J2P_ESTATE, "global row sums: band solvers only"); }
+        if(!s || !arrays) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(s->whole || !s->rowsum_all_odd) { return j2p_fail(J2P_ESTATE, "global row sums: band solvers only"); }
         arrays[0] = s->rowsum_all;
         arrays[1] = s->rowsum_all_odd;
         return J2P_OK;
@@ -1735,36 +1709,36 @@ int j2p_solver_global_rowsums(j2p_solver *s, double *arrays[2])
 
 int j2p_solver_link_bands(j2p_solver *s, const j2p_band_links *links)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(s->grad_done || s->interior_done) { return fail(J2P_ESTATE, "bands are linked between iterations only"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(s->grad_done || s->interior_done) { return j2p_fail(J2P_ESTATE, "bands are linked between iterations only"); }
         if(!links) {
                 s->linked = false;
                 return J2P_OK;
         }
-        if(s->whole) { return fail(J2P_ESTATE, "link_bands: band solvers only"); }
-        if(!s->fold) { return fail(J2P_ESTATE, "link_bands needs the folded norm reduction (the row sums leave from inside k_gradient)"); }
-        if(s->rowsum_alternate) { return fail(J2P_ESTATE, "link_bands: this solver's row sums already alternate for norm_from_bands"); }
-        if(links->npush == 0 || links->npush > (unsigned)kMaxBands) { return fail(J2P_EINVAL, "link_bands: 1..%d bands to push to", kMaxBands); }
-        if(links->ncount > (unsigned)kMaxBands) { return fail(J2P_EINVAL, "link_bands: at most %d counters", kMaxBands); }
+        if(s->whole) { return j2p_fail(J2P_ESTATE, "link_bands: band solvers only"); }
+        if(!s->fold) { return j2p_fail(J2P_ESTATE, "link_bands needs the folded norm reduction (the row sums leave from inside k_gradient)"); }
+        if(s->rowsum_alternate) { return j2p_fail(J2P_ESTATE, "link_bands: this solver's row sums already alternate for norm_from_bands"); }
+        if(links->npush == 0 || links->npush > (unsigned)kMaxBands) { return j2p_fail(J2P_EINVAL, "link_bands: 1..%d bands to push to", kMaxBands); }
+        if(links->ncount > (unsigned)kMaxBands) { return j2p_fail(J2P_EINVAL, "link_bands: at most %d counters", kMaxBands); }
         for(unsigned b = 0; b < links->ncount; b++) {
-                if(!links->count[b]) { return fail(J2P_EINVAL, "link_bands: counter %u is NULL", b); }
+                if(!links->count[b]) { return j2p_fail(J2P_EINVAL, "link_bands: counter %u is NULL", b); }
         }
         bool own[2] = {false, false};
         for(int par = 0; par < 2; par++) {
                 for(unsigned b = 0; b < links->npush; b++) {
-                        if(!links->push[par][b]) { return fail(J2P_EINVAL, "link_bands: push target %u is NULL", b); }
+                        if(!links->push[par][b]) { return j2p_fail(J2P_EINVAL, "link_bands: push target %u is NULL", b); }
                         own[par] = own[par] || links->push[par][b] == (par ? s->rowsum_all_odd : s->rowsum_all);
                 }
         }
-        if(!own[0] || !own[1]) { return fail(J2P_EINVAL, "link_bands: the push lists must contain this solver's own arrays"); }
+        if(!own[0] || !own[1]) { return j2p_fail(J2P_EINVAL, "link_bands: the push lists must contain this solver's own arrays"); }
         for(unsigned c = 0; c < s->nch; c++) {
                 // a neighbour is given for both buffers or for neither; the band at the top / bottom of the canvas has none
                 const bool up = links->up_halo[0][c] != nullptr, down = links->down_halo[0][c] != nullptr;
                 if(up != (links->up_halo[1][c] != nullptr) || down != (links->down_halo[1][c] != nullptr)) {
-                        return fail(J2P_EINVAL, "link_bands: channel %u: a neighbour's rows are needed for both x buffers", c);
+                        return j2p_fail(J2P_EINVAL, "link_bands: channel %u: a neighbour's rows are needed for both x buffers", c);
                 }
                 if(up != (s->row0 > 0) || down != (s->row0 + s->rows < s->H)) {
-                        return fail(J2P_EINVAL, "link_bands: channel %u: neighbours do not match the band's place in the canvas", c);
+                        return j2p_fail(J2P_EINVAL, "link_bands: channel %u: neighbours do not match the band's place in the canvas", c);
                 }
         }
         // the push lists live in device memory (see GradArgs::push)
@@ -1790,24 +1764,24 @@ int j2p_solver_link_bands(j2p_solver *s, const j2p_band_links *links)
 int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *const rowsums[], const unsigned first_tile_row[],
                                const unsigned tile_rows[], unsigned nout, float *const norm_out[])
 {
-        if(!s || !rowsums || !first_tile_row || !tile_rows) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(nband == 0 || nband > (unsigned)kMaxBands) { return fail(J2P_EINVAL, "1..%d bands", kMaxBands); }
-        if(nout > (unsigned)kMaxBands || (nout && !norm_out)) { return fail(J2P_EINVAL, "norm_from_bands: bad output list"); }
-        if(!s->grad_done || rowsums_owed(s)) { return fail(J2P_ESTATE, "norm_from_bands needs a finished gradient phase"); }
+        if(!s || !rowsums || !first_tile_row || !tile_rows) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(nband == 0 || nband > (unsigned)kMaxBands) { return j2p_fail(J2P_EINVAL, "1..%d bands", kMaxBands); }
+        if(nout > (unsigned)kMaxBands || (nout && !norm_out)) { return j2p_fail(J2P_EINVAL, "norm_from_bands: bad output list"); }
+        if(!s->grad_done || rowsums_owed(s)) { return j2p_fail(J2P_ESTATE, "norm_from_bands needs a finished gradient phase"); }
         // a whole-canvas solver above kNormInProjectPixels reduces its partials in one kernel and never forms the
         // level-1 row sums this call reads
-        if(s->whole && !s->fold) { return fail(J2P_ESTATE, "norm_from_bands: this solver leaves no per-tile-row sums (whole canvas, norm folding off)"); }
+        if(s->whole && !s->fold) { return j2p_fail(J2P_ESTATE, "norm_from_bands: this solver leaves no per-tile-row sums (whole canvas, norm folding off)"); }
         DeviceGuard guard(s->device);
         BandRowsums t;
         unsigned covered = 0;
         for(unsigned b = 0; b < nband; b++) {
-                if(first_tile_row[b] + tile_rows[b] > s->ntr_global) { return fail(J2P_EINVAL, "band %u: tile rows out of range", b); }
+                if(first_tile_row[b] + tile_rows[b] > s->ntr_global) { return j2p_fail(J2P_EINVAL, "band %u: tile rows out of range", b); }
                 t.rowsum[b] = rowsums[b];
                 t.first[b] = first_tile_row[b];
                 t.count[b] = tile_rows[b];
                 covered += tile_rows[b];
         }
-        if(covered != s->ntr_global) { return fail(J2P_EINVAL, "the bands cover %u of %u tile rows", covered, s->ntr_global); }
+        if(covered != s->ntr_global) { return j2p_fail(J2P_EINVAL, "the bands cover %u of %u tile rows", covered, s->ntr_global); }
         t.nband = nband;
         // where the float norm goes: this solver's own word(s), or the list given (every band's, this one included)
         if(nout == 0) {
@@ -1816,11 +1790,11 @@ int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *cons
         } else {
                 bool own = false;
                 for(unsigned b = 0; b < nout; b++) {
-                        if(!norm_out[b]) { return fail(J2P_EINVAL, "norm_from_bands: output %u is NULL", b); }
+                        if(!norm_out[b]) { return j2p_fail(J2P_EINVAL, "norm_from_bands: output %u is NULL", b); }
                         t.out[b] = norm_out[b];
                         own = own || norm_out[b] == s->norm;
                 }
-                if(!own) { return fail(J2P_EINVAL, "norm_from_bands: the output list must contain the solver's own norm"); }
+                if(!own) { return j2p_fail(J2P_EINVAL, "norm_from_bands: the output list must contain the solver's own norm"); }
                 t.nout = nout;
         }
         unsigned P = 1;
@@ -1834,25 +1808,25 @@ int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *cons
 
 int j2p_solver_norm_ptr(j2p_solver *s, float **norm)
 {
-        if(!s || !norm) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !norm) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *norm = s->norm;
         return J2P_OK;
 }
 
 int j2p_solver_norm_external(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(!s->grad_done || rowsums_owed(s)) { return fail(J2P_ESTATE, "norm_external needs a finished gradient phase"); }
-        if(s->whole && s->plan.nip()) { return fail(J2P_ESTATE, "norm_external: this solver reduces the norm inside its projection kernel"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s->grad_done || rowsums_owed(s)) { return j2p_fail(J2P_ESTATE, "norm_external needs a finished gradient phase"); }
+        if(s->whole && s->plan.nip()) { return j2p_fail(J2P_ESTATE, "norm_external: this solver reduces the norm inside its projection kernel"); }
         s->plan.level2 = J2P_NORM_L2_EXTERNAL;
         return J2P_OK;
 }
 
 int j2p_solver_copy_rows(j2p_solver *s, unsigned n, float *const dst[], const float *const src[], size_t floats)
 {
-        if(!s || !dst || !src) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !dst || !src) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(n == 0) { return J2P_OK; }
-        if(n > 2u * kMaxCh || (floats & 1) || floats > 0xfffffffeu) { return fail(J2P_EINVAL, "copy_rows: bad count / size"); }
+        if(n > 2u * kMaxCh || (floats & 1) || floats > 0xfffffffeu) { return j2p_fail(J2P_EINVAL, "copy_rows: bad count / size"); }
         DeviceGuard guard(s->device);
         RowCopies t;
         for(unsigned k = 0; k < n; k++) { t.dst[k] = dst[k]; t.src[k] = src[k]; }
@@ -1867,8 +1841,8 @@ int j2p_solver_copy_rows(j2p_solver *s, unsigned n, float *const dst[], const fl
 
 int j2p_solver_commit_initial_halo(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
-        if(s->iter != 0 || s->grad_done) { return fail(J2P_ESTATE, "initial halo can only be committed at iteration 0"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(s->iter != 0 || s->grad_done) { return j2p_fail(J2P_ESTATE, "initial halo can only be committed at iteration 0"); }
         DeviceGuard guard(s->device);
         const size_t hb = (size_t)kHalo * s->W * sizeof(float);
         for(unsigned c = 0; c < s->nch; c++) {
@@ -1882,9 +1856,9 @@ int j2p_solver_commit_initial_halo(j2p_solver *s)
 
 int j2p_solver_download(j2p_solver *s, unsigned c, float *out)
 {
-        if(!s || !out) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(c >= s->nch) { return fail(J2P_EINVAL, "channel %u out of range", c); }
-        if(s->grad_done) { return fail(J2P_ESTATE, "download between the two phases of an iteration"); }
+        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(c >= s->nch) { return j2p_fail(J2P_EINVAL, "channel %u out of range", c); }
+        if(s->grad_done) { return j2p_fail(J2P_ESTATE, "download between the two phases of an iteration"); }
         DeviceGuard guard(s->device);
         const float *src = s->ch[c].xbuf[s->cur] + (size_t)kHalo * s->W;
         HIP_TRY(hipMemcpyAsync(out, src, (size_t)s->rows * s->W * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -1894,8 +1868,8 @@ int j2p_solver_download(j2p_solver *s, unsigned c, float *out)
 
 int j2p_solver_download_gradient(j2p_solver *s, unsigned c, float *out)
 {
-        if(!s || !out) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(c >= s->nch) { return fail(J2P_EINVAL, "channel %u out of range", c); }
+        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(c >= s->nch) { return j2p_fail(J2P_EINVAL, "channel %u out of range", c); }
         DeviceGuard guard(s->device);
         HIP_TRY(hipMemcpyAsync(out, s->ch[c].grad, (size_t)s->rows * s->W * sizeof(float), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1904,15 +1878,15 @@ int j2p_solver_download_gradient(j2p_solver *s, unsigned c, float *out)
 
 int j2p_solver_plane_ptr(j2p_solver *s, unsigned c, float **dev_ptr)
 {
-        if(!s || !dev_ptr) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(c >= s->nch) { return fail(J2P_EINVAL, "channel %u out of range", c); }
+        if(!s || !dev_ptr) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(c >= s->nch) { return j2p_fail(J2P_EINVAL, "channel %u out of range", c); }
         *dev_ptr = s->ch[c].xbuf[s->cur] + (size_t)kHalo * s->W;
         return J2P_OK;
 }
 
 int j2p_solver_sync(j2p_solver *s)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         HIP_TRY(hipStreamSynchronize(s->stream));
         return J2P_OK;
@@ -1920,7 +1894,7 @@ int j2p_solver_sync(j2p_solver *s)
 
 int j2p_solver_enable_timing(j2p_solver *s, int on)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         int rc = flush_timing(s);
         s->timing = on > 0 ? (unsigned)on : 0u;
@@ -1960,14 +1934,14 @@ int j2p_solver_enable_timing(j2p_solver *s, int on)
 
 int j2p_solver_timing_overhead(j2p_solver *s, double *event_pair_ms)
 {
-        if(!s || !event_pair_ms) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!s || !event_pair_ms) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *event_pair_ms = s->ev_pair_ms;
         return J2P_OK;
 }
 
 int j2p_solver_kernel_times(j2p_solver *s, double *gradient_ms, double *project_ms, unsigned *samples)
 {
-        if(!s) { return fail(J2P_EINVAL, "solver is NULL"); }
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
         DeviceGuard guard(s->device);
         int rc = flush_timing(s);
         if(rc != J2P_OK) { return rc; }
@@ -1980,12 +1954,12 @@ int j2p_solver_kernel_times(j2p_solver *s, double *gradient_ms, double *project_
 
 int j2p_decode_plane(int device, unsigned w, unsigned h, const int16_t *data, const uint16_t *quant_table, float *out)
 {
-        if(!data || !quant_table || !out) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(w == 0 || h == 0 || (w & 7) || (h & 7)) { return fail(J2P_EINVAL, "plane %ux%u is not a positive multiple of 8", w, h); }
+        if(!data || !quant_table || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(w == 0 || h == 0 || (w & 7) || (h & 7)) { return j2p_fail(J2P_EINVAL, "plane %ux%u is not a positive multiple of 8", w, h); }
         int ndev = 0;
-        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return fail(J2P_EDEVICE, "no HIP device available"); }
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         const size_t n = (size_t)w * h;
         int16_t *dd = nullptr;
         float *df = nullptr, *dq = nullptr;
@@ -2004,7 +1978,7 @@ int j2p_decode_plane(int device, unsigned w, unsigned h, const int16_t *data, co
                 e = hipGetLastError();
         }
         if(e == hipSuccess) { e = hipMemcpy(out, df, n * sizeof(float), hipMemcpyDeviceToHost); }
-        if(e != hipSuccess) { rc = fail(e == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE, "decode_plane: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { rc = j2p_fail(e == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE, "decode_plane: %s", hipGetErrorString(e)); }
         (void)hipFree(dd);
         (void)hipFree(df);
         (void)hipFree(dq);
@@ -2013,12 +1987,12 @@ int j2p_decode_plane(int device, unsigned w, unsigned h, const int16_t *data, co
 
 int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
 {
-        if(!blocks) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(!blocks) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(n == 0) { return J2P_OK; }
         int ndev = 0;
-        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return fail(J2P_EDEVICE, "no HIP device available"); }
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         float *db = nullptr;
         int rc = J2P_OK;
         hipError_t e = dev_malloc((void **)&db, n * 64 * sizeof(float));
@@ -2028,386 +2002,18 @@ int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
                 e = hipGetLastError();
         }
         if(e == hipSuccess) { e = hipMemcpy(blocks, db, n * 64 * sizeof(float), hipMemcpyDeviceToHost); }
-        if(e != hipSuccess) { rc = fail(e == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE, "dct8x8_blocks: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { rc = j2p_fail(e == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE, "dct8x8_blocks: %s", hipGetErrorString(e)); }
         (void)hipFree(db);
         return rc;
-}
-
-// What the conversions of solved planes start from: rows [y0, y1) x w columns of the image from nplane (3 or 1) (solver,
-// channel) pairs on one device that all hold those canvas rows.  Checks arguments and state, gives per plane the first of
-// those rows in xbuf[cur] and its stride in floats, and waits for the streams of the solvers other than planes[0].solver,
-// on whose stream the caller launches.  `whole`: called as a whole-canvas form, which band solvers refuse.  what: "to_rgb",
-// "to_grey" or "to_tensor", for the messages.
-static int resolve_rows(const char *what, const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1,
-                        const float *ptr[3], unsigned stride[3])
-{
-        if(w == 0 || y0 >= y1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
-        for(unsigned i = 0; whole && i < nplane; i++) {
-                if(planes[i].solver && !planes[i].solver->whole) {
-                        return fail(J2P_ESTATE, "%s needs whole-canvas solvers (bands: j2p_planes_rows_%s)", what, what);
-                }
-        }
-        for(unsigned i = 0; i < 3; i++) { ptr[i] = nullptr; stride[i] = 0; }
-        for(unsigned i = 0; i < nplane; i++) {
-                j2p_solver *s = planes[i].solver;
-                if(!s || planes[i].channel >= s->nch) { return fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
-                if(s->device != planes[0].solver->device) { return fail(J2P_EINVAL, "planes live on different devices"); }
-                if(s->W < w || y0 < s->row0 || y1 > s->row0 + s->rows) {
-                        return fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
-                                    s->row0, s->row0 + s->rows, s->W);
-                }
-                if(s->grad_done) { return fail(J2P_ESTATE, "%s between the two phases of an iteration", what); }
-                ptr[i] = s->ch[planes[i].channel].xbuf[s->cur] + (size_t)(kHalo + (y0 - s->row0)) * s->W;
-                stride[i] = s->W;
-        }
-        DeviceGuard guard(planes[0].solver->device);
-        for(unsigned i = 1; i < nplane; i++) {
-                if(planes[i].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(planes[i].solver->stream)); }
-        }
-        return J2P_OK;
-}
-
-// rows [y0, y1) of the image as samples on the host, through k_to_samples: three planes -> RGB, one -> greyscale
-static int convert_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, unsigned bits,
-                        uint8_t *out_host)
-{
-        const char *what = nplane == 3 ? "to_rgb" : "to_grey";
-        if(!planes || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(bits != 8 && bits != 16) { return fail(J2P_EINVAL, "bits must be 8 or 16 (png.c:22)"); }
-        const float *ptr[3];
-        unsigned stride[3];
-        if(const int rc = resolve_rows(what, planes, nplane, whole, w, y0, y1, ptr, stride); rc != J2P_OK) { return rc; }
-        const unsigned h = y1 - y0;
-        j2p_solver *s0 = planes[0].solver;
-        DeviceGuard guard(s0->device);
-        const size_t bytes = (size_t)w * h * (size_t)nplane * (bits / 8);
-        void *dout = nullptr;
-        size_t dout_bytes = 0;
-        HIP_TRY(pool_take(s0->device, bytes, &dout, &dout_bytes));       // pooled like the solvers' arenas: no hipFree per image
-        hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, s0->stream, ptr[0], stride[0],
-                           ptr[1], stride[1], ptr[2], stride[2], w, h, bits, static_cast<uint8_t *>(dout));
-        hipError_t e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s0->stream);
-        if(e == hipSuccess) { e = hipStreamSynchronize(s0->stream); }
-        pool_give(s0->device, dout, dout_bytes);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_%s: %s", what, hipGetErrorString(e)); }
-        return J2P_OK;
-}
-
-int j2p_planes_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
-{
-        return convert_rows(planes, 3, true, w, 0, h, bits, out_host);
-}
-
-int j2p_planes_rows_to_rgb(const j2p_plane_ref planes[3], unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
-                           uint8_t *out_host)
-{
-        return convert_rows(planes, 3, false, w, row_begin, row_end, bits, out_host);
-}
-
-int j2p_planes_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned h, unsigned bits, uint8_t *out_host)
-{
-        return convert_rows(plane, 1, true, w, 0, h, bits, out_host);
-}
-
-int j2p_planes_rows_to_grey(const j2p_plane_ref *plane, unsigned w, unsigned row_begin, unsigned row_end, unsigned bits,
-                            uint8_t *out_host)
-{
-        return convert_rows(plane, 1, false, w, row_begin, row_end, bits, out_host);
-}
-
-// ---- tensor output: k_to_tensor ----
-static_assert(J2P_DTYPE_U8 == kDtypeU8 && J2P_DTYPE_F16 == kDtypeF16 && J2P_DTYPE_BF16 == kDtypeBF16 && J2P_DTYPE_F32 == kDtypeF32,
-              "the kernels' dtype codes are the header's");
-
-// Which destination path the full groups of 4 pixels of a w-column image take — the only place that knows the rule.  A
-// vector path stores 4 elements at once, 16 / 8 / 4 bytes for f32 / 16-bit / u8, and needs every such store aligned to its
-// width: the first row's address, and (in elements) the row stride and — planar, three planes — the channel stride multiples
-// of 4; a lane's first column is a multiple of 4 already.  Everything else, and every image narrower than one group, is
-// generic: correct for any strides, one element per store.  Decided per image, not per row: rows [a, b) of an image start
-// at a multiple of stride_y from its first row, so the bands of one image agree.
-static int tensor_path(unsigned w, unsigned nplane, int dtype, long long stride_c, long long stride_y, long long stride_x, uintptr_t address)
-{
-        const unsigned store_bytes = 4 * j2p_tensor_element_bytes(dtype);
-        if(w < 4 || address % store_bytes != 0 || stride_y % 4 != 0) { return kTensorGeneric; }
-        if(stride_x == 1 && (nplane == 1 || stride_c % 4 == 0)) { return kTensorPlanar; }
-        if(nplane == 3 && stride_c == 1 && stride_x == 3) { return kTensorInterleaved; }
-        return kTensorGeneric;
-}
-
-int j2p_debug_tensor_path(unsigned w, unsigned nplane, int dtype, ptrdiff_t stride_c, ptrdiff_t stride_y, ptrdiff_t stride_x,
-                          uintptr_t data_address, int *path)
-{
-        if(!path || (nplane != 1 && nplane != 3) || dtype < J2P_DTYPE_U8 || dtype > J2P_DTYPE_F32 || w == 0 || stride_c < 1 || stride_y < 1 ||
-           stride_x < 1) {
-                return fail(J2P_EINVAL, "bad argument");
-        }
-        *path = tensor_path(w, nplane, dtype, stride_c, stride_y, stride_x, data_address);
-        return J2P_OK;
-}
-
-using TensorKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, unsigned, unsigned, TensorOut);
-
-// [three planes / one][dtype][path]; one plane has no interleaved layout (tensor_path never chooses it there)
-#define J2P_TENSOR_ROW(NPLANE, DTYPE, THIRD) {k_to_tensor<NPLANE, DTYPE, kTensorGeneric>, k_to_tensor<NPLANE, DTYPE, kTensorPlanar>, THIRD}
-#define J2P_TENSOR_ROWS(NPLANE, THIRD)                                                                                                     \
-        {J2P_TENSOR_ROW(NPLANE, kDtypeU8, THIRD(kDtypeU8)), J2P_TENSOR_ROW(NPLANE, kDtypeF16, THIRD(kDtypeF16)),                               \
-         J2P_TENSOR_ROW(NPLANE, kDtypeBF16, THIRD(kDtypeBF16)), J2P_TENSOR_ROW(NPLANE, kDtypeF32, THIRD(kDtypeF32))}
-#define J2P_TENSOR_INTERLEAVED(DTYPE) k_to_tensor<3, DTYPE, kTensorInterleaved>
-#define J2P_TENSOR_NONE(DTYPE) nullptr
-static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENSOR_INTERLEAVED), J2P_TENSOR_ROWS(1, J2P_TENSOR_NONE)};
-#undef J2P_TENSOR_NONE
-#undef J2P_TENSOR_INTERLEAVED
-#undef J2P_TENSOR_ROWS
-#undef J2P_TENSOR_ROW
-
-// What both tensor outputs check before they launch, in this order: the arguments, the solvers' state and rows (resolve_rows),
-// the 16-byte alignment of the canvas rows, and the destination's dtype, strides, address, scale / bias and device.  Gives the
-// planes' first rows and strides and the kernels' view of the destination.
-static int tensor_resolve(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out,
-                          const float *ptr[3], unsigned stride[3], TensorOut &o)
-{
-        if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(nplane != 1 && nplane != 3) { return fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
-        if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride); rc != J2P_OK) { return rc; }
-        for(unsigned i = 0; i < nplane; i++) {
-                // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
-                if(stride[i] % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
-        }
-        if(out->dtype != J2P_DTYPE_U8 && out->dtype != J2P_DTYPE_F16 && out->dtype != J2P_DTYPE_BF16 && out->dtype != J2P_DTYPE_F32) {
-                return fail(J2P_EINVAL, "to_tensor: unknown dtype %d", out->dtype);
-        }
-        if(out->stride_c < 1 || out->stride_y < 1 || out->stride_x < 1) {
-                return fail(J2P_EINVAL, "to_tensor: strides (%td, %td, %td) must all be at least 1 element", out->stride_c, out->stride_y, out->stride_x);
-        }
-        if(!out->data) { return fail(J2P_EINVAL, "to_tensor: data is NULL"); }
-        if(reinterpret_cast<uintptr_t>(out->data) % j2p_tensor_element_bytes(out->dtype) != 0) {
-                return fail(J2P_EINVAL, "to_tensor: data is not aligned to the %u-byte element", j2p_tensor_element_bytes(out->dtype));
-        }
-        o.data = out->data;
-        o.stride_c = out->stride_c;
-        o.stride_y = out->stride_y;
-        o.stride_x = out->stride_x;
-        for(unsigned k = 0; k < 3; k++) {
-                // (one plane: only entry 0 is used, the others are not looked at)
-                const float sc = k < nplane ? out->scale[k] : 1.f, bi = k < nplane ? out->bias[k] : 0.f;
-                if(!__builtin_isfinite(sc) || !__builtin_isfinite(bi)) { return fail(J2P_EINVAL, "to_tensor: scale / bias of channel %u is not finite", k); }
-                if(out->dtype == J2P_DTYPE_U8 && (sc != 1.f || bi != 0.f)) {
-                        return fail(J2P_EINVAL, "to_tensor: u8 elements are the 8-bit samples: scale must be 1 and bias 0 (channel %u)", k);
-                }
-                o.scale[k] = sc;
-                o.bias[k] = bi;
-        }
-        j2p_solver *s0 = planes[0].solver;
-        DeviceGuard guard(s0->device);
-        {
-                int device = -1;
-                if(j2p_device_of_pointer(out->data, &device) != J2P_OK || device != s0->device) {
-                        return fail(J2P_EINVAL, "to_tensor: data is not device memory of the solvers' device %d (managed and host memory are refused)", s0->device);
-                }
-        }
-        return J2P_OK;
-}
-
-// rows [y0, y1) of the image from nplane (3 or 1) (solver, channel) pairs on one device into a strided tensor in that device's
-// memory, through k_to_tensor; out->data is the element of row y0.  Asynchronous: the kernel is queued on planes[0].solver's
-// stream and nothing waits for it.
-static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out)
-{
-        const float *ptr[3];
-        unsigned stride[3];
-        TensorOut o;
-        if(const int rc = tensor_resolve(planes, nplane, whole, w, y0, y1, out, ptr, stride, o); rc != J2P_OK) { return rc; }
-        j2p_solver *s0 = planes[0].solver;
-        DeviceGuard guard(s0->device);
-        const unsigned h = y1 - y0;
-        const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));
-        const TensorKernel kernel = kTensorKernels[nplane == 3 ? 0 : 1][out->dtype][path];
-        // a workgroup: 4 rows of 256 columns; grid-stride over rows from a grid of about 2048 workgroups, as k_to_samples'
-        const unsigned gx = (w + 255) / 256, row_groups = (h + 3) / 4;
-        const unsigned gy_cap = gx >= 2048 ? 1 : 2048 / gx;
-        const unsigned gy = row_groups < gy_cap ? row_groups : gy_cap;
-        hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1], stride[1], ptr[2], stride[2], w, h, o);
-        const hipError_t e = hipGetLastError();
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_tensor: %s", hipGetErrorString(e)); }
-        return J2P_OK;
-}
-
-int j2p_device_of_pointer(const void *p, int *device)
-{
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof(attr));
-        if(hipPointerGetAttributes(&attr, p) != hipSuccess) {
-                (void)hipGetLastError();                 // (plain host memory is an error to some runtimes, "unregistered" to others)
-                return J2P_EINVAL;
-        }
-        if(attr.type != hipMemoryTypeDevice || attr.isManaged) { return J2P_EINVAL; }
-        *device = attr.device;
-        return J2P_OK;
-}
-
-int j2p_planes_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_tensor *out)
-{
-        return tensor_rows(planes, nplane, true, w, 0, h, out);
-}
-
-int j2p_planes_rows_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned row_begin, unsigned row_end,
-                              const j2p_tensor *out)
-{
-        return tensor_rows(planes, nplane, false, w, row_begin, row_end, out);
-}
-
-// ---- resized tensor output: k_to_tensor_resized ----
-using ResizedKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, ResizeGeom, TensorOut);
-#define J2P_RESIZED_ROW(NPLANE) \
-        {k_to_tensor_resized<NPLANE, kDtypeU8>, k_to_tensor_resized<NPLANE, kDtypeF16>, k_to_tensor_resized<NPLANE, kDtypeBF16>, k_to_tensor_resized<NPLANE, kDtypeF32>}
-static const ResizedKernel kResizedKernels[2][4] = {J2P_RESIZED_ROW(3), J2P_RESIZED_ROW(1)};            // [three planes / one][dtype]
-#undef J2P_RESIZED_ROW
-
-// The tile of k_to_tensor_resized — output columns and consecutive output rows per wavefront — the only place that knows the
-// rule.  256 columns (64 lanes x 4) make a wavefront's source segment at least as long as k_to_tensor's 256 pixels at any
-// ratio; but a small output of a large image has few such tiles and every one of them a long footprint, so the tile is
-// halved while the chip (256 CUs x 4 SIMDs) would get fewer than two wavefronts per SIMD — not below 32 columns: the lanes
-// beyond the tile's columns only load and convert, they walk no taps.  Rows: a wavefront that owns several consecutive
-// output rows reads and converts the source row that two of them share once instead of twice (at ratios just above 1
-// that is every row) and spreads its set-up over them; up to 8, as long as about four wavefronts per SIMD remain.
-// Same bits for every tile: a column's sums do not depend on which lane or wavefront forms them.
-static void resize_tile(unsigned out_w, unsigned out_h, unsigned *lanes, unsigned *slots, unsigned *rows)
-{
-        unsigned tile = 64 * kResizeSlots;
-        while(tile > 32 && (unsigned long long)((out_w + tile - 1) / tile) * out_h < 2048) { tile /= 2; }
-        *lanes = tile < 64 ? tile : 64;
-        *slots = tile / *lanes;
-        const unsigned long long tiles = (out_w + tile - 1) / tile;
-        unsigned r = 8;
-        while(r > 1 && tiles * ((out_h + r - 1) / r) < 4096) { r /= 2; }
-        while(((out_h + r - 1) / r + 3) / 4 > 65535) { r *= 2; }                // (what a grid's y dimension may be)
-        *rows = r;
-}
-
-int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_resize *r,
-                                 const j2p_tensor *out)
-{
-        if(!planes || !out) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(const char *why = j2p_resize_error(r, w, h)) { return fail(J2P_EINVAL, "to_tensor: %s", why); }
-        const float *ptr[3];
-        unsigned stride[3];
-        TensorOut o;
-        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o); rc != J2P_OK) { return rc; }
-        j2p_solver *s0 = planes[0].solver;
-        DeviceGuard guard(s0->device);
-        ResizeGeom g;
-        g.box_x = r->box_x;
-        g.box_y = r->box_y;
-        const bool rx = r->out_w != r->box_w, ry = r->out_h != r->box_h;        // an axis that is not resized: one tap of weight 1
-        g.tap_bw = rx ? r->box_w : 1;
-        g.tap_ow = rx ? r->out_w : 1;
-        g.tap_bh = ry ? r->box_h : 1;
-        g.tap_oh = ry ? r->out_h : 1;
-        g.out_w = r->out_w;
-        g.out_h = r->out_h;
-        g.div_x = rx ? (float)r->box_w : 0.f;
-        g.div_y = ry ? (float)r->box_h : 0.f;
-        resize_tile(r->out_w, r->out_h, &g.lanes, &g.slots, &g.rows);
-        // what lets the kernel step from one column's taps to the next without dividing
-        g.qx = g.tap_bw / g.tap_ow;
-        g.rx = g.tap_bw % g.tap_ow;
-        g.qy = g.tap_bh / g.tap_oh;
-        g.ry = g.tap_bh % g.tap_oh;
-        g.qlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw / g.tap_ow);
-        g.rlanes = (unsigned)((unsigned long long)g.lanes * g.tap_bw % g.tap_ow);
-        // a workgroup: 4 wavefronts, one above the other, of one tile
-        const unsigned tile = g.lanes * g.slots, gx = (r->out_w + tile - 1) / tile, gy = ((r->out_h + g.rows - 1) / g.rows + 3) / 4;
-        hipLaunchKernelGGL(kResizedKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(gx, gy), dim3(256), 0, s0->stream, ptr[0], stride[0], ptr[1],
-                           stride[1], ptr[2], stride[2], g, o);
-        const hipError_t e = hipGetLastError();
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_tensor_resized: %s", hipGetErrorString(e)); }
-        return J2P_OK;
-}
-
-// block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
-// 1/sub_w x 1/sub_h of its resolution (k_quantise_blocks<sub_w, sub_h>): output block row r covers canvas rows
-// [8 * sub_h * r, 8 * sub_h * (r + 1)).  `whole`: called as a whole-canvas form, which band solvers refuse.
-static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
-                         unsigned r1, const uint16_t quant_table[64], int16_t *out_host)
-{
-        if(!plane || !quant_table || !out_host) { return fail(J2P_EINVAL, "NULL argument"); }
-        if(blocks_w == 0 || r0 >= r1) { return fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
-        j2p_solver *s = plane->solver;
-        if(whole && s && !s->whole) {
-                return fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: the j2p_planes_rows_to_coefficients forms)");
-        }
-        if(sub_w < 1 || sub_w > 2 || sub_h < 1 || sub_h > 2) {
-                return fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
-        }
-        if(!s || plane->channel >= s->nch) { return fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
-        QuantSteps steps;
-        for(int j = 0; j < 64; j++) {
-                if(quant_table[j] == 0) { return fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
-                steps.q[j] = (float)quant_table[j];
-        }
-        // One rule for every sampling: every block starts inside the solver's rows and columns, and rows beyond the band are
-        // replicated only where the band ends with the canvas (a band that is not the last ends on a multiple of 16).  For 1x1
-        // that is "the whole grid inside": W, the band's rows and every block's start are multiples of 8, so a block that starts
-        // inside ends inside.
-        const unsigned long long row_end = (unsigned long long)s->row0 + s->rows, step_y = 8ull * sub_h;
-        if(8ull * sub_w * (blocks_w - 1) >= s->W || step_y * r0 < s->row0 || step_y * (r1 - 1) >= row_end ||
-           (step_y * r1 > row_end && row_end != s->H)) {
-                return fail(J2P_EINVAL, "to_coefficients: block rows [%u,%u) x %u blocks of %ux%u-pixel samples are not inside the solver's rows "
-                            "[%u,%u) x %u columns (every block must start there; only the canvas's last rows and columns are replicated)",
-                            r0, r1, blocks_w, sub_w, sub_h, s->row0, s->row0 + s->rows, s->W);
-        }
-        if(s->grad_done) { return fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
-        const unsigned first = (unsigned)(step_y * r0);
-        const float *src = s->ch[plane->channel].xbuf[s->cur] + (size_t)(kHalo + (first - s->row0)) * s->W;
-        DeviceGuard guard(s->device);
-        const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
-        void *dout = nullptr;
-        size_t dout_bytes = 0;
-        HIP_TRY(pool_take(s->device, bytes, &dout, &dout_bytes));
-        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
-        const auto kernel = sub_w == 2 ? (sub_h == 2 ? k_quantise_blocks<2, 2> : k_quantise_blocks<2, 1>)
-                                       : (sub_h == 2 ? k_quantise_blocks<1, 2> : k_quantise_blocks<1, 1>);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s->stream, src, s->W, (unsigned)(row_end - first),
-                           blocks_w, r1 - r0, steps, static_cast<int16_t *>(dout));
-        hipError_t e = hipGetLastError();
-        if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s->stream); }
-        if(e == hipSuccess) { e = hipStreamSynchronize(s->stream); }
-        pool_give(s->device, dout, dout_bytes);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "planes_to_coefficients: %s", hipGetErrorString(e)); }
-        return J2P_OK;
-}
-
-int j2p_planes_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned blocks_h, const uint16_t quant_table[64],
-                               int16_t *out_host)
-{
-        return quantise_rows(plane, true, 1, 1, blocks_w, 0, blocks_h, quant_table, out_host);
-}
-
-int j2p_planes_rows_to_coefficients(const j2p_plane_ref *plane, unsigned blocks_w, unsigned block_row_begin, unsigned block_row_end,
-                                    const uint16_t quant_table[64], int16_t *out_host)
-{
-        return quantise_rows(plane, false, 1, 1, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
-}
-
-int j2p_planes_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned blocks_h,
-                                   const uint16_t quant_table[64], int16_t *out_host)
-{
-        return quantise_rows(plane, true, sub_w, sub_h, blocks_w, 0, blocks_h, quant_table, out_host);
-}
-
-int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub_w, unsigned sub_h, unsigned blocks_w,
-                                        unsigned block_row_begin, unsigned block_row_end, const uint16_t quant_table[64], int16_t *out_host)
-{
-        return quantise_rows(plane, false, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
 }
 
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,
                       unsigned long long *sqrt_mismatches)
 {
         int ndev = 0;
-        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return fail(J2P_EDEVICE, "no HIP device available"); }
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         unsigned long long *dm = nullptr, hm[2] = {0, 0};
         HIP_TRY(hipMalloc(&dm, sizeof(hm)));
         hipError_t e = hipMemset(dm, 0, sizeof(hm));
@@ -2416,7 +2022,7 @@ int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *d
                 e = hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost);
         }
         (void)hipFree(dm);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "math_selftest: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "math_selftest: %s", hipGetErrorString(e)); }
         if(div_mismatches) { *div_mismatches = hm[0]; }
         if(sqrt_mismatches) { *sqrt_mismatches = hm[1]; }
         return J2P_OK;
@@ -2425,9 +2031,9 @@ int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *d
 int j2p_sqrt_exhaustive(int device, unsigned long long *rsq_mismatches, unsigned long long *fast_mismatches)
 {
         int ndev = 0;
-        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return fail(J2P_EDEVICE, "no HIP device available"); }
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         unsigned long long *dm = nullptr, hm[2] = {0, 0};
         HIP_TRY(hipMalloc(&dm, sizeof(hm)));
         hipError_t e = hipMemset(dm, 0, sizeof(hm));
@@ -2436,7 +2042,7 @@ int j2p_sqrt_exhaustive(int device, unsigned long long *rsq_mismatches, unsigned
                 e = hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost);
         }
         (void)hipFree(dm);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "sqrt_exhaustive: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "sqrt_exhaustive: %s", hipGetErrorString(e)); }
         if(rsq_mismatches) { *rsq_mismatches = hm[0]; }
         if(fast_mismatches) { *fast_mismatches = hm[1]; }
         return J2P_OK;
@@ -2446,12 +2052,12 @@ int j2p_sqrt_exhaustive(int device, unsigned long long *rsq_mismatches, unsigned
 // report[0] = mismatches, report[1..8] = the first offenders
 int j2p_division_exhaustive(int device, int pass, unsigned first, unsigned count, unsigned long long report[9])
 {
-        if(pass < 1 || pass > 3) { return fail(J2P_EINVAL, "pass must be 1, 2 or 3"); }
-        if(!report) { return fail(J2P_EINVAL, "NULL argument"); }
+        if(pass < 1 || pass > 3) { return j2p_fail(J2P_EINVAL, "pass must be 1, 2 or 3"); }
+        if(!report) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         int ndev = 0;
-        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return fail(J2P_EDEVICE, "no HIP device available"); }
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
         DeviceGuard guard(device);
-        if(!guard.ok) { return fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         unsigned long long *dm = nullptr, hm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         HIP_TRY(dev_malloc((void **)&dm, sizeof(hm)));
         hipError_t e = hipMemset(dm, 0, sizeof(hm));
@@ -2462,9 +2068,34 @@ int j2p_division_exhaustive(int device, int pass, unsigned first, unsigned count
                 e = hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost);
         }
         (void)hipFree(dm);
-        if(e != hipSuccess) { return fail(J2P_EDEVICE, "division_exhaustive: %s", hipGetErrorString(e)); }
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "division_exhaustive: %s", hipGetErrorString(e)); }
         for(int i = 0; i < 9; i++) { report[i] = hm[i]; }
         return J2P_OK;
 }
 
 }  // extern "C"
+
+// ---- what the output stage sees of a solver (j2p_internal.h) ----
+j2p_solver_view j2p_solver_view_of(const j2p_solver *s)
+{
+        j2p_solver_view v;
+        v.device = s->device;
+        v.stream = s->stream;
+        v.nch = s->nch;
+        v.W = s->W;
+        v.H = s->H;
+        v.row0 = s->row0;
+        v.rows = s->rows;
+        v.whole = s->whole;
+        v.mid_iteration = s->grad_done;
+        return v;
+}
+
+int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **row)
+{
+        if(!s || !row) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(c >= s->nch) { return j2p_fail(J2P_EINVAL, "channel %u out of range", c); }
+        if(y < s->row0 || y >= s->row0 + s->rows) { return j2p_fail(J2P_EINVAL, "row %u is not one of the solver's [%u,%u)", y, s->row0, s->row0 + s->rows); }
+        *row = s->ch[c].xbuf[s->cur] + (size_t)(kHalo + (y - s->row0)) * s->W;
+        return J2P_OK;
+}

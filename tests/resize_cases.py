@@ -8,8 +8,8 @@ and never negative) and whose addition changes no bit, since a sum that starts a
 same area integral in float64, for the error bound of the CPU tests."""
 import numpy as np
 
-# source columns a wavefront of k_to_tensor_resized stages at a time (kResizeChunk in j2p_kernels.hip.h): the wide case below
-# is 1040 columns so that its rows span three chunks.  The tile rule (resize_tile in j2p_solver.hip): 256 output columns per
+# source columns a wavefront of k_to_tensor_resized stages at a time (kResizeChunk in j2p_output_kernels.hip.h): the wide case below
+# is 1040 columns so that its rows span three chunks.  The tile rule (resize_tile in j2p_output.hip): 256 output columns per
 # wavefront, halved down to 32 while there are fewer than 2048 wavefronts — the small cases run with tiles of 32, the wide ones
 # at widths 64, 65 and 1039 with tails of one column — and 2, 4 or 8 output rows per wavefront while 4096 wavefronts remain
 KERNEL_CHUNK = 512

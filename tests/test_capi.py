@@ -197,5 +197,8 @@ def test_no_kernel_spills_to_scratch(flags):
     assert r.returncode == 0, r.stderr[-500:]
     rows = [ln for ln in r.stdout.splitlines() if " scratch " in ln]
     assert len(rows) > 40, "kernel_resources.py found too few kernels"
+    # ... and of every device unit: the solver's kernels and the output stage's
+    for kernel in ("k_to_samples", "k_to_tensor<", "k_to_tensor_resized", "k_quantise_blocks", "k_gradient", "k_project"):
+        assert any(kernel in ln for ln in rows), f"kernel_resources.py lists no {kernel}"
     bad = [ln for ln in rows if not re.search(r"scratch 0$", ln)]
     assert not bad, "kernels with scratch:\n" + "\n".join(bad)

@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 from jpeg2png_amd.buildlib import CSRC, HIP_FLAGS, HIP_UNITS, INCLUDE, build  # noqa: E402
 
 name, flags = sys.argv[1], sys.argv[2:]
-build()                                     # the host-only objects are shared with the normal build
+build()                                     # every object but the solver unit's is shared with the normal build
 out_dir = os.path.join(ROOT, "ab")
 os.makedirs(out_dir, exist_ok=True)
 obj = os.path.join(out_dir, f"j2p_solver_{name}.o")

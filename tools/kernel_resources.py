@@ -9,16 +9,18 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from jpeg2png_amd.buildlib import HIP_FLAGS, INCLUDE, CSRC  # noqa: E402
+from jpeg2png_amd.buildlib import HIP_FLAGS, INCLUDE, CSRC, DEVICE_UNITS  # noqa: E402
 
 tmp = tempfile.TemporaryDirectory()                 # (a private directory: runs side by side, or by other users, do not collide)
-out = os.path.join(tmp.name, "j2p_res.s")
-cmd = ["/opt/rocm/bin/hipcc", *[f for f in HIP_FLAGS if f != "-Wall"], *sys.argv[1:], "-I", INCLUDE, "-I", CSRC,
-       "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, "j2p_solver.hip")]
-subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-md = open(out).read()
+md = ""
+for unit in DEVICE_UNITS:                           # every unit that holds device code
+    out = os.path.join(tmp.name, unit + ".s")
+    cmd = ["/opt/rocm/bin/hipcc", *[f for f in HIP_FLAGS if f != "-Wall"], *sys.argv[1:], "-I", INCLUDE, "-I", CSRC,
+           "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, unit)]
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    md += text[text.index("amdhsa.kernels"):]
 tmp.cleanup()
-md = md[md.index("amdhsa.kernels"):]
 for b in md.split("  - .agpr_count")[1:]:
     f = {k: re.search(r"\.%s:\s+(\S+)" % k, b).group(1) for k in
          ("name", "vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")}
