@@ -251,6 +251,13 @@ typedef struct j2p_exchange {
 } j2p_exchange;
 int j2p_solver_exchange_info(j2p_solver *s, j2p_exchange *info);
 
+/* Test hook, read-only: where the gradient phase leaves the STRIP partials partials_local is summed from — part_g2,
+ * doubles [channel][local tile row][strip] in device memory, one per wavefront item of k_gradient (sum of g^2 over
+ * rows_per_tile rows x 124 columns) — and their geometry.  After a gradient phase that folds level 1 into the launch
+ * (J2P_NORM_L1_TICKETS) every partial carries the iteration's parity in its sign bit; the magnitude is the sum.
+ * Any of the output pointers may be NULL.  (tests/test_norm_gpu.py compares the doubles with tests/norm_cases.py) */
+int j2p_solver_debug_partials(j2p_solver *s, double **part_g2, unsigned *ntx, unsigned *tile_rows_local, unsigned *rows_per_tile);
+
 /* Pieces of a row-tiled run inside ONE process (what j2p_tiled below is made of; peers' device pointers must be
  * accessible from the solver's device: same GPU, or peer access enabled).
  *   stream            : the hipStream_t the solver launches on
@@ -603,6 +610,33 @@ void j2p_debug_fail_run_after(int n);
  * inside the range the kernels screen for; both counters must come back 0 */
 int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *div_mismatches,
                       unsigned long long *sqrt_mismatches);
+
+/* test hook: ONE form of the ||g|| reduction on the caller's arrays (host memory), launched with the grid, LDS size and
+ * staging a solve uses for that geometry (the solver and this hook call the same launch functions).
+ *   J2P_NORM_FORM_ROWSUMS       k_rowsums: in = partials [channel][tile row][strip], nch * tile_rows * ntx doubles;
+ *                               rowsums_out = [tile row][channel] level-1 sums
+ *   J2P_NORM_FORM_NORM_WHOLE    k_norm_whole, both levels: in = partials as above; direct form for ntx <= 48, staged
+ *                               above, in as many rounds as 156 KiB of LDS make necessary; norm_out = [channel] floats
+ *   J2P_NORM_FORM_NORM_FINISH   k_norm_finish: in = row sums [tile row][channel]; norm_out (ntx is ignored from here on)
+ *   J2P_NORM_FORM_NORM_BANDS    k_norm_bands: in = the same global array, read as the bands [first_tile_row[b],
+ *                               + band_tile_rows[b]) in the order given (any order; they must tile the rows exactly,
+ *                               at most 32) — j2p_norm_selftest: as ONE band
+ *   J2P_NORM_FORM_FOLD_TREE     fold_tree, the tree k_gradient's last wavefront runs   } one launch of
+ *   J2P_NORM_FORM_PROJECT_TREE  norm_tree_load + norm_tree_reduce, k_project's (NIP)   } k_norm_trees_selftest
+ * tile_rows <= 4096, the two in-kernel trees <= 1024 (J2P_EINVAL beyond); nch 1..3; ntx 1..529.  The output a form does
+ * not write may be NULL.  fold_tile_row has no stand-alone form: it waits for partials stamped with the running
+ * iteration's parity, which only k_gradient stamps — it is tested through a solver (j2p_solver_debug_partials). */
+#define J2P_NORM_FORM_ROWSUMS 0
+#define J2P_NORM_FORM_NORM_WHOLE 1
+#define J2P_NORM_FORM_NORM_FINISH 2
+#define J2P_NORM_FORM_NORM_BANDS 3
+#define J2P_NORM_FORM_FOLD_TREE 4
+#define J2P_NORM_FORM_PROJECT_TREE 5
+int j2p_norm_selftest(int device, int form, unsigned nch, unsigned tile_rows, unsigned ntx, const double *in_host,
+                      double *rowsums_out_host, float *norm_out_host);
+int j2p_norm_selftest_bands(int device, int form, unsigned nch, unsigned tile_rows, unsigned ntx, const double *in_host,
+                            unsigned nband, const unsigned first_tile_row[], const unsigned band_tile_rows[],
+                            double *rowsums_out_host, float *norm_out_host);
 
 /* test hook: the two packed square-root sequences of the gradient kernel against sqrtf() on EVERY
  * float in [2^-100, 2^127) (about 1.9e9 values); both counters must come back 0 */

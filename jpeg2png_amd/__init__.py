@@ -110,7 +110,10 @@ C_ABI_SYMBOLS = [
     "compute", "j2p_compute", "j2p_compute_tiled", "j2p_compute_timing", "j2p_debug_fail_run_after", "j2p_solver_launches_per_iteration", "j2p_solver_timing_overhead",
     "j2p_debug_build", "j2p_debug_grad_items", "j2p_debug_norm_plan", "j2p_experiments_build", "j2p_solver_debug_violations", "j2p_solver_trace", "j2p_division_exhaustive",
     "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint",
+    "j2p_solver_debug_partials", "j2p_norm_selftest", "j2p_norm_selftest_bands",
 ]
+# the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
+NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
 J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 4, 5, 6
 J2P_OPT_NARROW_COEFFICIENTS = 7
 J2P_OPT_WIDE_FOOTPRINT = 8
@@ -232,6 +235,13 @@ def _bind(path):
     lib.j2p_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
     lib.j2p_math_selftest.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint,
                                       ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+    lib.j2p_solver_debug_partials.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint),
+                                              ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
+    lib.j2p_norm_selftest_bands.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p,
+                                            ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                            ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_norm_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_solver_debug_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     lib.j2p_solver_debug_violations.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_uint),
                                                 ctypes.POINTER(ctypes.c_ulonglong)]
@@ -323,6 +333,29 @@ def math_selftest(n, seed=1, device=0):
     d, q = ctypes.c_ulonglong(), ctypes.c_ulonglong()
     _check(load_library().j2p_math_selftest(device, n, seed, ctypes.byref(d), ctypes.byref(q)))
     return d.value, q.value
+
+
+def norm_selftest(form, data, bands=None, device=0):
+    """One form of the ||g|| reduction (a key of NORM_FORMS) on the caller's float64 array, launched as a solve launches
+    it (j2p_norm_selftest).  "rowsums", "norm_whole": data = partials [channel, tile row, strip]; every other form: row
+    sums [tile row, channel].  Returns the float32 norms [channel] — "rowsums": the float64 level-1 sums [tile row, channel].
+    bands ("norm_bands" only): [(first tile row, tile rows), ...] in the order the kernel is to take them; default: one."""
+    lib = load_library()
+    a = np.ascontiguousarray(data, dtype=np.float64)
+    from_partials = form in ("rowsums", "norm_whole")
+    if a.ndim != (3 if from_partials else 2):
+        raise J2PError(f"norm_selftest: '{form}' takes a {3 if from_partials else 2}-dimensional array")
+    nch, rows, ntx = a.shape if from_partials else (a.shape[1], a.shape[0], 0)
+    rowsums = np.full((rows, nch), np.nan, dtype=np.float64)
+    norms = np.full(nch, np.nan, dtype=np.float32)
+    if bands is None:
+        _check(lib.j2p_norm_selftest(device, NORM_FORMS[form], nch, rows, ntx, a.ctypes.data, rowsums.ctypes.data, norms.ctypes.data))
+    else:
+        first = (ctypes.c_uint * len(bands))(*[int(b[0]) for b in bands])
+        count = (ctypes.c_uint * len(bands))(*[int(b[1]) for b in bands])
+        _check(lib.j2p_norm_selftest_bands(device, NORM_FORMS[form], nch, rows, ntx, a.ctypes.data, len(bands), first, count,
+                                           rowsums.ctypes.data, norms.ctypes.data))
+    return rowsums if form == "rowsums" else norms
 
 
 def sqrt_exhaustive(device=0):
@@ -534,6 +567,31 @@ class Solver:
         e = _CExchange()
         _check(self._lib.j2p_solver_exchange_info(self._h, ctypes.byref(e)))
         return e
+
+    def norm_ptr(self):
+        """device address of the solver's [channel] float norms (j2p_solver_norm_ptr)"""
+        p = ctypes.c_void_p()
+        self._lib.j2p_solver_norm_ptr.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+        _check(self._lib.j2p_solver_norm_ptr(self._h, ctypes.byref(p)))
+        return p.value
+
+    def norm_from_bands(self, bands):
+        """between the two phases: ||g|| from the level-1 sums of the bands [(device address, first tile row, tile rows), ...],
+        in the order given, into this solver's norm (j2p_solver_norm_from_bands with nout = 0)"""
+        n = len(bands)
+        rs = (ctypes.c_void_p * n)(*[int(b[0]) for b in bands])
+        first = (ctypes.c_uint * n)(*[int(b[1]) for b in bands])
+        count = (ctypes.c_uint * n)(*[int(b[2]) for b in bands])
+        self._lib.j2p_solver_norm_from_bands.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
+        _check(self._lib.j2p_solver_norm_from_bands(self._h, n, rs, first, count, 0, None))
+
+    def debug_partials(self):
+        """diagnostics: (device address of the strip partials, float64 [channel][local tile row][strip]; strips per tile
+        row; local tile rows; rows per tile row) — j2p_solver_debug_partials"""
+        p, ntx, ntr, rpw = ctypes.c_void_p(), ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+        _check(self._lib.j2p_solver_debug_partials(self._h, ctypes.byref(p), ctypes.byref(ntx), ctypes.byref(ntr), ctypes.byref(rpw)))
+        return p.value, ntx.value, ntr.value, rpw.value
 
     def sync(self):
         _check(self._lib.j2p_solver_sync(self._h))

@@ -1633,6 +1633,24 @@ __device__ __forceinline__ float norm_tree_wave(const double *rowsum, unsigned n
         return norm_tree_reduce(t);
 }
 
+// test hook (j2p_norm_selftest): the two in-kernel forms of level 2 on a caller's row sums, one wavefront per channel.
+// form 0: fold_tree as k_gradient's last wavefront calls it — ONE wavefront takes every channel in turn, so the first
+// workgroup does and the others have nothing to do; `a` carries rowsum, ntr_global, nch_total and norm_out, nothing else.
+// form 1: norm_tree_load / norm_tree_reduce as a wavefront of k_project calls them for its channel.  ntr_global <= 1024.
+__global__ __launch_bounds__(64) void k_norm_trees_selftest(GradArgs a, int form)
+{
+        __shared__ double buf[kFoldMaxRows];
+        const int lane = (int)threadIdx.x;
+        if(form == 0) {
+                if(blockIdx.x == 0) { fold_tree(a, buf, lane); }
+                return;
+        }
+        WaveTreeRows tree;
+        norm_tree_load(a.rowsum, a.ntr_global, a.nch_total, blockIdx.x, lane, tree);
+        const float norm = norm_tree_reduce(tree);
+        if(lane == 0) { a.norm_out[blockIdx.x] = norm; }
+}
+
 // ---------------------------------------------------------------------------
 // Row-tiled runs inside one process (j2p_tiled): the two per-iteration exchanges as kernels that READ the other
 // bands' memory directly (peer access over xGMI, or plain device memory when bands share a GPU).

@@ -546,14 +546,55 @@ static void launch_band_log(j2p_solver *s, int which)
         }
 }
 
-// per-tile-row sums of the band's norm partials: blocks of up to 256 tile rows, as many as stage in LDS
+// The launches of the stand-alone reduction kernels as functions of plain arguments: what a solve launches and what
+// j2p_norm_selftest launches on a caller's arrays are the same lines (grid, LDS size, staging), so the hook cannot drift.
+static unsigned tree_width(unsigned tile_rows)           // P of tree_sum_lds: the power of two >= the tile rows
+{
+        unsigned P = 1;
+        while(P < tile_rows) { P <<= 1; }
+        return P;
+}
+// level 1: per-tile-row sums of norm partials: blocks of up to 256 tile rows, as many as stage in LDS
+static void launch_k_rowsums(hipStream_t st, const double *part, double *rowsum, unsigned ntx, unsigned tile_rows_local, unsigned nch)
+{
+        const unsigned total = tile_rows_local * nch;
+        unsigned per_block = kStageDoubles / ntx;
+        if(per_block > 256) { per_block = 256; }
+        hipLaunchKernelGGL(k_rowsums, dim3((total + per_block - 1) / per_block), dim3(256), 0, st,
+                           part, rowsum, ntx, tile_rows_local, nch, per_block);
+}
+// level 2 over the global [tile row][channel] sums
+static void launch_k_norm_finish(hipStream_t st, const double *rowsum_all, unsigned tile_rows_global, unsigned nch, float *norm)
+{
+        hipLaunchKernelGGL(k_norm_finish, dim3(nch), dim3(256), tree_width(tile_rows_global) * sizeof(double), st,
+                           rowsum_all, tile_rows_global, nch, norm);
+}
+// ... over the bands' own arrays (j2p_solver_norm_from_bands)
+static void launch_k_norm_bands(hipStream_t st, const BandRowsums &t, unsigned tile_rows_global, unsigned nch)
+{
+        hipLaunchKernelGGL(k_norm_bands, dim3(nch), dim3(256), tree_width(tile_rows_global) * sizeof(double), st, t, tile_rows_global, nch);
+}
+// both levels in one launch.  k_norm_whole (only the A/B baseline of the folded reduction, J2P_OPT_NORM_FOLD = 0) stages
+// the norm partials in up to 156 KiB of dynamic LDS: allowed once per device (idempotent) ...
+static hipError_t allow_k_norm_whole_lds()
+{
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_norm_whole), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNormLdsBytes);
+}
+// ... and as many of the partials staged at once as the CU's LDS holds (P <= 4096)
+static void launch_k_norm_whole(hipStream_t st, const double *part, unsigned ntx, unsigned tile_rows, unsigned nch, float *norm)
+{
+        const unsigned P = tree_width(tile_rows);
+        unsigned stage = 0;                                  // narrow canvases: direct form (4.6 vs 5.4 us at 4096^2)
+        if(ntx > 48) {
+                stage = tile_rows * ntx;
+                if((P + stage) * sizeof(double) > kNormLdsBytes) { stage = kNormLdsBytes / sizeof(double) - P; }
+        }
+        hipLaunchKernelGGL(k_norm_whole, dim3(nch), dim3(256), (P + stage) * sizeof(double), st, part, ntx, tile_rows, nch, norm, stage);
+}
+
 static void launch_rowsums(j2p_solver *s)
 {
-        const unsigned total = s->ntr_local * s->nch;
-        unsigned per_block = kStageDoubles / s->ntx;
-        if(per_block > 256) { per_block = 256; }
-        hipLaunchKernelGGL(k_rowsums, dim3((total + per_block - 1) / per_block), dim3(256), 0, s->stream,
-                           (const double *)s->part_g2, s->rowsum_local, s->ntx, s->ntr_local, s->nch, per_block);
+        launch_k_rowsums(s->stream, (const double *)s->part_g2, s->rowsum_local, s->ntx, s->ntr_local, s->nch);
 }
 
 // the end of a gradient phase — of a split one: on the solver's stream, which the caller has made wait for the boundary part
@@ -708,8 +749,6 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         if(log != s->phase_log) { return j2p_fail(J2P_ESTATE, "phase_project: logging differs from this iteration's gradient phase"); }
         if(part == 2 && !s->proj_boundary_done) { return j2p_fail(J2P_ESTATE, "interior part of phase_project before the boundary part"); }
         if(part != 2 && s->proj_boundary_done) { return j2p_fail(J2P_ESTATE, "boundary part of phase_project issued twice"); }
-        unsigned P = 1;
-        while(P < s->ntr_global) { P <<= 1; }
         // the global [tile row][channel] sums a band solver finishes ||g|| from: gathered by the caller, or — linked
         // bands — stored there by every band's gradient launch, even and odd iterations in two arrays
         const double *global_rows = s->whole ? rowsums_of(s, s->iter) : ((s->linked && (s->iter & 1)) ? s->rowsum_all_odd : s->rowsum_all);
@@ -719,21 +758,12 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         switch(part == 2 ? J2P_NORM_L2_EXTERNAL : s->plan.level2) {
         case J2P_NORM_L2_NORM_FINISH:
                 // level 1 came with the gradient phase (band solvers: the caller has gathered all bands' row sums)
-                hipLaunchKernelGGL(k_norm_finish, dim3(s->nch), dim3(256), P * sizeof(double), st,
-                                   global_rows, s->ntr_global, s->nch, s->norm);
+                launch_k_norm_finish(st, global_rows, s->ntr_global, s->nch, s->norm);
                 break;
-        case J2P_NORM_L2_NORM_WHOLE: {
-                // stage as many of the partials at once as the CU's LDS holds (P <= 4096)
-                unsigned stage = 0;                                  // narrow canvases: direct form (4.6 vs 5.4 us at 4096^2)
-                if(s->ntx > 48) {
-                        stage = s->ntr_local * s->ntx;
-                        if((P + stage) * sizeof(double) > kNormLdsBytes) { stage = kNormLdsBytes / sizeof(double) - P; }
-                }
-                hipLaunchKernelGGL(k_norm_whole, dim3(s->nch), dim3(256), (P + stage) * sizeof(double), st,
-                                   (const double *)s->part_g2, s->ntx, s->ntr_local, s->nch, s->norm, stage);
+        case J2P_NORM_L2_NORM_WHOLE:
+                launch_k_norm_whole(st, (const double *)s->part_g2, s->ntx, s->ntr_local, s->nch, s->norm);
                 break;
-        }
-        default: break;         // the gradient launch or the caller has written ||g||, or k_project runs the tree itself
+        default: break;        // the gradient launch or the caller has written ||g||, or k_project runs the tree itself
         }
         ProjArgs a;
         for(unsigned c = 0; c < s->nch; c++) { a.ch[c] = chan_dev(s, c); }
@@ -955,10 +985,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         DeviceGuard guard(device);
         if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
 
-        // k_norm_whole (only the A/B baseline of the folded reduction, J2P_OPT_NORM_FOLD = 0) stages the norm
-        // partials in up to 156 KiB of dynamic LDS (per device: idempotent)
-        if(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_norm_whole), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kNormLdsBytes) != hipSuccess) {
+        if(allow_k_norm_whole_lds() != hipSuccess) {
                 return j2p_fail(J2P_EDEVICE, "hipFuncSetAttribute(k_norm_whole, %u bytes of LDS) failed", kNormLdsBytes);
         }
         j2p_solver *s = new(std::nothrow) j2p_solver();
@@ -1641,6 +1668,16 @@ int j2p_solver_run(j2p_solver *s, unsigned n, j2p_log_row *rows)
         return J2P_OK;
 }
 
+int j2p_solver_debug_partials(j2p_solver *s, double **part_g2, unsigned *ntx, unsigned *tile_rows_local, unsigned *rows_per_tile)
+{
+        if(!s) { return j2p_fail(J2P_EINVAL, "solver is NULL"); }
+        if(part_g2) { *part_g2 = s->part_g2; }
+        if(ntx) { *ntx = s->ntx; }
+        if(tile_rows_local) { *tile_rows_local = s->ntr_local; }
+        if(rows_per_tile) { *rows_per_tile = s->rpw; }
+        return J2P_OK;
+}
+
 int j2p_solver_exchange_info(j2p_solver *s, j2p_exchange *info)
 {
         if(!s || !info) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
@@ -1797,9 +1834,7 @@ int j2p_solver_norm_from_bands(j2p_solver *s, unsigned nband, const double *cons
                 if(!own) { return j2p_fail(J2P_EINVAL, "norm_from_bands: the output list must contain the solver's own norm"); }
                 t.nout = nout;
         }
-        unsigned P = 1;
-        while(P < s->ntr_global) { P <<= 1; }
-        hipLaunchKernelGGL(k_norm_bands, dim3(s->nch), dim3(256), P * sizeof(double), s->stream, t, s->ntr_global, s->nch);
+        launch_k_norm_bands(s->stream, t, s->ntr_global, s->nch);
         HIP_TRY(hipGetLastError());
         // (a whole canvas whose k_project runs the tree keeps doing so: the words written here are the other bands')
         if(!(s->whole && s->plan.nip())) { s->plan.level2 = J2P_NORM_L2_EXTERNAL; }
@@ -2026,6 +2061,94 @@ int j2p_math_selftest(int device, size_t n, unsigned seed, unsigned long long *d
         if(div_mismatches) { *div_mismatches = hm[0]; }
         if(sqrt_mismatches) { *sqrt_mismatches = hm[1]; }
         return J2P_OK;
+}
+
+// one reduction form on the caller's arrays, launched exactly as a solve launches it (launch_k_* above)
+int j2p_norm_selftest_bands(int device, int form, unsigned nch, unsigned tile_rows, unsigned ntx, const double *in_host,
+                            unsigned nband, const unsigned first_tile_row[], const unsigned band_tile_rows[],
+                            double *rowsums_out_host, float *norm_out_host)
+{
+        const bool from_partials = form == J2P_NORM_FORM_ROWSUMS || form == J2P_NORM_FORM_NORM_WHOLE;
+        const bool in_kernel = form == J2P_NORM_FORM_FOLD_TREE || form == J2P_NORM_FORM_PROJECT_TREE;
+        if(form < J2P_NORM_FORM_ROWSUMS || form > J2P_NORM_FORM_PROJECT_TREE) { return j2p_fail(J2P_EINVAL, "norm_selftest: no form %d", form); }
+        if(!in_host || (form == J2P_NORM_FORM_ROWSUMS ? !rowsums_out_host : !norm_out_host)) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(nch == 0 || nch > (unsigned)kMaxCh) { return j2p_fail(J2P_EINVAL, "norm_selftest: 1..%d channels", kMaxCh); }
+        if(tile_rows == 0 || tile_rows > (in_kernel ? J2P_NORM_TREE_ROWS : (unsigned)kMaxTileRows)) {
+                return j2p_fail(J2P_EINVAL, "norm_selftest: form %d takes 1..%u tile rows", form, in_kernel ? J2P_NORM_TREE_ROWS : (unsigned)kMaxTileRows);
+        }
+        // (65536 columns, the JPEG limit, are 529 strips)
+        if(from_partials && (ntx == 0 || ntx > 529)) { return j2p_fail(J2P_EINVAL, "norm_selftest: 1..529 strips per tile row"); }
+        BandRowsums bands;
+        if(form == J2P_NORM_FORM_NORM_BANDS) {
+                if(!first_tile_row || !band_tile_rows || nband == 0 || nband > (unsigned)kMaxBands) { return j2p_fail(J2P_EINVAL, "norm_selftest: 1..%d bands", kMaxBands); }
+                std::vector<bool> covered(tile_rows, false);
+                for(unsigned b = 0; b < nband; b++) {
+                        if(first_tile_row[b] > tile_rows || band_tile_rows[b] > tile_rows - first_tile_row[b]) { return j2p_fail(J2P_EINVAL, "band %u: tile rows out of range", b); }
+                        for(unsigned r = 0; r < band_tile_rows[b]; r++) {
+                                if(covered[first_tile_row[b] + r]) { return j2p_fail(J2P_EINVAL, "band %u overlaps another", b); }
+                                covered[first_tile_row[b] + r] = true;
+                        }
+                }
+                for(unsigned r = 0; r < tile_rows; r++) {
+                        if(!covered[r]) { return j2p_fail(J2P_EINVAL, "the bands do not cover tile row %u", r); }
+                }
+        }
+        int ndev = 0;
+        if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
+        DeviceGuard guard(device);
+        if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        const size_t n_in = (size_t)nch * tile_rows * (from_partials ? ntx : 1u);
+        const size_t n_rowsums = (size_t)nch * tile_rows;
+        double *d_in = nullptr, *d_rowsums = nullptr;
+        float *d_norm = nullptr;
+        hipError_t e = hipMalloc(&d_in, n_in * sizeof(double));
+        if(e == hipSuccess) { e = hipMalloc(&d_rowsums, n_rowsums * sizeof(double)); }
+        if(e == hipSuccess) { e = hipMalloc(&d_norm, kMaxCh * sizeof(float)); }
+        if(e == hipSuccess) { e = hipMemcpy(d_in, in_host, n_in * sizeof(double), hipMemcpyHostToDevice); }
+        if(e == hipSuccess) { e = hipMemset(d_norm, 0xff, kMaxCh * sizeof(float)); }       // (NaN: a word nobody wrote shows)
+        if(e == hipSuccess && form == J2P_NORM_FORM_NORM_WHOLE) { e = allow_k_norm_whole_lds(); }
+        if(e == hipSuccess) {
+                switch(form) {
+                case J2P_NORM_FORM_ROWSUMS: launch_k_rowsums(nullptr, d_in, d_rowsums, ntx, tile_rows, nch); break;
+                case J2P_NORM_FORM_NORM_WHOLE: launch_k_norm_whole(nullptr, d_in, ntx, tile_rows, nch, d_norm); break;
+                case J2P_NORM_FORM_NORM_FINISH: launch_k_norm_finish(nullptr, d_in, tile_rows, nch, d_norm); break;
+                case J2P_NORM_FORM_NORM_BANDS:
+                        for(unsigned b = 0; b < nband; b++) {
+                                bands.rowsum[b] = d_in + (size_t)first_tile_row[b] * nch;
+                                bands.first[b] = first_tile_row[b];
+                                bands.count[b] = band_tile_rows[b];
+                        }
+                        bands.nband = nband;
+                        bands.out[0] = d_norm;
+                        bands.nout = 1;
+                        launch_k_norm_bands(nullptr, bands, tile_rows, nch);
+                        break;
+                default: {
+                        GradArgs a{};
+                        a.rowsum = d_in;
+                        a.ntr_global = tile_rows;
+                        a.nch_total = nch;
+                        a.norm_out = d_norm;
+                        hipLaunchKernelGGL(k_norm_trees_selftest, dim3(nch), dim3(64), 0, nullptr, a, form == J2P_NORM_FORM_FOLD_TREE ? 0 : 1);
+                        break;
+                }
+                }
+                e = hipGetLastError();
+        }
+        if(e == hipSuccess && form == J2P_NORM_FORM_ROWSUMS) { e = hipMemcpy(rowsums_out_host, d_rowsums, n_rowsums * sizeof(double), hipMemcpyDeviceToHost); }
+        else if(e == hipSuccess) { e = hipMemcpy(norm_out_host, d_norm, nch * sizeof(float), hipMemcpyDeviceToHost); }
+        (void)hipFree(d_in);
+        (void)hipFree(d_rowsums);
+        (void)hipFree(d_norm);
+        if(e != hipSuccess) { return j2p_fail(e == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE, "norm_selftest: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+int j2p_norm_selftest(int device, int form, unsigned nch, unsigned tile_rows, unsigned ntx, const double *in_host,
+                      double *rowsums_out_host, float *norm_out_host)
+{
+        const unsigned first = 0;
+        return j2p_norm_selftest_bands(device, form, nch, tile_rows, ntx, in_host, 1, &first, &tile_rows, rowsums_out_host, norm_out_host);
 }
 
 int j2p_sqrt_exhaustive(int device, unsigned long long *rsq_mismatches, unsigned long long *fast_mismatches)
