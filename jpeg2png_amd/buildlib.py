@@ -39,12 +39,15 @@ def _newer(target, sources):
 
 # every translation unit with the project headers it includes, directly or through another: what an edit rebuilds
 UNIT_HEADERS = {
-    "j2p_solver.hip": ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
+    "j2p_solver.hip": ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h", "j2p_geometry.h"),
     "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
-    "j2p_tiled.hip": ("j2p_internal.h",),
-    "j2p_batch.hip": ("j2p_internal.h",),
-    "compute_host.c": ("j2p_internal.h",),
+    "j2p_pool.hip": ("j2p_hip_host.h", "j2p_internal.h"),
+    "j2p_tiled.hip": ("j2p_internal.h", "j2p_geometry.h"),
+    "j2p_batch.hip": ("j2p_internal.h", "j2p_geometry.h"),
+    "compute_host.c": ("j2p_internal.h", "j2p_geometry.h"),
 }
+# the units the experiments build takes from the release build: they have no knobs
+NO_KNOBS = ("j2p_output.hip", "j2p_pool.hip")
 HIP_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".hip"))
 # the units that hold device code (the others are host code).  Only the solver's knows -DJ2P_DEBUG, -DJ2P_TRACE and
 # -DJ2P_EXP_*: the checked build and the A/B variants compile it alone and take every other object from the release build
@@ -125,7 +128,7 @@ def build_experiments(force=False, verbose=False):
     direction, where the norm is finished, ... (j2p_internal.h: j2p_exp_env) — and the split phases.  Same device code as
     the release build.  What the schedule-equivalence tests load (conftest.exp_lib)
     and the timing tools run on (J2P_LIBRARY=<this file>); never what a user of the library gets."""
-    build(force=False, verbose=verbose)             # compute_host.o and j2p_output.o, which have no knobs, are shared
+    build(force=False, verbose=verbose)             # compute_host.o and the NO_KNOBS objects are shared
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # (the objects do not travel with a gpurun lease, the library does: up to date against the SOURCES is enough)
     sources = {f for u in UNIT_HEADERS for f in _deps(u)}
@@ -133,8 +136,8 @@ def build_experiments(force=False, verbose=False):
         return EXP_LIB
     jobs, objs = [], []
     for u in HIP_UNITS:
-        if u == "j2p_output.hip":
-            objs.append(os.path.join(CSRC, "j2p_output.o"))
+        if u in NO_KNOBS:
+            objs.append(os.path.join(CSRC, u.replace(".hip", ".o")))
             continue
         src, obj = os.path.join(CSRC, u), os.path.join(CSRC, u.replace(".hip", "_exp.o"))
         objs.append(obj)

@@ -17,6 +17,7 @@
 #include "jpeg2png_amd.h"
 #include "jpeg2png_amd_compute.h"
 #include "j2p_internal.h"              /* the chunk rule (j2p_next_chunk), j2p_set_last_error, j2p_tiled_exchange_forced */
+#include "j2p_geometry.h"              /* the canvas, the band alignment and the least band */
 
 /* stands in for `omp critical(progressbar)` (compute.c:450): compute() may be entered from
  * several host threads at once (jpeg2png.c:147,330) and they share one progress bar */
@@ -266,10 +267,6 @@ int j2p_compute_tiled(unsigned nband, const int devices[], unsigned nchannel, st
         return compute_on(nband, devices, nchannel, coefs, log, pb, weight, pweight, iterations);
 }
 
-/* rows a band must at least have before compute() spreads a canvas over the GPUs of J2P_DEVICES: three 16-row
- * gradient segments, so that every band has an interior to hide the halo exchange behind */
-#define J2P_MIN_BAND_ROWS (3u * J2P_TILE_ROWS)
-
 void compute(unsigned nchannel, struct coef coefs[], struct logger *log, struct progressbar *pb,
              float weight, float pweight[], unsigned iterations)
 {
@@ -294,14 +291,12 @@ void compute(unsigned nchannel, struct coef coefs[], struct logger *log, struct 
         }
         unsigned nband = 1;
         if(ndev > 1 && coefs && nchannel >= 1 && nchannel <= J2P_MAX_CHANNELS) {
-                unsigned H = 0, align = J2P_TILE_ROWS;
+                j2p_canvas cv = J2P_CANVAS_NONE;
                 for(unsigned c = 0; c < nchannel; c++) {
-                        if(coefs[c].h * coefs[c].h_samp > H) { H = coefs[c].h * coefs[c].h_samp; }
-                        while(coefs[c].h_samp && align % (8 * coefs[c].h_samp)) { align += J2P_TILE_ROWS; }
+                        /* (a zero sampling factor is for the solver's create to report) */
+                        if(coefs[c].h_samp) { j2p_canvas_add(&cv, coefs[c].w, coefs[c].h, coefs[c].w_samp, coefs[c].h_samp); }
                 }
-                unsigned per = align > J2P_MIN_BAND_ROWS ? align : J2P_MIN_BAND_ROWS;
-                per = (per + align - 1) / align * align;
-                nband = H / per;
+                nband = cv.H / j2p_min_band_rows(cv.align);
                 if(nband > ndev) { nband = ndev; }
                 if(nband < 1) { nband = 1; }
         }

@@ -25,6 +25,7 @@
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
+#include "j2p_geometry.h"
 
 namespace {
 
@@ -60,8 +61,6 @@ namespace {
                 const int rc_ = (expr);                                                            \
                 if(rc_ != J2P_OK) { return rc_; }                                                  \
         } while(0)
-
-unsigned gcd_u(unsigned a, unsigned b) { return b ? gcd_u(b, a % b) : a; }
 
 // j2p_job::out_sub_w / out_sub_h: 0 means 1, so that zero-initialised jobs are 4:4:4
 unsigned out_sub(unsigned v) { return v ? v : 1u; }
@@ -248,41 +247,32 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
 {
         *handled = false;
         const unsigned nsolve = solves(d);
-        unsigned H[J2P_MAX_CHANNELS] = {0, 0, 0}, Wc[J2P_MAX_CHANNELS] = {0, 0, 0}, align = J2P_TILE_ROWS, hmin = ~0u;
+        // the canvas of every solve; the alignment is the one all the job's channels share
+        j2p_canvas all = J2P_CANVAS_NONE, cv[J2P_MAX_CHANNELS] = {J2P_CANVAS_NONE, J2P_CANVAS_NONE, J2P_CANVAS_NONE};
         for(unsigned c = 0; c < d.nchannel; c++) {
                 const j2p_plane &p = d.planes[c];
                 if(p.h_samp == 0 || p.h == 0 || p.w_samp == 0 || p.w == 0) { return j2p_fail(J2P_EINVAL, "job: channel %u: empty plane", c); }
-                align = align / gcd_u(align, 8 * p.h_samp) * (8 * p.h_samp);
-                const unsigned k = where(d, c).solve;
-                if(p.h * p.h_samp > H[k]) { H[k] = p.h * p.h_samp; }
-                if(p.w * p.w_samp > Wc[k]) { Wc[k] = p.w * p.w_samp; }
+                j2p_canvas_add(&all, p.w, p.h, p.w_samp, p.h_samp);
+                j2p_canvas_add(&cv[where(d, c).solve], p.w, p.h, p.w_samp, p.h_samp);
         }
+        const unsigned align = all.align;
+        unsigned hmin = ~0u;
         size_t pixels_min = ~(size_t)0;
         for(unsigned k = 0; k < nsolve; k++) {
-                if(H[k] < hmin) { hmin = H[k]; }
-                if((size_t)Wc[k] * H[k] < pixels_min) { pixels_min = (size_t)Wc[k] * H[k]; }
+                if(cv[k].H < hmin) { hmin = cv[k].H; }
+                if((size_t)cv[k].W * cv[k].H < pixels_min) { pixels_min = (size_t)cv[k].W * cv[k].H; }
         }
-        // at least three 16-row gradient segments per band
-        unsigned per = 3 * J2P_TILE_ROWS;
-        per = (per + align - 1) / align * align;
-        unsigned nband = hmin / per;
+        unsigned nband = hmin / j2p_min_band_rows(align);
         if(tile_min_band_pixels(d) && pixels_min / tile_min_band_pixels(d) < nband) { nband = (unsigned)(pixels_min / tile_min_band_pixels(d)); }
         if(nband > devices.size()) { nband = (unsigned)devices.size(); }
         if(nband > 32) { nband = 32; }
         if(nband < 2) { return J2P_OK; }
         // near-equal bands of the shortest canvas in units of the alignment; the last band ends where each canvas ends
         unsigned cuts[33];
-        {
-                const unsigned units = hmin / align;          // whole units; the remainder goes to the last band
-                unsigned start = 0;
-                for(unsigned b = 0; b < nband; b++) {
-                        cuts[b] = start * align;
-                        start += units / nband + (b < units % nband ? 1 : 0);
-                }
-        }
+        (void)j2p_near_equal_cuts(hmin / align, nband, align, cuts);      // whole units (at least nband); the remainder goes to the last band
         Engines eng;
         for(unsigned k = 0; k < nsolve; k++) {
-                cuts[nband] = H[k];
+                cuts[nband] = cv[k].H;
                 const int rc = j2p_tiled_create(&eng.e[k].t, nband, devices.data(), cuts, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k],
                                                 &d.pweight[k], d.iterations[k]);
                 if((rc == J2P_EDEVICE || rc == J2P_ENOMEM) && !j2p_tiled_exchange_forced()) {

@@ -98,10 +98,22 @@ j2p_solver_view j2p_solver_view_of(const j2p_solver *s);         // s is not NUL
 // the device address of canvas row y (one of the solver's own) of channel c in the current iterate; the rows after it follow
 // at a stride of W floats.  Hides the halo as j2p_solver_plane_ptr does.
 int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **row);
-// the device-memory pool of j2p_solver.hip, for buffers that live as long as one call: at least `bytes` bytes on `device`,
-// *got the size to give back with
+
+// ---- j2p_pool.hip ----
+// the device-memory pool, for a solver's arena and for buffers that live as long as one call: at least `bytes` bytes on
+// `device`, *got the size to give back with
 hipError_t j2p_pool_take(int device, size_t bytes, void **out, size_t *got);
 void j2p_pool_give(int device, void *ptr, size_t bytes);
+// hipMalloc that returns the pool's cached blocks to the device and tries once more when memory is short
+hipError_t j2p_dev_malloc(void **out, size_t bytes);
+// What is live on each device, for the non-temporal policy (j2p_solver.hip: nt_policy): the Infinity Cache is shared by
+// every solver iterating on the GPU — the images of a batch, the components of `-s`, the bands of a tiled run that
+// share a device — so the policy looks at the sum of their working sets, not at one solver's.
+struct LiveBytes {
+        size_t working_set = 0, g = 0, planes = 0, d = 0;
+};
+void j2p_live_add(int device, const LiveBytes &b, int sign);    // sign > 0: b joins the device's total, otherwise leaves it
+LiveBytes j2p_live_on(int device);
 
 // log rows from per-iteration sums like j2p_log_rows_from_sums(), but continuing a run: carried[] holds the prob
 // distance per channel of the state entering the first of the n iterations and is updated (all 0 at iteration 0);

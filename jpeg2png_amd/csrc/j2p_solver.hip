@@ -12,15 +12,19 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
-#include <mutex>
+#include <memory>
 #include <vector>
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
+#include "j2p_geometry.h"
 #include "j2p_hip_host.h"
 #include "j2p_kernels.hip.h"
 
 using namespace j2p;
+
+// what j2p_geometry.h restates of the kernels' constants
+static_assert(kStripCols == J2P_STRIP_COLS && kTY == J2P_TILE_ROWS && kHalo == J2P_HALO_ROWS, "j2p_geometry.h and j2p_kernels.hip.h disagree");
 
 namespace {
 
@@ -39,10 +43,8 @@ int j2p_fail(int code, const char *fmt, ...)
 
 namespace {
 
-struct ChanHost {
+struct ChanHost : j2p_row_window {           // crow0, crows: of d / pg held on this device; frow0, frows: of the decoded input (init only)
         unsigned cw = 0, ch = 0, ws = 1, hs = 1;
-        unsigned crow0 = 0, crows = 0;       // coefficient rows of d / pg held on this device
-        unsigned frow0 = 0, frows = 0;       // coefficient rows of the decoded input held (init only)
         float *xbuf[2] = {nullptr, nullptr}; // allocation bases, (rows + 2*halo) * W floats
         float *grad = nullptr;
         float *pg = nullptr;
@@ -116,7 +118,7 @@ struct j2p_solver {
         int nt = 0;                     // 0..3: streams with the non-temporal hint (nt_policy; J2P_OPT_NT_GRADIENT)
         bool nt_forced = false;         // set through J2P_OPT_NT_GRADIENT: the policy no longer touches it
         bool live_registered = false;   // this solver's bytes are part of the device's live total (nt_policy)
-        size_t live_ws = 0, live_g = 0, live_planes = 0, live_d = 0;
+        LiveBytes live;                 // what this solver adds to it
         bool phase_log = false;         // the gradient phase of the running iteration was issued with logging
         bool mixed_project = true;      // small canvases: all samplings in one projection launch (J2P_OPT_MIXED_PROJECT)
         bool wide_footprint = true;     // footprints 3, 4, 6, 8 columns wide take the wide-footprint path (J2P_OPT_WIDE_FOOTPRINT)
@@ -162,129 +164,6 @@ struct j2p_solver {
 
 namespace {
 
-// ---------------------------------------------------------------------------
-// Device-memory pool.  hipMalloc / hipFree cost milliseconds and hipFree synchronises the whole device, which
-// serialises the concurrent compute() calls of a multi-threaded host (jpeg2png.c:147,330) far more than the
-// solves themselves at 1080p.  A solver therefore makes ONE allocation (its arena) and returns it here when it
-// is destroyed; the next solver on that device takes the smallest cached block that fits.  Bounded: at most
-// kPoolBlocks blocks / kPoolBytes bytes stay cached per process, the rest is released; j2p_pool_trim() drops all.
-// ---------------------------------------------------------------------------
-struct PoolBlock {
-        int device;
-        void *ptr;
-        size_t bytes;
-};
-std::mutex g_pool_lock;
-std::vector<PoolBlock> g_pool;
-constexpr size_t kPoolBlocks = 16;                     // per device
-constexpr size_t kPoolBytesDefault = (size_t)8 << 30;  // per device; J2P_POOL_MIB overrides (0 = no caching)
-
-size_t pool_cap_bytes()
-{
-        static const size_t cap = [] {
-                const char *env = getenv("J2P_POOL_MIB");
-                if(env && *env) { return (size_t)strtoull(env, nullptr, 10) << 20; }
-                return kPoolBytesDefault;
-        }();
-        return cap;
-}
-
-void pool_drop_all()
-{
-        std::vector<PoolBlock> drop;
-        {
-                std::lock_guard<std::mutex> g(g_pool_lock);
-                drop.swap(g_pool);
-        }
-        for(const PoolBlock &b : drop) {
-                DeviceGuard guard(b.device);
-                (void)hipFree(b.ptr);
-        }
-}
-
-// hipMalloc for everything that does not go through the pool (log buffers, the stand-alone decode / DCT calls):
-// on out-of-memory the cached arenas go back to the device and the allocation is tried once more
-hipError_t dev_malloc(void **out, size_t bytes)
-{
-        hipError_t e = hipMalloc(out, bytes);
-        if(e == hipErrorOutOfMemory) {
-                (void)hipGetLastError();
-                pool_drop_all();
-                e = hipMalloc(out, bytes);
-        }
-        return e;
-}
-
-}  // namespace
-
-// (j2p_internal.h: the output stage's device buffers come from the pool too)
-hipError_t j2p_pool_take(int device, size_t bytes, void **out, size_t *got)
-{
-        {
-                std::lock_guard<std::mutex> g(g_pool_lock);
-                size_t best = g_pool.size();
-                for(size_t i = 0; i < g_pool.size(); i++) {
-                        const PoolBlock &b = g_pool[i];
-                        // a block more than twice the size asked for stays for a larger customer
-                        if(b.device == device && b.bytes >= bytes && b.bytes <= 2 * bytes + (1u << 20) &&
-                           (best == g_pool.size() || b.bytes < g_pool[best].bytes)) { best = i; }
-                }
-                if(best != g_pool.size()) {
-                        *out = g_pool[best].ptr;
-                        *got = g_pool[best].bytes;
-                        g_pool.erase(g_pool.begin() + (ptrdiff_t)best);
-                        return hipSuccess;
-                }
-        }
-        *got = bytes;
-        return dev_malloc(out, bytes);
-}
-
-void j2p_pool_give(int device, void *ptr, size_t bytes)
-{
-        if(!ptr) { return; }
-        {
-                std::lock_guard<std::mutex> g(g_pool_lock);
-                size_t total = bytes, blocks = 0;
-                for(const PoolBlock &b : g_pool) {
-                        if(b.device == device) { total += b.bytes; blocks++; }
-                }
-                if(blocks < kPoolBlocks && total <= pool_cap_bytes()) {
-                        g_pool.push_back(PoolBlock{device, ptr, bytes});
-                        return;
-                }
-        }
-        (void)hipFree(ptr);
-}
-
-namespace {
-
-// ---------------------------------------------------------------------------
-// What is live on each device, for the non-temporal policy (nt_policy): the Infinity Cache is shared by every
-// solver iterating on the GPU — the images of a batch, the components of `-s`, the bands of a tiled run that
-// share a device — so the policy looks at the sum of their working sets, not at one solver's.
-// ---------------------------------------------------------------------------
-struct LiveBytes {
-        size_t working_set = 0, g = 0, planes = 0, d = 0;
-};
-constexpr int kMaxDevices = 64;
-LiveBytes g_live[kMaxDevices];          // guarded by g_pool_lock
-
-void live_add(int device, const LiveBytes &b, int sign)
-{
-        if(device < 0 || device >= kMaxDevices) { return; }
-        std::lock_guard<std::mutex> g(g_pool_lock);
-        LiveBytes &l = g_live[device];
-        if(sign > 0) { l.working_set += b.working_set; l.g += b.g; l.planes += b.planes; l.d += b.d; }
-        else { l.working_set -= b.working_set; l.g -= b.g; l.planes -= b.planes; l.d -= b.d; }
-}
-LiveBytes live_on(int device)
-{
-        if(device < 0 || device >= kMaxDevices) { return LiveBytes{}; }
-        std::lock_guard<std::mutex> g(g_pool_lock);
-        return g_live[device];
-}
-
 // bump allocator over the arena: pass 1 (base == nullptr) only adds the sizes up
 struct Carver {
         char *base = nullptr;
@@ -315,21 +194,6 @@ void norm_defaults(j2p_solver *s)
         s->nip_form = s->whole && pixels <= kNormInProjectPixels ? 1 : 0;
         s->fold = !s->whole || s->nip_form || (pixels >= kFoldWholePixels && s->ntr_global <= J2P_NORM_TREE_ROWS);
 }
-// rows per gradient strip: 16; 8, then 4, while the strips make fewer wavefronts than half the chip's 4096 slots (the
-// launch is then one generation whose length is the busiest SIMD's: shorter strips balance it, at 25 / 50 instead of 12.5 %
-// redundant rows).  A limit of 4096 for the first step was measured too (profiles/r03_px_rpw_sweep.jsonl,
-// r03_rpw_concurrency.json): a single 2048^2 Y plane or 1080p 4:2:0 image gains 2 %, eight concurrent 1080p 4:2:0 images —
-// the batch case, where the chip is full anyway — lose 5.7 %; not taken
-constexpr unsigned long long kHalfStripWaves = 2048;
-constexpr unsigned long long kShortStripWaves = 2048;
-// half / quarter items at the end of a gradient launch (see j2p_solver_create): launches of fewer strips than this, and
-// the shares (1/256) of every XCD's run dealt that way
-constexpr unsigned long long kZoneMaxWaves = 3 * 4096;
-constexpr unsigned kZoneB = 32, kZoneC = 10;
-constexpr unsigned kBigZoneD = 200, kBigZoneB = 24, kBigZoneC = 8;
-
-unsigned gcd_u(unsigned a, unsigned b) { return b ? gcd_u(b, a % b) : a; }
-unsigned lcm_u(unsigned a, unsigned b) { return a / gcd_u(a, b) * b; }
 
 // nt_policy: which streams of the iteration get the non-temporal hint, so that what stays without it can live in
 // the 256 MiB Infinity Cache.  Per byte and iteration x_k and x_{k-1} are touched 2-3 times, g and the prob state
@@ -347,8 +211,7 @@ int nt_policy(const j2p_solver *s)
                 const char *env = j2p_exp_env("J2P_NT_SCOPE");
                 return env && strcmp(env, "solver") == 0;
         }();
-        LiveBytes l = live_on(s->device);
-        if(own_only || !s->live_registered) { l = LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}; }
+        const LiveBytes l = own_only || !s->live_registered ? s->live : j2p_live_on(s->device);
         if(l.working_set <= kNtWorkingSet) { return 0; }                        // everything fits
         if(l.working_set - l.g <= kNtWorkingSet) { return 1; }                  // everything but g fits
         if(l.planes + l.d <= kNtWorkingSet) { return 2; }                       // planes and d fit
@@ -364,11 +227,11 @@ void account_coefficient_bytes(j2p_solver *s)
                 const ChanHost &h = s->ch[c];
                 d_bytes += (size_t)(h.crows ? h.crows : 1) * h.cw * (h.narrow ? sizeof(uint8_t) : sizeof(int16_t));
         }
-        if(d_bytes == s->live_d) { return; }
-        if(s->live_registered) { live_add(s->device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, -1); }
-        s->live_ws = s->live_ws - s->live_d + d_bytes;
-        s->live_d = d_bytes;
-        if(s->live_registered) { live_add(s->device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, +1); }
+        if(d_bytes == s->live.d) { return; }
+        if(s->live_registered) { j2p_live_add(s->device, s->live, -1); }
+        s->live.working_set = s->live.working_set - s->live.d + d_bytes;
+        s->live.d = d_bytes;
+        if(s->live_registered) { j2p_live_add(s->device, s->live, +1); }
         if(!s->nt_forced) { s->nt = nt_policy(s); }
 }
 
@@ -637,7 +500,7 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.geo.seg_mul = seg_mul;
         a.geo.units = grad_units(s, nseg_launch);
         a.geo.ntr_launch = nseg_launch;
-        // (half / quarter items: whole phases of one channel per workgroup wavefront, see the policy in j2p_solver_create)
+        // (half / quarter items: whole phases of one channel per workgroup wavefront, see j2p_zone_shares in j2p_geometry.h)
         if(part == 0 && s->nch == 1) { a.geo.zone_d = s->zone_d; a.geo.zone_b = s->zone_b; a.geo.zone_c = s->zone_c; }
         a.geo.reverse = part == 0 && s->grad_reverse ? 1u : 0u;
         a.factor = s->factor;
@@ -903,6 +766,289 @@ int launch_init(j2p_solver *s)
         return J2P_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The stages of j2p_solver_create, in the order it runs them.  Each returns J2P_OK or the error with its text set; the
+// half-built solver is j2p_solver_create's to destroy.
+// ---------------------------------------------------------------------------
+
+// what the planes and the band say before a device is touched: the canvas, and in *band the rows the solver holds
+int validate(unsigned nchannel, const j2p_plane planes[], int band_local_arrays, j2p_canvas *cv, j2p_band *band, bool *is_whole)
+{
+        if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
+        for(unsigned c = 0; c < nchannel; c++) {
+                const j2p_plane &p = planes[c];
+                if(p.w == 0 || p.h == 0 || (p.w & 7) || (p.h & 7)) {
+                        return j2p_fail(J2P_EINVAL, "channel %u: coefficient plane %ux%u is not a positive multiple of 8 (box.c:6-7)", c, p.w, p.h);
+                }
+                if(p.w_samp == 0 || p.h_samp == 0) { return j2p_fail(J2P_EINVAL, "channel %u: zero sampling factor", c); }
+                if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
+                for(int j = 0; j < 64; j++) {
+                        if(p.quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
+                }
+                j2p_canvas_add(cv, p.w, p.h, p.w_samp, p.h_samp);
+        }
+        const unsigned H = cv->H, align = cv->align;
+        if(H > (unsigned)kMaxTileRows * kTY) { return j2p_fail(J2P_EINVAL, "canvas height %u exceeds %u", H, kMaxTileRows * kTY); }   // (shorter tile rows: only far below)
+        const bool covers = band->row_begin == 0 && (band->row_end == 0 || band->row_end >= H);
+        *is_whole = covers && !((band_local_arrays & J2P_BAND_EVEN_IF_WHOLE) && band->row_end >= H);   // (a band that names every row may stay one)
+        if(covers) { *band = j2p_band{0, H}; }
+        const unsigned row0 = band->row_begin, row1 = band->row_end;
+        if(!*is_whole) {
+                if(row0 >= row1 || row1 > H) { return j2p_fail(J2P_EINVAL, "bad band [%u,%u) for canvas height %u", row0, row1, H); }
+                if(row0 % align || (row1 % align && row1 != H)) {
+                        return j2p_fail(J2P_EINVAL, "band [%u,%u) must be aligned to %u rows", row0, row1, align);
+                }
+        }
+        return J2P_OK;
+}
+
+// the solver's geometry: every channel's row windows, the strip schedule, the reductions' extents.  Pure but for the
+// experiment switches read from the environment (once, here).
+int place(j2p_solver *s, const j2p_plane planes[], const float pweight[], int band_local_arrays)
+{
+        const unsigned W = s->W, H = s->H, nchannel = s->nch;
+        s->band_local = !s->whole && (band_local_arrays & J2P_BAND_LOCAL_ARRAYS) != 0;
+        {
+                // one projection launch per sampling class also on small canvases (J2P_OPT_MIXED_PROJECT)
+                const char *env = j2p_exp_env("J2P_MIXED_PROJECT");
+                if(env) { s->mixed_project = atoi(env) != 0; }
+                // ... and (A/B timing): band solvers finish ||g|| with a k_norm_finish launch instead of inside k_project
+                env = j2p_exp_env("J2P_BAND_NIP");
+                if(env) { s->band_nip = atoi(env) != 0; }
+        }
+        for(unsigned c = 0; c < nchannel; c++) {
+                const j2p_plane &p = planes[c];
+                ChanHost &h = s->ch[c];
+                h.cw = p.w; h.ch = p.h; h.ws = p.w_samp; h.hs = p.h_samp;
+                h.pweight = pweight[c];
+                if(!j2p_row_window_of(h.ch, h.hs, H, s->row0, s->row0 + s->rows, s->band_local, &h)) {
+                        return j2p_fail(J2P_EINVAL, "band-local arrays need every channel to cover the canvas height");
+                }
+        }
+        // reductions: tile rows are counted on the canvas, the band owns a contiguous range
+        j2p_strip_schedule sched = j2p_strip_schedule_of(W, H, s->rows, nchannel);
+        // (timing experiments: J2P_RPW = 2 ... 64 for every solver of the process; band solvers take
+        // only the divisors of the band alignment, 16 — tools/rpw_fine.py sweeps the rest on whole canvases)
+        if(const char *env = j2p_exp_env("J2P_RPW")) {
+                const int v = atoi(env);
+                if(v >= 2 && v <= 64 && (s->whole || kTY % v == 0)) {
+                        sched.rpw = (unsigned)v;
+                        j2p_zone_shares(&sched, s->rows, nchannel);
+                }
+        }
+        // (halves need two groups of four rows per tile row, quarters four: march_rows)
+        const unsigned g = sched.rpw;
+        if(const char *env = j2p_exp_env("J2P_ZONE_B")) { if(nchannel == 1 && g >= 8) { sched.zone_b = (unsigned)atoi(env); } }
+        if(const char *env = j2p_exp_env("J2P_ZONE_C")) { if(nchannel == 1 && g >= 16) { sched.zone_c = (unsigned)atoi(env); } }
+        if(const char *env = j2p_exp_env("J2P_ZONE_D")) { if(nchannel == 1 && g >= 8) { sched.zone_d = (unsigned)atoi(env); } }
+        j2p_zone_clamp(&sched);
+        s->rpw = sched.rpw;
+        s->ntx = sched.strips;
+        s->zone_d = sched.zone_d; s->zone_b = sched.zone_b; s->zone_c = sched.zone_c;
+        s->nseg = (s->rows + s->rpw - 1) / s->rpw;
+        s->ntr_local = s->nseg;
+        s->ntr_global = (H + s->rpw - 1) / s->rpw;
+        s->first_tr = s->row0 / s->rpw;
+        norm_defaults(s);
+        for(unsigned c = 0; c < nchannel; c++) {
+                const ChanHost &h = s->ch[c];
+                const unsigned strips = ((W + 64 * h.ws - 1) / (64 * h.ws)) * ((s->rows + 8 * h.hs - 1) / (8 * h.hs));
+                if(strips > s->strips_stride) { s->strips_stride = strips; }
+        }
+        return J2P_OK;
+}
+
+// floats of one x buffer: the solver's rows with a halo above and below
+size_t plane_floats_of(const j2p_solver *s) { return (size_t)(s->rows + 2 * kHalo) * s->W; }
+
+// one arena for everything (sizes first, then the pointers)
+int carve_arena(j2p_solver *s, const j2p_plane planes[])
+{
+        const int device = s->device;
+        const unsigned W = s->W, nchannel = s->nch, max_strips = s->strips_stride;
+        const size_t ntiles = (size_t)s->ntx * s->ntr_local, plane_floats = plane_floats_of(s);
+        float *q_all = nullptr;
+        Carver carve;
+        for(int pass = 0; pass < 2; pass++) {
+                if(pass == 1) {
+                        HIP_TRY(j2p_pool_take(device, carve.used + 256, &s->arena, &s->arena_bytes));
+                        carve.base = static_cast<char *>(s->arena);
+                        carve.used = 0;
+                }
+                for(unsigned c = 0; c < nchannel; c++) {
+                        ChanHost &h = s->ch[c];
+                        carve.take(h.xbuf[0], plane_floats);
+                        carve.take(h.xbuf[1], plane_floats);
+                        carve.take(h.grad, (size_t)s->rows * W);
+                        // the prob state always has at least one (zero) row: the gradient kernel reads it unconditionally
+                        carve.take(h.pg, (size_t)(h.crows ? h.crows : 1) * h.cw);
+                        carve.take(h.decoded, (size_t)h.frows * h.cw);
+                        carve.take(h.d, (size_t)(h.crows ? h.crows : 1) * h.cw);
+                        carve.take(h.d8, (size_t)(h.crows ? h.crows : 1) * h.cw);
+                        // device-side decode of a band's input window (own rows + halo rows, rounded out to whole
+                        // block rows) normally borrows the two x buffers as scratch; a band of only a few rows is
+                        // smaller than that window, and gets scratch of its own
+                        if(!planes[c].fdata) {
+                                const size_t cells = (size_t)((h.frow0 + h.frows + 7) / 8 - h.frow0 / 8) * 8 * h.cw;
+                                if(cells > plane_floats) {
+                                        carve.take(h.scratch_f, cells);
+                                        carve.take(h.scratch_d, cells);
+                                }
+                        }
+                }
+                carve.take(q_all, 64 * kMaxCh);
+                carve.take(s->part_g2, ntiles * nchannel);
+                carve.take(s->rowsum_local, (size_t)s->ntr_local * nchannel);
+                if(s->whole) {
+                        s->rowsum_all = s->rowsum_local;
+                } else {
+                        carve.take(s->rowsum_all, (size_t)s->ntr_global * nchannel);
+                        carve.take(s->rowsum_all_odd, (size_t)s->ntr_global * nchannel);
+                        carve.take(s->push_dev, 2);
+                        carve.take(s->rowsum_odd, (size_t)s->ntr_local * nchannel);
+                }
+                carve.take(s->norm, kMaxCh);
+                carve.take(s->tickets, (size_t)s->ntr_local + 1);
+                carve.take(s->dbg_counters, 3);
+                carve.take(s->d_maxabs, kMaxCh);
+                carve.take(s->part_tv, ntiles * 2);
+                carve.take(s->part_prob, (size_t)max_strips * nchannel);
+        }
+        for(unsigned c = 0; c < nchannel; c++) { s->ch[c].q = q_all + 64 * c; }
+        return J2P_OK;
+}
+
+// nt_policy (see nt_policy() above): this solver's bytes join the device's live total
+void register_live_bytes(j2p_solver *s)
+{
+        const size_t plane_floats = plane_floats_of(s);
+        for(unsigned c = 0; c < s->nch; c++) {
+                const ChanHost &h = s->ch[c];
+                const size_t cells = (size_t)(h.crows ? h.crows : 1) * h.cw;
+                s->live.working_set += (2 * plane_floats + (size_t)s->rows * s->W + cells) * sizeof(float) + cells * sizeof(int16_t);
+                s->live.planes += 2 * plane_floats * sizeof(float);
+                s->live.d += cells * sizeof(int16_t);
+        }
+        s->live.g = (size_t)s->nch * s->rows * s->W * sizeof(float);
+        j2p_live_add(s->device, s->live, +1);
+        s->live_registered = true;
+        s->nt = nt_policy(s);
+        // canvases whose planes x_k, x_{k-1} do not both fit the Infinity Cache: the gradient phase walks bottom-up
+        // (k_project walks top-down), so that each phase starts on the rows the one before touched last (Geo::reverse).
+        // Schedule only: the bits do not depend on who marches a row when.
+        s->grad_reverse = s->live.planes > kNtWorkingSet;
+        if(const char *env = j2p_exp_env("J2P_GRAD_REVERSE")) { s->grad_reverse = atoi(env) != 0; }
+}
+
+// the quantization tables go up, the counters start at zero.  qf: 64 * kMaxCh floats of the caller's that stay until the
+// stream has been synchronised (decide_narrow_and_wide)
+int upload_tables(j2p_solver *s, const j2p_plane planes[], float qf[])
+{
+        const unsigned nchannel = s->nch, max_strips = s->strips_stride;
+        float *q_all = s->ch[0].q;
+        for(unsigned c = 0; c < nchannel; c++) {
+                for(int j = 0; j < 64; j++) { qf[64 * c + j] = (float)planes[c].quant_table[j]; }
+        }
+        HIP_TRY(hipMemcpyAsync(q_all, qf, sizeof(float) * 64 * nchannel, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemsetAsync(s->tickets, 0, ((size_t)s->ntr_local + 1) * sizeof(unsigned), s->stream));
+        HIP_TRY(hipMemsetAsync(s->part_prob, 0, (size_t)max_strips * nchannel * sizeof(double), s->stream));
+        HIP_TRY(hipMemsetAsync(s->dbg_counters, 0, 3 * sizeof(unsigned long long), s->stream));
+        HIP_TRY(hipMemsetAsync(s->d_maxabs, 0, kMaxCh * sizeof(unsigned), s->stream));
+        return J2P_OK;
+}
+
+// one channel's coefficients go up (host arrays: whole-image unless band_local) and are narrowed to bytes; its input
+// window goes up decoded, or is decoded here
+int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p)
+{
+        ChanHost &h = s->ch[c];
+        const size_t plane_floats = plane_floats_of(s);
+        const size_t host_row0 = s->band_local ? h.crow0 : 0;
+        if(h.crows) {
+                // block-major: coefficient row r lives in block row r/8; rows are block aligned
+                const int16_t *src = p.data + (size_t)(h.crow0 - host_row0) * h.cw;
+                HIP_TRY(hipMemcpyAsync(h.d, src, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
+                // ... and once more as bytes, with the largest |d| (decide_narrow_and_wide reads it back)
+                const size_t cells = (size_t)h.crows * h.cw;
+                const unsigned blocks = (unsigned)((cells / 8 + 255) / 256);
+                hipLaunchKernelGGL(k_narrow_coefficients, dim3(blocks < 2048 ? (blocks ? blocks : 1) : 2048), dim3(256), 0, s->stream,
+                                   (const int16_t *)h.d, h.d8, cells, s->d_maxabs + c);
+        }
+        if(p.fdata) {
+                const float *src = p.fdata + (size_t)(h.frow0 - host_row0) * h.cw;
+                HIP_TRY(hipMemcpyAsync(h.decoded, src, (size_t)h.frows * h.cw * sizeof(float), hipMemcpyHostToDevice, s->stream));
+                return J2P_OK;
+        }
+        // decode on the device (jpeg.c:83-92 + box.c:5-19): whole block rows [b0, b1) of the input
+        // window.  Band rows are block aligned, so when the window has no halo rows (band_local, or
+        // a whole canvas) the blocks are already in h.d; otherwise the coefficients of the
+        // window go up once more into the (not yet initialised) gradient plane as scratch.
+        const unsigned b0 = h.frow0 / 8, b1 = (h.frow0 + h.frows + 7) / 8;
+        const unsigned nb_rows = b1 - b0;
+        const unsigned groups = ((h.cw / 8 + 7) / 8) * nb_rows;
+        // (cannot fire: carve_arena gave the channel scratch of its own exactly when the window's floats exceed an x
+        // buffer, and the int16 window is half of them)
+        if(!h.scratch_f && (size_t)nb_rows * 8 * h.cw > plane_floats) {
+                return j2p_fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
+        }
+        const int16_t *dsrc = nullptr;
+        if(h.crows && b0 * 8 >= h.crow0 && b1 * 8 <= h.crow0 + h.crows) {
+                dsrc = h.d + (size_t)(b0 * 8 - h.crow0) * h.cw;
+        } else {
+                // scratch: the first x buffer holds (rows + 4) * W floats >= the window's int16 data
+                int16_t *dtmp = h.scratch_d ? h.scratch_d : reinterpret_cast<int16_t *>(h.xbuf[0]);
+                const int16_t *src = p.data + (size_t)(b0 * 8 - host_row0) * h.cw;
+                HIP_TRY(hipMemcpyAsync(dtmp, src, (size_t)nb_rows * 8 * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
+                dsrc = dtmp;
+        }
+        if(h.frow0 == b0 * 8 && h.frows == nb_rows * 8) {
+                hipLaunchKernelGGL(k_decode, dim3((groups + 3) / 4), dim3(256), 0, s->stream, dsrc,
+                                   (const float *)h.q, h.decoded, h.cw, nb_rows);
+        } else {
+                // window not block aligned (halo rows of a band): decode into the second x buffer, copy the rows
+                float *ftmp = h.scratch_f ? h.scratch_f : h.xbuf[1];
+                hipLaunchKernelGGL(k_decode, dim3((groups + 3) / 4), dim3(256), 0, s->stream, dsrc,
+                                   (const float *)h.q, ftmp, h.cw, nb_rows);
+                HIP_TRY(hipMemcpyAsync(h.decoded, ftmp + (size_t)(h.frow0 - b0 * 8) * h.cw,
+                                       (size_t)h.frows * h.cw * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+        }
+        HIP_TRY(hipGetLastError());
+        return J2P_OK;
+}
+
+// waits for the uploads, then decides per channel what the projection reads: bytes where the values allow, and the
+// wide-footprint path for the footprints it has
+int decide_narrow_and_wide(j2p_solver *s)
+{
+        // (the largest |d| per channel comes back on the solver's own stream: a synchronous copy would wait for every
+        // blocking stream of the device)
+        unsigned maxabs[kMaxCh] = {0};
+        HIP_TRY(hipMemcpyAsync(maxabs, s->d_maxabs, sizeof(maxabs), hipMemcpyDeviceToHost, s->stream));
+        // the host arrays (and j2p_solver_create's stack table) may go away as soon as this returns
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        {
+                // one byte per coefficient where the channel's values allow it: the projection then reads d8 (ChanDev::d8)
+                const char *env = j2p_exp_env("J2P_NARROW_COEFFICIENTS");
+                for(unsigned c = 0; c < s->nch; c++) {
+                        ChanHost &h = s->ch[c];
+                        h.narrow_fits = h.crows != 0 && maxabs[c] <= 127;
+                        h.narrow = h.narrow_fits && !(env && atoi(env) == 0);
+                }
+                account_coefficient_bytes(s);
+        }
+        {
+                // the wide-footprint projection path for the footprints it has (J2P_OPT_WIDE_FOOTPRINT)
+                const char *env = j2p_exp_env("J2P_WIDE_FOOTPRINT");
+                s->wide_footprint = !(env && atoi(env) == 0);
+                set_wide_footprint(s);
+        }
+        return J2P_OK;
+}
+
+struct DestroySolver {
+        void operator()(j2p_solver *s) const { j2p_solver_destroy(s); }
+};
+
 }  // namespace
 
 extern "C" {
@@ -934,7 +1080,7 @@ void j2p_solver_destroy(j2p_solver *s)
         if(!s) { return; }
         DeviceGuard guard(s->device);
         if(s->stream) { (void)hipStreamSynchronize(s->stream); }
-        if(s->live_registered) { live_add(s->device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, -1); }
+        if(s->live_registered) { j2p_live_add(s->device, s->live, -1); }
         j2p_pool_give(s->device, s->arena, s->arena_bytes);
         (void)hipFree(s->logsums);
         (void)hipFree(s->log_band);
@@ -944,39 +1090,15 @@ void j2p_solver_destroy(j2p_solver *s)
         delete s;
 }
 
-void j2p_pool_trim(void) { pool_drop_all(); }
-
 int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
                       float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
 {
         if(!out || !planes || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *out = nullptr;
-        if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
-        unsigned W = 0, H = 0, align = (unsigned)J2P_TILE_ROWS;
-        for(unsigned c = 0; c < nchannel; c++) {
-                const j2p_plane &p = planes[c];
-                if(p.w == 0 || p.h == 0 || (p.w & 7) || (p.h & 7)) {
-                        return j2p_fail(J2P_EINVAL, "channel %u: coefficient plane %ux%u is not a positive multiple of 8 (box.c:6-7)", c, p.w, p.h);
-                }
-                if(p.w_samp == 0 || p.h_samp == 0) { return j2p_fail(J2P_EINVAL, "channel %u: zero sampling factor", c); }
-                if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
-                for(int j = 0; j < 64; j++) {
-                        if(p.quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
-                }
-                if(p.w * p.w_samp > W) { W = p.w * p.w_samp; }     // compute.c:410-416
-                if(p.h * p.h_samp > H) { H = p.h * p.h_samp; }
-                align = lcm_u(align, 8 * p.h_samp);
-        }
-        if(H > (unsigned)kMaxTileRows * kTY) { return j2p_fail(J2P_EINVAL, "canvas height %u exceeds %u", H, kMaxTileRows * kTY); }   // (shorter tile rows: only far below)
-        bool whole = band.row_begin == 0 && (band.row_end == 0 || band.row_end >= H);
-        if(whole && (band_local_arrays & J2P_BAND_EVEN_IF_WHOLE) && band.row_end >= H) { whole = false; band.row_end = H; }
-        unsigned row0 = whole ? 0 : band.row_begin, row1 = whole ? H : band.row_end;
-        if(!whole) {
-                if(row0 >= row1 || row1 > H) { return j2p_fail(J2P_EINVAL, "bad band [%u,%u) for canvas height %u", row0, row1, H); }
-                if(row0 % align || (row1 % align && row1 != H)) {
-                        return j2p_fail(J2P_EINVAL, "band [%u,%u) must be aligned to %u rows", row0, row1, align);
-                }
-        }
+        j2p_canvas cv = J2P_CANVAS_NONE;
+        bool whole = true;
+        int rc = validate(nchannel, planes, band_local_arrays, &cv, &band, &whole);
+        if(rc != J2P_OK) { return rc; }
         int ndev = 0;
         if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
                 return j2p_fail(J2P_EDEVICE, "no HIP device available: the jpeg2png_amd solver has no CPU fallback");
@@ -984,311 +1106,39 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         if(device < 0 || device >= ndev) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, ndev - 1); }
         DeviceGuard guard(device);
         if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
-
         if(allow_k_norm_whole_lds() != hipSuccess) {
                 return j2p_fail(J2P_EDEVICE, "hipFuncSetAttribute(k_norm_whole, %u bytes of LDS) failed", kNormLdsBytes);
         }
-        j2p_solver *s = new(std::nothrow) j2p_solver();
+        // the half-built solver is destroyed by every return but the last
+        std::unique_ptr<j2p_solver, DestroySolver> owner(new(std::nothrow) j2p_solver());
+        j2p_solver *s = owner.get();
         if(!s) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
         s->device = device;
         s->nch = nchannel;
-        s->W = W;
-        s->H = H;
-        s->row0 = row0;
-        s->rows = row1 - row0;
+        s->W = cv.W;
+        s->H = cv.H;
+        s->row0 = band.row_begin;
+        s->rows = band.row_end - band.row_begin;
         s->whole = whole;
-        s->band_local = !whole && (band_local_arrays & J2P_BAND_LOCAL_ARRAYS) != 0;
         s->weight = weight;
         s->iterations = iterations;
-        {
-                // schedule switches tests reach through the environment (read once, here): one projection launch per
-                // sampling class also on small canvases (J2P_OPT_MIXED_PROJECT)
-                const char *env = j2p_exp_env("J2P_MIXED_PROJECT");
-                if(env) { s->mixed_project = atoi(env) != 0; }
-                // ... and (A/B timing): band solvers finish ||g|| with a k_norm_finish launch instead of inside k_project
-                env = j2p_exp_env("J2P_BAND_NIP");
-                if(env) { s->band_nip = atoi(env) != 0; }
-        }
-        int rc = J2P_OK;
-#define CREATE_TRY(expr)                                                                           \
-        do {                                                                                       \
-                hipError_t e_ = (expr);                                                            \
-                if(e_ != hipSuccess) {                                                             \
-                        rc = j2p_fail(e_ == hipErrorOutOfMemory ? J2P_ENOMEM : J2P_EDEVICE,            \
-                                  "%s failed: %s", #expr, hipGetErrorString(e_));                  \
-                        j2p_solver_destroy(s);                                                     \
-                        return rc;                                                                 \
-                }                                                                                  \
-        } while(0)
         if(stream) { s->stream = (hipStream_t)stream; }
         else {
-                CREATE_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+                HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
                 s->own_stream = true;
         }
-
-        // ---- geometry of every buffer ----
-        for(unsigned c = 0; c < nchannel; c++) {
-                const j2p_plane &p = planes[c];
-                ChanHost &h = s->ch[c];
-                h.cw = p.w; h.ch = p.h; h.ws = p.w_samp; h.hs = p.h_samp;
-                h.pweight = pweight[c];
-                // coefficient rows of the band (block aligned because the band is)
-                unsigned c0 = row0 / h.hs, c1 = (row1 + h.hs - 1) / h.hs;
-                if(c0 > h.ch) { c0 = h.ch; }
-                if(c1 > h.ch) { c1 = h.ch; }
-                h.crow0 = c0;
-                h.crows = c1 - c0;
-                // rows of the decoded input the init kernel touches (own rows + halo, clamped like compute.c:298)
-                if(s->band_local) {
-                        if(h.ch * h.hs < H) {
-                                rc = j2p_fail(J2P_EINVAL, "band-local arrays need every channel to cover the canvas height");
-                                j2p_solver_destroy(s);
-                                return rc;
-                        }
-                        h.frow0 = h.crow0;
-                        h.frows = h.crows;
-                } else {
-                        const unsigned y0 = row0 >= (unsigned)kHalo ? row0 - kHalo : 0;
-                        const unsigned y1 = row1 + kHalo < H ? row1 + kHalo : H;
-                        unsigned f0 = y0 / h.hs, f1 = (y1 - 1) / h.hs + 1;
-                        if(f0 > h.ch - 1) { f0 = h.ch - 1; }
-                        if(f1 > h.ch) { f1 = h.ch; }
-                        if(f1 <= f0) { f1 = f0 + 1; }
-                        h.frow0 = f0;
-                        h.frows = f1 - f0;
-                }
-        }
-        // reductions: tile rows are counted on the canvas, the band owns a contiguous range
-        // Gradient strips: 128 columns (two per lane, packed arithmetic) by rpw rows = rows per norm partial ("tile row").
-        // A canvas that fills the chip: 16 rows (32 / 48 / 64 measured no faster).  A smaller canvas leaves
-        // wavefront slots empty and is bound by how long ONE wavefront takes to walk its rows (wave timelines,
-        // profiles/r03_wave_trace.jsonl: ~0.9 us per row trip whatever the SIMD's load), so it gets shorter strips (8 or 4
-        // rows: fewer trips per wavefront; narrower strips do not pay).  Functions of the CANVAS only (never
-        // of the band), so that every band of a tiled run — and the whole-canvas solver — reduce ||g|| over the same
-        // partials in the same order.
-        {
-                const unsigned strips = W <= 4 ? 1u : (W - 4 + kStripCols - 1) / kStripCols;
-                auto waves = [&](unsigned g) { return (unsigned long long)strips * nchannel * ((H + g - 1) / g); };
-                unsigned g = kTY;
-                // (limits measured, profiles/r03_px_rpw_sweep.jsonl)
-                if(waves(g) < kHalfStripWaves) { g = 8; }
-                if(g == 8 && waves(g) < kShortStripWaves) { g = 4; }
-                // (timing experiments: J2P_RPW = 2 ... 64 for every solver of the process; band solvers take
-                // only the divisors of the band alignment, 16 — tools/rpw_fine.py sweeps the rest on whole canvases)
-                if(const char *env = j2p_exp_env("J2P_RPW")) {
-                        const int v = atoi(env);
-                        if(v >= 2 && v <= 64 && (s->whole || kTY % v == 0)) { g = (unsigned)v; }
-                }
-                s->rpw = g;
-                s->ntx = strips;
-                // The LAST wavefronts of a gradient launch march half and quarter tile rows (grad_item): a launch ends with
-                // its last wavefront, and a whole 16-row item dispatched last keeps a few SIMDs busy for a wavefront life
-                // (17 us of 53 at 4096^2, profiles/r06_wave_trace.jsonl) while the rest of the chip drains.  Shares in
-                // 1/256 of every XCD's run; one channel per workgroup wavefront.  Who marches a row never changes a bit
-                // (march_rows), so the choice may depend on the BAND: measured (profiles/r06_zones_mid_sizes.jsonl,
-                // r06_zones_by_size.jsonl; us per iteration without / with) 1080p 30.1 / 28.7, 2048^2 45.5 / 42.2,
-                // 4096x2048 70.9 / 67.8, 4096x3072 94.2 / 92.0, 4096^2 120.0 / 118.7; nothing from three wavefront
-                // generations on (8192x4096 235.3 / 235.9, 16384x2048 230.8 / 231.1, 8192^2 515.7 / 515.8).
-                const unsigned long long launch_waves = (unsigned long long)strips * ((s->rows + g - 1) / g);
-                if(nchannel == 1 && g >= 8 && launch_waves < kZoneMaxWaves) {
-                        s->zone_b = kZoneB;
-                        s->zone_c = g >= 16 ? kZoneC : 0;
-                } else if(nchannel == 1 && g >= 16) {
-                        // ... and from three generations on the FIRST workgroups march two tile rows at once (34 row trips for
-                        // 32 rows: fewer source rows recomputed and re-read), the tail shares smaller: 16384x2048 229.8 -> 227.0
-                        // us per iteration, 8192^2 476.0 -> 471.1; below that doubles cost more at the end of the launch than they
-                        // save (2048^2 43.2 -> 46.0, 4096x2048 69.3 -> 72.4, 4096^2 +-0: profiles/r06_doubles.jsonl)
-                        s->zone_d = kBigZoneD;
-                        s->zone_b = kBigZoneB;
-                        s->zone_c = kBigZoneC;
-                }
-                // (halves need two groups of four rows per tile row, quarters four: march_rows)
-                if(const char *env = j2p_exp_env("J2P_ZONE_B")) { if(nchannel == 1 && g >= 8) { s->zone_b = (unsigned)atoi(env); } }
-                if(const char *env = j2p_exp_env("J2P_ZONE_C")) { if(nchannel == 1 && g >= 16) { s->zone_c = (unsigned)atoi(env); } }
-                if(const char *env = j2p_exp_env("J2P_ZONE_D")) { if(nchannel == 1 && g >= 8) { s->zone_d = (unsigned)atoi(env); } }
-                if(s->zone_b > 256) { s->zone_b = 256; }
-                if(s->zone_b + s->zone_c > 256) { s->zone_c = 256 - s->zone_b; }
-                if(s->zone_d + s->zone_b + s->zone_c > 256) { s->zone_d = 256 - s->zone_b - s->zone_c; }
-        }
-        s->nseg = (s->rows + s->rpw - 1) / s->rpw;
-        s->ntr_local = s->nseg;
-        s->ntr_global = (H + s->rpw - 1) / s->rpw;
-        s->first_tr = row0 / s->rpw;
-        norm_defaults(s);
-        const size_t ntiles = (size_t)s->ntx * s->ntr_local;
-        unsigned max_strips = 0;
-        for(unsigned c = 0; c < nchannel; c++) {
-                const ChanHost &h = s->ch[c];
-                const unsigned strips = ((W + 64 * h.ws - 1) / (64 * h.ws)) * ((s->rows + 8 * h.hs - 1) / (8 * h.hs));
-                if(strips > max_strips) { max_strips = strips; }
-        }
-        s->strips_stride = max_strips;
-        // ---- one arena for everything (sizes first, then the pointers) ----
-        const size_t plane_floats = (size_t)(s->rows + 2 * kHalo) * W;
-        float *q_all = nullptr;
-        Carver carve;
-        for(int pass = 0; pass < 2; pass++) {
-                if(pass == 1) {
-                        CREATE_TRY(j2p_pool_take(device, carve.used + 256, &s->arena, &s->arena_bytes));
-                        carve.base = static_cast<char *>(s->arena);
-                        carve.used = 0;
-                }
-                for(unsigned c = 0; c < nchannel; c++) {
-                        ChanHost &h = s->ch[c];
-                        carve.take(h.xbuf[0], plane_floats);
-                        carve.take(h.xbuf[1], plane_floats);
-                        carve.take(h.grad, (size_t)s->rows * W);
-                        // the prob state always has at least one (zero) row: the gradient kernel reads it unconditionally
-                        carve.take(h.pg, (size_t)(h.crows ? h.crows : 1) * h.cw);
-                        carve.take(h.decoded, (size_t)h.frows * h.cw);
-                        carve.take(h.d, (size_t)(h.crows ? h.crows : 1) * h.cw);
-                        carve.take(h.d8, (size_t)(h.crows ? h.crows : 1) * h.cw);
-                        // device-side decode of a band's input window (own rows + halo rows, rounded out to whole
-                        // block rows) normally borrows the two x buffers as scratch; a band of only a few rows is
-                        // smaller than that window, and gets scratch of its own
-                        if(!planes[c].fdata) {
-                                const size_t cells = (size_t)((h.frow0 + h.frows + 7) / 8 - h.frow0 / 8) * 8 * h.cw;
-                                if(cells > plane_floats) {
-                                        carve.take(h.scratch_f, cells);
-                                        carve.take(h.scratch_d, cells);
-                                }
-                        }
-                }
-                carve.take(q_all, 64 * kMaxCh);
-                carve.take(s->part_g2, ntiles * nchannel);
-                carve.take(s->rowsum_local, (size_t)s->ntr_local * nchannel);
-                if(whole) {
-                        s->rowsum_all = s->rowsum_local;
-                } else {
-                        carve.take(s->rowsum_all, (size_t)s->ntr_global * nchannel);
-                        carve.take(s->rowsum_all_odd, (size_t)s->ntr_global * nchannel);
-                        carve.take(s->push_dev, 2);
-                        carve.take(s->rowsum_odd, (size_t)s->ntr_local * nchannel);
-                }
-                carve.take(s->norm, kMaxCh);
-                carve.take(s->tickets, (size_t)s->ntr_local + 1);
-                carve.take(s->dbg_counters, 3);
-                carve.take(s->d_maxabs, kMaxCh);
-                carve.take(s->part_tv, ntiles * 2);
-                carve.take(s->part_prob, (size_t)max_strips * nchannel);
-        }
-
-        // ---- nt_policy (see nt_policy() above): this solver's bytes join the device's live total ----
-        {
-                for(unsigned c = 0; c < nchannel; c++) {
-                        const ChanHost &h = s->ch[c];
-                        const size_t cells = (size_t)(h.crows ? h.crows : 1) * h.cw;
-                        s->live_ws += (2 * plane_floats + (size_t)s->rows * W + cells) * sizeof(float) + cells * sizeof(int16_t);
-                        s->live_planes += 2 * plane_floats * sizeof(float);
-                        s->live_d += cells * sizeof(int16_t);
-                }
-                s->live_g = (size_t)nchannel * s->rows * W * sizeof(float);
-                live_add(device, LiveBytes{s->live_ws, s->live_g, s->live_planes, s->live_d}, +1);
-                s->live_registered = true;
-                s->nt = nt_policy(s);
-                // canvases whose planes x_k, x_{k-1} do not both fit the Infinity Cache: the gradient phase walks bottom-up
-                // (k_project walks top-down), so that each phase starts on the rows the one before touched last (Geo::reverse).
-                // Schedule only: the bits do not depend on who marches a row when.
-                s->grad_reverse = s->live_planes > kNtWorkingSet;
-                if(const char *env = j2p_exp_env("J2P_GRAD_REVERSE")) { s->grad_reverse = atoi(env) != 0; }
-        }
-
-        // ---- uploads (host arrays: whole-image unless band_local) ----
         float qf[64 * kMaxCh];
-        for(unsigned c = 0; c < nchannel; c++) {
-                s->ch[c].q = q_all + 64 * c;
-                for(int j = 0; j < 64; j++) { qf[64 * c + j] = (float)planes[c].quant_table[j]; }
+        rc = place(s, planes, pweight, band_local_arrays);
+        if(rc == J2P_OK) { rc = carve_arena(s, planes); }
+        if(rc == J2P_OK) {
+                register_live_bytes(s);
+                rc = upload_tables(s, planes, qf);
         }
-        CREATE_TRY(hipMemcpyAsync(q_all, qf, sizeof(float) * 64 * nchannel, hipMemcpyHostToDevice, s->stream));
-        CREATE_TRY(hipMemsetAsync(s->tickets, 0, ((size_t)s->ntr_local + 1) * sizeof(unsigned), s->stream));
-        CREATE_TRY(hipMemsetAsync(s->part_prob, 0, (size_t)max_strips * nchannel * sizeof(double), s->stream));
-        CREATE_TRY(hipMemsetAsync(s->dbg_counters, 0, 3 * sizeof(unsigned long long), s->stream));
-        CREATE_TRY(hipMemsetAsync(s->d_maxabs, 0, kMaxCh * sizeof(unsigned), s->stream));
-        for(unsigned c = 0; c < nchannel; c++) {
-                const j2p_plane &p = planes[c];
-                ChanHost &h = s->ch[c];
-                const size_t host_row0 = s->band_local ? h.crow0 : 0;
-                if(h.crows) {
-                        // block-major: coefficient row r lives in block row r/8; rows are block aligned
-                        const int16_t *src = p.data + (size_t)(h.crow0 - host_row0) * h.cw;
-                        CREATE_TRY(hipMemcpyAsync(h.d, src, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
-                        // ... and once more as bytes, with the largest |d| (decided behind the synchronisation below)
-                        const size_t cells = (size_t)h.crows * h.cw;
-                        const unsigned blocks = (unsigned)((cells / 8 + 255) / 256);
-                        hipLaunchKernelGGL(k_narrow_coefficients, dim3(blocks < 2048 ? (blocks ? blocks : 1) : 2048), dim3(256), 0, s->stream,
-                                           (const int16_t *)h.d, h.d8, cells, s->d_maxabs + c);
-                }
-                if(p.fdata) {
-                        const float *src = p.fdata + (size_t)(h.frow0 - host_row0) * h.cw;
-                        CREATE_TRY(hipMemcpyAsync(h.decoded, src, (size_t)h.frows * h.cw * sizeof(float), hipMemcpyHostToDevice, s->stream));
-                } else {
-                        // decode on the device (jpeg.c:83-92 + box.c:5-19): whole block rows [b0, b1) of the input
-                        // window.  Band rows are block aligned, so when the window has no halo rows (band_local, or
-                        // a whole canvas) the blocks are already in h.d; otherwise the coefficients of the
-                        // window go up once more into the (not yet initialised) gradient plane as scratch.
-                        const unsigned b0 = h.frow0 / 8, b1 = (h.frow0 + h.frows + 7) / 8;
-                        const unsigned nb_rows = b1 - b0;
-                        const unsigned groups = ((h.cw / 8 + 7) / 8) * nb_rows;
-                        const int16_t *dsrc = nullptr;
-                        if(h.crows && b0 * 8 >= h.crow0 && b1 * 8 <= h.crow0 + h.crows) {
-                                dsrc = h.d + (size_t)(b0 * 8 - h.crow0) * h.cw;
-                        } else {
-                                // scratch: the first x buffer holds (rows + 4) * W floats >= the window's int16 data
-                                if(!h.scratch_d && (size_t)nb_rows * 8 * h.cw * sizeof(int16_t) > plane_floats * sizeof(float)) {
-                                        rc = j2p_fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
-                                        j2p_solver_destroy(s);
-                                        return rc;
-                                }
-                                int16_t *dtmp = h.scratch_d ? h.scratch_d : reinterpret_cast<int16_t *>(h.xbuf[0]);
-                                const int16_t *src = p.data + (size_t)(b0 * 8 - host_row0) * h.cw;
-                                CREATE_TRY(hipMemcpyAsync(dtmp, src, (size_t)nb_rows * 8 * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
-                                dsrc = dtmp;
-                        }
-                        if(h.frow0 == b0 * 8 && h.frows == nb_rows * 8) {
-                                hipLaunchKernelGGL(k_decode, dim3((groups + 3) / 4), dim3(256), 0, s->stream, dsrc,
-                                                   (const float *)h.q, h.decoded, h.cw, nb_rows);
-                        } else {
-                                // window not block aligned (halo rows of a band): decode into the second x buffer, copy the rows
-                                if(!h.scratch_f && (size_t)nb_rows * 8 * h.cw > plane_floats) {
-                                        rc = j2p_fail(J2P_EINVAL, "channel %u: decode window does not fit the scratch plane", c);
-                                        j2p_solver_destroy(s);
-                                        return rc;
-                                }
-                                float *ftmp = h.scratch_f ? h.scratch_f : h.xbuf[1];
-                                hipLaunchKernelGGL(k_decode, dim3((groups + 3) / 4), dim3(256), 0, s->stream, dsrc,
-                                                   (const float *)h.q, ftmp, h.cw, nb_rows);
-                                CREATE_TRY(hipMemcpyAsync(h.decoded, ftmp + (size_t)(h.frow0 - b0 * 8) * h.cw,
-                                                          (size_t)h.frows * h.cw * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-                        }
-                        CREATE_TRY(hipGetLastError());
-                }
-        }
-        // (the largest |d| per channel comes back on the solver's own stream: a synchronous copy would wait for every
-        // blocking stream of the device)
-        unsigned maxabs[kMaxCh] = {0};
-        CREATE_TRY(hipMemcpyAsync(maxabs, s->d_maxabs, sizeof(maxabs), hipMemcpyDeviceToHost, s->stream));
-        // the host arrays (and the stack tables above) may go away as soon as this returns
-        CREATE_TRY(hipStreamSynchronize(s->stream));
-        {
-                // one byte per coefficient where the channel's values allow it: the projection then reads d8 (ChanDev::d8)
-                const char *env = j2p_exp_env("J2P_NARROW_COEFFICIENTS");
-                for(unsigned c = 0; c < nchannel; c++) {
-                        ChanHost &h = s->ch[c];
-                        h.narrow_fits = h.crows != 0 && maxabs[c] <= 127;
-                        h.narrow = h.narrow_fits && !(env && atoi(env) == 0);
-                }
-                account_coefficient_bytes(s);
-        }
-        {
-                // the wide-footprint projection path for the footprints it has (J2P_OPT_WIDE_FOOTPRINT)
-                const char *env = j2p_exp_env("J2P_WIDE_FOOTPRINT");
-                s->wide_footprint = !(env && atoi(env) == 0);
-                set_wide_footprint(s);
-        }
-#undef CREATE_TRY
-        rc = launch_init(s);
-        if(rc != J2P_OK) { j2p_solver_destroy(s); return rc; }
-        *out = s;
+        for(unsigned c = 0; rc == J2P_OK && c < nchannel; c++) { rc = upload_channel(s, c, planes[c]); }
+        if(rc == J2P_OK) { rc = decide_narrow_and_wide(s); }
+        if(rc == J2P_OK) { rc = launch_init(s); }
+        if(rc != J2P_OK) { return rc; }
+        *out = owner.release();
         return J2P_OK;
 }
 
@@ -1353,7 +1203,7 @@ int j2p_solver_trace(j2p_solver *s, int on, unsigned long long *host_out, unsign
         constexpr unsigned kCap = 1u << 19;                     // records (16 MiB)
         HIP_TRY(hipStreamSynchronize(s->stream));
         if(!s->trace) {
-                HIP_TRY(dev_malloc((void **)&s->trace, (size_t)kCap * 32));
+                HIP_TRY(j2p_dev_malloc((void **)&s->trace, (size_t)kCap * 32));
                 HIP_TRY(hipMemset(s->trace, 0, (size_t)kCap * 32));
                 s->trace_cap = kCap;
         }
@@ -1611,7 +1461,7 @@ int j2p_solver_set_logging(j2p_solver *s, int on)
         // depends on it)
         if(s->grad_done || s->interior_done) { return j2p_fail(J2P_ESTATE, "logging changes between iterations only"); }
         if(on && !s->log_band) {
-                HIP_TRY(dev_malloc((void **)&s->log_band, (2 + kMaxCh) * sizeof(double)));
+                HIP_TRY(j2p_dev_malloc((void **)&s->log_band, (2 + kMaxCh) * sizeof(double)));
                 HIP_TRY(hipMemsetAsync(s->log_band, 0, (2 + kMaxCh) * sizeof(double), s->stream));
         }
         s->log_phases = on != 0;
@@ -1630,7 +1480,7 @@ int j2p_solver_run(j2p_solver *s, unsigned n, j2p_log_row *rows)
                 (void)hipFree(s->logsums);
                 s->logsums = nullptr;
                 s->logsums_cap = 0;
-                HIP_TRY(dev_malloc((void **)&s->logsums, (size_t)n * kRow * sizeof(double)));
+                HIP_TRY(j2p_dev_malloc((void **)&s->logsums, (size_t)n * kRow * sizeof(double)));
                 s->logsums_cap = n;
         }
         for(unsigned i = 0; i < n; i++) {
@@ -2001,9 +1851,9 @@ int j2p_decode_plane(int device, unsigned w, unsigned h, const int16_t *data, co
         float qf[64];
         for(int j = 0; j < 64; j++) { qf[j] = (float)quant_table[j]; }
         int rc = J2P_OK;
-        hipError_t e = dev_malloc((void **)&dd, n * sizeof(int16_t));
-        if(e == hipSuccess) { e = dev_malloc((void **)&df, n * sizeof(float)); }
-        if(e == hipSuccess) { e = dev_malloc((void **)&dq, sizeof(qf)); }
+        hipError_t e = j2p_dev_malloc((void **)&dd, n * sizeof(int16_t));
+        if(e == hipSuccess) { e = j2p_dev_malloc((void **)&df, n * sizeof(float)); }
+        if(e == hipSuccess) { e = j2p_dev_malloc((void **)&dq, sizeof(qf)); }
         if(e == hipSuccess) { e = hipMemcpy(dd, data, n * sizeof(int16_t), hipMemcpyHostToDevice); }
         if(e == hipSuccess) { e = hipMemcpy(dq, qf, sizeof(qf), hipMemcpyHostToDevice); }
         if(e == hipSuccess) {
@@ -2030,7 +1880,7 @@ int j2p_dct8x8_blocks(int device, float *blocks, size_t n, int inverse)
         if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         float *db = nullptr;
         int rc = J2P_OK;
-        hipError_t e = dev_malloc((void **)&db, n * 64 * sizeof(float));
+        hipError_t e = j2p_dev_malloc((void **)&db, n * 64 * sizeof(float));
         if(e == hipSuccess) { e = hipMemcpy(db, blocks, n * 64 * sizeof(float), hipMemcpyHostToDevice); }
         if(e == hipSuccess) {
                 hipLaunchKernelGGL(k_dct_blocks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, nullptr, db, n, inverse);
@@ -2182,7 +2032,7 @@ int j2p_division_exhaustive(int device, int pass, unsigned first, unsigned count
         DeviceGuard guard(device);
         if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
         unsigned long long *dm = nullptr, hm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(dev_malloc((void **)&dm, sizeof(hm)));
+        HIP_TRY(j2p_dev_malloc((void **)&dm, sizeof(hm)));
         hipError_t e = hipMemset(dm, 0, sizeof(hm));
         if(e == hipSuccess) {
                 if(pass == 1) { hipLaunchKernelGGL(k_recip_exhaustive, dim3(8192), dim3(256), 0, nullptr, dm); }

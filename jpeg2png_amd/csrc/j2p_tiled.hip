@@ -49,6 +49,7 @@
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
+#include "j2p_geometry.h"
 
 namespace {
 
@@ -475,8 +476,6 @@ void band_main(j2p_tiled *t, unsigned b)
         }
 }
 
-unsigned gcd_u(unsigned a, unsigned b) { return b ? gcd_u(b, a % b) : a; }
-
 // can every band's GPU write every other band's memory?  (same device: yes)
 bool peers_reachable(unsigned nband, const int devices[], char *why, size_t why_len)
 {
@@ -620,14 +619,13 @@ int tiled_create_impl(j2p_tiled **out, unsigned nband, const int devices[], cons
         *out = nullptr;
         if(nband == 0 || nband > 32) { return j2p_fail(J2P_EINVAL, "1..32 bands, got %u", nband); }
         if(nchannel == 0 || nchannel > J2P_MAX_CHANNELS) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118)"); }
-        unsigned W = 0, H = 0, align = J2P_TILE_ROWS;
+        j2p_canvas cv = J2P_CANVAS_NONE;
         for(unsigned c = 0; c < nchannel; c++) {
                 const j2p_plane &p = planes[c];
                 if(p.w_samp == 0 || p.h_samp == 0 || p.w == 0 || p.h == 0) { return j2p_fail(J2P_EINVAL, "channel %u: empty plane", c); }
-                if(p.w * p.w_samp > W) { W = p.w * p.w_samp; }
-                if(p.h * p.h_samp > H) { H = p.h * p.h_samp; }
-                align = align / gcd_u(align, 8 * p.h_samp) * (8 * p.h_samp);
+                j2p_canvas_add(&cv, p.w, p.h, p.w_samp, p.h_samp);
         }
+        const unsigned W = cv.W, H = cv.H, align = cv.align;
         // band boundaries: the caller's, or near-equal multiples of the alignment
         std::vector<unsigned> edge(nband + 1);
         if(cuts) {
@@ -635,11 +633,8 @@ int tiled_create_impl(j2p_tiled **out, unsigned nband, const int devices[], cons
                 if(edge[0] != 0 || edge[nband] != H) { return j2p_fail(J2P_EINVAL, "cuts must run from 0 to the canvas height %u", H); }
         } else {
                 const unsigned units = (H + align - 1) / align;
-                if(units < nband) { return j2p_fail(J2P_EINVAL, "a canvas of %u rows has only %u bands of %u rows for %u devices", H, units, align, nband); }
-                unsigned start = 0;
-                for(unsigned b = 0; b < nband; b++) {
-                        edge[b] = start * align;
-                        start += units / nband + (b < units % nband ? 1 : 0);
+                if(!j2p_near_equal_cuts(units, nband, align, edge.data())) {
+                        return j2p_fail(J2P_EINVAL, "a canvas of %u rows has only %u bands of %u rows for %u devices", H, units, align, nband);
                 }
                 edge[nband] = H;
         }
@@ -972,23 +967,21 @@ int measure_plan(unsigned nband, const int devices[], unsigned nchannel, const j
 {
         *decided = 0;
         // ---- the scratch canvas: the job's first rows, three tile rows per band ----
-        unsigned align = J2P_TILE_ROWS, H = 0;
+        j2p_canvas cv = J2P_CANVAS_NONE;
         for(unsigned c = 0; c < nchannel; c++) {
                 const j2p_plane &p = planes[c];
                 if(p.w_samp == 0 || p.h_samp == 0 || p.w == 0 || p.h == 0) { return J2P_OK; }     // (the create proper reports it)
-                align = align / gcd_u(align, 8 * p.h_samp) * (8 * p.h_samp);
-                if(p.h * p.h_samp > H) { H = p.h * p.h_samp; }
+                j2p_canvas_add(&cv, p.w, p.h, p.w_samp, p.h_samp);
         }
-        const unsigned per_band = (3 * J2P_TILE_ROWS + align - 1) / align * align;
+        const unsigned per_band = j2p_min_band_rows(cv.align);
         const unsigned rows = per_band * nband;
-        if(H < rows) { return J2P_OK; }                       // a canvas this short is not worth the exercise: defaults
+        if(cv.H < rows) { return J2P_OK; }                     // a canvas this short is not worth the exercise: defaults
         j2p_plane scratch[J2P_MAX_CHANNELS];
-        unsigned W = 0;
+        const unsigned W = cv.W;                               // (the scratch planes keep their widths)
         for(unsigned c = 0; c < nchannel; c++) {
                 scratch[c] = planes[c];                        // data / fdata: the first rows ARE the arrays' prefixes
                 const unsigned h = rows / planes[c].h_samp;
                 if(scratch[c].h > h) { scratch[c].h = h; }
-                if(scratch[c].w * scratch[c].w_samp > W) { W = scratch[c].w * scratch[c].w_samp; }
         }
         unsigned Hs = 0;
         for(unsigned c = 0; c < nchannel; c++) { if(scratch[c].h * scratch[c].h_samp > Hs) { Hs = scratch[c].h * scratch[c].h_samp; } }

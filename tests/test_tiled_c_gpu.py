@@ -260,3 +260,23 @@ def test_rccl_exchange_with_one_band_as_its_own_neighbour(exp_lib, monkeypatch):
     np.testing.assert_allclose(rows, want_rows, rtol=1e-9, atol=1e-12)
     with pytest.raises(j.J2PError, match="one GPU per band"):
         j.TiledSolver(planes, 0.3, pws, 9, devices=[0, 0])
+
+
+def test_a_create_that_fails_halfway_leaves_the_device_usable(lib):
+    """a band solver refused after its stream has been made (band-local arrays of a canvas whose chroma covers only 16
+    of its 32 rows) hands back what it took: the same small solve gives the same bits before and after"""
+    import jpeg2png_amd as j
+    from jpeg2png_amd import synth
+    luma = synth.make_planes(16, 32, "444", 10, seed=12, y_only=True)[0]
+    chroma = synth.make_planes(16, 16, "420", 10, seed=12)[1:]
+    assert (luma.w, luma.h) == (16, 32) and all((p.w, p.h, p.w_samp, p.h_samp) == (8, 8, 2, 2) for p in chroma)
+    small = synth.make_planes(16, 16, "444", 10, seed=13, y_only=True)
+
+    def solve():
+        with j.Solver(small, 0.3, [0.001], 4) as s:
+            s.run(4)
+            return s.download(0)
+    before = solve()
+    with pytest.raises(j.J2PError, match="band-local arrays need every channel to cover the canvas height"):
+        j.Solver([luma] + chroma, 0.3, [0.001] * 3, 4, band=(0, 16), band_local_arrays=True)
+    assert bit_equal(solve(), before)
