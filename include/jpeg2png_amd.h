@@ -488,6 +488,49 @@ typedef struct j2p_resize {
 int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h,
                                  const j2p_resize *r, const j2p_tensor *out);
 
+/* Filtered tensor output: the same elements of the box, resampled to out_w x out_h with taps that come from a FILTER KERNEL
+ * — the formula of Pillow's resize and of torch's interpolate(antialias=True, align_corners=False) — where the area form
+ * takes them from overlap lengths.  One formula shrinks (the support widens with the ratio) and enlarges (the support stays
+ * at the filter's radius): out_w / out_h may be larger than the box.  Every bit is defined.
+ * Filters: J2P_FILTER_TRIANGLE, radius R = 1 ("bilinear"); J2P_FILTER_CUBIC, radius R = 2, Keys' cubic with a = -0.5
+ * ("bicubic").  Taps of output index X of one axis (box, out), every operation IEEE double and rounded on its own (nothing
+ * fused, no reciprocal), on host and device alike:
+ *     scale = (double)box / (double)out;   fs = scale > 1. ? scale : 1.;   sup = R * fs
+ *     c     = ((double)X + 0.5) * scale
+ *     first = max(0, (long)(c - sup + 0.5));   end = min(box, (long)(c + sup + 0.5))     (the casts truncate)
+ *     taps i = first .. end - 1 (always at least one):   u_i = (((double)i - c) + 0.5) / fs;   a = |u_i|
+ *     triangle: w_i = a < 1. ? 1. - a : 0.
+ *     cubic:    w_i = a < 1. ? ((1.5 * a - 2.5) * a) * a + 1.  :  a < 2. ? (((a - 5.) * a + 8.) * a - 4.) * -0.5  :  0.
+ *     S = 0.;  S = S + w_i for i ascending;   f_i = (float)(w_i / S)
+ * The window is clipped to the box and renormalised: image pixels outside the box are never used.  An axis with out == box
+ * has ONE tap, of weight 1.f, at i = X.  Then in f32, every operation rounded on its own, with the columns' weights fx and
+ * the rows' weights fy:
+ *     r_j = 0.f;  r_j = r_j + fx_i * v_k(box_x + i, box_y + j)            for i ascending
+ *     acc = 0.f;  acc = acc + fy_j * r_j                                   for j ascending
+ *     m = min(max(acc, 0.f), 255.f)
+ * (no division: the weights are normalised; both clamps are needed: the cubic has negative lobes, and rounding alone takes
+ * a triangle's sum beyond 255) and channel k's element is made of m as above.  out == box on both axes copies v_k, except
+ * that -0.f becomes +0.f.  Element (k, Y, X) goes to data + k * stride_c + Y * stride_y + X * stride_x; nothing else is written.
+ * Whole-canvas solvers only.  The checks of j2p_planes_to_tensor_resized, except that the output may be larger than the box,
+ * and J2P_EINVAL for an unknown filter and for out_w / out_h above J2P_RESAMPLE_MAX_OUT; a refused call writes nothing.
+ * ASYNCHRONOUS on planes[0].solver's stream: two kernels are queued (the taps of both axes into scratch memory that the
+ * solver keeps, then the sampling); no host synchronisation and, once that scratch has grown to the size, no allocation. */
+#define J2P_FILTER_TRIANGLE 1
+#define J2P_FILTER_CUBIC 2
+#define J2P_RESAMPLE_MAX_OUT 65536u
+typedef struct j2p_resample {
+        unsigned box_x, box_y, box_w, box_h;   /* source rectangle, image pixels */
+        unsigned out_w, out_h;                  /* 1 .. J2P_RESAMPLE_MAX_OUT each; smaller or larger than the box */
+        int filter;                             /* J2P_FILTER_* */
+} j2p_resample;
+int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h,
+                                   const j2p_resample *r, const j2p_tensor *out);
+/* Test hook (no device needed): the taps of output index X of an axis as above, computed by the host with the code the
+ * device runs: *first, *count and weights[0 .. *count).  J2P_EINVAL for an unknown filter, box or out 0, X >= out, or more
+ * taps than `capacity` (then *count is still set). */
+int j2p_debug_filter_taps(int filter, unsigned box, unsigned out, unsigned X, unsigned *first, unsigned *count, float *weights,
+                          unsigned capacity);
+
 /* JPEG output: ONE (solver, channel) pair's current iterate as quantised DCT coefficients, ready for libjpeg's
  * jpeg_write_coefficients — no RGB conversion and no 8-bit samples in between.  For each 8x8 block of the canvas plane:
  * dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes), every coefficient divided by quant_table[j] as
@@ -597,6 +640,9 @@ int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket);
  * required (J2P_EINVAL without), job->out_w x out_h stays the image's crop, which the box must lie inside, and the tensor has
  * r->out_w x r->out_h elements per channel.  Not with `tile`, as every tensor job.  r == NULL: j2p_batch_submit. */
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket);
+/* the same with a filter (j2p_planes_to_tensor_resampled): the tensor may be larger than the box.  *r is copied and travels next
+ * to the job, never in it; validated here, at submit.  r == NULL: j2p_batch_submit. */
+int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket);
 int j2p_batch_wait(j2p_batch *b, int ticket);               /* the job's status; its error text in j2p_last_error() */
 
 /* test hook: n > 0: the n-th j2p_solver_run() / j2p_tiled_run() call from now on (any thread) fails with J2P_EDEVICE

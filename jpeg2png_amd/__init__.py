@@ -61,6 +61,12 @@ class _CResize(ctypes.Structure):
                 ("out_w", ctypes.c_uint), ("out_h", ctypes.c_uint)]
 
 
+class _CResample(ctypes.Structure):
+    """j2p_resample: a source rectangle of the image, the size it is resampled to (smaller or larger) and the filter"""
+    _fields_ = [("box_x", ctypes.c_uint), ("box_y", ctypes.c_uint), ("box_w", ctypes.c_uint), ("box_h", ctypes.c_uint),
+                ("out_w", ctypes.c_uint), ("out_h", ctypes.c_uint), ("filter", ctypes.c_int)]
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -101,6 +107,7 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_coefficients_sub", "j2p_planes_rows_to_coefficients_sub",
     "j2p_planes_to_tensor", "j2p_planes_rows_to_tensor", "j2p_debug_tensor_path", "j2p_debug_job_layout",
     "j2p_planes_to_tensor_resized", "j2p_batch_submit_resized",
+    "j2p_planes_to_tensor_resampled", "j2p_batch_submit_resampled", "j2p_debug_filter_taps",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -268,6 +275,11 @@ def _bind(path):
     lib.j2p_planes_to_tensor_resized.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResize),
                                                  ctypes.POINTER(_CTensor)]
     lib.j2p_batch_submit_resized.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CResize), ctypes.POINTER(ctypes.c_int)]
+    lib.j2p_planes_to_tensor_resampled.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResample),
+                                                   ctypes.POINTER(_CTensor)]
+    lib.j2p_batch_submit_resampled.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CResample), ctypes.POINTER(ctypes.c_int)]
+    lib.j2p_debug_filter_taps.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint),
+                                          ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_float), ctypes.c_uint]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -468,6 +480,41 @@ def _c_resize(width, height, out_width, out_height, box):
     return _CResize(bx, by, bw, bh, ow, oh)
 
 
+# filter= of Solver.to_tensor and Batch.submit: None and "area" are the area form (j2p_resize), the others J2P_FILTER_*
+FILTERS = {"triangle": 1, "cubic": 2}
+J2P_RESAMPLE_MAX_OUT = 65536
+
+
+def _filter_code(filter):
+    """None for the area form (filter None or "area"), otherwise the J2P_FILTER_* code"""
+    if filter is None or filter == "area":
+        return None
+    if filter not in FILTERS:
+        raise J2PError(f"resize: unknown filter {filter!r} (\"area\", \"triangle\" or \"cubic\")")
+    return FILTERS[filter]
+
+
+def _c_resample(width, height, out_width, out_height, box, code):
+    """the j2p_resample of the same keywords with filter="triangle" / "cubic": as _c_resize, but the output may be larger than
+    the box (up to J2P_RESAMPLE_MAX_OUT a side).  Refuses what the library refuses (j2p_resample_error)."""
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("tensor output needs width and height")
+    try:
+        bx, by, bw, bh = (0, 0, int(width), int(height)) if box is None else (int(v) for v in box)
+    except (TypeError, ValueError):
+        raise J2PError("resize: box must be (x, y, width, height)") from None
+    if bw < 1 or bh < 1:
+        raise J2PError("resize: empty box")
+    if bx < 0 or by < 0 or bx + bw > int(width) or by + bh > int(height):
+        raise J2PError(f"resize: the box {(bx, by, bw, bh)} leaves the {int(width)} x {int(height)} image")
+    ow, oh = bw if out_width is None else int(out_width), bh if out_height is None else int(out_height)
+    if ow < 1 or oh < 1:
+        raise J2PError("resize: empty output")
+    if ow > J2P_RESAMPLE_MAX_OUT or oh > J2P_RESAMPLE_MAX_OUT:
+        raise J2PError(f"resize: the output {ow} x {oh} is larger than {J2P_RESAMPLE_MAX_OUT} a side")
+    return _CResample(bx, by, bw, bh, ow, oh, code)
+
+
 def _sampling(subsampling):
     """(sx, sy) of a coefficient output: 1 or 2 each"""
     try:
@@ -631,7 +678,7 @@ class Solver:
         return p.value or 0
 
     def to_tensor(self, width, height, dtype=None, layout="chw", scale=None, bias=None, out=None, out_width=None, out_height=None,
-                  box=None):
+                  box=None, filter=None):
         """The solved image, cropped to width x height, as an RGB (three-channel solver) or greyscale (one-channel solver)
         torch.Tensor on the solver's GPU — (3|1, height, width) for layout "chw", (height, width, 3|1) for "hwc" — without
         leaving the device (j2p_planes_rows_to_tensor): png.c's colour conversion and clamp to [0, 255], then per channel
@@ -643,10 +690,16 @@ class Solver:
         area-resampled to out_width x out_height (default: the box's size, a pure crop; never larger than the box), is what
         the tensor receives (j2p_planes_to_tensor_resized) — its shape is then (3|1, out_height, out_width) or the "hwc"
         form.  Whole-canvas solvers only.  Without any of the three the call is what it was.
+        filter: None or "area" — that area form; "triangle" or "cubic" — the antialiased triangle / cubic filter of
+        torchvision's Resize, F.interpolate(antialias=True) and Pillow (j2p_planes_to_tensor_resampled), with which
+        out_width / out_height may also be LARGER than the box.
         Nothing waits on the host: the kernel is queued on the solver's stream and torch's current stream is made to wait
         for it, so torch operations issued afterwards see the finished tensor."""
         resize = None
-        if out_width is not None or out_height is not None or box is not None:
+        code = _filter_code(filter)
+        if code is not None:
+            resize = _c_resample(width, height, out_width, out_height, box, code)
+        elif out_width is not None or out_height is not None or box is not None:
             resize = _c_resize(width, height, out_width, out_height, box)
         torch = _torch()
         if self.nch not in (1, 3):
@@ -669,7 +722,9 @@ class Solver:
         ours = torch.cuda.ExternalStream(self.stream(), device=dev)
         theirs = torch.cuda.current_stream(dev)
         ours.wait_stream(theirs)            # whatever torch still does with `out` (its allocation, a fill) comes first
-        if resize is not None:
+        if code is not None:
+            _check(self._lib.j2p_planes_to_tensor_resampled(refs, self.nch, int(image_width), int(image_height), ctypes.byref(resize), ctypes.byref(ct)))
+        elif resize is not None:
             _check(self._lib.j2p_planes_to_tensor_resized(refs, self.nch, int(image_width), int(image_height), ctypes.byref(resize), ctypes.byref(ct)))
         else:
             _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
@@ -864,7 +919,7 @@ class Batch:
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
-               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None):
+               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None):
         """tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
         GPU as that tensor's elements — shape (3|1, height, width) for layout "chw" or (height, width, 3|1) for "hwc", dtype
         uint8 / float16 / bfloat16 / float32, any view, with per-channel scale and bias as in Solver.to_tensor — by a worker
@@ -873,6 +928,8 @@ class Batch:
         out_width, out_height, box=(x, y, w, h) (with tensor= only): the tensor receives the rectangle `box` of the width x height
         image (default: all of it) area-resampled to out_width x out_height (default: the box's size), as in Solver.to_tensor;
         its shape is (3|1, out_height, out_width) or the "hwc" form, while width and height stay the image's;
+        filter (with tensor= only): None or "area" — that; "triangle" or "cubic" — the antialiased filter instead, which also
+        enlarges (an image smaller than its slot), as in Solver.to_tensor;
         quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
         quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
         writer entropy-codes — instead of the float planes;
@@ -883,7 +940,12 @@ class Batch:
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
         n = len(planes)
         resize = None
-        if out_width is not None or out_height is not None or box is not None:
+        code = _filter_code(filter)
+        if code is not None:
+            if tensor is None:
+                raise J2PError("job: filter belongs to tensor output (tensor=)")
+            resize = _c_resample(width, height, out_width, out_height, box, code)
+        elif out_width is not None or out_height is not None or box is not None:
             if tensor is None:
                 raise J2PError("job: out_width, out_height and box belong to tensor output (tensor=)")
             resize = _c_resize(width, height, out_width, out_height, box)
@@ -982,7 +1044,9 @@ class Batch:
             job.on_progress = cb
             keep = (keep, cb)                       # the trampoline lives as long as the job
         t = ctypes.c_int()
-        if resize is not None:
+        if code is not None:
+            _check(self._lib.j2p_batch_submit_resampled(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
+        elif resize is not None:
             _check(self._lib.j2p_batch_submit_resized(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
         else:
             _check(self._lib.j2p_batch_submit(self._h, ctypes.byref(job), ctypes.byref(t)))

@@ -33,6 +33,8 @@ struct Job {
         j2p_job desc;
         j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
         bool resized = false;
+        j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resampled: ... resampled with a filter
+        bool resampled = false;
         int ticket = 0;
         int device = -1;                    // tensor output: the tensor's device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -154,8 +156,8 @@ struct Engines {
 // Chunked when the caller watches (j2p_next_chunk), so that its bar and CSV keep moving.  `overlap`: the chunk of every
 // solve is issued before any of them is settled (sync, progress, done) — how the three solves of `-s` overlap on one GPU,
 // unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
-// resize (tensor jobs on one GPU only): the tensor receives the image resized.
-int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize)
+// resize / resample (tensor jobs on one GPU only, at most one of the two): the tensor receives the image resized.
+int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize, const j2p_resample *resample)
 {
         const unsigned nsolve = solves(d);
         if(!d.on_rows && !d.on_progress) {
@@ -213,6 +215,11 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p
                         if(resize) {
                                 // (never row-tiled: this one band is the whole canvas)
                                 JOB_TRY(j2p_planes_to_tensor_resized(ref, d.nchannel, d.out_w, d.out_h, resize, &d.out_tensor));
+                                JOB_TRY(j2p_solver_sync(ref[0].solver));
+                                continue;
+                        }
+                        if(resample) {
+                                JOB_TRY(j2p_planes_to_tensor_resampled(ref, d.nchannel, d.out_w, d.out_h, resample, &d.out_tensor));
                                 JOB_TRY(j2p_solver_sync(ref[0].solver));
                                 continue;
                         }
@@ -286,10 +293,10 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        return solve_and_deliver(d, eng.e, false, nullptr);
+        return solve_and_deliver(d, eng.e, false, nullptr, nullptr);
 }
 
-int run_job(const j2p_job &d, int device, const j2p_resize *resize)
+int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
@@ -297,7 +304,7 @@ int run_job(const j2p_job &d, int device, const j2p_resize *resize)
                 JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k], &d.pweight[k],
                                           d.iterations[k], whole, 0));
         }
-        return solve_and_deliver(d, eng.e, true, resize);
+        return solve_and_deliver(d, eng.e, true, resize, resample);
 }
 
 void worker_main(j2p_batch *b, int device)
@@ -335,7 +342,7 @@ void worker_main(j2p_batch *b, int device)
                 }
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
-                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr);
+                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -348,10 +355,14 @@ void worker_main(j2p_batch *b, int device)
         }
 }
 
-// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized
-int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
+// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled (never both)
+int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, int *ticket)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(f) {
+                if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resampled job needs tensor output (out_tensor)"); }
+                if(const char *why = j2p_resample_error(f, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+        }
         if(r) {
                 if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resized job needs tensor output (out_tensor)"); }
                 if(const char *why = j2p_resize_error(r, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
@@ -362,6 +373,10 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
         if(r) {
                 j->resize = *r;
                 j->resized = true;
+        }
+        if(f) {
+                j->resample = *f;
+                j->resampled = true;
         }
         if(job->out_tensor.data) {
                 // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor
@@ -434,12 +449,17 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        return submit(b, job, nullptr, ticket);
+        return submit(b, job, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
 {
-        return submit(b, job, r, ticket);
+        return submit(b, job, r, nullptr, ticket);
+}
+
+int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket)
+{
+        return submit(b, job, nullptr, r, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

@@ -32,6 +32,18 @@ static inline const char *j2p_resize_error(const j2p_resize *r, unsigned w, unsi
         return NULL;
 }
 
+// the same for a j2p_resample (j2p_planes_to_tensor_resampled, j2p_batch_submit_resampled): the output may be larger than the box
+static inline const char *j2p_resample_error(const j2p_resample *r, unsigned w, unsigned h)
+{
+        if(!r) { return "resample is NULL"; }
+        if(r->filter != J2P_FILTER_TRIANGLE && r->filter != J2P_FILTER_CUBIC) { return "resample: unknown filter"; }
+        if(r->box_w == 0 || r->box_h == 0) { return "resample: empty box"; }
+        if(r->box_x >= w || r->box_w > w - r->box_x || r->box_y >= h || r->box_h > h - r->box_y) { return "resample: the box leaves the image"; }
+        if(r->out_w == 0 || r->out_h == 0) { return "resample: empty output"; }
+        if(r->out_w > J2P_RESAMPLE_MAX_OUT || r->out_h > J2P_RESAMPLE_MAX_OUT) { return "resample: the output is larger than 65536"; }
+        return NULL;
+}
+
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
 // the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the
@@ -98,6 +110,11 @@ j2p_solver_view j2p_solver_view_of(const j2p_solver *s);         // s is not NUL
 // the device address of canvas row y (one of the solver's own) of channel c in the current iterate; the rows after it follow
 // at a stride of W floats.  Hides the halo as j2p_solver_plane_ptr does.
 int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **row);
+// at least `bytes` bytes of device memory that belong to the solver until it is destroyed, for what the output stage queues on
+// the solver's stream: taken from the pool once and grown on demand (growing waits for the stream, since what is queued may
+// still read the old block; a call that fits allocates nothing and waits for nothing).  One block: every call returns the same
+// memory, and stream order is what makes the next call's writes safe.
+int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out);
 
 // ---- j2p_pool.hip ----
 // the device-memory pool, for a solver's arena and for buffers that live as long as one call: at least `bytes` bytes on

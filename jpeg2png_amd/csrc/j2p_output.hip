@@ -1,9 +1,11 @@
 // jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
-// or cropped and area-resized, and to quantised JPEG coefficients (include/jpeg2png_amd.h: the j2p_planes_* functions).
+// or cropped and resized (area, or triangle / cubic taps), and to quantised JPEG coefficients (include/jpeg2png_amd.h: the
+// j2p_planes_* functions).
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
-// (j2p_internal.h), never the solver's struct, its halo or its arena.
+// (j2p_internal.h), never the solver's struct, its halo or its arena; j2p_solver_scratch lends it memory that lives with the
+// solver.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -305,6 +307,111 @@ int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, 
                            stride[1], ptr[2], stride[2], g, o);
         const hipError_t e = hipGetLastError();
         if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensor_resized: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+// ---- filtered tensor output: k_filter_taps, k_to_tensor_filtered ----
+static_assert(J2P_FILTER_TRIANGLE == kFilterTriangle && J2P_FILTER_CUBIC == kFilterCubic, "the kernels' filter codes are the header's");
+using FilteredKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterGeom, TensorOut);
+#define J2P_FILTERED_ROW(NPLANE) \
+        {k_to_tensor_filtered<NPLANE, kDtypeU8>, k_to_tensor_filtered<NPLANE, kDtypeF16>, k_to_tensor_filtered<NPLANE, kDtypeBF16>, k_to_tensor_filtered<NPLANE, kDtypeF32>}
+static const FilteredKernel kFilteredKernels[2][4] = {J2P_FILTERED_ROW(3), J2P_FILTERED_ROW(1)};          // [three planes / one][dtype]
+#undef J2P_FILTERED_ROW
+
+// Weights per output index in the scratch: ceil(2 * sup) + 2, with sup as filter_taps forms it.  A window has at most
+// trunc(c + sup + 0.5) - trunc(c - sup + 0.5) <= 2 * sup + 1 taps (plus what rounding c -+ sup adds: far below 1), so
+// ceil(2 * sup) + 1 hold every count and one more is spare.  An axis that is not resized has one tap.
+static unsigned filter_stride(int filter, unsigned box, unsigned out)
+{
+        if(out == box) { return 1; }
+        const double R = filter == kFilterCubic ? 2. : 1.;
+        const double scale = (double)box / (double)out;
+        const double sup = R * (scale > 1. ? scale : 1.);
+        const unsigned long long whole = (unsigned long long)(2. * sup);
+        return (unsigned)(whole + ((double)whole < 2. * sup ? 1 : 0) + 2);
+}
+
+int j2p_debug_filter_taps(int filter, unsigned box, unsigned out, unsigned X, unsigned *first, unsigned *count, float *weights,
+                          unsigned capacity)
+{
+        if(!first || !count || (!weights && capacity)) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(filter != J2P_FILTER_TRIANGLE && filter != J2P_FILTER_CUBIC) { return j2p_fail(J2P_EINVAL, "filter_taps: unknown filter %d", filter); }
+        if(box == 0 || out == 0 || X >= out) { return j2p_fail(J2P_EINVAL, "filter_taps: box %u, out %u, index %u", box, out, X); }
+        filter_taps(filter, box, out, X, first, count, capacity, [&](unsigned t, float f) { weights[t] = f; });
+        if(*count > capacity) { return j2p_fail(J2P_EINVAL, "filter_taps: %u taps, room for %u", *count, capacity); }
+        return J2P_OK;
+}
+
+// The tile of k_to_tensor_filtered: 256 columns x kFilterRows rows per wavefront where that still gives the chip (256 CUs x
+// 4 SIMDs) two wavefronts per SIMD.  Where it does not, columns go first, down to 64: a narrower tile converts 2R * fs more
+// source columns per tile, a few percent, while every output row a wavefront gives up makes it convert and walk the source
+// rows it shared with its neighbours (2R * fs of them) once more — (rows - 1 + 2R) / rows conversions per source row, 1.25
+// for the triangle at 4 rows and 2 at one.  Then rows, and last 32 columns, where half the lanes walk no taps (more
+// wavefronts still beat fuller ones there: j2p_output_kernels.hip.h).  Same bits for every tile.
+static void filter_tile(unsigned out_w, unsigned out_h, unsigned *lanes, unsigned *slots, unsigned *rows)
+{
+        unsigned tile = 64 * kResizeSlots, r = kFilterRows;
+        const auto few = [&] { return (unsigned long long)((out_w + tile - 1) / tile) * ((out_h + r - 1) / r) < 2048; };
+        while(tile > 64 && few()) { tile /= 2; }
+        while(r > 1 && few()) { r /= 2; }
+        if(few()) { tile = 32; }
+        *lanes = tile < 64 ? tile : 64;
+        *slots = tile / *lanes;
+        *rows = r;                              // (out_h <= 65536: the grid's y dimension is at most 16384)
+}
+
+int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_resample *r,
+                                   const j2p_tensor *out)
+{
+        if(!planes || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_resample_error(r, w, h)) { return j2p_fail(J2P_EINVAL, "to_tensor: %s", why); }
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o;
+        j2p_solver_view s0;
+        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(s0.device);
+        // the scratch: [first_x, count_x: out_w ints each][first_y, count_y: out_h][wx: out_w * stride_x floats][wy: out_h * stride_y]
+        FilterAxis ax, ay;
+        ax.box = r->box_w;
+        ax.out = r->out_w;
+        ax.stride = filter_stride(r->filter, r->box_w, r->out_w);
+        ay.box = r->box_h;
+        ay.out = r->out_h;
+        ay.stride = filter_stride(r->filter, r->box_h, r->out_h);
+        const size_t nwx = (size_t)ax.out * ax.stride, nwy = (size_t)ay.out * ay.stride;
+        const size_t words = 2 * ((size_t)ax.out + ay.out) + nwx + nwy;
+        void *scratch = nullptr;
+        if(const int rc = j2p_solver_scratch(planes[0].solver, words * 4, &scratch); rc != J2P_OK) { return rc; }
+        int *const ints = static_cast<int *>(scratch);
+        ax.first = ints;
+        ax.count = ints + ax.out;
+        ay.first = ints + 2 * (size_t)ax.out;
+        ay.count = ay.first + ay.out;
+        ax.weights = reinterpret_cast<float *>(ay.count + ay.out);
+        ay.weights = ax.weights + nwx;
+        const unsigned most = ax.out > ay.out ? ax.out : ay.out;
+        hipLaunchKernelGGL(k_filter_taps, dim3((most + 255) / 256, 2), dim3(256), 0, s0.stream, r->filter, ax, ay);
+        FilterGeom g;
+        g.box_x = r->box_x;
+        g.box_y = r->box_y;
+        g.out_w = r->out_w;
+        g.out_h = r->out_h;
+        g.stride_x = ax.stride;
+        g.stride_y = ay.stride;
+        g.first_x = ax.first;
+        g.count_x = ax.count;
+        g.first_y = ay.first;
+        g.count_y = ay.count;
+        g.wx = ax.weights;
+        g.wy = ay.weights;
+        filter_tile(r->out_w, r->out_h, &g.lanes, &g.slots, &g.rows);
+        // a workgroup: 4 wavefronts, one above the other, of one tile
+        const unsigned tile = g.lanes * g.slots, gx = (r->out_w + tile - 1) / tile, gy = ((r->out_h + g.rows - 1) / g.rows + 3) / 4;
+        hipLaunchKernelGGL(kFilteredKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(gx, gy), dim3(256), 0, s0.stream, ptr[0], stride[0], ptr[1],
+                           stride[1], ptr[2], stride[2], g, o);
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensor_resampled: %s", hipGetErrorString(e)); }
         return J2P_OK;
 }
 

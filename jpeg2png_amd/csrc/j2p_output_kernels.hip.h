@@ -1,5 +1,6 @@
 // jpeg2png_amd — gfx950 device code of the output stage: what turns solved planes into samples (k_to_samples), tensor
-// elements (k_to_tensor, k_to_tensor_resized) and quantised JPEG coefficients (k_quantise_blocks).  A device translation
+// elements (k_to_tensor, k_to_tensor_resized, k_filter_taps + k_to_tensor_filtered) and quantised JPEG coefficients
+// (k_quantise_blocks).  A device translation
 // unit of its own (j2p_output.hip), so that an edit here does not recompile the solver's kernels (j2p_kernels.hip.h), with
 // which it shares only j2p_dct.hip.h.  Compiled with the same flags: -ffp-contract=off, no fast-math, correctly rounded `/`.
 #pragma once
@@ -479,6 +480,279 @@ __global__ __launch_bounds__(256) void k_to_tensor_resized(const float *yp, unsi
 J2P_RESIZED_KERNELS(3)
 J2P_RESIZED_KERNELS(1)
 #undef J2P_RESIZED_KERNELS
+
+// ---------------------------------------------------------------------------
+// Filtered tensor output: the box resampled to out_w x out_h — smaller OR larger — with taps from a filter kernel (triangle,
+// Keys' cubic), the formula of Pillow and of torch's antialias path.  Every bit is defined (include/jpeg2png_amd.h).
+// TAPS: filter_taps below is the header's definition in IEEE double, one operation per line of it; host and device compile
+// the same text without contraction, so j2p_debug_filter_taps (host) and k_filter_taps (device) give the same bits.
+// k_filter_taps writes both axes' taps into scratch memory — one thread per output index: first[X], count[X] and the f32
+// weights at weights + X * stride, stride = ceil(2 * sup) + 2 >= any count (the host's filter_stride) — and
+// k_to_tensor_filtered only reads them: the filter is not its template parameter.
+// SAMPLING keeps k_to_tensor_resized's shape: a wavefront owns a tile of lanes x slots output columns (column X0 + p * lanes
+// + lane in slot p) and `rows` (1..kFilterRows) consecutive output rows; for every source row of those rows' windows, in
+// order, it stages the row segment its tile covers in chunks of kResizeChunk columns (16-byte loads aligned down to 4 floats,
+// converted ONCE, wave-private LDS, next chunk's loads in flight), every lane walks those taps of its columns that lie in the
+// chunk — chunks ascend, so r_j is summed in the defined order — and then every output row of the wavefront whose window
+// holds the source row takes acc = acc + fy * r_j: the rows ascend, so acc is summed in the defined order too.
+// ONE PASS: r_j is formed again by every wavefront whose rows use source row j, and never stored.  With `rows` output rows
+// per wavefront a source row is converted and walked (rows - 1 + 2R) / rows times when shrinking (triangle 1.25x at 4 rows,
+// 2x at one; cubic 1.75x and 4x) and about once per wavefront when enlarging, against a two-pass form's once — which would
+// pay an f32 intermediate of box_h x out_w x NPLANE floats written and read back (150 MB for 4096x3072 -> 4095x3071).
+// LDS: the padded index of the area kernel is kept.  At one tap step neighbouring lanes still read at a stride of box / out
+// floats when shrinking (their windows start that far apart), for which the pad was made; when enlarging they read the same
+// or the neighbouring word, which the LDS broadcasts.  What is new is that a lane's window is 2R * fs wide instead of
+// box / out + 1: neighbouring lanes' windows overlap, and a chunk boundary cuts more windows in two.
+// The weights are read from global memory, a lane its own run of floats (a tile's lanes x slots x count floats, read again
+// for every source row, stay in L1 / L2).  Tap-major, where the lanes of a wavefront read neighbouring floats at one tap
+// step, measured 7 to 11 % SLOWER where the tile was the same: the walk is bound by instructions, and
+// a lane's next weight is then a multiplication away instead of one float on.  A tile of 32 columns leaves lanes 32..63
+// without taps to walk; giving them the same columns of the next output row (half as many wavefronts, every lane busy) measured
+// 1.2 to 1.4 times SLOWER at 224x224: the walk waits for its loads, and more wavefronts hide that better than fuller ones.
+// ---------------------------------------------------------------------------
+constexpr int kFilterTriangle = 1, kFilterCubic = 2;             // J2P_FILTER_* (checked in j2p_output.hip)
+constexpr int kFilterRows = 4;                                   // output rows per wavefront, at most
+
+// w(a), a = |u|
+__host__ __device__ inline double filter_weight(int filter, double a)
+{
+        if(filter == kFilterTriangle) { return a < 1. ? 1. - a : 0.; }
+        if(a < 1.) { return ((1.5 * a - 2.5) * a) * a + 1.; }
+        if(a < 2.) { return (((a - 5.) * a + 8.) * a - 4.) * -0.5; }
+        return 0.;
+}
+
+// the taps of output index X of an axis (box, out): *first, *count, and put(t, f_t) for t < min(*count, capacity)
+template <typename Put>
+__host__ __device__ inline void filter_taps(int filter, unsigned box, unsigned out, unsigned X, unsigned *first, unsigned *count,
+                                            unsigned capacity, Put put)
+{
+        if(out == box) {                                                 // not resized: one tap of weight 1.f
+                *first = X;
+                *count = 1;
+                if(capacity >= 1) { put(0u, 1.f); }
+                return;
+        }
+        const double R = filter == kFilterCubic ? 2. : 1.;
+        const double scale = (double)box / (double)out;
+        const double fs = scale > 1. ? scale : 1.;
+        const double sup = R * fs;
+        const double c = ((double)X + 0.5) * scale;
+        long long lo = (long long)(c - sup + 0.5), hi = (long long)(c + sup + 0.5);
+        if(lo < 0) { lo = 0; }
+        if(hi > (long long)box) { hi = (long long)box; }
+        double S = 0.;
+        for(long long i = lo; i < hi; i++) {
+                const double u = (((double)i - c) + 0.5) / fs;
+                S = S + filter_weight(filter, __builtin_fabs(u));
+        }
+        *first = (unsigned)lo;
+        *count = (unsigned)(hi - lo);
+        for(long long i = lo; i < hi && (unsigned)(i - lo) < capacity; i++) {
+                const double u = (((double)i - c) + 0.5) / fs;
+                put((unsigned)(i - lo), (float)(filter_weight(filter, __builtin_fabs(u)) / S));
+        }
+}
+
+struct FilterAxis {
+        unsigned box, out, stride;      // stride: weights per output index (>= every count)
+        int *first, *count;             // [out]
+        float *weights;                 // [out * stride]
+};
+
+// blockIdx.y 0: the columns' taps, 1: the rows'
+__global__ __launch_bounds__(256) void k_filter_taps(int filter, FilterAxis ax, FilterAxis ay)
+{
+        const bool rows = blockIdx.y != 0;
+        const unsigned box = rows ? ay.box : ax.box, out = rows ? ay.out : ax.out, stride = rows ? ay.stride : ax.stride;
+        int *const firsts = rows ? ay.first : ax.first, *const counts = rows ? ay.count : ax.count;
+        const unsigned X = blockIdx.x * 256 + threadIdx.x;
+        if(X >= out) { return; }
+        float *const w = (rows ? ay.weights : ax.weights) + (size_t)X * stride;
+        unsigned first = 0, count = 0;
+        filter_taps(filter, box, out, X, &first, &count, stride, [&](unsigned t, float f) { w[t] = f; });
+        firsts[X] = (int)first;
+        counts[X] = (int)(count < stride ? count : stride);              // (never more: see filter_stride)
+}
+
+struct FilterGeom {
+        unsigned box_x, box_y;
+        unsigned out_w, out_h;
+        unsigned stride_x, stride_y;    // weights per output column / row
+        const int *first_x, *count_x, *first_y, *count_y;
+        const float *wx, *wy;
+        unsigned lanes, slots;          // the tile: lanes (a power of two, 32 or 64) x slots (1..kResizeSlots) columns
+        unsigned rows;                  // consecutive output rows per wavefront: 1..kFilterRows
+};
+
+template <int NPLANE, int DTYPE>
+__global__ __launch_bounds__(256) void k_to_tensor_filtered(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
+                                                            unsigned crs, FilterGeom g, TensorOut o)
+{
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
+        constexpr int kRounds = kResizeChunk / 256;
+        using E = TensorElement<DTYPE>;
+        using Raw = typename E::Raw;
+        __shared__ float stage[4][NPLANE][kResizeLds];
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned Yb = (blockIdx.y * 4 + (unsigned)wave) * g.rows;   // this wavefront's output rows: [Yb, Yb + nrow)
+        if(Yb >= g.out_h) { return; }                                    // (no workgroup barrier in this kernel)
+        const unsigned nrow = g.out_h - Yb < g.rows ? g.out_h - Yb : g.rows;
+        float (*const lds)[kResizeLds] = stage[wave];
+        const unsigned tile = g.lanes * g.slots;
+        const unsigned X0 = blockIdx.x * tile;                           // (the grid has no tile beyond out_w)
+        const unsigned ncol = g.out_w - X0 < tile ? g.out_w - X0 : tile;
+        // the taps of the lane's columns X0 + p * lanes + lane: box columns [fx, fx + nx), weights from wp
+        int fx[kResizeSlots], nx[kResizeSlots];
+        const float *wp[kResizeSlots];
+        bool has[kResizeSlots];
+#pragma unroll
+        for(int p = 0; p < kResizeSlots; p++) {
+                has[p] = (unsigned)p < g.slots && (unsigned)lane < g.lanes && (unsigned)p * g.lanes + (unsigned)lane < ncol;
+                const unsigned X = has[p] ? X0 + (unsigned)p * g.lanes + (unsigned)lane : X0;
+                fx[p] = g.first_x[X];
+                nx[p] = has[p] ? g.count_x[X] : 0;
+                wp[p] = g.wx + (size_t)X * g.stride_x;
+        }
+        // the tile's segment of a source row, in canvas columns: [c_begin, c_last], c_begin a multiple of 4 (first and
+        // first + count never decrease from one output index to the next)
+        const unsigned Xl = X0 + ncol - 1;
+        const int c_last = (int)g.box_x + g.first_x[Xl] + g.count_x[Xl] - 1;
+        const int c_begin = ((int)g.box_x + g.first_x[X0]) & ~3;
+        // the windows of the wavefront's rows: box rows [fy, fy + ny), the same in every lane; and the source rows of all of
+        // them, [j_begin, j_end] (windows never move backwards)
+        int fy[kFilterRows], ny[kFilterRows];
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+                const bool valid = (unsigned)q < nrow;
+                fy[q] = g.first_y[valid ? Yb + (unsigned)q : Yb];
+                ny[q] = valid ? g.count_y[Yb + (unsigned)q] : 0;
+        }
+        const int j_begin = g.first_y[Yb], j_end = g.first_y[Yb + nrow - 1] + g.count_y[Yb + nrow - 1] - 1;
+        Raw *const data = static_cast<Raw *>(o.data);
+
+        // the 16-byte loads of chunk c0 of source row j, into registers: issued one chunk ahead of their use
+        float4 ld[kRounds][NPLANE];
+#pragma unroll
+        for(int u = 0; u < kRounds; u++) {
+#pragma unroll
+                for(int k = 0; k < NPLANE; k++) { ld[u][k] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        }
+        const auto issue = [&](int j, int c0) {
+                const size_t row = (size_t)g.box_y + (size_t)j;
+#pragma unroll
+                for(int u = 0; u < kRounds; u++) {
+                        const int c = c0 + u * 256 + lane * 4;
+                        if(c <= c_last) {
+                                ld[u][0] = *reinterpret_cast<const float4 *>(yp + row * ys + c);
+                                if constexpr(NPLANE == 3) {
+                                        ld[u][1] = *reinterpret_cast<const float4 *>(cbp + row * cbs + c);
+                                        ld[u][2] = *reinterpret_cast<const float4 *>(crp + row * crs + c);
+                                }
+                        }
+                }
+        };
+
+        float acc[kFilterRows][kResizeSlots][NPLANE];
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) { acc[q][p][k] = 0.f; }
+                }
+        }
+        issue(j_begin, c_begin);
+        for(int j = j_begin; j <= j_end; j++) {
+                // r_j of every column of the lane: the row's chunks, left to right
+                float r[kResizeSlots][NPLANE];
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) { r[p][k] = 0.f; }
+                }
+                for(int c0 = c_begin; c0 <= c_last; c0 += kResizeChunk) {
+#pragma unroll
+                        for(int u = 0; u < kRounds; u++) {
+                                const int at = u * 256 + lane * 4;
+                                if(c0 + at <= c_last) {
+                                        const float yin[4] = {ld[u][0].x, ld[u][0].y, ld[u][0].z, ld[u][0].w};
+                                        const float4 cb4 = ld[u][NPLANE == 3 ? 1 : 0], cr4 = ld[u][NPLANE == 3 ? 2 : 0];   // (one plane: not looked at)
+                                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+#pragma unroll
+                                        for(int q = 0; q < 4; q++) {
+                                                const int idx = resize_lds_index(at + q);
+                                                clamped_pixel<NPLANE>(yin[q], cbin[q], crin[q], [&](int k, float x) { lds[k][idx] = x; });
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        // the next chunk's loads fly while this one's taps are walked
+                        if(c0 + kResizeChunk <= c_last) { issue(j, c0 + kResizeChunk); }
+                        else if(j < j_end) { issue(j + 1, c_begin); }
+                        const int rel0 = c0 - (int)g.box_x;              // the chunk's first column relative to the box (>= -3)
+#pragma unroll
+                        for(int p = 0; p < kResizeSlots; p++) {
+                                if(!has[p]) { continue; }
+                                const int i0 = fx[p] > rel0 ? fx[p] : rel0;
+                                const int last = fx[p] + nx[p] - 1;
+                                const int i1 = last < rel0 + kResizeChunk - 1 ? last : rel0 + kResizeChunk - 1;
+                                for(int i = i0; i <= i1; i++) {          // (none of this column's taps in this chunk: i0 > i1)
+                                        const float a = wp[p][i - fx[p]];
+                                        const int idx = resize_lds_index(i - rel0);
+#pragma unroll
+                                        for(int k = 0; k < NPLANE; k++) {
+                                                const float t = a * lds[k][idx];
+                                                r[p][k] = r[p][k] + t;
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();                 // the next chunk is staged over this one
+                }
+                // every output row of the wavefront whose window holds the row takes it with its weight
+#pragma unroll
+                for(int q = 0; q < kFilterRows; q++) {
+                        if(j < fy[q] || j >= fy[q] + ny[q]) { continue; }     // (wavefront-uniform; ny is 0 beyond nrow)
+                        const float b = g.wy[(size_t)(Yb + (unsigned)q) * g.stride_y + (unsigned)(j - fy[q])];
+#pragma unroll
+                        for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                                for(int k = 0; k < NPLANE; k++) {
+                                        const float t = b * r[p][k];
+                                        acc[q][p][k] = acc[q][p][k] + t;
+                                }
+                        }
+                }
+        }
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+                if((unsigned)q >= nrow) { continue; }
+                const long long rowo = (long long)(Yb + (unsigned)q) * o.stride_y;
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+                        if(!has[p]) { continue; }
+                        const long long X = (long long)(X0 + (unsigned)p * g.lanes + (unsigned)lane);
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) {
+                                float m = acc[q][p][k];
+                                m = m > 0.f ? m : 0.f;
+                                m = m < 255.f ? m : 255.f;
+                                data[(long long)k * o.stride_c + rowo + X * o.stride_x] = (Raw)E::make(m, o.scale[k], o.bias[k]);
+                        }
+                }
+        }
+}
+#define J2P_FILTERED_KERNELS(NPLANE)                                                                                                          \
+        template __global__ void k_to_tensor_filtered<NPLANE, kDtypeU8>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterGeom, TensorOut);   \
+        template __global__ void k_to_tensor_filtered<NPLANE, kDtypeF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterGeom, TensorOut);  \
+        template __global__ void k_to_tensor_filtered<NPLANE, kDtypeBF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterGeom, TensorOut); \
+        template __global__ void k_to_tensor_filtered<NPLANE, kDtypeF32>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterGeom, TensorOut);
+J2P_FILTERED_KERNELS(3)
+J2P_FILTERED_KERNELS(1)
+#undef J2P_FILTERED_KERNELS
 
 // ---------------------------------------------------------------------------
 // JPEG output: a solved plane straight to quantised coefficients — dct8x8s (ooura/dct.c:98-130) of every 8x8 block,

@@ -109,6 +109,8 @@ struct j2p_solver {
         bool proj_boundary_done = false;   // between the two parts of a split projection phase
         void *arena = nullptr;   // the one device allocation everything below is carved from (pooled, see j2p_pool_take)
         size_t arena_bytes = 0;
+        void *out_scratch = nullptr;     // the output stage's scratch (j2p_solver_scratch: the taps of a filtered tensor output); pooled, kept until destroy
+        size_t out_scratch_bytes = 0;
         // reductions
         bool fold = false;       // level 1 of the norm reduction inside k_gradient (J2P_OPT_NORM_FOLD; default: norm_defaults)
         unsigned zone_d = 0, zone_b = 0, zone_c = 0;   // shares (1/256) of a gradient launch dealt as double / half / quarter tile rows (grad_item)
@@ -1082,6 +1084,7 @@ void j2p_solver_destroy(j2p_solver *s)
         if(s->stream) { (void)hipStreamSynchronize(s->stream); }
         if(s->live_registered) { j2p_live_add(s->device, s->live, -1); }
         j2p_pool_give(s->device, s->arena, s->arena_bytes);
+        j2p_pool_give(s->device, s->out_scratch, s->out_scratch_bytes);
         (void)hipFree(s->logsums);
         (void)hipFree(s->log_band);
         (void)hipFree(s->trace);
@@ -2070,5 +2073,26 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
         if(c >= s->nch) { return j2p_fail(J2P_EINVAL, "channel %u out of range", c); }
         if(y < s->row0 || y >= s->row0 + s->rows) { return j2p_fail(J2P_EINVAL, "row %u is not one of the solver's [%u,%u)", y, s->row0, s->row0 + s->rows); }
         *row = s->ch[c].xbuf[s->cur] + (size_t)(kHalo + (y - s->row0)) * s->W;
+        return J2P_OK;
+}
+
+int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out)
+{
+        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(s->out_scratch_bytes < bytes) {
+                DeviceGuard guard(s->device);
+                // what is queued on the stream may still read the block that is given back: growing waits, reusing never does
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                j2p_pool_give(s->device, s->out_scratch, s->out_scratch_bytes);
+                s->out_scratch = nullptr;
+                s->out_scratch_bytes = 0;
+                const size_t want = (bytes + ((size_t)256 << 10) - 1) & ~(((size_t)256 << 10) - 1);
+                void *p = nullptr;
+                size_t got = 0;
+                HIP_TRY(j2p_pool_take(s->device, want, &p, &got));
+                s->out_scratch = p;
+                s->out_scratch_bytes = got;
+        }
+        *out = s->out_scratch;
         return J2P_OK;
 }
