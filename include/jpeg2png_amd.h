@@ -131,6 +131,11 @@ void j2p_pool_trim(void);
 int j2p_solver_debug_option(j2p_solver *s, int option, int value);
 /* bytes per quantised coefficient the projection kernel reads for channel c: 1 or 2 (J2P_OPT_NARROW_COEFFICIENTS) */
 int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *bytes);
+/* *shared = 1 when channel c keeps its gradient and its prob state in ONE buffer (a channel sampled 1x1 whose coefficient
+ * raster has the canvas's pitch, with the prob term on: the two are never live at the same pixel at the same time), else 0 */
+int j2p_solver_shares_state(const j2p_solver *s, unsigned c, int *shared);
+/* bytes of device memory the solver carved its planes, state and reduction buffers from */
+int j2p_solver_arena_bytes(const j2p_solver *s, size_t *bytes);
 /* *on = 1 when the interior strips of channel c take the wide-footprint projection path in an unlogged run (J2P_OPT_WIDE_FOOTPRINT,
  * J2P_OPT_MIXED_PROJECT), else 0 */
 int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on);
@@ -368,7 +373,9 @@ int j2p_solver_commit_initial_halo(j2p_solver *s);
 int j2p_solver_download(j2p_solver *s, unsigned c, float *out);
 
 /* diagnostics: channel c's objective gradient as the last gradient phase left it (W * band_rows
- * floats; compute.c's aux->obj_gradient before the step) */
+ * floats; compute.c's aux->obj_gradient before the step).  The gradient only BETWEEN the two phases of an iteration:
+ * the projection phase of a channel that keeps both in one buffer (j2p_solver_shares_state) writes the prob state of the
+ * next iteration over it, block by block. */
 int j2p_solver_download_gradient(j2p_solver *s, unsigned c, float *out);
 
 /* device pointer to channel c's current iterate (own rows), for on-device consumers */

@@ -116,7 +116,7 @@ C_ABI_SYMBOLS = [
     "j2p_batch_create", "j2p_batch_destroy", "j2p_batch_submit", "j2p_batch_wait",
     "compute", "j2p_compute", "j2p_compute_tiled", "j2p_compute_timing", "j2p_debug_fail_run_after", "j2p_solver_launches_per_iteration", "j2p_solver_timing_overhead",
     "j2p_debug_build", "j2p_debug_grad_items", "j2p_debug_norm_plan", "j2p_experiments_build", "j2p_solver_debug_violations", "j2p_solver_trace", "j2p_division_exhaustive",
-    "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint",
+    "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint", "j2p_solver_shares_state", "j2p_solver_arena_bytes",
     "j2p_solver_debug_partials", "j2p_norm_selftest", "j2p_norm_selftest_bands",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -737,7 +737,8 @@ class Solver:
         return out
 
     def download_gradient(self, c):
-        """diagnostics: the objective gradient the last gradient phase wrote for channel c"""
+        """diagnostics: the objective gradient the last gradient phase wrote for channel c — between phase_gradient() and
+        phase_project() only: afterwards the buffer of a channel that shares (shares_state) holds the next prob state"""
         out = np.empty((self.row_end - self.row_begin, self.W), dtype=np.float32)
         _check(self._lib.j2p_solver_download_gradient(self._h, c, out.ctypes.data))
         return out
@@ -757,6 +758,18 @@ class Solver:
         """bytes per quantised coefficient the projection reads for channel c: 1 (every |d| <= 127) or 2"""
         n = ctypes.c_uint()
         _check(self._lib.j2p_solver_coefficient_bytes(self._h, int(c), ctypes.byref(n)))
+        return n.value
+
+    def shares_state(self, c=0):
+        """True when channel c keeps its gradient and its prob state in one buffer (1x1 sampling at the canvas's pitch, prob term on)"""
+        n = ctypes.c_int()
+        _check(self._lib.j2p_solver_shares_state(self._h, int(c), ctypes.byref(n)))
+        return bool(n.value)
+
+    def arena_bytes(self):
+        """bytes of device memory the solver carved its planes, state and reduction buffers from"""
+        n = ctypes.c_size_t()
+        _check(self._lib.j2p_solver_arena_bytes(self._h, ctypes.byref(n)))
         return n.value
 
     def wide_footprint(self, c=0):

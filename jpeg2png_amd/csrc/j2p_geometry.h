@@ -3,6 +3,7 @@
 // of integers; C11 and C++, nothing from HIP, so that compute_host.c, the HIP units and a stand-alone C program
 // (tests/c/geometry_main.c) all include it.  Not part of the C-ABI.
 #pragma once
+#include <stddef.h>
 #include "jpeg2png_amd.h"          // J2P_TILE_ROWS, J2P_HALO_ROWS
 
 // ---- canvas and band alignment: accumulated over the channels ----
@@ -150,4 +151,46 @@ static inline int j2p_row_window_of(unsigned ch, unsigned hs, unsigned H, unsign
                 out->frows = f1 - f0;
         }
         return 1;
+}
+
+// ---- one buffer for the gradient g and the prob state pg of a channel ----
+// g (canvas raster: rows x W floats from canvas row row0) and pg (coefficient raster: crows x cw floats from coefficient
+// row crow0) are never live at the same time for the same pixel: k_gradient reads pg(r, x) only in the lane that then
+// stores g(r, x), k_project reads the g of its eight blocks and then writes their pg.  Where the two rasters put every
+// sample at the same offset — a channel sampled 1x1 whose coefficient raster has the canvas's pitch and starts at the
+// solver's first row — one buffer of rows x W floats serves as both.  A channel with fewer coefficient rows than the
+// canvas has rows still shares: beyond its coverage no pg is written and none is used (march_rows: the row test at the
+// point of use), the floats there are g's alone.  Not shared: prob term off (pweight == 0: pg must stay all zero, nobody
+// writes it, and 0 * g of a non-finite g would not be 0); subsampled, narrower or wide-footprint channels.
+static inline int j2p_shares_state(unsigned cw, unsigned ws, unsigned hs, unsigned crow0, unsigned W, unsigned row0, int prob_on, int wide)
+{
+        return ws == 1 && hs == 1 && cw == W && crow0 == row0 && prob_on && !wide;
+}
+
+// ---- what one channel keeps live per iteration, for the non-temporal policy (j2p_solver.hip: nt_policy) ----
+// planes: x_k and x_{k-1} with their halo rows; g: the gradient plane where it is a buffer of its own (a shared buffer is
+// counted once, in working_set, and is nobody's to hint apart: "everything but g" is then everything); d: the coefficients
+// at d_bytes each.  cells = floats of the prob state = coefficients held (at least one row).
+typedef struct {
+        size_t working_set, g, planes, d;
+} j2p_live_bytes;
+
+static inline void j2p_live_bytes_add(j2p_live_bytes *l, size_t plane_floats, size_t grad_floats, size_t cells, size_t d_bytes, int shared)
+{
+        const size_t state_floats = shared ? grad_floats : grad_floats + cells;
+        l->working_set += (2 * plane_floats + state_floats) * sizeof(float) + cells * d_bytes;
+        l->planes += 2 * plane_floats * sizeof(float);
+        l->d += cells * d_bytes;
+        if(!shared) { l->g += grad_floats * sizeof(float); }
+}
+
+// how many streams get the non-temporal hint so that the rest fits `cache` bytes: 0 none, 1 g, 2 g and the prob state,
+// 3 those and d.  A solver all of whose channels share has g == 0: level 1 is then level 0's test over again and never
+// applies — past the cache such a solver goes straight to hinting the shared buffer in both its roles.
+static inline int j2p_nt_level(const j2p_live_bytes *l, size_t cache)
+{
+        if(l->working_set <= cache) { return 0; }                        // everything fits
+        if(l->working_set - l->g <= cache) { return 1; }                 // everything but g fits
+        if(l->planes + l->d <= cache) { return 2; }                      // planes and d fit
+        return 3;
 }

@@ -118,7 +118,7 @@ struct ChanDev {
         float *xcur;        // x_k, own row 0 (halo rows at negative offsets)
         float *xprev;       // x_{k-1}; receives x_{k+1}
         float *grad;        // objective gradient, own rows
-        float *pg;          // carried prob-gradient state, coefficient raster, band-local
+        float *pg;          // carried prob-gradient state, coefficient raster, band-local; == grad where the channel shares (j2p_shares_state)
         const int16_t *d;   // quantised coefficients, block-major, band-local
         const uint8_t *d8;  // the same as d + 128 in one byte each when every |d| of the channel is <= 127 (k_narrow_coefficients), else NULL
         const float *q;     // 64 floats
@@ -944,6 +944,9 @@ constexpr int kGradWaves = 4;
 // d (read once per iteration by k_project) at 3.  What is left without the hint is what should stay cache-resident:
 // 4096^2 Y (288 MiB): level 1, 137 -> 127 us per iteration; 16384x2048 (576 MiB, the planes x_k, x_{k-1} are exactly
 // 256 MiB): level 3, 292 -> 240 us; when everything fits the hint costs 1-2 %.
+// A channel that keeps g and the prob state in ONE buffer (ChanDev::pg == ChanDev::grad, j2p_geometry.h: j2p_shares_state)
+// has no level 1: the hints still go by the role of the access (a g access at >= 1, a prob-state access at >= 2), and its
+// solver's policy goes from 0 straight to 2.
 // What one wavefront of a gradient launch works on (wave-uniform; grad_item): strip `wcol`, band-local target rows
 // [t0, t0 + nrows) of tile row `tr` — the whole tile row (kind 0), one of its halves (kind 1) or quarters (kind 2; `sub`
 // says which), or tile rows tr AND tr + 1 (kind 3).  Half and quarter items exist so that the LAST workgroups of a launch
@@ -1062,6 +1065,12 @@ __device__ __forceinline__ void march_rows(const GradArgs &a, v2f *xchg, const S
         // footprint).  Loaded unconditionally from a clamped address; `pmask` (per lane) and the row
         // test at the point of use decide whether it contributes.  A channel with pweight == 0 has an
         // all-zero state buffer, so it needs no special case.
+        // The state may live in the buffer g is stored to (k.pg == k.grad: unit sampling, cw == W, same first row, so the
+        // two rasters are one): the state of target row t at the lane's own columns is loaded R - 1 trips before this
+        // wavefront stores g there, and the store's value depends on the load.  Nobody else stores those pixels (items
+        // own disjoint rows, strips disjoint columns).  What a halo lane or a clamped row reads may already be a
+        // neighbour's g: halo lanes have p_scale == 0 and their g is neither stored nor summed; rows past the strip or
+        // the channel's coverage are not used at all.
         v2f p_scale;
         int p_col[2];
         {
@@ -2473,6 +2482,9 @@ __device__ __forceinline__ void project_strip(const ProjArgs &a, ProjShared &sh)
         }
 
         // ---- next iteration's prob gradient block (compute.c:49-51) ----
+        // (k.pg may be k.grad: the block's state goes over the block's g.  Every read of g by this wavefront — the 24 loads'
+        // eight, or stepped() on the strips at the edges — is of its own eight blocks and stands before these stores in
+        // program order, and e[] depends on all of them through the DCT: block-local, as x_{k+1} over x_{k-1} is.)
         if(k.prob_on) {
                 transpose8(e, scratch, lane);
                 idct8(e);

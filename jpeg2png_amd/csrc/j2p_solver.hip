@@ -47,7 +47,8 @@ struct ChanHost : j2p_row_window {           // crow0, crows: of d / pg held on 
         unsigned cw = 0, ch = 0, ws = 1, hs = 1;
         float *xbuf[2] = {nullptr, nullptr}; // allocation bases, (rows + 2*halo) * W floats
         float *grad = nullptr;
-        float *pg = nullptr;
+        float *pg = nullptr;                 // == grad where the channel keeps both in one buffer (`shared`)
+        bool shared = false;                 // j2p_shares_state: g and the prob state take turns in one buffer of rows * W floats
         int16_t *d = nullptr;
         uint8_t *d8 = nullptr;               // d + 128 in bytes (k_narrow_coefficients); read by k_project instead of d when `narrow`
         bool narrow_fits = false;            // every |d| of the channel's rows held here is <= 127
@@ -109,6 +110,7 @@ struct j2p_solver {
         bool proj_boundary_done = false;   // between the two parts of a split projection phase
         void *arena = nullptr;   // the one device allocation everything below is carved from (pooled, see j2p_pool_take)
         size_t arena_bytes = 0;
+        size_t arena_used = 0;   // ... of which carved (the pool may hand out a larger block)
         void *out_scratch = nullptr;     // the output stage's scratch (j2p_solver_scratch: the taps of a filtered tensor output); pooled, kept until destroy
         size_t out_scratch_bytes = 0;
         // reductions
@@ -123,6 +125,7 @@ struct j2p_solver {
         LiveBytes live;                 // what this solver adds to it
         bool phase_log = false;         // the gradient phase of the running iteration was issued with logging
         bool mixed_project = true;      // small canvases: all samplings in one projection launch (J2P_OPT_MIXED_PROJECT)
+        bool share_state = true;        // eligible channels keep g and the prob state in one buffer (J2P_SHARE_STATE=0, experiments build: two)
         bool wide_footprint = true;     // footprints 3, 4, 6, 8 columns wide take the wide-footprint path (J2P_OPT_WIDE_FOOTPRINT)
         unsigned *d_maxabs = nullptr;                 // [channel] largest |d| (k_narrow_coefficients, create only)
         unsigned long long *dbg_counters = nullptr;   // J2P_DEBUG builds: [0] address violations, [1] first site, [2] first offset
@@ -214,10 +217,8 @@ int nt_policy(const j2p_solver *s)
                 return env && strcmp(env, "solver") == 0;
         }();
         const LiveBytes l = own_only || !s->live_registered ? s->live : j2p_live_on(s->device);
-        if(l.working_set <= kNtWorkingSet) { return 0; }                        // everything fits
-        if(l.working_set - l.g <= kNtWorkingSet) { return 1; }                  // everything but g fits
-        if(l.planes + l.d <= kNtWorkingSet) { return 2; }                       // planes and d fit
-        return 3;
+        const j2p_live_bytes b = {l.working_set, l.g, l.planes, l.d};
+        return j2p_nt_level(&b, kNtWorkingSet);
 }
 
 // the bytes of the coefficients the projection actually reads (one or two per coefficient, ChanHost::narrow) in the
@@ -280,7 +281,8 @@ ChanDev chan_dev(const j2p_solver *s, unsigned c)
                 }
                 const size_t cells = (size_t)(h.crows ? h.crows : 1) * h.cw;
                 k.dbg.grad = {reinterpret_cast<const char *>(h.grad), reinterpret_cast<const char *>(h.grad + (size_t)s->rows * s->W)};
-                k.dbg.pg = {reinterpret_cast<const char *>(h.pg), reinterpret_cast<const char *>(h.pg + cells)};
+                // (a shared buffer: the prob state's range is the buffer's, the gradient's)
+                k.dbg.pg = {reinterpret_cast<const char *>(h.pg), reinterpret_cast<const char *>(h.pg + (h.shared ? (size_t)s->rows * s->W : cells))};
                 if(h.narrow) { k.dbg.d = {reinterpret_cast<const char *>(h.d8), reinterpret_cast<const char *>(h.d8 + cells)}; }
                 else { k.dbg.d = {reinterpret_cast<const char *>(h.d), reinterpret_cast<const char *>(h.d + cells)}; }
                 k.dbg.counters = s->dbg_counters;
@@ -747,7 +749,9 @@ int launch_init(j2p_solver *s)
                 const int fill_halo = s->band_local ? 0 : 1;
                 hipLaunchKernelGGL(k_init_state, dim3(2048), dim3(256), 0, s->stream, k, geo_of(s),
                                    (const float *)h.decoded, fill_halo);
-                if(h.crows) {
+                // (a shared buffer is zeroed whole: what a solve left in it is gradient as well as prob state)
+                if(h.shared) { hipLaunchKernelGGL(k_fill_zero, dim3(1024), dim3(256), 0, s->stream, h.pg, (size_t)s->rows * s->W); }
+                else if(h.crows) {
                         hipLaunchKernelGGL(k_fill_zero, dim3(1024), dim3(256), 0, s->stream, h.pg, (size_t)h.crows * h.cw);
                 }
         }
@@ -817,6 +821,10 @@ int place(j2p_solver *s, const j2p_plane planes[], const float pweight[], int ba
                 // ... and (A/B timing): band solvers finish ||g|| with a k_norm_finish launch instead of inside k_project
                 env = j2p_exp_env("J2P_BAND_NIP");
                 if(env) { s->band_nip = atoi(env) != 0; }
+                // ... and (A/B timing, the bits of both forms): g and the prob state in two buffers everywhere (0), or in
+                // one wherever the channel is eligible, whatever the solver's size (1)
+                env = j2p_exp_env("J2P_SHARE_STATE");
+                if(env) { s->share_state = atoi(env) != 0; }
         }
         for(unsigned c = 0; c < nchannel; c++) {
                 const j2p_plane &p = planes[c];
@@ -825,6 +833,23 @@ int place(j2p_solver *s, const j2p_plane planes[], const float pweight[], int ba
                 h.pweight = pweight[c];
                 if(!j2p_row_window_of(h.ch, h.hs, H, s->row0, s->row0 + s->rows, s->band_local, &h)) {
                         return j2p_fail(J2P_EINVAL, "band-local arrays need every channel to cover the canvas height");
+                }
+                // (wide-footprint channels are 3, 4, 6 or 8 columns wide, whatever J2P_OPT_WIDE_FOOTPRINT says later)
+                const bool wide = h.ws == 3 || h.ws == 4 || h.ws == 6 || h.ws == 8;
+                h.shared = s->share_state && j2p_shares_state(h.cw, h.ws, h.hs, h.crow0, W, s->row0, h.pweight != 0.f, wide);
+        }
+        // ... and only where one buffer makes the solver's own working set fit the Infinity Cache (coefficients counted as
+        // int16, as register_live_bytes does before they are known).  Past the cache it was measured both ways — 8192x4096
+        // and 16384x2048, whose two x planes fill the cache exactly, lose 0.4 and 1.0 %, 8192^2 gains 0.2 % — so such
+        // solvers keep the two buffers they had (profiles/r07_shared_state_ab.jsonl)
+        {
+                j2p_live_bytes l = {0, 0, 0, 0};
+                for(unsigned c = 0; c < nchannel; c++) {
+                        const ChanHost &h = s->ch[c];
+                        j2p_live_bytes_add(&l, (size_t)(s->rows + 2 * kHalo) * W, (size_t)s->rows * W, (size_t)(h.crows ? h.crows : 1) * h.cw, sizeof(int16_t), h.shared);
+                }
+                if(j2p_nt_level(&l, kNtWorkingSet) != 0 && !j2p_exp_env("J2P_SHARE_STATE")) {
+                        for(unsigned c = 0; c < nchannel; c++) { s->ch[c].shared = false; }
                 }
         }
         // reductions: tile rows are counted on the canvas, the band owns a contiguous range
@@ -874,6 +899,7 @@ int carve_arena(j2p_solver *s, const j2p_plane planes[])
         for(int pass = 0; pass < 2; pass++) {
                 if(pass == 1) {
                         HIP_TRY(j2p_pool_take(device, carve.used + 256, &s->arena, &s->arena_bytes));
+                        s->arena_used = carve.used;
                         carve.base = static_cast<char *>(s->arena);
                         carve.used = 0;
                 }
@@ -882,8 +908,10 @@ int carve_arena(j2p_solver *s, const j2p_plane planes[])
                         carve.take(h.xbuf[0], plane_floats);
                         carve.take(h.xbuf[1], plane_floats);
                         carve.take(h.grad, (size_t)s->rows * W);
-                        // the prob state always has at least one (zero) row: the gradient kernel reads it unconditionally
-                        carve.take(h.pg, (size_t)(h.crows ? h.crows : 1) * h.cw);
+                        // the prob state always has at least one (zero) row: the gradient kernel reads it unconditionally;
+                        // a shared channel's is the gradient's buffer (same pitch, same first row: the same offsets)
+                        if(h.shared) { h.pg = h.grad; }
+                        else { carve.take(h.pg, (size_t)(h.crows ? h.crows : 1) * h.cw); }
                         carve.take(h.decoded, (size_t)h.frows * h.cw);
                         carve.take(h.d, (size_t)(h.crows ? h.crows : 1) * h.cw);
                         carve.take(h.d8, (size_t)(h.crows ? h.crows : 1) * h.cw);
@@ -924,14 +952,17 @@ int carve_arena(j2p_solver *s, const j2p_plane planes[])
 void register_live_bytes(j2p_solver *s)
 {
         const size_t plane_floats = plane_floats_of(s);
+        j2p_live_bytes l = {0, 0, 0, 0};
         for(unsigned c = 0; c < s->nch; c++) {
                 const ChanHost &h = s->ch[c];
                 const size_t cells = (size_t)(h.crows ? h.crows : 1) * h.cw;
-                s->live.working_set += (2 * plane_floats + (size_t)s->rows * s->W + cells) * sizeof(float) + cells * sizeof(int16_t);
-                s->live.planes += 2 * plane_floats * sizeof(float);
-                s->live.d += cells * sizeof(int16_t);
+                // (a shared buffer counts once and is not "g": j2p_live_bytes_add)
+                j2p_live_bytes_add(&l, plane_floats, (size_t)s->rows * s->W, cells, sizeof(int16_t), h.shared);
         }
-        s->live.g = (size_t)s->nch * s->rows * s->W * sizeof(float);
+        s->live.working_set = l.working_set;
+        s->live.g = l.g;
+        s->live.planes = l.planes;
+        s->live.d = l.d;
         j2p_live_add(s->device, s->live, +1);
         s->live_registered = true;
         s->nt = nt_policy(s);
@@ -1187,6 +1218,20 @@ int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *byte
 {
         if(!s || !bytes || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_coefficient_bytes: bad argument"); }
         *bytes = s->ch[c].narrow ? 1u : 2u;
+        return J2P_OK;
+}
+
+int j2p_solver_shares_state(const j2p_solver *s, unsigned c, int *shared)
+{
+        if(!s || !shared || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_shares_state: bad argument"); }
+        *shared = s->ch[c].shared ? 1 : 0;
+        return J2P_OK;
+}
+
+int j2p_solver_arena_bytes(const j2p_solver *s, size_t *bytes)
+{
+        if(!s || !bytes) { return j2p_fail(J2P_EINVAL, "j2p_solver_arena_bytes: bad argument"); }
+        *bytes = s->arena_used;
         return J2P_OK;
 }
 
