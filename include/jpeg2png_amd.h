@@ -538,6 +538,39 @@ int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane
 int j2p_debug_filter_taps(int filter, unsigned box, unsigned out, unsigned X, unsigned *first, unsigned *count, float *weights,
                           unsigned capacity);
 
+/* Multi-output filtered tensor output: n (box, size, filter, tensor) items filled from the one solved image by ONE call — the
+ * crops of multi-crop training, FiveCrop / TenCrop, a pyramid of sizes.  No new arithmetic: output i receives exactly the
+ * elements that j2p_planes_to_tensor_resampled(planes, nplane, w, h, &outs[i].r, &outs[i].t) writes, bit for bit, and nothing
+ * else is written; the text of that function is the definition.  Each output is triangle or cubic, mixed freely; an output
+ * with out == box on both axes is the plain crop the filtered form defines.  The area form is not part of this call: an unknown
+ * filter code, 0 included, is J2P_EINVAL.  Boxes may overlap or be equal, sizes smaller or larger than the box, dtypes may
+ * differ between outputs.  Two outputs whose ELEMENTS alias are not detected: which of them wins is undefined.
+ * Every output is checked with the single call's own checks, all of them before anything is queued: a refused call writes no
+ * element of any output and queues nothing.  J2P_EINVAL also for n == 0, n > J2P_MAX_OUTPUTS and outs NULL; a band solver is
+ * J2P_ESTATE.
+ * ASYNCHRONOUS on planes[0].solver's stream, as the single call: no host synchronisation, no copy, and no allocation once the
+ * solver's scratch memory has grown to the call's size — the taps of all outputs share it, so that size is the sum of theirs.
+ * Queued are one launch that forms both axes' taps of every output and one sampling launch per dtype present (at most four),
+ * whose grid holds exactly the workgroups the outputs' own launches would have.  n == 1 is the single call. */
+#define J2P_MAX_OUTPUTS 16
+typedef struct j2p_output {
+        j2p_resample r;
+        j2p_tensor t;
+} j2p_output;
+int j2p_planes_to_tensors_resampled(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, unsigned n,
+                                    const j2p_output outs[]);
+/* Test hooks (no device needed): the work map of such a call for n specs of a w x h image and their tensors' dtypes, computed
+ * with the code the launch uses; the specs are checked as the call checks them (J2P_EINVAL).
+ * _plan: per output i its tile — tiles[3 * i ..] = lanes, slots, rows per wavefront — its own grid — grids[2 * i ..] = tile
+ * columns, row groups (of 4 wavefronts) — and launch_of[i], the sampling launch that holds it; *nlaunch, and per launch its
+ * dtype and its number of workgroups.  Launches are in ascending dtype code, a launch's outputs in list order.
+ * _workgroups: for workgroups [first, first + count) of launch `launch`, map[3 * k ..] = output, tile column, row group —
+ * what the kernel's workgroup of that index finds in its prefix table.  J2P_EINVAL beyond the launch's grid. */
+int j2p_debug_outputs_plan(unsigned w, unsigned h, unsigned n, const j2p_resample specs[], const int dtypes[], unsigned tiles[],
+                           unsigned grids[], unsigned launch_of[], unsigned *nlaunch, int launch_dtype[4], unsigned launch_workgroups[4]);
+int j2p_debug_outputs_workgroups(unsigned w, unsigned h, unsigned n, const j2p_resample specs[], const int dtypes[], unsigned launch,
+                                 unsigned first, unsigned count, unsigned map[]);
+
 /* JPEG output: ONE (solver, channel) pair's current iterate as quantised DCT coefficients, ready for libjpeg's
  * jpeg_write_coefficients — no RGB conversion and no 8-bit samples in between.  For each 8x8 block of the canvas plane:
  * dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes), every coefficient divided by quant_table[j] as
@@ -650,6 +683,13 @@ int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize 
 /* the same with a filter (j2p_planes_to_tensor_resampled): the tensor may be larger than the box.  *r is copied and travels next
  * to the job, never in it; validated here, at submit.  r == NULL: j2p_batch_submit. */
 int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket);
+/* a job that fills n tensors from its one solve (j2p_planes_to_tensors_resampled): the outputs are copied and travel next to the
+ * job, never in it.  job->out_w x out_h is the image's crop, which every box must lie inside; job->out_tensor.data must be NULL,
+ * out_bits 0 and out_coef[0] NULL (J2P_EINVAL otherwise); out_planes is still honoured; not with `tile`, as every tensor job.
+ * All tensors must be device memory of ONE GPU of the batch, on a worker of which the job runs (J2P_EINVAL at submit otherwise,
+ * as for a bad spec and n > J2P_MAX_OUTPUTS); after j2p_batch_wait every tensor is complete for any stream.  n == 0 or outs
+ * NULL: j2p_batch_submit. */
+int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const j2p_output outs[], int *ticket);
 int j2p_batch_wait(j2p_batch *b, int ticket);               /* the job's status; its error text in j2p_last_error() */
 
 /* test hook: n > 0: the n-th j2p_solver_run() / j2p_tiled_run() call from now on (any thread) fails with J2P_EDEVICE

@@ -67,6 +67,14 @@ class _CResample(ctypes.Structure):
                 ("out_w", ctypes.c_uint), ("out_h", ctypes.c_uint), ("filter", ctypes.c_int)]
 
 
+class _COutput(ctypes.Structure):
+    """j2p_output: one item of a multi-output call — what is resampled, and the tensor that receives it"""
+    _fields_ = [("r", _CResample), ("t", _CTensor)]
+
+
+J2P_MAX_OUTPUTS = 16
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -108,6 +116,7 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_tensor", "j2p_planes_rows_to_tensor", "j2p_debug_tensor_path", "j2p_debug_job_layout",
     "j2p_planes_to_tensor_resized", "j2p_batch_submit_resized",
     "j2p_planes_to_tensor_resampled", "j2p_batch_submit_resampled", "j2p_debug_filter_taps",
+    "j2p_planes_to_tensors_resampled", "j2p_batch_submit_outputs", "j2p_debug_outputs_plan", "j2p_debug_outputs_workgroups",
     "j2p_pool_trim", "j2p_solver_debug_option", "j2p_solver_stream", "j2p_solver_halo_rows",
     "j2p_solver_norm_from_bands", "j2p_solver_copy_rows", "j2p_solver_alternate_rowsums",
     "j2p_tiled_create", "j2p_tiled_destroy", "j2p_tiled_canvas", "j2p_tiled_band", "j2p_tiled_run", "j2p_tiled_reset", "j2p_tiled_sync",
@@ -280,6 +289,18 @@ def _bind(path):
     lib.j2p_batch_submit_resampled.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CResample), ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_filter_taps.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint),
                                           ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_float), ctypes.c_uint]
+    if hasattr(lib, "j2p_planes_to_tensors_resampled"):
+        # (a build of an earlier commit, loaded next to this one as the baseline of an A/B timing — tools/outputs_probe.py — has
+        # not got the multi-output calls; using them on it is an AttributeError)
+        lib.j2p_planes_to_tensors_resampled.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                        ctypes.POINTER(_COutput)]
+        lib.j2p_batch_submit_outputs.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_uint, ctypes.POINTER(_COutput),
+                                                 ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_debug_outputs_plan.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResample), ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                               ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint)]
+        lib.j2p_debug_outputs_workgroups.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResample),
+                                                     ctypes.POINTER(ctypes.c_int), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -395,6 +416,41 @@ def tensor_path(w, nplane, dtype, stride_c, stride_y, stride_x, address):
     _check(load_library().j2p_debug_tensor_path(int(w), int(nplane), int(dtype), int(stride_c), int(stride_y), int(stride_x), int(address),
                                                 ctypes.byref(path)))
     return TENSOR_PATHS[path.value]
+
+
+def _c_specs(specs, dtypes):
+    n = len(specs)
+    if len(dtypes) != n:
+        raise J2PError("outputs: one dtype per spec")
+    return (_CResample * max(n, 1))(*[s if isinstance(s, _CResample) else _CResample(*[int(v) for v in s]) for s in specs]), \
+        (ctypes.c_int * max(n, 1))(*[int(d) for d in dtypes])
+
+
+def outputs_plan(width, height, specs, dtypes):
+    """the work map of a multi-output call (j2p_debug_outputs_plan; no device needed) for specs — _CResample, or tuples (box_x,
+    box_y, box_w, box_h, out_w, out_h, filter code) — of a width x height image and their tensors' J2P_DTYPE_* codes: a dict of
+    tiles [(lanes, slots, rows)], grids [(tile columns, row groups)] and launch_of per output, and launches [(dtype,
+    workgroups)].  J2PError for what the call refuses."""
+    n = len(specs)
+    cs, cd = _c_specs(specs, dtypes)
+    tiles, grids, launch_of = (ctypes.c_uint * (3 * max(n, 1)))(), (ctypes.c_uint * (2 * max(n, 1)))(), (ctypes.c_uint * max(n, 1))()
+    nlaunch, ldtype, lwg = ctypes.c_uint(0), (ctypes.c_int * 4)(), (ctypes.c_uint * 4)()
+    _check(load_library().j2p_debug_outputs_plan(int(width), int(height), n, cs, cd, tiles, grids, launch_of, ctypes.byref(nlaunch), ldtype, lwg))
+    return {"tiles": [tuple(tiles[3 * i:3 * i + 3]) for i in range(n)], "grids": [tuple(grids[2 * i:2 * i + 2]) for i in range(n)],
+            "launch_of": list(launch_of[:n]), "launches": [(ldtype[k], lwg[k]) for k in range(nlaunch.value)]}
+
+
+def outputs_workgroups(width, height, specs, dtypes, launch, first=0, count=None):
+    """(output, tile column, row group) of workgroups [first, first + count) of sampling launch `launch` of that call, as the
+    kernel's workgroups find them in their prefix table (j2p_debug_outputs_workgroups): an array [count, 3].  count None: to
+    the end of the launch's grid."""
+    cs, cd = _c_specs(specs, dtypes)
+    if count is None:
+        count = outputs_plan(width, height, specs, dtypes)["launches"][launch][1] - first
+    out = np.zeros((int(count), 3), np.uint32)
+    _check(load_library().j2p_debug_outputs_workgroups(int(width), int(height), len(specs), cs, cd, int(launch), int(first), int(count),
+                                                       out.ctypes.data))
+    return out
 
 
 def job_layout():
@@ -513,6 +569,33 @@ def _c_resample(width, height, out_width, out_height, box, code):
     if ow > J2P_RESAMPLE_MAX_OUT or oh > J2P_RESAMPLE_MAX_OUT:
         raise J2PError(f"resize: the output {ow} x {oh} is larger than {J2P_RESAMPLE_MAX_OUT} a side")
     return _CResample(bx, by, bw, bh, ow, oh, code)
+
+
+_OUTPUT_KEYS = {"out_width", "out_height", "box", "filter", "dtype", "layout", "scale", "bias"}
+
+
+def _output_spec(width, height, o, tensor_key):
+    """(j2p_resample, the dict) of one item of outputs= of Solver.to_tensors / Batch.submit: the keywords of to_tensor, filter
+    required and "triangle" or "cubic" — the area form has no place in a list"""
+    if not isinstance(o, dict):
+        raise J2PError("outputs: every output is a dict")
+    unknown = set(o) - _OUTPUT_KEYS - {tensor_key}
+    if unknown:
+        raise J2PError(f"outputs: unknown key(s) {sorted(unknown)}")
+    code = _filter_code(o.get("filter"))
+    if code is None:
+        raise J2PError("outputs: every output names its filter, \"triangle\" or \"cubic\" (the area form is not part of a list)")
+    return _c_resample(width, height, o.get("out_width"), o.get("out_height"), o.get("box"), code)
+
+
+def _output_count(outputs):
+    try:
+        n = len(outputs)
+    except TypeError:
+        raise J2PError("outputs must be a list of dicts") from None
+    if n < 1 or n > J2P_MAX_OUTPUTS:
+        raise J2PError(f"outputs: {n} outputs (1 to {J2P_MAX_OUTPUTS} per call)")
+    return n
 
 
 def _sampling(subsampling):
@@ -736,6 +819,43 @@ class Solver:
         out.record_stream(theirs)
         return out
 
+    def to_tensors(self, width, height, outputs):
+        """Several resampled views of the solved width x height image from ONE call (j2p_planes_to_tensors_resampled): the crops
+        of multi-crop training, FiveCrop / TenCrop, a pyramid of sizes.  outputs: 1 to 16 dicts of out_width, out_height, box,
+        filter ("triangle" or "cubic", required) and optionally out=, dtype, layout, scale, bias, each with the meaning it has in
+        to_tensor.  Returns the list of tensors; tensor i holds bit for bit what to_tensor(width, height, **outputs[i]) gives.
+        Two launches (the taps of all outputs, the sampling) plus one sampling launch per further dtype, whatever the number
+        of outputs.  Stream handling is to_tensor's, once for the call and for every tensor."""
+        n = _output_count(outputs)
+        specs = [_output_spec(width, height, o, "out") for o in outputs]
+        torch = _torch()
+        if self.nch not in (1, 3):
+            raise J2PError("tensor output needs a solver of three channels (RGB) or one (greyscale)")
+        dev = torch.device("cuda", self.device)
+        tensors, items = [], (_COutput * n)()
+        for i, (o, r) in enumerate(zip(outputs, specs)):
+            out, dtype, layout = o.get("out"), o.get("dtype"), o.get("layout", "chw")
+            if out is None:
+                dtype = torch.float32 if dtype is None else dtype
+                _tensor_dtype(torch, dtype)
+                if layout not in ("chw", "hwc"):
+                    raise J2PError(f"tensor output: layout must be 'chw' or 'hwc', not {layout!r}")
+                out = torch.empty((self.nch, r.out_h, r.out_w) if layout == "chw" else (r.out_h, r.out_w, self.nch), dtype=dtype, device=dev)
+            elif dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
+                raise J2PError(f"tensor output: out is {out.dtype}, dtype says {dtype}")
+            items[i].r = r
+            items[i].t = _c_tensor(out, self.nch, r.out_w, r.out_h, layout, o.get("scale"), o.get("bias"), device=self.device)
+            tensors.append(out)
+        refs = (_CPlaneRef * self.nch)(*[_CPlaneRef(self._h, c) for c in range(self.nch)])
+        ours = torch.cuda.ExternalStream(self.stream(), device=dev)
+        theirs = torch.cuda.current_stream(dev)
+        ours.wait_stream(theirs)            # whatever torch still does with the tensors (their allocation, a fill) comes first
+        _check(self._lib.j2p_planes_to_tensors_resampled(refs, self.nch, int(width), int(height), n, items))
+        theirs.wait_stream(ours)
+        for t in tensors:
+            t.record_stream(theirs)         # (for THEIR stream, never for ours: see to_tensor)
+        return tensors
+
     def download_gradient(self, c):
         """diagnostics: the objective gradient the last gradient phase wrote for channel c — between phase_gradient() and
         phase_project() only: afterwards the buffer of a channel that shares (shares_state) holds the next prob state"""
@@ -932,7 +1052,7 @@ class Batch:
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
-               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None):
+               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None):
         """tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
         GPU as that tensor's elements — shape (3|1, height, width) for layout "chw" or (height, width, 3|1) for "hwc", dtype
         uint8 / float16 / bfloat16 / float32, any view, with per-channel scale and bias as in Solver.to_tensor — by a worker
@@ -943,6 +1063,9 @@ class Batch:
         its shape is (3|1, out_height, out_width) or the "hwc" form, while width and height stay the image's;
         filter (with tensor= only): None or "area" — that; "triangle" or "cubic" — the antialiased filter instead, which also
         enlarges (an image smaller than its slot), as in Solver.to_tensor;
+        outputs=[dicts] (with width and height; not with tensor=, bits, quant_tables or tile): the one solve fills 1 to 16 tensors
+        (j2p_batch_submit_outputs) — the dicts of Solver.to_tensors with tensor= in place of out= (required: a worker cannot
+        allocate for torch), all on one GPU of the batch; wait() returns the list of tensors, each complete for any stream;
         quant_tables=[one 64-entry table per plane] (with width and height, bits 0): wait() returns the list of the planes'
         quantised coefficients, int16 [ceil(height / 8), ceil(width / 8), 64] each (Solver.coefficients) — what a JPEG
         writer entropy-codes — instead of the float planes;
@@ -953,6 +1076,25 @@ class Batch:
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
         n = len(planes)
         resize = None
+        items = None
+        if outputs is not None:
+            if tensor is not None or bits or quant_tables is not None or subsampling is not None or tile:
+                raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
+            if out is not None or filter is not None or out_width is not None or out_height is not None or box is not None or \
+                    layout != "chw" or scale is not None or bias is not None:
+                raise J2PError("job: with outputs= every output carries its own keywords (out_width, out_height, box, filter, layout, scale, bias)")
+            specs = [_output_spec(width, height, o, "tensor") for o in outputs[:_output_count(outputs)]]
+            if any(o.get("tensor") is None for o in outputs):
+                raise J2PError("job: every output of outputs= needs its tensor=")
+            items = (_COutput * len(specs))()
+            for i, (o, r) in enumerate(zip(outputs, specs)):
+                t = o["tensor"]
+                if o.get("dtype") is not None and getattr(t, "dtype", None) != o["dtype"]:
+                    raise J2PError(f"tensor output: tensor is {getattr(t, 'dtype', None)}, dtype says {o['dtype']}")
+                items[i].r = r
+                items[i].t = _c_tensor(t, n, r.out_w, r.out_h, o.get("layout", "chw"), o.get("scale"), o.get("bias"))
+            if len({o["tensor"].device for o in outputs}) != 1:
+                raise J2PError("job: the tensors of outputs= must live on one GPU")
         code = _filter_code(filter)
         if code is not None:
             if tensor is None:
@@ -982,7 +1124,12 @@ class Batch:
         W = max(p.w * p.w_samp for p in planes)
         H = max(p.h * p.h_samp for p in planes)
         shapes = [(p.h * p.h_samp, p.w * p.w_samp) if separate else (H, W) for p in planes]
-        if tensor is not None:
+        if items is not None:
+            job.out_w, job.out_h = int(width), int(height)
+            # (the workers' streams know nothing of torch's: see tensor= below)
+            _torch().cuda.current_stream(outputs[0]["tensor"].device).synchronize()
+            out = [o["tensor"] for o in outputs]
+        elif tensor is not None:
             if quant_tables is not None or subsampling is not None:
                 raise J2PError("job: tensor output and coefficient output (quant_tables) exclude each other")
             if bits:
@@ -1057,7 +1204,9 @@ class Batch:
             job.on_progress = cb
             keep = (keep, cb)                       # the trampoline lives as long as the job
         t = ctypes.c_int()
-        if code is not None:
+        if items is not None:
+            _check(self._lib.j2p_batch_submit_outputs(self._h, ctypes.byref(job), len(items), items, ctypes.byref(t)))
+        elif code is not None:
             _check(self._lib.j2p_batch_submit_resampled(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
         elif resize is not None:
             _check(self._lib.j2p_batch_submit_resized(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))

@@ -35,6 +35,7 @@ struct Job {
         bool resized = false;
         j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resampled: ... resampled with a filter
         bool resampled = false;
+        std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
         int ticket = 0;
         int device = -1;                    // tensor output: the tensor's device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -157,7 +158,9 @@ struct Engines {
 // solve is issued before any of them is settled (sync, progress, done) — how the three solves of `-s` overlap on one GPU,
 // unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
 // resize / resample (tensor jobs on one GPU only, at most one of the two): the tensor receives the image resized.
-int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize, const j2p_resample *resample)
+// outputs (never empty when given; a job on one GPU without out_tensor): those tensors are filled from the solve.
+int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize, const j2p_resample *resample,
+                      const std::vector<j2p_output> *outputs)
 {
         const unsigned nsolve = solves(d);
         if(!d.on_rows && !d.on_progress) {
@@ -201,6 +204,12 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p
                         const Where at = where(d, c);
                         ref[c].channel = at.channel;
                         JOB_TRY(e[at.solve].band(b, &ref[c].solver, &row0[c], &row1[c]));
+                }
+                if(outputs) {
+                        // (never row-tiled: this one band is the whole canvas)
+                        JOB_TRY(j2p_planes_to_tensors_resampled(ref, d.nchannel, d.out_w, d.out_h, (unsigned)outputs->size(), outputs->data()));
+                        JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: every tensor complete, for any stream
+                        continue;
                 }
                 if(d.out_bits || d.out_tensor.data) {
                         const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;   // the band's image rows
@@ -293,10 +302,10 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        return solve_and_deliver(d, eng.e, false, nullptr, nullptr);
+        return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr);
 }
 
-int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample)
+int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
@@ -304,7 +313,7 @@ int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_re
                 JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k], &d.pweight[k],
                                           d.iterations[k], whole, 0));
         }
-        return solve_and_deliver(d, eng.e, true, resize, resample);
+        return solve_and_deliver(d, eng.e, true, resize, resample, outputs);
 }
 
 void worker_main(j2p_batch *b, int device)
@@ -342,7 +351,8 @@ void worker_main(j2p_batch *b, int device)
                 }
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
-                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr);
+                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr,
+                                     job->outputs.empty() ? nullptr : &job->outputs);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -355,10 +365,37 @@ void worker_main(j2p_batch *b, int device)
         }
 }
 
-// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled (never both)
-int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, int *ticket)
+// what j2p_batch_submit_outputs refuses at submit; *device: the one GPU that holds every tensor
+int validate_outputs(const j2p_job &d, unsigned n, const j2p_output *outs, int *device)
+{
+        if(n > J2P_MAX_OUTPUTS) { return j2p_fail(J2P_EINVAL, "job: %u outputs (at most %d)", n, J2P_MAX_OUTPUTS); }
+        if(d.out_tensor.data || d.out_bits || d.out_coef[0]) {
+                return j2p_fail(J2P_EINVAL, "job: a job with outputs needs out_tensor.data NULL, out_bits 0 and no out_coef");
+        }
+        if(d.nchannel != 1 && d.nchannel != 3) { return j2p_fail(J2P_EINVAL, "job: tensor output needs three channels (RGB) or one (greyscale)"); }
+        if(d.out_w == 0 || d.out_h == 0) { return j2p_fail(J2P_EINVAL, "job: tensor output needs out_w and out_h"); }
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: tensor output of a row-tiled job is not supported"); }
+        for(unsigned i = 0; i < n; i++) {
+                if(const char *why = j2p_resample_error(&outs[i].r, d.out_w, d.out_h)) { return j2p_fail(J2P_EINVAL, "job: output %u: %s", i, why); }
+                int dev = -1;
+                if(j2p_device_of_pointer(outs[i].t.data, &dev) != J2P_OK) {
+                        return j2p_fail(J2P_EINVAL, "job: output %u: the tensor's data is not device memory (managed and host memory are refused)", i);
+                }
+                if(i && dev != *device) { return j2p_fail(J2P_EINVAL, "job: output %u lives on device %d, output 0 on device %d", i, dev, *device); }
+                *device = dev;
+        }
+        return J2P_OK;
+}
+
+// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled, — nout != 0 —
+// j2p_batch_submit_outputs (never two of them)
+int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs, int *ticket)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        int outputs_device = -1;
+        if(nout) {
+                if(const int rc = validate_outputs(*job, nout, outs, &outputs_device); rc != J2P_OK) { return rc; }
+        }
         if(f) {
                 if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resampled job needs tensor output (out_tensor)"); }
                 if(const char *why = j2p_resample_error(f, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
@@ -378,10 +415,12 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
                 j->resample = *f;
                 j->resampled = true;
         }
-        if(job->out_tensor.data) {
-                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor
+        if(nout) { j->outputs.assign(outs, outs + nout); }
+        if(job->out_tensor.data || nout) {
+                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor(s)
                 int rc = validate_job(j->desc);
-                if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
+                if(nout) { j->device = outputs_device; }
+                else if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
                         rc = j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
                 }
                 bool owned = false;
@@ -449,17 +488,23 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        return submit(b, job, nullptr, nullptr, ticket);
+        return submit(b, job, nullptr, nullptr, 0, nullptr, ticket);
 }
 
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
 {
-        return submit(b, job, r, nullptr, ticket);
+        return submit(b, job, r, nullptr, 0, nullptr, ticket);
 }
 
 int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket)
 {
-        return submit(b, job, nullptr, r, ticket);
+        return submit(b, job, nullptr, r, 0, nullptr, ticket);
+}
+
+int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const j2p_output outs[], int *ticket)
+{
+        const bool none = n == 0 || !outs;
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

@@ -1,6 +1,6 @@
 // jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
-// or cropped and resized (area, or triangle / cubic taps), and to quantised JPEG coefficients (include/jpeg2png_amd.h: the
-// j2p_planes_* functions).
+// or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), and to quantised JPEG
+// coefficients (include/jpeg2png_amd.h: the j2p_planes_* functions).
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
@@ -360,6 +360,59 @@ static void filter_tile(unsigned out_w, unsigned out_h, unsigned *lanes, unsigne
         *rows = r;                              // (out_h <= 65536: the grid's y dimension is at most 16384)
 }
 
+// What one filtered output needs, from its spec alone (host arithmetic: the single call, the call of several outputs and the
+// work-map hooks all plan with this).  Its scratch, in 32-bit words:
+// [first_x, count_x: out_w ints each][first_y, count_y: out_h][wx: out_w * stride_x floats][wy: out_h * stride_y]
+struct OutputPlan {
+        unsigned stride_x, stride_y;    // weights per output column / row
+        size_t words;
+        unsigned lanes, slots, rows;    // the tile
+        unsigned gx, gy;                // its own grid: tile columns x row groups; a workgroup is 4 wavefronts, one above the other, of one tile
+};
+static OutputPlan plan_output(const j2p_resample &r)
+{
+        OutputPlan p;
+        p.stride_x = filter_stride(r.filter, r.box_w, r.out_w);
+        p.stride_y = filter_stride(r.filter, r.box_h, r.out_h);
+        p.words = 2 * ((size_t)r.out_w + r.out_h) + (size_t)r.out_w * p.stride_x + (size_t)r.out_h * p.stride_y;
+        filter_tile(r.out_w, r.out_h, &p.lanes, &p.slots, &p.rows);
+        const unsigned tile = p.lanes * p.slots;
+        p.gx = (r.out_w + tile - 1) / tile;
+        p.gy = ((r.out_h + p.rows - 1) / p.rows + 3) / 4;
+        return p;
+}
+// the arguments of both kernels for an output whose scratch starts at `ints`
+static void bind_output(const j2p_resample &r, const OutputPlan &p, int *ints, FilterAxis &ax, FilterAxis &ay, FilterGeom &g)
+{
+        ax.box = r.box_w;
+        ax.out = r.out_w;
+        ax.stride = p.stride_x;
+        ay.box = r.box_h;
+        ay.out = r.out_h;
+        ay.stride = p.stride_y;
+        ax.first = ints;
+        ax.count = ints + ax.out;
+        ay.first = ints + 2 * (size_t)ax.out;
+        ay.count = ay.first + ay.out;
+        ax.weights = reinterpret_cast<float *>(ay.count + ay.out);
+        ay.weights = ax.weights + (size_t)ax.out * ax.stride;
+        g.box_x = r.box_x;
+        g.box_y = r.box_y;
+        g.out_w = r.out_w;
+        g.out_h = r.out_h;
+        g.stride_x = ax.stride;
+        g.stride_y = ay.stride;
+        g.first_x = ax.first;
+        g.count_x = ax.count;
+        g.first_y = ay.first;
+        g.count_y = ay.count;
+        g.wx = ax.weights;
+        g.wy = ay.weights;
+        g.lanes = p.lanes;
+        g.slots = p.slots;
+        g.rows = p.rows;
+}
+
 int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_resample *r,
                                    const j2p_tensor *out)
 {
@@ -371,47 +424,179 @@ int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane
         j2p_solver_view s0;
         if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
         DeviceGuard guard(s0.device);
-        // the scratch: [first_x, count_x: out_w ints each][first_y, count_y: out_h][wx: out_w * stride_x floats][wy: out_h * stride_y]
-        FilterAxis ax, ay;
-        ax.box = r->box_w;
-        ax.out = r->out_w;
-        ax.stride = filter_stride(r->filter, r->box_w, r->out_w);
-        ay.box = r->box_h;
-        ay.out = r->out_h;
-        ay.stride = filter_stride(r->filter, r->box_h, r->out_h);
-        const size_t nwx = (size_t)ax.out * ax.stride, nwy = (size_t)ay.out * ay.stride;
-        const size_t words = 2 * ((size_t)ax.out + ay.out) + nwx + nwy;
+        const OutputPlan p = plan_output(*r);
         void *scratch = nullptr;
-        if(const int rc = j2p_solver_scratch(planes[0].solver, words * 4, &scratch); rc != J2P_OK) { return rc; }
-        int *const ints = static_cast<int *>(scratch);
-        ax.first = ints;
-        ax.count = ints + ax.out;
-        ay.first = ints + 2 * (size_t)ax.out;
-        ay.count = ay.first + ay.out;
-        ax.weights = reinterpret_cast<float *>(ay.count + ay.out);
-        ay.weights = ax.weights + nwx;
+        if(const int rc = j2p_solver_scratch(planes[0].solver, p.words * 4, &scratch); rc != J2P_OK) { return rc; }
+        FilterAxis ax, ay;
+        FilterGeom g;
+        bind_output(*r, p, static_cast<int *>(scratch), ax, ay, g);
         const unsigned most = ax.out > ay.out ? ax.out : ay.out;
         hipLaunchKernelGGL(k_filter_taps, dim3((most + 255) / 256, 2), dim3(256), 0, s0.stream, r->filter, ax, ay);
-        FilterGeom g;
-        g.box_x = r->box_x;
-        g.box_y = r->box_y;
-        g.out_w = r->out_w;
-        g.out_h = r->out_h;
-        g.stride_x = ax.stride;
-        g.stride_y = ay.stride;
-        g.first_x = ax.first;
-        g.count_x = ax.count;
-        g.first_y = ay.first;
-        g.count_y = ay.count;
-        g.wx = ax.weights;
-        g.wy = ay.weights;
-        filter_tile(r->out_w, r->out_h, &g.lanes, &g.slots, &g.rows);
-        // a workgroup: 4 wavefronts, one above the other, of one tile
-        const unsigned tile = g.lanes * g.slots, gx = (r->out_w + tile - 1) / tile, gy = ((r->out_h + g.rows - 1) / g.rows + 3) / 4;
-        hipLaunchKernelGGL(kFilteredKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(gx, gy), dim3(256), 0, s0.stream, ptr[0], stride[0], ptr[1],
+        hipLaunchKernelGGL(kFilteredKernels[nplane == 3 ? 0 : 1][out->dtype], dim3(p.gx, p.gy), dim3(256), 0, s0.stream, ptr[0], stride[0], ptr[1],
                            stride[1], ptr[2], stride[2], g, o);
         const hipError_t e = hipGetLastError();
         if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensor_resampled: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+// ---- several filtered outputs in one call: k_filter_taps_outputs, k_to_tensors_filtered ----
+static_assert(J2P_MAX_OUTPUTS == kMaxOutputs, "the kernels' tables hold the header's number of outputs");
+using FilteredOutputsKernel = void (*)(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterOutputs);
+#define J2P_FILTERED_ROW(NPLANE) \
+        {k_to_tensors_filtered<NPLANE, kDtypeU8>, k_to_tensors_filtered<NPLANE, kDtypeF16>, k_to_tensors_filtered<NPLANE, kDtypeBF16>, k_to_tensors_filtered<NPLANE, kDtypeF32>}
+static const FilteredOutputsKernel kFilteredOutputsKernels[2][4] = {J2P_FILTERED_ROW(3), J2P_FILTERED_ROW(1)};   // [three planes / one][dtype]
+#undef J2P_FILTERED_ROW
+
+// The work of a call of n outputs, from the specs and the dtypes alone: every output's plan as the single call makes it — the
+// same tile: whether a tile chosen from the call's total does better has not been measured — its place in the scratch (one
+// after the other: the size is the sum), and the sampling launches: one per dtype present, in ascending dtype code, each
+// with its outputs in list order and the prefix table of their workgroups.
+struct CallPlan {
+        OutputPlan out[kMaxOutputs];
+        size_t word0[kMaxOutputs], words;
+        unsigned launch_of[kMaxOutputs];
+        unsigned nlaunch;
+        int dtype[4];
+        unsigned count[4], member[4][kMaxOutputs], end[4][kMaxOutputs];
+};
+static void plan_call(unsigned n, const j2p_resample specs[], const int dtypes[], CallPlan &c)
+{
+        c.words = 0;
+        for(unsigned i = 0; i < n; i++) {
+                c.out[i] = plan_output(specs[i]);
+                c.word0[i] = c.words;
+                c.words += c.out[i].words;
+        }
+        c.nlaunch = 0;
+        for(int d = J2P_DTYPE_U8; d <= J2P_DTYPE_F32; d++) {
+                unsigned m = 0, workgroups = 0;
+                for(unsigned i = 0; i < n; i++) {
+                        if(dtypes[i] != d) { continue; }
+                        workgroups += c.out[i].gx * c.out[i].gy;          // (16 outputs of at most 2^20 workgroups each)
+                        c.member[c.nlaunch][m] = i;
+                        c.end[c.nlaunch][m] = workgroups;
+                        c.launch_of[i] = c.nlaunch;
+                        m++;
+                }
+                if(m == 0) { continue; }
+                c.dtype[c.nlaunch] = d;
+                c.count[c.nlaunch] = m;
+                c.nlaunch++;
+        }
+}
+
+int j2p_planes_to_tensors_resampled(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, unsigned n, const j2p_output outs[])
+{
+        if(!planes || !outs) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(n == 0 || n > J2P_MAX_OUTPUTS) { return j2p_fail(J2P_EINVAL, "to_tensors: %u outputs (1..%d)", n, J2P_MAX_OUTPUTS); }
+        if(n == 1) { return j2p_planes_to_tensor_resampled(planes, nplane, w, h, &outs[0].r, &outs[0].t); }
+        // every check of every output, before anything is queued
+        const float *ptr[3];
+        unsigned stride[3];
+        TensorOut o[kMaxOutputs];
+        j2p_solver_view s0;
+        for(unsigned i = 0; i < n; i++) {
+                if(const char *why = j2p_resample_error(&outs[i].r, w, h)) { return j2p_fail(J2P_EINVAL, "to_tensors: output %u: %s", i, why); }
+        }
+        for(unsigned i = 0; i < n; i++) {
+                if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, &outs[i].t, ptr, stride, o[i], s0); rc != J2P_OK) { return rc; }
+        }
+        DeviceGuard guard(s0.device);
+        j2p_resample specs[kMaxOutputs];
+        int dtypes[kMaxOutputs];
+        for(unsigned i = 0; i < n; i++) {
+                specs[i] = outs[i].r;
+                dtypes[i] = outs[i].t.dtype;
+        }
+        CallPlan c;
+        plan_call(n, specs, dtypes, c);
+        void *scratch = nullptr;
+        if(const int rc = j2p_solver_scratch(planes[0].solver, c.words * 4, &scratch); rc != J2P_OK) { return rc; }
+        FilterAxes axes;
+        FilterGeom g[kMaxOutputs];
+        axes.n = 2 * n;
+        unsigned tap_workgroups = 0;
+        for(unsigned i = 0; i < n; i++) {
+                bind_output(outs[i].r, c.out[i], static_cast<int *>(scratch) + c.word0[i], axes.axis[2 * i], axes.axis[2 * i + 1], g[i]);
+                for(unsigned a = 2 * i; a < 2 * i + 2; a++) {
+                        axes.filter[a] = outs[i].r.filter;
+                        tap_workgroups += (axes.axis[a].out + 255) / 256;
+                        axes.end[a] = tap_workgroups;
+                }
+        }
+        hipLaunchKernelGGL(k_filter_taps_outputs, dim3(tap_workgroups), dim3(256), 0, s0.stream, axes);
+        for(unsigned l = 0; l < c.nlaunch; l++) {
+                FilterOutputs f;
+                f.n = c.count[l];
+                for(unsigned m = 0; m < f.n; m++) {
+                        const unsigned i = c.member[l][m];
+                        f.end[m] = c.end[l][m];
+                        f.columns[m] = c.out[i].gx;
+                        f.g[m] = g[i];
+                        f.o[m] = o[i];
+                }
+                hipLaunchKernelGGL(kFilteredOutputsKernels[nplane == 3 ? 0 : 1][c.dtype[l]], dim3(f.end[f.n - 1]), dim3(256), 0, s0.stream, ptr[0],
+                                   stride[0], ptr[1], stride[1], ptr[2], stride[2], f);
+        }
+        const hipError_t e = hipGetLastError();
+        if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "planes_to_tensors_resampled: %s", hipGetErrorString(e)); }
+        return J2P_OK;
+}
+
+// what both hooks check: the specs as the call checks them, and the dtype codes
+static int debug_outputs_check(unsigned w, unsigned h, unsigned n, const j2p_resample specs[], const int dtypes[])
+{
+        if(!specs || !dtypes) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(n == 0 || n > J2P_MAX_OUTPUTS) { return j2p_fail(J2P_EINVAL, "to_tensors: %u outputs (1..%d)", n, J2P_MAX_OUTPUTS); }
+        for(unsigned i = 0; i < n; i++) {
+                if(const char *why = j2p_resample_error(&specs[i], w, h)) { return j2p_fail(J2P_EINVAL, "to_tensors: output %u: %s", i, why); }
+                if(dtypes[i] < J2P_DTYPE_U8 || dtypes[i] > J2P_DTYPE_F32) { return j2p_fail(J2P_EINVAL, "to_tensors: output %u: unknown dtype %d", i, dtypes[i]); }
+        }
+        return J2P_OK;
+}
+
+int j2p_debug_outputs_plan(unsigned w, unsigned h, unsigned n, const j2p_resample specs[], const int dtypes[], unsigned tiles[], unsigned grids[],
+                           unsigned launch_of[], unsigned *nlaunch, int launch_dtype[4], unsigned launch_workgroups[4])
+{
+        if(!tiles || !grids || !launch_of || !nlaunch || !launch_dtype || !launch_workgroups) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const int rc = debug_outputs_check(w, h, n, specs, dtypes); rc != J2P_OK) { return rc; }
+        CallPlan c;
+        plan_call(n, specs, dtypes, c);
+        for(unsigned i = 0; i < n; i++) {
+                tiles[3 * i] = c.out[i].lanes;
+                tiles[3 * i + 1] = c.out[i].slots;
+                tiles[3 * i + 2] = c.out[i].rows;
+                grids[2 * i] = c.out[i].gx;
+                grids[2 * i + 1] = c.out[i].gy;
+                launch_of[i] = c.launch_of[i];
+        }
+        *nlaunch = c.nlaunch;
+        for(unsigned l = 0; l < c.nlaunch; l++) {
+                launch_dtype[l] = c.dtype[l];
+                launch_workgroups[l] = c.end[l][c.count[l] - 1];
+        }
+        return J2P_OK;
+}
+
+int j2p_debug_outputs_workgroups(unsigned w, unsigned h, unsigned n, const j2p_resample specs[], const int dtypes[], unsigned launch,
+                                 unsigned first, unsigned count, unsigned map[])
+{
+        if(!map && count) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const int rc = debug_outputs_check(w, h, n, specs, dtypes); rc != J2P_OK) { return rc; }
+        CallPlan c;
+        plan_call(n, specs, dtypes, c);
+        if(launch >= c.nlaunch) { return j2p_fail(J2P_EINVAL, "to_tensors: launch %u of %u", launch, c.nlaunch); }
+        const unsigned total = c.end[launch][c.count[launch] - 1];
+        if(first > total || count > total - first) { return j2p_fail(J2P_EINVAL, "to_tensors: workgroups [%u, %u + %u) of %u", first, first, count, total); }
+        for(unsigned k = 0; k < count; k++) {
+                // what k_to_tensors_filtered's workgroup first + k does with its table
+                unsigned local;
+                const unsigned m = output_of_workgroup(c.end[launch], c.count[launch], first + k, &local);
+                const unsigned columns = c.out[c.member[launch][m]].gx, by = local / columns;
+                map[3 * k] = c.member[launch][m];
+                map[3 * k + 1] = local - by * columns;
+                map[3 * k + 2] = by;
+        }
         return J2P_OK;
 }
 

@@ -1,6 +1,6 @@
 // jpeg2png_amd — gfx950 device code of the output stage: what turns solved planes into samples (k_to_samples), tensor
-// elements (k_to_tensor, k_to_tensor_resized, k_filter_taps + k_to_tensor_filtered) and quantised JPEG coefficients
-// (k_quantise_blocks).  A device translation
+// elements (k_to_tensor, k_to_tensor_resized, k_filter_taps + k_to_tensor_filtered, and for several outputs in one call
+// k_filter_taps_outputs + k_to_tensors_filtered) and quantised JPEG coefficients (k_quantise_blocks).  A device translation
 // unit of its own (j2p_output.hip), so that an edit here does not recompile the solver's kernels (j2p_kernels.hip.h), with
 // which it shares only j2p_dct.hip.h.  Compiled with the same flags: -ffp-contract=off, no fast-math, correctly rounded `/`.
 #pragma once
@@ -870,5 +870,250 @@ template __global__ void k_quantise_blocks<1, 1>(const float *, unsigned, unsign
 template __global__ void k_quantise_blocks<2, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
 template __global__ void k_quantise_blocks<2, 1>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
 template __global__ void k_quantise_blocks<1, 2>(const float *, unsigned, unsigned, unsigned, unsigned, QuantSteps, int16_t *);
+
+// ---------------------------------------------------------------------------
+// Several filtered outputs in one call (j2p_planes_to_tensors_resampled): one launch for the taps of every axis of every
+// output, one sampling launch per dtype.  Kernels of their own BESIDE k_filter_taps and k_to_tensor_filtered, at the end of the
+// code object, and the tile's text a second time: with one device function under both sampling kernels the single call's
+// kernel came out of the compiler with another schedule and register count, and its time moved by -5 to +6 % depending on the
+// shape, where two builds of one source differ by 0.5 % at most.  filtered_tile IS
+// k_to_tensor_filtered's body with the tile column and the row group as arguments — the same staging, the same ascending
+// chunk and row order, the same bits; a change to one belongs in the other (tests/test_outputs_gpu.py compares their bits).
+// ---------------------------------------------------------------------------
+// the taps of index X of one axis into its arrays
+__device__ __forceinline__ void filter_axis_taps(int filter, const FilterAxis &a, unsigned X)
+{
+        float *const w = a.weights + (size_t)X * a.stride;
+        unsigned first = 0, count = 0;
+        filter_taps(filter, a.box, a.out, X, &first, &count, a.stride, [&](unsigned t, float f) { w[t] = f; });
+        a.first[X] = (int)first;
+        a.count[X] = (int)(count < a.stride ? count : a.stride);         // (never more: see filter_stride)
+}
+
+
+// Several outputs in one launch (j2p_planes_to_tensors_resampled): the launch's workgroups are those of the outputs' own
+// launches one after the other, end[i] the number of workgroups of outputs 0..i.  The output of workgroup `wg` and the
+// workgroup's index among that output's own: host and device compile this text (j2p_debug_outputs_workgroups).
+constexpr int kMaxOutputs = 16;                                  // J2P_MAX_OUTPUTS (checked in j2p_output.hip)
+__host__ __device__ inline unsigned output_of_workgroup(const unsigned *end, unsigned n, unsigned wg, unsigned *local)
+{
+        unsigned i = 0;
+        while(i + 1 < n && wg >= end[i]) { i++; }
+        *local = wg - (i ? end[i - 1] : 0);
+        return i;
+}
+
+// the taps of every axis of every output of a call in one launch: 2 * outputs axes, each with its filter and the workgroups
+// (of 256 indices) it needs — no workgroup without work
+struct FilterAxes {
+        unsigned n;                                      // axes: at most 2 * kMaxOutputs
+        unsigned end[2 * kMaxOutputs];
+        int filter[2 * kMaxOutputs];
+        FilterAxis axis[2 * kMaxOutputs];
+};
+__global__ __launch_bounds__(256) void k_filter_taps_outputs(FilterAxes axes)
+{
+        unsigned local;
+        const unsigned i = output_of_workgroup(axes.end, axes.n, blockIdx.x, &local);
+        const FilterAxis &a = axes.axis[i];
+        const unsigned X = local * 256 + threadIdx.x;
+        if(X >= a.out) { return; }
+        filter_axis_taps(axes.filter[i], a, X);
+}
+
+// one workgroup's work: tile column bx, row group by (4 wavefronts, one above the other) of the output g, o
+template <int NPLANE, int DTYPE>
+__device__ __forceinline__ void filtered_tile(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp, unsigned crs,
+                                              const FilterGeom &g, const TensorOut &o, unsigned bx, unsigned by)
+{
+        static_assert(NPLANE == 1 || NPLANE == 3, "greyscale or RGB");
+        constexpr int kRounds = kResizeChunk / 256;
+        using E = TensorElement<DTYPE>;
+        using Raw = typename E::Raw;
+        __shared__ float stage[4][NPLANE][kResizeLds];
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned Yb = (by * 4 + (unsigned)wave) * g.rows;           // this wavefront's output rows: [Yb, Yb + nrow)
+        if(Yb >= g.out_h) { return; }                                    // (no workgroup barrier in this kernel)
+        const unsigned nrow = g.out_h - Yb < g.rows ? g.out_h - Yb : g.rows;
+        float (*const lds)[kResizeLds] = stage[wave];
+        const unsigned tile = g.lanes * g.slots;
+        const unsigned X0 = bx * tile;                                   // (the grid has no tile beyond out_w)
+        const unsigned ncol = g.out_w - X0 < tile ? g.out_w - X0 : tile;
+        // the taps of the lane's columns X0 + p * lanes + lane: box columns [fx, fx + nx), weights from wp
+        int fx[kResizeSlots], nx[kResizeSlots];
+        const float *wp[kResizeSlots];
+        bool has[kResizeSlots];
+#pragma unroll
+        for(int p = 0; p < kResizeSlots; p++) {
+                has[p] = (unsigned)p < g.slots && (unsigned)lane < g.lanes && (unsigned)p * g.lanes + (unsigned)lane < ncol;
+                const unsigned X = has[p] ? X0 + (unsigned)p * g.lanes + (unsigned)lane : X0;
+                fx[p] = g.first_x[X];
+                nx[p] = has[p] ? g.count_x[X] : 0;
+                wp[p] = g.wx + (size_t)X * g.stride_x;
+        }
+        // the tile's segment of a source row, in canvas columns: [c_begin, c_last], c_begin a multiple of 4 (first and
+        // first + count never decrease from one output index to the next)
+        const unsigned Xl = X0 + ncol - 1;
+        const int c_last = (int)g.box_x + g.first_x[Xl] + g.count_x[Xl] - 1;
+        const int c_begin = ((int)g.box_x + g.first_x[X0]) & ~3;
+        // the windows of the wavefront's rows: box rows [fy, fy + ny), the same in every lane; and the source rows of all of
+        // them, [j_begin, j_end] (windows never move backwards)
+        int fy[kFilterRows], ny[kFilterRows];
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+                const bool valid = (unsigned)q < nrow;
+                fy[q] = g.first_y[valid ? Yb + (unsigned)q : Yb];
+                ny[q] = valid ? g.count_y[Yb + (unsigned)q] : 0;
+        }
+        const int j_begin = g.first_y[Yb], j_end = g.first_y[Yb + nrow - 1] + g.count_y[Yb + nrow - 1] - 1;
+        Raw *const data = static_cast<Raw *>(o.data);
+
+        // the 16-byte loads of chunk c0 of source row j, into registers: issued one chunk ahead of their use
+        float4 ld[kRounds][NPLANE];
+#pragma unroll
+        for(int u = 0; u < kRounds; u++) {
+#pragma unroll
+                for(int k = 0; k < NPLANE; k++) { ld[u][k] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        }
+        const auto issue = [&](int j, int c0) {
+                const size_t row = (size_t)g.box_y + (size_t)j;
+#pragma unroll
+                for(int u = 0; u < kRounds; u++) {
+                        const int c = c0 + u * 256 + lane * 4;
+                        if(c <= c_last) {
+                                ld[u][0] = *reinterpret_cast<const float4 *>(yp + row * ys + c);
+                                if constexpr(NPLANE == 3) {
+                                        ld[u][1] = *reinterpret_cast<const float4 *>(cbp + row * cbs + c);
+                                        ld[u][2] = *reinterpret_cast<const float4 *>(crp + row * crs + c);
+                                }
+                        }
+                }
+        };
+
+        float acc[kFilterRows][kResizeSlots][NPLANE];
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) { acc[q][p][k] = 0.f; }
+                }
+        }
+        issue(j_begin, c_begin);
+        for(int j = j_begin; j <= j_end; j++) {
+                // r_j of every column of the lane: the row's chunks, left to right
+                float r[kResizeSlots][NPLANE];
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) { r[p][k] = 0.f; }
+                }
+                for(int c0 = c_begin; c0 <= c_last; c0 += kResizeChunk) {
+#pragma unroll
+                        for(int u = 0; u < kRounds; u++) {
+                                const int at = u * 256 + lane * 4;
+                                if(c0 + at <= c_last) {
+                                        const float yin[4] = {ld[u][0].x, ld[u][0].y, ld[u][0].z, ld[u][0].w};
+                                        const float4 cb4 = ld[u][NPLANE == 3 ? 1 : 0], cr4 = ld[u][NPLANE == 3 ? 2 : 0];   // (one plane: not looked at)
+                                        const float cbin[4] = {cb4.x, cb4.y, cb4.z, cb4.w}, crin[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+#pragma unroll
+                                        for(int q = 0; q < 4; q++) {
+                                                const int idx = resize_lds_index(at + q);
+                                                clamped_pixel<NPLANE>(yin[q], cbin[q], crin[q], [&](int k, float x) { lds[k][idx] = x; });
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        // the next chunk's loads fly while this one's taps are walked
+                        if(c0 + kResizeChunk <= c_last) { issue(j, c0 + kResizeChunk); }
+                        else if(j < j_end) { issue(j + 1, c_begin); }
+                        const int rel0 = c0 - (int)g.box_x;              // the chunk's first column relative to the box (>= -3)
+#pragma unroll
+                        for(int p = 0; p < kResizeSlots; p++) {
+                                if(!has[p]) { continue; }
+                                const int i0 = fx[p] > rel0 ? fx[p] : rel0;
+                                const int last = fx[p] + nx[p] - 1;
+                                const int i1 = last < rel0 + kResizeChunk - 1 ? last : rel0 + kResizeChunk - 1;
+                                for(int i = i0; i <= i1; i++) {          // (none of this column's taps in this chunk: i0 > i1)
+                                        const float a = wp[p][i - fx[p]];
+                                        const int idx = resize_lds_index(i - rel0);
+#pragma unroll
+                                        for(int k = 0; k < NPLANE; k++) {
+                                                const float t = a * lds[k][idx];
+                                                r[p][k] = r[p][k] + t;
+                                        }
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();                 // the next chunk is staged over this one
+                }
+                // every output row of the wavefront whose window holds the row takes it with its weight
+#pragma unroll
+                for(int q = 0; q < kFilterRows; q++) {
+                        if(j < fy[q] || j >= fy[q] + ny[q]) { continue; }     // (wavefront-uniform; ny is 0 beyond nrow)
+                        const float b = g.wy[(size_t)(Yb + (unsigned)q) * g.stride_y + (unsigned)(j - fy[q])];
+#pragma unroll
+                        for(int p = 0; p < kResizeSlots; p++) {
+#pragma unroll
+                                for(int k = 0; k < NPLANE; k++) {
+                                        const float t = b * r[p][k];
+                                        acc[q][p][k] = acc[q][p][k] + t;
+                                }
+                        }
+                }
+        }
+#pragma unroll
+        for(int q = 0; q < kFilterRows; q++) {
+                if((unsigned)q >= nrow) { continue; }
+                const long long rowo = (long long)(Yb + (unsigned)q) * o.stride_y;
+#pragma unroll
+                for(int p = 0; p < kResizeSlots; p++) {
+                        if(!has[p]) { continue; }
+                        const long long X = (long long)(X0 + (unsigned)p * g.lanes + (unsigned)lane);
+#pragma unroll
+                        for(int k = 0; k < NPLANE; k++) {
+                                float m = acc[q][p][k];
+                                m = m > 0.f ? m : 0.f;
+                                m = m < 255.f ? m : 255.f;
+                                data[(long long)k * o.stride_c + rowo + X * o.stride_x] = (Raw)E::make(m, o.scale[k], o.bias[k]);
+                        }
+                }
+        }
+}
+// Several outputs of one dtype in one launch: a grid of exactly the workgroups the outputs' own launches have, flattened.  A
+// workgroup finds its output in the prefix table and from its index among that output's own the tile column (fastest, as
+// blockIdx.x is) and the row group; then it does what k_to_tensor_filtered's workgroup of that place does — same staging, same
+// ascending chunk and row order, same bits.  The views of one call differ in size by 5x and more: a grid sized for the largest
+// would mostly exit early, this one launches no workgroup without work.  Geometry and destinations are kernel arguments (16 of
+// each, 2.4 KB of the 4 KB there are): nothing is copied to the device for them, and the workgroup's own pair is read with
+// scalar loads at a uniform index.
+struct FilterOutputs {
+        unsigned n;
+        unsigned end[kMaxOutputs];                       // workgroups of outputs 0..i
+        unsigned columns[kMaxOutputs];                   // tile columns of output i: its own grid's x dimension
+        FilterGeom g[kMaxOutputs];
+        TensorOut o[kMaxOutputs];
+};
+static_assert(sizeof(FilterOutputs) + 6 * 8 <= 4096, "kernel arguments: 4 KB");
+
+template <int NPLANE, int DTYPE>
+__global__ __launch_bounds__(256) void k_to_tensors_filtered(const float *yp, unsigned ys, const float *cbp, unsigned cbs, const float *crp,
+                                                             unsigned crs, FilterOutputs a)
+{
+        unsigned local;
+        const unsigned i = output_of_workgroup(a.end, a.n, blockIdx.x, &local);
+        const unsigned columns = a.columns[i], by = local / columns;
+        filtered_tile<NPLANE, DTYPE>(yp, ys, cbp, cbs, crp, crs, a.g[i], a.o[i], local - by * columns, by);
+}
+#define J2P_FILTERED_OUTPUTS_KERNELS(NPLANE)                                                                                                  \
+        template __global__ void k_to_tensors_filtered<NPLANE, kDtypeU8>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterOutputs);   \
+        template __global__ void k_to_tensors_filtered<NPLANE, kDtypeF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterOutputs);  \
+        template __global__ void k_to_tensors_filtered<NPLANE, kDtypeBF16>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterOutputs); \
+        template __global__ void k_to_tensors_filtered<NPLANE, kDtypeF32>(const float *, unsigned, const float *, unsigned, const float *, unsigned, FilterOutputs);
+J2P_FILTERED_OUTPUTS_KERNELS(3)
+J2P_FILTERED_OUTPUTS_KERNELS(1)
+#undef J2P_FILTERED_OUTPUTS_KERNELS
 
 }  // namespace j2p
