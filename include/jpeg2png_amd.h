@@ -746,6 +746,64 @@ int j2p_sqrt_exhaustive(int device, unsigned long long *rsq_mismatches, unsigned
  * report[0] = number of mismatches, report[1..8] = the first offenders' bit patterns. */
 int j2p_division_exhaustive(int device, int pass, unsigned first, unsigned count, unsigned long long report[9]);
 
+/* Sample input: a solver from DECODED 8-bit planes — what the GPU's hardware JPEG decoder, ffmpeg (`yuvj420p`) or libjpeg's raw-data
+ * mode hand over: Y, Cb, Cr at the file's own sampling — instead of the quantised coefficients only a jpeg_read_coefficients caller
+ * has.  The library recomputes the coefficients from the samples on the device.
+ *
+ * planes[c] gives w, h, w_samp, h_samp and quant_table as for j2p_solver_create; planes[c].data and planes[c].fdata must both be NULL
+ * (J2P_EINVAL otherwise: no caller shall believe they are used too).  Whole canvas only: there is no band argument.  samples[c]
+ * describes channel c's 8-bit samples: `data` points into DEVICE memory of `device` or into HOST memory (hipPointerGetAttributes
+ * decides; managed memory and another GPU's memory are J2P_EINVAL, as for j2p_tensor), w x h is what is present of the coefficient
+ * plane (0 < w <= plane.w, 0 < h <= plane.h), and the strides are in bytes, each at least 1 (stride_x 2: one half of an interleaved
+ * NV12 chroma plane).
+ *
+ * The definition.  For channel c and the coefficient plane's sample (X, Y), 0 <= X < plane.w, 0 <= Y < plane.h:
+ *   s(X, Y) = data[min(Y, h - 1) * stride_y + min(X, w - 1) * stride_x]   — the last column and row replicated, which is how libjpeg's
+ *             encoder pads and the only thing a caller who has the visible samples alone can do;
+ *   v = (float)s - 128.f (exact);
+ *   every 8x8 block of v goes through dct8x8s (ooura/dct.c:98-130, the transform j2p_dct8x8_blocks exposes);
+ *   each coefficient is divided by (float)quant_table[j] as the correctly rounded f32 quotient, then rintf (ties to even).
+ * No clamp: |v| <= 128 and the transform's basis functions have an L1 norm of at most 8, so the result lies in [-1024, 1016] by
+ * construction (the +-1023 of j2p_planes_to_coefficients is libjpeg's limit for WRITING, not a property of the data).  These int16
+ * values are the solver's coefficients: from there on the solver is, bit for bit, the one j2p_solver_create makes from the same
+ * values with fdata == NULL — the device decode for x_0, the narrowing to bytes where they fit (j2p_solver_coefficient_bytes), the
+ * wide-footprint choice.  j2p_solver_reset works as for any solver: the coefficients are resident.
+ *
+ * Recovery.  A decoded sample is the inverse DCT of the dequantised coefficients rounded to 8 bits, so it is off by at most 1/2, and
+ * a per-sample error of at most e moves a coefficient by at most 8 * e: the quantised coefficient the file held is recovered EXACTLY
+ * when its step exceeds 8 and no sample of its block was clipped at 0 or 255.  j2p_solver_clipped_samples returns how many of the
+ * w x h samples present of channel c were 0 or 255 (counted by the same kernel; J2P_ESTATE for a solver not made from samples).  Where
+ * that count is not 0, or a step is 8 or less, recovery is not guaranteed (measured: still exact down to steps of 5, quality 75;
+ * mismatches by one step start at quality 90) — the library refuses nothing on account of it.
+ *
+ * Memory and ordering.  Device samples are read in place by a kernel on the solver's stream: the caller orders their producer before
+ * the call (a `stream` that is the producer's, or a wait).  Host samples are staged through a buffer the solver owns anyway, one
+ * hipMemcpy2DAsync per channel (of rows (w - 1) * stride_x + 1 bytes long: J2P_EINVAL when a stride_x above 4 or so makes them larger
+ * than the canvas's floats).  Either way create returns after the stream has been synchronised: the samples may be reused at once.
+ * Refused before a device is touched or anything is queued (J2P_EINVAL): samples or a data NULL, w or h zero or beyond the plane, a
+ * stride below 1, planes[c].data or .fdata set, and everything j2p_solver_create refuses. */
+typedef struct j2p_samples {
+        const uint8_t *data;               /* 8-bit samples: DEVICE memory of the solver's device, or HOST memory */
+        unsigned w, h;                     /* samples present: 0 < w <= plane.w, 0 < h <= plane.h */
+        ptrdiff_t stride_y, stride_x;      /* in bytes, >= 1 (stride_x 2: one half of an interleaved NV12 chroma plane) */
+} j2p_samples;
+int j2p_solver_create_from_samples(j2p_solver **out, int device, void *stream, unsigned nchannel,
+                                   const j2p_plane planes[], const j2p_samples samples[],
+                                   float weight, const float pweight[], unsigned iterations);
+/* diagnostics: the quantised coefficients channel c of ANY solver holds — its own block rows, block-major [rows / 8][w / 8][64],
+ * natural order, as j2p_plane.data.  Waits for the solver's stream. */
+int j2p_solver_download_coefficients(j2p_solver *s, unsigned c, int16_t *out_host);
+int j2p_solver_clipped_samples(const j2p_solver *s, unsigned c, unsigned long long *count);
+/* a batch job whose solvers are made from samples: samples[c] belongs to job->planes[c], whose data and fdata are NULL.  The samples
+ * are copied and travel next to the job, never in it (j2p_job keeps its layout).  n / outs are those of j2p_batch_submit_outputs; with
+ * n == 0 or outs == NULL the job's own output fields apply, so every output form a coefficient job has is available.  Device samples
+ * pin the job to a worker of their GPU, as tensor outputs do (all channels' on one GPU of the batch, and the same as the output
+ * tensors': J2P_EINVAL at submit otherwise, as for everything j2p_solver_create_from_samples refuses before it touches a device);
+ * they must be complete when the job is submitted — the workers' streams know nothing of the caller's — and, like host samples,
+ * stay valid until j2p_batch_wait.  Not with `tile`.  samples == NULL: j2p_batch_submit_outputs / j2p_batch_submit. */
+int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[],
+                             unsigned n, const j2p_output outs[], int *ticket);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,12 @@ class _COutput(ctypes.Structure):
 J2P_MAX_OUTPUTS = 16
 
 
+class _CSamples(ctypes.Structure):
+    """j2p_samples: one channel's 8-bit samples in device or host memory (strides in bytes)"""
+    _fields_ = [("data", ctypes.c_void_p), ("w", ctypes.c_uint), ("h", ctypes.c_uint),
+                ("stride_y", ctypes.c_ssize_t), ("stride_x", ctypes.c_ssize_t)]
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -127,6 +133,7 @@ C_ABI_SYMBOLS = [
     "j2p_debug_build", "j2p_debug_grad_items", "j2p_debug_norm_plan", "j2p_experiments_build", "j2p_solver_debug_violations", "j2p_solver_trace", "j2p_division_exhaustive",
     "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint", "j2p_solver_shares_state", "j2p_solver_arena_bytes",
     "j2p_solver_debug_partials", "j2p_norm_selftest", "j2p_norm_selftest_bands",
+    "j2p_solver_create_from_samples", "j2p_solver_download_coefficients", "j2p_solver_clipped_samples", "j2p_batch_submit_samples",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
@@ -301,6 +308,15 @@ def _bind(path):
                                                ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint)]
         lib.j2p_debug_outputs_workgroups.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CResample),
                                                      ctypes.POINTER(ctypes.c_int), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p]
+    if hasattr(lib, "j2p_solver_create_from_samples"):
+        # (as above: an earlier commit's build has no sample input)
+        lib.j2p_solver_create_from_samples.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint,
+                                                       ctypes.POINTER(_CPlane), ctypes.POINTER(_CSamples), ctypes.c_float,
+                                                       ctypes.POINTER(ctypes.c_float), ctypes.c_uint]
+        lib.j2p_solver_download_coefficients.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
+        lib.j2p_solver_clipped_samples.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong)]
+        lib.j2p_batch_submit_samples.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.c_uint,
+                                                 ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -632,9 +648,15 @@ class Solver:
         h = ctypes.c_void_p()
         _check(lib.j2p_solver_create(ctypes.byref(h), device, stream, self.nch, cpl, float(weight), pw,
                                      int(iterations), b, 1 if band_local_arrays else 0))
+        del keep
+        self._geom = [(int(p.w), int(p.h)) for p in planes]
+        self._adopt(h, device)
+
+    def _adopt(self, h, device):
+        """the rest of construction, once the C solver exists"""
+        lib = self._lib
         self._h = h
         self.device = int(device)
-        del keep
         W, H = ctypes.c_uint(), ctypes.c_uint()
         _check(lib.j2p_solver_canvas(h, ctypes.byref(W), ctypes.byref(H)))
         self.W, self.H = W.value, H.value
@@ -642,10 +664,74 @@ class Solver:
         _check(lib.j2p_solver_band(h, ctypes.byref(r0), ctypes.byref(r1)))
         self.row_begin, self.row_end = r0.value, r1.value
 
+    @classmethod
+    def from_samples(cls, samples, planes, weight, pweight, iterations, device=0, stream=None):
+        """A solver made from decoded 8-bit planes instead of coefficients (j2p_solver_create_from_samples): what a hardware JPEG
+        decoder, PyAV (`yuvj420p`) or libjpeg's raw-data mode hands over.  planes: Plane-likes with w, h, w_samp, h_samp and
+        quant_table, data=None (jpeg_header(...)["planes"] are such).  samples: one entry per plane — a 2-D torch.uint8 tensor
+        (on the solver's GPU: read in place; on the CPU: served like an array) or a 2-D numpy uint8 array, any strides >= 1 —
+        of (rows, columns) <= (plane.h, plane.w); the last row and column are replicated up to the plane's size.  The
+        coefficients are recomputed on the device (the header states the definition and when the file's are recovered
+        exactly); from there on the solver is the one Solver(planes with those coefficients) is.
+        For tensors on the GPU the solver's stream is made to wait for torch's current stream before the kernel reads them;
+        when the call returns they have been read."""
+        self = cls.__new__(cls)
+        lib = load_library()
+        self._lib = lib
+        self._h = None
+        self.nch = len(planes)
+        if len(samples) != self.nch:
+            raise J2PError(f"from_samples: {len(samples)} sample arrays for {self.nch} planes")
+        cpl = (_CPlane * self.nch)()
+        keep = []
+        for i, p in enumerate(planes):
+            if getattr(p, "data", None) is not None or getattr(p, "fdata", None) is not None:
+                raise J2PError(f"from_samples: plane {i} carries data / fdata; a solver made from samples takes neither")
+            q = np.ascontiguousarray(p.quant_table, dtype=np.uint16)
+            keep.append(q)
+            cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None, None, q.ctypes.data)
+        csm, held, on_gpu = _c_samples(samples, device)
+        if on_gpu:
+            # a stream of torch's, so that it can be made to wait for torch's current one (the library synchronises it before
+            # it returns); it lives as long as the solver, which launches on it
+            torch = _torch()
+            dev = torch.device("cuda", int(device))
+            ours = torch.cuda.Stream(device=dev) if stream is None else torch.cuda.ExternalStream(int(stream), device=dev)
+            ours.wait_stream(torch.cuda.current_stream(dev))
+            self._torch_stream = ours
+            stream = ours.cuda_stream
+        pw = (ctypes.c_float * self.nch)(*[float(x) for x in pweight])
+        h = ctypes.c_void_p()
+        _check(lib.j2p_solver_create_from_samples(ctypes.byref(h), int(device), stream, self.nch, cpl, csm, float(weight), pw, int(iterations)))
+        del keep, held
+        self._geom = [(int(p.w), int(p.h)) for p in planes]
+        self._adopt(h, device)
+        return self
+
+    def download_coefficients(self, c):
+        """diagnostics: the quantised coefficients channel c holds, int16 [block rows, blocks per row, 64] (j2p_solver_download_coefficients)"""
+        geom = getattr(self, "_geom", None)
+        if geom is None or (self.row_begin, self.row_end) != (0, self.H):
+            raise J2PError("download_coefficients: whole-canvas solvers made by Solver(...) or Solver.from_samples(...) only")
+        if not 0 <= int(c) < self.nch:
+            raise J2PError(f"download_coefficients: no channel {c}")
+        w, h = geom[int(c)]
+        out = np.empty((h // 8, w // 8, 64), dtype=np.int16)
+        _check(self._lib.j2p_solver_download_coefficients(self._h, int(c), out.ctypes.data))
+        return out
+
+    def clipped_samples(self, c):
+        """how many of channel c's samples were 0 or 255 (a solver made by from_samples): where not 0, the file's coefficients
+        are not guaranteed to have been recovered (j2p_solver_clipped_samples)"""
+        n = ctypes.c_ulonglong()
+        _check(self._lib.j2p_solver_clipped_samples(self._h, int(c), ctypes.byref(n)))
+        return n.value
+
     def close(self):
         if getattr(self, "_h", None) and not getattr(self, "_borrowed", False):
             self._lib.j2p_solver_destroy(self._h)
         self._h = None
+        self._torch_stream = None       # (after the solver, which synchronised it)
 
     def __del__(self):
         self.close()
@@ -937,15 +1023,49 @@ class Solver:
         return g.value, p.value, n.value
 
 
+def _c_samples(samples, device=None):
+    """the j2p_samples array of one 2-D uint8 torch tensor or numpy array per channel; returns (array, what must stay alive, the
+    GPU tensors among them).  device: the GPU a tensor in device memory must be on (None: any, but all on one)."""
+    arr = (_CSamples * len(samples))()
+    held, on_gpu = [], []
+    for i, a in enumerate(samples):
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise J2PError(f"samples[{i}]: a 2-D uint8 array is needed, not {a.dtype} with {a.ndim} dimensions")
+            ptr, shape, strides = a.ctypes.data, a.shape, a.strides
+        else:
+            torch = _torch()
+            if not isinstance(a, torch.Tensor):
+                raise J2PError(f"samples[{i}]: a torch.uint8 tensor or a numpy uint8 array is needed, not {type(a).__name__}")
+            if a.dtype != torch.uint8 or a.dim() != 2:
+                raise J2PError(f"samples[{i}]: a 2-D torch.uint8 tensor is needed, not {a.dtype} with {a.dim()} dimensions")
+            if a.is_cuda:
+                if device is not None and a.device.index != int(device):
+                    raise J2PError(f"samples[{i}]: the tensor is on {a.device}, the solver on device {device}")
+                if on_gpu and on_gpu[0].device != a.device:
+                    raise J2PError("samples: the tensors must live on one GPU")
+                on_gpu.append(a)
+            ptr, shape, strides = a.data_ptr(), tuple(a.shape), a.stride()
+        # (a dimension of size 1 is never stepped over; numpy and torch may report any stride for it)
+        sy = max(int(strides[0]), 1) if shape[0] == 1 else int(strides[0])
+        sx = max(int(strides[1]), 1) if shape[1] == 1 else int(strides[1])
+        if shape[0] < 1 or shape[1] < 1:
+            raise J2PError(f"samples[{i}]: empty ({shape[0]} x {shape[1]})")
+        arr[i] = _CSamples(ptr, int(shape[1]), int(shape[0]), sy, sx)
+        held.append(a)
+    return arr, held, on_gpu
+
+
 def _c_planes(planes):
     keep = []
     cpl = (_CPlane * len(planes))()
     for i, p in enumerate(planes):
-        d = np.ascontiguousarray(p.data, dtype=np.int16)
+        # (data None: the planes of a job made from samples — Batch.submit(samples=...))
+        d = None if p.data is None else np.ascontiguousarray(p.data, dtype=np.int16)
         q = np.ascontiguousarray(p.quant_table, dtype=np.uint16)
         f = None if p.fdata is None else np.ascontiguousarray(p.fdata, dtype=np.float32)
         keep += [d, q, f]
-        cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, d.ctypes.data, None if f is None else f.ctypes.data, q.ctypes.data)
+        cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None if d is None else d.ctypes.data, None if f is None else f.ctypes.data, q.ctypes.data)
     return cpl, keep
 
 
@@ -1052,8 +1172,14 @@ class Batch:
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
-               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None):
-        """tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
+               tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
+               samples=None):
+        """samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
+        out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit
+        samples as Solver.from_samples makes them (j2p_batch_submit_samples) — every output form is available.  Tensors on a GPU
+        pin the job to a worker of that GPU (one of the batch's, and the output tensors'); what torch has queued for them on its
+        current stream is waited for before the job is queued.  Arrays and tensors must stay unchanged until wait();
+        tensor=<torch CUDA tensor> (with width and height, bits 0; not with quant_tables or tile): the image is left on the
         GPU as that tensor's elements — shape (3|1, height, width) for layout "chw" or (height, width, 3|1) for "hwc", dtype
         uint8 / float16 / bfloat16 / float32, any view, with per-channel scale and bias as in Solver.to_tensor — by a worker
         of the tensor's GPU; wait() returns the tensor, complete for any stream.  What torch has queued for the tensor on its
@@ -1077,6 +1203,20 @@ class Batch:
         n = len(planes)
         resize = None
         items = None
+        csm = None
+        if samples is not None:
+            if tile:
+                raise J2PError("job: samples= excludes tile")
+            if filter is not None or out_width is not None or out_height is not None or box is not None:
+                raise J2PError("job: with samples= a resized tensor is an output of outputs=")
+            if len(samples) != n:
+                raise J2PError(f"job: {len(samples)} sample arrays for {n} planes")
+            if any(p.data is not None or p.fdata is not None for p in planes):
+                raise J2PError("job: with samples= the planes carry neither data nor fdata")
+            csm, held, on_gpu = _c_samples(samples)
+            if on_gpu:
+                # (the workers' streams know nothing of torch's: see tensor= below)
+                _torch().cuda.current_stream(on_gpu[0].device).synchronize()
         if outputs is not None:
             if tensor is not None or bits or quant_tables is not None or subsampling is not None or tile:
                 raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
@@ -1204,7 +1344,10 @@ class Batch:
             job.on_progress = cb
             keep = (keep, cb)                       # the trampoline lives as long as the job
         t = ctypes.c_int()
-        if items is not None:
+        if csm is not None:
+            keep = (keep, held)
+            _check(self._lib.j2p_batch_submit_samples(self._h, ctypes.byref(job), csm, 0 if items is None else len(items), items, ctypes.byref(t)))
+        elif items is not None:
             _check(self._lib.j2p_batch_submit_outputs(self._h, ctypes.byref(job), len(items), items, ctypes.byref(t)))
         elif code is not None:
             _check(self._lib.j2p_batch_submit_resampled(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
@@ -1341,3 +1484,101 @@ def compute(planes, weight, pweight, iterations, log=False, device=0):
         p.fdata = o
         p.w, p.h = W, H
     return rows
+
+
+def _zigzag_to_natural():
+    """natural-order index of the k-th coefficient of a zigzag scan (T.81 figure A.6): DQT segments store their steps in that order"""
+    order = sorted(((x, y) for y in range(8) for x in range(8)), key=lambda p: (p[0] + p[1], p[1] if (p[0] + p[1]) % 2 else p[0]))
+    return [y * 8 + x for x, y in order]
+
+
+_NATURAL_OF_ZIGZAG = _zigzag_to_natural()
+
+
+def jpeg_header(data):
+    """What Solver.from_samples needs of a JPEG besides its decoded planes, read from the file's bytes in pure Python (no libjpeg):
+    the marker segments up to the first SOS.  Returns a dict:
+      width, height     the image's size;
+      progressive       True for SOF2;
+      components        per component a dict of id, h_samp_factor, v_samp_factor, quant_table (uint16[64], natural order), the
+                        coefficient plane's size w, h (whole blocks) and w_samp, h_samp as read_jpeg derives them (jpeg.c:49-58:
+                        the largest sampling factor over the component's), and samples_w, samples_h: the samples a decoder
+                        delivers for it, ceil(width * h_samp_factor / the largest), likewise the rows;
+      planes            the same as Plane(w, h, w_samp, h_samp, data=None, quant_table) — what from_samples takes.
+    Handles baseline, extended and progressive files (SOF0 / SOF1 / SOF2), 8- and 16-bit tables, several tables per DQT segment.
+    ValueError for anything else: a component without its table, more than 3 components, 12-bit samples, a truncated segment,
+    no SOF before SOS, another coding process."""
+    data = bytes(data)
+    if len(data) < 4 or data[0:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG: no SOI marker")
+    tables, frame, pos = {}, None, 2
+    while True:
+        if pos + 2 > len(data):
+            raise ValueError("truncated JPEG: no SOS marker")
+        if data[pos] != 0xFF:
+            raise ValueError(f"no marker at byte {pos}")
+        marker = data[pos + 1]
+        if marker == 0xFF:                      # fill byte
+            pos += 1
+            continue
+        pos += 2
+        if marker == 0x01 or 0xD0 <= marker <= 0xD8:      # TEM, RSTn, SOI: no segment
+            continue
+        if marker == 0xD9:
+            raise ValueError("truncated JPEG: EOI before SOS")
+        if pos + 2 > len(data):
+            raise ValueError("truncated segment")
+        length = int.from_bytes(data[pos:pos + 2], "big")
+        if length < 2 or pos + length > len(data):
+            raise ValueError(f"truncated segment (marker 0xFF{marker:02X})")
+        body = data[pos + 2:pos + length]
+        pos += length
+        if marker == 0xDB:                      # DQT: one or more tables
+            at = 0
+            while at < len(body):
+                precision, slot = body[at] >> 4, body[at] & 15
+                at += 1
+                if precision > 1 or slot > 3:
+                    raise ValueError("invalid DQT segment")
+                size = 128 if precision else 64
+                if at + size > len(body):
+                    raise ValueError("truncated segment (DQT)")
+                raw = np.frombuffer(body, ">u2" if precision else np.uint8, 64, at).astype(np.uint16)
+                at += size
+                q = np.zeros(64, np.uint16)
+                q[_NATURAL_OF_ZIGZAG] = raw
+                tables[slot] = q
+        elif marker in (0xC0, 0xC1, 0xC2):      # SOF0 / SOF1 / SOF2
+            if len(body) < 6:
+                raise ValueError("truncated segment (SOF)")
+            if body[0] != 8:
+                raise ValueError(f"{body[0]}-bit samples (only 8-bit JPEGs are supported)")
+            n = body[5]
+            if n < 1 or n > 3:
+                raise ValueError(f"{n} components (1 to 3 are supported)")
+            if len(body) < 6 + 3 * n:
+                raise ValueError("truncated segment (SOF)")
+            frame = {"height": int.from_bytes(body[1:3], "big"), "width": int.from_bytes(body[3:5], "big"), "progressive": marker == 0xC2,
+                     "components": [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(n)]}
+            if frame["width"] == 0 or frame["height"] == 0 or any(h == 0 or v == 0 for _, h, v, _ in frame["components"]):
+                raise ValueError("invalid SOF segment")
+        elif 0xC0 <= marker <= 0xCF and marker not in (0xC4, 0xC8, 0xCC):
+            raise ValueError(f"unsupported coding process (marker 0xFF{marker:02X})")
+        elif marker == 0xDA:                    # SOS: the header ends here
+            break
+    if frame is None:
+        raise ValueError("no SOF segment before SOS")
+    hmax = max(h for _, h, _, _ in frame["components"])
+    vmax = max(v for _, _, v, _ in frame["components"])
+    width, height = frame["width"], frame["height"]
+    comps, planes = [], []
+    for cid, hs, vs, slot in frame["components"]:
+        if slot not in tables:
+            raise ValueError(f"component {cid}: quantisation table {slot} is missing")
+        sw, sh = -(-width * hs // hmax), -(-height * vs // vmax)
+        w, h = -(-sw // 8) * 8, -(-sh // 8) * 8
+        q = tables[slot].copy()
+        comps.append({"id": cid, "h_samp_factor": hs, "v_samp_factor": vs, "quant_table": q, "w": w, "h": h,
+                      "w_samp": hmax // hs, "h_samp": vmax // vs, "samples_w": sw, "samples_h": sh})
+        planes.append(Plane(w, h, hmax // hs, vmax // vs, None, q))
+    return {"width": width, "height": height, "progressive": frame["progressive"], "components": comps, "planes": planes}

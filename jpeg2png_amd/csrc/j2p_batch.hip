@@ -36,8 +36,9 @@ struct Job {
         j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resampled: ... resampled with a filter
         bool resampled = false;
         std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
+        std::vector<j2p_samples> samples;   // j2p_batch_submit_samples: [channel] the solvers are made from these, not from planes[].data
         int ticket = 0;
-        int device = -1;                    // tensor output: the tensor's device, the only one whose workers may take the job
+        int device = -1;                    // tensor output, device samples: their device, the only one whose workers may take the job
         int rc = J2P_OK;
         bool finished = false;
         char err[256] = "";
@@ -305,13 +306,20 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
         return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr);
 }
 
-int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs)
+// (samples: NULL, or [channel] what the solvers are made from instead of planes[].data)
+int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs,
+            const j2p_samples *samples)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
         for(unsigned k = 0; k < solves(d); k++) {
-                JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, d.separate ? 1 : d.nchannel, &d.planes[k], d.weight[k], &d.pweight[k],
-                                          d.iterations[k], whole, 0));
+                const unsigned nch = d.separate ? 1 : d.nchannel;
+                if(samples) {
+                        JOB_TRY(j2p_solver_create_from_samples(&eng.e[k].s, device, nullptr, nch, &d.planes[k], &samples[k], d.weight[k], &d.pweight[k],
+                                                               d.iterations[k]));
+                        continue;
+                }
+                JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, nch, &d.planes[k], d.weight[k], &d.pweight[k], d.iterations[k], whole, 0));
         }
         return solve_and_deliver(d, eng.e, true, resize, resample, outputs);
 }
@@ -352,7 +360,7 @@ void worker_main(j2p_batch *b, int device)
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
                         rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr,
-                                     job->outputs.empty() ? nullptr : &job->outputs);
+                                     job->outputs.empty() ? nullptr : &job->outputs, job->samples.empty() ? nullptr : job->samples.data());
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -387,11 +395,42 @@ int validate_outputs(const j2p_job &d, unsigned n, const j2p_output *outs, int *
         return J2P_OK;
 }
 
+// what j2p_batch_submit_samples refuses at submit; *device: the GPU that holds the device samples, or -1 (host samples only)
+int validate_samples(const j2p_job &d, const j2p_samples *samples, int *device)
+{
+        if(d.nchannel == 0 || d.nchannel > J2P_MAX_CHANNELS) { return j2p_fail(J2P_EINVAL, "job: nchannel must be 1..3"); }
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: sample input of a row-tiled job is not supported"); }
+        *device = -1;
+        for(unsigned c = 0; c < d.nchannel; c++) {
+                const j2p_plane &p = d.planes[c];
+                const j2p_samples &m = samples[c];
+                if(p.data || p.fdata) { return j2p_fail(J2P_EINVAL, "job: channel %u: a job with samples takes no data / fdata (both must be NULL)", c); }
+                if(!m.data) { return j2p_fail(J2P_EINVAL, "job: channel %u: samples: data is NULL", c); }
+                if(m.w == 0 || m.h == 0 || m.w > p.w || m.h > p.h) {
+                        return j2p_fail(J2P_EINVAL, "job: channel %u: samples: %ux%u samples for a coefficient plane of %ux%u", c, m.w, m.h, p.w, p.h);
+                }
+                if(m.stride_y < 1 || m.stride_x < 1) { return j2p_fail(J2P_EINVAL, "job: channel %u: samples: strides must be at least 1", c); }
+                int dev = -1;
+                const int kind = j2p_memory_of_pointer(m.data, &dev);
+                if(kind == J2P_MEMORY_OTHER) { return j2p_fail(J2P_EINVAL, "job: channel %u: samples: data is neither host nor plain device memory (managed memory is refused)", c); }
+                if(kind == J2P_MEMORY_DEVICE) {
+                        if(*device >= 0 && dev != *device) { return j2p_fail(J2P_EINVAL, "job: channel %u: samples live on device %d, others on device %d", c, dev, *device); }
+                        *device = dev;
+                }
+        }
+        return J2P_OK;
+}
+
 // j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled, — nout != 0 —
-// j2p_batch_submit_outputs (never two of them)
-int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs, int *ticket)
+// j2p_batch_submit_outputs (never two of them); samples != NULL: j2p_batch_submit_samples (with nout or without; never with r or f)
+int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs,
+           const j2p_samples *samples, int *ticket)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        int samples_device = -1;
+        if(samples) {
+                if(const int rc = validate_samples(*job, samples, &samples_device); rc != J2P_OK) { return rc; }
+        }
         int outputs_device = -1;
         if(nout) {
                 if(const int rc = validate_outputs(*job, nout, outs, &outputs_device); rc != J2P_OK) { return rc; }
@@ -416,6 +455,7 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
                 j->resampled = true;
         }
         if(nout) { j->outputs.assign(outs, outs + nout); }
+        if(samples) { j->samples.assign(samples, samples + job->nchannel); }
         if(job->out_tensor.data || nout) {
                 // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor(s)
                 int rc = validate_job(j->desc);
@@ -427,6 +467,18 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
                 for(int dev : b->devices) { owned = owned || dev == j->device; }
                 if(rc == J2P_OK && !owned) { rc = j2p_fail(J2P_EINVAL, "job: the tensor lives on device %d, which this batch does not drive", j->device); }
                 if(rc != J2P_OK) { delete j; return rc; }
+        }
+        if(samples_device >= 0) {
+                // device samples pin the job as tensors do: to their GPU, which must be the tensors' and one of the batch's
+                int rc = J2P_OK;
+                bool owned = false;
+                for(int dev : b->devices) { owned = owned || dev == samples_device; }
+                if(j->device >= 0 && j->device != samples_device) {
+                        rc = j2p_fail(J2P_EINVAL, "job: the samples live on device %d, the output tensor on device %d", samples_device, j->device);
+                }
+                else if(!owned) { rc = j2p_fail(J2P_EINVAL, "job: the samples live on device %d, which this batch does not drive", samples_device); }
+                if(rc != J2P_OK) { delete j; return rc; }
+                j->device = samples_device;
         }
         const bool pinned = j->device >= 0;
         {
@@ -488,23 +540,29 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        return submit(b, job, nullptr, nullptr, 0, nullptr, ticket);
+        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
 {
-        return submit(b, job, r, nullptr, 0, nullptr, ticket);
+        return submit(b, job, r, nullptr, 0, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket)
 {
-        return submit(b, job, nullptr, r, 0, nullptr, ticket);
+        return submit(b, job, nullptr, r, 0, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const j2p_output outs[], int *ticket)
 {
         const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, ticket);
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, ticket);
+}
+
+int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[], int *ticket)
+{
+        const bool none = n == 0 || !outs;
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, samples, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

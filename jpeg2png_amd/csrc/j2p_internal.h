@@ -16,6 +16,12 @@ int j2p_tiled_exchange_forced(void);
 // the device whose plain device memory p points into (hipPointerGetAttributes); J2P_EINVAL without an error text for host,
 // managed and unknown memory (j2p_output.hip) — what tensor output checks its destination with
 int j2p_device_of_pointer(const void *p, int *device);
+// what kind of memory p points into (hipPointerGetAttributes), for sample input, which takes two kinds: plain device memory
+// (*device: whose), host memory (pageable or pinned), or anything else — managed memory above all, which is refused
+#define J2P_MEMORY_HOST 0
+#define J2P_MEMORY_DEVICE 1
+#define J2P_MEMORY_OTHER 2
+int j2p_memory_of_pointer(const void *p, int *device);
 
 // bytes of one tensor element of a J2P_DTYPE_* code (u8 1, f32 4, the 16-bit kinds 2)
 static inline unsigned j2p_tensor_element_bytes(int dtype) { return dtype == J2P_DTYPE_U8 ? 1 : (dtype == J2P_DTYPE_F32 ? 4 : 2); }

@@ -2631,6 +2631,86 @@ __global__ __launch_bounds__(256) void k_decode(const int16_t *d, const float *q
         }
 }
 
+// ---------------------------------------------------------------------------
+// Sample input (j2p_solver_create_from_samples): 8-bit samples back to the quantised coefficients they were decoded from.
+// Sample (X, Y) of the coefficient plane is data[min(Y, h - 1) * stride_y + min(X, w - 1) * stride_x] (the last column and
+// row replicated, as libjpeg's encoder pads), v = (float)s - 128.f, every 8x8 block of v through dct8x8s, each coefficient
+// divided by its step as the IEEE f32 quotient (`/` under -fhip-fp32-correctly-rounded-divide-sqrt) and rounded to nearest
+// even.  No clamp: |v| <= 128 and the DCT rows have an L1 norm of at most 8, so the values lie in [-1024, 1016].
+// out: block-major int16 [block_rows * blocks_w][64], natural order — the solver's h.d.
+// Mapping of k_quantise_blocks: one wavefront = 8 horizontally adjacent blocks, lane >> 3 the block, lane & 7 the row; a
+// lane stores its 8 coefficients as one 16-byte vector.  Loads: `wide` (stride_x == 1, data and stride_y multiples of 8:
+// the host says so) — a lane's 8 bytes as one 8-byte load, 8 lanes 64 contiguous bytes of a row; otherwise 8 byte loads
+// stride_x apart.  Only lanes whose block crosses w or h take the clamped loads.
+// *clipped: how many of the w x h samples PRESENT (never the replicated ones) were 0 or 255 — one add per wavefront.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_samples_to_coefficients(const uint8_t *data, unsigned w, unsigned h, ptrdiff_t stride_y,
+                                                                 ptrdiff_t stride_x, int wide, unsigned blocks_w, unsigned block_rows,
+                                                                 const float *q, int16_t *out, unsigned long long *clipped)
+{
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
+        __shared__ float qs[64];
+        if(threadIdx.x < 64) { qs[threadIdx.x] = q[threadIdx.x]; }
+        __syncthreads();
+        const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+        const unsigned groups_x = (blocks_w + 7) / 8;
+        const unsigned grp = blockIdx.x * 4 + wave;
+        if(grp >= groups_x * block_rows) { return; }                    // whole wavefronts only: no barrier follows
+        const unsigned by = grp / groups_x, bx = (grp % groups_x) * 8 + (unsigned)(lane >> 3);
+        const int rr = lane & 7;
+        const bool ok = bx < blocks_w;
+        const unsigned x0 = bx * 8, y = by * 8 + (unsigned)rr;
+        unsigned s[8];
+#pragma unroll
+        for(int u = 0; u < 8; u++) { s[u] = 128u; }
+        unsigned nclip = 0;
+        if(ok && x0 + 8 <= w && y < h) {
+                const uint8_t *src = data + (ptrdiff_t)y * stride_y + (ptrdiff_t)x0 * stride_x;
+                if(wide) {
+                        const v2u r = *reinterpret_cast<const v2u *>(src);
+#pragma unroll
+                        for(int u = 0; u < 4; u++) {
+                                s[u] = (r.x >> (8 * u)) & 0xffu;
+                                s[4 + u] = (r.y >> (8 * u)) & 0xffu;
+                        }
+                } else {
+#pragma unroll
+                        for(int u = 0; u < 8; u++) { s[u] = src[(ptrdiff_t)u * stride_x]; }
+                }
+#pragma unroll
+                for(int u = 0; u < 8; u++) { nclip += (s[u] == 0u || s[u] == 255u) ? 1u : 0u; }
+        } else if(ok) {
+                // the block crosses the samples' last column or row: replicate them
+                const uint8_t *src = data + (ptrdiff_t)(y < h ? y : h - 1) * stride_y;
+#pragma unroll
+                for(int u = 0; u < 8; u++) {
+                        const unsigned x = x0 + (unsigned)u;
+                        s[u] = src[(ptrdiff_t)(x < w ? x : w - 1) * stride_x];
+                        nclip += (x < w && y < h && (s[u] == 0u || s[u] == 255u)) ? 1u : 0u;
+                }
+        }
+        float v[8];
+#pragma unroll
+        for(int u = 0; u < 8; u++) { v[u] = (float)s[u] - 128.f; }
+        float *scratch = tp + wave * kTpWave;
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        transpose8(v, scratch, lane);
+        fdct8(v);
+        unsigned packed[4];
+#pragma unroll
+        for(int u = 0; u < 8; u += 2) {
+                const unsigned lo = (unsigned)(int)rintf(v[u] / qs[rr * 8 + u]) & 0xffffu;
+                const unsigned hi = (unsigned)(int)rintf(v[u + 1] / qs[rr * 8 + u + 1]) & 0xffffu;
+                packed[u / 2] = lo | (hi << 16);
+        }
+        if(ok) { *reinterpret_cast<uint4 *>(out + ((size_t)by * blocks_w + bx) * 64 + rr * 8) = make_uint4(packed[0], packed[1], packed[2], packed[3]); }
+#pragma unroll
+        for(int off = 32; off > 0; off >>= 1) { nclip += (unsigned)__shfl_down((int)nclip, off, 64); }
+        if(lane == 0 && nclip) { atomicAdd(clipped, (unsigned long long)nclip); }
+}
+
 // plain 8x8 transforms on a block-major array (parity tests of the butterflies)
 __global__ __launch_bounds__(256) void k_dct_blocks(float *blocks, size_t nblocks, int inverse)
 {

@@ -231,6 +231,22 @@ int j2p_device_of_pointer(const void *p, int *device)
         return J2P_OK;
 }
 
+int j2p_memory_of_pointer(const void *p, int *device)
+{
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        if(hipPointerGetAttributes(&attr, p) != hipSuccess) {
+                (void)hipGetLastError();                 // (plain host memory is an error to some runtimes, "unregistered" to others)
+                return J2P_MEMORY_HOST;
+        }
+        if(attr.isManaged || attr.type == hipMemoryTypeManaged) { return J2P_MEMORY_OTHER; }
+        if(attr.type == hipMemoryTypeDevice) {
+                *device = attr.device;
+                return J2P_MEMORY_DEVICE;
+        }
+        return attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeUnregistered ? J2P_MEMORY_HOST : J2P_MEMORY_OTHER;
+}
+
 int j2p_planes_to_tensor(const j2p_plane_ref planes[], unsigned nplane, unsigned w, unsigned h, const j2p_tensor *out)
 {
         return tensor_rows(planes, nplane, true, w, 0, h, out);

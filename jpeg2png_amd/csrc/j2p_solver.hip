@@ -128,6 +128,9 @@ struct j2p_solver {
         bool share_state = true;        // eligible channels keep g and the prob state in one buffer (J2P_SHARE_STATE=0, experiments build: two)
         bool wide_footprint = true;     // footprints 3, 4, 6, 8 columns wide take the wide-footprint path (J2P_OPT_WIDE_FOOTPRINT)
         unsigned *d_maxabs = nullptr;                 // [channel] largest |d| (k_narrow_coefficients, create only)
+        unsigned long long *d_clipped = nullptr;      // [channel] samples that were 0 or 255 (k_samples_to_coefficients, create only)
+        unsigned long long clipped[kMaxCh] = {0, 0, 0};   // ... read back with d_maxabs (j2p_solver_clipped_samples)
+        bool sampled = false;                         // made by j2p_solver_create_from_samples
         unsigned long long *dbg_counters = nullptr;   // J2P_DEBUG builds: [0] address violations, [1] first site, [2] first offset
         unsigned long long *trace = nullptr;          // J2P_TRACE builds: wave records (tools/wave_trace.py)
         unsigned trace_cap = 0, trace_used = 0;      // records reserved by the launches so far
@@ -778,7 +781,9 @@ int launch_init(j2p_solver *s)
 // ---------------------------------------------------------------------------
 
 // what the planes and the band say before a device is touched: the canvas, and in *band the rows the solver holds
-int validate(unsigned nchannel, const j2p_plane planes[], int band_local_arrays, j2p_canvas *cv, j2p_band *band, bool *is_whole)
+// (samples: j2p_solver_create_from_samples — the planes carry no arrays, samples[c] stands in for them)
+int validate(unsigned nchannel, const j2p_plane planes[], const j2p_samples samples[], int band_local_arrays, j2p_canvas *cv, j2p_band *band,
+             bool *is_whole)
 {
         if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
         for(unsigned c = 0; c < nchannel; c++) {
@@ -787,7 +792,19 @@ int validate(unsigned nchannel, const j2p_plane planes[], int band_local_arrays,
                         return j2p_fail(J2P_EINVAL, "channel %u: coefficient plane %ux%u is not a positive multiple of 8 (box.c:6-7)", c, p.w, p.h);
                 }
                 if(p.w_samp == 0 || p.h_samp == 0) { return j2p_fail(J2P_EINVAL, "channel %u: zero sampling factor", c); }
-                if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
+                if(samples) {
+                        const j2p_samples &m = samples[c];
+                        if(p.data || p.fdata) { return j2p_fail(J2P_EINVAL, "channel %u: a solver made from samples takes no data / fdata (both must be NULL)", c); }
+                        if(!p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
+                        if(!m.data) { return j2p_fail(J2P_EINVAL, "channel %u: samples: data is NULL", c); }
+                        if(m.w == 0 || m.h == 0 || m.w > p.w || m.h > p.h) {
+                                return j2p_fail(J2P_EINVAL, "channel %u: samples: %ux%u samples for a coefficient plane of %ux%u", c, m.w, m.h, p.w, p.h);
+                        }
+                        if(m.stride_y < 1 || m.stride_x < 1) {
+                                return j2p_fail(J2P_EINVAL, "channel %u: samples: strides (y, x) = (%td, %td) must be at least 1", c, m.stride_y, m.stride_x);
+                        }
+                }
+                else if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
                 for(int j = 0; j < 64; j++) {
                         if(p.quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
                 }
@@ -941,6 +958,7 @@ int carve_arena(j2p_solver *s, const j2p_plane planes[])
                 carve.take(s->tickets, (size_t)s->ntr_local + 1);
                 carve.take(s->dbg_counters, 3);
                 carve.take(s->d_maxabs, kMaxCh);
+                carve.take(s->d_clipped, kMaxCh);
                 carve.take(s->part_tv, ntiles * 2);
                 carve.take(s->part_prob, (size_t)max_strips * nchannel);
         }
@@ -987,20 +1005,69 @@ int upload_tables(j2p_solver *s, const j2p_plane planes[], float qf[])
         HIP_TRY(hipMemsetAsync(s->part_prob, 0, (size_t)max_strips * nchannel * sizeof(double), s->stream));
         HIP_TRY(hipMemsetAsync(s->dbg_counters, 0, 3 * sizeof(unsigned long long), s->stream));
         HIP_TRY(hipMemsetAsync(s->d_maxabs, 0, kMaxCh * sizeof(unsigned), s->stream));
+        HIP_TRY(hipMemsetAsync(s->d_clipped, 0, kMaxCh * sizeof(unsigned long long), s->stream));
         return J2P_OK;
 }
 
-// one channel's coefficients go up (host arrays: whole-image unless band_local) and are narrowed to bytes; its input
-// window goes up decoded, or is decoded here
-int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p)
+// a channel's samples and where they are: device memory of the solver's device (read in place) or host memory (staged)
+struct SampleSource {
+        j2p_samples m;
+        bool on_device;
+};
+
+// the sample source of upload_channel: channel c's coefficients are computed into h.d from 8-bit samples
+// (k_samples_to_coefficients) instead of copied.  Device samples are read in place on the solver's stream; host samples
+// are staged through the channel's first x buffer — not initialised yet, as the decode scratch below — with one 2-D copy
+int samples_to_coefficients(j2p_solver *s, unsigned c, const SampleSource &src)
+{
+        ChanHost &h = s->ch[c];
+        j2p_samples m = src.m;
+        if(!src.on_device) {
+                // rows of (w - 1) * stride_x + 1 bytes at a pitch that keeps every row 8-byte aligned
+                const size_t row_bytes = (size_t)(m.w - 1) * (size_t)m.stride_x + 1, pitch = (row_bytes + 7) & ~(size_t)7;
+                if(pitch * m.h > plane_floats_of(s) * sizeof(float)) {
+                        return j2p_fail(J2P_EINVAL, "channel %u: samples: host samples with stride_x %td do not fit the staging buffer", c, m.stride_x);
+                }
+                uint8_t *stage = reinterpret_cast<uint8_t *>(h.xbuf[0]);
+                // (a plain 1-D copy for rows that already lie at the staging pitch measured the same: DESIGN.md section 19)
+                if((size_t)m.stride_y >= row_bytes) {
+                        HIP_TRY(hipMemcpy2DAsync(stage, pitch, m.data, (size_t)m.stride_y, row_bytes, m.h, hipMemcpyHostToDevice, s->stream));
+                } else {
+                        // (rows that overlap in memory: no 2-D copy describes them)
+                        for(unsigned y = 0; y < m.h; y++) {
+                                HIP_TRY(hipMemcpyAsync(stage + y * pitch, m.data + (size_t)y * (size_t)m.stride_y, row_bytes, hipMemcpyHostToDevice, s->stream));
+                        }
+                }
+                m.data = stage;
+                m.stride_y = (ptrdiff_t)pitch;
+        }
+        const unsigned blocks_w = h.cw / 8, block_rows = h.ch / 8;
+        const unsigned groups = ((blocks_w + 7) / 8) * block_rows;
+        const int wide = m.stride_x == 1 && ((reinterpret_cast<uintptr_t>(m.data) | (uintptr_t)m.stride_y) & 7) == 0;
+        hipLaunchKernelGGL(k_samples_to_coefficients, dim3((groups + 3) / 4), dim3(256), 0, s->stream, m.data, m.w, m.h, m.stride_y, m.stride_x,
+                           wide, blocks_w, block_rows, (const float *)h.q, h.d, s->d_clipped + c);
+        HIP_TRY(hipGetLastError());
+        return J2P_OK;
+}
+
+// one channel's coefficients go up (host arrays: whole-image unless band_local; or are computed from samples, m != NULL)
+// and are narrowed to bytes; its input window goes up decoded, or is decoded here
+int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p, const SampleSource *m)
 {
         ChanHost &h = s->ch[c];
         const size_t plane_floats = plane_floats_of(s);
         const size_t host_row0 = s->band_local ? h.crow0 : 0;
+        if(m) {
+                // (whole canvases only: h.d holds every block row, and the decode below finds its window there)
+                const int rc = samples_to_coefficients(s, c, *m);
+                if(rc != J2P_OK) { return rc; }
+        }
         if(h.crows) {
                 // block-major: coefficient row r lives in block row r/8; rows are block aligned
-                const int16_t *src = p.data + (size_t)(h.crow0 - host_row0) * h.cw;
-                HIP_TRY(hipMemcpyAsync(h.d, src, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
+                if(!m) {
+                        const int16_t *src = p.data + (size_t)(h.crow0 - host_row0) * h.cw;
+                        HIP_TRY(hipMemcpyAsync(h.d, src, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
+                }
                 // ... and once more as bytes, with the largest |d| (decide_narrow_and_wide reads it back)
                 const size_t cells = (size_t)h.crows * h.cw;
                 const unsigned blocks = (unsigned)((cells / 8 + 255) / 256);
@@ -1057,6 +1124,7 @@ int decide_narrow_and_wide(j2p_solver *s)
         // blocking stream of the device)
         unsigned maxabs[kMaxCh] = {0};
         HIP_TRY(hipMemcpyAsync(maxabs, s->d_maxabs, sizeof(maxabs), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->clipped, s->d_clipped, sizeof(s->clipped), hipMemcpyDeviceToHost, s->stream));
         // the host arrays (and j2p_solver_create's stack table) may go away as soon as this returns
         HIP_TRY(hipStreamSynchronize(s->stream));
         {
@@ -1124,14 +1192,17 @@ void j2p_solver_destroy(j2p_solver *s)
         delete s;
 }
 
-int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
-                      float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
+// j2p_solver_create, and — samples != NULL — j2p_solver_create_from_samples: the same stages, with the sample source in
+// the upload stage
+static int create_solver(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[], const j2p_samples samples[],
+                         float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
 {
-        if(!out || !planes || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(!out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *out = nullptr;
+        if(!planes || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         j2p_canvas cv = J2P_CANVAS_NONE;
         bool whole = true;
-        int rc = validate(nchannel, planes, band_local_arrays, &cv, &band, &whole);
+        int rc = validate(nchannel, planes, samples, band_local_arrays, &cv, &band, &whole);
         if(rc != J2P_OK) { return rc; }
         int ndev = 0;
         if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -1140,6 +1211,16 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         if(device < 0 || device >= ndev) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, ndev - 1); }
         DeviceGuard guard(device);
         if(!guard.ok) { return j2p_fail(J2P_EDEVICE, "hipSetDevice(%d) failed", device); }
+        // where the samples are: this device's memory or the host's; nothing else (before anything is made or queued)
+        SampleSource sources[kMaxCh];
+        for(unsigned c = 0; samples && c < nchannel; c++) {
+                int where = -1;
+                const int kind = j2p_memory_of_pointer(samples[c].data, &where);
+                if(kind == J2P_MEMORY_OTHER || (kind == J2P_MEMORY_DEVICE && where != device)) {
+                        return j2p_fail(J2P_EINVAL, "channel %u: samples: data is neither host memory nor device memory of device %d (managed memory and other GPUs' are refused)", c, device);
+                }
+                sources[c] = SampleSource{samples[c], kind == J2P_MEMORY_DEVICE};
+        }
         if(allow_k_norm_whole_lds() != hipSuccess) {
                 return j2p_fail(J2P_EDEVICE, "hipFuncSetAttribute(k_norm_whole, %u bytes of LDS) failed", kNormLdsBytes);
         }
@@ -1156,6 +1237,7 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
         s->whole = whole;
         s->weight = weight;
         s->iterations = iterations;
+        s->sampled = samples != nullptr;
         if(stream) { s->stream = (hipStream_t)stream; }
         else {
                 HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
@@ -1168,11 +1250,45 @@ int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchan
                 register_live_bytes(s);
                 rc = upload_tables(s, planes, qf);
         }
-        for(unsigned c = 0; rc == J2P_OK && c < nchannel; c++) { rc = upload_channel(s, c, planes[c]); }
+        for(unsigned c = 0; rc == J2P_OK && c < nchannel; c++) { rc = upload_channel(s, c, planes[c], samples ? &sources[c] : nullptr); }
         if(rc == J2P_OK) { rc = decide_narrow_and_wide(s); }
         if(rc == J2P_OK) { rc = launch_init(s); }
         if(rc != J2P_OK) { return rc; }
         *out = owner.release();
+        return J2P_OK;
+}
+
+int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
+                      float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
+{
+        return create_solver(out, device, stream, nchannel, planes, nullptr, weight, pweight, iterations, band, band_local_arrays);
+}
+
+int j2p_solver_create_from_samples(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
+                                   const j2p_samples samples[], float weight, const float pweight[], unsigned iterations)
+{
+        if(out) { *out = nullptr; }
+        if(!samples) { return j2p_fail(J2P_EINVAL, "samples is NULL"); }
+        const j2p_band whole = {0, 0};
+        return create_solver(out, device, stream, nchannel, planes, samples, weight, pweight, iterations, whole, 0);
+}
+
+int j2p_solver_clipped_samples(const j2p_solver *s, unsigned c, unsigned long long *count)
+{
+        if(!s || !count || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_clipped_samples: bad argument"); }
+        if(!s->sampled) { return j2p_fail(J2P_ESTATE, "j2p_solver_clipped_samples: the solver was not made from samples"); }
+        *count = s->clipped[c];
+        return J2P_OK;
+}
+
+int j2p_solver_download_coefficients(j2p_solver *s, unsigned c, int16_t *out_host)
+{
+        if(!s || !out_host || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_download_coefficients: bad argument"); }
+        const ChanHost &h = s->ch[c];
+        if(!h.crows) { return J2P_OK; }          // (a band below the channel's last row holds none)
+        DeviceGuard guard(s->device);
+        HIP_TRY(hipMemcpyAsync(out_host, h.d, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
         return J2P_OK;
 }
 
