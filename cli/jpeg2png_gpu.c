@@ -296,6 +296,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
+        bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
         bool grey;              /* -g: component 0 alone, one-channel job, greyscale PNG */
@@ -445,15 +446,46 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         int ticket = 0;
         pthread_once(&batch_once, batch_start);
         if(batch_rc != J2P_OK) { die("%s", batch_err); }
-        gpu_check(j2p_batch_submit(batch, &job, &ticket));
-        gpu_check(j2p_batch_wait(batch, ticket));
+        uint8_t *file = NULL;
+        size_t file_bytes = 0;
+        if(o->jpeg_quality && o->encode_on_gpu) {
+                /* -e: the same tables, but the coefficients stay on the GPU and the finished file comes down.  Room for a quarter
+                 * of a byte per sample at first; a file that needs more says how much, and the job runs again */
+                j2p_jpeg spec = {job.out_w, job.out_h, jp.n == 1 ? 1 : o->sub_w, jp.n == 1 ? 1 : o->sub_h, {NULL, NULL, NULL}};
+                for(unsigned c = 0; c < jp.n; c++) {
+                        spec.quant[c] = out_quant[c];
+                        job.out_quant[c] = NULL;
+                        job.out_coef[c] = NULL;
+                }
+                job.out_blocks_w = job.out_blocks_h = 0;
+                job.tile = 0;           /* (a row-tiled job has no file output) */
+                size_t capacity = 4096 + (size_t)job.out_w * job.out_h * jp.n / 4;
+                for(int attempt = 0;; attempt++) {
+                        file = malloc(capacity);
+                        if(!file) { die("could not allocate image data"); }
+                        gpu_check(j2p_batch_submit_jpeg(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket));
+                        const int rc = j2p_batch_wait(batch, ticket);
+                        if(rc != J2P_ESPACE || attempt) {
+                                gpu_check(rc);
+                                break;
+                        }
+                        free(file);
+                        capacity = file_bytes;
+                }
+        } else {
+                gpu_check(j2p_batch_submit(batch, &job, &ticket));
+                gpu_check(j2p_batch_wait(batch, ticket));
+        }
         for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
-        if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, out_coef); }
+        if(file) {
+                if(fwrite(file, 1, file_bytes, out) != file_bytes) { die_perror("could not write output file `%s`", outfile); }
+        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, out_coef); }
         else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
+        free(file);
         for(unsigned c = 0; c < 3; c++) { free(out_coef[c]); }
 }
 
@@ -503,6 +535,8 @@ static void usage(void)
                "  -S, --chroma-subsampling 444|422|420|440\n"
                "                               with -j: chroma at half the resolution across (422), across and down (420)\n"
                "                               or down (440), every sample the mean of the solved values it covers\n"
+               "  -e, --encode-on-gpu          with -j: the GPU also entropy-codes the file (default Huffman tables, the bytes\n"
+               "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -521,15 +555,15 @@ int main(int argc, char **argv)
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
-                {"chroma-subsampling", required_argument, NULL, 'S'}, {NULL, 0, NULL, 0}};
+                {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .jpeg_quality = 0, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+                            .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:e", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -546,6 +580,7 @@ int main(int argc, char **argv)
                 case 'g': o.grey = true; break;
                 case 'j': j_arg = optarg; break;
                 case 'S': S_arg = optarg; break;
+                case 'e': o.encode_on_gpu = true; break;
                 default: help = true; break;
                 }
         }
@@ -598,6 +633,7 @@ int main(int argc, char **argv)
                 o.sub_w = subs[k].w;
                 o.sub_h = subs[k].h;
         }
+        if(o.encode_on_gpu && !j_arg) { die("-e needs JPEG output (-j)"); }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);
         unsigned threads = cores > 0 ? (unsigned)cores : 1u;

@@ -804,6 +804,84 @@ int j2p_solver_clipped_samples(const j2p_solver *s, unsigned c, unsigned long lo
 int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[],
                              unsigned n, const j2p_output outs[], int *ticket);
 
+/* The JPEG file: quantised coefficients entropy-coded ON THE DEVICE, so that a complete baseline JPEG comes down instead of 2 bytes
+ * per sample of coefficients for a host library to code.  The file is, byte for byte, the one libjpeg writes from the same
+ * coefficients with jpeg_set_defaults, jpeg_set_colorspace, jpeg_set_quality(Q, TRUE) and jpeg_write_coefficients: default Huffman
+ * tables, one scan, no restart markers, no optimisation.  This is the definition.
+ *
+ * Inputs.  An image of width x height (1..65535 each) with ncomp = 1 or 3 components; chroma subsampling sub_w, sub_h, each 1 or 2
+ * (one component: taken as 1 whatever the fields hold).  Component 0 has bw x bh = ceil(width / 8) x ceil(height / 8) blocks,
+ * components 1 and 2 ceil(bw / sub_w) x ceil(bh / sub_h) — the grids j2p_planes_to_coefficients_sub produces.  A block is 64 int16 in
+ * natural order, every value in [-1023, 1023].  quant[c]: 64 steps, natural order, each 1..255 (the file is 8-bit baseline), and
+ * quant[2] must hold the values of quant[1] (the file has two table slots, as libjpeg's has); J2P_EINVAL otherwise.
+ *
+ * Header.  Every piece is FF, the marker's byte, the big-endian 16-bit length of what follows including the length itself, the payload:
+ *   1. FF D8 (alone).
+ *   2. APP0 (E0): "JFIF\0" 01 01 00 00 01 00 01 00 00.
+ *   3. DQT (DB): 00, then the 64 steps of table 0 in zigzag order.  Three components: a second DQT, 01 and table 1.
+ *   4. SOF0 (C0): 08, height, width (16 bits each), ncomp, then per component c: its id c + 1, its sampling byte — (sub_w << 4) | sub_h
+ *      for c = 0, 0x11 otherwise — and its table: 0 for c = 0, 1 otherwise.
+ *   5. DHT (C4), one per Huffman table: DC0 (class/slot byte 00), AC0 (10), and for three components DC1 (01), AC1 (11); the byte, 16
+ *      counts BITS, the symbols HUFFVAL.  The tables of Annex K.3 of the JPEG standard:
+ *        DC0 BITS    = {0,1,5,1,1,1,1,1,1,0,0,0,0,0,0,0}         DC1 BITS = {0,3,1,1,1,1,1,1,1,1,1,0,0,0,0,0}
+ *        DC0 HUFFVAL = DC1 HUFFVAL = {0,1,2,3,4,5,6,7,8,9,10,11}
+ *        AC0 BITS    = {0,2,1,3,3,2,4,3,5,5,4,4,0,0,1,125}
+ *        AC0 HUFFVAL = {01,02,03,00,04,11,05,12,21,31,41,06,13,51,61,07,22,71,14,32,81,91,a1,08,23,42,b1,c1,15,52,d1,f0,24,33,62,72,
+ *                       82,09,0a,16,17,18,19,1a,25,26,27,28,29,2a,34,35,36,37,38,39,3a,43,44,45,46,47,48,49,4a,53,54,55,56,57,58,59,
+ *                       5a,63,64,65,66,67,68,69,6a,73,74,75,76,77,78,79,7a,83,84,85,86,87,88,89,8a,92,93,94,95,96,97,98,99,9a,a2,a3,
+ *                       a4,a5,a6,a7,a8,a9,aa,b2,b3,b4,b5,b6,b7,b8,b9,ba,c2,c3,c4,c5,c6,c7,c8,c9,ca,d2,d3,d4,d5,d6,d7,d8,d9,da,e1,e2,
+ *                       e3,e4,e5,e6,e7,e8,e9,ea,f1,f2,f3,f4,f5,f6,f7,f8,f9,fa}   (hexadecimal)
+ *        AC1 BITS    = {0,2,1,2,4,4,3,4,7,5,4,4,0,1,2,119}
+ *        AC1 HUFFVAL = {00,01,02,03,11,04,05,21,31,06,12,41,51,07,61,71,13,22,32,81,08,14,42,91,a1,b1,c1,09,23,33,52,f0,15,62,72,d1,
+ *                       0a,16,24,34,e1,25,f1,17,18,19,1a,26,27,28,29,2a,35,36,37,38,39,3a,43,44,45,46,47,48,49,4a,53,54,55,56,57,58,
+ *                       59,5a,63,64,65,66,67,68,69,6a,73,74,75,76,77,78,79,7a,82,83,84,85,86,87,88,89,8a,92,93,94,95,96,97,98,99,9a,
+ *                       a2,a3,a4,a5,a6,a7,a8,a9,aa,b2,b3,b4,b5,b6,b7,b8,b9,ba,c2,c3,c4,c5,c6,c7,c8,c9,ca,d2,d3,d4,d5,d6,d7,d8,d9,da,
+ *                       e2,e3,e4,e5,e6,e7,e8,e9,ea,f2,f3,f4,f5,f6,f7,f8,f9,fa}
+ *      Codes are assigned as the standard does: in order of length, consecutive within a length, doubled from one length to the next.
+ *   6. SOS (DA): ncomp, per component its id and 00 for c = 0 or 11 otherwise, then 00 3F 00.
+ *
+ * Scan.  One component: its blocks in raster order.  Three: MCUs in raster order, ceil(bw / sub_w) x ceil(bh / sub_h) of them, each
+ * component 0's sub_h x sub_w blocks (rows outer), then one block of component 1 and one of component 2.  A block position beyond
+ * component 0's grid is a DUMMY block: all AC zero, DC that of the component's previous block — it codes as DC difference 0 and EOB.
+ * (The first block of a component in an MCU is never a dummy.)  Per block:
+ *   1. d = DC - pred[c]; pred starts at 0 and becomes this block's DC.
+ *   2. The category s is the bit length of |d|: code(DC table, s), then s bits of d (d >= 0) or of d - 1 (d < 0).
+ *   3. Coefficients 1..63 in zigzag order with a zero run r: for a non-zero v, while r > 15 write code(AC, 0xF0) and take 16 off r;
+ *      then code(AC, (r << 4) | s) and s bits as for the DC, and r = 0.
+ *   4. After the last coefficient, if r > 0: code(AC, 0x00).
+ * Component 0 uses DC0 / AC0, the others DC1 / AC1.  Bits fill bytes from the highest bit down; the last byte is completed with
+ * 1-bits; every FF byte of this data, that last byte included, is followed by 00.  Then FF D9.
+ *
+ * Output.  *size is always set to the file's size once it is known (every argument check passed).  When `capacity` is smaller —
+ * out_host may then be NULL — nothing is written and the call returns J2P_ESPACE: call again with that much room.  Nothing behind
+ * the file's last byte is touched. */
+#define J2P_ESPACE     -5   /* the caller's output buffer is too small; the size needed has been stored */
+typedef struct j2p_jpeg {
+        unsigned width, height, sub_w, sub_h;
+        const uint16_t *quant[3];
+} j2p_jpeg;
+/* The current iterate of nplane = 1 or 3 (solver, channel) pairs as that file: plane c quantised with quant[c] at the component's
+ * sampling by the kernel of j2p_planes_to_coefficients_sub, into device memory; coded there; header and data copied to out_host.
+ * planes[] may be one joint solver three times or three `-s` solvers on one device.  Whole-canvas solvers only (a band solver:
+ * J2P_ESTATE); the argument checks of j2p_planes_to_coefficients_sub apply to every plane with its grid, and the table rules above.
+ * Device memory is the scratch of planes[0].solver: a second call of the same size allocates nothing.  Synchronises, as
+ * j2p_planes_to_coefficients does (twice more on the way: the sizes of the two intermediate streams are read back, 8 bytes each, so
+ * that memory follows what the image needs and not the worst case). */
+int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
+                       size_t *size);
+/* The same coder on the caller's coefficients (host memory; coef_host[c]: component c's grid, block-major, as above) with no solver:
+ * transcoding, and what the directed tests use.  A coefficient outside [-1023, 1023] is J2P_EINVAL.  Device memory comes from the
+ * library's pool. */
+int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
+                       size_t capacity, size_t *size);
+/* A batch job that delivers the file (j2p_planes_to_jpeg on the worker): *spec is copied, with its tables, and travels next to the job;
+ * out / size must stay valid until j2p_batch_wait, after which *size is the file's size — also when the job failed with J2P_ESPACE.
+ * job->out_bits must be 0, out_coef[0] NULL and out_tensor.data NULL; not with `tile`; spec->width and height must equal job->out_w
+ * and out_h; the job has 1 or 3 channels (J2P_EINVAL at submit otherwise, as for the table rules).  samples: NULL, or as for
+ * j2p_batch_submit_samples.  out_planes is still honoured. */
+int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                          size_t capacity, size_t *size, int *ticket);
+
 #ifdef __cplusplus
 }
 #endif

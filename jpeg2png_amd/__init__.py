@@ -81,6 +81,15 @@ class _CSamples(ctypes.Structure):
                 ("stride_y", ctypes.c_ssize_t), ("stride_x", ctypes.c_ssize_t)]
 
 
+class _CJpeg(ctypes.Structure):
+    """j2p_jpeg: the image, its chroma subsampling and the quantisation tables of a JPEG file made on the device"""
+    _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("sub_w", ctypes.c_uint), ("sub_h", ctypes.c_uint),
+                ("quant", ctypes.c_void_p * 3)]
+
+
+J2P_ESPACE = -5         # the caller's output buffer is too small; the size needed has been stored
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -134,6 +143,7 @@ C_ABI_SYMBOLS = [
     "j2p_solver_coefficient_bytes", "j2p_solver_wide_footprint", "j2p_solver_shares_state", "j2p_solver_arena_bytes",
     "j2p_solver_debug_partials", "j2p_norm_selftest", "j2p_norm_selftest_bands",
     "j2p_solver_create_from_samples", "j2p_solver_download_coefficients", "j2p_solver_clipped_samples", "j2p_batch_submit_samples",
+    "j2p_planes_to_jpeg", "j2p_entropy_encode", "j2p_batch_submit_jpeg",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
@@ -317,6 +327,14 @@ def _bind(path):
         lib.j2p_solver_clipped_samples.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong)]
         lib.j2p_batch_submit_samples.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.c_uint,
                                                  ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_planes_to_jpeg"):
+        # (as above: an earlier commit's build does not write files)
+        lib.j2p_planes_to_jpeg.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_size_t)]
+        lib.j2p_entropy_encode.argtypes = [ctypes.c_int, ctypes.POINTER(_CJpeg), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        lib.j2p_batch_submit_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -625,6 +643,76 @@ def _sampling(subsampling):
     return sx, sy
 
 
+def quality_tables(quality, ncomp):
+    """libjpeg's quantisation tables for jpeg_set_quality(quality, TRUE): the base tables of Annex K scaled by the IJG rule and
+    clamped to 1..255 -> ncomp (1 or 3) uint16[64] arrays in natural order, luma first, then the chroma table twice"""
+    from .synth import quant_table
+    if ncomp not in (1, 3):
+        raise J2PError("quality_tables: three components or one")
+    q = min(max(int(quality), 1), 100)
+    return [quant_table("luma", q)] + [quant_table("chroma", q) for _ in range(ncomp - 1)]
+
+
+def _c_jpeg(width, height, ncomp, quality, quant_tables, subsampling):
+    """(j2p_jpeg, what it points into) of a file's keywords: quality or quant_tables, and subsampling=(sx, sy)"""
+    if (quality is None) == (quant_tables is None):
+        raise J2PError("jpeg: give quality or quant_tables, one of them")
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("jpeg: needs width and height")
+    tables = quality_tables(quality, ncomp) if quant_tables is None else list(quant_tables)
+    if len(tables) != ncomp:
+        raise J2PError("jpeg: one quantisation table per plane")
+    arrays = []
+    for q in tables:
+        q = np.asarray(q).reshape(-1)
+        if q.size != 64:
+            raise J2PError("jpeg: a quantisation table has 64 entries")
+        if q.min() < 1 or q.max() > 255:
+            raise J2PError("jpeg: quantisation steps must be 1..255 (the file is 8-bit baseline)")
+        arrays.append(np.ascontiguousarray(q, dtype=np.uint16))
+    sx, sy = _sampling(subsampling)
+    spec = _CJpeg(int(width), int(height), sx, sy)
+    for c in range(ncomp):
+        spec.quant[c] = arrays[c].ctypes.data
+    return spec, arrays
+
+
+def _jpeg_bytes(call, guess):
+    """what call(buffer address, capacity, size) leaves: once with room for `guess` bytes, again when the file is larger"""
+    size = ctypes.c_size_t(0)
+    for _ in range(2):
+        buf = np.empty(max(int(guess), size.value), dtype=np.uint8)
+        rc = call(buf.ctypes.data, buf.size, ctypes.byref(size))
+        if rc != J2P_ESPACE:
+            break
+    _check(rc)
+    return buf[:size.value].tobytes()
+
+
+def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0):
+    """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode): coefficients is a
+    list of 1 or 3 int16 arrays [blocks_h, blocks_w, 64] in natural order — component 0's grid ceil(height / 8) x ceil(width / 8),
+    the others' ceil of that over subsampling=(sx, sy) — every value in [-1023, 1023]; quant_tables: one per component, steps
+    1..255, the third equal to the second.  Byte for byte what libjpeg's jpeg_write_coefficients writes with its defaults."""
+    lib = load_library()
+    n = len(coefficients)
+    if n not in (1, 3):
+        raise J2PError("jpeg: three components or one")
+    spec, _held = _c_jpeg(width, height, n, None, quant_tables, subsampling)
+    bw, bh = -(-int(width) // 8), -(-int(height) // 8)
+    sx, sy = (spec.sub_w, spec.sub_h) if n == 3 else (1, 1)
+    arrays = []
+    for c, a in enumerate(coefficients):
+        grid = (bh, bw, 64) if c == 0 else (-(-bh // sy), -(-bw // sx), 64)
+        a = np.ascontiguousarray(a, dtype=np.int16)
+        if a.shape != grid:
+            raise J2PError(f"jpeg: component {c} has shape {a.shape}, its grid is {grid}")
+        arrays.append(a)
+    ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
+    total = sum(a.size for a in arrays)
+    return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
+
+
 class Solver:
     """Device-resident working set of one compute() call (include/jpeg2png_amd.h)."""
 
@@ -839,6 +927,25 @@ class Solver:
         ref = _CPlaneRef(self._h, int(c))
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
+
+    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=()):
+        """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg):
+        only the file comes down.  width x height: the image, cropped from the canvas's top left corner.  quality: libjpeg's
+        tables for it (quality_tables), or quant_tables: one 64-entry table per component, steps 1..255, natural order, the third
+        equal to the second.  subsampling=(sx, sy), 1 or 2 each: the sampling of components 1 and 2.  A solver of three channels
+        gives a colour file, one of one channel a greyscale file; others=(solver, solver): this solver's channel 0 and the
+        channel 0 of two more solvers (the separate solves of `-s`) give a colour file.  Whole-canvas solvers only.  Byte for
+        byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults."""
+        solvers = [self] + list(others)
+        if len(solvers) not in (1, 3):
+            raise J2PError("jpeg: others= takes the two other solvers of a colour file")
+        n = 3 if len(solvers) == 3 else self.nch
+        refs = (_CPlaneRef * 3)()
+        for c in range(n):
+            refs[c] = _CPlaneRef(solvers[c]._h, 0) if len(solvers) == 3 else _CPlaneRef(self._h, c)
+        spec, _held = _c_jpeg(width, height, n, quality, quant_tables, subsampling)
+        guess = 4096 + int(width) * int(height) * n // 4
+        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
 
     def stream(self):
         """the hipStream_t the solver launches on (an integer address)"""
@@ -1154,6 +1261,13 @@ class TiledSolver:
         self.close()
 
 
+class _JpegResult:
+    """what a jpeg= job of a Batch fills: the buffer and the file's size in it"""
+
+    def __init__(self, buffer, size):
+        self.buffer, self.size = buffer, size
+
+
 class Batch:
     """Images in flight over slots_per_device worker threads per GPU (include/jpeg2png_amd.h: j2p_batch_*).
     submit() returns a ticket; wait(ticket) returns the job's output: RGB samples [h, w, 3] (bits 8 / 16), greyscale
@@ -1173,8 +1287,13 @@ class Batch:
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None):
-        """samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
+               samples=None, jpeg=None):
+        """jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes} (with width and height; not
+        with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
+        JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
+        three planes.  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
+        reaches; a larger file fails the job with the size it needs in the message);
+        samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
         out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit
         samples as Solver.from_samples makes them (j2p_batch_submit_samples) — every output form is available.  Tensors on a GPU
         pin the job to a worker of that GPU (one of the batch's, and the output tensors'); what torch has queued for them on its
@@ -1217,6 +1336,19 @@ class Batch:
             if on_gpu:
                 # (the workers' streams know nothing of torch's: see tensor= below)
                 _torch().cuda.current_stream(on_gpu[0].device).synchronize()
+        cjpeg = None
+        if jpeg is not None:
+            if bits or quant_tables is not None or subsampling is not None or tensor is not None or outputs is not None or tile or out is not None:
+                raise J2PError("job: jpeg= excludes bits, quant_tables, subsampling, tensor=, outputs=, out and tile")
+            if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity"}:
+                raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
+            if n not in (1, 3):
+                raise J2PError("jpeg: three components or one")
+            cjpeg, jpeg_held = _c_jpeg(width, height, n, jpeg.get("quality"), jpeg.get("quant_tables"), jpeg.get("subsampling", (1, 1)))
+            sx, sy = (cjpeg.sub_w, cjpeg.sub_h) if n == 3 else (1, 1)
+            room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
+            jpeg_out = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8)
+            jpeg_size = ctypes.c_size_t(0)
         if outputs is not None:
             if tensor is not None or bits or quant_tables is not None or subsampling is not None or tile:
                 raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
@@ -1287,6 +1419,10 @@ class Batch:
             out = tensor
         elif layout != "chw" or scale is not None or bias is not None:
             raise J2PError("job: layout, scale and bias belong to tensor output (tensor=)")
+        elif cjpeg is not None:
+            job.out_w, job.out_h = int(width), int(height)
+            out = _JpegResult(jpeg_out, jpeg_size)
+            keep = (keep, jpeg_held)
         elif quant_tables is not None:
             if bits:
                 raise J2PError("job: coefficient output (quant_tables) needs bits = 0")
@@ -1346,6 +1482,10 @@ class Batch:
         t = ctypes.c_int()
         if csm is not None:
             keep = (keep, held)
+        if cjpeg is not None:
+            _check(self._lib.j2p_batch_submit_jpeg(self._h, ctypes.byref(job), csm, ctypes.byref(cjpeg), jpeg_out.ctypes.data, jpeg_out.size,
+                                                   ctypes.byref(jpeg_size), ctypes.byref(t)))
+        elif csm is not None:
             _check(self._lib.j2p_batch_submit_samples(self._h, ctypes.byref(job), csm, 0 if items is None else len(items), items, ctypes.byref(t)))
         elif items is not None:
             _check(self._lib.j2p_batch_submit_outputs(self._h, ctypes.byref(job), len(items), items, ctypes.byref(t)))
@@ -1361,6 +1501,8 @@ class Batch:
     def wait(self, ticket):
         out, _keep = self._pending.pop(ticket)
         _check(self._lib.j2p_batch_wait(self._h, ticket))
+        if isinstance(out, _JpegResult):
+            return out.buffer[:out.size.value].tobytes()
         return out
 
     def close(self):

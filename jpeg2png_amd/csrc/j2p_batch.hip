@@ -29,6 +29,15 @@
 
 namespace {
 
+// where the file of a j2p_batch_submit_jpeg job goes; spec.quant[] point into tables[]
+struct JpegOut {
+        bool on = false;
+        j2p_jpeg spec = {0, 0, 0, 0, {nullptr, nullptr, nullptr}};
+        uint16_t tables[3][64];
+        uint8_t *out = nullptr;
+        size_t capacity = 0, *size = nullptr;
+};
+
 struct Job {
         j2p_job desc;
         j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
@@ -37,6 +46,7 @@ struct Job {
         bool resampled = false;
         std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
         std::vector<j2p_samples> samples;   // j2p_batch_submit_samples: [channel] the solvers are made from these, not from planes[].data
+        JpegOut jpeg;                       // j2p_batch_submit_jpeg: the job delivers the file
         int ticket = 0;
         int device = -1;                    // tensor output, device samples: their device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -160,8 +170,9 @@ struct Engines {
 // unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
 // resize / resample (tensor jobs on one GPU only, at most one of the two): the tensor receives the image resized.
 // outputs (never empty when given; a job on one GPU without out_tensor): those tensors are filled from the solve.
+// jpeg (a job on one GPU with no other output but out_planes): the file is made from the solve.
 int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize, const j2p_resample *resample,
-                      const std::vector<j2p_output> *outputs)
+                      const std::vector<j2p_output> *outputs, const JpegOut *jpeg)
 {
         const unsigned nsolve = solves(d);
         if(!d.on_rows && !d.on_progress) {
@@ -210,6 +221,11 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p
                         // (never row-tiled: this one band is the whole canvas)
                         JOB_TRY(j2p_planes_to_tensors_resampled(ref, d.nchannel, d.out_w, d.out_h, (unsigned)outputs->size(), outputs->data()));
                         JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: every tensor complete, for any stream
+                        continue;
+                }
+                if(jpeg) {
+                        // (never row-tiled: this one band is the whole canvas)
+                        JOB_TRY(j2p_planes_to_jpeg(ref, d.nchannel, &jpeg->spec, jpeg->out, jpeg->capacity, jpeg->size));
                         continue;
                 }
                 if(d.out_bits || d.out_tensor.data) {
@@ -303,12 +319,12 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr);
+        return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr, nullptr);
 }
 
 // (samples: NULL, or [channel] what the solvers are made from instead of planes[].data)
 int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs,
-            const j2p_samples *samples)
+            const j2p_samples *samples, const JpegOut *jpeg)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
@@ -321,7 +337,7 @@ int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_re
                 }
                 JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, nch, &d.planes[k], d.weight[k], &d.pweight[k], d.iterations[k], whole, 0));
         }
-        return solve_and_deliver(d, eng.e, true, resize, resample, outputs);
+        return solve_and_deliver(d, eng.e, true, resize, resample, outputs, jpeg);
 }
 
 void worker_main(j2p_batch *b, int device)
@@ -360,7 +376,8 @@ void worker_main(j2p_batch *b, int device)
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
                         rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr,
-                                     job->outputs.empty() ? nullptr : &job->outputs, job->samples.empty() ? nullptr : job->samples.data());
+                                     job->outputs.empty() ? nullptr : &job->outputs, job->samples.empty() ? nullptr : job->samples.data(),
+                                     job->jpeg.on ? &job->jpeg : nullptr);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -422,11 +439,24 @@ int validate_samples(const j2p_job &d, const j2p_samples *samples, int *device)
 }
 
 // j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled, — nout != 0 —
-// j2p_batch_submit_outputs (never two of them); samples != NULL: j2p_batch_submit_samples (with nout or without; never with r or f)
+// j2p_batch_submit_outputs (never two of them); samples != NULL: j2p_batch_submit_samples (with nout or without; never with r or f);
+// jpeg != NULL: j2p_batch_submit_jpeg (with samples or without, and nothing else)
 int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs,
-           const j2p_samples *samples, int *ticket)
+           const j2p_samples *samples, const JpegOut *jpeg, int *ticket)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(jpeg) {
+                if(job->out_bits || job->out_coef[0] || job->out_tensor.data) {
+                        return j2p_fail(J2P_EINVAL, "job: a JPEG job needs out_bits 0, no out_coef and out_tensor.data NULL");
+                }
+                if(job->tile) { return j2p_fail(J2P_EINVAL, "job: JPEG output of a row-tiled job is not supported"); }
+                if(const char *why = j2p_jpeg_error(&jpeg->spec, job->nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+                if(jpeg->spec.width != job->out_w || jpeg->spec.height != job->out_h) {
+                        return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", jpeg->spec.width, jpeg->spec.height,
+                                        job->out_w, job->out_h);
+                }
+                if(!jpeg->size || (!jpeg->out && jpeg->capacity)) { return j2p_fail(J2P_EINVAL, "job: JPEG output needs out and size"); }
+        }
         int samples_device = -1;
         if(samples) {
                 if(const int rc = validate_samples(*job, samples, &samples_device); rc != J2P_OK) { return rc; }
@@ -456,6 +486,15 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
         }
         if(nout) { j->outputs.assign(outs, outs + nout); }
         if(samples) { j->samples.assign(samples, samples + job->nchannel); }
+        if(jpeg) {
+                // the tables travel with the job
+                j->jpeg = *jpeg;
+                j->jpeg.on = true;
+                for(unsigned c = 0; c < job->nchannel; c++) {
+                        memcpy(j->jpeg.tables[c], jpeg->spec.quant[c], sizeof(j->jpeg.tables[c]));
+                        j->jpeg.spec.quant[c] = j->jpeg.tables[c];
+                }
+        }
         if(job->out_tensor.data || nout) {
                 // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor(s)
                 int rc = validate_job(j->desc);
@@ -540,29 +579,41 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, ticket);
+        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
 {
-        return submit(b, job, r, nullptr, 0, nullptr, nullptr, ticket);
+        return submit(b, job, r, nullptr, 0, nullptr, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket)
 {
-        return submit(b, job, nullptr, r, 0, nullptr, nullptr, ticket);
+        return submit(b, job, nullptr, r, 0, nullptr, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const j2p_output outs[], int *ticket)
 {
         const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, ticket);
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, nullptr, ticket);
 }
 
 int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[], int *ticket)
 {
         const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, samples, ticket);
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, samples, nullptr, ticket);
+}
+
+int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
+                          size_t *size, int *ticket)
+{
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
+        JpegOut jpeg;
+        jpeg.spec = *spec;
+        jpeg.out = out;
+        jpeg.capacity = capacity;
+        jpeg.size = size;
+        return submit(b, job, nullptr, nullptr, 0, nullptr, samples, &jpeg, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

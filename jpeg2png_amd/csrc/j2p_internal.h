@@ -50,6 +50,26 @@ static inline const char *j2p_resample_error(const j2p_resample *r, unsigned w, 
         return NULL;
 }
 
+// the same for a j2p_jpeg of ncomp components (j2p_planes_to_jpeg, j2p_entropy_encode, j2p_batch_submit_jpeg)
+static inline const char *j2p_jpeg_error(const j2p_jpeg *spec, unsigned ncomp)
+{
+        if(!spec) { return "jpeg: spec is NULL"; }
+        if(ncomp != 1 && ncomp != 3) { return "jpeg: three components or one"; }
+        if(spec->width == 0 || spec->height == 0 || spec->width > 65535 || spec->height > 65535) { return "jpeg: width and height must be 1..65535"; }
+        if(ncomp == 3 && (spec->sub_w < 1 || spec->sub_w > 2 || spec->sub_h < 1 || spec->sub_h > 2)) { return "jpeg: sampling factors must be 1 or 2"; }
+        for(unsigned c = 0; c < ncomp; c++) {
+                if(!spec->quant[c]) { return "jpeg: a quantisation table is NULL"; }
+                for(int j = 0; j < 64; j++) {
+                        if(spec->quant[c][j] == 0) { return "jpeg: a quantisation step is zero"; }
+                        if(spec->quant[c][j] > 255) { return "jpeg: a quantisation step is above 255 (the file is 8-bit baseline)"; }
+                }
+        }
+        for(int j = 0; ncomp == 3 && j < 64; j++) {
+                if(spec->quant[2][j] != spec->quant[1][j]) { return "jpeg: quant[2] differs from quant[1] (the file has two table slots)"; }
+        }
+        return NULL;
+}
+
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
 // the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the
@@ -121,6 +141,8 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
 // still read the old block; a call that fits allocates nothing and waits for nothing).  One block: every call returns the same
 // memory, and stream order is what makes the next call's writes safe.
 int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out);
+// the size of that block now (0: none yet): a request beyond it gets ANOTHER block, and what the old one held is lost
+size_t j2p_solver_scratch_bytes(const j2p_solver *s);
 
 // ---- j2p_pool.hip ----
 // the device-memory pool, for a solver's arena and for buffers that live as long as one call: at least `bytes` bytes on

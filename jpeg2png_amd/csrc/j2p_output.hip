@@ -1,6 +1,6 @@
 // jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
-// or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), and to quantised JPEG
-// coefficients (include/jpeg2png_amd.h: the j2p_planes_* functions).
+// or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), to quantised JPEG
+// coefficients, and to the entropy-coded JPEG file itself (include/jpeg2png_amd.h: the j2p_planes_* functions, j2p_entropy_encode).
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
@@ -616,13 +616,22 @@ int j2p_debug_outputs_workgroups(unsigned w, unsigned h, unsigned n, const j2p_r
         return J2P_OK;
 }
 
+// what quantise_check found: enough to queue the kernel
+struct QuantiseLaunch {
+        j2p_solver_view s;
+        const float *src;               // the first canvas row of block row r0
+        unsigned rows;                  // canvas rows from there to the end of what the solver holds
+        QuantSteps steps;
+};
 // block rows [r0, r1) x blocks_w blocks of one (solver, channel) pair as quantised coefficients of the plane at
 // 1/sub_w x 1/sub_h of its resolution (k_quantise_blocks<sub_w, sub_h>): output block row r covers canvas rows
 // [8 * sub_h * r, 8 * sub_h * (r + 1)).  `whole`: called as a whole-canvas form, which band solvers refuse.
-static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
-                         unsigned r1, const uint16_t quant_table[64], int16_t *out_host)
+// In three steps, so that the JPEG file's coder can check every plane before it queues anything and keep the coefficients
+// on the device: quantise_check (arguments and state), quantise_queue (the launch), quantise_rows (both, and the download).
+static int quantise_check(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
+                          unsigned r1, const uint16_t quant_table[64], QuantiseLaunch &q)
 {
-        if(!plane || !quant_table || !out_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(!plane || !quant_table) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(blocks_w == 0 || r0 >= r1) { return j2p_fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
         const j2p_solver_view s = plane->solver ? j2p_solver_view_of(plane->solver) : j2p_solver_view{};
         if(whole && plane->solver && !s.whole) {
@@ -632,7 +641,7 @@ static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w,
                 return j2p_fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
         }
         if(!plane->solver || plane->channel >= s.nch) { return j2p_fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
-        QuantSteps steps;
+        QuantSteps &steps = q.steps;
         for(int j = 0; j < 64; j++) {
                 if(quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
                 steps.q[j] = (float)quant_table[j];
@@ -652,16 +661,33 @@ static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w,
         const unsigned first = (unsigned)(step_y * r0);
         const float *src = nullptr;
         if(const int rc = j2p_solver_row(plane->solver, plane->channel, first, &src); rc != J2P_OK) { return rc; }
+        q.s = s;
+        q.src = src;
+        q.rows = (unsigned)(row_end - first);
+        return J2P_OK;
+}
+// block rows [r0, r1) x blocks_w blocks of what quantise_check accepted into device memory `dout`, queued on `stream`
+static void quantise_queue(const QuantiseLaunch &q, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0, unsigned r1, hipStream_t stream,
+                           int16_t *dout)
+{
+        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
+        const auto kernel = sub_w == 2 ? (sub_h == 2 ? k_quantise_blocks<2, 2> : k_quantise_blocks<2, 1>)
+                                       : (sub_h == 2 ? k_quantise_blocks<1, 2> : k_quantise_blocks<1, 1>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, stream, q.src, q.s.W, q.rows, blocks_w, r1 - r0, q.steps, dout);
+}
+static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
+                         unsigned r1, const uint16_t quant_table[64], int16_t *out_host)
+{
+        if(!out_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        QuantiseLaunch q;
+        if(const int rc = quantise_check(plane, whole, sub_w, sub_h, blocks_w, r0, r1, quant_table, q); rc != J2P_OK) { return rc; }
+        const j2p_solver_view &s = q.s;
         DeviceGuard guard(s.device);
         const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
         void *dout = nullptr;
         size_t dout_bytes = 0;
         HIP_TRY(j2p_pool_take(s.device, bytes, &dout, &dout_bytes));
-        const unsigned long long groups = (unsigned long long)((blocks_w + 7) / 8) * (r1 - r0);
-        const auto kernel = sub_w == 2 ? (sub_h == 2 ? k_quantise_blocks<2, 2> : k_quantise_blocks<2, 1>)
-                                       : (sub_h == 2 ? k_quantise_blocks<1, 2> : k_quantise_blocks<1, 1>);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s.stream, src, s.W, (unsigned)(row_end - first),
-                           blocks_w, r1 - r0, steps, static_cast<int16_t *>(dout));
+        quantise_queue(q, sub_w, sub_h, blocks_w, r0, r1, s.stream, static_cast<int16_t *>(dout));
         hipError_t e = hipGetLastError();
         if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s.stream); }
         if(e == hipSuccess) { e = hipStreamSynchronize(s.stream); }
@@ -692,6 +718,326 @@ int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub
                                         unsigned block_row_begin, unsigned block_row_end, const uint16_t quant_table[64], int16_t *out_host)
 {
         return quantise_rows(plane, false, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
+}
+
+}  // extern "C"
+
+// ---- the JPEG file: k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_count, k_stuff_copy ----
+namespace {
+
+// Annex K.3 of the JPEG standard, as include/jpeg2png_amd.h states them: [0] the tables of component 0, [1] of the others
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kAcVals[2][162] = {
+        {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+         0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+         0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+         0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+         0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+         0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+         0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+         0xfa},
+        {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+         0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+         0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+         0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+         0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+         0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+         0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+         0xfa}};
+// natural index of zigzag position k (the kernels' kZigzagNatural)
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// the codes of one table, by symbol: in order of length, consecutive within a length, doubled from one length to the next
+void huffman_codes(const uint8_t bits[16], const uint8_t *vals, unsigned *by_symbol)
+{
+        unsigned code = 0, k = 0;
+        for(unsigned length = 1; length <= 16; length++) {
+                for(unsigned i = 0; i < bits[length - 1]; i++) { by_symbol[vals[k++]] = (length << 16) | code++; }
+                code <<= 1;
+        }
+}
+const HuffCodes &huffman_tables()
+{
+        static const HuffCodes tables = [] {
+                HuffCodes h;
+                memset(&h, 0, sizeof(h));
+                for(int t = 0; t < 2; t++) {
+                        huffman_codes(kDcBits[t], kDcVals, h.dc[t]);
+                        huffman_codes(kAcBits[t], kAcVals[t], h.ac[t]);
+                }
+                return h;
+        }();
+        return tables;
+}
+
+// everything in front of the entropy-coded data; at most 623 bytes.  Returns their number.
+constexpr size_t kJpegHeaderMax = 640;
+size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, uint8_t *out)
+{
+        uint8_t *p = out;
+        const auto segment = [&](uint8_t marker, size_t payload) {
+                *p++ = 0xff;
+                *p++ = marker;
+                *p++ = (uint8_t)((payload + 2) >> 8);
+                *p++ = (uint8_t)(payload + 2);
+        };
+        *p++ = 0xff;
+        *p++ = 0xd8;
+        static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+        segment(0xe0, sizeof(jfif));
+        memcpy(p, jfif, sizeof(jfif));
+        p += sizeof(jfif);
+        for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
+                segment(0xdb, 65);
+                *p++ = (uint8_t)t;
+                for(int k = 0; k < 64; k++) { *p++ = (uint8_t)spec.quant[t][kZigzag[k]]; }
+        }
+        segment(0xc0, 6 + 3 * ncomp);
+        *p++ = 8;
+        *p++ = (uint8_t)(spec.height >> 8);
+        *p++ = (uint8_t)spec.height;
+        *p++ = (uint8_t)(spec.width >> 8);
+        *p++ = (uint8_t)spec.width;
+        *p++ = (uint8_t)ncomp;
+        for(unsigned c = 0; c < ncomp; c++) {
+                *p++ = (uint8_t)(c + 1);
+                *p++ = c == 0 && ncomp == 3 ? (uint8_t)((spec.sub_w << 4) | spec.sub_h) : 0x11;
+                *p++ = c ? 1 : 0;
+        }
+        for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
+                segment(0xc4, 1 + 16 + 12);
+                *p++ = (uint8_t)t;
+                memcpy(p, kDcBits[t], 16);
+                memcpy(p + 16, kDcVals, 12);
+                p += 28;
+                segment(0xc4, 1 + 16 + 162);
+                *p++ = (uint8_t)(0x10 | t);
+                memcpy(p, kAcBits[t], 16);
+                memcpy(p + 16, kAcVals[t], 162);
+                p += 178;
+        }
+        segment(0xda, 1 + 2 * ncomp + 3);
+        *p++ = (uint8_t)ncomp;
+        for(unsigned c = 0; c < ncomp; c++) {
+                *p++ = (uint8_t)(c + 1);
+                *p++ = c ? 0x11 : 0x00;
+        }
+        *p++ = 0;
+        *p++ = 0x3f;
+        *p++ = 0;
+        return (size_t)(p - out);
+}
+
+// the component grids of a spec that j2p_jpeg_error accepted, and the scan's geometry but for the coefficients' addresses
+ScanGeom scan_geometry(const j2p_jpeg &spec, unsigned ncomp)
+{
+        ScanGeom g;
+        memset(&g, 0, sizeof(g));
+        g.ncomp = ncomp;
+        g.sub_w = ncomp == 3 ? spec.sub_w : 1;
+        g.sub_h = ncomp == 3 ? spec.sub_h : 1;
+        g.bw[0] = (spec.width + 7) / 8;
+        g.bh[0] = (spec.height + 7) / 8;
+        g.mcus_w = (g.bw[0] + g.sub_w - 1) / g.sub_w;
+        const unsigned mcus_h = (g.bh[0] + g.sub_h - 1) / g.sub_h;
+        for(unsigned c = 1; c < ncomp; c++) {
+                g.bw[c] = g.mcus_w;
+                g.bh[c] = mcus_h;
+        }
+        g.per_mcu = ncomp == 3 ? g.sub_w * g.sub_h + 2 : 1;
+        g.nslots = ncomp == 3 ? g.mcus_w * mcus_h * g.per_mcu : g.bw[0] * g.bh[0];       // (at most 6 * 8192^2 / 4)
+        return g;
+}
+
+size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
+// an exclusive sum of n counts on the stream: in -> out, sums: ceil(n / kScanTile) + 1 words, the last the total
+void queue_scan(hipStream_t stream, const unsigned *in, unsigned n, unsigned long long *sums, unsigned long long *out)
+{
+        const unsigned ntiles = (n + kScanTile - 1) / kScanTile;
+        hipLaunchKernelGGL(k_scan_sums, dim3(ntiles), dim3(256), 0, stream, in, n, sums);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, stream, sums, ntiles);
+        hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(256), 0, stream, in, n, static_cast<const unsigned long long *>(sums), out);
+}
+
+// The coder.  memory(bytes, &p, &moved): one block of device memory of at least that size which stays the same block while it
+// is large enough and is ANOTHER block (moved), contents lost, once it has to grow (j2p_solver_scratch); fill(stream, coef): queues what
+// leaves component c's coefficients at coef[c].  The block's layout, each part aligned to 256 bytes:
+//   [coefficients per component][len: nslots u32][off: nslots u64][sums: tiles + 1 u64]              known from the spec
+//   [stage: the stream, ceil(bits / 32) + 1 words][count: chunks u32][ffoff: chunks u64][sums]      known once the bits are
+//   [out: the stuffed bytes]                                                                        known once the FFs are
+// so the two totals are read back (8 bytes each, a wait each) and the block is asked for three times, the first two times
+// with a guess for what is not known yet; when it moved, what had been computed is computed again.  A second image of the
+// same size or smaller finds the block large enough at once.
+template <typename Memory, typename Fill>
+int encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, Memory memory, Fill fill, uint8_t *out_host, size_t capacity,
+                size_t *size)
+{
+        ScanGeom g = scan_geometry(spec, ncomp);
+        const HuffCodes &codes = huffman_tables();
+        const unsigned nslots = g.nslots, slot_tiles = (nslots + kScanTile - 1) / kScanTile;
+        size_t coef_at[3], fixed = 0;
+        for(unsigned c = 0; c < ncomp; c++) {
+                coef_at[c] = fixed;
+                fixed += round_up((size_t)g.bw[c] * g.bh[c] * 64 * sizeof(int16_t), 256);
+        }
+        const size_t coef_bytes = fixed;
+        const size_t len_at = fixed, off_at = len_at + round_up((size_t)nslots * 4, 256), sums_at = off_at + round_up((size_t)nslots * 8, 256);
+        fixed = sums_at + round_up(((size_t)slot_tiles + 1) * 8, 256);
+        char *base = nullptr;
+        const auto take = [&](size_t bytes, bool *moved) {
+                void *p = nullptr;
+                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
+                base = static_cast<char *>(p);
+                return (int)J2P_OK;
+        };
+        const auto at = [&](size_t offset) { return base + offset; };
+        // from the coefficients to the bit offsets
+        const auto lengths = [&] {
+                int16_t *coef[3] = {nullptr, nullptr, nullptr};
+                for(unsigned c = 0; c < ncomp; c++) {
+                        coef[c] = reinterpret_cast<int16_t *>(at(coef_at[c]));
+                        g.coef[c] = coef[c];
+                }
+                fill(stream, coef);
+                const unsigned per_workgroup = 4 * kEntropyIters;
+                hipLaunchKernelGGL(k_entropy_lengths, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
+                                   reinterpret_cast<unsigned *>(at(len_at)));
+                queue_scan(stream, reinterpret_cast<unsigned *>(at(len_at)), nslots, reinterpret_cast<unsigned long long *>(at(sums_at)),
+                           reinterpret_cast<unsigned long long *>(at(off_at)));
+        };
+        bool moved = false;
+        if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }     // (a file is rarely an eighth of its coefficients)
+        lengths();
+        unsigned long long bits = 0;
+        HIP_TRY(hipMemcpyAsync(&bits, at(sums_at) + (size_t)slot_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const size_t nbytes = (size_t)((bits + 7) / 8), stage_words = (size_t)((bits + 31) / 32) + 1;
+        const unsigned nchunks = (unsigned)((nbytes + kStuffChunk - 1) / kStuffChunk), chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
+        const size_t stage_at = fixed, count_at = stage_at + round_up(stage_words * 4, 256), ffoff_at = count_at + round_up((size_t)nchunks * 4, 256);
+        const size_t ffsums_at = ffoff_at + round_up((size_t)nchunks * 8, 256), out_at = ffsums_at + round_up(((size_t)chunk_tiles + 1) * 8, 256);
+        // from the bit offsets to the stream and where its FF bytes are
+        const auto pack = [&] {
+                (void)hipMemsetAsync(at(stage_at), 0, stage_words * 4, stream);
+                const unsigned per_workgroup = 4 * kEntropyIters;
+                hipLaunchKernelGGL(k_entropy_pack, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
+                                   reinterpret_cast<const unsigned long long *>(at(off_at)), reinterpret_cast<unsigned *>(at(stage_at)));
+                hipLaunchKernelGGL(k_stuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes,
+                                   nchunks, reinterpret_cast<unsigned *>(at(count_at)));
+                queue_scan(stream, reinterpret_cast<unsigned *>(at(count_at)), nchunks, reinterpret_cast<unsigned long long *>(at(ffsums_at)),
+                           reinterpret_cast<unsigned long long *>(at(ffoff_at)));
+        };
+        if(const int rc = take(out_at + nbytes + nbytes / 16 + 256, &moved); rc != J2P_OK) { return rc; }
+        if(moved) { lengths(); }
+        pack();
+        unsigned long long ffs = 0;
+        HIP_TRY(hipMemcpyAsync(&ffs, at(ffsums_at) + (size_t)chunk_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint8_t header[kJpegHeaderMax];
+        const size_t header_bytes = jpeg_header(spec, ncomp, header), data_bytes = nbytes + (size_t)ffs;
+        *size = header_bytes + data_bytes + 2;
+        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
+        if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
+        if(moved) {
+                lengths();
+                pack();
+        }
+        hipLaunchKernelGGL(k_stuff_copy, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes, nchunks,
+                           reinterpret_cast<const unsigned long long *>(at(ffoff_at)), reinterpret_cast<uint8_t *>(at(out_at)));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_host + header_bytes, at(out_at), data_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        memcpy(out_host, header, header_bytes);
+        out_host[header_bytes + data_bytes] = 0xff;
+        out_host[header_bytes + data_bytes + 1] = 0xd9;
+        return J2P_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
+{
+        if(!planes || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_error(spec, nplane)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        const ScanGeom g = scan_geometry(*spec, nplane);
+        // every check of every plane, before anything is queued
+        QuantiseLaunch q[3];
+        for(unsigned c = 0; c < nplane; c++) {
+                const unsigned sx = c ? g.sub_w : 1, sy = c ? g.sub_h : 1;
+                if(const int rc = quantise_check(&planes[c], true, sx, sy, g.bw[c], 0, g.bh[c], spec->quant[c], q[c]); rc != J2P_OK) { return rc; }
+                if(q[c].s.device != q[0].s.device) { return j2p_fail(J2P_EINVAL, "planes live on different devices"); }
+        }
+        DeviceGuard guard(q[0].s.device);
+        const hipStream_t stream = q[0].s.stream;
+        // everything is queued on planes[0].solver's stream: the other solvers' planes must be complete
+        for(unsigned c = 1; c < nplane; c++) {
+                if(planes[c].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(q[c].s.stream)); }
+        }
+        j2p_solver *const owner = planes[0].solver;
+        return encode_scan(
+                stream, *spec, nplane, [&](size_t bytes, void **p, bool *moved) {
+                        *moved = j2p_solver_scratch_bytes(owner) < bytes;
+                        return j2p_solver_scratch(owner, bytes, p);
+                },
+                [&](hipStream_t st, int16_t *const coef[3]) {
+                        for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
+                },
+                out_host, capacity, size);
+}
+
+int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                       size_t *size)
+{
+        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_error(spec, ncomp)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        const ScanGeom g = scan_geometry(*spec, ncomp);
+        size_t values[3] = {0, 0, 0};
+        for(unsigned c = 0; c < ncomp; c++) {
+                if(!coef_host[c]) { return j2p_fail(J2P_EINVAL, "jpeg: component %u has no coefficients", c); }
+                values[c] = (size_t)g.bw[c] * g.bh[c] * 64;
+                for(size_t i = 0; i < values[c]; i++) {
+                        if(coef_host[c][i] < -1023 || coef_host[c][i] > 1023) {
+                                return j2p_fail(J2P_EINVAL, "jpeg: component %u: coefficient %d (block %zu, index %zu) is outside [-1023, 1023]", c,
+                                                coef_host[c][i], i / 64, i % 64);
+                        }
+                }
+        }
+        int have = 0;
+        if(hipGetDeviceCount(&have) != hipSuccess || have <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
+        if(device < 0 || device >= have) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, have - 1); }
+        DeviceGuard guard(device);
+        hipStream_t stream = nullptr;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // one pooled block that grows as the solvers' scratch does
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        const int rc = encode_scan(
+                stream, *spec, ncomp,
+                [&](size_t bytes, void **p, bool *moved) {
+                        *moved = block_bytes < bytes;
+                        if(block_bytes < bytes) {
+                                HIP_TRY(hipStreamSynchronize(stream));
+                                j2p_pool_give(device, block, block_bytes);
+                                block = nullptr;
+                                block_bytes = 0;
+                                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
+                        }
+                        *p = block;
+                        return (int)J2P_OK;
+                },
+                [&](hipStream_t st, int16_t *const coef[3]) {
+                        for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
+                },
+                out_host, capacity, size);
+        (void)hipStreamSynchronize(stream);
+        j2p_pool_give(device, block, block_bytes);
+        (void)hipStreamDestroy(stream);
+        return rc;
 }
 
 }  // extern "C"

@@ -2237,6 +2237,8 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
         return J2P_OK;
 }
 
+size_t j2p_solver_scratch_bytes(const j2p_solver *s) { return s ? s->out_scratch_bytes : 0; }
+
 int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out)
 {
         if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
