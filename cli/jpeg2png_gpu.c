@@ -114,6 +114,8 @@ struct jpeg_in {
         unsigned w, h;
         unsigned n;             /* components read: 3, or 1 with -g (component 0 only) */
         struct component c[3];
+        uint8_t *file;          /* -d: the file's bytes, for the library to decode; c[].data are then NULL */
+        size_t file_size;
 };
 
 /* libjpeg's output_message hook: warnings (a truncated file, extraneous bytes ...) are printed and the
@@ -177,6 +179,54 @@ static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom, bool 
                 }
         }
         jpeg_destroy_decompress(&d);
+}
+
+/* -d: no libjpeg on the way in — the file's bytes go to the library, which reads the marker segments on the host (j2p_jpeg_parse, here,
+ * for the sizes) and Huffman-decodes the scan on the GPU that runs the job (j2p_batch_submit_file): jp gets the geometry and the tables,
+ * no coefficients, and keeps the bytes.  false, after one line on stderr: the file is valid but of a kind that decoder does not read
+ * (progressive, several scans, ...: J2P_ENOTSUP) and the caller goes on through libjpeg.  A damaged file dies with the library's message,
+ * here or when its job is waited for. */
+static bool read_file_for_gpu(const char *infile, FILE *in, struct jpeg_in *jp, unsigned zoom, bool grey)
+{
+        if(fseek(in, 0, SEEK_END) != 0) { die_perror("could not read input file `%s`", infile); }
+        const long size = ftell(in);
+        if(size < 0 || fseek(in, 0, SEEK_SET) != 0) { die_perror("could not read input file `%s`", infile); }
+        uint8_t *file = malloc((size_t)size + 1);
+        if(!file) { die("could not allocate memory for the file"); }
+        if(fread(file, 1, (size_t)size, in) != (size_t)size) { die_perror("could not read input file `%s`", infile); }
+        j2p_jpeg_info info;
+        const int rc = j2p_jpeg_parse(file, (size_t)size, &info);
+        if(rc == J2P_ENOTSUP) {
+                pthread_mutex_lock(&ui_lock);
+                if(bar_on) { bar_clear(); bar_on = false; }
+                fprintf(stderr, "jpeg2png: `%s`: %s; decoding with libjpeg\n", infile, j2p_last_error());
+                pthread_mutex_unlock(&ui_lock);
+                free(file);
+                rewind(in);
+                return false;
+        }
+        if(rc != J2P_OK) { die("`%s`: %s", infile, j2p_last_error()); }
+        if(!grey && info.ncomp != 3) { die("only 3 component jpegs are supported"); }
+        jp->w = info.width;
+        jp->h = info.height;
+        jp->n = grey ? 1 : 3;
+        for(unsigned c = 0; c < jp->n; c++) {
+                const j2p_jpeg_component *ci = &info.comp[c];
+                struct component *k = &jp->c[c];
+                for(int j = 0; j < 64; j++) {
+                        if(ci->quant[j] == 0) { die("invalid quantization table"); }
+                }
+                k->w = ci->blocks_w * 8;
+                k->h = ci->blocks_h * 8;
+                k->w_samp = ci->w_samp;
+                k->h_samp = ci->h_samp;
+                if(SIZE_MAX / k->h / k->w / (k->h_samp * zoom) / (k->w_samp * zoom) < 6) { die("jpeg is too big to fit in memory"); }
+                memcpy(k->quant, ci->quant, sizeof(k->quant));
+                k->data = NULL;
+        }
+        jp->file = file;
+        jp->file_size = (size_t)size;
+        return true;
 }
 
 /* ---- PNG out (the file side of png.c:20-78; pixels arrive already converted) ---- */
@@ -296,6 +346,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
+        bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
@@ -361,7 +412,10 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         FILE *in = fopen(infile, "rb");
         if(!in) { die_perror("could not open input file `%s`", infile); }
         struct jpeg_in jp;
-        read_coefficients(in, &jp, o->zoom, o->grey);
+        memset(&jp, 0, sizeof(jp));
+        if(!o->decode_on_gpu || !read_file_for_gpu(infile, in, &jp, o->zoom, o->grey)) {
+                read_coefficients(in, &jp, o->zoom, o->grey);
+        }
         fclose(in);
         /* zooming by z = the same solve with every component's sampling factors times z (compute.c:407-416): the
          * canvas, and the image written, are z times as wide and as high.  The library's canvas height limit is
@@ -399,7 +453,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 job.iterations[c] = o->iterations[c];
         }
         job.separate = o->grey || !o->joint;
-        job.tile = o->tile;
+        job.tile = o->tile && !jp.file;        /* (a row-tiled job takes no file) */
         {
                 /* (tests row-tile small images: the pixel gate of the library can be lowered from outside the program) */
                 const char *gate = getenv("J2P_TILE_MIN_BAND_PIXELS");
@@ -463,7 +517,8 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 for(int attempt = 0;; attempt++) {
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
-                        gpu_check(j2p_batch_submit_jpeg(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket));
+                        if(jp.file) { gpu_check(j2p_batch_submit_file_jpeg(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket)); }
+                        else { gpu_check(j2p_batch_submit_jpeg(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket)); }
                         const int rc = j2p_batch_wait(batch, ticket);
                         if(rc != J2P_ESPACE || attempt) {
                                 gpu_check(rc);
@@ -473,10 +528,12 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         capacity = file_bytes;
                 }
         } else {
-                gpu_check(j2p_batch_submit(batch, &job, &ticket));
+                if(jp.file) { gpu_check(j2p_batch_submit_file(batch, &job, jp.file, jp.file_size, 0, NULL, &ticket)); }
+                else { gpu_check(j2p_batch_submit(batch, &job, &ticket)); }
                 gpu_check(j2p_batch_wait(batch, ticket));
         }
         for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
+        free(jp.file);
         FILE *out = fopen(outfile, "wb");
         if(!out) { die_perror("could not open output file `%s`", outfile); }
         if(file) {
@@ -535,6 +592,9 @@ static void usage(void)
                "  -S, --chroma-subsampling 444|422|420|440\n"
                "                               with -j: chroma at half the resolution across (422), across and down (420)\n"
                "                               or down (440), every sample the mean of the solved values it covers\n"
+               "  -d, --decode-on-gpu          the GPU Huffman-decodes the input too (baseline files; others are read by libjpeg\n"
+               "                               after one line saying so): no libjpeg between the file's bytes and the solver;\n"
+               "                               such an image is not row-tiled\n"
                "  -e, --encode-on-gpu          with -j: the GPU also entropy-codes the file (default Huffman tables, the bytes\n"
                "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
@@ -555,7 +615,8 @@ int main(int argc, char **argv)
                 {"iterations", required_argument, NULL, 'i'}, {"probability-weight", required_argument, NULL, 'p'},
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
-                {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'}, {NULL, 0, NULL, 0}};
+                {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
+                {"decode-on-gpu", no_argument, NULL, 'd'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
                             .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
@@ -563,7 +624,7 @@ int main(int argc, char **argv)
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:e", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:ed", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -581,6 +642,7 @@ int main(int argc, char **argv)
                 case 'j': j_arg = optarg; break;
                 case 'S': S_arg = optarg; break;
                 case 'e': o.encode_on_gpu = true; break;
+                case 'd': o.decode_on_gpu = true; break;
                 default: help = true; break;
                 }
         }

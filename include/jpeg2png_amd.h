@@ -882,6 +882,112 @@ int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const co
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                           size_t capacity, size_t *size, int *ticket);
 
+/* Reading a JPEG file: the entropy-coded data of a baseline file Huffman-decoded ON THE DEVICE, so that a caller without libjpeg
+ * gets the file's true quantised coefficients at every quality.  For each component the result is the grid of whole blocks
+ * blocks_w x blocks_h of j2p_jpeg_info, block-major, 64 int16 in natural order — value for value what libjpeg's
+ * jpeg_read_coefficients delivers for the file.  This is the definition.
+ *
+ * Accepted.  SOF0 or SOF1 with 8-bit samples; Huffman coding; 1 or 3 components with sampling factors 1..4 and at most 10 blocks in
+ * an MCU; ONE scan that holds all components in the frame's order (Ss 0, Se 63, Ah/Al 0); any number of DQT (8- or 16-bit entries,
+ * slots 0..3) and DHT (slots 0..3) segments before the scan; DRI with RST0..7; fill bytes (FF FF) before markers; anything behind EOI.
+ *
+ * Markers.  FF D8, then segments: FF, the marker's byte, a big-endian 16-bit length that counts itself, the payload.
+ *   DQT (DB)  repeated: a byte (precision << 4) | slot, then 64 entries of 1 byte (precision 0) or 2 (precision 1) in zigzag order.
+ *   DHT (C4)  repeated: a byte (class << 4) | slot (class 0 DC, 1 AC), 16 counts BITS, then their sum symbols HUFFVAL.
+ *   SOF (C0, C1)  08, height, width (16 bits each), ncomp, per component: id, (h << 4) | v, quantisation slot.
+ *   DRI (DD)  the restart interval in MCUs, 16 bits; 0 switches restarts off.
+ *   SOS (DA)  ncomp, per component: id, (DC slot << 4) | AC slot; then 00 3F 00.  The entropy-coded data follows and ends at the
+ *             first FF whose next byte is none of 00, FF, D0..D7.  That marker must be EOI (D9), perhaps behind further segments.
+ * Codes.  As the standard assigns them: in order of length, consecutive within a length, doubled from one length to the next.  A
+ * table whose codes do not fit their lengths, or a DC table with a symbol above 15, is J2P_EFORMAT.
+ * Grids.  hmax, vmax: the largest factors.  Component c has ceil(ceil(width * h_c / hmax) / 8) x ceil(ceil(height * v_c / vmax) / 8)
+ * blocks.  One component: its blocks in raster order, an MCU is one block.  Three: ceil(width / (8 hmax)) x ceil(height / (8 vmax))
+ * MCUs in raster order, each component 0's v_0 x h_0 blocks (rows outer), then component 1's, then component 2's.  Blocks that pad a
+ * component's grid out to whole MCUs are decoded — their DC differences are links of the predictor chain — and not delivered.
+ * Block.  Bits are taken from the highest bit of each byte down.  A DC symbol s (0..15), then s bits v; an AC symbol (r << 4) | s:
+ * s = 0 and r = 15 skips 16 coefficients, any other s = 0 ends the block (the rest is zero), otherwise r zeros are skipped and s bits
+ * v give the coefficient at the next zigzag position.  Value extension: v < 2^(s-1) stands for v - (2^s - 1).  The DC is the
+ * difference plus the component's previous DC in scan order, 0 at the start of the scan and of every restart interval.
+ * Restarts.  With an interval of R MCUs, every R MCUs but the last are followed by 1-bits up to the byte boundary and the marker FF Dn,
+ * n counting 0..7 and round again; the DC predictors are 0 behind it.  Unstuffing: FF 00 is the data byte FF; FF FF is a fill byte.
+ *
+ * Refusals, with nothing delivered and nothing created.  J2P_EFORMAT: what libjpeg would warn about or die on — a truncated scan, a
+ * code in no table, a run past coefficient 63, a restart marker missing or out of sequence, a table the scan names that was never
+ * defined, a DC value outside int16, blocks missing or bytes left over when the data ends, a damaged segment.  J2P_ENOTSUP: valid
+ * files this decoder does not read — progressive, arithmetic, lossless or hierarchical coding, 12-bit samples, 2 or 4 components,
+ * several scans, a scan out of the frame's component order, DNL.  What the marker segments alone show is refused before a device is
+ * touched (j2p_jpeg_parse refuses exactly that, and touches nothing): no device is selected, nothing is allocated on one and nothing
+ * is queued.  The calls that take a file in either kind of memory ask the runtime what kind it is first (as sample input does), and a
+ * file in device memory is copied down for the parse.  Data too short for the frame's blocks (two bits each) and restart markers (two
+ * bytes each) counts as truncated: a file's claimed size alone makes the library allocate nothing. */
+#define J2P_EFORMAT    -6   /* the JPEG file is damaged                                        */
+#define J2P_ENOTSUP    -7   /* the JPEG file is valid, and of a kind this decoder does not read */
+typedef struct j2p_jpeg_component {
+        unsigned id, h_samp_factor, v_samp_factor;
+        unsigned blocks_w, blocks_h;       /* the delivered grid: the coefficient plane is blocks_w * 8 x blocks_h * 8 */
+        unsigned w_samp, h_samp;           /* hmax / h_samp_factor, vmax / v_samp_factor: j2p_plane's w_samp, h_samp */
+        unsigned quant_slot, dc_slot, ac_slot;
+        uint16_t quant[64];                /* the component's quantisation table, natural order */
+} j2p_jpeg_component;
+typedef struct j2p_jpeg_info {
+        unsigned width, height, ncomp;
+        unsigned extended;                 /* 1: SOF1 */
+        j2p_jpeg_component comp[3];
+        unsigned mcus_w, mcus_h, blocks_per_mcu;
+        unsigned restart_interval;         /* MCUs, 0: none */
+        unsigned intervals;                /* restart intervals in the scan (1 without restarts) */
+        size_t scan_begin, scan_end;       /* the entropy-coded data: file[scan_begin, scan_end) */
+} j2p_jpeg_info;
+/* Host only: the marker segments of the file -> *info (zeroed on failure).  What a caller needs to allocate with. */
+int j2p_jpeg_parse(const uint8_t *file, size_t size, j2p_jpeg_info *info);
+/* The file's coefficients on the host, no solver involved: the mirror of j2p_entropy_encode.  file: HOST memory, or DEVICE memory of
+ * `device` (its entropy-coded data is read in place; the file is copied down once for the host's parse; any other kind of memory is
+ * J2P_EINVAL, as for j2p_samples).
+ * coef_host[c]: room for comp[c].blocks_w * blocks_h * 64 values — untouched unless the call returns J2P_OK.  quant (may be NULL):
+ * receives the components' tables.  info (may be NULL): as j2p_jpeg_parse.  Device memory comes from the library's pool. */
+int j2p_entropy_decode(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64],
+                       j2p_jpeg_info *info);
+/* The same with the subsequence length in bits given (0: the default, J2P_DECODE_SUBSEQUENCE_BITS; otherwise
+ * J2P_DECODE_SUBSEQUENCE_MIN..MAX, any value in between, J2P_EINVAL outside) and statistics returned (stats may be NULL).  The
+ * result does not depend on the length; the test hook that makes an image of a few blocks cross every boundary. */
+#define J2P_DECODE_SUBSEQUENCE_BITS 1024u
+#define J2P_DECODE_SUBSEQUENCE_MIN 32u     /* longer than the longest symbol the kernels read (16 + 15 bits) */
+#define J2P_DECODE_SUBSEQUENCE_MAX 65536u
+#define J2P_DECODE_STATS_ROUNDS 16
+typedef struct j2p_decode_stats {
+        unsigned subsequences;             /* in the whole scan */
+        unsigned intervals;                /* restart intervals */
+        unsigned rounds;                   /* rounds in which a subsequence's entry state changed, the first included */
+        unsigned recomputed[J2P_DECODE_STATS_ROUNDS];   /* subsequences decoded again in round r (the first 16 rounds) */
+        unsigned long long data_bytes;     /* the entropy-coded data without stuffing and markers */
+        double decode_ms;                  /* host clock around the decode alone: the data's way up, every kernel, the read-backs of the
+                                              rounds — not the coefficients' way down */
+} j2p_decode_stats;
+int j2p_entropy_decode_ex(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64],
+                          j2p_jpeg_info *info, unsigned subsequence_bits, j2p_decode_stats *stats);
+/* A whole-canvas solver of the file's 1 or 3 components (one: the greyscale solver), its coefficients decoded on the device straight
+ * into the solver's resident coefficient buffers: from there on, bit for bit, the solver j2p_solver_create makes from the same
+ * coefficients with fdata == NULL.  file as for j2p_entropy_decode; pweight: one per component.  A refused file creates nothing. */
+int j2p_solver_create_from_jpeg(j2p_solver **out, int device, void *stream, const uint8_t *file, size_t size, float weight,
+                                const float pweight[], unsigned iterations, j2p_jpeg_info *info);
+/* A batch job whose solvers are made from a file: file / size are the file's bytes — HOST memory, or DEVICE memory of a GPU of the
+ * batch, which pins the job to a worker of that GPU as device samples do — and stay valid until j2p_batch_wait; they are not copied
+ * (a device file is copied down once, at submit, for the parse).  The marker segments are read at submit, on the caller's thread:
+ * what they show is refused there (J2P_EFORMAT, J2P_ENOTSUP) and no ticket is given; what only the data shows fails the job
+ * (j2p_batch_wait returns J2P_EFORMAT) and no other.  The worker decodes the scan once on its GPU and makes every solver of the job
+ * from that — the joint solve, the three of `separate`, or component 0 alone.  job->planes[c] carry no data (data and fdata NULL):
+ * w and h, where set, must be the file's component's; w_samp and h_samp left zero are the file's (a zooming caller gives the file's
+ * times the zoom); quant_table is ignored, the file's is used; nchannel 0 means the file's component count, otherwise it must be that
+ * count, or 1 for component 0 of a three-component file; out_w and out_h left zero are the file's width and height.  n / outs are
+ * those of j2p_batch_submit_outputs; with n == 0 or outs == NULL the job's own output fields apply, so every output form a
+ * coefficient job has is available.  Not with `tile` (J2P_EINVAL). */
+int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, unsigned n, const j2p_output outs[],
+                          int *ticket);
+/* File in and file out in one job: the solvers from `file` as above, the result as the JPEG file of j2p_batch_submit_jpeg (spec, out,
+ * capacity, out_size and the job's rules as there).  Bytes go in and bytes come out; no coefficient crosses the bus. */
+int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                               size_t capacity, size_t *out_size, int *ticket);
+
 #ifdef __cplusplus
 }
 #endif

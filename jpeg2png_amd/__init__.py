@@ -25,7 +25,8 @@ J2P_TILE_ROWS = 16
 
 
 class J2PError(RuntimeError):
-    pass
+    """code: the library's J2P_E* code where the error came from a library call (J2P_EFORMAT, J2P_ENOTSUP, ...), else None"""
+    code = None
 
 
 class _CPlane(ctypes.Structure):
@@ -88,6 +89,32 @@ class _CJpeg(ctypes.Structure):
 
 
 J2P_ESPACE = -5         # the caller's output buffer is too small; the size needed has been stored
+J2P_EFORMAT = -6        # a JPEG file given to the library is damaged
+J2P_ENOTSUP = -7        # a JPEG file given to the library is valid, and of a kind its decoder does not read
+
+
+class _CJpegComponent(ctypes.Structure):
+    """j2p_jpeg_component"""
+    _fields_ = [("id", ctypes.c_uint), ("h_samp_factor", ctypes.c_uint), ("v_samp_factor", ctypes.c_uint),
+                ("blocks_w", ctypes.c_uint), ("blocks_h", ctypes.c_uint), ("w_samp", ctypes.c_uint), ("h_samp", ctypes.c_uint),
+                ("quant_slot", ctypes.c_uint), ("dc_slot", ctypes.c_uint), ("ac_slot", ctypes.c_uint), ("quant", ctypes.c_uint16 * 64)]
+
+
+class _CJpegInfo(ctypes.Structure):
+    """j2p_jpeg_info: what j2p_jpeg_parse reads from a file's marker segments"""
+    _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("ncomp", ctypes.c_uint), ("extended", ctypes.c_uint),
+                ("comp", _CJpegComponent * 3), ("mcus_w", ctypes.c_uint), ("mcus_h", ctypes.c_uint), ("blocks_per_mcu", ctypes.c_uint),
+                ("restart_interval", ctypes.c_uint), ("intervals", ctypes.c_uint), ("scan_begin", ctypes.c_size_t), ("scan_end", ctypes.c_size_t)]
+
+
+J2P_DECODE_SUBSEQUENCE_BITS, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX = 1024, 32, 65536
+J2P_DECODE_STATS_ROUNDS = 16
+
+
+class _CDecodeStats(ctypes.Structure):
+    """j2p_decode_stats"""
+    _fields_ = [("subsequences", ctypes.c_uint), ("intervals", ctypes.c_uint), ("rounds", ctypes.c_uint),
+                ("recomputed", ctypes.c_uint * J2P_DECODE_STATS_ROUNDS), ("data_bytes", ctypes.c_ulonglong), ("decode_ms", ctypes.c_double)]
 
 
 class _CJob(ctypes.Structure):
@@ -144,6 +171,8 @@ C_ABI_SYMBOLS = [
     "j2p_solver_debug_partials", "j2p_norm_selftest", "j2p_norm_selftest_bands",
     "j2p_solver_create_from_samples", "j2p_solver_download_coefficients", "j2p_solver_clipped_samples", "j2p_batch_submit_samples",
     "j2p_planes_to_jpeg", "j2p_entropy_encode", "j2p_batch_submit_jpeg",
+    "j2p_jpeg_parse", "j2p_entropy_decode", "j2p_entropy_decode_ex", "j2p_solver_create_from_jpeg",
+    "j2p_batch_submit_file", "j2p_batch_submit_file_jpeg",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
@@ -335,6 +364,19 @@ def _bind(path):
                                            ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         lib.j2p_batch_submit_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_entropy_decode_ex"):
+        # (as above: an earlier commit's build does not read files)
+        lib.j2p_jpeg_parse.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpegInfo)]
+        lib.j2p_entropy_decode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+                                           ctypes.POINTER(_CJpegInfo)]
+        lib.j2p_entropy_decode_ex.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+                                              ctypes.POINTER(_CJpegInfo), ctypes.c_uint, ctypes.POINTER(_CDecodeStats)]
+        lib.j2p_batch_submit_file.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint,
+                                              ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_batch_submit_file_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
+                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_solver_create_from_jpeg.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_uint, ctypes.POINTER(_CJpegInfo)]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -351,7 +393,9 @@ def _bind(path):
 
 def _check(rc):
     if rc != 0:
-        raise J2PError(f"jpeg2png_amd error {rc}: {load_library().j2p_last_error().decode()}")
+        err = J2PError(f"jpeg2png_amd error {rc}: {load_library().j2p_last_error().decode()}")
+        err.code = rc
+        raise err
 
 
 def debug_build():
@@ -713,6 +757,59 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
     return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
 
 
+def _file_bytes(data):
+    """(address, size, what keeps it alive) of a JPEG file given as bytes-like host data, or as a 1-D uint8 torch tensor in device
+    memory, which the library reads in place"""
+    if hasattr(data, "data_ptr"):
+        if str(data.dtype) != "torch.uint8" or data.dim() != 1 or not data.is_contiguous():
+            raise J2PError("a file in a tensor is a contiguous 1-D uint8 tensor")
+        return data.data_ptr(), int(data.numel()), data
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    return a.ctypes.data, a.size, a
+
+
+def _jpeg_info_dict(info):
+    comps = [{"id": k.id, "h_samp_factor": k.h_samp_factor, "v_samp_factor": k.v_samp_factor, "blocks_w": k.blocks_w, "blocks_h": k.blocks_h,
+              "w": k.blocks_w * 8, "h": k.blocks_h * 8, "w_samp": k.w_samp, "h_samp": k.h_samp, "quant_slot": k.quant_slot, "dc_slot": k.dc_slot,
+              "ac_slot": k.ac_slot, "quant_table": np.array(k.quant, dtype=np.uint16)} for k in info.comp[:info.ncomp]]
+    return {"width": info.width, "height": info.height, "extended": bool(info.extended), "components": comps, "mcus_w": info.mcus_w,
+            "mcus_h": info.mcus_h, "blocks_per_mcu": info.blocks_per_mcu, "restart_interval": info.restart_interval, "intervals": info.intervals,
+            "scan_begin": info.scan_begin, "scan_end": info.scan_end}
+
+
+def jpeg_parse(data):
+    """j2p_jpeg_parse: the marker segments of a baseline JPEG file (host bytes), read by the library's C parser without touching a
+    device -> dict of width, height, components (per component id, sampling factors, the block grid, table slots, quant_table),
+    the MCU grid, restart_interval, intervals and the byte range of the entropy-coded data.  J2PError with code J2P_EFORMAT
+    (damaged) or J2P_ENOTSUP (valid, not read: progressive, arithmetic, 12-bit, several scans, ...)."""
+    addr, size, _keep = _file_bytes(bytes(data))
+    info = _CJpegInfo()
+    _check(load_library().j2p_jpeg_parse(addr, size, ctypes.byref(info)))
+    return _jpeg_info_dict(info)
+
+
+def entropy_decode(data, device=0, subsequence_bits=0, stats=False):
+    """the quantised coefficients of a baseline JPEG file, Huffman-decoded on the GPU (j2p_entropy_decode): a list of 1 or 3 int16
+    arrays [blocks_h, blocks_w, 64] in natural order — what libjpeg's jpeg_read_coefficients delivers.  data: bytes, or a 1-D uint8
+    torch tensor on the device, read in place.  subsequence_bits: 0 for the default, or J2P_DECODE_SUBSEQUENCE_MIN..MAX (the result
+    does not depend on it).  stats=True: (arrays, dict of subsequences, intervals, rounds, recomputed per round, data_bytes).
+    J2PError with code J2P_EFORMAT for a damaged file, J2P_ENOTSUP for a valid one of another kind."""
+    lib = load_library()
+    addr, size, _keep = _file_bytes(data)
+    info = _CJpegInfo()
+    # (the grids' sizes are needed before the call, so the marker segments are read here too — microseconds of host work; a device
+    # tensor's from a copy)
+    parsed = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data)
+    arrays = [np.full((k["blocks_h"], k["blocks_w"], 64), 0, dtype=np.int16) for k in parsed["components"]]
+    ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
+    st = _CDecodeStats()
+    _check(lib.j2p_entropy_decode_ex(int(device), addr, size, ptrs, None, ctypes.byref(info), int(subsequence_bits), ctypes.byref(st)))
+    if not stats:
+        return arrays
+    return arrays, {"subsequences": st.subsequences, "intervals": st.intervals, "rounds": st.rounds,
+                    "recomputed": list(st.recomputed)[:min(st.rounds, J2P_DECODE_STATS_ROUNDS)], "data_bytes": st.data_bytes, "decode_ms": st.decode_ms}
+
+
 class Solver:
     """Device-resident working set of one compute() call (include/jpeg2png_amd.h)."""
 
@@ -793,6 +890,41 @@ class Solver:
         _check(lib.j2p_solver_create_from_samples(ctypes.byref(h), int(device), stream, self.nch, cpl, csm, float(weight), pw, int(iterations)))
         del keep, held
         self._geom = [(int(p.w), int(p.h)) for p in planes]
+        self._adopt(h, device)
+        return self
+
+    @classmethod
+    def from_jpeg(cls, data, weight, pweight, iterations, device=0, stream=None):
+        """A solver made from a baseline JPEG FILE (j2p_solver_create_from_jpeg): the file's entropy-coded data is Huffman-decoded
+        on the GPU straight into the solver's resident coefficients — no libjpeg, and the file's true coefficients at every
+        quality.  data: bytes, or a 1-D uint8 torch tensor (on the solver's GPU: the scan is read in place).  pweight: one per
+        component of the file (1 or 3).  From there on the solver is the one Solver(planes with those coefficients) is.
+        self.jpeg holds what jpeg_parse returns.  J2PError with code J2P_EFORMAT / J2P_ENOTSUP for files that are refused."""
+        self = cls.__new__(cls)
+        lib = load_library()
+        self._lib = lib
+        self._h = None
+        addr, size, held = _file_bytes(data)
+        # (the marker segments first, on the host: a refused file and a pweight list of the wrong length cost no GPU work)
+        head = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data)
+        if len(pweight) != len(head["components"]):
+            raise J2PError(f"from_jpeg: {len(pweight)} pweights for a file of {len(head['components'])} components")
+        if hasattr(data, "data_ptr") and data.is_cuda:
+            torch = _torch()
+            dev = torch.device("cuda", int(device))
+            ours = torch.cuda.Stream(device=dev) if stream is None else torch.cuda.ExternalStream(int(stream), device=dev)
+            ours.wait_stream(torch.cuda.current_stream(dev))
+            ours.synchronize()          # (the host parses a copy of the file before anything is queued)
+            self._torch_stream = ours
+            stream = ours.cuda_stream
+        pw = (ctypes.c_float * len(pweight))(*[float(x) for x in pweight])
+        info = _CJpegInfo()
+        h = ctypes.c_void_p()
+        _check(lib.j2p_solver_create_from_jpeg(ctypes.byref(h), int(device), stream, addr, size, float(weight), pw, int(iterations), ctypes.byref(info)))
+        del held
+        self.jpeg = _jpeg_info_dict(info)
+        self.nch = info.ncomp
+        self._geom = [(k["w"], k["h"]) for k in self.jpeg["components"]]
         self._adopt(h, device)
         return self
 
@@ -1287,8 +1419,15 @@ class Batch:
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None, jpeg=None):
-        """jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes} (with width and height; not
+               samples=None, jpeg=None, file=None):
+        """file=bytes or a 1-D uint8 torch tensor (on a GPU of the batch: read in place, and the job runs there): the job's solvers
+        are made from that baseline JPEG file, Huffman-decoded on the worker's GPU (j2p_batch_submit_file, Solver.from_jpeg) —
+        planes may be None (all of the file's components at the file's sampling) or Plane-likes with data=None, as
+        jpeg_header(file)["planes"] are; width and height default to the file's.  Every output form is available (bits, tensor=,
+        outputs=, quant_tables=, jpeg=: file in and file out in one job); not with samples=, tile, nor a resized tensor outside
+        outputs=.  A file the parser refuses raises J2PError (code J2P_EFORMAT / J2P_ENOTSUP) here; damage only its data
+        shows fails the job in wait(), and no other job.
+        jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes} (with width and height; not
         with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
         JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
         three planes.  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
@@ -1319,6 +1458,23 @@ class Batch:
         tile=True: the image is row-tiled over the batch's devices instead of solved on one of them;
         tile_devices=(first, count): over that slice of the batch's device list only; on_progress(n): called from the worker
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
+        cfile = None
+        if file is not None:
+            if samples is not None or tile:
+                raise J2PError("job: file= excludes samples= and tile")
+            if filter is not None or out_width is not None or out_height is not None or box is not None:
+                raise J2PError("job: with file= a resized tensor is an output of outputs=")
+            cfile = _file_bytes(file)
+            head = jpeg_parse(file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file)
+            if planes is None:
+                planes = [Plane(k["w"], k["h"], k["w_samp"], k["h_samp"], None, k["quant_table"]) for k in head["components"]]
+            if any(p.data is not None or p.fdata is not None for p in planes):
+                raise J2PError("job: with file= the planes carry neither data nor fdata")
+            width = head["width"] if width is None else width
+            height = head["height"] if height is None else height
+            if hasattr(file, "data_ptr") and file.is_cuda:
+                # (the workers' streams know nothing of torch's: see tensor= below)
+                _torch().cuda.current_stream(file.device).synchronize()
         n = len(planes)
         resize = None
         items = None
@@ -1482,7 +1638,15 @@ class Batch:
         t = ctypes.c_int()
         if csm is not None:
             keep = (keep, held)
-        if cjpeg is not None:
+        if cfile is not None:
+            keep = (keep, cfile[2])
+            if cjpeg is not None:
+                _check(self._lib.j2p_batch_submit_file_jpeg(self._h, ctypes.byref(job), cfile[0], cfile[1], ctypes.byref(cjpeg), jpeg_out.ctypes.data,
+                                                            jpeg_out.size, ctypes.byref(jpeg_size), ctypes.byref(t)))
+            else:
+                _check(self._lib.j2p_batch_submit_file(self._h, ctypes.byref(job), cfile[0], cfile[1], 0 if items is None else len(items), items,
+                                                       ctypes.byref(t)))
+        elif cjpeg is not None:
             _check(self._lib.j2p_batch_submit_jpeg(self._h, ctypes.byref(job), csm, ctypes.byref(cjpeg), jpeg_out.ctypes.data, jpeg_out.size,
                                                    ctypes.byref(jpeg_size), ctypes.byref(t)))
         elif csm is not None:

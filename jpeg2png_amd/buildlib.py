@@ -40,15 +40,19 @@ def _newer(target, sources):
 # every translation unit with the project headers it includes, directly or through another: what an edit rebuilds
 UNIT_HEADERS = {
     "j2p_solver.hip": ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h", "j2p_geometry.h"),
-    "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
+    "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_decode_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
     "j2p_pool.hip": ("j2p_hip_host.h", "j2p_internal.h"),
     "j2p_tiled.hip": ("j2p_internal.h", "j2p_geometry.h"),
     "j2p_batch.hip": ("j2p_internal.h", "j2p_geometry.h"),
     "compute_host.c": ("j2p_internal.h", "j2p_geometry.h"),
+    "j2p_jpeg_parse.c": ("j2p_internal.h",),
 }
 # the units the experiments build takes from the release build: they have no knobs
 NO_KNOBS = ("j2p_output.hip", "j2p_pool.hip")
 HIP_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".hip"))
+# the pure C units (host code, gcc): the same objects in every build of the library
+C_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".c"))
+C_OBJECTS = tuple(os.path.join(CSRC, u.replace(".c", ".o")) for u in C_UNITS)
 # the units that hold device code (the others are host code).  Only the solver's knows -DJ2P_DEBUG, -DJ2P_TRACE and
 # -DJ2P_EXP_*: the checked build and the A/B variants compile it alone and take every other object from the release build
 DEVICE_UNITS = ("j2p_solver.hip", "j2p_output.hip")
@@ -83,10 +87,11 @@ def build(force=False, verbose=False):
         objs.append(obj)
         if force or _newer(obj, _deps(u)):
             jobs.append([hipcc, *HIP_FLAGS, *extra, "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj])
-    csrc, cobj = os.path.join(CSRC, "compute_host.c"), os.path.join(CSRC, "compute_host.o")
-    objs.append(cobj)
-    if force or _newer(cobj, _deps("compute_host.c")):
-        jobs.append([gcc, "-std=c11", "-O2", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-I", INCLUDE, "-c", csrc, "-o", cobj])
+    for u, cobj in zip(C_UNITS, C_OBJECTS):
+        objs.append(cobj)
+        if force or _newer(cobj, _deps(u)):
+            jobs.append([gcc, "-std=c11", "-O2", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-I", INCLUDE, "-I", CSRC, "-c", os.path.join(CSRC, u),
+                         "-o", cobj])
     if not jobs and not _newer(LIB, objs):
         return LIB
     from concurrent.futures import ThreadPoolExecutor
@@ -113,7 +118,7 @@ def build_debug(force=False, verbose=False):
     if force or _newer(obj, _deps("j2p_solver.hip")):
         _run([hipcc, *HIP_FLAGS, "-DJ2P_DEBUG", "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj], verbose)
     objs = [obj] + [os.path.join(CSRC, u.replace(".hip", ".o")) for u in HIP_UNITS if u != "j2p_solver.hip"]
-    objs.append(os.path.join(CSRC, "compute_host.o"))
+    objs.extend(C_OBJECTS)
     if force or _newer(DEBUG_LIB, objs):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-lpthread", "-Wl,-soname,libjpeg2png_amd_debug.so", "-o", DEBUG_LIB], verbose)
     return DEBUG_LIB
@@ -143,7 +148,7 @@ def build_experiments(force=False, verbose=False):
         objs.append(obj)
         if force or _newer(obj, _deps(u)):
             jobs.append([hipcc, *HIP_FLAGS, "-DJ2P_EXPERIMENTS", "-I", INCLUDE, "-I", CSRC, "-c", src, "-o", obj])
-    objs.append(os.path.join(CSRC, "compute_host.o"))
+    objs.extend(C_OBJECTS)
     if jobs or _newer(EXP_LIB, objs):
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=4) as ex:

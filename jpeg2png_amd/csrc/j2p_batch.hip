@@ -15,6 +15,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -38,6 +39,13 @@ struct JpegOut {
         size_t capacity = 0, *size = nullptr;
 };
 
+// the file of a j2p_batch_submit_file job: parsed at submit (a copy of it, for a file in device memory), decoded by the worker
+struct FileIn {
+        std::unique_ptr<j2p_jpeg_parsed> parsed;
+        const uint8_t *data = nullptr;      // the caller's bytes, valid until j2p_batch_wait
+        bool on_device = false;
+};
+
 struct Job {
         j2p_job desc;
         j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
@@ -47,6 +55,7 @@ struct Job {
         std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
         std::vector<j2p_samples> samples;   // j2p_batch_submit_samples: [channel] the solvers are made from these, not from planes[].data
         JpegOut jpeg;                       // j2p_batch_submit_jpeg: the job delivers the file
+        FileIn file;                        // j2p_batch_submit_file: the solvers' coefficients are decoded from this file
         int ticket = 0;
         int device = -1;                    // tensor output, device samples: their device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -322,12 +331,45 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
         return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr, nullptr);
 }
 
-// (samples: NULL, or [channel] what the solvers are made from instead of planes[].data)
+// a file job's engines: the file's scan decoded ONCE on the worker's GPU into pooled grids (j2p_decode_file: all components,
+// whichever of them the job solves), from which every solver of the job copies its channels on the device
+int create_from_file(const j2p_job &d, int device, const FileIn &file, Engines &eng)
+{
+        const j2p_jpeg_info &f = file.parsed->info;
+        size_t at[3] = {0, 0, 0}, bytes = 0;
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                at[c] = bytes;
+                bytes += ((size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64 * sizeof(int16_t) + 255) / 256 * 256;
+        }
+        hipStream_t stream = nullptr;
+        if(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { return j2p_fail(J2P_EDEVICE, "job: no stream for the file's decode"); }
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        int rc = J2P_OK;
+        if(j2p_pool_take(device, bytes, &block, &block_bytes) != hipSuccess) { rc = j2p_fail(J2P_ENOMEM, "job: no device memory for the file's coefficients"); }
+        int16_t *coef[3] = {nullptr, nullptr, nullptr};
+        for(unsigned c = 0; rc == J2P_OK && c < f.ncomp; c++) { coef[c] = reinterpret_cast<int16_t *>(static_cast<char *>(block) + at[c]); }
+        if(rc == J2P_OK) { rc = j2p_decode_file(device, stream, file.parsed.get(), file.data + f.scan_begin, file.on_device, 0, coef, nullptr); }
+        for(unsigned k = 0; rc == J2P_OK && k < solves(d); k++) {
+                const unsigned nch = d.separate ? 1 : d.nchannel;
+                rc = j2p_solver_create_from_decoded(&eng.e[k].s, device, nch, &d.planes[k], &coef[k], d.weight[k], &d.pweight[k], d.iterations[k]);
+        }
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamDestroy(stream);
+        if(block) { j2p_pool_give(device, block, block_bytes); }
+        return rc;
+}
+
+// (samples: NULL, or [channel] what the solvers are made from instead of planes[].data; file: NULL, or the file they are made from)
 int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs,
-            const j2p_samples *samples, const JpegOut *jpeg)
+            const j2p_samples *samples, const JpegOut *jpeg, const FileIn *file)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
+        if(file) {
+                JOB_TRY(create_from_file(d, device, *file, eng));
+                return solve_and_deliver(d, eng.e, true, resize, resample, outputs, jpeg);
+        }
         for(unsigned k = 0; k < solves(d); k++) {
                 const unsigned nch = d.separate ? 1 : d.nchannel;
                 if(samples) {
@@ -377,7 +419,7 @@ void worker_main(j2p_batch *b, int device)
                         if(single != device) { (void)hipSetDevice(single); }
                         rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr,
                                      job->outputs.empty() ? nullptr : &job->outputs, job->samples.empty() ? nullptr : job->samples.data(),
-                                     job->jpeg.on ? &job->jpeg : nullptr);
+                                     job->jpeg.on ? &job->jpeg : nullptr, job->file.parsed ? &job->file : nullptr);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -440,11 +482,52 @@ int validate_samples(const j2p_job &d, const j2p_samples *samples, int *device)
 
 // j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled, — nout != 0 —
 // j2p_batch_submit_outputs (never two of them); samples != NULL: j2p_batch_submit_samples (with nout or without; never with r or f);
-// jpeg != NULL: j2p_batch_submit_jpeg (with samples or without, and nothing else)
+// jpeg != NULL: j2p_batch_submit_jpeg (with samples or without, and nothing else); file != NULL: j2p_batch_submit_file and
+// j2p_batch_submit_file_jpeg (never with samples; with nout or with jpeg)
 int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs,
-           const j2p_samples *samples, const JpegOut *jpeg, int *ticket)
+           const j2p_samples *samples, const JpegOut *jpeg, int *ticket, const uint8_t *file = nullptr, size_t file_size = 0)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        // a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
+        // show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
+        FileIn file_in;
+        j2p_job filled;
+        int file_device = -1;
+        if(file) {
+                if(job->tile) { return j2p_fail(J2P_EINVAL, "job: file input of a row-tiled job is not supported"); }
+                uint8_t *copy = nullptr;
+                if(const int rc = j2p_decode_fetch(file, file_size, &copy, &file_in.on_device, &file_device); rc != J2P_OK) { return rc; }
+                file_in.parsed.reset(new(std::nothrow) j2p_jpeg_parsed);
+                const int rc = file_in.parsed ? j2p_jpeg_parse_full(copy ? copy : file, file_size, file_in.parsed.get()) : j2p_fail(J2P_ENOMEM, "host allocation failed");
+                free(copy);
+                if(rc != J2P_OK) { return rc; }
+                if(!file_in.on_device) { file_device = -1; }
+                file_in.data = file;
+                const j2p_jpeg_info &info = file_in.parsed->info;
+                filled = *job;
+                if(filled.nchannel == 0) { filled.nchannel = info.ncomp; }
+                // (one channel of a three-component file: component 0 alone, the greyscale solve)
+                if(filled.nchannel != info.ncomp && filled.nchannel != 1) {
+                        return j2p_fail(J2P_EINVAL, "job: %u channels for a file of %u components (all of them, or 1 for component 0 alone)", filled.nchannel, info.ncomp);
+                }
+                for(unsigned c = 0; c < filled.nchannel; c++) {
+                        j2p_plane &p = filled.planes[c];
+                        const j2p_jpeg_component &k = info.comp[c];
+                        if(p.data || p.fdata) { return j2p_fail(J2P_EINVAL, "job: channel %u: a job with a file takes no data / fdata (both must be NULL)", c); }
+                        if((p.w && p.w != k.blocks_w * 8) || (p.h && p.h != k.blocks_h * 8)) {
+                                return j2p_fail(J2P_EINVAL, "job: channel %u: the plane is %ux%u, the file's component %ux%u", c, p.w, p.h, k.blocks_w * 8, k.blocks_h * 8);
+                        }
+                        p.w = k.blocks_w * 8;
+                        p.h = k.blocks_h * 8;
+                        // (sampling factors left zero are the file's; a caller who zooms gives the file's times the zoom)
+                        if(!p.w_samp) { p.w_samp = k.w_samp; }
+                        if(!p.h_samp) { p.h_samp = k.h_samp; }
+                        p.quant_table = k.quant;           // (the file's table: lives in the job's parse)
+                }
+                if(!filled.out_w) { filled.out_w = info.width; }
+                if(!filled.out_h) { filled.out_h = info.height; }
+                job = &filled;
+        }
         if(jpeg) {
                 if(job->out_bits || job->out_coef[0] || job->out_tensor.data) {
                         return j2p_fail(J2P_EINVAL, "job: a JPEG job needs out_bits 0, no out_coef and out_tensor.data NULL");
@@ -486,6 +569,7 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
         }
         if(nout) { j->outputs.assign(outs, outs + nout); }
         if(samples) { j->samples.assign(samples, samples + job->nchannel); }
+        if(file) { j->file = std::move(file_in); }
         if(jpeg) {
                 // the tables travel with the job
                 j->jpeg = *jpeg;
@@ -518,6 +602,18 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
                 else if(!owned) { rc = j2p_fail(J2P_EINVAL, "job: the samples live on device %d, which this batch does not drive", samples_device); }
                 if(rc != J2P_OK) { delete j; return rc; }
                 j->device = samples_device;
+        }
+        if(file_device >= 0) {
+                // a file in device memory pins the job as device samples do
+                int rc = J2P_OK;
+                bool owned = false;
+                for(int dev : b->devices) { owned = owned || dev == file_device; }
+                if(j->device >= 0 && j->device != file_device) {
+                        rc = j2p_fail(J2P_EINVAL, "job: the file lives on device %d, the output tensor on device %d", file_device, j->device);
+                }
+                else if(!owned) { rc = j2p_fail(J2P_EINVAL, "job: the file lives on device %d, which this batch does not drive", file_device); }
+                if(rc != J2P_OK) { delete j; return rc; }
+                j->device = file_device;
         }
         const bool pinned = j->device >= 0;
         {
@@ -614,6 +710,26 @@ int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples sa
         jpeg.capacity = capacity;
         jpeg.size = size;
         return submit(b, job, nullptr, nullptr, 0, nullptr, samples, &jpeg, ticket);
+}
+
+int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, unsigned n, const j2p_output outs[], int *ticket)
+{
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
+        const bool none = n == 0 || !outs;
+        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, nullptr, ticket, file, size);
+}
+
+int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                               size_t capacity, size_t *out_size, int *ticket)
+{
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
+        JpegOut jpeg;
+        jpeg.spec = *spec;
+        jpeg.out = out;
+        jpeg.capacity = capacity;
+        jpeg.size = out_size;
+        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, &jpeg, ticket, file, size);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

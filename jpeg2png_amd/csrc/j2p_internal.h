@@ -70,6 +70,27 @@ static inline const char *j2p_jpeg_error(const j2p_jpeg *spec, unsigned ncomp)
         return NULL;
 }
 
+// ---- reading a JPEG file (j2p_jpeg_parse.c, pure C; the decode kernels of j2p_decode_kernels.hip.h) ----
+// One Huffman table in the form the kernels look symbols up in (the choice and what it costs: DESIGN.md section 21): an 8-bit
+// first level for the codes of up to 8 bits — look[the next 8 bits] = (length << 8) | symbol, 0 when the code is longer —
+// and per length 9..16 the canonical decode of T.81 F.2.2.3: the next `length` bits are a code of that length when they are
+// <= maxcode[length] (-1: no code of that length), and its symbol is vals[bits + valoff[length]].
+typedef struct j2p_huff_decode {
+        uint16_t look[256];
+        int32_t maxcode[17], valoff[17];
+        uint8_t vals[256];
+        uint32_t defined;
+} j2p_huff_decode;
+// everything j2p_jpeg_parse_full reads: what the caller sees (info) and what only the decoder needs
+typedef struct j2p_jpeg_parsed {
+        j2p_jpeg_info info;
+        uint16_t quant[4][64];          // by slot, natural order
+        unsigned quant_defined;         // bit per slot
+        j2p_huff_decode dc[4], ac[4];   // by slot
+} j2p_jpeg_parsed;
+// the marker segments of `file`: J2P_OK, J2P_EFORMAT or J2P_ENOTSUP (include/jpeg2png_amd.h); touches no device
+int j2p_jpeg_parse_full(const uint8_t *file, size_t size, j2p_jpeg_parsed *out);
+
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
 // the bar of the default `-i 50` twice; so chunks follow the clock: one iteration each at first, then a sixth of the
@@ -143,6 +164,21 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
 int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out);
 // the size of that block now (0: none yet): a request beyond it gets ANOTHER block, and what the old one held is lost
 size_t j2p_solver_scratch_bytes(const j2p_solver *s);
+
+// ---- reading a JPEG file on the device (j2p_output.hip) ----
+// the file where the host can parse it: `file` itself (*copy NULL), or a malloc'ed copy of device memory (*on_device, *device_of)
+int j2p_decode_fetch(const uint8_t *file, size_t size, uint8_t **copy, bool *on_device, int *device_of);
+// parsed's scan, whose bytes begin at `data` (host memory, or device memory of `device` read in place), decoded into the device
+// grids coef[c] (blocks_w * blocks_h * 64 int16) on `stream`; waits for the stream.  S: bits per subsequence, 0 the default.
+// The calling thread's device is `device`.  J2P_EFORMAT: the grids hold nothing of use.
+int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
+                    int16_t *const coef[3], j2p_decode_stats *stats);
+
+// a whole-canvas solver whose coefficients a decode has left in device memory of `device` (decoded[c]: channel c's grid,
+// planes[c].w / 8 x planes[c].h / 8 blocks; planes carry no arrays), copied into the resident buffers on the solver's own stream;
+// the grids may go away when it returns (j2p_solver.hip; what a batch job with a file makes its solvers with)
+int j2p_solver_create_from_decoded(j2p_solver **out, int device, unsigned nchannel, const j2p_plane planes[], const int16_t *const decoded[],
+                                   float weight, const float pweight[], unsigned iterations);
 
 // ---- j2p_pool.hip ----
 // the device-memory pool, for a solver's arena and for buffers that live as long as one call: at least `bytes` bytes on

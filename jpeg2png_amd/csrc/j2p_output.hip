@@ -1,6 +1,8 @@
 // jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
 // or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), to quantised JPEG
 // coefficients, and to the entropy-coded JPEG file itself (include/jpeg2png_amd.h: the j2p_planes_* functions, j2p_entropy_encode).
+// And, because it shares that file's scan kernels, the way back: a JPEG file's entropy-coded data to coefficients
+// (j2p_entropy_decode, j2p_decode_file; j2p_decode_kernels.hip.h).
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
@@ -9,11 +11,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <chrono>
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
 #include "j2p_hip_host.h"
 #include "j2p_output_kernels.hip.h"
+#include "j2p_decode_kernels.hip.h"
 
 using namespace j2p;
 
@@ -1038,6 +1042,311 @@ int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const co
         j2p_pool_give(device, block, block_bytes);
         (void)hipStreamDestroy(stream);
         return rc;
+}
+
+}  // extern "C"
+
+// ---- reading a JPEG file: k_unstuff_*, k_decode_* (j2p_decode_kernels.hip.h), the scans above ----
+namespace {
+
+DecodeTables decode_tables(const j2p_jpeg_parsed &p, unsigned S)
+{
+        DecodeTables t;
+        memset(&t, 0, sizeof(t));
+        for(int s = 0; s < 4; s++) {
+                t.tab[s] = p.dc[s];
+                t.tab[4 + s] = p.ac[s];
+        }
+        const j2p_jpeg_info &f = p.info;
+        DecodeGeom &g = t.g;
+        g.ncomp = f.ncomp;
+        g.per_mcu = f.blocks_per_mcu;
+        g.mcus_w = f.mcus_w;
+        g.nmcus = f.mcus_w * f.mcus_h;
+        g.ri = f.restart_interval ? f.restart_interval : g.nmcus;
+        g.nint = f.intervals;
+        g.nblocks = g.nmcus * g.per_mcu;
+        g.S = S;
+        unsigned blk = 0;
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                g.bw[c] = f.comp[c].blocks_w;
+                g.bh[c] = f.comp[c].blocks_h;
+                g.hs[c] = f.ncomp == 1 ? 1 : f.comp[c].h_samp_factor;
+                g.vs[c] = f.ncomp == 1 ? 1 : f.comp[c].v_samp_factor;
+                g.first_blk[c] = blk;
+                g.comp_base[c] = g.nmcus * blk;
+                g.dc_tab[c] = f.comp[c].dc_slot;
+                g.ac_tab[c] = f.comp[c].ac_slot;
+                for(unsigned k = 0; k < g.hs[c] * g.vs[c]; k++) { g.blk_comp[blk++] = c; }
+        }
+        return t;
+}
+
+const char *decode_error_text(unsigned flags)
+{
+        if(flags & kDecodeBadMarker) { return "a restart marker is missing or out of sequence"; }
+        if(flags & kDecodeBadCode) { return "a code that is in no Huffman table"; }
+        if(flags & kDecodeBadRun) { return "a run past coefficient 63"; }
+        if(flags & kDecodeBadEnd) { return "the scan is truncated, or data is left over behind its last block"; }
+        if(flags & kDecodeBadDc) { return "a DC value outside int16"; }
+        return "the block count disagrees with the decoder's state";
+}
+
+struct DecodeTake {
+        size_t total = 0;
+        size_t operator()(size_t bytes)
+        {
+                const size_t at = total;
+                total += round_up(bytes ? bytes : 1, 256);
+                return at;
+        }
+};
+
+// rounds queued before the change counters are first read back, and between two reads after that
+constexpr unsigned kDecodeFirstGroup = 3, kDecodeGroup = 4;
+
+}  // namespace
+
+// The decoder: p's scan from `data` (the entropy-coded bytes p.info.scan_begin.., HOST memory, or DEVICE memory of `device` read in
+// place) into the device grids coef[c] (blocks_w * blocks_h * 64 int16 each), on `stream`, which has been waited for on return.  One
+// pooled block holds every intermediate and goes back before returning.  stats may be NULL.
+int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
+                    int16_t *const coef[3], j2p_decode_stats *stats)
+{
+        const j2p_jpeg_parsed &p = *parsed;
+        const j2p_jpeg_info &f = p.info;
+        if(S == 0) { S = J2P_DECODE_SUBSEQUENCE_BITS; }
+        if(S < J2P_DECODE_SUBSEQUENCE_MIN || S > J2P_DECODE_SUBSEQUENCE_MAX) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", S, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        const size_t nraw = f.scan_end - f.scan_begin;
+        if(nraw == 0) { return j2p_fail(J2P_EFORMAT, "jpeg: the scan holds no data"); }
+        const unsigned long long bound = ((unsigned long long)nraw * 8 + S - 1) / S + f.intervals;
+        const unsigned long long blocks = (unsigned long long)f.mcus_w * f.mcus_h * f.blocks_per_mcu;
+        if(bound > 0x7fffffffull || blocks > 0xffffffffull || nraw / kUnstuffChunk > 0x7fffffffull) {
+                return j2p_fail(J2P_EINVAL, "decode: %zu bytes of data are too many for subsequences of %u bits", nraw, S);
+        }
+        const DecodeTables tables = decode_tables(p, S);
+        const unsigned nint = f.intervals, nbound = (unsigned)bound, nblocks = tables.g.nblocks;
+        const unsigned nchunks = (unsigned)((nraw + kUnstuffChunk - 1) / kUnstuffChunk);
+        const auto tiles = [](unsigned n) { return (n + kScanTile - 1) / kScanTile; };
+        const size_t clean_room = round_up(nraw + 16, 4);
+        DecodeTake take;
+        const size_t raw_at = take(data_on_device ? 0 : nraw), clean_at = take(clean_room);
+        const size_t keepc_at = take((size_t)nchunks * 4), markc_at = take((size_t)nchunks * 4), keepo_at = take((size_t)nchunks * 8);
+        const size_t marko_at = take((size_t)nchunks * 8), keeps_at = take(((size_t)tiles(nchunks) + 1) * 8), marks_at = take(((size_t)tiles(nchunks) + 1) * 8);
+        const size_t rst_at = take((size_t)nint * 8), icount_at = take((size_t)nint * 4), first_at = take((size_t)nint * 8);
+        const size_t isums_at = take(((size_t)tiles(nint) + 1) * 8);
+        const size_t exit_at[2] = {take((size_t)nbound * 8), take((size_t)nbound * 8)};
+        const size_t last_at = take((size_t)nbound * 8), done_at = take((size_t)nbound * 4), before_at = take((size_t)nbound * 8);
+        const size_t dsums_at = take(((size_t)tiles(nbound) + 1) * 8);
+        const size_t diff_at = take((size_t)nblocks * 4), dc_at = take((size_t)nblocks * 8), dcsums_at = take(((size_t)tiles(nblocks) + 1) * 8);
+        const size_t tables_at = take(sizeof(DecodeTables)), flags_at = take(256);     // flags: [0] the error word, [1..] the rounds' change counters
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        HIP_TRY(j2p_pool_take(device, take.total, &block, &block_bytes));
+        char *const base = static_cast<char *>(block);
+        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        const auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long *>(base + at); };
+        unsigned *const flags = u32(flags_at);
+        // everything below leaves through `finish`, which gives the block back once the stream is idle
+        const auto finish = [&](int rc) {
+                (void)hipStreamSynchronize(stream);
+                j2p_pool_give(device, block, block_bytes);
+                return rc;
+        };
+        const auto failed = [&](hipError_t e, const char *what) { return finish(j2p_fail(J2P_EDEVICE, "decode: %s: %s", what, hipGetErrorString(e))); };
+
+        const auto t_begin = std::chrono::steady_clock::now();
+        const uint8_t *raw = data;
+        hipError_t e = hipSuccess;
+        if(!data_on_device) {
+                e = hipMemcpyAsync(base + raw_at, data, nraw, hipMemcpyHostToDevice, stream);
+                raw = reinterpret_cast<const uint8_t *>(base + raw_at);
+        }
+        if(e == hipSuccess) { e = hipMemcpyAsync(base + tables_at, &tables, sizeof(tables), hipMemcpyHostToDevice, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + clean_at, 0xff, clean_room, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + rst_at, 0, (size_t)nint * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + exit_at[0], 0, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + last_at, 0xff, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + done_at, 0, (size_t)nbound * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + diff_at, 0, (size_t)nblocks * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(flags, 0, 256, stream); }
+        if(e != hipSuccess) { return failed(e, "staging"); }
+        // the clean stream and the restart markers' places
+        hipLaunchKernelGGL(k_unstuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, raw, nraw, nchunks, u32(keepc_at), u32(markc_at));
+        queue_scan(stream, u32(keepc_at), nchunks, u64(keeps_at), u64(keepo_at));
+        queue_scan(stream, u32(markc_at), nchunks, u64(marks_at), u64(marko_at));
+        hipLaunchKernelGGL(k_unstuff_copy, dim3((nchunks + 3) / 4), dim3(256), 0, stream, raw, nraw, nchunks, static_cast<const unsigned long long *>(u64(keepo_at)),
+                           static_cast<const unsigned long long *>(u64(marko_at)), nint, reinterpret_cast<uint8_t *>(base + clean_at), clean_room, u64(rst_at),
+                           flags);
+        // the subsequences of every interval
+        DecodeBuffers b;
+        b.tables = reinterpret_cast<const DecodeTables *>(base + tables_at);
+        b.words = u32(clean_at);
+        b.nwords = clean_room / 4;
+        b.clean_bytes = u64(keeps_at) + tiles(nchunks);
+        b.nmarkers = u64(marks_at) + tiles(nchunks);
+        b.rst = u64(rst_at);
+        b.first = u64(first_at);
+        b.nsub = u64(isums_at) + tiles(nint);
+        b.error = flags;
+        hipLaunchKernelGGL(k_decode_intervals, dim3((nint + 255) / 256), dim3(256), 0, stream, b, nint, S, u32(icount_at));
+        queue_scan(stream, u32(icount_at), nint, u64(isums_at), u64(first_at));
+        // rounds until no entry state changes: at most one per subsequence of the longest interval, and one that finds nothing to do
+        j2p_decode_stats st;
+        memset(&st, 0, sizeof(st));
+        st.intervals = nint;
+        unsigned rounds = 0;
+        bool settled = false;
+        while(!settled) {
+                if(rounds > nbound) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: the decoder's states did not settle in %u rounds", rounds)); }
+                const unsigned group = rounds == 0 ? kDecodeFirstGroup : kDecodeGroup;
+                if(rounds) { (void)hipMemsetAsync(flags + 1, 0, group * 4, stream); }
+                for(unsigned q = 0; q < group; q++, rounds++) {
+                        hipLaunchKernelGGL(k_decode_sync, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound,
+                                           static_cast<const unsigned long long *>(u64(exit_at[rounds & 1])), u64(exit_at[(rounds + 1) & 1]), u64(last_at),
+                                           u32(done_at), flags + 1 + q);
+                }
+                unsigned seen[1 + kDecodeGroup] = {0};
+                unsigned long long totals[2] = {0, 0};
+                e = hipMemcpyAsync(seen, flags, (1 + group) * 4, hipMemcpyDeviceToHost, stream);
+                if(e == hipSuccess) { e = hipMemcpyAsync(&totals[0], b.nsub, 8, hipMemcpyDeviceToHost, stream); }
+                if(e == hipSuccess) { e = hipMemcpyAsync(&totals[1], b.clean_bytes, 8, hipMemcpyDeviceToHost, stream); }
+                if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+                if(e != hipSuccess) { return failed(e, "rounds"); }
+                if(seen[0]) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(seen[0]))); }
+                st.subsequences = (unsigned)totals[0];
+                st.data_bytes = totals[1];
+                for(unsigned q = 0; q < group && !settled; q++) {
+                        if(seen[1 + q] == 0) {
+                                settled = true;
+                        } else {
+                                if(st.rounds < J2P_DECODE_STATS_ROUNDS) { st.recomputed[st.rounds] = seen[1 + q]; }
+                                st.rounds++;
+                        }
+                }
+        }
+        const unsigned long long *const exits = u64(exit_at[rounds & 1]);       // what the last round queued wrote
+        // the block ordinals, the ACs and the DC differences, the DCs
+        queue_scan(stream, u32(done_at), nbound, u64(dsums_at), u64(before_at));
+        DecodeOut o;
+        memset(&o, 0, sizeof(o));
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                o.coef[c] = coef[c];
+                (void)hipMemsetAsync(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64 * sizeof(int16_t), stream);
+        }
+        o.diff = u32(diff_at);
+        hipLaunchKernelGGL(k_decode_write, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound, exits, static_cast<const unsigned long long *>(u64(before_at)), o);
+        queue_scan(stream, u32(diff_at), nblocks, u64(dcsums_at), u64(dc_at));
+        hipLaunchKernelGGL(k_decode_dc, dim3((nblocks + 255) / 256), dim3(256), 0, stream, b.tables, static_cast<const unsigned *>(u32(diff_at)),
+                           static_cast<const unsigned long long *>(u64(dc_at)), o, flags);
+        unsigned bad = 0;
+        e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+        if(e != hipSuccess) { return failed(e, "the final pass"); }
+        if(bad) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(bad))); }
+        st.decode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if(stats) { *stats = st; }
+        return finish(J2P_OK);
+}
+
+// the file on the host for the parse: `file` itself, or a copy of device memory in `copy`; *on_device, *device_of: where it lives
+int j2p_decode_fetch(const uint8_t *file, size_t size, uint8_t **copy, bool *on_device, int *device_of)
+{
+        *copy = nullptr;
+        *on_device = false;
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        int where = -1;
+        const int kind = j2p_memory_of_pointer(file, &where);
+        if(kind == J2P_MEMORY_OTHER) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies in managed or unknown memory (plain device memory, or host memory)"); }
+        if(kind == J2P_MEMORY_DEVICE) {
+                *copy = static_cast<uint8_t *>(malloc(size));
+                if(!*copy) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                if(const hipError_t e = hipMemcpy(*copy, file, size, hipMemcpyDeviceToHost); e != hipSuccess) {
+                        free(*copy);
+                        *copy = nullptr;
+                        return j2p_fail(J2P_EDEVICE, "jpeg: reading the file: %s", hipGetErrorString(e));
+                }
+                *on_device = true;
+                *device_of = where;
+        }
+        return J2P_OK;
+}
+
+extern "C" {
+
+int j2p_entropy_decode_ex(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info,
+                          unsigned subsequence_bits, j2p_decode_stats *stats)
+{
+        if(!coef_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(subsequence_bits && (subsequence_bits < J2P_DECODE_SUBSEQUENCE_MIN || subsequence_bits > J2P_DECODE_SUBSEQUENCE_MAX)) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", subsequence_bits, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        uint8_t *copy = nullptr;
+        bool on_device = false;
+        int where = -1;
+        if(const int rc = j2p_decode_fetch(file, size, &copy, &on_device, &where); rc != J2P_OK) { return rc; }
+        j2p_jpeg_parsed *parsed = static_cast<j2p_jpeg_parsed *>(malloc(sizeof(j2p_jpeg_parsed)));
+        if(!parsed) {
+                free(copy);
+                return j2p_fail(J2P_ENOMEM, "out of memory");
+        }
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        hipStream_t stream = nullptr;
+        const int rc = [&]() -> int {
+                if(const int prc = j2p_jpeg_parse_full(copy ? copy : file, size, parsed); prc != J2P_OK) { return prc; }
+                const j2p_jpeg_info &f = parsed->info;
+                for(unsigned c = 0; c < f.ncomp; c++) {
+                        if(!coef_host[c]) { return j2p_fail(J2P_EINVAL, "decode: component %u has no room for its coefficients", c); }
+                }
+                int have = 0;
+                if(hipGetDeviceCount(&have) != hipSuccess || have <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
+                if(device < 0 || device >= have) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, have - 1); }
+                if(on_device && where != device) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the decode runs on %d", where, device); }
+                DeviceGuard guard(device);
+                HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+                size_t at[3] = {0, 0, 0}, bytes = 0;
+                for(unsigned c = 0; c < f.ncomp; c++) {
+                        at[c] = bytes;
+                        bytes += round_up((size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64 * sizeof(int16_t), 256);
+                }
+                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
+                int16_t *coef[3] = {nullptr, nullptr, nullptr};
+                for(unsigned c = 0; c < f.ncomp; c++) { coef[c] = reinterpret_cast<int16_t *>(static_cast<char *>(block) + at[c]); }
+                if(const int drc = j2p_decode_file(device, stream, parsed, file + f.scan_begin, on_device, subsequence_bits, coef, stats); drc != J2P_OK) {
+                        return drc;
+                }
+                // one staging copy down, so that nothing reaches the caller's arrays unless all of it does
+                int16_t *staged = static_cast<int16_t *>(malloc(bytes ? bytes : 1));
+                if(!staged) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                if(const hipError_t e = hipMemcpy(staged, block, bytes, hipMemcpyDeviceToHost); e != hipSuccess) {
+                        free(staged);
+                        return j2p_fail(J2P_EDEVICE, "decode: %s", hipGetErrorString(e));
+                }
+                for(unsigned c = 0; c < f.ncomp; c++) {
+                        memcpy(coef_host[c], reinterpret_cast<char *>(staged) + at[c], (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64 * sizeof(int16_t));
+                        if(quant) { memcpy(quant[c], f.comp[c].quant, sizeof(f.comp[c].quant)); }
+                }
+                free(staged);
+                if(info) { *info = f; }
+                return J2P_OK;
+        }();
+        if(stream) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipStreamDestroy(stream);
+        }
+        if(block) { j2p_pool_give(device, block, block_bytes); }
+        free(parsed);
+        free(copy);
+        return rc;
+}
+
+int j2p_entropy_decode(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info)
+{
+        return j2p_entropy_decode_ex(device, file, size, coef_host, quant, info, 0, nullptr);
 }
 
 }  // extern "C"

@@ -781,9 +781,10 @@ int launch_init(j2p_solver *s)
 // ---------------------------------------------------------------------------
 
 // what the planes and the band say before a device is touched: the canvas, and in *band the rows the solver holds
-// (samples: j2p_solver_create_from_samples — the planes carry no arrays, samples[c] stands in for them)
-int validate(unsigned nchannel, const j2p_plane planes[], const j2p_samples samples[], int band_local_arrays, j2p_canvas *cv, j2p_band *band,
-             bool *is_whole)
+// (samples: j2p_solver_create_from_samples — the planes carry no arrays, samples[c] stands in for them; from_file:
+// j2p_solver_create_from_jpeg — none either, the file's scan is decoded into the resident coefficients)
+int validate(unsigned nchannel, const j2p_plane planes[], const j2p_samples samples[], bool from_file, int band_local_arrays, j2p_canvas *cv,
+             j2p_band *band, bool *is_whole)
 {
         if(nchannel == 0 || nchannel > kMaxCh) { return j2p_fail(J2P_EINVAL, "nchannel must be 1..3 (compute.c:118), got %u", nchannel); }
         for(unsigned c = 0; c < nchannel; c++) {
@@ -804,7 +805,7 @@ int validate(unsigned nchannel, const j2p_plane planes[], const j2p_samples samp
                                 return j2p_fail(J2P_EINVAL, "channel %u: samples: strides (y, x) = (%td, %td) must be at least 1", c, m.stride_y, m.stride_x);
                         }
                 }
-                else if(!p.data || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
+                else if((!p.data && !from_file) || !p.quant_table) { return j2p_fail(J2P_EINVAL, "channel %u: data/quant_table is NULL", c); }
                 for(int j = 0; j < 64; j++) {
                         if(p.quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "channel %u: invalid quantization table (jpeg.c:41-45)", c); }
                 }
@@ -1050,9 +1051,10 @@ int samples_to_coefficients(j2p_solver *s, unsigned c, const SampleSource &src)
         return J2P_OK;
 }
 
-// one channel's coefficients go up (host arrays: whole-image unless band_local; or are computed from samples, m != NULL)
-// and are narrowed to bytes; its input window goes up decoded, or is decoded here
-int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p, const SampleSource *m)
+// one channel's coefficients go up (host arrays: whole-image unless band_local; or are computed from samples, m != NULL; or
+// are `resident` already, decoded from a file: j2p_decode_file) and are narrowed to bytes; its input window goes up decoded,
+// or is decoded here
+int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p, const SampleSource *m, bool resident)
 {
         ChanHost &h = s->ch[c];
         const size_t plane_floats = plane_floats_of(s);
@@ -1064,7 +1066,7 @@ int upload_channel(j2p_solver *s, unsigned c, const j2p_plane &p, const SampleSo
         }
         if(h.crows) {
                 // block-major: coefficient row r lives in block row r/8; rows are block aligned
-                if(!m) {
+                if(!m && !resident) {
                         const int16_t *src = p.data + (size_t)(h.crow0 - host_row0) * h.cw;
                         HIP_TRY(hipMemcpyAsync(h.d, src, (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
                 }
@@ -1192,17 +1194,26 @@ void j2p_solver_destroy(j2p_solver *s)
         delete s;
 }
 
-// j2p_solver_create, and — samples != NULL — j2p_solver_create_from_samples: the same stages, with the sample source in
-// the upload stage
+// a JPEG file as the source of a solver's coefficients: its parse, the scan's bytes and where they are — or, parsed == NULL, the
+// grids a decode of the file has already left in device memory (a batch job decodes once for all its solvers), copied on the device
+struct FileSource {
+        const j2p_jpeg_parsed *parsed;
+        const uint8_t *data;
+        bool on_device;
+        const int16_t *decoded[3];
+};
+
+// j2p_solver_create, and — samples != NULL — j2p_solver_create_from_samples, and — file != NULL — j2p_solver_create_from_jpeg:
+// the same stages, with the sample source or the file's decode in the upload stage
 static int create_solver(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[], const j2p_samples samples[],
-                         float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
+                         const FileSource *file, float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
 {
         if(!out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         *out = nullptr;
         if(!planes || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         j2p_canvas cv = J2P_CANVAS_NONE;
         bool whole = true;
-        int rc = validate(nchannel, planes, samples, band_local_arrays, &cv, &band, &whole);
+        int rc = validate(nchannel, planes, samples, file != nullptr, band_local_arrays, &cv, &band, &whole);
         if(rc != J2P_OK) { return rc; }
         int ndev = 0;
         if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -1250,7 +1261,22 @@ static int create_solver(j2p_solver **out, int device, void *stream, unsigned nc
                 register_live_bytes(s);
                 rc = upload_tables(s, planes, qf);
         }
-        for(unsigned c = 0; rc == J2P_OK && c < nchannel; c++) { rc = upload_channel(s, c, planes[c], samples ? &sources[c] : nullptr); }
+        if(rc == J2P_OK && file) {
+                // (a whole canvas: every channel's resident buffer is its component's whole grid)
+                int16_t *grids[3] = {nullptr, nullptr, nullptr};
+                for(unsigned c = 0; c < nchannel; c++) { grids[c] = s->ch[c].d; }
+                if(file->parsed) {
+                        rc = j2p_decode_file(device, s->stream, file->parsed, file->data, file->on_device, 0, grids, nullptr);
+                } else {
+                        for(unsigned c = 0; c < nchannel; c++) {
+                                const ChanHost &h = s->ch[c];
+                                HIP_TRY(hipMemcpyAsync(h.d, file->decoded[c], (size_t)h.crows * h.cw * sizeof(int16_t), hipMemcpyDeviceToDevice, s->stream));
+                        }
+                }
+        }
+        for(unsigned c = 0; rc == J2P_OK && c < nchannel; c++) {
+                rc = upload_channel(s, c, planes[c], samples ? &sources[c] : nullptr, file != nullptr);
+        }
         if(rc == J2P_OK) { rc = decide_narrow_and_wide(s); }
         if(rc == J2P_OK) { rc = launch_init(s); }
         if(rc != J2P_OK) { return rc; }
@@ -1261,7 +1287,7 @@ static int create_solver(j2p_solver **out, int device, void *stream, unsigned nc
 int j2p_solver_create(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
                       float weight, const float pweight[], unsigned iterations, j2p_band band, int band_local_arrays)
 {
-        return create_solver(out, device, stream, nchannel, planes, nullptr, weight, pweight, iterations, band, band_local_arrays);
+        return create_solver(out, device, stream, nchannel, planes, nullptr, nullptr, weight, pweight, iterations, band, band_local_arrays);
 }
 
 int j2p_solver_create_from_samples(j2p_solver **out, int device, void *stream, unsigned nchannel, const j2p_plane planes[],
@@ -1270,8 +1296,54 @@ int j2p_solver_create_from_samples(j2p_solver **out, int device, void *stream, u
         if(out) { *out = nullptr; }
         if(!samples) { return j2p_fail(J2P_EINVAL, "samples is NULL"); }
         const j2p_band whole = {0, 0};
-        return create_solver(out, device, stream, nchannel, planes, samples, weight, pweight, iterations, whole, 0);
+        return create_solver(out, device, stream, nchannel, planes, samples, nullptr, weight, pweight, iterations, whole, 0);
 }
+
+int j2p_solver_create_from_jpeg(j2p_solver **out, int device, void *stream, const uint8_t *file, size_t size, float weight, const float pweight[],
+                                unsigned iterations, j2p_jpeg_info *info)
+{
+        if(out) { *out = nullptr; }
+        if(!out || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        uint8_t *copy = nullptr;
+        bool on_device = false;
+        int where = -1;
+        if(const int rc = j2p_decode_fetch(file, size, &copy, &on_device, &where); rc != J2P_OK) { return rc; }
+        std::unique_ptr<uint8_t, decltype(&free)> copy_owner(copy, &free);
+        std::unique_ptr<j2p_jpeg_parsed> parsed(new(std::nothrow) j2p_jpeg_parsed);
+        if(!parsed) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
+        if(const int rc = j2p_jpeg_parse_full(copy ? copy : file, size, parsed.get()); rc != J2P_OK) { return rc; }
+        if(on_device && where != device) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the solver on %d", where, device); }
+        const j2p_jpeg_info &f = parsed->info;
+        j2p_plane planes[3];
+        memset(planes, 0, sizeof(planes));
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                planes[c].w = f.comp[c].blocks_w * 8;
+                planes[c].h = f.comp[c].blocks_h * 8;
+                planes[c].w_samp = f.comp[c].w_samp;
+                planes[c].h_samp = f.comp[c].h_samp;
+                planes[c].quant_table = f.comp[c].quant;
+        }
+        const FileSource source = {parsed.get(), file + f.scan_begin, on_device, {nullptr, nullptr, nullptr}};
+        const j2p_band whole = {0, 0};
+        const int rc = create_solver(out, device, stream, f.ncomp, planes, nullptr, &source, weight, pweight, iterations, whole, 0);
+        if(rc == J2P_OK && info) { *info = f; }
+        return rc;
+}
+
+}  // extern "C"
+
+int j2p_solver_create_from_decoded(j2p_solver **out, int device, unsigned nchannel, const j2p_plane planes[], const int16_t *const decoded[],
+                                   float weight, const float pweight[], unsigned iterations)
+{
+        if(out) { *out = nullptr; }
+        if(!decoded) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        FileSource source = {nullptr, nullptr, true, {nullptr, nullptr, nullptr}};
+        for(unsigned c = 0; c < nchannel && c < 3; c++) { source.decoded[c] = decoded[c]; }
+        const j2p_band whole = {0, 0};
+        return create_solver(out, device, nullptr, nchannel, planes, nullptr, &source, weight, pweight, iterations, whole, 0);
+}
+
+extern "C" {
 
 int j2p_solver_clipped_samples(const j2p_solver *s, unsigned c, unsigned long long *count)
 {

@@ -10,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from jpeg2png_amd.buildlib import CSRC, HIP_FLAGS, HIP_UNITS, INCLUDE, build  # noqa: E402
+from jpeg2png_amd.buildlib import C_OBJECTS, CSRC, HIP_FLAGS, HIP_UNITS, INCLUDE, build  # noqa: E402
 
 name, flags = sys.argv[1], sys.argv[2:]
 build()                                     # every object but the solver unit's is shared with the normal build
@@ -18,7 +18,7 @@ out_dir = os.path.join(ROOT, "ab")
 os.makedirs(out_dir, exist_ok=True)
 obj = os.path.join(out_dir, f"j2p_solver_{name}.o")
 subprocess.run(["/opt/rocm/bin/hipcc", *HIP_FLAGS, *flags, "-I", INCLUDE, "-I", CSRC, "-c", os.path.join(CSRC, "j2p_solver.hip"), "-o", obj], check=True)
-objs = [obj] + [os.path.join(CSRC, u.replace(".hip", ".o")) for u in HIP_UNITS if u != "j2p_solver.hip"] + [os.path.join(CSRC, "compute_host.o")]
+objs = [obj] + [os.path.join(CSRC, u.replace(".hip", ".o")) for u in HIP_UNITS if u != "j2p_solver.hip"] + list(C_OBJECTS)
 lib = os.path.join(out_dir, f"libj2p_{name}.so")
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-lpthread", "-o", lib], check=True)
 os.remove(obj)
