@@ -39,13 +39,6 @@ struct JpegOut {
         size_t capacity = 0, *size = nullptr;
 };
 
-// the file of a j2p_batch_submit_file job: parsed at submit (a copy of it, for a file in device memory), decoded by the worker
-struct FileIn {
-        std::unique_ptr<j2p_jpeg_parsed> parsed;
-        const uint8_t *data = nullptr;      // the caller's bytes, valid until j2p_batch_wait
-        bool on_device = false;
-};
-
 struct Job {
         j2p_job desc;
         j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
@@ -55,7 +48,8 @@ struct Job {
         std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
         std::vector<j2p_samples> samples;   // j2p_batch_submit_samples: [channel] the solvers are made from these, not from planes[].data
         JpegOut jpeg;                       // j2p_batch_submit_jpeg: the job delivers the file
-        FileIn file;                        // j2p_batch_submit_file: the solvers' coefficients are decoded from this file
+        j2p_jpeg_file file;                 // j2p_batch_submit_file: opened at submit; the worker decodes the solvers' coefficients from
+                                            // the caller's bytes, which stay valid until j2p_batch_wait
         int ticket = 0;
         int device = -1;                    // tensor output, device samples: their device, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -331,38 +325,22 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
         return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr, nullptr);
 }
 
-// a file job's engines: the file's scan decoded ONCE on the worker's GPU into pooled grids (j2p_decode_file: all components,
+// a file job's engines: the file's scan decoded ONCE on the worker's GPU into pooled grids (j2p_decoded_grids: all components,
 // whichever of them the job solves), from which every solver of the job copies its channels on the device
-int create_from_file(const j2p_job &d, int device, const FileIn &file, Engines &eng)
+int create_from_file(const j2p_job &d, int device, const j2p_jpeg_file &file, Engines &eng)
 {
-        const j2p_jpeg_info &f = file.parsed->info;
-        size_t at[3] = {0, 0, 0}, bytes = 0;
-        for(unsigned c = 0; c < f.ncomp; c++) {
-                at[c] = bytes;
-                bytes += ((size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64 * sizeof(int16_t) + 255) / 256 * 256;
-        }
-        hipStream_t stream = nullptr;
-        if(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { return j2p_fail(J2P_EDEVICE, "job: no stream for the file's decode"); }
-        void *block = nullptr;
-        size_t block_bytes = 0;
-        int rc = J2P_OK;
-        if(j2p_pool_take(device, bytes, &block, &block_bytes) != hipSuccess) { rc = j2p_fail(J2P_ENOMEM, "job: no device memory for the file's coefficients"); }
-        int16_t *coef[3] = {nullptr, nullptr, nullptr};
-        for(unsigned c = 0; rc == J2P_OK && c < f.ncomp; c++) { coef[c] = reinterpret_cast<int16_t *>(static_cast<char *>(block) + at[c]); }
-        if(rc == J2P_OK) { rc = j2p_decode_file(device, stream, file.parsed.get(), file.data + f.scan_begin, file.on_device, 0, coef, nullptr); }
+        const j2p_decoded_grids grids(device, file, 0, nullptr);
+        int rc = grids.rc;
         for(unsigned k = 0; rc == J2P_OK && k < solves(d); k++) {
                 const unsigned nch = d.separate ? 1 : d.nchannel;
-                rc = j2p_solver_create_from_decoded(&eng.e[k].s, device, nch, &d.planes[k], &coef[k], d.weight[k], &d.pweight[k], d.iterations[k]);
+                rc = j2p_solver_create_from_decoded(&eng.e[k].s, device, nch, &d.planes[k], &grids.coef[k], d.weight[k], &d.pweight[k], d.iterations[k]);
         }
-        (void)hipStreamSynchronize(stream);
-        (void)hipStreamDestroy(stream);
-        if(block) { j2p_pool_give(device, block, block_bytes); }
         return rc;
 }
 
 // (samples: NULL, or [channel] what the solvers are made from instead of planes[].data; file: NULL, or the file they are made from)
 int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs,
-            const j2p_samples *samples, const JpegOut *jpeg, const FileIn *file)
+            const j2p_samples *samples, const JpegOut *jpeg, const j2p_jpeg_file *file)
 {
         const j2p_band whole = {0, 0};
         Engines eng;
@@ -490,19 +468,13 @@ int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resa
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         // a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
         // show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
-        FileIn file_in;
+        j2p_jpeg_file file_in;
         j2p_job filled;
         int file_device = -1;
         if(file) {
                 if(job->tile) { return j2p_fail(J2P_EINVAL, "job: file input of a row-tiled job is not supported"); }
-                uint8_t *copy = nullptr;
-                if(const int rc = j2p_decode_fetch(file, file_size, &copy, &file_in.on_device, &file_device); rc != J2P_OK) { return rc; }
-                file_in.parsed.reset(new(std::nothrow) j2p_jpeg_parsed);
-                const int rc = file_in.parsed ? j2p_jpeg_parse_full(copy ? copy : file, file_size, file_in.parsed.get()) : j2p_fail(J2P_ENOMEM, "host allocation failed");
-                free(copy);
-                if(rc != J2P_OK) { return rc; }
-                if(!file_in.on_device) { file_device = -1; }
-                file_in.data = file;
+                if(const int rc = j2p_jpeg_open(file, file_size, &file_in); rc != J2P_OK) { return rc; }
+                file_device = file_in.device;
                 const j2p_jpeg_info &info = file_in.parsed->info;
                 filled = *job;
                 if(filled.nchannel == 0) { filled.nchannel = info.ncomp; }

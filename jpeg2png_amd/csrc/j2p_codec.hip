@@ -1,0 +1,615 @@
+// jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode) and a
+// baseline file's entropy-coded data back to coefficients (j2p_jpeg_open, j2p_decode_file, j2p_decoded_grids,
+// j2p_entropy_decode; include/jpeg2png_amd.h, j2p_internal.h).
+//
+// A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
+// uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
+// stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_scan.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <chrono>
+#include <new>
+
+#include "jpeg2png_amd.h"
+#include "j2p_internal.h"
+#include "j2p_hip_host.h"
+#include "j2p_codec_kernels.hip.h"
+#include "j2p_decode_kernels.hip.h"
+
+using namespace j2p;
+
+// ---- the JPEG file: k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_count, k_stuff_copy ----
+namespace {
+
+// Annex K.3 of the JPEG standard, as include/jpeg2png_amd.h states them: [0] the tables of component 0, [1] of the others
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kAcVals[2][162] = {
+        {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+         0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+         0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+         0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+         0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+         0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+         0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+         0xfa},
+        {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+         0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+         0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+         0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+         0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+         0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+         0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+         0xfa}};
+// natural index of zigzag position k (the kernels' kZigzagNatural)
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// the codes of one table, by symbol: in order of length, consecutive within a length, doubled from one length to the next
+void huffman_codes(const uint8_t bits[16], const uint8_t *vals, unsigned *by_symbol)
+{
+        unsigned code = 0, k = 0;
+        for(unsigned length = 1; length <= 16; length++) {
+                for(unsigned i = 0; i < bits[length - 1]; i++) { by_symbol[vals[k++]] = (length << 16) | code++; }
+                code <<= 1;
+        }
+}
+const HuffCodes &huffman_tables()
+{
+        static const HuffCodes tables = [] {
+                HuffCodes h;
+                memset(&h, 0, sizeof(h));
+                for(int t = 0; t < 2; t++) {
+                        huffman_codes(kDcBits[t], kDcVals, h.dc[t]);
+                        huffman_codes(kAcBits[t], kAcVals[t], h.ac[t]);
+                }
+                return h;
+        }();
+        return tables;
+}
+
+// everything in front of the entropy-coded data; at most 623 bytes.  Returns their number.
+constexpr size_t kJpegHeaderMax = 640;
+size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, uint8_t *out)
+{
+        uint8_t *p = out;
+        const auto segment = [&](uint8_t marker, size_t payload) {
+                *p++ = 0xff;
+                *p++ = marker;
+                *p++ = (uint8_t)((payload + 2) >> 8);
+                *p++ = (uint8_t)(payload + 2);
+        };
+        *p++ = 0xff;
+        *p++ = 0xd8;
+        static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+        segment(0xe0, sizeof(jfif));
+        memcpy(p, jfif, sizeof(jfif));
+        p += sizeof(jfif);
+        for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
+                segment(0xdb, 65);
+                *p++ = (uint8_t)t;
+                for(int k = 0; k < 64; k++) { *p++ = (uint8_t)spec.quant[t][kZigzag[k]]; }
+        }
+        segment(0xc0, 6 + 3 * ncomp);
+        *p++ = 8;
+        *p++ = (uint8_t)(spec.height >> 8);
+        *p++ = (uint8_t)spec.height;
+        *p++ = (uint8_t)(spec.width >> 8);
+        *p++ = (uint8_t)spec.width;
+        *p++ = (uint8_t)ncomp;
+        for(unsigned c = 0; c < ncomp; c++) {
+                *p++ = (uint8_t)(c + 1);
+                *p++ = c == 0 && ncomp == 3 ? (uint8_t)((spec.sub_w << 4) | spec.sub_h) : 0x11;
+                *p++ = c ? 1 : 0;
+        }
+        for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
+                segment(0xc4, 1 + 16 + 12);
+                *p++ = (uint8_t)t;
+                memcpy(p, kDcBits[t], 16);
+                memcpy(p + 16, kDcVals, 12);
+                p += 28;
+                segment(0xc4, 1 + 16 + 162);
+                *p++ = (uint8_t)(0x10 | t);
+                memcpy(p, kAcBits[t], 16);
+                memcpy(p + 16, kAcVals[t], 162);
+                p += 178;
+        }
+        segment(0xda, 1 + 2 * ncomp + 3);
+        *p++ = (uint8_t)ncomp;
+        for(unsigned c = 0; c < ncomp; c++) {
+                *p++ = (uint8_t)(c + 1);
+                *p++ = c ? 0x11 : 0x00;
+        }
+        *p++ = 0;
+        *p++ = 0x3f;
+        *p++ = 0;
+        return (size_t)(p - out);
+}
+
+// the scan's geometry for a spec that j2p_jpeg_error accepted, but for the coefficients' addresses
+ScanGeom scan_geometry(const j2p_jpeg &spec, unsigned ncomp)
+{
+        const j2p_scan_grids grids = j2p_scan_grids_of(spec, ncomp);
+        ScanGeom g;
+        memset(&g, 0, sizeof(g));
+        g.ncomp = ncomp;
+        g.sub_w = grids.sub_w;
+        g.sub_h = grids.sub_h;
+        for(unsigned c = 0; c < ncomp; c++) {
+                g.bw[c] = grids.bw[c];
+                g.bh[c] = grids.bh[c];
+        }
+        g.mcus_w = (g.bw[0] + g.sub_w - 1) / g.sub_w;
+        const unsigned mcus_h = (g.bh[0] + g.sub_h - 1) / g.sub_h;
+        g.per_mcu = ncomp == 3 ? g.sub_w * g.sub_h + 2 : 1;
+        g.nslots = ncomp == 3 ? g.mcus_w * mcus_h * g.per_mcu : g.bw[0] * g.bh[0];       // (at most 6 * 8192^2 / 4)
+        return g;
+}
+
+// an exclusive sum of n counts on the stream: in -> out, sums: ceil(n / kScanTile) + 1 words, the last the total
+void queue_scan(hipStream_t stream, const unsigned *in, unsigned n, unsigned long long *sums, unsigned long long *out)
+{
+        const unsigned ntiles = (n + kScanTile - 1) / kScanTile;
+        hipLaunchKernelGGL(k_scan_sums, dim3(ntiles), dim3(256), 0, stream, in, n, sums);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, stream, sums, ntiles);
+        hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(256), 0, stream, in, n, static_cast<const unsigned long long *>(sums), out);
+}
+
+}  // namespace
+
+j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp)
+{
+        j2p_scan_grids g;
+        memset(&g, 0, sizeof(g));
+        g.sub_w = ncomp == 3 ? spec.sub_w : 1;
+        g.sub_h = ncomp == 3 ? spec.sub_h : 1;
+        g.bw[0] = (spec.width + 7) / 8;
+        g.bh[0] = (spec.height + 7) / 8;
+        for(unsigned c = 1; c < ncomp; c++) {
+                g.bw[c] = (g.bw[0] + g.sub_w - 1) / g.sub_w;
+                g.bh[c] = (g.bh[0] + g.sub_h - 1) / g.sub_h;
+        }
+        return g;
+}
+
+// The coder (j2p_internal.h: what memory and fill are).  The block's layout, each part aligned to 256 bytes:
+//   [coefficients per component][len: nslots u32][off: nslots u64][sums: tiles + 1 u64]              known from the spec
+//   [stage: the stream, ceil(bits / 32) + 1 words][count: chunks u32][ffoff: chunks u64][sums]      known once the bits are
+//   [out: the stuffed bytes]                                                                        known once the FFs are
+// so the two totals are read back (8 bytes each, a wait each) and the block is asked for three times, the first two times
+// with a guess for what is not known yet; when it moved, what had been computed is computed again.  A second image of the
+// same size or smaller finds the block large enough at once.
+int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size)
+{
+        ScanGeom g = scan_geometry(spec, ncomp);
+        const HuffCodes &codes = huffman_tables();
+        const unsigned nslots = g.nslots, slot_tiles = (nslots + kScanTile - 1) / kScanTile;
+        j2p_carve part;
+        size_t coef_at[3];
+        for(unsigned c = 0; c < ncomp; c++) { coef_at[c] = part(j2p_grid_bytes(g.bw[c], g.bh[c])); }
+        const size_t coef_bytes = part.total;
+        const size_t len_at = part((size_t)nslots * 4), off_at = part((size_t)nslots * 8), sums_at = part(((size_t)slot_tiles + 1) * 8);
+        const size_t fixed = part.total;
+        char *base = nullptr;
+        const auto take = [&](size_t bytes, bool *moved) {
+                void *p = nullptr;
+                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
+                base = static_cast<char *>(p);
+                return (int)J2P_OK;
+        };
+        const auto at = [&](size_t offset) { return base + offset; };
+        // from the coefficients to the bit offsets
+        const auto lengths = [&] {
+                int16_t *coef[3] = {nullptr, nullptr, nullptr};
+                for(unsigned c = 0; c < ncomp; c++) {
+                        coef[c] = reinterpret_cast<int16_t *>(at(coef_at[c]));
+                        g.coef[c] = coef[c];
+                }
+                fill(stream, coef);
+                const unsigned per_workgroup = 4 * kEntropyIters;
+                hipLaunchKernelGGL(k_entropy_lengths, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
+                                   reinterpret_cast<unsigned *>(at(len_at)));
+                queue_scan(stream, reinterpret_cast<unsigned *>(at(len_at)), nslots, reinterpret_cast<unsigned long long *>(at(sums_at)),
+                           reinterpret_cast<unsigned long long *>(at(off_at)));
+        };
+        bool moved = false;
+        if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }     // (a file is rarely an eighth of its coefficients)
+        lengths();
+        unsigned long long bits = 0;
+        HIP_TRY(hipMemcpyAsync(&bits, at(sums_at) + (size_t)slot_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const size_t nbytes = (size_t)((bits + 7) / 8), stage_words = (size_t)((bits + 31) / 32) + 1;
+        const unsigned nchunks = (unsigned)((nbytes + kStuffChunk - 1) / kStuffChunk), chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
+        const size_t stage_at = part(stage_words * 4), count_at = part((size_t)nchunks * 4), ffoff_at = part((size_t)nchunks * 8);
+        const size_t ffsums_at = part(((size_t)chunk_tiles + 1) * 8), out_at = part.total;
+        // from the bit offsets to the stream and where its FF bytes are
+        const auto pack = [&] {
+                (void)hipMemsetAsync(at(stage_at), 0, stage_words * 4, stream);
+                const unsigned per_workgroup = 4 * kEntropyIters;
+                hipLaunchKernelGGL(k_entropy_pack, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
+                                   reinterpret_cast<const unsigned long long *>(at(off_at)), reinterpret_cast<unsigned *>(at(stage_at)));
+                hipLaunchKernelGGL(k_stuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes,
+                                   nchunks, reinterpret_cast<unsigned *>(at(count_at)));
+                queue_scan(stream, reinterpret_cast<unsigned *>(at(count_at)), nchunks, reinterpret_cast<unsigned long long *>(at(ffsums_at)),
+                           reinterpret_cast<unsigned long long *>(at(ffoff_at)));
+        };
+        if(const int rc = take(out_at + nbytes + nbytes / 16 + 256, &moved); rc != J2P_OK) { return rc; }
+        if(moved) { lengths(); }
+        pack();
+        unsigned long long ffs = 0;
+        HIP_TRY(hipMemcpyAsync(&ffs, at(ffsums_at) + (size_t)chunk_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint8_t header[kJpegHeaderMax];
+        const size_t header_bytes = jpeg_header(spec, ncomp, header), data_bytes = nbytes + (size_t)ffs;
+        *size = header_bytes + data_bytes + 2;
+        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
+        if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
+        if(moved) {
+                lengths();
+                pack();
+        }
+        hipLaunchKernelGGL(k_stuff_copy, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes, nchunks,
+                           reinterpret_cast<const unsigned long long *>(at(ffoff_at)), reinterpret_cast<uint8_t *>(at(out_at)));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_host + header_bytes, at(out_at), data_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        memcpy(out_host, header, header_bytes);
+        out_host[header_bytes + data_bytes] = 0xff;
+        out_host[header_bytes + data_bytes + 1] = 0xd9;
+        return J2P_OK;
+}
+
+// the device of a j2p_entropy_* call
+static int check_device(int device)
+{
+        int have = 0;
+        if(hipGetDeviceCount(&have) != hipSuccess || have <= 0) { return j2p_fail(J2P_EDEVICE, "no HIP device available"); }
+        if(device < 0 || device >= have) { return j2p_fail(J2P_EINVAL, "device %d out of range (0..%d)", device, have - 1); }
+        return J2P_OK;
+}
+
+extern "C" {
+
+int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                       size_t *size)
+{
+        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_error(spec, ncomp)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        const j2p_scan_grids g = j2p_scan_grids_of(*spec, ncomp);
+        size_t values[3] = {0, 0, 0};
+        for(unsigned c = 0; c < ncomp; c++) {
+                if(!coef_host[c]) { return j2p_fail(J2P_EINVAL, "jpeg: component %u has no coefficients", c); }
+                values[c] = (size_t)g.bw[c] * g.bh[c] * 64;
+                for(size_t i = 0; i < values[c]; i++) {
+                        if(coef_host[c][i] < -1023 || coef_host[c][i] > 1023) {
+                                return j2p_fail(J2P_EINVAL, "jpeg: component %u: coefficient %d (block %zu, index %zu) is outside [-1023, 1023]", c,
+                                                coef_host[c][i], i / 64, i % 64);
+                        }
+                }
+        }
+        if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(device);
+        hipStream_t stream = nullptr;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // one pooled block that grows as the solvers' scratch does
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        const int rc = j2p_encode_scan(
+                stream, *spec, ncomp,
+                [&](size_t bytes, void **p, bool *moved) {
+                        *moved = block_bytes < bytes;
+                        if(block_bytes < bytes) {
+                                HIP_TRY(hipStreamSynchronize(stream));
+                                j2p_pool_give(device, block, block_bytes);
+                                block = nullptr;
+                                block_bytes = 0;
+                                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
+                        }
+                        *p = block;
+                        return (int)J2P_OK;
+                },
+                [&](hipStream_t st, int16_t *const coef[3]) {
+                        for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
+                },
+                out_host, capacity, size);
+        (void)hipStreamSynchronize(stream);
+        j2p_pool_give(device, block, block_bytes);
+        (void)hipStreamDestroy(stream);
+        return rc;
+}
+
+}  // extern "C"
+
+// ---- reading a JPEG file: k_unstuff_*, k_decode_* (j2p_decode_kernels.hip.h), the scans above ----
+namespace {
+
+DecodeTables decode_tables(const j2p_jpeg_parsed &p, unsigned S)
+{
+        DecodeTables t;
+        memset(&t, 0, sizeof(t));
+        for(int s = 0; s < 4; s++) {
+                t.tab[s] = p.dc[s];
+                t.tab[4 + s] = p.ac[s];
+        }
+        const j2p_jpeg_info &f = p.info;
+        DecodeGeom &g = t.g;
+        g.ncomp = f.ncomp;
+        g.per_mcu = f.blocks_per_mcu;
+        g.mcus_w = f.mcus_w;
+        g.nmcus = f.mcus_w * f.mcus_h;
+        g.ri = f.restart_interval ? f.restart_interval : g.nmcus;
+        g.nint = f.intervals;
+        g.nblocks = g.nmcus * g.per_mcu;
+        g.S = S;
+        unsigned blk = 0;
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                g.bw[c] = f.comp[c].blocks_w;
+                g.bh[c] = f.comp[c].blocks_h;
+                g.hs[c] = f.ncomp == 1 ? 1 : f.comp[c].h_samp_factor;
+                g.vs[c] = f.ncomp == 1 ? 1 : f.comp[c].v_samp_factor;
+                g.first_blk[c] = blk;
+                g.comp_base[c] = g.nmcus * blk;
+                g.dc_tab[c] = f.comp[c].dc_slot;
+                g.ac_tab[c] = f.comp[c].ac_slot;
+                for(unsigned k = 0; k < g.hs[c] * g.vs[c]; k++) { g.blk_comp[blk++] = c; }
+        }
+        return t;
+}
+
+const char *decode_error_text(unsigned flags)
+{
+        if(flags & kDecodeBadMarker) { return "a restart marker is missing or out of sequence"; }
+        if(flags & kDecodeBadCode) { return "a code that is in no Huffman table"; }
+        if(flags & kDecodeBadRun) { return "a run past coefficient 63"; }
+        if(flags & kDecodeBadEnd) { return "the scan is truncated, or data is left over behind its last block"; }
+        if(flags & kDecodeBadDc) { return "a DC value outside int16"; }
+        return "the block count disagrees with the decoder's state";
+}
+
+// rounds queued before the change counters are first read back, and between two reads after that
+constexpr unsigned kDecodeFirstGroup = 3, kDecodeGroup = 4;
+
+}  // namespace
+
+// The decoder: p's scan from `data` (the entropy-coded bytes p.info.scan_begin.., HOST memory, or DEVICE memory of `device` read in
+// place) into the device grids coef[c] (blocks_w * blocks_h * 64 int16 each), on `stream`, which has been waited for on return.  One
+// pooled block holds every intermediate and goes back before returning.  stats may be NULL.
+int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
+                    int16_t *const coef[3], j2p_decode_stats *stats)
+{
+        const j2p_jpeg_parsed &p = *parsed;
+        const j2p_jpeg_info &f = p.info;
+        if(S == 0) { S = J2P_DECODE_SUBSEQUENCE_BITS; }
+        if(S < J2P_DECODE_SUBSEQUENCE_MIN || S > J2P_DECODE_SUBSEQUENCE_MAX) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", S, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        const size_t nraw = f.scan_end - f.scan_begin;
+        if(nraw == 0) { return j2p_fail(J2P_EFORMAT, "jpeg: the scan holds no data"); }
+        const unsigned long long bound = ((unsigned long long)nraw * 8 + S - 1) / S + f.intervals;
+        const unsigned long long blocks = (unsigned long long)f.mcus_w * f.mcus_h * f.blocks_per_mcu;
+        if(bound > 0x7fffffffull || blocks > 0xffffffffull || nraw / kUnstuffChunk > 0x7fffffffull) {
+                return j2p_fail(J2P_EINVAL, "decode: %zu bytes of data are too many for subsequences of %u bits", nraw, S);
+        }
+        const DecodeTables tables = decode_tables(p, S);
+        const unsigned nint = f.intervals, nbound = (unsigned)bound, nblocks = tables.g.nblocks;
+        const unsigned nchunks = (unsigned)((nraw + kUnstuffChunk - 1) / kUnstuffChunk);
+        const auto tiles = [](unsigned n) { return (n + kScanTile - 1) / kScanTile; };
+        const size_t clean_room = (nraw + 16 + 3) / 4 * 4;
+        j2p_carve take;
+        const size_t raw_at = take(data_on_device ? 0 : nraw), clean_at = take(clean_room);
+        const size_t keepc_at = take((size_t)nchunks * 4), markc_at = take((size_t)nchunks * 4), keepo_at = take((size_t)nchunks * 8);
+        const size_t marko_at = take((size_t)nchunks * 8), keeps_at = take(((size_t)tiles(nchunks) + 1) * 8), marks_at = take(((size_t)tiles(nchunks) + 1) * 8);
+        const size_t rst_at = take((size_t)nint * 8), icount_at = take((size_t)nint * 4), first_at = take((size_t)nint * 8);
+        const size_t isums_at = take(((size_t)tiles(nint) + 1) * 8);
+        const size_t exit_at[2] = {take((size_t)nbound * 8), take((size_t)nbound * 8)};
+        const size_t last_at = take((size_t)nbound * 8), done_at = take((size_t)nbound * 4), before_at = take((size_t)nbound * 8);
+        const size_t dsums_at = take(((size_t)tiles(nbound) + 1) * 8);
+        const size_t diff_at = take((size_t)nblocks * 4), dc_at = take((size_t)nblocks * 8), dcsums_at = take(((size_t)tiles(nblocks) + 1) * 8);
+        const size_t tables_at = take(sizeof(DecodeTables)), flags_at = take(256);     // flags: [0] the error word, [1..] the rounds' change counters
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        HIP_TRY(j2p_pool_take(device, take.total, &block, &block_bytes));
+        char *const base = static_cast<char *>(block);
+        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        const auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long *>(base + at); };
+        unsigned *const flags = u32(flags_at);
+        // everything below leaves through `finish`, which gives the block back once the stream is idle
+        const auto finish = [&](int rc) {
+                (void)hipStreamSynchronize(stream);
+                j2p_pool_give(device, block, block_bytes);
+                return rc;
+        };
+        const auto failed = [&](hipError_t e, const char *what) { return finish(j2p_fail(J2P_EDEVICE, "decode: %s: %s", what, hipGetErrorString(e))); };
+
+        const auto t_begin = std::chrono::steady_clock::now();
+        const uint8_t *raw = data;
+        hipError_t e = hipSuccess;
+        if(!data_on_device) {
+                e = hipMemcpyAsync(base + raw_at, data, nraw, hipMemcpyHostToDevice, stream);
+                raw = reinterpret_cast<const uint8_t *>(base + raw_at);
+        }
+        if(e == hipSuccess) { e = hipMemcpyAsync(base + tables_at, &tables, sizeof(tables), hipMemcpyHostToDevice, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + clean_at, 0xff, clean_room, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + rst_at, 0, (size_t)nint * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + exit_at[0], 0, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + last_at, 0xff, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + done_at, 0, (size_t)nbound * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + diff_at, 0, (size_t)nblocks * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(flags, 0, 256, stream); }
+        if(e != hipSuccess) { return failed(e, "staging"); }
+        // the clean stream and the restart markers' places
+        hipLaunchKernelGGL(k_unstuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, raw, nraw, nchunks, u32(keepc_at), u32(markc_at));
+        queue_scan(stream, u32(keepc_at), nchunks, u64(keeps_at), u64(keepo_at));
+        queue_scan(stream, u32(markc_at), nchunks, u64(marks_at), u64(marko_at));
+        hipLaunchKernelGGL(k_unstuff_copy, dim3((nchunks + 3) / 4), dim3(256), 0, stream, raw, nraw, nchunks, static_cast<const unsigned long long *>(u64(keepo_at)),
+                           static_cast<const unsigned long long *>(u64(marko_at)), nint, reinterpret_cast<uint8_t *>(base + clean_at), clean_room, u64(rst_at),
+                           flags);
+        // the subsequences of every interval
+        DecodeBuffers b;
+        b.tables = reinterpret_cast<const DecodeTables *>(base + tables_at);
+        b.words = u32(clean_at);
+        b.nwords = clean_room / 4;
+        b.clean_bytes = u64(keeps_at) + tiles(nchunks);
+        b.nmarkers = u64(marks_at) + tiles(nchunks);
+        b.rst = u64(rst_at);
+        b.first = u64(first_at);
+        b.nsub = u64(isums_at) + tiles(nint);
+        b.error = flags;
+        hipLaunchKernelGGL(k_decode_intervals, dim3((nint + 255) / 256), dim3(256), 0, stream, b, nint, S, u32(icount_at));
+        queue_scan(stream, u32(icount_at), nint, u64(isums_at), u64(first_at));
+        // rounds until no entry state changes: at most one per subsequence of the longest interval, and one that finds nothing to do
+        j2p_decode_stats st;
+        memset(&st, 0, sizeof(st));
+        st.intervals = nint;
+        unsigned rounds = 0;
+        bool settled = false;
+        while(!settled) {
+                if(rounds > nbound) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: the decoder's states did not settle in %u rounds", rounds)); }
+                const unsigned group = rounds == 0 ? kDecodeFirstGroup : kDecodeGroup;
+                if(rounds) { (void)hipMemsetAsync(flags + 1, 0, group * 4, stream); }
+                for(unsigned q = 0; q < group; q++, rounds++) {
+                        hipLaunchKernelGGL(k_decode_sync, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound,
+                                           static_cast<const unsigned long long *>(u64(exit_at[rounds & 1])), u64(exit_at[(rounds + 1) & 1]), u64(last_at),
+                                           u32(done_at), flags + 1 + q);
+                }
+                unsigned seen[1 + kDecodeGroup] = {0};
+                unsigned long long totals[2] = {0, 0};
+                e = hipMemcpyAsync(seen, flags, (1 + group) * 4, hipMemcpyDeviceToHost, stream);
+                if(e == hipSuccess) { e = hipMemcpyAsync(&totals[0], b.nsub, 8, hipMemcpyDeviceToHost, stream); }
+                if(e == hipSuccess) { e = hipMemcpyAsync(&totals[1], b.clean_bytes, 8, hipMemcpyDeviceToHost, stream); }
+                if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+                if(e != hipSuccess) { return failed(e, "rounds"); }
+                if(seen[0]) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(seen[0]))); }
+                st.subsequences = (unsigned)totals[0];
+                st.data_bytes = totals[1];
+                for(unsigned q = 0; q < group && !settled; q++) {
+                        if(seen[1 + q] == 0) {
+                                settled = true;
+                        } else {
+                                if(st.rounds < J2P_DECODE_STATS_ROUNDS) { st.recomputed[st.rounds] = seen[1 + q]; }
+                                st.rounds++;
+                        }
+                }
+        }
+        const unsigned long long *const exits = u64(exit_at[rounds & 1]);       // what the last round queued wrote
+        // the block ordinals, the ACs and the DC differences, the DCs
+        queue_scan(stream, u32(done_at), nbound, u64(dsums_at), u64(before_at));
+        DecodeOut o;
+        memset(&o, 0, sizeof(o));
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                o.coef[c] = coef[c];
+                (void)hipMemsetAsync(coef[c], 0, j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h), stream);
+        }
+        o.diff = u32(diff_at);
+        hipLaunchKernelGGL(k_decode_write, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound, exits, static_cast<const unsigned long long *>(u64(before_at)), o);
+        queue_scan(stream, u32(diff_at), nblocks, u64(dcsums_at), u64(dc_at));
+        hipLaunchKernelGGL(k_decode_dc, dim3((nblocks + 255) / 256), dim3(256), 0, stream, b.tables, static_cast<const unsigned *>(u32(diff_at)),
+                           static_cast<const unsigned long long *>(u64(dc_at)), o, flags);
+        unsigned bad = 0;
+        e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+        if(e != hipSuccess) { return failed(e, "the final pass"); }
+        if(bad) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(bad))); }
+        st.decode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if(stats) { *stats = st; }
+        return finish(J2P_OK);
+}
+
+int j2p_jpeg_open(const uint8_t *file, size_t size, j2p_jpeg_file *opened)
+{
+        *opened = j2p_jpeg_file();
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        int where = -1;
+        const int kind = j2p_memory_of_pointer(file, &where);
+        if(kind == J2P_MEMORY_OTHER) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies in managed or unknown memory (plain device memory, or host memory)"); }
+        // the parser reads host memory: a file in device memory comes down for it, and the copy goes when this returns
+        std::unique_ptr<uint8_t[]> copy;
+        if(kind == J2P_MEMORY_DEVICE) {
+                copy.reset(new(std::nothrow) uint8_t[size]);
+                if(!copy) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                if(const hipError_t e = hipMemcpy(copy.get(), file, size, hipMemcpyDeviceToHost); e != hipSuccess) {
+                        return j2p_fail(J2P_EDEVICE, "jpeg: reading the file: %s", hipGetErrorString(e));
+                }
+        }
+        std::unique_ptr<j2p_jpeg_parsed> parsed(new(std::nothrow) j2p_jpeg_parsed);
+        if(!parsed) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        if(const int rc = j2p_jpeg_parse_full(copy ? copy.get() : file, size, parsed.get()); rc != J2P_OK) { return rc; }
+        opened->scan = file + parsed->info.scan_begin;
+        opened->parsed = std::move(parsed);
+        opened->on_device = kind == J2P_MEMORY_DEVICE;
+        opened->device = opened->on_device ? where : -1;
+        return J2P_OK;
+}
+
+j2p_decoded_grids::j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats) : device_(device)
+{
+        rc = decode(file, S, stats);
+}
+
+int j2p_decoded_grids::decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats)
+{
+        const j2p_jpeg_info &f = file.parsed->info;
+        j2p_carve part;
+        for(unsigned c = 0; c < f.ncomp; c++) { at[c] = part(j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h)); }
+        bytes = part.total;
+        HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        HIP_TRY(j2p_pool_take(device_, bytes, &block, &block_bytes_));
+        for(unsigned c = 0; c < f.ncomp; c++) { coef[c] = reinterpret_cast<int16_t *>(static_cast<char *>(block) + at[c]); }
+        return j2p_decode_file(device_, stream_, file.parsed.get(), file.scan, file.on_device, S, coef, stats);
+}
+
+j2p_decoded_grids::~j2p_decoded_grids()
+{
+        if(stream_) {
+                (void)hipStreamSynchronize(stream_);
+                (void)hipStreamDestroy(stream_);
+        }
+        if(block) { j2p_pool_give(device_, block, block_bytes_); }
+}
+
+extern "C" {
+
+int j2p_entropy_decode_ex(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info,
+                          unsigned subsequence_bits, j2p_decode_stats *stats)
+{
+        if(!coef_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(subsequence_bits && (subsequence_bits < J2P_DECODE_SUBSEQUENCE_MIN || subsequence_bits > J2P_DECODE_SUBSEQUENCE_MAX)) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", subsequence_bits, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        j2p_jpeg_file opened;
+        if(const int rc = j2p_jpeg_open(file, size, &opened); rc != J2P_OK) { return rc; }
+        const j2p_jpeg_info &f = opened.parsed->info;
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                if(!coef_host[c]) { return j2p_fail(J2P_EINVAL, "decode: component %u has no room for its coefficients", c); }
+        }
+        if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
+        if(opened.on_device && opened.device != device) {
+                return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the decode runs on %d", opened.device, device);
+        }
+        DeviceGuard guard(device);
+        const j2p_decoded_grids grids(device, opened, subsequence_bits, stats);
+        if(grids.rc != J2P_OK) { return grids.rc; }
+        // one staging copy down, so that nothing reaches the caller's arrays unless all of it does
+        const std::unique_ptr<char[]> staged(new(std::nothrow) char[grids.bytes]);
+        if(!staged) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        if(const hipError_t e = hipMemcpy(staged.get(), grids.block, grids.bytes, hipMemcpyDeviceToHost); e != hipSuccess) {
+                return j2p_fail(J2P_EDEVICE, "decode: %s", hipGetErrorString(e));
+        }
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                memcpy(coef_host[c], staged.get() + grids.at[c], j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h));
+                if(quant) { memcpy(quant[c], f.comp[c].quant, sizeof(f.comp[c].quant)); }
+        }
+        if(info) { *info = f; }
+        return J2P_OK;
+}
+
+int j2p_entropy_decode(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info)
+{
+        return j2p_entropy_decode_ex(device, file, size, coef_host, quant, info, 0, nullptr);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // jpeg2png_amd — device code that READS a JPEG file: the entropy-coded data of one baseline scan Huffman-decoded into the
 // int16 coefficient grids (include/jpeg2png_amd.h: "Reading a JPEG file"; the argument: DESIGN.md section 21).  Included by
-// j2p_output.hip behind j2p_output_kernels.hip.h, whose k_scan_* kernels it reuses.  The passes, each a launch or a few;
+// j2p_codec.hip behind j2p_codec_kernels.hip.h, whose k_scan_* kernels it reuses.  The passes, each a launch or a few;
 // order between workgroups comes from launch boundaries only, nobody waits for anybody:
 //   k_unstuff_count      bytes kept and RSTn markers per 256-byte chunk of the data, k_scan_* twice     -> keepoff[], markoff[]
 //   k_unstuff_copy       the clean bit stream (no 00 behind FF, no markers, no fill bytes); every marker's byte offset in it

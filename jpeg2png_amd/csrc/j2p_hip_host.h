@@ -1,5 +1,5 @@
 // jpeg2png_amd — host-side HIP helpers shared by the translation units that call the runtime with a solver's device and
-// stream (j2p_solver.hip, j2p_output.hip); not part of the C-ABI.
+// stream (j2p_solver.hip, j2p_output.hip, j2p_codec.hip); not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -122,6 +122,8 @@ static inline unsigned j2p_next_chunk(unsigned done, unsigned left, double elaps
 }  // extern "C"
 
 #include <hip/hip_runtime_api.h>     // hipStream_t, hipError_t: every C++ unit of the library is a HIP unit
+#include <functional>
+#include <memory>
 
 // Environment knobs of the EXPERIMENTS build (-DJ2P_EXPERIMENTS: jpeg2png_amd/libjpeg2png_amd_exp.so, built by
 // buildlib.build_experiments() for the schedule-equivalence tests and the timing tools): the switches that move choices
@@ -165,14 +167,69 @@ int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out);
 // the size of that block now (0: none yet): a request beyond it gets ANOTHER block, and what the old one held is lost
 size_t j2p_solver_scratch_bytes(const j2p_solver *s);
 
-// ---- reading a JPEG file on the device (j2p_output.hip) ----
-// the file where the host can parse it: `file` itself (*copy NULL), or a malloc'ed copy of device memory (*on_device, *device_of)
-int j2p_decode_fetch(const uint8_t *file, size_t size, uint8_t **copy, bool *on_device, int *device_of);
+// ---- the JPEG codec (j2p_codec.hip) ----
+// offsets of the parts of one block of device memory, in the order asked for, each aligned to 256 bytes
+struct j2p_carve {
+        size_t total = 0;
+        size_t operator()(size_t bytes)
+        {
+                const size_t at = total;
+                total += ((bytes ? bytes : 1) + 255) / 256 * 256;
+                return at;
+        }
+};
+// bytes of a component's coefficient grid of bw x bh blocks
+static inline size_t j2p_grid_bytes(unsigned bw, unsigned bh) { return (size_t)bw * bh * 64 * sizeof(int16_t); }
+
+// the block grids of the file j2p_encode_scan writes from a spec that j2p_jpeg_error accepted: component c's grid has
+// bw[c] x bh[c] blocks; sub_w x sub_h of component 0's make an MCU (1 x 1 for one component)
+struct j2p_scan_grids {
+        unsigned sub_w, sub_h, bw[3], bh[3];
+};
+j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp);
+// The coder: the file of `spec` on the host from coefficients the caller leaves in device memory, on `stream`, which has been
+// waited for on return.  memory(bytes, &p, &moved): one block of device memory of at least that size which stays the same block
+// while it is large enough and is ANOTHER block (moved), contents lost, once it has to grow (j2p_solver_scratch);
+// fill(stream, coef): queues what leaves component c's coefficients (j2p_scan_grids_of) at coef[c].  Both may be called up to
+// three times.  J2P_ESPACE: *size is what the file needs.
+int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size);
+
+// A JPEG file opened for decoding: its marker segments parsed on the host (from a temporary copy for a file in device memory),
+// and where the caller's bytes are, which the decode reads in place.
+struct j2p_jpeg_file {
+        std::unique_ptr<j2p_jpeg_parsed> parsed;
+        const uint8_t *scan = nullptr;  // the caller's bytes from info.scan_begin on
+        bool on_device = false;         // ... which are plain device memory
+        int device = -1;                // ... of this device (-1: host memory)
+};
+// J2P_EINVAL (NULL or empty; managed or unknown memory), J2P_ENOMEM, J2P_EDEVICE (the copy), or what j2p_jpeg_parse_full says
+int j2p_jpeg_open(const uint8_t *file, size_t size, j2p_jpeg_file *opened);
 // parsed's scan, whose bytes begin at `data` (host memory, or device memory of `device` read in place), decoded into the device
 // grids coef[c] (blocks_w * blocks_h * 64 int16) on `stream`; waits for the stream.  S: bits per subsequence, 0 the default.
 // The calling thread's device is `device`.  J2P_EFORMAT: the grids hold nothing of use.
 int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
                     int16_t *const coef[3], j2p_decode_stats *stats);
+// The component grids of an opened file in one pooled block of `device` (the calling thread's), each at a 256-byte step, on a
+// stream of their own: construction decodes (j2p_decode_file), `rc` is what came of it, and only after J2P_OK do the grids hold
+// anything.  Destruction waits for the stream, destroys it and gives the block back.
+struct j2p_decoded_grids {
+        int rc = J2P_OK;
+        int16_t *coef[3] = {nullptr, nullptr, nullptr};
+        size_t at[3] = {0, 0, 0};       // coef[c] is the block + at[c]
+        void *block = nullptr;
+        size_t bytes = 0;               // the block's first bytes, which hold the grids
+        j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats);
+        ~j2p_decoded_grids();
+        j2p_decoded_grids(const j2p_decoded_grids &) = delete;
+        j2p_decoded_grids &operator=(const j2p_decoded_grids &) = delete;
+
+private:
+        int device_;
+        hipStream_t stream_ = nullptr;
+        size_t block_bytes_ = 0;
+        int decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats);
+};
 
 // a whole-canvas solver whose coefficients a decode has left in device memory of `device` (decoded[c]: channel c's grid,
 // planes[c].w / 8 x planes[c].h / 8 blocks; planes carry no arrays), copied into the resident buffers on the solver's own stream;

@@ -1304,16 +1304,12 @@ int j2p_solver_create_from_jpeg(j2p_solver **out, int device, void *stream, cons
 {
         if(out) { *out = nullptr; }
         if(!out || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        uint8_t *copy = nullptr;
-        bool on_device = false;
-        int where = -1;
-        if(const int rc = j2p_decode_fetch(file, size, &copy, &on_device, &where); rc != J2P_OK) { return rc; }
-        std::unique_ptr<uint8_t, decltype(&free)> copy_owner(copy, &free);
-        std::unique_ptr<j2p_jpeg_parsed> parsed(new(std::nothrow) j2p_jpeg_parsed);
-        if(!parsed) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
-        if(const int rc = j2p_jpeg_parse_full(copy ? copy : file, size, parsed.get()); rc != J2P_OK) { return rc; }
-        if(on_device && where != device) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the solver on %d", where, device); }
-        const j2p_jpeg_info &f = parsed->info;
+        j2p_jpeg_file opened;
+        if(const int rc = j2p_jpeg_open(file, size, &opened); rc != J2P_OK) { return rc; }
+        if(opened.on_device && opened.device != device) {
+                return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the solver on %d", opened.device, device);
+        }
+        const j2p_jpeg_info &f = opened.parsed->info;
         j2p_plane planes[3];
         memset(planes, 0, sizeof(planes));
         for(unsigned c = 0; c < f.ncomp; c++) {
@@ -1323,7 +1319,7 @@ int j2p_solver_create_from_jpeg(j2p_solver **out, int device, void *stream, cons
                 planes[c].h_samp = f.comp[c].h_samp;
                 planes[c].quant_table = f.comp[c].quant;
         }
-        const FileSource source = {parsed.get(), file + f.scan_begin, on_device, {nullptr, nullptr, nullptr}};
+        const FileSource source = {opened.parsed.get(), opened.scan, opened.on_device, {nullptr, nullptr, nullptr}};
         const j2p_band whole = {0, 0};
         const int rc = create_solver(out, device, stream, f.ncomp, planes, nullptr, &source, weight, pweight, iterations, whole, 0);
         if(rc == J2P_OK && info) { *info = f; }

@@ -126,6 +126,34 @@ def test_a_file_in_device_memory_gives_the_same(lib, good):
 
 
 @pytest.mark.gpu
+def test_damaged_files_in_device_memory_are_refused(lib, good):
+    """the failure exits of a file that was opened from device memory: one whose headers are refused (the parse of its host copy
+    fails: nothing is opened) and one whose scan is (the decode into the pooled grids fails), then a good decode of the same kind"""
+    import torch
+    import jpeg2png_amd as j
+    ok, want = good["sparse_41x23_420"]
+    rst_removed, _why = dc.damaged_cases()["rst_removed"]
+    comps, _, _ = dc.geometry(dc.parse(rst_removed))
+
+    def decode(data, shapes):
+        # (the C entry point: jpeg2png_amd.entropy_decode reads the headers of a host copy itself first)
+        buf = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        arrays = [np.full(s, 0x5A5A, dtype=np.int16) for s in shapes]
+        ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
+        return lib.j2p_entropy_decode(0, buf.data_ptr(), buf.numel(), ptrs, None, None), arrays
+
+    for name, bad, shapes, code in (("progressive", bytes(ok).replace(b"\xff\xc0", b"\xff\xc2", 1), [a.shape for a in want], j.J2P_ENOTSUP),
+                                    ("rst_removed", rst_removed, [(gh, gw, 64) for gh, gw, _, _ in comps], J2P_EFORMAT)):
+        rc, got = decode(bad, shapes)
+        assert rc == code, f"{name}: {rc} {lib.j2p_last_error().decode()}"
+        assert all((a == 0x5A5A).all() for a in got), name
+    rc, got = decode(ok, [a.shape for a in want])
+    assert rc == 0, lib.j2p_last_error().decode()
+    check("after the refusals", got, want)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", DAMAGED)
 def test_damaged_files_are_refused(lib, good, name):
     """J2P_EFORMAT, the pre-filled output untouched, and a good decode afterwards in the same process"""

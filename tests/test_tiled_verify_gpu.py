@@ -95,8 +95,8 @@ def test_a_broken_exchange_is_found_and_demoted(lib):
 def _variant(name, flag):
     lib_path = os.path.join(ROOT, "ab", f"libj2p_{name}.so")
     sources = [os.path.join(ROOT, "jpeg2png_amd", "csrc", f) for f in
-               ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_solver.hip", "j2p_output_kernels.hip.h", "j2p_output.hip", "j2p_tiled.hip",
-                "j2p_batch.hip", "compute_host.c")]
+               ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_solver.hip", "j2p_output_kernels.hip.h", "j2p_output.hip",
+                "j2p_codec_kernels.hip.h", "j2p_codec.hip", "j2p_tiled.hip", "j2p_batch.hip", "compute_host.c")]
     if not os.path.exists(lib_path) or any(os.path.getmtime(f) > os.path.getmtime(lib_path) for f in sources):
         subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variant.py"), name, flag], check=True, cwd=ROOT, timeout=600)
     return lib_path
