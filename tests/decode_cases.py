@@ -6,7 +6,11 @@ decode(data) -> (arrays, info): per component an int16 array [blocks_h, blocks_w
 Refused with .code EFORMAT or ENOTSUP and .why, a word for what was wrong.
 
 write(...) builds on tests/entropy_cases.py — its scan order, its _block and its four kinds of content, imported and not edited —
-and adds restart intervals, sampling factors beyond 2, Huffman tables other than Annex K's, fill bytes and bytes behind EOI."""
+and adds restart intervals, sampling factors beyond 2, Huffman tables other than Annex K's, fill bytes and bytes behind EOI.
+
+framing_cases() was chosen for what a JPEG file may contain; boundary_cases(), place_markers() and periodic_case() for where the
+device's kernels divide their work (restart markers on lane, chunk and workgroup edges, more intervals than a workgroup or a
+scan tile holds, more scan tiles than k_scan_tiles takes in one trip); damaged_cases() are the files to refuse."""
 import contextlib
 
 import numpy as np
@@ -369,52 +373,71 @@ def _segment(marker, payload, fill):
     return (b"\xff" * (2 if fill else 0)) + ec._segment(marker, payload)
 
 
-def write(coefficients, width, height, quant, sub=(1, 1), restart=0, tables="annex_k", fill=False, trailing=b"", dqt16=False, sof=0xC0, report=None):
-    """a baseline JPEG file of the coefficients (entropy_cases' grids for sub = (sx, sy), chroma 1x1).
-    restart: MCUs per restart interval (0: none).  tables: "annex_k" (slots 0 / 1 as libjpeg writes them), "swapped" (component 0 codes
-    with Annex K's chroma pair from slot 2, components 1 and 2 with the luma pair from slot 3) or "own" (tables built from this
-    file's own symbol counts, component 0's in slot 0, the others' in slot 1).  fill: two FF fill bytes in front of every marker
-    from DQT on, the RSTn included.  trailing: bytes behind EOI.  dqt16: 16-bit DQT entries, both tables in one segment.
-    report (a dict): receives 'stuffed_before_rst', how many restart markers follow a stuffed FF 00 directly."""
+def _code_scan(coefficients, order, per_mcu, nmcu, ri, swapped):
+    """the stuffed entropy-coded data of every restart interval, coded with entropy_cases' current tables: [bytes]"""
+    chunks = []
+    zero = np.zeros(64, dtype=np.int64)
+    for first in range(0, nmcu, ri):
+        bits, pred = ec._Bits(), [0, 0, 0]
+        for c, y, x in order[first * per_mcu:min(first + ri, nmcu) * per_mcu]:
+            t = (0 if c == 0 else 1) if not swapped else (1 if c == 0 else 0)
+            if y is None:
+                dummy = zero.copy()
+                dummy[0] = pred[c]
+                pred[c] = ec._block(bits, t, dummy, pred[c])
+            else:
+                pred[c] = ec._block(bits, t, coefficients[c][y, x], pred[c])
+        short = -bits.n % 8
+        bits.put((1 << short) - 1, short)
+        chunks.append(bytes(bits.data).replace(b"\xff", b"\xff\x00"))
+    return chunks
+
+
+def _layout(coefficients, width, height, sub):
+    """what the writer codes: (coefficients as grids, sub, scan order, blocks per MCU, MCUs)"""
     ncomp = len(coefficients)
     sub = sub if ncomp == 3 else (1, 1)
     grids = ec.grids(width, height, ncomp, sub)
     coefficients = [np.asarray(a).reshape(gh, gw, 64) for a, (gh, gw) in zip(coefficients, grids)]
     order = ec.scan_order(width, height, ncomp, sub)
     per_mcu = sub[0] * sub[1] + 2 if ncomp == 3 else 1
-    nmcu = len(order) // per_mcu
+    return coefficients, sub, order, per_mcu, len(order) // per_mcu
+
+
+def symbol_counts(coefficients, width, height, sub=(1, 1), restart=0):
+    """{"dc": [{symbol: count}, {symbol: count}], "ac": [...]}: what a file of these coefficients codes with table pair 0
+    (component 0) and pair 1 (the others)"""
+    coefficients, sub, order, per_mcu, nmcu = _layout(coefficients, width, height, sub)
+    counting = [_Counting(), _Counting()], [_Counting(), _Counting()]
+    with _coding_with(*counting):
+        _code_scan(coefficients, order, per_mcu, nmcu, restart or nmcu, False)
+    return {"dc": [t.counts for t in counting[0]], "ac": [t.counts for t in counting[1]]}
+
+
+def write(coefficients, width, height, quant, sub=(1, 1), restart=0, tables="annex_k", fill=False, trailing=b"", dqt16=False, sof=0xC0, report=None):
+    """a baseline JPEG file of the coefficients (entropy_cases' grids for sub = (sx, sy), chroma 1x1).
+    restart: MCUs per restart interval (0: none).  tables: "annex_k" (slots 0 / 1 as libjpeg writes them), "swapped" (component 0 codes
+    with Annex K's chroma pair from slot 2, components 1 and 2 with the luma pair from slot 3), "own" (tables built from this
+    file's own symbol counts, component 0's in slot 0, the others' in slot 1) or explicit ones, {"dc": [(BITS, HUFFVAL), (BITS,
+    HUFFVAL)], "ac": [...]}, written to slots 0 and 1 as "own" does.  fill: two FF fill bytes in front of every marker
+    from DQT on, the RSTn included.  trailing: bytes behind EOI.  dqt16: 16-bit DQT entries, both tables in one segment.
+    report (a dict): receives 'stuffed_before_rst', how many restart markers follow a stuffed FF 00 directly."""
+    ncomp = len(coefficients)
+    coefficients, sub, order, per_mcu, nmcu = _layout(coefficients, width, height, sub)
     ri = restart or nmcu
+    swapped = isinstance(tables, str) and tables == "swapped"
 
-    def code_scan():
-        chunks = []
-        zero = np.zeros(64, dtype=np.int64)
-        for first in range(0, nmcu, ri):
-            bits, pred = ec._Bits(), [0, 0, 0]
-            for c, y, x in order[first * per_mcu:min(first + ri, nmcu) * per_mcu]:
-                t = (0 if c == 0 else 1) if tables != "swapped" else (1 if c == 0 else 0)
-                if y is None:
-                    dummy = zero.copy()
-                    dummy[0] = pred[c]
-                    pred[c] = ec._block(bits, t, dummy, pred[c])
-                else:
-                    pred[c] = ec._block(bits, t, coefficients[c][y, x], pred[c])
-            short = -bits.n % 8
-            bits.put((1 << short) - 1, short)
-            chunks.append(bytes(bits.data).replace(b"\xff", b"\xff\x00"))
-        return chunks
-
-    if tables == "own":
-        counting = [_Counting(), _Counting()], [_Counting(), _Counting()]
-        with _coding_with(*counting):
-            code_scan()
-        pairs = {"dc": [optimal_table(t.counts) if t.counts else ANNEX_K["dc"][i] for i, t in enumerate(counting[0])],
-                 "ac": [optimal_table(t.counts) if t.counts else ANNEX_K["ac"][i] for i, t in enumerate(counting[1])]}
+    if isinstance(tables, dict):
+        pairs = tables
+    elif tables == "own":
+        counts = symbol_counts(coefficients, width, height, sub, restart)
+        pairs = {kind: [optimal_table(n) if n else ANNEX_K[kind][i] for i, n in enumerate(counts[kind])] for kind in ("dc", "ac")}
     else:
         pairs = ANNEX_K
     with _coding_with(pairs["dc"], pairs["ac"]):
-        chunks = code_scan()
+        chunks = _code_scan(coefficients, order, per_mcu, nmcu, ri, swapped)
 
-    slots = {"annex_k": (0, 1), "own": (0, 1), "swapped": (3, 2)}[tables]     # the slot of pair 0 (luma's, or the first own), of pair 1
+    slots = (3, 2) if swapped else (0, 1)                                      # the slot of pair 0 (luma's, or the first own), of pair 1
     ntab = 2 if ncomp == 3 else 1
     out = b"\xff\xd8" + ec._segment(0xe0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
     dqt = [bytes([(16 if dqt16 else 0) | t]) + b"".join(int(quant[t][ec.ZIGZAG[k]]).to_bytes(2 if dqt16 else 1, "big") for k in range(64)) for t in range(ntab)]
@@ -423,7 +446,7 @@ def write(coefficients, width, height, quant, sub=(1, 1), restart=0, tables="ann
     for c in range(ncomp):
         body += bytes([c + 1, (sub[0] << 4) | sub[1] if c == 0 else 0x11, 0 if c == 0 else 1])
     out += _segment(sof, body, fill)
-    used = (0, 1) if ncomp == 3 else ((1,) if tables == "swapped" else (0,))
+    used = (0, 1) if ncomp == 3 else ((1,) if swapped else (0,))
     for t in used:
         out += _segment(0xc4, bytes([slots[t]]) + bytes(pairs["dc"][t][0]) + bytes(pairs["dc"][t][1]), fill)
         out += _segment(0xc4, bytes([0x10 | slots[t]]) + bytes(pairs["ac"][t][0]) + bytes(pairs["ac"][t][1]), fill)
@@ -431,7 +454,7 @@ def write(coefficients, width, height, quant, sub=(1, 1), restart=0, tables="ann
         out += _segment(0xdd, bytes([restart >> 8, restart & 255]), fill)
     body = bytes([ncomp])
     for c in range(ncomp):
-        t = (0 if c == 0 else 1) if tables != "swapped" else (1 if c == 0 else 0)
+        t = (0 if c == 0 else 1) if not swapped else (1 if c == 0 else 0)
         body += bytes([c + 1, (slots[t] << 4) | slots[t]])
     out += _segment(0xda, body + bytes([0, 0x3f, 0]), fill)
     stuffed_before = 0
@@ -541,7 +564,217 @@ def damaged_cases():
     bits.put((1 << short) - 1, short)
     one = ec.make(8, 8, 1, (1, 1), "zero")
     out["run_past_63"] = ec.header(8, 8, 1, (1, 1), one["quant"]) + bytes(bits.data).replace(b"\xff", b"\xff\x00") + b"\xff\xd9"
+    # files whose marker segments and sizes are in order: only the kernels that decode the data can refuse them
+    # a DC that leaves int16 in its 17th block (the 16-block neighbour, boundary_cases()' dc_near_limit, is a good file)
+    out["dc_above_int16"] = _dc_file([2047] * 17)[0]
+    out["dc_below_int16"] = _dc_file([-2047] * 17)[0]
+    # whole bytes behind the last block's padding: one, and several 32-bit subsequences of data that belong to no block
+    four = write_case(ec.make(32, 8, 1, (1, 1), "sparse", seed=33))
+    out["leftover_byte"] = four[:-2] + b"\x7f" + b"\xff\xd9"
+    out["leftover_many"] = four[:-2] + bytes([0x12, 0x34, 0x56, 0x78] * 8) + b"\xff\xd9"
+    # one marker too many, the numbers in sequence: an empty interval in the middle, and one in front of EOI
+    f = write_case(rst, restart=2)
+    begin = parse(f)["scan_begin"]
+    cuts = [begin - 2] + [begin + a - 1 for a in marker_offsets(f)] + [len(f) - 2]        # the SOS segment's end, every RSTn, EOI
+    chunks = [f[a + 2:b] for a, b in zip(cuts, cuts[1:])]
+    assert len(chunks) == 9 and all(chunks)
+    for name, with_empty in (("rst_doubled", chunks[:4] + [b""] + chunks[4:]), ("rst_before_eoi", chunks + [b""])):
+        out[name] = f[:begin] + b"".join((bytes([0xff, 0xd0 + (k - 1) % 8]) if k else b"") + c for k, c in enumerate(with_empty)) + b"\xff\xd9"
+    assert f == f[:begin] + b"".join((bytes([0xff, 0xd0 + (k - 1) % 8]) if k else b"") + c for k, c in enumerate(chunks)) + b"\xff\xd9"
+    # ... and the right number of markers with nothing between two of them: eight grey blocks, a marker behind each, the third
+    # block's data gone.  Every other interval is whole, and a DC of -32768 (no differences at all) would be in range: nothing
+    # but the empty interval itself is wrong with this file
+    f = write_case(ec.make(64, 8, 1, (1, 1), "sparse", seed=34), restart=1)
+    begin, at = parse(f)["scan_begin"], marker_offsets(f)
+    out["rst_empty_interval"] = f[:begin + at[1] + 1] + f[begin + at[2] - 1:]
     want = {"cut_mid_block": ("truncated", "leftover", "code", "run"), "cut_between_blocks": ("truncated",), "rst_number_changed": ("restart",),
-            "rst_removed": ("restart",), "code_in_no_table": ("code",), "run_past_63": ("run",)}
+            "rst_removed": ("restart",), "code_in_no_table": ("code",), "run_past_63": ("run",), "dc_above_int16": ("dc",),
+            "dc_below_int16": ("dc",), "leftover_byte": ("leftover",), "leftover_many": ("leftover",), "rst_doubled": ("restart",),
+            "rst_before_eoi": ("restart",), "rst_empty_interval": ("truncated",)}
     assert sorted(out) == sorted(want), sorted(out)
     return {name: (data, want[name]) for name, data in out.items()}
+
+
+# ---- cases aimed at where the kernels divide their work: 4-byte lanes, 256-byte chunks and 1024-byte workgroups of the
+# unstuffing kernels, 256 intervals per workgroup of k_decode_intervals, 1024 elements per tile of the scans and 256 tiles per
+# trip of k_scan_tiles ----
+def marker_offsets(data):
+    """the offset, counted from scan_begin, of the Dn byte of every RSTn marker in the entropy-coded data, in order"""
+    frame = parse(data)
+    out, i, end = [], frame["scan_begin"], frame["scan_end"]
+    while i < end:
+        if data[i] != 0xFF:
+            i += 1
+        elif data[i + 1] == 0:
+            i += 2
+        elif 0xD0 <= data[i + 1] <= 0xD7:
+            out.append(i + 1 - frame["scan_begin"])
+            i += 2
+        else:
+            i += 1                       # a fill byte
+    return out
+
+
+def place_markers(data, targets=(), fixed=None):
+    """the file with FF fill bytes in front of its restart markers.  targets[m] (None, or no entry: the marker stays): as many fill
+    bytes (0..255) go in front of marker m as put its Dn byte at an offset, counted from scan_begin, congruent to targets[m] modulo
+    256; the markers are taken in order, because each insertion moves the later ones.  fixed = {m: n}: n fill bytes in front of
+    marker m, whatever offset that gives."""
+    data = bytes(data)
+    begin = parse(data)["scan_begin"]
+    fixed = fixed or {}
+    for m in range(len(marker_offsets(data))):
+        at = marker_offsets(data)[m]
+        if m in fixed:
+            n = fixed[m]
+        elif m < len(targets) and targets[m] is not None:
+            n = (targets[m] - at) % 256
+        else:
+            continue
+        data = data[:begin + at - 1] + b"\xff" * n + data[begin + at - 1:]
+    return data
+
+
+EDGE_TARGETS = (0, 1, 255, 254, 4, 3)   # the Dn byte's offset modulo 256: FF | Dn across a chunk edge, the pair at a chunk's start,
+#                                         at its end, one byte in front of that, and across and in front of a lane's edge
+
+
+def stuffed_on_chunk_edge(data):
+    """offsets from scan_begin of every stuffed FF 00 whose FF is a chunk's last byte and whose 00 the next chunk's first"""
+    frame = parse(data)
+    ecs = data[frame["scan_begin"]:frame["scan_end"]]
+    return [i for i in range(255, len(ecs) - 1, 256) if ecs[i] == 0xFF and ecs[i + 1] == 0]
+
+
+def blank_chunks(data):
+    """the 256-byte chunks of the entropy-coded data that hold nothing but FF: no byte to keep and no marker"""
+    frame = parse(data)
+    ecs = data[frame["scan_begin"]:frame["scan_end"]]
+    return [c for c in range(len(ecs) // 256) if ecs[256 * c:256 * c + 256] == b"\xff" * 256]
+
+
+def _markers_on_edges_case():
+    """24 MCUs of dense 4:4:4 with a restart marker behind each, the markers moved onto the unstuffing kernels' edges; the seed is
+    the first that also puts a marker's FF in the last byte of a 1024-byte group and a stuffed FF | 00 across a chunk edge.
+    -> (case, the file before placement, the placed file)"""
+    for seed in range(1, 400):
+        case = ec.make(48, 32, 3, (1, 1), "dense", seed=seed, quality=95)
+        plain = write_case(case, restart=1)
+        placed = place_markers(plain, [EDGE_TARGETS[m % 6] for m in range(23)])
+        at = marker_offsets(placed)
+        if any(a % 1024 == 0 for a in at[::6]) and stuffed_on_chunk_edge(placed):
+            return case, plain, placed
+    raise AssertionError("no seed puts a marker on a workgroup edge and a stuffed FF on a chunk edge")
+
+
+def fibonacci_tables(counts):
+    """symbol_counts' result with every table's counts replaced, in order of frequency, by consecutive Fibonacci numbers, and the
+    optimal tables of that: {"dc": [(BITS, HUFFVAL)] * 2, "ac": ...}.  Such a table is almost a single chain: one code of every
+    length, and with more than 15 symbols the lengths above 16 folded back."""
+    def skew(n):
+        out, a, b = {}, 1, 2
+        for s in sorted(n, key=lambda s: (n[s], s)):
+            out[s] = a
+            a, b = b, a + b
+        return out
+    return {kind: [optimal_table(skew(n)) if n else ANNEX_K[kind][i] for i, n in enumerate(counts[kind])] for kind in ("dc", "ac")}
+
+
+def _skewed_tables_case():
+    """dense 4:4:4 blocks in which every second coefficient in zigzag order is zero with probability one half: runs of 0 and 1
+    in front of every size, and an EOB where coefficient 63 went — an alphabet of about 20 AC symbols a table, all of which the
+    file uses, coded with tables skewed so that the rare ones have codes of up to 16 bits"""
+    case = ec.make(24, 40, 3, (1, 1), "dense", seed=22, quality=95)
+    rng = np.random.default_rng(22)
+    odd = np.array([ec.ZIGZAG[k] for k in range(1, 64, 2)])
+    for a in case["coefficients"]:
+        drop = rng.random(a.shape[:2] + (odd.size,)) < 0.5
+        a[:, :, odd] = np.where(drop, 0, a[:, :, odd])
+    tables = fibonacci_tables(symbol_counts(case["coefficients"], 24, 40, (1, 1)))
+    return case, write_case(case, tables=tables)
+
+
+def _dc_file(diffs):
+    """a grey file of len(diffs) blocks in a row, each coding its DC difference and an EOB (written with predictor 0 for every
+    block, as damaged_cases() writes run_past_63: the running sum may leave int16) -> (file, quant)"""
+    bits = ec._Bits()
+    block = np.zeros(64, dtype=np.int64)
+    for d in diffs:
+        block[0] = d
+        ec._block(bits, 0, block, 0)
+    short = -bits.n % 8
+    bits.put((1 << short) - 1, short)
+    quant = ec.quant_tables(75, 1)
+    return ec.header(8 * len(diffs), 8, 1, (1, 1), quant) + bytes(bits.data).replace(b"\xff", b"\xff\x00") + b"\xff\xd9", quant
+
+
+def _dc_near_limit_case():
+    data, quant = _dc_file([2047] * 16)
+    coefficients = np.zeros((1, 16, 64), dtype=np.int16)
+    coefficients[0, :, 0] = 2047 * np.arange(1, 17)
+    return {"width": 128, "height": 8, "sub": (1, 1), "quality": 75, "quant": quant, "coefficients": [coefficients]}, data
+
+
+BOUNDARY = ("markers_on_edges", "fill_covers_chunks", "intervals_257_grey", "intervals_1056_420", "intervals_212_short_last", "skewed_tables",
+            "dc_near_limit")
+_boundary = {}
+
+
+def boundary_cases():
+    """{name: (case, file)} beside framing_cases(); built once a process (the arrays are shared: do not write to them)"""
+    if not _boundary:
+        case, plain, placed = _markers_on_edges_case()
+        _boundary["markers_on_edges"] = (case, placed)
+        # 600 fill bytes cover two whole chunks when they begin in a chunk's first 89 bytes: the first marker of the middle for which they do
+        filled = [place_markers(plain, fixed={m: 600}) for m in range(6, 18)]
+        _boundary["fill_covers_chunks"] = (case, [f for f in filled if len(blank_chunks(f)) == 2][0])
+        grey = ec.make(2056, 8, 1, (1, 1), "sparse", seed=41)
+        _boundary["intervals_257_grey"] = (grey, write_case(grey, restart=1))
+        many = ec.make(528, 512, 3, (2, 2), "sparse", seed=42)                 # 33 x 32 MCUs
+        _boundary["intervals_1056_420"] = (many, write_case(many, restart=1))
+        _boundary["intervals_212_short_last"] = (many, write_case(many, restart=5))
+        _boundary["skewed_tables"] = _skewed_tables_case()
+        _boundary["dc_near_limit"] = _dc_near_limit_case()
+        assert tuple(_boundary) == BOUNDARY
+    return dict(_boundary)
+
+
+# ---- one short period, repeated: a file of any size in milliseconds ----
+PERIOD_SEED = 1
+_period = []
+
+
+def periodic_period():
+    """(blocks int16[4, 64], their entropy-coded bytes before stuffing, bits): four grey blocks (a DC and one to three small ACs
+    each) found by a seeded search, coded from predictor 0, such that the last block's DC is 0 (every repetition codes to the
+    same bits), the bits are whole bytes (no padding), 40 to 44 a block (at 32-bit subsequences there are more subsequences than
+    blocks, and blocks straddle them) and hold exactly one FF byte (the unstuffer has work in every repetition)"""
+    if not _period:
+        rng = np.random.default_rng(PERIOD_SEED)
+        for _trial in range(100000):
+            blocks = np.zeros((4, 64), dtype=np.int16)
+            blocks[:3, 0] = rng.integers(-1023, 1024, size=3)
+            for blk in blocks:
+                for _ in range(int(rng.integers(1, 4))):
+                    blk[ec.ZIGZAG[int(rng.integers(1, 12))]] = int(rng.integers(1, 32)) * (1 if rng.random() < 0.5 else -1)
+            bits, pred = ec._Bits(), 0
+            for blk in blocks:
+                pred = ec._block(bits, 0, blk, pred)
+            if bits.n % 8 == 0 and 160 <= bits.n <= 176 and bytes(bits.data).count(b"\xff") == 1:
+                _period.append((blocks, bytes(bits.data), bits.n))
+                break
+        else:
+            raise AssertionError("no period found")
+    blocks, raw, n = _period[0]
+    assert blocks[3, 0] == 0 and n % 8 == 0 and len(raw) * 8 == n and 40 * 4 <= n <= 44 * 4 and raw.count(b"\xff") == 1
+    return blocks, raw, n
+
+
+def periodic_case(bw, bh):
+    """a grey file of bw x bh blocks (a multiple of four) whose scan is periodic_period() repeated, and its coefficients
+    int16[bh, bw, 64]; the quantisation table is entropy_cases.quant_tables(75, 1)"""
+    blocks, raw, _n = periodic_period()
+    assert bw * bh % 4 == 0
+    quant = ec.quant_tables(75, 1)
+    data = ec.header(8 * bw, 8 * bh, 1, (1, 1), quant) + raw.replace(b"\xff", b"\xff\x00") * (bw * bh // 4) + b"\xff\xd9"
+    return data, np.tile(blocks, (bw * bh // 4, 1)).reshape(bh, bw, 64)

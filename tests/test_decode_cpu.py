@@ -40,7 +40,7 @@ def pil_files():
 @pytest.fixture(scope="module")
 def files():
     """every good file of this module: {name: file}"""
-    out = {f"written_{name}": data for name, (_case, data) in dc.framing_cases().items()}
+    out = {f"written_{name}": data for name, (_case, data) in {**dc.framing_cases(), **dc.boundary_cases()}.items()}
     for name, case in ec.directed_cases().items():
         if "368" not in name:
             out[f"directed_{name}"] = ec.encode(case["coefficients"], case["width"], case["height"], case["quant"], case["sub"])
@@ -69,7 +69,7 @@ def test_restated_decoder_is_libjpeg(read_coefficients, read_component, files, t
 
 
 def test_written_files_hold_their_coefficients():
-    for name, (case, data) in dc.framing_cases().items():
+    for name, (case, data) in {**dc.framing_cases(), **dc.boundary_cases()}.items():
         got, _ = dc.decode(data)
         for c, (a, b) in enumerate(zip(got, case["coefficients"])):
             assert np.array_equal(a, b), f"{name}: component {c}"
@@ -87,6 +87,105 @@ def test_written_files_are_what_their_names_say():
     assert sorted(swapped["dc"]) == [2, 3] and [c[4:] for c in swapped["components"]] == [[2, 2], [3, 3], [3, 3]]
     assert swapped["ac"][2] == annex["ac"][1] and swapped["ac"][3] == annex["ac"][0]
     assert [c[1:3] for c in dc.parse(cases["sparse_41x23_411"][1])["components"]] == [[4, 1], [1, 1], [1, 1]]
+    boundary_files_are_what_their_names_say()
+
+
+def _scan(data):
+    """(the entropy-coded data, the restated parser's frame)"""
+    frame = dc.parse(data)
+    return data[frame["scan_begin"]:frame["scan_end"]], frame
+
+
+def boundary_files_are_what_their_names_say():
+    """(the second half of test_written_files_are_what_their_names_say) every property that boundary_cases() aims at, read from
+    the files' bytes: a case that stops aiming at its edge fails here.  The edges are those of k_unstuff_count / k_unstuff_copy (a lane reads 4 bytes, a wavefront 256, a workgroup 1024, counted
+    from the first byte of the entropy-coded data), k_decode_intervals (256 intervals a workgroup) and the scans (1024 a tile)."""
+    cases = dc.boundary_cases()
+    assert tuple(cases) == dc.BOUNDARY
+    # markers_on_edges: 24 MCUs, 23 markers, each Dn where its target says
+    data = cases["markers_on_edges"][1]
+    ecs, frame = _scan(data)
+    at = dc.marker_offsets(data)
+    assert frame["restart_interval"] == 1 and len(at) == 23 and len(ecs) > 4096
+    assert [a % 256 for a in at] == [dc.EDGE_TARGETS[m % 6] for m in range(23)] and set(dc.EDGE_TARGETS) == {0, 1, 255, 254, 4, 3}
+    assert all(ecs[a - 1] == 0xFF and ecs[a] == 0xD0 + m % 8 for m, a in enumerate(at))
+    assert any(a % 1024 == 0 for a in at), "no marker's FF is the last byte of a 1024-byte group"
+    edge = dc.stuffed_on_chunk_edge(data)
+    assert edge and all(i % 256 == 255 and ecs[i:i + 2] == b"\xff\x00" for i in edge), "no stuffed FF | 00 across a chunk edge"
+    # fill_covers_chunks: the same scan with 600 fill bytes in front of one marker of the middle: two whole chunks of nothing but FF
+    data = cases["fill_covers_chunks"][1]
+    ecs, frame = _scan(data)
+    assert len(dc.marker_offsets(data)) == 23 and len(data) == len(dc.write_case(cases["fill_covers_chunks"][0], restart=1)) + 600
+    blank = [c for c in range(len(ecs) // 256) if ecs[256 * c:256 * c + 256] == b"\xff" * 256]
+    assert len(blank) == 2 and blank[1] == blank[0] + 1 and blank == dc.blank_chunks(data), f"chunks of fill bytes alone: {blank}"
+    fill = ecs.index(b"\xff" * 600)                                             # 600 fill bytes, the marker's FF, its Dn
+    assert fill <= 256 * blank[0] and 6 <= dc.marker_offsets(data).index(fill + 601) < 18
+    # the interval counts
+    for name, intervals, ri, last in (("intervals_257_grey", 257, 1, 1), ("intervals_1056_420", 1056, 1, 1), ("intervals_212_short_last", 212, 5, 1)):
+        data = cases[name][1]
+        ecs, frame = _scan(data)
+        chunks, numbers = dc._intervals(ecs)
+        _comps, mcus_w, mcus_h = dc.geometry(frame)
+        assert (len(chunks), frame["restart_interval"]) == (intervals, ri) and numbers == [m % 8 for m in range(intervals - 1)], name
+        assert mcus_w * mcus_h - (intervals - 1) * ri == last, name
+    assert dc.geometry(dc.parse(cases["intervals_212_short_last"][1]))[1] == 33 and 33 % 5
+    assert cases["intervals_1056_420"][1].count(b"\xff\xd7") == 131 and sum(a.shape[0] * a.shape[1] for a in cases["intervals_1056_420"][0]["coefficients"]) == 6336
+    # skewed_tables: nearly one code a length, and the longest there is
+    case, data = cases["skewed_tables"]
+    frame = dc.parse(data)
+    annex = dc.parse(dc.framing_cases()["restart_1"][1])
+    used = dc.symbol_counts(case["coefficients"], case["width"], case["height"], case["sub"])
+    for slot in (0, 1):
+        lengths = {length for length, _code in frame["ac"][slot]}
+        assert len(lengths) >= 12 and 16 in lengths and frame["ac"][slot] != annex["ac"][slot], sorted(lengths)
+        # ... and the file uses every code of them, the 16-bit ones included
+        assert sorted(frame["ac"][slot].values()) == sorted(used["ac"][slot])
+    # dc_near_limit: the running DC reaches 32752 in the 16th block
+    case, data = cases["dc_near_limit"]
+    assert case["coefficients"][0].shape == (1, 16, 64) and int(case["coefficients"][0].max()) == 32752 == 16 * 2047
+    assert np.array_equal(dc.decode(data)[0][0], case["coefficients"][0])
+
+
+def test_placed_markers_keep_the_data():
+    """place_markers adds fill bytes and nothing else"""
+    cases = dc.boundary_cases()
+    plain = dc.write_case(cases["markers_on_edges"][0], restart=1)
+    for name, added in (("markers_on_edges", None), ("fill_covers_chunks", 600)):
+        data = cases[name][1]
+        assert dc._intervals(_scan(data)[0]) == dc._intervals(_scan(plain)[0]), name
+        assert added is None or len(data) == len(plain) + added
+    assert dc.place_markers(plain, []) == plain and dc.place_markers(plain, [None] * 23) == plain
+    two = dc.place_markers(plain, [None, 7], fixed={0: 3})
+    assert dc.marker_offsets(two)[0] == dc.marker_offsets(plain)[0] + 3 and dc.marker_offsets(two)[1] % 256 == 7
+    assert dc.marker_offsets(two)[2:] == [a + len(two) - len(plain) for a in dc.marker_offsets(plain)[2:]]
+
+
+def test_periodic_files(read_coefficients, read_component, tmp_path):  # noqa: F811
+    """periodic_case: the 12x3 file is entropy_cases.encode's, the restatement's and libjpeg's; the 513x512 one (257 tiles of
+    blocks for the scans of the device's decoder and coder, tests/test_decode_gpu.py) is the same period more often"""
+    blocks, raw, nbits = dc.periodic_period()
+    assert blocks.shape == (4, 64) and blocks[3, 0] == 0                        # every repetition starts from predictor 0
+    assert nbits % 8 == 0 and len(raw) * 8 == nbits                             # no padding
+    assert 40 <= nbits / 4 <= 44                                                # more 32-bit subsequences than blocks
+    assert raw.count(b"\xff") == 1                                              # one stuffed byte a repetition
+    assert all(0 < np.count_nonzero(b[1:]) <= 3 for b in blocks)
+    quant = ec.quant_tables(75, 1)
+    data, want = dc.periodic_case(12, 3)
+    assert want.shape == (3, 12, 64) and data == ec.encode([want], 96, 24, quant)
+    got, _ = dc.decode(data)
+    assert np.array_equal(got[0], want)
+    path = str(tmp_path / "periodic.jpg")
+    open(path, "wb").write(data)
+    assert np.array_equal(libjpeg_arrays(read_coefficients, read_component, path, 1)[0], want)
+    big, coefficients = dc.periodic_case(513, 512)
+    stuffed = raw.replace(b"\xff", b"\xff\x00")
+    head = ec.header(4104, 4096, 1, (1, 1), quant)
+    assert len(stuffed) == nbits // 8 + 1 and len(big) == len(head) + 65664 * len(stuffed) + 2
+    assert big.startswith(head + stuffed * 12) and big.endswith(stuffed * 12 + b"\xff\xd9") and big.count(stuffed) == 65664
+    assert coefficients.shape == (512, 513, 64) and coefficients.dtype == np.int16
+    assert -(-513 * 512 // 1024) == 257                                         # tiles of the DC scan and of the coder's len[]
+    assert np.array_equal(coefficients.reshape(-1, 4, 64)[[0, 1, 32832, 65663]], np.broadcast_to(blocks, (4, 4, 64)))
+    assert np.array_equal(coefficients[:3, :12].reshape(-1, 64)[:12], want.reshape(-1, 64)[:12])
 
 
 def test_restated_decoder_inverts_encode():
@@ -101,6 +200,37 @@ def test_restated_decoder_refuses_the_damaged_files():
         with pytest.raises(dc.Refused) as e:
             dc.decode(data)
         assert e.value.code == dc.EFORMAT and e.value.why in whys, f"{name}: {e.value}"
+
+
+NEEDS_THE_KERNELS = ("dc_above_int16", "dc_below_int16", "leftover_byte", "leftover_many", "rst_doubled", "rst_before_eoi", "rst_empty_interval")
+
+
+def test_some_damage_only_the_kernels_can_see(lib):
+    """the C parser accepts these files: nothing in their marker segments or sizes is wrong, so it is the device's decoder that
+    refuses them (tests/test_decode_gpu.py), as the restatement does only while it decodes"""
+    import jpeg2png_amd as j
+    damaged = dc.damaged_cases()
+    for name in NEEDS_THE_KERNELS:
+        data, _whys = damaged[name]
+        info, frame = j.jpeg_parse(data), dc.parse(data)
+        assert (info["scan_begin"], info["scan_end"]) == (frame["scan_begin"], frame["scan_end"]), name
+    # the neighbours that are good files: 16 blocks of +2047 (boundary_cases) and of -2047, and the four blocks with nothing appended
+    got, _ = dc.decode(dc._dc_file([-2047] * 16)[0])
+    assert int(got[0].min()) == -32752
+    assert damaged["dc_above_int16"][0] != dc.boundary_cases()["dc_near_limit"][1]
+    ecs, _frame = _scan(damaged["leftover_many"][0])
+    assert ecs.endswith(bytes([0x12, 0x34, 0x56, 0x78] * 8)) and _scan(damaged["leftover_byte"][0])[0] == ecs[:-32] + b"\x7f"
+    dc.decode(damaged["leftover_byte"][0][:-3] + b"\xff\xd9")
+    for name, doubled in (("rst_doubled", 4), ("rst_before_eoi", 8)):
+        ecs, frame = _scan(damaged[name][0])
+        chunks, numbers = dc._intervals(ecs)
+        assert frame["restart_interval"] == 2 and numbers == [m % 8 for m in range(9)], name
+        assert [k for k, c in enumerate(chunks) if not c] == [doubled + 1 if name == "rst_before_eoi" else doubled], name
+    # the markers' count and numbers right, one interval empty, the seven others whole
+    ecs, frame = _scan(damaged["rst_empty_interval"][0])
+    chunks, numbers = dc._intervals(ecs)
+    whole = dc._intervals(_scan(dc.write_case(ec.make(64, 8, 1, (1, 1), "sparse", seed=34), restart=1))[0])[0]
+    assert frame["restart_interval"] == 1 and numbers == list(range(7)) and chunks == whole[:2] + [b""] + whole[3:] and all(whole)
 
 
 def test_c_parser_agrees_with_jpeg_header(lib, files):

@@ -4,7 +4,10 @@ Batch.submit(file=)): every comparison is exact, with the arrays of
 the plain-Python restatement in tests/decode_cases.py — which tests/test_decode_cpu.py holds against libjpeg, and which
 returns the coefficients the cases' files were written from.  The directed cases are a few blocks each; the two 368x368 ones
 (about 600 KB dense) are the only ones that cross a workgroup of the scans at the default subsequence length.  At the
-smallest length (32 bits) and an odd one (75) a 16x8 image has dozens of subsequences, and blocks and single symbols straddle them."""
+smallest length (32 bits) and an odd one (75) a 16x8 image has dozens of subsequences, and blocks and single symbols straddle them.
+decode_cases.boundary_cases() put restart markers, stuffed bytes and fill bytes on the unstuffing kernels' lane, chunk and
+workgroup edges, and have more restart intervals than a workgroup of k_decode_intervals (256) and a tile of the scans (1024)
+hold; the periodic file has more blocks, and at 32 bits more subsequences, than the 256 tiles k_scan_tiles takes in one trip."""
 import ctypes
 
 import numpy as np
@@ -25,7 +28,7 @@ def good():
     out = {}
     for name, case in ec.directed_cases().items():
         out[name] = (ec.encode(case["coefficients"], case["width"], case["height"], case["quant"], case["sub"]), case["coefficients"])
-    for name, (case, data) in dc.framing_cases().items():
+    for name, (case, data) in {**dc.framing_cases(), **dc.boundary_cases()}.items():
         out[name] = (data, case["coefficients"])
     for _data, arrays in out.values():
         for a in arrays:
@@ -35,7 +38,11 @@ def good():
 
 DIRECTED = sorted(ec.directed_cases())
 FRAMING = sorted(dc.framing_cases())
-DAMAGED = ("cut_mid_block", "cut_between_blocks", "rst_number_changed", "rst_removed", "code_in_no_table", "run_past_63")
+BOUNDARY = sorted(dc.BOUNDARY)          # aimed at the kernels' lanes, chunks, workgroups and tiles: decode_cases.boundary_cases()
+DAMAGED = ("cut_mid_block", "cut_between_blocks", "rst_number_changed", "rst_removed", "code_in_no_table", "run_past_63",
+           # refused by the kernels alone (kDecodeBadDc, the bytes-left-over arm of kDecodeBadEnd, the marker count of kDecodeBadMarker)
+           "dc_above_int16", "dc_below_int16", "leftover_byte", "leftover_many", "rst_doubled", "rst_before_eoi",
+           "rst_empty_interval")
 
 
 def c_decode(lib, data, shapes, bits=None, fill=0x5A5A):
@@ -62,7 +69,7 @@ def check(name, got, want):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", DIRECTED + FRAMING)
+@pytest.mark.parametrize("name", DIRECTED + FRAMING + BOUNDARY)
 def test_entropy_decode_is_the_restatement(lib, good, name):
     data, want = good[name]
     rc, got, _ = c_decode(lib, data, [a.shape for a in want])
@@ -72,7 +79,7 @@ def test_entropy_decode_is_the_restatement(lib, good, name):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bits", SMALL)
-@pytest.mark.parametrize("name", DIRECTED + FRAMING)
+@pytest.mark.parametrize("name", DIRECTED + FRAMING + BOUNDARY)
 def test_small_subsequences(lib, good, name, bits):
     data, want = good[name]
     rc, got, stats = c_decode(lib, data, [a.shape for a in want], bits=bits)
@@ -83,6 +90,46 @@ def test_small_subsequences(lib, good, name, bits):
     assert stats.subsequences >= stats.data_bytes * 8 // bits
     assert 1 <= stats.rounds <= stats.subsequences
     print(f"{name}: {bits} bits: {stats.subsequences} subsequences in {stats.intervals} intervals, {stats.rounds} rounds, recomputed {list(stats.recomputed)[:stats.rounds]}")
+
+
+@pytest.fixture(scope="module")
+def periodic():
+    """decode_cases.periodic_case(513, 512): (file, coefficients), 262 656 grey blocks"""
+    data, want = dc.periodic_case(513, 512)
+    want.setflags(write=False)
+    return data, want
+
+
+@pytest.mark.gpu
+def test_decode_across_257_scan_tiles(lib, periodic):
+    """4104 x 4096 grey, one 22-byte period 65 664 times: the 262 656 DC differences are 257 tiles of the scan in front of
+    k_decode_dc, so k_scan_tiles goes round its carry loop twice, and the sums of difference + 32768 pass 2^32; at 32 bits the
+    subsequences (more than the blocks: a block is 44 bits) are more than 256 tiles too, for the scan of done[]"""
+    import jpeg2png_amd as j
+    data, want = periodic
+    assert want.shape[0] * want.shape[1] == 262656 > 256 * 1024 and 262656 * 32768 > 1 << 32
+    got, stats = j.entropy_decode(data, stats=True)
+    check("periodic", got, [want])
+    assert stats["intervals"] == 1 and 1 <= stats["rounds"] <= stats["subsequences"]
+    got, stats = j.entropy_decode(data, subsequence_bits=32, stats=True)
+    check("periodic at 32 bits", got, [want])
+    assert stats["subsequences"] > 256 * 1024 and stats["subsequences"] >= stats["data_bytes"] * 8 // 32
+    assert stats["data_bytes"] == 262656 // 4 * len(dc.periodic_period()[1])
+    assert 1 <= stats["rounds"] <= stats["subsequences"]
+    print(f"periodic 513x512 blocks: 32 bits: {stats['subsequences']} subsequences, {stats['rounds']} rounds, recomputed {stats['recomputed']}")
+
+
+@pytest.mark.gpu
+def test_encode_across_257_scan_tiles(lib, periodic):
+    """the same coefficients through the device's coder: 257 tiles of len[] for its scan, and the file byte for byte"""
+    import jpeg2png_amd as j
+    data, want = periodic
+    got = j.entropy_encode([want], 4104, 4096, ec.quant_tables(75, 1))
+    assert len(got) == len(data)
+    if got != data:
+        a, b = np.frombuffer(got, np.uint8), np.frombuffer(data, np.uint8)
+        bad = np.flatnonzero(a != b)
+        raise AssertionError(f"{len(bad)} of {len(data)} bytes differ, the first at {bad[0]}: {a[bad[0]]:02x} for {b[bad[0]]:02x}")
 
 
 @pytest.mark.gpu
