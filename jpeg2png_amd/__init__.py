@@ -8,6 +8,8 @@ plain-C shim plus a C `compute()` with the reference's own signature.
 There is NO CPU fallback: if the shared library is missing or no GPU is present the
 calls raise.
 """
+import collections
+import contextlib
 import ctypes
 import os
 
@@ -592,10 +594,9 @@ def _c_tensor(t, nplane, width, height, layout, scale, bias, device=None):
     return _CTensor(t.data_ptr(), code, sc, sy, sx, (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias))
 
 
-def _c_resize(width, height, out_width, out_height, box):
-    """the j2p_resize of the keywords out_width / out_height / box of Solver.to_tensor and Batch.submit for a width x height
-    image: box (x, y, w, h) defaults to the whole image, a missing output size to the box's (a pure crop).  Refuses what the
-    library refuses (j2p_resize_error), before anything is allocated."""
+def _c_box(width, height, out_width, out_height, box):
+    """(x, y, w, h, out_w, out_h) of the keywords out_width / out_height / box of Solver.to_tensor and Batch.submit for a width x
+    height image: box (x, y, w, h) defaults to the whole image, a missing output size to the box's (a pure crop)"""
     if width is None or height is None or int(width) < 1 or int(height) < 1:
         raise J2PError("tensor output needs width and height")
     try:
@@ -609,6 +610,13 @@ def _c_resize(width, height, out_width, out_height, box):
     ow, oh = bw if out_width is None else int(out_width), bh if out_height is None else int(out_height)
     if ow < 1 or oh < 1:
         raise J2PError("resize: empty output")
+    return bx, by, bw, bh, ow, oh
+
+
+def _c_resize(width, height, out_width, out_height, box):
+    """the j2p_resize of those keywords: the area form, never larger than the box.  Refuses what the library refuses
+    (j2p_resize_error), before anything is allocated."""
+    bx, by, bw, bh, ow, oh = _c_box(width, height, out_width, out_height, box)
     if ow > bw or oh > bh:
         raise J2PError(f"resize: the output {ow} x {oh} is larger than the box {bw} x {bh} (enlarging is what zooming is for)")
     return _CResize(bx, by, bw, bh, ow, oh)
@@ -629,24 +637,40 @@ def _filter_code(filter):
 
 
 def _c_resample(width, height, out_width, out_height, box, code):
-    """the j2p_resample of the same keywords with filter="triangle" / "cubic": as _c_resize, but the output may be larger than
-    the box (up to J2P_RESAMPLE_MAX_OUT a side).  Refuses what the library refuses (j2p_resample_error)."""
-    if width is None or height is None or int(width) < 1 or int(height) < 1:
-        raise J2PError("tensor output needs width and height")
-    try:
-        bx, by, bw, bh = (0, 0, int(width), int(height)) if box is None else (int(v) for v in box)
-    except (TypeError, ValueError):
-        raise J2PError("resize: box must be (x, y, width, height)") from None
-    if bw < 1 or bh < 1:
-        raise J2PError("resize: empty box")
-    if bx < 0 or by < 0 or bx + bw > int(width) or by + bh > int(height):
-        raise J2PError(f"resize: the box {(bx, by, bw, bh)} leaves the {int(width)} x {int(height)} image")
-    ow, oh = bw if out_width is None else int(out_width), bh if out_height is None else int(out_height)
-    if ow < 1 or oh < 1:
-        raise J2PError("resize: empty output")
+    """the j2p_resample of the same keywords with filter="triangle" / "cubic": the output may be larger than the box (up to
+    J2P_RESAMPLE_MAX_OUT a side).  Refuses what the library refuses (j2p_resample_error)."""
+    bx, by, bw, bh, ow, oh = _c_box(width, height, out_width, out_height, box)
     if ow > J2P_RESAMPLE_MAX_OUT or oh > J2P_RESAMPLE_MAX_OUT:
         raise J2PError(f"resize: the output {ow} x {oh} is larger than {J2P_RESAMPLE_MAX_OUT} a side")
     return _CResample(bx, by, bw, bh, ow, oh, code)
+
+
+def _resize_spec(width, height, out_width, out_height, box, filter):
+    """what the keywords out_width / out_height / box / filter of Solver.to_tensor and Batch.submit ask for: None (none of them is
+    given), the j2p_resize of the area form (filter None or "area") or the j2p_resample of a filter"""
+    code = _filter_code(filter)
+    if code is not None:
+        return _c_resample(width, height, out_width, out_height, box, code)
+    if out_width is not None or out_height is not None or box is not None:
+        return _c_resize(width, height, out_width, out_height, box)
+    return None
+
+
+def _tensor_to_fill(torch, out, dtype, layout, nplane, width, height, device):
+    """the tensor Solver.to_tensor / to_tensors write into: the caller's `out` (whose dtype must be `dtype` where that is given), or
+    a new one of `dtype` (default float32) in that layout on the device"""
+    if out is not None:
+        if dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
+            raise J2PError(f"tensor output: out is {out.dtype}, dtype says {dtype}")
+        return out
+    dtype = torch.float32 if dtype is None else dtype
+    _tensor_dtype(torch, dtype)
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("tensor output needs width and height")
+    if layout not in ("chw", "hwc"):
+        raise J2PError(f"tensor output: layout must be 'chw' or 'hwc', not {layout!r}")
+    shape = (nplane, int(height), int(width)) if layout == "chw" else (int(height), int(width), nplane)
+    return torch.empty(shape, dtype=dtype, device=torch.device("cuda", device))
 
 
 _OUTPUT_KEYS = {"out_width", "out_height", "box", "filter", "dtype", "layout", "scale", "bias"}
@@ -1103,46 +1127,38 @@ class Solver:
         out_width / out_height may also be LARGER than the box.
         Nothing waits on the host: the kernel is queued on the solver's stream and torch's current stream is made to wait
         for it, so torch operations issued afterwards see the finished tensor."""
-        resize = None
-        code = _filter_code(filter)
-        if code is not None:
-            resize = _c_resample(width, height, out_width, out_height, box, code)
-        elif out_width is not None or out_height is not None or box is not None:
-            resize = _c_resize(width, height, out_width, out_height, box)
+        resize = _resize_spec(width, height, out_width, out_height, box, filter)
         torch = _torch()
         if self.nch not in (1, 3):
             raise J2PError("tensor output needs a solver of three channels (RGB) or one (greyscale)")
-        dev = torch.device("cuda", self.device)
-        image_width, image_height = width, height
-        if resize is not None:
-            width, height = resize.out_w, resize.out_h        # the tensor's
-        if out is None:
-            dtype = torch.float32 if dtype is None else dtype
-            _tensor_dtype(torch, dtype)
-            if width is None or height is None or int(width) < 1 or int(height) < 1:
-                raise J2PError("tensor output needs width and height")
-            shape = (self.nch, int(height), int(width)) if layout == "chw" else (int(height), int(width), self.nch)
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        elif dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
-            raise J2PError(f"tensor output: out is {out.dtype}, dtype says {dtype}")
-        ct = _c_tensor(out, self.nch, width, height, layout, scale, bias, device=self.device)
+        tw, th = (width, height) if resize is None else (resize.out_w, resize.out_h)        # the tensor's
+        out = _tensor_to_fill(torch, out, dtype, layout, self.nch, tw, th, self.device)
+        ct = _c_tensor(out, self.nch, tw, th, layout, scale, bias, device=self.device)
         refs = (_CPlaneRef * self.nch)(*[_CPlaneRef(self._h, c) for c in range(self.nch)])
+        with self._filling(torch, [out]):
+            if isinstance(resize, _CResample):
+                _check(self._lib.j2p_planes_to_tensor_resampled(refs, self.nch, int(width), int(height), ctypes.byref(resize), ctypes.byref(ct)))
+            elif resize is not None:
+                _check(self._lib.j2p_planes_to_tensor_resized(refs, self.nch, int(width), int(height), ctypes.byref(resize), ctypes.byref(ct)))
+            else:
+                _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
+        return out
+
+    @contextlib.contextmanager
+    def _filling(self, torch, tensors):
+        """the stream hand-off of to_tensor / to_tensors, around the call that queues the kernels which fill `tensors`"""
+        dev = torch.device("cuda", self.device)
         ours = torch.cuda.ExternalStream(self.stream(), device=dev)
         theirs = torch.cuda.current_stream(dev)
-        ours.wait_stream(theirs)            # whatever torch still does with `out` (its allocation, a fill) comes first
-        if code is not None:
-            _check(self._lib.j2p_planes_to_tensor_resampled(refs, self.nch, int(image_width), int(image_height), ctypes.byref(resize), ctypes.byref(ct)))
-        elif resize is not None:
-            _check(self._lib.j2p_planes_to_tensor_resized(refs, self.nch, int(image_width), int(image_height), ctypes.byref(resize), ctypes.byref(ct)))
-        else:
-            _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
+        ours.wait_stream(theirs)            # whatever torch still does with the tensors (their allocation, a fill) comes first
+        yield
         theirs.wait_stream(ours)
-        # `out` is now in use on torch's current stream, behind the kernel: an allocator that owns it for another stream must
-        # not hand it out again before that.  (Recorded for THEIR stream, never for ours: the allocator records an event on
-        # every recorded stream when the tensor is freed, and the solver's stream is destroyed with the solver — which a
-        # tensor may well outlive.)
-        out.record_stream(theirs)
-        return out
+        # The tensors are now in use on torch's current stream, behind the kernels: an allocator that owns them for another stream
+        # must not hand them out again before that.  (Recorded for THEIR stream, never for ours: the allocator records an event on
+        # every recorded stream when a tensor is freed, and the solver's stream is destroyed with the solver — which a tensor may
+        # well outlive.)
+        for t in tensors:
+            t.record_stream(theirs)
 
     def to_tensors(self, width, height, outputs):
         """Several resampled views of the solved width x height image from ONE call (j2p_planes_to_tensors_resampled): the crops
@@ -1156,29 +1172,16 @@ class Solver:
         torch = _torch()
         if self.nch not in (1, 3):
             raise J2PError("tensor output needs a solver of three channels (RGB) or one (greyscale)")
-        dev = torch.device("cuda", self.device)
         tensors, items = [], (_COutput * n)()
         for i, (o, r) in enumerate(zip(outputs, specs)):
-            out, dtype, layout = o.get("out"), o.get("dtype"), o.get("layout", "chw")
-            if out is None:
-                dtype = torch.float32 if dtype is None else dtype
-                _tensor_dtype(torch, dtype)
-                if layout not in ("chw", "hwc"):
-                    raise J2PError(f"tensor output: layout must be 'chw' or 'hwc', not {layout!r}")
-                out = torch.empty((self.nch, r.out_h, r.out_w) if layout == "chw" else (r.out_h, r.out_w, self.nch), dtype=dtype, device=dev)
-            elif dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
-                raise J2PError(f"tensor output: out is {out.dtype}, dtype says {dtype}")
+            layout = o.get("layout", "chw")
+            out = _tensor_to_fill(torch, o.get("out"), o.get("dtype"), layout, self.nch, r.out_w, r.out_h, self.device)
             items[i].r = r
             items[i].t = _c_tensor(out, self.nch, r.out_w, r.out_h, layout, o.get("scale"), o.get("bias"), device=self.device)
             tensors.append(out)
         refs = (_CPlaneRef * self.nch)(*[_CPlaneRef(self._h, c) for c in range(self.nch)])
-        ours = torch.cuda.ExternalStream(self.stream(), device=dev)
-        theirs = torch.cuda.current_stream(dev)
-        ours.wait_stream(theirs)            # whatever torch still does with the tensors (their allocation, a fill) comes first
-        _check(self._lib.j2p_planes_to_tensors_resampled(refs, self.nch, int(width), int(height), n, items))
-        theirs.wait_stream(ours)
-        for t in tensors:
-            t.record_stream(theirs)         # (for THEIR stream, never for ours: see to_tensor)
+        with self._filling(torch, tensors):
+            _check(self._lib.j2p_planes_to_tensors_resampled(refs, self.nch, int(width), int(height), n, items))
         return tensors
 
     def download_gradient(self, c):
@@ -1400,6 +1403,237 @@ class _JpegResult:
         self.buffer, self.size = buffer, size
 
 
+# ---- a job of a Batch: Batch.submit resolves the input (1) and the output (2) its keywords ask for, fills the _CJob (3) and calls the
+# C entry point of that (input kind, output kind) pair (4) ----
+
+# the keywords of Batch.submit that decide a job's output form; resized: one of out_width / out_height / box / filter is given
+_Wanted = collections.namedtuple("_Wanted", "separate tile bits out quant_tables subsampling tensor layout scale bias out_width out_height box filter outputs "
+                                            "jpeg resized")
+
+
+def _torch_has_finished(device):
+    """The workers' streams know nothing of torch's: what torch has queued on its current stream of that device for memory a job
+    reads or writes (a fill, the work of the memory's previous owner) has to be over before the job is queued."""
+    _torch().cuda.current_stream(device).synchronize()
+
+
+def _job_input(planes, width, height, samples, file, tile, resized):
+    """step 1 -> (input kind: "planes", "samples" or "file"; the planes; the image's width and height; the C entry point's arguments
+    for that input; what they point into).  resized: a tensor with out_width / out_height / box / filter is asked for."""
+    if file is not None:
+        if samples is not None or tile:
+            raise J2PError("job: file= excludes samples= and tile")
+        if resized:
+            raise J2PError("job: with file= a resized tensor is an output of outputs=")
+        address, size, held = _file_bytes(file)
+        head = jpeg_parse(file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file)
+        if planes is None:
+            planes = [Plane(k["w"], k["h"], k["w_samp"], k["h_samp"], None, k["quant_table"]) for k in head["components"]]
+        if any(p.data is not None or p.fdata is not None for p in planes):
+            raise J2PError("job: with file= the planes carry neither data nor fdata")
+        width = head["width"] if width is None else width
+        height = head["height"] if height is None else height
+        if hasattr(file, "data_ptr") and file.is_cuda:
+            _torch_has_finished(file.device)
+        return "file", planes, width, height, (address, size), [held]
+    if samples is not None:
+        if tile:
+            raise J2PError("job: samples= excludes tile")
+        if resized:
+            raise J2PError("job: with samples= a resized tensor is an output of outputs=")
+        if len(samples) != len(planes):
+            raise J2PError(f"job: {len(samples)} sample arrays for {len(planes)} planes")
+        if any(p.data is not None or p.fdata is not None for p in planes):
+            raise J2PError("job: with samples= the planes carry neither data nor fdata")
+        csm, held, on_gpu = _c_samples(samples)
+        if on_gpu:
+            _torch_has_finished(on_gpu[0].device)
+        return "samples", planes, width, height, (csm,), [held]
+    return "planes", planes, width, height, (), []
+
+
+def _job_output(job, want, planes, width, height):
+    """step 2 -> (output kind: "own" (the job's own fields: float planes, samples, coefficients or a tensor's rows), "resized",
+    "resampled", "outputs" or "jpeg"; what wait() hands back; what must stay alive until then; the C entry point's arguments for
+    that output).  Refuses the keywords that no form takes together; the form's function refuses the rest and fills its fields of
+    the job."""
+    n, filled = len(planes), None
+    if want.jpeg is not None:
+        if want.bits or want.quant_tables is not None or want.subsampling is not None or want.tensor is not None or want.outputs is not None or \
+                want.tile or want.out is not None:
+            raise J2PError("job: jpeg= excludes bits, quant_tables, subsampling, tensor=, outputs=, out and tile")
+        filled = ("jpeg",) + _fill_jpeg(job, want.jpeg, n, width, height)
+    if want.outputs is not None:
+        if want.tensor is not None or want.bits or want.quant_tables is not None or want.subsampling is not None or want.tile:
+            raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
+        if want.out is not None or want.resized or want.layout != "chw" or want.scale is not None or want.bias is not None:
+            raise J2PError("job: with outputs= every output carries its own keywords (out_width, out_height, box, filter, layout, scale, bias)")
+        filled = ("outputs",) + _fill_outputs(job, want.outputs, n, width, height)
+    if want.tensor is None and _filter_code(want.filter) is not None:
+        raise J2PError("job: filter belongs to tensor output (tensor=)")
+    if want.tensor is None and (want.out_width is not None or want.out_height is not None or want.box is not None):
+        raise J2PError("job: out_width, out_height and box belong to tensor output (tensor=)")
+    if want.outputs is not None:
+        return filled
+    if want.tensor is not None:
+        resize = _resize_spec(width, height, want.out_width, want.out_height, want.box, want.filter)
+        kind = "own" if resize is None else "resampled" if isinstance(resize, _CResample) else "resized"
+        return (kind,) + _fill_tensor(job, want, resize, n, width, height)
+    if want.layout != "chw" or want.scale is not None or want.bias is not None:
+        raise J2PError("job: layout, scale and bias belong to tensor output (tensor=)")
+    if want.jpeg is not None:
+        return filled
+    if want.quant_tables is not None:
+        return ("own",) + _fill_coefficients(job, want, n, width, height)
+    if want.subsampling is not None:
+        raise J2PError("job: subsampling needs coefficient output (quant_tables)")
+    return ("own",) + (_fill_samples(job, want, n, width, height) if want.bits else _fill_planes(job, planes, want.separate))
+
+
+# The output forms: each refuses what is wrong with its own keywords, fills its fields of the job and returns (what wait() hands
+# back, what must stay alive until then, the C entry point's arguments for that output).
+
+def _fill_jpeg(job, jpeg, n, width, height):
+    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity"}:
+        raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
+    if n not in (1, 3):
+        raise J2PError("jpeg: three components or one")
+    cjpeg, held = _c_jpeg(width, height, n, jpeg.get("quality"), jpeg.get("quant_tables"), jpeg.get("subsampling", (1, 1)))
+    sx, sy = (cjpeg.sub_w, cjpeg.sub_h) if n == 3 else (1, 1)
+    room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
+    buffer, size = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
+    job.out_w, job.out_h = int(width), int(height)
+    return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size))
+
+
+def _fill_outputs(job, outputs, n, width, height):
+    specs = [_output_spec(width, height, o, "tensor") for o in outputs[:_output_count(outputs)]]
+    if any(o.get("tensor") is None for o in outputs):
+        raise J2PError("job: every output of outputs= needs its tensor=")
+    items = (_COutput * len(specs))()
+    for i, (o, r) in enumerate(zip(outputs, specs)):
+        t = o["tensor"]
+        if o.get("dtype") is not None and getattr(t, "dtype", None) != o["dtype"]:
+            raise J2PError(f"tensor output: tensor is {getattr(t, 'dtype', None)}, dtype says {o['dtype']}")
+        items[i].r = r
+        items[i].t = _c_tensor(t, n, r.out_w, r.out_h, o.get("layout", "chw"), o.get("scale"), o.get("bias"))
+    if len({o["tensor"].device for o in outputs}) != 1:
+        raise J2PError("job: the tensors of outputs= must live on one GPU")
+    job.out_w, job.out_h = int(width), int(height)
+    _torch_has_finished(outputs[0]["tensor"].device)
+    return [o["tensor"] for o in outputs], [], (len(items), items)
+
+
+def _fill_tensor(job, want, resize, n, width, height):
+    if want.quant_tables is not None or want.subsampling is not None:
+        raise J2PError("job: tensor output and coefficient output (quant_tables) exclude each other")
+    if want.bits:
+        raise J2PError("job: tensor output needs bits = 0")
+    if want.out is not None:
+        raise J2PError("job: tensor output is written into `tensor`; out is for host arrays")
+    tw, th = (width, height) if resize is None else (resize.out_w, resize.out_h)        # the tensor's
+    job.out_tensor = _c_tensor(want.tensor, n, tw, th, want.layout, want.scale, want.bias)
+    job.out_w, job.out_h = int(width), int(height)
+    _torch_has_finished(want.tensor.device)
+    return want.tensor, [], () if resize is None else (ctypes.byref(resize),)
+
+
+def _fill_coefficients(job, want, n, width, height):
+    out = want.out
+    if want.bits:
+        raise J2PError("job: coefficient output (quant_tables) needs bits = 0")
+    if len(want.quant_tables) != n:
+        raise J2PError("job: one quantisation table per plane")
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("job: coefficient output needs width and height")
+    bw, bh = (int(width) + 7) // 8, (int(height) + 7) // 8
+    subs = [(1, 1)] * n if want.subsampling is None else [_sampling(v) for v in want.subsampling]
+    if len(subs) != n:
+        raise J2PError("job: one (sx, sy) pair per plane")
+    grids = [(-(-bh // sy), -(-bw // sx), 64) for sx, sy in subs]
+    tables = [np.ascontiguousarray(q, dtype=np.uint16).reshape(-1) for q in want.quant_tables]
+    if any(q.size != 64 for q in tables):
+        raise J2PError("job: a quantisation table has 64 entries")
+    if out is None:
+        out = [np.empty(g, dtype=np.int16) for g in grids]
+    if not (isinstance(out, (list, tuple)) and len(out) == n and all(
+            isinstance(a, np.ndarray) and a.shape == g and a.dtype == np.int16 and a.flags["C_CONTIGUOUS"]
+            and a.flags["WRITEABLE"] for a, g in zip(out, grids))):
+        raise J2PError(f"out must be a list of {n} writeable C-contiguous int16 arrays of shapes {grids}")
+    for c in range(n):
+        job.out_quant[c] = tables[c].ctypes.data
+        job.out_coef[c] = out[c].ctypes.data
+        job.out_sub_w[c], job.out_sub_h[c] = subs[c]
+    job.out_blocks_w, job.out_blocks_h = bw, bh
+    return out, [tables], ()
+
+
+def _fill_samples(job, want, n, width, height):
+    """(out: a caller's own RGB array, reused between jobs — nothing is then mapped or faulted in while other jobs' kernels run,
+    which costs those a stalled launch each time)"""
+    bits, out = want.bits, want.out
+    # (the C side writes height * width * 3 samples of bits / 8 bytes: anything else is a heap overflow or a half-written array,
+    # so it is an error here, not an assert that -O strips)
+    if bits not in (8, 16):
+        raise J2PError("job: out_bits must be 0, 8 or 16")
+    if n == 2:
+        raise J2PError("job: sample output needs three planes (RGB) or one (greyscale)")
+    shape = (height, width) if n == 1 else (height, width, 3)           # one plane: greyscale, one sample per pixel
+    if out is None:
+        out = np.empty(shape, dtype=np.uint8 if bits == 8 else ">u2")
+    if not (isinstance(out, np.ndarray) and out.shape == shape and out.flags["C_CONTIGUOUS"]
+            and out.flags["WRITEABLE"] and out.dtype.itemsize == bits // 8 and out.dtype.kind in "ui"):
+        raise J2PError(f"out must be a writeable C-contiguous {shape} array of "
+                                   f"{bits // 8}-byte integers for bits = {bits}")
+    job.out_bits, job.out_w, job.out_h = bits, width, height
+    job.out_rgb = out.ctypes.data
+    return out, [], ()
+
+
+def _fill_planes(job, planes, separate):
+    """the float planes: the canvas of a compute() call (compute.c:410-416) — all components' for a joint solve, its own for each of
+    the separate calls of `-s` (jpeg2png.c:147-152)"""
+    W = max(p.w * p.w_samp for p in planes)
+    H = max(p.h * p.h_samp for p in planes)
+    out = [np.empty((p.h * p.h_samp, p.w * p.w_samp) if separate else (H, W), dtype=np.float32) for p in planes]
+    for c, a in enumerate(out):
+        job.out_planes[c] = a.ctypes.data
+    return out, [], ()
+
+
+def _job_record(job, planes, weight, pweight, iterations, want, tile_devices, tile_min_band_pixels):
+    """step 3: everything of the _CJob but its output form -> what it points into"""
+    n = len(planes)
+    job.nchannel = n
+    job.tile = 1 if want.tile else 0
+    if tile_devices:
+        job.tile_first, job.tile_count = int(tile_devices[0]), int(tile_devices[1])
+    if tile_min_band_pixels is not None:           # 0 = no gate at all (tests with small images)
+        job.tile_min_band_pixels = int(tile_min_band_pixels) if tile_min_band_pixels else ctypes.c_size_t(-1).value
+    cpl, keep = _c_planes(planes)
+    for c in range(n):
+        job.planes[c] = cpl[c]
+    job.separate = 1 if want.separate else 0
+    ws = list(weight) if isinstance(weight, (list, tuple)) else [weight] * n
+    its = list(iterations) if isinstance(iterations, (list, tuple)) else [iterations] * n
+    for c in range(n):
+        job.weight[c], job.pweight[c], job.iterations[c] = float(ws[c]), float(pweight[c]), int(its[c])
+    return keep
+
+
+def _entry_point(source, source_args, kind, output_args):
+    """step 4 -> (the C entry point of an (input kind, output kind) pair, its arguments between the job and the ticket)"""
+    if kind == "jpeg":
+        if source == "file":
+            return "j2p_batch_submit_file_jpeg", source_args + output_args
+        return "j2p_batch_submit_jpeg", (source_args or (None,)) + output_args          # (samples NULL: the planes' coefficients)
+    if source != "planes":
+        # (step 1 has refused the resized kinds; no outputs: the job's own form)
+        return "j2p_batch_submit_" + source, source_args + (output_args or (0, None))
+    return {"own": "j2p_batch_submit", "resized": "j2p_batch_submit_resized", "resampled": "j2p_batch_submit_resampled",
+            "outputs": "j2p_batch_submit_outputs"}[kind], output_args
+
+
 class Batch:
     """Images in flight over slots_per_device worker threads per GPU (include/jpeg2png_amd.h: j2p_batch_*).
     submit() returns a ticket; wait(ticket) returns the job's output: RGB samples [h, w, 3] (bits 8 / 16), greyscale
@@ -1458,208 +1692,21 @@ class Batch:
         tile=True: the image is row-tiled over the batch's devices instead of solved on one of them;
         tile_devices=(first, count): over that slice of the batch's device list only; on_progress(n): called from the worker
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
-        cfile = None
-        if file is not None:
-            if samples is not None or tile:
-                raise J2PError("job: file= excludes samples= and tile")
-            if filter is not None or out_width is not None or out_height is not None or box is not None:
-                raise J2PError("job: with file= a resized tensor is an output of outputs=")
-            cfile = _file_bytes(file)
-            head = jpeg_parse(file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file)
-            if planes is None:
-                planes = [Plane(k["w"], k["h"], k["w_samp"], k["h_samp"], None, k["quant_table"]) for k in head["components"]]
-            if any(p.data is not None or p.fdata is not None for p in planes):
-                raise J2PError("job: with file= the planes carry neither data nor fdata")
-            width = head["width"] if width is None else width
-            height = head["height"] if height is None else height
-            if hasattr(file, "data_ptr") and file.is_cuda:
-                # (the workers' streams know nothing of torch's: see tensor= below)
-                _torch().cuda.current_stream(file.device).synchronize()
-        n = len(planes)
-        resize = None
-        items = None
-        csm = None
-        if samples is not None:
-            if tile:
-                raise J2PError("job: samples= excludes tile")
-            if filter is not None or out_width is not None or out_height is not None or box is not None:
-                raise J2PError("job: with samples= a resized tensor is an output of outputs=")
-            if len(samples) != n:
-                raise J2PError(f"job: {len(samples)} sample arrays for {n} planes")
-            if any(p.data is not None or p.fdata is not None for p in planes):
-                raise J2PError("job: with samples= the planes carry neither data nor fdata")
-            csm, held, on_gpu = _c_samples(samples)
-            if on_gpu:
-                # (the workers' streams know nothing of torch's: see tensor= below)
-                _torch().cuda.current_stream(on_gpu[0].device).synchronize()
-        cjpeg = None
-        if jpeg is not None:
-            if bits or quant_tables is not None or subsampling is not None or tensor is not None or outputs is not None or tile or out is not None:
-                raise J2PError("job: jpeg= excludes bits, quant_tables, subsampling, tensor=, outputs=, out and tile")
-            if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity"}:
-                raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
-            if n not in (1, 3):
-                raise J2PError("jpeg: three components or one")
-            cjpeg, jpeg_held = _c_jpeg(width, height, n, jpeg.get("quality"), jpeg.get("quant_tables"), jpeg.get("subsampling", (1, 1)))
-            sx, sy = (cjpeg.sub_w, cjpeg.sub_h) if n == 3 else (1, 1)
-            room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
-            jpeg_out = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8)
-            jpeg_size = ctypes.c_size_t(0)
-        if outputs is not None:
-            if tensor is not None or bits or quant_tables is not None or subsampling is not None or tile:
-                raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
-            if out is not None or filter is not None or out_width is not None or out_height is not None or box is not None or \
-                    layout != "chw" or scale is not None or bias is not None:
-                raise J2PError("job: with outputs= every output carries its own keywords (out_width, out_height, box, filter, layout, scale, bias)")
-            specs = [_output_spec(width, height, o, "tensor") for o in outputs[:_output_count(outputs)]]
-            if any(o.get("tensor") is None for o in outputs):
-                raise J2PError("job: every output of outputs= needs its tensor=")
-            items = (_COutput * len(specs))()
-            for i, (o, r) in enumerate(zip(outputs, specs)):
-                t = o["tensor"]
-                if o.get("dtype") is not None and getattr(t, "dtype", None) != o["dtype"]:
-                    raise J2PError(f"tensor output: tensor is {getattr(t, 'dtype', None)}, dtype says {o['dtype']}")
-                items[i].r = r
-                items[i].t = _c_tensor(t, n, r.out_w, r.out_h, o.get("layout", "chw"), o.get("scale"), o.get("bias"))
-            if len({o["tensor"].device for o in outputs}) != 1:
-                raise J2PError("job: the tensors of outputs= must live on one GPU")
-        code = _filter_code(filter)
-        if code is not None:
-            if tensor is None:
-                raise J2PError("job: filter belongs to tensor output (tensor=)")
-            resize = _c_resample(width, height, out_width, out_height, box, code)
-        elif out_width is not None or out_height is not None or box is not None:
-            if tensor is None:
-                raise J2PError("job: out_width, out_height and box belong to tensor output (tensor=)")
-            resize = _c_resize(width, height, out_width, out_height, box)
+        resized = filter is not None or out_width is not None or out_height is not None or box is not None
+        want = _Wanted(separate, tile, bits, out, quant_tables, subsampling, tensor, layout, scale, bias, out_width, out_height, box, filter, outputs,
+                       jpeg, resized)
+        source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized)
         job = _CJob()
-        job.nchannel = n
-        job.tile = 1 if tile else 0
-        if tile_devices:
-            job.tile_first, job.tile_count = int(tile_devices[0]), int(tile_devices[1])
-        if tile_min_band_pixels is not None:           # 0 = no gate at all (tests with small images)
-            job.tile_min_band_pixels = int(tile_min_band_pixels) if tile_min_band_pixels else ctypes.c_size_t(-1).value
-        cpl, keep = _c_planes(planes)
-        for c in range(n):
-            job.planes[c] = cpl[c]
-        job.separate = 1 if separate else 0
-        ws = list(weight) if isinstance(weight, (list, tuple)) else [weight] * n
-        its = list(iterations) if isinstance(iterations, (list, tuple)) else [iterations] * n
-        for c in range(n):
-            job.weight[c], job.pweight[c], job.iterations[c] = float(ws[c]), float(pweight[c]), int(its[c])
-        # canvas of a compute() call (compute.c:410-416): all components' for a joint solve, its own for each of the
-        # separate calls of `-s` (jpeg2png.c:147-152)
-        W = max(p.w * p.w_samp for p in planes)
-        H = max(p.h * p.h_samp for p in planes)
-        shapes = [(p.h * p.h_samp, p.w * p.w_samp) if separate else (H, W) for p in planes]
-        if items is not None:
-            job.out_w, job.out_h = int(width), int(height)
-            # (the workers' streams know nothing of torch's: see tensor= below)
-            _torch().cuda.current_stream(outputs[0]["tensor"].device).synchronize()
-            out = [o["tensor"] for o in outputs]
-        elif tensor is not None:
-            if quant_tables is not None or subsampling is not None:
-                raise J2PError("job: tensor output and coefficient output (quant_tables) exclude each other")
-            if bits:
-                raise J2PError("job: tensor output needs bits = 0")
-            if out is not None:
-                raise J2PError("job: tensor output is written into `tensor`; out is for host arrays")
-            if resize is not None:
-                job.out_tensor = _c_tensor(tensor, n, resize.out_w, resize.out_h, layout, scale, bias)
-            else:
-                job.out_tensor = _c_tensor(tensor, n, width, height, layout, scale, bias)
-            job.out_w, job.out_h = int(width), int(height)
-            # the workers' streams know nothing of torch's: what it has queued for this memory (a fill, the work of the
-            # memory's previous owner) has to be over before a worker writes
-            _torch().cuda.current_stream(tensor.device).synchronize()
-            out = tensor
-        elif layout != "chw" or scale is not None or bias is not None:
-            raise J2PError("job: layout, scale and bias belong to tensor output (tensor=)")
-        elif cjpeg is not None:
-            job.out_w, job.out_h = int(width), int(height)
-            out = _JpegResult(jpeg_out, jpeg_size)
-            keep = (keep, jpeg_held)
-        elif quant_tables is not None:
-            if bits:
-                raise J2PError("job: coefficient output (quant_tables) needs bits = 0")
-            if len(quant_tables) != n:
-                raise J2PError("job: one quantisation table per plane")
-            if width is None or height is None or int(width) < 1 or int(height) < 1:
-                raise J2PError("job: coefficient output needs width and height")
-            bw, bh = (int(width) + 7) // 8, (int(height) + 7) // 8
-            subs = [(1, 1)] * n if subsampling is None else [_sampling(v) for v in subsampling]
-            if len(subs) != n:
-                raise J2PError("job: one (sx, sy) pair per plane")
-            grids = [(-(-bh // sy), -(-bw // sx), 64) for sx, sy in subs]
-            tables = [np.ascontiguousarray(q, dtype=np.uint16).reshape(-1) for q in quant_tables]
-            if any(q.size != 64 for q in tables):
-                raise J2PError("job: a quantisation table has 64 entries")
-            if out is None:
-                out = [np.empty(g, dtype=np.int16) for g in grids]
-            if not (isinstance(out, (list, tuple)) and len(out) == n and all(
-                    isinstance(a, np.ndarray) and a.shape == g and a.dtype == np.int16 and a.flags["C_CONTIGUOUS"]
-                    and a.flags["WRITEABLE"] for a, g in zip(out, grids))):
-                raise J2PError(f"out must be a list of {n} writeable C-contiguous int16 arrays of shapes {grids}")
-            for c in range(n):
-                job.out_quant[c] = tables[c].ctypes.data
-                job.out_coef[c] = out[c].ctypes.data
-                job.out_sub_w[c], job.out_sub_h[c] = subs[c]
-            job.out_blocks_w, job.out_blocks_h = bw, bh
-            keep = (keep, tables)
-        elif subsampling is not None:
-            raise J2PError("job: subsampling needs coefficient output (quant_tables)")
-        elif bits:
-            # (out: a caller's own RGB array, reused between jobs — nothing is then mapped or faulted in while other jobs'
-            # kernels run, which costs those a stalled launch each time, DESIGN.md section 5)
-            # (the C side writes height * width * 3 samples of bits / 8 bytes: anything else is a heap overflow or a
-            # half-written array, so it is an error here, not an assert that -O strips)
-            if bits not in (8, 16):
-                raise J2PError("job: out_bits must be 0, 8 or 16")
-            if n == 2:
-                raise J2PError("job: sample output needs three planes (RGB) or one (greyscale)")
-            # one plane: greyscale, one sample per pixel
-            shape = (height, width) if n == 1 else (height, width, 3)
-            if out is None:
-                out = np.empty(shape, dtype=np.uint8 if bits == 8 else ">u2")
-            if not (isinstance(out, np.ndarray) and out.shape == shape and out.flags["C_CONTIGUOUS"]
-                    and out.flags["WRITEABLE"] and out.dtype.itemsize == bits // 8 and out.dtype.kind in "ui"):
-                raise J2PError(f"out must be a writeable C-contiguous {shape} array of "
-                                           f"{bits // 8}-byte integers for bits = {bits}")
-            job.out_bits, job.out_w, job.out_h = bits, width, height
-            job.out_rgb = out.ctypes.data
-        else:
-            out = [np.empty(shapes[c], dtype=np.float32) for c in range(n)]
-            for c in range(n):
-                job.out_planes[c] = out[c].ctypes.data
+        kind, result, filled, output_args = _job_output(job, want, planes, width, height)
+        keep += filled + _job_record(job, planes, weight, pweight, iterations, want, tile_devices, tile_min_band_pixels)
         if on_progress is not None:
             cb = _PROGRESS_CB(lambda _user, n: on_progress(int(n)))
             job.on_progress = cb
-            keep = (keep, cb)                       # the trampoline lives as long as the job
+            keep.append(cb)                         # the trampoline lives as long as the job
+        name, args = _entry_point(source, source_args, kind, output_args)
         t = ctypes.c_int()
-        if csm is not None:
-            keep = (keep, held)
-        if cfile is not None:
-            keep = (keep, cfile[2])
-            if cjpeg is not None:
-                _check(self._lib.j2p_batch_submit_file_jpeg(self._h, ctypes.byref(job), cfile[0], cfile[1], ctypes.byref(cjpeg), jpeg_out.ctypes.data,
-                                                            jpeg_out.size, ctypes.byref(jpeg_size), ctypes.byref(t)))
-            else:
-                _check(self._lib.j2p_batch_submit_file(self._h, ctypes.byref(job), cfile[0], cfile[1], 0 if items is None else len(items), items,
-                                                       ctypes.byref(t)))
-        elif cjpeg is not None:
-            _check(self._lib.j2p_batch_submit_jpeg(self._h, ctypes.byref(job), csm, ctypes.byref(cjpeg), jpeg_out.ctypes.data, jpeg_out.size,
-                                                   ctypes.byref(jpeg_size), ctypes.byref(t)))
-        elif csm is not None:
-            _check(self._lib.j2p_batch_submit_samples(self._h, ctypes.byref(job), csm, 0 if items is None else len(items), items, ctypes.byref(t)))
-        elif items is not None:
-            _check(self._lib.j2p_batch_submit_outputs(self._h, ctypes.byref(job), len(items), items, ctypes.byref(t)))
-        elif code is not None:
-            _check(self._lib.j2p_batch_submit_resampled(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
-        elif resize is not None:
-            _check(self._lib.j2p_batch_submit_resized(self._h, ctypes.byref(job), ctypes.byref(resize), ctypes.byref(t)))
-        else:
-            _check(self._lib.j2p_batch_submit(self._h, ctypes.byref(job), ctypes.byref(t)))
-        self._pending[t.value] = (out, keep)
+        _check(getattr(self._lib, name)(self._h, ctypes.byref(job), *args, ctypes.byref(t)))
+        self._pending[t.value] = (result, keep)
         return t.value
 
     def wait(self, ticket):

@@ -18,6 +18,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <thread>
 #include <vector>
 #include <stdio.h>
@@ -30,28 +31,69 @@
 
 namespace {
 
-// where the file of a j2p_batch_submit_jpeg job goes; spec.quant[] point into tables[]
+// The optional parts of a job.  j2p_job may not grow, so they arrive next to it: every entry point fills in the ones it carries,
+// and classify() turns the job and its request into the one record, Job, that everything downstream reads.
+struct Request {
+        const j2p_resize *resize = nullptr;
+        const j2p_resample *resample = nullptr;
+        unsigned nout = 0;
+        const j2p_output *outs = nullptr;
+        const j2p_samples *samples = nullptr;
+        const uint8_t *file = nullptr;
+        size_t file_size = 0;
+        const j2p_jpeg *jpeg = nullptr;     // the file the job delivers, with where it goes:
+        uint8_t *jpeg_out = nullptr;
+        size_t jpeg_capacity = 0, *jpeg_size = nullptr;
+        Request &resized(const j2p_resize *r) { resize = r; return *this; }
+        Request &resampled(const j2p_resample *r) { resample = r; return *this; }
+        // (no outputs, or an array that is not there, is the job's own output)
+        Request &outputs(unsigned n, const j2p_output *o) { if(n && o) { nout = n, outs = o; } return *this; }
+        Request &from_samples(const j2p_samples *m) { samples = m; return *this; }
+        Request &from_file(const uint8_t *f, size_t size) { file = f, file_size = size; return *this; }
+        Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size)
+        {
+                jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size;
+                return *this;
+        }
+};
+
+// what a job's solvers are made from: planes[].data / fdata, Job::samples, or Job::file
+enum class In { planes, samples, file };
+// what becomes of the solve: the job's own out_* fields (samples, coefficients or out_tensor's rows, and out_planes), out_tensor
+// filled through Job::resize or Job::resample, Job::outputs, or Job::jpeg.  out_planes come down after every form without out_bits.
+enum class Out { own, resized, resampled, outputs, jpeg };
+
+// where the file of an Out::jpeg job goes; spec.quant[] point into tables[] (so a JpegOut stays where it was set)
 struct JpegOut {
-        bool on = false;
         j2p_jpeg spec = {0, 0, 0, 0, {nullptr, nullptr, nullptr}};
         uint16_t tables[3][64];
         uint8_t *out = nullptr;
         size_t capacity = 0, *size = nullptr;
+        // from a request that validate_jpeg has passed: the tables travel with the job
+        void set(const Request &q, unsigned nchannel)
+        {
+                spec = *q.jpeg;
+                out = q.jpeg_out, capacity = q.jpeg_capacity, size = q.jpeg_size;
+                for(unsigned c = 0; c < nchannel; c++) {
+                        memcpy(tables[c], q.jpeg->quant[c], sizeof(tables[c]));
+                        spec.quant[c] = tables[c];
+                }
+        }
 };
 
 struct Job {
-        j2p_job desc;
-        j2p_resize resize = {0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resized: the tensor receives the image resized
-        bool resized = false;
-        j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // j2p_batch_submit_resampled: ... resampled with a filter
-        bool resampled = false;
-        std::vector<j2p_output> outputs;    // j2p_batch_submit_outputs: these tensors are filled from the one solve, not out_tensor
-        std::vector<j2p_samples> samples;   // j2p_batch_submit_samples: [channel] the solvers are made from these, not from planes[].data
-        JpegOut jpeg;                       // j2p_batch_submit_jpeg: the job delivers the file
-        j2p_jpeg_file file;                 // j2p_batch_submit_file: opened at submit; the worker decodes the solvers' coefficients from
-                                            // the caller's bytes, which stay valid until j2p_batch_wait
+        j2p_job desc;                       // (of a file job: with the sizes it left zero filled in from the file)
+        In in = In::planes;
+        Out out = Out::own;
+        std::vector<j2p_samples> samples;   // In::samples: [channel]
+        j2p_jpeg_file file;                 // In::file: opened at submit; the worker decodes the solvers' coefficients from the caller's
+                                            // bytes, which stay valid until j2p_batch_wait
+        j2p_resize resize = {0, 0, 0, 0, 0, 0};          // Out::resized
+        j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // Out::resampled
+        std::vector<j2p_output> outputs;    // Out::outputs: never empty
+        JpegOut jpeg;                       // Out::jpeg
         int ticket = 0;
-        int device = -1;                    // tensor output, device samples: their device, the only one whose workers may take the job
+        int device = -1;                    // tensors, device samples, a file in device memory: their GPU, the only one whose workers may take the job
         int rc = J2P_OK;
         bool finished = false;
         char err[256] = "";
@@ -65,7 +107,7 @@ struct j2p_batch {
         std::vector<std::thread> workers;
         std::mutex lock;
         std::condition_variable work, finished;
-        std::deque<Job *> queue;
+        std::deque<Job *> queue;            // (the batch owns a job from here until j2p_batch_wait has collected it)
         std::map<int, Job *> jobs;          // every job not yet collected by j2p_batch_wait
         int next_ticket = 1;
         bool quit = false;
@@ -82,7 +124,17 @@ namespace {
 // j2p_job::out_sub_w / out_sub_h: 0 means 1, so that zero-initialised jobs are 4:4:4
 unsigned out_sub(unsigned v) { return v ? v : 1u; }
 
-// what both paths of a job check before they touch anything
+// what leaving the image on the device as tensors needs, whether in out_tensor or in outputs
+int validate_tensor_form(const j2p_job &d)
+{
+        if(d.nchannel != 1 && d.nchannel != 3) { return j2p_fail(J2P_EINVAL, "job: tensor output needs three channels (RGB) or one (greyscale)"); }
+        if(d.out_w == 0 || d.out_h == 0) { return j2p_fail(J2P_EINVAL, "job: tensor output needs out_w and out_h"); }
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: tensor output of a row-tiled job is not supported"); }
+        return J2P_OK;
+}
+
+// The job's own fields: what the worker checks before it touches anything — so a job without tensors learns of it from
+// j2p_batch_wait — and what classify() checks at submit for a job with them.
 int validate_job(const j2p_job &d)
 {
         if(d.nchannel == 0 || d.nchannel > J2P_MAX_CHANNELS) { return j2p_fail(J2P_EINVAL, "job: nchannel must be 1..3"); }
@@ -108,9 +160,7 @@ int validate_job(const j2p_job &d)
         if(d.out_tensor.data) {
                 // tensor output: the image left in device memory, instead of samples and coefficients
                 if(d.out_bits || d.out_coef[0]) { return j2p_fail(J2P_EINVAL, "job: tensor output (out_tensor) needs out_bits 0 and no out_coef"); }
-                if(d.nchannel == 2) { return j2p_fail(J2P_EINVAL, "job: tensor output needs three channels (RGB) or one (greyscale)"); }
-                if(d.out_w == 0 || d.out_h == 0) { return j2p_fail(J2P_EINVAL, "job: tensor output needs out_w and out_h"); }
-                if(d.tile) { return j2p_fail(J2P_EINVAL, "job: tensor output of a row-tiled job is not supported"); }
+                JOB_TRY(validate_tensor_form(d));
         }
         return J2P_OK;
 }
@@ -167,16 +217,101 @@ struct Engines {
         }
 };
 
-// What a job does once its engines exist: the iterations (compute.c:427-453), then the samples, coefficients or planes.
+// Band b of a job's engines as delivery sees it: channel c's plane there and the canvas rows [row0[c], row1[c]) it holds.  The
+// solves of a job share their cuts (multiples of 16 rows: of a block row of either sampling) and differ only in where the last
+// band ends; the last band takes all that the output has left — the block row that overhangs the canvas too — and the rows
+// forms refuse what is not there.
+struct Band {
+        j2p_plane_ref ref[J2P_MAX_CHANNELS];
+        unsigned row0[J2P_MAX_CHANNELS], row1[J2P_MAX_CHANNELS];
+        bool last;
+        // the band's image rows [*y0, *y1); false: none (a band below the image, canvas padding only)
+        bool image_rows(const j2p_job &d, unsigned *y0, unsigned *y1) const
+        {
+                *y0 = row0[0];
+                *y1 = !last && row1[0] < d.out_h ? row1[0] : d.out_h;
+                return *y0 < *y1;
+        }
+};
+
+// ---- the output forms: what one band delivers.  Only the three rows forms are ever row-tiled; for the others the one band is the
+// whole canvas.  A form that fills tensors ends with a sync (synced): the ticket says complete, for any stream. ----
+
+int synced(int rc, const Band &band) { return rc != J2P_OK ? rc : j2p_solver_sync(band.ref[0].solver); }
+
+int deliver_samples(const j2p_job &d, const Band &band)
+{
+        unsigned y0, y1;
+        if(!band.image_rows(d, &y0, &y1)) { return J2P_OK; }
+        const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
+        uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
+        if(d.nchannel == 1) { return j2p_planes_rows_to_grey(band.ref, d.out_w, y0, y1, d.out_bits, out); }   // greyscale: one sample per pixel
+        return j2p_planes_rows_to_rgb(band.ref, d.out_w, y0, y1, d.out_bits, out);
+}
+
+int deliver_tensor_rows(const j2p_job &d, const Band &band)
+{
+        unsigned y0, y1;
+        if(!band.image_rows(d, &y0, &y1)) { return J2P_OK; }
+        j2p_tensor rows = d.out_tensor;                  // the band's first row of it
+        const size_t row_bytes = (size_t)(d.out_tensor.stride_y > 0 ? d.out_tensor.stride_y : 0) * j2p_tensor_element_bytes(d.out_tensor.dtype);
+        rows.data = static_cast<char *>(d.out_tensor.data) + (size_t)y0 * row_bytes;
+        return synced(j2p_planes_rows_to_tensor(band.ref, d.nchannel, d.out_w, y0, y1, &rows), band);
+}
+
+int deliver_coefficients(const j2p_job &d, const Band &band)
+{
+        for(unsigned c = 0; d.out_coef[0] && c < d.nchannel; c++) {
+                const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
+                const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
+                const unsigned r0 = band.row0[c] / (8 * sy), r1 = !band.last && band.row1[c] / (8 * sy) < bh ? band.row1[c] / (8 * sy) : bh;
+                if(r0 >= r1) { continue; }                       // band below the image (canvas padding only)
+                JOB_TRY(j2p_planes_rows_to_coefficients_sub(&band.ref[c], sx, sy, bw, r0, r1, d.out_quant[c], d.out_coef[c] + (size_t)r0 * bw * 64));
+        }
+        return J2P_OK;
+}
+
+int deliver_resized(const Job &j, const j2p_job &d, const Band &band)
+{
+        return synced(j2p_planes_to_tensor_resized(band.ref, d.nchannel, d.out_w, d.out_h, &j.resize, &d.out_tensor), band);
+}
+
+int deliver_resampled(const Job &j, const j2p_job &d, const Band &band)
+{
+        return synced(j2p_planes_to_tensor_resampled(band.ref, d.nchannel, d.out_w, d.out_h, &j.resample, &d.out_tensor), band);
+}
+
+int deliver_outputs(const Job &j, const j2p_job &d, const Band &band)
+{
+        return synced(j2p_planes_to_tensors_resampled(band.ref, d.nchannel, d.out_w, d.out_h, (unsigned)j.outputs.size(), j.outputs.data()), band);
+}
+
+int deliver_jpeg(const Job &j, const j2p_job &d, const Band &band)
+{
+        return j2p_planes_to_jpeg(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size);
+}
+
+int deliver(const Job &j, const Band &band)
+{
+        const j2p_job &d = j.desc;
+        switch(j.out) {
+        // (validate_job lets at most one of the three be asked for; none: out_planes only)
+        case Out::own: return d.out_bits ? deliver_samples(d, band) : d.out_tensor.data ? deliver_tensor_rows(d, band) : deliver_coefficients(d, band);
+        case Out::resized: return deliver_resized(j, d, band);
+        case Out::resampled: return deliver_resampled(j, d, band);
+        case Out::outputs: return deliver_outputs(j, d, band);
+        case Out::jpeg: return deliver_jpeg(j, d, band);
+        }
+        return J2P_OK;
+}
+
+// What a job does once its engines exist: the iterations (compute.c:427-453), then its output form, band by band.
 // Chunked when the caller watches (j2p_next_chunk), so that its bar and CSV keep moving.  `overlap`: the chunk of every
 // solve is issued before any of them is settled (sync, progress, done) — how the three solves of `-s` overlap on one GPU,
 // unless log rows make every run synchronous anyway.  Row-tiled jobs settle each solve right after issuing it.
-// resize / resample (tensor jobs on one GPU only, at most one of the two): the tensor receives the image resized.
-// outputs (never empty when given; a job on one GPU without out_tensor): those tensors are filled from the solve.
-// jpeg (a job on one GPU with no other output but out_planes): the file is made from the solve.
-int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p_resize *resize, const j2p_resample *resample,
-                      const std::vector<j2p_output> *outputs, const JpegOut *jpeg)
+int solve_and_deliver(const Job &j, const Engine *e, bool overlap)
 {
+        const j2p_job &d = j.desc;
         const unsigned nsolve = solves(d);
         if(!d.on_rows && !d.on_progress) {
                 for(unsigned k = 0; k < nsolve; k++) { JOB_TRY(e[k].run(d.iterations[k], nullptr)); }
@@ -208,64 +343,17 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p
                         }
                 }
         }
-        // Every band delivers its own rows from its own GPU.  The solves of a job share their cuts (multiples of 16 rows: of a
-        // block row of either sampling) and differ only in where the last band ends; the last band takes all that the output
-        // has left — the block row that overhangs the canvas too — and the rows forms refuse what is not there.
+        // every band delivers its own rows from its own GPU
         const unsigned nband = e[0].nband();
         for(unsigned b = 0; b < nband; b++) {
-                j2p_plane_ref ref[J2P_MAX_CHANNELS];
-                unsigned row0[J2P_MAX_CHANNELS], row1[J2P_MAX_CHANNELS];
+                Band band;
+                band.last = b + 1 == nband;
                 for(unsigned c = 0; c < d.nchannel; c++) {
                         const Where at = where(d, c);
-                        ref[c].channel = at.channel;
-                        JOB_TRY(e[at.solve].band(b, &ref[c].solver, &row0[c], &row1[c]));
+                        band.ref[c].channel = at.channel;
+                        JOB_TRY(e[at.solve].band(b, &band.ref[c].solver, &band.row0[c], &band.row1[c]));
                 }
-                if(outputs) {
-                        // (never row-tiled: this one band is the whole canvas)
-                        JOB_TRY(j2p_planes_to_tensors_resampled(ref, d.nchannel, d.out_w, d.out_h, (unsigned)outputs->size(), outputs->data()));
-                        JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: every tensor complete, for any stream
-                        continue;
-                }
-                if(jpeg) {
-                        // (never row-tiled: this one band is the whole canvas)
-                        JOB_TRY(j2p_planes_to_jpeg(ref, d.nchannel, &jpeg->spec, jpeg->out, jpeg->capacity, jpeg->size));
-                        continue;
-                }
-                if(d.out_bits || d.out_tensor.data) {
-                        const unsigned y0 = row0[0], y1 = b + 1 < nband && row1[0] < d.out_h ? row1[0] : d.out_h;   // the band's image rows
-                        if(y0 >= y1) { continue; }                       // band below the image (canvas padding only)
-                        if(d.out_bits) {
-                                const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
-                                uint8_t *out = d.out_rgb + (size_t)y0 * row_bytes;
-                                if(d.nchannel == 1) { JOB_TRY(j2p_planes_rows_to_grey(ref, d.out_w, y0, y1, d.out_bits, out)); }   // greyscale: one sample per pixel
-                                else { JOB_TRY(j2p_planes_rows_to_rgb(ref, d.out_w, y0, y1, d.out_bits, out)); }
-                                continue;
-                        }
-                        if(resize) {
-                                // (never row-tiled: this one band is the whole canvas)
-                                JOB_TRY(j2p_planes_to_tensor_resized(ref, d.nchannel, d.out_w, d.out_h, resize, &d.out_tensor));
-                                JOB_TRY(j2p_solver_sync(ref[0].solver));
-                                continue;
-                        }
-                        if(resample) {
-                                JOB_TRY(j2p_planes_to_tensor_resampled(ref, d.nchannel, d.out_w, d.out_h, resample, &d.out_tensor));
-                                JOB_TRY(j2p_solver_sync(ref[0].solver));
-                                continue;
-                        }
-                        j2p_tensor rows = d.out_tensor;                  // the band's first row of it
-                        const size_t row_bytes = (size_t)(d.out_tensor.stride_y > 0 ? d.out_tensor.stride_y : 0) * j2p_tensor_element_bytes(d.out_tensor.dtype);
-                        rows.data = static_cast<char *>(d.out_tensor.data) + (size_t)y0 * row_bytes;
-                        JOB_TRY(j2p_planes_rows_to_tensor(ref, d.nchannel, d.out_w, y0, y1, &rows));
-                        JOB_TRY(j2p_solver_sync(ref[0].solver));         // the ticket says: complete, for any stream
-                        continue;
-                }
-                for(unsigned c = 0; d.out_coef[0] && c < d.nchannel; c++) {
-                        const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
-                        const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
-                        const unsigned r0 = row0[c] / (8 * sy), r1 = b + 1 < nband && row1[c] / (8 * sy) < bh ? row1[c] / (8 * sy) : bh;
-                        if(r0 >= r1) { continue; }                       // band below the image (canvas padding only)
-                        JOB_TRY(j2p_planes_rows_to_coefficients_sub(&ref[c], sx, sy, bw, r0, r1, d.out_quant[c], d.out_coef[c] + (size_t)r0 * bw * 64));
-                }
+                JOB_TRY(deliver(j, band));
         }
         for(unsigned c = 0; !d.out_bits && c < d.nchannel; c++) {
                 if(d.out_planes[c]) { JOB_TRY(e[where(d, c).solve].download(where(d, c).channel, d.out_planes[c])); }
@@ -273,14 +361,15 @@ int solve_and_deliver(const j2p_job &d, const Engine *e, bool overlap, const j2p
         return J2P_OK;
 }
 
-// One image over several of the batch's devices (j2p_job::tile): every solve of the job becomes a j2p_tiled with band
-// b on devices[b]; the solves of `-s` share their cuts so that band b of the three components meets on one GPU for
-// the colour conversion.  Returns J2P_OK with *handled = false when the image should be solved on one GPU after all:
-// too small for two bands (rows, or pixels per band), or the devices cannot be tiled over (the create phase failed:
-// no peer access and no RCCL, or no room for the band arenas) — the caller then takes the single-solver path.
+// One image over several of the batch's devices (j2p_job::tile; classify() lets only In::planes jobs with Out::own ask for it):
+// every solve of the job becomes a j2p_tiled with band b on devices[b]; the solves of `-s` share their cuts so that band b of the
+// three components meets on one GPU for the colour conversion.  Returns J2P_OK with *handled = false when the image should be
+// solved on one GPU after all: too small for two bands (rows, or pixels per band), or the devices cannot be tiled over (the
+// create phase failed: no peer access and no RCCL, or no room for the band arenas) — the caller then takes the single-solver path.
 // Failures after the iterations have started stay failures.
-int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handled)
+int run_job_tiled(const Job &j, const std::vector<int> &devices, bool *handled)
 {
+        const j2p_job &d = j.desc;
         *handled = false;
         const unsigned nsolve = solves(d);
         // the canvas of every solve; the alignment is the one all the job's channels share
@@ -322,42 +411,42 @@ int run_job_tiled(const j2p_job &d, const std::vector<int> &devices, bool *handl
                 if(rc != J2P_OK) { return rc; }
         }
         *handled = true;
-        return solve_and_deliver(d, eng.e, false, nullptr, nullptr, nullptr, nullptr);
+        return solve_and_deliver(j, eng.e, false);
 }
 
-// a file job's engines: the file's scan decoded ONCE on the worker's GPU into pooled grids (j2p_decoded_grids: all components,
-// whichever of them the job solves), from which every solver of the job copies its channels on the device
-int create_from_file(const j2p_job &d, int device, const j2p_jpeg_file &file, Engines &eng)
+// The engines of a job on one GPU, made from its input kind.  A file's scan is decoded ONCE, on this GPU, into pooled grids
+// (j2p_decoded_grids: all components, whichever of them the job solves), from which every solver of the job copies its channels
+// on the device; the grids go when the solvers exist.
+int create_engines(const Job &j, int device, Engines &eng)
 {
-        const j2p_decoded_grids grids(device, file, 0, nullptr);
-        int rc = grids.rc;
-        for(unsigned k = 0; rc == J2P_OK && k < solves(d); k++) {
-                const unsigned nch = d.separate ? 1 : d.nchannel;
-                rc = j2p_solver_create_from_decoded(&eng.e[k].s, device, nch, &d.planes[k], &grids.coef[k], d.weight[k], &d.pweight[k], d.iterations[k]);
-        }
-        return rc;
-}
-
-// (samples: NULL, or [channel] what the solvers are made from instead of planes[].data; file: NULL, or the file they are made from)
-int run_job(const j2p_job &d, int device, const j2p_resize *resize, const j2p_resample *resample, const std::vector<j2p_output> *outputs,
-            const j2p_samples *samples, const JpegOut *jpeg, const j2p_jpeg_file *file)
-{
+        const j2p_job &d = j.desc;
         const j2p_band whole = {0, 0};
-        Engines eng;
-        if(file) {
-                JOB_TRY(create_from_file(d, device, *file, eng));
-                return solve_and_deliver(d, eng.e, true, resize, resample, outputs, jpeg);
+        std::optional<j2p_decoded_grids> grids;
+        if(j.in == In::file) {
+                grids.emplace(device, j.file, 0u, nullptr);
+                JOB_TRY(grids->rc);
         }
         for(unsigned k = 0; k < solves(d); k++) {
                 const unsigned nch = d.separate ? 1 : d.nchannel;
-                if(samples) {
-                        JOB_TRY(j2p_solver_create_from_samples(&eng.e[k].s, device, nullptr, nch, &d.planes[k], &samples[k], d.weight[k], &d.pweight[k],
-                                                               d.iterations[k]));
-                        continue;
+                j2p_solver **s = &eng.e[k].s;
+                switch(j.in) {
+                case In::planes: JOB_TRY(j2p_solver_create(s, device, nullptr, nch, &d.planes[k], d.weight[k], &d.pweight[k], d.iterations[k], whole, 0)); break;
+                case In::samples:
+                        JOB_TRY(j2p_solver_create_from_samples(s, device, nullptr, nch, &d.planes[k], &j.samples[k], d.weight[k], &d.pweight[k], d.iterations[k]));
+                        break;
+                case In::file:
+                        JOB_TRY(j2p_solver_create_from_decoded(s, device, nch, &d.planes[k], &grids->coef[k], d.weight[k], &d.pweight[k], d.iterations[k]));
+                        break;
                 }
-                JOB_TRY(j2p_solver_create(&eng.e[k].s, device, nullptr, nch, &d.planes[k], d.weight[k], &d.pweight[k], d.iterations[k], whole, 0));
         }
-        return solve_and_deliver(d, eng.e, true, resize, resample, outputs, jpeg);
+        return J2P_OK;
+}
+
+int run_job(const Job &j, int device)
+{
+        Engines eng;
+        JOB_TRY(create_engines(j, device, eng));
+        return solve_and_deliver(j, eng.e, true);
 }
 
 void worker_main(j2p_batch *b, int device)
@@ -367,7 +456,7 @@ void worker_main(j2p_batch *b, int device)
                 Job *job = nullptr;
                 {
                         std::unique_lock<std::mutex> g(b->lock);
-                        // the first queued job this worker may run: any job, except that one with a tensor is pinned to its GPU
+                        // the first queued job this worker may run: any job, except that a pinned one is for its GPU's workers
                         const auto mine = [&] {
                                 auto it = b->queue.begin();
                                 while(it != b->queue.end() && (*it)->device >= 0 && (*it)->device != device) { ++it; }
@@ -390,14 +479,12 @@ void worker_main(j2p_batch *b, int device)
                         else {
                                 const std::vector<int> share(b->devices.begin() + (ptrdiff_t)first, b->devices.begin() + (ptrdiff_t)(first + count));
                                 if(job->desc.tile_count) { single = share[0]; }     // untiled after all: on a GPU of its share
-                                if(share.size() > 1) { rc = run_job_tiled(job->desc, share, &tiled); }
+                                if(share.size() > 1) { rc = run_job_tiled(*job, share, &tiled); }
                         }
                 }
                 if(rc == J2P_OK && !tiled) {
                         if(single != device) { (void)hipSetDevice(single); }
-                        rc = run_job(job->desc, single, job->resized ? &job->resize : nullptr, job->resampled ? &job->resample : nullptr,
-                                     job->outputs.empty() ? nullptr : &job->outputs, job->samples.empty() ? nullptr : job->samples.data(),
-                                     job->jpeg.on ? &job->jpeg : nullptr, job->file.parsed ? &job->file : nullptr);
+                        rc = run_job(*job, single);
                         if(single != device) { (void)hipSetDevice(device); }
                 }
                 {
@@ -410,29 +497,56 @@ void worker_main(j2p_batch *b, int device)
         }
 }
 
-// what j2p_batch_submit_outputs refuses at submit; *device: the one GPU that holds every tensor
-int validate_outputs(const j2p_job &d, unsigned n, const j2p_output *outs, int *device)
+// ---- submit: the job and its request become the record, or are refused.  The first failing check decides the message, so the
+// order below is part of the interface: file, JPEG, samples, outputs, resample, resize, then the pins. ----
+
+// a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
+// show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
+int open_file(const Request &q, Job &j)
 {
-        if(n > J2P_MAX_OUTPUTS) { return j2p_fail(J2P_EINVAL, "job: %u outputs (at most %d)", n, J2P_MAX_OUTPUTS); }
-        if(d.out_tensor.data || d.out_bits || d.out_coef[0]) {
-                return j2p_fail(J2P_EINVAL, "job: a job with outputs needs out_tensor.data NULL, out_bits 0 and no out_coef");
+        j2p_job &d = j.desc;
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: file input of a row-tiled job is not supported"); }
+        JOB_TRY(j2p_jpeg_open(q.file, q.file_size, &j.file));
+        const j2p_jpeg_info &info = j.file.parsed->info;
+        if(d.nchannel == 0) { d.nchannel = info.ncomp; }
+        // (one channel of a three-component file: component 0 alone, the greyscale solve)
+        if(d.nchannel != info.ncomp && d.nchannel != 1) {
+                return j2p_fail(J2P_EINVAL, "job: %u channels for a file of %u components (all of them, or 1 for component 0 alone)", d.nchannel, info.ncomp);
         }
-        if(d.nchannel != 1 && d.nchannel != 3) { return j2p_fail(J2P_EINVAL, "job: tensor output needs three channels (RGB) or one (greyscale)"); }
-        if(d.out_w == 0 || d.out_h == 0) { return j2p_fail(J2P_EINVAL, "job: tensor output needs out_w and out_h"); }
-        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: tensor output of a row-tiled job is not supported"); }
-        for(unsigned i = 0; i < n; i++) {
-                if(const char *why = j2p_resample_error(&outs[i].r, d.out_w, d.out_h)) { return j2p_fail(J2P_EINVAL, "job: output %u: %s", i, why); }
-                int dev = -1;
-                if(j2p_device_of_pointer(outs[i].t.data, &dev) != J2P_OK) {
-                        return j2p_fail(J2P_EINVAL, "job: output %u: the tensor's data is not device memory (managed and host memory are refused)", i);
+        for(unsigned c = 0; c < d.nchannel; c++) {
+                j2p_plane &p = d.planes[c];
+                const j2p_jpeg_component &k = info.comp[c];
+                if(p.data || p.fdata) { return j2p_fail(J2P_EINVAL, "job: channel %u: a job with a file takes no data / fdata (both must be NULL)", c); }
+                if((p.w && p.w != k.blocks_w * 8) || (p.h && p.h != k.blocks_h * 8)) {
+                        return j2p_fail(J2P_EINVAL, "job: channel %u: the plane is %ux%u, the file's component %ux%u", c, p.w, p.h, k.blocks_w * 8, k.blocks_h * 8);
                 }
-                if(i && dev != *device) { return j2p_fail(J2P_EINVAL, "job: output %u lives on device %d, output 0 on device %d", i, dev, *device); }
-                *device = dev;
+                p.w = k.blocks_w * 8;
+                p.h = k.blocks_h * 8;
+                // (sampling factors left zero are the file's; a caller who zooms gives the file's times the zoom)
+                if(!p.w_samp) { p.w_samp = k.w_samp; }
+                if(!p.h_samp) { p.h_samp = k.h_samp; }
+                p.quant_table = k.quant;           // (the file's table: lives in the job's parse)
         }
+        if(!d.out_w) { d.out_w = info.width; }
+        if(!d.out_h) { d.out_h = info.height; }
         return J2P_OK;
 }
 
-// what j2p_batch_submit_samples refuses at submit; *device: the GPU that holds the device samples, or -1 (host samples only)
+int validate_jpeg(const j2p_job &d, const Request &q)
+{
+        if(d.out_bits || d.out_coef[0] || d.out_tensor.data) {
+                return j2p_fail(J2P_EINVAL, "job: a JPEG job needs out_bits 0, no out_coef and out_tensor.data NULL");
+        }
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: JPEG output of a row-tiled job is not supported"); }
+        if(const char *why = j2p_jpeg_error(q.jpeg, d.nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+        if(q.jpeg->width != d.out_w || q.jpeg->height != d.out_h) {
+                return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", q.jpeg->width, q.jpeg->height, d.out_w, d.out_h);
+        }
+        if(!q.jpeg_size || (!q.jpeg_out && q.jpeg_capacity)) { return j2p_fail(J2P_EINVAL, "job: JPEG output needs out and size"); }
+        return J2P_OK;
+}
+
+// *device: the GPU that holds the device samples, or -1 (host samples only)
 int validate_samples(const j2p_job &d, const j2p_samples *samples, int *device)
 {
         if(d.nchannel == 0 || d.nchannel > J2P_MAX_CHANNELS) { return j2p_fail(J2P_EINVAL, "job: nchannel must be 1..3"); }
@@ -458,143 +572,102 @@ int validate_samples(const j2p_job &d, const j2p_samples *samples, int *device)
         return J2P_OK;
 }
 
-// j2p_batch_submit, and — r != NULL — j2p_batch_submit_resized, — f != NULL — j2p_batch_submit_resampled, — nout != 0 —
-// j2p_batch_submit_outputs (never two of them); samples != NULL: j2p_batch_submit_samples (with nout or without; never with r or f);
-// jpeg != NULL: j2p_batch_submit_jpeg (with samples or without, and nothing else); file != NULL: j2p_batch_submit_file and
-// j2p_batch_submit_file_jpeg (never with samples; with nout or with jpeg)
-int submit(j2p_batch *b, const j2p_job *job, const j2p_resize *r, const j2p_resample *f, unsigned nout, const j2p_output *outs,
-           const j2p_samples *samples, const JpegOut *jpeg, int *ticket, const uint8_t *file = nullptr, size_t file_size = 0)
+// *device: the one GPU that holds every tensor
+int validate_outputs(const j2p_job &d, unsigned n, const j2p_output *outs, int *device)
+{
+        if(n > J2P_MAX_OUTPUTS) { return j2p_fail(J2P_EINVAL, "job: %u outputs (at most %d)", n, J2P_MAX_OUTPUTS); }
+        if(d.out_tensor.data || d.out_bits || d.out_coef[0]) {
+                return j2p_fail(J2P_EINVAL, "job: a job with outputs needs out_tensor.data NULL, out_bits 0 and no out_coef");
+        }
+        JOB_TRY(validate_tensor_form(d));
+        for(unsigned i = 0; i < n; i++) {
+                if(const char *why = j2p_resample_error(&outs[i].r, d.out_w, d.out_h)) { return j2p_fail(J2P_EINVAL, "job: output %u: %s", i, why); }
+                int dev = -1;
+                if(j2p_device_of_pointer(outs[i].t.data, &dev) != J2P_OK) {
+                        return j2p_fail(J2P_EINVAL, "job: output %u: the tensor's data is not device memory (managed and host memory are refused)", i);
+                }
+                if(i && dev != *device) { return j2p_fail(J2P_EINVAL, "job: output %u lives on device %d, output 0 on device %d", i, dev, *device); }
+                *device = dev;
+        }
+        return J2P_OK;
+}
+
+// The job runs on `device` only, where its tensor(s), device samples or file are (what: "the tensor lives", ...): that must be one of
+// the batch's GPUs, and the one an earlier pin chose.
+int pin(const j2p_batch &b, Job &j, int device, const char *what)
+{
+        if(j.device >= 0 && j.device != device) { return j2p_fail(J2P_EINVAL, "job: %s on device %d, the output tensor on device %d", what, device, j.device); }
+        bool owned = false;
+        for(int dev : b.devices) { owned = owned || dev == device; }
+        if(!owned) { return j2p_fail(J2P_EINVAL, "job: %s on device %d, which this batch does not drive", what, device); }
+        j.device = device;
+        return J2P_OK;
+}
+
+// j = the record of `given` and what its entry point sent along: the input kind and the output kind with their payloads, and the pin
+int classify(const j2p_batch &b, const j2p_job &given, const Request &q, Job &j)
+{
+        j.desc = given;
+        const j2p_job &d = j.desc;
+        int samples_device = -1, tensor_device = -1;
+        if(q.file) {
+                j.in = In::file;
+                JOB_TRY(open_file(q, j));
+        }
+        if(q.jpeg) {
+                j.out = Out::jpeg;
+                JOB_TRY(validate_jpeg(d, q));
+                j.jpeg.set(q, d.nchannel);
+        }
+        if(q.samples) {
+                j.in = In::samples;
+                JOB_TRY(validate_samples(d, q.samples, &samples_device));
+                j.samples.assign(q.samples, q.samples + d.nchannel);
+        }
+        if(q.nout) {
+                j.out = Out::outputs;
+                JOB_TRY(validate_outputs(d, q.nout, q.outs, &tensor_device));
+                j.outputs.assign(q.outs, q.outs + q.nout);
+        }
+        if(q.resample) {
+                j.out = Out::resampled;
+                if(!d.out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resampled job needs tensor output (out_tensor)"); }
+                if(const char *why = j2p_resample_error(q.resample, d.out_w, d.out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+                j.resample = *q.resample;
+        }
+        if(q.resize) {
+                j.out = Out::resized;
+                if(!d.out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resized job needs tensor output (out_tensor)"); }
+                if(const char *why = j2p_resize_error(q.resize, d.out_w, d.out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+                j.resize = *q.resize;
+        }
+        if(d.out_tensor.data || j.out == Out::outputs) {
+                // a job with tensors: what can be refused is refused here, and the job is pinned to the GPU that holds them
+                JOB_TRY(validate_job(d));
+                if(j.out != Out::outputs && j2p_device_of_pointer(d.out_tensor.data, &tensor_device) != J2P_OK) {
+                        return j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
+                }
+                JOB_TRY(pin(b, j, tensor_device, "the tensor lives"));
+        }
+        // device samples, and a file in device memory, pin the job as tensors do
+        if(samples_device >= 0) { JOB_TRY(pin(b, j, samples_device, "the samples live")); }
+        if(j.file.device >= 0) { JOB_TRY(pin(b, j, j.file.device, "the file lives")); }
+        return J2P_OK;
+}
+
+int submit(j2p_batch *b, const j2p_job *job, const Request &q, int *ticket)
 {
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        // a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
-        // show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
-        j2p_jpeg_file file_in;
-        j2p_job filled;
-        int file_device = -1;
-        if(file) {
-                if(job->tile) { return j2p_fail(J2P_EINVAL, "job: file input of a row-tiled job is not supported"); }
-                if(const int rc = j2p_jpeg_open(file, file_size, &file_in); rc != J2P_OK) { return rc; }
-                file_device = file_in.device;
-                const j2p_jpeg_info &info = file_in.parsed->info;
-                filled = *job;
-                if(filled.nchannel == 0) { filled.nchannel = info.ncomp; }
-                // (one channel of a three-component file: component 0 alone, the greyscale solve)
-                if(filled.nchannel != info.ncomp && filled.nchannel != 1) {
-                        return j2p_fail(J2P_EINVAL, "job: %u channels for a file of %u components (all of them, or 1 for component 0 alone)", filled.nchannel, info.ncomp);
-                }
-                for(unsigned c = 0; c < filled.nchannel; c++) {
-                        j2p_plane &p = filled.planes[c];
-                        const j2p_jpeg_component &k = info.comp[c];
-                        if(p.data || p.fdata) { return j2p_fail(J2P_EINVAL, "job: channel %u: a job with a file takes no data / fdata (both must be NULL)", c); }
-                        if((p.w && p.w != k.blocks_w * 8) || (p.h && p.h != k.blocks_h * 8)) {
-                                return j2p_fail(J2P_EINVAL, "job: channel %u: the plane is %ux%u, the file's component %ux%u", c, p.w, p.h, k.blocks_w * 8, k.blocks_h * 8);
-                        }
-                        p.w = k.blocks_w * 8;
-                        p.h = k.blocks_h * 8;
-                        // (sampling factors left zero are the file's; a caller who zooms gives the file's times the zoom)
-                        if(!p.w_samp) { p.w_samp = k.w_samp; }
-                        if(!p.h_samp) { p.h_samp = k.h_samp; }
-                        p.quant_table = k.quant;           // (the file's table: lives in the job's parse)
-                }
-                if(!filled.out_w) { filled.out_w = info.width; }
-                if(!filled.out_h) { filled.out_h = info.height; }
-                job = &filled;
-        }
-        if(jpeg) {
-                if(job->out_bits || job->out_coef[0] || job->out_tensor.data) {
-                        return j2p_fail(J2P_EINVAL, "job: a JPEG job needs out_bits 0, no out_coef and out_tensor.data NULL");
-                }
-                if(job->tile) { return j2p_fail(J2P_EINVAL, "job: JPEG output of a row-tiled job is not supported"); }
-                if(const char *why = j2p_jpeg_error(&jpeg->spec, job->nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-                if(jpeg->spec.width != job->out_w || jpeg->spec.height != job->out_h) {
-                        return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", jpeg->spec.width, jpeg->spec.height,
-                                        job->out_w, job->out_h);
-                }
-                if(!jpeg->size || (!jpeg->out && jpeg->capacity)) { return j2p_fail(J2P_EINVAL, "job: JPEG output needs out and size"); }
-        }
-        int samples_device = -1;
-        if(samples) {
-                if(const int rc = validate_samples(*job, samples, &samples_device); rc != J2P_OK) { return rc; }
-        }
-        int outputs_device = -1;
-        if(nout) {
-                if(const int rc = validate_outputs(*job, nout, outs, &outputs_device); rc != J2P_OK) { return rc; }
-        }
-        if(f) {
-                if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resampled job needs tensor output (out_tensor)"); }
-                if(const char *why = j2p_resample_error(f, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-        }
-        if(r) {
-                if(!job->out_tensor.data) { return j2p_fail(J2P_EINVAL, "job: a resized job needs tensor output (out_tensor)"); }
-                if(const char *why = j2p_resize_error(r, job->out_w, job->out_h)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-        }
-        Job *j = new(std::nothrow) Job();
+        std::unique_ptr<Job> j(new(std::nothrow) Job());
         if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
-        j->desc = *job;
-        if(r) {
-                j->resize = *r;
-                j->resized = true;
-        }
-        if(f) {
-                j->resample = *f;
-                j->resampled = true;
-        }
-        if(nout) { j->outputs.assign(outs, outs + nout); }
-        if(samples) { j->samples.assign(samples, samples + job->nchannel); }
-        if(file) { j->file = std::move(file_in); }
-        if(jpeg) {
-                // the tables travel with the job
-                j->jpeg = *jpeg;
-                j->jpeg.on = true;
-                for(unsigned c = 0; c < job->nchannel; c++) {
-                        memcpy(j->jpeg.tables[c], jpeg->spec.quant[c], sizeof(j->jpeg.tables[c]));
-                        j->jpeg.spec.quant[c] = j->jpeg.tables[c];
-                }
-        }
-        if(job->out_tensor.data || nout) {
-                // what can be refused is refused here, and the job is pinned to the GPU that holds its tensor(s)
-                int rc = validate_job(j->desc);
-                if(nout) { j->device = outputs_device; }
-                else if(rc == J2P_OK && j2p_device_of_pointer(job->out_tensor.data, &j->device) != J2P_OK) {
-                        rc = j2p_fail(J2P_EINVAL, "job: out_tensor.data is not device memory (managed and host memory are refused)");
-                }
-                bool owned = false;
-                for(int dev : b->devices) { owned = owned || dev == j->device; }
-                if(rc == J2P_OK && !owned) { rc = j2p_fail(J2P_EINVAL, "job: the tensor lives on device %d, which this batch does not drive", j->device); }
-                if(rc != J2P_OK) { delete j; return rc; }
-        }
-        if(samples_device >= 0) {
-                // device samples pin the job as tensors do: to their GPU, which must be the tensors' and one of the batch's
-                int rc = J2P_OK;
-                bool owned = false;
-                for(int dev : b->devices) { owned = owned || dev == samples_device; }
-                if(j->device >= 0 && j->device != samples_device) {
-                        rc = j2p_fail(J2P_EINVAL, "job: the samples live on device %d, the output tensor on device %d", samples_device, j->device);
-                }
-                else if(!owned) { rc = j2p_fail(J2P_EINVAL, "job: the samples live on device %d, which this batch does not drive", samples_device); }
-                if(rc != J2P_OK) { delete j; return rc; }
-                j->device = samples_device;
-        }
-        if(file_device >= 0) {
-                // a file in device memory pins the job as device samples do
-                int rc = J2P_OK;
-                bool owned = false;
-                for(int dev : b->devices) { owned = owned || dev == file_device; }
-                if(j->device >= 0 && j->device != file_device) {
-                        rc = j2p_fail(J2P_EINVAL, "job: the file lives on device %d, the output tensor on device %d", file_device, j->device);
-                }
-                else if(!owned) { rc = j2p_fail(J2P_EINVAL, "job: the file lives on device %d, which this batch does not drive", file_device); }
-                if(rc != J2P_OK) { delete j; return rc; }
-                j->device = file_device;
-        }
+        JOB_TRY(classify(*b, *job, q, *j));
         const bool pinned = j->device >= 0;
         {
                 std::lock_guard<std::mutex> g(b->lock);
-                if(b->quit) { delete j; return j2p_fail(J2P_ESTATE, "batch is shutting down"); }
-                j->ticket = b->next_ticket++;
-                b->jobs[j->ticket] = j;
-                b->queue.push_back(j);
-                *ticket = j->ticket;
+                if(b->quit) { return j2p_fail(J2P_ESTATE, "batch is shutting down"); }
+                *ticket = j->ticket = b->next_ticket++;
+                b->jobs[j->ticket] = j.get();
+                b->queue.push_back(j.release());
         }
         // (a pinned job may not be for the worker notify_one would wake)
         if(pinned) { b->work.notify_all(); } else { b->work.notify_one(); }
@@ -647,48 +720,40 @@ void j2p_batch_destroy(j2p_batch *b)
 
 int j2p_batch_submit(j2p_batch *b, const j2p_job *job, int *ticket)
 {
-        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, nullptr, ticket);
+        return submit(b, job, Request(), ticket);
 }
 
 int j2p_batch_submit_resized(j2p_batch *b, const j2p_job *job, const j2p_resize *r, int *ticket)
 {
-        return submit(b, job, r, nullptr, 0, nullptr, nullptr, nullptr, ticket);
+        return submit(b, job, Request().resized(r), ticket);
 }
 
 int j2p_batch_submit_resampled(j2p_batch *b, const j2p_job *job, const j2p_resample *r, int *ticket)
 {
-        return submit(b, job, nullptr, r, 0, nullptr, nullptr, nullptr, ticket);
+        return submit(b, job, Request().resampled(r), ticket);
 }
 
 int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const j2p_output outs[], int *ticket)
 {
-        const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, nullptr, ticket);
+        return submit(b, job, Request().outputs(n, outs), ticket);
 }
 
 int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[], int *ticket)
 {
-        const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, samples, nullptr, ticket);
+        return submit(b, job, Request().from_samples(samples).outputs(n, outs), ticket);
 }
 
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
                           size_t *size, int *ticket)
 {
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        JpegOut jpeg;
-        jpeg.spec = *spec;
-        jpeg.out = out;
-        jpeg.capacity = capacity;
-        jpeg.size = size;
-        return submit(b, job, nullptr, nullptr, 0, nullptr, samples, &jpeg, ticket);
+        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size), ticket);
 }
 
 int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, unsigned n, const j2p_output outs[], int *ticket)
 {
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
-        const bool none = n == 0 || !outs;
-        return submit(b, job, nullptr, nullptr, none ? 0 : n, none ? nullptr : outs, nullptr, nullptr, ticket, file, size);
+        return submit(b, job, Request().from_file(file, size).outputs(n, outs), ticket);
 }
 
 int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
@@ -696,12 +761,7 @@ int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *
 {
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        JpegOut jpeg;
-        jpeg.spec = *spec;
-        jpeg.out = out;
-        jpeg.capacity = capacity;
-        jpeg.size = out_size;
-        return submit(b, job, nullptr, nullptr, 0, nullptr, nullptr, &jpeg, ticket, file, size);
+        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size), ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)
