@@ -25,6 +25,8 @@
  *   -S, --chroma-subsampling 444|422|420|440 = with -j: the chroma components of the file at half the resolution across, across
  *                  and down, or down; every chroma sample is the mean of the solved values it covers (the mean the solver's
  *                  projection constrains, compute.c:351-359), taken in float on the GPU (j2p_planes_to_coefficients_sub)
+ *   -O, --optimize = with -j: Huffman tables made for the image instead of the standard's (libjpeg's optimize_coding; with -e the
+ *                  GPU counts the symbols, J2P_JPEG_OPTIMIZE) — the same coefficients in a smaller file, and the same file either way
  * Messages and exit codes follow the reference ("jpeg2png: <message>", EXIT_FAILURE).
  */
 #define _POSIX_C_SOURCE 200809L
@@ -298,7 +300,8 @@ static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
  * ceil(w / 8) x ceil(h / 8) blocks, the chroma components ceil(that / sub_w) x ceil(that / sub_h).  Only these real blocks are
  * filled: the dummy blocks that complete a partial MCU are libjpeg's own (jctrans.c), but it reaches them through arrays
  * whose sizes are rounded up to the component's sampling factors and that can hold v_samp_factor rows at a time */
-static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h, int16_t *const coef[3])
+static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h, bool optimize,
+                       int16_t *const coef[3])
 {
         struct jpeg_compress_struct c;
         struct jpeg_error_mgr err;
@@ -308,6 +311,7 @@ static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int qu
         jpeg_stdio_dest(&c, out);
         if(ncomp == 1) { sub_w = sub_h = 1; }
         setup_jpeg_out(&c, w, h, ncomp, quality, sub_w, sub_h);
+        if(optimize) { c.optimize_coding = TRUE; }
         const unsigned bw = (w + 7) / 8, bh = (h + 7) / 8;
 #if JPEG_LIB_VERSION >= 70
         /* IJG 7+: jpeg_write_coefficients expects what jpeg_calc_jpeg_dimensions / initial_setup would have left */
@@ -348,6 +352,7 @@ struct options {
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
         bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
+        bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
         bool grey;              /* -g: component 0 alone, one-channel job, greyscale PNG */
@@ -517,8 +522,12 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 for(int attempt = 0;; attempt++) {
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
-                        if(jp.file) { gpu_check(j2p_batch_submit_file_jpeg(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket)); }
-                        else { gpu_check(j2p_batch_submit_jpeg(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket)); }
+                        const unsigned flags = o->optimize ? J2P_JPEG_OPTIMIZE : 0u;
+                        if(jp.file) {
+                                gpu_check(j2p_batch_submit_file_jpeg_ex(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, flags, &ticket));
+                        } else {
+                                gpu_check(j2p_batch_submit_jpeg_ex(batch, &job, NULL, &spec, file, capacity, &file_bytes, flags, &ticket));
+                        }
                         const int rc = j2p_batch_wait(batch, ticket);
                         if(rc != J2P_ESPACE || attempt) {
                                 gpu_check(rc);
@@ -538,7 +547,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         if(!out) { die_perror("could not open output file `%s`", outfile); }
         if(file) {
                 if(fwrite(file, 1, file_bytes, out) != file_bytes) { die_perror("could not write output file `%s`", outfile); }
-        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, out_coef); }
+        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, o->optimize, out_coef); }
         else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
@@ -597,6 +606,8 @@ static void usage(void)
                "                               such an image is not row-tiled\n"
                "  -e, --encode-on-gpu          with -j: the GPU also entropy-codes the file (default Huffman tables, the bytes\n"
                "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
+               "  -O, --optimize               with -j: Huffman tables made for the image, a smaller file of the same\n"
+               "                               coefficients (with -e the GPU counts the symbols; the same bytes either way)\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -616,15 +627,15 @@ int main(int argc, char **argv)
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
-                {"decode-on-gpu", no_argument, NULL, 'd'}, {NULL, 0, NULL, 0}};
+                {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+                            .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:ed", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edO", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -643,6 +654,7 @@ int main(int argc, char **argv)
                 case 'S': S_arg = optarg; break;
                 case 'e': o.encode_on_gpu = true; break;
                 case 'd': o.decode_on_gpu = true; break;
+                case 'O': o.optimize = true; break;
                 default: help = true; break;
                 }
         }
@@ -696,6 +708,7 @@ int main(int argc, char **argv)
                 o.sub_h = subs[k].h;
         }
         if(o.encode_on_gpu && !j_arg) { die("-e needs JPEG output (-j)"); }
+        if(o.optimize && !j_arg) { die("-O needs JPEG output (-j)"); }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);
         unsigned threads = cores > 0 ? (unsigned)cores : 1u;

@@ -136,6 +136,9 @@ int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *byte
 int j2p_solver_shares_state(const j2p_solver *s, unsigned c, int *shared);
 /* bytes of device memory the solver carved its planes, state and reduction buffers from */
 int j2p_solver_arena_bytes(const j2p_solver *s, size_t *bytes);
+/* bytes of the one block the output stage keeps for this solver (tensor taps, the JPEG coder's stages): 0 before the first call that
+ * needs it; it only grows, and a call that finds it large enough allocates nothing */
+int j2p_solver_output_scratch_bytes(const j2p_solver *s, size_t *bytes);
 /* *on = 1 when the interior strips of channel c take the wide-footprint projection path in an unlogged run (J2P_OPT_WIDE_FOOTPRINT,
  * J2P_OPT_MIXED_PROJECT), else 0 */
 int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on);
@@ -882,6 +885,51 @@ int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const co
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                           size_t capacity, size_t *size, int *ticket);
 
+/* Optimised Huffman tables: the same coefficients in fewer bytes.  With J2P_JPEG_OPTIMIZE the file is, byte for byte, the one libjpeg
+ * writes from the same coefficients with optimize_coding = TRUE added to the calls named above, as IJG libjpeg 9d and later do it.
+ * Everything in "The JPEG file" stands except item 5 of the header and the codes used in the scan.  This is the definition.
+ *
+ * Counts.  One array of 256 counts per table: DC0 and AC0 from component 0, DC1 and AC1 from components 1 and 2 together.  The scan is
+ * walked exactly as it is coded, dummy blocks included.  Per block: count[s]++ for the category s of the DC difference; per non-zero AC
+ * coefficient with a zero run r in front, count[0xF0] += r >> 4 and count[((r & 15) << 4) | s]++; count[0x00]++ when the block ends
+ * in a zero run.  (A dummy block counts DC symbol 0 and AC symbol 0x00.)
+ * Lengths, per table.  freq[0..255] = count and freq[256] = 1, a pseudo-symbol that keeps the all-ones code unused; codesize[] = 0,
+ * others[] = -1.  Repeat: c1 is the index of the smallest non-zero freq, on a tie the LARGEST index (scan upwards with <=); c2 the same
+ * among the rest; stop when there is no c2; freq[c1] += freq[c2], freq[c2] = 0; add 1 to codesize of c1 and of everything on its others
+ * chain, append c2 to the end of that chain, add 1 to codesize of c2 and of its chain.  bits[n] is the number of symbols (256 included)
+ * with codesize == n, n up to 32.  For i = 32 down to 17, while bits[i] > 0: j = i - 2, lowered while bits[j] == 0; bits[i] -= 2,
+ * bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1.  With i the largest length <= 16 that has bits[i] > 0: bits[i] -= 1, which removes
+ * the pseudo-symbol.
+ * Symbols.  HUFFVAL is the symbols with a non-zero count, ordered by count descending and then by symbol value ascending; BITS[1..16]
+ * deals the lengths out to them in that order.  (Older libjpegs — 6b to 9c — and libjpeg-turbo order the symbols of one length by
+ * value instead: their files decode to the same coefficients, differ in bytes and are a few bytes larger.)
+ * Codes.  As for every table: in order of length, consecutive within a length, doubled from one length to the next.
+ * DHT.  DC0, AC0, and for three components DC1, AC1, in that order: the class/slot byte, 16 BITS, HUFFVAL at its true length.  The
+ * header is never longer than with the default tables: a table holds at most 12 DC or 162 AC symbols.
+ * Refusal.  A count above 1 000 000 000 is J2P_ENOTSUP before anything is written: libjpeg's own search for the rarest symbols starts
+ * from that value and is undefined beyond it (a table needs more than 10^9 pixels to get there).  So is a tree with a code longer than
+ * 32 bits before limiting, which libjpeg dies on (more than five million blocks whose symbol counts grow like Fibonacci numbers).
+ *
+ * The counts are taken on the device (k_entropy_histogram) and read back, 2 x 268 64-bit counters: a third wait on the way, next to
+ * the two of j2p_planes_to_jpeg.  The tables are made on the host between two launches.  flags == 0: every call below is the call it
+ * extends — the same launches, the same memory, the same bytes.  Unknown flag bits: J2P_EINVAL. */
+#define J2P_JPEG_OPTIMIZE 1u
+int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
+                          size_t *size, unsigned flags);
+/* What the coder saw of one file (stats may be NULL): the four count arrays above — taken on the device whether or not the flag is set,
+ * so that a test sees the kernel's counts themselves and not only a file they happen not to change — the bits of the scan before
+ * padding and stuffing, and the FF bytes that were stuffed.  Zeroed first; the counts are there once they have been read back, also
+ * when the call then fails with J2P_ESPACE. */
+typedef struct j2p_encode_stats {
+        unsigned long long dc0[256], ac0[256], dc1[256], ac1[256];
+        unsigned long long scan_bits, stuffed_bytes;
+} j2p_encode_stats;
+int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
+                          size_t capacity, size_t *size, unsigned flags, j2p_encode_stats *stats);
+/* The flag travels in the job's record next to the copied spec. */
+int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                             size_t capacity, size_t *size, unsigned flags, int *ticket);
+
 /* Reading a JPEG file: the entropy-coded data of a baseline file Huffman-decoded ON THE DEVICE, so that a caller without libjpeg
  * gets the file's true quantised coefficients at every quality.  For each component the result is the grid of whole blocks
  * blocks_w x blocks_h of j2p_jpeg_info, block-major, 64 int16 in natural order — value for value what libjpeg's
@@ -987,6 +1035,9 @@ int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file,
  * capacity, out_size and the job's rules as there).  Bytes go in and bytes come out; no coefficient crosses the bus. */
 int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
                                size_t capacity, size_t *out_size, int *ticket);
+/* ... with the flags of j2p_batch_submit_jpeg_ex */
+int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                  size_t capacity, size_t *out_size, unsigned flags, int *ticket);
 
 #ifdef __cplusplus
 }

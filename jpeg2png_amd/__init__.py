@@ -109,6 +109,15 @@ class _CJpegInfo(ctypes.Structure):
                 ("restart_interval", ctypes.c_uint), ("intervals", ctypes.c_uint), ("scan_begin", ctypes.c_size_t), ("scan_end", ctypes.c_size_t)]
 
 
+J2P_JPEG_OPTIMIZE = 1    # j2p_*_ex flags: Huffman tables made for the image
+
+
+class _CEncodeStats(ctypes.Structure):
+    """j2p_encode_stats"""
+    _fields_ = [("dc0", ctypes.c_ulonglong * 256), ("ac0", ctypes.c_ulonglong * 256), ("dc1", ctypes.c_ulonglong * 256),
+                ("ac1", ctypes.c_ulonglong * 256), ("scan_bits", ctypes.c_ulonglong), ("stuffed_bytes", ctypes.c_ulonglong)]
+
+
 J2P_DECODE_SUBSEQUENCE_BITS, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX = 1024, 32, 65536
 J2P_DECODE_STATS_ROUNDS = 16
 
@@ -175,6 +184,8 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_jpeg", "j2p_entropy_encode", "j2p_batch_submit_jpeg",
     "j2p_jpeg_parse", "j2p_entropy_decode", "j2p_entropy_decode_ex", "j2p_solver_create_from_jpeg",
     "j2p_batch_submit_file", "j2p_batch_submit_file_jpeg",
+    "j2p_planes_to_jpeg_ex", "j2p_entropy_encode_ex", "j2p_batch_submit_jpeg_ex", "j2p_batch_submit_file_jpeg_ex",
+    "j2p_solver_output_scratch_bytes",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
@@ -366,6 +377,18 @@ def _bind(path):
                                            ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         lib.j2p_batch_submit_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_entropy_encode_ex"):
+        # (as above: an earlier commit's build makes no tables)
+        lib.j2p_planes_to_jpeg_ex.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint]
+        lib.j2p_entropy_encode_ex.argtypes = [ctypes.c_int, ctypes.POINTER(_CJpeg), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_void_p,
+                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint, ctypes.POINTER(_CEncodeStats)]
+        lib.j2p_batch_submit_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
+                                                 ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_batch_submit_file_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
+                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
+                                                      ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_entropy_decode_ex"):
         # (as above: an earlier commit's build does not read files)
         lib.j2p_jpeg_parse.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpegInfo)]
@@ -757,11 +780,14 @@ def _jpeg_bytes(call, guess):
     return buf[:size.value].tobytes()
 
 
-def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0):
+def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False):
     """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode): coefficients is a
     list of 1 or 3 int16 arrays [blocks_h, blocks_w, 64] in natural order — component 0's grid ceil(height / 8) x ceil(width / 8),
     the others' ceil of that over subsampling=(sx, sy) — every value in [-1023, 1023]; quant_tables: one per component, steps
-    1..255, the third equal to the second.  Byte for byte what libjpeg's jpeg_write_coefficients writes with its defaults."""
+    1..255, the third equal to the second.  Byte for byte what libjpeg's jpeg_write_coefficients writes with its defaults.
+    optimize=True: with Huffman tables made for these coefficients from symbol counts taken on the GPU (J2P_JPEG_OPTIMIZE) — byte
+    for byte libjpeg's file with optimize_coding (IJG 9d and later).  stats=True: (file, dict of the device's counts dc0, ac0, dc1,
+    ac1 — 256 each — scan_bits and stuffed_bytes)."""
     lib = load_library()
     n = len(coefficients)
     if n not in (1, 3):
@@ -778,7 +804,16 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
         arrays.append(a)
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
     total = sum(a.size for a in arrays)
-    return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
+    if not optimize and not stats:
+        return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
+    st = _CEncodeStats()
+    flags = J2P_JPEG_OPTIMIZE if optimize else 0
+    file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_ex(int(device), ctypes.byref(spec), ptrs, n, out, cap, size, flags,
+                                                                        ctypes.byref(st) if stats else None), 4096 + total // 4)
+    if not stats:
+        return file
+    return file, {"dc0": list(st.dc0), "ac0": list(st.ac0), "dc1": list(st.dc1), "ac1": list(st.ac1), "scan_bits": st.scan_bits,
+                  "stuffed_bytes": st.stuffed_bytes}
 
 
 def _file_bytes(data):
@@ -1084,14 +1119,16 @@ class Solver:
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
-    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=()):
+    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False):
         """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg):
         only the file comes down.  width x height: the image, cropped from the canvas's top left corner.  quality: libjpeg's
         tables for it (quality_tables), or quant_tables: one 64-entry table per component, steps 1..255, natural order, the third
         equal to the second.  subsampling=(sx, sy), 1 or 2 each: the sampling of components 1 and 2.  A solver of three channels
         gives a colour file, one of one channel a greyscale file; others=(solver, solver): this solver's channel 0 and the
         channel 0 of two more solvers (the separate solves of `-s`) give a colour file.  Whole-canvas solvers only.  Byte for
-        byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults."""
+        byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults.  optimize=True: with
+        Huffman tables made for the image, as entropy_encode(optimize=True) makes them (j2p_planes_to_jpeg_ex) — the same
+        coefficients in fewer bytes, for one more wait on the way."""
         solvers = [self] + list(others)
         if len(solvers) not in (1, 3):
             raise J2PError("jpeg: others= takes the two other solvers of a colour file")
@@ -1101,7 +1138,9 @@ class Solver:
             refs[c] = _CPlaneRef(solvers[c]._h, 0) if len(solvers) == 3 else _CPlaneRef(self._h, c)
         spec, _held = _c_jpeg(width, height, n, quality, quant_tables, subsampling)
         guess = 4096 + int(width) * int(height) * n // 4
-        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
+        if not optimize:
+            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
+        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_ex(refs, n, ctypes.byref(spec), out, cap, size, J2P_JPEG_OPTIMIZE), guess)
 
     def stream(self):
         """the hipStream_t the solver launches on (an integer address)"""
@@ -1225,6 +1264,13 @@ class Solver:
         n = ctypes.c_uint()
         _check(self._lib.j2p_solver_wide_footprint(self._h, int(c), ctypes.byref(n)))
         return bool(n.value)
+
+    def output_scratch_bytes(self):
+        """bytes of the block the output stage keeps for this solver (j2p_solver_output_scratch_bytes): a call that finds it
+        large enough allocates nothing"""
+        n = ctypes.c_size_t()
+        _check(self._lib.j2p_solver_output_scratch_bytes(self._h, ctypes.byref(n)))
+        return n.value
 
     def debug_option(self, option, value):
         """schedule switches (J2P_OPT_*): speed only, never results"""
@@ -1494,7 +1540,7 @@ def _job_output(job, want, planes, width, height):
 # back, what must stay alive until then, the C entry point's arguments for that output).
 
 def _fill_jpeg(job, jpeg, n, width, height):
-    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity"}:
+    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity", "optimize"}:
         raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
     if n not in (1, 3):
         raise J2PError("jpeg: three components or one")
@@ -1503,7 +1549,8 @@ def _fill_jpeg(job, jpeg, n, width, height):
     room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
     buffer, size = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
     job.out_w, job.out_h = int(width), int(height)
-    return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size))
+    flags = J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
+    return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
 
 
 def _fill_outputs(job, outputs, n, width, height):
@@ -1624,9 +1671,11 @@ def _job_record(job, planes, weight, pweight, iterations, want, tile_devices, ti
 def _entry_point(source, source_args, kind, output_args):
     """step 4 -> (the C entry point of an (input kind, output kind) pair, its arguments between the job and the ticket)"""
     if kind == "jpeg":
+        flags = output_args[-1]                     # (without flags the entry points that have none: the calls they always were)
+        ex, output_args = ("_ex", output_args) if flags else ("", output_args[:-1])
         if source == "file":
-            return "j2p_batch_submit_file_jpeg", source_args + output_args
-        return "j2p_batch_submit_jpeg", (source_args or (None,)) + output_args          # (samples NULL: the planes' coefficients)
+            return "j2p_batch_submit_file_jpeg" + ex, source_args + output_args
+        return "j2p_batch_submit_jpeg" + ex, (source_args or (None,)) + output_args     # (samples NULL: the planes' coefficients)
     if source != "planes":
         # (step 1 has refused the resized kinds; no outputs: the job's own form)
         return "j2p_batch_submit_" + source, source_args + (output_args or (0, None))
@@ -1661,10 +1710,10 @@ class Batch:
         outputs=, quant_tables=, jpeg=: file in and file out in one job); not with samples=, tile, nor a resized tensor outside
         outputs=.  A file the parser refuses raises J2PError (code J2P_EFORMAT / J2P_ENOTSUP) here; damage only its data
         shows fails the job in wait(), and no other job.
-        jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes} (with width and height; not
+        jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes, "optimize": bool} (with width and height; not
         with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
         JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
-        three planes.  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
+        three planes.  optimize: Huffman tables made for the image, as Solver.to_jpeg(optimize=True).  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
         reaches; a larger file fails the job with the size it needs in the message);
         samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
         out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit

@@ -44,15 +44,16 @@ struct Request {
         const j2p_jpeg *jpeg = nullptr;     // the file the job delivers, with where it goes:
         uint8_t *jpeg_out = nullptr;
         size_t jpeg_capacity = 0, *jpeg_size = nullptr;
+        unsigned jpeg_flags = 0;            // J2P_JPEG_*
         Request &resized(const j2p_resize *r) { resize = r; return *this; }
         Request &resampled(const j2p_resample *r) { resample = r; return *this; }
         // (no outputs, or an array that is not there, is the job's own output)
         Request &outputs(unsigned n, const j2p_output *o) { if(n && o) { nout = n, outs = o; } return *this; }
         Request &from_samples(const j2p_samples *m) { samples = m; return *this; }
         Request &from_file(const uint8_t *f, size_t size) { file = f, file_size = size; return *this; }
-        Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size)
+        Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size, unsigned flags)
         {
-                jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size;
+                jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size, jpeg_flags = flags;
                 return *this;
         }
 };
@@ -69,10 +70,12 @@ struct JpegOut {
         uint16_t tables[3][64];
         uint8_t *out = nullptr;
         size_t capacity = 0, *size = nullptr;
+        unsigned flags = 0;
         // from a request that validate_jpeg has passed: the tables travel with the job
         void set(const Request &q, unsigned nchannel)
         {
                 spec = *q.jpeg;
+                flags = q.jpeg_flags;
                 out = q.jpeg_out, capacity = q.jpeg_capacity, size = q.jpeg_size;
                 for(unsigned c = 0; c < nchannel; c++) {
                         memcpy(tables[c], q.jpeg->quant[c], sizeof(tables[c]));
@@ -288,7 +291,7 @@ int deliver_outputs(const Job &j, const j2p_job &d, const Band &band)
 
 int deliver_jpeg(const Job &j, const j2p_job &d, const Band &band)
 {
-        return j2p_planes_to_jpeg(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size);
+        return j2p_planes_to_jpeg_ex(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, j.jpeg.flags);
 }
 
 int deliver(const Job &j, const Band &band)
@@ -539,6 +542,7 @@ int validate_jpeg(const j2p_job &d, const Request &q)
         }
         if(d.tile) { return j2p_fail(J2P_EINVAL, "job: JPEG output of a row-tiled job is not supported"); }
         if(const char *why = j2p_jpeg_error(q.jpeg, d.nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+        if(const char *why = j2p_jpeg_flags_error(q.jpeg_flags)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
         if(q.jpeg->width != d.out_w || q.jpeg->height != d.out_h) {
                 return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", q.jpeg->width, q.jpeg->height, d.out_w, d.out_h);
         }
@@ -743,11 +747,17 @@ int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples
         return submit(b, job, Request().from_samples(samples).outputs(n, outs), ticket);
 }
 
+int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
+                             size_t *size, unsigned flags, int *ticket)
+{
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
+        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, flags), ticket);
+}
+
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
                           size_t *size, int *ticket)
 {
-        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size), ticket);
+        return j2p_batch_submit_jpeg_ex(b, job, samples, spec, out, capacity, size, 0, ticket);
 }
 
 int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, unsigned n, const j2p_output outs[], int *ticket)
@@ -756,12 +766,18 @@ int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file,
         return submit(b, job, Request().from_file(file, size).outputs(n, outs), ticket);
 }
 
-int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
-                               size_t capacity, size_t *out_size, int *ticket)
+int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                  size_t capacity, size_t *out_size, unsigned flags, int *ticket)
 {
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size), ticket);
+        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, flags), ticket);
+}
+
+int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                               size_t capacity, size_t *out_size, int *ticket)
+{
+        return j2p_batch_submit_file_jpeg_ex(b, job, file, size, spec, out, capacity, out_size, 0, ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

@@ -14,12 +14,13 @@
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
 #include "j2p_hip_host.h"
+#include "j2p_huffman.h"
 #include "j2p_codec_kernels.hip.h"
 #include "j2p_decode_kernels.hip.h"
 
 using namespace j2p;
 
-// ---- the JPEG file: k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_count, k_stuff_copy ----
+// ---- the JPEG file: k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_count, k_stuff_copy; k_entropy_histogram ----
 namespace {
 
 // Annex K.3 of the JPEG standard, as include/jpeg2png_amd.h states them: [0] the tables of component 0, [1] of the others
@@ -56,23 +57,51 @@ void huffman_codes(const uint8_t bits[16], const uint8_t *vals, unsigned *by_sym
                 code <<= 1;
         }
 }
-const HuffCodes &huffman_tables()
+// the four tables of a file, as its DHT segments hold them: DC0, AC0, DC1, AC1
+struct FileTables {
+        j2p_huff_table t[4];
+};
+HuffCodes huffman_codes_of(const FileTables &f)
 {
-        static const HuffCodes tables = [] {
-                HuffCodes h;
-                memset(&h, 0, sizeof(h));
+        HuffCodes h;
+        memset(&h, 0, sizeof(h));
+        for(int t = 0; t < 2; t++) {
+                // (a DC table made for an image holds no symbol above 11: k_entropy_histogram counts none)
+                unsigned dc[256] = {0};
+                huffman_codes(f.t[2 * t].bits, f.t[2 * t].vals, dc);
+                memcpy(h.dc[t], dc, sizeof(h.dc[t]));
+                huffman_codes(f.t[2 * t + 1].bits, f.t[2 * t + 1].vals, h.ac[t]);
+        }
+        return h;
+}
+// Annex K.3
+const FileTables &default_tables()
+{
+        static const FileTables tables = [] {
+                FileTables f;
+                memset(&f, 0, sizeof(f));
                 for(int t = 0; t < 2; t++) {
-                        huffman_codes(kDcBits[t], kDcVals, h.dc[t]);
-                        huffman_codes(kAcBits[t], kAcVals[t], h.ac[t]);
+                        memcpy(f.t[2 * t].bits, kDcBits[t], 16);
+                        memcpy(f.t[2 * t].vals, kDcVals, 12);
+                        f.t[2 * t].nvals = 12;
+                        memcpy(f.t[2 * t + 1].bits, kAcBits[t], 16);
+                        memcpy(f.t[2 * t + 1].vals, kAcVals[t], 162);
+                        f.t[2 * t + 1].nvals = 162;
                 }
-                return h;
+                return f;
         }();
         return tables;
 }
+const HuffCodes &huffman_tables()
+{
+        static const HuffCodes tables = huffman_codes_of(default_tables());
+        return tables;
+}
 
-// everything in front of the entropy-coded data; at most 623 bytes.  Returns their number.
+// everything in front of the entropy-coded data; at most 623 bytes (a table has at most 12 DC or 162 AC symbols, which
+// j2p_encode_scan checks of the ones it makes).  Returns their number.
 constexpr size_t kJpegHeaderMax = 640;
-size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, uint8_t *out)
+size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, uint8_t *out)
 {
         uint8_t *p = out;
         const auto segment = [&](uint8_t marker, size_t payload) {
@@ -104,17 +133,13 @@ size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, uint8_t *out)
                 *p++ = c == 0 && ncomp == 3 ? (uint8_t)((spec.sub_w << 4) | spec.sub_h) : 0x11;
                 *p++ = c ? 1 : 0;
         }
-        for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
-                segment(0xc4, 1 + 16 + 12);
-                *p++ = (uint8_t)t;
-                memcpy(p, kDcBits[t], 16);
-                memcpy(p + 16, kDcVals, 12);
-                p += 28;
-                segment(0xc4, 1 + 16 + 162);
-                *p++ = (uint8_t)(0x10 | t);
-                memcpy(p, kAcBits[t], 16);
-                memcpy(p + 16, kAcVals[t], 162);
-                p += 178;
+        for(unsigned k = 0; k < (ncomp == 3 ? 4u : 2u); k++) {
+                const j2p_huff_table &t = tables.t[k];
+                segment(0xc4, 1 + 16 + t.nvals);
+                *p++ = (uint8_t)(((k & 1u) << 4) | (k >> 1));
+                memcpy(p, t.bits, 16);
+                memcpy(p + 16, t.vals, t.nvals);
+                p += 16 + t.nvals;
         }
         segment(0xda, 1 + 2 * ncomp + 3);
         *p++ = (uint8_t)ncomp;
@@ -174,24 +199,59 @@ j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp)
         return g;
 }
 
+// The tables made for this image from the device's counts (hist: [table][12 DC + 256 AC], as k_entropy_histogram leaves them),
+// and the counts as the caller sees them
+static int tables_from_counts(const unsigned long long *hist, unsigned ncomp, FileTables &tables, j2p_encode_stats *stats)
+{
+        memset(&tables, 0, sizeof(tables));
+        for(unsigned k = 0; k < 4; k++) {
+                uint64_t count[256] = {0};
+                const unsigned long long *from = hist + (k >> 1) * 268 + (k & 1u ? 12 : 0);
+                for(unsigned s = 0; s < (k & 1u ? 256u : 12u); s++) { count[s] = from[s]; }
+                if(stats) {
+                        unsigned long long *to = k == 0 ? stats->dc0 : (k == 1 ? stats->ac0 : (k == 2 ? stats->dc1 : stats->ac1));
+                        for(unsigned s = 0; s < 256; s++) { to[s] = count[s]; }
+                }
+                if(k >= 2 && ncomp != 3) { continue; }
+                const int rc = j2p_huff_build(count, &tables.t[k]);
+                if(rc == J2P_HUFF_COUNT) {
+                        return j2p_fail(J2P_ENOTSUP, "jpeg: a symbol is coded more than %llu times: no optimised table for it", J2P_HUFF_COUNT_MAX);
+                }
+                if(rc != J2P_HUFF_OK) { return j2p_fail(J2P_ENOTSUP, "jpeg: an optimised code would be longer than %d bits before limiting", J2P_HUFF_TREE_MAX); }
+                if(tables.t[k].nvals > (k & 1u ? 162u : 12u)) { return j2p_fail(J2P_EINVAL, "jpeg: a coefficient is outside [-1023, 1023]"); }
+        }
+        return J2P_OK;
+}
+
 // The coder (j2p_internal.h: what memory and fill are).  The block's layout, each part aligned to 256 bytes:
 //   [coefficients per component][len: nslots u32][off: nslots u64][sums: tiles + 1 u64]              known from the spec
+//   [hist: 2 x 268 u64 — only when the symbols are counted]
 //   [stage: the stream, ceil(bits / 32) + 1 words][count: chunks u32][ffoff: chunks u64][sums]      known once the bits are
 //   [out: the stuffed bytes]                                                                        known once the FFs are
 // so the two totals are read back (8 bytes each, a wait each) and the block is asked for three times, the first two times
 // with a guess for what is not known yet; when it moved, what had been computed is computed again.  A second image of the
 // same size or smaller finds the block large enough at once.
+// J2P_JPEG_OPTIMIZE (or stats) puts k_entropy_histogram and a third read-back and wait, of the 2 x 268 counters, between the
+// coefficients and the lengths: the tables are made on the host (j2p_huffman.h) and this call's own HuffCodes go to the two
+// coding kernels.  The counts live on the host from then on: a block that moves has its coefficients and stages made again,
+// not its counts.  Without either, the launches, the layout and the bytes are what they were before the option existed.
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
-                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size)
+                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                    unsigned flags, j2p_encode_stats *stats)
 {
         ScanGeom g = scan_geometry(spec, ncomp);
-        const HuffCodes &codes = huffman_tables();
+        const bool optimise = (flags & J2P_JPEG_OPTIMIZE) != 0, counting = optimise || stats;
+        HuffCodes own_codes;
+        FileTables own_tables;
+        const HuffCodes *codes = &huffman_tables();
+        const FileTables *tables = &default_tables();
         const unsigned nslots = g.nslots, slot_tiles = (nslots + kScanTile - 1) / kScanTile;
         j2p_carve part;
         size_t coef_at[3];
         for(unsigned c = 0; c < ncomp; c++) { coef_at[c] = part(j2p_grid_bytes(g.bw[c], g.bh[c])); }
         const size_t coef_bytes = part.total;
         const size_t len_at = part((size_t)nslots * 4), off_at = part((size_t)nslots * 8), sums_at = part(((size_t)slot_tiles + 1) * 8);
+        const size_t hist_at = counting ? part(kHistogramEntries * 8) : 0;
         const size_t fixed = part.total;
         char *base = nullptr;
         const auto take = [&](size_t bytes, bool *moved) {
@@ -201,22 +261,42 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                 return (int)J2P_OK;
         };
         const auto at = [&](size_t offset) { return base + offset; };
-        // from the coefficients to the bit offsets
-        const auto lengths = [&] {
+        const unsigned per_workgroup = 4 * kEntropyIters, coding_grid = (nslots + per_workgroup - 1) / per_workgroup;
+        // the coefficients into the block
+        const auto coefficients = [&] {
                 int16_t *coef[3] = {nullptr, nullptr, nullptr};
                 for(unsigned c = 0; c < ncomp; c++) {
                         coef[c] = reinterpret_cast<int16_t *>(at(coef_at[c]));
                         g.coef[c] = coef[c];
                 }
                 fill(stream, coef);
-                const unsigned per_workgroup = 4 * kEntropyIters;
-                hipLaunchKernelGGL(k_entropy_lengths, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
-                                   reinterpret_cast<unsigned *>(at(len_at)));
+        };
+        // from the coefficients to the bit offsets
+        const auto lengths = [&] {
+                hipLaunchKernelGGL(k_entropy_lengths, dim3(coding_grid), dim3(256), 0, stream, g, *codes, reinterpret_cast<unsigned *>(at(len_at)));
                 queue_scan(stream, reinterpret_cast<unsigned *>(at(len_at)), nslots, reinterpret_cast<unsigned long long *>(at(sums_at)),
                            reinterpret_cast<unsigned long long *>(at(off_at)));
         };
         bool moved = false;
         if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }     // (a file is rarely an eighth of its coefficients)
+        coefficients();
+        if(stats) { memset(stats, 0, sizeof(*stats)); }
+        if(counting) {
+                unsigned long long hist[kHistogramEntries];
+                HIP_TRY(hipMemsetAsync(at(hist_at), 0, sizeof(hist), stream));
+                hipLaunchKernelGGL(k_entropy_histogram, dim3(coding_grid), dim3(256), 0, stream, g, reinterpret_cast<unsigned long long *>(at(hist_at)));
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(hist, at(hist_at), sizeof(hist), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                FileTables made;
+                if(const int rc = tables_from_counts(hist, ncomp, made, stats); optimise && rc != J2P_OK) { return rc; }
+                if(optimise) {
+                        own_tables = made;
+                        own_codes = huffman_codes_of(own_tables);
+                        tables = &own_tables;
+                        codes = &own_codes;
+                }
+        }
         lengths();
         unsigned long long bits = 0;
         HIP_TRY(hipMemcpyAsync(&bits, at(sums_at) + (size_t)slot_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
@@ -228,8 +308,7 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         // from the bit offsets to the stream and where its FF bytes are
         const auto pack = [&] {
                 (void)hipMemsetAsync(at(stage_at), 0, stage_words * 4, stream);
-                const unsigned per_workgroup = 4 * kEntropyIters;
-                hipLaunchKernelGGL(k_entropy_pack, dim3((nslots + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream, g, codes,
+                hipLaunchKernelGGL(k_entropy_pack, dim3(coding_grid), dim3(256), 0, stream, g, *codes,
                                    reinterpret_cast<const unsigned long long *>(at(off_at)), reinterpret_cast<unsigned *>(at(stage_at)));
                 hipLaunchKernelGGL(k_stuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes,
                                    nchunks, reinterpret_cast<unsigned *>(at(count_at)));
@@ -237,17 +316,25 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                            reinterpret_cast<unsigned long long *>(at(ffoff_at)));
         };
         if(const int rc = take(out_at + nbytes + nbytes / 16 + 256, &moved); rc != J2P_OK) { return rc; }
-        if(moved) { lengths(); }
+        if(moved) {
+                coefficients();
+                lengths();
+        }
         pack();
         unsigned long long ffs = 0;
         HIP_TRY(hipMemcpyAsync(&ffs, at(ffsums_at) + (size_t)chunk_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        if(stats) {
+                stats->scan_bits = bits;
+                stats->stuffed_bytes = ffs;
+        }
         uint8_t header[kJpegHeaderMax];
-        const size_t header_bytes = jpeg_header(spec, ncomp, header), data_bytes = nbytes + (size_t)ffs;
+        const size_t header_bytes = jpeg_header(spec, ncomp, *tables, header), data_bytes = nbytes + (size_t)ffs;
         *size = header_bytes + data_bytes + 2;
         if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
         if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
         if(moved) {
+                coefficients();
                 lengths();
                 pack();
         }
@@ -273,10 +360,11 @@ static int check_device(int device)
 
 extern "C" {
 
-int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
-                       size_t *size)
+int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                          size_t *size, unsigned flags, j2p_encode_stats *stats)
 {
         if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const char *why = j2p_jpeg_error(spec, ncomp)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, ncomp);
         size_t values[3] = {0, 0, 0};
@@ -314,11 +402,17 @@ int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const co
                 [&](hipStream_t st, int16_t *const coef[3]) {
                         for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
                 },
-                out_host, capacity, size);
+                out_host, capacity, size, flags, stats);
         (void)hipStreamSynchronize(stream);
         j2p_pool_give(device, block, block_bytes);
         (void)hipStreamDestroy(stream);
         return rc;
+}
+
+int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                       size_t *size)
+{
+        return j2p_entropy_encode_ex(device, spec, coef_host, ncomp, out_host, capacity, size, 0, nullptr);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // jpeg2png_amd — gfx950 device code of the JPEG codec's coder: quantised coefficients in device memory into the entropy-coded
-// data of a JPEG file (k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_*).  Included by j2p_codec.hip alone, in front of
+// data of a JPEG file (k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_*; k_entropy_histogram counts the symbols for
+// tables made for the image).  Included by j2p_codec.hip alone, in front of
 // j2p_decode_kernels.hip.h, which reuses the k_scan_* kernels for the way back.  It shares nothing with the output stage's
 // kernels (j2p_output_kernels.hip.h): k_quantise_blocks, which leaves the coefficients, lives there.  Compiled with the
 // same flags as every device unit.
@@ -164,6 +165,50 @@ __global__ __launch_bounds__(256) void k_entropy_lengths(ScanGeom g, HuffCodes h
 #pragma unroll
                 for(int d = 32; d >= 1; d >>= 1) { n += __shfl_xor(n, d); }
                 if(lane == 0) { len[first + it] = n; }
+        }
+}
+
+// ---- the symbol counts the optimised Huffman tables are made from (include/jpeg2png_amd.h: "Optimised Huffman tables") ----
+// k_entropy_lengths' walk without the tables: lane 0 counts its block's DC category, a non-zero lane its (run & 15, size)
+// symbol and its run >> 4 ZRLs, lane 63 the EOB of a block that ends in zeros.  Counts go to an LDS histogram of the
+// workgroup, [table][12 DC + 256 AC] like the tables' (a workgroup sees at most 64 positions of 64 symbols: 32 bits hold
+// them), one ds_add per lane, and behind the barrier every non-zero entry is added to hist[2][268], 64-bit counters in
+// device memory that the host zeroed.  Integers: the result does not depend on who comes first.
+// At high quality most lanes of a block hold a (0, s) symbol — a handful of addresses for 63 lanes, which an LDS atomic
+// takes one after the other.  It does not show: the walk costs what it costs k_entropy_lengths, and the forms that merge
+// equal lanes first (a ballot per bit of the entry number, the lowest lane adds the popcount) or sum the ZRLs over the
+// wavefront before counting them were measured slower (profiles/patches/histogram_merged_lanes.patch).
+constexpr unsigned kHistogramEntries = 2 * 268;
+
+__global__ __launch_bounds__(256) void k_entropy_histogram(ScanGeom g, unsigned long long *hist)
+{
+        __shared__ unsigned count[kHistogramEntries];
+        for(unsigned i = threadIdx.x; i < kHistogramEntries; i += 256) { count[i] = 0; }
+        __syncthreads();
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const unsigned first = (blockIdx.x * 4 + wave) * kEntropyIters;
+        for(unsigned it = 0; it < kEntropyIters && first + it < g.nslots; it++) {
+                unsigned t;
+                const int v = scan_value(g, first + it, lane, &t);
+                const unsigned long long nz = __ballot(lane > 0 && v != 0);
+                const unsigned a = (unsigned)(v < 0 ? -v : v);
+                const unsigned s = 32u - (unsigned)__clz((int)a);
+                unsigned *mine = count + t * 268u;      // (every index below stays under 268 whatever the coefficients hold)
+                if(lane == 0) {
+                        atomicAdd(&mine[s < 12u ? s : 11u], 1u);
+                } else if(v != 0) {
+                        const unsigned long long before = (nz | 1ull) & ((1ull << lane) - 1ull);
+                        const unsigned run = (unsigned)lane - 1u - (63u - (unsigned)__clzll((long long)before));
+                        atomicAdd(&mine[12u + ((((run & 15u) << 4) | s) & 255u)], 1u);
+                        if(run >> 4) { atomicAdd(&mine[12u + 0xf0u], run >> 4); }
+                } else if(lane == 63) {
+                        atomicAdd(&mine[12u], 1u);
+                }
+        }
+        __syncthreads();
+        for(unsigned i = threadIdx.x; i < kHistogramEntries; i += 256) {
+                if(const unsigned n = count[i]) { atomicAdd(&hist[i], (unsigned long long)n); }
         }
 }
 

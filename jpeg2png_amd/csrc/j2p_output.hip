@@ -722,9 +722,11 @@ int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub
 }
 
 // the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_scan), which is the first solver's scratch
-int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
+int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
+                          unsigned flags)
 {
         if(!planes || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const char *why = j2p_jpeg_error(spec, nplane)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, nplane);
         // every check of every plane, before anything is queued
@@ -750,7 +752,12 @@ int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_
                 [&](hipStream_t st, int16_t *const coef[3]) {
                         for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
                 },
-                out_host, capacity, size);
+                out_host, capacity, size, flags);
+}
+
+int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
+{
+        return j2p_planes_to_jpeg_ex(planes, nplane, spec, out_host, capacity, size, 0);
 }
 
 }  // extern "C"

@@ -1419,6 +1419,13 @@ int j2p_solver_arena_bytes(const j2p_solver *s, size_t *bytes)
         return J2P_OK;
 }
 
+int j2p_solver_output_scratch_bytes(const j2p_solver *s, size_t *bytes)
+{
+        if(!s || !bytes) { return j2p_fail(J2P_EINVAL, "j2p_solver_output_scratch_bytes: bad argument"); }
+        *bytes = s->out_scratch_bytes;
+        return J2P_OK;
+}
+
 int j2p_solver_wide_footprint(const j2p_solver *s, unsigned c, unsigned *on)
 {
         if(!s || !on || c >= s->nch) { return j2p_fail(J2P_EINVAL, "j2p_solver_wide_footprint: bad argument"); }
