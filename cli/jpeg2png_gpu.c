@@ -7,7 +7,7 @@
  * What moves to the GPU: decode_coefficients + unbox (jpeg.c:83-92, box.c:5), the whole
  * solver, the luma fix-up and the YCbCr->RGB conversion (jpeg2png.c:156-159, png.c:37-62),
  * so that only int16 coefficients go up and only RGB bytes come down (with -j: only int16 coefficients, which
- * libjpeg Huffman-codes into a JPEG file).
+ * libjpeg Huffman-codes into a JPEG file; with -P: only the PNG file, and libpng is not used).
  *
  * Differences from the reference, on purpose:
  *   -t threads   = number of input files in flight (host threads reading / writing files; each file's GPU work
@@ -27,6 +27,9 @@
  *                  projection constrains, compute.c:351-359), taken in float on the GPU (j2p_planes_to_coefficients_sub)
  *   -O, --optimize = with -j: Huffman tables made for the image instead of the standard's (libjpeg's optimize_coding; with -e the
  *                  GPU counts the symbols, J2P_JPEG_OPTIMIZE) — the same coefficients in a smaller file, and the same file either way
+ *   -P, --png-on-gpu = the PNG is filtered and deflated on the GPU (j2p_batch_submit_png; include/jpeg2png_amd.h, "The PNG file") and
+ *                  written as it comes down: no libpng, and no samples on the bus.  The same pixels as without it, in another (usually
+ *                  somewhat larger) file; with -1, -g, -z, -s and -d; not with -j, not for row-tiled images
  * Messages and exit codes follow the reference ("jpeg2png: <message>", EXIT_FAILURE).
  */
 #define _POSIX_C_SOURCE 200809L
@@ -352,6 +355,7 @@ struct options {
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
         bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
+        bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
         bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
@@ -492,7 +496,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         job.out_quant[c] = out_quant[c];
                         job.out_coef[c] = out_coef[c];
                 }
-        } else {
+        } else if(!o->png_on_gpu) {
                 job.out_bits = o->png_bits;
                 size_t bytes = (size_t)job.out_w * job.out_h * jp.n * (o->png_bits / 8);
                 pixels = malloc(bytes);
@@ -528,6 +532,27 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         } else {
                                 gpu_check(j2p_batch_submit_jpeg_ex(batch, &job, NULL, &spec, file, capacity, &file_bytes, flags, &ticket));
                         }
+                        const int rc = j2p_batch_wait(batch, ticket);
+                        if(rc != J2P_ESPACE || attempt) {
+                                gpu_check(rc);
+                                break;
+                        }
+                        free(file);
+                        capacity = file_bytes;
+                }
+        } else if(o->png_on_gpu) {
+                /* -P: the samples stay on the GPU and the finished file comes down.  Room for three quarters of a byte per byte of
+                 * samples at first; a file that needs more says how much, and the job runs again */
+                const j2p_png spec = {job.out_w, job.out_h, o->png_bits, J2P_PNG_FILTER_ADAPTIVE, 0, 0};
+                job.out_bits = 0;
+                job.out_rgb = NULL;
+                job.tile = 0;           /* (a row-tiled job has no file output) */
+                size_t capacity = 4096 + (size_t)job.out_w * job.out_h * jp.n * (o->png_bits / 8) / 4 * 3;
+                for(int attempt = 0;; attempt++) {
+                        file = malloc(capacity);
+                        if(!file) { die("could not allocate image data"); }
+                        if(jp.file) { gpu_check(j2p_batch_submit_file_png(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket)); }
+                        else { gpu_check(j2p_batch_submit_png(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket)); }
                         const int rc = j2p_batch_wait(batch, ticket);
                         if(rc != J2P_ESPACE || attempt) {
                                 gpu_check(rc);
@@ -608,6 +633,8 @@ static void usage(void)
                "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
                "  -O, --optimize               with -j: Huffman tables made for the image, a smaller file of the same\n"
                "                               coefficients (with -e the GPU counts the symbols; the same bytes either way)\n"
+               "  -P, --png-on-gpu             the GPU also filters and deflates the PNG and only the file comes down: the same\n"
+               "                               pixels in another, usually somewhat larger file; not with -j, not for row-tiled images\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -627,15 +654,16 @@ int main(int argc, char **argv)
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
-                {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'}, {NULL, 0, NULL, 0}};
+                {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'},
+                {"png-on-gpu", no_argument, NULL, 'P'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
-                            .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
+                            .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .png_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edO", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOP", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -655,6 +683,7 @@ int main(int argc, char **argv)
                 case 'e': o.encode_on_gpu = true; break;
                 case 'd': o.decode_on_gpu = true; break;
                 case 'O': o.optimize = true; break;
+                case 'P': o.png_on_gpu = true; break;
                 default: help = true; break;
                 }
         }
@@ -709,6 +738,7 @@ int main(int argc, char **argv)
         }
         if(o.encode_on_gpu && !j_arg) { die("-e needs JPEG output (-j)"); }
         if(o.optimize && !j_arg) { die("-O needs JPEG output (-j)"); }
+        if(o.png_on_gpu && j_arg) { die("-P writes a PNG: not with JPEG output (-j)"); }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);
         unsigned threads = cores > 0 ? (unsigned)cores : 1u;

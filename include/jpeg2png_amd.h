@@ -1039,6 +1039,98 @@ int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *
 int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
                                   size_t capacity, size_t *out_size, unsigned flags, int *ticket);
 
+/* The PNG file: the image's samples filtered and deflated ON THE DEVICE, so that a complete PNG file comes down instead of 3 or 6 bytes
+ * per pixel for a host library to deflate on one core.  Every byte of the file is defined here; tests/png_cases.py restates it.  This is
+ * the definition.
+ *
+ * 1. Samples.  width x height pixels (1..2^24 each) of `channels` = 3 (RGB) or 1 (greyscale) samples of `bits` = 8 or 16 bits, rows from
+ *    the top, a row's pixels from the left, a pixel's samples interleaved, a 16-bit sample's high byte first: rb = width * bpp bytes a
+ *    row with bpp = channels * bits / 8 (3, 6, 1 or 2).  From solved planes they are exactly the bytes j2p_planes_to_rgb (three planes)
+ *    or j2p_planes_to_grey (one) deliver for the same width, height and bits — the same kernel writes them, into device memory.
+ * 2. Filtering.  Every row becomes a filter-type byte f and rb filtered bytes: byte x of the row, v, minus a prediction, mod 256.  With a
+ *    the row's byte x - bpp, b the byte x of the row above and c that row's byte x - bpp, each 0 where there is none (x < bpp, row 0) —
+ *    unfiltered bytes all, so that rows do not depend on each other's filtering:
+ *      f = 0 (none) 0;  1 (sub) a;  2 (up) b;  3 (average) floor((a + b) / 2);
+ *      4 (Paeth) with p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|: a if pa <= pb and pa <= pc, else b if pb <= pc, else c.
+ *    filter = 0..4 uses that f for every row.  filter = J2P_PNG_FILTER_ADAPTIVE chooses per row, as libpng's heuristic does: the f whose
+ *    rb filtered bytes have the smallest sum of |byte taken as signed| (byte below 128: itself, otherwise 256 - byte); on a tie the
+ *    lowest f.  The filtered stream is the rows one after the other, height * (rb + 1) bytes.
+ * 3. Tokens.  The stream is cut into deflate blocks of block_bytes bytes (0: J2P_PNG_BLOCK_BYTES; any value J2P_PNG_SIZE_MIN..MAX; the
+ *    last block holds the rest; at most J2P_PNG_BLOCKS_MAX blocks, J2P_EINVAL beyond).  Within a block, byte i is "same" when it is not
+ *    the block's first and equals byte i - 1.  A maximal stretch of same bytes, L of them, is cut into pieces of 258 counted from its
+ *    start (the last piece holds the rest).  A piece of 3 or more bytes is ONE match of its length at distance 1, emitted at its first
+ *    position; a piece of 1 or 2 bytes is that many literals; every byte that is not same is a literal.  There are no other matches.
+ *    (zlib's Z_RLE idea: a function of position that a scan evaluates, and what keeps flat areas from costing a bit per byte.)
+ * 4. Coding (RFC 1951).  Each block is one dynamic-Huffman block.  Symbols: literals 0..255, EOB 256 (counted once), a match's length
+ *    as the standard's symbol 257..285 with its extra bits.  Code lengths from the block's own counts, at most 15 bits:
+ *      a. Huffman's algorithm with two queues over the symbols in use: the leaves by count ascending, the nodes in the order they were
+ *         made; the two smallest heads are joined, a leaf before a node of the same weight.  bits[n]: the leaves at depth n.
+ *      b. For i from the deepest level down to 16, while bits[i] > 0: j = i - 2, lowered while bits[j] == 0; bits[i] -= 2,
+ *         bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1.
+ *      c. The lengths are dealt out, shortest first, to the symbols by count descending, then symbol value ascending.
+ *      d. Codes are canonical: in order of length, within a length in order of symbol value, consecutive (RFC 1951 3.2.2).
+ *    A block always has two symbols or more (a literal and EOB); with exactly two, each has one bit.  Distances: HDIST = 0, ONE distance
+ *    code, for distance 1 — of length 1 (the code `0`) where the block has a match, of length 0 where it has none; a match is its length
+ *    code, the extra bits, and that one bit.  The header: BFINAL, BTYPE = 2, HLIT = (the highest symbol in use) - 256, HDIST = 0, HCLEN,
+ *    then the lengths of the HLIT + 257 literal/length symbols and of the distance code as ONE sequence in the code-length code: a run
+ *    of n zeros is 18s (of 138, while 11 or more are left — the last of what is left), then one 17 (3..10) or up to two 0s; a run of n
+ *    equal non-zero lengths is the length once, then 16s (of 6, while 3 or more are left — the last of what is left), then the length
+ *    for the one or two left.  The code-length code comes from the counts of those symbols by a. - d. with the limit 7 (level 8 in b.);
+ *    HCLEN + 4 is the position of the last symbol in use in the standard's order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, at
+ *    least 4.  After the header the tokens in order, then EOB.  Every block but the last is followed by an empty stored block — three
+ *    zero bits, zero bits up to the byte boundary, 00 00 FF FF — so that every block starts on a byte boundary and inflates on its own
+ *    (no match reaches back across a block's first byte); the last block has BFINAL set and is followed by zero bits up to the byte
+ *    boundary.
+ * 5. Container.  The zlib stream: 78 01, the blocks, the Adler-32 of the filtered stream, high byte first.  It is cut into IDAT chunks
+ *    of idat_bytes bytes of data (0: J2P_PNG_IDAT_BYTES; J2P_PNG_SIZE_MIN..MAX; the last holds the rest).  A chunk: the data's length
+ *    (32 bits, high byte first), the type, the data, the CRC-32 of type and data.  The file: 89 50 4E 47 0D 0A 1A 0A; IHDR — width,
+ *    height (32 bits each), bits, colour type 2 (RGB) or 0 (greyscale), 0, 0, 0; the IDAT chunks; IEND.  No other chunk.
+ *
+ * How it is made.  The rows are filtered, and every block's symbols counted, on the device; the counts come down (288 words a block, a
+ * wait), the host makes every block's code and header (not quadratic in the alphabet) and knows every size from then on — the file's
+ * too, so J2P_ESPACE is answered before anything is coded; then the blocks are packed, the stream is laid into its chunks and their
+ * CRCs are taken on the device, and the file comes down (a second wait).  Output contract as for "The JPEG file": *size is set once it
+ * is known; with too little capacity — out_host may then be NULL — nothing is written and the call returns J2P_ESPACE. */
+#define J2P_PNG_FILTER_ADAPTIVE (-1)
+#define J2P_PNG_BLOCK_BYTES 65536u
+#define J2P_PNG_IDAT_BYTES 8192u
+#define J2P_PNG_SIZE_MIN 16u
+#define J2P_PNG_SIZE_MAX (1u << 24)
+#define J2P_PNG_SIDE_MAX (1u << 24)
+#define J2P_PNG_BLOCKS_MAX (1u << 20)
+typedef struct j2p_png {
+        unsigned width, height, bits;
+        int filter;                        /* 0..4: that filter for every row; J2P_PNG_FILTER_ADAPTIVE: chosen per row */
+        unsigned block_bytes, idat_bytes;  /* 0: the defaults */
+} j2p_png;
+/* What the coder saw of one file (stats may be NULL): rows per filter type, deflate blocks, tokens by kind, the bytes of the zlib stream
+ * and the Adler-32 of the filtered stream.  Complete once the counts have been read back, also when the call then fails with J2P_ESPACE. */
+typedef struct j2p_png_stats {
+        unsigned long long rows[5];
+        unsigned long long blocks, literals, matches, stream_bytes;
+        unsigned adler;
+} j2p_png_stats;
+/* The current iterate of nplane = 3 (RGB) or 1 (greyscale) (solver, channel) pairs as that file.  planes[] may be one joint solver three
+ * times or three `-s` solvers on one device.  Whole-canvas solvers only (a band solver: J2P_ESTATE); the argument checks of
+ * j2p_planes_to_rgb / j2p_planes_to_grey apply.  Device memory is the scratch of planes[0].solver: a second call of the same size
+ * allocates nothing.  Synchronises twice, as said above. */
+int j2p_planes_to_png(const j2p_plane_ref planes[], unsigned nplane, const j2p_png *spec, uint8_t *out_host, size_t capacity, size_t *size);
+/* The same coder on the caller's samples (host memory, item 1's layout) with no solver: for pixels from anywhere, and what the directed
+ * tests use.  Device memory comes from the library's pool. */
+int j2p_png_encode(int device, const j2p_png *spec, const uint8_t *samples_host, unsigned channels, uint8_t *out_host, size_t capacity,
+                   size_t *size, j2p_png_stats *stats);
+/* A batch job that delivers the file (j2p_planes_to_png on the worker): *spec is copied and travels next to the job (j2p_job keeps its
+ * layout); out / size must stay valid until j2p_batch_wait, after which *size is the file's size — also when the job failed with
+ * J2P_ESPACE.  job->out_bits must be 0, out_coef[0] NULL and out_tensor.data NULL; not with `tile`; spec->width and height must equal
+ * job->out_w and out_h; the job has 1 or 3 channels (J2P_EINVAL at submit otherwise, before any device work, and no ticket is given).
+ * samples: NULL, or as for j2p_batch_submit_samples.  out_planes is still honoured. */
+int j2p_batch_submit_png(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_png *spec, uint8_t *out, size_t capacity,
+                         size_t *size, int *ticket);
+/* File in and file out in one job: the solvers from the JPEG `file` as for j2p_batch_submit_file, the result as the PNG file above.
+ * Bytes go in and bytes come out; neither coefficients nor samples cross the bus. */
+int j2p_batch_submit_file_png(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_png *spec, uint8_t *out,
+                              size_t capacity, size_t *out_size, int *ticket);
+
 #ifdef __cplusplus
 }
 #endif

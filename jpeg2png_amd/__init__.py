@@ -118,6 +118,22 @@ class _CEncodeStats(ctypes.Structure):
                 ("ac1", ctypes.c_ulonglong * 256), ("scan_bits", ctypes.c_ulonglong), ("stuffed_bytes", ctypes.c_ulonglong)]
 
 
+class _CPng(ctypes.Structure):
+    """j2p_png: the image, the filter and the block sizes of a PNG file made on the device"""
+    _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("bits", ctypes.c_uint), ("filter", ctypes.c_int),
+                ("block_bytes", ctypes.c_uint), ("idat_bytes", ctypes.c_uint)]
+
+
+class _CPngStats(ctypes.Structure):
+    """j2p_png_stats"""
+    _fields_ = [("rows", ctypes.c_ulonglong * 5), ("blocks", ctypes.c_ulonglong), ("literals", ctypes.c_ulonglong),
+                ("matches", ctypes.c_ulonglong), ("stream_bytes", ctypes.c_ulonglong), ("adler", ctypes.c_uint)]
+
+
+J2P_PNG_FILTER_ADAPTIVE = -1
+J2P_PNG_BLOCK_BYTES, J2P_PNG_IDAT_BYTES, J2P_PNG_SIZE_MIN, J2P_PNG_SIZE_MAX = 65536, 8192, 16, 1 << 24
+PNG_FILTERS = {None: -1, "adaptive": -1, "none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4}
+
 J2P_DECODE_SUBSEQUENCE_BITS, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX = 1024, 32, 65536
 J2P_DECODE_STATS_ROUNDS = 16
 
@@ -186,6 +202,7 @@ C_ABI_SYMBOLS = [
     "j2p_batch_submit_file", "j2p_batch_submit_file_jpeg",
     "j2p_planes_to_jpeg_ex", "j2p_entropy_encode_ex", "j2p_batch_submit_jpeg_ex", "j2p_batch_submit_file_jpeg_ex",
     "j2p_solver_output_scratch_bytes",
+    "j2p_planes_to_png", "j2p_png_encode", "j2p_batch_submit_png", "j2p_batch_submit_file_png",
 ]
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
@@ -389,6 +406,16 @@ def _bind(path):
         lib.j2p_batch_submit_file_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
                                                       ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_png_encode"):
+        # (as above: an earlier commit's build writes no PNG)
+        lib.j2p_planes_to_png.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CPng), ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_size_t)]
+        lib.j2p_png_encode.argtypes = [ctypes.c_int, ctypes.POINTER(_CPng), ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_CPngStats)]
+        lib.j2p_batch_submit_png.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CPng), ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_batch_submit_file_png.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CPng),
+                                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_entropy_decode_ex"):
         # (as above: an earlier commit's build does not read files)
         lib.j2p_jpeg_parse.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpegInfo)]
@@ -816,6 +843,47 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
                   "stuffed_bytes": st.stuffed_bytes}
 
 
+def _c_png(width, height, bits=8, filter=None, block_bytes=0, idat_bytes=0):
+    """j2p_png of a file's keywords: filter None or "adaptive" (chosen per row), 0..4 or "none", "sub", "up", "average", "paeth"
+    (that one for every row); block_bytes, idat_bytes: 0 for the defaults"""
+    if width is None or height is None or int(width) < 1 or int(height) < 1:
+        raise J2PError("png: needs width and height")
+    if isinstance(filter, str) or filter is None:
+        if filter not in PNG_FILTERS:
+            raise J2PError(f"png: unknown filter {filter!r}")
+        filter = PNG_FILTERS[filter]
+    return _CPng(int(width), int(height), int(bits), int(filter), int(block_bytes), int(idat_bytes))
+
+
+def png_encode(samples, bits=8, filter=None, block_bytes=0, idat_bytes=0, device=0, stats=False):
+    """a PNG file (bytes) from samples, filtered and deflated on the GPU (j2p_png_encode): samples is [height, width, 3] (RGB) or
+    [height, width] (greyscale), uint8 for bits=8 and uint16 for bits=16 (written high byte first, as PNG wants them).  filter: None
+    chooses per row by libpng's heuristic, 0..4 (or "none", "sub", "up", "average", "paeth") uses one for every row.  block_bytes: the
+    filtered bytes per deflate block, idat_bytes: the data bytes per IDAT chunk; 0 for the defaults, 16..2^24 otherwise.  Every byte
+    is defined in include/jpeg2png_amd.h, "The PNG file".  stats=True: (file, dict of rows per filter type, blocks, literals,
+    matches, stream_bytes and adler)."""
+    lib = load_library()
+    a = np.asarray(samples)
+    if int(bits) not in (8, 16) or a.dtype != (np.uint8 if int(bits) == 8 else np.uint16):
+        raise J2PError("png: uint8 samples with bits=8, uint16 samples with bits=16")
+    if a.ndim == 2:
+        channels = 1
+    elif a.ndim == 3 and a.shape[2] in (1, 3):
+        channels = a.shape[2]
+    else:
+        raise J2PError(f"png: samples of shape {a.shape}: [height, width, 3] or [height, width]")
+    height, width = a.shape[:2]
+    a = np.ascontiguousarray(a.astype(">u2") if int(bits) == 16 else a)
+    spec = _c_png(width, height, bits, filter, block_bytes, idat_bytes)
+    st = _CPngStats()
+    file = _jpeg_bytes(lambda out, cap, size: lib.j2p_png_encode(int(device), ctypes.byref(spec), a.ctypes.data, channels, out, cap, size,
+                                                                 ctypes.byref(st) if stats else None), 4096 + a.nbytes * 3 // 4)
+    if not stats:
+        return file
+    return file, {"rows": list(st.rows), "blocks": st.blocks, "literals": st.literals, "matches": st.matches, "stream_bytes": st.stream_bytes,
+                  "adler": st.adler}
+
+
 def _file_bytes(data):
     """(address, size, what keeps it alive) of a JPEG file given as bytes-like host data, or as a 1-D uint8 torch tensor in device
     memory, which the library reads in place"""
@@ -1142,6 +1210,24 @@ class Solver:
             return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
         return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_ex(refs, n, ctypes.byref(spec), out, cap, size, J2P_JPEG_OPTIMIZE), guess)
 
+    def to_png(self, width, height, bits=8, filter=None, others=(), block_bytes=0, idat_bytes=0):
+        """the current iterate as a complete PNG file (bytes), converted to samples, filtered AND deflated on the GPU
+        (j2p_planes_to_png): only the file comes down.  width x height: the image, cropped from the canvas's top left corner; bits 8
+        or 16.  A solver of three channels gives an RGB file, one of one channel a greyscale file; others=(solver, solver): this
+        solver's channel 0 and the channel 0 of two more solvers (the separate solves of `-s`) give an RGB file.  Whole-canvas
+        solvers only.  The pixels are the bytes of j2p_planes_to_rgb / j2p_planes_to_grey; filter, block_bytes and idat_bytes as for
+        png_encode, whose file of those bytes this is."""
+        solvers = [self] + list(others)
+        if len(solvers) not in (1, 3):
+            raise J2PError("png: others= takes the two other solvers of an RGB file")
+        n = 3 if len(solvers) == 3 else self.nch
+        refs = (_CPlaneRef * 3)()
+        for c in range(min(n, 3)):
+            refs[c] = _CPlaneRef(solvers[c]._h, 0) if len(solvers) == 3 else _CPlaneRef(self._h, c)
+        spec = _c_png(width, height, bits, filter, block_bytes, idat_bytes)
+        guess = 4096 + int(width) * int(height) * n * (int(bits) // 8) * 3 // 4
+        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_png(refs, n, ctypes.byref(spec), out, cap, size), guess)
+
     def stream(self):
         """the hipStream_t the solver launches on (an integer address)"""
         p = ctypes.c_void_p()
@@ -1454,7 +1540,7 @@ class _JpegResult:
 
 # the keywords of Batch.submit that decide a job's output form; resized: one of out_width / out_height / box / filter is given
 _Wanted = collections.namedtuple("_Wanted", "separate tile bits out quant_tables subsampling tensor layout scale bias out_width out_height box filter outputs "
-                                            "jpeg resized")
+                                            "jpeg resized png")
 
 
 def _torch_has_finished(device):
@@ -1509,6 +1595,11 @@ def _job_output(job, want, planes, width, height):
                 want.tile or want.out is not None:
             raise J2PError("job: jpeg= excludes bits, quant_tables, subsampling, tensor=, outputs=, out and tile")
         filled = ("jpeg",) + _fill_jpeg(job, want.jpeg, n, width, height)
+    if want.png is not None:
+        if want.jpeg is not None or want.bits or want.quant_tables is not None or want.subsampling is not None or want.tensor is not None or \
+                want.outputs is not None or want.tile or want.out is not None:
+            raise J2PError("job: png= excludes jpeg=, bits, quant_tables, subsampling, tensor=, outputs=, out and tile")
+        filled = ("png",) + _fill_png(job, want.png, n, width, height)
     if want.outputs is not None:
         if want.tensor is not None or want.bits or want.quant_tables is not None or want.subsampling is not None or want.tile:
             raise J2PError("job: outputs= excludes tensor=, bits, quant_tables and tile")
@@ -1527,7 +1618,7 @@ def _job_output(job, want, planes, width, height):
         return (kind,) + _fill_tensor(job, want, resize, n, width, height)
     if want.layout != "chw" or want.scale is not None or want.bias is not None:
         raise J2PError("job: layout, scale and bias belong to tensor output (tensor=)")
-    if want.jpeg is not None:
+    if want.jpeg is not None or want.png is not None:
         return filled
     if want.quant_tables is not None:
         return ("own",) + _fill_coefficients(job, want, n, width, height)
@@ -1551,6 +1642,19 @@ def _fill_jpeg(job, jpeg, n, width, height):
     job.out_w, job.out_h = int(width), int(height)
     flags = J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
     return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
+
+
+def _fill_png(job, png, n, width, height):
+    if not isinstance(png, dict) or set(png) - {"bits", "filter", "block_bytes", "idat_bytes", "capacity"}:
+        raise J2PError("job: png= is a dict of bits, filter, block_bytes, idat_bytes and capacity")
+    if n not in (1, 3):
+        raise J2PError("png: three planes (RGB) or one (greyscale)")
+    cpng = _c_png(width, height, png.get("bits", 8), png.get("filter"), png.get("block_bytes", 0), png.get("idat_bytes", 0))
+    # (room for samples that do not compress at all: 9 bits a byte at most, and the framing)
+    room = 4096 + (int(width) * n * (cpng.bits // 8 or 1) + 1) * int(height) * 5 // 4
+    buffer, size = np.empty(int(png.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
+    job.out_w, job.out_h = int(width), int(height)
+    return _JpegResult(buffer, size), [cpng], (ctypes.byref(cpng), buffer.ctypes.data, buffer.size, ctypes.byref(size))
 
 
 def _fill_outputs(job, outputs, n, width, height):
@@ -1676,6 +1780,10 @@ def _entry_point(source, source_args, kind, output_args):
         if source == "file":
             return "j2p_batch_submit_file_jpeg" + ex, source_args + output_args
         return "j2p_batch_submit_jpeg" + ex, (source_args or (None,)) + output_args     # (samples NULL: the planes' coefficients)
+    if kind == "png":
+        if source == "file":
+            return "j2p_batch_submit_file_png", source_args + output_args
+        return "j2p_batch_submit_png", (source_args or (None,)) + output_args           # (samples NULL: the planes' coefficients)
     if source != "planes":
         # (step 1 has refused the resized kinds; no outputs: the job's own form)
         return "j2p_batch_submit_" + source, source_args + (output_args or (0, None))
@@ -1702,8 +1810,13 @@ class Batch:
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None, jpeg=None, file=None):
-        """file=bytes or a 1-D uint8 torch tensor (on a GPU of the batch: read in place, and the job runs there): the job's solvers
+               samples=None, jpeg=None, file=None, png=None):
+        """png={"bits": 8 or 16, "filter": None or 0..4 or a name, "block_bytes": n, "idat_bytes": n, "capacity": bytes} (with width and
+        height; not with jpeg=, bits, quant_tables, tensor=, outputs= or tile; samples= and file= are allowed): wait() returns the image
+        as a complete PNG file (bytes) that the worker converted, filtered and deflated on its GPU (j2p_batch_submit_png,
+        Solver.to_png) — one or three planes.  capacity: room for the file (default: 5/4 of the filtered samples, which no image
+        reaches; a larger file fails the job with the size it needs in the message);
+        file=bytes or a 1-D uint8 torch tensor (on a GPU of the batch: read in place, and the job runs there): the job's solvers
         are made from that baseline JPEG file, Huffman-decoded on the worker's GPU (j2p_batch_submit_file, Solver.from_jpeg) —
         planes may be None (all of the file's components at the file's sampling) or Plane-likes with data=None, as
         jpeg_header(file)["planes"] are; width and height default to the file's.  Every output form is available (bits, tensor=,
@@ -1743,7 +1856,7 @@ class Batch:
         thread whenever n more iterations of one of the job's solves have finished (the CLI's progress bar, jpeg2png.c:449-452)"""
         resized = filter is not None or out_width is not None or out_height is not None or box is not None
         want = _Wanted(separate, tile, bits, out, quant_tables, subsampling, tensor, layout, scale, bias, out_width, out_height, box, filter, outputs,
-                       jpeg, resized)
+                       jpeg, resized, png)
         source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized)
         job = _CJob()
         kind, result, filled, output_args = _job_output(job, want, planes, width, height)

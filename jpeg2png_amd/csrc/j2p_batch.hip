@@ -45,6 +45,9 @@ struct Request {
         uint8_t *jpeg_out = nullptr;
         size_t jpeg_capacity = 0, *jpeg_size = nullptr;
         unsigned jpeg_flags = 0;            // J2P_JPEG_*
+        const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
+        uint8_t *png_out = nullptr;
+        size_t png_capacity = 0, *png_size = nullptr;
         Request &resized(const j2p_resize *r) { resize = r; return *this; }
         Request &resampled(const j2p_resample *r) { resample = r; return *this; }
         // (no outputs, or an array that is not there, is the job's own output)
@@ -56,13 +59,19 @@ struct Request {
                 jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size, jpeg_flags = flags;
                 return *this;
         }
+        Request &png_to(const j2p_png *spec, uint8_t *out, size_t capacity, size_t *size)
+        {
+                png = spec, png_out = out, png_capacity = capacity, png_size = size;
+                return *this;
+        }
 };
 
 // what a job's solvers are made from: planes[].data / fdata, Job::samples, or Job::file
 enum class In { planes, samples, file };
 // what becomes of the solve: the job's own out_* fields (samples, coefficients or out_tensor's rows, and out_planes), out_tensor
-// filled through Job::resize or Job::resample, Job::outputs, or Job::jpeg.  out_planes come down after every form without out_bits.
-enum class Out { own, resized, resampled, outputs, jpeg };
+// filled through Job::resize or Job::resample, Job::outputs, Job::jpeg or Job::png.  out_planes come down after every form without
+// out_bits.
+enum class Out { own, resized, resampled, outputs, jpeg, png };
 
 // where the file of an Out::jpeg job goes; spec.quant[] point into tables[] (so a JpegOut stays where it was set)
 struct JpegOut {
@@ -84,6 +93,13 @@ struct JpegOut {
         }
 };
 
+// where the file of an Out::png job goes
+struct PngOut {
+        j2p_png spec = {0, 0, 0, 0, 0, 0};
+        uint8_t *out = nullptr;
+        size_t capacity = 0, *size = nullptr;
+};
+
 struct Job {
         j2p_job desc;                       // (of a file job: with the sizes it left zero filled in from the file)
         In in = In::planes;
@@ -95,6 +111,7 @@ struct Job {
         j2p_resample resample = {0, 0, 0, 0, 0, 0, 0};   // Out::resampled
         std::vector<j2p_output> outputs;    // Out::outputs: never empty
         JpegOut jpeg;                       // Out::jpeg
+        PngOut png;                         // Out::png
         int ticket = 0;
         int device = -1;                    // tensors, device samples, a file in device memory: their GPU, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -294,6 +311,11 @@ int deliver_jpeg(const Job &j, const j2p_job &d, const Band &band)
         return j2p_planes_to_jpeg_ex(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, j.jpeg.flags);
 }
 
+int deliver_png(const Job &j, const j2p_job &d, const Band &band)
+{
+        return j2p_planes_to_png(band.ref, d.nchannel, &j.png.spec, j.png.out, j.png.capacity, j.png.size);
+}
+
 int deliver(const Job &j, const Band &band)
 {
         const j2p_job &d = j.desc;
@@ -304,6 +326,7 @@ int deliver(const Job &j, const Band &band)
         case Out::resampled: return deliver_resampled(j, d, band);
         case Out::outputs: return deliver_outputs(j, d, band);
         case Out::jpeg: return deliver_jpeg(j, d, band);
+        case Out::png: return deliver_png(j, d, band);
         }
         return J2P_OK;
 }
@@ -501,7 +524,7 @@ void worker_main(j2p_batch *b, int device)
 }
 
 // ---- submit: the job and its request become the record, or are refused.  The first failing check decides the message, so the
-// order below is part of the interface: file, JPEG, samples, outputs, resample, resize, then the pins. ----
+// order below is part of the interface: file, JPEG, PNG, samples, outputs, resample, resize, then the pins. ----
 
 // a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
 // show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
@@ -547,6 +570,20 @@ int validate_jpeg(const j2p_job &d, const Request &q)
                 return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", q.jpeg->width, q.jpeg->height, d.out_w, d.out_h);
         }
         if(!q.jpeg_size || (!q.jpeg_out && q.jpeg_capacity)) { return j2p_fail(J2P_EINVAL, "job: JPEG output needs out and size"); }
+        return J2P_OK;
+}
+
+int validate_png(const j2p_job &d, const Request &q)
+{
+        if(d.out_bits || d.out_coef[0] || d.out_tensor.data) {
+                return j2p_fail(J2P_EINVAL, "job: a PNG job needs out_bits 0, no out_coef and out_tensor.data NULL");
+        }
+        if(d.tile) { return j2p_fail(J2P_EINVAL, "job: PNG output of a row-tiled job is not supported"); }
+        if(const char *why = j2p_png_error(q.png, d.nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
+        if(q.png->width != d.out_w || q.png->height != d.out_h) {
+                return j2p_fail(J2P_EINVAL, "job: the PNG is %ux%u, the job's image (out_w x out_h) %ux%u", q.png->width, q.png->height, d.out_w, d.out_h);
+        }
+        if(!q.png_size || (!q.png_out && q.png_capacity)) { return j2p_fail(J2P_EINVAL, "job: PNG output needs out and size"); }
         return J2P_OK;
 }
 
@@ -622,6 +659,12 @@ int classify(const j2p_batch &b, const j2p_job &given, const Request &q, Job &j)
                 j.out = Out::jpeg;
                 JOB_TRY(validate_jpeg(d, q));
                 j.jpeg.set(q, d.nchannel);
+        }
+        if(q.png) {
+                j.out = Out::png;
+                JOB_TRY(validate_png(d, q));
+                j.png.spec = *q.png;
+                j.png.out = q.png_out, j.png.capacity = q.png_capacity, j.png.size = q.png_size;
         }
         if(q.samples) {
                 j.in = In::samples;
@@ -778,6 +821,21 @@ int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *
                                size_t capacity, size_t *out_size, int *ticket)
 {
         return j2p_batch_submit_file_jpeg_ex(b, job, file, size, spec, out, capacity, out_size, 0, ticket);
+}
+
+int j2p_batch_submit_png(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_png *spec, uint8_t *out, size_t capacity, size_t *size,
+                         int *ticket)
+{
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: png: spec is NULL"); }
+        return submit(b, job, Request().from_samples(samples).png_to(spec, out, capacity, size), ticket);
+}
+
+int j2p_batch_submit_file_png(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_png *spec, uint8_t *out, size_t capacity,
+                              size_t *out_size, int *ticket)
+{
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: png: spec is NULL"); }
+        return submit(b, job, Request().from_file(file, size).png_to(spec, out, capacity, out_size), ticket);
 }
 
 void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)

@@ -1,6 +1,7 @@
 // jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode) and a
 // baseline file's entropy-coded data back to coefficients (j2p_jpeg_open, j2p_decode_file, j2p_decoded_grids,
-// j2p_entropy_decode; include/jpeg2png_amd.h, j2p_internal.h).
+// j2p_entropy_decode; include/jpeg2png_amd.h, j2p_internal.h) — and, at the end, the PNG coder: samples to the filtered and
+// deflated file (j2p_png_write, j2p_png_encode).
 //
 // A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
 // uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
@@ -10,6 +11,7 @@
 #include <string.h>
 #include <chrono>
 #include <new>
+#include <vector>
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
@@ -17,6 +19,7 @@
 #include "j2p_huffman.h"
 #include "j2p_codec_kernels.hip.h"
 #include "j2p_decode_kernels.hip.h"
+#include "j2p_png_kernels.hip.h"
 
 using namespace j2p;
 
@@ -704,6 +707,181 @@ int j2p_entropy_decode_ex(int device, const uint8_t *file, size_t size, int16_t 
 int j2p_entropy_decode(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info)
 {
         return j2p_entropy_decode_ex(device, file, size, coef_host, quant, info, 0, nullptr);
+}
+
+}  // extern "C"
+
+// ---- the PNG file: k_png_filter, k_png_count, the tables on the host (j2p_deflate.h), k_png_pack, k_png_chunks, k_png_crc ----
+namespace {
+
+// a chunk without data or with the 13 bytes of IHDR: length, type, data, CRC-32 of type and data
+size_t png_chunk(const char type[4], const uint8_t *data, unsigned n, uint8_t *out)
+{
+        out[0] = out[1] = out[2] = 0;
+        out[3] = (uint8_t)n;
+        memcpy(out + 4, type, 4);
+        if(n) { memcpy(out + 8, data, n); }
+        const uint32_t crc = j2p_crc32(out + 4, 4 + n);
+        for(int k = 0; k < 4; k++) { out[8 + n + k] = (uint8_t)(crc >> (24 - 8 * k)); }
+        return 12 + (size_t)n;
+}
+constexpr size_t kPngHead = 8 + 25, kPngTail = 12;       // the signature and IHDR; IEND
+
+}  // namespace
+
+// The coder (j2p_internal.h: what memory and fill are).  The block's layout, each part aligned to 256 bytes:
+//   [samples][stream: the filtered rows][chosen: 5 u32][counts: blocks x 288 u32][blocks: PngBlock each]    known from the spec
+//   [stage: the zlib stream, ceil(bytes / 4) + 1 words][out: the IDAT chunks]                                known once the counts are
+// The counts come down once (a wait), the tables are made on the host (j2p_deflate.h), and every size follows from them: the
+// file's own is known — and J2P_ESPACE answered — before anything is packed.  The block is asked for twice, the first time with
+// a guess for the second part; when it moved, the samples and the filtered rows are made again (the counts live on the host by
+// then).  A second image of the same size or smaller finds the block large enough at once.
+int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, const std::function<int(size_t, void **, bool *)> &memory,
+                  const std::function<void(hipStream_t, uint8_t *)> &fill, uint8_t *out_host, size_t capacity, size_t *size, j2p_png_stats *stats)
+{
+        const unsigned bpp = channels * spec.bits / 8;
+        const size_t rb = (size_t)spec.width * bpp, total = (size_t)spec.height * (rb + 1);
+        const unsigned block_bytes = spec.block_bytes ? spec.block_bytes : J2P_PNG_BLOCK_BYTES;
+        const unsigned idat_bytes = spec.idat_bytes ? spec.idat_bytes : J2P_PNG_IDAT_BYTES;
+        const size_t nblocks = (total + block_bytes - 1) / block_bytes;
+        if(nblocks > J2P_PNG_BLOCKS_MAX) {
+                return j2p_fail(J2P_EINVAL, "png: %zu deflate blocks of %u bytes (at most %u: raise block_bytes)", nblocks, block_bytes, J2P_PNG_BLOCKS_MAX);
+        }
+        j2p_carve part;
+        const size_t samples_at = part((size_t)spec.height * rb), stream_at = part(total), chosen_at = part(5 * 4);
+        const size_t counts_at = part(nblocks * J2P_DEFLATE_COUNTS * 4), blocks_at = part(nblocks * sizeof(PngBlock));
+        const size_t fixed = part.total;
+        char *base = nullptr;
+        const auto take = [&](size_t bytes, bool *moved) {
+                void *p = nullptr;
+                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
+                base = static_cast<char *>(p);
+                return (int)J2P_OK;
+        };
+        const auto u8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(base + at); };
+        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        // from the samples to the filtered rows
+        const auto filter = [&] {
+                fill(stream, u8(samples_at));
+                (void)hipMemsetAsync(base + chosen_at, 0, 5 * 4, stream);
+                hipLaunchKernelGGL(k_png_filter, dim3((spec.height + 3) / 4), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(samples_at)), rb, spec.height,
+                                   bpp, spec.filter < 0 ? 5u : (unsigned)spec.filter, u8(stream_at), u32(chosen_at));
+        };
+        bool moved = false;
+        if(const int rc = take(fixed + total / 2 + total / 4 + 4096, &moved); rc != J2P_OK) { return rc; }      // (a photograph's file: half to two thirds of its samples)
+        filter();
+        hipLaunchKernelGGL(k_png_count, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stream_at)), total, block_bytes,
+                           u32(counts_at));
+        HIP_TRY(hipGetLastError());
+        std::vector<unsigned> counts;
+        std::vector<PngBlock> blocks;
+        try {
+                counts.resize(nblocks * J2P_DEFLATE_COUNTS);
+                blocks.resize(nblocks);
+        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        unsigned chosen[5] = {0, 0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(counts.data(), base + counts_at, counts.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(chosen, base + chosen_at, sizeof(chosen), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        // the tables, the blocks' places and the checksum
+        j2p_png_stats st;
+        memset(&st, 0, sizeof(st));
+        for(int f = 0; f < 5; f++) { st.rows[f] = chosen[f]; }
+        st.blocks = nblocks;
+        uint32_t a = 1, b = 0;
+        unsigned long long zlen = 2;
+        {
+                j2p_deflate_block made;
+                for(size_t k = 0; k < nblocks; k++) {
+                        const unsigned *c = counts.data() + k * J2P_DEFLATE_COUNTS;
+                        const bool final = k + 1 == nblocks;
+                        j2p_deflate_block_make(c, final, &made);
+                        PngBlock &d = blocks[k];
+                        d.offset = zlen;
+                        d.header_bits = made.header_bits;
+                        d.final = final;
+                        memcpy(d.code, made.code, sizeof(d.code));
+                        memcpy(d.header, made.header, sizeof(d.header));
+                        zlen += made.bytes;
+                        st.literals += made.literals;
+                        st.matches += made.matches;
+                        const size_t n = final ? total - k * (size_t)block_bytes : block_bytes;
+                        j2p_deflate_adler_add(&a, &b, n, c[J2P_DEFLATE_SYMBOLS], c[J2P_DEFLATE_SYMBOLS + 1]);
+                }
+        }
+        zlen += 4;
+        st.adler = (b << 16) | a;
+        st.stream_bytes = zlen;
+        if(stats) { *stats = st; }
+        const unsigned long long nchunks = (zlen + idat_bytes - 1) / idat_bytes;
+        const size_t data_bytes = (size_t)(zlen + 12 * nchunks);
+        *size = kPngHead + data_bytes + kPngTail;
+        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "png: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
+        if(nchunks > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "png: %llu IDAT chunks of %u bytes are too many", nchunks, idat_bytes); }
+        const size_t stage_words = (size_t)((zlen + 3) / 4) + 1;
+        const size_t stage_at = part(stage_words * 4), out_at = part(data_bytes);
+        if(const int rc = take(part.total, &moved); rc != J2P_OK) { return rc; }
+        if(moved) { filter(); }
+        HIP_TRY(hipMemcpyAsync(base + blocks_at, blocks.data(), nblocks * sizeof(PngBlock), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(base + stage_at, 0, stage_words * 4, stream));
+        hipLaunchKernelGGL(k_png_pack, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stream_at)), total, block_bytes,
+                           reinterpret_cast<const PngBlock *>(base + blocks_at), st.adler, u32(stage_at));
+        hipLaunchKernelGGL(k_png_chunks, dim3((unsigned)((zlen + 1023) / 1024)), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stage_at)), (size_t)zlen,
+                           idat_bytes, u8(out_at));
+        hipLaunchKernelGGL(k_png_crc, dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, stream, u8(out_at), (size_t)zlen, idat_bytes, (unsigned)nchunks);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_host + kPngHead, base + out_at, data_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        static const uint8_t signature[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+        memcpy(out_host, signature, 8);
+        uint8_t ihdr[13];
+        for(int k = 0; k < 4; k++) {
+                ihdr[k] = (uint8_t)(spec.width >> (24 - 8 * k));
+                ihdr[4 + k] = (uint8_t)(spec.height >> (24 - 8 * k));
+        }
+        ihdr[8] = (uint8_t)spec.bits;
+        ihdr[9] = channels == 3 ? 2 : 0;
+        ihdr[10] = ihdr[11] = ihdr[12] = 0;
+        (void)png_chunk("IHDR", ihdr, 13, out_host + 8);
+        (void)png_chunk("IEND", nullptr, 0, out_host + kPngHead + data_bytes);
+        return J2P_OK;
+}
+
+extern "C" {
+
+int j2p_png_encode(int device, const j2p_png *spec, const uint8_t *samples_host, unsigned channels, uint8_t *out_host, size_t capacity, size_t *size,
+                   j2p_png_stats *stats)
+{
+        if(!samples_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_png_error(spec, channels)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
+        DeviceGuard guard(device);
+        hipStream_t stream = nullptr;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // one pooled block that grows as the solvers' scratch does
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        const size_t sample_bytes = (size_t)spec->width * spec->height * channels * (spec->bits / 8);
+        const int rc = j2p_png_write(
+                stream, *spec, channels,
+                [&](size_t bytes, void **p, bool *moved) {
+                        *moved = block_bytes < bytes;
+                        if(block_bytes < bytes) {
+                                HIP_TRY(hipStreamSynchronize(stream));
+                                j2p_pool_give(device, block, block_bytes);
+                                block = nullptr;
+                                block_bytes = 0;
+                                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
+                        }
+                        *p = block;
+                        return (int)J2P_OK;
+                },
+                [&](hipStream_t st, uint8_t *samples) { (void)hipMemcpyAsync(samples, samples_host, sample_bytes, hipMemcpyHostToDevice, st); }, out_host, capacity,
+                size, stats);
+        (void)hipStreamSynchronize(stream);
+        j2p_pool_give(device, block, block_bytes);
+        (void)hipStreamDestroy(stream);
+        return rc;
 }
 
 }  // extern "C"

@@ -70,6 +70,25 @@ static inline const char *j2p_jpeg_error(const j2p_jpeg *spec, unsigned ncomp)
         return NULL;
 }
 
+// the same for a j2p_png of `channels` samples per pixel (j2p_planes_to_png, j2p_png_encode, j2p_batch_submit_png)
+static inline const char *j2p_png_error(const j2p_png *spec, unsigned channels)
+{
+        if(!spec) { return "png: spec is NULL"; }
+        if(channels != 1 && channels != 3) { return "png: three samples per pixel (RGB) or one (greyscale)"; }
+        if(spec->width == 0 || spec->height == 0 || spec->width > J2P_PNG_SIDE_MAX || spec->height > J2P_PNG_SIDE_MAX) {
+                return "png: width and height must be 1..16777216";
+        }
+        if(spec->bits != 8 && spec->bits != 16) { return "png: bits must be 8 or 16"; }
+        if(spec->filter < J2P_PNG_FILTER_ADAPTIVE || spec->filter > 4) { return "png: filter must be 0..4, or J2P_PNG_FILTER_ADAPTIVE"; }
+        if(spec->block_bytes && (spec->block_bytes < J2P_PNG_SIZE_MIN || spec->block_bytes > J2P_PNG_SIZE_MAX)) {
+                return "png: block_bytes must be 0 (the default) or 16..16777216";
+        }
+        if(spec->idat_bytes && (spec->idat_bytes < J2P_PNG_SIZE_MIN || spec->idat_bytes > J2P_PNG_SIZE_MAX)) {
+                return "png: idat_bytes must be 0 (the default) or 16..16777216";
+        }
+        return NULL;
+}
+
 // ---- reading a JPEG file (j2p_jpeg_parse.c, pure C; the decode kernels of j2p_decode_kernels.hip.h) ----
 // One Huffman table in the form the kernels look symbols up in (the choice and what it costs: DESIGN.md section 21): an 8-bit
 // first level for the codes of up to 8 bits — look[the next 8 bits] = (length << 8) | symbol, 0 when the code is longer —
@@ -198,6 +217,15 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                     unsigned flags = 0, j2p_encode_stats *stats = nullptr);
 // what is wrong with the flags of a j2p_*_ex call that writes a JPEG file, or NULL
 static inline const char *j2p_jpeg_flags_error(unsigned flags) { return flags & ~J2P_JPEG_OPTIMIZE ? "jpeg: unknown flag bits" : nullptr; }
+
+// The PNG coder: the file of `spec` on the host from `channels` (1 or 3) interleaved samples per pixel that the caller leaves in
+// device memory, on `stream`, which has been waited for on return (twice on the way: the blocks' counts come down for the host's
+// tables).  memory: as for j2p_encode_scan; fill(stream, samples): queues what leaves the width * height * channels * bits / 8 bytes
+// of samples (16 bits: big-endian) at `samples`.  Both may be called twice.  J2P_ESPACE: *size is what the file needs, known before
+// anything is packed.  spec has passed j2p_png_error.  stats may be NULL.
+int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, const std::function<int(size_t, void **, bool *)> &memory,
+                  const std::function<void(hipStream_t, uint8_t *)> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                  j2p_png_stats *stats = nullptr);
 
 // A JPEG file opened for decoding: its marker segments parsed on the host (from a temporary copy for a file in device memory),
 // and where the caller's bytes are, which the decode reads in place.

@@ -1,7 +1,7 @@
 // jpeg2png_amd — the output stage: solved planes to samples on the host (PNG), to a strided tensor in device memory, whole
 // or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), to quantised JPEG
-// coefficients, and — those handed to the codec's coder (j2p_codec.hip) — to the entropy-coded JPEG file itself
-// (include/jpeg2png_amd.h: the j2p_planes_* functions).
+// coefficients, and — those handed to the codec's coder (j2p_codec.hip) — to the entropy-coded JPEG file itself; and samples
+// left in device memory for the codec's PNG coder, to the PNG file (include/jpeg2png_amd.h: the j2p_planes_* functions).
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
@@ -758,6 +758,34 @@ int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j
 int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
 {
         return j2p_planes_to_jpeg_ex(planes, nplane, spec, out_host, capacity, size, 0);
+}
+
+// the PNG file: the samples k_to_samples makes for j2p_planes_to_rgb / _grey, left in the coder's block (j2p_codec.hip: j2p_png_write),
+// which is the first solver's scratch
+int j2p_planes_to_png(const j2p_plane_ref planes[], unsigned nplane, const j2p_png *spec, uint8_t *out_host, size_t capacity, size_t *size)
+{
+        if(!planes || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_png_error(spec, nplane)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        const float *ptr[3];
+        unsigned stride[3];
+        j2p_solver_view s0;
+        if(const int rc = resolve_rows(nplane == 3 ? "to_rgb" : "to_grey", planes, nplane, true, spec->width, 0, spec->height, ptr, stride, s0); rc != J2P_OK) {
+                return rc;
+        }
+        DeviceGuard guard(s0.device);
+        j2p_solver *const owner = planes[0].solver;
+        const unsigned w = spec->width, h = spec->height, bits = spec->bits;
+        return j2p_png_write(
+                s0.stream, *spec, nplane,
+                [&](size_t bytes, void **p, bool *moved) {
+                        *moved = j2p_solver_scratch_bytes(owner) < bytes;
+                        return j2p_solver_scratch(owner, bytes, p);
+                },
+                [&](hipStream_t st, uint8_t *samples) {
+                        hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, st, ptr[0], stride[0], ptr[1], stride[1],
+                                           ptr[2], stride[2], w, h, bits, samples);
+                },
+                out_host, capacity, size);
 }
 
 }  // extern "C"
