@@ -234,6 +234,23 @@ static bool read_file_for_gpu(const char *infile, FILE *in, struct jpeg_in *jp, 
         return true;
 }
 
+/* -a: the EXIF Orientation tag of the input, read from its bytes by the library (j2p_jpeg_orientation: 1 where the file has none
+ * that counts); leaves `in` rewound */
+static unsigned read_orientation(const char *infile, FILE *in)
+{
+        if(fseek(in, 0, SEEK_END) != 0) { die_perror("could not read input file `%s`", infile); }
+        const long size = ftell(in);
+        if(size < 0 || fseek(in, 0, SEEK_SET) != 0) { die_perror("could not read input file `%s`", infile); }
+        uint8_t *file = malloc((size_t)size + 1);
+        if(!file) { die("could not allocate memory for the file"); }
+        if(fread(file, 1, (size_t)size, in) != (size_t)size) { die_perror("could not read input file `%s`", infile); }
+        unsigned orientation = 1;
+        if(j2p_jpeg_orientation(file, (size_t)size, &orientation) != J2P_OK) { die("`%s`: %s", infile, j2p_last_error()); }
+        free(file);
+        rewind(in);
+        return orientation;
+}
+
 /* ---- PNG out (the file side of png.c:20-78; pixels arrive already converted) ---- */
 
 static void png_fatal(png_structp png, png_const_charp msg)
@@ -356,6 +373,7 @@ struct options {
         bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
         bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
+        bool auto_orient;       /* -a: the input's EXIF Orientation is applied: every output is the upright image, and carries no tag */
         bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
@@ -422,6 +440,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         if(!in) { die_perror("could not open input file `%s`", infile); }
         struct jpeg_in jp;
         memset(&jp, 0, sizeof(jp));
+        const unsigned orientation = o->auto_orient ? read_orientation(infile, in) : 1;
         if(!o->decode_on_gpu || !read_file_for_gpu(infile, in, &jp, o->zoom, o->grey)) {
                 read_coefficients(in, &jp, o->zoom, o->grey);
         }
@@ -478,6 +497,12 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         }
         job.out_w = jp.w * zoom;
         job.out_h = jp.h * zoom;
+        if(orientation >= 5) {
+                /* -a: the job's solvers are oriented (ORIENT_NEXT below) and every output form is that of the upright image, here
+                 * a turned one (a file without the tag, or with tag 1, is the job it always was) */
+                job.out_w = jp.h * zoom;
+                job.out_h = jp.w * zoom;
+        }
         uint8_t *pixels = NULL;
         uint16_t out_quant[3][64];
         int16_t *out_coef[3] = {NULL, NULL, NULL};
@@ -509,6 +534,8 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         int ticket = 0;
         pthread_once(&batch_once, batch_start);
         if(batch_rc != J2P_OK) { die("%s", batch_err); }
+        /* (the orientation travels next to the job: set for this thread's next submit, before every one of them below) */
+#define ORIENT_NEXT() gpu_check(orientation > 1 ? j2p_batch_next_orientation(batch, orientation, jp.w * zoom, jp.h * zoom) : J2P_OK)
         uint8_t *file = NULL;
         size_t file_bytes = 0;
         if(o->jpeg_quality && o->encode_on_gpu) {
@@ -527,6 +554,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
                         const unsigned flags = o->optimize ? J2P_JPEG_OPTIMIZE : 0u;
+                        ORIENT_NEXT();
                         if(jp.file) {
                                 gpu_check(j2p_batch_submit_file_jpeg_ex(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, flags, &ticket));
                         } else {
@@ -551,6 +579,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 for(int attempt = 0;; attempt++) {
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
+                        ORIENT_NEXT();
                         if(jp.file) { gpu_check(j2p_batch_submit_file_png(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket)); }
                         else { gpu_check(j2p_batch_submit_png(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket)); }
                         const int rc = j2p_batch_wait(batch, ticket);
@@ -562,10 +591,12 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         capacity = file_bytes;
                 }
         } else {
+                ORIENT_NEXT();
                 if(jp.file) { gpu_check(j2p_batch_submit_file(batch, &job, jp.file, jp.file_size, 0, NULL, &ticket)); }
                 else { gpu_check(j2p_batch_submit(batch, &job, &ticket)); }
                 gpu_check(j2p_batch_wait(batch, ticket));
         }
+#undef ORIENT_NEXT
         for(unsigned c = 0; c < jp.n; c++) { free(jp.c[c].data); }
         free(jp.file);
         FILE *out = fopen(outfile, "wb");
@@ -635,6 +666,8 @@ static void usage(void)
                "                               coefficients (with -e the GPU counts the symbols; the same bytes either way)\n"
                "  -P, --png-on-gpu             the GPU also filters and deflates the PNG and only the file comes down: the same\n"
                "                               pixels in another, usually somewhat larger file; not with -j, not for row-tiled images\n"
+               "  -a, --auto-orient            apply the input's EXIF Orientation: every output is the upright image (turned and\n"
+               "                               mirrored on the GPU; the files written carry no tag); not for row-tiled images\n"
                "  -c, --csv-log FILE           per-iteration objective log\n"
                "  -q, --quiet                  no progress bar\n"
                "  -h, --help    -V, --version\n"
@@ -655,7 +688,7 @@ int main(int argc, char **argv)
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
                 {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'},
-                {"png-on-gpu", no_argument, NULL, 'P'}, {NULL, 0, NULL, 0}};
+                {"png-on-gpu", no_argument, NULL, 'P'}, {"auto-orient", no_argument, NULL, 'a'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
                             .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .png_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
         const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
@@ -663,7 +696,7 @@ int main(int argc, char **argv)
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOP", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOPa", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -684,6 +717,7 @@ int main(int argc, char **argv)
                 case 'd': o.decode_on_gpu = true; break;
                 case 'O': o.optimize = true; break;
                 case 'P': o.png_on_gpu = true; break;
+                case 'a': o.auto_orient = true; break;
                 default: help = true; break;
                 }
         }
@@ -764,6 +798,8 @@ int main(int argc, char **argv)
                 if(o.ndev == 0) { o.ndev = 1; o.devs[0] = 0; }
         }
 
+        /* (fewer files than GPUs: the images would be row-tiled over them, and a row-tiled job has no upright output) */
+        if(o.auto_orient && o.ndev > 1 && nin < (unsigned)o.ndev) { die("-a is not supported for row-tiled images (fewer files than GPUs)"); }
         if(!(nout == 0 || nout == nin)) { die("must give output file names for all input files or none"); }
         char **outfiles = malloc(sizeof(*outfiles) * nin);
         if(!outfiles) { die("could not allocate outfiles"); }

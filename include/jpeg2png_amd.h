@@ -1131,6 +1131,62 @@ int j2p_batch_submit_png(j2p_batch *b, const j2p_job *job, const j2p_samples sam
 int j2p_batch_submit_file_png(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_png *spec, uint8_t *out,
                               size_t capacity, size_t *out_size, int *ticket);
 
+/* Upright output: the file's EXIF Orientation applied to every output form, as a pure permutation of the solved planes.  This is the
+ * definition; tests/upright_cases.py restates it.
+ *
+ * Orientation o is 1..8 and the source image is w x h pixels (the file's frame size, times the zoom).  The upright image U is
+ * w' x h' = w x h for o in 1..4 and h x w for o in 5..8, and U[y][x] = I[sy][sx] per channel, on the full-resolution solved float
+ * planes (every channel of a solver lives on the full canvas: sampling factors play no part):
+ *
+ *      o   sx          sy                  o   sx          sy
+ *      1   x           y                   5   y           x
+ *      2   w - 1 - x   y                   6   y           h - 1 - x
+ *      3   w - 1 - x   h - 1 - y           7   w - 1 - y   h - 1 - x
+ *      4   x           h - 1 - y           8   w - 1 - y   x
+ *
+ * (what PIL's ImageOps.exif_transpose does.)  Beyond the image, at x >= w' or y >= h', U replicates its last column or row:
+ * U[y][x] = U[min(y, h' - 1)][min(x, w' - 1)] — what an output form sees where, unoriented, it sees the canvas's solved padding (the
+ * 8x8 blocks of JPEG output, an overhanging chroma grid).  The upright canvas against which a call's extents are checked is w' and h'
+ * rounded up to multiples of 16; everything beyond the image being replication, no result depends on that number.
+ *
+ * Every output form of an oriented solver — j2p_planes_to_rgb / _grey / _tensor / _tensor_resized / _tensor_resampled /
+ * _tensors_resampled / _coefficients / _coefficients_sub / _jpeg / _png — is, bit for bit, that form applied to U: the width, height,
+ * box and JPEG or PNG spec a call takes are those of the upright image.  The call queues the permutation (a copy kernel; orientations
+ * 5..8 through a tile in LDS) on the stream of planes[0].solver into a block of upright planes that belongs to that solver (also the planes of the other solvers of a
+ * call: one block is written and read in one stream's order only), once per call and for
+ * the channels the call reads, and then runs unchanged on those planes.  All planes of one call must carry the same orientation and
+ * source size (J2P_EINVAL otherwise).  With orientation 1, or none ever set, a call is what it was, launch for launch and byte for byte.
+ *
+ * NOT oriented: the raw float planes — j2p_job.out_planes, j2p_solver_plane_ptr, j2p_solver_download — which stay the solver's canvas.
+ * The j2p_planes_rows_* forms refuse an oriented solver (J2P_ESTATE), band solvers refuse an orientation other than 1 (J2P_ESTATE from
+ * the setter) and a job with `tile` refuses one (J2P_EINVAL at submit: j2p_batch_next_orientation). */
+/* the Orientation tag of a JPEG file: the SHORT 0x0112 in IFD0 of the first APP1 segment whose payload begins "Exif\0\0" — byte order
+ * II or MM, the magic 42 and the IFD0 offset honoured, nothing read outside the segment, segments read only up to SOS (so progressive
+ * files are read like baseline ones: nothing is decoded).  *orientation is 1 — and the call J2P_OK — where there is no such segment, the
+ * TIFF structure is damaged or truncated, the tag has another type or count, or its value is outside 1..8 (PIL's behaviour).  Host only,
+ * no allocation; independent of j2p_jpeg_parse.  J2P_EINVAL: a NULL argument. */
+int j2p_jpeg_orientation(const uint8_t *file, size_t size, unsigned *orientation);
+/* orientation 1..8 (J2P_EINVAL otherwise) for a source image of width x height pixels, both at least 1 and inside the canvas
+ * (J2P_EINVAL).  A band solver takes only 1 (J2P_ESTATE).  Queues nothing; holds until set again.  1 is "none". */
+int j2p_solver_set_orientation(j2p_solver *s, unsigned orientation, unsigned width, unsigned height);
+/* what was set: 1, 0, 0 for a solver that was never oriented (any of the three may be NULL) */
+int j2p_solver_orientation(const j2p_solver *s, unsigned *orientation, unsigned *width, unsigned *height);
+/* the size of the solver's block of upright planes now (0: none yet, and never any for orientation 1): taken from the pool on first
+ * use, grown as the output scratch grows, given back at destroy — a second call with the same orientation leaves it unchanged */
+int j2p_solver_upright_bytes(const j2p_solver *s, size_t *bytes);
+/* Upright batch jobs.  The orientation travels next to the job, never in it (j2p_job keeps its layout, as for every other optional
+ * part): this call sets it for the NEXT job the calling thread submits to `b`, through whichever j2p_batch_submit* entry point, and
+ * that submit consumes it whether it succeeds or not.  orientation: 0 = none (the call then only clears what was set), 1..8 = that
+ * EXIF orientation for a source image of orient_w x orient_h pixels (a file job: left zero, the file's frame), J2P_ORIENTATION_EXIF =
+ * the tag of the job's file, read at submit on the caller's thread (file jobs only).  What is wrong with it is refused by the submit
+ * (J2P_EINVAL, no ticket): a value above 8, J2P_ORIENTATION_EXIF without a file, no source size without a file, a job with `tile`.
+ * The worker sets the orientation on every solver it makes for the job (joint, `separate`, component 0 alone), and every output kind
+ * but out_planes follows: samples, tensors, resized and resampled ones, several outputs, coefficients, the JPEG and the PNG file.
+ * job->out_w / out_h, and the spec of a PNG or JPEG job, are the UPRIGHT image's; a file job that leaves out_w / out_h zero gets the
+ * upright size. */
+#define J2P_ORIENTATION_EXIF 0xffffffffu
+int j2p_batch_next_orientation(j2p_batch *b, unsigned orientation, unsigned orient_w, unsigned orient_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,7 +203,10 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_jpeg_ex", "j2p_entropy_encode_ex", "j2p_batch_submit_jpeg_ex", "j2p_batch_submit_file_jpeg_ex",
     "j2p_solver_output_scratch_bytes",
     "j2p_planes_to_png", "j2p_png_encode", "j2p_batch_submit_png", "j2p_batch_submit_file_png",
+    "j2p_jpeg_orientation", "j2p_solver_set_orientation", "j2p_solver_orientation", "j2p_solver_upright_bytes",
+    "j2p_batch_next_orientation",
 ]
+J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
 NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, "fold_tree": 4, "project_tree": 5}
 J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 4, 5, 6
@@ -354,6 +357,8 @@ def _bind(path):
     lib.j2p_tiled_host_cpu_seconds.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
     lib.j2p_planes_rows_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                                         ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    lib.j2p_planes_to_coefficients_sub.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                   ctypes.c_void_p, ctypes.c_void_p]
     lib.j2p_planes_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_CTensor)]
     lib.j2p_planes_rows_to_tensor.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
                                               ctypes.POINTER(_CTensor)]
@@ -416,6 +421,14 @@ def _bind(path):
                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
         lib.j2p_batch_submit_file_png.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CPng),
                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_jpeg_orientation"):
+        # (as above: an earlier commit's build has no upright output)
+        lib.j2p_jpeg_orientation.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint)]
+        lib.j2p_solver_set_orientation.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]
+        lib.j2p_solver_orientation.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                               ctypes.POINTER(ctypes.c_uint)]
+        lib.j2p_solver_upright_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+        lib.j2p_batch_next_orientation.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]
     if hasattr(lib, "j2p_entropy_decode_ex"):
         # (as above: an earlier commit's build does not read files)
         lib.j2p_jpeg_parse.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpegInfo)]
@@ -915,6 +928,20 @@ def jpeg_parse(data):
     return _jpeg_info_dict(info)
 
 
+def jpeg_orientation_c(data):
+    """j2p_jpeg_orientation: the EXIF Orientation tag of a JPEG file (host bytes), 1..8, read by the library's C reader; 1 where the
+    file has none that counts.  jpeg_orientation is its pure-Python twin."""
+    addr, size, _keep = _file_bytes(bytes(data))
+    o = ctypes.c_uint(0)
+    _check(load_library().j2p_jpeg_orientation(addr, size, ctypes.byref(o)))
+    return o.value
+
+
+def upright_size(orientation, width, height):
+    """(width, height) of the upright image of a width x height source under EXIF orientation 1..8"""
+    return (int(height), int(width)) if int(orientation) >= 5 else (int(width), int(height))
+
+
 def entropy_decode(data, device=0, subsequence_bits=0, stats=False):
     """the quantised coefficients of a baseline JPEG file, Huffman-decoded on the GPU (j2p_entropy_decode): a list of 1 or 3 int16
     arrays [blocks_h, blocks_w, 64] in natural order — what libjpeg's jpeg_read_coefficients delivers.  data: bytes, or a 1-D uint8
@@ -1021,12 +1048,14 @@ class Solver:
         return self
 
     @classmethod
-    def from_jpeg(cls, data, weight, pweight, iterations, device=0, stream=None):
+    def from_jpeg(cls, data, weight, pweight, iterations, device=0, stream=None, upright=False):
         """A solver made from a baseline JPEG FILE (j2p_solver_create_from_jpeg): the file's entropy-coded data is Huffman-decoded
         on the GPU straight into the solver's resident coefficients — no libjpeg, and the file's true coefficients at every
         quality.  data: bytes, or a 1-D uint8 torch tensor (on the solver's GPU: the scan is read in place).  pweight: one per
         component of the file (1 or 3).  From there on the solver is the one Solver(planes with those coefficients) is.
-        self.jpeg holds what jpeg_parse returns.  J2PError with code J2P_EFORMAT / J2P_ENOTSUP for files that are refused."""
+        self.jpeg holds what jpeg_parse returns.  J2PError with code J2P_EFORMAT / J2P_ENOTSUP for files that are refused.
+        upright=True: the file's EXIF Orientation tag (jpeg_orientation) is set on the solver with the file's size
+        (set_orientation): every output form then delivers the upright image."""
         self = cls.__new__(cls)
         lib = load_library()
         self._lib = lib
@@ -1053,7 +1082,44 @@ class Solver:
         self.nch = info.ncomp
         self._geom = [(k["w"], k["h"]) for k in self.jpeg["components"]]
         self._adopt(h, device)
+        if upright:
+            self.set_orientation(jpeg_orientation(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data),
+                                 self.jpeg["width"], self.jpeg["height"])
         return self
+
+    def set_orientation(self, orientation, width, height):
+        """EXIF orientation 1..8 of a source image of width x height pixels (j2p_solver_set_orientation): from now on every output
+        form — to_tensor(s), coefficients, to_jpeg, to_png, the sample forms — is that form of the UPRIGHT image (the header states
+        the permutation), whose width, height, boxes and specs the calls then take: height x width for orientations 5..8.  1 is
+        none.  download() and plane_ptr() stay the solver's canvas.  Whole-canvas solvers only."""
+        _check(self._lib.j2p_solver_set_orientation(self._h, int(orientation), int(width), int(height)))
+
+    @property
+    def orientation(self):
+        """the orientation set_orientation left (1: none)"""
+        if not hasattr(self._lib, "j2p_solver_orientation"):        # (an earlier commit's build: nothing to set)
+            return 1
+        o = ctypes.c_uint()
+        _check(self._lib.j2p_solver_orientation(self._h, ctypes.byref(o), None, None))
+        return o.value
+
+    def _upright_canvas(self):
+        """(W, H) of the canvas the output forms see: the solver's, or for an oriented solver the upright image rounded up to 16"""
+        if not hasattr(self._lib, "j2p_solver_orientation"):
+            return None
+        o, w, h = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+        _check(self._lib.j2p_solver_orientation(self._h, ctypes.byref(o), ctypes.byref(w), ctypes.byref(h)))
+        if o.value <= 1:
+            return None
+        uw, uh = upright_size(o.value, w.value, h.value)
+        return -(-uw // 16) * 16, -(-uh // 16) * 16
+
+    def upright_bytes(self):
+        """bytes of the block of upright planes an oriented solver's output calls permute into (j2p_solver_upright_bytes): 0 until
+        the first such call, unchanged by a second one"""
+        n = ctypes.c_size_t()
+        _check(self._lib.j2p_solver_upright_bytes(self._h, ctypes.byref(n)))
+        return n.value
 
     def download_coefficients(self, c):
         """diagnostics: the quantised coefficients channel c holds, int16 [block rows, blocks per row, 64] (j2p_solver_download_coefficients)"""
@@ -1176,14 +1242,18 @@ class Solver:
         if q.size != 64:
             raise J2PError("quant_table must have 64 entries")
         sx, sy = _sampling(subsampling)
-        # a band's block rows: those that start in it (cuts are multiples of 16 rows)
-        r0, r1 = -(-self.row_begin // (8 * sy)), -(-self.row_end // (8 * sy))
-        bw = -(-self.W // (8 * sx)) if blocks_w is None else int(blocks_w)
+        upright = self._upright_canvas()
+        # a band's block rows: those that start in it (cuts are multiples of 16 rows); an oriented solver: the upright canvas's
+        r0, r1 = (-(-self.row_begin // (8 * sy)), -(-self.row_end // (8 * sy))) if upright is None else (0, -(-upright[1] // (8 * sy)))
+        bw = -(-(self.W if upright is None else upright[0]) // (8 * sx)) if blocks_w is None else int(blocks_w)
         bh = (r1 - r0) if blocks_h is None else int(blocks_h)
         if bw < 0 or bh < 0:
             raise J2PError("blocks_w / blocks_h must not be negative")
         out = np.empty((bh, bw, 64), dtype=np.int16)
         ref = _CPlaneRef(self._h, int(c))
+        if upright is not None:         # (the rows forms take no oriented solver)
+            _check(self._lib.j2p_planes_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, bh, q.ctypes.data, out.ctypes.data))
+            return out
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
@@ -1265,6 +1335,8 @@ class Solver:
                 _check(self._lib.j2p_planes_to_tensor_resampled(refs, self.nch, int(width), int(height), ctypes.byref(resize), ctypes.byref(ct)))
             elif resize is not None:
                 _check(self._lib.j2p_planes_to_tensor_resized(refs, self.nch, int(width), int(height), ctypes.byref(resize), ctypes.byref(ct)))
+            elif self.orientation > 1:          # (the rows forms take no oriented solver)
+                _check(self._lib.j2p_planes_to_tensor(refs, self.nch, int(width), int(height), ctypes.byref(ct)))
             else:
                 _check(self._lib.j2p_planes_rows_to_tensor(refs, self.nch, int(width), self.row_begin, self.row_begin + int(height), ctypes.byref(ct)))
         return out
@@ -1810,8 +1882,12 @@ class Batch:
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None, jpeg=None, file=None, png=None):
-        """png={"bits": 8 or 16, "filter": None or 0..4 or a name, "block_bytes": n, "idat_bytes": n, "capacity": bytes} (with width and
+               samples=None, jpeg=None, file=None, png=None, orientation=None):
+        """orientation=1..8 or "exif" (the tag of file=, read at submit; file jobs only; not with tile): every solver of the job is
+        oriented (Solver.set_orientation) and every output kind but the float planes delivers the UPRIGHT image, whose size width and
+        height then are — for a file job they default to the file's upright size; the source image is the file's frame, or without
+        a file width x height turned back;
+        png={"bits": 8 or 16, "filter": None or 0..4 or a name, "block_bytes": n, "idat_bytes": n, "capacity": bytes} (with width and
         height; not with jpeg=, bits, quant_tables, tensor=, outputs= or tile; samples= and file= are allowed): wait() returns the image
         as a complete PNG file (bytes) that the worker converted, filtered and deflated on its GPU (j2p_batch_submit_png,
         Solver.to_png) — one or three planes.  capacity: room for the file (default: 5/4 of the filtered samples, which no image
@@ -1857,8 +1933,28 @@ class Batch:
         resized = filter is not None or out_width is not None or out_height is not None or box is not None
         want = _Wanted(separate, tile, bits, out, quant_tables, subsampling, tensor, layout, scale, bias, out_width, out_height, box, filter, outputs,
                        jpeg, resized, png)
-        source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized)
         job = _CJob()
+        oriented = (0, 0, 0)            # what travels next to the job: j2p_batch_next_orientation
+        if orientation is not None:
+            # (what else is wrong with it — "exif" without file=, tile — the library refuses at submit)
+            host = None if file is None else (file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file)    # (one copy of a device file)
+            if orientation == "exif":
+                code = J2P_ORIENTATION_EXIF
+                found = 1 if host is None else jpeg_orientation(host)
+            else:
+                code = found = int(orientation)
+                if not 1 <= code <= 8:
+                    err = J2PError(f"job: orientation {orientation!r} (1..8 or \"exif\")")
+                    err.code = -1       # J2P_EINVAL, as the library's own refusals carry it
+                    raise err
+            oriented = (code, 0, 0)
+            if host is not None and (width is None or height is None):
+                head = jpeg_parse(host)
+                uw, uh = upright_size(found, head["width"], head["height"])
+                width, height = (uw if width is None else width), (uh if height is None else height)
+            elif file is None and width is not None and height is not None:
+                oriented = (code,) + upright_size(found, width, height)     # (turned back: the same swap)
+        source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized)
         kind, result, filled, output_args = _job_output(job, want, planes, width, height)
         keep += filled + _job_record(job, planes, weight, pweight, iterations, want, tile_devices, tile_min_band_pixels)
         if on_progress is not None:
@@ -1867,6 +1963,8 @@ class Batch:
             keep.append(cb)                         # the trampoline lives as long as the job
         name, args = _entry_point(source, source_args, kind, output_args)
         t = ctypes.c_int()
+        if oriented[0]:
+            _check(self._lib.j2p_batch_next_orientation(self._h, *oriented))        # (this thread's next submit: the one below)
         _check(getattr(self._lib, name)(self._h, ctypes.byref(job), *args, ctypes.byref(t)))
         self._pending[t.value] = (result, keep)
         return t.value
@@ -2008,6 +2106,60 @@ def _zigzag_to_natural():
 
 
 _NATURAL_OF_ZIGZAG = _zigzag_to_natural()
+
+
+def jpeg_orientation(data):
+    """The EXIF Orientation tag of a JPEG file (bytes), 1..8 — the pure-Python twin of j2p_jpeg_orientation: the SHORT 0x0112 in
+    IFD0 of the first APP1 segment whose payload begins b"Exif\\0\\0", byte order II or MM, the magic 42 and the IFD0 offset
+    honoured, nothing read outside the segment, segments read only up to SOS.  1 where there is no such segment, the TIFF
+    structure is damaged or truncated, the tag has another type or count, or its value is outside 1..8 (PIL's behaviour)."""
+    f = bytes(data)
+    if len(f) < 4 or f[0] != 0xff or f[1] != 0xd8:
+        return 1
+    pos = 2
+    while True:
+        if pos + 2 > len(f) or f[pos] != 0xff:
+            return 1
+        marker = f[pos + 1]
+        if marker == 0xff:
+            pos += 1
+            continue
+        pos += 2
+        if marker == 0x01 or 0xd0 <= marker <= 0xd8:
+            continue
+        if marker in (0xd9, 0xda) or pos + 2 > len(f):
+            return 1
+        length = (f[pos] << 8) | f[pos + 1]
+        if length < 2 or length > len(f) - pos:
+            return 1
+        body = f[pos + 2:pos + length]
+        pos += length
+        if marker == 0xe1 and body[:6] == b"Exif\0\0":
+            return _tiff_orientation(body[6:])
+
+
+def _tiff_orientation(t):
+    if len(t) < 8 or t[:2] not in (b"MM", b"II"):
+        return 1
+    order = "big" if t[:2] == b"MM" else "little"
+    u = lambda at, n: int.from_bytes(t[at:at + n], order)
+    if u(2, 2) != 42:
+        return 1
+    ifd = u(4, 4)
+    if ifd > len(t) - 2:
+        return 1
+    entries = u(ifd, 2)
+    if entries * 12 > len(t) - 2 - ifd:
+        return 1
+    for k in range(entries):
+        e = ifd + 2 + 12 * k
+        if u(e, 2) != 0x0112:
+            continue
+        if u(e + 2, 2) != 3 or u(e + 4, 4) != 1:
+            return 1
+        v = u(e + 8, 2)
+        return v if 1 <= v <= 8 else 1
+    return 1
 
 
 def jpeg_header(data):

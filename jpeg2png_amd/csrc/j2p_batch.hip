@@ -45,6 +45,7 @@ struct Request {
         uint8_t *jpeg_out = nullptr;
         size_t jpeg_capacity = 0, *jpeg_size = nullptr;
         unsigned jpeg_flags = 0;            // J2P_JPEG_*
+        unsigned orientation = 0, orient_w = 0, orient_h = 0;    // j2p_batch_next_orientation: what the calling thread set for this submit
         const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
         uint8_t *png_out = nullptr;
         size_t png_capacity = 0, *png_size = nullptr;
@@ -112,6 +113,7 @@ struct Job {
         std::vector<j2p_output> outputs;    // Out::outputs: never empty
         JpegOut jpeg;                       // Out::jpeg
         PngOut png;                         // Out::png
+        unsigned orientation = 0, orient_w = 0, orient_h = 0;   // j2p_batch_next_orientation, settled at submit: 0 / 1 none, 2..8 of that source size
         int ticket = 0;
         int device = -1;                    // tensors, device samples, a file in device memory: their GPU, the only one whose workers may take the job
         int rc = J2P_OK;
@@ -259,8 +261,16 @@ struct Band {
 
 int synced(int rc, const Band &band) { return rc != J2P_OK ? rc : j2p_solver_sync(band.ref[0].solver); }
 
-int deliver_samples(const j2p_job &d, const Band &band)
+// an oriented job (never row-tiled: its one band is the whole canvas) delivers through the whole-canvas forms, which see the
+// upright planes; the rows forms take no oriented solver
+bool oriented(const Job &j) { return j.orientation > 1; }
+
+int deliver_samples(const Job &j, const j2p_job &d, const Band &band)
 {
+        if(oriented(j)) {
+                return d.nchannel == 1 ? j2p_planes_to_grey(band.ref, d.out_w, d.out_h, d.out_bits, d.out_rgb)
+                                       : j2p_planes_to_rgb(band.ref, d.out_w, d.out_h, d.out_bits, d.out_rgb);
+        }
         unsigned y0, y1;
         if(!band.image_rows(d, &y0, &y1)) { return J2P_OK; }
         const size_t row_bytes = (size_t)d.out_w * (d.nchannel == 1 ? 1 : 3) * (d.out_bits / 8);
@@ -269,8 +279,9 @@ int deliver_samples(const j2p_job &d, const Band &band)
         return j2p_planes_rows_to_rgb(band.ref, d.out_w, y0, y1, d.out_bits, out);
 }
 
-int deliver_tensor_rows(const j2p_job &d, const Band &band)
+int deliver_tensor_rows(const Job &j, const j2p_job &d, const Band &band)
 {
+        if(oriented(j)) { return synced(j2p_planes_to_tensor(band.ref, d.nchannel, d.out_w, d.out_h, &d.out_tensor), band); }
         unsigned y0, y1;
         if(!band.image_rows(d, &y0, &y1)) { return J2P_OK; }
         j2p_tensor rows = d.out_tensor;                  // the band's first row of it
@@ -279,11 +290,15 @@ int deliver_tensor_rows(const j2p_job &d, const Band &band)
         return synced(j2p_planes_rows_to_tensor(band.ref, d.nchannel, d.out_w, y0, y1, &rows), band);
 }
 
-int deliver_coefficients(const j2p_job &d, const Band &band)
+int deliver_coefficients(const Job &j, const j2p_job &d, const Band &band)
 {
         for(unsigned c = 0; d.out_coef[0] && c < d.nchannel; c++) {
                 const unsigned sx = out_sub(d.out_sub_w[c]), sy = out_sub(d.out_sub_h[c]);
                 const unsigned bw = (d.out_blocks_w + sx - 1) / sx, bh = (d.out_blocks_h + sy - 1) / sy;
+                if(oriented(j)) {
+                        JOB_TRY(j2p_planes_to_coefficients_sub(&band.ref[c], sx, sy, bw, bh, d.out_quant[c], d.out_coef[c]));
+                        continue;
+                }
                 const unsigned r0 = band.row0[c] / (8 * sy), r1 = !band.last && band.row1[c] / (8 * sy) < bh ? band.row1[c] / (8 * sy) : bh;
                 if(r0 >= r1) { continue; }                       // band below the image (canvas padding only)
                 JOB_TRY(j2p_planes_rows_to_coefficients_sub(&band.ref[c], sx, sy, bw, r0, r1, d.out_quant[c], d.out_coef[c] + (size_t)r0 * bw * 64));
@@ -321,7 +336,7 @@ int deliver(const Job &j, const Band &band)
         const j2p_job &d = j.desc;
         switch(j.out) {
         // (validate_job lets at most one of the three be asked for; none: out_planes only)
-        case Out::own: return d.out_bits ? deliver_samples(d, band) : d.out_tensor.data ? deliver_tensor_rows(d, band) : deliver_coefficients(d, band);
+        case Out::own: return d.out_bits ? deliver_samples(j, d, band) : d.out_tensor.data ? deliver_tensor_rows(j, d, band) : deliver_coefficients(j, d, band);
         case Out::resized: return deliver_resized(j, d, band);
         case Out::resampled: return deliver_resampled(j, d, band);
         case Out::outputs: return deliver_outputs(j, d, band);
@@ -464,6 +479,7 @@ int create_engines(const Job &j, int device, Engines &eng)
                         JOB_TRY(j2p_solver_create_from_decoded(s, device, nch, &d.planes[k], &grids->coef[k], d.weight[k], &d.pweight[k], d.iterations[k]));
                         break;
                 }
+                if(oriented(j)) { JOB_TRY(j2p_solver_set_orientation(*s, j.orientation, j.orient_w, j.orient_h)); }
         }
         return J2P_OK;
 }
@@ -527,7 +543,8 @@ void worker_main(j2p_batch *b, int device)
 // order below is part of the interface: file, JPEG, PNG, samples, outputs, resample, resize, then the pins. ----
 
 // a file job: the marker segments are read here, on the caller's thread and before any device is asked for work — what they
-// show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the sizes the job left zero are filled in from the file
+// show is refused at submit (J2P_EFORMAT, J2P_ENOTSUP); the plane sizes the job left zero are filled in from the file (the
+// image's: settle_orientation)
 int open_file(const Request &q, Job &j)
 {
         j2p_job &d = j.desc;
@@ -553,8 +570,42 @@ int open_file(const Request &q, Job &j)
                 if(!p.h_samp) { p.h_samp = k.h_samp; }
                 p.quant_table = k.quant;           // (the file's table: lives in the job's parse)
         }
-        if(!d.out_w) { d.out_w = info.width; }
-        if(!d.out_h) { d.out_h = info.height; }
+        return J2P_OK;
+}
+
+// The orientation that arrived next to the job (Job::orientation), settled at submit: the tag read from the file's bytes (J2P_ORIENTATION_EXIF; of a file in device memory,
+// from a copy of what precedes its scan), the source size a file job left zero taken from the file, and then the image size a
+// file job left zero: the upright one.
+int settle_orientation(const Request &q, Job &j)
+{
+        j2p_job &d = j.desc;
+        if(j.orientation) {
+                if(d.tile) { return j2p_fail(J2P_EINVAL, "job: upright output of a row-tiled job is not supported"); }
+                if(j.orientation == J2P_ORIENTATION_EXIF) {
+                        if(!q.file) { return j2p_fail(J2P_EINVAL, "job: J2P_ORIENTATION_EXIF needs a job with a file"); }
+                        if(j.file.on_device) {
+                                std::vector<uint8_t> head(j.file.parsed->info.scan_begin < q.file_size ? j.file.parsed->info.scan_begin : q.file_size);
+                                if(hipMemcpy(head.data(), q.file, head.size(), hipMemcpyDeviceToHost) != hipSuccess) {
+                                        return j2p_fail(J2P_EDEVICE, "job: the file's head could not be copied from device memory");
+                                }
+                                JOB_TRY(j2p_jpeg_orientation(head.data(), head.size(), &j.orientation));
+                        } else {
+                                JOB_TRY(j2p_jpeg_orientation(q.file, q.file_size, &j.orientation));
+                        }
+                }
+                if(j.orientation > 8) { return j2p_fail(J2P_EINVAL, "job: orientation %u (0: none, 1..8, J2P_ORIENTATION_EXIF)", j.orientation); }
+                if(q.file) {
+                        if(!j.orient_w) { j.orient_w = j.file.parsed->info.width; }
+                        if(!j.orient_h) { j.orient_h = j.file.parsed->info.height; }
+                }
+                if(j.orient_w == 0 || j.orient_h == 0) { return j2p_fail(J2P_EINVAL, "job: an orientation needs the source image's size (orient_w, orient_h)"); }
+        }
+        if(q.file) {
+                const j2p_jpeg_info &info = j.file.parsed->info;
+                const bool transposed = j.orientation >= 5;
+                if(!d.out_w) { d.out_w = j.orientation > 1 ? (transposed ? j.orient_h : j.orient_w) : info.width; }
+                if(!d.out_h) { d.out_h = j.orientation > 1 ? (transposed ? j.orient_w : j.orient_h) : info.height; }
+        }
         return J2P_OK;
 }
 
@@ -649,12 +700,14 @@ int pin(const j2p_batch &b, Job &j, int device, const char *what)
 int classify(const j2p_batch &b, const j2p_job &given, const Request &q, Job &j)
 {
         j.desc = given;
+        j.orientation = q.orientation, j.orient_w = q.orient_w, j.orient_h = q.orient_h;
         const j2p_job &d = j.desc;
         int samples_device = -1, tensor_device = -1;
         if(q.file) {
                 j.in = In::file;
                 JOB_TRY(open_file(q, j));
         }
+        JOB_TRY(settle_orientation(q, j));
         if(q.jpeg) {
                 j.out = Out::jpeg;
                 JOB_TRY(validate_jpeg(d, q));
@@ -702,8 +755,20 @@ int classify(const j2p_batch &b, const j2p_job &given, const Request &q, Job &j)
         return J2P_OK;
 }
 
-int submit(j2p_batch *b, const j2p_job *job, const Request &q, int *ticket)
+// what j2p_batch_next_orientation left for the calling thread's next submit
+thread_local struct {
+        const j2p_batch *batch = nullptr;
+        unsigned orientation = 0, orient_w = 0, orient_h = 0;
+} next_orientation;
+
+int submit(j2p_batch *b, const j2p_job *job, const Request &entry, int *ticket)
 {
+        // (consumed by this submit, whatever becomes of it)
+        Request q = entry;
+        if(next_orientation.batch && next_orientation.batch == b) {
+                q.orientation = next_orientation.orientation, q.orient_w = next_orientation.orient_w, q.orient_h = next_orientation.orient_h;
+        }
+        next_orientation.batch = nullptr;
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         std::unique_ptr<Job> j(new(std::nothrow) Job());
         if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
@@ -842,6 +907,16 @@ void j2p_debug_job_layout(size_t *size, size_t *out_tensor_offset)
 {
         if(size) { *size = sizeof(j2p_job); }
         if(out_tensor_offset) { *out_tensor_offset = offsetof(j2p_job, out_tensor); }
+}
+
+int j2p_batch_next_orientation(j2p_batch *b, unsigned orientation, unsigned orient_w, unsigned orient_h)
+{
+        if(!b) { return j2p_fail(J2P_EINVAL, "batch is NULL"); }
+        next_orientation.batch = orientation ? b : nullptr;
+        next_orientation.orientation = orientation;
+        next_orientation.orient_w = orient_w;
+        next_orientation.orient_h = orient_h;
+        return J2P_OK;
 }
 
 int j2p_batch_wait(j2p_batch *b, int ticket)

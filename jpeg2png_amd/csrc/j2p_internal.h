@@ -173,6 +173,8 @@ struct j2p_solver_view {
         unsigned row0, rows;            // the canvas rows this solver holds: [row0, row0 + rows)
         bool whole;                     // ... which are all of them (not a band)
         bool mid_iteration;             // between the two phases of an iteration: the planes are not an iterate
+        unsigned orientation;           // j2p_solver_set_orientation: 1 = none, otherwise of a source image of orient_w x orient_h
+        unsigned orient_w, orient_h;
 };
 j2p_solver_view j2p_solver_view_of(const j2p_solver *s);         // s is not NULL
 // the device address of canvas row y (one of the solver's own) of channel c in the current iterate; the rows after it follow
@@ -185,6 +187,10 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
 int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out);
 // the size of that block now (0: none yet): a request beyond it gets ANOTHER block, and what the old one held is lost
 size_t j2p_solver_scratch_bytes(const j2p_solver *s);
+// the same kind of block, a second one, for the upright planes of the calls this solver is the first plane of (j2p_output.hip,
+// "upright planes"): live
+// together with the scratch, which the forms that run on the upright planes use as before
+int j2p_solver_upright(j2p_solver *s, size_t bytes, float **out);
 
 // ---- the JPEG codec (j2p_codec.hip) ----
 // offsets of the parts of one block of device memory, in the order asked for, each aligned to 256 bytes

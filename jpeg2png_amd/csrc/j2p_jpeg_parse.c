@@ -3,6 +3,7 @@
 // in, the component-to-table map, the restart interval and the byte range of the entropy-coded data.  The C twin of the
 // Python package's jpeg_header(), which tests/test_decode_cpu.py holds it against.  No allocation, no global state; every
 // read is checked against `size` first (tests/c/jpeg_parse_main.c runs it over prefixes and damaged copies under sanitizers).
+// At the end, independent of all that: the reader of the EXIF Orientation tag (j2p_jpeg_orientation; tests/c/orientation_main.c).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -256,4 +257,65 @@ int j2p_jpeg_parse(const uint8_t *file, size_t size, j2p_jpeg_info *info)
                 memset(info, 0, sizeof(*info));
         }
         return rc;
+}
+
+// ---- the EXIF Orientation tag (include/jpeg2png_amd.h: "Upright output") ----
+// 16 / 32 bits of a TIFF structure in its byte order
+static unsigned tiff16(const uint8_t *p, int big) { return big ? ((unsigned)p[0] << 8) | p[1] : ((unsigned)p[1] << 8) | p[0]; }
+static unsigned long tiff32(const uint8_t *p, int big)
+{
+        return big ? ((unsigned long)p[0] << 24) | ((unsigned long)p[1] << 16) | ((unsigned long)p[2] << 8) | p[3]
+                   : ((unsigned long)p[3] << 24) | ((unsigned long)p[2] << 16) | ((unsigned long)p[1] << 8) | p[0];
+}
+
+// the tag of one TIFF structure of n bytes (what follows "Exif\0\0" in its segment), 1 where it has none that counts
+static unsigned tiff_orientation(const uint8_t *t, size_t n)
+{
+        if(n < 8) { return 1; }
+        int big;
+        if(t[0] == 'M' && t[1] == 'M') { big = 1; }
+        else if(t[0] == 'I' && t[1] == 'I') { big = 0; }
+        else { return 1; }
+        if(tiff16(t + 2, big) != 42) { return 1; }
+        const unsigned long ifd = tiff32(t + 4, big);
+        if(ifd > n - 2) { return 1; }                   // (n >= 8: no wrap)
+        const unsigned entries = tiff16(t + ifd, big);
+        if((size_t)entries * 12 > n - 2 - ifd) { return 1; }     // an entry count that overruns the segment: a damaged structure
+        for(unsigned k = 0; k < entries; k++) {
+                const uint8_t *e = t + ifd + 2 + 12 * (size_t)k;
+                if(tiff16(e, big) != 0x0112) { continue; }
+                if(tiff16(e + 2, big) != 3 || tiff32(e + 4, big) != 1) { return 1; }      // SHORT, one value
+                const unsigned v = tiff16(e + 8, big);
+                return v >= 1 && v <= 8 ? v : 1;
+        }
+        return 1;
+}
+
+int j2p_jpeg_orientation(const uint8_t *file, size_t size, unsigned *orientation)
+{
+        if(!file || !orientation) { return refuse(J2P_EINVAL, "NULL argument"); }
+        *orientation = 1;
+        if(size < 4 || file[0] != 0xff || file[1] != 0xd8) { return J2P_OK; }
+        size_t pos = 2;
+        for(;;) {
+                if(pos + 2 > size || file[pos] != 0xff) { return J2P_OK; }
+                const unsigned marker = file[pos + 1];
+                if(marker == 0xff) {            // a fill byte
+                        pos++;
+                        continue;
+                }
+                pos += 2;
+                if(marker == 0x01 || (marker >= 0xd0 && marker <= 0xd8)) { continue; }  // TEM, RSTn, SOI: no segment
+                if(marker == 0xd9 || marker == 0xda) { return J2P_OK; }                 // EOI, SOS: nothing is read beyond
+                if(pos + 2 > size) { return J2P_OK; }
+                const size_t length = be16(file + pos);
+                if(length < 2 || length > size - pos) { return J2P_OK; }
+                const uint8_t *body = file + pos + 2;
+                const size_t n = length - 2;
+                pos += length;
+                if(marker == 0xe1 && n >= 6 && memcmp(body, "Exif\0\0", 6) == 0) {
+                        *orientation = tiff_orientation(body + 6, n - 6);
+                        return J2P_OK;
+                }
+        }
 }

@@ -2,6 +2,7 @@
 // or cropped and resized (area, or triangle / cubic taps; several such outputs in one call), to quantised JPEG
 // coefficients, and — those handed to the codec's coder (j2p_codec.hip) — to the entropy-coded JPEG file itself; and samples
 // left in device memory for the codec's PNG coder, to the PNG file (include/jpeg2png_amd.h: the j2p_planes_* functions).
+// Every form of an oriented solver (j2p_solver_set_orientation) runs on the solver's upright planes instead: "upright planes" below.
 //
 // A translation unit of its own, with its own device code (j2p_output_kernels.hip.h): it changes more often than the solver
 // and must not recompile the solver's kernels.  It sees of a solver what j2p_solver_view and j2p_solver_row give
@@ -20,13 +21,134 @@ using namespace j2p;
 
 extern "C" {
 
+// ---- upright planes: k_upright_rows, k_upright_transpose ----
+// An oriented solver (j2p_solver_set_orientation, 2..8) shows the forms below not its canvas but UPRIGHT planes: the
+// permutation of the current iterate, replication included (include/jpeg2png_amd.h, "Upright output").  This is the one place
+// that knows: form_view gives the canvas a call's extents are checked against, plane_rows the address of a row — and notes in
+// the call's Upright which planes have to be permuted — and upright_queue, which a form calls once, after its last check and
+// before its first launch, queues those permutations.  An unoriented solver passes through all three untouched: no launch, no
+// allocation.
+// Ordering rule: every upright plane of a call — also those of OTHER solvers (`-s`: three solvers, one channel each) — lies in the
+// block of the call's first solver, the owner, on whose stream the form launches, and is written there: the block is written,
+// read and regrown in that one stream's order only, so no call can overwrite or give back what another stream still reads.  The
+// other solvers' iterates are read after their streams have been waited for, as the forms always did.
+struct Upright {
+        j2p_solver *owner = nullptr;    // the first oriented plane's solver: planes[0].solver of the call
+        unsigned slots = 3;             // planes the call reads at most (set by the caller before plane_rows)
+        unsigned n = 0;                 // distinct planes noted
+        struct Plane {
+                const j2p_solver *solver;
+                unsigned channel;
+                const float *src;       // row 0 of the solver's iterate
+                unsigned src_stride;    // that solver's canvas width: solvers of one call may differ in it
+                float *dst;
+        } plane[3];
+        UprightGeom g;                  // the same for all of them (same_orientation) but for src_stride
+        bool transposed = false;        // orientations 5..8
+};
+
+static j2p_solver_view form_view(const j2p_solver *solver)
+{
+        j2p_solver_view v = j2p_solver_view_of(solver);
+        if(v.orientation > 1) {
+                const bool transposed = v.orientation >= 5;
+                v.W = ((transposed ? v.orient_h : v.orient_w) + 15) / 16 * 16;
+                v.H = ((transposed ? v.orient_w : v.orient_h) + 15) / 16 * 16;
+                v.row0 = 0;             // (whole: band solvers take no orientation)
+                v.rows = v.H;
+        }
+        return v;
+}
+
+// true when b's planes can stand next to a's in one call: the same orientation of the same source image
+static bool same_orientation(const j2p_solver_view &a, const j2p_solver_view &b)
+{
+        const bool oa = a.orientation > 1, ob = b.orientation > 1;
+        return oa == ob && (!oa || (a.orientation == b.orientation && a.orient_w == b.orient_w && a.orient_h == b.orient_h));
+}
+
+// the address of row y of (solver, channel) as a form sees it, s = form_view(solver): the rows after it follow at s.W floats
+static int plane_rows(const j2p_plane_ref &plane, const j2p_solver_view &s, unsigned y, Upright &up, const float **row)
+{
+        if(s.orientation <= 1) { return j2p_solver_row(plane.solver, plane.channel, y, row); }
+        if(plane.channel >= s.nch || y >= s.H) { return j2p_fail(J2P_EINVAL, "row %u of channel %u is not one of the upright canvas", y, plane.channel); }
+        for(unsigned k = 0; k < up.n; k++) {
+                if(up.plane[k].solver == plane.solver && up.plane[k].channel == plane.channel) {       // the same plane twice in one call: permuted once
+                        *row = up.plane[k].dst + (size_t)y * s.W;
+                        return J2P_OK;
+                }
+        }
+        if(up.n == 3) { return j2p_fail(J2P_EINVAL, "more than three planes in one call"); }
+        if(!up.owner) { up.owner = plane.solver; }
+        const size_t plane_floats = (size_t)s.W * s.H;
+        // (the same size for every plane of a call — at least the owner's channels, so that a joint solver's block has one size
+        // whatever a call reads: only a call's first request can move the block)
+        const unsigned owner_nch = j2p_solver_view_of(up.owner).nch, slots = up.slots > owner_nch ? up.slots : owner_nch;
+        float *base = nullptr;
+        if(const int rc = j2p_solver_upright(up.owner, plane_floats * slots * sizeof(float), &base); rc != J2P_OK) { return rc; }
+        Upright::Plane &P = up.plane[up.n];
+        P.solver = plane.solver;
+        P.channel = plane.channel;
+        P.dst = base + plane_floats * up.n;
+        if(const int rc = j2p_solver_row(plane.solver, plane.channel, 0, &P.src); rc != J2P_OK) { return rc; }
+        P.src_stride = j2p_solver_view_of(plane.solver).W;
+        up.n++;
+        *row = P.dst + (size_t)y * s.W;
+        const bool transposed = s.orientation >= 5;
+        up.transposed = transposed;
+        UprightGeom &g = up.g;
+        g.w = s.orient_w;
+        g.h = s.orient_h;
+        g.uw = transposed ? s.orient_h : s.orient_w;
+        g.uh = transposed ? s.orient_w : s.orient_h;
+        g.UW = s.W;
+        g.UH = s.H;
+        g.src_stride = 0;               // (per launch: upright_queue)
+        g.flip_x = s.orientation == 2 || s.orientation == 3 || s.orientation == 7 || s.orientation == 8;
+        g.flip_y = s.orientation == 3 || s.orientation == 4 || s.orientation == 6 || s.orientation == 7;
+        return J2P_OK;
+}
+
+// Queues what plane_rows noted on `stream`, the owner's, on which the form launches: one launch for the planes that share a
+// source stride (all of a joint solver's), so at most one per solver.  The caller has waited for the other solvers' streams.
+static int upright_queue(const Upright &up, hipStream_t stream)
+{
+        bool done[3] = {false, false, false};
+        for(unsigned i = 0; i < up.n; i++) {
+                if(done[i]) { continue; }
+                UprightGeom g = up.g;
+                g.src_stride = up.plane[i].src_stride;
+                const float *src[3] = {nullptr, nullptr, nullptr};
+                float *dst[3] = {nullptr, nullptr, nullptr};
+                unsigned n = 0;
+                for(unsigned k = i; k < up.n; k++) {
+                        if(done[k] || up.plane[k].src_stride != g.src_stride) { continue; }
+                        src[n] = up.plane[k].src;
+                        dst[n] = up.plane[k].dst;
+                        done[k] = true;
+                        n++;
+                }
+                const UprightPlanes p = {src[0], src[1], src[2], dst[0], dst[1], dst[2]};
+                if(up.transposed) {
+                        hipLaunchKernelGGL(k_upright_transpose, dim3((g.UW + kUprightTile - 1) / kUprightTile, (g.UH + kUprightTile - 1) / kUprightTile, n),
+                                           dim3(256), 0, stream, p, g);
+                } else {
+                        hipLaunchKernelGGL(k_upright_rows, dim3((g.UW + 255) / 256, (g.UH + 3) / 4, n), dim3(256), 0, stream, p, g);
+                }
+                const hipError_t e = hipGetLastError();
+                if(e != hipSuccess) { return j2p_fail(J2P_EDEVICE, "upright planes: %s", hipGetErrorString(e)); }
+        }
+        return J2P_OK;
+}
+
 // What the conversions of solved planes start from: rows [y0, y1) x w columns of the image from nplane (3 or 1) (solver,
 // channel) pairs on one device that all hold those canvas rows.  Checks arguments and state, gives per plane the first of
 // those rows in the current iterate and its stride in floats and the view of planes[0].solver, and waits for the streams of
 // the other solvers: the caller launches on planes[0].solver's.  `whole`: called as a whole-canvas form, which band solvers
-// refuse.  what: "to_rgb", "to_grey" or "to_tensor", for the messages.
+// refuse.  what: "to_rgb", "to_grey" or "to_tensor", for the messages.  Oriented solvers: canvas, rows and view are those of the
+// upright planes (form_view), and `up` is what the caller hands to upright_queue before it launches.
 static int resolve_rows(const char *what, const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1,
-                        const float *ptr[3], unsigned stride[3], j2p_solver_view &first)
+                        const float *ptr[3], unsigned stride[3], j2p_solver_view &first, Upright &up)
 {
         if(w == 0 || y0 >= y1) { return j2p_fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
         for(unsigned i = 0; whole && i < nplane; i++) {
@@ -35,17 +157,20 @@ static int resolve_rows(const char *what, const j2p_plane_ref *planes, unsigned 
                 }
         }
         for(unsigned i = 0; i < 3; i++) { ptr[i] = nullptr; stride[i] = 0; }
+        up.slots = nplane;
         for(unsigned i = 0; i < nplane; i++) {
-                const j2p_solver_view s = planes[i].solver ? j2p_solver_view_of(planes[i].solver) : j2p_solver_view{};
+                const j2p_solver_view s = planes[i].solver ? form_view(planes[i].solver) : j2p_solver_view{};
                 if(!planes[i].solver || planes[i].channel >= s.nch) { return j2p_fail(J2P_EINVAL, "plane %u: bad solver/channel", i); }
                 if(i == 0) { first = s; }
                 if(s.device != first.device) { return j2p_fail(J2P_EINVAL, "planes live on different devices"); }
+                if(!whole && s.orientation > 1) { return j2p_fail(J2P_ESTATE, "the rows forms take no oriented solver (plane %u)", i); }
+                if(!same_orientation(first, s)) { return j2p_fail(J2P_EINVAL, "plane %u: another orientation or source size than plane 0's", i); }
                 if(s.W < w || y0 < s.row0 || y1 > s.row0 + s.rows) {
                         return j2p_fail(J2P_EINVAL, "plane %u: rows [%u,%u) x %u columns are not inside the solver's [%u,%u) x %u", i, y0, y1, w,
                                     s.row0, s.row0 + s.rows, s.W);
                 }
                 if(s.mid_iteration) { return j2p_fail(J2P_ESTATE, "%s between the two phases of an iteration", what); }
-                if(const int rc = j2p_solver_row(planes[i].solver, planes[i].channel, y0, &ptr[i]); rc != J2P_OK) { return rc; }
+                if(const int rc = plane_rows(planes[i], s, y0, up, &ptr[i]); rc != J2P_OK) { return rc; }
                 stride[i] = s.W;
         }
         DeviceGuard guard(first.device);
@@ -65,13 +190,18 @@ static int convert_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole
         const float *ptr[3];
         unsigned stride[3];
         j2p_solver_view s0;
-        if(const int rc = resolve_rows(what, planes, nplane, whole, w, y0, y1, ptr, stride, s0); rc != J2P_OK) { return rc; }
+        Upright up;
+        if(const int rc = resolve_rows(what, planes, nplane, whole, w, y0, y1, ptr, stride, s0, up); rc != J2P_OK) { return rc; }
         const unsigned h = y1 - y0;
         DeviceGuard guard(s0.device);
         const size_t bytes = (size_t)w * h * (size_t)nplane * (bits / 8);
         void *dout = nullptr;
         size_t dout_bytes = 0;
         HIP_TRY(j2p_pool_take(s0.device, bytes, &dout, &dout_bytes));       // pooled like the solvers' arenas: no hipFree per image
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) {
+                j2p_pool_give(s0.device, dout, dout_bytes);
+                return rc;
+        }
         hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, s0.stream, ptr[0], stride[0],
                            ptr[1], stride[1], ptr[2], stride[2], w, h, bits, static_cast<uint8_t *>(dout));
         hipError_t e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s0.stream);
@@ -150,17 +280,24 @@ static const TensorKernel kTensorKernels[2][4][3] = {J2P_TENSOR_ROWS(3, J2P_TENS
 
 // What both tensor outputs check before they launch, in this order: the arguments, the solvers' state and rows (resolve_rows),
 // the 16-byte alignment of the canvas rows, and the destination's dtype, strides, address, scale / bias and device.  Gives the
-// planes' first rows and strides, the kernels' view of the destination and the view of planes[0].solver.
+// planes' first rows and strides, the kernels' view of the destination and the view of planes[0].solver.  In two parts: a call
+// of several outputs resolves its planes once (tensor_resolve for its first output) and checks every further destination with
+// tensor_destination alone.
+static int tensor_destination(const j2p_tensor *out, unsigned nplane, const j2p_solver_view &s0, TensorOut &o);
 static int tensor_resolve(const j2p_plane_ref *planes, unsigned nplane, bool whole, unsigned w, unsigned y0, unsigned y1, const j2p_tensor *out,
-                          const float *ptr[3], unsigned stride[3], TensorOut &o, j2p_solver_view &s0)
+                          const float *ptr[3], unsigned stride[3], TensorOut &o, j2p_solver_view &s0, Upright &up)
 {
         if(!planes || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(nplane != 1 && nplane != 3) { return j2p_fail(J2P_EINVAL, "to_tensor: three planes (RGB) or one (greyscale), not %u", nplane); }
-        if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride, s0); rc != J2P_OK) { return rc; }
+        if(const int rc = resolve_rows("to_tensor", planes, nplane, whole, w, y0, y1, ptr, stride, s0, up); rc != J2P_OK) { return rc; }
         for(unsigned i = 0; i < nplane; i++) {
                 // what k_to_tensor's 16-byte loads rest on (see there): true of every solver j2p_solver_create makes
                 if(stride[i] % 4 != 0 || reinterpret_cast<uintptr_t>(ptr[i]) % 16 != 0) { return j2p_fail(J2P_ESTATE, "plane %u: canvas rows are not 16-byte aligned", i); }
         }
+        return tensor_destination(out, nplane, s0, o);
+}
+static int tensor_destination(const j2p_tensor *out, unsigned nplane, const j2p_solver_view &s0, TensorOut &o)
+{
         if(out->dtype != J2P_DTYPE_U8 && out->dtype != J2P_DTYPE_F16 && out->dtype != J2P_DTYPE_BF16 && out->dtype != J2P_DTYPE_F32) {
                 return j2p_fail(J2P_EINVAL, "to_tensor: unknown dtype %d", out->dtype);
         }
@@ -204,8 +341,10 @@ static int tensor_rows(const j2p_plane_ref *planes, unsigned nplane, bool whole,
         unsigned stride[3];
         TensorOut o;
         j2p_solver_view s0;
-        if(const int rc = tensor_resolve(planes, nplane, whole, w, y0, y1, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        Upright up;
+        if(const int rc = tensor_resolve(planes, nplane, whole, w, y0, y1, out, ptr, stride, o, s0, up); rc != J2P_OK) { return rc; }
         DeviceGuard guard(s0.device);
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
         const unsigned h = y1 - y0;
         const int path = tensor_path(w, nplane, out->dtype, out->stride_c, out->stride_y, out->stride_x, reinterpret_cast<uintptr_t>(out->data));
         const TensorKernel kernel = kTensorKernels[nplane == 3 ? 0 : 1][out->dtype][path];
@@ -296,8 +435,10 @@ int j2p_planes_to_tensor_resized(const j2p_plane_ref planes[], unsigned nplane, 
         unsigned stride[3];
         TensorOut o;
         j2p_solver_view s0;
-        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        Upright up;
+        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0, up); rc != J2P_OK) { return rc; }
         DeviceGuard guard(s0.device);
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
         ResizeGeom g;
         g.box_x = r->box_x;
         g.box_y = r->box_y;
@@ -439,11 +580,13 @@ int j2p_planes_to_tensor_resampled(const j2p_plane_ref planes[], unsigned nplane
         unsigned stride[3];
         TensorOut o;
         j2p_solver_view s0;
-        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0); rc != J2P_OK) { return rc; }
+        Upright up;
+        if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, out, ptr, stride, o, s0, up); rc != J2P_OK) { return rc; }
         DeviceGuard guard(s0.device);
         const OutputPlan p = plan_output(*r);
         void *scratch = nullptr;
         if(const int rc = j2p_solver_scratch(planes[0].solver, p.words * 4, &scratch); rc != J2P_OK) { return rc; }
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
         FilterAxis ax, ay;
         FilterGeom g;
         bind_output(*r, p, static_cast<int *>(scratch), ax, ay, g);
@@ -515,8 +658,11 @@ int j2p_planes_to_tensors_resampled(const j2p_plane_ref planes[], unsigned nplan
         for(unsigned i = 0; i < n; i++) {
                 if(const char *why = j2p_resample_error(&outs[i].r, w, h)) { return j2p_fail(J2P_EINVAL, "to_tensors: output %u: %s", i, why); }
         }
+        Upright up;
         for(unsigned i = 0; i < n; i++) {
-                if(const int rc = tensor_resolve(planes, nplane, true, w, 0, h, &outs[i].t, ptr, stride, o[i], s0); rc != J2P_OK) { return rc; }
+                const int rc = i == 0 ? tensor_resolve(planes, nplane, true, w, 0, h, &outs[0].t, ptr, stride, o[0], s0, up)
+                                      : tensor_destination(&outs[i].t, nplane, s0, o[i]);
+                if(rc != J2P_OK) { return rc; }
         }
         DeviceGuard guard(s0.device);
         j2p_resample specs[kMaxOutputs];
@@ -529,6 +675,7 @@ int j2p_planes_to_tensors_resampled(const j2p_plane_ref planes[], unsigned nplan
         plan_call(n, specs, dtypes, c);
         void *scratch = nullptr;
         if(const int rc = j2p_solver_scratch(planes[0].solver, c.words * 4, &scratch); rc != J2P_OK) { return rc; }
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
         FilterAxes axes;
         FilterGeom g[kMaxOutputs];
         axes.n = 2 * n;
@@ -630,11 +777,11 @@ struct QuantiseLaunch {
 // In three steps, so that the JPEG file's coder can check every plane before it queues anything and keep the coefficients
 // on the device: quantise_check (arguments and state), quantise_queue (the launch), quantise_rows (both, and the download).
 static int quantise_check(const j2p_plane_ref *plane, bool whole, unsigned sub_w, unsigned sub_h, unsigned blocks_w, unsigned r0,
-                          unsigned r1, const uint16_t quant_table[64], QuantiseLaunch &q)
+                          unsigned r1, const uint16_t quant_table[64], QuantiseLaunch &q, Upright &up)
 {
         if(!plane || !quant_table) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(blocks_w == 0 || r0 >= r1) { return j2p_fail(J2P_EINVAL, whole ? "empty image" : "empty row range"); }
-        const j2p_solver_view s = plane->solver ? j2p_solver_view_of(plane->solver) : j2p_solver_view{};
+        const j2p_solver_view s = plane->solver ? form_view(plane->solver) : j2p_solver_view{};
         if(whole && plane->solver && !s.whole) {
                 return j2p_fail(J2P_ESTATE, "to_coefficients needs a whole-canvas solver (bands: the j2p_planes_rows_to_coefficients forms)");
         }
@@ -642,6 +789,7 @@ static int quantise_check(const j2p_plane_ref *plane, bool whole, unsigned sub_w
                 return j2p_fail(J2P_EINVAL, "to_coefficients: sampling factors %ux%u (1 and 2 are supported)", sub_w, sub_h);
         }
         if(!plane->solver || plane->channel >= s.nch) { return j2p_fail(J2P_EINVAL, "plane 0: bad solver/channel"); }
+        if(!whole && s.orientation > 1) { return j2p_fail(J2P_ESTATE, "the rows forms take no oriented solver"); }
         QuantSteps &steps = q.steps;
         for(int j = 0; j < 64; j++) {
                 if(quant_table[j] == 0) { return j2p_fail(J2P_EINVAL, "to_coefficients: quantisation table entry %d is zero", j); }
@@ -661,7 +809,7 @@ static int quantise_check(const j2p_plane_ref *plane, bool whole, unsigned sub_w
         if(s.mid_iteration) { return j2p_fail(J2P_ESTATE, "to_coefficients between the two phases of an iteration"); }
         const unsigned first = (unsigned)(step_y * r0);
         const float *src = nullptr;
-        if(const int rc = j2p_solver_row(plane->solver, plane->channel, first, &src); rc != J2P_OK) { return rc; }
+        if(const int rc = plane_rows(*plane, s, first, up, &src); rc != J2P_OK) { return rc; }
         q.s = s;
         q.src = src;
         q.rows = (unsigned)(row_end - first);
@@ -681,13 +829,19 @@ static int quantise_rows(const j2p_plane_ref *plane, bool whole, unsigned sub_w,
 {
         if(!out_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         QuantiseLaunch q;
-        if(const int rc = quantise_check(plane, whole, sub_w, sub_h, blocks_w, r0, r1, quant_table, q); rc != J2P_OK) { return rc; }
+        Upright up;
+        up.slots = 1;
+        if(const int rc = quantise_check(plane, whole, sub_w, sub_h, blocks_w, r0, r1, quant_table, q, up); rc != J2P_OK) { return rc; }
         const j2p_solver_view &s = q.s;
         DeviceGuard guard(s.device);
         const size_t bytes = (size_t)blocks_w * (r1 - r0) * 64 * sizeof(int16_t);
         void *dout = nullptr;
         size_t dout_bytes = 0;
         HIP_TRY(j2p_pool_take(s.device, bytes, &dout, &dout_bytes));
+        if(const int rc = upright_queue(up, s.stream); rc != J2P_OK) {
+                j2p_pool_give(s.device, dout, dout_bytes);
+                return rc;
+        }
         quantise_queue(q, sub_w, sub_h, blocks_w, r0, r1, s.stream, static_cast<int16_t *>(dout));
         hipError_t e = hipGetLastError();
         if(e == hipSuccess) { e = hipMemcpyAsync(out_host, dout, bytes, hipMemcpyDeviceToHost, s.stream); }
@@ -731,10 +885,13 @@ int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, nplane);
         // every check of every plane, before anything is queued
         QuantiseLaunch q[3];
+        Upright up;
+        up.slots = nplane;
         for(unsigned c = 0; c < nplane; c++) {
                 const unsigned sx = c ? g.sub_w : 1, sy = c ? g.sub_h : 1;
-                if(const int rc = quantise_check(&planes[c], true, sx, sy, g.bw[c], 0, g.bh[c], spec->quant[c], q[c]); rc != J2P_OK) { return rc; }
+                if(const int rc = quantise_check(&planes[c], true, sx, sy, g.bw[c], 0, g.bh[c], spec->quant[c], q[c], up); rc != J2P_OK) { return rc; }
                 if(q[c].s.device != q[0].s.device) { return j2p_fail(J2P_EINVAL, "planes live on different devices"); }
+                if(!same_orientation(q[0].s, q[c].s)) { return j2p_fail(J2P_EINVAL, "plane %u: another orientation or source size than plane 0's", c); }
         }
         DeviceGuard guard(q[0].s.device);
         const hipStream_t stream = q[0].s.stream;
@@ -742,6 +899,7 @@ int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j
         for(unsigned c = 1; c < nplane; c++) {
                 if(planes[c].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(q[c].s.stream)); }
         }
+        if(const int rc = upright_queue(up, stream); rc != J2P_OK) { return rc; }
         j2p_solver *const owner = planes[0].solver;
         return j2p_encode_scan(
                 stream, *spec, nplane,
@@ -769,10 +927,13 @@ int j2p_planes_to_png(const j2p_plane_ref planes[], unsigned nplane, const j2p_p
         const float *ptr[3];
         unsigned stride[3];
         j2p_solver_view s0;
-        if(const int rc = resolve_rows(nplane == 3 ? "to_rgb" : "to_grey", planes, nplane, true, spec->width, 0, spec->height, ptr, stride, s0); rc != J2P_OK) {
+        Upright up;
+        if(const int rc = resolve_rows(nplane == 3 ? "to_rgb" : "to_grey", planes, nplane, true, spec->width, 0, spec->height, ptr, stride, s0, up);
+           rc != J2P_OK) {
                 return rc;
         }
         DeviceGuard guard(s0.device);
+        if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
         j2p_solver *const owner = planes[0].solver;
         const unsigned w = spec->width, h = spec->height, bits = spec->bits;
         return j2p_png_write(

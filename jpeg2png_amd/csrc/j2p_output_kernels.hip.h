@@ -1,7 +1,8 @@
 // jpeg2png_amd — gfx950 device code of the output stage: what turns solved planes into samples (k_to_samples), tensor
 // elements (k_to_tensor, k_to_tensor_resized, k_filter_taps + k_to_tensor_filtered, and for several outputs in one call
 // k_filter_taps_outputs + k_to_tensors_filtered) and quantised JPEG coefficients (k_quantise_blocks; from there to the
-// entropy-coded file: j2p_codec_kernels.hip.h).  A device translation
+// entropy-coded file: j2p_codec_kernels.hip.h), and what lays an oriented solver's planes upright in front of any of them
+// (k_upright_rows, k_upright_transpose).  A device translation
 // unit of its own (j2p_output.hip), so that an edit here does not recompile the solver's kernels (j2p_kernels.hip.h), with
 // which it shares only j2p_dct.hip.h.  Compiled with the same flags: -ffp-contract=off, no fast-math, correctly rounded `/`.
 #pragma once
@@ -1116,5 +1117,90 @@ __global__ __launch_bounds__(256) void k_to_tensors_filtered(const float *yp, un
 J2P_FILTERED_OUTPUTS_KERNELS(3)
 J2P_FILTERED_OUTPUTS_KERNELS(1)
 #undef J2P_FILTERED_OUTPUTS_KERNELS
+
+// ---------------------------------------------------------------------------
+// Upright planes: the EXIF orientation (2..8) applied to a solver's current iterate as a pure permutation, replication
+// included (include/jpeg2png_amd.h: j2p_solver_set_orientation states the map).  U[y][x] = I[sy][sx] for every (x, y) of the
+// upright canvas UW x UH; beyond the upright image uw x uh the destination coordinate is clamped BEFORE the map, so the
+// canvas's last columns and rows replicate the image's and every load stays inside the source image.  No arithmetic touches
+// a value: every output form on U gives the bits it gives on a canvas that held U.
+// With (u, v) = (x, y), or (y, x) for the transposing orientations 5..8: sx = flip_x ? w - 1 - u : u, sy = flip_y ? h - 1 - v : v.
+// Up to three planes per launch (blockIdx.z), named members picked with compares: an array among the kernel arguments,
+// indexed by a register or merely passed on by reference, is copied into private memory.
+// ---------------------------------------------------------------------------
+struct UprightGeom {
+        unsigned w, h;                  // the source image
+        unsigned uw, uh;                // the upright image: w x h, or h x w when transposing
+        unsigned UW, UH;                // the upright canvas (the destination's stride and rows)
+        unsigned src_stride;            // the solver's canvas width
+        unsigned flip_x, flip_y;
+};
+struct UprightPlanes {
+        const float *src0, *src1, *src2;
+        float *dst0, *dst1, *dst2;
+};
+
+// Orientations 2..4: rows stay rows.  A workgroup copies 4 destination rows x 256 columns, a lane one column of each row: a
+// wavefront's loads and stores are 256 consecutive bytes either way (a reversed row is read backwards, lane by lane, from
+// the same lines).
+__global__ __launch_bounds__(256) void k_upright_rows(UprightPlanes p, UprightGeom g)
+{
+        const float *src = blockIdx.z == 0 ? p.src0 : (blockIdx.z == 1 ? p.src1 : p.src2);
+        float *dst = blockIdx.z == 0 ? p.dst0 : (blockIdx.z == 1 ? p.dst1 : p.dst2);
+        const unsigned x = blockIdx.x * 256 + threadIdx.x;
+        if(x >= g.UW) { return; }
+        const unsigned cx = x < g.uw ? x : g.uw - 1;
+        const unsigned sx = g.flip_x ? g.w - 1 - cx : cx;
+        float v[4];
+#pragma unroll
+        for(unsigned k = 0; k < 4; k++) {
+                const unsigned y = blockIdx.y * 4 + k;
+                const unsigned cy = y < g.uh ? y : g.uh - 1;
+                const unsigned sy = g.flip_y ? g.h - 1 - cy : cy;
+                v[k] = src[(size_t)sy * g.src_stride + sx];
+        }
+#pragma unroll
+        for(unsigned k = 0; k < 4; k++) {
+                const unsigned y = blockIdx.y * 4 + k;
+                if(y < g.UH) { dst[(size_t)y * g.UW + x] = v[k]; }
+        }
+}
+
+// Orientations 5..8: a destination tile of kUprightTile x kUprightTile goes through LDS.  Loading, wavefront r of 4 takes the
+// tile's destination columns i = r, r + 4, ...: those are source ROWS, and its lanes j run along the source row (the
+// destination's y), so a load instruction reads 256 consecutive bytes.  Storing, a wavefront takes destination rows j and its
+// lanes i run along x: 256 consecutive bytes again.  The tile is tile[i][j] with a pitch of kUprightTile + 1 floats: the
+// row-wise ds_write_b32 of the load phase puts a half-wavefront's 32 lanes on 32 consecutive banks, and the column-wise
+// ds_read_b32 of the store phase reads lane i at dword i * 65 + j, bank (i + j) % 32 — distinct over the 32 lanes that
+// can conflict.  16.25 KiB per workgroup.
+constexpr int kUprightTile = 64;
+__global__ __launch_bounds__(256) void k_upright_transpose(UprightPlanes p, UprightGeom g)
+{
+        __shared__ float tile[kUprightTile][kUprightTile + 1];
+        const float *src = blockIdx.z == 0 ? p.src0 : (blockIdx.z == 1 ? p.src1 : p.src2);
+        float *dst = blockIdx.z == 0 ? p.dst0 : (blockIdx.z == 1 ? p.dst1 : p.dst2);
+        const unsigned lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+        const unsigned x0 = blockIdx.x * kUprightTile, y0 = blockIdx.y * kUprightTile;
+        {
+                const unsigned y = y0 + lane;
+                const unsigned cy = y < g.uh ? y : g.uh - 1;
+                const unsigned sx = g.flip_x ? g.w - 1 - cy : cy;
+#pragma unroll 4
+                for(unsigned i = wave; i < (unsigned)kUprightTile; i += 4) {
+                        const unsigned x = x0 + i;
+                        const unsigned cx = x < g.uw ? x : g.uw - 1;
+                        const unsigned sy = g.flip_y ? g.h - 1 - cx : cx;
+                        tile[i][lane] = src[(size_t)sy * g.src_stride + sx];
+                }
+        }
+        __syncthreads();
+        const unsigned x = x0 + lane;
+        if(x >= g.UW) { return; }
+#pragma unroll 4
+        for(unsigned j = wave; j < (unsigned)kUprightTile; j += 4) {
+                const unsigned y = y0 + j;
+                if(y < g.UH) { dst[(size_t)y * g.UW + x] = tile[lane][j]; }
+        }
+}
 
 }  // namespace j2p

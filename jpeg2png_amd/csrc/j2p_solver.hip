@@ -113,6 +113,9 @@ struct j2p_solver {
         size_t arena_used = 0;   // ... of which carved (the pool may hand out a larger block)
         void *out_scratch = nullptr;     // the output stage's scratch (j2p_solver_scratch: the taps of a filtered tensor output); pooled, kept until destroy
         size_t out_scratch_bytes = 0;
+        void *upright = nullptr;         // the upright planes of an oriented solver (j2p_solver_upright), next to the scratch: the two are live together
+        size_t upright_bytes = 0;
+        unsigned orientation = 1, orient_w = 0, orient_h = 0;   // j2p_solver_set_orientation: 1 = none
         // reductions
         bool fold = false;       // level 1 of the norm reduction inside k_gradient (J2P_OPT_NORM_FOLD; default: norm_defaults)
         unsigned zone_d = 0, zone_b = 0, zone_c = 0;   // shares (1/256) of a gradient launch dealt as double / half / quarter tile rows (grad_item)
@@ -1186,6 +1189,7 @@ void j2p_solver_destroy(j2p_solver *s)
         if(s->live_registered) { j2p_live_add(s->device, s->live, -1); }
         j2p_pool_give(s->device, s->arena, s->arena_bytes);
         j2p_pool_give(s->device, s->out_scratch, s->out_scratch_bytes);
+        j2p_pool_give(s->device, s->upright, s->upright_bytes);
         (void)hipFree(s->logsums);
         (void)hipFree(s->log_band);
         (void)hipFree(s->trace);
@@ -1423,6 +1427,36 @@ int j2p_solver_output_scratch_bytes(const j2p_solver *s, size_t *bytes)
 {
         if(!s || !bytes) { return j2p_fail(J2P_EINVAL, "j2p_solver_output_scratch_bytes: bad argument"); }
         *bytes = s->out_scratch_bytes;
+        return J2P_OK;
+}
+
+int j2p_solver_upright_bytes(const j2p_solver *s, size_t *bytes)
+{
+        if(!s || !bytes) { return j2p_fail(J2P_EINVAL, "j2p_solver_upright_bytes: bad argument"); }
+        *bytes = s->upright_bytes;
+        return J2P_OK;
+}
+
+int j2p_solver_set_orientation(j2p_solver *s, unsigned orientation, unsigned width, unsigned height)
+{
+        if(!s) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(orientation < 1 || orientation > 8) { return j2p_fail(J2P_EINVAL, "set_orientation: orientation %u (1..8)", orientation); }
+        if(width == 0 || height == 0 || width > s->W || height > s->H) {
+                return j2p_fail(J2P_EINVAL, "set_orientation: a source image of %u x %u is not inside the canvas of %u x %u", width, height, s->W, s->H);
+        }
+        if(!s->whole && orientation != 1) { return j2p_fail(J2P_ESTATE, "set_orientation: a band solver has no upright output"); }
+        s->orientation = orientation;
+        s->orient_w = width;
+        s->orient_h = height;
+        return J2P_OK;
+}
+
+int j2p_solver_orientation(const j2p_solver *s, unsigned *orientation, unsigned *width, unsigned *height)
+{
+        if(!s) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(orientation) { *orientation = s->orientation; }
+        if(width) { *width = s->orient_w; }
+        if(height) { *height = s->orient_h; }
         return J2P_OK;
 }
 
@@ -2300,6 +2334,9 @@ j2p_solver_view j2p_solver_view_of(const j2p_solver *s)
         v.rows = s->rows;
         v.whole = s->whole;
         v.mid_iteration = s->grad_done;
+        v.orientation = s->orientation;
+        v.orient_w = s->orient_w;
+        v.orient_h = s->orient_h;
         return v;
 }
 
@@ -2314,23 +2351,38 @@ int j2p_solver_row(const j2p_solver *s, unsigned c, unsigned y, const float **ro
 
 size_t j2p_solver_scratch_bytes(const j2p_solver *s) { return s ? s->out_scratch_bytes : 0; }
 
-int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out)
+// one pooled block of the solver's, grown to at least `bytes`: what j2p_solver_scratch and j2p_solver_upright both do
+static int grow_block(j2p_solver *s, void *&block, size_t &block_bytes, size_t bytes)
 {
-        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        if(s->out_scratch_bytes < bytes) {
+        if(block_bytes < bytes) {
                 DeviceGuard guard(s->device);
                 // what is queued on the stream may still read the block that is given back: growing waits, reusing never does
                 HIP_TRY(hipStreamSynchronize(s->stream));
-                j2p_pool_give(s->device, s->out_scratch, s->out_scratch_bytes);
-                s->out_scratch = nullptr;
-                s->out_scratch_bytes = 0;
+                j2p_pool_give(s->device, block, block_bytes);
+                block = nullptr;
+                block_bytes = 0;
                 const size_t want = (bytes + ((size_t)256 << 10) - 1) & ~(((size_t)256 << 10) - 1);
                 void *p = nullptr;
                 size_t got = 0;
                 HIP_TRY(j2p_pool_take(s->device, want, &p, &got));
-                s->out_scratch = p;
-                s->out_scratch_bytes = got;
+                block = p;
+                block_bytes = got;
         }
+        return J2P_OK;
+}
+
+int j2p_solver_scratch(j2p_solver *s, size_t bytes, void **out)
+{
+        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const int rc = grow_block(s, s->out_scratch, s->out_scratch_bytes, bytes); rc != J2P_OK) { return rc; }
         *out = s->out_scratch;
+        return J2P_OK;
+}
+
+int j2p_solver_upright(j2p_solver *s, size_t bytes, float **out)
+{
+        if(!s || !out) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const int rc = grow_block(s, s->upright, s->upright_bytes, bytes); rc != J2P_OK) { return rc; }
+        *out = static_cast<float *>(s->upright);
         return J2P_OK;
 }
