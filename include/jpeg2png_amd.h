@@ -128,7 +128,16 @@ void j2p_pool_trim(void);
                                      channels, see "Zooming" at j2p_plane) is projected by the wide-footprint path wherever its strip
                                      lies inside canvas and coverage — except in the one-launch projection of small canvases with
                                      several samplings (J2P_OPT_MIXED_PROJECT); 0: the generic path for those channels — same bits */
+#define J2P_OPT_PHASE_ORDER 9     /* J2P_PHASE_ORDER(gradient, project): the order in which every XCD walks its run of each phase
+                                     launch's work; negative = default: the policy of j2p_geometry.h (j2p_phase_order_of).
+                                     The environment variable J2P_PHASE_ORDER, read at create, takes the same values — same bits */
+#define J2P_ORDER_FORWARD 0         /* every XCD walks its contiguous run of the canvas top-down */
+#define J2P_ORDER_REVERSE 1         /* every XCD walks its OWN run bottom-up: with the other phase forward each phase starts
+                                       on the rows the XCD's L2 touched last in the phase before (serpentine) */
+#define J2P_PHASE_ORDER(gradient, project) ((gradient) | ((project) << 1))
 int j2p_solver_debug_option(j2p_solver *s, int option, int value);
+/* the orders the solver's next iteration takes: J2P_ORDER_* of the gradient and of the projection phase */
+int j2p_solver_phase_order(const j2p_solver *s, unsigned *gradient, unsigned *project);
 /* bytes per quantised coefficient the projection kernel reads for channel c: 1 or 2 (J2P_OPT_NARROW_COEFFICIENTS) */
 int j2p_solver_coefficient_bytes(const j2p_solver *s, unsigned c, unsigned *bytes);
 /* *shared = 1 when channel c keeps its gradient and its prob state in ONE buffer (a channel sampled 1x1 whose coefficient
@@ -153,10 +162,25 @@ int j2p_debug_build(void);
 /* Test hook (no device needed): the map from k_gradient's workgroups to (strip, rows) — j2p_kernels.hip.h: grad_item —
  * evaluated on the host for a W x rows plane with `rows_per_tile`-row tile rows, one wavefront per strip
  * (channel_wavefronts 1) or per strip and channel (2, 3), the given shares (1/256 of every XCD's run) of double / half /
- * quarter tile-row items, top-down or bottom-up.  items: up to max_items records of five unsigned {strip, first row,
- * rows, tile row, kind (0 whole, 1 half, 2 quarter, 3 double)}; *n_items: how many the launch has; *workgroups: its grid. */
+ * quarter tile-row items, every XCD's run top-down (`reverse` 0) or bottom-up (J2P_ORDER_REVERSE).  items: up to max_items records of five unsigned {strip,
+ * first row, rows, tile row, kind (0 whole, 1 half, 2 quarter, 3 double)} in dispatch order (workgroup, then wavefront);
+ * *n_items: how many the launch has; *workgroups: its grid. */
 int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
                          unsigned zone_c, int reverse, unsigned *items, unsigned max_items, unsigned *n_items, unsigned *workgroups);
+/* ... and with item_workgroup[i] = the workgroup of item i (it runs on XCD workgroup % 8) */
+int j2p_debug_grad_items_workgroups(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
+                                    unsigned zone_c, int reverse, unsigned *items, unsigned *item_workgroup, unsigned max_items, unsigned *n_items,
+                                    unsigned *workgroups);
+/* Test hook (no device needed): the map from a projection launch's workgroups to strips — j2p_kernels.hip.h: project_item —
+ * evaluated on the host for a launch over `nby` block rows of `strips_x` strips (by = by_offset + i * by_mul for i < nby: the
+ * whole phase is 0, 1, block rows; the split phases take the first and last, or all but those), walked in `order`
+ * (J2P_ORDER_FORWARD or J2P_ORDER_REVERSE).  items: up to max_items records of four unsigned {workgroup, wavefront,
+ * block row, strip in the row} of the ACTIVE wavefronts in dispatch order; *n_items: how many; *workgroups: the grid. */
+int j2p_debug_project_items(unsigned strips_x, unsigned nby, unsigned by_offset, unsigned by_mul, int order, unsigned *items,
+                            unsigned max_items, unsigned *n_items, unsigned *workgroups);
+/* Test hook (no device needed): the phase-order policy (j2p_geometry.h: j2p_phase_order_of) for a solver of W x rows canvas rows
+ * whose iteration touches `working_set` bytes, `planes` of them the two iterates, whole canvas (band 0) or band (1) */
+int j2p_debug_phase_order(size_t working_set, size_t planes, unsigned W, unsigned rows, int band, unsigned *gradient, unsigned *project);
 /* Test hook (no device needed): the solver's norm plan — who reduces ||g|| between the two phase kernels of ONE iteration
  * (DESIGN.md section 4 has the table) — for a whole-canvas (whole 1) or band (0) solver with J2P_OPT_NORM_FOLD `fold`,
  * J2P_OPT_NORM_IN_PROJECT `norm_in_project` (0, 1, 2), bands finishing ||g|| inside k_project (`band_nip`, the default) or

@@ -205,6 +205,7 @@ C_ABI_SYMBOLS = [
     "j2p_planes_to_png", "j2p_png_encode", "j2p_batch_submit_png", "j2p_batch_submit_file_png",
     "j2p_jpeg_orientation", "j2p_solver_set_orientation", "j2p_solver_orientation", "j2p_solver_upright_bytes",
     "j2p_batch_next_orientation",
+    "j2p_solver_phase_order", "j2p_debug_project_items", "j2p_debug_phase_order", "j2p_debug_grad_items_workgroups",
 ]
 J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -212,6 +213,16 @@ NORM_FORMS = {"rowsums": 0, "norm_whole": 1, "norm_finish": 2, "norm_bands": 3, 
 J2P_OPT_NORM_FOLD, J2P_OPT_NORM_IN_PROJECT, J2P_OPT_NT_GRADIENT, J2P_OPT_MIXED_PROJECT = 1, 4, 5, 6
 J2P_OPT_NARROW_COEFFICIENTS = 7
 J2P_OPT_WIDE_FOOTPRINT = 8
+J2P_OPT_PHASE_ORDER = 9
+# the order in which every XCD walks its run of a phase launch (J2P_ORDER_*): top-down, or its own run bottom-up
+J2P_ORDER_FORWARD, J2P_ORDER_REVERSE = 0, 1
+
+
+def phase_order(gradient, project):
+    """the value of J2P_OPT_PHASE_ORDER (and of the environment's J2P_PHASE_ORDER) for the two phases' orders"""
+    return int(gradient) | (int(project) << 1)
+
+
 ZOOM_MAX = 4
 J2P_DTYPE_U8, J2P_DTYPE_F16, J2P_DTYPE_BF16, J2P_DTYPE_F32 = 0, 1, 2, 3
 TENSOR_PATHS = ("generic", "planar", "interleaved")     # what j2p_debug_tensor_path reports: 0, 1, 2
@@ -1433,6 +1444,13 @@ class Solver:
     def debug_option(self, option, value):
         """schedule switches (J2P_OPT_*): speed only, never results"""
         _check(self._lib.j2p_solver_debug_option(self._h, int(option), int(value)))
+
+    def phase_order(self):
+        """(gradient, project): the J2P_ORDER_* the next iteration's phase launches take (J2P_OPT_PHASE_ORDER)"""
+        self._lib.j2p_solver_phase_order.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
+        g, p = ctypes.c_uint(), ctypes.c_uint()
+        _check(self._lib.j2p_solver_phase_order(self._h, ctypes.byref(g), ctypes.byref(p)))
+        return g.value, p.value
 
     def debug_violations(self):
         """J2P_DEBUG builds: (count, first site code, first offset) of the phase kernels' address checks"""

@@ -120,6 +120,33 @@ static inline j2p_strip_schedule j2p_strip_schedule_of(unsigned W, unsigned H, u
         return p;
 }
 
+// ---- the order in which every XCD walks its run of the two phase launches ----
+// Both phase kernels give XCD q the q-th contiguous run of the canvas (grad_item, project_item).  J2P_ORDER_FORWARD: the
+// run top-down.  J2P_ORDER_REVERSE: the XCD's own run bottom-up.  One phase forward and the other backwards (serpentine)
+// lets every phase start on the rows the phase before touched last: they are still in the XCD's OWN L2 (4 MiB each), and —
+// planes that do not fit it — in the Infinity Cache.  Schedule only: no bit depends on who marches a row when.
+// working_set: the bytes an iteration touches; planes: x_k and x_{k-1} of them; cache: the Infinity Cache; W x rows: the
+// solver's canvas rows; band: a band of a row-tiled run, not a whole canvas.
+typedef struct {
+        unsigned gradient, project;     // J2P_ORDER_*
+} j2p_phase_order;
+
+static inline j2p_phase_order j2p_phase_order_of(size_t working_set, size_t planes, size_t cache, unsigned W, unsigned rows, int band)
+{
+        j2p_phase_order o = { J2P_ORDER_FORWARD, J2P_ORDER_FORWARD };
+        (void)working_set; (void)W; (void)rows;
+        // Whole canvases: the GRADIENT phase bottom-up, the projection top-down.  Measured against both forward, the
+        // projection reversed instead, and both reversed (profiles/phase_order_sweep.jsonl, us per iteration forward /
+        // serpentine): 1080p Y 29.1 / 28.6, 2048^2 43.7 / 42.2, 4096^2 117.3 / 115.8, 8192x4096 226.4 / 223.9,
+        // 16384x2048 222.7 / 220.8; no size of the sweep slower.  Reversing the projection instead gains as much or more
+        // at 4096x2048 (69.6 / 67.7) and on 1080p 4:2:0 joint (73.0 / 71.2) and less at 2048^2 and 8192x4096: one rule,
+        // this one.  Both reversed is both forward with the ends exchanged: no gain.
+        // Past the Infinity Cache (planes > cache) the same order keeps what the cache holds of the planes (8192^2
+        // 502 -> 458 us per iteration); bands get it there only, as before: within the cache they were not measured.
+        if(!band || planes > cache) { o.gradient = J2P_ORDER_REVERSE; }
+        return o;
+}
+
 // ---- the rows of one channel a solver of canvas rows [row0, row1) holds, in coefficient rows of the channel ----
 typedef struct {
         unsigned crow0, crows;          // of d / pg: the band's own rows (block aligned because the band is)

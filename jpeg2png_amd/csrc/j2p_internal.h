@@ -149,7 +149,8 @@ static inline unsigned j2p_next_chunk(unsigned done, unsigned left, double elaps
 // AMONG the release kernels (rows per strip, item shares, launch direction, where the norm is finished, ...) and the
 // split phases.  Its device code is the release build's.  The release library carries neither the switches nor the split
 // phases and reads only J2P_DEVICE, J2P_DEVICES, J2P_TILED_EXCHANGE, J2P_TILED_WAIT, J2P_TILED_VERIFY, J2P_RCCL_LIBRARY,
-// J2P_POOL_MIB and J2P_COMPUTE_TIMING.
+// J2P_POOL_MIB, J2P_COMPUTE_TIMING and J2P_PHASE_ORDER (the value of J2P_OPT_PHASE_ORDER for every solver created: the
+// benchmark can then be run in either launch order as it stands).
 static inline const char *j2p_exp_env(const char *name)
 {
 #ifdef J2P_EXPERIMENTS

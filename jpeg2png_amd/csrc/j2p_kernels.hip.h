@@ -133,6 +133,9 @@ struct ChanDev {
 #endif
 };
 
+// the order in which every XCD walks its run of a phase launch (grad_item, project_item; jpeg2png_amd.h)
+constexpr unsigned kOrderForward = J2P_ORDER_FORWARD, kOrderReverse = J2P_ORDER_REVERSE;
+
 struct Geo {
         unsigned W, H;      // canvas
         unsigned row0;      // first canvas row of the band
@@ -148,9 +151,9 @@ struct Geo {
         // and tile rows of the launch, and the shares (in 1/256) of every XCD's run that are dealt as double, as half and as
         // quarter tile rows
         unsigned units, ntr_launch, zone_d, zone_b, zone_c;
-        // 1: the launch walks the canvas bottom-up (unit n - 1 - u instead of u).  k_project walks top-down, so each
-        // phase then STARTS on the rows the phase before touched last — what the Infinity Cache still holds of planes
-        // that do not fit it (j2p_solver_create: canvases whose two planes exceed the cache)
+        // kOrderReverse: every XCD walks its run of the launch bottom-up (grad_item).  With k_project top-down each phase
+        // then STARTS on the rows the phase before touched last: what the XCD's own L2 still holds, and what the Infinity
+        // Cache still holds of planes that do not fit it.  The choice is j2p_phase_order_of's (j2p_geometry.h)
         unsigned reverse;
 #ifdef J2P_TRACE
         unsigned long long *trace;   // TraceRec buffer (record 0 unused) or NULL
@@ -210,6 +213,7 @@ struct ProjArgs {
         // sampling): by = by_offset + i * by_mul for i < nby
         // (all: 0,1,brows; first and last only: 0,brows-1,2; all but those: 1,1,brows-2)
         unsigned by_offset[kMaxCh], by_mul[kMaxCh], nby[kMaxCh];
+        unsigned order;             // how every XCD walks its run of the launch's strips (project_item): kOrderForward / kOrderReverse
         // non-NULL: the norm is not read from `norm` but reduced by every wavefront itself from the level-1 row sums
         // [tile row][channel] the gradient launch left behind (norm_tree_wave) — no reduction kernel between the phases
         const double *norm_rowsums;
@@ -1431,7 +1435,8 @@ __host__ __device__ __forceinline__ bool grad_item(const Geo &g, unsigned b, int
         } else {
                 return false;
         }
-        if(g.reverse) { u = n - 1 - u; }
+        // zones are chosen by dispatch position above, so the short items stay last whichever way the units are walked
+        if(g.reverse) { u = first + run - 1 - (u - first); }
         const unsigned id = J == 1 ? 4 * u + strip_in_group : u;        // (pair row, strip) of the launch, row-major
         const unsigned pair_row = id / g.ntx;
         const unsigned tr_launch = 2 * pair_row + tile_in_pair;
@@ -1444,6 +1449,20 @@ __host__ __device__ __forceinline__ bool grad_item(const Geo &g, unsigned b, int
         it.t0 = it.tile0 + sub * it.nrows;
         it.active = tr_launch < g.ntr_launch && it.t0 < (int)g.rows;
         return true;
+}
+
+// The order in which a projection launch hands out its strips: workgroup b of nwg -> item l, four consecutive strips of
+// the launch (row-major over block rows; lstrip = 4 l + wavefront).  Workgroup b runs on XCD b % 8: every XCD gets a
+// contiguous run of items, as in the gradient launch, and walks it top-down (kOrderForward) or bottom-up
+// (kOrderReverse: the run's LAST item first — the XCD starts on the rows its own L2 touched last in the phase before).
+// An XCD's run is empty where b >> 3 is never below it (fewer than 8 workgroups): no workgroup has that number.
+// (host too: j2p_debug_project_items, tests/test_phase_order_cpu.py)
+__host__ __device__ __forceinline__ unsigned project_item(unsigned b, unsigned nwg, unsigned order)
+{
+        const unsigned q = b & 7, j = b >> 3;
+        const unsigned first = chunk_base(nwg, q);
+        const unsigned run = chunk_base(nwg, q + 1) - first;
+        return order == kOrderReverse ? first + run - 1 - j : first + j;
 }
 
 // (the checked build carries its range descriptors in registers: at four wavefronts per SIMD it spilled 132-164 bytes to
@@ -2104,12 +2123,7 @@ __device__ __forceinline__ void project_strip(const ProjArgs &a, ProjShared &sh)
         const unsigned brows = (a.geo.rows + 8 * hs - 1) / (8 * hs);  // block rows in the band
         // workgroup b runs on XCD b % 8: give every XCD a contiguous run of strips (as k_gradient does) — the eight
         // L2s then each stream one region of the planes instead of interleaving at 1 KB (68.8 -> 67.8 us at 4096^2)
-        unsigned lstrip;
-        {
-                const unsigned b = wg, xcd = b & 7, q = nwg >> 3, rem = nwg & 7;
-                const unsigned l = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (b >> 3);
-                lstrip = l * 4 + wave;                                // index within this launch
-        }
+        unsigned lstrip = project_item(wg, nwg, a.order) * 4 + wave;   // index within this launch
         // (wavefronts past the launch's last strip stay until the workgroup barrier below)
         const bool active = lstrip < strips_x * a.nby[zi];
         if(!active) { lstrip = 0; }

@@ -119,7 +119,9 @@ struct j2p_solver {
         // reductions
         bool fold = false;       // level 1 of the norm reduction inside k_gradient (J2P_OPT_NORM_FOLD; default: norm_defaults)
         unsigned zone_d = 0, zone_b = 0, zone_c = 0;   // shares (1/256) of a gradient launch dealt as double / half / quarter tile rows (grad_item)
-        bool grad_reverse = false;         // the gradient launch walks the canvas bottom-up (Geo::reverse)
+        // how every XCD walks its run of each phase launch (grad_item, project_item): j2p_phase_order_of's choice unless
+        // J2P_OPT_PHASE_ORDER / the environment's J2P_PHASE_ORDER forced one
+        j2p_phase_order order = { J2P_ORDER_FORWARD, J2P_ORDER_FORWARD };
         int nip_form = 0;               // J2P_OPT_NORM_IN_PROJECT (with fold): level 2 inside k_project, by every wavefront (1) or the workgroup's first (2)
         NormPlan plan;                  // the running iteration's (do_phase_gradient); between iterations: nobody reads it
         int nt = 0;                     // 0..3: streams with the non-temporal hint (nt_policy; J2P_OPT_NT_GRADIENT)
@@ -512,7 +514,7 @@ int do_phase_gradient(j2p_solver *s, bool log, int part = 0, hipStream_t st = nu
         a.geo.ntr_launch = nseg_launch;
         // (half / quarter items: whole phases of one channel per workgroup wavefront, see j2p_zone_shares in j2p_geometry.h)
         if(part == 0 && s->nch == 1) { a.geo.zone_d = s->zone_d; a.geo.zone_b = s->zone_b; a.geo.zone_c = s->zone_c; }
-        a.geo.reverse = part == 0 && s->grad_reverse ? 1u : 0u;
+        a.geo.reverse = part == 0 ? s->order.gradient : kOrderForward;
         a.factor = s->factor;
         a.a_tv = (float)(1. / (double)sqrtf((float)s->nch));                    // compute.c:90
         const float alpha = s->weight / sqrtf((float)(4 / 2));                  // compute.c:258
@@ -647,6 +649,7 @@ int do_phase_project(j2p_solver *s, bool log, int part = 0)
         a.norm = s->norm;
         a.part_prob = s->part_prob;
         a.strips_per_chan = s->strips_stride;
+        a.order = s->order.project;
         const int nip = s->plan.nip();
         a.norm_rowsums = nip ? global_rows : nullptr;
         a.norm_rows = s->ntr_global;
@@ -970,6 +973,19 @@ int carve_arena(j2p_solver *s, const j2p_plane planes[])
         return J2P_OK;
 }
 
+// J2P_OPT_PHASE_ORDER / J2P_PHASE_ORDER: value = J2P_PHASE_ORDER(gradient, project); negative: back to the policy; false: no such order
+bool force_phase_order(j2p_solver *s, int value)
+{
+        if(value < 0) {
+                s->order = j2p_phase_order_of(s->live.working_set, s->live.planes, kNtWorkingSet, s->W, s->rows, !s->whole);
+                return true;
+        }
+        if(value > J2P_PHASE_ORDER(J2P_ORDER_REVERSE, J2P_ORDER_REVERSE)) { return false; }
+        s->order.gradient = (unsigned)value & 1u;
+        s->order.project = (unsigned)value >> 1;
+        return true;
+}
+
 // nt_policy (see nt_policy() above): this solver's bytes join the device's live total
 void register_live_bytes(j2p_solver *s)
 {
@@ -988,11 +1004,11 @@ void register_live_bytes(j2p_solver *s)
         j2p_live_add(s->device, s->live, +1);
         s->live_registered = true;
         s->nt = nt_policy(s);
-        // canvases whose planes x_k, x_{k-1} do not both fit the Infinity Cache: the gradient phase walks bottom-up
-        // (k_project walks top-down), so that each phase starts on the rows the one before touched last (Geo::reverse).
-        // Schedule only: the bits do not depend on who marches a row when.
-        s->grad_reverse = s->live.planes > kNtWorkingSet;
-        if(const char *env = j2p_exp_env("J2P_GRAD_REVERSE")) { s->grad_reverse = atoi(env) != 0; }
+        // which way every XCD walks its run of each phase.  Schedule only: the bits do not depend on who marches a row when.
+        s->order = j2p_phase_order_of(s->live.working_set, s->live.planes, kNtWorkingSet, s->W, s->rows, !s->whole);
+        if(const char *env = j2p_exp_env("J2P_GRAD_REVERSE")) { s->order.gradient = atoi(env) != 0 ? J2P_ORDER_REVERSE : J2P_ORDER_FORWARD; }
+        // (read by the release library too: the benchmark can then be run in either order as it stands)
+        if(const char *env = getenv("J2P_PHASE_ORDER")) { force_phase_order(s, atoi(env)); }
 }
 
 // the quantization tables go up, the counters start at zero.  qf: 64 * kMaxCh floats of the caller's that stay until the
@@ -1397,8 +1413,19 @@ int j2p_solver_debug_option(j2p_solver *s, int option, int value)
                 s->wide_footprint = value != 0;
                 set_wide_footprint(s);
                 break;
+        case J2P_OPT_PHASE_ORDER:
+                if(!force_phase_order(s, value)) { return j2p_fail(J2P_EINVAL, "J2P_OPT_PHASE_ORDER is J2P_PHASE_ORDER(gradient, project) of J2P_ORDER_* values, or negative"); }
+                break;
         default: return j2p_fail(J2P_EINVAL, "unknown option %d", option);
         }
+        return J2P_OK;
+}
+
+int j2p_solver_phase_order(const j2p_solver *s, unsigned *gradient, unsigned *project)
+{
+        if(!s || !gradient || !project) { return j2p_fail(J2P_EINVAL, "j2p_solver_phase_order: bad argument"); }
+        *gradient = s->order.gradient;
+        *project = s->order.project;
         return J2P_OK;
 }
 
@@ -1506,9 +1533,9 @@ int j2p_experiments_build(void)
 #endif
 }
 
-int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
-                         unsigned zone_c, int reverse, unsigned *items /* [max][5]: strip, first row, rows, tile row, kind */, unsigned max_items,
-                         unsigned *n_items, unsigned *workgroups)
+static int debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
+                            unsigned zone_c, int reverse, unsigned *items /* [max][5]: strip, first row, rows, tile row, kind */,
+                            unsigned *item_workgroup /* [max] or NULL */, unsigned max_items, unsigned *n_items, unsigned *workgroups)
 {
         // the map of k_gradient's launch (grad_item) evaluated on the HOST, wavefront by wavefront: no device needed
         if(!items || !n_items || !workgroups || W < 8 || rows == 0 || rows_per_tile == 0 || channel_wavefronts < 1 || channel_wavefronts > 3) {
@@ -1524,7 +1551,7 @@ int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsi
         const bool joint = channel_wavefronts > 1;
         g.units = joint ? positions : (positions + 3) / 4;
         g.zone_d = zone_d; g.zone_b = zone_b; g.zone_c = zone_c;
-        g.reverse = reverse ? 1u : 0u;
+        g.reverse = reverse ? kOrderReverse : kOrderForward;
         const unsigned nwg = grad_grid(g.units, zone_shares(g));
         *workgroups = nwg;
         unsigned n = 0;
@@ -1537,11 +1564,60 @@ int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsi
                                 unsigned *o = items + 5 * (size_t)n;
                                 const unsigned t1 = (unsigned)(it.t0 + it.nrows) < rows ? (unsigned)(it.t0 + it.nrows) : rows;
                                 o[0] = (unsigned)it.wcol; o[1] = (unsigned)it.t0; o[2] = t1 - (unsigned)it.t0; o[3] = it.tr; o[4] = (unsigned)it.kind;
+                                if(item_workgroup) { item_workgroup[n] = b; }
                         }
                         n++;
                 }
         }
         *n_items = n;
+        return J2P_OK;
+}
+
+int j2p_debug_grad_items(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
+                         unsigned zone_c, int reverse, unsigned *items, unsigned max_items, unsigned *n_items, unsigned *workgroups)
+{
+        return debug_grad_items(W, rows, rows_per_tile, channel_wavefronts, zone_d, zone_b, zone_c, reverse, items, nullptr, max_items, n_items, workgroups);
+}
+
+int j2p_debug_grad_items_workgroups(unsigned W, unsigned rows, unsigned rows_per_tile, unsigned channel_wavefronts, unsigned zone_d, unsigned zone_b,
+                                    unsigned zone_c, int reverse, unsigned *items, unsigned *item_workgroup, unsigned max_items, unsigned *n_items,
+                                    unsigned *workgroups)
+{
+        if(!item_workgroup) { return j2p_fail(J2P_EINVAL, "bad argument"); }
+        return debug_grad_items(W, rows, rows_per_tile, channel_wavefronts, zone_d, zone_b, zone_c, reverse, items, item_workgroup, max_items, n_items, workgroups);
+}
+
+int j2p_debug_project_items(unsigned strips_x, unsigned nby, unsigned by_offset, unsigned by_mul, int order, unsigned *items /* [max][4]: workgroup, wavefront, block row, strip */,
+                            unsigned max_items, unsigned *n_items, unsigned *workgroups)
+{
+        // the map of a projection launch (project_item and project_strip's arithmetic behind it) evaluated on the HOST
+        if(!items || !n_items || !workgroups || strips_x == 0 || nby == 0 || (order != (int)kOrderForward && order != (int)kOrderReverse)) {
+                return j2p_fail(J2P_EINVAL, "bad argument");
+        }
+        const unsigned strips = strips_x * nby, nwg = (strips + 3) / 4;     // the grid of do_phase_project
+        *workgroups = nwg;
+        unsigned n = 0;
+        for(unsigned b = 0; b < nwg; b++) {
+                for(unsigned wave = 0; wave < 4; wave++) {
+                        const unsigned lstrip = project_item(b, nwg, (unsigned)order) * 4 + wave;
+                        if(lstrip >= strips) { continue; }
+                        if(n < max_items) {
+                                unsigned *o = items + 4 * (size_t)n;
+                                o[0] = b; o[1] = wave; o[2] = by_offset + (lstrip / strips_x) * by_mul; o[3] = lstrip % strips_x;
+                        }
+                        n++;
+                }
+        }
+        *n_items = n;
+        return J2P_OK;
+}
+
+int j2p_debug_phase_order(size_t working_set, size_t planes, unsigned W, unsigned rows, int band, unsigned *gradient, unsigned *project)
+{
+        if(!gradient || !project) { return j2p_fail(J2P_EINVAL, "bad argument"); }
+        const j2p_phase_order o = j2p_phase_order_of(working_set, planes, kNtWorkingSet, W, rows, band);
+        *gradient = o.gradient;
+        *project = o.project;
         return J2P_OK;
 }
 
