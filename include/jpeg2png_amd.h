@@ -106,6 +106,10 @@ void j2p_solver_destroy(j2p_solver *s);
  * that runs out of memory drops the cache and retries.  j2p_pool_trim() releases the cache; j2p_batch_destroy()
  * and j2p_tiled_destroy() call it. */
 void j2p_pool_trim(void);
+/* diagnostics: blocks the CALLING thread has taken from the cache or the device so far (a solver's arena, its scratch, a
+ * coder's block — each request that was not met by the block already held counts once).  A call whose block had to grow k
+ * times took 1 + k; a call that found its block large enough took none. */
+unsigned long long j2p_pool_thread_takes(void);
 
 /* diagnostics: schedule switches that change speed, never results (A/B timing and the parity tests of both
  * schedules).  Only between iterations. */

@@ -206,6 +206,7 @@ C_ABI_SYMBOLS = [
     "j2p_jpeg_orientation", "j2p_solver_set_orientation", "j2p_solver_orientation", "j2p_solver_upright_bytes",
     "j2p_batch_next_orientation",
     "j2p_solver_phase_order", "j2p_debug_project_items", "j2p_debug_phase_order", "j2p_debug_grad_items_workgroups",
+    "j2p_pool_thread_takes",
 ]
 J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -352,6 +353,10 @@ def _bind(path):
     lib.j2p_solver_debug_violations.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_uint),
                                                 ctypes.POINTER(ctypes.c_ulonglong)]
     lib.j2p_pool_trim.restype = None
+    if hasattr(lib, "j2p_pool_thread_takes"):
+        # (a build of an earlier commit, loaded as the baseline of an A/B timing, does not count its takes)
+        lib.j2p_pool_thread_takes.argtypes = []
+        lib.j2p_pool_thread_takes.restype = ctypes.c_ulonglong
     lib.j2p_tiled_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_int),
                                      ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, ctypes.POINTER(_CPlane), ctypes.c_float,
                                      ctypes.POINTER(ctypes.c_float), ctypes.c_uint]

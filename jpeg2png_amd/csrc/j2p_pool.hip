@@ -24,6 +24,7 @@ struct PoolBlock {
 };
 std::mutex g_pool_lock;
 std::vector<PoolBlock> g_pool;
+thread_local unsigned long long t_pool_takes = 0;      // j2p_pool_thread_takes: this thread's calls of j2p_pool_take
 constexpr size_t kPoolBlocks = 16;                     // per device
 constexpr size_t kPoolBytesDefault = (size_t)8 << 30;  // per device; J2P_POOL_MIB overrides (0 = no caching)
 
@@ -67,6 +68,7 @@ hipError_t j2p_dev_malloc(void **out, size_t bytes)
 
 hipError_t j2p_pool_take(int device, size_t bytes, void **out, size_t *got)
 {
+        t_pool_takes++;
         {
                 std::lock_guard<std::mutex> g(g_pool_lock);
                 size_t best = g_pool.size();
@@ -105,6 +107,7 @@ void j2p_pool_give(int device, void *ptr, size_t bytes)
 }
 
 extern "C" void j2p_pool_trim(void) { pool_drop_all(); }
+extern "C" unsigned long long j2p_pool_thread_takes(void) { return t_pool_takes; }
 
 namespace {
 

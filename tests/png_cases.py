@@ -80,6 +80,17 @@ def tokens(block):
     return out
 
 
+def token_positions(block):
+    """{position in the block: its token} of tokens(block): a literal at its byte, a match at its first byte (the bytes behind it
+    in the match — the silent ones — have no entry)"""
+    out, at = {}, 0
+    for token in tokens(block):
+        out[at] = token
+        at += 1 if token[0] == "lit" else token[1]
+    assert at == len(block)
+    return out
+
+
 def length_symbol(n):
     """-> (symbol, extra bits, their value)"""
     k = max(i for i in range(29) if LENGTH_BASE[i] <= n)
@@ -374,6 +385,82 @@ def filters_image():
     return np.array(rows, dtype=np.uint8)
 
 
+# ---- the edges of a tile: the 1024 positions of a block that its workgroup takes per trip (k_png_count, k_png_pack) ----
+TILE = 1024
+# every name tile_cases() gives (tests/test_png_cpu.py asserts of each what it is there for)
+TILE_CASE_NAMES = ("tiles_exact", "tiles_plus_1", "block_1025", "run_over_tiles", "match_at_tile_end", "match_at_tile_start", "tail_1", "tail_2",
+                   "tail_3", "block_ends_in_ahead", "run_cut_at_tile", "dense_tile")
+DENSE_TILE_BITS = TILE * 15 + 6         # what k_png_pack's staging words of a tile are sized for
+
+
+def _stream_case(stream, block_bytes, idat_bytes=64):
+    """one greyscale row under filter 0 whose filtered stream is `stream` (its first byte the filter byte: 0)"""
+    assert stream[0] == 0
+    return _case([list(stream[1:])], len(stream) - 1, 1, filter=0, block_bytes=block_bytes, idat_bytes=idat_bytes)
+
+
+def _noise(rng, n, values=256):
+    """a stream of n bytes behind its filter byte in which no two neighbours are equal"""
+    out = [0]
+    while len(out) < n:
+        v = int(rng.integers(0, values))
+        if v != out[-1]:
+            out.append(v)
+    return out
+
+
+def _with_run(stream, head, last, value=None):
+    """stream with positions head..last (inclusive) holding one value that the bytes on either side do not hold"""
+    out = list(stream)
+    around = {out[head - 1]} | ({out[last + 1]} if last + 1 < len(out) else set())
+    value = next(v for v in range(200, 256) if v not in around) if value is None else value
+    assert value not in around
+    out[head:last + 1] = [value] * (last + 1 - head)
+    return out
+
+
+def ruler(n):
+    """(i & -i).bit_length() for i = 1 .. 2^n - 1: value k 2^(n - k) times, no two neighbours equal"""
+    return [(i & -i).bit_length() for i in range(1, 1 << n)]
+
+
+def dense_tile_stream():
+    """a block whose tile 0 has as many bits as a tile can have: 1023 literals of 15 bits and, at its last position, a match with 15
+    bits of length code, 5 extra bits and the distance's bit.  The filter byte and 230 values a few times each are the rare symbols;
+    the ruler sequence behind (values 1..18, 2^17 down to 1 times) makes the tree 18 deep, so that limiting to 15 bits leaves every
+    rare symbol — the match of 200 among them, counted once — with 15"""
+    stream = [0] + [20 + p % 230 for p in range(1, TILE - 1)]
+    stream += [stream[-1]] * 200
+    return stream + ruler(18)
+
+
+def tile_cases():
+    rng = np.random.default_rng(1024)
+    out = {}
+    # an exact number of tiles, one byte more, and a tile and a byte: values 0..2, so that short runs lie on every tile edge
+    small = [0] + [int(v) for v in rng.integers(0, 3, size=4 * TILE)]
+    out["tiles_exact"] = _stream_case(small[:4 * TILE], 4 * TILE)
+    # (the last tile's one byte is place 1 of its piece: a literal whose stretch began in the tile before)
+    plus1 = list(small)
+    plus1[4 * TILE - 3:] = [7, 9, 9, 9]
+    out["tiles_plus_1"] = _stream_case(plus1, 4 * TILE + 1)
+    out["block_1025"] = _stream_case(small[:TILE + 1], 2 * TILE)
+    # one value from 500 to 3700: tile 1024..2047 and tile 2048..3071 hold no byte that breaks the run
+    out["run_over_tiles"] = _stream_case(_with_run(_noise(rng, 4 * TILE), 500, 3700), 4 * TILE)
+    # the pieces behind a head at 248 begin at 249, 507, 765 and 1023; behind one at 249, at 1024
+    long_run = _with_run(_noise(rng, 1600), 248, 1400)
+    out["match_at_tile_end"] = _stream_case(long_run, 2 * TILE)
+    out["match_at_tile_start"] = _stream_case(_with_run(_noise(rng, 1600), 249, 1400), 2 * TILE)
+    for k in (1, 2, 3):
+        out[f"tail_{k}"] = _stream_case(_with_run(_noise(rng, 1100), 248, 248 + 3 * 258 + k), 2 * TILE)
+    # the same stream cut 101 bytes into the look-ahead of position 1023, and at the tile's end
+    out["block_ends_in_ahead"] = _stream_case(long_run, TILE + 100)
+    out["run_cut_at_tile"] = _stream_case(long_run, TILE)
+    out["dense_tile"] = _stream_case(dense_tile_stream(), 1 << 19, idat_bytes=0)
+    assert tuple(out) == TILE_CASE_NAMES
+    return out
+
+
 def directed_cases():
     rng = np.random.default_rng(2025)
     out = {}
@@ -408,4 +495,5 @@ def directed_cases():
     assert exact and plus1, n
     out["idat_exact"] = dict(base, idat_bytes=exact[0])
     out["idat_plus_1"] = dict(base, idat_bytes=plus1[0])
+    out.update(tile_cases())
     return out

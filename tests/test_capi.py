@@ -17,9 +17,23 @@ def declared_symbols():
     for h in ("jpeg2png_amd.h", "jpeg2png_amd_compute.h"):
         text = open(os.path.join(ROOT, "include", h)).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        for m in re.finditer(r"^\s*(?:const\s+)?(?:int|void|char)\s*\*?\s*(j2p_\w+|compute)\s*\(", text, flags=re.M):
+        for m in re.finditer(r"^\s*(?:const\s+)?(?:int|void|char|unsigned\s+long\s+long)\s*\*?\s*(j2p_\w+|compute)\s*\(", text, flags=re.M):
             names.add(m.group(1))
     return names
+
+
+def test_the_pattern_sees_every_return_type_the_headers_use():
+    """declared_symbols() looks for the return types the headers use: a declaration with another one must not drop out of the
+    comparison with the binding's list unseen — every line that opens a j2p_ declaration at the left margin is one it found"""
+    found = declared_symbols()
+    assert "j2p_pool_thread_takes" in found and "j2p_pool_trim" in found
+    for h in ("jpeg2png_amd.h", "jpeg2png_amd_compute.h"):
+        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
+        for m in re.finditer(r"^[A-Za-z_][\w \t\*]*?\b(j2p_\w+)\s*\(", text, flags=re.M):
+            line = text[m.start():text.index("\n", m.start())]
+            if line.startswith(("typedef", "#", "static", "struct", "return")):
+                continue
+            assert m.group(1) in found, line
 
 
 def test_headers_and_binding_list_agree():

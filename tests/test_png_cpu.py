@@ -294,5 +294,87 @@ def test_case_preconditions(cases, reports):
     assert n % cases["idat_exact"]["idat_bytes"] == 0 and n % cases["idat_plus_1"]["idat_bytes"] == 1
     assert pc.idat_data(reports["idat_plus_1"][0])[1].count(b"IDAT") == n // cases["idat_plus_1"]["idat_bytes"] + 1
     for name, case in cases.items():
-        if name not in ("all_256", "fibonacci", "runs"):
+        if name not in ("all_256", "fibonacci", "runs") + pc.TILE_CASE_NAMES:
             assert 16 <= case["block_bytes"] <= 64 and 16 <= case["idat_bytes"] <= 64, name
+
+
+def token_bits(token, lengths):
+    """the bits a token takes under a block's code lengths: a literal's code; a match's length code, its extra bits and the distance's bit"""
+    if token[0] == "lit":
+        return lengths[token[1]]
+    symbol, extra_bits, _extra = pc.length_symbol(token[1])
+    return lengths[symbol] + extra_bits + 1
+
+
+def test_tile_edge_case_preconditions(cases, reports):
+    """what each case of png_cases.tile_cases() is there for, position by position, by the restatement alone: a later change of the
+    cases cannot quietly miss the edge.  Positions are those of the block's bytes; a tile is 1024 of them."""
+    T = pc.TILE
+    assert set(pc.TILE_CASE_NAMES) <= set(cases)
+
+    def block(name, k=0):
+        """(block k's bytes, {position: token}, its report)"""
+        size = cases[name]["block_bytes"]
+        data = reports[name][1]["filtered"][k * size:(k + 1) * size]
+        return data, pc.token_positions(data), reports[name][1]["blocks"][k]
+
+    def breaking(data, lo, hi):
+        """the positions lo..hi-1 whose byte does not equal the one before"""
+        return [p for p in range(lo, min(hi, len(data))) if p == 0 or data[p] != data[p - 1]]
+
+    for name in pc.TILE_CASE_NAMES:
+        case = cases[name]
+        assert (case["height"], case["channels"], case["bits"], case["filter"]) == (1, 1, 8, 0), name
+        assert reports[name][1]["filtered"][0] == 0 and len(reports[name][1]["filtered"]) == case["width"] + 1, name
+    data, at, _ = block("tiles_exact")
+    assert len(data) == 4 * T == cases["tiles_exact"]["block_bytes"] and len(reports["tiles_exact"][1]["blocks"]) == 1
+    data, at, _ = block("tiles_plus_1")
+    assert len(data) == 4 * T + 1 == cases["tiles_plus_1"]["block_bytes"] and len(reports["tiles_plus_1"][1]["blocks"]) == 1
+    v = data[4 * T]
+    assert data[4 * T - 3] != v and [at.get(p) for p in range(4 * T - 2, 4 * T + 1)] == [("lit", v)] * 3      # the head, place 0, place 1
+    data, at, _ = block("block_1025")
+    assert len(data) == T + 1 and len(reports["block_1025"][1]["blocks"]) == 1
+
+    data, at, _ = block("run_over_tiles")
+    assert len(data) == 4 * T and len(reports["run_over_tiles"][1]["blocks"]) == 1
+    assert breaking(data, 500, 3702) == [500, 3701] and not breaking(data, T, 2 * T) and not breaking(data, 2 * T, 3 * T)
+    assert at[500][0] == "lit" and at[1017] == ("match", 258) and not any(p in at for p in range(1018, 1275)) and 1275 in at
+    assert at[3597] == ("match", 3700 - 3597 + 1) and 3 * T <= 3597 and 3700 < 4 * T and at[3701][0] == "lit"
+    # (nothing else matches: the noise has no two neighbours equal)
+    assert reports["run_over_tiles"][1]["stats"]["matches"] == 13 and len(breaking(data, 0, 4 * T)) == 4 * T - 3200
+
+    data, at, _ = block("match_at_tile_end")
+    assert breaking(data, 248, 1402) == [248, 1401] and at[T - 1] == ("match", 258) and T - 1 + 257 < len(data)
+    assert [p for p in at if 249 <= p <= T - 1] == [249, 507, 765, T - 1]
+    data, at, _ = block("match_at_tile_start")
+    assert breaking(data, 249, 1402) == [249, 1401] and at[T] == ("match", 258) and T - 1 not in at and data[T - 1] == data[T]
+    assert [p for p in at if 250 <= p <= T] == [250, 508, 766, T]
+
+    for k in (1, 2, 3):
+        data, at, _ = block(f"tail_{k}")
+        last = 248 + 3 * 258 + k
+        assert breaking(data, 248, last + 2) == [248, last + 1] and last == T - 2 + k and at[765] == ("match", 258), k
+    data, at, _ = block("tail_1")
+    assert at[T - 1] == ("lit", data[248]) and at[T] == ("lit", data[T]) and data[T] != data[248]
+    data, at, _ = block("tail_2")
+    assert at[T - 1] == at[T] == ("lit", data[248]) and at[T + 1][0] == "lit" and data[T + 1] != data[248]
+    data, at, _ = block("tail_3")
+    assert at[T - 1] == ("match", 3) and T not in at and T + 1 not in at and at[T + 2][0] == "lit"
+
+    assert reports["block_ends_in_ahead"][1]["filtered"] == reports["run_cut_at_tile"][1]["filtered"] == reports["match_at_tile_end"][1]["filtered"]
+    data, at, _ = block("block_ends_in_ahead")
+    assert len(data) == T + 100 and at[T - 1] == ("match", 101) and T - 1 + 101 == len(data) and len(reports["block_ends_in_ahead"][1]["blocks"]) == 2
+    data, at, _ = block("run_cut_at_tile")
+    assert len(data) == T and at[T - 1] == ("lit", data[248]) and data[T - 2] == data[T - 1] and T - 2 not in at      # place 0 with nothing behind it
+    data, at, _ = block("run_cut_at_tile", 1)
+    assert at[0] == ("lit", data[0]) and at[1] == ("match", 258) and data[0] == block("run_cut_at_tile")[0][T - 1]
+
+    # the dense tile: 1023 literals of 15 bits and a match of 15 + 5 + 1 at the tile's last position — the bound of kPngWords
+    data, at, b = block("dense_tile")
+    assert len(reports["dense_tile"][1]["blocks"]) == 1 and len(data) == T - 1 + 200 + (1 << 18) - 1
+    assert b["longest"] == 18 and max(b["lengths"]) == 15 and b["header_bits"] == 296
+    assert all(at[p][0] == "lit" for p in range(T - 1)) and at[T - 1] == ("match", 200) and T + 199 in at and T + 198 not in at
+    assert all(token_bits(at[p], b["lengths"]) == 15 for p in range(T - 1)) and token_bits(at[T - 1], b["lengths"]) == 21
+    assert sum(token_bits(at[p], b["lengths"]) for p in range(T)) == pc.DENSE_TILE_BITS == 15366
+    # ... which begin 24 bits into a word of the stream: the first and last word of the tile are both shared
+    assert (b["offset"] * 8 + b["header_bits"]) % 32 >= 24

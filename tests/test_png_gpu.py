@@ -109,6 +109,11 @@ def test_refusals(lib):
         j.png_encode(ok, bits=16)
     with pytest.raises(j.J2PError, match="shape"):
         j.png_encode(np.zeros((4, 4, 2), np.uint8))
+    # more deflate blocks than J2P_PNG_BLOCKS_MAX (2^20): 4097 rows of 4097 bytes in blocks of 16 — refused before any block is taken
+    takes = lib.j2p_pool_thread_takes()
+    with pytest.raises(j.J2PError, match="deflate blocks"):
+        j.png_encode(np.zeros((4097, 4096), np.uint8), block_bytes=16)
+    assert lib.j2p_pool_thread_takes() == takes
     spec = j._c_png(4, 4, 12)
     size = ctypes.c_size_t(0)
     assert lib.j2p_png_encode(0, ctypes.byref(spec), ok.ctypes.data, 3, None, 0, ctypes.byref(size), None) == -1
