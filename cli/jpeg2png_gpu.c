@@ -27,6 +27,9 @@
  *                  projection constrains, compute.c:351-359), taken in float on the GPU (j2p_planes_to_coefficients_sub)
  *   -O, --optimize = with -j: Huffman tables made for the image instead of the standard's (libjpeg's optimize_coding; with -e the
  *                  GPU counts the symbols, J2P_JPEG_OPTIMIZE) — the same coefficients in a smaller file, and the same file either way
+ *   -r, --progressive = with -j: the progressive file of libjpeg's jpeg_simple_progression() — ten scans (six with -g), every one with
+ *                  Huffman tables of its own (include/jpeg2png_amd.h, "The progressive JPEG file"); with -e the GPU codes every scan
+ *                  (j2p_batch_submit_jpeg_progressive), without it libjpeg does — the same file either way.  -O changes nothing about it
  *   -P, --png-on-gpu = the PNG is filtered and deflated on the GPU (j2p_batch_submit_png; include/jpeg2png_amd.h, "The PNG file") and
  *                  written as it comes down: no libpng, and no samples on the bus.  The same pixels as without it, in another (usually
  *                  somewhat larger) file; with -1, -g, -z, -s and -d; not with -j, not for row-tiled images
@@ -321,7 +324,7 @@ static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
  * filled: the dummy blocks that complete a partial MCU are libjpeg's own (jctrans.c), but it reaches them through arrays
  * whose sizes are rounded up to the component's sampling factors and that can hold v_samp_factor rows at a time */
 static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h, bool optimize,
-                       int16_t *const coef[3])
+                       bool progressive, int16_t *const coef[3])
 {
         struct jpeg_compress_struct c;
         struct jpeg_error_mgr err;
@@ -332,6 +335,7 @@ static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int qu
         if(ncomp == 1) { sub_w = sub_h = 1; }
         setup_jpeg_out(&c, w, h, ncomp, quality, sub_w, sub_h);
         if(optimize) { c.optimize_coding = TRUE; }
+        if(progressive) { jpeg_simple_progression(&c); }
         const unsigned bw = (w + 7) / 8, bh = (h + 7) / 8;
 #if JPEG_LIB_VERSION >= 70
         /* IJG 7+: jpeg_write_coefficients expects what jpeg_calc_jpeg_dimensions / initial_setup would have left */
@@ -374,6 +378,7 @@ struct options {
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
         bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
         bool auto_orient;       /* -a: the input's EXIF Orientation is applied: every output is the upright image, and carries no tag */
+        bool progressive;       /* -r: with -j, the progressive file (jpeg_simple_progression; with -e j2p_batch_submit_*_progressive) */
         bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
@@ -555,7 +560,11 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         if(!file) { die("could not allocate image data"); }
                         const unsigned flags = o->optimize ? J2P_JPEG_OPTIMIZE : 0u;
                         ORIENT_NEXT();
-                        if(jp.file) {
+                        if(o->progressive && jp.file) {
+                                gpu_check(j2p_batch_submit_file_jpeg_progressive(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket));
+                        } else if(o->progressive) {
+                                gpu_check(j2p_batch_submit_jpeg_progressive(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket));
+                        } else if(jp.file) {
                                 gpu_check(j2p_batch_submit_file_jpeg_ex(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, flags, &ticket));
                         } else {
                                 gpu_check(j2p_batch_submit_jpeg_ex(batch, &job, NULL, &spec, file, capacity, &file_bytes, flags, &ticket));
@@ -603,7 +612,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         if(!out) { die_perror("could not open output file `%s`", outfile); }
         if(file) {
                 if(fwrite(file, 1, file_bytes, out) != file_bytes) { die_perror("could not write output file `%s`", outfile); }
-        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, o->optimize, out_coef); }
+        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, o->optimize, o->progressive, out_coef); }
         else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
@@ -664,6 +673,9 @@ static void usage(void)
                "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
                "  -O, --optimize               with -j: Huffman tables made for the image, a smaller file of the same\n"
                "                               coefficients (with -e the GPU counts the symbols; the same bytes either way)\n"
+               "  -r, --progressive            with -j: a progressive JPEG (libjpeg's simple progression: ten scans, six with -g,\n"
+               "                               each with Huffman tables of its own); with -e the GPU codes every scan; the\n"
+               "                               same bytes either way\n"
                "  -P, --png-on-gpu             the GPU also filters and deflates the PNG and only the file comes down: the same\n"
                "                               pixels in another, usually somewhat larger file; not with -j, not for row-tiled images\n"
                "  -a, --auto-orient            apply the input's EXIF Orientation: every output is the upright image (turned and\n"
@@ -688,6 +700,7 @@ int main(int argc, char **argv)
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
                 {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'},
+                {"progressive", no_argument, NULL, 'r'},
                 {"png-on-gpu", no_argument, NULL, 'P'}, {"auto-orient", no_argument, NULL, 'a'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
                             .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .png_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
@@ -696,7 +709,7 @@ int main(int argc, char **argv)
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOPa", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOPar", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -716,6 +729,7 @@ int main(int argc, char **argv)
                 case 'e': o.encode_on_gpu = true; break;
                 case 'd': o.decode_on_gpu = true; break;
                 case 'O': o.optimize = true; break;
+                case 'r': o.progressive = true; break;
                 case 'P': o.png_on_gpu = true; break;
                 case 'a': o.auto_orient = true; break;
                 default: help = true; break;
@@ -772,6 +786,7 @@ int main(int argc, char **argv)
         }
         if(o.encode_on_gpu && !j_arg) { die("-e needs JPEG output (-j)"); }
         if(o.optimize && !j_arg) { die("-O needs JPEG output (-j)"); }
+        if(o.progressive && !j_arg) { die("-r needs JPEG output (-j)"); }
         if(o.png_on_gpu && j_arg) { die("-P writes a PNG: not with JPEG output (-j)"); }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);

@@ -958,6 +958,85 @@ int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const
 int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                              size_t capacity, size_t *size, unsigned flags, int *ticket);
 
+/* The progressive JPEG file: the same coefficients as the ten scans (six for one component) of libjpeg's jpeg_simple_progression(),
+ * coded on the device.  The file is, byte for byte, the one libjpeg (IJG 9d and later) writes from the same coefficients with
+ * jpeg_simple_progression() added to the calls named under "Optimised Huffman tables" — libjpeg forces optimize_coding in progressive
+ * mode, so every Huffman-coded scan carries tables made from that scan's own symbol counts, by the rules given there ("Lengths",
+ * "Symbols", "Codes", "Refusal").  Inputs and output are those of "The JPEG file".  No other scan script is offered.  This is the
+ * definition; where the wording below and libjpeg differ, libjpeg's output is the authority.
+ *
+ * Scans, each (components; Ss-Se; Ah, Al).  Three components:
+ *    1. (0,1,2; 0-0; 0,1)    2. (0; 1-5; 0,2)    3. (2; 1-63; 0,1)    4. (1; 1-63; 0,1)    5. (0; 6-63; 0,2)
+ *    6. (0; 1-63; 2,1)       7. (0,1,2; 0-0; 1,0)    8. (2; 1-63; 1,0)    9. (1; 1-63; 1,0)   10. (0; 1-63; 1,0)
+ * One component:
+ *    1. (0; 0-0; 0,1)    2. (0; 1-5; 0,2)    3. (0; 6-63; 0,2)    4. (0; 1-63; 2,1)    5. (0; 0-0; 1,0)    6. (0; 1-63; 1,0)
+ *
+ * File.  Items 1 to 3 of the header of "The JPEG file"; the frame header of item 4 with marker SOF2 (C2) in place of SOF0; then per
+ * scan its DHT segments, its SOS and its data; then FF D9.
+ *   DHT.  One segment per table the scan uses, made from the scan's own counts: for each component of the scan in order, its DC table
+ *   if the scan is a DC first scan (Ss = 0, Ah = 0) and then its AC table if Se > 0, a table once.  Component 0 uses slots DC0 / AC0,
+ *   the others DC1 / AC1.  So scan 1 of three components carries DC0 then DC1, an AC scan its one AC table (class/slot byte 10 for
+ *   component 0, 11 otherwise), a DC refinement scan none.
+ *   SOS (DA).  The number of components, per component its id c + 1 and the byte (Td << 4) | Ta — Td the DC slot in a DC first scan
+ *   and 0 otherwise, Ta the AC slot when Se > 0 and 0 otherwise — then Ss, Se, (Ah << 4) | Al.
+ *   Data.  Each scan's bits fill bytes from the highest bit down, the scan's last byte is completed with 1-bits, and every FF byte of
+ *   the scan's data is followed by 00 — per scan, on its own.
+ *
+ * Geometry.  A DC scan of three components walks the MCUs exactly as the scan of "The JPEG file" does, dummy blocks included; of one
+ * component, its blocks in raster order.  A dummy block holds the DC of the component's previous block in the scan.  An AC scan walks
+ * its one component's own block grid in raster order, without dummy blocks.
+ *
+ * Coding, per scan kind (code(s): the scan's table for the component; >> on a DC is an arithmetic shift):
+ *   DC first.  v = DC >> Al; d = v - pred[c], pred from 0, becoming v; category s = bit length of |d|; code(s), then s bits of d
+ *   (d >= 0) or of d - 1.  A dummy block codes d = 0.
+ *   DC refinement.  One raw bit per position: (DC >> Al) & 1 — for a dummy block its predecessor's bit, not 0.
+ *   AC first.  For k = Ss..Se in zigzag order, t = |c| >> Al (the shift applies to the absolute value: +-1 at Al = 1 is zero).  A zero
+ *   lengthens the run r.  A non-zero t first flushes a pending EOB run; then while r > 15: code(0xF0), r -= 16; then
+ *   code((r << 4) | s) with s the bit length of t, and s bits: t, or ~t for a negative coefficient; r = 0.  A block that ends with
+ *   r > 0 adds 1 to EOBRUN, which is flushed when it reaches 0x7FFF and at the end of the scan.  A flush of EOBRUN > 0 is
+ *   code(n << 4) with n = floor(log2(EOBRUN)) followed by the low n bits of EOBRUN.
+ *   AC refinement.  t = |c| >> Al; EOB is the position of the block's last t == 1 (0 if none); r = 0 and an empty buffer of correction
+ *   bits per block.  For k = Ss..Se: a zero t lengthens r.  Otherwise: while r > 15 and k <= EOB — flush the pending EOB run,
+ *   code(0xF0), r -= 16, emit and empty the buffer.  Then if t > 1, buffer the bit t & 1; if t == 1, flush the pending EOB run,
+ *   code((r << 4) | 1), one sign bit (1 for a positive coefficient), emit and empty the buffer, r = 0.  After the block, if r > 0 or
+ *   the buffer is not empty: EOBRUN += 1 and the buffered bits join the run's own buffer; the run is flushed when EOBRUN == 0x7FFF or
+ *   when its buffer holds MORE than 937 bits (libjpeg's 1000 - 64 + 1).  A flush is the EOBn symbol and its extra bits as above, then
+ *   the run's buffered bits in order.  The end of the scan flushes.
+ *
+ * Refusals.  Those of the optimised tables (a count above 10^9, a tree deeper than 32: J2P_ENOTSUP).  A coefficient whose shifted
+ * magnitude needs more than 10 bits cannot come from values in [-1023, 1023]; a table that holds such a symbol is refused as the
+ * baseline coder refuses it (J2P_EINVAL, "outside [-1023, 1023]").
+ *
+ * On the device the symbols of ALL scans are counted first and read back with one wait; the host makes every table (2 DC and 7 AC for
+ * three components, 1 DC and 3 AC for one); every scan's bits and stuffed FF bytes come back as arrays with one wait each.  So a file
+ * costs the waits of the optimised call, whatever the number of scans.  The calls below are new entry points and no flag of the _ex
+ * calls: those keep refusing every flag bit but J2P_JPEG_OPTIMIZE. */
+#define J2P_PROGRESSIVE_SCANS 10
+typedef struct j2p_progressive_scan {
+        unsigned ncomp, comp[3];        /* the scan's components */
+        unsigned ss, se, ah, al;
+        unsigned ntables, table[2];     /* the tables it carries, in DHT order: (class << 4) | slot */
+        unsigned long long counts[2][256];      /* ... and their symbol counts as taken on the device */
+        unsigned long long bits;                /* of the scan's data before padding and stuffing */
+        unsigned long long stuffed_bytes;       /* FF bytes that got their 00 */
+        unsigned long long eob_runs;            /* EOB runs flushed (AC scans) */
+} j2p_progressive_scan;
+typedef struct j2p_progressive_stats {
+        unsigned nscans;
+        j2p_progressive_scan scan[J2P_PROGRESSIVE_SCANS];
+} j2p_progressive_stats;
+/* j2p_planes_to_jpeg with the progressive file as its result; every rule of that call stands. */
+int j2p_planes_to_jpeg_progressive(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
+                                   size_t *size);
+/* j2p_entropy_encode with the progressive file as its result.  stats may be NULL; zeroed first; the counts are there once they have
+ * been read back, the bits and stuffed bytes once those have, also when the call then fails with J2P_ESPACE. */
+int j2p_entropy_encode_progressive(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
+                                   size_t capacity, size_t *size, j2p_progressive_stats *stats);
+/* j2p_batch_submit_jpeg and j2p_batch_submit_file_jpeg with the progressive file as the job's result: the choice travels in the job's
+ * record next to the copied spec, not in j2p_job.  Every rule of those calls stands (not with `tile`, ...). */
+int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                                      size_t capacity, size_t *size, int *ticket);
+
 /* Reading a JPEG file: the entropy-coded data of a baseline file Huffman-decoded ON THE DEVICE, so that a caller without libjpeg
  * gets the file's true quantised coefficients at every quality.  For each component the result is the grid of whole blocks
  * blocks_w x blocks_h of j2p_jpeg_info, block-major, 64 int16 in natural order — value for value what libjpeg's
@@ -1066,6 +1145,9 @@ int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *
 /* ... with the flags of j2p_batch_submit_jpeg_ex */
 int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
                                   size_t capacity, size_t *out_size, unsigned flags, int *ticket);
+/* ... with the progressive file as the result (j2p_batch_submit_jpeg_progressive) */
+int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec,
+                                           uint8_t *out, size_t capacity, size_t *out_size, int *ticket);
 
 /* The PNG file: the image's samples filtered and deflated ON THE DEVICE, so that a complete PNG file comes down instead of 3 or 6 bytes
  * per pixel for a host library to deflate on one core.  Every byte of the file is defined here; tests/png_cases.py restates it.  This is

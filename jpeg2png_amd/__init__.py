@@ -118,6 +118,18 @@ class _CEncodeStats(ctypes.Structure):
                 ("ac1", ctypes.c_ulonglong * 256), ("scan_bits", ctypes.c_ulonglong), ("stuffed_bytes", ctypes.c_ulonglong)]
 
 
+class _CProgressiveScan(ctypes.Structure):
+    """j2p_progressive_scan"""
+    _fields_ = [("ncomp", ctypes.c_uint), ("comp", ctypes.c_uint * 3), ("ss", ctypes.c_uint), ("se", ctypes.c_uint), ("ah", ctypes.c_uint),
+                ("al", ctypes.c_uint), ("ntables", ctypes.c_uint), ("table", ctypes.c_uint * 2), ("counts", (ctypes.c_ulonglong * 256) * 2),
+                ("bits", ctypes.c_ulonglong), ("stuffed_bytes", ctypes.c_ulonglong), ("eob_runs", ctypes.c_ulonglong)]
+
+
+class _CProgressiveStats(ctypes.Structure):
+    """j2p_progressive_stats"""
+    _fields_ = [("nscans", ctypes.c_uint), ("scan", _CProgressiveScan * 10)]
+
+
 class _CPng(ctypes.Structure):
     """j2p_png: the image, the filter and the block sizes of a PNG file made on the device"""
     _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("bits", ctypes.c_uint), ("filter", ctypes.c_int),
@@ -202,6 +214,8 @@ C_ABI_SYMBOLS = [
     "j2p_batch_submit_file", "j2p_batch_submit_file_jpeg",
     "j2p_planes_to_jpeg_ex", "j2p_entropy_encode_ex", "j2p_batch_submit_jpeg_ex", "j2p_batch_submit_file_jpeg_ex",
     "j2p_solver_output_scratch_bytes",
+    "j2p_planes_to_jpeg_progressive", "j2p_entropy_encode_progressive", "j2p_batch_submit_jpeg_progressive",
+    "j2p_batch_submit_file_jpeg_progressive",
     "j2p_planes_to_png", "j2p_png_encode", "j2p_batch_submit_png", "j2p_batch_submit_file_png",
     "j2p_jpeg_orientation", "j2p_solver_set_orientation", "j2p_solver_orientation", "j2p_solver_upright_bytes",
     "j2p_batch_next_orientation",
@@ -427,6 +441,14 @@ def _bind(path):
         lib.j2p_batch_submit_file_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
                                                       ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_entropy_encode_progressive"):
+        # (as above: an earlier commit's build writes no progressive file)
+        lib.j2p_planes_to_jpeg_progressive.argtypes = lib.j2p_planes_to_jpeg.argtypes
+        lib.j2p_entropy_encode_progressive.argtypes = lib.j2p_entropy_encode.argtypes + [ctypes.POINTER(_CProgressiveStats)]
+        lib.j2p_batch_submit_jpeg_progressive.argtypes = lib.j2p_batch_submit_jpeg.argtypes
+        lib.j2p_batch_submit_file_jpeg_progressive.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t,
+                                                               ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
+                                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_png_encode"):
         # (as above: an earlier commit's build writes no PNG)
         lib.j2p_planes_to_png.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CPng), ctypes.c_void_p, ctypes.c_size_t,
@@ -836,14 +858,18 @@ def _jpeg_bytes(call, guess):
     return buf[:size.value].tobytes()
 
 
-def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False):
+def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False, progressive=False):
     """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode): coefficients is a
     list of 1 or 3 int16 arrays [blocks_h, blocks_w, 64] in natural order — component 0's grid ceil(height / 8) x ceil(width / 8),
     the others' ceil of that over subsampling=(sx, sy) — every value in [-1023, 1023]; quant_tables: one per component, steps
     1..255, the third equal to the second.  Byte for byte what libjpeg's jpeg_write_coefficients writes with its defaults.
     optimize=True: with Huffman tables made for these coefficients from symbol counts taken on the GPU (J2P_JPEG_OPTIMIZE) — byte
     for byte libjpeg's file with optimize_coding (IJG 9d and later).  stats=True: (file, dict of the device's counts dc0, ac0, dc1,
-    ac1 — 256 each — scan_bits and stuffed_bytes)."""
+    ac1 — 256 each — scan_bits and stuffed_bytes).
+    progressive=True: the progressive file of libjpeg's jpeg_simple_progression() (j2p_entropy_encode_progressive; include/jpeg2png_amd.h:
+    "The progressive JPEG file"), every scan with tables of its own — optimize= changes nothing about it.  stats=True then gives
+    (file, list of one dict per scan: components, ss, se, ah, al, tables — {(class << 4) | slot: 256 counts}, in DHT order —, bits,
+    stuffed_bytes and eob_runs)."""
     lib = load_library()
     n = len(coefficients)
     if n not in (1, 3):
@@ -860,6 +886,15 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
         arrays.append(a)
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
     total = sum(a.size for a in arrays)
+    if progressive:
+        ps = _CProgressiveStats()
+        file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_progressive(int(device), ctypes.byref(spec), ptrs, n, out, cap, size,
+                                                                                     ctypes.byref(ps) if stats else None), 4096 + total // 4)
+        if not stats:
+            return file
+        return file, [{"components": tuple(k.comp[:k.ncomp]), "ss": k.ss, "se": k.se, "ah": k.ah, "al": k.al,
+                       "tables": {k.table[t]: list(k.counts[t]) for t in range(k.ntables)}, "bits": k.bits, "stuffed_bytes": k.stuffed_bytes,
+                       "eob_runs": k.eob_runs} for k in ps.scan[:ps.nscans]]
     if not optimize and not stats:
         return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
     st = _CEncodeStats()
@@ -1273,7 +1308,7 @@ class Solver:
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
-    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False):
+    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False, progressive=False):
         """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg):
         only the file comes down.  width x height: the image, cropped from the canvas's top left corner.  quality: libjpeg's
         tables for it (quality_tables), or quant_tables: one 64-entry table per component, steps 1..255, natural order, the third
@@ -1282,7 +1317,8 @@ class Solver:
         channel 0 of two more solvers (the separate solves of `-s`) give a colour file.  Whole-canvas solvers only.  Byte for
         byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults.  optimize=True: with
         Huffman tables made for the image, as entropy_encode(optimize=True) makes them (j2p_planes_to_jpeg_ex) — the same
-        coefficients in fewer bytes, for one more wait on the way."""
+        coefficients in fewer bytes, for one more wait on the way.  progressive=True: the progressive file, as
+        entropy_encode(progressive=True) writes it (j2p_planes_to_jpeg_progressive); optimize= changes nothing about it."""
         solvers = [self] + list(others)
         if len(solvers) not in (1, 3):
             raise J2PError("jpeg: others= takes the two other solvers of a colour file")
@@ -1292,6 +1328,8 @@ class Solver:
             refs[c] = _CPlaneRef(solvers[c]._h, 0) if len(solvers) == 3 else _CPlaneRef(self._h, c)
         spec, _held = _c_jpeg(width, height, n, quality, quant_tables, subsampling)
         guess = 4096 + int(width) * int(height) * n // 4
+        if progressive:
+            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_progressive(refs, n, ctypes.byref(spec), out, cap, size), guess)
         if not optimize:
             return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
         return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_ex(refs, n, ctypes.byref(spec), out, cap, size, J2P_JPEG_OPTIMIZE), guess)
@@ -1726,7 +1764,7 @@ def _job_output(job, want, planes, width, height):
 # back, what must stay alive until then, the C entry point's arguments for that output).
 
 def _fill_jpeg(job, jpeg, n, width, height):
-    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity", "optimize"}:
+    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity", "optimize", "progressive"}:
         raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
     if n not in (1, 3):
         raise J2PError("jpeg: three components or one")
@@ -1735,7 +1773,7 @@ def _fill_jpeg(job, jpeg, n, width, height):
     room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
     buffer, size = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
     job.out_w, job.out_h = int(width), int(height)
-    flags = J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
+    flags = "progressive" if jpeg.get("progressive") else J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
     return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
 
 
@@ -1871,7 +1909,10 @@ def _entry_point(source, source_args, kind, output_args):
     """step 4 -> (the C entry point of an (input kind, output kind) pair, its arguments between the job and the ticket)"""
     if kind == "jpeg":
         flags = output_args[-1]                     # (without flags the entry points that have none: the calls they always were)
-        ex, output_args = ("_ex", output_args) if flags else ("", output_args[:-1])
+        if flags == "progressive":                  # (an entry point of its own, and no flag)
+            ex, output_args = "_progressive", output_args[:-1]
+        else:
+            ex, output_args = ("_ex", output_args) if flags else ("", output_args[:-1])
         if source == "file":
             return "j2p_batch_submit_file_jpeg" + ex, source_args + output_args
         return "j2p_batch_submit_jpeg" + ex, (source_args or (None,)) + output_args     # (samples NULL: the planes' coefficients)
@@ -1922,10 +1963,11 @@ class Batch:
         outputs=, quant_tables=, jpeg=: file in and file out in one job); not with samples=, tile, nor a resized tensor outside
         outputs=.  A file the parser refuses raises J2PError (code J2P_EFORMAT / J2P_ENOTSUP) here; damage only its data
         shows fails the job in wait(), and no other job.
-        jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes, "optimize": bool} (with width and height; not
+        jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes, "optimize": bool, "progressive": bool} (with width and height; not
         with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
         JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
-        three planes.  optimize: Huffman tables made for the image, as Solver.to_jpeg(optimize=True).  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
+        three planes.  optimize: Huffman tables made for the image, as Solver.to_jpeg(optimize=True).  progressive: the
+        progressive file, as Solver.to_jpeg(progressive=True) (j2p_batch_submit_jpeg_progressive); optimize changes nothing about it.  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
         reaches; a larger file fails the job with the size it needs in the message);
         samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
         out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit

@@ -45,6 +45,7 @@ struct Request {
         uint8_t *jpeg_out = nullptr;
         size_t jpeg_capacity = 0, *jpeg_size = nullptr;
         unsigned jpeg_flags = 0;            // J2P_JPEG_*
+        bool jpeg_progressive = false;      // ... as the progressive file (flags 0)
         unsigned orientation = 0, orient_w = 0, orient_h = 0;    // j2p_batch_next_orientation: what the calling thread set for this submit
         const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
         uint8_t *png_out = nullptr;
@@ -58,6 +59,11 @@ struct Request {
         Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size, unsigned flags)
         {
                 jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size, jpeg_flags = flags;
+                return *this;
+        }
+        Request &progressive()
+        {
+                jpeg_progressive = true;
                 return *this;
         }
         Request &png_to(const j2p_png *spec, uint8_t *out, size_t capacity, size_t *size)
@@ -81,11 +87,13 @@ struct JpegOut {
         uint8_t *out = nullptr;
         size_t capacity = 0, *size = nullptr;
         unsigned flags = 0;
+        bool progressive = false;
         // from a request that validate_jpeg has passed: the tables travel with the job
         void set(const Request &q, unsigned nchannel)
         {
                 spec = *q.jpeg;
                 flags = q.jpeg_flags;
+                progressive = q.jpeg_progressive;
                 out = q.jpeg_out, capacity = q.jpeg_capacity, size = q.jpeg_size;
                 for(unsigned c = 0; c < nchannel; c++) {
                         memcpy(tables[c], q.jpeg->quant[c], sizeof(tables[c]));
@@ -323,6 +331,7 @@ int deliver_outputs(const Job &j, const j2p_job &d, const Band &band)
 
 int deliver_jpeg(const Job &j, const j2p_job &d, const Band &band)
 {
+        if(j.jpeg.progressive) { return j2p_planes_to_jpeg_progressive(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size); }
         return j2p_planes_to_jpeg_ex(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, j.jpeg.flags);
 }
 
@@ -862,6 +871,13 @@ int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples
         return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, flags), ticket);
 }
 
+int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                                      size_t capacity, size_t *size, int *ticket)
+{
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
+        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, 0).progressive(), ticket);
+}
+
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
                           size_t *size, int *ticket)
 {
@@ -880,6 +896,14 @@ int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
         return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, flags), ticket);
+}
+
+int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                           size_t capacity, size_t *out_size, int *ticket)
+{
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
+        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
+        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, 0).progressive(), ticket);
 }
 
 int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,

@@ -1,9 +1,10 @@
-// jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode) and a
+// jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode; the
+// progressive file: j2p_encode_progressive, j2p_entropy_encode_progressive) and a
 // baseline file's entropy-coded data back to coefficients (j2p_jpeg_open, j2p_decode_file, j2p_decoded_grids,
 // j2p_entropy_decode; include/jpeg2png_amd.h, j2p_internal.h) — and, at the end, the PNG coder: samples to the filtered and
 // deflated file (j2p_png_write, j2p_png_encode).
 //
-// A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
+// A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_progressive_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
 // uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
 // stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_scan.
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <string.h>
 #include <chrono>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "jpeg2png_amd.h"
@@ -18,6 +20,7 @@
 #include "j2p_hip_host.h"
 #include "j2p_huffman.h"
 #include "j2p_codec_kernels.hip.h"
+#include "j2p_progressive_kernels.hip.h"
 #include "j2p_decode_kernels.hip.h"
 #include "j2p_png_kernels.hip.h"
 
@@ -104,7 +107,8 @@ const HuffCodes &huffman_tables()
 // everything in front of the entropy-coded data; at most 623 bytes (a table has at most 12 DC or 162 AC symbols, which
 // j2p_encode_scan checks of the ones it makes).  Returns their number.
 constexpr size_t kJpegHeaderMax = 640;
-size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, uint8_t *out)
+// SOI, APP0, the DQTs and the frame header with marker `sof` (C0: baseline, C2: progressive); at most 200 bytes.  Returns their number.
+size_t jpeg_frame(const j2p_jpeg &spec, unsigned ncomp, uint8_t sof, uint8_t *out)
 {
         uint8_t *p = out;
         const auto segment = [&](uint8_t marker, size_t payload) {
@@ -124,7 +128,7 @@ size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &table
                 *p++ = (uint8_t)t;
                 for(int k = 0; k < 64; k++) { *p++ = (uint8_t)spec.quant[t][kZigzag[k]]; }
         }
-        segment(0xc0, 6 + 3 * ncomp);
+        segment(sof, 6 + 3 * ncomp);
         *p++ = 8;
         *p++ = (uint8_t)(spec.height >> 8);
         *p++ = (uint8_t)spec.height;
@@ -136,6 +140,17 @@ size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &table
                 *p++ = c == 0 && ncomp == 3 ? (uint8_t)((spec.sub_w << 4) | spec.sub_h) : 0x11;
                 *p++ = c ? 1 : 0;
         }
+        return (size_t)(p - out);
+}
+size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, uint8_t *out)
+{
+        uint8_t *p = out + jpeg_frame(spec, ncomp, 0xc0, out);
+        const auto segment = [&](uint8_t marker, size_t payload) {
+                *p++ = 0xff;
+                *p++ = marker;
+                *p++ = (uint8_t)((payload + 2) >> 8);
+                *p++ = (uint8_t)(payload + 2);
+        };
         for(unsigned k = 0; k < (ncomp == 3 ? 4u : 2u); k++) {
                 const j2p_huff_table &t = tables.t[k];
                 segment(0xc4, 1 + 16 + t.nvals);
@@ -352,6 +367,301 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         return J2P_OK;
 }
 
+// ---- the progressive file: k_prog_* (j2p_progressive_kernels.hip.h), k_scan_*, k_stuff_* ----
+namespace {
+
+// jpeg_simple_progression(): (components; Ss-Se; Ah, Al)
+struct ProgScript {
+        unsigned ncomp, comp[3], ss, se, ah, al;
+};
+const ProgScript kProgColour[10] = {{3, {0, 1, 2}, 0, 0, 0, 1}, {1, {0}, 1, 5, 0, 2},  {1, {2}, 1, 63, 0, 1},       {1, {1}, 1, 63, 0, 1}, {1, {0}, 6, 63, 0, 2},
+                                    {1, {0}, 1, 63, 2, 1},      {3, {0, 1, 2}, 0, 0, 1, 0}, {1, {2}, 1, 63, 1, 0}, {1, {1}, 1, 63, 1, 0}, {1, {0}, 1, 63, 1, 0}};
+const ProgScript kProgGrey[6] = {{1, {0}, 0, 0, 0, 1}, {1, {0}, 1, 5, 0, 2}, {1, {0}, 6, 63, 0, 2}, {1, {0}, 1, 63, 2, 1}, {1, {0}, 0, 0, 1, 0}, {1, {0}, 1, 63, 1, 0}};
+
+// the tables a scan carries, in DHT order, as (class << 4) | slot: a DC first scan its components' DC tables, an AC scan its AC table
+unsigned prog_scan_tables(const ProgScript &s, unsigned table[2])
+{
+        if(s.ss == 0 && s.ah == 0) {
+                table[0] = 0x00;
+                table[1] = 0x01;
+                return s.ncomp == 3 ? 2 : 1;
+        }
+        if(s.ss == 0) { return 0; }
+        table[0] = 0x10 | (s.comp[0] ? 1u : 0u);
+        return 1;
+}
+
+// a scan's DHT segments and SOS; at most 2 * 277 + 14 bytes.  Returns their number.
+constexpr size_t kProgScanHeaderMax = 576;
+size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned table[2], const j2p_huff_table made[2], uint8_t *out)
+{
+        uint8_t *p = out;
+        const auto segment = [&](uint8_t marker, size_t payload) {
+                *p++ = 0xff;
+                *p++ = marker;
+                *p++ = (uint8_t)((payload + 2) >> 8);
+                *p++ = (uint8_t)(payload + 2);
+        };
+        for(unsigned k = 0; k < ntables; k++) {
+                segment(0xc4, 1 + 16 + made[k].nvals);
+                *p++ = (uint8_t)table[k];
+                memcpy(p, made[k].bits, 16);
+                memcpy(p + 16, made[k].vals, made[k].nvals);
+                p += 16 + made[k].nvals;
+        }
+        segment(0xda, 1 + 2 * s.ncomp + 3);
+        *p++ = (uint8_t)s.ncomp;
+        for(unsigned i = 0; i < s.ncomp; i++) {
+                const unsigned slot = s.comp[i] ? 1u : 0u;
+                *p++ = (uint8_t)(s.comp[i] + 1);
+                *p++ = (uint8_t)(((s.ss == 0 && s.ah == 0 ? slot : 0u) << 4) | (s.se ? slot : 0u));
+        }
+        *p++ = (uint8_t)s.ss;
+        *p++ = (uint8_t)s.se;
+        *p++ = (uint8_t)((s.ah << 4) | s.al);
+        return (size_t)(p - out);
+}
+
+}  // namespace
+
+// The progressive coder (j2p_internal.h: what memory and fill are).  A scan's ITEMS are its positions (DC) or its component's blocks
+// (AC); all scans' items stand in one row, scan after scan.  The block's layout, each part aligned to 256 bytes:
+//   [coefficients per component][len: items u32][off: items u64][sums][per AC scan — flags: blocks u8][per AC scan — run: blocks u32]
+//   [hist: scans x 512 u64][flushes: scans u64]                                                      known from the spec
+//   [stage: every scan's stream, ceil(bits / 32) + 1 words each][count: chunks u32][ffoff: chunks u64][sums]   once the bits are
+//   [out: every scan's stuffed bytes, one behind the other]                                          once the FFs are
+// ONE exclusive sum places the items of all scans (a scan's stream starts at its first item's offset) and ONE the FF counts of all
+// scans' chunks, so three reads come back as arrays — all counts, all scans' bits, all scans' FFs — with a wait each, as in the
+// optimised call, and the file's bytes with a fourth.  The block is asked for three times under the rule of j2p_encode_scan: when
+// it moved, what had been computed on the device is computed again; the counts and tables live on the host by then.
+int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                           const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                           j2p_progressive_stats *stats)
+{
+        ScanGeom g = scan_geometry(spec, ncomp);
+        const ProgScript *const script = ncomp == 3 ? kProgColour : kProgGrey;
+        const unsigned nscans = ncomp == 3 ? 10 : 6;
+        ProgScan scan[J2P_PROGRESSIVE_SCANS];
+        size_t first[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        for(unsigned s = 0; s < nscans; s++) {
+                const ProgScript &k = script[s];
+                const unsigned c = k.comp[0];
+                scan[s] = {k.ss, k.se, k.al, k.ah ? 1u : 0u, k.ss == 0 ? g.nslots : g.bw[c] * g.bh[c]};
+                first[s + 1] = first[s] + scan[s].n;
+        }
+        const size_t nitems = first[nscans];
+        if(nitems > 0xffffffffull) { return j2p_fail(J2P_EINVAL, "jpeg: %zu scan positions are too many", nitems); }
+        const unsigned item_tiles = (unsigned)((nitems + kScanTile - 1) / kScanTile);
+        j2p_carve part;
+        size_t coef_at[3], flags_at[J2P_PROGRESSIVE_SCANS] = {0}, run_at[J2P_PROGRESSIVE_SCANS] = {0};
+        for(unsigned c = 0; c < ncomp; c++) { coef_at[c] = part(j2p_grid_bytes(g.bw[c], g.bh[c])); }
+        const size_t coef_bytes = part.total;
+        const size_t len_at = part(nitems * 4), off_at = part(nitems * 8), sums_at = part(((size_t)item_tiles + 1) * 8);
+        for(unsigned s = 0; s < nscans; s++) {
+                if(scan[s].ss) { flags_at[s] = part((size_t)scan[s].n); }
+        }
+        const size_t runs_at = part.total;
+        for(unsigned s = 0; s < nscans; s++) {
+                if(scan[s].ss) { run_at[s] = part((size_t)scan[s].n * 4); }
+        }
+        const size_t runs_bytes = part.total - runs_at;
+        const size_t hist_bytes = (size_t)nscans * (kProgHistogram + 1) * 8;
+        const size_t hist_at = part(hist_bytes), fixed = part.total;     // (the flush counters behind the counts)
+        char *base = nullptr;
+        const auto take = [&](size_t bytes, bool *moved) {
+                void *p = nullptr;
+                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
+                base = static_cast<char *>(p);
+                return (int)J2P_OK;
+        };
+        const auto u8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(base + at); };
+        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        const auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long *>(base + at); };
+        const auto grid = [](unsigned n) { return dim3((n + 255) / 256); };
+        static const ProgCodes no_codes = {};
+        std::vector<ProgCodes> codes(nscans, no_codes);
+        const int16_t *coef[3] = {nullptr, nullptr, nullptr};
+        // the coefficients into the block, and what of every AC scan needs no table: the blocks' flags and the EOB runs
+        const auto coefficients = [&] {
+                int16_t *into[3] = {nullptr, nullptr, nullptr};
+                for(unsigned c = 0; c < ncomp; c++) {
+                        into[c] = reinterpret_cast<int16_t *>(base + coef_at[c]);
+                        coef[c] = g.coef[c] = into[c];
+                }
+                fill(stream, into);
+                (void)hipMemsetAsync(base + hist_at, 0, hist_bytes, stream);
+                (void)hipMemsetAsync(base + runs_at, 0, runs_bytes, stream);
+                for(unsigned s = 0; s < nscans; s++) {
+                        if(scan[s].ss == 0) { continue; }
+                        const unsigned per_workgroup = 4 * kEntropyIters;
+                        hipLaunchKernelGGL(k_prog_classify, dim3((scan[s].n + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream,
+                                           coef[script[s].comp[0]], scan[s], u8(flags_at[s]));
+                        hipLaunchKernelGGL(k_prog_runs, grid(scan[s].n), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(flags_at[s])), scan[s],
+                                           u32(run_at[s]), u64(hist_at) + (size_t)nscans * kProgHistogram + s);
+                }
+        };
+        // one scan's walk in one of its three modes
+        const auto walk = [&](auto mode, unsigned s, unsigned *stage) {
+                constexpr int kMode = decltype(mode)::value;
+                unsigned long long *const hist = u64(hist_at) + (size_t)s * kProgHistogram;
+                unsigned *const len = u32(len_at) + first[s];
+                const unsigned long long *const off = u64(off_at) + first[s];
+                if(scan[s].ss == 0) {
+                        if(kMode == kProgCount && scan[s].refine) { return; }
+                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_dc<kMode>), grid(scan[s].n), dim3(256), 0, stream, g, scan[s], codes[s], hist, len, off, stage);
+                } else {
+                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_ac<kMode>), grid(scan[s].n), dim3(256), 0, stream, coef[script[s].comp[0]], scan[s],
+                                           static_cast<const uint8_t *>(u8(flags_at[s])), static_cast<const unsigned *>(u32(run_at[s])), codes[s], hist, len, off,
+                                           stage);
+                }
+        };
+        const auto lengths = [&] {
+                for(unsigned s = 0; s < nscans; s++) { walk(std::integral_constant<int, kProgLength>(), s, nullptr); }
+                queue_scan(stream, u32(len_at), (unsigned)nitems, u64(sums_at), u64(off_at));
+        };
+        bool moved = false;
+        if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }
+        coefficients();
+        for(unsigned s = 0; s < nscans; s++) { walk(std::integral_constant<int, kProgCount>(), s, nullptr); }
+        HIP_TRY(hipGetLastError());
+        // wait 1: every scan's counts
+        std::vector<unsigned long long> hist;
+        try {
+                hist.resize(hist_bytes / 8);
+        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        HIP_TRY(hipMemcpyAsync(hist.data(), base + hist_at, hist_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if(stats) {
+                memset(stats, 0, sizeof(*stats));
+                stats->nscans = nscans;
+        }
+        j2p_huff_table made[J2P_PROGRESSIVE_SCANS][2];
+        unsigned ntables[J2P_PROGRESSIVE_SCANS], table[J2P_PROGRESSIVE_SCANS][2];
+        memset(made, 0, sizeof(made));
+        int refused = J2P_OK;
+        for(unsigned s = 0; s < nscans; s++) {
+                ntables[s] = prog_scan_tables(script[s], table[s]);
+                if(stats) {
+                        j2p_progressive_scan &o = stats->scan[s];
+                        o.ncomp = script[s].ncomp;
+                        memcpy(o.comp, script[s].comp, sizeof(o.comp));
+                        o.ss = script[s].ss, o.se = script[s].se, o.ah = script[s].ah, o.al = script[s].al;
+                        o.ntables = ntables[s];
+                        memcpy(o.table, table[s], sizeof(o.table));
+                        o.eob_runs = hist[(size_t)nscans * kProgHistogram + s];
+                }
+                for(unsigned k = 0; k < ntables[s]; k++) {
+                        uint64_t count[256];
+                        for(unsigned i = 0; i < 256; i++) { count[i] = hist[(size_t)s * kProgHistogram + k * 256 + i]; }
+                        if(stats) { memcpy(stats->scan[s].counts[k], count, sizeof(count)); }
+                        if(refused != J2P_OK) { continue; }
+                        const int rc = j2p_huff_build(count, &made[s][k]);
+                        if(rc == J2P_HUFF_COUNT) {
+                                refused = j2p_fail(J2P_ENOTSUP, "jpeg: a symbol is coded more than %llu times: no optimised table for it", J2P_HUFF_COUNT_MAX);
+                        } else if(rc != J2P_HUFF_OK) {
+                                refused = j2p_fail(J2P_ENOTSUP, "jpeg: an optimised code would be longer than %d bits before limiting", J2P_HUFF_TREE_MAX);
+                        }
+                        // a DC category above 11, an AC size above 10: the shifted magnitude needs more bits than the file's precision has
+                        for(unsigned i = 0; i < made[s][k].nvals && refused == J2P_OK; i++) {
+                                const unsigned v = made[s][k].vals[i];
+                                if(table[s][k] & 0x10 ? (v & 15u) > 10u : v > 11u) { refused = j2p_fail(J2P_EINVAL, "jpeg: a coefficient is outside [-1023, 1023]"); }
+                        }
+                        huffman_codes(made[s][k].bits, made[s][k].vals, codes[s].code[k]);
+                }
+        }
+        if(refused != J2P_OK) { return refused; }
+        // wait 2: every scan's bits
+        lengths();
+        unsigned long long begins[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        const auto read_bits = [&]() -> int {
+                for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&begins[s], u64(off_at) + first[s], 8, hipMemcpyDeviceToHost, stream)); }
+                HIP_TRY(hipMemcpyAsync(&begins[nscans], u64(sums_at) + item_tiles, 8, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                return J2P_OK;
+        };
+        if(const int rc = read_bits(); rc != J2P_OK) { return rc; }
+        size_t nbytes[J2P_PROGRESSIVE_SCANS], stage_word[J2P_PROGRESSIVE_SCANS + 1] = {0}, chunk[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        size_t byte[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        for(unsigned s = 0; s < nscans; s++) {
+                const unsigned long long bits = begins[s + 1] - begins[s];
+                if(stats) { stats->scan[s].bits = bits; }
+                nbytes[s] = (size_t)((bits + 7) / 8);
+                stage_word[s + 1] = stage_word[s] + (size_t)((bits + 31) / 32) + 1;
+                chunk[s + 1] = chunk[s] + (nbytes[s] + kStuffChunk - 1) / kStuffChunk;
+                byte[s + 1] = byte[s] + nbytes[s];
+        }
+        if(chunk[nscans] > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "jpeg: %zu bytes of scan data are too many", byte[nscans]); }
+        const unsigned nchunks = (unsigned)chunk[nscans], chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
+        const size_t stage_at = part(stage_word[nscans] * 4), count_at = part((size_t)nchunks * 4), ffoff_at = part((size_t)nchunks * 8);
+        const size_t ffsums_at = part(((size_t)chunk_tiles + 1) * 8), out_at = part.total;
+        // from the bit offsets to every scan's stream and where its FF bytes are
+        const auto pack = [&] {
+                (void)hipMemsetAsync(base + stage_at, 0, stage_word[nscans] * 4, stream);
+                for(unsigned s = 0; s < nscans; s++) {
+                        unsigned *const stage = u32(stage_at) + stage_word[s];
+                        const unsigned n = (unsigned)(chunk[s + 1] - chunk[s]);
+                        walk(std::integral_constant<int, kProgPack>(), s, stage);
+                        hipLaunchKernelGGL(k_stuff_count, dim3((n + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(stage), nbytes[s], n,
+                                           u32(count_at) + chunk[s]);
+                }
+                queue_scan(stream, u32(count_at), nchunks, u64(ffsums_at), u64(ffoff_at));
+        };
+        if(const int rc = take(out_at + byte[nscans] + byte[nscans] / 16 + 256, &moved); rc != J2P_OK) { return rc; }
+        if(moved) {
+                coefficients();
+                lengths();
+        }
+        pack();
+        // wait 3: every scan's FF bytes
+        unsigned long long ffs[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&ffs[s], u64(ffoff_at) + chunk[s], 8, hipMemcpyDeviceToHost, stream)); }
+        HIP_TRY(hipMemcpyAsync(&ffs[nscans], u64(ffsums_at) + chunk_tiles, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        // the headers, and with them the file's size
+        uint8_t frame[256];
+        std::vector<uint8_t> heads;
+        size_t head_at[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        try {
+                heads.resize((size_t)nscans * kProgScanHeaderMax);
+        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        const size_t frame_bytes = jpeg_frame(spec, ncomp, 0xc2, frame);
+        for(unsigned s = 0; s < nscans; s++) {
+                if(stats) { stats->scan[s].stuffed_bytes = ffs[s + 1] - ffs[s]; }
+                head_at[s + 1] = head_at[s] + prog_scan_header(script[s], ntables[s], table[s], made[s], heads.data() + head_at[s]);
+        }
+        const size_t data_bytes = byte[nscans] + (size_t)ffs[nscans];
+        *size = frame_bytes + head_at[nscans] + data_bytes + 2;
+        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
+        if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
+        if(moved) {
+                coefficients();
+                lengths();
+                pack();
+        }
+        // wait 4: the scans' bytes to their places in the file, the headers between them
+        uint8_t *p = out_host + frame_bytes;
+        for(unsigned s = 0; s < nscans; s++) {
+                const unsigned n = (unsigned)(chunk[s + 1] - chunk[s]);
+                const size_t stuffed = nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]);
+                hipLaunchKernelGGL(k_stuff_copy, dim3((n + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(u32(stage_at) + stage_word[s]), nbytes[s], n,
+                                   static_cast<const unsigned long long *>(u64(ffoff_at) + chunk[s]), u8(out_at) + byte[s]);
+                p += head_at[s + 1] - head_at[s];
+                HIP_TRY(hipMemcpyAsync(p, base + out_at + byte[s] + (size_t)ffs[s], stuffed, hipMemcpyDeviceToHost, stream));
+                p += stuffed;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        memcpy(out_host, frame, frame_bytes);
+        p = out_host + frame_bytes;
+        for(unsigned s = 0; s < nscans; s++) {
+                memcpy(p, heads.data() + head_at[s], head_at[s + 1] - head_at[s]);
+                p += head_at[s + 1] - head_at[s] + nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]);
+        }
+        p[0] = 0xff;
+        p[1] = 0xd9;
+        return J2P_OK;
+}
+
 // the device of a j2p_entropy_* call
 static int check_device(int device)
 {
@@ -361,13 +671,13 @@ static int check_device(int device)
         return J2P_OK;
 }
 
-extern "C" {
-
-int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
-                          size_t *size, unsigned flags, j2p_encode_stats *stats)
+// a coder (j2p_encode_scan, j2p_encode_progressive) on the caller's coefficients in host memory: the argument checks, a stream, one
+// pooled block that grows as the solvers' scratch does
+using HostCoder = std::function<int(hipStream_t, const std::function<int(size_t, void **, bool *)> &, const std::function<void(hipStream_t, int16_t *const[3])> &)>;
+static int encode_host_coefficients(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, const size_t *size,
+                                    const HostCoder &coder)
 {
         if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const char *why = j2p_jpeg_error(spec, ncomp)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, ncomp);
         size_t values[3] = {0, 0, 0};
@@ -385,11 +695,10 @@ int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const
         DeviceGuard guard(device);
         hipStream_t stream = nullptr;
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        // one pooled block that grows as the solvers' scratch does
         void *block = nullptr;
         size_t block_bytes = 0;
-        const int rc = j2p_encode_scan(
-                stream, *spec, ncomp,
+        const int rc = coder(
+                stream,
                 [&](size_t bytes, void **p, bool *moved) {
                         *moved = block_bytes < bytes;
                         if(block_bytes < bytes) {
@@ -404,12 +713,31 @@ int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const
                 },
                 [&](hipStream_t st, int16_t *const coef[3]) {
                         for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
-                },
-                out_host, capacity, size, flags, stats);
+                });
         (void)hipStreamSynchronize(stream);
         j2p_pool_give(device, block, block_bytes);
         (void)hipStreamDestroy(stream);
         return rc;
+}
+
+extern "C" {
+
+int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                          size_t *size, unsigned flags, j2p_encode_stats *stats)
+{
+        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
+                return j2p_encode_scan(stream, *spec, ncomp, memory, fill, out_host, capacity, size, flags, stats);
+        });
+}
+
+int j2p_entropy_encode_progressive(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                                   size_t *size, j2p_progressive_stats *stats)
+{
+        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
+                return j2p_encode_progressive(stream, *spec, ncomp, memory, fill, out_host, capacity, size, stats);
+        });
 }
 
 int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,

@@ -222,6 +222,11 @@ j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp);
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                     const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
                     unsigned flags = 0, j2p_encode_stats *stats = nullptr);
+// The progressive coder: j2p_encode_scan's contract with the file of "The progressive JPEG file" (include/jpeg2png_amd.h) as its
+// result.  The symbols of all scans are counted on the device; the stream is waited for four times whatever the number of scans.
+int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                           const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                           j2p_progressive_stats *stats = nullptr);
 // what is wrong with the flags of a j2p_*_ex call that writes a JPEG file, or NULL
 static inline const char *j2p_jpeg_flags_error(unsigned flags) { return flags & ~J2P_JPEG_OPTIMIZE ? "jpeg: unknown flag bits" : nullptr; }
 

@@ -876,8 +876,9 @@ int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub
 }
 
 // the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_scan), which is the first solver's scratch
-int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
-                          unsigned flags)
+// (progressive: j2p_encode_progressive codes them, and flags is 0)
+static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
+                          unsigned flags, bool progressive)
 {
         if(!planes || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
@@ -901,16 +902,26 @@ int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j
         }
         if(const int rc = upright_queue(up, stream); rc != J2P_OK) { return rc; }
         j2p_solver *const owner = planes[0].solver;
-        return j2p_encode_scan(
-                stream, *spec, nplane,
-                [&](size_t bytes, void **p, bool *moved) {
-                        *moved = j2p_solver_scratch_bytes(owner) < bytes;
-                        return j2p_solver_scratch(owner, bytes, p);
-                },
-                [&](hipStream_t st, int16_t *const coef[3]) {
-                        for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
-                },
-                out_host, capacity, size, flags);
+        const auto memory = [&](size_t bytes, void **p, bool *moved) {
+                *moved = j2p_solver_scratch_bytes(owner) < bytes;
+                return j2p_solver_scratch(owner, bytes, p);
+        };
+        const auto fill = [&](hipStream_t st, int16_t *const coef[3]) {
+                for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
+        };
+        if(progressive) { return j2p_encode_progressive(stream, *spec, nplane, memory, fill, out_host, capacity, size); }
+        return j2p_encode_scan(stream, *spec, nplane, memory, fill, out_host, capacity, size, flags);
+}
+
+int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
+                          unsigned flags)
+{
+        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, flags, false);
+}
+
+int j2p_planes_to_jpeg_progressive(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
+{
+        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, 0, true);
 }
 
 int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
