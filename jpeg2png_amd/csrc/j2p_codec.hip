@@ -7,6 +7,9 @@
 // A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_progressive_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
 // uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
 // stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_scan.
+//
+// The three file coders each work in one device block whose size they learn on the way: j2p_coder_block.h asks `memory` for it and
+// queues a coder's stages again when it moved, PooledCall is the stand-alone entry points' `memory`, stuffed_streams both JPEG coders' end.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,6 +20,7 @@
 
 #include "jpeg2png_amd.h"
 #include "j2p_internal.h"
+#include "j2p_coder_block.h"
 #include "j2p_hip_host.h"
 #include "j2p_huffman.h"
 #include "j2p_codec_kernels.hip.h"
@@ -107,28 +111,39 @@ const HuffCodes &huffman_tables()
 // everything in front of the entropy-coded data; at most 623 bytes (a table has at most 12 DC or 162 AC symbols, which
 // j2p_encode_scan checks of the ones it makes).  Returns their number.
 constexpr size_t kJpegHeaderMax = 640;
+// a marker segment's first four bytes at p, which moves behind them: the marker and the length of `payload` bytes and itself
+void segment(uint8_t *&p, uint8_t marker, size_t payload)
+{
+        *p++ = 0xff;
+        *p++ = marker;
+        *p++ = (uint8_t)((payload + 2) >> 8);
+        *p++ = (uint8_t)(payload + 2);
+}
+// one table's DHT segment at p, which moves behind it; id: (class << 4) | slot
+void dht_segment(uint8_t *&p, unsigned id, const j2p_huff_table &t)
+{
+        segment(p, 0xc4, 1 + 16 + t.nvals);
+        *p++ = (uint8_t)id;
+        memcpy(p, t.bits, 16);
+        memcpy(p + 16, t.vals, t.nvals);
+        p += 16 + t.nvals;
+}
 // SOI, APP0, the DQTs and the frame header with marker `sof` (C0: baseline, C2: progressive); at most 200 bytes.  Returns their number.
 size_t jpeg_frame(const j2p_jpeg &spec, unsigned ncomp, uint8_t sof, uint8_t *out)
 {
         uint8_t *p = out;
-        const auto segment = [&](uint8_t marker, size_t payload) {
-                *p++ = 0xff;
-                *p++ = marker;
-                *p++ = (uint8_t)((payload + 2) >> 8);
-                *p++ = (uint8_t)(payload + 2);
-        };
         *p++ = 0xff;
         *p++ = 0xd8;
         static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-        segment(0xe0, sizeof(jfif));
+        segment(p, 0xe0, sizeof(jfif));
         memcpy(p, jfif, sizeof(jfif));
         p += sizeof(jfif);
         for(unsigned t = 0; t < (ncomp == 3 ? 2u : 1u); t++) {
-                segment(0xdb, 65);
+                segment(p, 0xdb, 65);
                 *p++ = (uint8_t)t;
                 for(int k = 0; k < 64; k++) { *p++ = (uint8_t)spec.quant[t][kZigzag[k]]; }
         }
-        segment(sof, 6 + 3 * ncomp);
+        segment(p, sof, 6 + 3 * ncomp);
         *p++ = 8;
         *p++ = (uint8_t)(spec.height >> 8);
         *p++ = (uint8_t)spec.height;
@@ -145,21 +160,8 @@ size_t jpeg_frame(const j2p_jpeg &spec, unsigned ncomp, uint8_t sof, uint8_t *ou
 size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, uint8_t *out)
 {
         uint8_t *p = out + jpeg_frame(spec, ncomp, 0xc0, out);
-        const auto segment = [&](uint8_t marker, size_t payload) {
-                *p++ = 0xff;
-                *p++ = marker;
-                *p++ = (uint8_t)((payload + 2) >> 8);
-                *p++ = (uint8_t)(payload + 2);
-        };
-        for(unsigned k = 0; k < (ncomp == 3 ? 4u : 2u); k++) {
-                const j2p_huff_table &t = tables.t[k];
-                segment(0xc4, 1 + 16 + t.nvals);
-                *p++ = (uint8_t)(((k & 1u) << 4) | (k >> 1));
-                memcpy(p, t.bits, 16);
-                memcpy(p + 16, t.vals, t.nvals);
-                p += 16 + t.nvals;
-        }
-        segment(0xda, 1 + 2 * ncomp + 3);
+        for(unsigned k = 0; k < (ncomp == 3 ? 4u : 2u); k++) { dht_segment(p, ((k & 1u) << 4) | (k >> 1), tables.t[k]); }
+        segment(p, 0xda, 1 + 2 * ncomp + 3);
         *p++ = (uint8_t)ncomp;
         for(unsigned c = 0; c < ncomp; c++) {
                 *p++ = (uint8_t)(c + 1);
@@ -191,6 +193,8 @@ ScanGeom scan_geometry(const j2p_jpeg &spec, unsigned ncomp)
         return g;
 }
 
+using ull = unsigned long long;     // the kernels' 64-bit counts and offsets
+
 // an exclusive sum of n counts on the stream: in -> out, sums: ceil(n / kScanTile) + 1 words, the last the total
 void queue_scan(hipStream_t stream, const unsigned *in, unsigned n, unsigned long long *sums, unsigned long long *out)
 {
@@ -217,6 +221,15 @@ j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp)
         return g;
 }
 
+// j2p_huff_build (j2p_huffman.h), its refusals as a coder answers them
+static int build_table(const uint64_t count[256], j2p_huff_table *table)
+{
+        const int rc = j2p_huff_build(count, table);
+        if(rc == J2P_HUFF_COUNT) { return j2p_fail(J2P_ENOTSUP, "jpeg: a symbol is coded more than %llu times: no optimised table for it", J2P_HUFF_COUNT_MAX); }
+        if(rc != J2P_HUFF_OK) { return j2p_fail(J2P_ENOTSUP, "jpeg: an optimised code would be longer than %d bits before limiting", J2P_HUFF_TREE_MAX); }
+        return J2P_OK;
+}
+
 // The tables made for this image from the device's counts (hist: [table][12 DC + 256 AC], as k_entropy_histogram leaves them),
 // and the counts as the caller sees them
 static int tables_from_counts(const unsigned long long *hist, unsigned ncomp, FileTables &tables, j2p_encode_stats *stats)
@@ -231,15 +244,77 @@ static int tables_from_counts(const unsigned long long *hist, unsigned ncomp, Fi
                         for(unsigned s = 0; s < 256; s++) { to[s] = count[s]; }
                 }
                 if(k >= 2 && ncomp != 3) { continue; }
-                const int rc = j2p_huff_build(count, &tables.t[k]);
-                if(rc == J2P_HUFF_COUNT) {
-                        return j2p_fail(J2P_ENOTSUP, "jpeg: a symbol is coded more than %llu times: no optimised table for it", J2P_HUFF_COUNT_MAX);
-                }
-                if(rc != J2P_HUFF_OK) { return j2p_fail(J2P_ENOTSUP, "jpeg: an optimised code would be longer than %d bits before limiting", J2P_HUFF_TREE_MAX); }
+                if(const int rc = build_table(count, &tables.t[k]); rc != J2P_OK) { return rc; }
                 if(tables.t[k].nvals > (k & 1u ? 162u : 12u)) { return j2p_fail(J2P_EINVAL, "jpeg: a coefficient is outside [-1023, 1023]"); }
         }
         return J2P_OK;
 }
+
+namespace {
+
+// what n streams of a JPEG file are once their FF bytes are counted
+struct Stuffed {
+        size_t nbytes[J2P_PROGRESSIVE_SCANS];   // stream s before stuffing
+        ull ffs[J2P_PROGRESSIVE_SCANS + 1];     // the FF bytes of the streams before s; [n]: of all
+        size_t bytes(unsigned s) const { return nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]); }    // stream s in the file
+};
+
+// The end both JPEG coders share: n streams (a baseline file's one scan, a progressive file's scans) of bits[s] bits, through the
+// block's parts behind `part` — [stage: ceil(bits / 32) + 1 words per stream][count: chunks u32][ffoff: chunks u64][sums][out: the
+// stuffed bytes, one stream behind the other] — to the host.  The block's last stage and its last two requests are here, and the
+// block is not asked again afterwards: pack(s, stage) queues what leaves stream s in its zeroed words, then the FF bytes of every
+// stream's chunks are counted and ONE exclusive sum places them all.  The sums at the streams' first chunks and the total come
+// down (a wait); place(done, to) writes the file's size and, where the buffer has room for it (or else its error ends the call), the
+// headers, and says where stream s goes on the host (to[s]); every stream is stuffed and comes down (a wait), and EOI follows the last.
+// A baseline file cannot meet the refusal: its scan has at most 6 * 8192^2 / 4 slots of less than 1700 bits, 84 million chunks.
+template<class Pack, class Place>
+int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part, unsigned n, const ull *bits, const Pack &pack, const Place &place)
+{
+        Stuffed done;
+        size_t word[J2P_PROGRESSIVE_SCANS + 1] = {0}, chunk[J2P_PROGRESSIVE_SCANS + 1] = {0}, byte[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        for(unsigned s = 0; s < n; s++) {
+                done.nbytes[s] = (size_t)((bits[s] + 7) / 8);
+                word[s + 1] = word[s] + (size_t)((bits[s] + 31) / 32) + 1;
+                chunk[s + 1] = chunk[s] + (done.nbytes[s] + kStuffChunk - 1) / kStuffChunk;
+                byte[s + 1] = byte[s] + done.nbytes[s];
+        }
+        if(chunk[n] > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "jpeg: %zu bytes of scan data are too many", byte[n]); }
+        const unsigned nchunks = (unsigned)chunk[n], chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
+        const size_t stage_at = part(word[n] * 4), count_at = part((size_t)nchunks * 4), ffoff_at = part((size_t)nchunks * 8);
+        const size_t ffsums_at = part(((size_t)chunk_tiles + 1) * 8), out_at = part.total;
+        const auto chunks = [&](unsigned s) { return (unsigned)(chunk[s + 1] - chunk[s]); };
+        // from the bit offsets to every stream and where its FF bytes are
+        const auto streams = [&] {
+                (void)hipMemsetAsync(block.at(stage_at), 0, word[n] * 4, stream);
+                for(unsigned s = 0; s < n; s++) {
+                        unsigned *const stage = block.at<unsigned>(stage_at) + word[s];
+                        pack(s, stage);
+                        hipLaunchKernelGGL(k_stuff_count, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(stage), done.nbytes[s],
+                                           chunks(s), block.at<unsigned>(count_at) + chunk[s]);
+                }
+                queue_scan(stream, block.at<unsigned>(count_at), nchunks, block.at<ull>(ffsums_at), block.at<ull>(ffoff_at));
+        };
+        if(const int rc = block.grow(out_at + byte[n] + byte[n] / 16 + 256); rc != J2P_OK) { return rc; }
+        block.stage(streams);
+        done.ffs[0] = 0;
+        for(unsigned s = 1; s < n; s++) { HIP_TRY(hipMemcpyAsync(&done.ffs[s], block.at<ull>(ffoff_at) + chunk[s], 8, hipMemcpyDeviceToHost, stream)); }
+        HIP_TRY(hipMemcpyAsync(&done.ffs[n], block.at<ull>(ffsums_at) + chunk_tiles, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint8_t *to[J2P_PROGRESSIVE_SCANS];
+        if(const int rc = place(done, to); rc != J2P_OK) { return rc; }
+        if(const int rc = block.grow(out_at + byte[n] + (size_t)done.ffs[n]); rc != J2P_OK) { return rc; }
+        for(unsigned s = 0; s < n; s++) {
+                hipLaunchKernelGGL(k_stuff_copy, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(block.at<unsigned>(stage_at) + word[s]),
+                                   done.nbytes[s], chunks(s), static_cast<const ull *>(block.at<ull>(ffoff_at) + chunk[s]), block.at<uint8_t>(out_at) + byte[s]);
+                HIP_TRY(hipMemcpyAsync(to[s], block.at(out_at) + byte[s] + (size_t)done.ffs[s], done.bytes(s), hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        memcpy(to[n - 1] + done.bytes(n - 1), "\xff\xd9", 2);
+        return J2P_OK;
+}
+
+}  // namespace
 
 // The coder (j2p_internal.h: what memory and fill are).  The block's layout, each part aligned to 256 bytes:
 //   [coefficients per component][len: nslots u32][off: nslots u64][sums: tiles + 1 u64]              known from the spec
@@ -247,12 +322,13 @@ static int tables_from_counts(const unsigned long long *hist, unsigned ncomp, Fi
 //   [stage: the stream, ceil(bits / 32) + 1 words][count: chunks u32][ffoff: chunks u64][sums]      known once the bits are
 //   [out: the stuffed bytes]                                                                        known once the FFs are
 // so the two totals are read back (8 bytes each, a wait each) and the block is asked for three times, the first two times
-// with a guess for what is not known yet; when it moved, what had been computed is computed again.  A second image of the
-// same size or smaller finds the block large enough at once.
+// with a guess for what is not known yet (j2p_coder_block.h).  Its stages are the coefficients, the lengths and — in
+// stuffed_streams — the stream: a block that moved has them queued again.  A second image of the same size or smaller finds the
+// block large enough at once.
 // J2P_JPEG_OPTIMIZE (or stats) puts k_entropy_histogram and a third read-back and wait, of the 2 x 268 counters, between the
 // coefficients and the lengths: the tables are made on the host (j2p_huffman.h) and this call's own HuffCodes go to the two
-// coding kernels.  The counts live on the host from then on: a block that moves has its coefficients and stages made again,
-// not its counts.  Without either, the launches, the layout and the bytes are what they were before the option existed.
+// coding kernels.  The counting is no stage: the counts live on the host from then on.  Without either, the launches, the layout
+// and the bytes are what they were before the option existed.
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                     const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
                     unsigned flags, j2p_encode_stats *stats)
@@ -271,40 +347,28 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         const size_t len_at = part((size_t)nslots * 4), off_at = part((size_t)nslots * 8), sums_at = part(((size_t)slot_tiles + 1) * 8);
         const size_t hist_at = counting ? part(kHistogramEntries * 8) : 0;
         const size_t fixed = part.total;
-        char *base = nullptr;
-        const auto take = [&](size_t bytes, bool *moved) {
-                void *p = nullptr;
-                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
-                base = static_cast<char *>(p);
-                return (int)J2P_OK;
-        };
-        const auto at = [&](size_t offset) { return base + offset; };
+        j2p_coder_block block(memory);
         const unsigned per_workgroup = 4 * kEntropyIters, coding_grid = (nslots + per_workgroup - 1) / per_workgroup;
         // the coefficients into the block
         const auto coefficients = [&] {
                 int16_t *coef[3] = {nullptr, nullptr, nullptr};
-                for(unsigned c = 0; c < ncomp; c++) {
-                        coef[c] = reinterpret_cast<int16_t *>(at(coef_at[c]));
-                        g.coef[c] = coef[c];
-                }
+                for(unsigned c = 0; c < ncomp; c++) { g.coef[c] = coef[c] = block.at<int16_t>(coef_at[c]); }
                 fill(stream, coef);
         };
         // from the coefficients to the bit offsets
         const auto lengths = [&] {
-                hipLaunchKernelGGL(k_entropy_lengths, dim3(coding_grid), dim3(256), 0, stream, g, *codes, reinterpret_cast<unsigned *>(at(len_at)));
-                queue_scan(stream, reinterpret_cast<unsigned *>(at(len_at)), nslots, reinterpret_cast<unsigned long long *>(at(sums_at)),
-                           reinterpret_cast<unsigned long long *>(at(off_at)));
+                hipLaunchKernelGGL(k_entropy_lengths, dim3(coding_grid), dim3(256), 0, stream, g, *codes, block.at<unsigned>(len_at));
+                queue_scan(stream, block.at<unsigned>(len_at), nslots, block.at<ull>(sums_at), block.at<ull>(off_at));
         };
-        bool moved = false;
-        if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }     // (a file is rarely an eighth of its coefficients)
-        coefficients();
+        if(const int rc = block.grow(fixed + coef_bytes / 4); rc != J2P_OK) { return rc; }     // (a file is rarely an eighth of its coefficients)
+        block.stage(coefficients);
         if(stats) { memset(stats, 0, sizeof(*stats)); }
         if(counting) {
                 unsigned long long hist[kHistogramEntries];
-                HIP_TRY(hipMemsetAsync(at(hist_at), 0, sizeof(hist), stream));
-                hipLaunchKernelGGL(k_entropy_histogram, dim3(coding_grid), dim3(256), 0, stream, g, reinterpret_cast<unsigned long long *>(at(hist_at)));
+                HIP_TRY(hipMemsetAsync(block.at(hist_at), 0, sizeof(hist), stream));
+                hipLaunchKernelGGL(k_entropy_histogram, dim3(coding_grid), dim3(256), 0, stream, g, block.at<ull>(hist_at));
                 HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(hist, at(hist_at), sizeof(hist), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(hist, block.at(hist_at), sizeof(hist), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipStreamSynchronize(stream));
                 FileTables made;
                 if(const int rc = tables_from_counts(hist, ncomp, made, stats); optimise && rc != J2P_OK) { return rc; }
@@ -315,56 +379,28 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                         codes = &own_codes;
                 }
         }
-        lengths();
-        unsigned long long bits = 0;
-        HIP_TRY(hipMemcpyAsync(&bits, at(sums_at) + (size_t)slot_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
+        block.stage(lengths);
+        ull bits = 0;
+        HIP_TRY(hipMemcpyAsync(&bits, block.at<ull>(sums_at) + slot_tiles, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        const size_t nbytes = (size_t)((bits + 7) / 8), stage_words = (size_t)((bits + 31) / 32) + 1;
-        const unsigned nchunks = (unsigned)((nbytes + kStuffChunk - 1) / kStuffChunk), chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
-        const size_t stage_at = part(stage_words * 4), count_at = part((size_t)nchunks * 4), ffoff_at = part((size_t)nchunks * 8);
-        const size_t ffsums_at = part(((size_t)chunk_tiles + 1) * 8), out_at = part.total;
-        // from the bit offsets to the stream and where its FF bytes are
-        const auto pack = [&] {
-                (void)hipMemsetAsync(at(stage_at), 0, stage_words * 4, stream);
-                hipLaunchKernelGGL(k_entropy_pack, dim3(coding_grid), dim3(256), 0, stream, g, *codes,
-                                   reinterpret_cast<const unsigned long long *>(at(off_at)), reinterpret_cast<unsigned *>(at(stage_at)));
-                hipLaunchKernelGGL(k_stuff_count, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes,
-                                   nchunks, reinterpret_cast<unsigned *>(at(count_at)));
-                queue_scan(stream, reinterpret_cast<unsigned *>(at(count_at)), nchunks, reinterpret_cast<unsigned long long *>(at(ffsums_at)),
-                           reinterpret_cast<unsigned long long *>(at(ffoff_at)));
-        };
-        if(const int rc = take(out_at + nbytes + nbytes / 16 + 256, &moved); rc != J2P_OK) { return rc; }
-        if(moved) {
-                coefficients();
-                lengths();
-        }
-        pack();
-        unsigned long long ffs = 0;
-        HIP_TRY(hipMemcpyAsync(&ffs, at(ffsums_at) + (size_t)chunk_tiles * 8, 8, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if(stats) {
-                stats->scan_bits = bits;
-                stats->stuffed_bytes = ffs;
-        }
-        uint8_t header[kJpegHeaderMax];
-        const size_t header_bytes = jpeg_header(spec, ncomp, *tables, header), data_bytes = nbytes + (size_t)ffs;
-        *size = header_bytes + data_bytes + 2;
-        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
-        if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
-        if(moved) {
-                coefficients();
-                lengths();
-                pack();
-        }
-        hipLaunchKernelGGL(k_stuff_copy, dim3((nchunks + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const unsigned *>(at(stage_at)), nbytes, nchunks,
-                           reinterpret_cast<const unsigned long long *>(at(ffoff_at)), reinterpret_cast<uint8_t *>(at(out_at)));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out_host + header_bytes, at(out_at), data_bytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        memcpy(out_host, header, header_bytes);
-        out_host[header_bytes + data_bytes] = 0xff;
-        out_host[header_bytes + data_bytes + 1] = 0xd9;
-        return J2P_OK;
+        return stuffed_streams(
+                stream, block, part, 1, &bits,
+                [&](unsigned, unsigned *stage) {
+                        hipLaunchKernelGGL(k_entropy_pack, dim3(coding_grid), dim3(256), 0, stream, g, *codes,
+                                           static_cast<const ull *>(block.at<ull>(off_at)), stage);
+                },
+                [&](const Stuffed &done, uint8_t **to) {
+                        if(stats) { stats->scan_bits = bits, stats->stuffed_bytes = done.ffs[1]; }
+                        uint8_t header[kJpegHeaderMax];
+                        const size_t header_bytes = jpeg_header(spec, ncomp, *tables, header);
+                        *size = header_bytes + done.bytes(0) + 2;
+                        if(capacity < *size || !out_host) {
+                                return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0);
+                        }
+                        memcpy(out_host, header, header_bytes);
+                        to[0] = out_host + header_bytes;
+                        return (int)J2P_OK;
+                });
 }
 
 // ---- the progressive file: k_prog_* (j2p_progressive_kernels.hip.h), k_scan_*, k_stuff_* ----
@@ -396,20 +432,8 @@ constexpr size_t kProgScanHeaderMax = 576;
 size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned table[2], const j2p_huff_table made[2], uint8_t *out)
 {
         uint8_t *p = out;
-        const auto segment = [&](uint8_t marker, size_t payload) {
-                *p++ = 0xff;
-                *p++ = marker;
-                *p++ = (uint8_t)((payload + 2) >> 8);
-                *p++ = (uint8_t)(payload + 2);
-        };
-        for(unsigned k = 0; k < ntables; k++) {
-                segment(0xc4, 1 + 16 + made[k].nvals);
-                *p++ = (uint8_t)table[k];
-                memcpy(p, made[k].bits, 16);
-                memcpy(p + 16, made[k].vals, made[k].nvals);
-                p += 16 + made[k].nvals;
-        }
-        segment(0xda, 1 + 2 * s.ncomp + 3);
+        for(unsigned k = 0; k < ntables; k++) { dht_segment(p, table[k], made[k]); }
+        segment(p, 0xda, 1 + 2 * s.ncomp + 3);
         *p++ = (uint8_t)s.ncomp;
         for(unsigned i = 0; i < s.ncomp; i++) {
                 const unsigned slot = s.comp[i] ? 1u : 0u;
@@ -432,8 +456,9 @@ size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned ta
 //   [out: every scan's stuffed bytes, one behind the other]                                          once the FFs are
 // ONE exclusive sum places the items of all scans (a scan's stream starts at its first item's offset) and ONE the FF counts of all
 // scans' chunks, so three reads come back as arrays — all counts, all scans' bits, all scans' FFs — with a wait each, as in the
-// optimised call, and the file's bytes with a fourth.  The block is asked for three times under the rule of j2p_encode_scan: when
-// it moved, what had been computed on the device is computed again; the counts and tables live on the host by then.
+// optimised call, and the file's bytes with a fourth.  The block is asked for three times as j2p_encode_scan's is, with the same
+// three stages (j2p_coder_block.h): the coefficients — with them the flags and the EOB runs — every scan's lengths, and in
+// stuffed_streams every scan's stream.  The walk that counts is no stage: the counts and tables live on the host by then.
 int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                            const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
                            j2p_progressive_stats *stats)
@@ -467,16 +492,7 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         const size_t runs_bytes = part.total - runs_at;
         const size_t hist_bytes = (size_t)nscans * (kProgHistogram + 1) * 8;
         const size_t hist_at = part(hist_bytes), fixed = part.total;     // (the flush counters behind the counts)
-        char *base = nullptr;
-        const auto take = [&](size_t bytes, bool *moved) {
-                void *p = nullptr;
-                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
-                base = static_cast<char *>(p);
-                return (int)J2P_OK;
-        };
-        const auto u8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(base + at); };
-        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
-        const auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long *>(base + at); };
+        j2p_coder_block block(memory);
         const auto grid = [](unsigned n) { return dim3((n + 255) / 256); };
         static const ProgCodes no_codes = {};
         std::vector<ProgCodes> codes(nscans, no_codes);
@@ -484,44 +500,40 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         // the coefficients into the block, and what of every AC scan needs no table: the blocks' flags and the EOB runs
         const auto coefficients = [&] {
                 int16_t *into[3] = {nullptr, nullptr, nullptr};
-                for(unsigned c = 0; c < ncomp; c++) {
-                        into[c] = reinterpret_cast<int16_t *>(base + coef_at[c]);
-                        coef[c] = g.coef[c] = into[c];
-                }
+                for(unsigned c = 0; c < ncomp; c++) { coef[c] = g.coef[c] = into[c] = block.at<int16_t>(coef_at[c]); }
                 fill(stream, into);
-                (void)hipMemsetAsync(base + hist_at, 0, hist_bytes, stream);
-                (void)hipMemsetAsync(base + runs_at, 0, runs_bytes, stream);
+                (void)hipMemsetAsync(block.at(hist_at), 0, hist_bytes, stream);
+                (void)hipMemsetAsync(block.at(runs_at), 0, runs_bytes, stream);
                 for(unsigned s = 0; s < nscans; s++) {
                         if(scan[s].ss == 0) { continue; }
                         const unsigned per_workgroup = 4 * kEntropyIters;
                         hipLaunchKernelGGL(k_prog_classify, dim3((scan[s].n + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream,
-                                           coef[script[s].comp[0]], scan[s], u8(flags_at[s]));
-                        hipLaunchKernelGGL(k_prog_runs, grid(scan[s].n), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(flags_at[s])), scan[s],
-                                           u32(run_at[s]), u64(hist_at) + (size_t)nscans * kProgHistogram + s);
+                                           coef[script[s].comp[0]], scan[s], block.at<uint8_t>(flags_at[s]));
+                        hipLaunchKernelGGL(k_prog_runs, grid(scan[s].n), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])),
+                                           scan[s], block.at<unsigned>(run_at[s]), block.at<ull>(hist_at) + (size_t)nscans * kProgHistogram + s);
                 }
         };
         // one scan's walk in one of its three modes
         const auto walk = [&](auto mode, unsigned s, unsigned *stage) {
                 constexpr int kMode = decltype(mode)::value;
-                unsigned long long *const hist = u64(hist_at) + (size_t)s * kProgHistogram;
-                unsigned *const len = u32(len_at) + first[s];
-                const unsigned long long *const off = u64(off_at) + first[s];
+                ull *const hist = block.at<ull>(hist_at) + (size_t)s * kProgHistogram;
+                unsigned *const len = block.at<unsigned>(len_at) + first[s];
+                const ull *const off = block.at<ull>(off_at) + first[s];
                 if(scan[s].ss == 0) {
                         if(kMode == kProgCount && scan[s].refine) { return; }
                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_dc<kMode>), grid(scan[s].n), dim3(256), 0, stream, g, scan[s], codes[s], hist, len, off, stage);
                 } else {
                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_ac<kMode>), grid(scan[s].n), dim3(256), 0, stream, coef[script[s].comp[0]], scan[s],
-                                           static_cast<const uint8_t *>(u8(flags_at[s])), static_cast<const unsigned *>(u32(run_at[s])), codes[s], hist, len, off,
-                                           stage);
+                                           static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])), static_cast<const unsigned *>(block.at<unsigned>(run_at[s])),
+                                           codes[s], hist, len, off, stage);
                 }
         };
         const auto lengths = [&] {
                 for(unsigned s = 0; s < nscans; s++) { walk(std::integral_constant<int, kProgLength>(), s, nullptr); }
-                queue_scan(stream, u32(len_at), (unsigned)nitems, u64(sums_at), u64(off_at));
+                queue_scan(stream, block.at<unsigned>(len_at), (unsigned)nitems, block.at<ull>(sums_at), block.at<ull>(off_at));
         };
-        bool moved = false;
-        if(const int rc = take(fixed + coef_bytes / 4, &moved); rc != J2P_OK) { return rc; }
-        coefficients();
+        if(const int rc = block.grow(fixed + coef_bytes / 4); rc != J2P_OK) { return rc; }
+        block.stage(coefficients);
         for(unsigned s = 0; s < nscans; s++) { walk(std::integral_constant<int, kProgCount>(), s, nullptr); }
         HIP_TRY(hipGetLastError());
         // wait 1: every scan's counts
@@ -529,7 +541,7 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         try {
                 hist.resize(hist_bytes / 8);
         } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
-        HIP_TRY(hipMemcpyAsync(hist.data(), base + hist_at, hist_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(hist.data(), block.at(hist_at), hist_bytes, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if(stats) {
                 memset(stats, 0, sizeof(*stats));
@@ -555,12 +567,7 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                         for(unsigned i = 0; i < 256; i++) { count[i] = hist[(size_t)s * kProgHistogram + k * 256 + i]; }
                         if(stats) { memcpy(stats->scan[s].counts[k], count, sizeof(count)); }
                         if(refused != J2P_OK) { continue; }
-                        const int rc = j2p_huff_build(count, &made[s][k]);
-                        if(rc == J2P_HUFF_COUNT) {
-                                refused = j2p_fail(J2P_ENOTSUP, "jpeg: a symbol is coded more than %llu times: no optimised table for it", J2P_HUFF_COUNT_MAX);
-                        } else if(rc != J2P_HUFF_OK) {
-                                refused = j2p_fail(J2P_ENOTSUP, "jpeg: an optimised code would be longer than %d bits before limiting", J2P_HUFF_TREE_MAX);
-                        }
+                        refused = build_table(count, &made[s][k]);
                         // a DC category above 11, an AC size above 10: the shifted magnitude needs more bits than the file's precision has
                         for(unsigned i = 0; i < made[s][k].nvals && refused == J2P_OK; i++) {
                                 const unsigned v = made[s][k].vals[i];
@@ -571,95 +578,44 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         }
         if(refused != J2P_OK) { return refused; }
         // wait 2: every scan's bits
-        lengths();
-        unsigned long long begins[J2P_PROGRESSIVE_SCANS + 1] = {0};
-        const auto read_bits = [&]() -> int {
-                for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&begins[s], u64(off_at) + first[s], 8, hipMemcpyDeviceToHost, stream)); }
-                HIP_TRY(hipMemcpyAsync(&begins[nscans], u64(sums_at) + item_tiles, 8, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                return J2P_OK;
-        };
-        if(const int rc = read_bits(); rc != J2P_OK) { return rc; }
-        size_t nbytes[J2P_PROGRESSIVE_SCANS], stage_word[J2P_PROGRESSIVE_SCANS + 1] = {0}, chunk[J2P_PROGRESSIVE_SCANS + 1] = {0};
-        size_t byte[J2P_PROGRESSIVE_SCANS + 1] = {0};
-        for(unsigned s = 0; s < nscans; s++) {
-                const unsigned long long bits = begins[s + 1] - begins[s];
-                if(stats) { stats->scan[s].bits = bits; }
-                nbytes[s] = (size_t)((bits + 7) / 8);
-                stage_word[s + 1] = stage_word[s] + (size_t)((bits + 31) / 32) + 1;
-                chunk[s + 1] = chunk[s] + (nbytes[s] + kStuffChunk - 1) / kStuffChunk;
-                byte[s + 1] = byte[s] + nbytes[s];
-        }
-        if(chunk[nscans] > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "jpeg: %zu bytes of scan data are too many", byte[nscans]); }
-        const unsigned nchunks = (unsigned)chunk[nscans], chunk_tiles = (nchunks + kScanTile - 1) / kScanTile;
-        const size_t stage_at = part(stage_word[nscans] * 4), count_at = part((size_t)nchunks * 4), ffoff_at = part((size_t)nchunks * 8);
-        const size_t ffsums_at = part(((size_t)chunk_tiles + 1) * 8), out_at = part.total;
-        // from the bit offsets to every scan's stream and where its FF bytes are
-        const auto pack = [&] {
-                (void)hipMemsetAsync(base + stage_at, 0, stage_word[nscans] * 4, stream);
-                for(unsigned s = 0; s < nscans; s++) {
-                        unsigned *const stage = u32(stage_at) + stage_word[s];
-                        const unsigned n = (unsigned)(chunk[s + 1] - chunk[s]);
-                        walk(std::integral_constant<int, kProgPack>(), s, stage);
-                        hipLaunchKernelGGL(k_stuff_count, dim3((n + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(stage), nbytes[s], n,
-                                           u32(count_at) + chunk[s]);
-                }
-                queue_scan(stream, u32(count_at), nchunks, u64(ffsums_at), u64(ffoff_at));
-        };
-        if(const int rc = take(out_at + byte[nscans] + byte[nscans] / 16 + 256, &moved); rc != J2P_OK) { return rc; }
-        if(moved) {
-                coefficients();
-                lengths();
-        }
-        pack();
-        // wait 3: every scan's FF bytes
-        unsigned long long ffs[J2P_PROGRESSIVE_SCANS + 1] = {0};
-        for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&ffs[s], u64(ffoff_at) + chunk[s], 8, hipMemcpyDeviceToHost, stream)); }
-        HIP_TRY(hipMemcpyAsync(&ffs[nscans], u64(ffsums_at) + chunk_tiles, 8, hipMemcpyDeviceToHost, stream));
+        block.stage(lengths);
+        ull begins[J2P_PROGRESSIVE_SCANS + 1] = {0}, bits[J2P_PROGRESSIVE_SCANS];
+        for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&begins[s], block.at<ull>(off_at) + first[s], 8, hipMemcpyDeviceToHost, stream)); }
+        HIP_TRY(hipMemcpyAsync(&begins[nscans], block.at<ull>(sums_at) + item_tiles, 8, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        // the headers, and with them the file's size
-        uint8_t frame[256];
-        std::vector<uint8_t> heads;
-        size_t head_at[J2P_PROGRESSIVE_SCANS + 1] = {0};
-        try {
-                heads.resize((size_t)nscans * kProgScanHeaderMax);
-        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
-        const size_t frame_bytes = jpeg_frame(spec, ncomp, 0xc2, frame);
         for(unsigned s = 0; s < nscans; s++) {
-                if(stats) { stats->scan[s].stuffed_bytes = ffs[s + 1] - ffs[s]; }
-                head_at[s + 1] = head_at[s] + prog_scan_header(script[s], ntables[s], table[s], made[s], heads.data() + head_at[s]);
+                bits[s] = begins[s + 1] - begins[s];
+                if(stats) { stats->scan[s].bits = bits[s]; }
         }
-        const size_t data_bytes = byte[nscans] + (size_t)ffs[nscans];
-        *size = frame_bytes + head_at[nscans] + data_bytes + 2;
-        if(capacity < *size || !out_host) { return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0); }
-        if(const int rc = take(out_at + data_bytes, &moved); rc != J2P_OK) { return rc; }
-        if(moved) {
-                coefficients();
-                lengths();
-                pack();
-        }
-        // wait 4: the scans' bytes to their places in the file, the headers between them
-        uint8_t *p = out_host + frame_bytes;
-        for(unsigned s = 0; s < nscans; s++) {
-                const unsigned n = (unsigned)(chunk[s + 1] - chunk[s]);
-                const size_t stuffed = nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]);
-                hipLaunchKernelGGL(k_stuff_copy, dim3((n + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(u32(stage_at) + stage_word[s]), nbytes[s], n,
-                                   static_cast<const unsigned long long *>(u64(ffoff_at) + chunk[s]), u8(out_at) + byte[s]);
-                p += head_at[s + 1] - head_at[s];
-                HIP_TRY(hipMemcpyAsync(p, base + out_at + byte[s] + (size_t)ffs[s], stuffed, hipMemcpyDeviceToHost, stream));
-                p += stuffed;
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(stream));
-        memcpy(out_host, frame, frame_bytes);
-        p = out_host + frame_bytes;
-        for(unsigned s = 0; s < nscans; s++) {
-                memcpy(p, heads.data() + head_at[s], head_at[s + 1] - head_at[s]);
-                p += head_at[s + 1] - head_at[s] + nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]);
-        }
-        p[0] = 0xff;
-        p[1] = 0xd9;
-        return J2P_OK;
+        // waits 3 and 4: every scan's FF bytes; the scans' bytes to their places in the file, the headers between them
+        return stuffed_streams(
+                stream, block, part, nscans, bits, [&](unsigned s, unsigned *stage) { walk(std::integral_constant<int, kProgPack>(), s, stage); },
+                [&](const Stuffed &done, uint8_t **to) {
+                        uint8_t frame[256];
+                        std::vector<uint8_t> heads;
+                        size_t head_at[J2P_PROGRESSIVE_SCANS + 1] = {0};
+                        const size_t frame_bytes = jpeg_frame(spec, ncomp, 0xc2, frame);
+                        try {
+                                heads.resize((size_t)nscans * kProgScanHeaderMax);
+                        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                        for(unsigned s = 0; s < nscans; s++) {
+                                if(stats) { stats->scan[s].stuffed_bytes = done.ffs[s + 1] - done.ffs[s]; }
+                                head_at[s + 1] = head_at[s] + prog_scan_header(script[s], ntables[s], table[s], made[s], heads.data() + head_at[s]);
+                        }
+                        *size = frame_bytes + head_at[nscans] + 2;
+                        for(unsigned s = 0; s < nscans; s++) { *size += done.bytes(s); }
+                        if(capacity < *size || !out_host) {
+                                return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0);
+                        }
+                        memcpy(out_host, frame, frame_bytes);
+                        uint8_t *p = out_host + frame_bytes;
+                        for(unsigned s = 0; s < nscans; s++) {
+                                memcpy(p, heads.data() + head_at[s], head_at[s + 1] - head_at[s]);
+                                to[s] = p + head_at[s + 1] - head_at[s];
+                                p = to[s] + done.bytes(s);
+                        }
+                        return (int)J2P_OK;
+                });
 }
 
 // the device of a j2p_entropy_* call
@@ -671,8 +627,45 @@ static int check_device(int device)
         return J2P_OK;
 }
 
-// a coder (j2p_encode_scan, j2p_encode_progressive) on the caller's coefficients in host memory: the argument checks, a stream, one
-// pooled block that grows as the solvers' scratch does
+// What a stand-alone call (j2p_entropy_encode*, j2p_png_encode) gives its coder: a stream of its own and, as `memory` (std::ref), one
+// pooled block that grows as the solvers' scratch does — a request beyond it waits for the stream (what is queued may still read
+// the old block), gives the block back and takes a larger one.  The calling thread's device is `device`.
+struct PooledCall {
+        const int device;
+        hipStream_t stream = nullptr;
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        explicit PooledCall(int device) : device(device) {}
+        PooledCall(const PooledCall &) = delete;
+        PooledCall &operator=(const PooledCall &) = delete;
+        int open()
+        {
+                HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+                return J2P_OK;
+        }
+        int operator()(size_t bytes, void **p, bool *moved)
+        {
+                *moved = block_bytes < bytes;
+                if(*moved) {
+                        HIP_TRY(hipStreamSynchronize(stream));
+                        j2p_pool_give(device, block, block_bytes);
+                        block = nullptr;
+                        block_bytes = 0;
+                        HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
+                }
+                *p = block;
+                return J2P_OK;
+        }
+        ~PooledCall()
+        {
+                if(!stream) { return; }
+                (void)hipStreamSynchronize(stream);
+                j2p_pool_give(device, block, block_bytes);
+                (void)hipStreamDestroy(stream);
+        }
+};
+
+// a coder (j2p_encode_scan, j2p_encode_progressive) on the caller's coefficients in host memory: the argument checks and a PooledCall
 using HostCoder = std::function<int(hipStream_t, const std::function<int(size_t, void **, bool *)> &, const std::function<void(hipStream_t, int16_t *const[3])> &)>;
 static int encode_host_coefficients(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, const size_t *size,
                                     const HostCoder &coder)
@@ -693,31 +686,11 @@ static int encode_host_coefficients(int device, const j2p_jpeg *spec, const int1
         }
         if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
         DeviceGuard guard(device);
-        hipStream_t stream = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        void *block = nullptr;
-        size_t block_bytes = 0;
-        const int rc = coder(
-                stream,
-                [&](size_t bytes, void **p, bool *moved) {
-                        *moved = block_bytes < bytes;
-                        if(block_bytes < bytes) {
-                                HIP_TRY(hipStreamSynchronize(stream));
-                                j2p_pool_give(device, block, block_bytes);
-                                block = nullptr;
-                                block_bytes = 0;
-                                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
-                        }
-                        *p = block;
-                        return (int)J2P_OK;
-                },
-                [&](hipStream_t st, int16_t *const coef[3]) {
-                        for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
-                });
-        (void)hipStreamSynchronize(stream);
-        j2p_pool_give(device, block, block_bytes);
-        (void)hipStreamDestroy(stream);
-        return rc;
+        PooledCall call(device);
+        if(const int rc = call.open(); rc != J2P_OK) { return rc; }
+        return coder(call.stream, std::ref(call), [&](hipStream_t st, int16_t *const coef[3]) {
+                for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
+        });
 }
 
 extern "C" {
@@ -1062,8 +1035,9 @@ constexpr size_t kPngHead = 8 + 25, kPngTail = 12;       // the signature and IH
 //   [stage: the zlib stream, ceil(bytes / 4) + 1 words][out: the IDAT chunks]                                known once the counts are
 // The counts come down once (a wait), the tables are made on the host (j2p_deflate.h), and every size follows from them: the
 // file's own is known — and J2P_ESPACE answered — before anything is packed.  The block is asked for twice, the first time with
-// a guess for the second part; when it moved, the samples and the filtered rows are made again (the counts live on the host by
-// then).  A second image of the same size or smaller finds the block large enough at once.
+// a guess for the second part (j2p_coder_block.h); its one stage makes the samples and the filtered rows, again when the block
+// moved (the counts live on the host by then, and the blocks' records go up after the second request).  A second image of the
+// same size or smaller finds the block large enough at once.
 int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, const std::function<int(size_t, void **, bool *)> &memory,
                   const std::function<void(hipStream_t, uint8_t *)> &fill, uint8_t *out_host, size_t capacity, size_t *size, j2p_png_stats *stats)
 {
@@ -1079,27 +1053,18 @@ int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, co
         const size_t samples_at = part((size_t)spec.height * rb), stream_at = part(total), chosen_at = part(5 * 4);
         const size_t counts_at = part(nblocks * J2P_DEFLATE_COUNTS * 4), blocks_at = part(nblocks * sizeof(PngBlock));
         const size_t fixed = part.total;
-        char *base = nullptr;
-        const auto take = [&](size_t bytes, bool *moved) {
-                void *p = nullptr;
-                if(const int rc = memory(bytes, &p, moved); rc != J2P_OK) { return rc; }
-                base = static_cast<char *>(p);
-                return (int)J2P_OK;
-        };
-        const auto u8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(base + at); };
-        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        j2p_coder_block block(memory);
         // from the samples to the filtered rows
         const auto filter = [&] {
-                fill(stream, u8(samples_at));
-                (void)hipMemsetAsync(base + chosen_at, 0, 5 * 4, stream);
-                hipLaunchKernelGGL(k_png_filter, dim3((spec.height + 3) / 4), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(samples_at)), rb, spec.height,
-                                   bpp, spec.filter < 0 ? 5u : (unsigned)spec.filter, u8(stream_at), u32(chosen_at));
+                fill(stream, block.at<uint8_t>(samples_at));
+                (void)hipMemsetAsync(block.at(chosen_at), 0, 5 * 4, stream);
+                hipLaunchKernelGGL(k_png_filter, dim3((spec.height + 3) / 4), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(samples_at)), rb, spec.height,
+                                   bpp, spec.filter < 0 ? 5u : (unsigned)spec.filter, block.at<uint8_t>(stream_at), block.at<unsigned>(chosen_at));
         };
-        bool moved = false;
-        if(const int rc = take(fixed + total / 2 + total / 4 + 4096, &moved); rc != J2P_OK) { return rc; }      // (a photograph's file: half to two thirds of its samples)
-        filter();
-        hipLaunchKernelGGL(k_png_count, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stream_at)), total, block_bytes,
-                           u32(counts_at));
+        if(const int rc = block.grow(fixed + total / 2 + total / 4 + 4096); rc != J2P_OK) { return rc; }      // (a photograph's file: half to two thirds of its samples)
+        block.stage(filter);
+        hipLaunchKernelGGL(k_png_count, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(stream_at)), total, block_bytes,
+                           block.at<unsigned>(counts_at));
         HIP_TRY(hipGetLastError());
         std::vector<unsigned> counts;
         std::vector<PngBlock> blocks;
@@ -1108,8 +1073,8 @@ int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, co
                 blocks.resize(nblocks);
         } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
         unsigned chosen[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(counts.data(), base + counts_at, counts.size() * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(chosen, base + chosen_at, sizeof(chosen), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(counts.data(), block.at(counts_at), counts.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(chosen, block.at(chosen_at), sizeof(chosen), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         // the tables, the blocks' places and the checksum
         j2p_png_stats st;
@@ -1148,17 +1113,16 @@ int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, co
         if(nchunks > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "png: %llu IDAT chunks of %u bytes are too many", nchunks, idat_bytes); }
         const size_t stage_words = (size_t)((zlen + 3) / 4) + 1;
         const size_t stage_at = part(stage_words * 4), out_at = part(data_bytes);
-        if(const int rc = take(part.total, &moved); rc != J2P_OK) { return rc; }
-        if(moved) { filter(); }
-        HIP_TRY(hipMemcpyAsync(base + blocks_at, blocks.data(), nblocks * sizeof(PngBlock), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(base + stage_at, 0, stage_words * 4, stream));
-        hipLaunchKernelGGL(k_png_pack, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stream_at)), total, block_bytes,
-                           reinterpret_cast<const PngBlock *>(base + blocks_at), st.adler, u32(stage_at));
-        hipLaunchKernelGGL(k_png_chunks, dim3((unsigned)((zlen + 1023) / 1024)), dim3(256), 0, stream, static_cast<const uint8_t *>(u8(stage_at)), (size_t)zlen,
-                           idat_bytes, u8(out_at));
-        hipLaunchKernelGGL(k_png_crc, dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, stream, u8(out_at), (size_t)zlen, idat_bytes, (unsigned)nchunks);
+        if(const int rc = block.grow(part.total); rc != J2P_OK) { return rc; }
+        HIP_TRY(hipMemcpyAsync(block.at(blocks_at), blocks.data(), nblocks * sizeof(PngBlock), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(block.at(stage_at), 0, stage_words * 4, stream));
+        hipLaunchKernelGGL(k_png_pack, dim3((unsigned)nblocks), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(stream_at)), total, block_bytes,
+                           reinterpret_cast<const PngBlock *>(block.at(blocks_at)), st.adler, block.at<unsigned>(stage_at));
+        hipLaunchKernelGGL(k_png_chunks, dim3((unsigned)((zlen + 1023) / 1024)), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(stage_at)), (size_t)zlen,
+                           idat_bytes, block.at<uint8_t>(out_at));
+        hipLaunchKernelGGL(k_png_crc, dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, stream, block.at<uint8_t>(out_at), (size_t)zlen, idat_bytes, (unsigned)nchunks);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out_host + kPngHead, base + out_at, data_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(out_host + kPngHead, block.at(out_at), data_bytes, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         static const uint8_t signature[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
         memcpy(out_host, signature, 8);
@@ -1184,32 +1148,13 @@ int j2p_png_encode(int device, const j2p_png *spec, const uint8_t *samples_host,
         if(const char *why = j2p_png_error(spec, channels)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
         DeviceGuard guard(device);
-        hipStream_t stream = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        // one pooled block that grows as the solvers' scratch does
-        void *block = nullptr;
-        size_t block_bytes = 0;
+        PooledCall call(device);
+        if(const int rc = call.open(); rc != J2P_OK) { return rc; }
         const size_t sample_bytes = (size_t)spec->width * spec->height * channels * (spec->bits / 8);
-        const int rc = j2p_png_write(
-                stream, *spec, channels,
-                [&](size_t bytes, void **p, bool *moved) {
-                        *moved = block_bytes < bytes;
-                        if(block_bytes < bytes) {
-                                HIP_TRY(hipStreamSynchronize(stream));
-                                j2p_pool_give(device, block, block_bytes);
-                                block = nullptr;
-                                block_bytes = 0;
-                                HIP_TRY(j2p_pool_take(device, bytes, &block, &block_bytes));
-                        }
-                        *p = block;
-                        return (int)J2P_OK;
-                },
+        return j2p_png_write(
+                call.stream, *spec, channels, std::ref(call),
                 [&](hipStream_t st, uint8_t *samples) { (void)hipMemcpyAsync(samples, samples_host, sample_bytes, hipMemcpyHostToDevice, st); }, out_host, capacity,
                 size, stats);
-        (void)hipStreamSynchronize(stream);
-        j2p_pool_give(device, block, block_bytes);
-        (void)hipStreamDestroy(stream);
-        return rc;
 }
 
 }  // extern "C"

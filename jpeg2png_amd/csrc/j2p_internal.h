@@ -217,7 +217,7 @@ j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp);
 // waited for on return.  memory(bytes, &p, &moved): one block of device memory of at least that size which stays the same block
 // while it is large enough and is ANOTHER block (moved), contents lost, once it has to grow (j2p_solver_scratch);
 // fill(stream, coef): queues what leaves component c's coefficients (j2p_scan_grids_of) at coef[c].  Both may be called up to
-// three times.  J2P_ESPACE: *size is what the file needs.  flags: J2P_JPEG_* bits, checked by the caller.  With J2P_JPEG_OPTIMIZE,
+// three times, by the coder's j2p_coder_block (j2p_coder_block.h).  J2P_ESPACE: *size is what the file needs.  flags: J2P_JPEG_* bits, checked by the caller.  With J2P_JPEG_OPTIMIZE,
 // or with stats (may be NULL), the symbols are counted on the device and the stream is waited for once more on the way.
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                     const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,

@@ -875,6 +875,15 @@ int j2p_planes_rows_to_coefficients_sub(const j2p_plane_ref *plane, unsigned sub
         return quantise_rows(plane, false, sub_w, sub_h, blocks_w, block_row_begin, block_row_end, quant_table, out_host);
 }
 
+// a file coder's `memory` (j2p_internal.h) that is owner's scratch: another block, its contents lost, once a request is beyond it
+static std::function<int(size_t, void **, bool *)> scratch_memory(j2p_solver *owner)
+{
+        return [owner](size_t bytes, void **p, bool *moved) {
+                *moved = j2p_solver_scratch_bytes(owner) < bytes;
+                return j2p_solver_scratch(owner, bytes, p);
+        };
+}
+
 // the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_scan), which is the first solver's scratch
 // (progressive: j2p_encode_progressive codes them, and flags is 0)
 static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
@@ -901,11 +910,7 @@ static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j
                 if(planes[c].solver != planes[0].solver) { HIP_TRY(hipStreamSynchronize(q[c].s.stream)); }
         }
         if(const int rc = upright_queue(up, stream); rc != J2P_OK) { return rc; }
-        j2p_solver *const owner = planes[0].solver;
-        const auto memory = [&](size_t bytes, void **p, bool *moved) {
-                *moved = j2p_solver_scratch_bytes(owner) < bytes;
-                return j2p_solver_scratch(owner, bytes, p);
-        };
+        const auto memory = scratch_memory(planes[0].solver);
         const auto fill = [&](hipStream_t st, int16_t *const coef[3]) {
                 for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
         };
@@ -945,14 +950,9 @@ int j2p_planes_to_png(const j2p_plane_ref planes[], unsigned nplane, const j2p_p
         }
         DeviceGuard guard(s0.device);
         if(const int rc = upright_queue(up, s0.stream); rc != J2P_OK) { return rc; }
-        j2p_solver *const owner = planes[0].solver;
         const unsigned w = spec->width, h = spec->height, bits = spec->bits;
         return j2p_png_write(
-                s0.stream, *spec, nplane,
-                [&](size_t bytes, void **p, bool *moved) {
-                        *moved = j2p_solver_scratch_bytes(owner) < bytes;
-                        return j2p_solver_scratch(owner, bytes, p);
-                },
+                s0.stream, *spec, nplane, scratch_memory(planes[0].solver),
                 [&](hipStream_t st, uint8_t *samples) {
                         hipLaunchKernelGGL(nplane == 3 ? k_to_samples<3> : k_to_samples<1>, dim3(2048), dim3(256), 0, st, ptr[0], stride[0], ptr[1], stride[1],
                                            ptr[2], stride[2], w, h, bits, samples);

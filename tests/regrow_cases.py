@@ -1,9 +1,10 @@
 """The inputs of tests/test_regrow_gpu.py — images and coefficients whose file is larger than the coders' first guess, so that the one
 device block a coder works in has to grow in the middle of a call — and the coders' requests for that block restated from the sizes
-of the restatements' files (tests/entropy_cases.py, tests/huffman_cases.py, tests/png_cases.py).  Nothing here imports the library:
-tests/test_regrow_cpu.py holds the arithmetic, tests/test_regrow_gpu.py the library's count of the blocks it took against it.
+of the restatements' files (tests/entropy_cases.py, tests/huffman_cases.py, tests/progressive_cases.py, tests/png_cases.py).  Nothing here
+imports the library: tests/test_regrow_cpu.py holds the arithmetic, tests/test_regrow_gpu.py the library's count of the blocks it took
+against it.
 
-The block's layout is the one jpeg2png_amd/csrc/j2p_codec.hip documents above j2p_encode_scan and j2p_png_write: parts aligned to 256
+The block's layout is the one jpeg2png_amd/csrc/j2p_codec.hip documents above j2p_encode_scan, j2p_encode_progressive and j2p_png_write: parts aligned to 256
 bytes; the parts whose size is not known yet are guessed in the earlier requests."""
 import numpy as np
 
@@ -68,6 +69,29 @@ def jpeg_requests(case, nbytes, stuffed, counting=False):
     chunks = -(-nbytes // STUFF_CHUNK)
     out_at = fixed + carve(words * 4, chunks * 4, chunks * 8, (-(-chunks // SCAN_TILE) + 1) * 8)
     return [fixed + carve(*coefficients) // 4, out_at + nbytes + nbytes // 16 + 256, out_at + nbytes + stuffed]
+
+
+def progressive_requests(case, report):
+    """the three sizes j2p_encode_progressive asks its block to have, for a file whose scans `report` describes
+    (progressive_cases.encode_report: per scan its bits before padding and its stuffed FF bytes).  A scan's items are its positions (DC)
+    or its component's blocks (AC); the counts are 512 per scan and a flush counter each"""
+    import progressive_cases as prc
+    ncomp = len(case["coefficients"])
+    grids = ec.grids(case["width"], case["height"], ncomp, case["sub"])
+    nslots = len(ec.scan_order(case["width"], case["height"], ncomp, case["sub"]))
+    scans = prc.SCANS[ncomp]
+    assert len(report) == len(scans)
+    items = [nslots if ss == 0 else grids[comps[0]][0] * grids[comps[0]][1] for comps, ss, _se, _ah, _al in scans]
+    ac = [n for n, (_comps, ss, _se, _ah, _al) in zip(items, scans) if ss]
+    coefficients = [gh * gw * 128 for gh, gw in grids]
+    nitems = sum(items)
+    fixed = carve(*coefficients, nitems * 4, nitems * 8, (-(-nitems // SCAN_TILE) + 1) * 8, *ac, *[4 * n for n in ac], len(scans) * 513 * 8)
+    nbytes = [-(-r["bits"] // 8) for r in report]
+    words = sum(-(-r["bits"] // 32) + 1 for r in report)
+    chunks = sum(-(-n // STUFF_CHUNK) for n in nbytes)
+    out_at = fixed + carve(words * 4, chunks * 4, chunks * 8, (-(-chunks // SCAN_TILE) + 1) * 8)
+    data, stuffed = sum(nbytes), sum(r["stuffed"] for r in report)
+    return [fixed + carve(*coefficients) // 4, out_at + data + data // 16 + 256, out_at + data + stuffed]
 
 
 def noisy_planes(width, height, seed=304, density=0.6):

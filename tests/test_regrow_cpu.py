@@ -36,6 +36,25 @@ def test_a_sparse_image_of_the_same_size_outgrows_the_first_guess_only():
     assert ffs <= nbytes // 16 + 256 and first < second and third <= second and rg.takes([first, second, third]) == 2
 
 
+def test_the_progressive_file_of_the_heavy_blocks_outgrows_both_guesses_and_the_sparse_one_the_first():
+    """the layout above j2p_encode_progressive: six scans of 16 items each; 30464 bytes are known from the spec, 24624 of them the
+    counts"""
+    import progressive_cases as prc
+    case = rg.heavy_case()
+    _file, report = prc.encode_case(case)
+    nbytes, ffs = sum(-(-r["bits"] // 8) for r in report), sum(r["stuffed"] for r in report)
+    assert (nbytes, ffs) == (1392, 376) and ffs > nbytes // 16 + 256 == 343
+    requests = rg.progressive_requests(case, report)
+    assert requests == [30976, 34503, 34536] and rg.takes(requests) == 3
+    assert requests[0] - 16 * 128 // 4 == rg.carve(16 * 128, 96 * 4, 96 * 8, 2 * 8, *[16] * 4, *[64] * 4, 6 * 513 * 8) == 30464
+    case = rg.sparse_case()
+    _file, report = prc.encode_case(case)
+    assert (sum(-(-r["bits"] // 8) for r in report), sum(r["stuffed"] for r in report)) == (48, 0)
+    requests = rg.progressive_requests(case, report)
+    # (the third request is smaller than the second: its guess for the FF bytes was 259)
+    assert requests == [30976, 31795, 31536] and rg.takes(requests) == 2
+
+
 def test_noise_outgrows_the_png_coders_guess_and_zeros_do_not():
     image = rg.noise_image()
     _file, report = pc.encode(image.reshape(48, -1), 48, 48, idat_bytes=16)

@@ -1,9 +1,10 @@
-"""The block that moves in the middle of a call.  Both file coders (j2p_encode_scan, j2p_png_write) ask their `memory` callback for one
-device block several times, the earlier times with a guess for the part whose size is not known yet; when a later request is larger
-the block is ANOTHER one, its contents are gone, and what had been computed is queued again (the three `if(moved)` of
-jpeg2png_amd/csrc/j2p_codec.hip).  Here each of those is reached on purpose, through both callbacks — the pooled block of the
-stand-alone entry points and a solver's scratch, which grows in steps of 256 KiB — and the file is held byte for byte against the
-restatement all the same.
+"""The block that moves in the middle of a call.  The three file coders (j2p_encode_scan, j2p_encode_progressive, j2p_png_write) ask
+their `memory` callback for one device block several times, the earlier times with a guess for the part whose size is not known yet;
+when a later request is larger the block is ANOTHER one, its contents are gone, and the coder's j2p_coder_block
+(jpeg2png_amd/csrc/j2p_coder_block.h) queues again every stage the coder had handed it: coefficients, lengths and streams for the
+JPEG files, the filtered rows for the PNG.  tests/test_coder_block_cpu.py holds that rule by itself; here every later request of
+every coder moves its block on purpose, through both callbacks — the pooled block of the stand-alone entry points and a solver's
+scratch, which grows in steps of 256 KiB — and the file is held byte for byte against the restatement all the same.
 
 That the block moved is seen from j2p_pool_thread_takes(): a call took 1 + moves blocks.  Every test empties the pool first
 (a cached block of another size would be taken in place of a fresh one and change the count) and asserts the count of every call
@@ -44,9 +45,9 @@ def png_call(lib, samples, room, **spec):
 
 @pytest.mark.gpu
 def test_png_encode_whose_stream_outgrows_the_guess(lib):
-    """j2p_png_encode, the second request: `if(moved) { filter(); }` — with the adaptive filter, whose rows per filter type are
-    counted in the block (chosen[], zeroed inside filter()): the second call gets the first call's blocks back from the pool, counts
-    and all, and must report the same rows"""
+    """j2p_png_encode, the second request, which runs the one stage (filter) again — with the adaptive filter, whose rows per filter
+    type are counted in the block (chosen[], zeroed inside filter()): the second call gets the first call's blocks back from the
+    pool, counts and all, and must report the same rows"""
     lib.j2p_pool_trim()
     image = rg.noise_image()
     want, report = pc.encode(image.reshape(48, -1), 48, 48, idat_bytes=16)
@@ -71,9 +72,9 @@ def jpeg_takes(case, file, counting=False):
 
 @pytest.mark.gpu
 def test_entropy_encode_whose_stream_outgrows_both_guesses(lib):
-    """j2p_entropy_encode, the second and the third request: `if(moved) { coefficients(); lengths(); }` and `if(moved) {
-    coefficients(); lengths(); pack(); }` — 32x32 grey blocks of 63 coefficients of 1023: 3280 bytes of stream for a guess of 512,
-    and 1744 FF bytes in them for a guess of 461"""
+    """j2p_entropy_encode, the second and the third request: the coefficients and the lengths are queued again, then those and the
+    stream — 32x32 grey blocks of 63 coefficients of 1023: 3280 bytes of stream for a guess of 512, and 1744 FF bytes in them for
+    a guess of 461"""
     import test_entropy_gpu as teg
     case = rg.heavy_case()
     want = ec.encode(case["coefficients"], 32, 32, case["quant"])
@@ -90,6 +91,30 @@ def test_entropy_encode_whose_stream_outgrows_both_guesses(lib):
     assert jpeg_takes(sparse, want) == 2
     lib.j2p_pool_trim()
     (rc, size, buf), took = counted(lib, lambda: teg.c_call(lib, sparse, len(want) + 64))
+    assert rc == 0 and took == 2 and buf[:size].tobytes() == want
+
+
+@pytest.mark.gpu
+def test_progressive_encode_whose_stream_outgrows_both_guesses(lib):
+    """j2p_entropy_encode_progressive, the second and the third request, on the same blocks: six scans whose streams together have
+    1392 bytes for a guess of 512, and 376 FF bytes in them for a guess of 343.  What is queued again reaches over all scans: the
+    coefficients with every AC scan's flags and EOB runs, every scan's lengths, every scan's stream"""
+    import progressive_cases as prc
+    import test_progressive_gpu as tpg
+    case = rg.heavy_case()
+    want, report = prc.encode_case(case)
+    assert rg.takes(rg.progressive_requests(case, report)) == 3
+    lib.j2p_pool_trim()
+    (rc, size, buf), took = counted(lib, lambda: tpg.c_call(lib, case, len(want) + 64))
+    assert rc == 0, lib.j2p_last_error().decode()
+    assert took == 3, "the block did not move twice"
+    assert buf[:size].tobytes() == want and (buf[size:] == 0xA5).all()
+    # the control: the sparse image's streams outgrow the first guess, its FF bytes (none) not theirs
+    sparse = rg.sparse_case()
+    want, report = prc.encode_case(sparse)
+    assert rg.takes(rg.progressive_requests(sparse, report)) == 2
+    lib.j2p_pool_trim()
+    (rc, size, buf), took = counted(lib, lambda: tpg.c_call(lib, sparse, len(want) + 64))
     assert rc == 0 and took == 2 and buf[:size].tobytes() == want
 
 
