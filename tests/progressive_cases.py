@@ -6,7 +6,8 @@ tests/test_progressive_gpu.py the device's coder against the restatement).
 A scan is first walked into its operations — ("s", table, symbol) and ("b", value, length) — with no table in hand; the counts
 and the coded bits both read that list, so what is counted is what is coded.  encode_report(...) returns the file and, per scan,
 its parameters, the counts of each table it used, its bits before padding, its stuffed FF bytes, how many EOB runs it flushed and
-why, and how many ZRLs it emitted."""
+why, and how many ZRLs it emitted — and what the directed cases are searched and asserted by: every EOB run it flushed (its first
+block, its length, why), the 1-bits that completed the scan's last byte and that byte before stuffing."""
 import numpy as np
 
 import entropy_cases as ec
@@ -59,8 +60,14 @@ def _dc_refine(zz, width, height, sub, al, ops):
 class _Run:
     """the pending EOB run of an AC scan: its length and, in refinement scans, the correction bits that wait with it"""
 
-    def __init__(self, ops, table, flushes):
-        self.ops, self.table, self.flushes, self.n, self.bits = ops, table, flushes, 0, []
+    def __init__(self, ops, table, runs):
+        self.ops, self.table, self.runs, self.n, self.bits, self.first = ops, table, runs, 0, [], 0
+
+    def join(self, b):
+        """block b joins the run"""
+        if self.n == 0:
+            self.first = b
+        self.n += 1
 
     def flush(self, why):
         if self.n == 0:
@@ -70,13 +77,13 @@ class _Run:
         if extra:
             self.ops.append(("b", self.n & ((1 << extra) - 1), extra))
         self.ops += [("b", b, 1) for b in self.bits]
+        self.runs.append((self.first, self.n, why))
         self.n, self.bits = 0, []
-        self.flushes[why] += 1
 
 
-def _ac_first(blocks, table, ss, se, al, ops, flushes):
-    run = _Run(ops, table, flushes)
-    for block in blocks:
+def _ac_first(blocks, table, ss, se, al, ops, runs):
+    run = _Run(ops, table, runs)
+    for b, block in enumerate(blocks):
         r = 0
         for k in (range(ss, se + 1) if any(block[ss:se + 1]) else ()):
             v = block[k]
@@ -95,19 +102,19 @@ def _ac_first(blocks, table, ss, se, al, ops, flushes):
             ops.append(("b", (t if v >= 0 else ~t) & ((1 << s) - 1), s))
             r = 0
         if r > 0 or not any(block[ss:se + 1]):           # (a band of zeros: walked at once)
-            run.n += 1
+            run.join(b)
             if run.n == EOBRUN_LIMIT:
                 run.flush("limit_7fff")
     run.flush("end_of_scan")
 
 
-def _ac_refine(blocks, table, ss, se, al, ops, flushes):
+def _ac_refine(blocks, table, ss, se, al, ops, runs):
     """returns the number of ZRLs"""
-    run = _Run(ops, table, flushes)
+    run = _Run(ops, table, runs)
     zrls = 0
-    for block in blocks:
+    for b, block in enumerate(blocks):
         if not any(block[ss:se + 1]):                   # (a band of zeros, walked at once: it joins the run with no correction bit)
-            run.n += 1
+            run.join(b)
             if run.n == EOBRUN_LIMIT:
                 run.flush("limit_7fff")
             continue
@@ -135,7 +142,7 @@ def _ac_refine(blocks, table, ss, se, al, ops, flushes):
             waiting = []
             r = 0
         if r > 0 or waiting:
-            run.n += 1
+            run.join(b)
             run.bits += waiting
             if run.n == EOBRUN_LIMIT:
                 run.flush("limit_7fff")
@@ -145,10 +152,11 @@ def _ac_refine(blocks, table, ss, se, al, ops, flushes):
     return zrls
 
 
-def scan_operations(zz, width, height, sub, scan):
-    """(operations, flushes by reason, ZRLs of a refinement scan) of one scan; zz: per component [row][column][zigzag position]"""
+def scan_walk(zz, width, height, sub, scan):
+    """(operations, EOB runs as (first block, length, why) in the order they were flushed, ZRLs of a refinement scan) of one scan;
+    zz: per component [row][column][zigzag position]"""
     comps, ss, se, ah, al = scan
-    ops, flushes, zrls = [], dict.fromkeys(WHY, 0), 0
+    ops, runs, zrls = [], [], 0
     if ss == 0:
         (_dc_refine if ah else _dc_first)(zz, width, height, sub, al, ops)
     else:
@@ -156,10 +164,23 @@ def scan_operations(zz, width, height, sub, scan):
         blocks = [b for row in zz[c] for b in row]
         table = ("ac", 0 if c == 0 else 1)
         if ah:
-            zrls = _ac_refine(blocks, table, ss, se, al, ops, flushes)
+            zrls = _ac_refine(blocks, table, ss, se, al, ops, runs)
         else:
-            _ac_first(blocks, table, ss, se, al, ops, flushes)
-    return ops, flushes, zrls
+            _ac_first(blocks, table, ss, se, al, ops, runs)
+    return ops, runs, zrls
+
+
+def count_by_why(runs):
+    flushes = dict.fromkeys(WHY, 0)
+    for _first, _length, why in runs:
+        flushes[why] += 1
+    return flushes
+
+
+def scan_operations(zz, width, height, sub, scan):
+    """(operations, flushes by reason, ZRLs of a refinement scan) of one scan"""
+    ops, runs, zrls = scan_walk(zz, width, height, sub, scan)
+    return ops, count_by_why(runs), zrls
 
 
 def scan_tables(ncomp, scan):
@@ -186,7 +207,8 @@ def _sos(scan):
 
 def encode_report(coefficients, width, height, quant, sub=(1, 1)):
     """(file, [per scan: dict(scan, counts {table: 256 counts}, tables {table: (BITS, HUFFVAL, longest)}, bits, stuffed, flushes,
-    zrls)])"""
+    zrls, runs [(first block, length, why)], short: the 1-bits that completed the last byte, last: that byte before stuffing, None
+    where the scan has no data)])"""
     ncomp = len(coefficients)
     sub = sub if ncomp == 3 else (1, 1)
     zz = [np.asarray(a).reshape(gh, gw, 64)[:, :, ec.ZIGZAG].tolist() for a, (gh, gw) in zip(coefficients, ec.grids(width, height, ncomp, sub))]
@@ -195,7 +217,7 @@ def encode_report(coefficients, width, height, quant, sub=(1, 1)):
     file = bytearray(plain[:sof] + b"\xff\xc2" + plain[sof + 2:dht])
     report = []
     for scan in SCANS[ncomp]:
-        ops, flushes, zrls = scan_operations(zz, width, height, sub, scan)
+        ops, runs, zrls = scan_walk(zz, width, height, sub, scan)
         counts = {t: [0] * 256 for t in scan_tables(ncomp, scan)}
         for op in ops:
             if op[0] == "s":
@@ -221,7 +243,7 @@ def encode_report(coefficients, width, height, quant, sub=(1, 1)):
         data = bytes(bits.data)
         file += _sos(scan) + data.replace(b"\xff", b"\xff\x00")
         report.append({"scan": scan, "counts": counts, "tables": tables, "bits": nbits, "stuffed": data.count(b"\xff"),
-                       "flushes": flushes, "zrls": zrls})
+                       "flushes": count_by_why(runs), "zrls": zrls, "runs": runs, "short": short, "last": data[-1] if data else None})
     return bytes(file + b"\xff\xd9"), report
 
 
@@ -280,12 +302,142 @@ def refine_zrl_case():
     return case
 
 
+def _put(case, b, values):
+    """block b of a grey case: {zigzag position: value}"""
+    flat = case["coefficients"][0].reshape(-1, 64)
+    for k, v in values.items():
+        flat[b, ec.ZIGZAG[k]] = v
+
+
+def cut_from_block_case(b):
+    """grey 1456x1456 (33124 blocks), all zero but block b, which is new in every AC scan and ends in a tail in each — 4 at 1 (scan
+    1-5), -4 at 6 (6-63), 2 at 7 (2, 1), -1 at 8 (1, 0): the run that starts AT block b is cut at 32767 blocks.  With b = 1 (mod 4) the
+    walking lane of k_prog_runs reaches its 16-byte alignment with a length of 3 (mod 4), the only residue from which four blocks at
+    once could step onto 32767 (32763 + 4): the guard of that fast path decides.  b = 1: the lane of block 1 walks, fifteen single
+    steps first; b = 17: another workgroup lane than that of block 0, which walks the seventeen blocks in front"""
+    case = ec.make(1456, 1456, 1, (1, 1), "zero")
+    _put(case, b, {1: 4, 6: -4, 7: 2, 8: -1})
+    return case
+
+
+BOTH_LIMITS = {"dense": range(0, 15), "sixty": range(1015, 1015 + 10 * 3001, 3001), "fifty": range(32787, 32787 + 8 * 7, 7)}
+
+
+def both_limits_case():
+    """grey 1456x1456: blocks 0..14 hold 2 and -3 at every AC position (945 correction bits in the last scan: the 937-bit rule cuts
+    behind block 14); ten blocks hold 3 at 1..60 (600 correction bits) inside the run that starts at block 15 and is cut at 32767
+    blocks, eight blocks hold -2 at 1..50 (400) in the run behind it.  600 + 400 > 937: a cutter that keeps the flushed run's
+    waiting bits cuts the last run where libjpeg does not"""
+    case = ec.make(1456, 1456, 1, (1, 1), "zero")
+    for b in BOTH_LIMITS["dense"]:
+        _put(case, b, {k: 2 if k % 2 else -3 for k in range(1, 64)})
+    for b in BOTH_LIMITS["sixty"]:
+        _put(case, b, {k: 3 for k in range(1, 61)})
+    for b in BOTH_LIMITS["fifty"]:
+        _put(case, b, {k: -2 for k in range(1, 51)})
+    return case
+
+
+# a base seed at which row_1's one block is a late block with a coefficient at position 63 (a refinement scan with no run at all);
+# the densities below were chosen so that the family then shows every run tests/test_progressive_cpu.py asserts of it
+ROW_SEED = 52
+ROW_SIZES = (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
+
+
+def row_case(n):
+    """grey 8n x 8, one row of n blocks from one seeded generator: quiet blocks (zero, 55 %), CARRIERS (43 %: 1 to 24 coefficients
+    of magnitude 4..7: new in the first scans, corrections in both refinement scans — some five waiting bits a block, so that
+    the 937-bit rule cuts runs of the long rows) and LATE blocks (2 %: one to three of +-1, +-2 or +-3: new only in a refinement
+    scan, one in four at position 63, where no tail follows); from 17 blocks on, blocks 15, 16, 17 and n - 1 are late blocks.
+    The sizes are those around the 16 flag bytes a load of k_prog_runs, the 64 blocks a workgroup of k_prog_classify and the 1024
+    items a tile of k_scan_* (over the items of all scans)"""
+    case = ec.make(8 * n, 8, 1, (1, 1), "zero")
+    rng = np.random.default_rng(ROW_SEED + n)
+    forced = (15, 16, 17, n - 1) if n >= 17 else ()
+    for b in range(n):
+        kind = rng.random()
+        if b in forced or kind < 0.02:
+            where = 1 + rng.permutation(63)[:int(rng.integers(1, 4))]
+            if rng.random() < 0.25:
+                where[0] = 63
+            _put(case, b, {int(k): int(rng.choice([1, -1, 2, -2, 3, -3])) for k in where})
+        elif kind < 0.45:
+            where = 1 + rng.permutation(63)[:int(rng.integers(1, 25))]
+            _put(case, b, {int(k): int(rng.choice([4, -5, 6, -7, -4, 5, -6, 7])) for k in where})
+    return case
+
+
+# ---- how a scan's stream ends ----
+KINDS = ("dc_first", "dc_refine", "ac_first", "ac_refine")
+STREAM_ENDS = tuple(f"{kind}_{end}" for kind in KINDS for end in ("whole_bytes", "ff_end")) + ("whole_words",)
+END_SHAPES = ((16, 8, 1, (1, 1)), (24, 16, 3, (2, 2)))
+
+
+def scan_kind(scan):
+    _comps, ss, _se, ah, _al = scan
+    return ("dc" if ss == 0 else "ac") + ("_refine" if ah else "_first")
+
+
+def stream_ends(report):
+    """which of STREAM_ENDS a file's report shows.  <kind>_whole_bytes: a scan of that kind that is not the file's last ends with no
+    padding bit; <kind>_ff_end: one that is not the last is completed with 1-bits to a last byte of FF, so its stuffed 00 is the
+    scan's final byte, in front of the next scan's DHT; whole_words: some scan's bits are a multiple of 32"""
+    out = set()
+    for r in report[:-1]:
+        if r["short"] == 0:
+            out.add(scan_kind(r["scan"]) + "_whole_bytes")
+        elif r["last"] == 0xff:
+            out.add(scan_kind(r["scan"]) + "_ff_end")
+    if any(r["bits"] % 32 == 0 for r in report):
+        out.add("whole_words")
+    return out
+
+
+_END_SEEDS = {}
+
+
+def _stream_end_seeds():
+    """{one of STREAM_ENDS: (shape, seed)}: per property the first seed (of a fixed sequence, as entropy_cases._search) whose sparse
+    16x8 grey or 24x16 4:2:0 case shows it — found in one pass, once.  dc_refine_whole_bytes is not searched: a DC refinement scan
+    is one bit per position, 2 and 12 at these sizes, never a multiple of 8 (dc_refine_whole_bytes_case is built by hand)"""
+    wanted = set(STREAM_ENDS) - {"dc_refine_whole_bytes"}
+    if not _END_SEEDS:
+        found = {}
+        for seed in range(1, 4000):
+            for shape in END_SHAPES:
+                for end in stream_ends(encode_case(ec.make(*shape, "sparse", seed=seed))[1]):
+                    found.setdefault(end, (shape, seed))
+            if wanted <= set(found):
+                break
+        else:
+            raise AssertionError(f"no seed gives the directed endings {sorted(wanted - set(found))}")
+        _END_SEEDS.update({end: found[end] for end in wanted})
+    return _END_SEEDS
+
+
+def dc_refine_whole_bytes_case():
+    """grey 64x8: eight positions, eight bits of DC refinement and no padding"""
+    return ec.make(64, 8, 1, (1, 1), "sparse", seed=1)
+
+
+def stream_end_cases():
+    """{"end_" + one of STREAM_ENDS: a case that shows it}"""
+    cases = {"end_" + end: ec.make(*shape, "sparse", seed=seed) for end, (shape, seed) in sorted(_stream_end_seeds().items())}
+    cases["end_dc_refine_whole_bytes"] = dc_refine_whole_bytes_case()
+    return cases
+
+
 EXISTING = ["grey_8x8_zero", "colour_1x1_420", "sparse_41x23_420", "sparse_40x24_422", "sparse_41x23_440", "dc_swing", "run_lengths",
             "stuffed_end", "dense_368x368_420", "sparse_368x368_420"]
+STREAM_END_NAMES = ["end_" + end for end in STREAM_ENDS]
 
 
 def new_cases():
-    return {"eobrun_limit": eobrun_limit_case(), "correction_limit": correction_limit_case(), "refine_zrl": refine_zrl_case()}
+    cases = {"eobrun_limit": eobrun_limit_case(), "correction_limit": correction_limit_case(), "refine_zrl": refine_zrl_case(),
+             "cut_from_block_1": cut_from_block_case(1), "cut_from_block_17": cut_from_block_case(17), "both_limits": both_limits_case()}
+    cases.update({f"row_{n}": row_case(n) for n in ROW_SIZES})
+    cases.update(stream_end_cases())
+    return cases
 
 
 def gpu_cases():

@@ -3,7 +3,9 @@ j2p_batch_submit_jpeg_progressive, j2p_batch_submit_file_jpeg_progressive; entro
 Batch.submit(jpeg={"progressive": True})): every file is, byte for byte, the restatement's of tests/progressive_cases.py — which
 tests/test_progressive_cpu.py holds against libjpeg's jpeg_simple_progression() — of the same coefficients, and the device's
 per-scan symbol counts, bits, stuffed bytes and EOB runs are the restatement's.  The counts are compared themselves: a wrong
-count that happens not to move a code length would pass a comparison of files."""
+count that happens not to move a code length would pass a comparison of files.  What each case of progressive_cases.gpu_cases() is
+there for — where k_prog_runs cuts a run and from which block, the loops of its walk, how a scan's stream ends — is asserted from
+the restatement's report by tests/test_progressive_cpu.py::test_case_preconditions."""
 import ctypes
 
 import numpy as np
@@ -85,8 +87,9 @@ def c_call(lib, case, room, fill=0xA5, behind=64):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["stuffed_end", "sparse_41x23_420", "refine_zrl"])
+@pytest.mark.parametrize("name", ["stuffed_end", "sparse_41x23_420", "refine_zrl"] + pc.STREAM_END_NAMES)
 def test_one_byte_short_reports_the_size_and_touches_nothing(lib, directed, name):
+    """... the end_<...> cases among them: scans that end on a byte, on a word, and on an FF whose 00 is the scan's final byte"""
     case, want, _report = directed[name]
     rc, size, buf = c_call(lib, case, len(want) - 1)
     assert rc == J2P_ESPACE and size == len(want) and (buf == 0xA5).all()
