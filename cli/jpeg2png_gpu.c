@@ -30,6 +30,9 @@
  *   -r, --progressive = with -j: the progressive file of libjpeg's jpeg_simple_progression() — ten scans (six with -g), every one with
  *                  Huffman tables of its own (include/jpeg2png_amd.h, "The progressive JPEG file"); with -e the GPU codes every scan
  *                  (j2p_batch_submit_jpeg_progressive), without it libjpeg does — the same file either way.  -O changes nothing about it
+ *   -D, --decode-any-on-gpu = -d, and a progressive input's scans are all decoded on the GPU as well (j2p_batch_next_file_scans;
+ *                  include/jpeg2png_amd.h, "Reading a progressive JPEG file"); a file that decoder still refuses goes to libjpeg after
+ *                  the one line -d prints
  *   -P, --png-on-gpu = the PNG is filtered and deflated on the GPU (j2p_batch_submit_png; include/jpeg2png_amd.h, "The PNG file") and
  *                  written as it comes down: no libpng, and no samples on the bus.  The same pixels as without it, in another (usually
  *                  somewhat larger) file; with -1, -g, -z, -s and -d; not with -j, not for row-tiled images
@@ -194,7 +197,7 @@ static void read_coefficients(FILE *in, struct jpeg_in *jp, unsigned zoom, bool 
  * no coefficients, and keeps the bytes.  false, after one line on stderr: the file is valid but of a kind that decoder does not read
  * (progressive, several scans, ...: J2P_ENOTSUP) and the caller goes on through libjpeg.  A damaged file dies with the library's message,
  * here or when its job is waited for. */
-static bool read_file_for_gpu(const char *infile, FILE *in, struct jpeg_in *jp, unsigned zoom, bool grey)
+static bool read_file_for_gpu(const char *infile, FILE *in, struct jpeg_in *jp, unsigned zoom, bool grey, bool any)
 {
         if(fseek(in, 0, SEEK_END) != 0) { die_perror("could not read input file `%s`", infile); }
         const long size = ftell(in);
@@ -203,7 +206,15 @@ static bool read_file_for_gpu(const char *infile, FILE *in, struct jpeg_in *jp, 
         if(!file) { die("could not allocate memory for the file"); }
         if(fread(file, 1, (size_t)size, in) != (size_t)size) { die_perror("could not read input file `%s`", infile); }
         j2p_jpeg_info info;
-        const int rc = j2p_jpeg_parse(file, (size_t)size, &info);
+        int rc;
+        if(any) {               /* -D: progressive files too (j2p_jpeg_parse_scans) */
+                j2p_jpeg_scans *scans = malloc(sizeof(*scans));
+                if(!scans) { die("could not allocate memory for the file"); }
+                rc = j2p_jpeg_parse_scans(file, (size_t)size, &info, scans);
+                free(scans);
+        } else {
+                rc = j2p_jpeg_parse(file, (size_t)size, &info);
+        }
         if(rc == J2P_ENOTSUP) {
                 pthread_mutex_lock(&ui_lock);
                 if(bar_on) { bar_clear(); bar_on = false; }
@@ -374,6 +385,7 @@ struct options {
         float weights[3], pweights[3];
         unsigned png_bits;
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
+        bool decode_any_on_gpu; /* -D: -d, and progressive files are decoded on the GPU too (j2p_batch_next_file_scans) */
         bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
         bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
         bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
@@ -446,7 +458,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         struct jpeg_in jp;
         memset(&jp, 0, sizeof(jp));
         const unsigned orientation = o->auto_orient ? read_orientation(infile, in) : 1;
-        if(!o->decode_on_gpu || !read_file_for_gpu(infile, in, &jp, o->zoom, o->grey)) {
+        if(!o->decode_on_gpu || !read_file_for_gpu(infile, in, &jp, o->zoom, o->grey, o->decode_any_on_gpu)) {
                 read_coefficients(in, &jp, o->zoom, o->grey);
         }
         fclose(in);
@@ -540,7 +552,10 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         pthread_once(&batch_once, batch_start);
         if(batch_rc != J2P_OK) { die("%s", batch_err); }
         /* (the orientation travels next to the job: set for this thread's next submit, before every one of them below) */
-#define ORIENT_NEXT() gpu_check(orientation > 1 ? j2p_batch_next_orientation(batch, orientation, jp.w * zoom, jp.h * zoom) : J2P_OK)
+#define ORIENT_NEXT() do { \
+                gpu_check(orientation > 1 ? j2p_batch_next_orientation(batch, orientation, jp.w * zoom, jp.h * zoom) : J2P_OK); \
+                gpu_check(jp.file && o->decode_any_on_gpu ? j2p_batch_next_file_scans(batch, 1) : J2P_OK); /* (-D: what the submit below accepts) */ \
+        } while(0)
         uint8_t *file = NULL;
         size_t file_bytes = 0;
         if(o->jpeg_quality && o->encode_on_gpu) {
@@ -669,6 +684,8 @@ static void usage(void)
                "  -d, --decode-on-gpu          the GPU Huffman-decodes the input too (baseline files; others are read by libjpeg\n"
                "                               after one line saying so): no libjpeg between the file's bytes and the solver;\n"
                "                               such an image is not row-tiled\n"
+               "  -D, --decode-any-on-gpu      -d, and the GPU decodes every scan of a progressive file too; what it still does\n"
+               "                               not read goes to libjpeg after that one line\n"
                "  -e, --encode-on-gpu          with -j: the GPU also entropy-codes the file (default Huffman tables, the bytes\n"
                "                               libjpeg would write) and only the file comes down; not for row-tiled images\n"
                "  -O, --optimize               with -j: Huffman tables made for the image, a smaller file of the same\n"
@@ -699,7 +716,7 @@ int main(int argc, char **argv)
                 {"second-order-weight", required_argument, NULL, 'w'}, {"zoom", required_argument, NULL, 'z'},
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
-                {"decode-on-gpu", no_argument, NULL, 'd'}, {"optimize", no_argument, NULL, 'O'},
+                {"decode-on-gpu", no_argument, NULL, 'd'}, {"decode-any-on-gpu", no_argument, NULL, 'D'}, {"optimize", no_argument, NULL, 'O'},
                 {"progressive", no_argument, NULL, 'r'},
                 {"png-on-gpu", no_argument, NULL, 'P'}, {"auto-orient", no_argument, NULL, 'a'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
@@ -709,7 +726,7 @@ int main(int argc, char **argv)
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edOPar", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edDOPar", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -728,6 +745,7 @@ int main(int argc, char **argv)
                 case 'S': S_arg = optarg; break;
                 case 'e': o.encode_on_gpu = true; break;
                 case 'd': o.decode_on_gpu = true; break;
+                case 'D': o.decode_on_gpu = o.decode_any_on_gpu = true; break;
                 case 'O': o.optimize = true; break;
                 case 'r': o.progressive = true; break;
                 case 'P': o.png_on_gpu = true; break;

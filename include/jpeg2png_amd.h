@@ -1149,6 +1149,86 @@ int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_
 int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec,
                                            uint8_t *out, size_t capacity, size_t *out_size, int *ticket);
 
+/* Reading a progressive JPEG file: every scan of an SOF2 file decoded ON THE DEVICE.  The result is, for each component, the
+ * blocks_w x blocks_h grid of "Reading a JPEG file", value for value what libjpeg's jpeg_read_coefficients delivers for the file;
+ * where this wording and libjpeg differ on a file libjpeg reads without a warning, libjpeg is the authority.  The calls of
+ * "Reading a JPEG file" keep refusing SOF2 with J2P_ENOTSUP; the calls below are the way in.  This is the definition.
+ *
+ * Accepted.  SOF2, 8-bit samples, Huffman coding, 1 or 3 components with the sampling limits of the baseline reader; up to
+ * J2P_DECODE_SCANS_MAX scans (more: J2P_ENOTSUP); DHT and DRI segments between scans — a scan uses the tables and the restart interval
+ * in force at its SOS, so every scan carries its own snapshot of them (at most J2P_SCAN_TABLES_MAX table definitions in a file, more:
+ * J2P_ENOTSUP); DQT only before the first SOS (a later one: J2P_ENOTSUP).  A single-scan SOF0 / SOF1 file is decoded by the path of
+ * "Reading a JPEG file", unchanged; a multi-scan SOF0 / SOF1 file stays J2P_ENOTSUP.
+ *
+ * Scans (T.81 G.1.1.1.1).  SOS: ncomp, per component id and (DC slot << 4) | AC slot, then Ss, Se, (Ah << 4) | Al.
+ *   Ss = 0 implies Se = 0: a DC scan of 1..ncomp components in the frame's order.  Ss > 0 implies one component and Ss <= Se <= 63.
+ *   Al <= 13; Ah is 0 or Al + 1.  For each (component, coefficient) the first scan that covers it has Ah = 0 and every later one has Ah
+ *   equal to the Al before it (so a coefficient has ONE first scan).  A component's AC scans come behind its DC first scan.  Anything
+ *   else is a bogus progression, J2P_EFORMAT.  A script that ends before Al reaches 0 is valid: the values stay shifted, as libjpeg
+ *   leaves them; a coefficient no scan covers stays 0.
+ * Geometry.  A scan of several components walks the MCUs of "Reading a JPEG file" restricted to its components, the blocks that pad
+ *   the grids included; its restart interval counts MCUs.  A scan of one component, DC or AC, walks that component's own
+ *   blocks_w x blocks_h grid in raster order; its restart interval counts blocks.
+ * Decoding.  Symbols, value extension, unstuffing and restart markers as in "Reading a JPEG file".
+ *   DC first (Ah = 0).  A symbol s, s bits, extended, added to the component's predictor (0 at the start of the scan and of every
+ *     restart interval); coefficient 0 becomes predictor << Al.
+ *   DC refinement.  One bit per block position, padding blocks included: coefficient 0 |= bit << Al.
+ *   AC first.  From k = Ss.  Symbol (r << 4) | s: s = 0, r = 15 skips 16 positions; s = 0, r < 15 is EOBn — this block from k on and
+ *     the next (1 << r) + (r extra bits) - 1 blocks hold nothing in the band; otherwise k += r, s bits extended give the value v, the
+ *     coefficient at zigzag k becomes v << Al (kept to 16 bits), k += 1.  The block is done when k passes Se.
+ *   AC refinement.  libjpeg's decode_mcu_AC_refine.  From k = Ss.  Symbol (r << 4) | s with s 0 or 1; s = 1 is followed by a sign bit:
+ *     the new coefficient is +(1 << Al) for 1, -(1 << Al) for 0.  EOBn as above.  Otherwise the walk goes on from k past r coefficients
+ *     that were zero when the scan began, up to the next such one, k', where the new coefficient goes (nowhere for 15/0), and k = k' + 1.
+ *     Every coefficient already non-zero that is passed — on the way to k', behind an EOBn to the band's end, in every block of an EOB
+ *     run over the whole band — reads one correction bit, in zigzag order, behind the symbol's own bits: a 1 adds (1 << Al) away
+ *     from zero when that bit of the coefficient is still clear.
+ *   A restart marker resets the predictors and must not fall inside an EOB run.
+ * Refusals.  J2P_EFORMAT: a truncated scan, a code in no table, a run past Se, an EOB run past the last block of its restart
+ *   interval, s > 1 in a refinement scan, a DC that does not fit int16 with its shift, bytes left over behind a scan's or an
+ *   interval's last block, a restart marker missing or out of sequence, a bogus progression, a table a scan needs that is not defined.
+ *   What the marker segments alone show is refused before a device is touched, as for "Reading a JPEG file".  Per scan the data must hold
+ *   a bit for every block of a DC scan, a bit for every 32767 blocks of an AC scan and two bytes for every restart marker, or the scan
+ *   counts as truncated: a claimed size alone makes the library allocate nothing. */
+#define J2P_DECODE_SCANS_MAX 128
+#define J2P_SCAN_TABLES_MAX 392
+typedef struct j2p_jpeg_scan {
+        unsigned ncomp;                    /* components in the scan */
+        unsigned comp[3];                  /* ... as indices into j2p_jpeg_info.comp, ascending */
+        unsigned ss, se, ah, al;
+        unsigned dc_slot[3], ac_slot[3];   /* as the SOS names them, per component of the scan */
+        unsigned restart_interval;         /* in force at the SOS: MCUs (several components) or blocks (one); 0: none */
+        unsigned intervals;                /* restart intervals in the scan */
+        size_t begin, end;                 /* the scan's entropy-coded data: file[begin, end) */
+} j2p_jpeg_scan;
+typedef struct j2p_jpeg_scans {
+        unsigned nscans;
+        unsigned progressive;              /* 1: SOF2.  0: a sequential file, one scan, decoded as "Reading a JPEG file" says */
+        j2p_jpeg_scan scan[J2P_DECODE_SCANS_MAX];
+} j2p_jpeg_scans;
+/* Host only: j2p_jpeg_parse for the files accepted above (both zeroed on failure).  info keeps its layout: scan_begin is the first scan's
+ * begin, scan_end the last scan's end, restart_interval the value in force at the first scan, intervals the sum over the scans; a
+ * component's dc_slot / ac_slot are those of its first DC / AC scan. */
+int j2p_jpeg_parse_scans(const uint8_t *file, size_t size, j2p_jpeg_info *info, j2p_jpeg_scans *scans);
+typedef struct j2p_scans_stats {
+        unsigned scans;
+        unsigned dc_first, ac_first, dc_refine, ac_refine;     /* scans of each kind */
+        unsigned subsequences;             /* of all first scans together: they share one array and the same rounds */
+        unsigned rounds;                   /* rounds in which a subsequence's entry state changed */
+        unsigned host_waits;               /* times the host waited for the stream during the decode */
+        unsigned long long data_bytes;     /* the scans' entropy-coded data as the file holds it */
+        double decode_ms;                  /* host clock around the decode alone, as in j2p_decode_stats */
+        double ac_refine_share;            /* of decode_ms: the AC refinement launches, by events around them (0 without such scans) */
+} j2p_scans_stats;
+/* j2p_entropy_decode_ex for the files accepted above; file, coef_host, quant, info and subsequence_bits as there.  stats may be NULL. */
+int j2p_entropy_decode_scans(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64],
+                             j2p_jpeg_info *info, unsigned subsequence_bits, j2p_scans_stats *stats);
+/* j2p_solver_create_from_jpeg for the files accepted above, argument for argument. */
+int j2p_solver_create_from_jpeg_scans(j2p_solver **out, int device, void *stream, const uint8_t *file, size_t size, float weight,
+                                      const float pweight[], unsigned iterations, j2p_jpeg_info *info);
+/* Makes the calling thread's NEXT j2p_batch_submit_file* call on b (any of the five) accept what this section accepts (accept != 0), as
+ * j2p_batch_next_orientation hands a submit its orientation: consumed by that submit whatever becomes of it; j2p_job is untouched. */
+int j2p_batch_next_file_scans(j2p_batch *b, unsigned accept);
+
 /* The PNG file: the image's samples filtered and deflated ON THE DEVICE, so that a complete PNG file comes down instead of 3 or 6 bytes
  * per pixel for a host library to deflate on one core.  Every byte of the file is defined here; tests/png_cases.py restates it.  This is
  * the definition.

@@ -156,6 +156,28 @@ class _CDecodeStats(ctypes.Structure):
                 ("recomputed", ctypes.c_uint * J2P_DECODE_STATS_ROUNDS), ("data_bytes", ctypes.c_ulonglong), ("decode_ms", ctypes.c_double)]
 
 
+J2P_DECODE_SCANS_MAX = 128
+
+
+class _CJpegScan(ctypes.Structure):
+    """j2p_jpeg_scan"""
+    _fields_ = [("ncomp", ctypes.c_uint), ("comp", ctypes.c_uint * 3), ("ss", ctypes.c_uint), ("se", ctypes.c_uint), ("ah", ctypes.c_uint),
+                ("al", ctypes.c_uint), ("dc_slot", ctypes.c_uint * 3), ("ac_slot", ctypes.c_uint * 3), ("restart_interval", ctypes.c_uint),
+                ("intervals", ctypes.c_uint), ("begin", ctypes.c_size_t), ("end", ctypes.c_size_t)]
+
+
+class _CJpegScans(ctypes.Structure):
+    """j2p_jpeg_scans"""
+    _fields_ = [("nscans", ctypes.c_uint), ("progressive", ctypes.c_uint), ("scan", _CJpegScan * J2P_DECODE_SCANS_MAX)]
+
+
+class _CScansStats(ctypes.Structure):
+    """j2p_scans_stats"""
+    _fields_ = [("scans", ctypes.c_uint), ("dc_first", ctypes.c_uint), ("ac_first", ctypes.c_uint), ("dc_refine", ctypes.c_uint),
+                ("ac_refine", ctypes.c_uint), ("subsequences", ctypes.c_uint), ("rounds", ctypes.c_uint), ("host_waits", ctypes.c_uint),
+                ("data_bytes", ctypes.c_ulonglong), ("decode_ms", ctypes.c_double), ("ac_refine_share", ctypes.c_double)]
+
+
 class _CJob(ctypes.Structure):
     _fields_ = [("nchannel", ctypes.c_uint), ("planes", _CPlane * 3), ("separate", ctypes.c_int),
                 ("weight", ctypes.c_float * 3), ("pweight", ctypes.c_float * 3), ("iterations", ctypes.c_uint * 3),
@@ -221,6 +243,7 @@ C_ABI_SYMBOLS = [
     "j2p_batch_next_orientation",
     "j2p_solver_phase_order", "j2p_debug_project_items", "j2p_debug_phase_order", "j2p_debug_grad_items_workgroups",
     "j2p_pool_thread_takes",
+    "j2p_jpeg_parse_scans", "j2p_entropy_decode_scans", "j2p_solver_create_from_jpeg_scans", "j2p_batch_next_file_scans",
 ]
 J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -480,6 +503,13 @@ def _bind(path):
                                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
         lib.j2p_solver_create_from_jpeg.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                     ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_uint, ctypes.POINTER(_CJpegInfo)]
+    if hasattr(lib, "j2p_entropy_decode_scans"):
+        # (as above: an earlier commit's build does not read progressive files)
+        lib.j2p_jpeg_parse_scans.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpegInfo), ctypes.POINTER(_CJpegScans)]
+        lib.j2p_entropy_decode_scans.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+                                                 ctypes.POINTER(_CJpegInfo), ctypes.c_uint, ctypes.POINTER(_CScansStats)]
+        lib.j2p_solver_create_from_jpeg_scans.argtypes = lib.j2p_solver_create_from_jpeg.argtypes
+        lib.j2p_batch_next_file_scans.argtypes = [ctypes.c_void_p, ctypes.c_uint]
     lib.j2p_debug_tensor_path.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.c_ssize_t,
                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     lib.j2p_debug_job_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
@@ -968,13 +998,24 @@ def _jpeg_info_dict(info):
             "scan_begin": info.scan_begin, "scan_end": info.scan_end}
 
 
-def jpeg_parse(data):
+def jpeg_parse(data, progressive=False):
     """j2p_jpeg_parse: the marker segments of a baseline JPEG file (host bytes), read by the library's C parser without touching a
     device -> dict of width, height, components (per component id, sampling factors, the block grid, table slots, quant_table),
     the MCU grid, restart_interval, intervals and the byte range of the entropy-coded data.  J2PError with code J2P_EFORMAT
-    (damaged) or J2P_ENOTSUP (valid, not read: progressive, arithmetic, 12-bit, several scans, ...)."""
+    (damaged) or J2P_ENOTSUP (valid, not read: progressive, arithmetic, 12-bit, several scans, ...).
+    progressive=True: j2p_jpeg_parse_scans — progressive files are read too, and the dict gains "progressive" and "scans": per scan
+    its components (frame indices), ss, se, ah, al, dc_slots, ac_slots, restart_interval, intervals, begin, end."""
     addr, size, _keep = _file_bytes(bytes(data))
     info = _CJpegInfo()
+    if progressive:
+        scans = _CJpegScans()
+        _check(load_library().j2p_jpeg_parse_scans(addr, size, ctypes.byref(info), ctypes.byref(scans)))
+        out = _jpeg_info_dict(info)
+        out["progressive"] = bool(scans.progressive)
+        out["scans"] = [{"components": list(q.comp[:q.ncomp]), "ss": q.ss, "se": q.se, "ah": q.ah, "al": q.al,
+                         "dc_slots": list(q.dc_slot[:q.ncomp]), "ac_slots": list(q.ac_slot[:q.ncomp]), "restart_interval": q.restart_interval,
+                         "intervals": q.intervals, "begin": q.begin, "end": q.end} for q in scans.scan[:scans.nscans]]
+        return out
     _check(load_library().j2p_jpeg_parse(addr, size, ctypes.byref(info)))
     return _jpeg_info_dict(info)
 
@@ -993,7 +1034,7 @@ def upright_size(orientation, width, height):
     return (int(height), int(width)) if int(orientation) >= 5 else (int(width), int(height))
 
 
-def entropy_decode(data, device=0, subsequence_bits=0, stats=False):
+def entropy_decode(data, device=0, subsequence_bits=0, stats=False, progressive=False):
     """the quantised coefficients of a baseline JPEG file, Huffman-decoded on the GPU (j2p_entropy_decode): a list of 1 or 3 int16
     arrays [blocks_h, blocks_w, 64] in natural order — what libjpeg's jpeg_read_coefficients delivers.  data: bytes, or a 1-D uint8
     torch tensor on the device, read in place.  subsequence_bits: 0 for the default, or J2P_DECODE_SUBSEQUENCE_MIN..MAX (the result
@@ -1004,9 +1045,14 @@ def entropy_decode(data, device=0, subsequence_bits=0, stats=False):
     info = _CJpegInfo()
     # (the grids' sizes are needed before the call, so the marker segments are read here too — microseconds of host work; a device
     # tensor's from a copy)
-    parsed = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data)
+    parsed = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data, progressive=progressive)
     arrays = [np.full((k["blocks_h"], k["blocks_w"], 64), 0, dtype=np.int16) for k in parsed["components"]]
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
+    if progressive:
+        # j2p_entropy_decode_scans: progressive files too; stats=True: (arrays, dict of j2p_scans_stats)
+        ss = _CScansStats()
+        _check(lib.j2p_entropy_decode_scans(int(device), addr, size, ptrs, None, ctypes.byref(info), int(subsequence_bits), ctypes.byref(ss)))
+        return (arrays, {name: getattr(ss, name) for name, _ in _CScansStats._fields_}) if stats else arrays
     st = _CDecodeStats()
     _check(lib.j2p_entropy_decode_ex(int(device), addr, size, ptrs, None, ctypes.byref(info), int(subsequence_bits), ctypes.byref(st)))
     if not stats:
@@ -1099,21 +1145,22 @@ class Solver:
         return self
 
     @classmethod
-    def from_jpeg(cls, data, weight, pweight, iterations, device=0, stream=None, upright=False):
+    def from_jpeg(cls, data, weight, pweight, iterations, device=0, stream=None, upright=False, progressive=False):
         """A solver made from a baseline JPEG FILE (j2p_solver_create_from_jpeg): the file's entropy-coded data is Huffman-decoded
         on the GPU straight into the solver's resident coefficients — no libjpeg, and the file's true coefficients at every
         quality.  data: bytes, or a 1-D uint8 torch tensor (on the solver's GPU: the scan is read in place).  pweight: one per
         component of the file (1 or 3).  From there on the solver is the one Solver(planes with those coefficients) is.
         self.jpeg holds what jpeg_parse returns.  J2PError with code J2P_EFORMAT / J2P_ENOTSUP for files that are refused.
         upright=True: the file's EXIF Orientation tag (jpeg_orientation) is set on the solver with the file's size
-        (set_orientation): every output form then delivers the upright image."""
+        (set_orientation): every output form then delivers the upright image.
+        progressive=True: j2p_solver_create_from_jpeg_scans — a progressive file's scans are all decoded on the GPU too."""
         self = cls.__new__(cls)
         lib = load_library()
         self._lib = lib
         self._h = None
         addr, size, held = _file_bytes(data)
         # (the marker segments first, on the host: a refused file and a pweight list of the wrong length cost no GPU work)
-        head = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data)
+        head = jpeg_parse(data.cpu().numpy().tobytes() if hasattr(data, "data_ptr") else data, progressive=progressive)
         if len(pweight) != len(head["components"]):
             raise J2PError(f"from_jpeg: {len(pweight)} pweights for a file of {len(head['components'])} components")
         if hasattr(data, "data_ptr") and data.is_cuda:
@@ -1127,9 +1174,9 @@ class Solver:
         pw = (ctypes.c_float * len(pweight))(*[float(x) for x in pweight])
         info = _CJpegInfo()
         h = ctypes.c_void_p()
-        _check(lib.j2p_solver_create_from_jpeg(ctypes.byref(h), int(device), stream, addr, size, float(weight), pw, int(iterations), ctypes.byref(info)))
+        _check((lib.j2p_solver_create_from_jpeg_scans if progressive else lib.j2p_solver_create_from_jpeg)(ctypes.byref(h), int(device), stream, addr, size, float(weight), pw, int(iterations), ctypes.byref(info)))
         del held
-        self.jpeg = _jpeg_info_dict(info)
+        self.jpeg = head if progressive else _jpeg_info_dict(info)      # (with the scans: what jpeg_parse(progressive=True) returned)
         self.nch = info.ncomp
         self._geom = [(k["w"], k["h"]) for k in self.jpeg["components"]]
         self._adopt(h, device)
@@ -1682,7 +1729,7 @@ def _torch_has_finished(device):
     _torch().cuda.current_stream(device).synchronize()
 
 
-def _job_input(planes, width, height, samples, file, tile, resized):
+def _job_input(planes, width, height, samples, file, tile, resized, progressive=False):
     """step 1 -> (input kind: "planes", "samples" or "file"; the planes; the image's width and height; the C entry point's arguments
     for that input; what they point into).  resized: a tensor with out_width / out_height / box / filter is asked for."""
     if file is not None:
@@ -1691,7 +1738,7 @@ def _job_input(planes, width, height, samples, file, tile, resized):
         if resized:
             raise J2PError("job: with file= a resized tensor is an output of outputs=")
         address, size, held = _file_bytes(file)
-        head = jpeg_parse(file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file)
+        head = jpeg_parse(file.cpu().numpy().tobytes() if hasattr(file, "data_ptr") else file, progressive=progressive)
         if planes is None:
             planes = [Plane(k["w"], k["h"], k["w_samp"], k["h_samp"], None, k["quant_table"]) for k in head["components"]]
         if any(p.data is not None or p.fdata is not None for p in planes):
@@ -1946,8 +1993,10 @@ class Batch:
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None, jpeg=None, file=None, png=None, orientation=None):
-        """orientation=1..8 or "exif" (the tag of file=, read at submit; file jobs only; not with tile): every solver of the job is
+               samples=None, jpeg=None, file=None, png=None, orientation=None, progressive=False):
+        """progressive=True (with file=): the file may be a progressive JPEG, every scan of which the worker decodes on its GPU
+        (j2p_batch_next_file_scans, Solver.from_jpeg(progressive=True)); without it a progressive file is refused as before;
+        orientation=1..8 or "exif" (the tag of file=, read at submit; file jobs only; not with tile): every solver of the job is
         oriented (Solver.set_orientation) and every output kind but the float planes delivers the UPRIGHT image, whose size width and
         height then are — for a file job they default to the file's upright size; the source image is the file's frame, or without
         a file width x height turned back;
@@ -2014,12 +2063,12 @@ class Batch:
                     raise err
             oriented = (code, 0, 0)
             if host is not None and (width is None or height is None):
-                head = jpeg_parse(host)
+                head = jpeg_parse(host, progressive=progressive)
                 uw, uh = upright_size(found, head["width"], head["height"])
                 width, height = (uw if width is None else width), (uh if height is None else height)
             elif file is None and width is not None and height is not None:
                 oriented = (code,) + upright_size(found, width, height)     # (turned back: the same swap)
-        source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized)
+        source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized, progressive)
         kind, result, filled, output_args = _job_output(job, want, planes, width, height)
         keep += filled + _job_record(job, planes, weight, pweight, iterations, want, tile_devices, tile_min_band_pixels)
         if on_progress is not None:
@@ -2030,6 +2079,8 @@ class Batch:
         t = ctypes.c_int()
         if oriented[0]:
             _check(self._lib.j2p_batch_next_orientation(self._h, *oriented))        # (this thread's next submit: the one below)
+        if progressive and file is not None:
+            _check(self._lib.j2p_batch_next_file_scans(self._h, 1))
         _check(getattr(self._lib, name)(self._h, ctypes.byref(job), *args, ctypes.byref(t)))
         self._pending[t.value] = (result, keep)
         return t.value

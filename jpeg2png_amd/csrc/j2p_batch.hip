@@ -47,6 +47,7 @@ struct Request {
         unsigned jpeg_flags = 0;            // J2P_JPEG_*
         bool jpeg_progressive = false;      // ... as the progressive file (flags 0)
         unsigned orientation = 0, orient_w = 0, orient_h = 0;    // j2p_batch_next_orientation: what the calling thread set for this submit
+        bool file_scans = false;                                 // j2p_batch_next_file_scans: the file goes through the scans parser
         const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
         uint8_t *png_out = nullptr;
         size_t png_capacity = 0, *png_size = nullptr;
@@ -558,8 +559,8 @@ int open_file(const Request &q, Job &j)
 {
         j2p_job &d = j.desc;
         if(d.tile) { return j2p_fail(J2P_EINVAL, "job: file input of a row-tiled job is not supported"); }
-        JOB_TRY(j2p_jpeg_open(q.file, q.file_size, &j.file));
-        const j2p_jpeg_info &info = j.file.parsed->info;
+        JOB_TRY(q.file_scans ? j2p_jpeg_open_scans(q.file, q.file_size, &j.file) : j2p_jpeg_open(q.file, q.file_size, &j.file));
+        const j2p_jpeg_info &info = j.file.info();
         if(d.nchannel == 0) { d.nchannel = info.ncomp; }
         // (one channel of a three-component file: component 0 alone, the greyscale solve)
         if(d.nchannel != info.ncomp && d.nchannel != 1) {
@@ -593,7 +594,7 @@ int settle_orientation(const Request &q, Job &j)
                 if(j.orientation == J2P_ORIENTATION_EXIF) {
                         if(!q.file) { return j2p_fail(J2P_EINVAL, "job: J2P_ORIENTATION_EXIF needs a job with a file"); }
                         if(j.file.on_device) {
-                                std::vector<uint8_t> head(j.file.parsed->info.scan_begin < q.file_size ? j.file.parsed->info.scan_begin : q.file_size);
+                                std::vector<uint8_t> head(j.file.info().scan_begin < q.file_size ? j.file.info().scan_begin : q.file_size);
                                 if(hipMemcpy(head.data(), q.file, head.size(), hipMemcpyDeviceToHost) != hipSuccess) {
                                         return j2p_fail(J2P_EDEVICE, "job: the file's head could not be copied from device memory");
                                 }
@@ -604,13 +605,13 @@ int settle_orientation(const Request &q, Job &j)
                 }
                 if(j.orientation > 8) { return j2p_fail(J2P_EINVAL, "job: orientation %u (0: none, 1..8, J2P_ORIENTATION_EXIF)", j.orientation); }
                 if(q.file) {
-                        if(!j.orient_w) { j.orient_w = j.file.parsed->info.width; }
-                        if(!j.orient_h) { j.orient_h = j.file.parsed->info.height; }
+                        if(!j.orient_w) { j.orient_w = j.file.info().width; }
+                        if(!j.orient_h) { j.orient_h = j.file.info().height; }
                 }
                 if(j.orient_w == 0 || j.orient_h == 0) { return j2p_fail(J2P_EINVAL, "job: an orientation needs the source image's size (orient_w, orient_h)"); }
         }
         if(q.file) {
-                const j2p_jpeg_info &info = j.file.parsed->info;
+                const j2p_jpeg_info &info = j.file.info();
                 const bool transposed = j.orientation >= 5;
                 if(!d.out_w) { d.out_w = j.orientation > 1 ? (transposed ? j.orient_h : j.orient_w) : info.width; }
                 if(!d.out_h) { d.out_h = j.orientation > 1 ? (transposed ? j.orient_w : j.orient_h) : info.height; }
@@ -769,6 +770,10 @@ thread_local struct {
         const j2p_batch *batch = nullptr;
         unsigned orientation = 0, orient_w = 0, orient_h = 0;
 } next_orientation;
+// what j2p_batch_next_file_scans left for it
+thread_local struct {
+        const j2p_batch *batch = nullptr;
+} next_file_scans;
 
 int submit(j2p_batch *b, const j2p_job *job, const Request &entry, int *ticket)
 {
@@ -778,6 +783,8 @@ int submit(j2p_batch *b, const j2p_job *job, const Request &entry, int *ticket)
                 q.orientation = next_orientation.orientation, q.orient_w = next_orientation.orient_w, q.orient_h = next_orientation.orient_h;
         }
         next_orientation.batch = nullptr;
+        q.file_scans = next_file_scans.batch && next_file_scans.batch == b;
+        next_file_scans.batch = nullptr;
         if(!b || !job || !ticket) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
         std::unique_ptr<Job> j(new(std::nothrow) Job());
         if(!j) { return j2p_fail(J2P_ENOMEM, "host allocation failed"); }
@@ -940,6 +947,13 @@ int j2p_batch_next_orientation(j2p_batch *b, unsigned orientation, unsigned orie
         next_orientation.orientation = orientation;
         next_orientation.orient_w = orient_w;
         next_orientation.orient_h = orient_h;
+        return J2P_OK;
+}
+
+int j2p_batch_next_file_scans(j2p_batch *b, unsigned accept)
+{
+        if(!b) { return j2p_fail(J2P_EINVAL, "batch is NULL"); }
+        next_file_scans.batch = accept ? b : nullptr;
         return J2P_OK;
 }
 

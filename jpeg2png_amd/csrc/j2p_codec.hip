@@ -1,10 +1,11 @@
 // jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode; the
 // progressive file: j2p_encode_progressive, j2p_entropy_encode_progressive) and a
 // baseline file's entropy-coded data back to coefficients (j2p_jpeg_open, j2p_decode_file, j2p_decoded_grids,
-// j2p_entropy_decode; include/jpeg2png_amd.h, j2p_internal.h) — and, at the end, the PNG coder: samples to the filtered and
+// j2p_entropy_decode; every scan of a progressive file: j2p_jpeg_open_scans, j2p_decode_scans_file, j2p_decode_opened,
+// j2p_entropy_decode_scans; include/jpeg2png_amd.h, j2p_internal.h) — and, at the end, the PNG coder: samples to the filtered and
 // deflated file (j2p_png_write, j2p_png_encode).
 //
-// A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_progressive_kernels.hip.h, j2p_decode_kernels.hip.h): neither way
+// A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_progressive_kernels.hip.h, j2p_decode_kernels.hip.h, j2p_scan_decode_kernels.hip.h): neither way
 // uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
 // stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_scan.
 //
@@ -26,6 +27,7 @@
 #include "j2p_codec_kernels.hip.h"
 #include "j2p_progressive_kernels.hip.h"
 #include "j2p_decode_kernels.hip.h"
+#include "j2p_scan_decode_kernels.hip.h"
 #include "j2p_png_kernels.hip.h"
 
 using namespace j2p;
@@ -764,6 +766,8 @@ const char *decode_error_text(unsigned flags)
         if(flags & kDecodeBadRun) { return "a run past coefficient 63"; }
         if(flags & kDecodeBadEnd) { return "the scan is truncated, or data is left over behind its last block"; }
         if(flags & kDecodeBadDc) { return "a DC value outside int16"; }
+        if(flags & kDecodeBadRefine) { return "a refinement scan's symbol of more than one bit"; }
+        if(flags & kDecodeBadEobRun) { return "an EOB run past the last block of its restart interval"; }
         return "the block count disagrees with the decoder's state";
 }
 
@@ -917,6 +921,260 @@ int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parse
         return finish(J2P_OK);
 }
 
+// ---- reading a progressive JPEG file: k_unstuff_* per scan, k_scans_* (j2p_scan_decode_kernels.hip.h) ----
+// Every scan is unstuffed by launches of its own into one clean buffer (no host wait: a scan's clean bytes are at most its raw ones,
+// so the host knows where each begins).  All first scans share one subsequence array and the rounds of j2p_decode_file, so the host
+// waits as often as for one baseline scan, whatever the number of scans; the refinement scans are queued behind the final pass in
+// file order, and the one wait that ends the decode covers them.
+int j2p_decode_scans_file(int device, hipStream_t stream, const j2p_scans_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
+                          int16_t *const coef[3], j2p_scans_stats *stats)
+{
+        const j2p_scans_parsed &p = *parsed;
+        const j2p_jpeg_info &f = p.base.info;
+        const unsigned nscans = p.scans.nscans;
+        if(S == 0) { S = J2P_DECODE_SUBSEQUENCE_BITS; }
+        if(S < J2P_DECODE_SUBSEQUENCE_MIN || S > J2P_DECODE_SUBSEQUENCE_MAX) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", S, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        if(!p.scans.progressive || nscans == 0 || nscans > J2P_DECODE_SCANS_MAX) { return j2p_fail(J2P_EINVAL, "decode: not a progressive file's scans"); }
+        const size_t nraw = f.scan_end - f.scan_begin;
+        const auto tiles = [](unsigned n) { return (n + kScanTile - 1) / kScanTile; };
+        // the scans as the kernels see them, and how much of everything there is
+        std::vector<ScanDesc> descs(nscans);
+        std::vector<unsigned short> iscan;
+        struct Unstuff {
+                size_t raw_at, nraw, clean_room;
+                unsigned nchunks;
+                size_t keepc, markc, keepo, marko, keeps, marks;
+        };
+        std::vector<Unstuff> un(nscans);
+        j2p_scans_stats st;
+        memset(&st, 0, sizeof(st));
+        st.scans = nscans;
+        unsigned long long clean_room = 0, nint_all = 0, bound = 0, ndiff = 0, data_bytes = 0;
+        for(unsigned s = 0; s < nscans; s++) {
+                const j2p_jpeg_scan &q = p.scans.scan[s];
+                ScanDesc &d = descs[s];
+                memset(&d, 0, sizeof(d));
+                d.kind = q.ss == 0 ? (q.ah ? kScanDcRefine : kScanDcFirst) : (q.ah ? kScanAcRefine : kScanAcFirst);
+                (d.kind == kScanDcFirst ? st.dc_first : d.kind == kScanAcFirst ? st.ac_first : d.kind == kScanDcRefine ? st.dc_refine : st.ac_refine)++;
+                d.ncomp = q.ncomp;
+                unsigned blk = 0;
+                unsigned long long units = q.ncomp > 1 ? (unsigned long long)f.mcus_w * f.mcus_h : 0;
+                for(unsigned c = 0; c < q.ncomp; c++) {
+                        const j2p_jpeg_component &k = f.comp[q.comp[c]];
+                        d.comp[c] = q.comp[c];
+                        d.bw[c] = k.blocks_w;
+                        d.bh[c] = k.blocks_h;
+                        d.hs[c] = q.ncomp == 1 ? 1 : k.h_samp_factor;
+                        d.vs[c] = q.ncomp == 1 ? 1 : k.v_samp_factor;
+                        d.first_blk[c] = blk;
+                        d.dc_tab[c] = d.kind == kScanDcFirst ? p.dc_table[s][c] : 0;
+                        if(q.ncomp == 1) { units = (unsigned long long)k.blocks_w * k.blocks_h; }
+                        for(unsigned i = 0; i < d.hs[c] * d.vs[c] && blk < 12; i++) { d.blk_comp[blk++] = c; }
+                }
+                d.per_mcu = blk;
+                if(units * blk > 0xffffffffull || units == 0) { return j2p_fail(J2P_EINVAL, "decode: a scan of %llu blocks is too large", units * blk); }
+                for(unsigned c = 0; c < q.ncomp; c++) { d.comp_off[c] = (unsigned)units * d.first_blk[c]; }
+                d.ac_tab = q.ss ? p.ac_table[s] : 0;
+                d.mcus_w = q.ncomp == 1 ? d.bw[0] : f.mcus_w;
+                d.units = (unsigned)units;
+                d.ri = q.restart_interval && q.restart_interval < d.units ? q.restart_interval : d.units;
+                d.nint = q.intervals;
+                d.nblocks = d.units * d.per_mcu;
+                d.ss = q.ss;
+                d.se = q.se;
+                d.al = q.al;
+                if(d.nint != (d.units + d.ri - 1) / d.ri || q.end <= q.begin || q.begin < f.scan_begin || q.end > f.scan_end) {
+                        return j2p_fail(J2P_EINVAL, "decode: scan %u is inconsistent", s);
+                }
+                d.rst_base = (unsigned)nint_all;
+                d.clean_base = clean_room;
+                Unstuff &u = un[s];
+                u.raw_at = q.begin - f.scan_begin;
+                u.nraw = q.end - q.begin;
+                u.clean_room = (u.nraw + 16 + 3) / 4 * 4;
+                if(u.nraw / kUnstuffChunk > 0x7fffffffull) { return j2p_fail(J2P_EINVAL, "decode: %zu bytes of data are too many", u.nraw); }
+                u.nchunks = (unsigned)((u.nraw + kUnstuffChunk - 1) / kUnstuffChunk);
+                clean_room += u.clean_room;
+                data_bytes += u.nraw;
+                nint_all += d.nint;
+                if(d.kind == kScanDcFirst || d.kind == kScanAcFirst) {
+                        d.sub_base = (unsigned)iscan.size();
+                        try {
+                                iscan.insert(iscan.end(), d.nint, (unsigned short)s);
+                        } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                        bound += ((unsigned long long)u.nraw * 8 + S - 1) / S + d.nint;
+                }
+                if(d.kind == kScanDcFirst) {
+                        d.diff_base = (unsigned)ndiff;
+                        ndiff += d.nblocks;
+                }
+        }
+        if(bound > 0x7fffffffull || nint_all > 0x7fffffffull || ndiff > 0xffffffffull || iscan.empty()) {
+                return j2p_fail(J2P_EINVAL, "decode: %zu bytes of data are too many for subsequences of %u bits", nraw, S);
+        }
+        const unsigned nfirst = (unsigned)iscan.size(), nbound = (unsigned)bound, nint = (unsigned)nint_all, nblocks = (unsigned)ndiff;
+        j2p_carve take;
+        const size_t raw_at = take(data_on_device ? 0 : nraw), clean_at = take(clean_room);
+        for(Unstuff &u : un) {
+                u.keepc = take((size_t)u.nchunks * 4);
+                u.markc = take((size_t)u.nchunks * 4);
+                u.keepo = take((size_t)u.nchunks * 8);
+                u.marko = take((size_t)u.nchunks * 8);
+                u.keeps = take(((size_t)tiles(u.nchunks) + 1) * 8);
+                u.marks = take(((size_t)tiles(u.nchunks) + 1) * 8);
+        }
+        const size_t rst_at = take((size_t)nint * 8), icount_at = take((size_t)nfirst * 4), first_at = take((size_t)nfirst * 8);
+        const size_t isums_at = take(((size_t)tiles(nfirst) + 1) * 8), iscan_at = take((size_t)nfirst * 2);
+        const size_t exit_at[2] = {take((size_t)nbound * 8), take((size_t)nbound * 8)};
+        const size_t last_at = take((size_t)nbound * 8), done_at = take((size_t)nbound * 4), before_at = take((size_t)nbound * 8);
+        const size_t dsums_at = take(((size_t)tiles(nbound) + 1) * 8);
+        const size_t diff_at = take((size_t)nblocks * 4), dc_at = take((size_t)nblocks * 8), dcsums_at = take(((size_t)tiles(nblocks) + 1) * 8);
+        const size_t descs_at = take(sizeof(ScanDesc) * nscans), pool_at = take(sizeof(j2p_huff_decode) * (p.ntables ? p.ntables : 1)), flags_at = take(256);
+        void *block = nullptr;
+        size_t block_bytes = 0;
+        HIP_TRY(j2p_pool_take(device, take.total, &block, &block_bytes));
+        char *const base = static_cast<char *>(block);
+        const auto u32 = [&](size_t at) { return reinterpret_cast<unsigned *>(base + at); };
+        const auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long *>(base + at); };
+        unsigned *const flags = u32(flags_at);
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        const auto finish = [&](int rc) {
+                (void)hipStreamSynchronize(stream);
+                for(hipEvent_t e : ev) {
+                        if(e) { (void)hipEventDestroy(e); }
+                }
+                j2p_pool_give(device, block, block_bytes);
+                return rc;
+        };
+        const auto failed = [&](hipError_t e, const char *what) { return finish(j2p_fail(J2P_EDEVICE, "decode: %s: %s", what, hipGetErrorString(e))); };
+        for(unsigned s = 0; s < nscans; s++) {
+                descs[s].clean_bytes = u64(un[s].keeps) + tiles(un[s].nchunks);
+                descs[s].nmarkers = u64(un[s].marks) + tiles(un[s].nchunks);
+        }
+
+        const auto t_begin = std::chrono::steady_clock::now();
+        const uint8_t *raw = data;
+        hipError_t e = hipSuccess;
+        if(!data_on_device) {
+                e = hipMemcpyAsync(base + raw_at, data, nraw, hipMemcpyHostToDevice, stream);
+                raw = reinterpret_cast<const uint8_t *>(base + raw_at);
+        }
+        if(e == hipSuccess) { e = hipMemcpyAsync(base + descs_at, descs.data(), sizeof(ScanDesc) * nscans, hipMemcpyHostToDevice, stream); }
+        if(e == hipSuccess && p.ntables) { e = hipMemcpyAsync(base + pool_at, p.pool, sizeof(j2p_huff_decode) * p.ntables, hipMemcpyHostToDevice, stream); }
+        if(e == hipSuccess) { e = hipMemcpyAsync(base + iscan_at, iscan.data(), (size_t)nfirst * 2, hipMemcpyHostToDevice, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + clean_at, 0xff, clean_room, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + rst_at, 0, (size_t)nint * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + exit_at[0], 0, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + last_at, 0xff, (size_t)nbound * 8, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + done_at, 0, (size_t)nbound * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(base + diff_at, 0, (size_t)nblocks * 4, stream); }
+        if(e == hipSuccess) { e = hipMemsetAsync(flags, 0, 256, stream); }
+        for(unsigned c = 0; c < f.ncomp && e == hipSuccess; c++) { e = hipMemsetAsync(coef[c], 0, j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h), stream); }
+        if(e != hipSuccess) { return failed(e, "staging"); }
+        // every scan's clean stream and its restart markers' places
+        for(unsigned s = 0; s < nscans; s++) {
+                const Unstuff &u = un[s];
+                const uint8_t *const from = raw + u.raw_at;
+                hipLaunchKernelGGL(k_unstuff_count, dim3((u.nchunks + 3) / 4), dim3(256), 0, stream, from, u.nraw, u.nchunks, u32(u.keepc), u32(u.markc));
+                queue_scan(stream, u32(u.keepc), u.nchunks, u64(u.keeps), u64(u.keepo));
+                queue_scan(stream, u32(u.markc), u.nchunks, u64(u.marks), u64(u.marko));
+                hipLaunchKernelGGL(k_unstuff_copy, dim3((u.nchunks + 3) / 4), dim3(256), 0, stream, from, u.nraw, u.nchunks,
+                                   static_cast<const unsigned long long *>(u64(u.keepo)), static_cast<const unsigned long long *>(u64(u.marko)), descs[s].nint,
+                                   reinterpret_cast<uint8_t *>(base + clean_at + descs[s].clean_base), u.clean_room, u64(rst_at) + descs[s].rst_base, flags);
+        }
+        ScansBuffers b;
+        b.scans = reinterpret_cast<const ScanDesc *>(base + descs_at);
+        b.pool = reinterpret_cast<const j2p_huff_decode *>(base + pool_at);
+        b.words = u32(clean_at);
+        b.nwords = clean_room / 4;
+        b.rst = u64(rst_at);
+        b.iscan = reinterpret_cast<const unsigned short *>(base + iscan_at);
+        b.first = u64(first_at);
+        b.nsub = u64(isums_at) + tiles(nfirst);
+        b.nfirst = nfirst;
+        b.S = S;
+        b.error = flags;
+        hipLaunchKernelGGL(k_scans_intervals, dim3((nfirst + 255) / 256), dim3(256), 0, stream, b, u32(icount_at));
+        queue_scan(stream, u32(icount_at), nfirst, u64(isums_at), u64(first_at));
+        // the rounds of the first scans, all together
+        unsigned rounds = 0;
+        bool settled = false;
+        while(!settled) {
+                if(rounds > nbound) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: the decoder's states did not settle in %u rounds", rounds)); }
+                const unsigned group = rounds == 0 ? kDecodeFirstGroup : kDecodeGroup;
+                if(rounds) { (void)hipMemsetAsync(flags + 1, 0, group * 4, stream); }
+                for(unsigned q = 0; q < group; q++, rounds++) {
+                        hipLaunchKernelGGL(k_scans_sync, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound,
+                                           static_cast<const unsigned long long *>(u64(exit_at[rounds & 1])), u64(exit_at[(rounds + 1) & 1]), u64(last_at),
+                                           u32(done_at), flags + 1 + q);
+                }
+                unsigned seen[1 + kDecodeGroup] = {0};
+                unsigned long long total = 0;
+                e = hipMemcpyAsync(seen, flags, (1 + group) * 4, hipMemcpyDeviceToHost, stream);
+                if(e == hipSuccess) { e = hipMemcpyAsync(&total, b.nsub, 8, hipMemcpyDeviceToHost, stream); }
+                if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+                st.host_waits++;
+                if(e != hipSuccess) { return failed(e, "rounds"); }
+                if(seen[0]) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(seen[0]))); }
+                st.subsequences = (unsigned)total;
+                for(unsigned q = 0; q < group && !settled; q++) {
+                        if(seen[1 + q] == 0) {
+                                settled = true;
+                        } else {
+                                st.rounds++;
+                        }
+                }
+        }
+        const unsigned long long *const exits = u64(exit_at[rounds & 1]);
+        queue_scan(stream, u32(done_at), nbound, u64(dsums_at), u64(before_at));
+        ScansOut o;
+        memset(&o, 0, sizeof(o));
+        for(unsigned c = 0; c < f.ncomp; c++) { o.coef[c] = coef[c]; }
+        o.diff = u32(diff_at);
+        hipLaunchKernelGGL(k_scans_write, dim3((nbound + 255) / 256), dim3(256), 0, stream, b, nbound, exits, static_cast<const unsigned long long *>(u64(before_at)), o);
+        queue_scan(stream, u32(diff_at), nblocks, u64(dcsums_at), u64(dc_at));
+        for(unsigned s = 0; s < nscans; s++) {
+                if(descs[s].kind == kScanDcFirst) {
+                        hipLaunchKernelGGL(k_scans_dc, dim3((descs[s].nblocks + 255) / 256), dim3(256), 0, stream, b, s, static_cast<const unsigned *>(u32(diff_at)),
+                                           static_cast<const unsigned long long *>(u64(dc_at)), o);
+                }
+        }
+        // the refinement scans: a coefficient's come behind its first scan and in file order; DC and AC ones touch different coefficients
+        for(unsigned s = 0; s < nscans; s++) {
+                if(descs[s].kind == kScanDcRefine) { hipLaunchKernelGGL(k_scans_dc_refine, dim3((descs[s].nblocks + 255) / 256), dim3(256), 0, stream, b, s, o); }
+        }
+        if(st.ac_refine) {
+                e = hipEventCreate(&ev[0]);
+                if(e == hipSuccess) { e = hipEventCreate(&ev[1]); }
+                if(e == hipSuccess) { e = hipEventRecord(ev[0], stream); }
+                if(e != hipSuccess) { return failed(e, "events"); }
+                for(unsigned s = 0; s < nscans; s++) {
+                        if(descs[s].kind == kScanAcRefine) {
+                                hipLaunchKernelGGL(k_scans_ac_refine, dim3((descs[s].nint + 3) / 4), dim3(256), 0, stream, b, s, coef[descs[s].comp[0]]);
+                        }
+                }
+                e = hipEventRecord(ev[1], stream);
+                if(e != hipSuccess) { return failed(e, "events"); }
+        }
+        unsigned bad = 0;
+        e = hipGetLastError();
+        if(e == hipSuccess) { e = hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, stream); }
+        if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+        st.host_waits++;
+        if(e != hipSuccess) { return failed(e, "the final pass"); }
+        if(bad) { return finish(j2p_fail(J2P_EFORMAT, "jpeg: %s", decode_error_text(bad))); }
+        st.data_bytes = data_bytes;
+        st.decode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if(st.ac_refine) {
+                float ms = 0.f;
+                if(hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess && st.decode_ms > 0.) { st.ac_refine_share = (double)ms / st.decode_ms; }
+        }
+        if(stats) { *stats = st; }
+        return finish(J2P_OK);
+}
+
 int j2p_jpeg_open(const uint8_t *file, size_t size, j2p_jpeg_file *opened)
 {
         *opened = j2p_jpeg_file();
@@ -943,21 +1201,66 @@ int j2p_jpeg_open(const uint8_t *file, size_t size, j2p_jpeg_file *opened)
         return J2P_OK;
 }
 
-j2p_decoded_grids::j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats) : device_(device)
+int j2p_jpeg_open_scans(const uint8_t *file, size_t size, j2p_jpeg_file *opened)
 {
-        rc = decode(file, S, stats);
+        *opened = j2p_jpeg_file();
+        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        int where = -1;
+        const int kind = j2p_memory_of_pointer(file, &where);
+        if(kind == J2P_MEMORY_OTHER) { return j2p_fail(J2P_EINVAL, "jpeg: the file lies in managed or unknown memory (plain device memory, or host memory)"); }
+        std::unique_ptr<uint8_t[]> copy;
+        if(kind == J2P_MEMORY_DEVICE) {
+                copy.reset(new(std::nothrow) uint8_t[size]);
+                if(!copy) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+                if(const hipError_t e = hipMemcpy(copy.get(), file, size, hipMemcpyDeviceToHost); e != hipSuccess) {
+                        return j2p_fail(J2P_EDEVICE, "jpeg: reading the file: %s", hipGetErrorString(e));
+                }
+        }
+        std::unique_ptr<j2p_scans_parsed> scans(new(std::nothrow) j2p_scans_parsed);
+        if(!scans) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        if(const int rc = j2p_jpeg_parse_scans_full(copy ? copy.get() : file, size, scans.get()); rc != J2P_OK) { return rc; }
+        opened->scan = file + scans->base.info.scan_begin;
+        opened->scans = std::move(scans);
+        opened->on_device = kind == J2P_MEMORY_DEVICE;
+        opened->device = opened->on_device ? where : -1;
+        return J2P_OK;
 }
 
-int j2p_decoded_grids::decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats)
+// an opened file's decode into coef[] on `stream`: every scan of a progressive file, or the one scan of a sequential file
+int j2p_decode_opened(int device, hipStream_t stream, const j2p_jpeg_file &file, unsigned S, int16_t *const coef[3], j2p_decode_stats *stats,
+                      j2p_scans_stats *scans_stats)
 {
-        const j2p_jpeg_info &f = file.parsed->info;
+        if(!file.scans) { return j2p_decode_file(device, stream, file.parsed.get(), file.scan, file.on_device, S, coef, stats); }
+        if(file.scans->scans.progressive) { return j2p_decode_scans_file(device, stream, file.scans.get(), file.scan, file.on_device, S, coef, scans_stats); }
+        j2p_decode_stats one;
+        const int rc = j2p_decode_file(device, stream, &file.scans->base, file.scan, file.on_device, S, coef, &one);
+        if(rc == J2P_OK && scans_stats) {
+                memset(scans_stats, 0, sizeof(*scans_stats));
+                scans_stats->scans = 1;
+                scans_stats->subsequences = one.subsequences;
+                scans_stats->rounds = one.rounds;
+                scans_stats->data_bytes = one.data_bytes;
+                scans_stats->decode_ms = one.decode_ms;
+        }
+        return rc;
+}
+
+j2p_decoded_grids::j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats, j2p_scans_stats *scans_stats)
+    : device_(device)
+{
+        rc = decode(file, S, stats, scans_stats);
+}
+
+int j2p_decoded_grids::decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats, j2p_scans_stats *scans_stats)
+{
+        const j2p_jpeg_info &f = file.info();
         j2p_carve part;
         for(unsigned c = 0; c < f.ncomp; c++) { at[c] = part(j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h)); }
         bytes = part.total;
         HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         HIP_TRY(j2p_pool_take(device_, bytes, &block, &block_bytes_));
         for(unsigned c = 0; c < f.ncomp; c++) { coef[c] = reinterpret_cast<int16_t *>(static_cast<char *>(block) + at[c]); }
-        return j2p_decode_file(device_, stream_, file.parsed.get(), file.scan, file.on_device, S, coef, stats);
+        return j2p_decode_opened(device_, stream_, file, S, coef, stats, scans_stats);
 }
 
 j2p_decoded_grids::~j2p_decoded_grids()
@@ -992,6 +1295,39 @@ int j2p_entropy_decode_ex(int device, const uint8_t *file, size_t size, int16_t 
         const j2p_decoded_grids grids(device, opened, subsequence_bits, stats);
         if(grids.rc != J2P_OK) { return grids.rc; }
         // one staging copy down, so that nothing reaches the caller's arrays unless all of it does
+        const std::unique_ptr<char[]> staged(new(std::nothrow) char[grids.bytes]);
+        if(!staged) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
+        if(const hipError_t e = hipMemcpy(staged.get(), grids.block, grids.bytes, hipMemcpyDeviceToHost); e != hipSuccess) {
+                return j2p_fail(J2P_EDEVICE, "decode: %s", hipGetErrorString(e));
+        }
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                memcpy(coef_host[c], staged.get() + grids.at[c], j2p_grid_bytes(f.comp[c].blocks_w, f.comp[c].blocks_h));
+                if(quant) { memcpy(quant[c], f.comp[c].quant, sizeof(f.comp[c].quant)); }
+        }
+        if(info) { *info = f; }
+        return J2P_OK;
+}
+
+int j2p_entropy_decode_scans(int device, const uint8_t *file, size_t size, int16_t *const coef_host[3], uint16_t quant[3][64], j2p_jpeg_info *info,
+                             unsigned subsequence_bits, j2p_scans_stats *stats)
+{
+        if(!coef_host) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(subsequence_bits && (subsequence_bits < J2P_DECODE_SUBSEQUENCE_MIN || subsequence_bits > J2P_DECODE_SUBSEQUENCE_MAX)) {
+                return j2p_fail(J2P_EINVAL, "decode: %u bits in a subsequence (%u..%u)", subsequence_bits, J2P_DECODE_SUBSEQUENCE_MIN, J2P_DECODE_SUBSEQUENCE_MAX);
+        }
+        j2p_jpeg_file opened;
+        if(const int rc = j2p_jpeg_open_scans(file, size, &opened); rc != J2P_OK) { return rc; }
+        const j2p_jpeg_info &f = opened.info();
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                if(!coef_host[c]) { return j2p_fail(J2P_EINVAL, "decode: component %u has no room for its coefficients", c); }
+        }
+        if(const int rc = check_device(device); rc != J2P_OK) { return rc; }
+        if(opened.on_device && opened.device != device) {
+                return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the decode runs on %d", opened.device, device);
+        }
+        DeviceGuard guard(device);
+        const j2p_decoded_grids grids(device, opened, subsequence_bits, nullptr, stats);
+        if(grids.rc != J2P_OK) { return grids.rc; }
         const std::unique_ptr<char[]> staged(new(std::nothrow) char[grids.bytes]);
         if(!staged) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
         if(const hipError_t e = hipMemcpy(staged.get(), grids.block, grids.bytes, hipMemcpyDeviceToHost); e != hipSuccess) {

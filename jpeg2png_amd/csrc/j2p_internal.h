@@ -109,6 +109,17 @@ typedef struct j2p_jpeg_parsed {
 } j2p_jpeg_parsed;
 // the marker segments of `file`: J2P_OK, J2P_EFORMAT or J2P_ENOTSUP (include/jpeg2png_amd.h); touches no device
 int j2p_jpeg_parse_full(const uint8_t *file, size_t size, j2p_jpeg_parsed *out);
+// everything j2p_jpeg_parse_scans_full reads ("Reading a progressive JPEG file").  base: the frame, the quantisation tables and, for a
+// sequential file (scans.progressive == 0), the whole baseline parse.  pool: every Huffman table the file defines, in file order;
+// a scan's tables are the ones in force at its SOS: dc_table[s][c] for component c of a DC first scan, ac_table[s] for an AC scan.
+typedef struct j2p_scans_parsed {
+        j2p_jpeg_parsed base;
+        j2p_jpeg_scans scans;
+        unsigned ntables;
+        uint16_t dc_table[J2P_DECODE_SCANS_MAX][3], ac_table[J2P_DECODE_SCANS_MAX];
+        j2p_huff_decode pool[J2P_SCAN_TABLES_MAX];
+} j2p_scans_parsed;
+int j2p_jpeg_parse_scans_full(const uint8_t *file, size_t size, j2p_scans_parsed *out);
 
 // Iterations per device round trip WHEN SOMEBODY IS WATCHING (a progress bar, log rows: compute.c:428,449-452 tick once per
 // iteration, in real time).  A host sync per iteration would cost a small image most of its speed and a fixed chunk moves
@@ -243,17 +254,28 @@ int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, co
 // and where the caller's bytes are, which the decode reads in place.
 struct j2p_jpeg_file {
         std::unique_ptr<j2p_jpeg_parsed> parsed;
+        std::unique_ptr<j2p_scans_parsed> scans;        // j2p_jpeg_open_scans: every scan; info() is then scans->base.info
+        const j2p_jpeg_info &info() const { return scans ? scans->base.info : parsed->info; }
         const uint8_t *scan = nullptr;  // the caller's bytes from info.scan_begin on
         bool on_device = false;         // ... which are plain device memory
         int device = -1;                // ... of this device (-1: host memory)
 };
 // J2P_EINVAL (NULL or empty; managed or unknown memory), J2P_ENOMEM, J2P_EDEVICE (the copy), or what j2p_jpeg_parse_full says
 int j2p_jpeg_open(const uint8_t *file, size_t size, j2p_jpeg_file *opened);
+// ... through the scans parser: scans is set, and parsed too for a sequential file (then j2p_decode_file decodes it)
+int j2p_jpeg_open_scans(const uint8_t *file, size_t size, j2p_jpeg_file *opened);
 // parsed's scan, whose bytes begin at `data` (host memory, or device memory of `device` read in place), decoded into the device
 // grids coef[c] (blocks_w * blocks_h * 64 int16) on `stream`; waits for the stream.  S: bits per subsequence, 0 the default.
 // The calling thread's device is `device`.  J2P_EFORMAT: the grids hold nothing of use.
 int j2p_decode_file(int device, hipStream_t stream, const j2p_jpeg_parsed *parsed, const uint8_t *data, bool data_on_device, unsigned S,
                     int16_t *const coef[3], j2p_decode_stats *stats);
+struct j2p_jpeg_file;
+// an opened file's decode, whichever way it was opened (scans_stats: what a file opened by j2p_jpeg_open_scans fills; both may be NULL)
+int j2p_decode_opened(int device, hipStream_t stream, const j2p_jpeg_file &file, unsigned S, int16_t *const coef[3], j2p_decode_stats *stats,
+                      j2p_scans_stats *scans_stats);
+// every scan of a progressive file (p->scans.progressive), whose bytes from info.scan_begin on are `data`: j2p_decode_file's contract
+int j2p_decode_scans_file(int device, hipStream_t stream, const j2p_scans_parsed *p, const uint8_t *data, bool data_on_device, unsigned S,
+                          int16_t *const coef[3], j2p_scans_stats *stats);
 // The component grids of an opened file in one pooled block of `device` (the calling thread's), each at a 256-byte step, on a
 // stream of their own: construction decodes (j2p_decode_file), `rc` is what came of it, and only after J2P_OK do the grids hold
 // anything.  Destruction waits for the stream, destroys it and gives the block back.
@@ -263,7 +285,7 @@ struct j2p_decoded_grids {
         size_t at[3] = {0, 0, 0};       // coef[c] is the block + at[c]
         void *block = nullptr;
         size_t bytes = 0;               // the block's first bytes, which hold the grids
-        j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats);
+        j2p_decoded_grids(int device, const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats, j2p_scans_stats *scans_stats = nullptr);
         ~j2p_decoded_grids();
         j2p_decoded_grids(const j2p_decoded_grids &) = delete;
         j2p_decoded_grids &operator=(const j2p_decoded_grids &) = delete;
@@ -272,7 +294,7 @@ private:
         int device_;
         hipStream_t stream_ = nullptr;
         size_t block_bytes_ = 0;
-        int decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats);
+        int decode(const j2p_jpeg_file &file, unsigned S, j2p_decode_stats *stats, j2p_scans_stats *scans_stats);
 };
 
 // a whole-canvas solver whose coefficients a decode has left in device memory of `device` (decoded[c]: channel c's grid,

@@ -1221,6 +1221,7 @@ struct FileSource {
         const uint8_t *data;
         bool on_device;
         const int16_t *decoded[3];
+        const j2p_jpeg_file *opened = nullptr;          // parsed == NULL too: a file opened by j2p_jpeg_open_scans, decoded by j2p_decode_opened
 };
 
 // j2p_solver_create, and — samples != NULL — j2p_solver_create_from_samples, and — file != NULL — j2p_solver_create_from_jpeg:
@@ -1285,7 +1286,9 @@ static int create_solver(j2p_solver **out, int device, void *stream, unsigned nc
                 // (a whole canvas: every channel's resident buffer is its component's whole grid)
                 int16_t *grids[3] = {nullptr, nullptr, nullptr};
                 for(unsigned c = 0; c < nchannel; c++) { grids[c] = s->ch[c].d; }
-                if(file->parsed) {
+                if(file->opened) {
+                        rc = j2p_decode_opened(device, s->stream, *file->opened, 0, grids, nullptr, nullptr);
+                } else if(file->parsed) {
                         rc = j2p_decode_file(device, s->stream, file->parsed, file->data, file->on_device, 0, grids, nullptr);
                 } else {
                         for(unsigned c = 0; c < nchannel; c++) {
@@ -1340,6 +1343,34 @@ int j2p_solver_create_from_jpeg(j2p_solver **out, int device, void *stream, cons
                 planes[c].quant_table = f.comp[c].quant;
         }
         const FileSource source = {opened.parsed.get(), opened.scan, opened.on_device, {nullptr, nullptr, nullptr}};
+        const j2p_band whole = {0, 0};
+        const int rc = create_solver(out, device, stream, f.ncomp, planes, nullptr, &source, weight, pweight, iterations, whole, 0);
+        if(rc == J2P_OK && info) { *info = f; }
+        return rc;
+}
+
+int j2p_solver_create_from_jpeg_scans(j2p_solver **out, int device, void *stream, const uint8_t *file, size_t size, float weight,
+                                      const float pweight[], unsigned iterations, j2p_jpeg_info *info)
+{
+        if(out) { *out = nullptr; }
+        if(!out || !pweight) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        j2p_jpeg_file opened;
+        if(const int rc = j2p_jpeg_open_scans(file, size, &opened); rc != J2P_OK) { return rc; }
+        if(opened.on_device && opened.device != device) {
+                return j2p_fail(J2P_EINVAL, "jpeg: the file lies on device %d, the solver on %d", opened.device, device);
+        }
+        const j2p_jpeg_info &f = opened.info();
+        j2p_plane planes[3];
+        memset(planes, 0, sizeof(planes));
+        for(unsigned c = 0; c < f.ncomp; c++) {
+                planes[c].w = f.comp[c].blocks_w * 8;
+                planes[c].h = f.comp[c].blocks_h * 8;
+                planes[c].w_samp = f.comp[c].w_samp;
+                planes[c].h_samp = f.comp[c].h_samp;
+                planes[c].quant_table = f.comp[c].quant;
+        }
+        FileSource source = {nullptr, opened.scan, opened.on_device, {nullptr, nullptr, nullptr}};
+        source.opened = &opened;
         const j2p_band whole = {0, 0};
         const int rc = create_solver(out, device, stream, f.ncomp, planes, nullptr, &source, weight, pweight, iterations, whole, 0);
         if(rc == J2P_OK && info) { *info = f; }
