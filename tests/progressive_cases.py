@@ -57,6 +57,20 @@ def _dc_refine(zz, width, height, sub, al, ops):
         ops.append(("b", v & 1, 1))
 
 
+def dc_slice(values, ah, ops):
+    """one restart interval of a DC scan (tests/scan_decode_cases.py writes files with restarts): values, [(component, DC >> Al)]
+    of its positions in scan order, coded as _dc_first and _dc_refine code a whole scan; the predictors start at 0"""
+    pred = [0, 0, 0]
+    for c, v in values:
+        if ah:
+            ops.append(("b", v & 1, 1))
+        else:
+            d, pred[c] = v - pred[c], v
+            s = abs(d).bit_length()
+            ops.append(("s", ("dc", 0 if c == 0 else 1), s))
+            _magnitude(ops, d, s)
+
+
 class _Run:
     """the pending EOB run of an AC scan: its length and, in refinement scans, the correction bits that wait with it"""
 

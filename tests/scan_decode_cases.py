@@ -8,7 +8,11 @@ se, ah, al, dc_slots, ac_slots, restart_interval, intervals, begin, end and the 
 Refused files raise decode_cases.Refused with .code and .why.
 
 write(coefficients, width, height, quant, sub, script) -> the file of that script: a list of (components, Ss, Se, Ah, Al); a DC
-scan names all components (interleaved) or one.  Every scan brings the tables made for it."""
+scan names all components (interleaved) or one.  Every scan brings the tables made for it.  restart=, dri= and fill= give the file
+restart intervals, per scan if wanted, and fill bytes in front of a scan's markers.
+
+edge_cases() are the good files aimed at where the kernels divide their work and at what a restart interval ends;
+damaged_cases() the files to refuse, each with the restatement's reason."""
 import numpy as np
 
 import decode_cases as dc
@@ -376,23 +380,59 @@ STOPS_AT_1 = {1: [((0,), 0, 0, 0, 1), ((0,), 1, 63, 0, 2), ((0,), 1, 63, 2, 1)],
               3: [((0, 1, 2), 0, 0, 0, 1)] + [((c,), 1, 63, 0, 2) for c in range(3)] + [((c,), 1, 63, 2, 1) for c in range(3)]}
 
 
-def _dc_alone(plane, c, ah, al, ops):
-    """a DC scan of one component of several: its own grid in raster order, no padding blocks"""
-    pred = 0
-    for row in plane:
-        for block in row:
-            v = block[0] >> al
+def _scan_units(zz, width, height, sub, comps):
+    """per unit of a scan (an MCU of an interleaved scan, a block of the own grid of a one-component scan): [(component, block in
+    zigzag order, None for a block that pads the grid out to whole MCUs)]"""
+    if len(comps) == 1:
+        return [[(comps[0], block)] for row in zz[comps[0]] for block in row]
+    order = ec.scan_order(width, height, len(zz), sub)
+    per = sub[0] * sub[1] + 2
+    return [[(c, None if y is None else zz[c][y][x]) for c, y, x in order[at:at + per]] for at in range(0, len(order), per)]
+
+
+def scan_intervals(zz, width, height, sub, scan, ri=0):
+    """[(operations, EOB runs as (first block of the scan, length, why), ZRLs)] per restart interval of one scan: ri of the scan's
+    units each (0: one interval).  Every interval is walked on its own by the coder's restatement, so the pending EOB run is
+    flushed with its waiting correction bits and the DC predictors start at 0; a padding block repeats its predecessor's DC"""
+    comps, ss, se, ah, al = scan
+    units = _scan_units(zz, width, height, sub, comps)
+    ri = ri if 0 < ri < len(units) else len(units)
+    values, last = [], [0, 0, 0]
+    if ss == 0:
+        for unit in units:
+            row = []
+            for c, block in unit:
+                if block is not None:
+                    last[c] = block[0]
+                row.append((c, last[c] >> al))
+            values.append(row)
+    out = []
+    for first in range(0, len(units), ri):
+        ops, runs, zrls = [], [], 0
+        if ss == 0:
+            pc.dc_slice([v for row in values[first:first + ri] for v in row], ah, ops)
+        else:
+            blocks = [unit[0][1] for unit in units[first:first + ri]]
+            table = ("ac", min(comps[0], 1))
             if ah:
-                ops.append(("b", v & 1, 1))
+                zrls = pc._ac_refine(blocks, table, ss, se, al, ops, runs)
             else:
-                d, pred = v - pred, v
-                s = abs(d).bit_length()
-                ops.append(("s", ("dc", min(c, 1)), s))
-                pc._magnitude(ops, d, s)
+                pc._ac_first(blocks, table, ss, se, al, ops, runs)
+        out.append((ops, [(first + b, n, why) for b, n, why in runs], zrls))
+    return out
 
 
-def write(coefficients, width, height, quant, sub=(1, 1), script=None, mutate=None):
-    """mutate(scan index, operations) -> operations: what damaged_cases() spoil a scan with"""
+def write(coefficients, width, height, quant, sub=(1, 1), script=None, mutate=None, restart=None, dri=None, fill=None, report=None):
+    """restart = n: one DRI segment of n in front of the first SOS; dri = {scan index: n}: one in front of that scan's tables and
+    SOS (0 turns restarts off from there on).  The interval counts the scan's own units (scan_intervals); behind each but the last
+    the stream is padded with ones to a byte and RSTn follows, n counted modulo 8.
+    fill = {scan index: {"targets": [...], "fixed": {m: n}}}: FF fill bytes in front of that scan's restart markers, as
+    decode_cases.place_markers puts them: targets[m] (None, or no entry: none) is what the offset of marker m's Dn byte, counted
+    from the scan's begin, is congruent to modulo 256; fixed[m] is a number of fill bytes.
+    mutate(index, operations) -> operations: what damaged_cases() spoil a scan with; where a restart interval is in force the scan
+    is given interval by interval, and index is (scan index, interval).
+    report (a list) receives per scan {"scan", "restart_interval", "intervals": [{"runs", "zrls", "operations", "bits", "bytes"}]}:
+    what scan_intervals gave (after mutate), the interval's bits before padding and its bytes after stuffing"""
     ncomp = len(coefficients)
     sub = sub if ncomp == 3 else (1, 1)
     script = pc.SCANS[ncomp] if script is None else script
@@ -400,38 +440,59 @@ def write(coefficients, width, height, quant, sub=(1, 1), script=None, mutate=No
     plain = ec.header(width, height, ncomp, sub, quant)
     sof, dht = plain.index(b"\xff\xc0"), plain.index(b"\xff\xc4")
     file = bytearray(plain[:sof] + b"\xff\xc2" + plain[sof + 2:dht])
+    changes = dict(dri or {})
+    if restart:
+        changes[0] = restart
+    ri = 0
     for index, scan in enumerate(script):
-        comps, ss, _se, ah, al = scan
-        if ss == 0 and len(comps) == 1 and ncomp == 3:
-            ops = []
-            _dc_alone(zz[comps[0]], comps[0], ah, al, ops)
-        else:
-            ops, _runs, _zrls = pc.scan_walk(zz, width, height, sub, scan)
+        if index in changes:
+            ri = changes[index]
+            file += ec._segment(0xdd, bytes([ri >> 8, ri & 255]))
+        intervals = scan_intervals(zz, width, height, sub, scan, ri)
         if mutate is not None:
-            ops = mutate(index, ops)
+            intervals = [(mutate((index, k) if ri else index, ops), runs, zrls) for k, (ops, runs, zrls) in enumerate(intervals)]
         counts = {}
-        for op in ops:
-            if op[0] == "s":
-                counts.setdefault(op[1], [0] * 256)[op[2]] += 1
+        for ops, _runs, _zrls in intervals:
+            for op in ops:
+                if op[0] == "s":
+                    counts.setdefault(op[1], [0] * 256)[op[2]] += 1
         codes = {}
         for t, count in counts.items():
             bits, vals, _longest = hc.table(count)
             file += ec._segment(0xc4, bytes([((t[0] == "ac") << 4) | t[1]]) + bytes(bits) + bytes(vals))
             codes[t] = ec._codes(bits, vals)
-        out = ec._Bits()
-        for op in ops:
-            if op[0] == "s":
-                out.put(*codes[op[1]][op[2]])
-            else:
-                out.put(op[1], op[2])
-        short = -out.n % 8
-        out.put((1 << short) - 1, short)
-        file += pc._sos(scan) + bytes(out.data).replace(b"\xff", b"\xff\x00")
+        file += pc._sos(scan)
+        places = (fill or {}).get(index, {})
+        targets, fixed = places.get("targets", ()), places.get("fixed", {})
+        data, told = bytearray(), []
+        for k, (ops, runs, zrls) in enumerate(intervals):
+            if k:
+                m = k - 1
+                if m in fixed:
+                    data += b"\xff" * fixed[m]
+                elif m < len(targets) and targets[m] is not None:
+                    data += b"\xff" * ((targets[m] - (len(data) + 1)) % 256)
+                data += bytes([0xff, 0xd0 + m % 8])
+            out = ec._Bits()
+            for op in ops:
+                if op[0] == "s":
+                    out.put(*codes[op[1]][op[2]])
+                else:
+                    out.put(op[1], op[2])
+            nbits = out.n
+            short = -out.n % 8
+            out.put((1 << short) - 1, short)
+            chunk = bytes(out.data).replace(b"\xff", b"\xff\x00")
+            data += chunk
+            told.append({"runs": runs, "zrls": zrls, "operations": ops, "bits": nbits, "bytes": len(chunk)})
+        file += data
+        if report is not None:
+            report.append({"scan": scan, "restart_interval": ri, "intervals": told})
     return bytes(file + b"\xff\xd9")
 
 
-def write_case(case, script=None, mutate=None):
-    return write(case["coefficients"], case["width"], case["height"], case["quant"], case["sub"], script, mutate)
+def write_case(case, script=None, mutate=None, **kw):
+    return write(case["coefficients"], case["width"], case["height"], case["quant"], case["sub"], script, mutate, **kw)
 
 
 # ---- the cases ----
@@ -502,6 +563,181 @@ def written_cases():
             for name, (case, script) in plans.items()}
 
 
+# ---- files of one scan's data taken apart: where the unstuffing kernels lay their chunks and lanes from the scan's own begin ----
+def scan_chunks(data, index):
+    """the entropy-coded data of scan `index`, still stuffed, cut at its RSTn markers (a file without fill bytes)"""
+    s = parse_scans(data)["scans"][index]
+    ecs, out, cur, i = data[s["begin"]:s["end"]], [], bytearray(), 0
+    while i < len(ecs):
+        if ecs[i] == 0xFF and 0xD0 <= ecs[i + 1] <= 0xD7:
+            out.append(bytes(cur))
+            cur = bytearray()
+        else:
+            cur += ecs[i:i + 2] if ecs[i] == 0xFF else ecs[i:i + 1]
+        i += 2 if ecs[i] == 0xFF else 1
+    return out + [bytes(cur)]
+
+
+def with_chunks(data, index, chunks):
+    """the file with scan `index`'s data replaced by these chunks, RSTn between them numbered in sequence"""
+    s = parse_scans(data)["scans"][index]
+    return data[:s["begin"]] + b"".join((bytes([0xff, 0xd0 + (k - 1) % 8]) if k else b"") + c for k, c in enumerate(chunks)) + data[s["end"]:]
+
+
+def scan_marker_offsets(data, index):
+    """decode_cases.marker_offsets of one scan: the offset, counted from the scan's begin, of the Dn byte of each of its RSTn"""
+    s = parse_scans(data)["scans"][index]
+    out, i = [], s["begin"]
+    while i < s["end"]:
+        if data[i] != 0xFF:
+            i += 1
+        elif data[i + 1] == 0:
+            i += 2
+        elif 0xD0 <= data[i + 1] <= 0xD7:
+            out.append(i + 1 - s["begin"])
+            i += 2
+        else:
+            i += 1                       # a fill byte
+    return out
+
+
+def scan_stuffed_on_chunk_edge(data, index):
+    """decode_cases.stuffed_on_chunk_edge of one scan"""
+    s = parse_scans(data)["scans"][index]
+    ecs = data[s["begin"]:s["end"]]
+    return [i for i in range(255, len(ecs) - 1, 256) if ecs[i] == 0xFF and ecs[i + 1] == 0]
+
+
+def scan_blank_chunks(data, index):
+    """decode_cases.blank_chunks of one scan"""
+    s = parse_scans(data)["scans"][index]
+    ecs = data[s["begin"]:s["end"]]
+    return [c for c in range(len(ecs) // 256) if ecs[256 * c:256 * c + 256] == b"\xff" * 256]
+
+
+# ---- good files aimed at where the kernels divide their work, and at what a restart interval ends ----
+SPLIT = [((0,), 0, 0, 0, 1), ((0,), 1, 5, 0, 1), ((0,), 6, 63, 0, 1), ((0,), 0, 0, 1, 0), ((0,), 1, 5, 1, 0), ((0,), 6, 63, 1, 0)]
+FROM_13 = [((0,), 0, 0, 0, 13), ((0,), 1, 63, 0, 13)] + [s for al in range(12, -1, -1) for s in (((0,), 0, 0, al + 1, al), ((0,), 1, 63, al + 1, al))]
+MOD4_RESTARTS = {1: 4, 2: 10, 3: 7}     # 18 blocks: 5 intervals (the last of 2 blocks), 2 (8), 3 (4)
+DIRECTED_KINDS = "BACBAB"               # the kinds of directed_case()'s intervals of four blocks; the last has two
+EDGE_SCANS = (1, 5)                     # of progressive_cases.SCANS[3]: luma's first AC scan (1..5) and its AC refinement scan (Al 2 to 1)
+
+
+def directed_case():
+    """grey 176x8: 22 blocks, with restart=4 five intervals of four blocks and one of two, written with SPLIT (the AC band in two,
+    first at Al 1, then refined).  In the band 6..63 (zigzag positions; c: 4..7 with either sign, which is new in the first scan
+    and a correction bit in the refinement scan) the four blocks of an interval of kind
+      A: c at 6 | 1 at 10 | nothing | nothing: the first scan ends in an EOB run of 4, the refinement scan in one of 3
+      B: c at 6 | c at 7 and 12..19 | c at 8 | nothing: the first scan ends in a run of 2, the refinement scan is ONE run of 4 that
+         carries 11 waiting correction bits of three blocks
+      C: as B, but the first and the last block hold c at 6 and 1 at 63: the first scan ends in a run of 1, the refinement scan
+         begins with three ZRLs and the interval's rarest symbol, flushes a run of 2 with ten waiting bits and ends in no run at all
+    In the band 1..5 every block holds 3 at 1 and -2 at 2, but blocks 8 and 9, the first of the middle interval: block 8 holds 1 at
+    5 alone (the refinement scan codes it as run 4, size 1: no position is left behind it), block 9 holds c at 5 alone (the first
+    scan codes it as run 4, size 2)"""
+    case = ec.make(176, 8, 1, (1, 1), "zero")
+    rng = np.random.default_rng(26)
+
+    def c():
+        return int(rng.integers(4, 8)) * (1 if rng.random() < 0.5 else -1)
+    for k, kind in enumerate(DIRECTED_KINDS):
+        blocks = [{6: c(), 63: 1} if kind == "C" else {6: c()}, {10: 1} if kind == "A" else {p: c() for p in (7, 12, 13, 14, 15, 16, 17, 18, 19)}, {} if kind == "A" else {8: c()},
+                  {6: c(), 63: 1} if kind == "C" else {}]
+        for i, values in enumerate(blocks[:22 - 4 * k]):
+            b = 4 * k + i
+            values.update({5: 1} if b == 8 else {5: c()} if b == 9 else {1: 3, 2: -2})
+            values[0] = 2 * int(rng.integers(-100, 100)) + (b % 3 == 0)        # (its last bit: no byte of a DC refinement scan is FF)
+            pc._put(case, b, values)
+    return case
+
+
+def _dc_scan_file(diffs, al):
+    """a grey file of len(diffs) blocks in a row and one scan, DC at Al = al, that codes these differences whatever their sum is (in
+    the manner of decode_cases._dc_file) -> (file, the DC values << al)"""
+    def ops_of(_index, _ops):
+        ops = []
+        for d in diffs:
+            s = abs(d).bit_length()
+            ops.append(("s", ("dc", 0), s))
+            pc._magnitude(ops, d, s)
+        return ops
+    zero = ec.make(8 * len(diffs), 8, 1, (1, 1), "zero")
+    return write_case(zero, [((0,), 0, 0, 0, al)], ops_of), np.cumsum(diffs) * (1 << al)
+
+
+DC_LIMIT_DIFFS = {0: [16383, 16383, 1, -16383, -16383, -16383, -16383, -3], 1: [8191, 8191, 1, -8191, -8191, -8191, -8191, -3]}
+
+
+def _from_13_case():
+    """grey 16x8: both signs of the int16 range with |v| >> 13 <= 3, values that appear at every Al from 13 down, and a 1 at 63"""
+    case = ec.make(16, 8, 1, (1, 1), "zero")
+    pc._put(case, 0, {0: 32767, 1: 32767, 2: -32767, 3: 8192, 4: -8192, 5: -8191, 9: 16384, 10: -24575, 62: 21845, 63: 1})
+    pc._put(case, 1, {0: -32768, 1: -32767, 2: 32767, 63: -10923})
+    for al in range(13):
+        pc._put(case, 1, {20 + 2 * al: (1 << al) * (-1) ** al, 21 + 2 * al: (3 << al) - 1})
+    return case
+
+
+def _edges_colour_case():
+    """(case, file, fills): 24 MCUs of dense 4:4:4 written with restart=1, the markers of the scans EDGE_SCANS moved onto
+    decode_cases.EDGE_TARGETS counted from their own scan's begin; the seed is the first for which a stuffed FF | 00 then lies across a
+    chunk edge of a scan that is not the file's first"""
+    targets = [dc.EDGE_TARGETS[m % 6] for m in range(23)]
+    fills = {index: {"targets": targets} for index in EDGE_SCANS}
+    for seed in range(1, 400):
+        case = ec.make(48, 32, 3, (1, 1), "dense", seed=seed, quality=95)
+        data = write_case(case, restart=1, fill=fills)
+        if any(scan_stuffed_on_chunk_edge(data, index) for index in range(1, len(pc.SCANS[3]))):
+            return case, data, fills
+    raise AssertionError("no seed puts a stuffed FF on a chunk edge of a later scan")
+
+
+def edge_cases():
+    """{name: (file, the coefficients it must decode to, or None where only the restatement says)}"""
+    if "edge" in _cache:
+        return _cache["edge"]
+    out = {}
+
+    def add(name, case, script, **kw):
+        out[name] = (write_case(case, script, **kw), _stopped(case, script if script is not None else pc.SCANS[len(case["coefficients"])]))
+    grey = ec.make(41, 23, 1, (1, 1), "sparse", seed=11)
+    c420 = ec.make(41, 23, 3, (2, 2), "sparse", seed=12)
+    c422 = ec.make(40, 24, 3, (2, 1), "dense", seed=13)
+    c444 = ec.make(24, 16, 3, (1, 1), "sparse", seed=14)
+    dummy = ec.make(17, 9, 3, (2, 2), "dense", seed=15)
+    wide = ec.make(2056, 8, 1, (1, 1), "sparse", seed=41)
+    add("intervals_257_grey", wide, SPECTRAL[1], restart=1)
+    add("refine_257_grey", wide, REFINE_3[1], restart=1)
+    for residue, restart in MOD4_RESTARTS.items():
+        add(f"refine_intervals_mod4_{residue}", grey, REFINE_3[1], restart=restart)
+    add("refine_3_422_rst", c422, REFINE_3[3], restart=3)
+    add("dc_alone_420_rst", c420, DC_ALONE[3], restart=2)
+    add("stops_at_1_444_rst", c444, STOPS_AT_1[3], restart=3)
+    add("dummy_blocks_17x9_rst", dummy, None, restart=2)
+    add("dri_between_grids_420", c420, None, restart=8)
+    add("dri_changes", c420, None, dri={0: 2, 1: 5, 7: 0})
+    add("eob_run_ends_each_interval", directed_case(), SPLIT, restart=4)
+    case, data, fills = _edges_colour_case()
+    out["markers_on_edges_scan_k"] = (data, _stopped(case, pc.SCANS[3]))
+    # 600 fill bytes cover two whole chunks when they begin in a chunk's first 89 bytes: the first marker of the middle for which they do
+    filled = [write_case(case, restart=1, fill={EDGE_SCANS[1]: {"fixed": {m: 600}}}) for m in range(4, 20)]
+    filled = [f for f in filled if len(scan_blank_chunks(f, EDGE_SCANS[1])) == 2]
+    if not filled:
+        raise AssertionError("no marker of the refinement scan begins 600 fill bytes in a chunk's first 89 bytes")
+    out["fill_covers_chunks_scan_k"] = (filled[0], _stopped(case, pc.SCANS[3]))
+    add("refine_from_13", _from_13_case(), FROM_13)
+    for al, diffs in DC_LIMIT_DIFFS.items():
+        data, values = _dc_scan_file(diffs, al)
+        want = np.zeros((1, len(diffs), 64), np.int16)
+        want[0, :, 0] = values
+        out[f"dc_near_limit_al{al}"] = (data, [want])
+    three = ec.make(24, 8, 1, (1, 1), "zero")
+    three["coefficients"][0][0, :, 0] = 30000
+    add("dc_reset_by_restart", three, SPECTRAL[1], restart=1)
+    _cache["edge"] = out
+    return out
+
+
 _cache = {}
 
 
@@ -511,6 +747,7 @@ def good_files():
         out = dict(pil_files())
         out.update({f"coder_{name}": pc.encode_case(case)[0] for name, case in pc.gpu_cases().items()})
         out.update({f"written_{name}": data for name, (data, _want) in written_cases().items()})
+        out.update({f"edge_{name}": data for name, (data, _want) in edge_cases().items()})
         _cache["files"] = out
     return _cache["files"]
 
@@ -596,4 +833,99 @@ def damaged_cases():
     at = pil.index(b"\xff\xd1", ac["begin"], ac["end"])
     out["restart_out_of_sequence"] = (pil[:at + 1] + b"\xd2" + pil[at + 2:], ("restart",))
     out["byte_behind_dc_refinement"] = (good[:scans[4]["end"]] + b"\x55" + good[scans[4]["end"]:], ("leftover",))
+    out.update(_damaged_in_one_kernel())
     return out
+
+
+def _symbol_at(ops, pick):
+    """the index of the last operation that is a symbol for which pick(symbol) holds"""
+    return max(i for i, op in enumerate(ops) if op[0] == "s" and pick(op[2]))
+
+
+def _run_one_longer(where):
+    """mutate: in the scan and interval `where`, the last EOBn symbol's extra bits count one block more (the symbol stays: the run
+    is no power of two less one)"""
+    def mutate(index, ops):
+        ops = list(ops)
+        if index == where:
+            at = _symbol_at(ops, lambda rs: rs & 15 == 0 and 1 <= rs >> 4 < 15)
+            _b, value, length = ops[at + 1]
+            assert length == ops[at][2] >> 4 and value + 1 < 1 << length, ops[at:at + 2]
+            ops[at + 1] = ("b", value + 1, length)
+        return ops
+    return mutate
+
+
+def _symbol_swapped(where, old, new, drop_bits):
+    """mutate: in the scan and interval `where` the one symbol `old` becomes `new`; drop_bits: and loses the bits behind it"""
+    def mutate(index, ops):
+        ops = list(ops)
+        if index == where:
+            at = [i for i, op in enumerate(ops) if op[0] == "s" and op[2] == old]
+            assert len(at) == 1, (where, old, at)
+            ops[at[0]] = ("s", ops[at[0]][1], new)
+            if drop_bits:
+                assert ops[at[0] + 1][0] == "b"
+                del ops[at[0] + 1]
+        return ops
+    return mutate
+
+
+# of directed_case() written with SPLIT and restart=4: the scans, and the intervals that are neither a scan's first nor its last
+_DC_REFINE, _AC_REFINE_LOW, _AC_FIRST_LOW, _AC_FIRST, _AC_REFINE = 3, 4, 1, 2, 5
+_KIND_A, _KIND_C, _KIND_B = 1, 2, 3
+
+
+def _damaged_in_one_kernel():
+    """{name: (file, (why,))}: files that both parsers accept and that have ONE fault, which one kernel alone can see (the name of
+    the kernel in front): everything else in them is whole, and the faults sit in a middle interval of a scan with restarts"""
+    out = {}
+    # k_scans_dc: the neighbours of dc_near_limit_al0 and _al1, one step over
+    for al, diffs in DC_LIMIT_DIFFS.items():
+        out[f"dc_above_int16_al{al}"] = (_dc_scan_file(diffs[:2] + [2] + diffs[3:], al)[0], ("dc",))
+        out[f"dc_below_int16_al{al}"] = (_dc_scan_file(diffs[:-1] + [-4], al)[0], ("dc",))
+    case = directed_case()
+    good = write_case(case, SPLIT, restart=4)
+    # k_scans_dc_refine: 12 and 10 blocks an interval are two bytes each; the first gives its second byte to the next
+    twelve = write_case(case, SPLIT, restart=12)
+    a, b = scan_chunks(twelve, _DC_REFINE)
+    assert len(a) == len(b) == 2 and 0xFF not in a + b
+    out["dc_refine_interval_short_next_long"] = (with_chunks(twelve, _DC_REFINE, [a[:1], a[1:] + b]), ("truncated",))
+    chunks = scan_chunks(good, _DC_REFINE)
+    assert len(chunks) == 6
+    # (the short interval alone would show only one direction of the length check: here an interval is a byte long and none is short)
+    out["dc_refine_byte_behind_interval"] = (with_chunks(good, _DC_REFINE, chunks[:2] + [chunks[2] + b"\x55"] + chunks[3:]), ("leftover",))
+    out["dc_refine_rst_removed"] = (with_chunks(good, _DC_REFINE, chunks[:2] + [chunks[2] + chunks[3]] + chunks[4:]), ("restart",))
+    at = parse_scans(good)["scans"][_DC_REFINE]["begin"] + scan_marker_offsets(good, _DC_REFINE)[2]
+    assert good[at] == 0xD2
+    out["dc_refine_rst_renumbered"] = (good[:at] + b"\xd5" + good[at + 1:], ("restart",))
+    # k_scans_ac_refine and scans_symbols: symbols and extra bits changed where the writer codes them
+    out["eob_run_crosses_restart_refine"] = (write_case(case, SPLIT, _run_one_longer((_AC_REFINE, _KIND_B)), restart=4), ("eobrun",))
+    out["eob_run_crosses_restart_first"] = (write_case(case, SPLIT, _run_one_longer((_AC_FIRST, _KIND_A)), restart=4), ("eobrun",))
+    out["refine_run_past_band"] = (write_case(case, SPLIT, _symbol_swapped((_AC_REFINE_LOW, _KIND_C), 0x41, 0x51, False), restart=4), ("run",))
+    out["refine_zrl_past_band"] = (write_case(case, SPLIT, _symbol_swapped((_AC_REFINE_LOW, _KIND_C), 0x41, 0xf0, True), restart=4), ("run",))
+    out["first_zrl_past_band"] = (write_case(case, SPLIT, _symbol_swapped((_AC_FIRST_LOW, _KIND_C), 0x42, 0xf0, True), restart=4), ("run",))
+    # k_scans_ac_refine: the bytes of interval 3, one EOB4 symbol, its two extra bits and 11 correction bits
+    chunks = scan_chunks(good, _AC_REFINE)
+    k = _KIND_B
+    assert len(chunks) == 6 and len(chunks[k]) == 2 and 0xFF not in chunks[k]
+    out["refine_byte_behind_interval"] = (with_chunks(good, _AC_REFINE, chunks[:k] + [chunks[k] + b"\x55"] + chunks[k + 1:]), ("leftover",))
+    out["refine_interval_cut_short"] = (with_chunks(good, _AC_REFINE, chunks[:k] + [chunks[k][:-1]] + chunks[k + 1:]), ("truncated",))
+    out["refine_rst_removed"] = (with_chunks(good, _AC_REFINE, chunks[:k] + [chunks[k] + chunks[k + 1]] + chunks[k + 2:]), ("restart",))
+    out["refine_rst_doubled"] = (with_chunks(good, _AC_REFINE, chunks[:k] + [b""] + chunks[k:]), ("restart",))
+    # a bit flip in a middle interval that leads to a prefix in no table, found by search against the restatement
+    for k in (3, 2, 1, 4):
+        begin = parse_scans(good)["scans"][_AC_REFINE]["begin"] + sum(len(c) + 2 for c in chunks[:k])
+        assert good[begin:begin + len(chunks[k])] == chunks[k]
+        for bit in range(8 * len(chunks[k])):
+            i = begin + bit // 8
+            flipped = good[:i] + bytes([good[i] ^ (0x80 >> (bit % 8))]) + good[i + 1:]
+            if flipped[i] == 0xFF or good[i] == 0xFF or good[i - 1] == 0xFF:
+                continue
+            try:
+                decode(flipped)
+            except Refused as e:
+                if e.why == "code":
+                    out["refine_code_in_no_table"] = (flipped, ("code",))
+                    return out
+    raise AssertionError("no bit of a middle interval, flipped, gives a prefix in no table")

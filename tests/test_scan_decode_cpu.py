@@ -103,6 +103,90 @@ def test_restated_decoder_refuses_damaged_data():
         assert e.value.code == sc.EFORMAT and e.value.why in whys, f"{name}: {e.value}"
 
 
+def test_edge_case_preconditions(lib):
+    """what every edge_ file and every damaged file is named for, from the parse and the writer's reports alone"""
+    import decode_cases as dc
+    edge = sc.edge_cases()
+    for name, (_data, want) in edge.items():
+        got = sc.expected(f"edge_{name}")
+        for c, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a, np.asarray(b).reshape(a.shape)), f"{name}: component {c}"
+    scans = {name: sc.parse_scans(data)["scans"] for name, data in sc.good_files().items()}
+
+    def intervals(name):
+        return [s["intervals"] for s in scans["edge_" + name]]
+    # more first-scan intervals than a workgroup of k_scans_intervals (256) and a tile of the scan over their counts (1024) hold:
+    # no other file comes near; 257 intervals of a refinement scan are 65 workgroups of four wavefronts, one live in the last
+    assert intervals("intervals_257_grey") == [257] * 4 and all(s["ah"] == 0 for s in scans["edge_intervals_257_grey"])
+    assert all(sum(s["intervals"] for s in ss if s["ah"] == 0) <= 150 for name, ss in scans.items() if not name.startswith("edge_"))
+    assert intervals("refine_257_grey") == [257] * 8 and -(-257 // 4) == 65 and 257 % 4 == 1
+    for index, s in enumerate(scans["edge_refine_257_grey"]):
+        if s["ss"] == 0 and s["ah"]:        # a DC refinement interval: one bit, padded to a byte (a set bit: FF, stuffed, in front of RSTn)
+            assert set(sc.scan_chunks(edge["refine_257_grey"][0], index)) == {b"\x7f", b"\xff\x00"}
+    for residue, restart in sc.MOD4_RESTARTS.items():
+        assert intervals(f"refine_intervals_mod4_{residue}") == [-(-18 // restart)] * 8 and -(-18 // restart) % 4 == residue and 18 % restart
+    # interleaved and one-component scans cut by restarts in one file; DC refinement intervals of 12 bits (three MCUs of 4:2:2)
+    for name in ("refine_3_422_rst", "stops_at_1_444_rst"):
+        assert {len(s["components"]) for s in scans["edge_" + name] if s["intervals"] > 1} == {1, 3}, name
+    dc_refinements = [s for s in scans["edge_refine_3_422_rst"] if s["ss"] == 0 and s["ah"]]
+    assert [(len(s["components"]), s["restart_interval"], s["intervals"]) for s in dc_refinements] == [(3, 3, 3)] * 3
+    assert intervals("dc_alone_420_rst") == [9, 3, 3, 3, 9, 3, 3, 9, 9] and [s["ss"] for s in scans["edge_dc_alone_420_rst"]][:3] == [0, 0, 0]
+    grids, mcus_w, mcus_h = dc.geometry(sc.parse_scans(edge["dummy_blocks_17x9_rst"][0]))
+    assert (mcus_h * 2, mcus_w * 2) == (2, 4) and grids[0][:2] == (2, 3) and intervals("dummy_blocks_17x9_rst")[0] == 1   # padding blocks inside the interval
+    luma_ac_alone = [3 if s["components"] == [0] and s["ss"] else 1 for s in scans["edge_dri_between_grids_420"]]
+    assert intervals("dummy_blocks_17x9_rst") == intervals("dri_between_grids_420") == luma_ac_alone
+    assert [s["restart_interval"] for s in scans["edge_dri_changes"]] == [2] + [5] * 6 + [0] * 3
+    assert all(s["ah"] for s in scans["edge_dri_changes"][7:]) and intervals("dri_changes") == [3, 4, 2, 2, 4, 4, 2, 1, 1, 1]
+    scans = {name[5:]: ss for name, ss in scans.items() if name.startswith("edge_")}
+    # EOB runs at the intervals' ends
+    report = []
+    case = sc.directed_case()
+    assert sc.write_case(case, sc.SPLIT, restart=4, report=report) == edge["eob_run_ends_each_interval"][0]
+    zz = case["coefficients"][0].reshape(-1, 64)[:, ec.ZIGZAG]
+    for index in (2, 5):
+        told = report[index]["intervals"]
+        ends = [i["runs"][-1] if i["runs"] and i["runs"][-1][2] == "end_of_scan" else None for i in told]
+        assert len(told) == 6 and sum(1 for r in ends if r is not None and r[1] > 1) >= 4, (index, ends)
+    carried = [sum(1 for b in range(first, first + n) if (np.abs(zz[b, 6:]) >= 2).any()) for i in report[5]["intervals"] for first, n, _why in i["runs"]]
+    assert max(carried) >= 3, carried           # one run's waiting correction bits come from three blocks
+    # markers on the unstuffing kernels' edges, counted from the scan's own begin
+    data = edge["markers_on_edges_scan_k"][0]
+    for index in sc.EDGE_SCANS:
+        s = scans["markers_on_edges_scan_k"][index]
+        assert index > 0 and s["ss"] and bool(s["ah"]) == (index == sc.EDGE_SCANS[1])
+        at = sc.scan_marker_offsets(data, index)
+        assert len(at) == 23 and [a % 256 for a in at] == [dc.EDGE_TARGETS[m % 6] for m in range(23)], (index, at)
+        assert any(a % 256 == 0 and a >= 256 for a in at)           # FF | Dn across a chunk edge
+    assert any(scans["markers_on_edges_scan_k"][index]["begin"] % 4 for index in sc.EDGE_SCANS)         # chunks laid from an unaligned address
+    assert any(sc.scan_stuffed_on_chunk_edge(data, index) for index in range(1, 10))
+    data = edge["fill_covers_chunks_scan_k"][0]
+    assert len(sc.scan_blank_chunks(data, sc.EDGE_SCANS[1])) == 2 and scans["fill_covers_chunks_scan_k"][sc.EDGE_SCANS[1]]["ah"]
+    # the Al ladder, and the coefficients it carries
+    ladder = [(s["ss"], s["ah"], s["al"]) for s in scans["refine_from_13"]]
+    assert ladder == [(ss, ah, al) for _c, ss, _se, ah, al in sc.FROM_13] and len(ladder) == 28 and ladder[:2] == [(0, 0, 13), (1, 0, 13)]
+    assert ladder[-2:] == [(0, 1, 0), (1, 1, 0)]
+    values = np.concatenate([a.reshape(-1) for a in sc.expected("edge_refine_from_13")]).astype(np.int64)
+    assert values.max() == 32767 and values.min() == -32768 and (np.abs(values.reshape(-1, 64)[:, 1:]) >> 13).max() == 3
+    # the DC extremes
+    for al, (top, bottom) in ((0, (32767, -32768)), (1, (32766, -32768))):
+        got = sc.expected(f"edge_dc_near_limit_al{al}")[0][0, :, 0].astype(np.int64)
+        assert got.max() == top and got.min() == bottom and scans[f"dc_near_limit_al{al}"][0]["al"] == al
+        assert (got >> al).max() == (32767 >> al) and (got >> al).min() == -(32768 >> al)
+    got = sc.expected("edge_dc_reset_by_restart")[0][0, :, 0]
+    assert got.tolist() == [30000] * 3 and 3 * 30000 > 32767 and scans["dc_reset_by_restart"][0]["restart_interval"] == 1
+    # the damaged files: both parsers accept them, the restatement refuses each for its one reason
+    damaged = sc.damaged_cases()
+    assert len(damaged) == 6 + 18
+    for name, (data, whys) in damaged.items():
+        sc.parse_scans(data)
+        rc, _info, _scans = _c_parse(lib, data)
+        assert rc == 0, f"{name}: {lib.j2p_last_error().decode()}"
+        with pytest.raises(sc.Refused) as e:
+            sc.decode(data)
+        assert e.value.code == sc.EFORMAT and e.value.why in whys, f"{name}: {e.value}"
+        assert len(whys) == 1 or name == "scan_cut_short", name
+
+
 def test_header_refusals_touch_no_device(lib):
     """every new entry point refuses on the parse alone: the right code, nothing written, on a machine with or without a GPU"""
     import jpeg2png_amd as j

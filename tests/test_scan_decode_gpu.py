@@ -4,8 +4,12 @@ Solver.from_jpeg and Batch.submit): every comparison is exact, with the arrays o
 tests/scan_decode_cases.py, which tests/test_scan_decode_cpu.py holds against libjpeg.  The files are small: PIL's of up to 83x61
 pixels, the progressive coder's directed cases (the EOB-run flush at 32767, the 937-bit correction limit, refinement ZRLs, the scan
 endings), and writer-made scripts (spectral selection alone, DC scans one component at a time, Al 3 refined down to 0, a script
-that stops at Al 1, 128 scans).  At 32 bits a subsequence every boundary is crossed: an EOBn symbol and its extra bits, a symbol
-that ends a band, the last symbol of an interval; 75 is a length no power of two divides."""
+that stops at Al 1, 128 scans), and the edge_ files of scan_decode_cases.edge_cases(): writer-made scripts with restart intervals,
+1028 intervals of first scans and 257 of refinement scans, markers and fill bytes on the unstuffing kernels' edges counted from a
+later scan's begin, Al 13 refined to 0, DC at the int16 limits.  The damaged files each have one fault that one kernel alone can
+refuse, and the text of the refusal is the one that belongs to the restatement's reason.  At 32 bits a subsequence every boundary
+is crossed: an EOBn symbol and its extra bits, a symbol that ends a band, the last symbol of an interval; 75 is a length no power
+of two divides."""
 import ctypes
 
 import numpy as np
@@ -19,7 +23,7 @@ from test_jpeg_out_gpu import read_coefficients  # noqa: F401
 
 J2P_EFORMAT, J2P_ENOTSUP = -6, -7
 LENGTHS = (0, 32, 75, 1024)             # the default, J2P_DECODE_SUBSEQUENCE_MIN, an odd one, the default given
-GROUPS = ("pil_L0", "pil_RGB0", "pil_RGB1", "pil_RGB2", "coder", "written")
+GROUPS = ("pil_L0", "pil_RGB0", "pil_RGB1", "pil_RGB2", "coder", "written", "edge")
 
 
 def group(name):
@@ -127,19 +131,30 @@ def test_stats(lib):
 
 
 DAMAGED = ("scan_cut_short", "eob_run_one_too_long", "refinement_symbol_of_two_bits", "run_past_se", "restart_out_of_sequence",
-           "byte_behind_dc_refinement")
+           "byte_behind_dc_refinement",
+           "dc_above_int16_al0", "dc_below_int16_al0", "dc_above_int16_al1", "dc_below_int16_al1",
+           "dc_refine_interval_short_next_long", "dc_refine_byte_behind_interval", "dc_refine_rst_removed", "dc_refine_rst_renumbered",
+           "eob_run_crosses_restart_refine", "eob_run_crosses_restart_first", "refine_run_past_band", "refine_zrl_past_band", "first_zrl_past_band",
+           "refine_byte_behind_interval", "refine_interval_cut_short", "refine_rst_removed", "refine_rst_doubled", "refine_code_in_no_table")
+# what the library says of a file the restatement refuses for this reason (written from the restatement's reasons and the header's
+# account of the refusals: a file with one fault has one text)
+_ENDS = "the scan is truncated, or data is left over behind its last block"
+WHY_TEXT = {"restart": "a restart marker is missing or out of sequence", "code": "a code that is in no Huffman table", "run": "a run past coefficient 63",
+            "truncated": _ENDS, "leftover": _ENDS, "dc": "a DC value outside int16", "refine": "a refinement scan's symbol of more than one bit",
+            "eobrun": "an EOB run past the last block of its restart interval"}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", DAMAGED)
 def test_damaged_files_are_refused(lib, name):
-    """J2P_EFORMAT, the pre-filled output untouched, and a good decode afterwards in the same process"""
+    """J2P_EFORMAT with the text of the file's one fault, the pre-filled output untouched, and a good decode afterwards in the same process"""
     assert sorted(DAMAGED) == sorted(sc.damaged_cases())
-    data, _why = sc.damaged_cases()[name]
+    data, whys = sc.damaged_cases()[name]
     comps, _, _ = dc.geometry(sc.parse_scans(data))
     for bits in (0, 32, 75):
         rc, got, _ = c_decode(lib, data, [(gh, gw, 64) for gh, gw, _, _ in comps], bits=bits)
         assert rc == J2P_EFORMAT, f"{name} at {bits} bits: {rc} {lib.j2p_last_error().decode()}"
+        assert lib.j2p_last_error().decode() in {"jpeg: " + WHY_TEXT[why] for why in whys}, f"{name} at {bits} bits: {lib.j2p_last_error().decode()}"
         assert all((a == 0x5A5A).all() for a in got), name
     ok = "pil_41x23_q75_RGB2_plain"
     want = sc.expected(ok)
@@ -196,6 +211,35 @@ def test_a_damaged_progressive_file_makes_no_solver(lib):
 
 
 # ---- batch jobs ----
+@pytest.mark.gpu
+def test_a_file_damaged_in_its_last_scan_fails_its_own_job_and_not_its_neighbours(lib):
+    """the fault sits in the last AC refinement scan: the launches that end the decode find it, behind everything the file's other
+    scans queued.  The jobs in front of it and behind it give what they give alone, bit for bit"""
+    import jpeg2png_amd as j
+    bad, _ = sc.damaged_cases()["eob_run_crosses_restart_refine"]
+    last = sc.parse_scans(bad)["scans"][-1]
+    assert last["ss"] and last["ah"] and last["intervals"] > 1
+    with pytest.raises(sc.Refused):
+        sc.decode(bad)
+    good = [sc.good_files()[name] for name in ("edge_eob_run_ends_each_interval", "pil_41x23_q75_L0_rst_blocks")]
+    args = (0.3, [0.001], 6)
+    alone = []
+    for data in good:
+        with j.Batch(devices=(0,), slots_per_device=1) as b:
+            alone.append(b.wait(b.submit(None, *args, file=data, progressive=True)))
+    with j.Batch(devices=(0,), slots_per_device=3) as b:
+        tickets = [b.submit(None, *args, file=data, progressive=True) for data in (good[0], bad, good[1])]
+        with pytest.raises(j.J2PError) as e:
+            b.wait(tickets[1])
+        assert e.value.code == J2P_EFORMAT
+        for t, ref in zip((tickets[0], tickets[2]), alone):
+            got = b.wait(t)
+            assert len(got) == len(ref) == 1 and all(bit_equal(a, r) for a, r in zip(got, ref))
+        again = b.wait(b.submit(None, *args, file=good[0], progressive=True))           # ... and the worker that refused goes on working
+        assert all(bit_equal(a, r) for a, r in zip(again, alone[0]))
+    assert alone[0][0].shape != alone[1][0].shape and all(np.asarray(a[0]).any() for a in alone)       # (two images, neither blank)
+
+
 @pytest.mark.gpu
 def test_batch_progressive_file_jobs_equal_baseline_file_jobs(lib):
     """Batch.submit(file=, progressive=True) against the same job from the baseline file of the same coefficients: joint, separate,
