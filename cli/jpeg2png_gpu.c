@@ -30,6 +30,9 @@
  *   -r, --progressive = with -j: the progressive file of libjpeg's jpeg_simple_progression() — ten scans (six with -g), every one with
  *                  Huffman tables of its own (include/jpeg2png_amd.h, "The progressive JPEG file"); with -e the GPU codes every scan
  *                  (j2p_batch_submit_jpeg_progressive), without it libjpeg does — the same file either way.  -O changes nothing about it
+ *   -R, --restart N | NB = with -j: restart markers every N MCU rows, or with a B behind the number every N MCUs, as cjpeg -restart
+ *                  spells them (libjpeg's restart_in_rows / restart_interval; include/jpeg2png_amd.h, "Restart intervals"); with -e the
+ *                  GPU writes the intervals (j2p_batch_submit_jpeg_opt), without it libjpeg does — the same file either way
  *   -D, --decode-any-on-gpu = -d, and a progressive input's scans are all decoded on the GPU as well (j2p_batch_next_file_scans;
  *                  include/jpeg2png_amd.h, "Reading a progressive JPEG file"); a file that decoder still refuses goes to libjpeg after
  *                  the one line -d prints
@@ -335,7 +338,7 @@ static void jpeg_out_tables(unsigned ncomp, int quality, uint16_t quant[3][64])
  * filled: the dummy blocks that complete a partial MCU are libjpeg's own (jctrans.c), but it reaches them through arrays
  * whose sizes are rounded up to the component's sampling factors and that can hold v_samp_factor rows at a time */
 static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int quality, unsigned sub_w, unsigned sub_h, bool optimize,
-                       bool progressive, int16_t *const coef[3])
+                       bool progressive, unsigned restart_interval, unsigned restart_in_rows, int16_t *const coef[3])
 {
         struct jpeg_compress_struct c;
         struct jpeg_error_mgr err;
@@ -347,6 +350,8 @@ static void write_jpeg(FILE *out, unsigned w, unsigned h, unsigned ncomp, int qu
         setup_jpeg_out(&c, w, h, ncomp, quality, sub_w, sub_h);
         if(optimize) { c.optimize_coding = TRUE; }
         if(progressive) { jpeg_simple_progression(&c); }
+        c.restart_interval = restart_interval;
+        c.restart_in_rows = (int)restart_in_rows;
         const unsigned bw = (w + 7) / 8, bh = (h + 7) / 8;
 #if JPEG_LIB_VERSION >= 70
         /* IJG 7+: jpeg_write_coefficients expects what jpeg_calc_jpeg_dimensions / initial_setup would have left */
@@ -391,6 +396,7 @@ struct options {
         bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
         bool auto_orient;       /* -a: the input's EXIF Orientation is applied: every output is the upright image, and carries no tag */
         bool progressive;       /* -r: with -j, the progressive file (jpeg_simple_progression; with -e j2p_batch_submit_*_progressive) */
+        unsigned restart_interval, restart_in_rows;     /* -R NB, -R N: with -j, restart intervals of N MCUs or N MCU rows */
         bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
         bool joint, quiet;
@@ -574,8 +580,13 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
                         const unsigned flags = o->optimize ? J2P_JPEG_OPTIMIZE : 0u;
+                        const j2p_jpeg_options options = {flags, o->progressive ? 1u : 0u, o->restart_interval, o->restart_in_rows};
                         ORIENT_NEXT();
-                        if(o->progressive && jp.file) {
+                        if((o->restart_interval || o->restart_in_rows) && jp.file) {
+                                gpu_check(j2p_batch_submit_file_jpeg_opt(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &options, &ticket));
+                        } else if(o->restart_interval || o->restart_in_rows) {
+                                gpu_check(j2p_batch_submit_jpeg_opt(batch, &job, NULL, &spec, file, capacity, &file_bytes, &options, &ticket));
+                        } else if(o->progressive && jp.file) {
                                 gpu_check(j2p_batch_submit_file_jpeg_progressive(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket));
                         } else if(o->progressive) {
                                 gpu_check(j2p_batch_submit_jpeg_progressive(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket));
@@ -627,7 +638,7 @@ static void decode_file(const char *infile, const char *outfile, const struct op
         if(!out) { die_perror("could not open output file `%s`", outfile); }
         if(file) {
                 if(fwrite(file, 1, file_bytes, out) != file_bytes) { die_perror("could not write output file `%s`", outfile); }
-        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, o->optimize, o->progressive, out_coef); }
+        } else if(o->jpeg_quality) { write_jpeg(out, job.out_w, job.out_h, jp.n, o->jpeg_quality, o->sub_w, o->sub_h, o->optimize, o->progressive, o->restart_interval, o->restart_in_rows, out_coef); }
         else { write_png(out, job.out_w, job.out_h, o->png_bits, jp.n, pixels); }
         fclose(out);
         free(pixels);
@@ -693,6 +704,8 @@ static void usage(void)
                "  -r, --progressive            with -j: a progressive JPEG (libjpeg's simple progression: ten scans, six with -g,\n"
                "                               each with Huffman tables of its own); with -e the GPU codes every scan; the\n"
                "                               same bytes either way\n"
+               "  -R, --restart N | NB         with -j: restart markers every N MCU rows, or (NB) every N MCUs, 1..65535; with -e\n"
+               "                               the GPU writes them; the same bytes either way\n"
                "  -P, --png-on-gpu             the GPU also filters and deflates the PNG and only the file comes down: the same\n"
                "                               pixels in another, usually somewhat larger file; not with -j, not for row-tiled images\n"
                "  -a, --auto-orient            apply the input's EXIF Orientation: every output is the upright image (turned and\n"
@@ -717,16 +730,16 @@ int main(int argc, char **argv)
                 {"greyscale", no_argument, NULL, 'g'}, {"jpeg", required_argument, NULL, 'j'},
                 {"chroma-subsampling", required_argument, NULL, 'S'}, {"encode-on-gpu", no_argument, NULL, 'e'},
                 {"decode-on-gpu", no_argument, NULL, 'd'}, {"decode-any-on-gpu", no_argument, NULL, 'D'}, {"optimize", no_argument, NULL, 'O'},
-                {"progressive", no_argument, NULL, 'r'},
+                {"progressive", no_argument, NULL, 'r'}, {"restart", required_argument, NULL, 'R'},
                 {"png-on-gpu", no_argument, NULL, 'P'}, {"auto-orient", no_argument, NULL, 'a'}, {NULL, 0, NULL, 0}};
         struct options o = {.iterations = {50, 50, 50}, .weights = {0.3f, 0.f, 0.f}, .pweights = {0.001f, 0.001f, 0.001f},
                             .png_bits = 8, .jpeg_quality = 0, .encode_on_gpu = false, .png_on_gpu = false, .optimize = false, .sub_w = 1, .sub_h = 1, .joint = true, .quiet = false, .grey = false, .zoom = 1, .tile = false, .csv = NULL, .ndev = 1, .devs = {0}};
-        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL;
+        const char *w_arg = NULL, *p_arg = NULL, *i_arg = NULL, *t_arg = NULL, *c_arg = NULL, *z_arg = NULL, *j_arg = NULL, *S_arg = NULL, *R_arg = NULL;
         char **outs = calloc((size_t)argc, sizeof(*outs));
         unsigned nout = 0;
         bool force = false, help = false, version = false;
         int ch;
-        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edDOPar", longopts, NULL)) != -1) {
+        while((ch = getopt_long(argc, argv, "h?Vo:fc:t:qs1i:p:w:z:gj:S:edDOParR:", longopts, NULL)) != -1) {
                 switch(ch) {
                 case 'V': version = true; break;
                 case 'o': outs[nout++] = optarg; break;
@@ -748,6 +761,7 @@ int main(int argc, char **argv)
                 case 'D': o.decode_on_gpu = o.decode_any_on_gpu = true; break;
                 case 'O': o.optimize = true; break;
                 case 'r': o.progressive = true; break;
+                case 'R': R_arg = optarg; break;
                 case 'P': o.png_on_gpu = true; break;
                 case 'a': o.auto_orient = true; break;
                 default: help = true; break;
@@ -805,6 +819,15 @@ int main(int argc, char **argv)
         if(o.encode_on_gpu && !j_arg) { die("-e needs JPEG output (-j)"); }
         if(o.optimize && !j_arg) { die("-O needs JPEG output (-j)"); }
         if(o.progressive && !j_arg) { die("-r needs JPEG output (-j)"); }
+        if(R_arg) {
+                char *end = NULL;
+                const unsigned long n = strtoul(R_arg, &end, 10);
+                const bool blocks = end != R_arg && (*end == 'B' || *end == 'b') && end[1] == '\0';
+                if(end == R_arg || (*end != '\0' && !blocks) || R_arg[0] == '-' || n < 1 || n > 65535) { die("invalid restart interval"); }
+                if(!j_arg) { die("-R needs JPEG output (-j)"); }
+                o.restart_interval = blocks ? (unsigned)n : 0;
+                o.restart_in_rows = blocks ? 0 : (unsigned)n;
+        }
         if(o.png_on_gpu && j_arg) { die("-P writes a PNG: not with JPEG output (-j)"); }
         /* the reference leaves the thread count to OpenMP, i.e. one per online core (jpeg2png.c:246-257) */
         long cores = sysconf(_SC_NPROCESSORS_ONLN);

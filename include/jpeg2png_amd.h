@@ -838,7 +838,7 @@ int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples
 /* The JPEG file: quantised coefficients entropy-coded ON THE DEVICE, so that a complete baseline JPEG comes down instead of 2 bytes
  * per sample of coefficients for a host library to code.  The file is, byte for byte, the one libjpeg writes from the same
  * coefficients with jpeg_set_defaults, jpeg_set_colorspace, jpeg_set_quality(Q, TRUE) and jpeg_write_coefficients: default Huffman
- * tables, one scan, no restart markers, no optimisation.  This is the definition.
+ * tables, one scan, no restart markers (unless asked for: "Restart intervals", below), no optimisation.  This is the definition.
  *
  * Inputs.  An image of width x height (1..65535 each) with ncomp = 1 or 3 components; chroma subsampling sub_w, sub_h, each 1 or 2
  * (one component: taken as 1 whatever the fields hold).  Component 0 has bw x bh = ceil(width / 8) x ceil(height / 8) blocks,
@@ -1036,6 +1036,82 @@ int j2p_entropy_encode_progressive(int device, const j2p_jpeg *spec, const int16
  * record next to the copied spec, not in j2p_job.  Every rule of those calls stands (not with `tile`, ...). */
 int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                                       size_t capacity, size_t *size, int *ticket);
+
+/* Restart intervals: any of the three files above with RSTn markers in its scans, which make a file robust to damage and let a
+ * parallel decoder — this library's own first of all — split every scan.  With restarts the file is, byte for byte, the one libjpeg
+ * (IJG 9d) writes with the calls named under "The JPEG file", "Optimised Huffman tables" and "The progressive JPEG file" and, before
+ * jpeg_write_coefficients, cinfo.restart_interval = N or cinfo.restart_in_rows = R.  This is the definition; where the wording below
+ * and libjpeg differ, libjpeg's output is the authority.
+ *
+ * Units.  An interleaved scan — the baseline scan of three components, a progressive DC scan of three components — counts MCUs.  A
+ * scan of one component — every AC scan, every scan of a one-component file — counts that component's blocks in raster order.
+ * restart_interval = N (1..65535) is the interval of every scan.  restart_in_rows = R (1..65535) sets a scan's interval to
+ * min(R x units per row of that scan, 65535), units per row being the MCUs per row of an interleaved scan and the component's
+ * blocks per row of a one-component scan: the interval changes between the scans of a subsampled progressive file.
+ * DRI.  A DRI segment (FF DD 00 04, the interval as 16 bits) stands behind the scan's DHT segments and immediately in front of its
+ * SOS, and only where the interval differs from the one last written, which starts at 0 — also when the interval holds the whole scan
+ * and no marker follows.  A 40x24 4:2:0 progressive file with R = 1 has DRI 3 in front of scans 1, 3, 7 and DRI 5 in front of scans
+ * 2, 5 and 10; with N = 3 one DRI, in front of scan 1.
+ * Intervals.  Behind every interval but the scan's last: a pending EOB run is flushed (its EOBn symbol, its extra bits, then its
+ * waiting correction bits); the last byte is completed with 1-bits; every FF of the data, one made by that padding included, is
+ * followed by 00; then FF D0+(k mod 8) for the k-th marker of the scan, counted from 0 per scan, not stuffed.  The DC predictors
+ * restart at 0; an interval of a DC refinement scan is its bits padded to a byte.  An EOB run never spans a marker; the cuts at 32767
+ * blocks and 937 correction bits apply within an interval as before.
+ * Counts.  With tables made for the image the symbol counts are those of the scan as coded: DC categories follow the reset
+ * predictors, and there is one EOBn per flush, the flushes at interval ends included.
+ * Refusals.  J2P_EINVAL for N or R above 65535 and for both non-zero; everything the three coders refuse without restarts.
+ *
+ * On the device the restart plan is pure host arithmetic (j2p_debug_restart_plan shows it).  Every interval starts on a byte, so its
+ * pad is (-its bits) mod 8 and is known from the unpadded bit offsets: a lane per interval adds it to the length of the interval's last
+ * item, the exclusive sum runs once more, and the lane or wavefront of every interval's last item writes the 1-bits.  The staging
+ * stream stays pure data; the markers go in where the FFs are stuffed.  No wait is added: a file costs the waits it cost.
+ *
+ * One options record for all three files.  flags: J2P_JPEG_* bits; progressive: 0 or 1 (flags then change nothing);
+ * restart_interval, restart_in_rows: 0 for none.  With both 0 a j2p_*_opt call is the call it extends — the same launches, the same
+ * memory, the same bytes.  The calls without options keep their signatures and keep refusing what they refuse. */
+typedef struct j2p_jpeg_options {
+        unsigned flags;
+        unsigned progressive;
+        unsigned restart_interval;
+        unsigned restart_in_rows;
+} j2p_jpeg_options;
+/* one scan of the restart plan: its units, the units in a row, its interval (0: none), the number of intervals (1 without) and
+ * whether a DRI segment precedes its SOS */
+typedef struct j2p_restart_scan {
+        unsigned units, units_per_row, interval, intervals, dri;
+} j2p_restart_scan;
+typedef struct j2p_restart_plan {
+        unsigned nscans;        /* 1 for a baseline file */
+        j2p_restart_scan scan[J2P_PROGRESSIVE_SCANS];
+} j2p_restart_plan;
+/* Test hook, needs no device: the plan of the file of width x height pixels with ncomp components and sub_w x sub_h blocks of component
+ * 0 in an MCU.  J2P_EINVAL for options the coders refuse. */
+int j2p_debug_restart_plan(unsigned width, unsigned height, unsigned ncomp, unsigned sub_w, unsigned sub_h, const j2p_jpeg_options *options,
+                           j2p_restart_plan *plan);
+/* what the coder did per scan, as taken on the device: the interval and the number of intervals, the 1-bits that completed the
+ * intervals' last bytes (the scan's last included) and the RSTn markers written */
+typedef struct j2p_restart_scan_stats {
+        unsigned interval, intervals;
+        unsigned long long padding_bits, markers;
+} j2p_restart_scan_stats;
+typedef struct j2p_restart_stats {
+        unsigned nscans;
+        j2p_restart_scan_stats scan[J2P_PROGRESSIVE_SCANS];
+} j2p_restart_stats;
+/* j2p_planes_to_jpeg, _ex and _progressive as one call */
+int j2p_planes_to_jpeg_opt(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
+                           size_t *size, const j2p_jpeg_options *options);
+/* j2p_entropy_encode, _ex and _progressive as one call.  stats is filled by the baseline and optimised coders, progressive_stats by
+ * the progressive one (its `bits` are those before any padding), restart_stats by all; each may be NULL and is zeroed first. */
+int j2p_entropy_encode_opt(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
+                           size_t capacity, size_t *size, const j2p_jpeg_options *options, j2p_encode_stats *stats,
+                           j2p_progressive_stats *progressive_stats, j2p_restart_stats *restart_stats);
+/* j2p_batch_submit_jpeg and j2p_batch_submit_file_jpeg with the options, which are copied and travel in the job's record next to the
+ * copied spec, not in j2p_job. */
+int j2p_batch_submit_jpeg_opt(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                              size_t capacity, size_t *size, const j2p_jpeg_options *options, int *ticket);
+int j2p_batch_submit_file_jpeg_opt(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                   size_t capacity, size_t *out_size, const j2p_jpeg_options *options, int *ticket);
 
 /* Reading a JPEG file: the entropy-coded data of a baseline file Huffman-decoded ON THE DEVICE, so that a caller without libjpeg
  * gets the file's true quantised coefficients at every quality.  For each component the result is the grid of whole blocks

@@ -130,6 +130,32 @@ class _CProgressiveStats(ctypes.Structure):
     _fields_ = [("nscans", ctypes.c_uint), ("scan", _CProgressiveScan * 10)]
 
 
+class _CJpegOptions(ctypes.Structure):
+    """j2p_jpeg_options"""
+    _fields_ = [("flags", ctypes.c_uint), ("progressive", ctypes.c_uint), ("restart_interval", ctypes.c_uint), ("restart_in_rows", ctypes.c_uint)]
+
+
+class _CRestartScan(ctypes.Structure):
+    """j2p_restart_scan"""
+    _fields_ = [("units", ctypes.c_uint), ("units_per_row", ctypes.c_uint), ("interval", ctypes.c_uint), ("intervals", ctypes.c_uint),
+                ("dri", ctypes.c_uint)]
+
+
+class _CRestartPlan(ctypes.Structure):
+    """j2p_restart_plan"""
+    _fields_ = [("nscans", ctypes.c_uint), ("scan", _CRestartScan * 10)]
+
+
+class _CRestartScanStats(ctypes.Structure):
+    """j2p_restart_scan_stats"""
+    _fields_ = [("interval", ctypes.c_uint), ("intervals", ctypes.c_uint), ("padding_bits", ctypes.c_ulonglong), ("markers", ctypes.c_ulonglong)]
+
+
+class _CRestartStats(ctypes.Structure):
+    """j2p_restart_stats"""
+    _fields_ = [("nscans", ctypes.c_uint), ("scan", _CRestartScanStats * 10)]
+
+
 class _CPng(ctypes.Structure):
     """j2p_png: the image, the filter and the block sizes of a PNG file made on the device"""
     _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("bits", ctypes.c_uint), ("filter", ctypes.c_int),
@@ -244,6 +270,7 @@ C_ABI_SYMBOLS = [
     "j2p_solver_phase_order", "j2p_debug_project_items", "j2p_debug_phase_order", "j2p_debug_grad_items_workgroups",
     "j2p_pool_thread_takes",
     "j2p_jpeg_parse_scans", "j2p_entropy_decode_scans", "j2p_solver_create_from_jpeg_scans", "j2p_batch_next_file_scans",
+    "j2p_debug_restart_plan", "j2p_planes_to_jpeg_opt", "j2p_entropy_encode_opt", "j2p_batch_submit_jpeg_opt", "j2p_batch_submit_file_jpeg_opt",
 ]
 J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -472,6 +499,15 @@ def _bind(path):
         lib.j2p_batch_submit_file_jpeg_progressive.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t,
                                                                ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
                                                                ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_entropy_encode_opt"):
+        # (as above: an earlier commit's build writes no restart markers)
+        lib.j2p_debug_restart_plan.argtypes = [ctypes.c_uint] * 5 + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(_CRestartPlan)]
+        lib.j2p_planes_to_jpeg_opt.argtypes = lib.j2p_planes_to_jpeg.argtypes + [ctypes.POINTER(_CJpegOptions)]
+        lib.j2p_entropy_encode_opt.argtypes = lib.j2p_entropy_encode.argtypes + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(_CEncodeStats),
+                                                                                 ctypes.POINTER(_CProgressiveStats), ctypes.POINTER(_CRestartStats)]
+        lib.j2p_batch_submit_jpeg_opt.argtypes = lib.j2p_batch_submit_jpeg.argtypes[:-1] + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_batch_submit_file_jpeg_opt.argtypes = lib.j2p_batch_submit_file_jpeg_progressive.argtypes[:-1] + [ctypes.POINTER(_CJpegOptions),
+                                                                                                                 ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_png_encode"):
         # (as above: an earlier commit's build writes no PNG)
         lib.j2p_planes_to_png.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CPng), ctypes.c_void_p, ctypes.c_size_t,
@@ -888,7 +924,32 @@ def _jpeg_bytes(call, guess):
     return buf[:size.value].tobytes()
 
 
-def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False, progressive=False):
+def _restart_options(optimize, progressive, restart_rows, restart_interval):
+    """j2p_jpeg_options of a file's keywords, or None without restart intervals (the calls without options are then made as ever)"""
+    rows, interval = int(restart_rows or 0), int(restart_interval or 0)
+    if rows < 0 or interval < 0:
+        raise J2PError("jpeg: restart_rows and restart_interval are not negative")
+    if not rows and not interval:
+        return None
+    if rows > 0xffffffff or interval > 0xffffffff:       # (what the record cannot hold; the library refuses everything above 65535)
+        raise J2PError("jpeg: restart_rows and restart_interval are above 65535")
+    return _CJpegOptions(J2P_JPEG_OPTIMIZE if optimize and not progressive else 0, 1 if progressive else 0, interval, rows)
+
+
+def _restart_plan(width, height, ncomp, subsampling=(1, 1), progressive=False, restart_rows=0, restart_interval=0):
+    """test hook: the restart intervals of the file these keywords describe, from the library's host arithmetic alone (j2p_debug_restart_plan; no
+    device): per scan a dict of units, units_per_row, interval, intervals and dri (a DRI segment precedes its SOS)"""
+    lib = load_library()
+    sx, sy = _sampling(subsampling)
+    options = _CJpegOptions(0, 1 if progressive else 0, int(restart_interval or 0), int(restart_rows or 0))
+    plan = _CRestartPlan()
+    _check(lib.j2p_debug_restart_plan(int(width), int(height), int(ncomp), sx, sy, ctypes.byref(options), ctypes.byref(plan)))
+    return [{"units": k.units, "units_per_row": k.units_per_row, "interval": k.interval, "intervals": k.intervals, "dri": bool(k.dri)}
+            for k in plan.scan[:plan.nscans]]
+
+
+def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False, progressive=False,
+                   restart_rows=0, restart_interval=0):
     """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode): coefficients is a
     list of 1 or 3 int16 arrays [blocks_h, blocks_w, 64] in natural order — component 0's grid ceil(height / 8) x ceil(width / 8),
     the others' ceil of that over subsampling=(sx, sy) — every value in [-1023, 1023]; quant_tables: one per component, steps
@@ -899,7 +960,11 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
     progressive=True: the progressive file of libjpeg's jpeg_simple_progression() (j2p_entropy_encode_progressive; include/jpeg2png_amd.h:
     "The progressive JPEG file"), every scan with tables of its own — optimize= changes nothing about it.  stats=True then gives
     (file, list of one dict per scan: components, ss, se, ah, al, tables — {(class << 4) | slot: 256 counts}, in DHT order —, bits,
-    stuffed_bytes and eob_runs)."""
+    stuffed_bytes and eob_runs).
+    restart_rows=R or restart_interval=N: the same file with restart intervals of R rows of MCUs (of blocks, in a scan of one
+    component) or of N MCUs (blocks) — libjpeg's restart_in_rows and restart_interval (j2p_entropy_encode_opt; include/jpeg2png_amd.h:
+    "Restart intervals").  stats=True then gives the dict, or each scan's dict, one more entry: "restart", a dict of interval,
+    intervals, padding_bits and markers as taken on the device (for a baseline file under the dict's own key "restart")."""
     lib = load_library()
     n = len(coefficients)
     if n not in (1, 3):
@@ -916,6 +981,21 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
         arrays.append(a)
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
     total = sum(a.size for a in arrays)
+    options = _restart_options(optimize, progressive, restart_rows, restart_interval)
+    if options is not None:
+        st, ps, rs = _CEncodeStats(), _CProgressiveStats(), _CRestartStats()
+        file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_opt(int(device), ctypes.byref(spec), ptrs, n, out, cap, size, ctypes.byref(options),
+                                                                             ctypes.byref(st) if stats else None, ctypes.byref(ps) if stats else None,
+                                                                             ctypes.byref(rs) if stats else None), 4096 + total // 4 + total // 32)
+        if not stats:
+            return file
+        restart = [{"interval": k.interval, "intervals": k.intervals, "padding_bits": k.padding_bits, "markers": k.markers} for k in rs.scan[:rs.nscans]]
+        if progressive:
+            return file, [{"components": tuple(k.comp[:k.ncomp]), "ss": k.ss, "se": k.se, "ah": k.ah, "al": k.al,
+                           "tables": {k.table[t]: list(k.counts[t]) for t in range(k.ntables)}, "bits": k.bits, "stuffed_bytes": k.stuffed_bytes,
+                           "eob_runs": k.eob_runs, "restart": r} for k, r in zip(ps.scan[:ps.nscans], restart)]
+        return file, {"dc0": list(st.dc0), "ac0": list(st.ac0), "dc1": list(st.dc1), "ac1": list(st.ac1), "scan_bits": st.scan_bits,
+                      "stuffed_bytes": st.stuffed_bytes, "restart": restart[0]}
     if progressive:
         ps = _CProgressiveStats()
         file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_progressive(int(device), ctypes.byref(spec), ptrs, n, out, cap, size,
@@ -1355,7 +1435,8 @@ class Solver:
         _check(self._lib.j2p_planes_rows_to_coefficients_sub(ctypes.byref(ref), sx, sy, bw, r0, r0 + bh, q.ctypes.data, out.ctypes.data))
         return out
 
-    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False, progressive=False):
+    def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False, progressive=False,
+                restart_rows=0, restart_interval=0):
         """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg):
         only the file comes down.  width x height: the image, cropped from the canvas's top left corner.  quality: libjpeg's
         tables for it (quality_tables), or quant_tables: one 64-entry table per component, steps 1..255, natural order, the third
@@ -1365,7 +1446,9 @@ class Solver:
         byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults.  optimize=True: with
         Huffman tables made for the image, as entropy_encode(optimize=True) makes them (j2p_planes_to_jpeg_ex) — the same
         coefficients in fewer bytes, for one more wait on the way.  progressive=True: the progressive file, as
-        entropy_encode(progressive=True) writes it (j2p_planes_to_jpeg_progressive); optimize= changes nothing about it."""
+        entropy_encode(progressive=True) writes it (j2p_planes_to_jpeg_progressive); optimize= changes nothing about it.
+        restart_rows=R or restart_interval=N: any of the three with restart intervals, as entropy_encode(restart_rows=,
+        restart_interval=) writes them (j2p_planes_to_jpeg_opt)."""
         solvers = [self] + list(others)
         if len(solvers) not in (1, 3):
             raise J2PError("jpeg: others= takes the two other solvers of a colour file")
@@ -1375,6 +1458,10 @@ class Solver:
             refs[c] = _CPlaneRef(solvers[c]._h, 0) if len(solvers) == 3 else _CPlaneRef(self._h, c)
         spec, _held = _c_jpeg(width, height, n, quality, quant_tables, subsampling)
         guess = 4096 + int(width) * int(height) * n // 4
+        options = _restart_options(optimize, progressive, restart_rows, restart_interval)
+        if options is not None:
+            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_opt(refs, n, ctypes.byref(spec), out, cap, size, ctypes.byref(options)),
+                               guess + guess // 8)
         if progressive:
             return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_progressive(refs, n, ctypes.byref(spec), out, cap, size), guess)
         if not optimize:
@@ -1811,17 +1898,23 @@ def _job_output(job, want, planes, width, height):
 # back, what must stay alive until then, the C entry point's arguments for that output).
 
 def _fill_jpeg(job, jpeg, n, width, height):
-    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity", "optimize", "progressive"}:
+    if not isinstance(jpeg, dict) or set(jpeg) - {"quality", "quant_tables", "subsampling", "capacity", "optimize", "progressive", "restart_rows",
+                                                   "restart_interval"}:
         raise J2PError("job: jpeg= is a dict of quality or quant_tables, subsampling and capacity")
     if n not in (1, 3):
         raise J2PError("jpeg: three components or one")
     cjpeg, held = _c_jpeg(width, height, n, jpeg.get("quality"), jpeg.get("quant_tables"), jpeg.get("subsampling", (1, 1)))
     sx, sy = (cjpeg.sub_w, cjpeg.sub_h) if n == 3 else (1, 1)
     room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
+    options = _restart_options(jpeg.get("optimize"), jpeg.get("progressive"), jpeg.get("restart_rows"), jpeg.get("restart_interval"))
+    if options is not None:             # (a marker and a pad per block per scan at the most)
+        room += 3 * 10 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
     buffer, size = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
     job.out_w, job.out_h = int(width), int(height)
     flags = "progressive" if jpeg.get("progressive") else J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
-    return _JpegResult(buffer, size), [cjpeg, held], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
+    if options is not None:
+        flags = options                 # (the options record: the _opt entry points)
+    return _JpegResult(buffer, size), [cjpeg, held, options], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
 
 
 def _fill_png(job, png, n, width, height):
@@ -1956,7 +2049,9 @@ def _entry_point(source, source_args, kind, output_args):
     """step 4 -> (the C entry point of an (input kind, output kind) pair, its arguments between the job and the ticket)"""
     if kind == "jpeg":
         flags = output_args[-1]                     # (without flags the entry points that have none: the calls they always were)
-        if flags == "progressive":                  # (an entry point of its own, and no flag)
+        if isinstance(flags, _CJpegOptions):        # (restart intervals: the one entry point that takes the options record)
+            ex, output_args = "_opt", output_args[:-1] + (ctypes.byref(flags),)
+        elif flags == "progressive":                # (an entry point of its own, and no flag)
             ex, output_args = "_progressive", output_args[:-1]
         else:
             ex, output_args = ("_ex", output_args) if flags else ("", output_args[:-1])
@@ -2016,7 +2111,9 @@ class Batch:
         with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
         JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
         three planes.  optimize: Huffman tables made for the image, as Solver.to_jpeg(optimize=True).  progressive: the
-        progressive file, as Solver.to_jpeg(progressive=True) (j2p_batch_submit_jpeg_progressive); optimize changes nothing about it.  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
+        progressive file, as Solver.to_jpeg(progressive=True) (j2p_batch_submit_jpeg_progressive); optimize changes nothing about it.
+        "restart_rows": R or "restart_interval": N in the dict: restart intervals, as Solver.to_jpeg(restart_rows=, restart_interval=)
+        (j2p_batch_submit_jpeg_opt, j2p_batch_submit_file_jpeg_opt).  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
         reaches; a larger file fails the job with the size it needs in the message);
         samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
         out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit

@@ -42,7 +42,7 @@ UNIT_HEADERS = {
     "j2p_solver.hip": ("j2p_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h", "j2p_geometry.h"),
     "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
     "j2p_codec.hip": ("j2p_codec_kernels.hip.h", "j2p_progressive_kernels.hip.h", "j2p_decode_kernels.hip.h", "j2p_scan_decode_kernels.hip.h", "j2p_png_kernels.hip.h",
-                      "j2p_hip_host.h", "j2p_internal.h", "j2p_coder_block.h", "j2p_huffman.h", "j2p_deflate.h"),
+                      "j2p_hip_host.h", "j2p_internal.h", "j2p_coder_block.h", "j2p_huffman.h", "j2p_deflate.h", "j2p_restart.h"),
     "j2p_pool.hip": ("j2p_hip_host.h", "j2p_internal.h"),
     "j2p_tiled.hip": ("j2p_internal.h", "j2p_geometry.h"),
     "j2p_batch.hip": ("j2p_internal.h", "j2p_geometry.h"),

@@ -24,6 +24,7 @@
 #include "j2p_coder_block.h"
 #include "j2p_hip_host.h"
 #include "j2p_huffman.h"
+#include "j2p_restart.h"
 #include "j2p_codec_kernels.hip.h"
 #include "j2p_progressive_kernels.hip.h"
 #include "j2p_decode_kernels.hip.h"
@@ -110,7 +111,7 @@ const HuffCodes &huffman_tables()
         return tables;
 }
 
-// everything in front of the entropy-coded data; at most 623 bytes (a table has at most 12 DC or 162 AC symbols, which
+// everything in front of the entropy-coded data; at most 623 bytes and the 6 of a DRI segment (a table has at most 12 DC or 162 AC symbols, which
 // j2p_encode_scan checks of the ones it makes).  Returns their number.
 constexpr size_t kJpegHeaderMax = 640;
 // a marker segment's first four bytes at p, which moves behind them: the marker and the length of `payload` bytes and itself
@@ -159,10 +160,19 @@ size_t jpeg_frame(const j2p_jpeg &spec, unsigned ncomp, uint8_t sof, uint8_t *ou
         }
         return (size_t)(p - out);
 }
-size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, uint8_t *out)
+// a DRI segment at p, which moves behind it
+void dri_segment(uint8_t *&p, unsigned interval)
+{
+        segment(p, 0xdd, 2);
+        *p++ = (uint8_t)(interval >> 8);
+        *p++ = (uint8_t)interval;
+}
+// dri: the scan's restart interval, 0 for a file without one (no DRI segment)
+size_t jpeg_header(const j2p_jpeg &spec, unsigned ncomp, const FileTables &tables, unsigned dri, uint8_t *out)
 {
         uint8_t *p = out + jpeg_frame(spec, ncomp, 0xc0, out);
         for(unsigned k = 0; k < (ncomp == 3 ? 4u : 2u); k++) { dht_segment(p, ((k & 1u) << 4) | (k >> 1), tables.t[k]); }
+        if(dri) { dri_segment(p, dri); }
         segment(p, 0xda, 1 + 2 * ncomp + 3);
         *p++ = (uint8_t)ncomp;
         for(unsigned c = 0; c < ncomp; c++) {
@@ -257,8 +267,17 @@ namespace {
 // what n streams of a JPEG file are once their FF bytes are counted
 struct Stuffed {
         size_t nbytes[J2P_PROGRESSIVE_SCANS];   // stream s before stuffing
-        ull ffs[J2P_PROGRESSIVE_SCANS + 1];     // the FF bytes of the streams before s; [n]: of all
-        size_t bytes(unsigned s) const { return nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]); }    // stream s in the file
+        ull ffs[J2P_PROGRESSIVE_SCANS + 1];     // the FF bytes, and twice the RSTn markers, of the streams before s; [n]: of all
+        unsigned markers[J2P_PROGRESSIVE_SCANS] = {0};  // the RSTn markers of stream s (restart intervals)
+        size_t bytes(unsigned s) const { return nbytes[s] + (size_t)(ffs[s + 1] - ffs[s]); }    // stream s in the file, markers included
+        ull stuffed(unsigned s) const { return ffs[s + 1] - ffs[s] - 2ull * markers[s]; }       // FF bytes of stream s that got their 00
+};
+
+// where the RSTn markers of the streams stand (restart intervals): ends_at[s] is the place in the block of stream s's nends[s] sorted
+// byte positions (k_restart_ends), which pack(s, stage) queues with the stream
+struct RestartEnds {
+        unsigned nends[J2P_PROGRESSIVE_SCANS];
+        size_t ends_at[J2P_PROGRESSIVE_SCANS];
 };
 
 // The end both JPEG coders share: n streams (a baseline file's one scan, a progressive file's scans) of bits[s] bits, through the
@@ -269,10 +288,19 @@ struct Stuffed {
 // down (a wait); place(done, to) writes the file's size and, where the buffer has room for it (or else its error ends the call), the
 // headers, and says where stream s goes on the host (to[s]); every stream is stuffed and comes down (a wait), and EOI follows the last.
 // A baseline file cannot meet the refusal: its scan has at most 6 * 8192^2 / 4 slots of less than 1700 bits, 84 million chunks.
+// restart (may be NULL: the launches are then what they were before restart intervals existed): a stream with markers is counted and
+// copied by the _restart siblings of the two kernels, and the markers are bytes of the stream from the first guess on.
 template<class Pack, class Place>
-int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part, unsigned n, const ull *bits, const Pack &pack, const Place &place)
+int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part, unsigned n, const ull *bits, const Pack &pack, const Place &place,
+                    const RestartEnds *restart = nullptr)
 {
         Stuffed done;
+        size_t marker_bytes = 0;
+        for(unsigned s = 0; restart && s < n; s++) {
+                done.markers[s] = restart->nends[s];
+                marker_bytes += 2 * (size_t)restart->nends[s];
+        }
+        const auto ends = [&](unsigned s) { return static_cast<const ull *>(block.at<ull>(restart->ends_at[s])); };
         size_t word[J2P_PROGRESSIVE_SCANS + 1] = {0}, chunk[J2P_PROGRESSIVE_SCANS + 1] = {0}, byte[J2P_PROGRESSIVE_SCANS + 1] = {0};
         for(unsigned s = 0; s < n; s++) {
                 done.nbytes[s] = (size_t)((bits[s] + 7) / 8);
@@ -291,12 +319,17 @@ int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part,
                 for(unsigned s = 0; s < n; s++) {
                         unsigned *const stage = block.at<unsigned>(stage_at) + word[s];
                         pack(s, stage);
+                        if(done.markers[s]) {
+                                hipLaunchKernelGGL(k_stuff_count_restart, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(stage),
+                                                   done.nbytes[s], chunks(s), ends(s), done.markers[s], block.at<unsigned>(count_at) + chunk[s]);
+                                continue;
+                        }
                         hipLaunchKernelGGL(k_stuff_count, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(stage), done.nbytes[s],
                                            chunks(s), block.at<unsigned>(count_at) + chunk[s]);
                 }
                 queue_scan(stream, block.at<unsigned>(count_at), nchunks, block.at<ull>(ffsums_at), block.at<ull>(ffoff_at));
         };
-        if(const int rc = block.grow(out_at + byte[n] + byte[n] / 16 + 256); rc != J2P_OK) { return rc; }
+        if(const int rc = block.grow(out_at + byte[n] + byte[n] / 16 + 256 + marker_bytes); rc != J2P_OK) { return rc; }
         block.stage(streams);
         done.ffs[0] = 0;
         for(unsigned s = 1; s < n; s++) { HIP_TRY(hipMemcpyAsync(&done.ffs[s], block.at<ull>(ffoff_at) + chunk[s], 8, hipMemcpyDeviceToHost, stream)); }
@@ -306,6 +339,14 @@ int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part,
         if(const int rc = place(done, to); rc != J2P_OK) { return rc; }
         if(const int rc = block.grow(out_at + byte[n] + (size_t)done.ffs[n]); rc != J2P_OK) { return rc; }
         for(unsigned s = 0; s < n; s++) {
+                if(done.markers[s]) {
+                        hipLaunchKernelGGL(k_stuff_copy_restart, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream,
+                                           static_cast<const unsigned *>(block.at<unsigned>(stage_at) + word[s]), done.nbytes[s], chunks(s),
+                                           static_cast<const ull *>(block.at<ull>(ffoff_at) + chunk[s]), ends(s), done.markers[s],
+                                           block.at<uint8_t>(out_at) + byte[s]);
+                        HIP_TRY(hipMemcpyAsync(to[s], block.at(out_at) + byte[s] + (size_t)done.ffs[s], done.bytes(s), hipMemcpyDeviceToHost, stream));
+                        continue;
+                }
                 hipLaunchKernelGGL(k_stuff_copy, dim3((chunks(s) + 3) / 4), dim3(256), 0, stream, static_cast<const unsigned *>(block.at<unsigned>(stage_at) + word[s]),
                                    done.nbytes[s], chunks(s), static_cast<const ull *>(block.at<ull>(ffoff_at) + chunk[s]), block.at<uint8_t>(out_at) + byte[s]);
                 HIP_TRY(hipMemcpyAsync(to[s], block.at(out_at) + byte[s] + (size_t)done.ffs[s], done.bytes(s), hipMemcpyDeviceToHost, stream));
@@ -321,6 +362,7 @@ int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part,
 // The coder (j2p_internal.h: what memory and fill are).  The block's layout, each part aligned to 256 bytes:
 //   [coefficients per component][len: nslots u32][off: nslots u64][sums: tiles + 1 u64]              known from the spec
 //   [hist: 2 x 268 u64 — only when the symbols are counted]
+//   [ends: intervals - 1 u64][padding: u64 — only with restart intervals that put a marker into the scan]
 //   [stage: the stream, ceil(bits / 32) + 1 words][count: chunks u32][ffoff: chunks u64][sums]      known once the bits are
 //   [out: the stuffed bytes]                                                                        known once the FFs are
 // so the two totals are read back (8 bytes each, a wait each) and the block is asked for three times, the first two times
@@ -331,11 +373,17 @@ int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part,
 // coefficients and the lengths: the tables are made on the host (j2p_huffman.h) and this call's own HuffCodes go to the two
 // coding kernels.  The counting is no stage: the counts live on the host from then on.  Without either, the launches, the layout
 // and the bytes are what they were before the option existed.
+// Restart intervals (include/jpeg2png_amd.h: "Restart intervals"; j2p_codec_kernels.hip.h says how) put the _restart siblings in the
+// places of the three walking kernels, k_restart_pad and a second exclusive sum into the lengths stage and k_restart_ends into the
+// stream's; the pads' sum comes down with the bits, so no wait is added.
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                     const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                    unsigned flags, j2p_encode_stats *stats)
+                    unsigned flags, j2p_encode_stats *stats, const j2p_restart_scan *restart, j2p_restart_scan_stats *restart_stats)
 {
         ScanGeom g = scan_geometry(spec, ncomp);
+        // restart intervals: ri positions each; the _restart kernels only where a marker stands (an interval that holds the whole scan
+        // changes the header alone)
+        const unsigned dri = restart ? restart->interval : 0, nint = restart ? restart->intervals : 1, ri = nint > 1 ? dri * g.per_mcu : 0;
         const bool optimise = (flags & J2P_JPEG_OPTIMIZE) != 0, counting = optimise || stats;
         HuffCodes own_codes;
         FileTables own_tables;
@@ -348,6 +396,7 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         const size_t coef_bytes = part.total;
         const size_t len_at = part((size_t)nslots * 4), off_at = part((size_t)nslots * 8), sums_at = part(((size_t)slot_tiles + 1) * 8);
         const size_t hist_at = counting ? part(kHistogramEntries * 8) : 0;
+        const size_t ends_at = ri ? part((size_t)(nint - 1) * 8) : 0, padding_at = ri ? part(8) : 0;
         const size_t fixed = part.total;
         j2p_coder_block block(memory);
         const unsigned per_workgroup = 4 * kEntropyIters, coding_grid = (nslots + per_workgroup - 1) / per_workgroup;
@@ -359,6 +408,17 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         };
         // from the coefficients to the bit offsets
         const auto lengths = [&] {
+                if(ri) {
+                        // every interval's pad from the unpadded offsets into its last position's length; the offsets once more
+                        hipLaunchKernelGGL(k_entropy_lengths_restart, dim3(coding_grid), dim3(256), 0, stream, g, *codes, ri, block.at<unsigned>(len_at));
+                        queue_scan(stream, block.at<unsigned>(len_at), nslots, block.at<ull>(sums_at), block.at<ull>(off_at));
+                        (void)hipMemsetAsync(block.at(padding_at), 0, 8, stream);
+                        hipLaunchKernelGGL(k_restart_pad, dim3((nint + 255) / 256), dim3(256), 0, stream, block.at<unsigned>(len_at),
+                                           static_cast<const ull *>(block.at<ull>(off_at)), static_cast<const ull *>(block.at<ull>(sums_at) + slot_tiles), nslots, ri,
+                                           nint, block.at<ull>(padding_at));
+                        queue_scan(stream, block.at<unsigned>(len_at), nslots, block.at<ull>(sums_at), block.at<ull>(off_at));
+                        return;
+                }
                 hipLaunchKernelGGL(k_entropy_lengths, dim3(coding_grid), dim3(256), 0, stream, g, *codes, block.at<unsigned>(len_at));
                 queue_scan(stream, block.at<unsigned>(len_at), nslots, block.at<ull>(sums_at), block.at<ull>(off_at));
         };
@@ -368,7 +428,11 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
         if(counting) {
                 unsigned long long hist[kHistogramEntries];
                 HIP_TRY(hipMemsetAsync(block.at(hist_at), 0, sizeof(hist), stream));
-                hipLaunchKernelGGL(k_entropy_histogram, dim3(coding_grid), dim3(256), 0, stream, g, block.at<ull>(hist_at));
+                if(ri) {
+                        hipLaunchKernelGGL(k_entropy_histogram_restart, dim3(coding_grid), dim3(256), 0, stream, g, ri, block.at<ull>(hist_at));
+                } else {
+                        hipLaunchKernelGGL(k_entropy_histogram, dim3(coding_grid), dim3(256), 0, stream, g, block.at<ull>(hist_at));
+                }
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipMemcpyAsync(hist, block.at(hist_at), sizeof(hist), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipStreamSynchronize(stream));
@@ -382,19 +446,32 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                 }
         }
         block.stage(lengths);
-        ull bits = 0;
+        ull bits = 0, padding = 0;        // (with intervals `bits` holds every interval's pad, the last one's too)
         HIP_TRY(hipMemcpyAsync(&bits, block.at<ull>(sums_at) + slot_tiles, 8, hipMemcpyDeviceToHost, stream));
+        if(ri) { HIP_TRY(hipMemcpyAsync(&padding, block.at(padding_at), 8, hipMemcpyDeviceToHost, stream)); }
         HIP_TRY(hipStreamSynchronize(stream));
+        if(restart_stats) { *restart_stats = {dri, nint, ri ? padding : (0ull - bits) & 7ull, 0}; }
+        RestartEnds ends;
+        ends.nends[0] = nint - 1;
+        ends.ends_at[0] = ends_at;
         return stuffed_streams(
                 stream, block, part, 1, &bits,
                 [&](unsigned, unsigned *stage) {
+                        if(ri) {
+                                hipLaunchKernelGGL(k_entropy_pack_restart, dim3(coding_grid), dim3(256), 0, stream, g, *codes, ri,
+                                                   static_cast<const ull *>(block.at<ull>(off_at)), stage);
+                                hipLaunchKernelGGL(k_restart_ends, dim3((nint - 1 + 255) / 256), dim3(256), 0, stream,
+                                                   static_cast<const ull *>(block.at<ull>(off_at)), ri, nint - 1, block.at<ull>(ends_at));
+                                return;
+                        }
                         hipLaunchKernelGGL(k_entropy_pack, dim3(coding_grid), dim3(256), 0, stream, g, *codes,
                                            static_cast<const ull *>(block.at<ull>(off_at)), stage);
                 },
                 [&](const Stuffed &done, uint8_t **to) {
-                        if(stats) { stats->scan_bits = bits, stats->stuffed_bytes = done.ffs[1]; }
+                        if(stats) { stats->scan_bits = bits - padding, stats->stuffed_bytes = done.stuffed(0); }
+                        if(restart_stats) { restart_stats->markers = done.markers[0]; }
                         uint8_t header[kJpegHeaderMax];
-                        const size_t header_bytes = jpeg_header(spec, ncomp, *tables, header);
+                        const size_t header_bytes = jpeg_header(spec, ncomp, *tables, dri, header);
                         *size = header_bytes + done.bytes(0) + 2;
                         if(capacity < *size || !out_host) {
                                 return j2p_fail(J2P_ESPACE, "jpeg: the file has %zu bytes, the buffer %zu", *size, out_host ? capacity : 0);
@@ -402,7 +479,8 @@ int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, co
                         memcpy(out_host, header, header_bytes);
                         to[0] = out_host + header_bytes;
                         return (int)J2P_OK;
-                });
+                },
+                ri ? &ends : nullptr);
 }
 
 // ---- the progressive file: k_prog_* (j2p_progressive_kernels.hip.h), k_scan_*, k_stuff_* ----
@@ -429,12 +507,15 @@ unsigned prog_scan_tables(const ProgScript &s, unsigned table[2])
         return 1;
 }
 
-// a scan's DHT segments and SOS; at most 2 * 277 + 14 bytes.  Returns their number.
+// a scan's DHT segments, DRI and SOS; at most 2 * 277 + 6 + 14 bytes.  Returns their number.
 constexpr size_t kProgScanHeaderMax = 576;
-size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned table[2], const j2p_huff_table made[2], uint8_t *out)
+// restart: the scan's entry of the restart plan (NULL: none): its DRI segment, where the plan has one, stands in front of the SOS
+size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned table[2], const j2p_huff_table made[2], const j2p_restart_scan *restart,
+                        uint8_t *out)
 {
         uint8_t *p = out;
         for(unsigned k = 0; k < ntables; k++) { dht_segment(p, table[k], made[k]); }
+        if(restart && restart->dri) { dri_segment(p, restart->interval); }
         segment(p, 0xda, 1 + 2 * s.ncomp + 3);
         *p++ = (uint8_t)s.ncomp;
         for(unsigned i = 0; i < s.ncomp; i++) {
@@ -454,6 +535,7 @@ size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned ta
 // (AC); all scans' items stand in one row, scan after scan.  The block's layout, each part aligned to 256 bytes:
 //   [coefficients per component][len: items u32][off: items u64][sums][per AC scan — flags: blocks u8][per AC scan — run: blocks u32]
 //   [hist: scans x 512 u64][flushes: scans u64]                                                      known from the spec
+//   [per scan with restart markers — ends: intervals - 1 u64][padding: scans u64 — only with such a scan]
 //   [stage: every scan's stream, ceil(bits / 32) + 1 words each][count: chunks u32][ffoff: chunks u64][sums]   once the bits are
 //   [out: every scan's stuffed bytes, one behind the other]                                          once the FFs are
 // ONE exclusive sum places the items of all scans (a scan's stream starts at its first item's offset) and ONE the FF counts of all
@@ -463,18 +545,25 @@ size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned ta
 // stuffed_streams every scan's stream.  The walk that counts is no stage: the counts and tables live on the host by then.
 int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                            const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                           j2p_progressive_stats *stats)
+                           j2p_progressive_stats *stats, const j2p_restart_plan *restart, j2p_restart_stats *restart_stats)
 {
         ScanGeom g = scan_geometry(spec, ncomp);
         const ProgScript *const script = ncomp == 3 ? kProgColour : kProgGrey;
         const unsigned nscans = ncomp == 3 ? 10 : 6;
         ProgScan scan[J2P_PROGRESSIVE_SCANS];
         size_t first[J2P_PROGRESSIVE_SCANS + 1] = {0};
+        // restart intervals: ri[s] items each in scan s, nint[s] of them; ri 0 where no marker stands (no intervals, or one that holds
+        // the whole scan), and such a scan's launches are the ones it had before restart intervals existed
+        unsigned ri[J2P_PROGRESSIVE_SCANS] = {0}, nint[J2P_PROGRESSIVE_SCANS];
+        bool restarts = false;
         for(unsigned s = 0; s < nscans; s++) {
                 const ProgScript &k = script[s];
                 const unsigned c = k.comp[0];
                 scan[s] = {k.ss, k.se, k.al, k.ah ? 1u : 0u, k.ss == 0 ? g.nslots : g.bw[c] * g.bh[c]};
                 first[s + 1] = first[s] + scan[s].n;
+                nint[s] = restart ? restart->scan[s].intervals : 1;
+                if(nint[s] > 1) { ri[s] = restart->scan[s].interval * (k.ss == 0 ? g.per_mcu : 1u); }
+                restarts = restarts || ri[s];
         }
         const size_t nitems = first[nscans];
         if(nitems > 0xffffffffull) { return j2p_fail(J2P_EINVAL, "jpeg: %zu scan positions are too many", nitems); }
@@ -493,7 +582,12 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         }
         const size_t runs_bytes = part.total - runs_at;
         const size_t hist_bytes = (size_t)nscans * (kProgHistogram + 1) * 8;
-        const size_t hist_at = part(hist_bytes), fixed = part.total;     // (the flush counters behind the counts)
+        const size_t hist_at = part(hist_bytes);                         // (the flush counters behind the counts)
+        size_t ends_at[J2P_PROGRESSIVE_SCANS] = {0};
+        for(unsigned s = 0; s < nscans; s++) {
+                if(ri[s]) { ends_at[s] = part((size_t)(nint[s] - 1) * 8); }
+        }
+        const size_t padding_at = restarts ? part((size_t)nscans * 8) : 0, fixed = part.total;
         j2p_coder_block block(memory);
         const auto grid = [](unsigned n) { return dim3((n + 255) / 256); };
         static const ProgCodes no_codes = {};
@@ -511,6 +605,12 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                         const unsigned per_workgroup = 4 * kEntropyIters;
                         hipLaunchKernelGGL(k_prog_classify, dim3((scan[s].n + per_workgroup - 1) / per_workgroup), dim3(256), 0, stream,
                                            coef[script[s].comp[0]], scan[s], block.at<uint8_t>(flags_at[s]));
+                        if(ri[s]) {
+                                hipLaunchKernelGGL(k_prog_runs_restart, grid(scan[s].n), dim3(256), 0, stream,
+                                                   static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])), scan[s], ri[s], block.at<unsigned>(run_at[s]),
+                                                   block.at<ull>(hist_at) + (size_t)nscans * kProgHistogram + s);
+                                continue;
+                        }
                         hipLaunchKernelGGL(k_prog_runs, grid(scan[s].n), dim3(256), 0, stream, static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])),
                                            scan[s], block.at<unsigned>(run_at[s]), block.at<ull>(hist_at) + (size_t)nscans * kProgHistogram + s);
                 }
@@ -523,7 +623,16 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                 const ull *const off = block.at<ull>(off_at) + first[s];
                 if(scan[s].ss == 0) {
                         if(kMode == kProgCount && scan[s].refine) { return; }
+                        if(ri[s]) {
+                                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_dc_restart<kMode>), grid(scan[s].n), dim3(256), 0, stream, g, scan[s], ri[s], codes[s], hist,
+                                                   len, off, stage);
+                                return;
+                        }
                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_dc<kMode>), grid(scan[s].n), dim3(256), 0, stream, g, scan[s], codes[s], hist, len, off, stage);
+                } else if(kMode == kProgPack && ri[s]) {
+                        hipLaunchKernelGGL(k_prog_ac_pack_restart, grid(scan[s].n), dim3(256), 0, stream, coef[script[s].comp[0]], scan[s], ri[s],
+                                           static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])), static_cast<const unsigned *>(block.at<unsigned>(run_at[s])),
+                                           codes[s], off, stage);
                 } else {
                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prog_ac<kMode>), grid(scan[s].n), dim3(256), 0, stream, coef[script[s].comp[0]], scan[s],
                                            static_cast<const uint8_t *>(block.at<uint8_t>(flags_at[s])), static_cast<const unsigned *>(block.at<unsigned>(run_at[s])),
@@ -532,6 +641,17 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         };
         const auto lengths = [&] {
                 for(unsigned s = 0; s < nscans; s++) { walk(std::integral_constant<int, kProgLength>(), s, nullptr); }
+                queue_scan(stream, block.at<unsigned>(len_at), (unsigned)nitems, block.at<ull>(sums_at), block.at<ull>(off_at));
+                if(!restarts) { return; }
+                // every interval's pad from the unpadded offsets into its last item's length; the offsets once more
+                (void)hipMemsetAsync(block.at(padding_at), 0, (size_t)nscans * 8, stream);
+                for(unsigned s = 0; s < nscans; s++) {
+                        if(!ri[s]) { continue; }
+                        const ull *const behind = s + 1 < nscans ? block.at<ull>(off_at) + first[s + 1] : block.at<ull>(sums_at) + item_tiles;
+                        hipLaunchKernelGGL(k_restart_pad, grid(nint[s]), dim3(256), 0, stream, block.at<unsigned>(len_at) + first[s],
+                                           static_cast<const ull *>(block.at<ull>(off_at) + first[s]), behind, scan[s].n, ri[s], nint[s],
+                                           block.at<ull>(padding_at) + s);
+                }
                 queue_scan(stream, block.at<unsigned>(len_at), (unsigned)nitems, block.at<ull>(sums_at), block.at<ull>(off_at));
         };
         if(const int rc = block.grow(fixed + coef_bytes / 4); rc != J2P_OK) { return rc; }
@@ -584,14 +704,33 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
         ull begins[J2P_PROGRESSIVE_SCANS + 1] = {0}, bits[J2P_PROGRESSIVE_SCANS];
         for(unsigned s = 1; s < nscans; s++) { HIP_TRY(hipMemcpyAsync(&begins[s], block.at<ull>(off_at) + first[s], 8, hipMemcpyDeviceToHost, stream)); }
         HIP_TRY(hipMemcpyAsync(&begins[nscans], block.at<ull>(sums_at) + item_tiles, 8, hipMemcpyDeviceToHost, stream));
+        ull padding[J2P_PROGRESSIVE_SCANS] = {0};       // (a scan with intervals: its bits hold every interval's pad, the last one's too)
+        if(restarts) { HIP_TRY(hipMemcpyAsync(padding, block.at(padding_at), (size_t)nscans * 8, hipMemcpyDeviceToHost, stream)); }
         HIP_TRY(hipStreamSynchronize(stream));
+        RestartEnds ends;
+        if(restart_stats) {
+                memset(restart_stats, 0, sizeof(*restart_stats));
+                restart_stats->nscans = nscans;
+        }
         for(unsigned s = 0; s < nscans; s++) {
                 bits[s] = begins[s + 1] - begins[s];
-                if(stats) { stats->scan[s].bits = bits[s]; }
+                if(stats) { stats->scan[s].bits = bits[s] - padding[s]; }
+                ends.nends[s] = ri[s] ? nint[s] - 1 : 0;
+                ends.ends_at[s] = ends_at[s];
+                if(restart_stats) {
+                        restart_stats->scan[s] = {restart ? restart->scan[s].interval : 0, nint[s], ri[s] ? padding[s] : (0ull - bits[s]) & 7ull, ends.nends[s]};
+                }
         }
         // waits 3 and 4: every scan's FF bytes; the scans' bytes to their places in the file, the headers between them
         return stuffed_streams(
-                stream, block, part, nscans, bits, [&](unsigned s, unsigned *stage) { walk(std::integral_constant<int, kProgPack>(), s, stage); },
+                stream, block, part, nscans, bits,
+                [&](unsigned s, unsigned *stage) {
+                        walk(std::integral_constant<int, kProgPack>(), s, stage);
+                        if(ri[s]) {
+                                hipLaunchKernelGGL(k_restart_ends, grid(nint[s] - 1), dim3(256), 0, stream, static_cast<const ull *>(block.at<ull>(off_at) + first[s]),
+                                                   ri[s], nint[s] - 1, block.at<ull>(ends_at[s]));
+                        }
+                },
                 [&](const Stuffed &done, uint8_t **to) {
                         uint8_t frame[256];
                         std::vector<uint8_t> heads;
@@ -601,8 +740,9 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                                 heads.resize((size_t)nscans * kProgScanHeaderMax);
                         } catch(const std::bad_alloc &) { return j2p_fail(J2P_ENOMEM, "out of memory"); }
                         for(unsigned s = 0; s < nscans; s++) {
-                                if(stats) { stats->scan[s].stuffed_bytes = done.ffs[s + 1] - done.ffs[s]; }
-                                head_at[s + 1] = head_at[s] + prog_scan_header(script[s], ntables[s], table[s], made[s], heads.data() + head_at[s]);
+                                if(stats) { stats->scan[s].stuffed_bytes = done.stuffed(s); }
+                                head_at[s + 1] = head_at[s] + prog_scan_header(script[s], ntables[s], table[s], made[s], restart ? &restart->scan[s] : nullptr,
+                                                                                 heads.data() + head_at[s]);
                         }
                         *size = frame_bytes + head_at[nscans] + 2;
                         for(unsigned s = 0; s < nscans; s++) { *size += done.bytes(s); }
@@ -617,7 +757,39 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                                 p = to[s] + done.bytes(s);
                         }
                         return (int)J2P_OK;
-                });
+                },
+                restarts ? &ends : nullptr);
+}
+
+const char *j2p_jpeg_options_error(const j2p_jpeg_options *options)
+{
+        if(!options) { return "jpeg: NULL options"; }
+        if(const char *why = j2p_jpeg_flags_error(options->flags)) { return why; }
+        if(options->progressive > 1) { return "jpeg: progressive is 0 or 1"; }
+        return j2p_restart_error(options->restart_interval, options->restart_in_rows);
+}
+
+int j2p_encode_options(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const j2p_jpeg_options &options,
+                       const std::function<int(size_t, void **, bool *)> &memory, const std::function<void(hipStream_t, int16_t *const[3])> &fill,
+                       uint8_t *out_host, size_t capacity, size_t *size, j2p_encode_stats *stats, j2p_progressive_stats *progressive_stats,
+                       j2p_restart_stats *restart_stats)
+{
+        const bool restarts = options.restart_interval || options.restart_in_rows;
+        const j2p_restart_plan plan = j2p_restart_plan_of(spec.width, spec.height, ncomp, spec.sub_w, spec.sub_h, options.progressive != 0,
+                                                          options.restart_interval, options.restart_in_rows);
+        if(restart_stats) { memset(restart_stats, 0, sizeof(*restart_stats)); }
+        if(options.progressive) {
+                return j2p_encode_progressive(stream, spec, ncomp, memory, fill, out_host, capacity, size, progressive_stats, restarts ? &plan : nullptr,
+                                              restart_stats);
+        }
+        j2p_restart_scan_stats one = {0, 0, 0, 0};
+        const int rc = j2p_encode_scan(stream, spec, ncomp, memory, fill, out_host, capacity, size, options.flags, stats, restarts ? &plan.scan[0] : nullptr,
+                                       restart_stats ? &one : nullptr);
+        if(restart_stats && one.intervals) {
+                restart_stats->nscans = 1;
+                restart_stats->scan[0] = one;
+        }
+        return rc;
 }
 
 // the device of a j2p_entropy_* call
@@ -719,6 +891,29 @@ int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const co
                        size_t *size)
 {
         return j2p_entropy_encode_ex(device, spec, coef_host, ncomp, out_host, capacity, size, 0, nullptr);
+}
+
+int j2p_entropy_encode_opt(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                           size_t *size, const j2p_jpeg_options *options, j2p_encode_stats *stats, j2p_progressive_stats *progressive_stats,
+                           j2p_restart_stats *restart_stats)
+{
+        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_options_error(options)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
+                return j2p_encode_options(stream, *spec, ncomp, *options, memory, fill, out_host, capacity, size, stats, progressive_stats, restart_stats);
+        });
+}
+
+int j2p_debug_restart_plan(unsigned width, unsigned height, unsigned ncomp, unsigned sub_w, unsigned sub_h, const j2p_jpeg_options *options,
+                           j2p_restart_plan *plan)
+{
+        if(!plan) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_options_error(options)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        if((ncomp != 1 && ncomp != 3) || width < 1 || height < 1 || width > 65535 || height > 65535 || sub_w < 1 || sub_w > 2 || sub_h < 1 || sub_h > 2) {
+                return j2p_fail(J2P_EINVAL, "jpeg: no such file: %ux%u, %u components, %ux%u blocks of the first in an MCU", width, height, ncomp, sub_w, sub_h);
+        }
+        *plan = j2p_restart_plan_of(width, height, ncomp, sub_w, sub_h, options->progressive != 0, options->restart_interval, options->restart_in_rows);
+        return J2P_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // jpeg2png_amd — gfx950 device code of the JPEG codec's coder: quantised coefficients in device memory into the entropy-coded
 // data of a JPEG file (k_entropy_lengths, k_scan_*, k_entropy_pack, k_stuff_*; k_entropy_histogram counts the symbols for
-// tables made for the image).  Included by j2p_codec.hip alone, in front of
+// tables made for the image; the k_*_restart siblings and k_restart_* at the end are for files with restart intervals).
+// Included by j2p_codec.hip alone, in front of
 // j2p_decode_kernels.hip.h, which reuses the k_scan_* kernels for the way back.  It shares nothing with the output stage's
 // kernels (j2p_output_kernels.hip.h): k_quantise_blocks, which leaves the coefficients, lives there.  Compiled with the
 // same flags as every device unit.
@@ -383,6 +384,252 @@ __global__ __launch_bounds__(256) void k_stuff_copy(const unsigned *stage, size_
                 const uint8_t byte = (uint8_t)(x >> (8 * k));
                 *dst++ = byte;
                 if(byte == 0xff) { *dst++ = 0; }
+        }
+}
+
+// ---- restart intervals (include/jpeg2png_amd.h: "Restart intervals"): a scan's items — its positions, or an AC scan's blocks —
+// in intervals of ri items, nint of them, the last possibly shorter ----
+// Every interval is completed to a byte with 1-bits, so every interval STARTS on a byte and its pad is (-its bits) mod 8, which the
+// unpadded offsets give without anybody waiting for anybody:
+//   k_restart_pad       a lane per interval adds the pad to the length of the interval's last item; the exclusive sum is queued again
+//   k_restart_ends      a lane per interval but the last: the byte of the padded stream behind which its RSTn marker stands   -> ends[]
+// The staging stream stays pure data.  The markers go in where the FFs are stuffed: ends[] is sorted (an interval has at least one
+// bit, so at least a byte), k_stuff_count_restart adds 2 per end inside its chunk, k_stuff_copy_restart shifts every byte by the
+// FFs and twice the ends in front of it, and the lane that holds the byte in front of an end writes FF, D0 + (ordinal & 7) behind it.
+
+// scan_dc_predictor in a scan with restart intervals of `ri` positions (whole MCUs; include/jpeg2png_amd.h: "Restart intervals"):
+// 0 for the first real block of a component in its interval — the walk never goes behind the interval's first MCU — and within
+// the interval as above, a dummy block repeating its predecessor
+__device__ __forceinline__ int scan_dc_predictor_restart(const ScanGeom &g, unsigned slot, unsigned ri)
+{
+        const unsigned begin = slot / ri * ri;
+        if(g.ncomp == 1) { return slot > begin ? g.coef[0][(size_t)(slot - 1) * 64] : 0; }
+        unsigned mcu = slot / g.per_mcu, k = slot - mcu * g.per_mcu;
+        const unsigned hv = g.per_mcu - 2, mcu0 = begin / g.per_mcu;
+        if(k >= hv) { return mcu > mcu0 ? g.coef[1 + k - hv][(size_t)(mcu - 1) * 64] : 0; }
+        for(;;) {
+                if(k == 0) {
+                        if(mcu == mcu0) { return 0; }
+                        mcu--;
+                        k = hv - 1;
+                } else {
+                        k--;
+                }
+                unsigned c;
+                size_t block;
+                if(scan_block(g, mcu * g.per_mcu + k, c, block)) { return g.coef[0][block * 64]; }
+        }
+}
+
+// scan_value with that predictor
+__device__ __forceinline__ int scan_value_restart(const ScanGeom &g, unsigned slot, int lane, unsigned *table, unsigned ri)
+{
+        unsigned c;
+        size_t block;
+        const bool real = scan_block(g, slot, c, block);
+        *table = c ? 1 : 0;
+        if(!real) { return 0; }
+        const int v = g.coef[c][block * 64 + kZigzagNatural[lane]];
+        return lane == 0 ? v - scan_dc_predictor_restart(g, slot, ri) : v;
+}
+
+// The three walking kernels for a scan with restart intervals of ri positions: k_entropy_lengths, k_entropy_histogram and
+// k_entropy_pack line for line, but that the DC differences are taken against scan_dc_predictor_restart and that the wavefront of
+// EVERY interval's last position sets the 1-bits that complete its byte — every interval starts on a byte (k_restart_pad), so the
+// pad is known from the position's own end.  Copies and no template: the kernels above stay, text and machine code, what they were.
+__global__ __launch_bounds__(256) void k_entropy_lengths_restart(ScanGeom g, HuffCodes h, unsigned ri, unsigned *len)
+{
+        __shared__ unsigned tab[2][268];
+        entropy_tables(h, tab);
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const unsigned first = (blockIdx.x * 4 + wave) * kEntropyIters;
+        for(unsigned it = 0; it < kEntropyIters && first + it < g.nslots; it++) {
+                unsigned t;
+                const int v = scan_value_restart(g, first + it, lane, &t, ri);
+                unsigned n = entropy_lane(tab[t], tab[t] + 12, lane, v, __ballot(lane > 0 && v != 0)).n;
+#pragma unroll
+                for(int d = 32; d >= 1; d >>= 1) { n += __shfl_xor(n, d); }
+                if(lane == 0) { len[first + it] = n; }
+        }
+}
+
+
+__global__ __launch_bounds__(256) void k_entropy_histogram_restart(ScanGeom g, unsigned ri, unsigned long long *hist)
+{
+        __shared__ unsigned count[kHistogramEntries];
+        for(unsigned i = threadIdx.x; i < kHistogramEntries; i += 256) { count[i] = 0; }
+        __syncthreads();
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const unsigned first = (blockIdx.x * 4 + wave) * kEntropyIters;
+        for(unsigned it = 0; it < kEntropyIters && first + it < g.nslots; it++) {
+                unsigned t;
+                const int v = scan_value_restart(g, first + it, lane, &t, ri);
+                const unsigned long long nz = __ballot(lane > 0 && v != 0);
+                const unsigned a = (unsigned)(v < 0 ? -v : v);
+                const unsigned s = 32u - (unsigned)__clz((int)a);
+                unsigned *mine = count + t * 268u;      // (every index below stays under 268 whatever the coefficients hold)
+                if(lane == 0) {
+                        atomicAdd(&mine[s < 12u ? s : 11u], 1u);
+                } else if(v != 0) {
+                        const unsigned long long before = (nz | 1ull) & ((1ull << lane) - 1ull);
+                        const unsigned run = (unsigned)lane - 1u - (63u - (unsigned)__clzll((long long)before));
+                        atomicAdd(&mine[12u + ((((run & 15u) << 4) | s) & 255u)], 1u);
+                        if(run >> 4) { atomicAdd(&mine[12u + 0xf0u], run >> 4); }
+                } else if(lane == 63) {
+                        atomicAdd(&mine[12u], 1u);
+                }
+        }
+        __syncthreads();
+        for(unsigned i = threadIdx.x; i < kHistogramEntries; i += 256) {
+                if(const unsigned n = count[i]) { atomicAdd(&hist[i], (unsigned long long)n); }
+        }
+}
+
+
+__global__ __launch_bounds__(256) void k_entropy_pack_restart(ScanGeom g, HuffCodes h, unsigned ri, const unsigned long long *off, unsigned *stage)
+{
+        __shared__ unsigned tab[2][268];
+        __shared__ unsigned words[4][kEntropyWords];
+        if(threadIdx.x < 4 * kEntropyWords) { (&words[0][0])[threadIdx.x] = 0; }
+        entropy_tables(h, tab);
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const unsigned first = (blockIdx.x * 4 + wave) * kEntropyIters;
+        for(unsigned it = 0; it < kEntropyIters; it++) {                // (the same trips for every wavefront: barriers inside)
+                const unsigned slot = first + it;
+                const bool live = slot < g.nslots;
+                unsigned long long base = 0;
+                unsigned total = 0;
+                if(live) {
+                        unsigned t;
+                        const int v = scan_value_restart(g, slot, lane, &t, ri);
+                        const LaneCode code = entropy_lane(tab[t], tab[t] + 12, lane, v, __ballot(lane > 0 && v != 0));
+                        unsigned incl = code.n;
+#pragma unroll
+                        for(int d = 1; d < 64; d <<= 1) {
+                                const unsigned up = __shfl_up(incl, d);
+                                if(lane >= d) { incl += up; }
+                        }
+                        total = __shfl(incl, 63);
+                        base = off[slot];
+                        if(code.n) {
+                                // the lane's bits at bit p of the wavefront's buffer (bit 0: the highest bit of word 0): three words
+                                const unsigned p = (unsigned)(base & 31u) + incl - code.n, w = p >> 5, b = p & 31u;
+                                const unsigned long long val = code.bits << (64u - code.n);
+                                const unsigned part[3] = {(unsigned)(val >> (32u + b)), (unsigned)(val >> b), (unsigned)(val << (32u - b))};
+#pragma unroll
+                                for(unsigned k = 0; k < 3; k++) {
+                                        if(part[k] && w + k < kEntropyWords) { atomicOr(&words[wave][w + k], part[k]); }
+                                }
+                        }
+                }
+                __syncthreads();
+                if(live) {
+                        const unsigned nwords = ((unsigned)(base & 31u) + total + 31u) >> 5;    // (at most 53)
+                        if((unsigned)lane < nwords) {
+                                const unsigned x = __builtin_bswap32(words[wave][lane]);         // the stream is bytes: big-endian words
+                                words[wave][lane] = 0;
+                                unsigned *dst = stage + (size_t)(base >> 5) + lane;
+                                if(lane == 0 || (unsigned)lane == nwords - 1) {
+                                        if(x) { atomicOr(dst, x); }                              // shared with the neighbours
+                                } else {
+                                        *dst = x;
+                                }
+                        }
+                        if((slot == g.nslots - 1 || (slot + 1) % ri == 0) && lane == 0) {
+                                const unsigned long long end = base + total;
+                                const unsigned pad = (8u - (unsigned)(end & 7u)) & 7u;
+                                if(pad) { atomicOr(stage + (size_t)(end >> 5), __builtin_bswap32(((1u << pad) - 1u) << (32u - (unsigned)(end & 31u) - pad))); }
+                        }
+                }
+                __syncthreads();
+        }
+}
+
+// len, off: the scan's items and their unpadded offsets; *total: the offset behind the last.  *padding += the pads.
+__global__ __launch_bounds__(256) void k_restart_pad(unsigned *len, const unsigned long long *off, const unsigned long long *total, unsigned n,
+                                                     unsigned ri, unsigned nint, unsigned long long *padding)
+{
+        const unsigned i = blockIdx.x * 256 + threadIdx.x;
+        if(i >= nint) { return; }
+        const unsigned long long begin = (unsigned long long)i * ri, end = begin + ri < n ? begin + ri : n;
+        const unsigned long long bits = (end < n ? off[end] : *total) - off[begin];
+        const unsigned pad = (unsigned)(0ull - bits) & 7u;
+        if(pad) {
+                len[end - 1] += pad;
+                atomicAdd(padding, (unsigned long long)pad);
+        }
+}
+
+// off: the items' padded offsets, off[0] at the scan's first byte; ends[i]: bytes of the scan's stream in front of marker i
+__global__ __launch_bounds__(256) void k_restart_ends(const unsigned long long *off, unsigned ri, unsigned nends, unsigned long long *ends)
+{
+        const unsigned i = blockIdx.x * 256 + threadIdx.x;
+        if(i < nends) { ends[i] = (off[((size_t)i + 1) * ri] - off[0]) >> 3; }
+}
+
+// the ends at or below byte `at`: the ordinal of the first marker that stands behind byte `at` or later
+__device__ __forceinline__ unsigned restart_ends_before(const unsigned long long *ends, unsigned nends, unsigned long long at)
+{
+        unsigned lo = 0, hi = nends;
+        while(lo < hi) {
+                const unsigned mid = lo + (hi - lo) / 2;
+                if(ends[mid] <= at) {
+                        lo = mid + 1;
+                } else {
+                        hi = mid;
+                }
+        }
+        return lo;
+}
+
+// k_stuff_count with 2 more for every marker behind a byte of the chunk
+__global__ __launch_bounds__(256) void k_stuff_count_restart(const unsigned *stage, size_t nbytes, unsigned nchunks, const unsigned long long *ends,
+                                                             unsigned nends, unsigned *count)
+{
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned chunk = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        if(chunk >= nchunks) { return; }
+        unsigned ff;
+        (void)stuff_word(stage, nbytes, chunk, lane, &ff);
+#pragma unroll
+        for(int d = 32; d >= 1; d >>= 1) { ff += __shfl_xor(ff, d); }
+        if(lane == 0) {
+                const unsigned long long at = (unsigned long long)chunk * kStuffChunk;
+                count[chunk] = ff + 2u * (restart_ends_before(ends, nends, at + kStuffChunk) - restart_ends_before(ends, nends, at));
+        }
+}
+
+// k_stuff_copy with the markers: ffoff[chunk] counts the FFs and twice the markers in front of the chunk
+__global__ __launch_bounds__(256) void k_stuff_copy_restart(const unsigned *stage, size_t nbytes, unsigned nchunks, const unsigned long long *ffoff,
+                                                            const unsigned long long *ends, unsigned nends, uint8_t *out)
+{
+        const int lane = (int)threadIdx.x & 63;
+        const unsigned chunk = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        if(chunk >= nchunks) { return; }
+        unsigned ff;
+        const unsigned x = stuff_word(stage, nbytes, chunk, lane, &ff);
+        const size_t at = (size_t)chunk * kStuffChunk + (size_t)lane * 4;
+        unsigned marker = restart_ends_before(ends, nends, at);
+        const unsigned extra = ff + 2u * (restart_ends_before(ends, nends, at + 4) - marker);
+        unsigned incl = extra;
+#pragma unroll
+        for(int d = 1; d < 64; d <<= 1) {
+                const unsigned up = __shfl_up(incl, d);
+                if(lane >= d) { incl += up; }
+        }
+        uint8_t *dst = out + at + ffoff[chunk] + (incl - extra);
+        for(unsigned k = 0; k < 4 && at + k < nbytes; k++) {
+                const uint8_t byte = (uint8_t)(x >> (8 * k));
+                *dst++ = byte;
+                if(byte == 0xff) { *dst++ = 0; }
+                if(marker < nends && ends[marker] == at + k + 1) {
+                        *dst++ = 0xff;
+                        *dst++ = (uint8_t)(0xd0u + (marker & 7u));
+                        marker++;
+                }
         }
 }
 

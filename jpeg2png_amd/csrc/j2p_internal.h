@@ -232,12 +232,25 @@ j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp);
 // or with stats (may be NULL), the symbols are counted on the device and the stream is waited for once more on the way.
 int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                     const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                    unsigned flags = 0, j2p_encode_stats *stats = nullptr);
+                    unsigned flags = 0, j2p_encode_stats *stats = nullptr, const j2p_restart_scan *restart = nullptr,
+                    j2p_restart_scan_stats *restart_stats = nullptr);
+// (restart: the scan's entry of the file's restart plan, j2p_restart.h — NULL, or an interval of 0, for a file without restart
+// intervals, whose launches and bytes are what they were; restart_stats may be NULL)
 // The progressive coder: j2p_encode_scan's contract with the file of "The progressive JPEG file" (include/jpeg2png_amd.h) as its
 // result.  The symbols of all scans are counted on the device; the stream is waited for four times whatever the number of scans.
 int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
                            const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                           j2p_progressive_stats *stats = nullptr);
+                           j2p_progressive_stats *stats = nullptr, const j2p_restart_plan *restart = nullptr,
+                           j2p_restart_stats *restart_stats = nullptr);
+// The coder the options of a j2p_*_opt call choose, on one footing: j2p_encode_progressive for options->progressive, else
+// j2p_encode_scan with options->flags, either with the restart plan of the options (j2p_restart.h).  options has passed
+// j2p_jpeg_options_error.  stats, progressive_stats, restart_stats: may be NULL; the one of the other coder is left alone.
+int j2p_encode_options(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const j2p_jpeg_options &options,
+                       const std::function<int(size_t, void **, bool *)> &memory, const std::function<void(hipStream_t, int16_t *const[3])> &fill,
+                       uint8_t *out_host, size_t capacity, size_t *size, j2p_encode_stats *stats = nullptr,
+                       j2p_progressive_stats *progressive_stats = nullptr, j2p_restart_stats *restart_stats = nullptr);
+// what is wrong with the options of a j2p_*_opt call, or NULL
+const char *j2p_jpeg_options_error(const j2p_jpeg_options *options);
 // what is wrong with the flags of a j2p_*_ex call that writes a JPEG file, or NULL
 static inline const char *j2p_jpeg_flags_error(unsigned flags) { return flags & ~J2P_JPEG_OPTIMIZE ? "jpeg: unknown flag bits" : nullptr; }
 

@@ -885,12 +885,12 @@ static std::function<int(size_t, void **, bool *)> scratch_memory(j2p_solver *ow
 }
 
 // the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_scan), which is the first solver's scratch
-// (progressive: j2p_encode_progressive codes them, and flags is 0)
+// (progressive: j2p_encode_progressive codes them; j2p_encode_options chooses, and hands the restart intervals on)
 static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
-                          unsigned flags, bool progressive)
+                          const j2p_jpeg_options *options)
 {
         if(!planes || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
+        if(const char *why = j2p_jpeg_options_error(options)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const char *why = j2p_jpeg_error(spec, nplane)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, nplane);
         // every check of every plane, before anything is queued
@@ -914,19 +914,26 @@ static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j
         const auto fill = [&](hipStream_t st, int16_t *const coef[3]) {
                 for(unsigned c = 0; c < nplane; c++) { quantise_queue(q[c], c ? g.sub_w : 1, c ? g.sub_h : 1, g.bw[c], 0, g.bh[c], st, coef[c]); }
         };
-        if(progressive) { return j2p_encode_progressive(stream, *spec, nplane, memory, fill, out_host, capacity, size); }
-        return j2p_encode_scan(stream, *spec, nplane, memory, fill, out_host, capacity, size, flags);
+        return j2p_encode_options(stream, *spec, nplane, *options, memory, fill, out_host, capacity, size);
+}
+
+int j2p_planes_to_jpeg_opt(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
+                           const j2p_jpeg_options *options)
+{
+        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, options);
 }
 
 int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
                           unsigned flags)
 {
-        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, flags, false);
+        const j2p_jpeg_options options = {flags, 0, 0, 0};
+        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, &options);
 }
 
 int j2p_planes_to_jpeg_progressive(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)
 {
-        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, 0, true);
+        const j2p_jpeg_options options = {0, 1, 0, 0};
+        return planes_to_jpeg(planes, nplane, spec, out_host, capacity, size, &options);
 }
 
 int j2p_planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size)

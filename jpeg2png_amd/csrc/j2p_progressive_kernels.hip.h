@@ -1,7 +1,8 @@
 // jpeg2png_amd — gfx950 device code of the progressive JPEG coder: the scans of libjpeg's jpeg_simple_progression() from the
 // quantised coefficients in device memory (include/jpeg2png_amd.h: "The progressive JPEG file").  Included by j2p_codec.hip
 // alone, behind j2p_codec_kernels.hip.h, whose scan geometry (ScanGeom, scan_block, scan_dc_predictor), exclusive sums
-// (k_scan_*) and byte stuffing (k_stuff_*) it uses as they are; it adds no line to them.
+// (k_scan_*) and byte stuffing (k_stuff_*) it uses as they are; it adds no line to them.  Restart intervals (the kRestart bodies
+// below, k_restart_* and k_stuff_*_restart there) cut the scans into intervals of items that each end on a byte.
 //
 // Every scan is a row of ITEMS whose bits follow each other in the scan's stream: a DC scan's items are the positions of
 // the interleaved scan (dummy blocks included), an AC scan's the blocks of its one component in raster order.  What makes
@@ -216,14 +217,17 @@ __global__ __launch_bounds__(256) void k_prog_classify(const int16_t *coef, Prog
 // walked by ONE lane, sixteen flag bytes a load with the next load already under way: an image that is one segment (no block
 // emits: a flat image, or a refinement scan that meets no new coefficient) is walked by one lane alone (DESIGN.md section 25:
 // measured).
+// kRestart (include/jpeg2png_amd.h: "Restart intervals"): the scan has restart intervals of ri blocks, and a block that begins an
+// interval begins a segment too — an EOB run never spans a marker; without it ri is not read.
+template <bool kRestart>
 struct ProgRunWalk {
         unsigned *run;
-        unsigned first, refine;
+        unsigned first, refine, ri;
         unsigned length = 0, waiting = 0, start = 0, made = 0;
-        // block i with flag byte f; true: it emits, the segment ended in front of it
+        // block i with flag byte f; true: it emits (or begins an interval), the segment ended in front of it
         __device__ __forceinline__ bool step(unsigned f, unsigned i)
         {
-                if(i > first && (f & kProgEmits)) { return true; }
+                if(i > first && ((f & kProgEmits) || (kRestart && i % ri == 0))) { return true; }
                 if(f & kProgTail) {
                         if(length == 0) { start = i; }
                         length++;
@@ -236,7 +240,8 @@ struct ProgRunWalk {
         // correction bits — at once
         __device__ __forceinline__ bool four(unsigned word, unsigned at)
         {
-                if(word == 0x40404040u && length > 0 && length + 4 < kProgEobRunMax) {
+                // (with intervals: only where none of the four begins one — length > 0 puts `at` behind the segment's first block)
+                if(word == 0x40404040u && length > 0 && length + 4 < kProgEobRunMax && (!kRestart || (at % ri != 0 && at % ri + 4 <= ri))) {
                         length += 4;
                         return false;
                 }
@@ -253,12 +258,13 @@ struct ProgRunWalk {
         }
 };
 
-__global__ __launch_bounds__(256) void k_prog_runs(const uint8_t *flags, ProgScan p, unsigned *run, unsigned long long *flushes)
+template <bool kRestart>
+__device__ __forceinline__ void prog_runs(const uint8_t *flags, const ProgScan &p, unsigned *run, unsigned long long *flushes, unsigned ri)
 {
         const unsigned b = blockIdx.x * 256 + threadIdx.x;
         if(b >= p.n) { return; }
-        if(b != 0 && !(flags[b] & kProgEmits)) { return; }
-        ProgRunWalk w = {run, b, p.refine};
+        if(b != 0 && !(flags[b] & kProgEmits) && !(kRestart && b % ri == 0)) { return; }
+        ProgRunWalk<kRestart> w = {run, b, p.refine, ri};
         unsigned i = b;
         bool ended = false;
         for(; i < p.n && (i & 15u) && !ended; i++) { ended = w.step(flags[i], i); }
@@ -285,6 +291,14 @@ __global__ __launch_bounds__(256) void k_prog_runs(const uint8_t *flags, ProgSca
         w.flush();
         if(w.made) { atomicAdd(flushes, (unsigned long long)w.made); }
 }
+__global__ __launch_bounds__(256) void k_prog_runs(const uint8_t *flags, ProgScan p, unsigned *run, unsigned long long *flushes)
+{
+        prog_runs<false>(flags, p, run, flushes, 0);
+}
+__global__ __launch_bounds__(256) void k_prog_runs_restart(const uint8_t *flags, ProgScan p, unsigned ri, unsigned *run, unsigned long long *flushes)
+{
+        prog_runs<true>(flags, p, run, flushes, ri);
+}
 
 // the scan's table(s) into LDS
 __device__ __forceinline__ void prog_tables(const ProgCodes &h, unsigned (*tab)[256])
@@ -304,9 +318,10 @@ __device__ __forceinline__ void prog_counts_out(const unsigned *count, unsigned 
 // ---- k_prog_ac: one AC scan of component `coef`, a lane per block ----
 // off: the bit offsets of ALL scans' items (one exclusive sum), off[0] this scan's first item's — the scan's stream starts
 // there; stage: the scan's stream, zeroed.  hist: COUNT only; h: LENGTH and PACK; len: LENGTH; off, stage: PACK.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_prog_ac(const int16_t *coef, ProgScan p, const uint8_t *flags, const unsigned *run, ProgCodes h,
-                                                 unsigned long long *hist, unsigned *len, const unsigned long long *off, unsigned *stage)
+// kRestart: intervals of ri blocks (run[] is k_prog_runs_restart's); the lane of every interval's last block completes its byte.
+template <int MODE, bool kRestart>
+__device__ __forceinline__ void prog_ac(const int16_t *coef, const ProgScan &p, const uint8_t *flags, const unsigned *run, const ProgCodes &h,
+                                        unsigned long long *hist, unsigned *len, const unsigned long long *off, unsigned *stage, unsigned ri)
 {
         __shared__ unsigned lds[kProgHistogram];
         if constexpr(MODE == kProgCount) {
@@ -344,19 +359,33 @@ __global__ __launch_bounds__(256) void k_prog_ac(const int16_t *coef, ProgScan p
                 } else {
                         ProgPackSink o(lds, stage, off[b] - off[0]);
                         item(o);
-                        o.finish(b == p.n - 1);
+                        o.finish(b == p.n - 1 || (kRestart && (b + 1) % ri == 0));
                 }
         }
         if constexpr(MODE == kProgCount) { prog_counts_out(lds, hist); }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_prog_ac(const int16_t *coef, ProgScan p, const uint8_t *flags, const unsigned *run, ProgCodes h,
+                                                 unsigned long long *hist, unsigned *len, const unsigned long long *off, unsigned *stage)
+{
+        prog_ac<MODE, false>(coef, p, flags, run, h, hist, len, off, stage, 0);
+}
+// (COUNT and LENGTH have no sibling: what a block counts and measures depends on run[] alone)
+__global__ __launch_bounds__(256) void k_prog_ac_pack_restart(const int16_t *coef, ProgScan p, unsigned ri, const uint8_t *flags, const unsigned *run,
+                                                              ProgCodes h, const unsigned long long *off, unsigned *stage)
+{
+        prog_ac<kProgPack, true>(coef, p, flags, run, h, nullptr, nullptr, off, stage, ri);
 }
 
 // ---- k_prog_dc: a DC scan of all components, a lane per position of the interleaved scan ----
 // first scan (Ah 0): the difference of DC >> Al against the component's previous position, category and magnitude bits as in the
 // baseline scan, table 0 for component 0 and table 1 for the others; refinement: the bit Al of the DC, no table.  A dummy block
 // holds its predecessor's DC: difference 0, and its predecessor's bit.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_prog_dc(ScanGeom g, ProgScan p, ProgCodes h, unsigned long long *hist, unsigned *len,
-                                                 const unsigned long long *off, unsigned *stage)
+// kRestart: intervals of ri positions — the predictor is scan_dc_predictor_restart's, and the lane of every interval's last position
+// completes its byte.
+template <int MODE, bool kRestart>
+__device__ __forceinline__ void prog_dc(const ScanGeom &g, const ProgScan &p, const ProgCodes &h, unsigned long long *hist, unsigned *len,
+                                        const unsigned long long *off, unsigned *stage, unsigned ri)
 {
         __shared__ unsigned lds[kProgHistogram];
         if constexpr(MODE == kProgCount) {
@@ -370,7 +399,7 @@ __global__ __launch_bounds__(256) void k_prog_dc(ScanGeom g, ProgScan p, ProgCod
                 unsigned c;
                 size_t block;
                 const bool real = scan_block(g, slot, c, block);
-                const int before = scan_dc_predictor(g, slot);
+                const int before = kRestart ? scan_dc_predictor_restart(g, slot, ri) : scan_dc_predictor(g, slot);
                 const int dc = real ? g.coef[c][block * 64] : before;
                 const unsigned t = c ? 1u : 0u;
                 const auto item = [&](auto &o) {
@@ -393,10 +422,22 @@ __global__ __launch_bounds__(256) void k_prog_dc(ScanGeom g, ProgScan p, ProgCod
                 } else {
                         ProgPackSink o(lds + 256 * t, stage, off[slot] - off[0]);
                         item(o);
-                        o.finish(slot == p.n - 1);
+                        o.finish(slot == p.n - 1 || (kRestart && (slot + 1) % ri == 0));
                 }
         }
         if constexpr(MODE == kProgCount) { prog_counts_out(lds, hist); }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_prog_dc(ScanGeom g, ProgScan p, ProgCodes h, unsigned long long *hist, unsigned *len,
+                                                 const unsigned long long *off, unsigned *stage)
+{
+        prog_dc<MODE, false>(g, p, h, hist, len, off, stage, 0);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_prog_dc_restart(ScanGeom g, ProgScan p, unsigned ri, ProgCodes h, unsigned long long *hist, unsigned *len,
+                                                         const unsigned long long *off, unsigned *stage)
+{
+        prog_dc<MODE, true>(g, p, h, hist, len, off, stage, ri);
 }
 
 }  // namespace j2p
