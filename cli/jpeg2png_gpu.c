@@ -26,13 +26,16 @@
  *                  and down, or down; every chroma sample is the mean of the solved values it covers (the mean the solver's
  *                  projection constrains, compute.c:351-359), taken in float on the GPU (j2p_planes_to_coefficients_sub)
  *   -O, --optimize = with -j: Huffman tables made for the image instead of the standard's (libjpeg's optimize_coding; with -e the
- *                  GPU counts the symbols, J2P_JPEG_OPTIMIZE) — the same coefficients in a smaller file, and the same file either way
+ *                  GPU counts the symbols, J2P_JPEG_OPTIMIZE in j2p_jpeg_options.flags) — the same coefficients in a smaller
+ *                  file, and the same file either way
  *   -r, --progressive = with -j: the progressive file of libjpeg's jpeg_simple_progression() — ten scans (six with -g), every one with
  *                  Huffman tables of its own (include/jpeg2png_amd.h, "The progressive JPEG file"); with -e the GPU codes every scan
- *                  (j2p_batch_submit_jpeg_progressive), without it libjpeg does — the same file either way.  -O changes nothing about it
+ *                  (j2p_batch_submit_jpeg_opt or j2p_batch_submit_file_jpeg_opt, j2p_jpeg_options.progressive), without it
+ *                  libjpeg does — the same file either way.  -O changes nothing about it
  *   -R, --restart N | NB = with -j: restart markers every N MCU rows, or with a B behind the number every N MCUs, as cjpeg -restart
  *                  spells them (libjpeg's restart_in_rows / restart_interval; include/jpeg2png_amd.h, "Restart intervals"); with -e the
- *                  GPU writes the intervals (j2p_batch_submit_jpeg_opt), without it libjpeg does — the same file either way
+ *                  GPU writes the intervals (the same two calls, j2p_jpeg_options.restart_*), without it libjpeg does — the same
+ *                  file either way
  *   -D, --decode-any-on-gpu = -d, and a progressive input's scans are all decoded on the GPU as well (j2p_batch_next_file_scans;
  *                  include/jpeg2png_amd.h, "Reading a progressive JPEG file"); a file that decoder still refuses goes to libjpeg after
  *                  the one line -d prints
@@ -392,10 +395,10 @@ struct options {
         int jpeg_quality;       /* -j: 1..100 = write a JPEG of that libjpeg quality instead of a PNG; 0 = PNG */
         bool decode_any_on_gpu; /* -D: -d, and progressive files are decoded on the GPU too (j2p_batch_next_file_scans) */
         bool decode_on_gpu;     /* -d: the input's scan is Huffman-decoded on the GPU (j2p_entropy_decode); libjpeg only for files that decoder does not read */
-        bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg) and written as it comes down */
+        bool encode_on_gpu;     /* -e: with -j, the file is entropy-coded on the GPU (j2p_batch_submit_jpeg_opt, _file_jpeg_opt) and written as it comes down */
         bool png_on_gpu;        /* -P: the PNG is coded on the GPU (j2p_batch_submit_png) and written as it comes down */
         bool auto_orient;       /* -a: the input's EXIF Orientation is applied: every output is the upright image, and carries no tag */
-        bool progressive;       /* -r: with -j, the progressive file (jpeg_simple_progression; with -e j2p_batch_submit_*_progressive) */
+        bool progressive;       /* -r: with -j, the progressive file (jpeg_simple_progression; with -e j2p_jpeg_options.progressive) */
         unsigned restart_interval, restart_in_rows;     /* -R NB, -R N: with -j, restart intervals of N MCUs or N MCU rows */
         bool optimize;          /* -O: with -j, Huffman tables made for the image (optimize_coding; with -e J2P_JPEG_OPTIMIZE) */
         unsigned sub_w, sub_h;  /* -S: the chroma components of that JPEG at 1 / sub_w x 1 / sub_h of the resolution (1 or 2) */
@@ -575,25 +578,17 @@ static void decode_file(const char *infile, const char *outfile, const struct op
                 }
                 job.out_blocks_w = job.out_blocks_h = 0;
                 job.tile = 0;           /* (a row-tiled job has no file output) */
+                /* -O, -r and -R as the one record that describes the file */
+                const j2p_jpeg_options options = {o->optimize ? J2P_JPEG_OPTIMIZE : 0u, o->progressive ? 1u : 0u, o->restart_interval, o->restart_in_rows};
                 size_t capacity = 4096 + (size_t)job.out_w * job.out_h * jp.n / 4;
                 for(int attempt = 0;; attempt++) {
                         file = malloc(capacity);
                         if(!file) { die("could not allocate image data"); }
-                        const unsigned flags = o->optimize ? J2P_JPEG_OPTIMIZE : 0u;
-                        const j2p_jpeg_options options = {flags, o->progressive ? 1u : 0u, o->restart_interval, o->restart_in_rows};
                         ORIENT_NEXT();
-                        if((o->restart_interval || o->restart_in_rows) && jp.file) {
+                        if(jp.file) {
                                 gpu_check(j2p_batch_submit_file_jpeg_opt(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &options, &ticket));
-                        } else if(o->restart_interval || o->restart_in_rows) {
-                                gpu_check(j2p_batch_submit_jpeg_opt(batch, &job, NULL, &spec, file, capacity, &file_bytes, &options, &ticket));
-                        } else if(o->progressive && jp.file) {
-                                gpu_check(j2p_batch_submit_file_jpeg_progressive(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, &ticket));
-                        } else if(o->progressive) {
-                                gpu_check(j2p_batch_submit_jpeg_progressive(batch, &job, NULL, &spec, file, capacity, &file_bytes, &ticket));
-                        } else if(jp.file) {
-                                gpu_check(j2p_batch_submit_file_jpeg_ex(batch, &job, jp.file, jp.file_size, &spec, file, capacity, &file_bytes, flags, &ticket));
                         } else {
-                                gpu_check(j2p_batch_submit_jpeg_ex(batch, &job, NULL, &spec, file, capacity, &file_bytes, flags, &ticket));
+                                gpu_check(j2p_batch_submit_jpeg_opt(batch, &job, NULL, &spec, file, capacity, &file_bytes, &options, &ticket));
                         }
                         const int rc = j2p_batch_wait(batch, ticket);
                         if(rc != J2P_ESPACE || attempt) {

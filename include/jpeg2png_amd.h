@@ -939,8 +939,9 @@ int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples sa
  * 32 bits before limiting, which libjpeg dies on (more than five million blocks whose symbol counts grow like Fibonacci numbers).
  *
  * The counts are taken on the device (k_entropy_histogram) and read back, 2 x 268 64-bit counters: a third wait on the way, next to
- * the two of j2p_planes_to_jpeg.  The tables are made on the host between two launches.  flags == 0: every call below is the call it
- * extends — the same launches, the same memory, the same bytes.  Unknown flag bits: J2P_EINVAL. */
+ * the two of j2p_planes_to_jpeg.  The tables are made on the host between two launches.  Without the flag nothing of this happens:
+ * the launches, the memory and the bytes of "The JPEG file".  Unknown flag bits: J2P_EINVAL.  (The three _ex calls: shorthands, see
+ * j2p_jpeg_options.) */
 #define J2P_JPEG_OPTIMIZE 1u
 int j2p_planes_to_jpeg_ex(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
                           size_t *size, unsigned flags);
@@ -954,7 +955,6 @@ typedef struct j2p_encode_stats {
 } j2p_encode_stats;
 int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
                           size_t capacity, size_t *size, unsigned flags, j2p_encode_stats *stats);
-/* The flag travels in the job's record next to the copied spec. */
 int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                              size_t capacity, size_t *size, unsigned flags, int *ticket);
 
@@ -1009,8 +1009,8 @@ int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples
  *
  * On the device the symbols of ALL scans are counted first and read back with one wait; the host makes every table (2 DC and 7 AC for
  * three components, 1 DC and 3 AC for one); every scan's bits and stuffed FF bytes come back as arrays with one wait each.  So a file
- * costs the waits of the optimised call, whatever the number of scans.  The calls below are new entry points and no flag of the _ex
- * calls: those keep refusing every flag bit but J2P_JPEG_OPTIMIZE. */
+ * costs the waits of the optimised call, whatever the number of scans.  Progressive is a member of j2p_jpeg_options and no flag: the
+ * _ex calls keep refusing every flag bit but J2P_JPEG_OPTIMIZE.  (The _progressive calls: shorthands, see j2p_jpeg_options.) */
 #define J2P_PROGRESSIVE_SCANS 10
 typedef struct j2p_progressive_scan {
         unsigned ncomp, comp[3];        /* the scan's components */
@@ -1025,15 +1025,12 @@ typedef struct j2p_progressive_stats {
         unsigned nscans;
         j2p_progressive_scan scan[J2P_PROGRESSIVE_SCANS];
 } j2p_progressive_stats;
-/* j2p_planes_to_jpeg with the progressive file as its result; every rule of that call stands. */
 int j2p_planes_to_jpeg_progressive(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
                                    size_t *size);
-/* j2p_entropy_encode with the progressive file as its result.  stats may be NULL; zeroed first; the counts are there once they have
- * been read back, the bits and stuffed bytes once those have, also when the call then fails with J2P_ESPACE. */
+/* stats may be NULL; zeroed first; the counts are there once they have been read back, the bits and stuffed bytes once those have,
+ * also when the call then fails with J2P_ESPACE. */
 int j2p_entropy_encode_progressive(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
                                    size_t capacity, size_t *size, j2p_progressive_stats *stats);
-/* j2p_batch_submit_jpeg and j2p_batch_submit_file_jpeg with the progressive file as the job's result: the choice travels in the job's
- * record next to the copied spec, not in j2p_job.  Every rule of those calls stands (not with `tile`, ...). */
 int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                                       size_t capacity, size_t *size, int *ticket);
 
@@ -1066,9 +1063,18 @@ int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2
  * item, the exclusive sum runs once more, and the lane or wavefront of every interval's last item writes the 1-bits.  The staging
  * stream stays pure data; the markers go in where the FFs are stuffed.  No wait is added: a file costs the waits it cost.
  *
- * One options record for all three files.  flags: J2P_JPEG_* bits; progressive: 0 or 1 (flags then change nothing);
- * restart_interval, restart_in_rows: 0 for none.  With both 0 a j2p_*_opt call is the call it extends — the same launches, the same
- * memory, the same bytes.  The calls without options keep their signatures and keep refusing what they refuse. */
+ * The options record: the description of a JPEG write.  flags: J2P_JPEG_* bits; progressive: 0 or 1 (flags then change nothing);
+ * restart_interval, restart_in_rows: 0 for none.  The four j2p_*_opt calls below take it and are the calls every JPEG write goes
+ * through; it is the one thing that travels from them to the coder (a batch copies it into the job's record next to the copied spec,
+ * not into j2p_job).  A member that is 0 costs nothing: {0, 0, 0, 0} has the launches, the memory and the bytes of "The JPEG file".
+ * Refusals, after a NULL argument and before anything else of the call is looked at (a batch job: after the job's own rules and
+ * the spec's): NULL options, unknown flag bits, progressive above 1, the restart members as above — all J2P_EINVAL.
+ * The twelve older calls are shorthands, each for the _opt call of its name with the record
+ *      j2p_planes_to_jpeg, j2p_entropy_encode, j2p_batch_submit_jpeg, j2p_batch_submit_file_jpeg                       {0, 0, 0, 0}
+ *      ..._ex(flags) of the four                                                                                       {flags, 0, 0, 0}
+ *      ..._progressive of the four                                                                                     {0, 1, 0, 0}
+ * and, for j2p_entropy_encode_ex and j2p_entropy_encode_progressive, their stats as stats / progressive_stats.  Every rule of the
+ * _opt call is theirs; they keep their signatures and refuse what they refused. */
 typedef struct j2p_jpeg_options {
         unsigned flags;
         unsigned progressive;
@@ -1098,16 +1104,17 @@ typedef struct j2p_restart_stats {
         unsigned nscans;
         j2p_restart_scan_stats scan[J2P_PROGRESSIVE_SCANS];
 } j2p_restart_stats;
-/* j2p_planes_to_jpeg, _ex and _progressive as one call */
+/* the planes of "The JPEG file" as the file of `options` */
 int j2p_planes_to_jpeg_opt(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity,
                            size_t *size, const j2p_jpeg_options *options);
-/* j2p_entropy_encode, _ex and _progressive as one call.  stats is filled by the baseline and optimised coders, progressive_stats by
- * the progressive one (its `bits` are those before any padding), restart_stats by all; each may be NULL and is zeroed first. */
+/* ... and the caller's coefficients.  stats is filled by the baseline and optimised coders, progressive_stats by the progressive one
+ * (its `bits` are those before any padding), restart_stats by all; each may be NULL and is zeroed first.  Asking for stats has the
+ * baseline coder count the symbols (one more wait), as J2P_JPEG_OPTIMIZE does. */
 int j2p_entropy_encode_opt(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host,
                            size_t capacity, size_t *size, const j2p_jpeg_options *options, j2p_encode_stats *stats,
                            j2p_progressive_stats *progressive_stats, j2p_restart_stats *restart_stats);
-/* j2p_batch_submit_jpeg and j2p_batch_submit_file_jpeg with the options, which are copied and travel in the job's record next to the
- * copied spec, not in j2p_job. */
+/* ... and a batch job's image, from its coefficients or samples (rules: j2p_batch_submit_jpeg) or from a file (rules:
+ * j2p_batch_submit_file_jpeg). */
 int j2p_batch_submit_jpeg_opt(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
                               size_t capacity, size_t *size, const j2p_jpeg_options *options, int *ticket);
 int j2p_batch_submit_file_jpeg_opt(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
@@ -1218,10 +1225,9 @@ int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file,
  * capacity, out_size and the job's rules as there).  Bytes go in and bytes come out; no coefficient crosses the bus. */
 int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
                                size_t capacity, size_t *out_size, int *ticket);
-/* ... with the flags of j2p_batch_submit_jpeg_ex */
+/* (shorthands, see j2p_jpeg_options) */
 int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
                                   size_t capacity, size_t *out_size, unsigned flags, int *ticket);
-/* ... with the progressive file as the result (j2p_batch_submit_jpeg_progressive) */
 int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec,
                                            uint8_t *out, size_t capacity, size_t *out_size, int *ticket);
 

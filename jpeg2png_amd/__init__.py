@@ -471,43 +471,31 @@ def _bind(path):
         lib.j2p_solver_clipped_samples.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong)]
         lib.j2p_batch_submit_samples.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.c_uint,
                                                  ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
-    if hasattr(lib, "j2p_planes_to_jpeg"):
-        # (as above: an earlier commit's build does not write files)
-        lib.j2p_planes_to_jpeg.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
-                                           ctypes.POINTER(ctypes.c_size_t)]
-        lib.j2p_entropy_encode.argtypes = [ctypes.c_int, ctypes.POINTER(_CJpeg), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_void_p,
-                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-        lib.j2p_batch_submit_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
-                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
-    if hasattr(lib, "j2p_entropy_encode_ex"):
-        # (as above: an earlier commit's build makes no tables)
-        lib.j2p_planes_to_jpeg_ex.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint]
-        lib.j2p_entropy_encode_ex.argtypes = [ctypes.c_int, ctypes.POINTER(_CJpeg), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_void_p,
-                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint, ctypes.POINTER(_CEncodeStats)]
-        lib.j2p_batch_submit_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.POINTER(_CJpeg),
-                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
-                                                 ctypes.POINTER(ctypes.c_int)]
-        lib.j2p_batch_submit_file_jpeg_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
-                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
-                                                      ctypes.POINTER(ctypes.c_int)]
-    if hasattr(lib, "j2p_entropy_encode_progressive"):
-        # (as above: an earlier commit's build writes no progressive file)
-        lib.j2p_planes_to_jpeg_progressive.argtypes = lib.j2p_planes_to_jpeg.argtypes
-        lib.j2p_entropy_encode_progressive.argtypes = lib.j2p_entropy_encode.argtypes + [ctypes.POINTER(_CProgressiveStats)]
-        lib.j2p_batch_submit_jpeg_progressive.argtypes = lib.j2p_batch_submit_jpeg.argtypes
-        lib.j2p_batch_submit_file_jpeg_progressive.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t,
-                                                               ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t,
-                                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_entropy_encode_opt"):
-        # (as above: an earlier commit's build writes no restart markers)
-        lib.j2p_debug_restart_plan.argtypes = [ctypes.c_uint] * 5 + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(_CRestartPlan)]
-        lib.j2p_planes_to_jpeg_opt.argtypes = lib.j2p_planes_to_jpeg.argtypes + [ctypes.POINTER(_CJpegOptions)]
-        lib.j2p_entropy_encode_opt.argtypes = lib.j2p_entropy_encode.argtypes + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(_CEncodeStats),
-                                                                                 ctypes.POINTER(_CProgressiveStats), ctypes.POINTER(_CRestartStats)]
-        lib.j2p_batch_submit_jpeg_opt.argtypes = lib.j2p_batch_submit_jpeg.argtypes[:-1] + [ctypes.POINTER(_CJpegOptions), ctypes.POINTER(ctypes.c_int)]
-        lib.j2p_batch_submit_file_jpeg_opt.argtypes = lib.j2p_batch_submit_file_jpeg_progressive.argtypes[:-1] + [ctypes.POINTER(_CJpegOptions),
-                                                                                                                 ctypes.POINTER(ctypes.c_int)]
+        # (as above: an earlier commit's build does not write files, or not every kind).  The record describes a JPEG write: the
+        # three _opt calls and the one behind a batch's file are what this module calls, the twelve older ones are their shorthands
+        planes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        coded = [ctypes.c_int, ctypes.POINTER(_CJpeg), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
+                 ctypes.POINTER(ctypes.c_size_t)]
+        to = [ctypes.POINTER(_CJpeg), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        job = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples)] + to
+        file = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t] + to
+        options, ticket = [ctypes.POINTER(_CJpegOptions)], [ctypes.POINTER(ctypes.c_int)]
+        lib.j2p_debug_restart_plan.argtypes = [ctypes.c_uint] * 5 + options + [ctypes.POINTER(_CRestartPlan)]
+        lib.j2p_planes_to_jpeg_opt.argtypes = planes + options
+        lib.j2p_planes_to_jpeg.argtypes = lib.j2p_planes_to_jpeg_progressive.argtypes = planes
+        lib.j2p_planes_to_jpeg_ex.argtypes = planes + [ctypes.c_uint]
+        lib.j2p_entropy_encode_opt.argtypes = coded + options + [ctypes.POINTER(_CEncodeStats), ctypes.POINTER(_CProgressiveStats),
+                                                                 ctypes.POINTER(_CRestartStats)]
+        lib.j2p_entropy_encode.argtypes = coded
+        lib.j2p_entropy_encode_ex.argtypes = coded + [ctypes.c_uint, ctypes.POINTER(_CEncodeStats)]
+        lib.j2p_entropy_encode_progressive.argtypes = coded + [ctypes.POINTER(_CProgressiveStats)]
+        lib.j2p_batch_submit_jpeg_opt.argtypes = job + options + ticket
+        lib.j2p_batch_submit_jpeg.argtypes = lib.j2p_batch_submit_jpeg_progressive.argtypes = job + ticket
+        lib.j2p_batch_submit_jpeg_ex.argtypes = job + [ctypes.c_uint] + ticket
+        lib.j2p_batch_submit_file_jpeg_opt.argtypes = file + options + ticket
+        lib.j2p_batch_submit_file_jpeg.argtypes = lib.j2p_batch_submit_file_jpeg_progressive.argtypes = file + ticket
+        lib.j2p_batch_submit_file_jpeg_ex.argtypes = file + [ctypes.c_uint] + ticket
     if hasattr(lib, "j2p_png_encode"):
         # (as above: an earlier commit's build writes no PNG)
         lib.j2p_planes_to_png.argtypes = [ctypes.POINTER(_CPlaneRef), ctypes.c_uint, ctypes.POINTER(_CPng), ctypes.c_void_p, ctypes.c_size_t,
@@ -535,8 +523,6 @@ def _bind(path):
                                               ctypes.POINTER(_CJpegInfo), ctypes.c_uint, ctypes.POINTER(_CDecodeStats)]
         lib.j2p_batch_submit_file.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint,
                                               ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
-        lib.j2p_batch_submit_file_jpeg.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_CJpeg),
-                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
         lib.j2p_solver_create_from_jpeg.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                     ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_uint, ctypes.POINTER(_CJpegInfo)]
     if hasattr(lib, "j2p_entropy_decode_scans"):
@@ -925,12 +911,10 @@ def _jpeg_bytes(call, guess):
 
 
 def _restart_options(optimize, progressive, restart_rows, restart_interval):
-    """j2p_jpeg_options of a file's keywords, or None without restart intervals (the calls without options are then made as ever)"""
+    """j2p_jpeg_options of a file's keywords: the record that every call which writes a JPEG file takes"""
     rows, interval = int(restart_rows or 0), int(restart_interval or 0)
     if rows < 0 or interval < 0:
         raise J2PError("jpeg: restart_rows and restart_interval are not negative")
-    if not rows and not interval:
-        return None
     if rows > 0xffffffff or interval > 0xffffffff:       # (what the record cannot hold; the library refuses everything above 65535)
         raise J2PError("jpeg: restart_rows and restart_interval are above 65535")
     return _CJpegOptions(J2P_JPEG_OPTIMIZE if optimize and not progressive else 0, 1 if progressive else 0, interval, rows)
@@ -950,19 +934,19 @@ def _restart_plan(width, height, ncomp, subsampling=(1, 1), progressive=False, r
 
 def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1), device=0, optimize=False, stats=False, progressive=False,
                    restart_rows=0, restart_interval=0):
-    """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode): coefficients is a
+    """a baseline JPEG file (bytes) from quantised coefficients, entropy-coded on the GPU (j2p_entropy_encode_opt): coefficients is a
     list of 1 or 3 int16 arrays [blocks_h, blocks_w, 64] in natural order — component 0's grid ceil(height / 8) x ceil(width / 8),
     the others' ceil of that over subsampling=(sx, sy) — every value in [-1023, 1023]; quant_tables: one per component, steps
     1..255, the third equal to the second.  Byte for byte what libjpeg's jpeg_write_coefficients writes with its defaults.
     optimize=True: with Huffman tables made for these coefficients from symbol counts taken on the GPU (J2P_JPEG_OPTIMIZE) — byte
     for byte libjpeg's file with optimize_coding (IJG 9d and later).  stats=True: (file, dict of the device's counts dc0, ac0, dc1,
     ac1 — 256 each — scan_bits and stuffed_bytes).
-    progressive=True: the progressive file of libjpeg's jpeg_simple_progression() (j2p_entropy_encode_progressive; include/jpeg2png_amd.h:
+    progressive=True: the progressive file of libjpeg's jpeg_simple_progression() (include/jpeg2png_amd.h:
     "The progressive JPEG file"), every scan with tables of its own — optimize= changes nothing about it.  stats=True then gives
     (file, list of one dict per scan: components, ss, se, ah, al, tables — {(class << 4) | slot: 256 counts}, in DHT order —, bits,
     stuffed_bytes and eob_runs).
     restart_rows=R or restart_interval=N: the same file with restart intervals of R rows of MCUs (of blocks, in a scan of one
-    component) or of N MCUs (blocks) — libjpeg's restart_in_rows and restart_interval (j2p_entropy_encode_opt; include/jpeg2png_amd.h:
+    component) or of N MCUs (blocks) — libjpeg's restart_in_rows and restart_interval (include/jpeg2png_amd.h:
     "Restart intervals").  stats=True then gives the dict, or each scan's dict, one more entry: "restart", a dict of interval,
     intervals, padding_bits and markers as taken on the device (for a baseline file under the dict's own key "restart")."""
     lib = load_library()
@@ -982,39 +966,32 @@ def entropy_encode(coefficients, width, height, quant_tables, subsampling=(1, 1)
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
     total = sum(a.size for a in arrays)
     options = _restart_options(optimize, progressive, restart_rows, restart_interval)
-    if options is not None:
-        st, ps, rs = _CEncodeStats(), _CProgressiveStats(), _CRestartStats()
-        file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_opt(int(device), ctypes.byref(spec), ptrs, n, out, cap, size, ctypes.byref(options),
-                                                                             ctypes.byref(st) if stats else None, ctypes.byref(ps) if stats else None,
-                                                                             ctypes.byref(rs) if stats else None), 4096 + total // 4 + total // 32)
-        if not stats:
-            return file
-        restart = [{"interval": k.interval, "intervals": k.intervals, "padding_bits": k.padding_bits, "markers": k.markers} for k in rs.scan[:rs.nscans]]
-        if progressive:
-            return file, [{"components": tuple(k.comp[:k.ncomp]), "ss": k.ss, "se": k.se, "ah": k.ah, "al": k.al,
-                           "tables": {k.table[t]: list(k.counts[t]) for t in range(k.ntables)}, "bits": k.bits, "stuffed_bytes": k.stuffed_bytes,
-                           "eob_runs": k.eob_runs, "restart": r} for k, r in zip(ps.scan[:ps.nscans], restart)]
-        return file, {"dc0": list(st.dc0), "ac0": list(st.ac0), "dc1": list(st.dc1), "ac1": list(st.ac1), "scan_bits": st.scan_bits,
-                      "stuffed_bytes": st.stuffed_bytes, "restart": restart[0]}
-    if progressive:
-        ps = _CProgressiveStats()
-        file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_progressive(int(device), ctypes.byref(spec), ptrs, n, out, cap, size,
-                                                                                     ctypes.byref(ps) if stats else None), 4096 + total // 4)
-        if not stats:
-            return file
-        return file, [{"components": tuple(k.comp[:k.ncomp]), "ss": k.ss, "se": k.se, "ah": k.ah, "al": k.al,
-                       "tables": {k.table[t]: list(k.counts[t]) for t in range(k.ntables)}, "bits": k.bits, "stuffed_bytes": k.stuffed_bytes,
-                       "eob_runs": k.eob_runs} for k in ps.scan[:ps.nscans]]
-    if not optimize and not stats:
-        return _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode(int(device), ctypes.byref(spec), ptrs, n, out, cap, size), 4096 + total // 4)
-    st = _CEncodeStats()
-    flags = J2P_JPEG_OPTIMIZE if optimize else 0
-    file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_ex(int(device), ctypes.byref(spec), ptrs, n, out, cap, size, flags,
-                                                                        ctypes.byref(st) if stats else None), 4096 + total // 4)
+    restarts = bool(options.restart_interval or options.restart_in_rows)
+    # (a record the caller does not ask for stays NULL: without stats and optimize= the baseline coder counts nothing)
+    st = _CEncodeStats() if stats and not progressive else None
+    ps = _CProgressiveStats() if stats and progressive else None
+    rs = _CRestartStats() if stats and restarts else None
+    ref = lambda record: None if record is None else ctypes.byref(record)
+    file = _jpeg_bytes(lambda out, cap, size: lib.j2p_entropy_encode_opt(int(device), ctypes.byref(spec), ptrs, n, out, cap, size, ctypes.byref(options),
+                                                                         ref(st), ref(ps), ref(rs)),
+                       4096 + total // 4 + (total // 32 if restarts else 0))      # (room for markers and pads only where there are any)
     if not stats:
         return file
-    return file, {"dc0": list(st.dc0), "ac0": list(st.ac0), "dc1": list(st.dc1), "ac1": list(st.ac1), "scan_bits": st.scan_bits,
-                  "stuffed_bytes": st.stuffed_bytes}
+    restart = [{"interval": k.interval, "intervals": k.intervals, "padding_bits": k.padding_bits, "markers": k.markers}
+               for k in (rs.scan[:rs.nscans] if restarts else ())]
+    if progressive:
+        scans = [{"components": tuple(k.comp[:k.ncomp]), "ss": k.ss, "se": k.se, "ah": k.ah, "al": k.al,
+                  "tables": {k.table[t]: list(k.counts[t]) for t in range(k.ntables)}, "bits": k.bits, "stuffed_bytes": k.stuffed_bytes,
+                  "eob_runs": k.eob_runs} for k in ps.scan[:ps.nscans]]
+        assert not restarts or len(restart) == len(scans)       # (the coder reports every scan's intervals)
+        for scan, r in zip(scans, restart):
+            scan["restart"] = r
+        return file, scans
+    scan = {"dc0": list(st.dc0), "ac0": list(st.ac0), "dc1": list(st.dc1), "ac1": list(st.ac1), "scan_bits": st.scan_bits,
+            "stuffed_bytes": st.stuffed_bytes}
+    if restarts:
+        scan["restart"] = restart[0]
+    return file, scan
 
 
 def _c_png(width, height, bits=8, filter=None, block_bytes=0, idat_bytes=0):
@@ -1437,18 +1414,18 @@ class Solver:
 
     def to_jpeg(self, width, height, quality=None, quant_tables=None, subsampling=(1, 1), others=(), optimize=False, progressive=False,
                 restart_rows=0, restart_interval=0):
-        """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg):
+        """the current iterate as a complete baseline JPEG file (bytes), quantised AND entropy-coded on the GPU (j2p_planes_to_jpeg_opt):
         only the file comes down.  width x height: the image, cropped from the canvas's top left corner.  quality: libjpeg's
         tables for it (quality_tables), or quant_tables: one 64-entry table per component, steps 1..255, natural order, the third
         equal to the second.  subsampling=(sx, sy), 1 or 2 each: the sampling of components 1 and 2.  A solver of three channels
         gives a colour file, one of one channel a greyscale file; others=(solver, solver): this solver's channel 0 and the
         channel 0 of two more solvers (the separate solves of `-s`) give a colour file.  Whole-canvas solvers only.  Byte for
         byte what libjpeg's jpeg_write_coefficients writes from Solver.coefficients() with its defaults.  optimize=True: with
-        Huffman tables made for the image, as entropy_encode(optimize=True) makes them (j2p_planes_to_jpeg_ex) — the same
+        Huffman tables made for the image, as entropy_encode(optimize=True) makes them — the same
         coefficients in fewer bytes, for one more wait on the way.  progressive=True: the progressive file, as
-        entropy_encode(progressive=True) writes it (j2p_planes_to_jpeg_progressive); optimize= changes nothing about it.
+        entropy_encode(progressive=True) writes it; optimize= changes nothing about it.
         restart_rows=R or restart_interval=N: any of the three with restart intervals, as entropy_encode(restart_rows=,
-        restart_interval=) writes them (j2p_planes_to_jpeg_opt)."""
+        restart_interval=) writes them."""
         solvers = [self] + list(others)
         if len(solvers) not in (1, 3):
             raise J2PError("jpeg: others= takes the two other solvers of a colour file")
@@ -1459,14 +1436,9 @@ class Solver:
         spec, _held = _c_jpeg(width, height, n, quality, quant_tables, subsampling)
         guess = 4096 + int(width) * int(height) * n // 4
         options = _restart_options(optimize, progressive, restart_rows, restart_interval)
-        if options is not None:
-            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_opt(refs, n, ctypes.byref(spec), out, cap, size, ctypes.byref(options)),
-                               guess + guess // 8)
-        if progressive:
-            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_progressive(refs, n, ctypes.byref(spec), out, cap, size), guess)
-        if not optimize:
-            return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg(refs, n, ctypes.byref(spec), out, cap, size), guess)
-        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_ex(refs, n, ctypes.byref(spec), out, cap, size, J2P_JPEG_OPTIMIZE), guess)
+        if options.restart_interval or options.restart_in_rows:     # (room for markers and pads only where there are any)
+            guess += guess // 8
+        return _jpeg_bytes(lambda out, cap, size: self._lib.j2p_planes_to_jpeg_opt(refs, n, ctypes.byref(spec), out, cap, size, ctypes.byref(options)), guess)
 
     def to_png(self, width, height, bits=8, filter=None, others=(), block_bytes=0, idat_bytes=0):
         """the current iterate as a complete PNG file (bytes), converted to samples, filtered AND deflated on the GPU
@@ -1907,14 +1879,12 @@ def _fill_jpeg(job, jpeg, n, width, height):
     sx, sy = (cjpeg.sub_w, cjpeg.sub_h) if n == 3 else (1, 1)
     room = 4096 + 2 * 64 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
     options = _restart_options(jpeg.get("optimize"), jpeg.get("progressive"), jpeg.get("restart_rows"), jpeg.get("restart_interval"))
-    if options is not None:             # (a marker and a pad per block per scan at the most)
+    if options.restart_interval or options.restart_in_rows:     # (a marker and a pad per block per scan at the most)
         room += 3 * 10 * (-(-int(width) // 8) * -(-int(height) // 8)) * (1 + (n - 1) / (sx * sy))
     buffer, size = np.empty(int(jpeg.get("capacity") or room), dtype=np.uint8), ctypes.c_size_t(0)
     job.out_w, job.out_h = int(width), int(height)
-    flags = "progressive" if jpeg.get("progressive") else J2P_JPEG_OPTIMIZE if jpeg.get("optimize") else 0
-    if options is not None:
-        flags = options                 # (the options record: the _opt entry points)
-    return _JpegResult(buffer, size), [cjpeg, held, options], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size), flags)
+    return _JpegResult(buffer, size), [cjpeg, held, options], (ctypes.byref(cjpeg), buffer.ctypes.data, buffer.size, ctypes.byref(size),
+                                                               ctypes.byref(options))
 
 
 def _fill_png(job, png, n, width, height):
@@ -2048,16 +2018,9 @@ def _job_record(job, planes, weight, pweight, iterations, want, tile_devices, ti
 def _entry_point(source, source_args, kind, output_args):
     """step 4 -> (the C entry point of an (input kind, output kind) pair, its arguments between the job and the ticket)"""
     if kind == "jpeg":
-        flags = output_args[-1]                     # (without flags the entry points that have none: the calls they always were)
-        if isinstance(flags, _CJpegOptions):        # (restart intervals: the one entry point that takes the options record)
-            ex, output_args = "_opt", output_args[:-1] + (ctypes.byref(flags),)
-        elif flags == "progressive":                # (an entry point of its own, and no flag)
-            ex, output_args = "_progressive", output_args[:-1]
-        else:
-            ex, output_args = ("_ex", output_args) if flags else ("", output_args[:-1])
         if source == "file":
-            return "j2p_batch_submit_file_jpeg" + ex, source_args + output_args
-        return "j2p_batch_submit_jpeg" + ex, (source_args or (None,)) + output_args     # (samples NULL: the planes' coefficients)
+            return "j2p_batch_submit_file_jpeg_opt", source_args + output_args
+        return "j2p_batch_submit_jpeg_opt", (source_args or (None,)) + output_args      # (samples NULL: the planes' coefficients)
     if kind == "png":
         if source == "file":
             return "j2p_batch_submit_file_png", source_args + output_args
@@ -2109,11 +2072,11 @@ class Batch:
         shows fails the job in wait(), and no other job.
         jpeg={"quality": Q or "quant_tables": [...], "subsampling": (sx, sy), "capacity": bytes, "optimize": bool, "progressive": bool} (with width and height; not
         with bits, quant_tables, tensor=, outputs= or tile; samples= is allowed): wait() returns the image as a complete baseline
-        JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg, Solver.to_jpeg) — one or
+        JPEG file (bytes) that the worker quantised and entropy-coded on its GPU (j2p_batch_submit_jpeg_opt, with file= j2p_batch_submit_file_jpeg_opt; Solver.to_jpeg) — one or
         three planes.  optimize: Huffman tables made for the image, as Solver.to_jpeg(optimize=True).  progressive: the
-        progressive file, as Solver.to_jpeg(progressive=True) (j2p_batch_submit_jpeg_progressive); optimize changes nothing about it.
-        "restart_rows": R or "restart_interval": N in the dict: restart intervals, as Solver.to_jpeg(restart_rows=, restart_interval=)
-        (j2p_batch_submit_jpeg_opt, j2p_batch_submit_file_jpeg_opt).  capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
+        progressive file, as Solver.to_jpeg(progressive=True); optimize changes nothing about it.
+        "restart_rows": R or "restart_interval": N in the dict: restart intervals, as Solver.to_jpeg(restart_rows=, restart_interval=).
+        capacity: room for the file (default: 4096 + 2 bytes per sample, which a file of natural content never
         reaches; a larger file fails the job with the size it needs in the message);
         samples=[one 2-D uint8 torch tensor or numpy array per plane] (planes with data=None; not with tile, nor with the
         out_width / out_height / box / filter of tensor=, which outputs= covers): the job's solvers are made from decoded 8-bit

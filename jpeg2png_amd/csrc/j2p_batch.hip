@@ -44,10 +44,7 @@ struct Request {
         const j2p_jpeg *jpeg = nullptr;     // the file the job delivers, with where it goes:
         uint8_t *jpeg_out = nullptr;
         size_t jpeg_capacity = 0, *jpeg_size = nullptr;
-        unsigned jpeg_flags = 0;            // J2P_JPEG_*
-        bool jpeg_progressive = false;      // ... as the progressive file (flags 0)
-        unsigned jpeg_restart_interval = 0, jpeg_restart_in_rows = 0;    // ... with restart intervals (j2p_jpeg_options)
-        const j2p_jpeg_options *jpeg_record = nullptr;                   // a j2p_*_opt call's record, which validate_jpeg checks as a whole
+        j2p_jpeg_options jpeg_options = {0, 0, 0, 0};   // ... and which file it is: the caller's record as it came, for validate_jpeg
         unsigned orientation = 0, orient_w = 0, orient_h = 0;    // j2p_batch_next_orientation: what the calling thread set for this submit
         bool file_scans = false;                                 // j2p_batch_next_file_scans: the file goes through the scans parser
         const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
@@ -59,21 +56,9 @@ struct Request {
         Request &outputs(unsigned n, const j2p_output *o) { if(n && o) { nout = n, outs = o; } return *this; }
         Request &from_samples(const j2p_samples *m) { samples = m; return *this; }
         Request &from_file(const uint8_t *f, size_t size) { file = f, file_size = size; return *this; }
-        Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size, unsigned flags)
+        Request &jpeg_to(const j2p_jpeg *spec, uint8_t *out, size_t capacity, size_t *size, const j2p_jpeg_options &options)
         {
-                jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size, jpeg_flags = flags;
-                return *this;
-        }
-        Request &progressive()
-        {
-                jpeg_progressive = true;
-                return *this;
-        }
-        // a j2p_*_opt call's options (checked for NULL by the caller)
-        Request &jpeg_options(const j2p_jpeg_options &o)
-        {
-                jpeg_record = &o;
-                jpeg_flags = o.flags, jpeg_progressive = o.progressive != 0, jpeg_restart_interval = o.restart_interval, jpeg_restart_in_rows = o.restart_in_rows;
+                jpeg = spec, jpeg_out = out, jpeg_capacity = capacity, jpeg_size = size, jpeg_options = options;
                 return *this;
         }
         Request &png_to(const j2p_png *spec, uint8_t *out, size_t capacity, size_t *size)
@@ -96,16 +81,12 @@ struct JpegOut {
         uint16_t tables[3][64];
         uint8_t *out = nullptr;
         size_t capacity = 0, *size = nullptr;
-        unsigned flags = 0;
-        bool progressive = false;
-        unsigned restart_interval = 0, restart_in_rows = 0;
+        j2p_jpeg_options options = {0, 0, 0, 0};
         // from a request that validate_jpeg has passed: the tables travel with the job
         void set(const Request &q, unsigned nchannel)
         {
                 spec = *q.jpeg;
-                flags = q.jpeg_flags;
-                progressive = q.jpeg_progressive;
-                restart_interval = q.jpeg_restart_interval, restart_in_rows = q.jpeg_restart_in_rows;
+                options = q.jpeg_options;
                 out = q.jpeg_out, capacity = q.jpeg_capacity, size = q.jpeg_size;
                 for(unsigned c = 0; c < nchannel; c++) {
                         memcpy(tables[c], q.jpeg->quant[c], sizeof(tables[c]));
@@ -343,12 +324,7 @@ int deliver_outputs(const Job &j, const j2p_job &d, const Band &band)
 
 int deliver_jpeg(const Job &j, const j2p_job &d, const Band &band)
 {
-        if(j.jpeg.restart_interval || j.jpeg.restart_in_rows) {
-                const j2p_jpeg_options options = {j.jpeg.flags, j.jpeg.progressive ? 1u : 0u, j.jpeg.restart_interval, j.jpeg.restart_in_rows};
-                return j2p_planes_to_jpeg_opt(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, &options);
-        }
-        if(j.jpeg.progressive) { return j2p_planes_to_jpeg_progressive(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size); }
-        return j2p_planes_to_jpeg_ex(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, j.jpeg.flags);
+        return j2p_planes_to_jpeg_opt(band.ref, d.nchannel, &j.jpeg.spec, j.jpeg.out, j.jpeg.capacity, j.jpeg.size, &j.jpeg.options);
 }
 
 int deliver_png(const Job &j, const j2p_job &d, const Band &band)
@@ -641,10 +617,7 @@ int validate_jpeg(const j2p_job &d, const Request &q)
         }
         if(d.tile) { return j2p_fail(J2P_EINVAL, "job: JPEG output of a row-tiled job is not supported"); }
         if(const char *why = j2p_jpeg_error(q.jpeg, d.nchannel)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-        if(const char *why = j2p_jpeg_flags_error(q.jpeg_flags)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-        if(q.jpeg_record) {
-                if(const char *why = j2p_jpeg_options_error(q.jpeg_record)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
-        }
+        if(const char *why = j2p_jpeg_options_error(&q.jpeg_options)) { return j2p_fail(J2P_EINVAL, "job: %s", why); }
         if(q.jpeg->width != d.out_w || q.jpeg->height != d.out_h) {
                 return j2p_fail(J2P_EINVAL, "job: the JPEG is %ux%u, the job's image (out_w x out_h) %ux%u", q.jpeg->width, q.jpeg->height, d.out_w, d.out_h);
         }
@@ -889,26 +862,14 @@ int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples
         return submit(b, job, Request().from_samples(samples).outputs(n, outs), ticket);
 }
 
-int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
-                             size_t *size, unsigned flags, int *ticket)
-{
-        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, flags), ticket);
-}
-
-int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
-                                      size_t capacity, size_t *size, int *ticket)
-{
-        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, 0).progressive(), ticket);
-}
-
+// A JPEG job from samples (or, with none, from the job's coefficients), and one from a file: the record says which file is
+// written, and the older entry points are these two with their records.
 int j2p_batch_submit_jpeg_opt(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
                               size_t *size, const j2p_jpeg_options *options, int *ticket)
 {
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
         if(!options) { return j2p_fail(J2P_EINVAL, "job: jpeg: options is NULL"); }
-        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, 0).jpeg_options(*options), ticket);
+        return submit(b, job, Request().from_samples(samples).jpeg_to(spec, out, capacity, size, *options), ticket);
 }
 
 int j2p_batch_submit_file_jpeg_opt(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
@@ -917,41 +878,55 @@ int j2p_batch_submit_file_jpeg_opt(j2p_batch *b, const j2p_job *job, const uint8
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
         if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
         if(!options) { return j2p_fail(J2P_EINVAL, "job: jpeg: options is NULL"); }
-        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, 0).jpeg_options(*options), ticket);
+        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, *options), ticket);
+}
+
+int j2p_batch_submit_jpeg_ex(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
+                             size_t *size, unsigned flags, int *ticket)
+{
+        const j2p_jpeg_options options = {flags, 0, 0, 0};
+        return j2p_batch_submit_jpeg_opt(b, job, samples, spec, out, capacity, size, &options, ticket);
+}
+
+int j2p_batch_submit_jpeg_progressive(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out,
+                                      size_t capacity, size_t *size, int *ticket)
+{
+        const j2p_jpeg_options options = {0, 1, 0, 0};
+        return j2p_batch_submit_jpeg_opt(b, job, samples, spec, out, capacity, size, &options, ticket);
 }
 
 int j2p_batch_submit_jpeg(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_jpeg *spec, uint8_t *out, size_t capacity,
                           size_t *size, int *ticket)
 {
-        return j2p_batch_submit_jpeg_ex(b, job, samples, spec, out, capacity, size, 0, ticket);
+        const j2p_jpeg_options options = {0, 0, 0, 0};
+        return j2p_batch_submit_jpeg_opt(b, job, samples, spec, out, capacity, size, &options, ticket);
+}
+
+int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                  size_t capacity, size_t *out_size, unsigned flags, int *ticket)
+{
+        const j2p_jpeg_options options = {flags, 0, 0, 0};
+        return j2p_batch_submit_file_jpeg_opt(b, job, file, size, spec, out, capacity, out_size, &options, ticket);
+}
+
+int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                                           size_t capacity, size_t *out_size, int *ticket)
+{
+        const j2p_jpeg_options options = {0, 1, 0, 0};
+        return j2p_batch_submit_file_jpeg_opt(b, job, file, size, spec, out, capacity, out_size, &options, ticket);
+}
+
+int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
+                               size_t capacity, size_t *out_size, int *ticket)
+{
+        const j2p_jpeg_options options = {0, 0, 0, 0};
+        return j2p_batch_submit_file_jpeg_opt(b, job, file, size, spec, out, capacity, out_size, &options, ticket);
 }
 
 int j2p_batch_submit_file(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, unsigned n, const j2p_output outs[], int *ticket)
 {
         if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
         return submit(b, job, Request().from_file(file, size).outputs(n, outs), ticket);
-}
-
-int j2p_batch_submit_file_jpeg_ex(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
-                                  size_t capacity, size_t *out_size, unsigned flags, int *ticket)
-{
-        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
-        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, flags), ticket);
-}
-
-int j2p_batch_submit_file_jpeg_progressive(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
-                                           size_t capacity, size_t *out_size, int *ticket)
-{
-        if(!file || size == 0) { return j2p_fail(J2P_EINVAL, "job: file is NULL or empty"); }
-        if(!spec) { return j2p_fail(J2P_EINVAL, "job: jpeg: spec is NULL"); }
-        return submit(b, job, Request().from_file(file, size).jpeg_to(spec, out, capacity, out_size, 0).progressive(), ticket);
-}
-
-int j2p_batch_submit_file_jpeg(j2p_batch *b, const j2p_job *job, const uint8_t *file, size_t size, const j2p_jpeg *spec, uint8_t *out,
-                               size_t capacity, size_t *out_size, int *ticket)
-{
-        return j2p_batch_submit_file_jpeg_ex(b, job, file, size, spec, out, capacity, out_size, 0, ticket);
 }
 
 int j2p_batch_submit_png(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], const j2p_png *spec, uint8_t *out, size_t capacity, size_t *size,

@@ -1,5 +1,5 @@
-// jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file (j2p_encode_scan, j2p_entropy_encode; the
-// progressive file: j2p_encode_progressive, j2p_entropy_encode_progressive) and a
+// jpeg2png_amd — the JPEG codec: quantised coefficients to the entropy-coded file a j2p_jpeg_options record describes
+// (j2p_encode_options, j2p_entropy_encode_opt and its shorthands, over the file-local j2p_encode_scan and j2p_encode_progressive) and a
 // baseline file's entropy-coded data back to coefficients (j2p_jpeg_open, j2p_decode_file, j2p_decoded_grids,
 // j2p_entropy_decode; every scan of a progressive file: j2p_jpeg_open_scans, j2p_decode_scans_file, j2p_decode_opened,
 // j2p_entropy_decode_scans; include/jpeg2png_amd.h, j2p_internal.h) — and, at the end, the PNG coder: samples to the filtered and
@@ -7,7 +7,7 @@
 //
 // A translation unit of its own, with its own device code (j2p_codec_kernels.hip.h, j2p_progressive_kernels.hip.h, j2p_decode_kernels.hip.h, j2p_scan_decode_kernels.hip.h): neither way
 // uses a kernel of the output stage or of the solver, and an edit here recompiles neither.  It knows no solver: the output
-// stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_scan.
+// stage's j2p_planes_to_jpeg hands the coder its coefficients and a solver's scratch through j2p_encode_options.
 //
 // The three file coders each work in one device block whose size they learn on the way: j2p_coder_block.h asks `memory` for it and
 // queues a coder's stages again when it moved, PooledCall is the stand-alone entry points' `memory`, stuffed_streams both JPEG coders' end.
@@ -376,9 +376,9 @@ int stuffed_streams(hipStream_t stream, j2p_coder_block &block, j2p_carve &part,
 // Restart intervals (include/jpeg2png_amd.h: "Restart intervals"; j2p_codec_kernels.hip.h says how) put the _restart siblings in the
 // places of the three walking kernels, k_restart_pad and a second exclusive sum into the lengths stage and k_restart_ends into the
 // stream's; the pads' sum comes down with the bits, so no wait is added.
-int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
-                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                    unsigned flags, j2p_encode_stats *stats, const j2p_restart_scan *restart, j2p_restart_scan_stats *restart_stats)
+static int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                           const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                           unsigned flags, j2p_encode_stats *stats, const j2p_restart_scan *restart, j2p_restart_scan_stats *restart_stats)
 {
         ScanGeom g = scan_geometry(spec, ncomp);
         // restart intervals: ri positions each; the _restart kernels only where a marker stands (an interval that holds the whole scan
@@ -543,9 +543,9 @@ size_t prog_scan_header(const ProgScript &s, unsigned ntables, const unsigned ta
 // optimised call, and the file's bytes with a fourth.  The block is asked for three times as j2p_encode_scan's is, with the same
 // three stages (j2p_coder_block.h): the coefficients — with them the flags and the EOB runs — every scan's lengths, and in
 // stuffed_streams every scan's stream.  The walk that counts is no stage: the counts and tables live on the host by then.
-int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
-                           const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                           j2p_progressive_stats *stats, const j2p_restart_plan *restart, j2p_restart_stats *restart_stats)
+static int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
+                                  const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
+                                  j2p_progressive_stats *stats, const j2p_restart_plan *restart, j2p_restart_stats *restart_stats)
 {
         ScanGeom g = scan_geometry(spec, ncomp);
         const ProgScript *const script = ncomp == 3 ? kProgColour : kProgGrey;
@@ -670,7 +670,7 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
                 stats->nscans = nscans;
         }
         j2p_huff_table made[J2P_PROGRESSIVE_SCANS][2];
-        unsigned ntables[J2P_PROGRESSIVE_SCANS], table[J2P_PROGRESSIVE_SCANS][2];
+        unsigned ntables[J2P_PROGRESSIVE_SCANS], table[J2P_PROGRESSIVE_SCANS][2] = {};   // (zero behind a scan's ntables: stats copy both)
         memset(made, 0, sizeof(made));
         int refused = J2P_OK;
         for(unsigned s = 0; s < nscans; s++) {
@@ -764,7 +764,7 @@ int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned nc
 const char *j2p_jpeg_options_error(const j2p_jpeg_options *options)
 {
         if(!options) { return "jpeg: NULL options"; }
-        if(const char *why = j2p_jpeg_flags_error(options->flags)) { return why; }
+        if(options->flags & ~J2P_JPEG_OPTIMIZE) { return "jpeg: unknown flag bits"; }
         if(options->progressive > 1) { return "jpeg: progressive is 0 or 1"; }
         return j2p_restart_error(options->restart_interval, options->restart_in_rows);
 }
@@ -839,12 +839,16 @@ struct PooledCall {
         }
 };
 
-// a coder (j2p_encode_scan, j2p_encode_progressive) on the caller's coefficients in host memory: the argument checks and a PooledCall
-using HostCoder = std::function<int(hipStream_t, const std::function<int(size_t, void **, bool *)> &, const std::function<void(hipStream_t, int16_t *const[3])> &)>;
-static int encode_host_coefficients(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, const size_t *size,
-                                    const HostCoder &coder)
+extern "C" {
+
+// The file `options` describe from the caller's coefficients in host memory: the argument checks, in the order the header gives
+// them, and a PooledCall for j2p_encode_options.  A NULL stats pointer stays NULL on the way down, so only a caller who asks has the symbols counted.
+int j2p_entropy_encode_opt(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
+                           size_t *size, const j2p_jpeg_options *options, j2p_encode_stats *stats, j2p_progressive_stats *progressive_stats,
+                           j2p_restart_stats *restart_stats)
 {
         if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
+        if(const char *why = j2p_jpeg_options_error(options)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         if(const char *why = j2p_jpeg_error(spec, ncomp)) { return j2p_fail(J2P_EINVAL, "%s", why); }
         const j2p_scan_grids g = j2p_scan_grids_of(*spec, ncomp);
         size_t values[3] = {0, 0, 0};
@@ -862,46 +866,36 @@ static int encode_host_coefficients(int device, const j2p_jpeg *spec, const int1
         DeviceGuard guard(device);
         PooledCall call(device);
         if(const int rc = call.open(); rc != J2P_OK) { return rc; }
-        return coder(call.stream, std::ref(call), [&](hipStream_t st, int16_t *const coef[3]) {
-                for(unsigned c = 0; c < ncomp; c++) { (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st); }
-        });
+        return j2p_encode_options(
+                call.stream, *spec, ncomp, *options, std::ref(call),
+                [&](hipStream_t st, int16_t *const coef[3]) {
+                        for(unsigned c = 0; c < ncomp; c++) {
+                                (void)hipMemcpyAsync(coef[c], coef_host[c], values[c] * sizeof(int16_t), hipMemcpyHostToDevice, st);
+                        }
+                },
+                out_host, capacity, size, stats, progressive_stats, restart_stats);
 }
 
-extern "C" {
-
+// the shorthands: each is j2p_entropy_encode_opt with its record
 int j2p_entropy_encode_ex(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
                           size_t *size, unsigned flags, j2p_encode_stats *stats)
 {
-        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        if(const char *why = j2p_jpeg_flags_error(flags)) { return j2p_fail(J2P_EINVAL, "%s", why); }
-        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
-                return j2p_encode_scan(stream, *spec, ncomp, memory, fill, out_host, capacity, size, flags, stats);
-        });
+        const j2p_jpeg_options options = {flags, 0, 0, 0};
+        return j2p_entropy_encode_opt(device, spec, coef_host, ncomp, out_host, capacity, size, &options, stats, nullptr, nullptr);
 }
 
 int j2p_entropy_encode_progressive(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
                                    size_t *size, j2p_progressive_stats *stats)
 {
-        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
-                return j2p_encode_progressive(stream, *spec, ncomp, memory, fill, out_host, capacity, size, stats);
-        });
+        const j2p_jpeg_options options = {0, 1, 0, 0};
+        return j2p_entropy_encode_opt(device, spec, coef_host, ncomp, out_host, capacity, size, &options, nullptr, stats, nullptr);
 }
 
 int j2p_entropy_encode(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
                        size_t *size)
 {
-        return j2p_entropy_encode_ex(device, spec, coef_host, ncomp, out_host, capacity, size, 0, nullptr);
-}
-
-int j2p_entropy_encode_opt(int device, const j2p_jpeg *spec, const int16_t *const coef_host[3], unsigned ncomp, uint8_t *out_host, size_t capacity,
-                           size_t *size, const j2p_jpeg_options *options, j2p_encode_stats *stats, j2p_progressive_stats *progressive_stats,
-                           j2p_restart_stats *restart_stats)
-{
-        if(!coef_host || !size) { return j2p_fail(J2P_EINVAL, "NULL argument"); }
-        if(const char *why = j2p_jpeg_options_error(options)) { return j2p_fail(J2P_EINVAL, "%s", why); }
-        return encode_host_coefficients(device, spec, coef_host, ncomp, size, [&](hipStream_t stream, const auto &memory, const auto &fill) {
-                return j2p_encode_options(stream, *spec, ncomp, *options, memory, fill, out_host, capacity, size, stats, progressive_stats, restart_stats);
-        });
+        const j2p_jpeg_options options = {0, 0, 0, 0};
+        return j2p_entropy_encode_opt(device, spec, coef_host, ncomp, out_host, capacity, size, &options, nullptr, nullptr, nullptr);
 }
 
 int j2p_debug_restart_plan(unsigned width, unsigned height, unsigned ncomp, unsigned sub_w, unsigned sub_h, const j2p_jpeg_options *options,

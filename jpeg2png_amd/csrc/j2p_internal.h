@@ -218,45 +218,32 @@ struct j2p_carve {
 // bytes of a component's coefficient grid of bw x bh blocks
 static inline size_t j2p_grid_bytes(unsigned bw, unsigned bh) { return (size_t)bw * bh * 64 * sizeof(int16_t); }
 
-// the block grids of the file j2p_encode_scan writes from a spec that j2p_jpeg_error accepted: component c's grid has
+// the block grids of the file j2p_encode_options writes from a spec that j2p_jpeg_error accepted: component c's grid has
 // bw[c] x bh[c] blocks; sub_w x sub_h of component 0's make an MCU (1 x 1 for one component)
 struct j2p_scan_grids {
         unsigned sub_w, sub_h, bw[3], bh[3];
 };
 j2p_scan_grids j2p_scan_grids_of(const j2p_jpeg &spec, unsigned ncomp);
-// The coder: the file of `spec` on the host from coefficients the caller leaves in device memory, on `stream`, which has been
-// waited for on return.  memory(bytes, &p, &moved): one block of device memory of at least that size which stays the same block
-// while it is large enough and is ANOTHER block (moved), contents lost, once it has to grow (j2p_solver_scratch);
-// fill(stream, coef): queues what leaves component c's coefficients (j2p_scan_grids_of) at coef[c].  Both may be called up to
-// three times, by the coder's j2p_coder_block (j2p_coder_block.h).  J2P_ESPACE: *size is what the file needs.  flags: J2P_JPEG_* bits, checked by the caller.  With J2P_JPEG_OPTIMIZE,
-// or with stats (may be NULL), the symbols are counted on the device and the stream is waited for once more on the way.
-int j2p_encode_scan(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
-                    const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                    unsigned flags = 0, j2p_encode_stats *stats = nullptr, const j2p_restart_scan *restart = nullptr,
-                    j2p_restart_scan_stats *restart_stats = nullptr);
-// (restart: the scan's entry of the file's restart plan, j2p_restart.h — NULL, or an interval of 0, for a file without restart
-// intervals, whose launches and bytes are what they were; restart_stats may be NULL)
-// The progressive coder: j2p_encode_scan's contract with the file of "The progressive JPEG file" (include/jpeg2png_amd.h) as its
-// result.  The symbols of all scans are counted on the device; the stream is waited for four times whatever the number of scans.
-int j2p_encode_progressive(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const std::function<int(size_t, void **, bool *)> &memory,
-                           const std::function<void(hipStream_t, int16_t *const[3])> &fill, uint8_t *out_host, size_t capacity, size_t *size,
-                           j2p_progressive_stats *stats = nullptr, const j2p_restart_plan *restart = nullptr,
-                           j2p_restart_stats *restart_stats = nullptr);
-// The coder the options of a j2p_*_opt call choose, on one footing: j2p_encode_progressive for options->progressive, else
-// j2p_encode_scan with options->flags, either with the restart plan of the options (j2p_restart.h).  options has passed
-// j2p_jpeg_options_error.  stats, progressive_stats, restart_stats: may be NULL; the one of the other coder is left alone.
+// The coder: the file of `spec` that `options` describe (include/jpeg2png_amd.h: "Restart intervals" has the record), on the host,
+// from coefficients the caller leaves in device memory, on `stream`, which has been waited for on return.  memory(bytes, &p, &moved):
+// one block of device memory of at least that size which stays the same block while it is large enough and is ANOTHER block (moved),
+// contents lost, once it has to grow (j2p_solver_scratch); fill(stream, coef): queues what leaves component c's coefficients
+// (j2p_scan_grids_of) at coef[c].  Both may be called up to three times, by the coder's j2p_coder_block (j2p_coder_block.h).
+// J2P_ESPACE: *size is what the file needs.  options has passed j2p_jpeg_options_error.  The record chooses the coder in
+// j2p_codec.hip — the progressive one for options.progressive, else the baseline one with options.flags — and its restart plan
+// (j2p_restart.h); with all of it 0 the launches and the bytes are the baseline file's as they ever were.  stats,
+// progressive_stats, restart_stats: may be NULL; the one of the other coder is left alone.  With J2P_JPEG_OPTIMIZE, with stats or
+// in a progressive file the symbols are counted on the device and the stream is waited for once more on the way.
 int j2p_encode_options(hipStream_t stream, const j2p_jpeg &spec, unsigned ncomp, const j2p_jpeg_options &options,
                        const std::function<int(size_t, void **, bool *)> &memory, const std::function<void(hipStream_t, int16_t *const[3])> &fill,
                        uint8_t *out_host, size_t capacity, size_t *size, j2p_encode_stats *stats = nullptr,
                        j2p_progressive_stats *progressive_stats = nullptr, j2p_restart_stats *restart_stats = nullptr);
-// what is wrong with the options of a j2p_*_opt call, or NULL
+// what is wrong with the record of a call that writes a JPEG file, or NULL
 const char *j2p_jpeg_options_error(const j2p_jpeg_options *options);
-// what is wrong with the flags of a j2p_*_ex call that writes a JPEG file, or NULL
-static inline const char *j2p_jpeg_flags_error(unsigned flags) { return flags & ~J2P_JPEG_OPTIMIZE ? "jpeg: unknown flag bits" : nullptr; }
 
 // The PNG coder: the file of `spec` on the host from `channels` (1 or 3) interleaved samples per pixel that the caller leaves in
 // device memory, on `stream`, which has been waited for on return (twice on the way: the blocks' counts come down for the host's
-// tables).  memory: as for j2p_encode_scan; fill(stream, samples): queues what leaves the width * height * channels * bits / 8 bytes
+// tables).  memory: as for j2p_encode_options; fill(stream, samples): queues what leaves the width * height * channels * bits / 8 bytes
 // of samples (16 bits: big-endian) at `samples`.  Both may be called twice.  J2P_ESPACE: *size is what the file needs, known before
 // anything is packed.  spec has passed j2p_png_error.  stats may be NULL.
 int j2p_png_write(hipStream_t stream, const j2p_png &spec, unsigned channels, const std::function<int(size_t, void **, bool *)> &memory,

@@ -884,8 +884,8 @@ static std::function<int(size_t, void **, bool *)> scratch_memory(j2p_solver *ow
         };
 }
 
-// the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_scan), which is the first solver's scratch
-// (progressive: j2p_encode_progressive codes them; j2p_encode_options chooses, and hands the restart intervals on)
+// the JPEG file: the planes quantised into the coder's block (j2p_codec.hip: j2p_encode_options, which chooses the coder by the
+// record and hands the restart intervals on), which is the first solver's scratch
 static int planes_to_jpeg(const j2p_plane_ref planes[], unsigned nplane, const j2p_jpeg *spec, uint8_t *out_host, size_t capacity, size_t *size,
                           const j2p_jpeg_options *options)
 {

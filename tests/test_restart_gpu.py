@@ -82,8 +82,14 @@ def test_file_and_statistics_are_the_restatements_and_decode_back(lib, restated,
         assert np.array_equal(a, b), f"{name}: component {c}"
 
 
-def c_call(lib, case, options, room, fill=0xA5, behind=64):
-    """j2p_entropy_encode_opt into `room` bytes of a buffer of room + behind, pre-filled with `fill` -> (rc, size, buffer)"""
+# the twelve older entry points are shorthands: each coder's record, and what its entry points' names end in
+RECORD = {"baseline": (0, 0, 0, 0), "optimized": (1, 0, 0, 0), "progressive": (0, 1, 0, 0)}
+SHORTHAND = {"baseline": "", "optimized": "_ex", "progressive": "_progressive"}
+
+
+def c_call(lib, case, options, room, fill=0xA5, behind=64, shorthand=None, stats=False):
+    """j2p_entropy_encode_opt — or, with shorthand=coder, the older entry point whose record `options` is — into `room` bytes of a
+    buffer of room + behind, pre-filled with `fill` -> (rc, size, buffer), and with stats the coder's own record behind them"""
     import jpeg2png_amd as j
     n = len(case["coefficients"])
     tables = [np.ascontiguousarray(t, dtype=np.uint16) for t in case["quant"]]
@@ -94,28 +100,67 @@ def c_call(lib, case, options, room, fill=0xA5, behind=64):
     ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in arrays])
     buf = np.full(room + behind, fill, dtype=np.uint8)
     size = ctypes.c_size_t(0)
-    opt = j._CJpegOptions(*options)
-    rc_ = lib.j2p_entropy_encode_opt(0, ctypes.byref(spec), ptrs, n, buf.ctypes.data, room, ctypes.byref(size), ctypes.byref(opt), None, None, None)
-    return rc_, size.value, buf
+    record = (j._CProgressiveStats if options[1] else j._CEncodeStats)() if stats else None
+    ref = None if record is None else ctypes.byref(record)
+    head = (0, ctypes.byref(spec), ptrs, n, buf.ctypes.data, room, ctypes.byref(size))
+    if shorthand is None:
+        opt = j._CJpegOptions(*options)
+        rc_ = lib.j2p_entropy_encode_opt(*head, ctypes.byref(opt), None if options[1] else ref, ref if options[1] else None, None)
+    else:
+        assert tuple(options) == RECORD[shorthand] and not (stats and shorthand == "baseline")
+        tail = {"baseline": (), "optimized": (options[0], ref), "progressive": (ref,)}[shorthand]
+        rc_ = getattr(lib, "j2p_entropy_encode" + SHORTHAND[shorthand])(*head, *tail)
+    return (rc_, size.value, buf) + ((record,) if stats else ())
+
+
+def planes_call(lib, solver, n, spec, options=None, shorthand=None):
+    """j2p_planes_to_jpeg_opt with `options` — or the older entry point of shorthand=coder — on the solver's n planes -> the file"""
+    import jpeg2png_amd as j
+    refs = (j._CPlaneRef * 3)(*[j._CPlaneRef(solver._h, c) for c in range(n)])
+    buf, size = np.empty(1 << 16, dtype=np.uint8), ctypes.c_size_t(0)
+    head = (refs, n, ctypes.byref(spec), buf.ctypes.data, buf.size, ctypes.byref(size))
+    if shorthand is None:
+        opt = j._CJpegOptions(*options)
+        rc_ = lib.j2p_planes_to_jpeg_opt(*head, ctypes.byref(opt))
+    else:
+        rc_ = getattr(lib, "j2p_planes_to_jpeg" + SHORTHAND[shorthand])(*head, *((RECORD[shorthand][0],) if shorthand == "optimized" else ()))
+    assert rc_ == 0, lib.j2p_last_error().decode()
+    return buf[:size.value].tobytes()
+
+
+def shorthand_entry(coder, called):
+    """a stand-in for jpeg2png_amd._entry_point: the job Batch.submit has built goes, as it is, to the older C entry point of `coder`
+    in the place of the _opt one — the record, which must be that shorthand's, leaves the arguments and _ex gets its flags"""
+    import jpeg2png_amd as j
+    real = j._entry_point
+
+    def entry(source, source_args, kind, output_args):
+        name, args = real(source, source_args, kind, output_args)
+        record = args[-1]._obj
+        assert name.endswith("_jpeg_opt") and (record.flags, record.progressive, record.restart_interval, record.restart_in_rows) == RECORD[coder]
+        called.append(name[:-len("_opt")] + SHORTHAND[coder])
+        return called[-1], args[:-1] + ((record.flags,) if coder == "optimized" else ())
+    return entry
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("coder", rc.CODERS)
 def test_without_restarts_the_opt_call_is_the_old_call(lib, coder):
-    """... byte for byte, for a buffer of exactly the file's size with sentinels behind"""
+    """entropy_encode makes the _opt call: its file is j2p_entropy_encode's, _ex's and _progressive's byte for byte, called as C
+    calls them, for a buffer of exactly the file's size with sentinels behind"""
     import jpeg2png_amd as j
     case = ec.make(41, 23, 3, (2, 2), "sparse", seed=4123)
-    old = j.entropy_encode(case["coefficients"], 41, 23, case["quant"], (2, 2), optimize=coder == "optimized", progressive=coder == "progressive")
-    rc_, size, buf = c_call(lib, case, (1 if coder == "optimized" else 0, 1 if coder == "progressive" else 0, 0, 0), len(old))
-    assert rc_ == 0 and size == len(old) and buf[:size].tobytes() == old and (buf[size:] == 0xA5).all()
+    new = j.entropy_encode(case["coefficients"], 41, 23, case["quant"], (2, 2), optimize=coder == "optimized", progressive=coder == "progressive")
+    rc_, size, buf = c_call(lib, case, RECORD[coder], len(new), shorthand=coder)
+    assert rc_ == 0 and size == len(new) and buf[:size].tobytes() == new and (buf[size:] == 0xA5).all()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("coder", rc.CODERS)
 def test_without_restarts_the_planes_and_batch_opt_calls_are_the_old_calls(lib, monkeypatch, coder):
-    """j2p_planes_to_jpeg_opt, j2p_batch_submit_jpeg_opt (planes and samples) and j2p_batch_submit_file_jpeg_opt with both restart
-    fields 0: the Python layer is made to hand every file's keywords to the _opt entry points as a record, where it would take the
-    old entry points, and the files are the old entry points' byte for byte"""
+    """Solver.to_jpeg and Batch.submit (planes, samples and file=) make the _opt calls with both restart fields 0: their files are,
+    byte for byte, those of j2p_planes_to_jpeg, _ex and _progressive, of j2p_batch_submit_jpeg, _ex and _progressive and of the
+    three j2p_batch_submit_file_jpeg calls, which get the same solver and the same jobs through ctypes"""
     import jpeg2png_amd as j
     from jpeg2png_amd import synth
     keys = {"optimize": coder == "optimized", "progressive": coder == "progressive"}
@@ -124,10 +169,14 @@ def test_without_restarts_the_planes_and_batch_opt_calls_are_the_old_calls(lib, 
     args = (case.weight, case.pweight, case.iterations)
     jpeg = dict(keys, quality=85, subsampling=(2, 2))
 
-    def files():
+    def files(old):
         with j.Solver(planes, 0.3, [0.001] * 3, 3) as s:
             s.run(3)
-            out = [s.to_jpeg(45, 38, quality=80, subsampling=(2, 2), **keys)]
+            if old:
+                spec, _held = j._c_jpeg(45, 38, 3, 80, None, (2, 2))
+                out = [planes_call(lib, s, 3, spec, shorthand=coder)]
+            else:
+                out = [s.to_jpeg(45, 38, quality=80, subsampling=(2, 2), **keys)]
         with j.Batch(devices=(0,), slots_per_device=2) as b:
             tickets = [b.submit(case.coefficient_planes(), *args, width=37, height=19, jpeg=jpeg),
                        b.submit(case.bare_planes(), *args, width=37, height=19, jpeg=jpeg, samples=[np.array(a) for a in case.samples])]
@@ -135,18 +184,82 @@ def test_without_restarts_the_planes_and_batch_opt_calls_are_the_old_calls(lib, 
             out.append(b.wait(b.submit(None, *args, file=plain_file, jpeg=jpeg)))
         return out
     plain_file = j.entropy_encode(ec.make(37, 19, 3, (2, 2), "sparse", seed=3719)["coefficients"], 37, 19, j.quality_tables(85, 3), (2, 2))
-    old = files()
+    new = files(False)
     called = []
-
-    def record(optimize, progressive, restart_rows, restart_interval):
-        assert not restart_rows and not restart_interval
-        called.append(1)
-        return j._CJpegOptions(j.J2P_JPEG_OPTIMIZE if optimize and not progressive else 0, 1 if progressive else 0, 0, 0)
-    monkeypatch.setattr(j, "_restart_options", record)
-    new = files()
-    assert len(called) == 4 and len(old) == 4
+    with monkeypatch.context() as m:
+        m.setattr(j, "_entry_point", shorthand_entry(coder, called))
+        old = files(True)
+    assert called == ["j2p_batch_submit_jpeg" + SHORTHAND[coder]] * 2 + ["j2p_batch_submit_file_jpeg" + SHORTHAND[coder]]
+    assert len(new) == 4 and len(old) == 4 and all(len(f) > 100 for f in old)
     for k, (a, b) in enumerate(zip(new, old)):
         same_file(a, b, f"{coder}: file {k}")
+
+
+def fields(x):
+    """a ctypes record as plain Python values, member for member"""
+    if isinstance(x, ctypes.Structure):
+        return {name: fields(getattr(x, name)) for name, *_ in x._fields_}
+    return [fields(v) for v in x] if isinstance(x, ctypes.Array) else x
+
+
+SHORTHAND_SHAPES = {"420_41x23": (41, 23, 3, (2, 2), 4123), "grey_17x9": (17, 9, 1, (1, 1), 179)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", sorted(SHORTHAND_SHAPES))
+def test_every_shorthand_writes_its_records_file(lib, monkeypatch, shape):
+    """each of the twelve older entry points against the _opt call of its family with the shorthand's record — {0,0,0,0}, {flags,0,0,0},
+    {0,1,0,0} — on the smallest shapes with an MCU walk, dummy blocks on both edges (41x23 4:2:0: 3x2 MCUs) and a scan of one
+    component (17x9): the same file byte for byte, and for j2p_entropy_encode_ex / _progressive the same statistics"""
+    import jpeg2png_amd as j
+    from jpeg2png_amd.synth import Plane
+    width, height, n, sub, seed = SHORTHAND_SHAPES[shape]
+    case = ec.make(width, height, n, sub, "sparse", seed=seed)
+    sizes = {}
+    for coder in rc.CODERS:
+        stats = coder != "baseline"
+        new = c_call(lib, case, RECORD[coder], 1 << 16, stats=stats)
+        old = c_call(lib, case, RECORD[coder], 1 << 16, shorthand=coder, stats=stats)
+        assert new[0] == 0 and old[0] == 0 and new[1] == old[1] > 100, coder
+        assert np.array_equal(new[2], old[2]) and (new[2][new[1]:] == 0xA5).all(), coder
+        sizes[coder] = new[1]
+        if stats:
+            got, want = fields(old[3]), fields(new[3])
+            assert got == want, coder
+            assert want["nscans"] == (10 if n == 3 else 6) if coder == "progressive" else want["scan_bits"] > 0
+    assert sizes["optimized"] < sizes["baseline"] and len(set(sizes.values())) == 3      # (three different files)
+    grids = ec.grids(width, height, n, case["sub"])
+    planes = [Plane(gw * 8, gh * 8, *((1, 1) if c == 0 else case["sub"]), np.ascontiguousarray(case["coefficients"][c], np.int16).reshape(-1),
+                    np.asarray(case["quant"][c], np.uint16)) for c, (gh, gw) in enumerate(grids)]
+    bare = [Plane(p.w, p.h, p.w_samp, p.h_samp, None, p.quant_table) for p in planes]
+    rng = np.random.default_rng(seed)
+    samples = [rng.integers(0, 256, (-(-height // (p.h_samp if c else 1)), -(-width // (p.w_samp if c else 1))), dtype=np.uint8)
+               for c, p in enumerate(planes)]
+    file = c_call(lib, case, RECORD["baseline"], 1 << 16)
+    file = file[2][:file[1]].tobytes()
+    spec, _held = j._c_jpeg(width, height, n, 80, None, case["sub"])
+    args = (0.3, [0.001] * n, 2)
+    with j.Solver(planes, *args) as s:
+        s.run(2)
+        for coder in rc.CODERS:
+            same_file(planes_call(lib, s, n, spec, shorthand=coder), planes_call(lib, s, n, spec, options=RECORD[coder]), f"planes, {coder}")
+    with j.Batch(devices=(0,), slots_per_device=2) as b:
+        def submit(coder):
+            jpeg = {"quality": 80, "subsampling": case["sub"], "optimize": coder == "optimized", "progressive": coder == "progressive"}
+            return [b.submit(planes, *args, width=width, height=height, jpeg=jpeg),
+                    b.submit(bare, *args, width=width, height=height, jpeg=jpeg, samples=samples),
+                    b.submit(None, *args, file=file, jpeg=jpeg)]
+        called = []
+        for coder in rc.CODERS:
+            new = submit(coder)
+            with monkeypatch.context() as m:
+                m.setattr(j, "_entry_point", shorthand_entry(coder, called))
+                old = submit(coder)
+            for k, (a, o) in enumerate(zip(new, old)):
+                got, want = b.wait(o), b.wait(a)
+                assert len(want) > 100
+                same_file(got, want, f"batch, {coder}: job {k}")
+    assert sorted(set(called)) == sorted(f + SHORTHAND[c] for f in ("j2p_batch_submit_jpeg", "j2p_batch_submit_file_jpeg") for c in rc.CODERS)
 
 
 @pytest.mark.gpu
@@ -173,6 +286,31 @@ def test_a_batch_record_is_refused_for_what_is_wrong_with_it(lib):
         rc_ = b._lib.j2p_batch_submit_jpeg_opt(b._h, ctypes.byref(job), None, ctypes.byref(spec), buf.ctypes.data, buf.size, ctypes.byref(size), None,
                                                ctypes.byref(ticket))
         assert rc_ == -1 and "options is NULL" in b._lib.j2p_last_error().decode()
+        # (the flags of an _ex call are its record's: refused in the same words, as they were when they travelled alone)
+        rc_ = b._lib.j2p_batch_submit_jpeg_ex(b._h, ctypes.byref(job), None, ctypes.byref(spec), buf.ctypes.data, buf.size, ctypes.byref(size), 2,
+                                              ctypes.byref(ticket))
+        assert rc_ == -1 and ticket.value == -7 and b._lib.j2p_last_error().decode() == "job: jpeg: unknown flag bits"
+        # ... and the same of a file job, whose two entry points hand their record to the same check
+        data = np.frombuffer(j.entropy_encode(ec.make(37, 19, 3, (2, 2), "sparse", seed=3719)["coefficients"], 37, 19, j.quality_tables(85, 3), (2, 2)),
+                             dtype=np.uint8)
+        fjob = j._CJob()
+        fjob.nchannel = 3
+        bare, _fkeep = j._c_planes(case.bare_planes())
+        for c in range(3):
+            fjob.planes[c] = bare[c]
+            fjob.weight[c], fjob.pweight[c], fjob.iterations[c] = 0.3, 0.001, 1
+        head = (b._h, ctypes.byref(fjob), data.ctypes.data, data.size, ctypes.byref(spec), buf.ctypes.data, buf.size, ctypes.byref(size))
+        for options, message in (((0, 2, 0, 0), "job: jpeg: progressive is 0 or 1"), ((2, 0, 0, 0), "job: jpeg: unknown flag bits"),
+                                 ((0, 1, 1, 1), "job: jpeg: restart_interval and restart_in_rows are both set")):
+            opt = j._CJpegOptions(*options)
+            rc_ = b._lib.j2p_batch_submit_file_jpeg_opt(*head, ctypes.byref(opt), ctypes.byref(ticket))
+            assert rc_ == -1 and ticket.value == -7 and b._lib.j2p_last_error().decode() == message, options
+        rc_ = b._lib.j2p_batch_submit_file_jpeg_ex(*head, 2, ctypes.byref(ticket))
+        assert rc_ == -1 and ticket.value == -7 and b._lib.j2p_last_error().decode() == "job: jpeg: unknown flag bits"
+        # (a good record: the job is taken, so what was refused above was refused for the record alone)
+        opt = j._CJpegOptions(1, 0, 0, 1)
+        assert b._lib.j2p_batch_submit_file_jpeg_opt(*head, ctypes.byref(opt), ctypes.byref(ticket)) == 0, b._lib.j2p_last_error().decode()
+        assert b._lib.j2p_batch_wait(b._h, ticket.value) == 0 and size.value > 100 and bytes(buf[:2]) == b"\xff\xd8"
 
 
 @pytest.mark.gpu
