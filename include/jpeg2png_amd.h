@@ -1459,6 +1459,64 @@ int j2p_solver_upright_bytes(const j2p_solver *s, size_t *bytes);
 #define J2P_ORIENTATION_EXIF 0xffffffffu
 int j2p_batch_next_orientation(j2p_batch *b, unsigned orientation, unsigned orient_w, unsigned orient_h);
 
+/* Estimated tables: quantisation tables read off decoded 8-bit samples, for sample input that has no trustworthy header — frames of
+ * a hardware or video decoder, a JPEG saved again as PNG or YUV, and the recompressed JPEG, whose header carries the LAST
+ * compression's small steps while the blocking is the first one's.  Two steps: a histogram made on the device and a rule applied
+ * to it on the host.  This text is the definition of both.
+ *
+ * 1. The histogram (j2p_samples_histogram).  `samples` is one channel as for sample input: device memory of `device` or host memory,
+ *    any strides >= 1.  A COMPLETE block (bx, by) has bx * 8 + 8 <= w and by * 8 + 8 <= h; a block that would need replicated
+ *    samples is not looked at (its coefficients are not the file's).  A complete block with any sample equal to 0 or 255 is
+ *    EXCLUDED (the decoder's clamp has moved its coefficients) and only counted in *excluded.  For every other complete block:
+ *    v = (float)s - 128.f, the block through dct8x8s exactly as sample input does, and for natural-order frequency j
+ *    m = |(int)rintf(coefficient j)| — the step is 1, nothing is divided — and hist[j][m] += 1; *blocks counts these blocks.
+ *    m <= 1016 by the argument of sample input (a counted block's samples lie in 1..254), so hist is uint32_t [64][1024], row
+ *    j at hist_host + j * 1024.  Every row's counts add up to *blocks.  Host samples are staged as sample input stages them (one
+ *    2-D copy of the complete blocks' rows); the call queues everything on `stream` (NULL: one of its own), synchronises it
+ *    once and returns with the samples read.  Refused before a device is touched (J2P_EINVAL): a NULL argument or data, w or h
+ *    zero, a stride below 1; then managed memory and another GPU's.  A plane with no complete block gives zeros and launches nothing.
+ *
+ * 2. The rule (j2p_quant_estimate: host code, integers only).  For frequency j, with d(m, q) the distance of m to the nearest
+ *    multiple of q:
+ *      nz   = the number of values with m >= 2;
+ *      qmax = the largest q in 255..4 for which at most 5 * nz / 100 (integer division) of the values have d(m, q) > 1;
+ *      step = among q = qmax, qmax - 1, qmax - 2 with q >= 4 the one with the smallest sum over the values with m >= 2 of
+ *             min(d(m, q), 2)^2, the larger q on a tie;
+ *             where no qmax exists: none when the same search over the values with m >= 4 alone (and 5 % of their number) finds
+ *             one — a large step whose zeros' noise reaches 2 and 3; otherwise s = 3 when at most nz / 4 (integer division) of
+ *             the values with m >= 2 are no exact multiple of 3; otherwise s = 2 by the same test; otherwise s = 1; and s is
+ *             named only when 2 * sum over m >= 2 of min(hist[j][m], hist[j][m + s]) >= nz — the counts repeat with period s,
+ *             which clusters around the multiples of a larger step do not;
+ *      determined[j] = a step was named and nz >= 12.
+ *    (A decoded sample is off by at most 1/2, which moves a coefficient by less than 1 almost always: the values of a frequency
+ *    quantised with step q lie within 1 of q's multiples.  Multiples of q are multiples of its divisors too, hence the LARGEST q.
+ *    Every value lies within 1 of a multiple of 3, so the small steps are told apart by EXACT multiples: about one value in
+ *    twelve is moved off its multiple, while a step that is not the file's leaves a third of them or more off.)
+ *    quality = the Qf in 1..100 whose IJG table — jpeg_set_quality(Qf, TRUE) on Annex K's luminance table, or with `chroma` the
+ *    chrominance one — minimises the sum over determined entries of |ijg(Qf)[j] - step[j]|; the higher Qf on a tie; 100 when
+ *    nothing is determined.  table[j] = step[j] where determined, otherwise max(ijg(quality)[j], 2 * (mmax_j - 1)) clamped to
+ *    1..255, mmax_j the largest m of row j with a count: the box of a coefficient taken as 0 still holds what was seen.  The
+ *    fill errs towards small steps, which can only make the solver do less.
+ *
+ * Not covered: RGB input; a block grid that does not start at sample (0, 0) (a cropped image); chroma that was upsampled after
+ * decoding (estimate from planes at the file's own sampling). */
+typedef struct j2p_quant_estimate_result {
+        uint16_t table[64];                /* natural order, 1..255 */
+        uint8_t determined[64];            /* 1: read off the histogram; 0: filled from the fitted IJG table */
+        int quality;                       /* the fitted IJG quality, 1..100 */
+} j2p_quant_estimate_result;
+int j2p_samples_histogram(int device, void *stream, const j2p_samples *samples, uint32_t *hist_host, unsigned long long *blocks,
+                          unsigned long long *excluded);
+int j2p_quant_estimate(const uint32_t hist[64][1024], int chroma, j2p_quant_estimate_result *out);
+/* j2p_batch_submit_samples with estimated tables: the worker that takes the job runs j2p_samples_histogram and j2p_quant_estimate on
+ * every channel's samples — channel 0 against the luminance base table, the others against the chrominance one — and makes the
+ * job's solvers with those tables, as j2p_solver_create_from_samples does.  The flag travels next to the job (j2p_job keeps its
+ * layout).  job->planes[c].quant_table: NULL in every plane, or set in every plane (then ignored); some set and some not is
+ * J2P_EINVAL, as are `tile` and samples == NULL, with nothing queued.  estimates: NULL, or nchannel records the worker fills
+ * before the job finishes; they stay the caller's and must live until j2p_batch_wait. */
+int j2p_batch_submit_samples_estimated(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[],
+                                       j2p_quant_estimate_result estimates[], int *ticket);
+
 #ifdef __cplusplus
 }
 #endif

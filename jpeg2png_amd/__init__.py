@@ -84,6 +84,11 @@ class _CSamples(ctypes.Structure):
                 ("stride_y", ctypes.c_ssize_t), ("stride_x", ctypes.c_ssize_t)]
 
 
+class _CQuantEstimate(ctypes.Structure):
+    """j2p_quant_estimate_result: one channel's estimated table"""
+    _fields_ = [("table", ctypes.c_uint16 * 64), ("determined", ctypes.c_uint8 * 64), ("quality", ctypes.c_int)]
+
+
 class _CJpeg(ctypes.Structure):
     """j2p_jpeg: the image, its chroma subsampling and the quantisation tables of a JPEG file made on the device"""
     _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("sub_w", ctypes.c_uint), ("sub_h", ctypes.c_uint),
@@ -271,6 +276,7 @@ C_ABI_SYMBOLS = [
     "j2p_pool_thread_takes",
     "j2p_jpeg_parse_scans", "j2p_entropy_decode_scans", "j2p_solver_create_from_jpeg_scans", "j2p_batch_next_file_scans",
     "j2p_debug_restart_plan", "j2p_planes_to_jpeg_opt", "j2p_entropy_encode_opt", "j2p_batch_submit_jpeg_opt", "j2p_batch_submit_file_jpeg_opt",
+    "j2p_samples_histogram", "j2p_quant_estimate", "j2p_batch_submit_samples_estimated",
 ]
 J2P_ORIENTATION_EXIF = 0xffffffff           # j2p_batch_next_orientation: the tag of the job's file
 # the forms of the ||g|| reduction j2p_norm_selftest launches (J2P_NORM_FORM_*)
@@ -471,6 +477,13 @@ def _bind(path):
         lib.j2p_solver_clipped_samples.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong)]
         lib.j2p_batch_submit_samples.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.c_uint,
                                                  ctypes.POINTER(_COutput), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "j2p_samples_histogram"):
+        # (as above: an earlier commit's build estimates no tables)
+        lib.j2p_samples_histogram.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(_CSamples), ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+        lib.j2p_quant_estimate.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_CQuantEstimate)]
+        lib.j2p_batch_submit_samples_estimated.argtypes = [ctypes.c_void_p, ctypes.POINTER(_CJob), ctypes.POINTER(_CSamples), ctypes.c_uint,
+                                                           ctypes.POINTER(_COutput), ctypes.POINTER(_CQuantEstimate), ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "j2p_entropy_encode_opt"):
         # (as above: an earlier commit's build does not write files, or not every kind).  The record describes a JPEG write: the
         # three _opt calls and the one behind a batch's file are what this module calls, the twelve older ones are their shorthands
@@ -1158,7 +1171,7 @@ class Solver:
         self.row_begin, self.row_end = r0.value, r1.value
 
     @classmethod
-    def from_samples(cls, samples, planes, weight, pweight, iterations, device=0, stream=None):
+    def from_samples(cls, samples, planes, weight, pweight, iterations, device=0, stream=None, quant=None):
         """A solver made from decoded 8-bit planes instead of coefficients (j2p_solver_create_from_samples): what a hardware JPEG
         decoder, PyAV (`yuvj420p`) or libjpeg's raw-data mode hands over.  planes: Plane-likes with w, h, w_samp, h_samp and
         quant_table, data=None (jpeg_header(...)["planes"] are such).  samples: one entry per plane — a 2-D torch.uint8 tensor
@@ -1167,22 +1180,24 @@ class Solver:
         coefficients are recomputed on the device (the header states the definition and when the file's are recovered
         exactly); from there on the solver is the one Solver(planes with those coefficients) is.
         For tensors on the GPU the solver's stream is made to wait for torch's current stream before the kernel reads them;
-        when the call returns they have been read."""
+        when the call returns they have been read.
+        quant="estimate": the tables are read off the samples — one histogram launch per channel (samples_histogram) and the
+        estimator (estimate_quant_table; channel 0 against the luminance base table, the others against the chrominance one) —
+        and the call proceeds with them as it does with given ones.  The planes' quant_table may then be None (in every plane;
+        tables given in every plane are ignored).  Solver.estimated_tables keeps the (table, determined, quality) triples;
+        it is None for every other solver."""
         self = cls.__new__(cls)
         lib = load_library()
         self._lib = lib
         self._h = None
         self.nch = len(planes)
+        self.estimated_tables = None
         if len(samples) != self.nch:
             raise J2PError(f"from_samples: {len(samples)} sample arrays for {self.nch} planes")
-        cpl = (_CPlane * self.nch)()
-        keep = []
+        estimate = _want_estimate(quant, planes, "from_samples")
         for i, p in enumerate(planes):
             if getattr(p, "data", None) is not None or getattr(p, "fdata", None) is not None:
                 raise J2PError(f"from_samples: plane {i} carries data / fdata; a solver made from samples takes neither")
-            q = np.ascontiguousarray(p.quant_table, dtype=np.uint16)
-            keep.append(q)
-            cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None, None, q.ctypes.data)
         csm, held, on_gpu = _c_samples(samples, device)
         if on_gpu:
             # a stream of torch's, so that it can be made to wait for torch's current one (the library synchronises it before
@@ -1193,6 +1208,17 @@ class Solver:
             ours.wait_stream(torch.cuda.current_stream(dev))
             self._torch_stream = ours
             stream = ours.cuda_stream
+        tables = [p.quant_table for p in planes]
+        if estimate:
+            # (on the solver's stream, which waits for the samples' producer; each call returns with its channel read)
+            self.estimated_tables = [estimate_quant_table(samples_histogram(a, device, stream)[0], chroma=c > 0) for c, a in enumerate(samples)]
+            tables = [t for t, _, _ in self.estimated_tables]
+        cpl = (_CPlane * self.nch)()
+        keep = []
+        for i, p in enumerate(planes):
+            q = np.ascontiguousarray(tables[i], dtype=np.uint16)
+            keep.append(q)
+            cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None, None, q.ctypes.data)
         pw = (ctypes.c_float * self.nch)(*[float(x) for x in pweight])
         h = ctypes.c_void_p()
         _check(lib.j2p_solver_create_from_samples(ctypes.byref(h), int(device), stream, self.nch, cpl, csm, float(weight), pw, int(iterations)))
@@ -1673,13 +1699,69 @@ def _c_planes(planes):
     keep = []
     cpl = (_CPlane * len(planes))()
     for i, p in enumerate(planes):
-        # (data None: the planes of a job made from samples — Batch.submit(samples=...))
+        # (data None: the planes of a job made from samples — Batch.submit(samples=...); quant_table None: with quant="estimate")
         d = None if p.data is None else np.ascontiguousarray(p.data, dtype=np.int16)
-        q = np.ascontiguousarray(p.quant_table, dtype=np.uint16)
+        q = None if p.quant_table is None else np.ascontiguousarray(p.quant_table, dtype=np.uint16)
         f = None if p.fdata is None else np.ascontiguousarray(p.fdata, dtype=np.float32)
         keep += [d, q, f]
-        cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None if d is None else d.ctypes.data, None if f is None else f.ctypes.data, q.ctypes.data)
+        cpl[i] = _CPlane(p.w, p.h, p.w_samp, p.h_samp, None if d is None else d.ctypes.data, None if f is None else f.ctypes.data,
+                         None if q is None else q.ctypes.data)
     return cpl, keep
+
+
+def samples_histogram(samples, device=0, stream=None):
+    """The histogram the table estimator reads (j2p_samples_histogram; the header's "Estimated tables" is the definition): samples
+    is ONE channel — a 2-D torch.uint8 tensor (on GPU `device`: read in place; on the CPU: served like an array) or a 2-D numpy uint8
+    array, any strides >= 1.  Every complete 8x8 block without a sample of 0 or 255 goes through the DCT on the device and the
+    magnitudes of its 64 rounded coefficients are counted -> (hist uint32 [64, 1024], blocks counted, blocks excluded).
+    stream: the stream to queue on (the caller has ordered the samples' producer before it); None: for a tensor on the GPU a
+    stream that is made to wait for torch's current one, as in Solver.from_samples, otherwise one of the call's own.  The call
+    returns with the samples read."""
+    lib = load_library()
+    csm, held, on_gpu = _c_samples([samples], device)
+    if on_gpu and stream is None:
+        torch = _torch()
+        dev = torch.device("cuda", int(device))
+        ours = torch.cuda.Stream(device=dev)
+        ours.wait_stream(torch.cuda.current_stream(dev))
+        held.append(ours)
+        stream = ours.cuda_stream
+    hist = np.empty((64, 1024), np.uint32)
+    blocks, excluded = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+    _check(lib.j2p_samples_histogram(int(device), stream, csm, hist.ctypes.data, ctypes.byref(blocks), ctypes.byref(excluded)))
+    del held
+    return hist, blocks.value, excluded.value
+
+
+def _estimate_triple(r):
+    return (np.array(r.table, dtype=np.uint16), np.array(r.determined, dtype=np.uint8).astype(bool), int(r.quality))
+
+
+def estimate_quant_table(hist, chroma=False):
+    """A quantisation table from a channel's histogram (j2p_quant_estimate: host code; the header's "Estimated tables" is the rule)
+    -> (table uint16 [64] in natural order, determined bool [64], the fitted IJG quality).  chroma: fit and fill against the
+    chrominance base table instead of the luminance one.  Entries that are not determined are filled from the fitted table."""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (64, 1024):
+        raise J2PError(f"estimate_quant_table: a [64, 1024] histogram is needed, not {h.shape}")
+    r = _CQuantEstimate()
+    _check(lib.j2p_quant_estimate(h.ctypes.data, 1 if chroma else 0, ctypes.byref(r)))
+    return _estimate_triple(r)
+
+
+def _want_estimate(quant, planes, what):
+    """quant=None or "estimate"; with "estimate" the planes carry no table at all or one each (which is then ignored)"""
+    if quant is None:
+        return False
+    if quant != "estimate":
+        raise J2PError(f"{what}: quant={quant!r} (None or \"estimate\")")
+    have = [getattr(p, "quant_table", None) is not None for p in planes]
+    if any(have) and not all(have):
+        err = J2PError(f"{what}: quant=\"estimate\" with a quant_table in some planes and none in others")
+        err.code = -1       # J2P_EINVAL, as the library's own refusals carry it
+        raise err
+    return True
 
 
 class TiledSolver:
@@ -2047,12 +2129,18 @@ class Batch:
         _check(lib.j2p_batch_create(ctypes.byref(h), len(devices), devs, int(slots_per_device)))
         self._h = h
         self._pending = {}
+        self._estimates = {}
 
     def submit(self, planes, weight, pweight, iterations, separate=False, width=None, height=None, bits=0, tile=False,
                tile_devices=None, tile_min_band_pixels=None, out=None, on_progress=None, quant_tables=None, subsampling=None,
                tensor=None, layout="chw", scale=None, bias=None, out_width=None, out_height=None, box=None, filter=None, outputs=None,
-               samples=None, jpeg=None, file=None, png=None, orientation=None, progressive=False):
-        """progressive=True (with file=): the file may be a progressive JPEG, every scan of which the worker decodes on its GPU
+               samples=None, jpeg=None, file=None, png=None, orientation=None, progressive=False, quant=None):
+        """quant="estimate" (with samples=; not with tile, jpeg= or png=): the worker reads the job's quantisation tables off the
+        samples before it makes the solvers — a histogram launch per channel and the estimator, as
+        Solver.from_samples(quant="estimate") does (j2p_batch_submit_samples_estimated).  The planes' quant_table may then be None
+        (in every plane; tables given in every plane are ignored).  After wait(ticket), estimated_tables(ticket) returns the
+        (table, determined, quality) triples;
+        progressive=True (with file=): the file may be a progressive JPEG, every scan of which the worker decodes on its GPU
         (j2p_batch_next_file_scans, Solver.from_jpeg(progressive=True)); without it a progressive file is refused as before;
         orientation=1..8 or "exif" (the tag of file=, read at submit; file jobs only; not with tile): every solver of the job is
         oriented (Solver.set_orientation) and every output kind but the float planes delivers the UPRIGHT image, whose size width and
@@ -2128,6 +2216,13 @@ class Batch:
                 width, height = (uw if width is None else width), (uh if height is None else height)
             elif file is None and width is not None and height is not None:
                 oriented = (code,) + upright_size(found, width, height)     # (turned back: the same swap)
+        estimates = None
+        if _want_estimate(quant, planes or (), "job"):
+            if samples is None or tile or jpeg is not None or png is not None:
+                err = J2PError("job: quant=\"estimate\" needs samples= and excludes tile, jpeg= and png=")
+                err.code = -1       # J2P_EINVAL, as the library's own refusals carry it
+                raise err
+            estimates = (_CQuantEstimate * len(planes))()
         source, planes, width, height, source_args, keep = _job_input(planes, width, height, samples, file, tile, resized, progressive)
         kind, result, filled, output_args = _job_output(job, want, planes, width, height)
         keep += filled + _job_record(job, planes, weight, pweight, iterations, want, tile_devices, tile_min_band_pixels)
@@ -2136,6 +2231,8 @@ class Batch:
             job.on_progress = cb
             keep.append(cb)                         # the trampoline lives as long as the job
         name, args = _entry_point(source, source_args, kind, output_args)
+        if estimates is not None:
+            name, args = name + "_estimated", args + (estimates,)
         t = ctypes.c_int()
         if oriented[0]:
             _check(self._lib.j2p_batch_next_orientation(self._h, *oriented))        # (this thread's next submit: the one below)
@@ -2143,7 +2240,15 @@ class Batch:
             _check(self._lib.j2p_batch_next_file_scans(self._h, 1))
         _check(getattr(self._lib, name)(self._h, ctypes.byref(job), *args, ctypes.byref(t)))
         self._pending[t.value] = (result, keep)
+        if estimates is not None:
+            self._estimates[t.value] = estimates
         return t.value
+
+    def estimated_tables(self, ticket):
+        """the (table, determined, quality) triples, one per plane, of a job submitted with quant="estimate" — once, after wait(ticket)"""
+        if ticket in self._pending:
+            raise J2PError(f"estimated_tables: job {ticket} has not been waited for")
+        return [_estimate_triple(r) for r in self._estimates.pop(ticket)]
 
     def wait(self, ticket):
         out, _keep = self._pending.pop(ticket)

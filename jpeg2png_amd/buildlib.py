@@ -43,21 +43,22 @@ UNIT_HEADERS = {
     "j2p_output.hip": ("j2p_output_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
     "j2p_codec.hip": ("j2p_codec_kernels.hip.h", "j2p_progressive_kernels.hip.h", "j2p_decode_kernels.hip.h", "j2p_scan_decode_kernels.hip.h", "j2p_png_kernels.hip.h",
                       "j2p_hip_host.h", "j2p_internal.h", "j2p_coder_block.h", "j2p_huffman.h", "j2p_deflate.h", "j2p_restart.h"),
+    "j2p_estimate.hip": ("j2p_estimate_kernels.hip.h", "j2p_dct.hip.h", "j2p_hip_host.h", "j2p_internal.h"),
     "j2p_pool.hip": ("j2p_hip_host.h", "j2p_internal.h"),
     "j2p_tiled.hip": ("j2p_internal.h", "j2p_geometry.h"),
     "j2p_batch.hip": ("j2p_internal.h", "j2p_geometry.h"),
-    "compute_host.c": ("j2p_internal.h", "j2p_geometry.h"),
+    "compute_host.c": ("j2p_internal.h", "j2p_geometry.h", "j2p_quant_estimate.h"),
     "j2p_jpeg_parse.c": ("j2p_internal.h",),
 }
 # the units the experiments build takes from the release build: they have no knobs
-NO_KNOBS = ("j2p_output.hip", "j2p_codec.hip", "j2p_pool.hip")
+NO_KNOBS = ("j2p_output.hip", "j2p_codec.hip", "j2p_estimate.hip", "j2p_pool.hip")
 HIP_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".hip"))
 # the pure C units (host code, gcc): the same objects in every build of the library
 C_UNITS = tuple(u for u in UNIT_HEADERS if u.endswith(".c"))
 C_OBJECTS = tuple(os.path.join(CSRC, u.replace(".c", ".o")) for u in C_UNITS)
 # the units that hold device code (the others are host code).  Only the solver's knows -DJ2P_DEBUG, -DJ2P_TRACE and
 # -DJ2P_EXP_*: the checked build and the A/B variants compile it alone and take every other object from the release build
-DEVICE_UNITS = ("j2p_solver.hip", "j2p_output.hip", "j2p_codec.hip")
+DEVICE_UNITS = ("j2p_solver.hip", "j2p_output.hip", "j2p_codec.hip", "j2p_estimate.hip")
 PUBLIC_HEADERS = ("jpeg2png_amd.h", "jpeg2png_amd_compute.h")
 
 

@@ -18,6 +18,7 @@
 #include "jpeg2png_amd_compute.h"
 #include "j2p_internal.h"              /* the chunk rule (j2p_next_chunk), j2p_set_last_error, j2p_tiled_exchange_forced */
 #include "j2p_geometry.h"              /* the canvas, the band alignment and the least band */
+#include "j2p_quant_estimate.h"        /* the table estimator's rule */
 
 /* stands in for `omp critical(progressbar)` (compute.c:450): compute() may be entered from
  * several host threads at once (jpeg2png.c:147,330) and they share one progress bar */
@@ -308,4 +309,14 @@ void compute(unsigned nchannel, struct coef coefs[], struct logger *log, struct 
                 fprintf(stderr, "%s\n", (msg && *msg) ? msg : "GPU solver failed");
                 exit(EXIT_FAILURE);
         }
+}
+
+/* the table estimator's rule (j2p_quant_estimate.h): host code, no device */
+int j2p_quant_estimate(const uint32_t hist[64][1024], int chroma, j2p_quant_estimate_result *out)
+{
+        if(j2p_quant_estimate_rule(hist, chroma, out) != 0) {
+                j2p_set_last_error("j2p_quant_estimate: NULL argument");
+                return J2P_EINVAL;
+        }
+        return J2P_OK;
 }

@@ -50,6 +50,9 @@ struct Request {
         const j2p_png *png = nullptr;       // the PNG file the job delivers, with where it goes:
         uint8_t *png_out = nullptr;
         size_t png_capacity = 0, *png_size = nullptr;
+        bool estimate = false;              // j2p_batch_submit_samples_estimated: the tables are read off the samples ...
+        j2p_quant_estimate_result *estimates = nullptr;     // ... and reported here (or nowhere)
+        Request &estimated(j2p_quant_estimate_result *e) { estimate = true, estimates = e; return *this; }
         Request &resized(const j2p_resize *r) { resize = r; return *this; }
         Request &resampled(const j2p_resample *r) { resample = r; return *this; }
         // (no outputs, or an array that is not there, is the job's own output)
@@ -107,6 +110,8 @@ struct Job {
         In in = In::planes;
         Out out = Out::own;
         std::vector<j2p_samples> samples;   // In::samples: [channel]
+        bool estimate = false;              // In::samples: the worker estimates the tables (planes[].quant_table is not read) ...
+        j2p_quant_estimate_result *estimates = nullptr;     // ... and reports them here, [channel], when the caller wants them
         j2p_jpeg_file file;                 // In::file: opened at submit; the worker decodes the solvers' coefficients from the caller's
                                             // bytes, which stay valid until j2p_batch_wait
         j2p_resize resize = {0, 0, 0, 0, 0, 0};          // Out::resized
@@ -463,6 +468,21 @@ int create_engines(const Job &j, int device, Engines &eng)
 {
         const j2p_job &d = j.desc;
         const j2p_band whole = {0, 0};
+        // estimated tables: the two steps of Solver.from_samples(quant="estimate"), a histogram launch per channel and the rule
+        j2p_plane sampled[J2P_MAX_CHANNELS];
+        uint16_t tables[J2P_MAX_CHANNELS][64];
+        for(unsigned c = 0; j.in == In::samples && c < d.nchannel; c++) {
+                sampled[c] = d.planes[c];
+                if(!j.estimate) { continue; }
+                std::vector<uint32_t> hist(64 * 1024);
+                unsigned long long blocks = 0, excluded = 0;
+                j2p_quant_estimate_result r;
+                JOB_TRY(j2p_samples_histogram(device, nullptr, &j.samples[c], hist.data(), &blocks, &excluded));
+                JOB_TRY(j2p_quant_estimate(reinterpret_cast<const uint32_t (*)[1024]>(hist.data()), c != 0, &r));
+                memcpy(tables[c], r.table, sizeof(tables[c]));
+                sampled[c].quant_table = tables[c];
+                if(j.estimates) { j.estimates[c] = r; }
+        }
         std::optional<j2p_decoded_grids> grids;
         if(j.in == In::file) {
                 grids.emplace(device, j.file, 0u, nullptr);
@@ -474,7 +494,7 @@ int create_engines(const Job &j, int device, Engines &eng)
                 switch(j.in) {
                 case In::planes: JOB_TRY(j2p_solver_create(s, device, nullptr, nch, &d.planes[k], d.weight[k], &d.pweight[k], d.iterations[k], whole, 0)); break;
                 case In::samples:
-                        JOB_TRY(j2p_solver_create_from_samples(s, device, nullptr, nch, &d.planes[k], &j.samples[k], d.weight[k], &d.pweight[k], d.iterations[k]));
+                        JOB_TRY(j2p_solver_create_from_samples(s, device, nullptr, nch, &sampled[k], &j.samples[k], d.weight[k], &d.pweight[k], d.iterations[k]));
                         break;
                 case In::file:
                         JOB_TRY(j2p_solver_create_from_decoded(s, device, nch, &d.planes[k], &grids->coef[k], d.weight[k], &d.pweight[k], d.iterations[k]));
@@ -720,10 +740,19 @@ int classify(const j2p_batch &b, const j2p_job &given, const Request &q, Job &j)
                 j.png.spec = *q.png;
                 j.png.out = q.png_out, j.png.capacity = q.png_capacity, j.png.size = q.png_size;
         }
+        if(q.estimate && !q.samples) { return j2p_fail(J2P_EINVAL, "job: estimated tables need samples"); }
         if(q.samples) {
                 j.in = In::samples;
                 JOB_TRY(validate_samples(d, q.samples, &samples_device));
                 j.samples.assign(q.samples, q.samples + d.nchannel);
+        }
+        if(q.estimate) {
+                // no table at all, or one in every plane (ignored): a job with some cannot mean either
+                unsigned have = 0;
+                for(unsigned c = 0; c < d.nchannel; c++) { have += d.planes[c].quant_table ? 1u : 0u; }
+                if(have && have != d.nchannel) { return j2p_fail(J2P_EINVAL, "job: estimated tables, but %u of %u planes carry a quant_table", have, d.nchannel); }
+                j.estimate = true;
+                j.estimates = q.estimates;
         }
         if(q.nout) {
                 j.out = Out::outputs;
@@ -860,6 +889,12 @@ int j2p_batch_submit_outputs(j2p_batch *b, const j2p_job *job, unsigned n, const
 int j2p_batch_submit_samples(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[], int *ticket)
 {
         return submit(b, job, Request().from_samples(samples).outputs(n, outs), ticket);
+}
+
+int j2p_batch_submit_samples_estimated(j2p_batch *b, const j2p_job *job, const j2p_samples samples[], unsigned n, const j2p_output outs[],
+                                       j2p_quant_estimate_result estimates[], int *ticket)
+{
+        return submit(b, job, Request().from_samples(samples).outputs(n, outs).estimated(estimates), ticket);
 }
 
 // A JPEG job from samples (or, with none, from the job's coefficients), and one from a file: the record says which file is

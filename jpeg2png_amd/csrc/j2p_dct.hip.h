@@ -1,8 +1,11 @@
-// jpeg2png_amd — the 8-point DCT passes and the 8x8 lane transpose: the device code that the solver's kernels
-// (j2p_kernels.hip.h) and the output stage's (j2p_output_kernels.hip.h) share.  Nothing else is shared between the two device
-// translation units.  Bit-exactness rules: see j2p_kernels.hip.h.
+// jpeg2png_amd — the 8-point DCT passes, the 8x8 lane transpose and the load of a block row's 8-bit samples: the device code
+// that the solver's kernels (j2p_kernels.hip.h), the output stage's (j2p_output_kernels.hip.h) and the table estimator's
+// (j2p_estimate_kernels.hip.h) share.  Nothing else is shared between the device translation units.  Bit-exactness rules:
+// see j2p_kernels.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
 
 namespace j2p {
 
@@ -106,6 +109,27 @@ __device__ __forceinline__ void transpose8(float (&v)[8], float *scratch, int la
 #pragma unroll
         for(int i = 0; i < 8; i++) { v[i] = src[i * kTpLine]; }
         __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------
+// One lane's 8 samples of a block row, stride_x bytes apart from src — the load of sample input (k_samples_to_coefficients)
+// and of the histogram of j2p_estimate_kernels.hip.h.  `wide` (stride_x == 1 and src a multiple of 8: the host says so): one
+// 8-byte load, 8 lanes 64 contiguous bytes of a row; otherwise 8 byte loads.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void load_samples8(const uint8_t *src, ptrdiff_t stride_x, int wide, unsigned (&s)[8])
+{
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        if(wide) {
+                const v2u r = *reinterpret_cast<const v2u *>(src);
+#pragma unroll
+                for(int u = 0; u < 4; u++) {
+                        s[u] = (r.x >> (8 * u)) & 0xffu;
+                        s[4 + u] = (r.y >> (8 * u)) & 0xffu;
+                }
+        } else {
+#pragma unroll
+                for(int u = 0; u < 8; u++) { s[u] = src[(ptrdiff_t)u * stride_x]; }
+        }
 }
 
 }  // namespace j2p

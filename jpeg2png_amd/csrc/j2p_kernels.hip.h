@@ -2662,7 +2662,6 @@ __global__ __launch_bounds__(256) void k_samples_to_coefficients(const uint8_t *
                                                                  ptrdiff_t stride_x, int wide, unsigned blocks_w, unsigned block_rows,
                                                                  const float *q, int16_t *out, unsigned long long *clipped)
 {
-        typedef unsigned v2u __attribute__((ext_vector_type(2)));
         __shared__ __attribute__((aligned(16))) float tp[4 * kTpWave];
         __shared__ float qs[64];
         if(threadIdx.x < 64) { qs[threadIdx.x] = q[threadIdx.x]; }
@@ -2681,17 +2680,7 @@ __global__ __launch_bounds__(256) void k_samples_to_coefficients(const uint8_t *
         unsigned nclip = 0;
         if(ok && x0 + 8 <= w && y < h) {
                 const uint8_t *src = data + (ptrdiff_t)y * stride_y + (ptrdiff_t)x0 * stride_x;
-                if(wide) {
-                        const v2u r = *reinterpret_cast<const v2u *>(src);
-#pragma unroll
-                        for(int u = 0; u < 4; u++) {
-                                s[u] = (r.x >> (8 * u)) & 0xffu;
-                                s[4 + u] = (r.y >> (8 * u)) & 0xffu;
-                        }
-                } else {
-#pragma unroll
-                        for(int u = 0; u < 8; u++) { s[u] = src[(ptrdiff_t)u * stride_x]; }
-                }
+                load_samples8(src, stride_x, wide, s);
 #pragma unroll
                 for(int u = 0; u < 8; u++) { nclip += (s[u] == 0u || s[u] == 255u) ? 1u : 0u; }
         } else if(ok) {
